@@ -90,6 +90,20 @@ def pmc_valu_per_particle_step(args, N, Ng):
     return table.get(key), f"profiles/{PMC_SUMMARY}: SQ_INSTS_VALU per launch / particle-steps per launch, {key}"
 
 
+# --dump-outputs: values kept per array, at most 2 x 16 MB for x and v plus 2 MB for each of the seven others (float64): < 64 MB
+DUMP_PARTICLE_VALUES = 1 << 21
+DUMP_OTHER_VALUES = 1 << 18
+
+
+def fixed_sample(torch, t, cap):
+    """Device tensor t -> host array: all of it, or `cap` of its values at flat indices drawn by a generator seeded with its
+    size alone (the same positions in every run with the same arguments), in index order."""
+    if t.numel() <= cap:
+        return t.cpu().numpy()
+    flat = np.sort(np.random.default_rng(t.numel()).choice(t.numel(), cap, replace=False))
+    return t[tuple(torch.as_tensor(i, device=t.device) for i in np.unravel_index(flat, tuple(t.shape)))].cpu().numpy()
+
+
 def _cpu_env(args):
     """One environment of the CPU baseline: (steps done, seconds) for the faithful NumPy oracle."""
     N, Ng, L, dt, budget_s, seed = args
@@ -201,7 +215,13 @@ def main():
     ap.add_argument("--probe-passes", type=int, default=100, help="passes of the copy-ceiling probe in front of the warm-up")
     ap.add_argument("--cpu-procs", type=int, default=1, help="processes (one env each) for the CPU baseline")
     ap.add_argument("--profile-steps", type=int, default=-1, help="steps of the event-bracketed pass (-1 = --steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed steps left, as rank 0's caller would read it, to DIR/<name>.npy: particles x, v "
+                         "(a fixed sample of at most 2^21 values each), fields n, E_mesh, phi, energies KE, PE, PE_reward and the "
+                         "gathered returns; the inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     presets = {1: dict(envs=1, particles=10_000, mesh=128),
                2: dict(),
                3: dict(envs=128, mesh=512, dtype="float32", positions="fixed32", init="two-stream", actions=3),
@@ -383,6 +403,15 @@ def main():
         per_rank_ms = [float(e[0]) for e in every]
         gather_ms = [float(e[1]) for e in every]
 
+    dump = None
+    if rank == 0 and args.dump_outputs:       # taken here: with --order cold more steps follow
+        env.sync()
+        views = env.torch_views()
+        dump = {k: fixed_sample(torch, views[k], DUMP_PARTICLE_VALUES) for k in ("x", "v")}
+        dump.update({k: fixed_sample(torch, views[k], DUMP_OTHER_VALUES) for k in ("n", "E_mesh", "phi", "KE", "PE", "PE_reward")})
+        dump["returns"] = fixed_sample(torch, torch.clamp(1.0 - returns, min=0.0).to(torch.float64), DUMP_OTHER_VALUES)
+        del views
+
     if args.order == "cold":
         # rounds 1-3: the longer region and the event pass behind the headline one
         if rank == 0 and args.steady_steps > 0:
@@ -472,6 +501,10 @@ def main():
         "placement": env._h.placement_stats(),
         "roofline": roof, "kernels": kernels,
     }
+    if dump is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for k, a in dump.items():
+            np.save(os.path.join(args.dump_outputs, k + ".npy"), a)
     if rank == 0:
         out["cpu_baseline"] = cpu_leg          # measured before the GPU was touched (rank 0, N = 1 only)
         print(json.dumps(out), flush=True)

@@ -741,7 +741,10 @@ void placement_leg(pic_handle* h, size_t pbytes) {
   };
   void* best = h->v;                                                  // the block kept by earlier legs, or null
   double best_n = ps.best_n, worst_n = ps.worst_n;                    // normalised; 0 = none yet
-  float best_raw = 0.f, worst_raw = 0.f;
+  // raw ms of the kept pair's reading and of the slowest reading of the leg (the rates pic_placement reports).  Blocks are chosen on
+  // normalised readings, whose raw times were taken against different references: the pair with the largest ratio can stream faster
+  // than the one kept, so the slowest rate reported is that of the slowest raw reading, never above the kept pair's.
+  float best_raw = 0.f, slowest_raw = 0.f;
   int timed = 0, found_at = 0;
   size_t last = 0, best_at = 0;                                       // blocks.size() at the last / at the best reading
   int outcome = PIC_PLACED_MEMORY;                                    // (the feeder ran into the block or memory limit, or hipMalloc failed)
@@ -772,7 +775,8 @@ void placement_leg(pic_handle* h, size_t pbytes) {
       ok = reading(first, &n, &raw);
       if (!ok) break;
       best = first; best_n = n; best_raw = raw; best_at = last;
-      if (worst_n < n) { worst_n = n; worst_raw = raw; }
+      if (worst_n < n) worst_n = n;
+      slowest_raw = std::max(slowest_raw, raw);
       ++timed;
       if (b == first) continue;
     }
@@ -780,7 +784,8 @@ void placement_leg(pic_handle* h, size_t pbytes) {
     if (!ok) break;
     ++timed;
     if (best_n == 0.0 || n < best_n) { best = b; best_n = n; best_raw = raw; best_at = last; }
-    if (n > worst_n) { worst_n = n; worst_raw = raw; }
+    if (n > worst_n) worst_n = n;
+    slowest_raw = std::max(slowest_raw, raw);
     if (worst_n >= kGain * best_n) {                                  // a fast pair, known to be one ...
       // ... but there are more than two kinds (5.0-5.3 / 5.6-5.75 / 5.85-6.0 TB/s read on used devices, 0.983 / 0.970 / 0.963 ms per
       // step at config 2), and the first pair 10 % above the slowest is often of the middle one: a reading costs 0.7 ms, so
@@ -823,8 +828,8 @@ void placement_leg(pic_handle* h, size_t pbytes) {
   st.malloc_seconds += feed.malloc_seconds;
   st.outcome = outcome;
   if (best_raw > 0.f) st.kept_gbytes_per_s = gb_per_ms / best_raw;
-  if (worst_raw > 0.f && (st.slowest_gbytes_per_s == 0.0 || gb_per_ms / worst_raw < st.slowest_gbytes_per_s))
-    st.slowest_gbytes_per_s = gb_per_ms / worst_raw;
+  if (slowest_raw > 0.f && (st.slowest_gbytes_per_s == 0.0 || gb_per_ms / slowest_raw < st.slowest_gbytes_per_s))
+    st.slowest_gbytes_per_s = gb_per_ms / slowest_raw;
   st.seconds += seconds();
   st.legs = ps.legs;
 }
