@@ -266,9 +266,9 @@ __device__ __noinline__ T wrap_periodic_far(T q, T L) {   // |q| beyond one box 
 template <typename T>
 __device__ __forceinline__ T wrap_periodic(T q, T L, unsigned& bad) {
   // the three near ranges as selects (a particle moves a small fraction of L per sub-stage)
-  T up = q + L;                       // q in [-L, 0)
+  T up = q + L;                       // q in [-L, 0]
   up = (up >= L) ? T(0) : up;         // tiny negative q: q + L rounds to L, the second mod gives 0
-  T r = (q < T(0)) ? up : q;
+  T r = (q <= T(0)) ? up : q;         // q = -0.0 (or +0.0): L -> +0.0, as np.mod gives (not -0.0)
   r = (q >= L) ? q - L : r;           // q in [L, 2L): exact (Sterbenz)
   // For q in [-L, 2L) r now lies in [0, L).  One range test therefore catches both a position further away
   // (fmod path) and a NaN / inf one (counted, parked on node 0, never used as an index).
@@ -371,7 +371,10 @@ __device__ __forceinline__ typename P::X pos_from_length(double xs, double L, un
 
 // q + (c p) dt  (integration.py:42).  PosU32: the displacement is rounded to position units and added modulo
 // 2^32, which is the periodic wrap; a displacement of half a box or more per sub-stage cannot be represented
-// (and is far outside any CFL-limited step): counted as a bad position.
+// (and is far outside any CFL-limited step): counted as a bad position.  The counter (pic_bad_count) is a diagnostic
+// that counts such drift EVALUATIONS, not distinct particles: a step evaluates some drifts more than once (q1 at the
+// deposit that opens it and again in the sweep or phase that kicks, the next step's q1 at its end), so one particle with an
+// unrepresentable c1 / c4 displacement adds a fixed number per step that depends on the schedule (tests/test_gpu_local_parity.py).
 template <typename P>
 __device__ __forceinline__ typename P::X drift(typename P::X q, typename P::V p, typename P::W c, const Consts<P>& k,
                                                unsigned& bad) {

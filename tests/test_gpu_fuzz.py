@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import circ_err, rel_err
+from hp_checks import check_handle_step
 
 pytestmark = pytest.mark.gpu
 
@@ -59,7 +60,7 @@ def test_random_shapes_against_oracle():
                 finite = False
             if not finite:
                 # the reference's Sherman-Morrison solve is singular for this (L, Ng); the device
-                # solver has no such failure mode, its own invariants are checked instead
+                # solver has no such failure mode: the step-local checks below compare it with hp_reference instead
                 assert np.isfinite(Em[e]).all() and abs(n[e].sum() * (L / Ng) - n0 * L) < 1e-9 * n0 * L, tag
                 continue
             scale = max(1.0, float(np.max(np.abs(ref.v))))
@@ -70,6 +71,11 @@ def test_random_shapes_against_oracle():
                 assert rel_err(Em[e], ref.E_mesh) < 1e-8, tag
             assert abs(ke[e] - ref.kinetic_energy()) <= 1e-11 * max(1.0, ref.kinetic_energy()), tag
             checked += 1
+        # every environment, the reference's solve singular or not: one more step against tests/hp_reference.py from the
+        # device's state -- positions and velocities, the density against the exact deposit of the stored positions, E_mesh and
+        # phi against the extended-precision solve of the device's own density, the energies (derived bounds, tests/hp_checks.py)
+        check_handle_step(env, "float64", None, interpol, E_ext, tag=str(tag))
+        assert env.bad_count() == 0, tag
         env.close()
     assert checked >= CASES          # most environments have a finite reference to compare with
 

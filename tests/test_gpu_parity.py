@@ -806,12 +806,13 @@ def test_phase_histogram_and_kl_on_device(oc):
 def test_edge_sizes(oc, po):
     """Ragged and extreme shapes: fewer particles than one tile, one particle, the largest mesh,
     a mesh over the LDS limit, zero steps.
-    Parity is checked only where the reference itself is defined: for some (L, Ng) pairs the Sherman-Morrison denominator of
-    its periodic solve (src/env/solve.py:27-53) is exactly 0 and its fields are inf / nan (the oracle, which restates
-    that solve, warns "divide by zero" here).  For those shapes the oracle branch below is SKIPPED -- parity is undefined there,
-    not green -- and only the size-independent properties (charge, no bad positions) are asserted; `skipped` names them."""
+    Trajectory parity with the oracle is checked where the reference itself is defined: for some (L, Ng) pairs the Sherman-Morrison
+    denominator of its periodic solve (src/env/solve.py:27-53) is exactly 0 and its fields are inf / nan.  Every shape,
+    those included, gets the step-local checks against tests/hp_reference.py: one more step from the state the three-step call
+    left, and the density, field, potential and energies of the state after it."""
+    from hp_checks import check_handle_step
     L = 50.0
-    skipped = []
+    singular = []
     for N, Ng in ((1, 8), (7, 16), (511, 64), (513, 64), (4097, 2700)):
         rng = np.random.default_rng(N)
         x0, v0 = rng.uniform(0, L, N), rng.normal(0, 1, N)
@@ -828,12 +829,15 @@ def test_edge_sizes(oc, po):
             assert circ_err(x[0], ref.x, L) / L < 1e-12 and rel_err(v[0], ref.v) < 1e-11, (N, Ng)
             assert rel_err(env.fields()[1][0], ref.E_mesh) < 1e-9, (N, Ng)
         else:
-            skipped.append((N, Ng))
+            singular.append((N, Ng))
         n = env.fields()[0]
         assert np.allclose(n.sum(axis=1) * (L / Ng), L, rtol=1e-12) and env.bad_count() == 0
+        # every shape, the singular ones included: a fourth step against tests/hp_reference.py from the device's state
+        check_handle_step(env, "float64", None, "CIC", tag="edge size")
+        assert env.bad_count() == 0
         env.close()
-    assert len(skipped) < 5, skipped              # at least one of the shapes is compared with the oracle
-    print("test_edge_sizes: the reference's solve is singular, no parity asserted, for (N, Ng) in", skipped)
+    assert len(singular) < 5, singular            # at least one of the shapes is compared with the oracle as well
+    print("test_edge_sizes: skipped shapes: none; checked against hp_reference only (the reference's solve is singular):", singular)
     with pytest.raises(oc._abi.PicError, match="Ng too large"):
         oc.BatchedPIC(1, 1000, 4096, L=L, dt=0.05)
 
@@ -843,6 +847,7 @@ def test_largest_meshes_are_admitted_at_create_or_refused_there(oc, dtype, ng_sw
     """The LDS budget of a workgroup (64 KB: dynamic meshes + the kernels' static arrays) is checked by pic_create: the largest
     admitted mesh of either schedule steps, one cell more is EINVAL at create -- never a launch failure later -- and the
     message quotes the bound that is enforced."""
+    from hp_checks import check_handle_step
     L, N = 50.0, 3000
     rng = np.random.default_rng(ng_sweeps)
     x0, v0 = rng.uniform(0, L, (1, N)).astype(dtype), rng.normal(0, 1, (1, N)).astype(dtype)
@@ -853,6 +858,10 @@ def test_largest_meshes_are_admitted_at_create_or_refused_there(oc, dtype, ng_sw
         env.step(None, 2)
         n = env.fields()[0]
         assert np.allclose(n.sum() * (L / Ng), L, rtol=1e-6 if dtype == "float32" else 1e-12) and env.bad_count() == 0
+        # the mesh at the LDS limit against tests/hp_reference.py: one more step from the state the two-step call left, then
+        # per-node density, solve, potential and energies
+        check_handle_step(env, dtype, None, "CIC", tag="largest mesh")
+        assert env.bad_count() == 0
         env.close()
     with pytest.raises(oc._abi.PicError, match=f"at most {ng_sweeps} cells"):
         oc.BatchedPIC(1, N, ng_sweeps + 1, L=L, dt=0.05, dtype=dtype, blocks_per_env=2)
