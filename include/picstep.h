@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PICSTEP_ABI_VERSION 4
+#define PICSTEP_ABI_VERSION 5
 
 enum { PIC_F64 = 0, PIC_F32 = 1 };           /* particle dtype (velocities; positions too unless fixed point) */
 enum { PIC_POS_FLOAT = 0,                    /* positions stored in the particle dtype                         */
@@ -310,6 +310,55 @@ typedef struct {
   double malloc_seconds, timing_seconds, free_seconds;
 } pic_placement;
 int pic_placement_stats(pic_handle* h, pic_placement* out);
+
+/* Rollout recorder (ABI 5): small reductions of the state, computed on the device after every `stride`-th step of ANY stepping
+ * entry (pic_step, pic_step_history, pic_step_snapshots, pic_step_actions[_traj], pic_step_ext_traj, pic_step_feedback,
+ * pic_step_observe, stage 3 of pic_step_stage) and held on the device until read -- the analyses the reference runs on a full
+ * (2N, Nt) particle snapshot (src/interpret/landau.py, spectrum.py, the KL of run_ddpg.py:276-312) without the snapshot.
+ * Steps are counted from pic_record_start over all calls; step k is recorded when k % stride == 0.  A recorded step ends like
+ * the last step of a call and two kernels follow it (a particle pass for the histograms, one workgroup per environment for the
+ * rest): particles, fields and energies are bit for bit those of the same calls without a recorder.  A record is bitwise
+ * reproducible and does not depend on blocks_per_env or the schedule -- except KE, which is the step's own (pic_get_energies'):
+ * its per-workgroup partial sums follow the sweep grid in the last bits.  Resets and pic_set_particles count no step and do not
+ * end the recording.  A stepping call that would take the record count past `capacity` is refused (PIC_ENOMEM) before any
+ * step runs.  Histogram edges are np.histogram / np.histogram2d's (as pic_phase_histogram). */
+typedef struct pic_record_config {
+  int32_t stride;                  /* >= 1 */
+  int32_t n_modes;                 /* rows 0..n_modes-1 of fft(E_mesh) / Ng * 2 (spectrum.py:16); 0..Ng/2+1            */
+  int32_t x_bins, v_bins;          /* marginal histograms of x on [0, L] and v on [vmin, vmax]; 0..4096, 0 = none        */
+  int32_t phase_x_bins, phase_v_bins;  /* phase-space histogram behind entropy / KL, 1..4096 each, or both 0 = none     */
+  double  vmin, vmax;              /* vmax > vmin */
+  double  phase_dx, phase_dv;      /* f = counts * n0 / phase_dx / phase_dv / N; 0 = L / phase_x_bins, (vmax - vmin) / phase_v_bins */
+  const double* feq;               /* NULL, or host [phase_x_bins][phase_v_bins]: the KL target (estimate_f normalisation) */
+  int64_t capacity;                /* records held on the device, >= 1 */
+} pic_record_config;
+
+/* Host outputs of pic_record_read for records first..first+count-1; any pointer may be NULL.  Per record: step [count]
+ * (int64, the step index k; 0 for a pic_record_now right after pic_record_start); per record and environment ([count][num_envs]):
+ * KE, PE, PE_reward as pic_get_energies reports them, field_energy = sum(E_mesh^2) dx (landau.py:68), entropy =
+ * -sum_{f>0} f ln f dx dv (landau.py:19-25, dx dv = phase_dx phase_dv), kl = sum rel_entr(f, feq + 1e-12) dx dv (pic_phase_kl;
+ * NaN without feq or phase histogram), inside = particles with x in [0, L] and v in [vmin, vmax] (int64); re / im
+ * [count][num_envs][n_modes]; x_hist [count][num_envs][x_bins], v_hist [count][num_envs][v_bins] (uint32). */
+typedef struct pic_record_out {
+  int64_t* step;
+  double* KE;
+  double* PE;
+  double* PE_reward;
+  double* field_energy;
+  double* entropy;
+  double* kl;
+  double* re;
+  double* im;
+  uint32_t* x_hist;
+  uint32_t* v_hist;
+  int64_t* inside;
+} pic_record_out;
+
+int pic_record_start(pic_handle* h, const pic_record_config* cfg);   /* allocates (PIC_ENOMEM if capacity does not fit); PIC_ESTATE if on */
+int pic_record_now(pic_handle* h);                                   /* append a record of the current state (e.g. t = 0) */
+int pic_record_count(pic_handle* h, int64_t* n);                     /* records held (0 and PIC_OK when not recording) */
+int pic_record_read(pic_handle* h, int64_t first, int64_t count, pic_record_out* out);   /* PIC_ESTATE when not recording */
+int pic_record_stop(pic_handle* h);                                  /* frees; the records are gone */
 
 int pic_sync(pic_handle* h);
 /* Number of particle positions found non-finite or out of range by the last sweeps (0 = healthy). */

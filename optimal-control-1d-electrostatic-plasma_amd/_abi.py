@@ -15,7 +15,7 @@ PIC_POS_FLOAT, PIC_POS_FIXED32 = 0, 1
 PIC_ACC_AUTO, PIC_ACC_FIX64, PIC_ACC_PACKED, PIC_ACC_F64 = 0, 1, 2, 3
 PIC_CIC, PIC_TSC = 0, 1
 PIC_HOST, PIC_DEVICE = 0, 1
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 # accum_dtype spellings of the Python layer -> PIC_ACC_*
 ACCUMULATORS = {None: PIC_ACC_AUTO, "auto": PIC_ACC_AUTO, "fix64": PIC_ACC_FIX64, "fixed": PIC_ACC_PACKED,
@@ -33,6 +33,22 @@ class PicConfig(C.Structure):
         ("device_id", C.c_int32), ("blocks_per_env", C.c_int32), ("env_index_base", C.c_int32),
         ("position_dtype", C.c_int32), ("placement", C.c_int32), ("placement_ms", C.c_int32),
     ]
+
+
+class PicRecordConfig(C.Structure):
+    """pic_record_config (include/picstep.h): what the rollout recorder keeps of every recorded step."""
+    _fields_ = [
+        ("stride", C.c_int32), ("n_modes", C.c_int32), ("x_bins", C.c_int32), ("v_bins", C.c_int32),
+        ("phase_x_bins", C.c_int32), ("phase_v_bins", C.c_int32),
+        ("vmin", C.c_double), ("vmax", C.c_double), ("phase_dx", C.c_double), ("phase_dv", C.c_double),
+        ("feq", C.c_void_p), ("capacity", C.c_int64),
+    ]
+
+
+class PicRecordOut(C.Structure):
+    """pic_record_out (include/picstep.h): host arrays receiving records, any may be NULL."""
+    _fields_ = [(name, C.c_void_p) for name in ("step", "KE", "PE", "PE_reward", "field_energy", "entropy", "kl", "re", "im",
+                                                  "x_hist", "v_hist", "inside")]
 
 
 class PicError(RuntimeError):
@@ -76,6 +92,11 @@ SIGNATURES = {
     "pic_phase_histogram": [_vp, C.c_int, C.c_double, C.c_double, _vp],
     "pic_phase_kl": [_vp, C.c_int, C.c_double, C.c_double, _vp, _vp],
     "pic_stream_probe": [_vp, C.c_int, _dp],
+    "pic_record_start": [_vp, C.POINTER(PicRecordConfig)],
+    "pic_record_now": [_vp],
+    "pic_record_count": [_vp, _i64p],
+    "pic_record_read": [_vp, C.c_int64, C.c_int64, C.POINTER(PicRecordOut)],
+    "pic_record_stop": [_vp],
     "pic_set_stream": [_vp, _vp],
     "pic_own_stream": [_vp],
     "pic_schedule": [_vp],
@@ -479,6 +500,53 @@ class Handle:
         kl = np.empty(self.num_envs)
         self._chk(self.lib.pic_phase_kl(self._h, int(f.shape[0]), float(vmin), float(vmax), _ptr(f), _ptr(kl)))
         return kl
+
+    # -- rollout recorder (pic_record_*) ------------------------------------------------------------
+    def record_start(self, stride=1, n_modes=0, x_bins=0, v_bins=0, phase_bins=(0, 0), vmin=-25.0, vmax=25.0, phase_dx=0.0,
+                     phase_dv=0.0, feq=None, capacity=1024):
+        px, pv = (int(b) for b in phase_bins)
+        f = None
+        if feq is not None:
+            f = np.ascontiguousarray(np.asarray(feq, dtype=np.float64))
+            if f.shape != (px, pv):
+                raise ValueError(f"feq must be [{px}, {pv}] (the phase bins), not {list(f.shape)}")
+        cfg = PicRecordConfig(int(stride), int(n_modes), int(x_bins), int(v_bins), px, pv, float(vmin), float(vmax),
+                              float(phase_dx), float(phase_dv), None if f is None else f.ctypes.data, int(capacity))
+        self._chk(self.lib.pic_record_start(self._h, C.byref(cfg)))
+        self.record_config = {"stride": int(stride), "n_modes": int(n_modes), "x_bins": int(x_bins), "v_bins": int(v_bins),
+                              "phase_bins": (px, pv), "vmin": float(vmin), "vmax": float(vmax), "feq": f is not None}
+
+    def record_now(self):
+        self._chk(self.lib.pic_record_now(self._h))
+
+    def record_count(self):
+        n = C.c_int64()
+        self._chk(self.lib.pic_record_count(self._h, C.byref(n)))
+        return n.value
+
+    def record_read(self, first=0, count=None):
+        """Records first..first+count-1 (all from `first` by default) -> dict of host arrays: step [R]; KE, PE, PE_reward,
+        field_energy, entropy, kl, inside [R, E]; re, im [R, E, n_modes]; x_hist [R, E, x_bins], v_hist [R, E, v_bins]."""
+        c = getattr(self, "record_config", None)
+        if c is None:
+            raise PicError("record_read: not recording")
+        if count is None:
+            count = self.record_count() - int(first)
+        R, E = int(count), self.num_envs
+        out = {"step": np.empty(R, dtype=np.int64), "inside": np.empty((R, E), dtype=np.int64)}
+        for k in ("KE", "PE", "PE_reward", "field_energy", "entropy", "kl"):
+            out[k] = np.empty((R, E))
+        out["re"] = np.empty((R, E, c["n_modes"]))
+        out["im"] = np.empty((R, E, c["n_modes"]))
+        out["x_hist"] = np.empty((R, E, c["x_bins"]), dtype=np.uint32)
+        out["v_hist"] = np.empty((R, E, c["v_bins"]), dtype=np.uint32)
+        o = PicRecordOut(*(out[name].ctypes.data for name, _ in PicRecordOut._fields_))
+        self._chk(self.lib.pic_record_read(self._h, int(first), R, C.byref(o)))
+        return out
+
+    def record_stop(self):
+        self._chk(self.lib.pic_record_stop(self._h))
+        self.record_config = None
 
     def stream_probe(self, repeats=10):
         g = C.c_double()

@@ -59,6 +59,7 @@
 #include "pic_solve.h"
 #include "pic_resident.h"
 #include "pic_aux.h"
+#include "pic_record.h"
 
 
 // ---------------------------------------------------------------------------------------------
@@ -76,6 +77,28 @@ struct PlacementState {
   bool x_cleared = false;
 };
 constexpr int RING = 8;                                          // accumulator rows in rotation
+
+// The rollout recorder of a handle (pic_record_*, pic_record.h).  Records live in two device arrays, one slot per record:
+// doubles [cap][env][d_stride] (KE, PE, PE_reward, field_energy, entropy, kl, re [M], im [M]) and uint32 [cap][env][u_stride]
+// (x_hist, v_hist, inside), the latter zeroed when recording starts; the step indices are known here.
+struct Recorder {
+  bool on = false;
+  int stride = 1, M = 0, xb = 0, vb = 0, px = 0, pv = 0;
+  double vmin = 0, vmax = 0, pdx = 0, pdv = 0;
+  int64_t cap = 0;
+  int64_t k = 0;                      // steps made since pic_record_start
+  std::vector<int64_t> steps;         // step index of every record held
+  long long d_stride = 0, u_stride = 0;
+  double* d = nullptr;
+  unsigned* u = nullptr;
+  unsigned* phase = nullptr;          // [env][px pv] counts of the record being made (zero between records)
+  double* feq = nullptr;              // [px pv] or null
+  int phase_lds = 0;
+  int rr = 1;                         // copies of each marginal bin in the particle pass's LDS
+  size_t lds = 0;
+  int gx = 1;                         // particle-pass workgroups per environment
+  long long tiles_per_wg = 1;
+};
 
 struct pic_handle {
   pic_config cfg{};
@@ -108,6 +131,7 @@ struct pic_handle {
   double* post_hist_row = nullptr;    // the same for the solve that post_slot stands for
   PlacementStats place{};             // what the search for an (x, v) placement did, all legs together (pic_placement_stats)
   PlacementState place_state{};       // what a later leg of it needs to know (placement_leg, resume_placement)
+  Recorder rec{};                     // pic_record_*: reductions recorded after every rec.stride-th step (advance, pic_step_stage)
   void* x = nullptr;
   void* v = nullptr;
   void* scratch = nullptr;        // [env][ld] positions of a probe (eval_field / compute_E)
@@ -1110,7 +1134,7 @@ int pic_destroy(pic_handle* h) {
   if (h->stream) hipStreamSynchronize(h->stream);
   prof_drain(h);
   for (hipEvent_t e : h->ev) hipEventDestroy(e);
-  void* bufs[] = {h->x, h->scratch, h->stage, h->ring, h->ke_part, h->n, h->E_mesh, h->phi, h->ext, h->ext2, h->probe_ext,
+  void* bufs[] = {h->rec.d, h->rec.u, h->rec.phase, h->rec.feq, h->x, h->scratch, h->stage, h->ring, h->ke_part, h->n, h->E_mesh, h->phi, h->ext, h->ext2, h->probe_ext,
                   h->basis, h->act, h->modes, h->aux_n, h->aux_E, h->aux_pe, h->aux_phi, h->KE, h->bad, h->tw, h->traj, h->res_q1, h->res_carry};
   for (void* b : bufs)
     if (b) hipFree(b);
@@ -1318,7 +1342,7 @@ static int ensure_twiddle(pic_handle* h, int rows) {
 
 // nsteps x PIC.update_state under `sc`, all launches enqueued, no host synchronisation.  hist: device [nsteps][3][env] record of
 // the energies, or null; snap (resident schedule only): device record of the particles.
-static int advance(pic_handle* h, const StepControl& sc, int nsteps, double* hist, void* snap = nullptr) {
+static int advance_steps(pic_handle* h, const StepControl& sc, int nsteps, double* hist, void* snap) {
   if (nsteps <= 0) return PIC_OK;
   const int E = h->cfg.num_envs;
   if (h->resident) {
@@ -1373,6 +1397,78 @@ static int advance(pic_handle* h, const StepControl& sc, int nsteps, double* his
   return PIC_OK;
 }
 
+// the two recorder kernels on the state as it stands (pic_record.h); appends one record
+static int record_enqueue(pic_handle* h) {
+  Recorder& r = h->rec;
+  const int E = h->cfg.num_envs;
+  const int64_t slot = (int64_t)r.steps.size();
+  if (slot >= r.cap) return fail(h, PIC_ENOMEM, "the recorder is full");      // (every caller has checked: a last guard of the slot)
+  RecordHistArgs ha{};
+  ha.rec = r.u + (size_t)slot * E * r.u_stride;
+  ha.u_stride = r.u_stride;
+  ha.phase = r.phase;
+  ha.xb = r.xb; ha.vb = r.vb; ha.px = r.px; ha.pv = r.pv;
+  ha.phase_lds = r.phase_lds;
+  ha.rr = r.rr;
+  ha.N = h->cfg.N; ha.ld = h->ld; ha.tiles_per_wg = r.tiles_per_wg;
+  ha.L = h->cfg.L; ha.vmin = r.vmin; ha.vmax = r.vmax;
+  // np.linspace steps: (stop - start) / div
+  ha.sx = r.xb ? (h->cfg.L - 0.0) / r.xb : 0.0;
+  ha.sv = r.vb ? (r.vmax - r.vmin) / r.vb : 0.0;
+  ha.spx = r.px ? (h->cfg.L - 0.0) / r.px : 0.0;
+  ha.spv = r.pv ? (r.vmax - r.vmin) / r.pv : 0.0;
+  const dim3 grid(r.gx, E);
+  if (h->fmt == FMT_F64)
+    hipLaunchKernelGGL(record_hist_kernel<PosF64>, grid, dim3(BLOCK), r.lds, h->stream, (const double*)h->x, (const double*)h->v, ha);
+  else if (h->fmt == FMT_F32)
+    hipLaunchKernelGGL(record_hist_kernel<PosF32>, grid, dim3(BLOCK), r.lds, h->stream, (const float*)h->x, (const float*)h->v, ha);
+  else
+    hipLaunchKernelGGL(record_hist_kernel<PosU32>, grid, dim3(BLOCK), r.lds, h->stream, (const unsigned*)h->x, (const float*)h->v, ha);
+  RecordFinishArgs fa{};
+  fa.E_mesh = h->E_mesh; fa.KE = h->KE; fa.tw = h->tw; fa.tw_rows = h->tw_rows; fa.Ng = h->cfg.Ng; fa.M = r.M; fa.dx = h->dx;
+  fa.rec = r.d + (size_t)slot * E * r.d_stride;
+  fa.d_stride = r.d_stride;
+  fa.phase = r.phase; fa.nb2 = r.px * r.pv; fa.feq = r.feq;
+  fa.norm = r.px ? h->cfg.n0 / r.pdx / r.pdv / (double)h->cfg.N : 0.0;      // objective.py:12, left to right
+  fa.dxdv = r.pdx * r.pdv;
+  hipLaunchKernelGGL(record_finish_kernel, dim3(E), dim3(BLOCK), 0, h->stream, fa);
+  HIPCHK(h, hipGetLastError());
+  r.steps.push_back(r.k);
+  return PIC_OK;
+}
+
+// records that nsteps more steps would add
+static int64_t records_ahead(const pic_handle* h, int64_t nsteps) {
+  const Recorder& r = h->rec;
+  return r.on ? (r.k + nsteps) / r.stride - r.k / r.stride : 0;
+}
+
+// advance_steps with the recorder: the steps are cut behind every recorded step, which therefore ends like the last step of a
+// call (full sweep D and a solve launch of its own; resident schedule: the end of a launch) -- stepping call by call gives the
+// same bits -- and the record kernels follow it on the stream.
+static int advance(pic_handle* h, const StepControl& sc, int nsteps, double* hist, void* snap = nullptr) {
+  Recorder& r = h->rec;
+  if (!r.on || nsteps <= 0) return advance_steps(h, sc, nsteps, hist, snap);
+  const int E = h->cfg.num_envs;
+  for (int done = 0; done < nsteps;) {
+    const int n = (int)std::min<int64_t>(r.stride - r.k % r.stride, nsteps - done);
+    StepControl part = sc;
+    if (part.ctl.ext) part.ctl.ext += (size_t)done * sc.ext_step;
+    if (part.ctl.act) part.ctl.act += (size_t)done * sc.act_step;
+    if (part.fb.act_hist) part.fb.act_hist += (size_t)done * E * 2 * sc.fb.M;
+    int rc = advance_steps(h, part, n, hist ? hist + (size_t)done * 3 * E : nullptr,
+                           snap ? static_cast<char*>(snap) + (size_t)done * 2 * E * (size_t)h->cfg.N * h->esz : nullptr);
+    if (rc) return rc;
+    r.k += n;
+    done += n;
+    if (r.k % r.stride == 0) {
+      rc = record_enqueue(h);
+      if (rc) return rc;
+    }
+  }
+  return PIC_OK;
+}
+
 int pic_step_stage(pic_handle* h, int stage, const double* E_ext, int mem_kind) {
   if (!h) return PIC_EINVAL;
   if (!h->has_state) return fail(h, PIC_ESTATE, "pic_step_stage: call pic_reset first");
@@ -1382,10 +1478,13 @@ int pic_step_stage(pic_handle* h, int stage, const double* E_ext, int mem_kind) 
   Control ctl{};
   int rc = stage_ext(h, E_ext, mem_kind, &ctl.ext);
   if (rc) return rc;
+  if (stage == 1 && h->rec.on && (int64_t)h->rec.steps.size() + records_ahead(h, 1) > h->rec.cap)
+    return fail(h, PIC_ENOMEM, "pic_step_stage: the step would take the recorder past its capacity");
   h->res_q1_valid = false;           // (a resident handle steps by sweeps here: its carried q1 mesh goes stale)
   run_stages(h, stage, stage, ctl);
   h->mid_stage = stage == 3 ? 0 : stage;
   HIPCHK(h, hipGetLastError());
+  if (stage == 3 && h->rec.on && ++h->rec.k % h->rec.stride == 0) return record_enqueue(h);
   return PIC_OK;
 }
 
@@ -1393,6 +1492,9 @@ static int check_steppable(pic_handle* h, int nsteps, const char* who) {
   if (!h->has_state) return fail(h, PIC_ESTATE, std::string(who) + ": call pic_reset first");
   if (nsteps < 0) return fail(h, PIC_EINVAL, std::string(who) + ": nsteps < 0");
   if (h->mid_stage) return fail(h, PIC_ESTATE, std::string(who) + ": a staged step is in progress (finish pic_step_stage 1..3)");
+  if (h->rec.on && (int64_t)h->rec.steps.size() + records_ahead(h, nsteps) > h->rec.cap)
+    return fail(h, PIC_ENOMEM, std::string(who) + ": the steps would take the recorder past its capacity (read and restart it, or "
+                                                   "record with a larger capacity)");
   return PIC_OK;
 }
 
@@ -2076,6 +2178,141 @@ int pic_phase_kl(pic_handle* h, int nbins, double vmin, double vmax, const doubl
   if (d) hipFree(d);
   if (df) hipFree(df);
   if (e != hipSuccess) return fail(h, PIC_EHIP, std::string("pic_phase_kl: ") + hipGetErrorString(e));
+  return PIC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Rollout recorder (include/picstep.h: pic_record_*; hooks: advance, pic_step_stage)
+// ---------------------------------------------------------------------------------------------
+static void record_free(pic_handle* h) {
+  Recorder& r = h->rec;
+  for (void* b : {(void*)r.d, (void*)r.u, (void*)r.phase, (void*)r.feq})
+    if (b) hipFree(b);
+  r = Recorder{};
+}
+
+int pic_record_start(pic_handle* h, const pic_record_config* c) {
+  if (!h || !c) return fail(h, PIC_EINVAL, "pic_record_start: null argument");
+  if (h->rec.on) return fail(h, PIC_ESTATE, "pic_record_start: already recording (pic_record_stop first)");
+  if (h->mid_stage) return fail(h, PIC_ESTATE, "pic_record_start: a staged step is in progress (finish pic_step_stage 1..3)");
+  const int Ng = h->cfg.Ng;
+  const bool phase = c->phase_x_bins > 0 || c->phase_v_bins > 0;
+  if (c->stride < 1 || c->n_modes < 0 || c->n_modes > Ng / 2 + 1 || c->x_bins < 0 || c->x_bins > 4096 || c->v_bins < 0 ||
+      c->v_bins > 4096 || (phase && (c->phase_x_bins < 1 || c->phase_x_bins > 4096 || c->phase_v_bins < 1 || c->phase_v_bins > 4096)) ||
+      !(std::isfinite(c->vmin) && std::isfinite(c->vmax) && c->vmax > c->vmin) || !(c->phase_dx >= 0) || !(c->phase_dv >= 0) ||
+      (c->feq && !phase) || c->capacity < 1)
+    return fail(h, PIC_EINVAL, "pic_record_start: need stride >= 1, 0 <= n_modes <= Ng/2+1, 0 <= x_bins, v_bins <= 4096, phase bins both 0 "
+                               "or both in 1..4096, finite vmin < vmax, phase_dx, phase_dv >= 0, feq only with a phase histogram, capacity >= 1");
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  Recorder r;
+  r.stride = c->stride; r.M = c->n_modes; r.xb = c->x_bins; r.vb = c->v_bins;
+  r.px = phase ? c->phase_x_bins : 0; r.pv = phase ? c->phase_v_bins : 0;
+  r.vmin = c->vmin; r.vmax = c->vmax;
+  r.pdx = c->phase_dx > 0 ? c->phase_dx : (r.px ? h->cfg.L / r.px : 0.0);
+  r.pdv = c->phase_dv > 0 ? c->phase_dv : (r.pv ? (r.vmax - r.vmin) / r.pv : 0.0);
+  r.cap = c->capacity;
+  r.d_stride = 6 + 2 * (long long)r.M;
+  r.u_stride = (long long)r.xb + r.vb + 1;
+  const int E = h->cfg.num_envs;
+  const size_t nb2 = (size_t)r.px * r.pv;
+  const size_t dbytes = (size_t)r.cap * E * r.d_stride * sizeof(double), ubytes = (size_t)r.cap * E * r.u_stride * sizeof(unsigned);
+  if ((size_t)r.cap > ((size_t)1 << 40) / ((size_t)E * (r.d_stride * 8 + r.u_stride * 4)))
+    return fail(h, PIC_ENOMEM, "pic_record_start: capacity does not fit on the device");
+  bool ok = hipMalloc((void**)&r.d, dbytes) == hipSuccess && hipMalloc((void**)&r.u, ubytes) == hipSuccess &&
+            (!nb2 || hipMalloc((void**)&r.phase, (size_t)E * nb2 * sizeof(unsigned)) == hipSuccess) &&
+            (!c->feq || hipMalloc((void**)&r.feq, nb2 * sizeof(double)) == hipSuccess);
+  if (!ok) {
+    hipGetLastError();
+    h->rec = r;
+    record_free(h);
+    return fail(h, PIC_ENOMEM, "pic_record_start: capacity does not fit on the device");
+  }
+  hipError_t e = hipMemsetAsync(r.u, 0, ubytes, h->stream);
+  if (e == hipSuccess && nb2) e = hipMemsetAsync(r.phase, 0, (size_t)E * nb2 * sizeof(unsigned), h->stream);
+  if (e == hipSuccess && c->feq) e = hipMemcpyAsync(r.feq, c->feq, nb2 * sizeof(double), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  h->rec = r;
+  if (e != hipSuccess) {
+    record_free(h);
+    return fail(h, PIC_EHIP, std::string("pic_record_start: ") + hipGetErrorString(e));
+  }
+  if (r.M > 1) {
+    const int rc = ensure_twiddle(h, r.M - 1);
+    if (rc) { record_free(h); return rc; }
+  }
+  // particle pass geometry: about 1024 workgroups in all, each over a contiguous range of 16-byte tiles
+  const long long vec = h->fmt == FMT_F64 ? 2 : 4;
+  const long long cols = ((h->cfg.N + vec - 1) / vec + BLOCK - 1) / BLOCK;     // tiles per lane if one workgroup took it all
+  long long gx = std::max(1LL, std::min(cols, (1024LL + E - 1) / E));
+  h->rec.tiles_per_wg = (cols + gx - 1) / gx;
+  h->rec.gx = (int)((cols + h->rec.tiles_per_wg - 1) / h->rec.tiles_per_wg);
+  // (pic_record.h: rr copies of each marginal bin within 32 KiB, phase rows of pv + 1 words)
+  int rr = 16;
+  while (rr > 1 && (size_t)rr * (r.xb + r.vb) * sizeof(unsigned) > ((size_t)32 << 10)) rr /= 2;
+  h->rec.rr = rr;
+  const size_t marg = ((size_t)rr * (r.xb + r.vb) + 1) * sizeof(unsigned), prow = (size_t)r.px * (r.pv + 1) * sizeof(unsigned);
+  h->rec.phase_lds = marg + prow <= (size_t)kRecordLdsBytes ? 1 : 0;
+  h->rec.lds = marg + (h->rec.phase_lds ? prow : 0);
+  h->rec.on = true;
+  return PIC_OK;
+}
+
+int pic_record_now(pic_handle* h) {
+  if (!h) return PIC_EINVAL;
+  if (!h->rec.on) return fail(h, PIC_ESTATE, "pic_record_now: not recording (pic_record_start first)");
+  if (!h->has_state) return fail(h, PIC_ESTATE, "pic_record_now: call pic_reset first");
+  if (h->mid_stage) return fail(h, PIC_ESTATE, "pic_record_now: a staged step is in progress (finish pic_step_stage 1..3)");
+  if ((int64_t)h->rec.steps.size() >= h->rec.cap) return fail(h, PIC_ENOMEM, "pic_record_now: the recorder is full");
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  return record_enqueue(h);
+}
+
+int pic_record_count(pic_handle* h, int64_t* n) {
+  if (!h || !n) return fail(h, PIC_EINVAL, "pic_record_count: null argument");
+  *n = h->rec.on ? (int64_t)h->rec.steps.size() : 0;
+  return PIC_OK;
+}
+
+int pic_record_read(pic_handle* h, int64_t first, int64_t count, pic_record_out* out) {
+  if (!h || !out) return fail(h, PIC_EINVAL, "pic_record_read: null argument");
+  const Recorder& r = h->rec;
+  if (!r.on) return fail(h, PIC_ESTATE, "pic_record_read: not recording (the records of a stopped recorder are gone)");
+  if (first < 0 || count < 0 || first + count > (int64_t)r.steps.size())
+    return fail(h, PIC_EINVAL, "pic_record_read: records first..first+count-1 are not all held");
+  if (count == 0) return PIC_OK;
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  const size_t E = (size_t)h->cfg.num_envs, n = (size_t)count;
+  std::vector<double> d(n * E * r.d_stride);
+  std::vector<unsigned> u(n * E * r.u_stride);
+  HIPCHK(h, hipMemcpyAsync(d.data(), r.d + (size_t)first * E * r.d_stride, d.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(u.data(), r.u + (size_t)first * E * r.u_stride, u.size() * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  double* scal[6] = {out->KE, out->PE, out->PE_reward, out->field_energy, out->entropy, out->kl};
+  const size_t M = (size_t)r.M, xb = (size_t)r.xb, vb = (size_t)r.vb;
+  for (size_t i = 0; i < n; ++i) {
+    if (out->step) out->step[i] = r.steps[(size_t)first + i];
+    for (size_t e = 0; e < E; ++e) {
+      const double* src = d.data() + (i * E + e) * r.d_stride;
+      const unsigned* us = u.data() + (i * E + e) * r.u_stride;
+      for (int q = 0; q < 6; ++q)
+        if (scal[q]) scal[q][i * E + e] = src[q];
+      if (out->re) std::memcpy(out->re + (i * E + e) * M, src + 6, M * sizeof(double));
+      if (out->im) std::memcpy(out->im + (i * E + e) * M, src + 6 + M, M * sizeof(double));
+      if (out->x_hist) std::memcpy(out->x_hist + (i * E + e) * xb, us, xb * sizeof(unsigned));
+      if (out->v_hist) std::memcpy(out->v_hist + (i * E + e) * vb, us + xb, vb * sizeof(unsigned));
+      if (out->inside) out->inside[i * E + e] = us[xb + vb];
+    }
+  }
+  return PIC_OK;
+}
+
+int pic_record_stop(pic_handle* h) {
+  if (!h) return PIC_EINVAL;
+  if (!h->rec.on) return PIC_OK;
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  const hipError_t e = hipStreamSynchronize(h->stream);
+  record_free(h);
+  if (e != hipSuccess) return fail(h, PIC_EHIP, std::string("pic_record_stop: ") + hipGetErrorString(e));
   return PIC_OK;
 }
 

@@ -8,6 +8,7 @@ from typing import Optional
 import numpy as np
 
 from .. import _abi
+from .record import Record, recorder_args, recording_session
 
 
 class _DeviceView:
@@ -259,6 +260,38 @@ class BatchedPIC:
         """Reward.compute_kl_divergence (reward.py:43-46) of every environment against `feq` [nbins, nbins]: histogram and
         reduction on the device, one value per environment read back (pic_phase_kl)."""
         return self._h.phase_kl(feq, vmin, vmax)
+
+    # -- rollout recorder (include/picstep.h: pic_record_*) ----------------------------------------
+    def start_recording(self, stride: int = 1, modes: Optional[int] = None, x_bins: int = 0, v_bins: int = 0, phase_bins=None,
+                        vmin: float = -25.0, vmax: float = 25.0, feq=None, capacity: int = 4096, phase_dx: float = 0.0,
+                        phase_dv: float = 0.0):
+        """Record every `stride`-th step of every stepping call from now on (and `record_now()`), on the device: the energies,
+        field_energy = sum(E_mesh^2) dx, spectrum rows 0..modes-1 (default: compute_E_k_spectrum's non-negative k), x / v
+        histograms of x_bins / v_bins bins, and from a phase_bins (int or (nx, nv)) histogram on [0, L] x [vmin, vmax] the
+        entropy of landau.py:19-25 and, with feq [nx, nv], the KL cost of pic_phase_kl.  A call that would hold more than
+        `capacity` records is refused before it steps.  Recording changes no particle, field or energy."""
+        self._h.record_start(**recorder_args(self.N_mesh, stride, modes, x_bins, v_bins, phase_bins, vmin, vmax, feq, capacity,
+                                             phase_dx, phase_dv))
+
+    def record_now(self):
+        """Append a record of the current state (e.g. t = 0 before the first step)."""
+        self._h.record_now()
+
+    def recorded(self) -> Record:
+        """All records held so far as a Record (they stay held until stop_recording)."""
+        c = self._h.record_config
+        if c is None:
+            raise RuntimeError("recorded(): not recording (start_recording first)")
+        return Record._from_read(self._h.record_read(), self.dt, self.L, self.N_mesh, c["vmin"], c["vmax"])
+
+    def stop_recording(self):
+        """Stop and free the records (read them with recorded() first)."""
+        self._h.record_stop()
+
+    def recording(self, **kwargs):
+        """Context manager: start_recording(**kwargs) on entry; on exit the yielded session's `.record` receives recorded()
+        and the recorder stops."""
+        return recording_session(self, **kwargs)
 
     def stream_probe(self, repeats=10):
         """GB/s of a read-2-arrays / write-2-arrays copy with the sweeps' grid on this device."""

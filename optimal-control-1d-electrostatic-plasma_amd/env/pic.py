@@ -18,6 +18,7 @@ from typing import Callable, List, Optional
 import numpy as np
 
 from .. import _abi
+from .record import Record, recorder_args, recording_session
 
 
 class PIC:
@@ -354,6 +355,43 @@ class PIC:
         self._cache["energies"] = (float(ke[0]), float(pe[0]), float(per[0]))
         info = {"KE": self._cache["energies"][0], "PE": self._cache["energies"][1], "PE_reward": self._cache["energies"][2]}
         return obs, max(1.0 - pe_pre, 0.0), False, info
+
+    # -- rollout recorder (BatchedPIC.start_recording on this object's handle) ------------------------
+    def start_recording(self, stride: int = 1, modes: Optional[int] = None, x_bins: int = 0, v_bins: int = 0, phase_bins=None,
+                        vmin: float = -25.0, vmax: float = 25.0, feq=None, capacity: int = 4096, phase_dx: float = 0.0,
+                        phase_dv: float = 0.0):
+        """BatchedPIC.start_recording for this environment.  The records belong to the current handle: once update_params
+        changes what the handle is made of, recorded() raises instead of returning records of another configuration."""
+        h = self._ensure_handle()
+        h.record_start(**recorder_args(self.N_mesh, stride, modes, x_bins, v_bins, phase_bins, vmin, vmax, feq, capacity,
+                                       phase_dx, phase_dv))
+        self._rec = (h, self._key())
+
+    def _recording_handle(self, who):
+        rec = getattr(self, "_rec", None)
+        if rec is None:
+            raise RuntimeError(f"{who}: not recording (start_recording first)")
+        if rec[0] is not self._handle or rec[1] != self._key():
+            raise RuntimeError(f"{who}: the records were lost when update_params changed the environment's configuration "
+                               "(the device handle was re-created); start_recording again")
+        return rec[0]
+
+    def record_now(self):
+        self._recording_handle("record_now").record_now()
+
+    def recorded(self) -> Record:
+        h = self._recording_handle("recorded")
+        c = h.record_config
+        return Record._from_read(h.record_read(), self.dt, self.L, self.N_mesh, c["vmin"], c["vmax"])
+
+    def stop_recording(self):
+        rec = getattr(self, "_rec", None)
+        self._rec = None
+        if rec is not None and rec[0] is self._handle:
+            rec[0].record_stop()
+
+    def recording(self, **kwargs):
+        return recording_session(self, **kwargs)
 
     def close(self):
         if self._handle is not None:
