@@ -36,6 +36,10 @@ enum { PIC_ACC_AUTO = 0,                     /* deposit accumulator: library's c
        PIC_ACC_PACKED = 2,                    /* float32 particles, CIC: (count, sum of w_r) per cell in one word     */
        PIC_ACC_F64 = 3 };                     /* float64 particles: float64 running sums in LDS (ds_add_f64)          */
 enum { PIC_CIC = 0, PIC_TSC = 1 };           /* src/env/interpolate.py:4 (CIC), :22 (TSC)     */
+enum { PIC_YOSHIDA4 = 0,                     /* time integrator of a step (pic_set_integrator), src/env/integration.py: */
+       PIC_SYMPLECTIC_EULER = 1,              /*   symplectic_4th_order (:60, the default), symplectic_euler (:50),     */
+       PIC_VERLET = 2,                        /*   verlet (:54), forward_euler (:8)                                     */
+       PIC_FORWARD_EULER = 3 };
 enum { PIC_PLACE_AUTO = 0,                   /* large states: look for x and v in two different regions of HBM (pic_placement_info) */
        PIC_PLACE_OFF = 1 };                   /* no search: x | v in one allocation                                                 */
 enum { PIC_HOST = 0, PIC_DEVICE = 1 };       /* where a caller buffer lives                   */
@@ -165,6 +169,22 @@ int pic_eval_field(pic_handle* h, const void* x, int mem_kind, const double* E_e
  * pic_step_stage(1) are refused while a staged step is open; pic_reset / pic_set_particles abandon it. */
 int pic_step_stage(pic_handle* h, int stage, const double* E_ext, int mem_kind);
 
+/* Time integrator of every later step (additive to ABI 5: a handle starts with PIC_YOSHIDA4 and nothing else changes).  Each
+ * scheme is PIC.update_state (pic.py:131-146) with symplectic_4th_order replaced by that function of src/env/integration.py,
+ * in its operand order; E = gathered mesh field + E_ext, E_ext held over the step:
+ *   PIC_SYMPLECTIC_EULER  1 force evaluation   p' = p + (1 (-E(q))) dt ; q' = q + (1 p') dt
+ *   PIC_VERLET            2                    p+ = p + (0.5 (-E(q))) dt ; q' = q + (1 p+) dt ; p' = p+ + (0.5 (-E(q'))) dt
+ *   PIC_FORWARD_EULER     1                    x' = x + dt v ; v' = v + dt (-E(x))
+ * followed by the wrap and the post-step refresh, as Yoshida-4.  Every stepping entry runs every scheme, on both schedules and
+ * with the recorder on or off; a step costs one pass over the particles (Verlet: one more per call).
+ * pic_step_stage takes stages 1..S, S = evals_per_step: stage k evaluates the force with its E_ext and makes the sweep behind
+ * it.  Between Verlet's stages 1 and 2 pic_get_particles returns (q' as drifted, not yet wrapped -- fixed32 positions are
+ * wrapped by their format --, p+), the state its reference evaluates the second force at.
+ * A change is refused (PIC_ESTATE) while a staged step is open, and drops the cached deposits as pic_invalidate does;
+ * PIC_EINVAL for an unknown scheme. */
+int pic_set_integrator(pic_handle* h, int scheme);
+int pic_get_integrator(pic_handle* h, int* scheme, int* evals_per_step);
+
 /* nsteps x PIC.update_state with the energies of every step kept, i.e. the E / PE traces PIC.simulate
  * returns (pic.py:175-223) without its particle snapshots: hist, host [nsteps][3][num_envs] float64 =
  * KE, PE, PE_reward after each step (total energy = KE + PE).  E_ext as in pic_step, constant over the steps.
@@ -253,7 +273,8 @@ int pic_phase_histogram(pic_handle* h, int nbins, double vmin, double vmax, uint
 int pic_phase_kl(pic_handle* h, int nbins, double vmin, double vmax, const double* feq, double* kl);
 
 /* Per-kernel timing with HIP events on the handle's stream (bench.py's roofline leg).
- * kinds: 0..3 = sweeps A..D, 4 = field solve. ms_sum / launches are arrays of 8. */
+ * kinds: 0..3 = sweeps A..D, 4 = field solve, 5 = auxiliary sweeps (refresh, first deposits), 6 = resident launches,
+ * 7 = the particle sweeps of the other integrators (pic_set_integrator). ms_sum / launches are arrays of 8. */
 int pic_profile(pic_handle* h, int enable);
 int pic_profile_read(pic_handle* h, double* ms_sum, int64_t* launches);
 

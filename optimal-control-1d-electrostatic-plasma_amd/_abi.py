@@ -15,14 +15,31 @@ PIC_POS_FLOAT, PIC_POS_FIXED32 = 0, 1
 PIC_ACC_AUTO, PIC_ACC_FIX64, PIC_ACC_PACKED, PIC_ACC_F64 = 0, 1, 2, 3
 PIC_CIC, PIC_TSC = 0, 1
 PIC_HOST, PIC_DEVICE = 0, 1
+PIC_YOSHIDA4, PIC_SYMPLECTIC_EULER, PIC_VERLET, PIC_FORWARD_EULER = 0, 1, 2, 3
 ABI_VERSION = 5
+
+# time integrators by the reference's function names (src/env/integration.py) -> PIC_* scheme, force evaluations per step
+INTEGRATORS = {"symplectic_4th_order": PIC_YOSHIDA4, "symplectic_euler": PIC_SYMPLECTIC_EULER, "verlet": PIC_VERLET,
+               "forward_euler": PIC_FORWARD_EULER}
+INTEGRATOR_NAMES = {v: k for k, v in INTEGRATORS.items()}
+EVALS_PER_STEP = {PIC_YOSHIDA4: 3, PIC_SYMPLECTIC_EULER: 1, PIC_VERLET: 2, PIC_FORWARD_EULER: 1}
+
+
+def integrator_id(integrator):
+    """PIC_* scheme of `integrator`: one of the reference's function names, or a function carrying one as its __name__ (so the
+    reference's own `verlet` may be passed).  Anything else raises ValueError."""
+    name = integrator if isinstance(integrator, str) else getattr(integrator, "__name__", None)
+    if name not in INTEGRATORS:
+        raise ValueError(f"integrator must be one of {sorted(INTEGRATORS)} (a name, or a function of that name), "
+                         f"not {integrator!r}")
+    return INTEGRATORS[name]
 
 # accum_dtype spellings of the Python layer -> PIC_ACC_*
 ACCUMULATORS = {None: PIC_ACC_AUTO, "auto": PIC_ACC_AUTO, "fix64": PIC_ACC_FIX64, "fixed": PIC_ACC_PACKED,
                 "packed": PIC_ACC_PACKED, "float64": PIC_ACC_F64}
 POSITION_FORMATS = {None: PIC_POS_FLOAT, "float": PIC_POS_FLOAT, "fixed32": PIC_POS_FIXED32}
 
-KIND_NAMES = ("sweep_A", "sweep_B", "sweep_C", "sweep_D", "field_solve", "sweep_aux", "resident", "")
+KIND_NAMES = ("sweep_A", "sweep_B", "sweep_C", "sweep_D", "field_solve", "sweep_aux", "resident", "sweep_integrator")
 
 
 class PicConfig(C.Structure):
@@ -66,6 +83,8 @@ SIGNATURES = {
     "pic_reset_sampled": [_vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_uint64],
     "pic_step": [_vp, _vp, C.c_int, C.c_int],
     "pic_step_stage": [_vp, C.c_int, _vp, C.c_int],
+    "pic_set_integrator": [_vp, C.c_int],
+    "pic_get_integrator": [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "pic_step_history": [_vp, _vp, C.c_int, C.c_int, _vp],
     "pic_step_snapshots": [_vp, _vp, C.c_int, C.c_int, _vp, _vp],
     "pic_get_particles": [_vp, _vp, _vp, C.c_int],
@@ -176,7 +195,8 @@ class Handle:
 
     def __init__(self, N, Ng, num_envs=1, L=50.0, n0=1.0, dt=0.1, gamma=5.0, particle_dtype="float64",
                  accum_dtype=None, interpol="CIC", device_id=0, blocks_per_env=0, env_index_base=0,
-                 position_dtype=None, placement="auto", placement_ms=0):
+                 position_dtype=None, placement="auto", placement_ms=0, integrator="symplectic_4th_order"):
+        scheme = integrator_id(integrator)
         self.lib = load()
         pd = {"float64": PIC_F64, "float32": PIC_F32}[str(np.dtype(particle_dtype))]
         # LDS mesh accumulator (include/picstep.h PIC_ACC_*).  None: the library's choice -- the packed word for
@@ -201,6 +221,8 @@ class Handle:
             msg = self.lib.pic_last_error(None)
             self._h = C.c_void_p()
             raise PicError(f"pic_create failed ({rc}): {msg.decode() if msg else ''}")
+        if scheme != PIC_YOSHIDA4:
+            self.set_integrator(scheme)
 
     def _chk(self, rc):
         if rc != 0:
@@ -245,6 +267,17 @@ class Handle:
     def invalidate(self):
         """Call after writing x / v through the device views (or call refresh())."""
         self._chk(self.lib.pic_invalidate(self._h))
+
+    def set_integrator(self, integrator):
+        """Time integrator of the later steps: a PIC_* scheme, a reference function name or a function of that name."""
+        scheme = integrator if isinstance(integrator, int) else integrator_id(integrator)
+        self._chk(self.lib.pic_set_integrator(self._h, int(scheme)))
+
+    def integrator(self):
+        """-> (reference function name, force evaluations per step)"""
+        scheme, evals = C.c_int(), C.c_int()
+        self._chk(self.lib.pic_get_integrator(self._h, C.byref(scheme), C.byref(evals)))
+        return INTEGRATOR_NAMES[scheme.value], evals.value
 
     def step(self, E_ext=None, nsteps=1):
         if E_ext is None:
@@ -389,7 +422,7 @@ class Handle:
         ms = (C.c_double * 8)()
         cnt = (C.c_int64 * 8)()
         self._chk(self.lib.pic_profile_read(self._h, ms, cnt))
-        return {KIND_NAMES[i]: (ms[i], cnt[i]) for i in range(7) if cnt[i]}
+        return {KIND_NAMES[i]: (ms[i], cnt[i]) for i in range(8) if cnt[i]}
 
     def set_actuator(self, basis_cos, basis_sin):
         bc = np.ascontiguousarray(basis_cos, dtype=np.float64)

@@ -91,7 +91,13 @@ enum Stage : int {
   // a step, which nothing of the next step's dynamics reads -- moves from sweep D, the one sweep bound by VALU issue, into the next
   // step's sweep B, which is bound by memory and reads x' anyway.  Same positions, same cells and weights, same integer sums.
   ST_B2 = 6,       // as B, and deposits its INPUT positions (the previous step's x') into the second mesh
-  ST_D2 = 7        // as D without the deposit of x' (wrap, KE, store, the next step's q1 deposit)
+  ST_D2 = 7,       // as D without the deposit of x' (wrap, KE, store, the next step's q1 deposit)
+  // The one-evaluation schemes and Stormer-Verlet (pic_set_integrator).  Their steps start from the deposit of the
+  // stored, wrapped x itself (no first drift), which the step before made as its post-step deposit: one row serves both.
+  ST_SE = 8,       // symplectic Euler: gather at x ; kick(d) ; drift(c) ; wrap ; deposit x' ; KE ; store
+  ST_FE = 9,       // forward Euler: gather at x ; drift(c) with the OLD p ; kick(d) ; wrap ; deposit x' ; KE ; store
+  ST_VK = 10,      // Verlet's closing half-kick: gather at q ; kick(d) ; wrap ; KE ; store (no deposit: the input row is x''s)
+  ST_VM = 11       // Verlet, merged: as VK, then the next step's half-kick (same field) ; drift(c) ; deposit ; store
 };
 
 // Mesh accumulators that cross a kernel boundary: per environment and node the sum of shape weights as a 64-bit

@@ -539,6 +539,225 @@ __global__ __launch_bounds__(NW * 64) void resident_kernel(typename P::X* __rest
   PIC_STAMP_LOADS(26);
 }
 
+// resident_scheme_kernel<P, A, SHAPE, PPT, NW, SCHEME>: the steps of symplectic Euler, Stormer-Verlet or forward Euler
+// (SCHEME = PIC_SYMPLECTIC_EULER / PIC_VERLET / PIC_FORWARD_EULER, pic_set_integrator) inside one workgroup, as resident_kernel
+// does Yoshida-4's.  Same LDS layout, same helpers, same integer deposits, and the particle arithmetic of the streaming sweeps
+// (pic_sweep.h: push_scheme) line for line, so particles and fields come out bit for bit as from the sweeps (KE excepted, as
+// ever).  Simpler than resident_kernel: every launch deposits its particles' x once at entry (no mesh crosses launches, no cell
+// and weights are carried), and a Verlet step solves the field of x' once for its closing half-kick and once more for the next
+// step's opening one (the merge the streaming schedule makes saves a pass over HBM; here both are LDS work).
+template <typename P, typename A, int SHAPE, int PPT, int NW, int SCHEME>
+__global__ __launch_bounds__(NW * 64) void resident_scheme_kernel(typename P::X* __restrict__ x, typename P::V* __restrict__ v,
+                                                                  ResidentIO io, SweepArgs a, InlineDoubles act_inline) {
+  constexpr int NT = NW * 64;
+  using T = typename P::W;
+  using X = typename P::X;
+  using V = typename P::V;
+  const int nsteps = io.nsteps, num_envs = io.num_envs, mode = io.mode;
+
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  const int Ng = a.Ng;
+  const int stride = Ng + 2;
+  const int R = a.R;
+  A* accA = reinterpret_cast<A*>(smem_raw);
+  A* accB = accA + (size_t)R * stride;
+  double* sb = reinterpret_cast<double*>(accB + (size_t)R * stride);
+  double* se = sb + Ng;
+  double* s2 = se + Ng;
+  double* xt_lds = s2 + Ng;
+  T* Es = reinterpret_cast<T*>(xt_lds + Ng);
+  __shared__ double ws[2 * NW], wsf[2 * NW];
+  __shared__ double slot[2], slot2[2];
+  __shared__ double a_lds[2 * kMaxFeedbackModes];
+  static_assert(sizeof(ws) + sizeof(wsf) + sizeof(slot) + sizeof(slot2) + sizeof(a_lds) == kResidentStaticLds,
+                "pic_create sizes the LDS of both resident kernels alike");
+
+  const int tid = threadIdx.x;
+  const int env = blockIdx.x;
+  const int rep = (tid >> 6) & (R - 1);
+  const Consts<P> k(a);
+  X* xe = x + (size_t)env * a.ld;
+  V* ve = v + (size_t)env * a.ld;
+  const size_t row = (size_t)env * Ng;
+  const int words = R * stride;
+  RefreshCtx rc{s2, se, slot2, ws, wsf, a_lds, xt_lds, row, env, a.N_over_L};
+  const bool has_ext = mode & RM_EXT;
+  const T half = T(0.5), one = T(1);
+  const T d_kick = SCHEME == PIC_VERLET ? half : one;          // integration.py:50-56: (c, d) = (1, 1); (1, 0.5) then (0, 0.5)
+
+  // particles: the pairs of resident_kernel (slots 2g, 2g + 1 = particles 2 (g NT + tid) and the one after it)
+  auto slot_index = [&](int s) { return 2 * ((long long)(s >> 1) * NT + tid) + (s & 1); };
+  typedef X XPair __attribute__((ext_vector_type(2)));
+  typedef V VPair __attribute__((ext_vector_type(2)));
+  X xs[PPT];
+  V vs[PPT];
+  unsigned live = 0u;
+#pragma unroll
+  for (int g = 0; g < PPT / 2; ++g) {
+    const long long i = slot_index(2 * g);
+    XPair xp = {X(0), X(0)};
+    VPair vp = {V(0), V(0)};
+    if (i < a.N) {
+      xp = *reinterpret_cast<const XPair*>(xe + i);
+      vp = *reinterpret_cast<const VPair*>(ve + i);
+      live |= (i + 1 < a.N ? 3u : 1u) << (2 * g);
+    }
+    xs[2 * g] = xp.x; xs[2 * g + 1] = xp.y;
+    vs[2 * g] = vp.x; vs[2 * g + 1] = vp.y;
+  }
+  unsigned bad = 0u;
+
+  if (has_ext && !(mode & (RM_PER_STEP | RM_FEEDBACK))) {      // a field held for the call: one copy in LDS
+    const Control ctl = io.c.ctl;
+    const double* act = (mode & RM_ACT_INLINE) ? kernarg_ptr<double>(kResidentInlineOffset) : ctl.act;
+    if (act)
+      for (int j = tid; j < Ng; j += NT)
+        xt_lds[j] = actuator_field(ctl.basis, ctl.basis + (size_t)Ng * ctl.M, act + (size_t)env * 2 * ctl.M, j, ctl.M);
+    else
+      for (int j = tid; j < Ng; j += NT) xt_lds[j] = ctl.ext[row + j];
+  }
+  // the deposit of the stored (wrapped) positions: the field of the first force evaluation
+  for (int i = tid; i < words; i += NT) accA[i] = A{};
+  for (int i = tid; i < words; i += NT) accB[i] = A{};
+  __syncthreads();
+#pragma unroll
+  for (int s = 0; s < PPT; ++s) {
+    if (live & (1u << s)) {
+      T w[3];
+      X xw;
+      int j;
+      unsigned frac;
+      locate<P, SHAPE>(xs[s], k, xw, j, w, frac, bad);
+      deposit<A, P, SHAPE>(accA + (size_t)rep * stride, j, w, frac, k.magic);
+    }
+  }
+  __syncthreads();
+
+  A* cur = accA;                 // deposit of the positions the step starts from
+  A* nxt = accB;
+  double ke = 0.0;
+  for (int step = 0; step < nsteps; ++step) {
+    ke = 0.0;
+    if (mode & RM_FEEDBACK) {    // the action of this step from the field the step before left (step 0: as it stands in memory)
+      const ResidentCtl c = RESIDENT_ARG(ResidentCtl, c);
+      const ResidentOut out = RESIDENT_ARG(ResidentOut, o);
+      Feedback fb = c.fb;
+      if (fb.act_hist) fb.act_hist += (size_t)step * num_envs * 2 * fb.M;
+      feedback_action<NW>(out.E + row, fb, env, Ng, wsf, a_lds);
+      __syncthreads();
+      for (int j = tid; j < Ng; j += NT) xt_lds[j] = actuator_field(c.ctl.basis, c.ctl.basis + (size_t)Ng * c.ctl.M, a_lds, j, c.ctl.M);
+    } else if (mode & RM_PER_STEP) {
+      const ResidentCtl c = RESIDENT_ARG(ResidentCtl, c);
+      if (c.ctl.act)
+        for (int j = tid; j < Ng; j += NT)
+          xt_lds[j] = actuator_field(c.ctl.basis, c.ctl.basis + (size_t)Ng * c.ctl.M,
+                                     c.ctl.act + (size_t)step * c.act_step + (size_t)env * 2 * c.ctl.M, j, c.ctl.M);
+      else
+        for (int j = tid; j < Ng; j += NT) xt_lds[j] = c.ctl.ext[(size_t)step * c.ext_step + row + j];
+    }
+    // the step's (first) force evaluation: field of `cur`, deposit of the drifted positions into `nxt`
+    resident_field<T, A, SHAPE, NW, false>(cur, R, stride, has_ext, Ng, a.fg, a.scale, a.n0, a.dx, sb, slot, Es, nxt, nullptr,
+                                           mode, num_envs, rc, 0.0, 0);
+#pragma unroll
+    for (int s = 0; s < PPT; ++s) {
+      if (live & (1u << s)) {
+        T w[3];
+        X xw;
+        int j;
+        unsigned frac;
+        X q = xs[s];
+        V p = vs[s];
+        locate<P, SHAPE>(q, k, xw, j, w, frac, bad);
+        const T E = gather_field<T, SHAPE>(Es, j, w);
+        if (SCHEME == PIC_FORWARD_EULER) {
+          q = drift<P>(xw, p, one, k, bad);
+          p = p + (V)((d_kick * (-E)) * k.dt);
+        } else {
+          p = p + (V)((d_kick * (-E)) * k.dt);
+          q = drift<P>(q, p, one, k, bad);
+        }
+        locate<P, SHAPE>(q, k, xw, j, w, frac, bad);
+        deposit<A, P, SHAPE>(nxt + (size_t)rep * stride, j, w, frac, k.magic);
+        if (SCHEME != PIC_VERLET) {
+          q = xw;
+          ke += (double)p * (double)p;
+        }
+        xs[s] = q;
+        vs[s] = p;
+      }
+    }
+    __syncthreads();
+    if (SCHEME == PIC_VERLET) {  // the closing half-kick at x' (no drift): field of `nxt`
+      resident_field<T, A, SHAPE, NW, false>(nxt, R, stride, has_ext, Ng, a.fg, a.scale, a.n0, a.dx, sb, slot, Es, cur, nullptr,
+                                             mode, num_envs, rc, 0.0, 0);
+#pragma unroll
+      for (int s = 0; s < PPT; ++s) {
+        if (live & (1u << s)) {
+          T w[3];
+          X xw;
+          int j;
+          unsigned frac;
+          V p = vs[s];
+          locate<P, SHAPE>(xs[s], k, xw, j, w, frac, bad);
+          const T E = gather_field<T, SHAPE>(Es, j, w);
+          p = p + (V)((d_kick * (-E)) * k.dt);
+          xs[s] = xw;
+          ke += (double)p * (double)p;
+          vs[s] = p;
+        }
+      }
+      __syncthreads();
+    }
+    A* t = cur;
+    cur = nxt;
+    nxt = t;
+
+    if ((mode & RM_RECORD) || step == nsteps - 1) {   // post-step refresh (pic.py:145-146; no external field) from `cur`
+      const ResidentOut out = RESIDENT_ARG(ResidentOut, o);
+      const double unit = ldexp(1.0, -a.fg);
+      for (int j = tid; j < Ng; j += NT) {
+        const double nj = ((double)mesh_node_sum<A, SHAPE>(cur, R, stride, Ng, a.fg, j) * unit) * a.scale;
+        out.n[row + j] = nj;
+        sb[j] = nj - a.n0;
+      }
+      __syncthreads();
+      SolveOut o{};
+      o.E = out.E; o.phi = out.phi; o.KE = out.KE; o.PE = out.PE; o.PEr = out.PEr;
+      o.hist = out.hist ? out.hist + (size_t)step * 3 * num_envs : nullptr;
+      o.num_envs = num_envs;
+      solve_block<NW>(o, env, Ng, a.dx, a.N_over_L, ke, sb, se, ws, slot);
+      __syncthreads();
+    }
+
+    if (mode & RM_SNAP) {        // as resident_kernel
+      using F = typename P::V;
+      const ResidentEdge e = RESIDENT_ARG(ResidentEdge, e);
+      F* sx = static_cast<F*>(e.snap) + ((size_t)step * 2 * num_envs + env) * (size_t)a.N;
+      F* sv = sx + (size_t)num_envs * (size_t)a.N;
+#pragma unroll
+      for (int s = 0; s < PPT; ++s) {
+        if (live & (1u << s)) {
+          const long long i = slot_index(s);
+          F xf = (F)pos_to_length<P>(xs[s], a.L);
+          if (P::kFixed && xf >= (F)a.L) xf = F(0);
+          sx[i] = xf;
+          sv[i] = vs[s];
+        }
+      }
+    }
+  }
+
+#pragma unroll
+  for (int g = 0; g < PPT / 2; ++g) {
+    if (live & (1u << (2 * g))) {
+      const long long i = slot_index(2 * g);
+      *reinterpret_cast<XPair*>(xe + i) = XPair{xs[2 * g], xs[2 * g + 1]};
+      *reinterpret_cast<VPair*>(ve + i) = VPair{vs[2 * g], vs[2 * g + 1]};
+    }
+  }
+  if (bad) atomicAdd(RESIDENT_ARG(ResidentEdge, e).bad, (unsigned long long)bad);
+}
+
 #undef RESIDENT_ARG
 
 }  // namespace

@@ -1,5 +1,6 @@
 // pic_sweep.h -- the push sweeps: in-prologue field solve, one particle through one Yoshida sub-stage, flush of the
-// LDS mesh into the global fixed-point accumulators, and sweep_kernel<P, A, SHAPE, STAGE> itself.
+// LDS mesh into the global fixed-point accumulators, and sweep_kernel<P, A, SHAPE, STAGE> itself; the stages of
+// the other integrators (push_scheme).
 #pragma once
 #include "pic_device.h"
 #include "pic_solve.h"
@@ -99,6 +100,49 @@ __device__ __forceinline__ void push_one(typename P::X& xq, typename P::V& vp, c
   vp = p;
 }
 
+// One particle through a step of symplectic or forward Euler, or a sub-stage of Stormer-Verlet (ST_SE, ST_FE, ST_VK, ST_VM;
+// integration.py:8-10, :26-58, pic_set_integrator).  Each starts from the field of the deposit of the position it reads, with
+// push_one's operand order: kick p + (d (-E)) dt, drift q + (c p) dt.  The reference skips a kick or drift whose coefficient is
+// zero; so do these (Verlet's closing half-kick has no drift at all).
+template <typename P, typename A, int SHAPE, int STAGE>
+__device__ __forceinline__ void push_scheme(typename P::X& xq, typename P::V& vp, const typename P::W* __restrict__ Es,
+                                            A* __restrict__ acc, const Consts<P>& k, double& ke, unsigned& bad) {
+  using T = typename P::W;
+  using V = typename P::V;
+  T w[3];
+  typename P::X xw;
+  int j;
+  unsigned frac;
+  typename P::X q = xq;
+  V p = vp;
+  locate<P, SHAPE>(q, k, xw, j, w, frac, bad);
+  const T E = gather_field<T, SHAPE>(Es, j, w);                 // util.py:105 / pic.py:120
+  if (STAGE == ST_FE) {
+    // integration.py:10, eta + dt grad(eta): the drift takes the velocity the step starts with.  (grad_func has wrapped eta's
+    // positions in place, util.py:51; the stored x is wrapped already, so xw is q)
+    q = drift<P>(xw, p, k.c_cur, k, bad);                        // x + (1 v) dt = x + v dt, the same bits as x + dt v
+    p = p + (V)((k.d_cur * (-E)) * k.dt);                        // v + (1 (-E)) dt = v + dt (-E)
+  } else {
+    p = p + (V)((k.d_cur * (-E)) * k.dt);                        // integration.py:32
+    if (STAGE == ST_VK || STAGE == ST_VM) {
+      q = xw;                                                    // pic.py:139 (+ util.py:51): the step ends here
+      ke += (double)p * (double)p;
+    }
+    if (STAGE == ST_VM) p = p + (V)((k.d_cur * (-E)) * k.dt);    // the next step's first half-kick: same field, second addition
+    if (STAGE != ST_VK) q = drift<P>(q, p, k.c_cur, k, bad);     // integration.py:42
+  }
+  if (STAGE != ST_VK) {
+    locate<P, SHAPE>(q, k, xw, j, w, frac, bad);
+    deposit<A, P, SHAPE>(acc, j, w, frac, k.magic);
+    if (STAGE != ST_VM) {                                        // (VM stores the drifted q, as sweep C does: the next sweep wraps it)
+      q = xw;
+      ke += (double)p * (double)p;
+    }
+  }
+  xq = q;
+  vp = p;
+}
+
 // Total of one mesh node over the R LDS replicas of a workgroup, periodic ghost slots folded in, as an integer
 // in units of 2^-fg (the unit of the global accumulators).
 template <typename A, int SHAPE>
@@ -184,13 +228,14 @@ __global__ __launch_bounds__(BLOCK) void sweep_kernel(typename P::X* __restrict_
   using XV = typename P::XV;
   using VV = typename P::VV;
   constexpr bool kIsB = (STAGE == ST_B || STAGE == ST_B2), kIsD = (STAGE == ST_D || STAGE == ST_D2);
-  constexpr bool kGather = (kIsB || STAGE == ST_C || kIsD);
+  constexpr bool kScheme = (STAGE >= ST_SE);                                   // push_scheme's stages
+  constexpr bool kGather = (kIsB || STAGE == ST_C || kIsD || kScheme);
   constexpr bool kStore = (kGather || STAGE == ST_REFRESH);
   constexpr bool kStoreV = kGather;
   constexpr bool kReadV = (STAGE != ST_PROBE);
-  constexpr bool kFirst = (STAGE != ST_D2);                                    // deposits into the first LDS mesh (-> acc_out)
+  constexpr bool kFirst = (STAGE != ST_D2 && STAGE != ST_VK);                  // deposits into the first LDS mesh (-> acc_out)
   constexpr bool kDual = (kIsD || STAGE == ST_REFRESH || STAGE == ST_B2);      // ... into the second one (-> acc_out2)
-  constexpr bool kEnergy = (kIsD || STAGE == ST_REFRESH);                      // sum of p^2 per workgroup
+  constexpr bool kEnergy = (kIsD || STAGE == ST_REFRESH || kScheme);           // sum of p^2 per workgroup
 
   // LDS: [R meshes: acc][R meshes: acc2 (dual stages)][field tile Es]; the mesh region is the scratch of the
   // prologue solve first
@@ -290,7 +335,8 @@ __global__ __launch_bounds__(BLOCK) void sweep_kernel(typename P::X* __restrict_
 #pragma unroll
     for (int c = 0; c < VEC; ++c) {
       typename P::V pv = kReadV ? vs[c] : typename P::V(0);
-      push_one<P, A, SHAPE, STAGE>(xs[c], pv, Es, acc, acc2, k, ke, bad);
+      if constexpr (kScheme) push_scheme<P, A, SHAPE, STAGE>(xs[c], pv, Es, acc, k, ke, bad);
+      else push_one<P, A, SHAPE, STAGE>(xs[c], pv, Es, acc, acc2, k, ke, bad);
       if (kReadV) vs[c] = pv;
     }
     if (kStore) {
@@ -308,7 +354,8 @@ __global__ __launch_bounds__(BLOCK) void sweep_kernel(typename P::X* __restrict_
   for (long long c = i; c < end; ++c) {       // ragged tail (fewer than VEC particles left for this lane)
     typename P::X xq = xe[c];
     typename P::V pv = kReadV ? ve[c] : typename P::V(0);
-    push_one<P, A, SHAPE, STAGE>(xq, pv, Es, acc, acc2, k, ke, bad);
+    if constexpr (kScheme) push_scheme<P, A, SHAPE, STAGE>(xq, pv, Es, acc, k, ke, bad);
+    else push_one<P, A, SHAPE, STAGE>(xq, pv, Es, acc, acc2, k, ke, bad);
     if (kStore) {
       xe[c] = xq;
       if (kStoreV) ve[c] = pv;

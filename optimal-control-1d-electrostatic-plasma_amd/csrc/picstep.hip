@@ -121,6 +121,7 @@ struct pic_handle {
   size_t res_lds = 0;
   double dx = 0, scale = 0;
   double cs[4]{}, ds[4]{};
+  int scheme = PIC_YOSHIDA4;          // time integrator of the steps (pic_set_integrator)
   hipStream_t stream = nullptr;       // the stream every call works on (own_stream, or the caller's)
   hipStream_t own_stream = nullptr;   // created by pic_create, destroyed by pic_destroy
   bool v_separate = false;            // v is an allocation of its own (large states: alloc_particles)
@@ -273,6 +274,10 @@ void launch_sweep_s(pic_handle* h, const SweepIO& io, int stage, void* x, void* 
     case ST_REFRESH: launch_sweep_t<P, A, SHAPE, ST_REFRESH>(h, io, x, v, a); break;
     case ST_B2: launch_sweep_t<P, A, SHAPE, ST_B2>(h, io, x, v, a); break;
     case ST_D2: launch_sweep_t<P, A, SHAPE, ST_D2>(h, io, x, v, a); break;
+    case ST_SE: launch_sweep_t<P, A, SHAPE, ST_SE>(h, io, x, v, a); break;
+    case ST_FE: launch_sweep_t<P, A, SHAPE, ST_FE>(h, io, x, v, a); break;
+    case ST_VK: launch_sweep_t<P, A, SHAPE, ST_VK>(h, io, x, v, a); break;
+    case ST_VM: launch_sweep_t<P, A, SHAPE, ST_VM>(h, io, x, v, a); break;
     default: launch_sweep_t<P, A, SHAPE, ST_PROBE>(h, io, x, v, a); break;
   }
 }
@@ -335,7 +340,7 @@ void launch_sweep(pic_handle* h, int stage, void* x, void* v, double c_prev, dou
   SweepArgs a;
   a.N = h->cfg.N; a.ld = h->ld; a.chunk = h->chunk; a.Ng = h->cfg.Ng; a.nblk = h->nblk; a.R = h->R;
   a.act_inline = (ctl.act && h->inline_act) ? 1 : 0;
-  const bool push = stage <= ST_D || stage == ST_B2 || stage == ST_D2;
+  const bool push = stage <= ST_D || stage == ST_B2 || stage == ST_D2 || stage >= ST_SE;
   a.reverse = push ? (h->sweep_parity ^= 1) : 0;
   a.fg = h->fg; a.magic = h->magic;
   a.S = h->S; a.sub = (long long)h->cfg.num_envs * h->cfg.Ng;
@@ -367,7 +372,9 @@ void launch_sweep(pic_handle* h, int stage, void* x, void* v, double c_prev, dou
     io.post.out.KE = h->KE; io.post.out.PE = h->PE; io.post.out.PEr = h->PEr;
     io.post.out.hist = h->post_hist_row; io.post.out.num_envs = h->cfg.num_envs;
   }
-  prof_begin(h, stage <= ST_D ? stage : (stage == ST_B2 ? (int)ST_B : (stage == ST_D2 ? (int)ST_D : 5)));
+  // (the particle sweeps of the other integrators -- Verlet's opening sweep is a sweep C -- count in the eighth kind)
+  const bool scheme_sweep = stage >= ST_SE || (stage == ST_C && h->scheme != PIC_YOSHIDA4);
+  prof_begin(h, scheme_sweep ? 7 : stage <= ST_D ? stage : (stage == ST_B2 ? (int)ST_B : (stage == ST_D2 ? (int)ST_D : 5)));
   if (h->fmt == FMT_F64) launch_sweep_p<PosF64>(h, io, stage, x, v, a);
   else if (h->fmt == FMT_F32) launch_sweep_p<PosF32>(h, io, stage, x, v, a);
   else launch_sweep_p<PosU32>(h, io, stage, x, v, a);
@@ -378,6 +385,18 @@ void launch_sweep(pic_handle* h, int stage, void* x, void* v, double c_prev, dou
 
 template <typename P, typename A, int SHAPE, int PPT, int NW>
 void launch_resident_t(pic_handle* h, const ResidentIO& io, const SweepArgs& a, const InlineDoubles& act) {
+  if (h->scheme != PIC_YOSHIDA4) {      // the other integrators: a kernel of their own (pic_resident.h: resident_scheme_kernel)
+    const dim3 grid(h->cfg.num_envs), block(NW * 64);
+    auto* x = static_cast<typename P::X*>(h->x);
+    auto* v = static_cast<typename P::V*>(h->v);
+    if (h->scheme == PIC_SYMPLECTIC_EULER)
+      hipLaunchKernelGGL((resident_scheme_kernel<P, A, SHAPE, PPT, NW, PIC_SYMPLECTIC_EULER>), grid, block, h->res_lds, h->stream, x, v, io, a, act);
+    else if (h->scheme == PIC_VERLET)
+      hipLaunchKernelGGL((resident_scheme_kernel<P, A, SHAPE, PPT, NW, PIC_VERLET>), grid, block, h->res_lds, h->stream, x, v, io, a, act);
+    else
+      hipLaunchKernelGGL((resident_scheme_kernel<P, A, SHAPE, PPT, NW, PIC_FORWARD_EULER>), grid, block, h->res_lds, h->stream, x, v, io, a, act);
+    return;
+  }
   // More environments than CUs and a slot count whose lean kernel fits 128 registers: two workgroups per CU beat
   // the 15 % the carried cell / weights save per workgroup (profiles/experiments_r2.md 5).
   // (carrying three TSC weights for 16 particles per lane would need more than 256 registers: that kernel is not even compiled,
@@ -466,8 +485,9 @@ void launch_solve(pic_handle* h, const SolveIO& io) {
   prof_end(h);
 }
 
-// the post-step refresh (pic.py:145-146, no external field: pic.py:114-117) from the deposit in ring row `slot`
-void launch_final_solve(pic_handle* h, int slot) {
+// the post-step refresh (pic.py:145-146, no external field: pic.py:114-117) from the deposit in ring row `slot`; retire = false
+// (the other integrators): the row stays, as the deposit the next step's force is solved from
+void launch_final_solve(pic_handle* h, int slot, bool retire = true) {
   SolveIO o{};
   o.acc = ring_row(h, slot);
   o.ke_part = h->ke_part; o.n = h->n; o.out.E = h->E_mesh; o.out.phi = h->phi;
@@ -475,7 +495,7 @@ void launch_final_solve(pic_handle* h, int slot) {
   o.out.hist = h->hist_row; o.out.num_envs = h->cfg.num_envs;
   o.out.fb = h->fb;
   launch_solve(h, o);
-  ring_retire(h, slot);
+  if (retire) ring_retire(h, slot);
 }
 
 void drop_cached_deposits(pic_handle* h) {
@@ -490,9 +510,15 @@ int refresh_fields(pic_handle* h) {
   drop_cached_deposits(h);
   const int f = ring_take_clean(h), qn = ring_take_clean(h);
   launch_sweep(h, ST_REFRESH, h->x, h->v, 0, 0, 0, -1, Control{}, ring_row(h, f), ring_row(h, qn));
-  launch_final_solve(h, f);
+  if (h->scheme == PIC_YOSHIDA4) {
+    launch_final_solve(h, f);
+    h->q_slot = qn;   // ST_REFRESH also deposited the next step's q1
+  } else {
+    launch_final_solve(h, f, false);
+    ring_retire(h, qn);
+    h->q_slot = f;    // the other integrators start from the deposit of x itself
+  }
   HIPCHK(h, launch_status(h));
-  h->q_slot = qn;   // ST_REFRESH also deposited the next step's q1
   return PIC_OK;
 }
 
@@ -1340,6 +1366,83 @@ static int ensure_twiddle(pic_handle* h, int rows) {
   return PIC_OK;
 }
 
+// ---- the other integrators on the streaming schedule (pic_set_integrator) ----------------------------------------
+// Between steps h->q_slot holds the deposit of the stored, wrapped x: the post-step deposit of the step before, which is also the
+// field of the next step's (first) force evaluation -- one row, no first drift to deposit.  Where it is missing (particles loaded
+// without a refresh, or a Yoshida-4 q1 dropped by a change of scheme) a probe sweep deposits x.
+static void scheme_first_deposit(pic_handle* h) {
+  if (h->q_slot >= 0) return;
+  h->q_slot = ring_take_clean(h);
+  launch_sweep(h, ST_PROBE, h->x, h->v, 0.0, 0.0, 0.0, -1, Control{}, ring_row(h, h->q_slot), nullptr);
+}
+
+// One step's sweeps under `ctl`, or its stage `only` (1..S) for pic_step_stage.  merge (Verlet, a further step follows with the
+// same external field): the closing half-kick of this step and the opening half-kick and drift of the next one are ONE sweep
+// (ST_VM), two additions in the order separate sweeps make them; *open tells the next step that its opening sweep is done.
+static void run_scheme_step(pic_handle* h, const Control& ctl, int only, bool merge, bool* open) {
+  if (h->scheme != PIC_VERLET) {
+    scheme_first_deposit(h);
+    const int f = ring_take_clean(h);
+    launch_sweep(h, h->scheme == PIC_SYMPLECTIC_EULER ? ST_SE : ST_FE, h->x, h->v, 0.0, 1.0, 1.0, h->q_slot, ctl, ring_row(h, f),
+                 nullptr);                                   // integration.py:50-51 (c = d = 1) / :8-10
+    ring_retire(h, h->q_slot);
+    launch_final_solve(h, f, false);
+    h->q_slot = f;
+    return;
+  }
+  if (only != 2 && !(open && *open)) {                       // step(c = 1, d = 0.5): kick, drift, deposit of q' (a sweep C)
+    scheme_first_deposit(h);
+    const int r = ring_take_clean(h);
+    launch_sweep(h, ST_C, h->x, h->v, 0.0, 1.0, 0.5, h->q_slot, ctl, ring_row(h, r), nullptr);
+    ring_retire(h, h->q_slot);
+    h->q_slot = r;
+  }
+  if (only == 1) return;
+  if (merge) {                                               // step(c = 0, d = 0.5), then the next step's step(c = 1, d = 0.5)
+    const int r = ring_take_clean(h);
+    launch_sweep(h, ST_VM, h->x, h->v, 0.0, 1.0, 0.5, h->q_slot, ctl, ring_row(h, r), nullptr);
+    launch_final_solve(h, h->q_slot);                        // this step's refresh: KE from the merged sweep, n and E from x''s deposit
+    h->q_slot = r;
+    *open = true;
+  } else {                                                   // step(c = 0, d = 0.5): the closing half-kick alone
+    launch_sweep(h, ST_VK, h->x, h->v, 0.0, 0.0, 0.5, h->q_slot, ctl, nullptr, nullptr);
+    launch_final_solve(h, h->q_slot, false);
+    if (open) *open = false;
+  }
+}
+
+static void advance_scheme(pic_handle* h, const StepControl& sc, int nsteps, double* hist) {
+  const int E = h->cfg.num_envs;
+  const size_t act_row = (size_t)E * 2 * sc.ctl.M;
+  h->inline_act = sc.inline_n > 0 ? &sc.inline_act : nullptr;
+  // Verlet merges where the two half-kicks of a merged sweep see one external field: held for the call.  A new field every step,
+  // or the feedback law's (whose action needs the post-step solve first), runs two sweeps per step.
+  const bool held = sc.fb.M == 0 && sc.ext_step == 0 && sc.act_step == 0;
+  bool open = false;
+  for (int s = 0; s < nsteps; ++s) {
+    Control ctl = sc.ctl;
+    if (ctl.ext) ctl.ext += (size_t)s * sc.ext_step;
+    if (ctl.act) ctl.act += (size_t)s * sc.act_step;
+    h->hist_row = hist ? hist + (size_t)s * 3 * E : nullptr;
+    if (sc.fb.M > 0) {                                       // as advance_steps
+      Feedback fb = sc.fb;
+      fb.act_out = h->act;
+      if (s == 0) hipLaunchKernelGGL(feedback_kernel, dim3(E), dim3(BLOCK), 0, h->stream, h->E_mesh, fb, h->cfg.Ng);
+      ctl.act = h->act;
+      ctl.ext = nullptr;
+      h->fb = Feedback{};
+      if (s + 1 < nsteps) {
+        h->fb = fb;
+        if (fb.act_hist) h->fb.act_hist = fb.act_hist + (size_t)(s + 1) * act_row;
+      }
+    }
+    run_scheme_step(h, ctl, 0, held && s + 1 < nsteps, &open);
+  }
+  h->hist_row = nullptr;
+  h->fb = Feedback{};
+  h->inline_act = nullptr;
+}
+
 // nsteps x PIC.update_state under `sc`, all launches enqueued, no host synchronisation.  hist: device [nsteps][3][env] record of
 // the energies, or null; snap (resident schedule only): device record of the particles.
 static int advance_steps(pic_handle* h, const StepControl& sc, int nsteps, double* hist, void* snap) {
@@ -1351,11 +1454,16 @@ static int advance_steps(pic_handle* h, const StepControl& sc, int nsteps, doubl
     ring_retire(h, h->stage_slot);
     h->q_slot = h->stage_slot = -1;
     // the q1 mesh and the carried cells the kernel leaves behind are valid only if the launch went out: after a failed one the
-    // next call must deposit q1 itself instead of taking over an unwritten block
+    // next call must deposit q1 itself instead of taking over an unwritten block (the other integrators' kernel leaves none)
     const hipError_t e = launch_status(h);
-    h->res_q1_valid = e == hipSuccess;
-    h->res_carry_valid = e == hipSuccess && h->res_carry != nullptr;
+    h->res_q1_valid = e == hipSuccess && h->scheme == PIC_YOSHIDA4;
+    h->res_carry_valid = h->res_q1_valid && h->res_carry != nullptr;
     HIPCHK(h, e);
+    return PIC_OK;
+  }
+  if (h->scheme != PIC_YOSHIDA4) {
+    advance_scheme(h, sc, nsteps, hist);
+    HIPCHK(h, launch_status(h));
     return PIC_OK;
   }
   const size_t act_row = (size_t)E * 2 * sc.ctl.M;
@@ -1472,8 +1580,9 @@ static int advance(pic_handle* h, const StepControl& sc, int nsteps, double* his
 int pic_step_stage(pic_handle* h, int stage, const double* E_ext, int mem_kind) {
   if (!h) return PIC_EINVAL;
   if (!h->has_state) return fail(h, PIC_ESTATE, "pic_step_stage: call pic_reset first");
-  if (stage < 1 || stage > 3 || stage != h->mid_stage + 1)
-    return fail(h, PIC_ESTATE, "pic_step_stage: stages run in the order 1, 2, 3");
+  const int S = h->scheme == PIC_YOSHIDA4 ? 3 : (h->scheme == PIC_VERLET ? 2 : 1);      // force evaluations per step
+  if (stage < 1 || stage > S || stage != h->mid_stage + 1)
+    return fail(h, PIC_ESTATE, "pic_step_stage: stages run in the order 1.." + std::to_string(S) + " of the handle's integrator");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   Control ctl{};
   int rc = stage_ext(h, E_ext, mem_kind, &ctl.ext);
@@ -1481,17 +1590,35 @@ int pic_step_stage(pic_handle* h, int stage, const double* E_ext, int mem_kind) 
   if (stage == 1 && h->rec.on && (int64_t)h->rec.steps.size() + records_ahead(h, 1) > h->rec.cap)
     return fail(h, PIC_ENOMEM, "pic_step_stage: the step would take the recorder past its capacity");
   h->res_q1_valid = false;           // (a resident handle steps by sweeps here: its carried q1 mesh goes stale)
-  run_stages(h, stage, stage, ctl);
-  h->mid_stage = stage == 3 ? 0 : stage;
+  if (h->scheme == PIC_YOSHIDA4) run_stages(h, stage, stage, ctl);
+  else run_scheme_step(h, ctl, S == 1 ? 0 : stage, false, nullptr);
+  h->mid_stage = stage == S ? 0 : stage;
   HIPCHK(h, hipGetLastError());
-  if (stage == 3 && h->rec.on && ++h->rec.k % h->rec.stride == 0) return record_enqueue(h);
+  if (stage == S && h->rec.on && ++h->rec.k % h->rec.stride == 0) return record_enqueue(h);
+  return PIC_OK;
+}
+
+int pic_set_integrator(pic_handle* h, int scheme) {
+  if (!h) return PIC_EINVAL;
+  if (scheme < PIC_YOSHIDA4 || scheme > PIC_FORWARD_EULER) return fail(h, PIC_EINVAL, "pic_set_integrator: unknown scheme");
+  if (h->mid_stage) return fail(h, PIC_ESTATE, "pic_set_integrator: a staged step is in progress (finish its pic_step_stage calls)");
+  if (scheme == h->scheme) return PIC_OK;
+  drop_cached_deposits(h);           // the cached deposit belongs to a scheme (Yoshida-4: q1 = x + (c1 v) dt; the others: x)
+  h->scheme = scheme;
+  return PIC_OK;
+}
+
+int pic_get_integrator(pic_handle* h, int* scheme, int* evals_per_step) {
+  if (!h) return PIC_EINVAL;
+  if (scheme) *scheme = h->scheme;
+  if (evals_per_step) *evals_per_step = h->scheme == PIC_YOSHIDA4 ? 3 : (h->scheme == PIC_VERLET ? 2 : 1);
   return PIC_OK;
 }
 
 static int check_steppable(pic_handle* h, int nsteps, const char* who) {
   if (!h->has_state) return fail(h, PIC_ESTATE, std::string(who) + ": call pic_reset first");
   if (nsteps < 0) return fail(h, PIC_EINVAL, std::string(who) + ": nsteps < 0");
-  if (h->mid_stage) return fail(h, PIC_ESTATE, std::string(who) + ": a staged step is in progress (finish pic_step_stage 1..3)");
+  if (h->mid_stage) return fail(h, PIC_ESTATE, std::string(who) + ": a staged step is in progress (finish its pic_step_stage calls)");
   if (h->rec.on && (int64_t)h->rec.steps.size() + records_ahead(h, nsteps) > h->rec.cap)
     return fail(h, PIC_ENOMEM, std::string(who) + ": the steps would take the recorder past its capacity (read and restart it, or "
                                                    "record with a larger capacity)");
@@ -2194,7 +2321,7 @@ static void record_free(pic_handle* h) {
 int pic_record_start(pic_handle* h, const pic_record_config* c) {
   if (!h || !c) return fail(h, PIC_EINVAL, "pic_record_start: null argument");
   if (h->rec.on) return fail(h, PIC_ESTATE, "pic_record_start: already recording (pic_record_stop first)");
-  if (h->mid_stage) return fail(h, PIC_ESTATE, "pic_record_start: a staged step is in progress (finish pic_step_stage 1..3)");
+  if (h->mid_stage) return fail(h, PIC_ESTATE, "pic_record_start: a staged step is in progress (finish its pic_step_stage calls)");
   const int Ng = h->cfg.Ng;
   const bool phase = c->phase_x_bins > 0 || c->phase_v_bins > 0;
   if (c->stride < 1 || c->n_modes < 0 || c->n_modes > Ng / 2 + 1 || c->x_bins < 0 || c->x_bins > 4096 || c->v_bins < 0 ||
@@ -2261,7 +2388,7 @@ int pic_record_now(pic_handle* h) {
   if (!h) return PIC_EINVAL;
   if (!h->rec.on) return fail(h, PIC_ESTATE, "pic_record_now: not recording (pic_record_start first)");
   if (!h->has_state) return fail(h, PIC_ESTATE, "pic_record_now: call pic_reset first");
-  if (h->mid_stage) return fail(h, PIC_ESTATE, "pic_record_now: a staged step is in progress (finish pic_step_stage 1..3)");
+  if (h->mid_stage) return fail(h, PIC_ESTATE, "pic_record_now: a staged step is in progress (finish its pic_step_stage calls)");
   if ((int64_t)h->rec.steps.size() >= h->rec.cap) return fail(h, PIC_ENOMEM, "pic_record_now: the recorder is full");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   return record_enqueue(h);

@@ -26,7 +26,8 @@ class PIC:
 
     def __init__(self, N: int = 40000, N_mesh: int = 400, n0: float = 1.0, L: float = 50.0, dt: float = 1.0,
                  tmin: float = 0.0, tmax: float = 50.0, gamma: float = 5.0, A: float = 0.1, n_mode: int = 4,
-                 interpol: str = "CIC", init_dist=None, device: int = 0, dtype="float64", position_dtype=None):
+                 interpol: str = "CIC", init_dist=None, device: int = 0, dtype="float64", position_dtype=None,
+                 integrator="symplectic_4th_order"):
         self.N = N
         self.N_mesh = N_mesh
         self.n0 = n0
@@ -43,6 +44,9 @@ class PIC:
         self.device = device
         self.dtype = np.dtype(dtype)
         self.position_dtype = position_dtype          # None / "float", or "fixed32" with dtype="float32" 
+        # the time integrator of update_state: a function name of src/env/integration.py, or that function
+        _abi.integrator_id(integrator)
+        self.integrator = integrator
         self._handle = None
         self._handle_key = None
         self._cache = {}
@@ -52,7 +56,7 @@ class PIC:
     # -- device plumbing ---------------------------------------------------------------------
     def _key(self):
         return (self.N, self.N_mesh, float(self.L), float(self.n0), float(self.dt), self.interpol, self.device,
-                str(self.dtype), self.position_dtype)
+                str(self.dtype), self.position_dtype, _abi.integrator_id(self.integrator))
 
     def _ensure_handle(self):
         key = self._key()
@@ -63,7 +67,8 @@ class PIC:
                     carry = self._handle.particles()
                 self._handle.close()
             self._handle = _abi.Handle(self.N, self.N_mesh, 1, self.L, self.n0, self.dt, self.gamma, self.dtype,
-                                       None, self.interpol, self.device, position_dtype=self.position_dtype)
+                                       None, self.interpol, self.device, position_dtype=self.position_dtype,
+                                       integrator=self.integrator)
             self._handle_key = key
             if carry is not None:
                 self._handle.reset(*carry)
@@ -187,6 +192,8 @@ class PIC:
         self._fields_hidden = False
 
     def update_params(self, **kwargs):
+        if kwargs.get("integrator") is not None:
+            _abi.integrator_id(kwargs["integrator"])     # ValueError before anything changes; the new key re-creates the handle
         for key in kwargs.keys():
             if hasattr(self, key) is True and kwargs[key] is not None:
                 setattr(self, key, kwargs[key])
@@ -216,7 +223,8 @@ class PIC:
         return np.concatenate([eta[self.N:, :], -force], axis=0)
 
     def update_state(self, E_external: Optional[np.ndarray] = None):
-        """pic.py:131-146: one Yoshida-4 step with an optional external mesh field (Ng,1)."""
+        """pic.py:131-146: one step of the integrator (Yoshida-4 unless chosen otherwise) with an optional external mesh
+        field (Ng,1)."""
         h = self._ensure_handle()
         if E_external is not None:
             E_external = np.asarray(E_external, dtype=np.float64).reshape(-1)
@@ -235,6 +243,20 @@ class PIC:
             return self.update_state(None)
         h = self._ensure_handle()
         x, v = self._particles()
+        scheme = _abi.integrator_id(self.integrator)
+        if scheme != _abi.PIC_YOSHIDA4:
+            # one call per force evaluation: at [x; v], and for Verlet once more at [q'; p+] (q' drifted, not yet wrapped)
+            eta = np.concatenate([x.reshape(-1, 1), v.reshape(-1, 1)], axis=0)
+            S = _abi.EVALS_PER_STEP[scheme]
+            for stage in range(1, S + 1):
+                field = input_func(eta)
+                h.step_stage(stage, None if field is None else np.asarray(field, dtype=np.float64).reshape(-1))
+                if stage < S:
+                    xs, vs = h.particles()
+                    eta = np.concatenate([xs[0].astype(np.float64).reshape(-1, 1), vs[0].astype(np.float64).reshape(-1, 1)], axis=0)
+            self._invalidate()
+            self._fields_hidden = False
+            return
         c1 = 0.5 * (1 / (2 - 2 ** (1 / 3)))                        # integration.py:62-66, same expression order
         eta = np.concatenate([x.reshape(-1, 1) + c1 * v.reshape(-1, 1) * self.dt, v.reshape(-1, 1)], axis=0)
         for stage in (1, 2, 3):
