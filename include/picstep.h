@@ -106,7 +106,10 @@ int pic_reset(pic_handle* h, const void* x0, const void* v0, int mem_kind);
  * on), x uniform on [0, L), v truncated to [-10, 10], then the velocity perturbation
  * v *= 1 + A sin(2 pi n_mode x / L) (pic.py:68) and update_density + update_E_field.  Counter-based
  * Philox generator keyed by (seed, environment): reproducible, but NOT the reference's NumPy stream --
- * the host samplers of the Python layer keep that. */
+ * the host samplers of the Python layer keep that.  Every velocity before the perturbation lies in
+ * [-10, 10] (a particle whose 63 rejection attempts all fall outside draws from the truncated normal).
+ * PIC_EINVAL for sigma < 1/sqrt(2 pi): the reference accepts with u < pdf(v), so where the peak of pdf
+ * exceeds 1 its density is min(pdf, 1), which this sampler does not reproduce -- use the host samplers. */
 int pic_reset_sampled(pic_handle* h, int kind, double a, double v0, double sigma, double A, int n_mode,
                       uint64_t seed);
 
@@ -154,7 +157,8 @@ int pic_get_cic(pic_handle* h, int env, int64_t* indx_l, int64_t* indx_r, double
 /* compute_E on arbitrary positions (src/env/util.py:73-116), used by compute_electric_energy
  * (util.py:119-131) and estimate_electric_energy (objective.py:20-35): deposit x -> solve ->
  * E_mesh (+E_ext).  Does not modify the environments' state (probes have their own deposit accumulator and
- * E_ext staging, so they may also run between pic_step_stage calls).  x: [num_envs][N] particle dtype;
+ * E_ext staging, so they may also run between pic_step_stage calls), pic_bad_count included: a non-finite
+ * probe position is deposited at x = 0 and counted nowhere (same for pic_compute_E).  x: [num_envs][N] particle dtype;
  * E_ext: NULL or [num_envs][Ng] host float64; outputs (host, [num_envs][Ng] / [num_envs], any
  * may be NULL): n, E_mesh (with E_ext added), half_sum_E2_dx = 0.5*sum(E_mesh^2)*dx. */
 int pic_eval_field(pic_handle* h, const void* x, int mem_kind, const double* E_ext,
@@ -382,7 +386,8 @@ int pic_record_read(pic_handle* h, int64_t first, int64_t count, pic_record_out*
 int pic_record_stop(pic_handle* h);                                  /* frees; the records are gone */
 
 int pic_sync(pic_handle* h);
-/* Number of particle positions found non-finite or out of range by the last sweeps (0 = healthy). */
+/* Number of particle positions found non-finite or out of range by the last sweeps (0 = healthy).  Counts the state's
+ * particles only: the positions of pic_eval_field / pic_compute_E probes never add to it. */
 int pic_bad_count(pic_handle* h, int64_t* count);
 const char* pic_last_error(pic_handle* h);   /* h may be NULL: error of the last failed pic_create */
 int pic_abi_version(void);

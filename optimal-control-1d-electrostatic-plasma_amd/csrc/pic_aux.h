@@ -183,15 +183,33 @@ __device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uin
   }
 }
 
-__device__ __forceinline__ double u01(uint32_t a, uint32_t b) {       // 53 random bits -> (0, 1)
+// 53 random bits -> (0, 1]: (bits + 0.5) 2^-53 is exact below 2^52; above, bits + 0.5 rounds to even, and for
+// bits = 2^53 - 1 up to 2^53, so the result can be exactly 1.0 (harmless to its callers: x >= L maps to 0, log(1) = 0)
+__device__ __forceinline__ double u01(uint32_t a, uint32_t b) {
   const unsigned long long bits = ((unsigned long long)a << 21) ^ ((unsigned long long)b >> 11);
   return ((double)bits + 0.5) * (1.0 / 9007199254740992.0);
 }
 
+// A draw from N(mu, sg) truncated to [-10, 10] by inverse CDF, for a particle whose 63 rejection attempts all fell outside:
+// u in (0, 1] from a counter of its own.  The interval is reflected onto the left tail (upper end b <= |lower end|), where
+// normcdf keeps its relative accuracy; below b = -37 normcdf(b) underflows and the tail is the exponential one,
+// b + log(u) / |b| (its relative error in density is O(1 / b^2)).  The result lies in [-10, 10] by construction.
+// Not inlined: normcdf / normcdfinv inside the sampler's loop took it to 256 VGPRs and 1 KB of scratch per lane.
+__device__ __noinline__ double truncated_normal(double mu, double sg, double u) {
+  double lo = (-10.0 - mu) / sg, hi = (10.0 - mu) / sg, s = 1.0;
+  if (lo > -hi) { const double t = lo; lo = -hi; hi = -t; s = -1.0; }       // now |hi| <= |lo|
+  const double plo = normcdf(lo), phi = normcdf(hi);
+  double z = (phi > 0.0) ? normcdfinv(plo + u * (phi - plo)) : hi + log(u) / fabs(hi);
+  z = fmin(fmax(z, lo), hi);                         // normcdfinv's last-bit error at the ends of the interval
+  return fmin(fmax(mu + sg * (s * z), -10.0), 10.0);
+}
+
 // kind 0: two-stream, halves at +v0 / -v0 (dist.py:70-102); kind 1: bump-on-tail, int(N/(1+a)) bulk
 // particles from N(0,1) then the beam from N(v0, sigma) (dist.py:151-189, same ordering as high_indx).
-// Velocities are truncated to [-10, 10] like the reference's uniform proposal; then v *= 1 + A sin(2 pi
-// n_mode x / L) (src/env/pic.py:68).
+// Velocities are truncated to [-10, 10] like the reference's uniform proposal: Box-Muller proposals outside are redrawn,
+// up to 63 attempts, and a particle that exhausts them draws from the truncated normal directly (truncated_normal), so
+// that no velocity leaves the support.  Then v *= 1 + A sin(2 pi n_mode x / L) (src/env/pic.py:68).  The host refuses
+// sigma < 1/sqrt(2 pi), where the reference's acceptance u < pdf(v) flattens the top of the Gaussian (include/picstep.h).
 template <typename P>
 __global__ __launch_bounds__(BLOCK) void sample_kernel(typename P::X* __restrict__ x, typename P::V* __restrict__ v,
                                                        long long N, long long ld,
@@ -209,9 +227,13 @@ __global__ __launch_bounds__(BLOCK) void sample_kernel(typename P::X* __restrict
     double xs = u01(c[0], c[1]) * L;
     if (xs >= L) xs = 0.0;
     double ua = u01(c[2], c[3]), vs = 0.0;
-    for (uint32_t attempt = 1; attempt < 64; ++attempt) {
+    for (uint32_t attempt = 1; attempt <= 64; ++attempt) {
       uint32_t d[4] = {(uint32_t)i, (uint32_t)((unsigned long long)i >> 32), attempt, 0x50494332u};
       philox4x32_10(d, k0, k1);
+      if (attempt == 64) {                         // 63 rejections (a beam far outside [-10, 10]): the truncated normal itself
+        vs = truncated_normal(mu, sg, u01(d[0], d[1]));
+        break;
+      }
       double sn, cs;
       sincospi(2.0 * u01(d[0], d[1]), &sn, &cs);
       vs = mu + sg * sqrt(-2.0 * log(ua)) * cs;

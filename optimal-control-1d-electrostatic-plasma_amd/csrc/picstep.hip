@@ -183,6 +183,8 @@ struct pic_handle {
   bool h_part_refused = false;    // ... could not be had: do not ask again
   double* h_fields = nullptr;     // pinned host staging for n | E_mesh | phi (meshes up to 256 KB each in total), or null
   unsigned long long* bad = nullptr;
+  unsigned long long* probe_bad = nullptr;   // bad + 1: where the probes count their non-finite positions (never read: pic_bad_count
+                                             // describes the state's particles, and a probe's positions are not among them)
   bool has_state = false;
   // profiling
   bool prof = false;
@@ -365,7 +367,7 @@ void launch_sweep(pic_handle* h, int stage, void* x, void* v, double c_prev, dou
   io.zero0 = z[0] >= 0 ? ring_row(h, z[0]) : nullptr;
   io.zero1 = z[1] >= 0 ? ring_row(h, z[1]) : nullptr;
   io.ke_part = h->ke_part;
-  io.bad = h->bad;
+  io.bad = out == h->probe_acc ? h->probe_bad : h->bad;
   if (post_slot >= 0) {            // sweep C also carries the previous step's post-step refresh (pic_sweep.h: SweepIO::post)
     io.post.acc = ring_row(h, post_slot);
     io.post.ke_part = h->ke_part; io.post.n = h->n; io.post.out.E = h->E_mesh; io.post.out.phi = h->phi;
@@ -543,7 +545,7 @@ int upload(pic_handle* h, void* dst_padded, const void* src, int mem_kind) {
 }
 
 // positions arrive as floats of the particle dtype; the fixed-point format converts them on the device
-int upload_positions(pic_handle* h, void* dst_padded, const void* src, int mem_kind) {
+int upload_positions(pic_handle* h, void* dst_padded, const void* src, int mem_kind, unsigned long long* bad) {
   if (h->fmt != FMT_U32) return upload(h, dst_padded, src, mem_kind);
   const float* dsrc = static_cast<const float*>(src);
   if (mem_kind == PIC_HOST) {
@@ -553,7 +555,7 @@ int upload_positions(pic_handle* h, void* dst_padded, const void* src, int mem_k
     dsrc = static_cast<const float*>(h->stage);
   }
   hipLaunchKernelGGL((positions_in_kernel<PosU32, float>), aux_grid(h, h->cfg.num_envs), dim3(BLOCK), 0, h->stream, dsrc,
-                     static_cast<unsigned*>(dst_padded), h->cfg.N, h->ld, h->cfg.L, h->bad);
+                     static_cast<unsigned*>(dst_padded), h->cfg.N, h->ld, h->cfg.L, bad);
   HIPCHK(h, hipGetLastError());
   return PIC_OK;
 }
@@ -1146,8 +1148,9 @@ int pic_create(const pic_config* cfg, pic_handle** out) {
   CREATE_CHK(hipHostMalloc((void**)&h->h_probe_pe, sbytes, hipHostMallocDefault));
   CREATE_CHK(hipMalloc((void**)&h->aux_pe, sbytes));
   CREATE_CHK(hipMemsetAsync(h->aux_pe, 0, sbytes, h->stream));
-  CREATE_CHK(hipMalloc((void**)&h->bad, sizeof(unsigned long long)));
-  CREATE_CHK(hipMemsetAsync(h->bad, 0, sizeof(unsigned long long), h->stream));
+  CREATE_CHK(hipMalloc((void**)&h->bad, 2 * sizeof(unsigned long long)));
+  CREATE_CHK(hipMemsetAsync(h->bad, 0, 2 * sizeof(unsigned long long), h->stream));
+  h->probe_bad = h->bad + 1;
   CREATE_CHK(hipStreamSynchronize(h->stream));
 #undef CREATE_CHK
   *out = h;
@@ -1221,7 +1224,7 @@ int pic_set_particles(pic_handle* h, const void* x, const void* v, int mem_kind)
   if (!h || !x || !v) return fail(h, PIC_EINVAL, "pic_set_particles: null argument");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   drop_cached_deposits(h);      // first: an upload that fails half way has still changed x, and no cached deposit may outlive that
-  int rc = upload_positions(h, h->x, x, mem_kind);
+  int rc = upload_positions(h, h->x, x, mem_kind, h->bad);
   if (rc) return rc;
   rc = upload(h, h->v, v, mem_kind);
   if (rc) return rc;
@@ -1994,7 +1997,7 @@ int pic_eval_field(pic_handle* h, const void* x, int mem_kind, const double* E_e
   }
   int rc = ensure_scratch(h);
   if (rc) return rc;
-  rc = upload_positions(h, h->scratch, x, mem_kind);
+  rc = upload_positions(h, h->scratch, x, mem_kind, h->probe_bad);
   if (rc) return rc;
   rc = probe_solve(h, E_ext, false);
   if (rc) return rc;
@@ -2012,7 +2015,7 @@ int pic_compute_E(pic_handle* h, const void* x, int mem_kind, const double* E_ex
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   int rc = ensure_scratch(h);
   if (rc) return rc;
-  rc = upload_positions(h, h->scratch, x, mem_kind);
+  rc = upload_positions(h, h->scratch, x, mem_kind, h->probe_bad);
   if (rc) return rc;
   const int E_ = h->cfg.num_envs;
   const long long N = h->cfg.N;
@@ -2225,6 +2228,11 @@ int pic_reset_sampled(pic_handle* h, int kind, double a, double v0, double sigma
                       uint64_t seed) {
   if (!h || (kind != 0 && kind != 1) || !(sigma > 0) || (kind == 1 && !(a >= 0)))
     return fail(h, PIC_EINVAL, "pic_reset_sampled: kind must be 0 (two-stream) or 1 (bump-on-tail), sigma > 0, a >= 0");
+  // the reference accepts with u < pdf(v) (dist.py:66-68): where the peak 1/sqrt(2 pi)/sigma exceeds 1 its density is
+  // min(pdf, 1), a clipped Gaussian this sampler does not draw
+  if (1.0 / sqrt(2.0 * M_PI) / sigma > 1.0)
+    return fail(h, PIC_EINVAL, "pic_reset_sampled: sigma < 1/sqrt(2 pi) (the reference's density is clipped there): "
+                               "draw on the host (env.dist) and pass the sample to pic_reset");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   resume_placement(h);
   const dim3 grid = aux_grid(h, h->cfg.num_envs, 2048);

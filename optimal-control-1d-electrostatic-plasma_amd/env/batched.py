@@ -50,7 +50,10 @@ class BatchedPIC:
         """`reinit()` for every environment with the sample drawn on the device: the distributions of the
         reference's TwoStream / BumpOnTail (same particle ordering), velocity perturbation included.  A new
         `seed` gives a new ensemble; environment e always differs from environment e'.  Not NumPy's RNG
-        stream -- use `reset(x0, v0)` with the host samplers when the reference's exact particles are wanted."""
+        stream -- use `reset(x0, v0)` with the host samplers when the reference's exact particles are wanted.
+        Velocities before the perturbation lie in [-10, 10], the support of the reference's proposal.  Raises PicError
+        for sigma < 1/sqrt(2 pi): there the reference accepts with u < pdf(v) > 1 somewhere, so its density is the
+        clipped min(pdf, 1), which the device does not draw; use the host samplers (`env.dist`) and `reset` instead."""
         self._h.reset_sampled(kind, a, v0, sigma, A, n_mode, seed)
 
     def reset_device(self, x_ptr, v_ptr):

@@ -37,6 +37,19 @@ class Case:
 
 
 
+def _planted_positions(c, rng):
+    """Positions on and next to the edges the index rule and the wrap can get wrong: +-0, L - ulp, tiny negatives, k dx
+    and its two neighbours (in the particle dtype)."""
+    W = np.dtype(c.dtype).type
+    L = W(c.L)
+    dx = W(c.L / c.Ng)
+    k = rng.integers(0, c.Ng, 24)
+    kd = (k.astype(c.dtype) * dx).astype(c.dtype)
+    edge = [W(0.0), W(-0.0), np.nextafter(L, W(0)), W(-1e-30), -np.nextafter(W(0), W(1)), W(-1e-7 * c.L * 1e-9)]
+    pts = np.concatenate([np.array(edge, dtype=c.dtype), kd, np.nextafter(kd, W(c.L)), np.nextafter(kd, W(-1))])
+    return pts
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # bounds
 # ---------------------------------------------------------------------------------------------------------------------
@@ -56,6 +69,20 @@ def _acc_kind(c):
 
 def _u(c):
     return U64 if c.dtype == "float64" else U32
+
+
+def gather_bound(c, E_mesh):
+    """|gathered - sum_k w_k(exact) E_mesh[node_k]| for the device's gather (csrc/pic_device.h: gather_field) from the mesh
+    E_mesh it holds, at one particle.  The device computes in the particle dtype W (float for float32 and fixed32 particles):
+      the mesh tile is E_mesh cast to W: |dE_k| <= u_W |E_k|, times sum|w| <= 1 + n_w w_err;
+      each weight is off by w_err (_weight_err): n_w w_err max|E|;
+      n_w products and n_w - 1 additions in W, recursive summation: (2 n_w - 1) u_W sum|w_k E_k| (+ second order).
+    With the particle dtype's store of the result (exact: the sum is already in W):
+      |dE_p| <= max|E| (n_w w_err + (1 + n_w w_err) u_W + 2 n_w u_W)."""
+    nw = 2 if c.shape == "CIC" else 3
+    we = _weight_err(c)
+    uw = _u(c)
+    return float(np.max(np.abs(E_mesh))) * (nw * we + (1 + nw * we) * uw + 2 * nw * uw)
 
 
 def _weight_err(c):

@@ -39,6 +39,14 @@ def fixed_to_length(u, L):
     return u.astype(LD) * LD(L) / TWO32
 
 
+def fixed_from_length(x, L):
+    """The 32-bit fixed-point image of lengths x: round(mod(x, L) / L 2^32) mod 2^32, the remainder exact in longdouble and
+    one rounding to the 2^-32 grid (ties to even).  Finite x only."""
+    L = LD(L)
+    r = np.mod(as_ld(x), L)
+    return (np.rint(r / L * TWO32).astype(np.uint64) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+
+
 def yoshida4_coefficients():
     """The reference's float64 coefficients (integration.py:62-75), carried exactly into longdouble."""
     cbrt2 = 2 ** (1 / 3)

@@ -14,7 +14,8 @@ import pytest
 
 import hp_reference as hp
 from conftest import record_measure
-from hp_checks import (U64, Case, _acc_kind, _fg, _ratio, _read, check_energies_of, check_push, check_stages)
+from hp_checks import (U64, Case, _acc_kind, _fg, _planted_positions, _ratio, _read, check_energies_of, check_push,
+                       check_stages)
 
 pytestmark = pytest.mark.gpu
 
@@ -81,17 +82,6 @@ CASES = _matrix()
 def _make(oc, c):
     return oc.BatchedPIC(c.envs, c.N, c.Ng, n0=c.n0, L=c.L, dt=c.dt, interpol=c.shape, dtype=c.dtype, accum_dtype=c.accum,
                          blocks_per_env=c.bpe, position_dtype=c.pos)
-
-
-def _planted_positions(c, rng):
-    W = np.dtype(c.dtype).type
-    L = W(c.L)
-    dx = W(c.L / c.Ng)
-    k = rng.integers(0, c.Ng, 24)
-    kd = (k.astype(c.dtype) * dx).astype(c.dtype)
-    edge = [W(0.0), W(-0.0), np.nextafter(L, W(0)), W(-1e-30), -np.nextafter(W(0), W(1)), W(-1e-7 * c.L * 1e-9)]
-    pts = np.concatenate([np.array(edge, dtype=c.dtype), kd, np.nextafter(kd, W(c.L)), np.nextafter(kd, W(-1))])
-    return pts
 
 
 def _initial_state(c, rng):
