@@ -385,6 +385,45 @@ int pic_record_count(pic_handle* h, int64_t* n);                     /* records 
 int pic_record_read(pic_handle* h, int64_t first, int64_t count, pic_record_out* out);   /* PIC_ESTATE when not recording */
 int pic_record_stop(pic_handle* h);                                  /* frees; the records are gone */
 
+/* Differentiable rollouts (the tape): the vector-Jacobian product of T Yoshida-4 steps from the state at pic_tape_start -- the
+ * energies KE_t, PE_t, PE_reward_t of every step ([T][3][num_envs], pic_step_history's layout) and the final particles as
+ * functions of every step's external field e_t (raw, or the actuator product of actions[t]) and of the initial particles.  The
+ * derivative is the almost-everywhere one of the device's arithmetic: the wrap has slope 1, the CIC weights slopes -+1/dx.
+ * Float64 particles and positions, PIC_ACC_FIX64, CIC and Yoshida-4 only (anything else: PIC_EINVAL, the reason in
+ * pic_last_error).  While a tape is open pic_step, pic_step_history, pic_step_snapshots, pic_step_actions[_traj],
+ * pic_step_ext_traj and pic_step_observe append to it (calls are cut behind every checkpoint step, as the recorder cuts them:
+ * the same bits as untaped); a call that would take it past max_steps is refused with PIC_ENOMEM before any step runs;
+ * pic_step_feedback, pic_step_stage, pic_reset, pic_reset_sampled, pic_set_particles, pic_set_actuator and pic_set_integrator
+ * are refused with PIC_ESTATE.  DESIGN.md 7c. */
+typedef struct pic_tape_config {
+  int64_t max_steps;               /* >= 1: steps the tape can hold */
+  int64_t checkpoint_every;        /* (x, v) kept every this many steps; 0 = the library chooses: ceil(sqrt(max_steps)), or
+                                      the interval needing the fewest bytes when that exceeds budget_bytes */
+  int64_t budget_bytes;            /* > 0: PIC_ENOMEM at pic_tape_start if the tape (checkpoints, fields, backward memory) needs more */
+} pic_tape_config;
+
+typedef struct pic_tape_info {
+  int64_t steps;                   /* steps taped so far */
+  int64_t checkpoint_every;
+  int64_t bytes;                   /* device memory the tape holds */
+  int64_t replay_mismatches;       /* particle values of the last backward's replays that differ from the forward's (0 expected) */
+  int64_t unit_retries;            /* repeated adjoint deposits (0: the unit of the adjoint deposits cannot overflow) */
+  int64_t launches;                /* kernels the last backward enqueued */
+  int64_t replay_bad_positions;    /* non-finite / out-of-range positions the last backward's replay met (0 expected) */
+} pic_tape_info;
+
+int pic_tape_start(pic_handle* h, const pic_tape_config* cfg);   /* checkpoints the current state; PIC_ESTATE if a tape is open */
+/* cot_hist [T][3][num_envs], cot_x / cot_v [num_envs][N] cotangents (each may be NULL = 0); outputs (each may be NULL):
+ * g_ext [T][num_envs][Ng], g_actions [T][num_envs][2M] = B^T g_ext (needs pic_set_actuator), g_x0 / g_v0 [num_envs][N].  All in
+ * mem_kind memory.  Asynchronous on the handle's stream for PIC_DEVICE; the handle's particles, fields, energies and cached
+ * deposits are not touched.  The tape stays open (another backward with other cotangents may follow).  With PIC_HOST the call
+ * waits and returns PIC_ESTATE if the replay differed from the taped forward (particles written through pic_device_ptrs while
+ * taping); with PIC_DEVICE read replay_mismatches from pic_tape_stats. */
+int pic_tape_backward(pic_handle* h, const double* cot_hist, const void* cot_x, const void* cot_v, int mem_kind, double* g_ext,
+                      double* g_actions, void* g_x0, void* g_v0);
+int pic_tape_stats(pic_handle* h, pic_tape_info* out);           /* all zero when no tape is open; synchronises */
+int pic_tape_stop(pic_handle* h);                                /* frees the tape */
+
 int pic_sync(pic_handle* h);
 /* Number of particle positions found non-finite or out of range by the last sweeps (0 = healthy).  Counts the state's
  * particles only: the positions of pic_eval_field / pic_compute_E probes never add to it. */

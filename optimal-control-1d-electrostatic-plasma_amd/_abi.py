@@ -68,6 +68,17 @@ class PicRecordOut(C.Structure):
                                                   "x_hist", "v_hist", "inside")]
 
 
+class PicTapeConfig(C.Structure):
+    """pic_tape_config (include/picstep.h): capacity and checkpoint interval of a differentiable rollout."""
+    _fields_ = [("max_steps", C.c_int64), ("checkpoint_every", C.c_int64), ("budget_bytes", C.c_int64)]
+
+
+class PicTapeInfo(C.Structure):
+    """pic_tape_info (include/picstep.h)."""
+    _fields_ = [(name, C.c_int64) for name in ("steps", "checkpoint_every", "bytes", "replay_mismatches", "unit_retries",
+                                                "launches", "replay_bad_positions")]
+
+
 class PicError(RuntimeError):
     pass
 
@@ -116,6 +127,10 @@ SIGNATURES = {
     "pic_record_count": [_vp, _i64p],
     "pic_record_read": [_vp, C.c_int64, C.c_int64, C.POINTER(PicRecordOut)],
     "pic_record_stop": [_vp],
+    "pic_tape_start": [_vp, C.POINTER(PicTapeConfig)],
+    "pic_tape_backward": [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp],
+    "pic_tape_stats": [_vp, C.POINTER(PicTapeInfo)],
+    "pic_tape_stop": [_vp],
     "pic_set_stream": [_vp, _vp],
     "pic_own_stream": [_vp],
     "pic_schedule": [_vp],
@@ -580,6 +595,45 @@ class Handle:
     def record_stop(self):
         self._chk(self.lib.pic_record_stop(self._h))
         self.record_config = None
+
+    # -- differentiable rollouts (pic_tape_*) -------------------------------------------------------
+    def tape_start(self, max_steps, checkpoint_every=0, budget_bytes=0):
+        cfg = PicTapeConfig(int(max_steps), int(checkpoint_every), int(budget_bytes))
+        self._chk(self.lib.pic_tape_start(self._h, C.byref(cfg)))
+
+    def tape_stats(self):
+        o = PicTapeInfo()
+        self._chk(self.lib.pic_tape_stats(self._h, C.byref(o)))
+        return {name: int(getattr(o, name)) for name, _ in PicTapeInfo._fields_}
+
+    def tape_backward(self, cot_hist=None, cot_x=None, cot_v=None, ext=True, actions=False, particles=False):
+        """Host arrays in, host arrays out: dict with g_ext [T][num_envs][Ng], g_actions [T][num_envs][2M], g_x0 / g_v0
+        [num_envs][N] (those asked for)."""
+        T = self.tape_stats()["steps"]
+        E = self.num_envs
+
+        def host(a, shape):
+            return None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(shape))
+        ch, cx, cv = host(cot_hist, (T, 3, E)), host(cot_x, (E, self.N)), host(cot_v, (E, self.N))
+        out = {}
+        if ext:
+            out["g_ext"] = np.zeros((T, E, self.Ng))
+        if actions:
+            out["g_actions"] = np.zeros((T, E, 2 * getattr(self, "max_mode", 0)))
+        if particles:
+            out["g_x0"] = np.zeros((E, self.N))
+            out["g_v0"] = np.zeros((E, self.N))
+        self._chk(self.lib.pic_tape_backward(self._h, _ptr(ch), _ptr(cx), _ptr(cv), PIC_HOST, _ptr(out.get("g_ext")),
+                                             _ptr(out.get("g_actions")), _ptr(out.get("g_x0")), _ptr(out.get("g_v0"))))
+        return out
+
+    def tape_backward_device(self, cot_hist, cot_x, cot_v, g_ext, g_actions, g_x0, g_v0):
+        """Device pointers (0 = NULL) in and out; asynchronous on the handle's stream."""
+        p = [None if not q else _ptr(int(q)) for q in (cot_hist, cot_x, cot_v, g_ext, g_actions, g_x0, g_v0)]
+        self._chk(self.lib.pic_tape_backward(self._h, p[0], p[1], p[2], PIC_DEVICE, p[3], p[4], p[5], p[6]))
+
+    def tape_stop(self):
+        self._chk(self.lib.pic_tape_stop(self._h))
 
     def stream_probe(self, repeats=10):
         g = C.c_double()

@@ -60,6 +60,7 @@
 #include "pic_resident.h"
 #include "pic_aux.h"
 #include "pic_record.h"
+#include "pic_adjoint.h"
 
 
 // ---------------------------------------------------------------------------------------------
@@ -100,6 +101,31 @@ struct Recorder {
   long long tiles_per_wg = 1;
 };
 
+
+// The tape of a differentiable rollout (pic_tape_*, pic_adjoint.h).  One device block holds the checkpoints
+// (x, v every `every` steps, the first at pic_tape_start), every step's external field and all the backward's working memory,
+// (a-bar included), so that pic_tape_backward allocates nothing.
+struct Tape {
+  bool on = false;
+  int64_t max_steps = 0, every = 1, steps = 0, nck = 0;
+  size_t bytes = 0;
+  void* block = nullptr;
+  double* ck = nullptr;               // [nck][2][env][ld] checkpoints: (x, v) before step c * every
+  double* ext = nullptr;              // [max_steps][env][Ng] e_t
+  double* seg = nullptr;              // [every + 1][2][env][ld] one segment's replayed states
+  double* F = nullptr;                // [every][3][env][Ng] its sub-stage fields
+  double* M = nullptr;                // [every][env][Ng] its post-step fields
+  double* lam = nullptr;              // [2][env][ld] lambda_q, lambda_p
+  double* cot = nullptr;              // [max_steps][3][env] energy cotangents
+  double* gext = nullptr;             // [max_steps][env][Ng] e-bar
+  double* nu = nullptr;               // [env][Ng]
+  acc_t* acc = nullptr;               // [env][Ng] zero between uses
+  unsigned long long* cmax = nullptr; // [env] zero between uses
+  unsigned long long* counters = nullptr;   // [0] replay mismatches of the last backward, [1] replay positions out of range
+  double* gact = nullptr;             // [max_steps][env][2M] a-bar (M: the actuator's modes at pic_tape_start; none without one)
+  int64_t launches = 0;               // kernels the last backward enqueued
+};
+
 struct pic_handle {
   pic_config cfg{};
   int fmt = FMT_F64;
@@ -133,6 +159,7 @@ struct pic_handle {
   PlacementStats place{};             // what the search for an (x, v) placement did, all legs together (pic_placement_stats)
   PlacementState place_state{};       // what a later leg of it needs to know (placement_leg, resume_placement)
   Recorder rec{};                     // pic_record_*: reductions recorded after every rec.stride-th step (advance, pic_step_stage)
+  Tape tape{};                        // pic_tape_*: checkpoints and external fields of a differentiable rollout (advance)
   void* x = nullptr;
   void* v = nullptr;
   void* scratch = nullptr;        // [env][ld] positions of a probe (eval_field / compute_E)
@@ -1164,7 +1191,7 @@ int pic_destroy(pic_handle* h) {
   prof_drain(h);
   for (hipEvent_t e : h->ev) hipEventDestroy(e);
   void* bufs[] = {h->rec.d, h->rec.u, h->rec.phase, h->rec.feq, h->x, h->scratch, h->stage, h->ring, h->ke_part, h->n, h->E_mesh, h->phi, h->ext, h->ext2, h->probe_ext,
-                  h->basis, h->act, h->modes, h->aux_n, h->aux_E, h->aux_pe, h->aux_phi, h->KE, h->bad, h->tw, h->traj, h->res_q1, h->res_carry};
+                  h->basis, h->act, h->modes, h->aux_n, h->aux_E, h->aux_pe, h->aux_phi, h->KE, h->bad, h->tw, h->traj, h->res_q1, h->res_carry, h->tape.block};
   for (void* b : bufs)
     if (b) hipFree(b);
   if (h->v_separate && h->v) hipFree(h->v);
@@ -1222,6 +1249,7 @@ int pic_sync(pic_handle* h) {
 
 int pic_set_particles(pic_handle* h, const void* x, const void* v, int mem_kind) {
   if (!h || !x || !v) return fail(h, PIC_EINVAL, "pic_set_particles: null argument");
+  if (h->tape.on) return fail(h, PIC_ESTATE, "pic_set_particles: refused while a tape is open (pic_tape_stop first)");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   drop_cached_deposits(h);      // first: an upload that fails half way has still changed x, and no cached deposit may outlive that
   int rc = upload_positions(h, h->x, x, mem_kind, h->bad);
@@ -1248,6 +1276,7 @@ int pic_refresh(pic_handle* h) {
 
 int pic_reset(pic_handle* h, const void* x0, const void* v0, int mem_kind) {
   if (!h) return PIC_EINVAL;
+  if (h->tape.on) return fail(h, PIC_ESTATE, "pic_reset: refused while a tape is open (pic_tape_stop first)");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   resume_placement(h);
   HIPCHK(h, hipMemsetAsync(h->bad, 0, sizeof(unsigned long long), h->stream));
@@ -1557,7 +1586,7 @@ static int64_t records_ahead(const pic_handle* h, int64_t nsteps) {
 // advance_steps with the recorder: the steps are cut behind every recorded step, which therefore ends like the last step of a
 // call (full sweep D and a solve launch of its own; resident schedule: the end of a launch) -- stepping call by call gives the
 // same bits -- and the record kernels follow it on the stream.
-static int advance(pic_handle* h, const StepControl& sc, int nsteps, double* hist, void* snap = nullptr) {
+static int advance_recorded(pic_handle* h, const StepControl& sc, int nsteps, double* hist, void* snap) {
   Recorder& r = h->rec;
   if (!r.on || nsteps <= 0) return advance_steps(h, sc, nsteps, hist, snap);
   const int E = h->cfg.num_envs;
@@ -1580,8 +1609,58 @@ static int advance(pic_handle* h, const StepControl& sc, int nsteps, double* his
   return PIC_OK;
 }
 
+// e_t of n steps of `sc` into the tape (pic_adjoint.h: tape_ext_kernel)
+static int tape_record_ext(pic_handle* h, const StepControl& sc, int n) {
+  Tape& t = h->tape;
+  TapeExtArgs a{};
+  a.ext = sc.ctl.ext; a.act = sc.ctl.act; a.basis = sc.ctl.basis;
+  a.out = t.ext + (size_t)t.steps * h->cfg.num_envs * h->cfg.Ng;
+  a.ext_step = sc.ext_step; a.act_step = sc.act_step;
+  a.Ng = h->cfg.Ng; a.M = sc.ctl.M; a.num_envs = h->cfg.num_envs;
+  a.act_inline = sc.ctl.act && sc.inline_n > 0;
+  hipLaunchKernelGGL(tape_ext_kernel, dim3(h->cfg.num_envs, n), dim3(ABLOCK), 0, h->stream, a, sc.inline_act);
+  HIPCHK(h, hipGetLastError());
+  return PIC_OK;
+}
+
+static int tape_checkpoint(pic_handle* h, int64_t c) {
+  const size_t part = (size_t)h->cfg.num_envs * h->ld;
+  double* dst = h->tape.ck + (size_t)c * 2 * part;
+  HIPCHK(h, hipMemcpyAsync(dst, h->x, part * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(dst + part, h->v, part * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  return PIC_OK;
+}
+
+// advance_recorded (and the recorder) under an open tape: the calls are cut behind every checkpoint step, as the recorder cuts
+// them behind a recorded step (same bits), each part's external fields go on the tape first and the state after a checkpoint
+// step is copied out.
+static int advance(pic_handle* h, const StepControl& sc, int nsteps, double* hist, void* snap = nullptr) {
+  Tape& t = h->tape;
+  if (!t.on || nsteps <= 0) return advance_recorded(h, sc, nsteps, hist, snap);
+  const int E = h->cfg.num_envs;
+  for (int done = 0; done < nsteps;) {
+    const int n = (int)std::min<int64_t>(t.every - t.steps % t.every, nsteps - done);
+    StepControl part = sc;
+    if (part.ctl.ext) part.ctl.ext += (size_t)done * sc.ext_step;
+    if (part.ctl.act) part.ctl.act += (size_t)done * sc.act_step;
+    int rc = tape_record_ext(h, part, n);
+    if (rc) return rc;
+    rc = advance_recorded(h, part, n, hist ? hist + (size_t)done * 3 * E : nullptr,
+                          snap ? static_cast<char*>(snap) + (size_t)done * 2 * E * (size_t)h->cfg.N * h->esz : nullptr);
+    if (rc) return rc;
+    t.steps += n;
+    done += n;
+    if (t.steps % t.every == 0) {
+      rc = tape_checkpoint(h, t.steps / t.every);
+      if (rc) return rc;
+    }
+  }
+  return PIC_OK;
+}
+
 int pic_step_stage(pic_handle* h, int stage, const double* E_ext, int mem_kind) {
   if (!h) return PIC_EINVAL;
+  if (h->tape.on) return fail(h, PIC_ESTATE, "pic_step_stage: refused while a tape is open (pic_tape_stop first)");
   if (!h->has_state) return fail(h, PIC_ESTATE, "pic_step_stage: call pic_reset first");
   const int S = h->scheme == PIC_YOSHIDA4 ? 3 : (h->scheme == PIC_VERLET ? 2 : 1);      // force evaluations per step
   if (stage < 1 || stage > S || stage != h->mid_stage + 1)
@@ -1603,6 +1682,7 @@ int pic_step_stage(pic_handle* h, int stage, const double* E_ext, int mem_kind) 
 
 int pic_set_integrator(pic_handle* h, int scheme) {
   if (!h) return PIC_EINVAL;
+  if (h->tape.on) return fail(h, PIC_ESTATE, "pic_set_integrator: refused while a tape is open (pic_tape_stop first)");
   if (scheme < PIC_YOSHIDA4 || scheme > PIC_FORWARD_EULER) return fail(h, PIC_EINVAL, "pic_set_integrator: unknown scheme");
   if (h->mid_stage) return fail(h, PIC_ESTATE, "pic_set_integrator: a staged step is in progress (finish its pic_step_stage calls)");
   if (scheme == h->scheme) return PIC_OK;
@@ -1625,6 +1705,8 @@ static int check_steppable(pic_handle* h, int nsteps, const char* who) {
   if (h->rec.on && (int64_t)h->rec.steps.size() + records_ahead(h, nsteps) > h->rec.cap)
     return fail(h, PIC_ENOMEM, std::string(who) + ": the steps would take the recorder past its capacity (read and restart it, or "
                                                    "record with a larger capacity)");
+  if (h->tape.on && h->tape.steps + nsteps > h->tape.max_steps)
+    return fail(h, PIC_ENOMEM, std::string(who) + ": the steps would take the tape past max_steps (pic_tape_start)");
   return PIC_OK;
 }
 
@@ -2077,6 +2159,7 @@ int pic_solve_poisson(pic_handle* h, const double* rhs, double* phi, double* E_m
 int pic_set_actuator(pic_handle* h, int max_mode, const double* basis_cos, const double* basis_sin) {
   if (!h || !basis_cos || !basis_sin || max_mode < 1 || max_mode > 64)
     return fail(h, PIC_EINVAL, "pic_set_actuator: need 1 <= max_mode <= 64 and both basis tables");
+  if (h->tape.on) return fail(h, PIC_ESTATE, "pic_set_actuator: refused while a tape is open (pic_tape_stop first)");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (h->basis) { hipFree(h->basis); h->basis = nullptr; }
@@ -2184,6 +2267,8 @@ int pic_step_actions_traj(pic_handle* h, const double* actions, int mem_kind, in
 
 int pic_step_feedback(pic_handle* h, int max_mode, int nsteps, double* actions_out, double* hist) {
   if (!h) return PIC_EINVAL;
+  if (h->tape.on)
+    return fail(h, PIC_ESTATE, "pic_step_feedback: refused while a tape is open (its actions depend on the state: the gradient through the law would be missing)");
   int rc = check_steppable(h, nsteps, "pic_step_feedback");
   if (rc) return rc;
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
@@ -2233,6 +2318,7 @@ int pic_reset_sampled(pic_handle* h, int kind, double a, double v0, double sigma
   if (1.0 / sqrt(2.0 * M_PI) / sigma > 1.0)
     return fail(h, PIC_EINVAL, "pic_reset_sampled: sigma < 1/sqrt(2 pi) (the reference's density is clipped there): "
                                "draw on the host (env.dist) and pass the sample to pic_reset");
+  if (h->tape.on) return fail(h, PIC_ESTATE, "pic_reset_sampled: refused while a tape is open (pic_tape_stop first)");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   resume_placement(h);
   const dim3 grid = aux_grid(h, h->cfg.num_envs, 2048);
@@ -2517,6 +2603,245 @@ int pic_bad_count(pic_handle* h, int64_t* count) {
   HIPCHK(h, hipMemcpyAsync(&c, h->bad, sizeof(c), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   *count = (int64_t)c;
+  return PIC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Differentiable rollouts (include/picstep.h: pic_tape_*; kernels: pic_adjoint.h; hook: advance)
+// ---------------------------------------------------------------------------------------------
+static AdjArgs adjoint_args(const pic_handle* h) {
+  AdjArgs a{};
+  a.N = h->cfg.N; a.ld = h->ld; a.Ng = h->cfg.Ng; a.fg = h->fg; a.magic = h->magic;
+  int b = 0;
+  while (((int64_t)1 << b) < h->cfg.N) ++b;
+  a.bitsN = b;
+  a.L = h->cfg.L; a.dx = h->dx; a.dt = h->cfg.dt; a.scale = h->scale; a.N_over_L = (double)h->cfg.N / h->cfg.L;
+  for (int i = 0; i < 4; ++i) { a.c[i] = h->cs[i]; a.d[i] = h->ds[i]; }
+  return a;
+}
+
+// bytes of a tape of max_steps steps with a checkpoint every `every` steps; *offs: the parts' offsets in its block
+static size_t tape_layout(const pic_handle* h, int64_t max_steps, int64_t every, size_t (&offs)[12]) {
+  const size_t E = h->cfg.num_envs, part = E * h->ld * sizeof(double), mesh = E * h->cfg.Ng * sizeof(double);
+  const int64_t nck = max_steps / every + 1;
+  const size_t sizes[12] = {(size_t)nck * 2 * part, (size_t)max_steps * mesh, (size_t)(every + 1) * 2 * part,
+                            (size_t)every * 3 * mesh, (size_t)every * mesh, 2 * part, (size_t)max_steps * 3 * E * sizeof(double),
+                            (size_t)max_steps * mesh, mesh, E * h->cfg.Ng * sizeof(acc_t), (E + 2) * sizeof(unsigned long long),
+                            (size_t)max_steps * E * 2 * h->act_modes * sizeof(double)};
+  size_t at = 0;
+  for (int i = 0; i < 12; ++i) {
+    offs[i] = at;
+    at += (sizes[i] + 255) & ~(size_t)255;
+  }
+  return at;
+}
+
+static void tape_free(pic_handle* h) {
+  if (h->tape.block) hipFree(h->tape.block);
+  h->tape = Tape{};
+}
+
+int pic_tape_start(pic_handle* h, const pic_tape_config* c) {
+  if (!h || !c) return fail(h, PIC_EINVAL, "pic_tape_start: null argument");
+  if (h->tape.on) return fail(h, PIC_ESTATE, "pic_tape_start: a tape is open (pic_tape_stop first)");
+  if (h->fmt != FMT_F64)
+    return fail(h, PIC_EINVAL, "pic_tape_start: the tape needs float64 particles with float64 positions (float32 and fixed32 are "
+                               "not differentiated)");
+  if (h->acc_kind != PIC_ACC_FIX64)
+    return fail(h, PIC_EINVAL, "pic_tape_start: the tape needs the 64-bit fixed-point accumulator (PIC_ACC_F64 sums depend on the "
+                               "order of the adds, so a replay would not be bitwise)");
+  if (h->cfg.interpol != PIC_CIC)
+    return fail(h, PIC_EINVAL, "pic_tape_start: the tape needs CIC (the reference's TSC weights jump at cell edges: its cost is "
+                               "not differentiable)");
+  if (h->scheme != PIC_YOSHIDA4)
+    return fail(h, PIC_EINVAL, "pic_tape_start: the tape differentiates the Yoshida-4 integrator only");
+  if (c->max_steps < 1 || c->checkpoint_every < 0 || c->budget_bytes < 0)
+    return fail(h, PIC_EINVAL, "pic_tape_start: need max_steps >= 1, checkpoint_every >= 0, budget_bytes >= 0");
+  if (!h->has_state) return fail(h, PIC_ESTATE, "pic_tape_start: call pic_reset first");
+  if (h->mid_stage) return fail(h, PIC_ESTATE, "pic_tape_start: a staged step is in progress");
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  int64_t every = c->checkpoint_every;
+  size_t offs[12];
+  if (every == 0) {
+    // about sqrt(max_steps) (checkpoints and one segment's replay weigh alike); when that exceeds budget_bytes, the interval
+    // that needs the fewest bytes
+    every = std::min<int64_t>(c->max_steps, std::max<int64_t>(1, (int64_t)std::ceil(std::sqrt((double)c->max_steps))));
+    if (c->budget_bytes > 0 && tape_layout(h, c->max_steps, every, offs) > (size_t)c->budget_bytes) {
+      size_t best = tape_layout(h, c->max_steps, every, offs);
+      for (int64_t s = 1; s <= c->max_steps; ++s) {
+        const size_t b = tape_layout(h, c->max_steps, s, offs);
+        if (b < best) { best = b; every = s; }
+      }
+    }
+  }
+  every = std::min<int64_t>(every, c->max_steps);
+  const size_t bytes = tape_layout(h, c->max_steps, every, offs);
+  if (c->budget_bytes > 0 && bytes > (size_t)c->budget_bytes)
+    return fail(h, PIC_ENOMEM, "pic_tape_start: the tape needs " + std::to_string(bytes) + " bytes, more than budget_bytes");
+  void* block = nullptr;
+  if (hipMalloc(&block, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(h, PIC_ENOMEM, "pic_tape_start: the tape (" + std::to_string(bytes) + " bytes) does not fit on the device");
+  }
+  Tape& t = h->tape;
+  t = Tape{};
+  t.block = block;
+  char* b = static_cast<char*>(block);
+  t.ck = (double*)(b + offs[0]); t.ext = (double*)(b + offs[1]); t.seg = (double*)(b + offs[2]); t.F = (double*)(b + offs[3]);
+  t.M = (double*)(b + offs[4]); t.lam = (double*)(b + offs[5]); t.cot = (double*)(b + offs[6]); t.gext = (double*)(b + offs[7]);
+  t.nu = (double*)(b + offs[8]); t.acc = (acc_t*)(b + offs[9]); t.cmax = (unsigned long long*)(b + offs[10]);
+  t.counters = t.cmax + h->cfg.num_envs;
+  t.gact = h->act_modes ? (double*)(b + offs[11]) : nullptr;
+  t.max_steps = c->max_steps; t.every = every; t.nck = c->max_steps / every + 1; t.bytes = bytes;
+  HIPCHK(h, hipMemsetAsync(b + offs[9], 0, offs[11] - offs[9], h->stream));    // acc, cmax, counters
+  int rc = tape_checkpoint(h, 0);
+  if (rc) { tape_free(h); return rc; }
+  t.on = true;
+  return PIC_OK;
+}
+
+int pic_tape_stop(pic_handle* h) {
+  if (!h) return PIC_EINVAL;
+  if (!h->tape.block) return PIC_OK;
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  const hipError_t e = hipStreamSynchronize(h->stream);
+  tape_free(h);
+  if (e != hipSuccess) return fail(h, PIC_EHIP, std::string("pic_tape_stop: ") + hipGetErrorString(e));
+  return PIC_OK;
+}
+
+int pic_tape_stats(pic_handle* h, pic_tape_info* out) {
+  if (!h || !out) return fail(h, PIC_EINVAL, "pic_tape_stats: null argument");
+  std::memset(out, 0, sizeof(*out));
+  const Tape& t = h->tape;
+  if (!t.on) return PIC_OK;
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  unsigned long long cnt[2] = {0, 0};
+  HIPCHK(h, hipMemcpyAsync(cnt, t.counters, sizeof(cnt), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  out->steps = t.steps;
+  out->checkpoint_every = t.every;
+  out->bytes = (int64_t)t.bytes;
+  out->replay_mismatches = (int64_t)cnt[0];
+  out->unit_retries = 0;              // the adjoint deposits' unit cannot overflow (pic_adjoint.h: adj_unit_exp)
+  out->replay_bad_positions = (int64_t)cnt[1];
+  out->launches = t.launches;
+  return PIC_OK;
+}
+
+// the fields of one replayed sub-stage: deposit in t.acc -> E (+ e_t) into `E_out`, the row cleared behind its read
+static void tape_solve(pic_handle* h, const double* ext, double* E_out) {
+  SolveIO io{};
+  io.acc = h->tape.acc; io.acc_clear = h->tape.acc;
+  io.out.ext = ext; io.out.E = E_out; io.out.num_envs = h->cfg.num_envs;
+  SolveArgs a{};
+  a.N = h->cfg.N; a.Ng = h->cfg.Ng; a.nblk = h->nblk; a.fg = h->fg; a.L = h->cfg.L; a.dx = h->dx; a.n0 = h->cfg.n0;
+  a.scale = h->scale; a.N_over_L = (double)h->cfg.N / h->cfg.L; a.S = 1; a.sub = (long long)h->cfg.num_envs * h->cfg.Ng;
+  hipLaunchKernelGGL(field_solve_kernel, dim3(h->cfg.num_envs), dim3(SBLOCK), h->solve_lds, h->stream, io, a);
+  ++h->tape.launches;
+}
+
+int pic_tape_backward(pic_handle* h, const double* cot_hist, const void* cot_x, const void* cot_v, int mem_kind, double* g_ext,
+                      double* g_actions, void* g_x0, void* g_v0) {
+  if (!h) return PIC_EINVAL;
+  Tape& t = h->tape;
+  if (!t.on) return fail(h, PIC_ESTATE, "pic_tape_backward: no tape is open (pic_tape_start)");
+  if (mem_kind != PIC_HOST && mem_kind != PIC_DEVICE) return fail(h, PIC_EINVAL, "pic_tape_backward: bad mem_kind");
+  if (g_actions && !t.gact)
+    return fail(h, PIC_ESTATE, "pic_tape_backward: g_actions needs an actuator set before pic_tape_start (pic_set_actuator)");
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  const int E = h->cfg.num_envs, Ng = h->cfg.Ng;
+  const int64_t T = t.steps;
+  const size_t part = (size_t)E * h->ld, mesh = (size_t)E * Ng;
+  const hipMemcpyKind in = mem_kind == PIC_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+  const hipMemcpyKind outk = mem_kind == PIC_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  const AdjArgs a = adjoint_args(h);
+  t.launches = 0;
+  double* lx = t.lam;
+  double* lv = t.lam + part;
+  HIPCHK(h, hipMemsetAsync(t.counters, 0, 2 * sizeof(unsigned long long), h->stream));
+  HIPCHK(h, hipMemsetAsync(t.gext, 0, (size_t)T * mesh * sizeof(double), h->stream));
+  HIPCHK(h, hipMemsetAsync(t.lam, 0, 2 * part * sizeof(double), h->stream));
+  if (cot_hist && T > 0) HIPCHK(h, hipMemcpyAsync(t.cot, cot_hist, (size_t)T * 3 * E * sizeof(double), in, h->stream));
+  else if (T > 0) HIPCHK(h, hipMemsetAsync(t.cot, 0, (size_t)T * 3 * E * sizeof(double), h->stream));
+  int rc = PIC_OK;
+  if (cot_x) rc = upload(h, lx, cot_x, mem_kind);
+  if (!rc && cot_v) rc = upload(h, lv, cot_v, mem_kind);
+  if (rc) return rc;
+
+  long long gx = (h->cfg.N + (long long)ABLOCK * 8 - 1) / ((long long)ABLOCK * 8);       // ~8 particles per lane
+  gx = std::max<long long>(1, std::min<long long>(gx, std::max(1, 2048 / E)));
+  const dim3 pgrid((unsigned)gx, E), mgrid(E);
+  const size_t acc_lds = (size_t)(Ng + 1) * sizeof(unsigned long long), mesh_lds = (size_t)Ng * sizeof(double);
+  const int64_t nseg = (T + t.every - 1) / t.every;
+  for (int64_t sgi = nseg - 1; sgi >= 0; --sgi) {
+    const int64_t t0 = sgi * t.every, len = std::min<int64_t>(t.every, T - t0);
+    // restore the segment's checkpoint into the replay states (never into the handle's x, v) and replay it step by step
+    HIPCHK(h, hipMemcpyAsync(t.seg, t.ck + (size_t)sgi * 2 * part, 2 * part * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    for (int64_t i = 0; i < len; ++i) {
+      const double* x = t.seg + (size_t)i * 2 * part;
+      AdjStep st{x, x + part, t.F + (size_t)i * 3 * mesh, (long long)mesh};
+      const double* e_t = t.ext + (size_t)(t0 + i) * mesh;
+      double* xo = t.seg + (size_t)(i + 1) * 2 * part;
+      hipLaunchKernelGGL(adjoint_replay_kernel<1>, pgrid, dim3(ABLOCK), acc_lds, h->stream, st, t.acc, nullptr, nullptr, a, t.counters + 1);
+      tape_solve(h, e_t, t.F + (size_t)(i * 3 + 0) * mesh);
+      hipLaunchKernelGGL(adjoint_replay_kernel<2>, pgrid, dim3(ABLOCK), acc_lds, h->stream, st, t.acc, nullptr, nullptr, a, t.counters + 1);
+      tape_solve(h, e_t, t.F + (size_t)(i * 3 + 1) * mesh);
+      hipLaunchKernelGGL(adjoint_replay_kernel<3>, pgrid, dim3(ABLOCK), acc_lds, h->stream, st, t.acc, nullptr, nullptr, a, t.counters + 1);
+      tape_solve(h, e_t, t.F + (size_t)(i * 3 + 2) * mesh);
+      hipLaunchKernelGGL(adjoint_replay_kernel<4>, pgrid, dim3(ABLOCK), acc_lds, h->stream, st, t.acc, xo, xo + part, a, t.counters + 1);
+      tape_solve(h, nullptr, t.M + (size_t)i * mesh);
+      t.launches += 4;
+    }
+    // the replayed end of the segment against the state the forward left there
+    const double* end = t.seg + (size_t)len * 2 * part;
+    const double* want_x = sgi + 1 < nseg ? t.ck + (size_t)(sgi + 1) * 2 * part : (const double*)h->x;
+    const double* want_v = sgi + 1 < nseg ? want_x + part : (const double*)h->v;
+    hipLaunchKernelGGL(tape_compare_kernel, pgrid, dim3(ABLOCK), 0, h->stream, end, end + part, want_x, want_v, h->cfg.N, h->ld, t.counters);
+    ++t.launches;
+    // reverse through the segment
+    for (int64_t i = len - 1; i >= 0; --i) {
+      const double* x = t.seg + (size_t)i * 2 * part;
+      const AdjStep st{x, x + part, t.F + (size_t)i * 3 * mesh, (long long)mesh};
+      const double* cot = t.cot + (size_t)(t0 + i) * 3 * E;
+      double* ge = t.gext + (size_t)(t0 + i) * mesh;
+      hipLaunchKernelGGL(adjoint_mesh_kernel, mgrid, dim3(SBLOCK), mesh_lds, h->stream, nullptr, t.cmax, t.M + (size_t)i * mesh, cot, ge, t.nu, a, E);
+      hipLaunchKernelGGL(adjoint_pass_kernel<3>, pgrid, dim3(ABLOCK), 0, h->stream, st, t.nu, cot, lx, lv, t.cmax, a, E);
+      hipLaunchKernelGGL(adjoint_deposit_kernel<3>, pgrid, dim3(ABLOCK), acc_lds, h->stream, st, lv, t.cmax, t.acc, a);
+      hipLaunchKernelGGL(adjoint_mesh_kernel, mgrid, dim3(SBLOCK), mesh_lds, h->stream, t.acc, t.cmax, nullptr, nullptr, ge, t.nu, a, E);
+      hipLaunchKernelGGL(adjoint_pass_kernel<2>, pgrid, dim3(ABLOCK), 0, h->stream, st, t.nu, nullptr, lx, lv, t.cmax, a, E);
+      hipLaunchKernelGGL(adjoint_deposit_kernel<2>, pgrid, dim3(ABLOCK), acc_lds, h->stream, st, lv, t.cmax, t.acc, a);
+      hipLaunchKernelGGL(adjoint_mesh_kernel, mgrid, dim3(SBLOCK), mesh_lds, h->stream, t.acc, t.cmax, nullptr, nullptr, ge, t.nu, a, E);
+      hipLaunchKernelGGL(adjoint_pass_kernel<1>, pgrid, dim3(ABLOCK), 0, h->stream, st, t.nu, nullptr, lx, lv, t.cmax, a, E);
+      hipLaunchKernelGGL(adjoint_deposit_kernel<1>, pgrid, dim3(ABLOCK), acc_lds, h->stream, st, lv, t.cmax, t.acc, a);
+      hipLaunchKernelGGL(adjoint_mesh_kernel, mgrid, dim3(SBLOCK), mesh_lds, h->stream, t.acc, t.cmax, nullptr, nullptr, ge, t.nu, a, E);
+      hipLaunchKernelGGL(adjoint_pass_kernel<0>, pgrid, dim3(ABLOCK), 0, h->stream, st, t.nu, nullptr, lx, lv, t.cmax, a, E);
+      t.launches += 11;
+    }
+    HIPCHK(h, hipGetLastError());
+  }
+  if (g_ext && T > 0) HIPCHK(h, hipMemcpyAsync(g_ext, t.gext, (size_t)T * mesh * sizeof(double), outk, h->stream));
+  if (g_actions && T > 0) {
+    hipLaunchKernelGGL(adjoint_actions_kernel, dim3(E, (unsigned)T), dim3(ABLOCK), 0, h->stream, t.gext, h->basis,
+                       mem_kind == PIC_HOST ? t.gact : g_actions, Ng, h->act_modes, E);
+    ++t.launches;
+    if (mem_kind == PIC_HOST)
+      HIPCHK(h, hipMemcpyAsync(g_actions, t.gact, (size_t)T * E * 2 * h->act_modes * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  }
+  if (g_x0) rc = download(h, g_x0, lx, mem_kind);
+  if (!rc && g_v0) rc = download(h, g_v0, lv, mem_kind);
+  if (rc) return rc;
+  HIPCHK(h, hipGetLastError());
+  if (mem_kind == PIC_HOST) {
+    // host outputs: the call waits anyway, so a replay that left the forward's trajectory (particles written through
+    // pic_device_ptrs while taping) is an error here, not only a count in pic_tape_stats
+    unsigned long long cnt = 0;
+    HIPCHK(h, hipMemcpyAsync(&cnt, t.counters, sizeof(cnt), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (cnt)
+      return fail(h, PIC_ESTATE, "pic_tape_backward: the replay differs from the taped forward in " + std::to_string(cnt) +
+                                     " particle values (were the particles written while the tape was open?): the gradient is not valid");
+  }
   return PIC_OK;
 }
 

@@ -345,5 +345,86 @@ class BatchedPIC:
         """update_density + update_E_field on the current particles (also valid after a write through the views)."""
         self._h.refresh()
 
+    # -- differentiable rollouts (pic_tape_*, DESIGN.md 7c) ------------------------------------------
+    def start_tape(self, max_steps: int, checkpoint_every: int = 0, budget_bytes: int = 0):
+        """Open a tape: the steps that follow (step, step_history, step_actions[_traj], step_ext_traj, step_observe, up to
+        max_steps of them) can be differentiated by `backward`.  checkpoint_every = 0: about sqrt(max_steps).  Float64 particles,
+        CIC, Yoshida-4 and the fixed-point accumulator only.  Resets, feedback steps, staged steps and changes of actuator or
+        integrator are refused while it is open."""
+        self._h.tape_start(max_steps, checkpoint_every, budget_bytes)
+
+    def stop_tape(self):
+        self._h.tape_stop()
+
+    def tape_stats(self):
+        """steps, checkpoint_every, bytes, replay_mismatches (of the last backward; 0 expected), unit_retries, launches."""
+        return self._h.tape_stats()
+
+    def taping(self, max_steps: int, checkpoint_every: int = 0, budget_bytes: int = 0):
+        """Context manager: start_tape(...) on entry, stop_tape() on exit."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def cm():
+            self.start_tape(max_steps, checkpoint_every, budget_bytes)
+            try:
+                yield self
+            finally:
+                self.stop_tape()
+        return cm()
+
+    def backward(self, d_KE=None, d_PE=None, d_PE_reward=None, d_x=None, d_v=None):
+        """Vector-Jacobian product of the taped steps: cotangents d_KE, d_PE, d_PE_reward [T, num_envs] of the energy traces
+        (step_history's) and d_x, d_v [num_envs, N] of the final particles (each None = 0).  Returns a dict: "ext" [T, num_envs,
+        N_mesh] (gradient with respect to every step's external field), "actions" [T, num_envs, 2*max_mode] (= B^T ext; with an
+        actuator), "x0", "v0" [num_envs, N] (initial particles).  NumPy arrays, or float64 CUDA tensors if any cotangent is one
+        (then stream-ordered like step_actions_traj_torch).  Raises PicError if the replay of the taped steps does not reproduce
+        the forward bit for bit (particles written through the views while taping): such a gradient would be wrong."""
+        T = self._h.tape_stats()["steps"]
+        E = self.num_envs
+        given = [a for a in (d_KE, d_PE, d_PE_reward, d_x, d_v) if a is not None]
+        on_device = any(hasattr(a, "is_cuda") and a.is_cuda for a in given)
+        M = getattr(self, "max_mode", 0)
+        if not on_device:
+            hist = None
+            if any(a is not None for a in (d_KE, d_PE, d_PE_reward)):
+                hist = np.zeros((T, 3, E))
+                for k, a in enumerate((d_KE, d_PE, d_PE_reward)):
+                    if a is not None:
+                        hist[:, k] = np.asarray(a, dtype=np.float64).reshape(T, E)
+            out = self._h.tape_backward(hist, d_x, d_v, ext=True, actions=M > 0, particles=True)
+            res = {"ext": out["g_ext"], "x0": out["g_x0"], "v0": out["g_v0"]}
+            if M > 0:
+                res["actions"] = out["g_actions"]
+            return res
+        import torch
+        dev = f"cuda:{self.device}"
+        f64 = dict(dtype=torch.float64, device=dev)
+        hist = None
+        if any(a is not None for a in (d_KE, d_PE, d_PE_reward)):
+            hist = torch.zeros((T, 3, E), **f64)
+            for k, a in enumerate((d_KE, d_PE, d_PE_reward)):
+                if a is not None:
+                    hist[:, k] = torch.as_tensor(a, **f64).reshape(T, E)
+        cx = None if d_x is None else torch.as_tensor(d_x, **f64).reshape(E, self.N).contiguous()
+        cv = None if d_v is None else torch.as_tensor(d_v, **f64).reshape(E, self.N).contiguous()
+        res = {"ext": torch.empty((T, E, self.N_mesh), **f64), "x0": torch.empty((E, self.N), **f64),
+               "v0": torch.empty((E, self.N), **f64)}
+        if M > 0:
+            res["actions"] = torch.empty((T, E, 2 * M), **f64)
+        shared = getattr(self, "_torch_stream", None) is not None
+        if not shared:
+            torch.cuda.current_stream(self.device).synchronize()
+
+        def ptr(t):
+            return 0 if t is None or t.numel() == 0 else t.data_ptr()
+        self._h.tape_backward_device(ptr(hist), ptr(cx), ptr(cv), ptr(res["ext"]), ptr(res.get("actions")), ptr(res["x0"]),
+                                     ptr(res["v0"]))
+        st = self._h.tape_stats()                    # (waits for the backward)
+        if st["replay_mismatches"]:
+            raise _abi.PicError(f"backward: the replay differs from the taped forward in {st['replay_mismatches']} particle values "
+                                "(were the particles written while the tape was open?): the gradient is not valid")
+        return res
+
     def close(self):
         self._h.close()

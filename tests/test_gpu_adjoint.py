@@ -1,0 +1,374 @@
+"""Differentiable rollouts on the device (pic_tape_*): the adjoint against the autograd oracle
+(tests/hp_adjoint.py), against finite differences of the device's own forward, bitwise reproducibility, no perturbation of the
+forward, the C contract and the torch Function."""
+import numpy as np
+import pytest
+
+import hp_adjoint as ha
+from conftest import record_measure
+from oracle import pic_oracle as po
+
+pytestmark = pytest.mark.gpu
+
+L = 50.0
+M = 3
+PARITY_BOUND = 1.3e-11        # 100 x the largest relative error measured against the oracle, 1.3e-13 (ceiling 1e-9)
+
+
+def _make(E, N, Ng, seed=1, **kw):
+    import ocplasma_amd as oc
+    from ocplasma_amd.env.batched import BatchedPIC
+    env = BatchedPIC(E, N, Ng, L=L, dt=0.1, **kw)
+    X = np.empty((E, N))
+    V = np.empty((E, N))
+    for e in range(E):
+        X[e], V[e] = po.synthetic_bump_on_tail(N, L, seed=seed + 7 * e)
+    env.reset(X, V)
+    env.set_actuator(oc.E_field(L, Ng, M))
+    return env, X, V
+
+
+def _actions(T, E, seed):
+    return np.random.default_rng(seed).uniform(-0.5, 0.5, (T, E, 2 * M))
+
+
+def _ext_of(actions, Ng):
+    T, E, _ = actions.shape
+    out = np.empty((T, E, Ng))
+    for t in range(T):
+        for e in range(E):
+            out[t, e] = po.actuator_field(L, Ng, M, actions[t, e, :M], actions[t, e, M:]).ravel()
+    return out
+
+
+def _bt(g_ext, Ng):
+    bc, bs = po.actuator_basis(L, Ng, M)
+    return np.concatenate([g_ext @ bc, g_ext @ bs], axis=-1)
+
+
+def _taped_grad(env, actions, cot_hist, cot_x=None, cot_v=None, every=0):
+    env.start_tape(actions.shape[0], every)
+    env.step_actions_traj(actions)
+    T, E = actions.shape[:2]
+    out = env._h.tape_backward(cot_hist, cot_x, cot_v, ext=True, actions=True, particles=True)
+    st = env.tape_stats()
+    env.stop_tape()
+    assert st["replay_mismatches"] == 0, st
+    assert st["unit_retries"] == 0, st
+    return out
+
+
+def _rel(a, b):
+    return float(np.linalg.norm(np.ravel(a - b)) / max(np.linalg.norm(np.ravel(b)), 1e-300))
+
+
+@pytest.mark.parametrize("E,N,Ng,Ts", [(4, 3000, 64, (1, 5, 20)), (2, 20000, 250, (5, 20)), (1, 40000, 128, (5,))])
+def test_adjoint_matches_autograd(E, N, Ng, Ts):
+    for T in Ts:
+        env, X, V = _make(E, N, Ng, seed=T)
+        x0, v0 = env.particles()
+        rng = np.random.default_rng(T)
+        a = _actions(T, E, T)
+        cot = rng.standard_normal((T, 3, E))
+        cx, cv = rng.standard_normal((E, N)), rng.standard_normal((E, N))
+        out = _taped_grad(env, a, cot, cx, cv)
+        S = ha.Setup(N, Ng, L, 1.0, env.dt)
+        ext = _ext_of(a, Ng)
+        worst = 0.0
+        for e in range(E):
+            ge, gx, gv = ha.autograd_vjp(x0[e], v0[e], ext[:, e], S, cot[:, :, e], cx[e], cv[e])
+            errs = (_rel(out["g_ext"][:, e], ge), _rel(out["g_actions"][:, e], _bt(ge, Ng)), _rel(out["g_x0"][e], gx),
+                    _rel(out["g_v0"][e], gv))
+            worst = max(worst, *errs)
+        record_measure(f"adjoint.parity.E{E}_N{N}_Ng{Ng}_T{T}", worst)
+        assert worst < PARITY_BOUND, worst
+        env.close()
+
+
+def _cost(env, X, V, a, lam):
+    env.reset(X, V)
+    _, _, per = env.step_actions_traj(a, history=True)
+    return per.sum(axis=0) + lam * (a ** 2).sum(axis=(0, 2)) * L / 4
+
+
+def _cost_grad(env, X, V, a, lam):
+    env.reset(X, V)
+    T, E = a.shape[:2]
+    cot = np.zeros((T, 3, E))
+    cot[:, 2] = 1.0
+    out = _taped_grad(env, a, cot)
+    return out["g_actions"] + lam * a * L / 2
+
+
+def test_directional_derivative_matches_device_finite_differences():
+    E, N, Ng, T, lam = 2, 5000, 64, 10, 0.1
+    env, X, V = _make(E, N, Ng, seed=3)
+    a = _actions(T, E, 3)
+    g = _cost_grad(env, X, V, a, lam)
+    rng = np.random.default_rng(9)
+    eps = 1e-6
+    worst = 0.0
+    for _ in range(3):
+        d = rng.standard_normal(a.shape)
+        fd = (_cost(env, X, V, a + eps * d, lam).sum() - _cost(env, X, V, a - eps * d, lam).sum()) / (2 * eps)
+        an = float((g * d).sum())
+        worst = max(worst, abs(fd - an) / abs(an))
+    record_measure("adjoint.fd_rel_eps1e-6", worst)
+    assert worst < 1.5e-7, worst         # 100 x the 1.5e-9 measured at eps = 1e-6 (ceiling 1e-5)
+    env.close()
+
+
+def test_one_gradient_step_lowers_the_cost_in_every_environment():
+    E, N, Ng, T, lam = 4, 5000, 250, 20, 0.1
+    env, X, V = _make(E, N, Ng, seed=5)
+    a = _actions(T, E, 5)
+    J0 = _cost(env, X, V, a, lam)
+    g = _cost_grad(env, X, V, a, lam)
+    eta = 1e-3 * J0 / (g ** 2).sum(axis=(0, 2))
+    J1 = _cost(env, X, V, a - eta[None, :, None] * g, lam)
+    assert np.all(J1 < J0), (J0, J1)
+    env.close()
+
+
+def test_gradients_are_bitwise_reproducible():
+    E, N, Ng, T = 3, 3000, 64, 7
+    a = _actions(T, E, 2)
+    rng = np.random.default_rng(2)
+    cot = rng.standard_normal((T, 3, E))
+    cx, cv = rng.standard_normal((E, N)), rng.standard_normal((E, N))
+
+    def run(every=0, **kw):
+        env, X, V = _make(E, N, Ng, seed=2, **kw)
+        out = _taped_grad(env, a, cot, cx, cv, every)
+        sched = env._h.schedule()
+        env.close()
+        return out, sched
+
+    ref, s0 = run()
+    variants = [run()[0], run(blocks_per_env=1)[0], run(blocks_per_env=2)[0], run(blocks_per_env=-1)[0]]
+    variants += [run(every=k)[0] for k in (1, 3, T)]
+    assert s0 == "resident" and run(blocks_per_env=2)[1] == "streaming"
+    for out in variants:
+        for k in ref:
+            assert np.array_equal(out[k], ref[k]), k
+    # environment 1 alone
+    import ocplasma_amd as oc
+    from ocplasma_amd.env.batched import BatchedPIC
+    x1, v1 = po.synthetic_bump_on_tail(N, L, seed=2 + 7)
+    one = BatchedPIC(1, N, Ng, L=L, dt=0.1)
+    one.reset(np.asarray(x1)[None], np.asarray(v1)[None])
+    one.set_actuator(oc.E_field(L, Ng, M))
+    alone = _taped_grad(one, a[:, 1:2], cot[:, :, 1:2], cx[1:2], cv[1:2])
+    for k in ("g_ext", "g_actions"):
+        assert np.array_equal(alone[k][:, 0], ref[k][:, 1]), k
+    for k in ("g_x0", "g_v0"):
+        assert np.array_equal(alone[k][0], ref[k][1]), k
+    one.close()
+
+
+@pytest.mark.parametrize("blocks", [0, 2])
+def test_taping_does_not_perturb_the_forward(blocks):
+    E, N, Ng, T = 2, 3000, 64, 6
+    a = _actions(T, E, 4)
+    envs = [_make(E, N, Ng, seed=4, blocks_per_env=blocks)[0] for _ in range(2)]
+    taped, twin = envs
+    for env in envs:
+        env._h.record_start(stride=2, n_modes=2, x_bins=8, capacity=16)
+    taped.start_tape(T + 3, 2)
+    h1 = taped.step_actions_traj(a, history=True)
+    h2 = twin.step_actions_traj(a, history=True)
+    for u, w in zip(h1, h2):
+        assert np.array_equal(u, w)
+    for u, w in zip(taped.particles() + taped.fields() + taped.energies(), twin.particles() + twin.fields() + twin.energies()):
+        assert np.array_equal(u, w)
+    taped.backward(d_PE_reward=np.ones((T, E)))
+    for u, w in zip(taped.particles() + taped.fields() + taped.energies(), twin.particles() + twin.fields() + twin.energies()):
+        assert np.array_equal(u, w)
+    # the handle keeps stepping like the twin
+    for env in envs:
+        env.step_actions(a[0], 3)
+    for u, w in zip(taped.particles() + taped.fields() + taped.energies(), twin.particles() + twin.fields() + twin.energies()):
+        assert np.array_equal(u, w)
+    # same sweep grid and the same cut points (tape interval = recorder stride): every record equal, KE included
+    r1, r2 = taped._h.record_read(), twin._h.record_read()
+    for k in r1:
+        assert np.array_equal(np.asarray(r1[k]), np.asarray(r2[k]), equal_nan=True), k
+    taped.stop_tape()
+    for env in envs:
+        env.close()
+
+
+def test_tape_contract():
+    from ocplasma_amd._abi import PicError
+    env, X, V = _make(1, 2000, 64, seed=6)
+    env.start_tape(4, 2)
+    refused = [lambda: env.step_feedback(1), lambda: env._h.step_stage(1), lambda: env.reset(X, V),
+               lambda: env.reset_sampled("two-stream"), lambda: env._h.set_particles(X, V),
+               lambda: env._h.set_actuator(np.zeros((64, 2)), np.zeros((64, 2))),
+               lambda: env._h.set_integrator("verlet")]
+    for f in refused:
+        with pytest.raises(PicError, match="-3"):
+            f()
+    x_before = env.particles()[0].copy()
+    with pytest.raises(PicError, match="-4"):
+        env.step(None, 5)                                            # past max_steps: refused before any step
+    assert np.array_equal(env.particles()[0], x_before)
+    env.step(None, 4)
+    assert env.tape_stats()["steps"] == 4
+    with pytest.raises(PicError, match="-3"):
+        env.start_tape(2)
+    env.stop_tape()
+    with pytest.raises(PicError, match="-4"):
+        env.start_tape(10 ** 6, 1, budget_bytes=1 << 20)
+    with pytest.raises(PicError, match="-4"):
+        env.start_tape(1 << 40)
+    env.close()
+    for kw, what in (({"dtype": "float32"}, "float64"), ({"accum_dtype": "float64"}, "order"), ({"interpol": "TSC"}, "TSC")):
+        from ocplasma_amd.env.batched import BatchedPIC
+        e2 = BatchedPIC(1, 2000, 64, L=L, dt=0.1, **kw)
+        e2.reset_sampled("two-stream")
+        with pytest.raises(PicError, match=what):
+            e2.start_tape(3)
+        e2.close()
+    from ocplasma_amd.env.batched import BatchedPIC
+    e3 = BatchedPIC(1, 2000, 64, L=L, dt=0.1, integrator="verlet")
+    e3.reset_sampled("two-stream")
+    with pytest.raises(PicError, match="Yoshida"):
+        e3.start_tape(3)
+    e3.close()
+
+
+@pytest.mark.parametrize("E", [2, 6])
+def test_adjoint_matches_autograd_for_every_kind_of_control(E):
+    """Raw fields (a trajectory, and one held by pic_step / step_observe), held actions given on the host (E = 2: inside the
+    kernel arguments; E = 6: staged to the device), held actions on the device and step_observe's action: every way a step's
+    e_t reaches the tape, against the oracle."""
+    import torch
+    N, Ng = 3000, 64
+    env, X, V = _make(E, N, Ng, seed=20 + E)
+    x0, v0 = env.particles()
+    rng = np.random.default_rng(E)
+    raw = 0.05 * rng.standard_normal((5, E, Ng))
+    acts = _actions(3, E, E)
+    T = 9
+    env.start_tape(T, 3)
+    env.step_ext_traj(raw[0:2])                                     # t = 0, 1
+    env.step(raw[2], 2)                                             # t = 2, 3 (held field)
+    env.step_actions(acts[0], 2)                                    # t = 4, 5 (held host action)
+    env.step_actions_torch(torch.tensor(acts[1], dtype=torch.float64, device="cuda"))   # t = 6 (device action)
+    env.step_observe(actions=acts[2])                               # t = 7
+    env.step_observe(E_external=raw[3])                             # t = 8
+    ext = np.concatenate([raw[0:2], raw[2:3], raw[2:3], _ext_of(acts[[0, 0, 1, 2]], Ng), raw[3:4]])
+    cot = rng.standard_normal((T, 3, E))
+    cx, cv = rng.standard_normal((E, N)), rng.standard_normal((E, N))
+    out = env._h.tape_backward(cot, cx, cv, ext=True, actions=False, particles=True)
+    st = env.tape_stats()
+    env.stop_tape()
+    assert st["steps"] == T and st["replay_mismatches"] == 0 and st["replay_bad_positions"] == 0, st
+    S = ha.Setup(N, Ng, L, 1.0, env.dt)
+    worst = 0.0
+    for e in range(E):
+        ge, gx, gv = ha.autograd_vjp(x0[e], v0[e], ext[:, e], S, cot[:, :, e], cx[e], cv[e])
+        worst = max(worst, _rel(out["g_ext"][:, e], ge), _rel(out["g_x0"][e], gx), _rel(out["g_v0"][e], gv))
+    record_measure(f"adjoint.parity.controls_E{E}", worst)
+    assert worst < PARITY_BOUND, worst
+    env.close()
+
+
+def test_backward_refuses_a_replay_that_left_the_forward():
+    """Particles written through the device views while taping: the replay no longer reproduces the forward, and the gradient
+    is refused instead of returned."""
+    from ocplasma_amd._abi import PicError
+    env, X, V = _make(2, 3000, 64, seed=12)
+    a = _actions(4, 2, 12)
+    env.start_tape(4)
+    env.step_actions_traj(a)
+    env.sync()
+    import torch
+    env.torch_views()["x"][0, 10] += 1e-3
+    torch.cuda.synchronize()
+    with pytest.raises(PicError, match="replay differs"):
+        env.backward(d_PE_reward=np.ones((4, 2)))
+    assert env.tape_stats()["replay_mismatches"] > 0
+    env.stop_tape()
+    env.close()
+
+
+def test_default_interval_follows_the_budget():
+    """checkpoint_every = 0: ceil(sqrt(T)) when the budget allows it, else the interval needing the fewest bytes."""
+    from ocplasma_amd._abi import PicError
+    env, X, V = _make(2, 3000, 64, seed=13)
+    T = 16
+    sizes = {}
+    for k in range(1, T + 1):
+        env.start_tape(T, k)
+        sizes[k] = env.tape_stats()["bytes"]
+        env.stop_tape()
+    best = min(sizes, key=lambda k: (sizes[k], k))
+    env.start_tape(T)
+    assert env.tape_stats()["checkpoint_every"] == 4
+    env.stop_tape()
+    assert sizes[best] < sizes[4], sizes
+    env.start_tape(T, 0, budget_bytes=sizes[best])
+    st = env.tape_stats()
+    assert st["checkpoint_every"] == best and st["bytes"] == sizes[best], st
+    env.stop_tape()
+    with pytest.raises(PicError, match="-4"):
+        env.start_tape(T, 0, budget_bytes=sizes[best] - 1)
+    env.close()
+
+
+
+def test_torch_rollout_matches_tape_and_passes_gradcheck():
+    import torch
+    from ocplasma_amd._abi import PicError
+    from ocplasma_amd.env import grad
+    E, N, Ng, T = 2, 3000, 64, 5
+    env, X, V = _make(E, N, Ng, seed=8)
+    a = _actions(T, E, 8)
+    at = torch.tensor(a, dtype=torch.float64, device="cuda", requires_grad=True)
+    ke, pe, per = grad.rollout(env, at)
+    (per.sum() + 0.5 * ke.sum()).backward()
+    env.stop_tape()
+    env.reset(X, V)
+    cot = np.zeros((T, 3, E))
+    cot[:, 2] = 1.0
+    cot[:, 0] = 0.5
+    ref = _taped_grad(env, a, cot)
+    assert np.array_equal(at.grad.cpu().numpy(), ref["g_actions"])
+    # a stale backward raises
+    env.reset(X, V)
+    at2 = torch.tensor(a, dtype=torch.float64, device="cuda", requires_grad=True)
+    ke, pe, per = grad.rollout(env, at2)
+    with pytest.raises(PicError, match="-4"):
+        env.step_actions(a[0])                                       # the rollout's tape is full: no step can slip in
+    env.stop_tape()
+    env.reset(X, V)                                                  # the environment moves on
+    with pytest.raises(PicError, match="moved on"):
+        per.sum().backward()
+    env.stop_tape()
+    env.close()
+    # gradcheck at 2 x N = 500, T = 3: every evaluation on an environment of its own (gradcheck evaluates the function again
+    # between the forward and the backward it checks, which would make a shared environment's tape stale)
+    def f(u):
+        env, _, _ = _make(2, 500, 32, seed=9)
+        return grad.rollout(env, u)
+    u = torch.tensor(_actions(3, 2, 9), dtype=torch.float64, device="cuda", requires_grad=True)
+    assert torch.autograd.gradcheck(f, (u,), eps=1e-6, atol=1e-6, rtol=1e-4)
+    # raw fields: rollout_ext against the tape of step_ext_traj
+    env, X, V = _make(2, 3000, 64, seed=14)
+    e = 0.05 * np.random.default_rng(14).standard_normal((4, 2, 64))
+    et = torch.tensor(e, dtype=torch.float64, device="cuda", requires_grad=True)
+    ke, pe, per = grad.rollout_ext(env, et)
+    (pe.sum() - ke.sum()).backward()
+    env.stop_tape()
+    env.reset(X, V)
+    cot = np.zeros((4, 3, 2))
+    cot[:, 1] = 1.0
+    cot[:, 0] = -1.0
+    env.start_tape(4)
+    env.step_ext_traj(e)
+    ref = env._h.tape_backward(cot)
+    env.stop_tape()
+    assert np.array_equal(et.grad.cpu().numpy(), ref["g_ext"])
+    env.close()
