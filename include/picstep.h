@@ -248,6 +248,19 @@ int pic_step_ext_traj(pic_handle* h, const double* E_ext_traj, int mem_kind, int
  * pic_step_actions gives. */
 int pic_step_feedback(pic_handle* h, int max_mode, int nsteps, double* actions_out, double* hist);
 
+/* nsteps of a linear feedback law with a gain of its own: before every step the modes
+ * m = (Re E_1..Re E_M, Im E_1..Im E_M), M = max_mode, of the mesh field the previous step left (the current E_mesh for the first
+ * step) are pic_step_feedback's, and the actuator coefficients are a = G m with the environment's own G:
+ *     a[i] = sum over k = 0..2M-1 with G[i][k] != 0, in ascending k, of G[i][k] * m[k]
+ * in float64, the first such product starting the sum and every further one added to it (no fused multiply-add); a row without
+ * a non-zero entry gives +0.  With G = G0 = diag(-1 x M, +1 x M) every step is pic_step_feedback's, bit for bit.
+ * gain: [num_envs][2M][2M] float64, row-major, in mem_kind memory (read in stream order).  max_mode: as pic_step_feedback.
+ * actions_out, modes_out: NULL, or host [nsteps][num_envs][2M]: a and m of every step; hist as above.  Accepted wherever
+ * pic_step_feedback is (every format, interpolation and integrator, recorder on or off) and, unlike it, while a tape is open:
+ * the taped steps keep their m_t and the call's gain, so that pic_tape_backward[_feedback] differentiates through the law. */
+int pic_step_feedback_gain(pic_handle* h, int max_mode, const double* gain, int mem_kind, int nsteps, double* actions_out,
+                           double* modes_out, double* hist);
+
 /* One iteration of a Gym-style loop in ONE call with ONE synchronisation (src/control/rl/ddpg.py:421-468, ppo.py, sac.py:
  * env.update_state(E) -> next_state = env.get_state() -> reward from the new state's electric energy): nsteps steps under
  * the given control -- E_ext [num_envs][Ng] on the mesh (util.py:102-103) or actions [num_envs][2*max_mode] actuator
@@ -391,8 +404,11 @@ int pic_record_stop(pic_handle* h);                                  /* frees; t
  * derivative is the almost-everywhere one of the device's arithmetic: the wrap has slope 1, the CIC weights slopes -+1/dx.
  * Float64 particles and positions, PIC_ACC_FIX64, CIC and Yoshida-4 only (anything else: PIC_EINVAL, the reason in
  * pic_last_error).  While a tape is open pic_step, pic_step_history, pic_step_snapshots, pic_step_actions[_traj],
- * pic_step_ext_traj and pic_step_observe append to it (calls are cut behind every checkpoint step, as the recorder cuts them:
- * the same bits as untaped); a call that would take it past max_steps is refused with PIC_ENOMEM before any step runs;
+ * pic_step_ext_traj, pic_step_observe and pic_step_feedback_gain append to it (calls are cut behind every checkpoint step, as
+ * the recorder cuts them: the same bits as untaped); a call that would take it past max_steps is refused with PIC_ENOMEM before
+ * any step runs.  A gain-law call keeps its gain [num_envs][2M][2M] once and every step's modes m_t; the first one also
+ * allocates the record of the law's steps (3 [max_steps][num_envs][2M] plus one [num_envs][Ng] of float64); both count in
+ * `bytes` and against budget_bytes (PIC_ENOMEM beyond it);
  * pic_step_feedback, pic_step_stage, pic_reset, pic_reset_sampled, pic_set_particles, pic_set_actuator and pic_set_integrator
  * are refused with PIC_ESTATE.  DESIGN.md 7c. */
 typedef struct pic_tape_config {
@@ -421,6 +437,14 @@ int pic_tape_start(pic_handle* h, const pic_tape_config* cfg);   /* checkpoints 
  * taping); with PIC_DEVICE read replay_mismatches from pic_tape_stats. */
 int pic_tape_backward(pic_handle* h, const double* cot_hist, const void* cot_x, const void* cot_v, int mem_kind, double* g_ext,
                       double* g_actions, void* g_x0, void* g_v0);
+/* pic_tape_backward of a tape that holds steps of pic_step_feedback_gain, with cotangents on their modes: cot_modes
+ * [T][num_envs][2M] (NULL = 0; ignored on the other steps); modes_out [T][num_envs][2M]: the taped m_t (0 on the other steps).
+ * The gradient includes the state path through the law (pic_tape_backward does too, with cot_modes = 0): a-bar_t = B^T e-bar_t,
+ * m-bar_t = G^T a-bar_t + cot_modes_t, and J^T m-bar_t is a cotangent on the field step t started from.  g_actions holds
+ * a-bar_t on every step; the gradient with respect to the gain of a call is sum over its steps of a-bar_t m_t^T (per environment),
+ * which the caller forms from g_actions and modes_out. */
+int pic_tape_backward_feedback(pic_handle* h, const double* cot_hist, const void* cot_x, const void* cot_v, const double* cot_modes,
+                               int mem_kind, double* g_ext, double* g_actions, void* g_x0, void* g_v0, double* modes_out);
 int pic_tape_stats(pic_handle* h, pic_tape_info* out);           /* all zero when no tape is open; synchronises */
 int pic_tape_stop(pic_handle* h);                                /* frees the tape */
 

@@ -117,6 +117,7 @@ SIGNATURES = {
     "pic_step_actions_traj": [_vp, _vp, C.c_int, C.c_int, _vp],
     "pic_step_ext_traj": [_vp, _vp, C.c_int, C.c_int, _vp, _vp],
     "pic_step_feedback": [_vp, C.c_int, C.c_int, _vp, _vp],
+    "pic_step_feedback_gain": [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp],
     "pic_step_observe": [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp],
     "pic_get_modes": [_vp, C.c_int, _vp, _vp, C.c_int],
     "pic_phase_histogram": [_vp, C.c_int, C.c_double, C.c_double, _vp],
@@ -129,6 +130,7 @@ SIGNATURES = {
     "pic_record_stop": [_vp],
     "pic_tape_start": [_vp, C.POINTER(PicTapeConfig)],
     "pic_tape_backward": [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp],
+    "pic_tape_backward_feedback": [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp],
     "pic_tape_stats": [_vp, C.POINTER(PicTapeInfo)],
     "pic_tape_stop": [_vp],
     "pic_set_stream": [_vp, _vp],
@@ -497,6 +499,36 @@ class Handle:
             out.update(KE=hist[:, 0], PE=hist[:, 1], PE_reward=hist[:, 2])
         return out or None
 
+    def step_feedback_gain(self, gain, nsteps, actions=False, modes=False, history=False, device_ptr=None):
+        """nsteps of the gain law a = G m on the device (pic_step_feedback_gain; the actuator's max_mode).  gain: host
+        [num_envs][2M][2M] float64, or device_ptr (an address of such an array on the device; gain is then ignored).  Returns a
+        dict with "actions", "modes" [nsteps][num_envs][2M] and / or "KE", "PE", "PE_reward" [nsteps][num_envs] as asked for;
+        with none of them the call is asynchronous and returns None."""
+        k = int(nsteps)
+        E, n = self.num_envs, 2 * self.max_mode
+        if device_ptr is None:
+            g = np.ascontiguousarray(np.asarray(gain, dtype=np.float64))
+            if g.shape != (E, n, n):
+                raise ValueError(f"gain must be [num_envs, 2*max_mode, 2*max_mode] = {(E, n, n)}, got {g.shape}")
+            gp, kind = _ptr(g), PIC_HOST
+        else:
+            gp, kind = _ptr(int(device_ptr)), PIC_DEVICE
+        act = np.empty((k, E, n)) if actions else None
+        md = np.empty((k, E, n)) if modes else None
+        hist = self._hist_out(k, history)
+        first = self.tape_stats()["steps"] if getattr(self, "_taping", False) else None
+        self._chk(self.lib.pic_step_feedback_gain(self._h, self.max_mode, gp, kind, k, _ptr(act), _ptr(md), _ptr(hist)))
+        if first is not None and k > 0:
+            self._law_calls.append((first, k))
+        out = {}
+        if act is not None:
+            out["actions"] = act
+        if md is not None:
+            out["modes"] = md
+        if hist is not None:
+            out.update(KE=hist[:, 0], PE=hist[:, 1], PE_reward=hist[:, 2])
+        return out or None
+
     def step_observe(self, E_ext=None, actions=None, nsteps=1, particles=True, out=None):
         """One Gym-style iteration in one call with one synchronisation (pic_step_observe): nsteps steps under E_ext
         [num_envs][Ng] or actions [num_envs][2*max_mode] (or neither), then -> (x, v, KE, PE, PE_reward) of the new state
@@ -600,6 +632,7 @@ class Handle:
     def tape_start(self, max_steps, checkpoint_every=0, budget_bytes=0):
         cfg = PicTapeConfig(int(max_steps), int(checkpoint_every), int(budget_bytes))
         self._chk(self.lib.pic_tape_start(self._h, C.byref(cfg)))
+        self._taping, self._law_calls = True, []       # (first step, steps) of every gain-law call on the tape
 
     def tape_stats(self):
         o = PicTapeInfo()
@@ -634,6 +667,31 @@ class Handle:
 
     def tape_stop(self):
         self._chk(self.lib.pic_tape_stop(self._h))
+        self._taping, self._law_calls = False, []
+
+    def tape_law_calls(self):
+        """(first step, steps) of every pic_step_feedback_gain call on the open tape, in order."""
+        return list(getattr(self, "_law_calls", []))
+
+    def tape_backward_feedback(self, cot_hist=None, cot_x=None, cot_v=None, cot_modes=None):
+        """pic_tape_backward_feedback with host arrays: dict with g_ext, g_actions, modes [T][num_envs][2M], g_x0, g_v0."""
+        T = self.tape_stats()["steps"]
+        E, n = self.num_envs, 2 * self.max_mode
+
+        def host(a, shape):
+            return None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(shape))
+        ch, cx, cv, cm = host(cot_hist, (T, 3, E)), host(cot_x, (E, self.N)), host(cot_v, (E, self.N)), host(cot_modes, (T, E, n))
+        out = {"g_ext": np.zeros((T, E, self.Ng)), "g_actions": np.zeros((T, E, n)), "modes": np.zeros((T, E, n)),
+               "g_x0": np.zeros((E, self.N)), "g_v0": np.zeros((E, self.N))}
+        self._chk(self.lib.pic_tape_backward_feedback(self._h, _ptr(ch), _ptr(cx), _ptr(cv), _ptr(cm), PIC_HOST, _ptr(out["g_ext"]),
+                                                      _ptr(out["g_actions"]), _ptr(out["g_x0"]), _ptr(out["g_v0"]),
+                                                      _ptr(out["modes"])))
+        return out
+
+    def tape_backward_feedback_device(self, cot_hist, cot_x, cot_v, cot_modes, g_ext, g_actions, g_x0, g_v0, modes):
+        """Device pointers (0 = NULL) in and out; asynchronous on the handle's stream."""
+        p = [None if not q else _ptr(int(q)) for q in (cot_hist, cot_x, cot_v, cot_modes, g_ext, g_actions, g_x0, g_v0, modes)]
+        self._chk(self.lib.pic_tape_backward_feedback(self._h, p[0], p[1], p[2], p[3], PIC_DEVICE, p[4], p[5], p[6], p[7], p[8]))
 
     def stream_probe(self, repeats=10):
         g = C.c_double()

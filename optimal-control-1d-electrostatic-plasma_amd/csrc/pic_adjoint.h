@@ -11,6 +11,9 @@
 //   adjoint_deposit_kernel the adjoint deposit mu_K = sum_i (-d_K dt lambda_p,i) W(q_K,i) in 64-bit fixed point
 //   adjoint_mesh_kernel    mu (or the refresh cotangent) -> nu = K^T m = -K (m - mean m), and e-bar_t += mu
 //   adjoint_actions_kernel the actuator part: a-bar_t = B^T e-bar_t
+//   law_adjoint_kernel     a step of the gain law a = G m(E): E-bar = J^T (G^T a-bar + m-bar), a cotangent on the
+//                          field the step started from, which the refresh of the step before adds to its m
+//   adjoint_start_kernel   lambda_x0 += s W'(x_0) . nu: the field at the start of the tape, read by a first law step
 #pragma once
 #include "pic_device.h"
 #include "pic_solve.h"
@@ -228,12 +231,13 @@ __global__ __launch_bounds__(ABLOCK) void adjoint_deposit_kernel(AdjStep s, cons
 
 // One workgroup per environment.  Deposit mode (acc != null): m = mu = acc * unit (the row is cleared behind the read, and the
 // environment's max with it), e-bar_t += mu.  Refresh mode (acc == null): m = (a_PE N/L + a_PEr) dx M for the post-step field M
-// and the cotangents of step t, cot [3][env].  Either way nu = K^T m = -K (m - mean m) (the field operator is antisymmetric: the
-// central difference is, the periodic Poisson inverse is symmetric, and both are circulant), through the forward's scans.
+// and the cotangents of step t, cot [3][env] (M null: m = 0), plus `add` [env][Ng] if given (the E-bar of a gain-law step that
+// reads this field).  Either way nu = K^T m = -K (m - mean m) (the field operator is antisymmetric: the central difference is,
+// the periodic Poisson inverse is symmetric, and both are circulant), through the forward's scans.
 __global__ __launch_bounds__(SBLOCK) void adjoint_mesh_kernel(acc_t* __restrict__ acc, unsigned long long* __restrict__ cmax,
                                                               const double* __restrict__ M, const double* __restrict__ cot,
                                                               double* __restrict__ gext, double* __restrict__ nu, AdjArgs a,
-                                                              int num_envs) {
+                                                              int num_envs, const double* __restrict__ add) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   double* sb = reinterpret_cast<double*>(smem_raw);
   __shared__ double ws[2 * SWAVES];
@@ -252,9 +256,10 @@ __global__ __launch_bounds__(SBLOCK) void adjoint_mesh_kernel(acc_t* __restrict_
       loc += mu;
     }
   } else {
-    const double f = (cot[(size_t)num_envs + env] * a.N_over_L + cot[2 * (size_t)num_envs + env]) * a.dx;
+    const double f = M ? (cot[(size_t)num_envs + env] * a.N_over_L + cot[2 * (size_t)num_envs + env]) * a.dx : 0.0;
     for (int j = tid; j < Ng; j += SBLOCK) {
-      const double m = f * M[row + j];
+      double m = M ? f * M[row + j] : 0.0;
+      if (add) m = m + add[row + j];
       sb[j] = m;
       loc += m;
     }
@@ -308,6 +313,59 @@ __global__ __launch_bounds__(ABLOCK) void adjoint_actions_kernel(const double* _
     for (int j = 0; j < Ng; ++j) s += b[(size_t)j * M + mm] * g[j];
     gact[((size_t)t * num_envs + env) * 2 * M + m] = s;
   }
+}
+
+// E-bar [env][Ng] of one gain-law step (a = G m, m = (Re E_1..Re E_M, Im E_1..Im E_M) of the field E the step started from,
+// pic_device.h: feedback_action): a-bar = B^T e-bar (in another order than adjoint_actions_kernel's), m-bar = G^T a-bar + cot_m (ascending i),
+// E-bar_j = 2/Ng sum_m (m-bar_Re,m cos - m-bar_Im,m sin)(2 pi m j / Ng) (mesh_mode's map, spectrum.py:16).  Grid (num_envs).
+__global__ __launch_bounds__(ABLOCK) void law_adjoint_kernel(const double* __restrict__ gext, const double* __restrict__ basis,
+                                                             const double* __restrict__ gain, const double* __restrict__ cot_m,
+                                                             const double* __restrict__ tw, int rows, double* __restrict__ Ebar,
+                                                             int Ng, int M) {
+  __shared__ double sa[2 * kMaxFeedbackModes], sm[2 * kMaxFeedbackModes];
+  const int env = blockIdx.x, n = 2 * M, tid = threadIdx.x, lane = tid & 63;
+  const double* g = gext + (size_t)env * Ng;
+  for (int m = tid >> 6; m < n; m += AWAVES) {                    // one wave per coefficient, a fixed-order wave sum
+    const double* b = basis + (m < M ? 0 : (size_t)Ng * M);
+    const int mm = m < M ? m : m - M;
+    double s = 0.0;
+    for (int j = lane; j < Ng; j += 64) s += b[(size_t)j * M + mm] * g[j];
+    s = wave_sum(s);
+    if (lane == 0) sa[m] = s;
+  }
+  __syncthreads();
+  const double* G = gain + (size_t)env * n * n;
+  for (int k = tid; k < n; k += ABLOCK) {
+    double s = 0.0;
+    for (int i = 0; i < n; ++i) s += G[(size_t)i * n + k] * sa[i];
+    sm[k] = s + cot_m[(size_t)env * n + k];
+  }
+  __syncthreads();
+  const double c = 2.0 / Ng;
+  for (int j = tid; j < Ng; j += ABLOCK) {
+    double s = 0.0;
+    for (int m = 0; m < M; ++m) {
+      s += sm[m] * tw[(size_t)m * Ng + j];
+      s -= sm[M + m] * tw[((size_t)rows + m) * Ng + j];
+    }
+    Ebar[(size_t)env * Ng + j] = c * s;
+  }
+}
+
+// lambda_x += s W'(x) . nu at positions x [env][ld] (the tape's first checkpoint): the deposit of the field the tape started from
+__global__ __launch_bounds__(ABLOCK) void adjoint_start_kernel(const double* __restrict__ x, const double* __restrict__ nu,
+                                                               double* __restrict__ lx, AdjArgs a) {
+  const int env = blockIdx.y, Ng = a.Ng;
+  const Consts<PosF64> k(a.L, a.dx, Ng);
+  const size_t prow = (size_t)env * a.ld, row = (size_t)env * Ng;
+  unsigned bad = 0u;
+  for (long long i = (long long)blockIdx.x * ABLOCK + threadIdx.x; i < a.N; i += (long long)gridDim.x * ABLOCK) {
+    double w[3], xw;
+    int j, jr;
+    adj_locate(x[prow + i], k, xw, j, jr, w, bad);
+    lx[prow + i] = lx[prow + i] + a.scale * slope_dot(nu + row, j, jr, a.dx);
+  }
+  (void)bad;
 }
 
 }  // namespace

@@ -547,27 +547,69 @@ __device__ __forceinline__ void mesh_mode(const double* __restrict__ E, const do
 }
 
 // Linear feedback law of run_feedback.py:133-135 (and the behaviour-cloning action of src/control/rl/ddpg.py:369-371): the
-// actuator coefficients of the next step are (-Re, +Im) of modes 1..M of the mesh field the last step left.
+// actuator coefficients of the next step are (-Re, +Im) of modes 1..M of the mesh field the last step left.  With a gain
+// (pic_step_feedback_gain) the law is a = G m instead, m = (Re E_1..Re E_M, Im E_1..Im E_M) of the same field.
 struct Feedback {
   const double* tw;      // [2][rows][Ng] cos | sin twiddles, row m-1 = mode m
   int rows;
   int M;                 // 0 = no feedback
   double* act_out;       // [env][2M] the action computed (read by the next force evaluations), or null
   double* act_hist;      // [env][2M] of the step the action is for, in a per-step record, or null
+  const double* gain;    // [env][2M][2M] row-major G of the gain law, or null: the reference law
+  double* modes;         // [env][2M] m of the gain law, read back by the workgroup for the product (needed with gain)
+  double* modes_hist;    // [env][2M] m of the step the action is for, in a per-step record, or null
 };
+
+// a_i = sum_k G[i][k] m_k over the k with G[i][k] != 0, in ascending k: the first such term starts the sum, the others are
+// plain float64 adds (no G[i][k] != 0: +0).  With G0 = diag(-1 x M, +1 x M) this is -Re, +Im bit for bit, signed zeros
+// included (include/picstep.h: pic_step_feedback_gain).
+__device__ __forceinline__ double gain_row(const double* __restrict__ g, const double* __restrict__ m, int n) {
+  double acc = 0.0;
+  bool any = false;
+  for (int k = 0; k < n; ++k) {
+    const double gk = g[k];
+    if (gk != 0.0) {
+      const double t = gk * m[k];
+      acc = any ? acc + t : t;
+      any = true;
+    }
+  }
+  return acc;
+}
 
 // a_lds (2M doubles of LDS, or null) also receives the action; the caller puts a barrier before reading it
 template <int NW>
 __device__ __forceinline__ void feedback_action(const double* __restrict__ E, const Feedback& fb, int env, int Ng,
                                                 double* __restrict__ ws, double* __restrict__ a_lds) {
+  const size_t r = (size_t)env * 2 * fb.M;
   for (int m = 0; m < fb.M; ++m) {
     double re, im;
     mesh_mode<NW>(E, fb.tw + (size_t)m * Ng, fb.tw + ((size_t)fb.rows + m) * Ng, Ng, ws, re, im);
     if (threadIdx.x == 0) {
+      if (fb.gain) {
+        double* mv = a_lds ? a_lds : fb.modes + r;
+        mv[m] = re; mv[fb.M + m] = im;
+        if (fb.modes_hist) { fb.modes_hist[r + m] = re; fb.modes_hist[r + fb.M + m] = im; }
+        continue;
+      }
       const double c = -re, s = im;
       if (a_lds) { a_lds[m] = c; a_lds[fb.M + m] = s; }
-      if (fb.act_out) { fb.act_out[(size_t)env * 2 * fb.M + m] = c; fb.act_out[(size_t)env * 2 * fb.M + fb.M + m] = s; }
-      if (fb.act_hist) { fb.act_hist[(size_t)env * 2 * fb.M + m] = c; fb.act_hist[(size_t)env * 2 * fb.M + fb.M + m] = s; }
+      if (fb.act_out) { fb.act_out[r + m] = c; fb.act_out[r + fb.M + m] = s; }
+      if (fb.act_hist) { fb.act_hist[r + m] = c; fb.act_hist[r + fb.M + m] = s; }
+    }
+  }
+  if (fb.gain) {
+    // the modes wait in a_lds (the resident kernels) or in global memory (one workgroup of its own: visible behind the barrier)
+    __syncthreads();
+    const int n = 2 * fb.M;
+    int i = threadIdx.x;
+    asm volatile("" : "+v"(i));      // (as mesh_mode: keeps the per-lane addresses below out of registers held across a step loop)
+    const double a = i < n ? gain_row(fb.gain + (r + i) * n, a_lds ? a_lds : fb.modes + r, n) : 0.0;
+    if (a_lds) __syncthreads();      // (every lane has read the modes before a_lds takes the action)
+    if (i < n) {
+      if (a_lds) a_lds[i] = a;
+      if (fb.act_out) fb.act_out[r + i] = a;
+      if (fb.act_hist) fb.act_hist[r + i] = a;
     }
   }
 }

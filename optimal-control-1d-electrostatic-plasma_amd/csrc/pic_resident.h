@@ -146,6 +146,7 @@ __device__ __forceinline__ void resident_field(const A* __restrict__ acc_all, in
     const ResidentCtl c = RESIDENT_ARG(ResidentCtl, c);
     Feedback fb = c.fb;
     if (fb.act_hist) fb.act_hist += (size_t)(prev_step + 1) * num_envs * 2 * fb.M;
+    if (fb.modes_hist) fb.modes_hist += (size_t)(prev_step + 1) * num_envs * 2 * fb.M;
     feedback_action<NW>(out.E + rc.row, fb, rc.env, Ng, rc.wsf, rc.a_lds);
     __syncthreads();
     int t0 = tid;
@@ -643,6 +644,7 @@ __global__ __launch_bounds__(NW * 64) void resident_scheme_kernel(typename P::X*
       const ResidentOut out = RESIDENT_ARG(ResidentOut, o);
       Feedback fb = c.fb;
       if (fb.act_hist) fb.act_hist += (size_t)step * num_envs * 2 * fb.M;
+      if (fb.modes_hist) fb.modes_hist += (size_t)step * num_envs * 2 * fb.M;
       feedback_action<NW>(out.E + row, fb, env, Ng, wsf, a_lds);
       __syncthreads();
       for (int j = tid; j < Ng; j += NT) xt_lds[j] = actuator_field(c.ctl.basis, c.ctl.basis + (size_t)Ng * c.ctl.M, a_lds, j, c.ctl.M);

@@ -124,6 +124,16 @@ struct Tape {
   unsigned long long* counters = nullptr;   // [0] replay mismatches of the last backward, [1] replay positions out of range
   double* gact = nullptr;             // [max_steps][env][2M] a-bar (M: the actuator's modes at pic_tape_start; none without one)
   int64_t launches = 0;               // kernels the last backward enqueued
+  int64_t budget = 0;                 // budget_bytes of pic_tape_start (0: none)
+  // steps of the gain law (pic_step_feedback_gain): one block allocated by the first such call, one gain per call;
+  // both count in `bytes`
+  void* law_block = nullptr;
+  double* lact = nullptr;             // [max_steps][env][2M] a_t of the law's steps (their e_t = B a_t goes to `ext` behind the call)
+  double* lmodes = nullptr;           // [max_steps][env][2M] m_t of the law's steps, zero on the others
+  double* lcot = nullptr;             // [max_steps][env][2M] cotangents on m_t of a backward
+  double* lE = nullptr;               // [env][Ng] E-bar_t = J^T (G^T a-bar_t + m-bar_t) of a law step
+  std::vector<int> law;               // [max_steps] per step: the index of its gain in `gains`, or -1 (empty: no law step yet)
+  std::vector<double*> gains;         // per call: [env][2M][2M]
 };
 
 struct pic_handle {
@@ -195,6 +205,8 @@ struct pic_handle {
   bool res_carry_valid = false;
   const InlineDoubles* inline_act = nullptr;   // streaming schedule, for the duration of a call: the held action rides in the sweeps' argument blocks
   Feedback fb{};                  // feedback outputs wanted from the NEXT post-step solve of the streaming schedule (fb.M = 0: none)
+  double* gain = nullptr;         // [env][2M][2M] device copy of a host gain (pic_step_feedback_gain)
+  double* fb_modes = nullptr;     // [env][2 kMaxFeedbackModes] the gain law's m, step by step
   double* aux_n = nullptr;        // probe outputs
   double* aux_E = nullptr;
   double* aux_pe = nullptr;
@@ -1191,7 +1203,9 @@ int pic_destroy(pic_handle* h) {
   prof_drain(h);
   for (hipEvent_t e : h->ev) hipEventDestroy(e);
   void* bufs[] = {h->rec.d, h->rec.u, h->rec.phase, h->rec.feq, h->x, h->scratch, h->stage, h->ring, h->ke_part, h->n, h->E_mesh, h->phi, h->ext, h->ext2, h->probe_ext,
-                  h->basis, h->act, h->modes, h->aux_n, h->aux_E, h->aux_pe, h->aux_phi, h->KE, h->bad, h->tw, h->traj, h->res_q1, h->res_carry, h->tape.block};
+                  h->basis, h->act, h->modes, h->aux_n, h->aux_E, h->aux_pe, h->aux_phi, h->KE, h->bad, h->tw, h->traj, h->res_q1, h->res_carry, h->tape.block,
+                  h->gain, h->fb_modes, h->tape.law_block};
+  for (double* g : h->tape.gains) hipFree(g);
   for (void* b : bufs)
     if (b) hipFree(b);
   if (h->v_separate && h->v) hipFree(h->v);
@@ -1398,6 +1412,13 @@ static int ensure_twiddle(pic_handle* h, int rows) {
   return PIC_OK;
 }
 
+// the per-step records of a feedback call (actions, the gain law's modes) moved on by `steps` steps
+static void fb_skip(Feedback& fb, size_t steps, int E) {
+  const size_t row = (size_t)E * 2 * fb.M;
+  if (fb.act_hist) fb.act_hist += steps * row;
+  if (fb.modes_hist) fb.modes_hist += steps * row;
+}
+
 // ---- the other integrators on the streaming schedule (pic_set_integrator) ----------------------------------------
 // Between steps h->q_slot holds the deposit of the stored, wrapped x: the post-step deposit of the step before, which is also the
 // field of the next step's (first) force evaluation -- one row, no first drift to deposit.  Where it is missing (particles loaded
@@ -1445,7 +1466,6 @@ static void run_scheme_step(pic_handle* h, const Control& ctl, int only, bool me
 
 static void advance_scheme(pic_handle* h, const StepControl& sc, int nsteps, double* hist) {
   const int E = h->cfg.num_envs;
-  const size_t act_row = (size_t)E * 2 * sc.ctl.M;
   h->inline_act = sc.inline_n > 0 ? &sc.inline_act : nullptr;
   // Verlet merges where the two half-kicks of a merged sweep see one external field: held for the call.  A new field every step,
   // or the feedback law's (whose action needs the post-step solve first), runs two sweeps per step.
@@ -1465,7 +1485,7 @@ static void advance_scheme(pic_handle* h, const StepControl& sc, int nsteps, dou
       h->fb = Feedback{};
       if (s + 1 < nsteps) {
         h->fb = fb;
-        if (fb.act_hist) h->fb.act_hist = fb.act_hist + (size_t)(s + 1) * act_row;
+        fb_skip(h->fb, s + 1, E);
       }
     }
     run_scheme_step(h, ctl, 0, held && s + 1 < nsteps, &open);
@@ -1498,7 +1518,6 @@ static int advance_steps(pic_handle* h, const StepControl& sc, int nsteps, doubl
     HIPCHK(h, launch_status(h));
     return PIC_OK;
   }
-  const size_t act_row = (size_t)E * 2 * sc.ctl.M;
   h->inline_act = sc.inline_n > 0 ? &sc.inline_act : nullptr;      // (launch_sweep: the held action inside the sweeps' arguments)
   for (int s = 0; s < nsteps; ++s) {
     Control ctl = sc.ctl;
@@ -1520,7 +1539,7 @@ static int advance_steps(pic_handle* h, const StepControl& sc, int nsteps, doubl
       h->fb = Feedback{};
       if (s + 1 < nsteps) {
         h->fb = fb;
-        if (fb.act_hist) h->fb.act_hist = fb.act_hist + (size_t)(s + 1) * act_row;
+        fb_skip(h->fb, s + 1, E);
       }
     }
     // (the actuator's field of step s: built by sweep B of step 0, after that by the previous step's sweep D -- or, under a
@@ -1595,7 +1614,7 @@ static int advance_recorded(pic_handle* h, const StepControl& sc, int nsteps, do
     StepControl part = sc;
     if (part.ctl.ext) part.ctl.ext += (size_t)done * sc.ext_step;
     if (part.ctl.act) part.ctl.act += (size_t)done * sc.act_step;
-    if (part.fb.act_hist) part.fb.act_hist += (size_t)done * E * 2 * sc.fb.M;
+    fb_skip(part.fb, done, E);
     int rc = advance_steps(h, part, n, hist ? hist + (size_t)done * 3 * E : nullptr,
                            snap ? static_cast<char*>(snap) + (size_t)done * 2 * E * (size_t)h->cfg.N * h->esz : nullptr);
     if (rc) return rc;
@@ -1643,11 +1662,21 @@ static int advance(pic_handle* h, const StepControl& sc, int nsteps, double* his
     StepControl part = sc;
     if (part.ctl.ext) part.ctl.ext += (size_t)done * sc.ext_step;
     if (part.ctl.act) part.ctl.act += (size_t)done * sc.act_step;
-    int rc = tape_record_ext(h, part, n);
+    fb_skip(part.fb, done, E);
+    int rc = part.fb.M > 0 ? PIC_OK : tape_record_ext(h, part, n);
     if (rc) return rc;
     rc = advance_recorded(h, part, n, hist ? hist + (size_t)done * 3 * E : nullptr,
                           snap ? static_cast<char*>(snap) + (size_t)done * 2 * E * (size_t)h->cfg.N * h->esz : nullptr);
     if (rc) return rc;
+    if (part.fb.M > 0) {
+      // the gain law's actions exist only once their steps have run: e_t = B a_t from the actions the steps wrote on the tape
+      // (pic_step_feedback_gain points act_hist at its rows)
+      StepControl made{};
+      made.ctl.basis = sc.ctl.basis; made.ctl.M = sc.ctl.M; made.ctl.act = part.fb.act_hist;
+      made.act_step = (long long)E * 2 * sc.ctl.M;
+      rc = tape_record_ext(h, made, n);
+      if (rc) return rc;
+    }
     t.steps += n;
     done += n;
     if (t.steps % t.every == 0) {
@@ -1724,7 +1753,8 @@ int pic_step(pic_handle* h, const double* E_ext, int mem_kind, int nsteps) {
 // Runs `sc` for nsteps steps with the energies (hist, may be null) and / or the particles (snap, may be null) of every step
 // kept on the device and read back once at the end; act_out (may be null): host [nsteps][env][2M] record of the feedback
 // law's actions.  Returns after the read-backs, or -- nothing to read back -- without waiting for the device.
-static int step_recording(pic_handle* h, StepControl sc, int nsteps, double* hist, void* snap, double* act_out, const char* who) {
+static int step_recording(pic_handle* h, StepControl sc, int nsteps, double* hist, void* snap, double* act_out, const char* who,
+                          double* modes_out = nullptr) {
   if (nsteps == 0) return PIC_OK;
   const int E = h->cfg.num_envs;
   const size_t hbytes = (size_t)nsteps * 3 * E * sizeof(double);
@@ -1732,15 +1762,18 @@ static int step_recording(pic_handle* h, StepControl sc, int nsteps, double* his
   const size_t abytes = (size_t)nsteps * E * 2 * sc.fb.M * sizeof(double);
   double* dh = nullptr;
   double* da = nullptr;
+  double* dm = nullptr;
   void* ds = nullptr;
-  auto release = [&]() { if (dh) hipFree(dh); if (da) hipFree(da); if (ds) hipFree(ds); };
+  auto release = [&]() { if (dh) hipFree(dh); if (da) hipFree(da); if (dm) hipFree(dm); if (ds) hipFree(ds); };
   if (hist && hipMalloc((void**)&dh, hbytes) != hipSuccess) return fail(h, PIC_ENOMEM, std::string(who) + ": history buffer");
   if (act_out && sc.fb.M > 0 && hipMalloc((void**)&da, abytes) != hipSuccess) { release(); return fail(h, PIC_ENOMEM, std::string(who) + ": action record"); }
+  if (modes_out && sc.fb.gain && hipMalloc((void**)&dm, abytes) != hipSuccess) { release(); return fail(h, PIC_ENOMEM, std::string(who) + ": mode record"); }
   if (snap && hipMalloc(&ds, sbytes) != hipSuccess) {
     release();
     return fail(h, PIC_ENOMEM, std::string(who) + ": the snapshots of all steps do not fit on the device; record fewer steps per call");
   }
-  sc.fb.act_hist = da;
+  if (da || !sc.fb.act_hist) sc.fb.act_hist = da;      // (pic_step_feedback_gain under a tape: the tape's rows)
+  if (dm) sc.fb.modes_hist = dm;
   int rc = PIC_OK;
   if (!ds || h->resident) {
     rc = advance(h, sc, nsteps, dh, ds);      // energies: every post-step solve records its own entry; resident: the kernel records all
@@ -1751,7 +1784,7 @@ static int step_recording(pic_handle* h, StepControl sc, int nsteps, double* his
       StepControl one = sc;
       if (one.ctl.ext) one.ctl.ext += (size_t)s * sc.ext_step;
       if (one.ctl.act) one.ctl.act += (size_t)s * sc.act_step;
-      if (one.fb.act_hist) one.fb.act_hist += (size_t)s * E * 2 * sc.fb.M;
+      fb_skip(one.fb, s, E);
       rc = advance(h, one, 1, dh ? dh + (size_t)s * 3 * E : nullptr);
       if (rc != PIC_OK) break;
       if (h->fmt == FMT_F64)
@@ -1766,13 +1799,14 @@ static int step_recording(pic_handle* h, StepControl sc, int nsteps, double* his
     }
   }
   hipError_t e = hipGetLastError();
-  if (!dh && !da && !ds) {
+  if (!dh && !da && !dm && !ds) {
     if (rc != PIC_OK) return rc;
     if (e != hipSuccess) return fail(h, PIC_EHIP, std::string(who) + ": " + hipGetErrorString(e));
     return PIC_OK;
   }
   if (rc == PIC_OK && e == hipSuccess && dh) e = hipMemcpyAsync(hist, dh, hbytes, hipMemcpyDeviceToHost, h->stream);
   if (rc == PIC_OK && e == hipSuccess && da) e = hipMemcpyAsync(act_out, da, abytes, hipMemcpyDeviceToHost, h->stream);
+  if (rc == PIC_OK && e == hipSuccess && dm) e = hipMemcpyAsync(modes_out, dm, abytes, hipMemcpyDeviceToHost, h->stream);
   if (rc == PIC_OK && e == hipSuccess && ds) e = hipMemcpyAsync(snap, ds, sbytes, hipMemcpyDeviceToHost, h->stream);
   hipError_t e2 = hipStreamSynchronize(h->stream);
   release();
@@ -2284,6 +2318,88 @@ int pic_step_feedback(pic_handle* h, int max_mode, int nsteps, double* actions_o
   return step_recording(h, sc, nsteps, hist, nullptr, actions_out, "pic_step_feedback");
 }
 
+// the gain law's record on an open tape (allocated by its first call) and one more gain of `gbytes`, within budget_bytes
+static int tape_law_reserve(pic_handle* h, size_t gbytes) {
+  Tape& t = h->tape;
+  const char* who = "pic_step_feedback_gain";
+  const size_t rows = ((size_t)t.max_steps * h->cfg.num_envs * 2 * h->act_modes * sizeof(double) + 255) & ~(size_t)255;
+  const size_t lbytes = t.law_block ? 0 : 3 * rows + (size_t)h->cfg.num_envs * h->cfg.Ng * sizeof(double);
+  if (t.budget > 0 && t.bytes + lbytes + gbytes > (size_t)t.budget)
+    return fail(h, PIC_ENOMEM, std::string(who) + ": the law's record and this call's gain would take the tape past budget_bytes (pic_tape_start)");
+  if (!t.law_block) {
+    if (hipMalloc(&t.law_block, lbytes) != hipSuccess) {
+      (void)hipGetLastError();
+      t.law_block = nullptr;
+      return fail(h, PIC_ENOMEM, std::string(who) + ": the tape's record of the law's steps does not fit on the device");
+    }
+    char* b = static_cast<char*>(t.law_block);
+    t.lact = (double*)b; t.lmodes = (double*)(b + rows); t.lcot = (double*)(b + 2 * rows); t.lE = (double*)(b + 3 * rows);
+    HIPCHK(h, hipMemsetAsync(t.lmodes, 0, rows, h->stream));
+    t.law.assign((size_t)t.max_steps, -1);
+    t.bytes += lbytes;
+  }
+  double* g = nullptr;
+  if (hipMalloc((void**)&g, gbytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(h, PIC_ENOMEM, std::string(who) + ": the tape's copy of the gain does not fit on the device");
+  }
+  t.gains.push_back(g);
+  t.bytes += gbytes;
+  return PIC_OK;
+}
+
+int pic_step_feedback_gain(pic_handle* h, int max_mode, const double* gain, int mem_kind, int nsteps, double* actions_out,
+                           double* modes_out, double* hist) {
+  if (!h) return PIC_EINVAL;
+  const char* who = "pic_step_feedback_gain";
+  if (!gain) return fail(h, PIC_EINVAL, "pic_step_feedback_gain: null gain");
+  if (mem_kind != PIC_HOST && mem_kind != PIC_DEVICE) return fail(h, PIC_EINVAL, "pic_step_feedback_gain: bad mem_kind");
+  int rc = check_steppable(h, nsteps, who);
+  if (rc) return rc;
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  StepControl sc;
+  rc = actuator_control(h, sc, who);
+  if (rc) return rc;
+  if (max_mode != h->act_modes || max_mode > kMaxFeedbackModes)
+    return fail(h, PIC_EINVAL, "pic_step_feedback_gain: max_mode must equal the actuator's (pic_set_actuator) and be at most 16");
+  if (nsteps == 0) return PIC_OK;
+  rc = ensure_twiddle(h, max_mode);
+  if (rc) return rc;
+  const int E = h->cfg.num_envs, n = 2 * max_mode;
+  const size_t gbytes = (size_t)E * n * n * sizeof(double);
+  if (!h->fb_modes) HIPCHK(h, hipMalloc((void**)&h->fb_modes, (size_t)E * 2 * kMaxFeedbackModes * sizeof(double)));
+  const hipMemcpyKind in = mem_kind == PIC_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+  Tape& t = h->tape;
+  const double* g = gain;
+  if (t.on) {                        // the gain goes on the tape once per call
+    rc = tape_law_reserve(h, gbytes);
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(t.gains.back(), gain, gbytes, in, h->stream));
+    g = t.gains.back();
+  } else if (mem_kind == PIC_HOST) {
+    if (!h->gain) HIPCHK(h, hipMalloc((void**)&h->gain, (size_t)E * 4 * kMaxFeedbackModes * kMaxFeedbackModes * sizeof(double)));
+    HIPCHK(h, hipMemcpyAsync(h->gain, gain, gbytes, in, h->stream));
+    g = h->gain;
+  }
+  sc.fb.tw = h->tw; sc.fb.rows = h->tw_rows; sc.fb.M = max_mode;
+  sc.fb.act_out = h->act;
+  sc.fb.gain = g;
+  sc.fb.modes = h->fb_modes;
+  if (!t.on) return step_recording(h, sc, nsteps, hist, nullptr, actions_out, who, modes_out);
+  // taped: the steps write their actions and modes on the tape, the caller's records are copied from there
+  const int64_t s0 = t.steps;
+  const size_t row = (size_t)E * n;
+  sc.fb.act_hist = t.lact + (size_t)s0 * row;
+  sc.fb.modes_hist = t.lmodes + (size_t)s0 * row;
+  rc = step_recording(h, sc, nsteps, hist, nullptr, nullptr, who);
+  for (int64_t s = s0; s < t.steps; ++s) t.law[(size_t)s] = (int)t.gains.size() - 1;
+  if (rc) return rc;
+  if (actions_out) HIPCHK(h, hipMemcpyAsync(actions_out, sc.fb.act_hist, (size_t)nsteps * row * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (modes_out) HIPCHK(h, hipMemcpyAsync(modes_out, sc.fb.modes_hist, (size_t)nsteps * row * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (actions_out || modes_out) HIPCHK(h, hipStreamSynchronize(h->stream));
+  return PIC_OK;
+}
+
 int pic_get_modes(pic_handle* h, int max_mode, double* re, double* im, int mem_kind) {
   if (!h || max_mode < 1 || max_mode >= h->cfg.Ng) return fail(h, PIC_EINVAL, "pic_get_modes: bad max_mode");
   if (!h->has_state) return fail(h, PIC_ESTATE, "pic_get_modes: call pic_reset first");
@@ -2638,6 +2754,8 @@ static size_t tape_layout(const pic_handle* h, int64_t max_steps, int64_t every,
 
 static void tape_free(pic_handle* h) {
   if (h->tape.block) hipFree(h->tape.block);
+  if (h->tape.law_block) hipFree(h->tape.law_block);
+  for (double* g : h->tape.gains) hipFree(g);
   h->tape = Tape{};
 }
 
@@ -2693,6 +2811,7 @@ int pic_tape_start(pic_handle* h, const pic_tape_config* c) {
   t.counters = t.cmax + h->cfg.num_envs;
   t.gact = h->act_modes ? (double*)(b + offs[11]) : nullptr;
   t.max_steps = c->max_steps; t.every = every; t.nck = c->max_steps / every + 1; t.bytes = bytes;
+  t.budget = c->budget_bytes;
   HIPCHK(h, hipMemsetAsync(b + offs[9], 0, offs[11] - offs[9], h->stream));    // acc, cmax, counters
   int rc = tape_checkpoint(h, 0);
   if (rc) { tape_free(h); return rc; }
@@ -2741,14 +2860,25 @@ static void tape_solve(pic_handle* h, const double* ext, double* E_out) {
   ++h->tape.launches;
 }
 
-int pic_tape_backward(pic_handle* h, const double* cot_hist, const void* cot_x, const void* cot_v, int mem_kind, double* g_ext,
-                      double* g_actions, void* g_x0, void* g_v0) {
-  if (!h) return PIC_EINVAL;
+// E-bar of the gain-law step s into t.lE (pic_adjoint.h: law_adjoint_kernel); e-bar_s must be complete
+static void tape_law_cot(pic_handle* h, int64_t s) {
   Tape& t = h->tape;
-  if (!t.on) return fail(h, PIC_ESTATE, "pic_tape_backward: no tape is open (pic_tape_start)");
-  if (mem_kind != PIC_HOST && mem_kind != PIC_DEVICE) return fail(h, PIC_EINVAL, "pic_tape_backward: bad mem_kind");
+  const int E = h->cfg.num_envs, Ng = h->cfg.Ng, M = h->act_modes;
+  const size_t mesh = (size_t)E * Ng, row = (size_t)E * 2 * M;
+  hipLaunchKernelGGL(law_adjoint_kernel, dim3(E), dim3(ABLOCK), 0, h->stream, t.gext + (size_t)s * mesh, h->basis,
+                     t.gains[(size_t)t.law[(size_t)s]], t.lcot + (size_t)s * row, h->tw, h->tw_rows, t.lE, Ng, M);
+  ++t.launches;
+}
+
+static int tape_backward(pic_handle* h, const char* who, const double* cot_hist, const void* cot_x, const void* cot_v,
+                         const double* cot_modes, int mem_kind, double* g_ext, double* g_actions, void* g_x0, void* g_v0,
+                         double* modes_out) {
+  Tape& t = h->tape;
+  const std::string w(who);
+  if (!t.on) return fail(h, PIC_ESTATE, w + ": no tape is open (pic_tape_start)");
+  if (mem_kind != PIC_HOST && mem_kind != PIC_DEVICE) return fail(h, PIC_EINVAL, w + ": bad mem_kind");
   if (g_actions && !t.gact)
-    return fail(h, PIC_ESTATE, "pic_tape_backward: g_actions needs an actuator set before pic_tape_start (pic_set_actuator)");
+    return fail(h, PIC_ESTATE, w + ": g_actions needs an actuator set before pic_tape_start (pic_set_actuator)");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   const int E = h->cfg.num_envs, Ng = h->cfg.Ng;
   const int64_t T = t.steps;
@@ -2768,6 +2898,14 @@ int pic_tape_backward(pic_handle* h, const double* cot_hist, const void* cot_x, 
   if (cot_x) rc = upload(h, lx, cot_x, mem_kind);
   if (!rc && cot_v) rc = upload(h, lv, cot_v, mem_kind);
   if (rc) return rc;
+  // steps of the gain law: the action of step s + 1 depends on the field step s left, so the refresh adjoint of
+  // step s also carries E-bar_{s+1} = J^T (G^T a-bar_{s+1} + m-bar_{s+1}); E-bar_0 reaches x_0 through the field at the start
+  const bool law = !t.law.empty();
+  const size_t lrow = (size_t)E * 2 * h->act_modes;
+  if (law && T > 0) {
+    if (cot_modes) HIPCHK(h, hipMemcpyAsync(t.lcot, cot_modes, (size_t)T * lrow * sizeof(double), in, h->stream));
+    else HIPCHK(h, hipMemsetAsync(t.lcot, 0, (size_t)T * lrow * sizeof(double), h->stream));
+  }
 
   long long gx = (h->cfg.N + (long long)ABLOCK * 8 - 1) / ((long long)ABLOCK * 8);       // ~8 particles per lane
   gx = std::max<long long>(1, std::min<long long>(gx, std::max(1, 2048 / E)));
@@ -2805,22 +2943,37 @@ int pic_tape_backward(pic_handle* h, const double* cot_hist, const void* cot_x, 
       const AdjStep st{x, x + part, t.F + (size_t)i * 3 * mesh, (long long)mesh};
       const double* cot = t.cot + (size_t)(t0 + i) * 3 * E;
       double* ge = t.gext + (size_t)(t0 + i) * mesh;
-      hipLaunchKernelGGL(adjoint_mesh_kernel, mgrid, dim3(SBLOCK), mesh_lds, h->stream, nullptr, t.cmax, t.M + (size_t)i * mesh, cot, ge, t.nu, a, E);
+      const bool feeds = law && t0 + i + 1 < T && t.law[(size_t)(t0 + i + 1)] >= 0;
+      if (feeds) tape_law_cot(h, t0 + i + 1);
+      hipLaunchKernelGGL(adjoint_mesh_kernel, mgrid, dim3(SBLOCK), mesh_lds, h->stream, nullptr, t.cmax, t.M + (size_t)i * mesh, cot, ge, t.nu, a, E,
+                         feeds ? (const double*)t.lE : nullptr);
       hipLaunchKernelGGL(adjoint_pass_kernel<3>, pgrid, dim3(ABLOCK), 0, h->stream, st, t.nu, cot, lx, lv, t.cmax, a, E);
       hipLaunchKernelGGL(adjoint_deposit_kernel<3>, pgrid, dim3(ABLOCK), acc_lds, h->stream, st, lv, t.cmax, t.acc, a);
-      hipLaunchKernelGGL(adjoint_mesh_kernel, mgrid, dim3(SBLOCK), mesh_lds, h->stream, t.acc, t.cmax, nullptr, nullptr, ge, t.nu, a, E);
+      hipLaunchKernelGGL(adjoint_mesh_kernel, mgrid, dim3(SBLOCK), mesh_lds, h->stream, t.acc, t.cmax, nullptr, nullptr, ge, t.nu, a, E, nullptr);
       hipLaunchKernelGGL(adjoint_pass_kernel<2>, pgrid, dim3(ABLOCK), 0, h->stream, st, t.nu, nullptr, lx, lv, t.cmax, a, E);
       hipLaunchKernelGGL(adjoint_deposit_kernel<2>, pgrid, dim3(ABLOCK), acc_lds, h->stream, st, lv, t.cmax, t.acc, a);
-      hipLaunchKernelGGL(adjoint_mesh_kernel, mgrid, dim3(SBLOCK), mesh_lds, h->stream, t.acc, t.cmax, nullptr, nullptr, ge, t.nu, a, E);
+      hipLaunchKernelGGL(adjoint_mesh_kernel, mgrid, dim3(SBLOCK), mesh_lds, h->stream, t.acc, t.cmax, nullptr, nullptr, ge, t.nu, a, E, nullptr);
       hipLaunchKernelGGL(adjoint_pass_kernel<1>, pgrid, dim3(ABLOCK), 0, h->stream, st, t.nu, nullptr, lx, lv, t.cmax, a, E);
       hipLaunchKernelGGL(adjoint_deposit_kernel<1>, pgrid, dim3(ABLOCK), acc_lds, h->stream, st, lv, t.cmax, t.acc, a);
-      hipLaunchKernelGGL(adjoint_mesh_kernel, mgrid, dim3(SBLOCK), mesh_lds, h->stream, t.acc, t.cmax, nullptr, nullptr, ge, t.nu, a, E);
+      hipLaunchKernelGGL(adjoint_mesh_kernel, mgrid, dim3(SBLOCK), mesh_lds, h->stream, t.acc, t.cmax, nullptr, nullptr, ge, t.nu, a, E, nullptr);
       hipLaunchKernelGGL(adjoint_pass_kernel<0>, pgrid, dim3(ABLOCK), 0, h->stream, st, t.nu, nullptr, lx, lv, t.cmax, a, E);
       t.launches += 11;
     }
     HIPCHK(h, hipGetLastError());
   }
+  if (law && T > 0 && t.law[0] >= 0) {      // lambda_x0 += s W'(x_0) . K^T E-bar_0 at the tape-start positions
+    tape_law_cot(h, 0);
+    hipLaunchKernelGGL(adjoint_mesh_kernel, mgrid, dim3(SBLOCK), mesh_lds, h->stream, nullptr, t.cmax, nullptr, nullptr, nullptr, t.nu, a, E,
+                       (const double*)t.lE);
+    hipLaunchKernelGGL(adjoint_start_kernel, pgrid, dim3(ABLOCK), 0, h->stream, (const double*)t.ck, (const double*)t.nu, lx, a);
+    t.launches += 2;
+  }
   if (g_ext && T > 0) HIPCHK(h, hipMemcpyAsync(g_ext, t.gext, (size_t)T * mesh * sizeof(double), outk, h->stream));
+  if (modes_out && T > 0) {
+    if (law) HIPCHK(h, hipMemcpyAsync(modes_out, t.lmodes, (size_t)T * lrow * sizeof(double), outk, h->stream));
+    else if (mem_kind == PIC_HOST) std::memset(modes_out, 0, (size_t)T * lrow * sizeof(double));
+    else HIPCHK(h, hipMemsetAsync(modes_out, 0, (size_t)T * lrow * sizeof(double), h->stream));
+  }
   if (g_actions && T > 0) {
     hipLaunchKernelGGL(adjoint_actions_kernel, dim3(E, (unsigned)T), dim3(ABLOCK), 0, h->stream, t.gext, h->basis,
                        mem_kind == PIC_HOST ? t.gact : g_actions, Ng, h->act_modes, E);
@@ -2839,10 +2992,25 @@ int pic_tape_backward(pic_handle* h, const double* cot_hist, const void* cot_x, 
     HIPCHK(h, hipMemcpyAsync(&cnt, t.counters, sizeof(cnt), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (cnt)
-      return fail(h, PIC_ESTATE, "pic_tape_backward: the replay differs from the taped forward in " + std::to_string(cnt) +
+      return fail(h, PIC_ESTATE, w + ": the replay differs from the taped forward in " + std::to_string(cnt) +
                                      " particle values (were the particles written while the tape was open?): the gradient is not valid");
   }
   return PIC_OK;
+}
+
+int pic_tape_backward(pic_handle* h, const double* cot_hist, const void* cot_x, const void* cot_v, int mem_kind, double* g_ext,
+                      double* g_actions, void* g_x0, void* g_v0) {
+  if (!h) return PIC_EINVAL;
+  return tape_backward(h, "pic_tape_backward", cot_hist, cot_x, cot_v, nullptr, mem_kind, g_ext, g_actions, g_x0, g_v0, nullptr);
+}
+
+int pic_tape_backward_feedback(pic_handle* h, const double* cot_hist, const void* cot_x, const void* cot_v, const double* cot_modes,
+                               int mem_kind, double* g_ext, double* g_actions, void* g_x0, void* g_v0, double* modes_out) {
+  if (!h) return PIC_EINVAL;
+  if (modes_out && !h->tape.gact)
+    return fail(h, PIC_ESTATE, "pic_tape_backward_feedback: modes_out needs an actuator set before pic_tape_start (pic_set_actuator)");
+  return tape_backward(h, "pic_tape_backward_feedback", cot_hist, cot_x, cot_v, cot_modes, mem_kind, g_ext, g_actions, g_x0, g_v0,
+                       modes_out);
 }
 
 }  // extern "C"

@@ -165,6 +165,34 @@ class BatchedPIC:
         "KE", "PE", "PE_reward" [nsteps, num_envs] as asked for (None, and asynchronous, with neither)."""
         return self._h.step_feedback(nsteps, actions, history)
 
+    def step_feedback_gain(self, gain, nsteps: int, actions: bool = False, modes: bool = False, history: bool = False):
+        """nsteps of the linear law a = G m on the device (pic_step_feedback_gain): before each step
+        m = (Re E_1..Re E_M, Im E_1..Im E_M) of the current E_mesh (M = max_mode) and a[i] = sum_k G[i][k] m[k] over the non-zero
+        G[i][k] in ascending k.  gain: NumPy or a float64 CUDA tensor, [num_envs, 2M, 2M] or [2M, 2M] for every environment;
+        G0 = diag(-1 x M, +1 x M) is step_feedback bit for bit.  Allowed while a tape is open (the steps are differentiable
+        through the law: backward returns "modes" and "gain").  Returns a dict with "actions", "modes" [nsteps, num_envs, 2M]
+        and / or "KE", "PE", "PE_reward" [nsteps, num_envs] as asked for (None, and asynchronous, with none of them)."""
+        E, n = self.num_envs, 2 * self.max_mode
+        if hasattr(gain, "is_cuda") and gain.is_cuda:
+            import torch
+            if gain.dtype != torch.float64:
+                raise ValueError("gain must be float64")
+            g = gain.reshape(1, n, n).expand(E, n, n) if gain.dim() == 2 else gain
+            if tuple(g.shape) != (E, n, n):
+                raise ValueError(f"gain must be [{E}, {n}, {n}] or [{n}, {n}]")
+            g = g.contiguous()
+            shared = getattr(self, "_torch_stream", None) is not None
+            if not shared:
+                torch.cuda.current_stream(self.device).synchronize()
+            out = self._h.step_feedback_gain(None, nsteps, actions, modes, history, device_ptr=g.data_ptr())
+            if not shared and out is None:
+                self._h.sync()           # (g, a temporary, must outlive the steps that read it)
+            return out
+        g = np.asarray(gain, dtype=np.float64)
+        if g.shape == (n, n):
+            g = np.broadcast_to(g, (E, n, n))
+        return self._h.step_feedback_gain(np.ascontiguousarray(g), nsteps, actions, modes, history)
+
     def modes(self, max_mode: int):
         """Complex [num_envs, max_mode]: rows 1..max_mode of compute_E_k_spectrum for the current E_mesh."""
         return self._h.modes(max_mode)
@@ -347,10 +375,11 @@ class BatchedPIC:
 
     # -- differentiable rollouts (pic_tape_*) ------------------------------------------
     def start_tape(self, max_steps: int, checkpoint_every: int = 0, budget_bytes: int = 0):
-        """Open a tape: the steps that follow (step, step_history, step_actions[_traj], step_ext_traj, step_observe, up to
-        max_steps of them) can be differentiated by `backward`.  checkpoint_every = 0: about sqrt(max_steps).  Float64 particles,
-        CIC, Yoshida-4 and the fixed-point accumulator only.  Resets, feedback steps, staged steps and changes of actuator or
-        integrator are refused while it is open."""
+        """Open a tape: the steps that follow (step, step_history, step_actions[_traj], step_ext_traj, step_observe,
+        step_feedback_gain, up to max_steps of them) can be differentiated by `backward`.  checkpoint_every = 0: about
+        sqrt(max_steps).  Float64 particles, CIC, Yoshida-4 and the fixed-point accumulator only.  Resets, step_feedback (use
+        step_feedback_gain with G0 for a differentiable reference law), staged steps and changes of actuator or integrator are
+        refused while it is open."""
         self._h.tape_start(max_steps, checkpoint_every, budget_bytes)
 
     def stop_tape(self):
@@ -373,18 +402,27 @@ class BatchedPIC:
                 self.stop_tape()
         return cm()
 
-    def backward(self, d_KE=None, d_PE=None, d_PE_reward=None, d_x=None, d_v=None):
+    def backward(self, d_KE=None, d_PE=None, d_PE_reward=None, d_x=None, d_v=None, d_modes=None):
         """Vector-Jacobian product of the taped steps: cotangents d_KE, d_PE, d_PE_reward [T, num_envs] of the energy traces
         (step_history's) and d_x, d_v [num_envs, N] of the final particles (each None = 0).  Returns a dict: "ext" [T, num_envs,
         N_mesh] (gradient with respect to every step's external field), "actions" [T, num_envs, 2*max_mode] (= B^T ext; with an
         actuator), "x0", "v0" [num_envs, N] (initial particles).  NumPy arrays, or float64 CUDA tensors if any cotangent is one
         (then stream-ordered like step_actions_traj_torch).  Raises PicError if the replay of the taped steps does not reproduce
-        the forward bit for bit (particles written through the views while taping): such a gradient would be wrong."""
+        the forward bit for bit (particles written through the views while taping): such a gradient would be wrong.
+        A tape with steps of step_feedback_gain: the gradient includes the path through the law; d_modes
+        [T, num_envs, 2*max_mode] are cotangents on their modes (ignored on other steps), and the dict also holds "modes"
+        [T, num_envs, 2*max_mode] (the taped m_t, zero on other steps) and "gain": sum over the call's steps of
+        actions_t modes_t^T, [num_envs, 2M, 2M] for one gain-law call, a list of them for several."""
         T = self._h.tape_stats()["steps"]
         E = self.num_envs
-        given = [a for a in (d_KE, d_PE, d_PE_reward, d_x, d_v) if a is not None]
+        given = [a for a in (d_KE, d_PE, d_PE_reward, d_x, d_v, d_modes) if a is not None]
         on_device = any(hasattr(a, "is_cuda") and a.is_cuda for a in given)
         M = getattr(self, "max_mode", 0)
+        calls = self._h.tape_law_calls()
+        if calls:
+            return self._backward_law(T, calls, on_device, d_KE, d_PE, d_PE_reward, d_x, d_v, d_modes)
+        if d_modes is not None:
+            raise ValueError("backward: d_modes needs steps of step_feedback_gain on the tape")
         if not on_device:
             hist = None
             if any(a is not None for a in (d_KE, d_PE, d_PE_reward)):
@@ -424,6 +462,52 @@ class BatchedPIC:
         if st["replay_mismatches"]:
             raise _abi.PicError(f"backward: the replay differs from the taped forward in {st['replay_mismatches']} particle values "
                                 "(were the particles written while the tape was open?): the gradient is not valid")
+        return res
+
+    def _backward_law(self, T, calls, on_device, d_KE, d_PE, d_PE_reward, d_x, d_v, d_modes):
+        E, n = self.num_envs, 2 * self.max_mode
+
+        def gains(act, md):
+            g = [sum(act[s][:, :, None] * md[s][:, None, :] for s in range(first, first + k)) for first, k in calls]
+            return g[0] if len(g) == 1 else g
+        if not on_device:
+            hist = None
+            if any(a is not None for a in (d_KE, d_PE, d_PE_reward)):
+                hist = np.zeros((T, 3, E))
+                for k, a in enumerate((d_KE, d_PE, d_PE_reward)):
+                    if a is not None:
+                        hist[:, k] = np.asarray(a, dtype=np.float64).reshape(T, E)
+            out = self._h.tape_backward_feedback(hist, d_x, d_v, d_modes)
+            res = {"ext": out["g_ext"], "x0": out["g_x0"], "v0": out["g_v0"], "actions": out["g_actions"], "modes": out["modes"]}
+            res["gain"] = gains(res["actions"], res["modes"])
+            return res
+        import torch
+        dev = f"cuda:{self.device}"
+        f64 = dict(dtype=torch.float64, device=dev)
+        hist = None
+        if any(a is not None for a in (d_KE, d_PE, d_PE_reward)):
+            hist = torch.zeros((T, 3, E), **f64)
+            for k, a in enumerate((d_KE, d_PE, d_PE_reward)):
+                if a is not None:
+                    hist[:, k] = torch.as_tensor(a, **f64).reshape(T, E)
+        cx = None if d_x is None else torch.as_tensor(d_x, **f64).reshape(E, self.N).contiguous()
+        cv = None if d_v is None else torch.as_tensor(d_v, **f64).reshape(E, self.N).contiguous()
+        cm = None if d_modes is None else torch.as_tensor(d_modes, **f64).reshape(T, E, n).contiguous()
+        res = {"ext": torch.empty((T, E, self.N_mesh), **f64), "x0": torch.empty((E, self.N), **f64),
+               "v0": torch.empty((E, self.N), **f64), "actions": torch.empty((T, E, n), **f64), "modes": torch.empty((T, E, n), **f64)}
+        shared = getattr(self, "_torch_stream", None) is not None
+        if not shared:
+            torch.cuda.current_stream(self.device).synchronize()
+
+        def ptr(t):
+            return 0 if t is None or t.numel() == 0 else t.data_ptr()
+        self._h.tape_backward_feedback_device(ptr(hist), ptr(cx), ptr(cv), ptr(cm), ptr(res["ext"]), ptr(res["actions"]),
+                                              ptr(res["x0"]), ptr(res["v0"]), ptr(res["modes"]))
+        st = self._h.tape_stats()                    # (waits for the backward)
+        if st["replay_mismatches"]:
+            raise _abi.PicError(f"backward: the replay differs from the taped forward in {st['replay_mismatches']} particle values "
+                                "(were the particles written while the tape was open?): the gradient is not valid")
+        res["gain"] = gains(res["actions"], res["modes"])
         return res
 
     def close(self):
