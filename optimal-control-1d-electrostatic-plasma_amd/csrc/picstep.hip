@@ -252,6 +252,18 @@ int fail(pic_handle* h, int code, const std::string& msg) {
   return code;
 }
 
+// f(PosF64{}), f(PosF32{}) or f(PosU32{}): the handle's particle format, the one place that turns h->fmt into a type.  A body
+// writes its pointer casts as typename P::X* / typename P::V* with P = decltype(p).
+template <typename F>
+void with_format(const pic_handle* h, F&& f) {
+  if (h->fmt == FMT_F64) f(PosF64{});
+  else if (h->fmt == FMT_F32) f(PosF32{});
+  else f(PosU32{});
+}
+
+// force evaluations per step of an integrator (pic_get_integrator, pic_step_stage)
+int evals_per_step(int scheme) { return scheme == PIC_YOSHIDA4 ? 3 : (scheme == PIC_VERLET ? 2 : 1); }
+
 void yoshida_coefficients(double (&c)[4], double (&d)[4]) {
   // integration.py:62-69, same expressions in the same order
   const double cbrt2 = std::pow(2.0, 1.0 / 3.0);
@@ -372,25 +384,42 @@ void prof_end(pic_handle* h) {
   hipEventRecord(h->ev[2 * (h->ev_kind.size() - 1) + 1], h->stream);
 }
 
+// The SweepArgs fields the push sweeps and the resident kernel share: geometry, fixed point, units.  The rest (the sweeps'
+// partition, ring sub-rows and stage coefficients; the resident kernel's LDS replicas) is the caller's.
+SweepArgs sweep_args(const pic_handle* h) {
+  SweepArgs a{};
+  a.N = h->cfg.N; a.ld = h->ld; a.Ng = h->cfg.Ng;
+  a.fg = h->fg; a.magic = h->magic;
+  a.L = h->cfg.L; a.dx = h->dx; a.dt = h->cfg.dt;
+  a.rdx = h->fmt == FMT_F64 ? 1.0 / h->dx : (double)(1.0f / (float)h->dx);
+  a.scale = h->scale; a.n0 = h->cfg.n0;
+  a.to_units = 4294967296.0 / h->cfg.L;
+  a.N_over_L = (double)h->cfg.N / h->cfg.L;
+  return a;
+}
+
+// SolveArgs of a field solve that reads S sub-rows of its accumulator row
+SolveArgs solve_args(const pic_handle* h, int S) {
+  SolveArgs a{};
+  a.N = h->cfg.N; a.Ng = h->cfg.Ng; a.nblk = h->nblk; a.fg = h->fg; a.L = h->cfg.L; a.dx = h->dx; a.n0 = h->cfg.n0;
+  a.scale = h->scale; a.N_over_L = (double)h->cfg.N / h->cfg.L;
+  a.S = S; a.sub = (long long)h->cfg.num_envs * h->cfg.Ng;
+  return a;
+}
+
 // One sweep over all environments.  in_slot: ring row the gather field is solved from (gather stages);
 // out / out2: rows (or the probe accumulator) receiving the deposits.  The sweep also clears up to two
 // retired ring rows for later use.
 void launch_sweep(pic_handle* h, int stage, void* x, void* v, double c_prev, double c_cur, double d_cur,
                   int in_slot, const Control& ctl, acc_t* out, acc_t* out2, int post_slot = -1, double* ext_out = nullptr,
                   const double* next_act = nullptr) {
-  SweepArgs a;
-  a.N = h->cfg.N; a.ld = h->ld; a.chunk = h->chunk; a.Ng = h->cfg.Ng; a.nblk = h->nblk; a.R = h->R;
+  SweepArgs a = sweep_args(h);
+  a.chunk = h->chunk; a.nblk = h->nblk; a.R = h->R;
   a.act_inline = (ctl.act && h->inline_act) ? 1 : 0;
   const bool push = stage <= ST_D || stage == ST_B2 || stage == ST_D2 || stage >= ST_SE;
   a.reverse = push ? (h->sweep_parity ^= 1) : 0;
-  a.fg = h->fg; a.magic = h->magic;
   a.S = h->S; a.sub = (long long)h->cfg.num_envs * h->cfg.Ng;
-  a.L = h->cfg.L; a.dx = h->dx; a.dt = h->cfg.dt;
-  a.rdx = h->fmt == FMT_F64 ? 1.0 / h->dx : (double)(1.0f / (float)h->dx);
   a.c_prev = c_prev; a.c_cur = c_cur; a.d_cur = d_cur; a.c_next = h->cs[0];
-  a.scale = h->scale; a.n0 = h->cfg.n0;
-  a.to_units = 4294967296.0 / h->cfg.L;
-  a.N_over_L = (double)h->cfg.N / h->cfg.L;
   SweepIO io{};
   io.acc_in = in_slot >= 0 ? ring_row(h, in_slot) : nullptr;
   io.ctl = ctl;
@@ -416,9 +445,7 @@ void launch_sweep(pic_handle* h, int stage, void* x, void* v, double c_prev, dou
   // (the particle sweeps of the other integrators -- Verlet's opening sweep is a sweep C -- count in the eighth kind)
   const bool scheme_sweep = stage >= ST_SE || (stage == ST_C && h->scheme != PIC_YOSHIDA4);
   prof_begin(h, scheme_sweep ? 7 : stage <= ST_D ? stage : (stage == ST_B2 ? (int)ST_B : (stage == ST_D2 ? (int)ST_D : 5)));
-  if (h->fmt == FMT_F64) launch_sweep_p<PosF64>(h, io, stage, x, v, a);
-  else if (h->fmt == FMT_F32) launch_sweep_p<PosF32>(h, io, stage, x, v, a);
-  else launch_sweep_p<PosU32>(h, io, stage, x, v, a);
+  with_format(h, [&](auto p) { launch_sweep_p<decltype(p)>(h, io, stage, x, v, a); });
   prof_end(h);
   for (int k = 0; k < 2; ++k)
     if (z[k] >= 0) h->clean.push_back(z[k]);      // zero for every LATER launch of this stream
@@ -483,18 +510,31 @@ struct StepControl {
   // one held action of few coefficients, given on the host: inside the resident kernel's own argument block (no copy, no launch)
   int inline_n = 0;
   InlineDoubles inline_act{};
+
+  // the control of the same call from its step s on (E environments): the per-step fields / actions and the feedback law's
+  // per-step records (actions, the gain law's modes) moved on by s steps
+  StepControl after(size_t s, int E) const {
+    StepControl o = *this;
+    if (o.ctl.ext) o.ctl.ext += s * ext_step;
+    if (o.ctl.act) o.ctl.act += s * act_step;
+    const size_t row = (size_t)E * 2 * fb.M;
+    if (o.fb.act_hist) o.fb.act_hist += s * row;
+    if (o.fb.modes_hist) o.fb.modes_hist += s * row;
+    return o;
+  }
 };
+
+// the entries of step s in a call's per-step records: energies hist [nsteps][3][env], particles snap [nsteps][2][env][N]
+// (either may be null)
+double* hist_at(const pic_handle* h, double* hist, size_t s) { return hist ? hist + s * 3 * h->cfg.num_envs : nullptr; }
+void* snap_at(const pic_handle* h, void* snap, size_t s) {
+  return snap ? static_cast<char*>(snap) + s * 2 * h->cfg.num_envs * (size_t)h->cfg.N * h->esz : nullptr;
+}
 
 // nsteps environment steps in one launch of the resident schedule; hist: device [nsteps][3][env] or null
 void launch_resident(pic_handle* h, const StepControl& sc, int nsteps, double* hist, void* snap = nullptr) {
-  SweepArgs a{};
-  a.N = h->cfg.N; a.ld = h->ld; a.Ng = h->cfg.Ng; a.R = h->res_R;
-  a.fg = h->fg; a.magic = h->magic;
-  a.L = h->cfg.L; a.dx = h->dx; a.dt = h->cfg.dt;
-  a.rdx = h->fmt == FMT_F64 ? 1.0 / h->dx : (double)(1.0f / (float)h->dx);
-  a.scale = h->scale; a.n0 = h->cfg.n0;
-  a.to_units = 4294967296.0 / h->cfg.L;
-  a.N_over_L = (double)h->cfg.N / h->cfg.L;
+  SweepArgs a = sweep_args(h);
+  a.R = h->res_R;
   ResidentIO io{};
   io.nsteps = nsteps; io.num_envs = h->cfg.num_envs;
   io.c1 = h->cs[0]; io.c2 = h->cs[1]; io.d1 = h->ds[1]; io.d2 = h->ds[2];
@@ -510,19 +550,14 @@ void launch_resident(pic_handle* h, const StepControl& sc, int nsteps, double* h
   io.mode = (sc.inline_n > 0 ? RM_ACT_INLINE : 0) | (sc.ctl.ext || sc.ctl.act || sc.fb.M > 0 ? RM_EXT : 0) | (sc.ext_step || sc.act_step ? RM_PER_STEP : 0) |
             (sc.fb.M > 0 ? RM_FEEDBACK : 0) | (snap ? RM_SNAP : 0) | (hist || sc.fb.M > 0 ? RM_RECORD : 0);
   prof_begin(h, 6);
-  if (h->fmt == FMT_F64) launch_resident_p<PosF64>(h, io, a, sc.inline_act);
-  else if (h->fmt == FMT_F32) launch_resident_p<PosF32>(h, io, a, sc.inline_act);
-  else launch_resident_p<PosU32>(h, io, a, sc.inline_act);
+  with_format(h, [&](auto p) { launch_resident_p<decltype(p)>(h, io, a, sc.inline_act); });
   prof_end(h);
 }
 
 void launch_solve(pic_handle* h, const SolveIO& io) {
-  SolveArgs a;
-  a.N = h->cfg.N; a.Ng = h->cfg.Ng; a.nblk = h->nblk; a.fg = h->fg; a.L = h->cfg.L; a.dx = h->dx; a.n0 = h->cfg.n0;
-  a.scale = h->scale; a.N_over_L = (double)h->cfg.N / h->cfg.L;
-  a.S = io.acc ? h->S : 1; a.sub = (long long)h->cfg.num_envs * h->cfg.Ng;
   prof_begin(h, 4);
-  hipLaunchKernelGGL(field_solve_kernel, dim3(h->cfg.num_envs), dim3(SBLOCK), h->solve_lds, h->stream, io, a);
+  hipLaunchKernelGGL(field_solve_kernel, dim3(h->cfg.num_envs), dim3(SBLOCK), h->solve_lds, h->stream, io,
+                     solve_args(h, io.acc ? h->S : 1));
   prof_end(h);
 }
 
@@ -623,38 +658,32 @@ int download_positions(pic_handle* h, void* dst, const void* src_padded, int mem
 }
 
 // mesh [env][Ng] gathered at the positions x [env][ld] with the handle's shape function -> out, dense [env][N]
-template <typename P>
-void launch_gather_p(pic_handle* h, const void* x, const double* mesh, void* out) {
-  const dim3 grid = aux_grid(h, h->cfg.num_envs);
-  const size_t lds = ((size_t)h->cfg.Ng + 2) * sizeof(typename P::W);
-  if (h->cfg.interpol == PIC_TSC)
-    hipLaunchKernelGGL((gather_E_kernel<P, PIC_TSC>), grid, dim3(BLOCK), lds, h->stream, (const typename P::X*)x, mesh,
-                       (typename P::W*)out, h->cfg.N, h->ld, h->cfg.Ng, h->cfg.L, h->dx);
-  else
-    hipLaunchKernelGGL((gather_E_kernel<P, PIC_CIC>), grid, dim3(BLOCK), lds, h->stream, (const typename P::X*)x, mesh,
-                       (typename P::W*)out, h->cfg.N, h->ld, h->cfg.Ng, h->cfg.L, h->dx);
-}
 void launch_gather(pic_handle* h, const void* x, const double* mesh, void* out) {
-  if (h->fmt == FMT_F64) launch_gather_p<PosF64>(h, x, mesh, out);
-  else if (h->fmt == FMT_F32) launch_gather_p<PosF32>(h, x, mesh, out);
-  else launch_gather_p<PosU32>(h, x, mesh, out);
+  const dim3 grid = aux_grid(h, h->cfg.num_envs);
+  with_format(h, [&](auto p) {
+    using P = decltype(p);
+    const size_t lds = ((size_t)h->cfg.Ng + 2) * sizeof(typename P::W);
+    if (h->cfg.interpol == PIC_TSC)
+      hipLaunchKernelGGL((gather_E_kernel<P, PIC_TSC>), grid, dim3(BLOCK), lds, h->stream, (const typename P::X*)x, mesh,
+                         (typename P::W*)out, h->cfg.N, h->ld, h->cfg.Ng, h->cfg.L, h->dx);
+    else
+      hipLaunchKernelGGL((gather_E_kernel<P, PIC_CIC>), grid, dim3(BLOCK), lds, h->stream, (const typename P::X*)x, mesh,
+                         (typename P::W*)out, h->cfg.N, h->ld, h->cfg.Ng, h->cfg.L, h->dx);
+  });
 }
 
 // indices and weights of `nenv` environments' worth of positions x [nenv][ld] -> idx, w [nenv][3][N]
-template <typename P>
-void launch_shape_query_p(pic_handle* h, const void* x, int nenv, int shape, long long* idx, double* w) {
-  const dim3 grid = aux_grid(h, nenv);
-  if (shape == PIC_TSC)
-    hipLaunchKernelGGL((shape_query_kernel<P, PIC_TSC>), grid, dim3(BLOCK), 0, h->stream, (const typename P::X*)x, h->cfg.N,
-                       h->ld, h->cfg.Ng, h->cfg.L, h->dx, idx, w);
-  else
-    hipLaunchKernelGGL((shape_query_kernel<P, PIC_CIC>), grid, dim3(BLOCK), 0, h->stream, (const typename P::X*)x, h->cfg.N,
-                       h->ld, h->cfg.Ng, h->cfg.L, h->dx, idx, w);
-}
 void launch_shape_query(pic_handle* h, const void* x, int nenv, int shape, long long* idx, double* w) {
-  if (h->fmt == FMT_F64) launch_shape_query_p<PosF64>(h, x, nenv, shape, idx, w);
-  else if (h->fmt == FMT_F32) launch_shape_query_p<PosF32>(h, x, nenv, shape, idx, w);
-  else launch_shape_query_p<PosU32>(h, x, nenv, shape, idx, w);
+  const dim3 grid = aux_grid(h, nenv);
+  with_format(h, [&](auto p) {
+    using P = decltype(p);
+    if (shape == PIC_TSC)
+      hipLaunchKernelGGL((shape_query_kernel<P, PIC_TSC>), grid, dim3(BLOCK), 0, h->stream, (const typename P::X*)x, h->cfg.N,
+                         h->ld, h->cfg.Ng, h->cfg.L, h->dx, idx, w);
+    else
+      hipLaunchKernelGGL((shape_query_kernel<P, PIC_CIC>), grid, dim3(BLOCK), 0, h->stream, (const typename P::X*)x, h->cfg.N,
+                         h->ld, h->cfg.Ng, h->cfg.L, h->dx, idx, w);
+  });
 }
 
 }  // namespace
@@ -1291,6 +1320,8 @@ int pic_refresh(pic_handle* h) {
 int pic_reset(pic_handle* h, const void* x0, const void* v0, int mem_kind) {
   if (!h) return PIC_EINVAL;
   if (h->tape.on) return fail(h, PIC_ESTATE, "pic_reset: refused while a tape is open (pic_tape_stop first)");
+  // (before resume_placement: a leg may move v, and a reset refused after that would leave garbage behind has_state)
+  if (!x0 || !v0) return fail(h, PIC_EINVAL, "pic_set_particles: null argument");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   resume_placement(h);
   HIPCHK(h, hipMemsetAsync(h->bad, 0, sizeof(unsigned long long), h->stream));
@@ -1412,13 +1443,6 @@ static int ensure_twiddle(pic_handle* h, int rows) {
   return PIC_OK;
 }
 
-// the per-step records of a feedback call (actions, the gain law's modes) moved on by `steps` steps
-static void fb_skip(Feedback& fb, size_t steps, int E) {
-  const size_t row = (size_t)E * 2 * fb.M;
-  if (fb.act_hist) fb.act_hist += steps * row;
-  if (fb.modes_hist) fb.modes_hist += steps * row;
-}
-
 // ---- the other integrators on the streaming schedule (pic_set_integrator) ----------------------------------------
 // Between steps h->q_slot holds the deposit of the stored, wrapped x: the post-step deposit of the step before, which is also the
 // field of the next step's (first) force evaluation -- one row, no first drift to deposit.  Where it is missing (particles loaded
@@ -1464,37 +1488,6 @@ static void run_scheme_step(pic_handle* h, const Control& ctl, int only, bool me
   }
 }
 
-static void advance_scheme(pic_handle* h, const StepControl& sc, int nsteps, double* hist) {
-  const int E = h->cfg.num_envs;
-  h->inline_act = sc.inline_n > 0 ? &sc.inline_act : nullptr;
-  // Verlet merges where the two half-kicks of a merged sweep see one external field: held for the call.  A new field every step,
-  // or the feedback law's (whose action needs the post-step solve first), runs two sweeps per step.
-  const bool held = sc.fb.M == 0 && sc.ext_step == 0 && sc.act_step == 0;
-  bool open = false;
-  for (int s = 0; s < nsteps; ++s) {
-    Control ctl = sc.ctl;
-    if (ctl.ext) ctl.ext += (size_t)s * sc.ext_step;
-    if (ctl.act) ctl.act += (size_t)s * sc.act_step;
-    h->hist_row = hist ? hist + (size_t)s * 3 * E : nullptr;
-    if (sc.fb.M > 0) {                                       // as advance_steps
-      Feedback fb = sc.fb;
-      fb.act_out = h->act;
-      if (s == 0) hipLaunchKernelGGL(feedback_kernel, dim3(E), dim3(BLOCK), 0, h->stream, h->E_mesh, fb, h->cfg.Ng);
-      ctl.act = h->act;
-      ctl.ext = nullptr;
-      h->fb = Feedback{};
-      if (s + 1 < nsteps) {
-        h->fb = fb;
-        fb_skip(h->fb, s + 1, E);
-      }
-    }
-    run_scheme_step(h, ctl, 0, held && s + 1 < nsteps, &open);
-  }
-  h->hist_row = nullptr;
-  h->fb = Feedback{};
-  h->inline_act = nullptr;
-}
-
 // nsteps x PIC.update_state under `sc`, all launches enqueued, no host synchronisation.  hist: device [nsteps][3][env] record of
 // the energies, or null; snap (resident schedule only): device record of the particles.
 static int advance_steps(pic_handle* h, const StepControl& sc, int nsteps, double* hist, void* snap) {
@@ -1513,41 +1506,42 @@ static int advance_steps(pic_handle* h, const StepControl& sc, int nsteps, doubl
     HIPCHK(h, e);
     return PIC_OK;
   }
-  if (h->scheme != PIC_YOSHIDA4) {
-    advance_scheme(h, sc, nsteps, hist);
-    HIPCHK(h, launch_status(h));
-    return PIC_OK;
-  }
   h->inline_act = sc.inline_n > 0 ? &sc.inline_act : nullptr;      // (launch_sweep: the held action inside the sweeps' arguments)
+  // (Yoshida-4: the actuator's field of step s is built by sweep B of step 0, after that by the previous step's sweep D -- or,
+  // under a held action, still the one step 0 left; the feedback law's action exists only after the post-step solve: every step
+  // builds)
+  const bool rollout = sc.fb.M == 0 && sc.ctl.act != nullptr;
+  // Verlet merges where the two half-kicks of a merged sweep see one external field: held for the call.  A new field every step,
+  // or the feedback law's (whose action needs the post-step solve first), runs two sweeps per step.
+  const bool held = sc.fb.M == 0 && sc.ext_step == 0 && sc.act_step == 0;
+  bool open = false;
   for (int s = 0; s < nsteps; ++s) {
-    Control ctl = sc.ctl;
-    if (ctl.ext) ctl.ext += (size_t)s * sc.ext_step;
-    if (ctl.act) ctl.act += (size_t)s * sc.act_step;
-    h->hist_row = hist ? hist + (size_t)s * 3 * E : nullptr;
-    bool rides = s + 1 < nsteps;     // the post-step solve rides with the next step's sweep B
+    const bool last = s + 1 == nsteps;
+    Control ctl = sc.after(s, E).ctl;
+    h->hist_row = hist_at(h, hist, s);
     if (sc.fb.M > 0) {
       // The action of step s is the feedback law's on the field step s-1 left: the post-step solve is on the critical path
       // (a launch of its own that also computes the next action); before the first step a small kernel does it.
-      Feedback fb = sc.fb;
-      fb.act_out = h->act;
       if (s == 0) {
+        Feedback fb = sc.fb;
+        fb.act_out = h->act;
         hipLaunchKernelGGL(feedback_kernel, dim3(E), dim3(BLOCK), 0, h->stream, h->E_mesh, fb, h->cfg.Ng);
       }
       ctl.act = h->act;
       ctl.ext = nullptr;
-      rides = false;
       h->fb = Feedback{};
-      if (s + 1 < nsteps) {
-        h->fb = fb;
-        fb_skip(h->fb, s + 1, E);
+      if (!last) {
+        h->fb = sc.after(s + 1, E).fb;
+        h->fb.act_out = h->act;
       }
     }
-    // (the actuator's field of step s: built by sweep B of step 0, after that by the previous step's sweep D -- or, under a
-    // held action, still the one step 0 left; the feedback law's action exists only after the post-step solve: every step builds)
-    const bool rollout = sc.fb.M == 0 && sc.ctl.act != nullptr;
-    const bool held = rollout && sc.act_step == 0;
-    const double* next_act = (rollout && !held && s + 1 < nsteps) ? ctl.act + sc.act_step : nullptr;
-    run_stages(h, 1, 3, ctl, rides, rollout && s > 0, next_act);
+    if (h->scheme == PIC_YOSHIDA4) {
+      // the post-step solve rides with the next step's sweep C, but for the last step's and the feedback law's
+      const double* next_act = (rollout && sc.act_step != 0 && !last) ? sc.after(s + 1, E).ctl.act : nullptr;
+      run_stages(h, 1, 3, ctl, !last && sc.fb.M == 0, rollout && s > 0, next_act);
+    } else {
+      run_scheme_step(h, ctl, 0, held && !last, &open);
+    }
   }
   h->hist_row = h->post_hist_row = nullptr;
   h->fb = Feedback{};
@@ -1577,12 +1571,11 @@ static int record_enqueue(pic_handle* h) {
   ha.spx = r.px ? (h->cfg.L - 0.0) / r.px : 0.0;
   ha.spv = r.pv ? (r.vmax - r.vmin) / r.pv : 0.0;
   const dim3 grid(r.gx, E);
-  if (h->fmt == FMT_F64)
-    hipLaunchKernelGGL(record_hist_kernel<PosF64>, grid, dim3(BLOCK), r.lds, h->stream, (const double*)h->x, (const double*)h->v, ha);
-  else if (h->fmt == FMT_F32)
-    hipLaunchKernelGGL(record_hist_kernel<PosF32>, grid, dim3(BLOCK), r.lds, h->stream, (const float*)h->x, (const float*)h->v, ha);
-  else
-    hipLaunchKernelGGL(record_hist_kernel<PosU32>, grid, dim3(BLOCK), r.lds, h->stream, (const unsigned*)h->x, (const float*)h->v, ha);
+  with_format(h, [&](auto p) {
+    using P = decltype(p);
+    hipLaunchKernelGGL(record_hist_kernel<P>, grid, dim3(BLOCK), r.lds, h->stream, (const typename P::X*)h->x,
+                       (const typename P::V*)h->v, ha);
+  });
   RecordFinishArgs fa{};
   fa.E_mesh = h->E_mesh; fa.KE = h->KE; fa.tw = h->tw; fa.tw_rows = h->tw_rows; fa.Ng = h->cfg.Ng; fa.M = r.M; fa.dx = h->dx;
   fa.rec = r.d + (size_t)slot * E * r.d_stride;
@@ -1600,32 +1593,6 @@ static int record_enqueue(pic_handle* h) {
 static int64_t records_ahead(const pic_handle* h, int64_t nsteps) {
   const Recorder& r = h->rec;
   return r.on ? (r.k + nsteps) / r.stride - r.k / r.stride : 0;
-}
-
-// advance_steps with the recorder: the steps are cut behind every recorded step, which therefore ends like the last step of a
-// call (full sweep D and a solve launch of its own; resident schedule: the end of a launch) -- stepping call by call gives the
-// same bits -- and the record kernels follow it on the stream.
-static int advance_recorded(pic_handle* h, const StepControl& sc, int nsteps, double* hist, void* snap) {
-  Recorder& r = h->rec;
-  if (!r.on || nsteps <= 0) return advance_steps(h, sc, nsteps, hist, snap);
-  const int E = h->cfg.num_envs;
-  for (int done = 0; done < nsteps;) {
-    const int n = (int)std::min<int64_t>(r.stride - r.k % r.stride, nsteps - done);
-    StepControl part = sc;
-    if (part.ctl.ext) part.ctl.ext += (size_t)done * sc.ext_step;
-    if (part.ctl.act) part.ctl.act += (size_t)done * sc.act_step;
-    fb_skip(part.fb, done, E);
-    int rc = advance_steps(h, part, n, hist ? hist + (size_t)done * 3 * E : nullptr,
-                           snap ? static_cast<char*>(snap) + (size_t)done * 2 * E * (size_t)h->cfg.N * h->esz : nullptr);
-    if (rc) return rc;
-    r.k += n;
-    done += n;
-    if (r.k % r.stride == 0) {
-      rc = record_enqueue(h);
-      if (rc) return rc;
-    }
-  }
-  return PIC_OK;
 }
 
 // e_t of n steps of `sc` into the tape (pic_adjoint.h: tape_ext_kernel)
@@ -1650,35 +1617,43 @@ static int tape_checkpoint(pic_handle* h, int64_t c) {
   return PIC_OK;
 }
 
-// advance_recorded (and the recorder) under an open tape: the calls are cut behind every checkpoint step, as the recorder cuts
-// them behind a recorded step (same bits), each part's external fields go on the tape first and the state after a checkpoint
-// step is copied out.
+// advance_steps, cut into parts where the recorder or an open tape needs the state between two steps.  A part runs up to the
+// nearest of the next recorded step, the next checkpoint step and the end of the call; such a step therefore ends like the last
+// step of a call (full sweep D and a solve launch of its own; resident schedule: the end of a launch) -- stepping call by call
+// gives the same bits.  Behind a part come the record kernels of a recorded step, then the tape's copy of the
+// state after a checkpoint step.  Under a tape each part's external fields go on the tape first.
 static int advance(pic_handle* h, const StepControl& sc, int nsteps, double* hist, void* snap = nullptr) {
+  Recorder& r = h->rec;
   Tape& t = h->tape;
-  if (!t.on || nsteps <= 0) return advance_recorded(h, sc, nsteps, hist, snap);
   const int E = h->cfg.num_envs;
   for (int done = 0; done < nsteps;) {
-    const int n = (int)std::min<int64_t>(t.every - t.steps % t.every, nsteps - done);
-    StepControl part = sc;
-    if (part.ctl.ext) part.ctl.ext += (size_t)done * sc.ext_step;
-    if (part.ctl.act) part.ctl.act += (size_t)done * sc.act_step;
-    fb_skip(part.fb, done, E);
-    int rc = part.fb.M > 0 ? PIC_OK : tape_record_ext(h, part, n);
+    int64_t n = nsteps - done;
+    if (r.on) n = std::min<int64_t>(n, r.stride - r.k % r.stride);
+    if (t.on) n = std::min<int64_t>(n, t.every - t.steps % t.every);
+    const StepControl part = sc.after(done, E);
+    int rc = t.on && part.fb.M == 0 ? tape_record_ext(h, part, (int)n) : PIC_OK;
     if (rc) return rc;
-    rc = advance_recorded(h, part, n, hist ? hist + (size_t)done * 3 * E : nullptr,
-                          snap ? static_cast<char*>(snap) + (size_t)done * 2 * E * (size_t)h->cfg.N * h->esz : nullptr);
+    rc = advance_steps(h, part, (int)n, hist_at(h, hist, done), snap_at(h, snap, done));
     if (rc) return rc;
+    done += (int)n;
+    if (r.on) {
+      r.k += n;
+      if (r.k % r.stride == 0) {
+        rc = record_enqueue(h);
+        if (rc) return rc;
+      }
+    }
+    if (!t.on) continue;
     if (part.fb.M > 0) {
       // the gain law's actions exist only once their steps have run: e_t = B a_t from the actions the steps wrote on the tape
       // (pic_step_feedback_gain points act_hist at its rows)
       StepControl made{};
       made.ctl.basis = sc.ctl.basis; made.ctl.M = sc.ctl.M; made.ctl.act = part.fb.act_hist;
       made.act_step = (long long)E * 2 * sc.ctl.M;
-      rc = tape_record_ext(h, made, n);
+      rc = tape_record_ext(h, made, (int)n);
       if (rc) return rc;
     }
     t.steps += n;
-    done += n;
     if (t.steps % t.every == 0) {
       rc = tape_checkpoint(h, t.steps / t.every);
       if (rc) return rc;
@@ -1691,15 +1666,15 @@ int pic_step_stage(pic_handle* h, int stage, const double* E_ext, int mem_kind) 
   if (!h) return PIC_EINVAL;
   if (h->tape.on) return fail(h, PIC_ESTATE, "pic_step_stage: refused while a tape is open (pic_tape_stop first)");
   if (!h->has_state) return fail(h, PIC_ESTATE, "pic_step_stage: call pic_reset first");
-  const int S = h->scheme == PIC_YOSHIDA4 ? 3 : (h->scheme == PIC_VERLET ? 2 : 1);      // force evaluations per step
+  const int S = evals_per_step(h->scheme);
   if (stage < 1 || stage > S || stage != h->mid_stage + 1)
     return fail(h, PIC_ESTATE, "pic_step_stage: stages run in the order 1.." + std::to_string(S) + " of the handle's integrator");
+  if (stage == 1 && h->rec.on && (int64_t)h->rec.steps.size() + records_ahead(h, 1) > h->rec.cap)
+    return fail(h, PIC_ENOMEM, "pic_step_stage: the step would take the recorder past its capacity");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   Control ctl{};
   int rc = stage_ext(h, E_ext, mem_kind, &ctl.ext);
   if (rc) return rc;
-  if (stage == 1 && h->rec.on && (int64_t)h->rec.steps.size() + records_ahead(h, 1) > h->rec.cap)
-    return fail(h, PIC_ENOMEM, "pic_step_stage: the step would take the recorder past its capacity");
   h->res_q1_valid = false;           // (a resident handle steps by sweeps here: its carried q1 mesh goes stale)
   if (h->scheme == PIC_YOSHIDA4) run_stages(h, stage, stage, ctl);
   else run_scheme_step(h, ctl, S == 1 ? 0 : stage, false, nullptr);
@@ -1720,10 +1695,10 @@ int pic_set_integrator(pic_handle* h, int scheme) {
   return PIC_OK;
 }
 
-int pic_get_integrator(pic_handle* h, int* scheme, int* evals_per_step) {
+int pic_get_integrator(pic_handle* h, int* scheme, int* evals) {
   if (!h) return PIC_EINVAL;
   if (scheme) *scheme = h->scheme;
-  if (evals_per_step) *evals_per_step = h->scheme == PIC_YOSHIDA4 ? 3 : (h->scheme == PIC_VERLET ? 2 : 1);
+  if (evals) *evals = evals_per_step(h->scheme);
   return PIC_OK;
 }
 
@@ -1739,11 +1714,19 @@ static int check_steppable(pic_handle* h, int nsteps, const char* who) {
   return PIC_OK;
 }
 
-int pic_step(pic_handle* h, const double* E_ext, int mem_kind, int nsteps) {
-  if (!h) return PIC_EINVAL;
-  int rc = check_steppable(h, nsteps, "pic_step");
+// The head of every stepping entry point: the handle, the entry point's own argument check (bad_args: what is wrong, or null),
+// check_steppable, the device.  Nothing has been enqueued or changed when it fails.
+static int step_prologue(pic_handle* h, int nsteps, const char* who, const char* bad_args = nullptr) {
+  if (!h || bad_args) return fail(h, PIC_EINVAL, std::string(who) + ": " + (bad_args ? bad_args : "null argument"));
+  int rc = check_steppable(h, nsteps, who);
   if (rc) return rc;
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  return PIC_OK;
+}
+
+int pic_step(pic_handle* h, const double* E_ext, int mem_kind, int nsteps) {
+  int rc = step_prologue(h, nsteps, "pic_step");
+  if (rc) return rc;
   StepControl sc;
   rc = stage_ext(h, E_ext, mem_kind, &sc.ctl.ext);
   if (rc) return rc;
@@ -1781,21 +1764,13 @@ static int step_recording(pic_handle* h, StepControl sc, int nsteps, double* his
     // particle snapshots on the streaming schedule: step by step, a copy kernel after each
     const dim3 grid = aux_grid(h, E);
     for (int s = 0; s < nsteps && rc == PIC_OK; ++s) {
-      StepControl one = sc;
-      if (one.ctl.ext) one.ctl.ext += (size_t)s * sc.ext_step;
-      if (one.ctl.act) one.ctl.act += (size_t)s * sc.act_step;
-      fb_skip(one.fb, s, E);
-      rc = advance(h, one, 1, dh ? dh + (size_t)s * 3 * E : nullptr);
+      rc = advance(h, sc.after(s, E), 1, hist_at(h, dh, s));
       if (rc != PIC_OK) break;
-      if (h->fmt == FMT_F64)
-        hipLaunchKernelGGL(record_particles_kernel<PosF64>, grid, dim3(BLOCK), 0, h->stream, (const double*)h->x,
-                           (const double*)h->v, (double*)ds, s, h->cfg.N, h->ld, h->cfg.L);
-      else if (h->fmt == FMT_F32)
-        hipLaunchKernelGGL(record_particles_kernel<PosF32>, grid, dim3(BLOCK), 0, h->stream, (const float*)h->x,
-                           (const float*)h->v, (float*)ds, s, h->cfg.N, h->ld, h->cfg.L);
-      else
-        hipLaunchKernelGGL(record_particles_kernel<PosU32>, grid, dim3(BLOCK), 0, h->stream, (const unsigned*)h->x,
-                           (const float*)h->v, (float*)ds, s, h->cfg.N, h->ld, h->cfg.L);
+      with_format(h, [&](auto p) {
+        using P = decltype(p);
+        hipLaunchKernelGGL(record_particles_kernel<P>, grid, dim3(BLOCK), 0, h->stream, (const typename P::X*)h->x,
+                           (const typename P::V*)h->v, (typename P::V*)ds, s, h->cfg.N, h->ld, h->cfg.L);
+      });
     }
   }
   hipError_t e = hipGetLastError();
@@ -1816,26 +1791,23 @@ static int step_recording(pic_handle* h, StepControl sc, int nsteps, double* his
   return PIC_OK;
 }
 
-int pic_step_history(pic_handle* h, const double* E_ext, int mem_kind, int nsteps, double* hist) {
-  if (!h || !hist) return fail(h, PIC_EINVAL, "pic_step_history: null argument");
-  int rc = check_steppable(h, nsteps, "pic_step_history");
+// pic_step_history and pic_step_snapshots: a held field (or none), the energies and / or the particles of every step read back
+static int step_held_recorded(pic_handle* h, const double* E_ext, int mem_kind, int nsteps, void* snap, double* hist,
+                              const char* who, bool args_ok) {
+  int rc = step_prologue(h, nsteps, who, args_ok ? nullptr : "null argument");
   if (rc) return rc;
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
   StepControl sc;
   rc = stage_ext(h, E_ext, mem_kind, &sc.ctl.ext);
   if (rc) return rc;
-  return step_recording(h, sc, nsteps, hist, nullptr, nullptr, "pic_step_history");
+  return step_recording(h, sc, nsteps, hist, snap, nullptr, who);
+}
+
+int pic_step_history(pic_handle* h, const double* E_ext, int mem_kind, int nsteps, double* hist) {
+  return step_held_recorded(h, E_ext, mem_kind, nsteps, nullptr, hist, "pic_step_history", hist != nullptr);
 }
 
 int pic_step_snapshots(pic_handle* h, const double* E_ext, int mem_kind, int nsteps, void* snap, double* hist) {
-  if (!h || !snap) return fail(h, PIC_EINVAL, "pic_step_snapshots: null argument");
-  int rc = check_steppable(h, nsteps, "pic_step_snapshots");
-  if (rc) return rc;
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  StepControl sc;
-  rc = stage_ext(h, E_ext, mem_kind, &sc.ctl.ext);
-  if (rc) return rc;
-  return step_recording(h, sc, nsteps, hist, snap, nullptr, "pic_step_snapshots");
+  return step_held_recorded(h, E_ext, mem_kind, nsteps, snap, hist, "pic_step_snapshots", snap != nullptr);
 }
 
 // a per-step input trajectory [nsteps][row] (host or device) -> device pointer
@@ -1851,10 +1823,8 @@ static int stage_traj(pic_handle* h, const double* src, int mem_kind, size_t row
 }
 
 int pic_step_ext_traj(pic_handle* h, const double* E_ext_traj, int mem_kind, int nsteps, double* hist, void* snap) {
-  if (!h || !E_ext_traj) return fail(h, PIC_EINVAL, "pic_step_ext_traj: null argument");
-  int rc = check_steppable(h, nsteps, "pic_step_ext_traj");
+  int rc = step_prologue(h, nsteps, "pic_step_ext_traj", E_ext_traj ? nullptr : "null argument");
   if (rc) return rc;
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
   StepControl sc;
   sc.ext_step = (long long)h->cfg.num_envs * h->cfg.Ng;
   rc = stage_traj(h, E_ext_traj, mem_kind, (size_t)sc.ext_step, nsteps, &sc.ctl.ext);
@@ -2215,11 +2185,24 @@ static int actuator_control(pic_handle* h, StepControl& sc, const char* who) {
   return PIC_OK;
 }
 
-int pic_step_actions(pic_handle* h, const double* actions, int mem_kind, int nsteps) {
-  if (!h || !actions) return fail(h, PIC_EINVAL, "pic_step_actions: null argument");
-  int rc = check_steppable(h, nsteps, "pic_step_actions");
+// The feedback law of a call (pic_step_feedback, pic_step_feedback_gain) on the actuator's modes, with their twiddles (a call of
+// no steps checks and makes none)
+static int feedback_control(pic_handle* h, int max_mode, int nsteps, StepControl& sc, const char* who) {
+  int rc = actuator_control(h, sc, who);
   if (rc) return rc;
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (max_mode != h->act_modes || max_mode > kMaxFeedbackModes)
+    return fail(h, PIC_EINVAL, std::string(who) + ": max_mode must equal the actuator's (pic_set_actuator) and be at most 16");
+  if (nsteps == 0) return PIC_OK;
+  rc = ensure_twiddle(h, max_mode);
+  if (rc) return rc;
+  sc.fb.tw = h->tw; sc.fb.rows = h->tw_rows; sc.fb.M = max_mode;
+  sc.fb.act_out = h->act;
+  return PIC_OK;
+}
+
+int pic_step_actions(pic_handle* h, const double* actions, int mem_kind, int nsteps) {
+  int rc = step_prologue(h, nsteps, "pic_step_actions", actions ? nullptr : "null argument");
+  if (rc) return rc;
   StepControl sc;
   rc = actuator_control(h, sc, "pic_step_actions");
   if (rc) return rc;
@@ -2233,11 +2216,8 @@ int pic_step_actions(pic_handle* h, const double* actions, int mem_kind, int nst
 
 int pic_step_observe(pic_handle* h, const double* E_ext, const double* actions, int nsteps, void* x, void* v, double* KE,
                      double* PE, double* PE_reward) {
-  if (!h) return PIC_EINVAL;
-  if (E_ext && actions) return fail(h, PIC_EINVAL, "pic_step_observe: E_ext and actions are alternatives");
-  int rc = check_steppable(h, nsteps, "pic_step_observe");
+  int rc = step_prologue(h, nsteps, "pic_step_observe", E_ext && actions ? "E_ext and actions are alternatives" : nullptr);
   if (rc) return rc;
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
   StepControl sc;
   if (actions) {
     rc = actuator_control(h, sc, "pic_step_observe");
@@ -2286,10 +2266,8 @@ int pic_step_observe(pic_handle* h, const double* E_ext, const double* actions, 
 }
 
 int pic_step_actions_traj(pic_handle* h, const double* actions, int mem_kind, int nsteps, double* hist) {
-  if (!h || !actions) return fail(h, PIC_EINVAL, "pic_step_actions_traj: null argument");
-  int rc = check_steppable(h, nsteps, "pic_step_actions_traj");
+  int rc = step_prologue(h, nsteps, "pic_step_actions_traj", actions ? nullptr : "null argument");
   if (rc) return rc;
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
   StepControl sc;
   rc = actuator_control(h, sc, "pic_step_actions_traj");
   if (rc) return rc;
@@ -2300,21 +2278,13 @@ int pic_step_actions_traj(pic_handle* h, const double* actions, int mem_kind, in
 }
 
 int pic_step_feedback(pic_handle* h, int max_mode, int nsteps, double* actions_out, double* hist) {
-  if (!h) return PIC_EINVAL;
-  if (h->tape.on)
+  if (h && h->tape.on)
     return fail(h, PIC_ESTATE, "pic_step_feedback: refused while a tape is open (its actions depend on the state: the gradient through the law would be missing)");
-  int rc = check_steppable(h, nsteps, "pic_step_feedback");
+  int rc = step_prologue(h, nsteps, "pic_step_feedback");
   if (rc) return rc;
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
   StepControl sc;
-  rc = actuator_control(h, sc, "pic_step_feedback");
+  rc = feedback_control(h, max_mode, nsteps, sc, "pic_step_feedback");
   if (rc) return rc;
-  if (max_mode != h->act_modes || max_mode > kMaxFeedbackModes)
-    return fail(h, PIC_EINVAL, "pic_step_feedback: max_mode must equal the actuator's (pic_set_actuator) and be at most 16");
-  rc = ensure_twiddle(h, max_mode);
-  if (rc) return rc;
-  sc.fb.tw = h->tw; sc.fb.rows = h->tw_rows; sc.fb.M = max_mode;
-  sc.fb.act_out = h->act;
   return step_recording(h, sc, nsteps, hist, nullptr, actions_out, "pic_step_feedback");
 }
 
@@ -2350,21 +2320,12 @@ static int tape_law_reserve(pic_handle* h, size_t gbytes) {
 
 int pic_step_feedback_gain(pic_handle* h, int max_mode, const double* gain, int mem_kind, int nsteps, double* actions_out,
                            double* modes_out, double* hist) {
-  if (!h) return PIC_EINVAL;
   const char* who = "pic_step_feedback_gain";
-  if (!gain) return fail(h, PIC_EINVAL, "pic_step_feedback_gain: null gain");
-  if (mem_kind != PIC_HOST && mem_kind != PIC_DEVICE) return fail(h, PIC_EINVAL, "pic_step_feedback_gain: bad mem_kind");
-  int rc = check_steppable(h, nsteps, who);
+  int rc = step_prologue(h, nsteps, who, !gain ? "null gain" : (mem_kind != PIC_HOST && mem_kind != PIC_DEVICE) ? "bad mem_kind" : nullptr);
   if (rc) return rc;
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
   StepControl sc;
-  rc = actuator_control(h, sc, who);
-  if (rc) return rc;
-  if (max_mode != h->act_modes || max_mode > kMaxFeedbackModes)
-    return fail(h, PIC_EINVAL, "pic_step_feedback_gain: max_mode must equal the actuator's (pic_set_actuator) and be at most 16");
-  if (nsteps == 0) return PIC_OK;
-  rc = ensure_twiddle(h, max_mode);
-  if (rc) return rc;
+  rc = feedback_control(h, max_mode, nsteps, sc, who);
+  if (rc || nsteps == 0) return rc;
   const int E = h->cfg.num_envs, n = 2 * max_mode;
   const size_t gbytes = (size_t)E * n * n * sizeof(double);
   if (!h->fb_modes) HIPCHK(h, hipMalloc((void**)&h->fb_modes, (size_t)E * 2 * kMaxFeedbackModes * sizeof(double)));
@@ -2381,8 +2342,6 @@ int pic_step_feedback_gain(pic_handle* h, int max_mode, const double* gain, int 
     HIPCHK(h, hipMemcpyAsync(h->gain, gain, gbytes, in, h->stream));
     g = h->gain;
   }
-  sc.fb.tw = h->tw; sc.fb.rows = h->tw_rows; sc.fb.M = max_mode;
-  sc.fb.act_out = h->act;
   sc.fb.gain = g;
   sc.fb.modes = h->fb_modes;
   if (!t.on) return step_recording(h, sc, nsteps, hist, nullptr, actions_out, who, modes_out);
@@ -2438,15 +2397,11 @@ int pic_reset_sampled(pic_handle* h, int kind, double a, double v0, double sigma
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   resume_placement(h);
   const dim3 grid = aux_grid(h, h->cfg.num_envs, 2048);
-  if (h->fmt == FMT_F64)
-    hipLaunchKernelGGL(sample_kernel<PosF64>, grid, dim3(BLOCK), 0, h->stream, (double*)h->x, (double*)h->v, h->cfg.N,
+  with_format(h, [&](auto p) {
+    using P = decltype(p);
+    hipLaunchKernelGGL(sample_kernel<P>, grid, dim3(BLOCK), 0, h->stream, (typename P::X*)h->x, (typename P::V*)h->v, h->cfg.N,
                        h->ld, kind, a, v0, sigma, A, n_mode, h->cfg.L, (unsigned long long)seed, h->cfg.env_index_base);
-  else if (h->fmt == FMT_F32)
-    hipLaunchKernelGGL(sample_kernel<PosF32>, grid, dim3(BLOCK), 0, h->stream, (float*)h->x, (float*)h->v, h->cfg.N,
-                       h->ld, kind, a, v0, sigma, A, n_mode, h->cfg.L, (unsigned long long)seed, h->cfg.env_index_base);
-  else
-    hipLaunchKernelGGL(sample_kernel<PosU32>, grid, dim3(BLOCK), 0, h->stream, (unsigned*)h->x, (float*)h->v, h->cfg.N,
-                       h->ld, kind, a, v0, sigma, A, n_mode, h->cfg.L, (unsigned long long)seed, h->cfg.env_index_base);
+  });
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipMemsetAsync(h->bad, 0, sizeof(unsigned long long), h->stream));
   h->has_state = true;
@@ -2462,15 +2417,11 @@ static hipError_t phase_counts(pic_handle* h, int nbins, double vmin, double vma
   e = hipMemsetAsync(d, 0, nb, h->stream);
   const dim3 grid = aux_grid(h, h->cfg.num_envs, 2048);
   if (e == hipSuccess) {
-    if (h->fmt == FMT_F64)
-      hipLaunchKernelGGL(phase_hist_kernel<PosF64>, grid, dim3(BLOCK), 0, h->stream, (const double*)h->x,
-                         (const double*)h->v, d, h->cfg.N, h->ld, nbins, h->cfg.L, vmin, vmax);
-    else if (h->fmt == FMT_F32)
-      hipLaunchKernelGGL(phase_hist_kernel<PosF32>, grid, dim3(BLOCK), 0, h->stream, (const float*)h->x,
-                         (const float*)h->v, d, h->cfg.N, h->ld, nbins, h->cfg.L, vmin, vmax);
-    else
-      hipLaunchKernelGGL(phase_hist_kernel<PosU32>, grid, dim3(BLOCK), 0, h->stream, (const unsigned*)h->x,
-                         (const float*)h->v, d, h->cfg.N, h->ld, nbins, h->cfg.L, vmin, vmax);
+    with_format(h, [&](auto p) {
+      using P = decltype(p);
+      hipLaunchKernelGGL(phase_hist_kernel<P>, grid, dim3(BLOCK), 0, h->stream, (const typename P::X*)h->x,
+                         (const typename P::V*)h->v, d, h->cfg.N, h->ld, nbins, h->cfg.L, vmin, vmax);
+    });
     e = hipGetLastError();
   }
   if (e != hipSuccess) { hipFree(d); return e; }
@@ -2578,7 +2529,7 @@ int pic_record_start(pic_handle* h, const pic_record_config* c) {
     if (rc) { record_free(h); return rc; }
   }
   // particle pass geometry: about 1024 workgroups in all, each over a contiguous range of 16-byte tiles
-  const long long vec = h->fmt == FMT_F64 ? 2 : 4;
+  const long long vec = h->vec;
   const long long cols = ((h->cfg.N + vec - 1) / vec + BLOCK - 1) / BLOCK;     // tiles per lane if one workgroup took it all
   long long gx = std::max(1LL, std::min(cols, (1024LL + E - 1) / E));
   h->rec.tiles_per_wg = (cols + gx - 1) / gx;
@@ -2725,13 +2676,15 @@ int pic_bad_count(pic_handle* h, int64_t* count) {
 // ---------------------------------------------------------------------------------------------
 // Differentiable rollouts (include/picstep.h: pic_tape_*; kernels: pic_adjoint.h; hook: advance)
 // ---------------------------------------------------------------------------------------------
+// the forward sweeps' geometry and fixed point (sweep_args), the adjoint deposits' headroom and the Yoshida-4 coefficients
 static AdjArgs adjoint_args(const pic_handle* h) {
+  const SweepArgs s = sweep_args(h);
   AdjArgs a{};
-  a.N = h->cfg.N; a.ld = h->ld; a.Ng = h->cfg.Ng; a.fg = h->fg; a.magic = h->magic;
+  a.N = s.N; a.ld = s.ld; a.Ng = s.Ng; a.fg = s.fg; a.magic = s.magic;
   int b = 0;
   while (((int64_t)1 << b) < h->cfg.N) ++b;
   a.bitsN = b;
-  a.L = h->cfg.L; a.dx = h->dx; a.dt = h->cfg.dt; a.scale = h->scale; a.N_over_L = (double)h->cfg.N / h->cfg.L;
+  a.L = s.L; a.dx = s.dx; a.dt = s.dt; a.scale = s.scale; a.N_over_L = s.N_over_L;
   for (int i = 0; i < 4; ++i) { a.c[i] = h->cs[i]; a.d[i] = h->ds[i]; }
   return a;
 }
@@ -2853,10 +2806,8 @@ static void tape_solve(pic_handle* h, const double* ext, double* E_out) {
   SolveIO io{};
   io.acc = h->tape.acc; io.acc_clear = h->tape.acc;
   io.out.ext = ext; io.out.E = E_out; io.out.num_envs = h->cfg.num_envs;
-  SolveArgs a{};
-  a.N = h->cfg.N; a.Ng = h->cfg.Ng; a.nblk = h->nblk; a.fg = h->fg; a.L = h->cfg.L; a.dx = h->dx; a.n0 = h->cfg.n0;
-  a.scale = h->scale; a.N_over_L = (double)h->cfg.N / h->cfg.L; a.S = 1; a.sub = (long long)h->cfg.num_envs * h->cfg.Ng;
-  hipLaunchKernelGGL(field_solve_kernel, dim3(h->cfg.num_envs), dim3(SBLOCK), h->solve_lds, h->stream, io, a);
+  // (not launch_solve: the replay's launches stay out of pic_profile's counters)
+  hipLaunchKernelGGL(field_solve_kernel, dim3(h->cfg.num_envs), dim3(SBLOCK), h->solve_lds, h->stream, io, solve_args(h, 1));
   ++h->tape.launches;
 }
 
