@@ -410,7 +410,7 @@ int pic_record_stop(pic_handle* h);                                  /* frees; t
  * allocates the record of the law's steps (3 [max_steps][num_envs][2M] plus one [num_envs][Ng] of float64); both count in
  * `bytes` and against budget_bytes (PIC_ENOMEM beyond it);
  * pic_step_feedback, pic_step_stage, pic_reset, pic_reset_sampled, pic_set_particles, pic_set_actuator and pic_set_integrator
- * are refused with PIC_ESTATE.  DESIGN.md 7c. */
+ * are refused with PIC_ESTATE.  DESIGN.md 7c; the stepwise reverse walk (pic_tape_walk_*): 7e. */
 typedef struct pic_tape_config {
   int64_t max_steps;               /* >= 1: steps the tape can hold */
   int64_t checkpoint_every;        /* (x, v) kept every this many steps; 0 = the library chooses: ceil(sqrt(max_steps)), or
@@ -447,6 +447,25 @@ int pic_tape_backward_feedback(pic_handle* h, const double* cot_hist, const void
                                int mem_kind, double* g_ext, double* g_actions, void* g_x0, void* g_v0, double* modes_out);
 int pic_tape_stats(pic_handle* h, pic_tape_info* out);           /* all zero when no tape is open; synchronises */
 int pic_tape_stop(pic_handle* h);                                /* frees the tape */
+/* The reverse pass one step at a time (a walk), so that a caller can put the vector-Jacobian product of its own
+ * policy between two reverse steps.  pic_tape_walk_begin starts at step T (the tape's length); obs_modes M_o (1 <= M_o < Ng)
+ * fixes the layout of the mode cotangents, [num_envs][2 M_o]: Re E_1..E_Mo then Im E_1..E_Mo (pic_get_modes' map).
+ * pic_tape_walk_step reverses the next step t not yet walked (T-1, T-2, ...; its index in *step).  Its cotangents refer to what
+ * step t produced (each may be NULL = 0): cot_energies [3][num_envs] (its row of pic_step_history's layout), cot_x / cot_v
+ * [num_envs][N] on the state it left, cot_modes [num_envs][2 M_o] on the modes of the field it left (the observation of step
+ * t+1).  Outputs (each may be NULL): g_ext [num_envs][Ng] = e-bar_t, g_actions [num_envs][2M] = B^T e-bar_t (needs an
+ * actuator).  When t is the last step of its checkpoint segment the call first replays and compares the segment, as
+ * pic_tape_backward does.  pic_tape_walk_end, once all T steps are walked, adds cot_x0 / cot_v0 on the tape's starting state and
+ * cot_modes0 on the modes of the field there, and writes g_x0 / g_v0 [num_envs][N].  A tape with steps of pic_step_feedback_gain
+ * is walked with the law's own term G^T a-bar_{t+1} added to cot_modes: zero injections give pic_tape_backward_feedback's bits.
+ * PIC_DEVICE: asynchronous on the handle's stream.  PIC_HOST: a call with outputs waits, and pic_tape_walk_end returns
+ * PIC_ESTATE if a replay differed from the taped forward.  Any step appended to the tape, pic_tape_start / stop / backward* and a
+ * new pic_tape_walk_begin abandon a walk; walk_step and walk_end then return PIC_ESTATE, as they do without one. */
+int pic_tape_walk_begin(pic_handle* h, int obs_modes, int mem_kind);
+int pic_tape_walk_step(pic_handle* h, const double* cot_energies, const void* cot_x, const void* cot_v, const double* cot_modes,
+                       int mem_kind, double* g_ext, double* g_actions, int64_t* step);
+int pic_tape_walk_end(pic_handle* h, const void* cot_x0, const void* cot_v0, const double* cot_modes0, int mem_kind, void* g_x0,
+                      void* g_v0);
 
 int pic_sync(pic_handle* h);
 /* Number of particle positions found non-finite or out of range by the last sweeps (0 = healthy).  Counts the state's

@@ -133,6 +133,9 @@ SIGNATURES = {
     "pic_tape_backward_feedback": [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp],
     "pic_tape_stats": [_vp, C.POINTER(PicTapeInfo)],
     "pic_tape_stop": [_vp],
+    "pic_tape_walk_begin": [_vp, C.c_int, C.c_int],
+    "pic_tape_walk_step": [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _i64p],
+    "pic_tape_walk_end": [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp],
     "pic_set_stream": [_vp, _vp],
     "pic_own_stream": [_vp],
     "pic_schedule": [_vp],
@@ -692,6 +695,21 @@ class Handle:
         """Device pointers (0 = NULL) in and out; asynchronous on the handle's stream."""
         p = [None if not q else _ptr(int(q)) for q in (cot_hist, cot_x, cot_v, cot_modes, g_ext, g_actions, g_x0, g_v0, modes)]
         self._chk(self.lib.pic_tape_backward_feedback(self._h, p[0], p[1], p[2], p[3], PIC_DEVICE, p[4], p[5], p[6], p[7], p[8]))
+
+    def tape_walk_begin(self, obs_modes, mem_kind=PIC_HOST):
+        self._chk(self.lib.pic_tape_walk_begin(self._h, int(obs_modes), int(mem_kind)))
+
+    def tape_walk_step(self, cot_energies, cot_x, cot_v, cot_modes, mem_kind, g_ext, g_actions):
+        """pic_tape_walk_step: addresses (int, 0 = NULL; device or host memory as mem_kind says) in and out; returns the step."""
+        p = [None if not q else _ptr(int(q)) for q in (cot_energies, cot_x, cot_v, cot_modes, g_ext, g_actions)]
+        step = C.c_int64(-1)
+        self._chk(self.lib.pic_tape_walk_step(self._h, p[0], p[1], p[2], p[3], int(mem_kind), p[4], p[5], C.byref(step)))
+        return step.value
+
+    def tape_walk_end(self, cot_x0, cot_v0, cot_modes0, mem_kind, g_x0, g_v0):
+        """pic_tape_walk_end: addresses (int, 0 = NULL) in and out."""
+        p = [None if not q else _ptr(int(q)) for q in (cot_x0, cot_v0, cot_modes0, g_x0, g_v0)]
+        self._chk(self.lib.pic_tape_walk_end(self._h, p[0], p[1], p[2], int(mem_kind), p[3], p[4]))
 
     def stream_probe(self, repeats=10):
         g = C.c_double()

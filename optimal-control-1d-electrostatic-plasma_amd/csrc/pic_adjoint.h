@@ -12,8 +12,10 @@
 //   adjoint_mesh_kernel    mu (or the refresh cotangent) -> nu = K^T m = -K (m - mean m), and e-bar_t += mu
 //   adjoint_actions_kernel the actuator part: a-bar_t = B^T e-bar_t
 //   law_adjoint_kernel     a step of the gain law a = G m(E): E-bar = J^T (G^T a-bar + m-bar), a cotangent on the
-//                          field the step started from, which the refresh of the step before adds to its m
-//   adjoint_start_kernel   lambda_x0 += s W'(x_0) . nu: the field at the start of the tape, read by a first law step
+//                          field the step started from, which the refresh of the step before adds to its m; without a gain
+//                          E-bar = J^T m-bar alone (a walk's cotangent on an observation of M_o modes)
+//   adjoint_start_kernel   lambda_x0 += s W'(x_0) . nu: the field at the start of the tape, read by a first law step; plus
+//                          the caller's cotangents on the starting state (pic_tape_walk_end)
 #pragma once
 #include "pic_device.h"
 #include "pic_solve.h"
@@ -147,15 +149,20 @@ __device__ __forceinline__ void block_max_to(double v, unsigned long long* __res
 //   K = 2, 1: lambda_q(K+1) += s W'(q(K+1)) . nu(K+1) (the deposit of the pass before), drift K+1, kick K as above
 //   K = 0: lambda_q1 += s W'(q1) . nu1; lambda_x = lambda_q1, lambda_v = lambda_p1 + c1 dt lambda_q1
 // nu: [env][Ng] or null (K = 3 without an energy cotangent on PE / PE_reward); cot: [3][env] of step t (K = 3), or null.
+// cx, cv [env][cld] (K = 3, each optional): cotangents on the state step t left (a walk's injection), added to
+// lambda_x', lambda_v' before the refresh terms.
 template <int K>
 __global__ __launch_bounds__(ABLOCK) void adjoint_pass_kernel(AdjStep s, const double* __restrict__ nu, const double* __restrict__ cot,
                                                               double* __restrict__ lx, double* __restrict__ lv,
-                                                              unsigned long long* __restrict__ cmax, AdjArgs a, int num_envs) {
+                                                              unsigned long long* __restrict__ cmax, AdjArgs a, int num_envs,
+                                                              const double* __restrict__ cx = nullptr,
+                                                              const double* __restrict__ cv = nullptr, long long cld = 0) {
   const int env = blockIdx.y, Ng = a.Ng;
   const Consts<PosF64> k(a.L, a.dx, Ng);
   const size_t prow = (size_t)env * a.ld, row = (size_t)env * Ng;
   const double* nue = nu ? nu + row : nullptr;
   const double a_ke = (K == 3 && cot) ? cot[env] : 0.0;
+  const size_t crow = (size_t)env * cld;
   unsigned bad = 0u;
   double cm = 0.0;
   for (long long i = (long long)blockIdx.x * ABLOCK + threadIdx.x; i < a.N; i += (long long)gridDim.x * ABLOCK) {
@@ -165,6 +172,8 @@ __global__ __launch_bounds__(ABLOCK) void adjoint_pass_kernel(AdjStep s, const d
     double w[3], xw;
     int j, jr;
     if (K == 3) {
+      if (cx) lq = lq + cx[crow + i];                              // lambda_x(t+1) += x-bar(t+1)
+      if (cv) lp = lp + cv[crow + i];                              // lambda_v(t+1) += v-bar(t+1)
       adj_locate(q[4], k, xw, j, jr, w, bad);                      // x' = wrap(q4): the refresh deposit's cell
       if (nue) lq = lq + a.scale * slope_dot(nue, j, jr, a.dx);
       lp = lp + a_ke * p[3];                                       // KE = 0.5 sum v'^2
@@ -315,15 +324,21 @@ __global__ __launch_bounds__(ABLOCK) void adjoint_actions_kernel(const double* _
   }
 }
 
-// E-bar [env][Ng] of one gain-law step (a = G m, m = (Re E_1..Re E_M, Im E_1..Im E_M) of the field E the step started from,
-// pic_device.h: feedback_action): a-bar = B^T e-bar (in another order than adjoint_actions_kernel's), m-bar = G^T a-bar + cot_m (ascending i),
-// E-bar_j = 2/Ng sum_m (m-bar_Re,m cos - m-bar_Im,m sin)(2 pi m j / Ng) (mesh_mode's map, spectrum.py:16).  Grid (num_envs).
+// E-bar [env][Ng] of the field E a step started from, read through its modes m = (Re E_1..Re E_R, Im E_1..Im E_R) (mesh_mode's
+// map, spectrum.py:16).  A gain-law step (gain non-null, pic_device.h: feedback_action) reads M of them: a-bar = B^T e-bar (in
+// another order than adjoint_actions_kernel's), m-bar_k = G^T a-bar + cot_m (ascending i).  cot_m [env][2 Mc] (or null): a
+// cotangent on Mc modes (the law's own, or a walk's observation); without a gain m-bar = cot_m alone.  With
+// R = max(M of the gain, Mc): E-bar_j = 2/Ng sum_m (m-bar_Re,m cos - m-bar_Im,m sin)(2 pi m j / Ng).  Grid (num_envs); dynamic
+// LDS of 2 (Mg + R) doubles.
 __global__ __launch_bounds__(ABLOCK) void law_adjoint_kernel(const double* __restrict__ gext, const double* __restrict__ basis,
                                                              const double* __restrict__ gain, const double* __restrict__ cot_m,
                                                              const double* __restrict__ tw, int rows, double* __restrict__ Ebar,
-                                                             int Ng, int M) {
-  __shared__ double sa[2 * kMaxFeedbackModes], sm[2 * kMaxFeedbackModes];
-  const int env = blockIdx.x, n = 2 * M, tid = threadIdx.x, lane = tid & 63;
+                                                             int Ng, int M, int Mc) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  const int Mg = gain ? M : 0, R = Mg > Mc ? Mg : Mc;
+  double* sa = reinterpret_cast<double*>(smem_raw);
+  double* sm = sa + 2 * Mg;
+  const int env = blockIdx.x, n = 2 * Mg, tid = threadIdx.x, lane = tid & 63;
   const double* g = gext + (size_t)env * Ng;
   for (int m = tid >> 6; m < n; m += AWAVES) {                    // one wave per coefficient, a fixed-order wave sum
     const double* b = basis + (m < M ? 0 : (size_t)Ng * M);
@@ -334,36 +349,53 @@ __global__ __launch_bounds__(ABLOCK) void law_adjoint_kernel(const double* __res
     if (lane == 0) sa[m] = s;
   }
   __syncthreads();
-  const double* G = gain + (size_t)env * n * n;
-  for (int k = tid; k < n; k += ABLOCK) {
-    double s = 0.0;
-    for (int i = 0; i < n; ++i) s += G[(size_t)i * n + k] * sa[i];
-    sm[k] = s + cot_m[(size_t)env * n + k];
+  const double* G = gain ? gain + (size_t)env * n * n : nullptr;
+  const double* cm = cot_m ? cot_m + (size_t)env * 2 * Mc : nullptr;
+  for (int r = tid; r < 2 * R; r += ABLOCK) {
+    const int m = r < R ? r : r - R, im = r < R ? 0 : 1;
+    const double c = cm && m < Mc ? cm[im * Mc + m] : 0.0;
+    double s;
+    if (m < Mg) {
+      const int k = im * Mg + m;
+      s = 0.0;
+      for (int i = 0; i < n; ++i) s += G[(size_t)i * n + k] * sa[i];
+      s = s + c;
+    } else {
+      s = c;
+    }
+    sm[r] = s;
   }
   __syncthreads();
   const double c = 2.0 / Ng;
   for (int j = tid; j < Ng; j += ABLOCK) {
     double s = 0.0;
-    for (int m = 0; m < M; ++m) {
+    for (int m = 0; m < R; ++m) {
       s += sm[m] * tw[(size_t)m * Ng + j];
-      s -= sm[M + m] * tw[((size_t)rows + m) * Ng + j];
+      s -= sm[R + m] * tw[((size_t)rows + m) * Ng + j];
     }
     Ebar[(size_t)env * Ng + j] = c * s;
   }
 }
 
 // lambda_x += s W'(x) . nu at positions x [env][ld] (the tape's first checkpoint): the deposit of the field the tape started from
+// (nu null: none); then lambda_x += cx, lambda_v += cv [env][cld] (each optional: a walk's cotangents on the starting state)
 __global__ __launch_bounds__(ABLOCK) void adjoint_start_kernel(const double* __restrict__ x, const double* __restrict__ nu,
-                                                               double* __restrict__ lx, AdjArgs a) {
+                                                               double* __restrict__ lx, AdjArgs a, double* __restrict__ lv = nullptr,
+                                                               const double* __restrict__ cx = nullptr,
+                                                               const double* __restrict__ cv = nullptr, long long cld = 0) {
   const int env = blockIdx.y, Ng = a.Ng;
   const Consts<PosF64> k(a.L, a.dx, Ng);
   const size_t prow = (size_t)env * a.ld, row = (size_t)env * Ng;
   unsigned bad = 0u;
   for (long long i = (long long)blockIdx.x * ABLOCK + threadIdx.x; i < a.N; i += (long long)gridDim.x * ABLOCK) {
-    double w[3], xw;
-    int j, jr;
-    adj_locate(x[prow + i], k, xw, j, jr, w, bad);
-    lx[prow + i] = lx[prow + i] + a.scale * slope_dot(nu + row, j, jr, a.dx);
+    if (nu) {
+      double w[3], xw;
+      int j, jr;
+      adj_locate(x[prow + i], k, xw, j, jr, w, bad);
+      lx[prow + i] = lx[prow + i] + a.scale * slope_dot(nu + row, j, jr, a.dx);
+    }
+    if (cx) lx[prow + i] = lx[prow + i] + cx[(size_t)env * cld + i];
+    if (cv) lv[prow + i] = lv[prow + i] + cv[(size_t)env * cld + i];
   }
   (void)bad;
 }

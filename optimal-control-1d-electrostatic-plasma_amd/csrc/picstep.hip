@@ -134,6 +134,14 @@ struct Tape {
   double* lE = nullptr;               // [env][Ng] E-bar_t = J^T (G^T a-bar_t + m-bar_t) of a law step
   std::vector<int> law;               // [max_steps] per step: the index of its gain in `gains`, or -1 (empty: no law step yet)
   std::vector<double*> gains;         // per call: [env][2M][2M]
+  // the reverse walk (pic_tape_walk_*); pic_tape_backward[_feedback] is a walk of its own.  Any append, start,
+  // stop, backward or new walk abandons it.
+  bool walk = false;                  // a walk is in progress
+  int64_t wnext = -1;                 // the next step it reverses (-1: all walked)
+  int wmo = 0;                        // M_o: modes of the walk's mode cotangents
+  double* wstage = nullptr;           // [2][env][N] + [env][2 M_o] host cotangents of a step on the device (allocated on demand)
+  size_t wstage_bytes = 0;
+  double* wE = nullptr;               // [env][Ng] E-bar of a walk's mode cotangents on a tape without a law block (else lE)
 };
 
 struct pic_handle {
@@ -1626,6 +1634,7 @@ static int advance(pic_handle* h, const StepControl& sc, int nsteps, double* his
   Recorder& r = h->rec;
   Tape& t = h->tape;
   const int E = h->cfg.num_envs;
+  t.walk = false;                     // appending abandons a walk
   for (int done = 0; done < nsteps;) {
     int64_t n = nsteps - done;
     if (r.on) n = std::min<int64_t>(n, r.stride - r.k % r.stride);
@@ -2707,6 +2716,8 @@ static size_t tape_layout(const pic_handle* h, int64_t max_steps, int64_t every,
 
 static void tape_free(pic_handle* h) {
   if (h->tape.block) hipFree(h->tape.block);
+  if (h->tape.wstage) hipFree(h->tape.wstage);
+  if (h->tape.wE) hipFree(h->tape.wE);
   if (h->tape.law_block) hipFree(h->tape.law_block);
   for (double* g : h->tape.gains) hipFree(g);
   h->tape = Tape{};
@@ -2811,16 +2822,174 @@ static void tape_solve(pic_handle* h, const double* ext, double* E_out) {
   ++h->tape.launches;
 }
 
-// E-bar of the gain-law step s into t.lE (pic_adjoint.h: law_adjoint_kernel); e-bar_s must be complete
-static void tape_law_cot(pic_handle* h, int64_t s) {
+// E-bar of the field step s started from (pic_adjoint.h: law_adjoint_kernel): the gain law's term if step s is a law step
+// (e-bar_s must be complete), plus cot_m [env][2 mc] on its modes (either may be absent).  Returns where it went (t.lE, or t.wE
+// without a law block), or null: nothing to add.
+static const double* tape_mode_cot(pic_handle* h, int64_t s, const double* cot_m, int mc) {
   Tape& t = h->tape;
+  const bool lawstep = s >= 0 && s < t.steps && !t.law.empty() && t.law[(size_t)s] >= 0;
+  if (!lawstep && !cot_m) return nullptr;
+  double* Ebar = t.lE ? t.lE : t.wE;
   const int E = h->cfg.num_envs, Ng = h->cfg.Ng, M = h->act_modes;
-  const size_t mesh = (size_t)E * Ng, row = (size_t)E * 2 * M;
-  hipLaunchKernelGGL(law_adjoint_kernel, dim3(E), dim3(ABLOCK), 0, h->stream, t.gext + (size_t)s * mesh, h->basis,
-                     t.gains[(size_t)t.law[(size_t)s]], t.lcot + (size_t)s * row, h->tw, h->tw_rows, t.lE, Ng, M);
+  const int mg = lawstep ? M : 0, R = std::max(mg, cot_m ? mc : 0);
+  hipLaunchKernelGGL(law_adjoint_kernel, dim3(E), dim3(ABLOCK), (size_t)2 * (mg + R) * sizeof(double), h->stream,
+                     lawstep ? (const double*)(t.gext + (size_t)s * E * Ng) : nullptr, (const double*)h->basis,
+                     lawstep ? (const double*)t.gains[(size_t)t.law[(size_t)s]] : nullptr, cot_m, (const double*)h->tw, h->tw_rows,
+                     Ebar, Ng, M, cot_m ? mc : 0);
   ++t.launches;
+  return Ebar;
 }
 
+// the launch geometry of the reverse pass
+struct WalkGeom {
+  dim3 pgrid, mgrid;
+  size_t acc_lds, mesh_lds;
+};
+
+static WalkGeom walk_geom(const pic_handle* h) {
+  const int E = h->cfg.num_envs, Ng = h->cfg.Ng;
+  long long gx = (h->cfg.N + (long long)ABLOCK * 8 - 1) / ((long long)ABLOCK * 8);       // ~8 particles per lane
+  gx = std::max<long long>(1, std::min<long long>(gx, std::max(1, 2048 / E)));
+  return {dim3((unsigned)gx, E), dim3(E), (size_t)(Ng + 1) * sizeof(unsigned long long), (size_t)Ng * sizeof(double)};
+}
+
+// a walk from step T: lambda, e-bar, the counters and the launch count at zero; twiddles for M_o modes
+static int walk_open(pic_handle* h, int mo) {
+  Tape& t = h->tape;
+  const size_t part = (size_t)h->cfg.num_envs * h->ld, mesh = (size_t)h->cfg.num_envs * h->cfg.Ng;
+  t.walk = false;
+  if (mo > 0) {
+    const int rc = ensure_twiddle(h, mo);
+    if (rc) return rc;
+    if (!t.lE && !t.wE && hipMalloc((void**)&t.wE, mesh * sizeof(double)) != hipSuccess) {
+      (void)hipGetLastError();
+      t.wE = nullptr;
+      return fail(h, PIC_ENOMEM, "pic_tape_walk_begin: the walk's mode cotangent does not fit on the device");
+    }
+  }
+  t.launches = 0;
+  HIPCHK(h, hipMemsetAsync(t.counters, 0, 2 * sizeof(unsigned long long), h->stream));
+  if (t.steps > 0) HIPCHK(h, hipMemsetAsync(t.gext, 0, (size_t)t.steps * mesh * sizeof(double), h->stream));
+  HIPCHK(h, hipMemsetAsync(t.lam, 0, 2 * part * sizeof(double), h->stream));
+  t.walk = true;
+  t.wnext = t.steps - 1;
+  t.wmo = mo;
+  return PIC_OK;
+}
+
+// restore the checkpoint of segment sgi into the replay states (never into the handle's x, v), replay it step by step and
+// compare its end with the state the forward left there
+static int walk_replay(pic_handle* h, int64_t sgi, const AdjArgs& a, const WalkGeom& g) {
+  Tape& t = h->tape;
+  const size_t part = (size_t)h->cfg.num_envs * h->ld, mesh = (size_t)h->cfg.num_envs * h->cfg.Ng;
+  const int64_t nseg = (t.steps + t.every - 1) / t.every;
+  const int64_t t0 = sgi * t.every, len = std::min<int64_t>(t.every, t.steps - t0);
+  HIPCHK(h, hipMemcpyAsync(t.seg, t.ck + (size_t)sgi * 2 * part, 2 * part * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  for (int64_t i = 0; i < len; ++i) {
+    const double* x = t.seg + (size_t)i * 2 * part;
+    AdjStep st{x, x + part, t.F + (size_t)i * 3 * mesh, (long long)mesh};
+    const double* e_t = t.ext + (size_t)(t0 + i) * mesh;
+    double* xo = t.seg + (size_t)(i + 1) * 2 * part;
+    hipLaunchKernelGGL(adjoint_replay_kernel<1>, g.pgrid, dim3(ABLOCK), g.acc_lds, h->stream, st, t.acc, nullptr, nullptr, a, t.counters + 1);
+    tape_solve(h, e_t, t.F + (size_t)(i * 3 + 0) * mesh);
+    hipLaunchKernelGGL(adjoint_replay_kernel<2>, g.pgrid, dim3(ABLOCK), g.acc_lds, h->stream, st, t.acc, nullptr, nullptr, a, t.counters + 1);
+    tape_solve(h, e_t, t.F + (size_t)(i * 3 + 1) * mesh);
+    hipLaunchKernelGGL(adjoint_replay_kernel<3>, g.pgrid, dim3(ABLOCK), g.acc_lds, h->stream, st, t.acc, nullptr, nullptr, a, t.counters + 1);
+    tape_solve(h, e_t, t.F + (size_t)(i * 3 + 2) * mesh);
+    hipLaunchKernelGGL(adjoint_replay_kernel<4>, g.pgrid, dim3(ABLOCK), g.acc_lds, h->stream, st, t.acc, xo, xo + part, a, t.counters + 1);
+    tape_solve(h, nullptr, t.M + (size_t)i * mesh);
+    t.launches += 4;
+  }
+  const double* end = t.seg + (size_t)len * 2 * part;
+  const double* want_x = sgi + 1 < nseg ? t.ck + (size_t)(sgi + 1) * 2 * part : (const double*)h->x;
+  const double* want_v = sgi + 1 < nseg ? want_x + part : (const double*)h->v;
+  hipLaunchKernelGGL(tape_compare_kernel, g.pgrid, dim3(ABLOCK), 0, h->stream, end, end + part, want_x, want_v, h->cfg.N, h->ld, t.counters);
+  ++t.launches;
+  return PIC_OK;
+}
+
+// cotangents a reverse step injects, all on the device: on the modes of the field the step left (mc modes) and on the state it
+// left (rows of cld elements); each may be null
+struct WalkCot {
+  const double* modes = nullptr;
+  int mc = 0;
+  const double* x = nullptr;
+  const double* v = nullptr;
+  long long cld = 0;
+};
+
+// reverse step t.wnext (its energy cotangents in t.cot's row): first the replay of its segment if it is the segment's last step
+static int walk_reverse(pic_handle* h, const WalkCot& c, const AdjArgs& a, const WalkGeom& g) {
+  Tape& t = h->tape;
+  const int E = h->cfg.num_envs;
+  const size_t part = (size_t)E * h->ld, mesh = (size_t)E * h->cfg.Ng;
+  const int64_t s = t.wnext, sgi = s / t.every, t0 = sgi * t.every, i = s - t0;
+  if (s + 1 == std::min<int64_t>(t0 + t.every, t.steps)) {
+    const int rc = walk_replay(h, sgi, a, g);
+    if (rc) return rc;
+  }
+  double* lx = t.lam;
+  double* lv = t.lam + part;
+  const double* x = t.seg + (size_t)i * 2 * part;
+  const AdjStep st{x, x + part, t.F + (size_t)i * 3 * mesh, (long long)mesh};
+  const double* cot = t.cot + (size_t)s * 3 * E;
+  double* ge = t.gext + (size_t)s * mesh;
+  // the field step s left is read by the law of step s + 1 and by the caller's observation: E-bar joins its refresh adjoint
+  const double* Ebar = tape_mode_cot(h, s + 1, c.modes, c.mc);
+  hipLaunchKernelGGL(adjoint_mesh_kernel, g.mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, nullptr, t.cmax, t.M + (size_t)i * mesh, cot, ge, t.nu, a, E,
+                     Ebar);
+  hipLaunchKernelGGL(adjoint_pass_kernel<3>, g.pgrid, dim3(ABLOCK), 0, h->stream, st, t.nu, cot, lx, lv, t.cmax, a, E, c.x, c.v, c.cld);
+  hipLaunchKernelGGL(adjoint_deposit_kernel<3>, g.pgrid, dim3(ABLOCK), g.acc_lds, h->stream, st, lv, t.cmax, t.acc, a);
+  hipLaunchKernelGGL(adjoint_mesh_kernel, g.mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, t.acc, t.cmax, nullptr, nullptr, ge, t.nu, a, E, nullptr);
+  hipLaunchKernelGGL(adjoint_pass_kernel<2>, g.pgrid, dim3(ABLOCK), 0, h->stream, st, t.nu, nullptr, lx, lv, t.cmax, a, E, nullptr, nullptr, 0ll);
+  hipLaunchKernelGGL(adjoint_deposit_kernel<2>, g.pgrid, dim3(ABLOCK), g.acc_lds, h->stream, st, lv, t.cmax, t.acc, a);
+  hipLaunchKernelGGL(adjoint_mesh_kernel, g.mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, t.acc, t.cmax, nullptr, nullptr, ge, t.nu, a, E, nullptr);
+  hipLaunchKernelGGL(adjoint_pass_kernel<1>, g.pgrid, dim3(ABLOCK), 0, h->stream, st, t.nu, nullptr, lx, lv, t.cmax, a, E, nullptr, nullptr, 0ll);
+  hipLaunchKernelGGL(adjoint_deposit_kernel<1>, g.pgrid, dim3(ABLOCK), g.acc_lds, h->stream, st, lv, t.cmax, t.acc, a);
+  hipLaunchKernelGGL(adjoint_mesh_kernel, g.mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, t.acc, t.cmax, nullptr, nullptr, ge, t.nu, a, E, nullptr);
+  hipLaunchKernelGGL(adjoint_pass_kernel<0>, g.pgrid, dim3(ABLOCK), 0, h->stream, st, t.nu, nullptr, lx, lv, t.cmax, a, E, nullptr, nullptr, 0ll);
+  t.launches += 11;
+  --t.wnext;
+  HIPCHK(h, hipGetLastError());
+  return PIC_OK;
+}
+
+// after the last reverse step: the field at the tape start (read by a first law step and by the caller's observation c.modes)
+// and the caller's cotangents on the starting state reach lambda_0 = (g_x0, g_v0)
+static int walk_close(pic_handle* h, const WalkCot& c, const AdjArgs& a, const WalkGeom& g) {
+  Tape& t = h->tape;
+  const int E = h->cfg.num_envs;
+  const size_t part = (size_t)E * h->ld;
+  const double* Ebar = t.steps > 0 ? tape_mode_cot(h, 0, c.modes, c.mc) : nullptr;
+  const bool field = Ebar != nullptr;
+  if (field) {      // lambda_x0 += s W'(x_0) . K^T E-bar_0 at the tape-start positions
+    hipLaunchKernelGGL(adjoint_mesh_kernel, g.mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, nullptr, t.cmax, nullptr, nullptr, nullptr, t.nu, a, E,
+                       Ebar);
+    ++t.launches;
+  }
+  if (field || c.x || c.v) {
+    hipLaunchKernelGGL(adjoint_start_kernel, g.pgrid, dim3(ABLOCK), 0, h->stream, (const double*)t.ck, field ? (const double*)t.nu : nullptr,
+                       t.lam, a, t.lam + part, c.x, c.v, c.cld);
+    ++t.launches;
+  }
+  t.walk = false;
+  HIPCHK(h, hipGetLastError());
+  return PIC_OK;
+}
+
+// waits for the stream; PIC_ESTATE if a replay of the walk left the forward's trajectory (particles written through
+// pic_device_ptrs while taping): the gradient would be wrong
+static int walk_check(pic_handle* h, const std::string& w) {
+  unsigned long long cnt = 0;
+  HIPCHK(h, hipMemcpyAsync(&cnt, h->tape.counters, sizeof(cnt), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (cnt)
+    return fail(h, PIC_ESTATE, w + ": the replay differs from the taped forward in " + std::to_string(cnt) +
+                                   " particle values (were the particles written while the tape was open?): the gradient is not valid");
+  return PIC_OK;
+}
+
+// the whole reverse pass in one call: a walk over every step with the whole trajectory's cotangents
 static int tape_backward(pic_handle* h, const char* who, const double* cot_hist, const void* cot_x, const void* cot_v,
                          const double* cot_modes, int mem_kind, double* g_ext, double* g_actions, void* g_x0, void* g_v0,
                          double* modes_out) {
@@ -2833,92 +3002,41 @@ static int tape_backward(pic_handle* h, const char* who, const double* cot_hist,
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   const int E = h->cfg.num_envs, Ng = h->cfg.Ng;
   const int64_t T = t.steps;
-  const size_t part = (size_t)E * h->ld, mesh = (size_t)E * Ng;
+  const size_t mesh = (size_t)E * Ng;
   const hipMemcpyKind in = mem_kind == PIC_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
   const hipMemcpyKind outk = mem_kind == PIC_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
   const AdjArgs a = adjoint_args(h);
-  t.launches = 0;
+  const WalkGeom g = walk_geom(h);
+  int rc = walk_open(h, 0);
+  if (rc) return rc;
   double* lx = t.lam;
-  double* lv = t.lam + part;
-  HIPCHK(h, hipMemsetAsync(t.counters, 0, 2 * sizeof(unsigned long long), h->stream));
-  HIPCHK(h, hipMemsetAsync(t.gext, 0, (size_t)T * mesh * sizeof(double), h->stream));
-  HIPCHK(h, hipMemsetAsync(t.lam, 0, 2 * part * sizeof(double), h->stream));
+  double* lv = t.lam + (size_t)E * h->ld;
   if (cot_hist && T > 0) HIPCHK(h, hipMemcpyAsync(t.cot, cot_hist, (size_t)T * 3 * E * sizeof(double), in, h->stream));
   else if (T > 0) HIPCHK(h, hipMemsetAsync(t.cot, 0, (size_t)T * 3 * E * sizeof(double), h->stream));
-  int rc = PIC_OK;
   if (cot_x) rc = upload(h, lx, cot_x, mem_kind);
   if (!rc && cot_v) rc = upload(h, lv, cot_v, mem_kind);
-  if (rc) return rc;
+  if (rc) { t.walk = false; return rc; }
   // steps of the gain law: the action of step s + 1 depends on the field step s left, so the refresh adjoint of
   // step s also carries E-bar_{s+1} = J^T (G^T a-bar_{s+1} + m-bar_{s+1}); E-bar_0 reaches x_0 through the field at the start
   const bool law = !t.law.empty();
-  const size_t lrow = (size_t)E * 2 * h->act_modes;
+  const int M = h->act_modes;
+  const size_t lrow = (size_t)E * 2 * M;
   if (law && T > 0) {
     if (cot_modes) HIPCHK(h, hipMemcpyAsync(t.lcot, cot_modes, (size_t)T * lrow * sizeof(double), in, h->stream));
     else HIPCHK(h, hipMemsetAsync(t.lcot, 0, (size_t)T * lrow * sizeof(double), h->stream));
   }
-
-  long long gx = (h->cfg.N + (long long)ABLOCK * 8 - 1) / ((long long)ABLOCK * 8);       // ~8 particles per lane
-  gx = std::max<long long>(1, std::min<long long>(gx, std::max(1, 2048 / E)));
-  const dim3 pgrid((unsigned)gx, E), mgrid(E);
-  const size_t acc_lds = (size_t)(Ng + 1) * sizeof(unsigned long long), mesh_lds = (size_t)Ng * sizeof(double);
-  const int64_t nseg = (T + t.every - 1) / t.every;
-  for (int64_t sgi = nseg - 1; sgi >= 0; --sgi) {
-    const int64_t t0 = sgi * t.every, len = std::min<int64_t>(t.every, T - t0);
-    // restore the segment's checkpoint into the replay states (never into the handle's x, v) and replay it step by step
-    HIPCHK(h, hipMemcpyAsync(t.seg, t.ck + (size_t)sgi * 2 * part, 2 * part * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    for (int64_t i = 0; i < len; ++i) {
-      const double* x = t.seg + (size_t)i * 2 * part;
-      AdjStep st{x, x + part, t.F + (size_t)i * 3 * mesh, (long long)mesh};
-      const double* e_t = t.ext + (size_t)(t0 + i) * mesh;
-      double* xo = t.seg + (size_t)(i + 1) * 2 * part;
-      hipLaunchKernelGGL(adjoint_replay_kernel<1>, pgrid, dim3(ABLOCK), acc_lds, h->stream, st, t.acc, nullptr, nullptr, a, t.counters + 1);
-      tape_solve(h, e_t, t.F + (size_t)(i * 3 + 0) * mesh);
-      hipLaunchKernelGGL(adjoint_replay_kernel<2>, pgrid, dim3(ABLOCK), acc_lds, h->stream, st, t.acc, nullptr, nullptr, a, t.counters + 1);
-      tape_solve(h, e_t, t.F + (size_t)(i * 3 + 1) * mesh);
-      hipLaunchKernelGGL(adjoint_replay_kernel<3>, pgrid, dim3(ABLOCK), acc_lds, h->stream, st, t.acc, nullptr, nullptr, a, t.counters + 1);
-      tape_solve(h, e_t, t.F + (size_t)(i * 3 + 2) * mesh);
-      hipLaunchKernelGGL(adjoint_replay_kernel<4>, pgrid, dim3(ABLOCK), acc_lds, h->stream, st, t.acc, xo, xo + part, a, t.counters + 1);
-      tape_solve(h, nullptr, t.M + (size_t)i * mesh);
-      t.launches += 4;
-    }
-    // the replayed end of the segment against the state the forward left there
-    const double* end = t.seg + (size_t)len * 2 * part;
-    const double* want_x = sgi + 1 < nseg ? t.ck + (size_t)(sgi + 1) * 2 * part : (const double*)h->x;
-    const double* want_v = sgi + 1 < nseg ? want_x + part : (const double*)h->v;
-    hipLaunchKernelGGL(tape_compare_kernel, pgrid, dim3(ABLOCK), 0, h->stream, end, end + part, want_x, want_v, h->cfg.N, h->ld, t.counters);
-    ++t.launches;
-    // reverse through the segment
-    for (int64_t i = len - 1; i >= 0; --i) {
-      const double* x = t.seg + (size_t)i * 2 * part;
-      const AdjStep st{x, x + part, t.F + (size_t)i * 3 * mesh, (long long)mesh};
-      const double* cot = t.cot + (size_t)(t0 + i) * 3 * E;
-      double* ge = t.gext + (size_t)(t0 + i) * mesh;
-      const bool feeds = law && t0 + i + 1 < T && t.law[(size_t)(t0 + i + 1)] >= 0;
-      if (feeds) tape_law_cot(h, t0 + i + 1);
-      hipLaunchKernelGGL(adjoint_mesh_kernel, mgrid, dim3(SBLOCK), mesh_lds, h->stream, nullptr, t.cmax, t.M + (size_t)i * mesh, cot, ge, t.nu, a, E,
-                         feeds ? (const double*)t.lE : nullptr);
-      hipLaunchKernelGGL(adjoint_pass_kernel<3>, pgrid, dim3(ABLOCK), 0, h->stream, st, t.nu, cot, lx, lv, t.cmax, a, E);
-      hipLaunchKernelGGL(adjoint_deposit_kernel<3>, pgrid, dim3(ABLOCK), acc_lds, h->stream, st, lv, t.cmax, t.acc, a);
-      hipLaunchKernelGGL(adjoint_mesh_kernel, mgrid, dim3(SBLOCK), mesh_lds, h->stream, t.acc, t.cmax, nullptr, nullptr, ge, t.nu, a, E, nullptr);
-      hipLaunchKernelGGL(adjoint_pass_kernel<2>, pgrid, dim3(ABLOCK), 0, h->stream, st, t.nu, nullptr, lx, lv, t.cmax, a, E);
-      hipLaunchKernelGGL(adjoint_deposit_kernel<2>, pgrid, dim3(ABLOCK), acc_lds, h->stream, st, lv, t.cmax, t.acc, a);
-      hipLaunchKernelGGL(adjoint_mesh_kernel, mgrid, dim3(SBLOCK), mesh_lds, h->stream, t.acc, t.cmax, nullptr, nullptr, ge, t.nu, a, E, nullptr);
-      hipLaunchKernelGGL(adjoint_pass_kernel<1>, pgrid, dim3(ABLOCK), 0, h->stream, st, t.nu, nullptr, lx, lv, t.cmax, a, E);
-      hipLaunchKernelGGL(adjoint_deposit_kernel<1>, pgrid, dim3(ABLOCK), acc_lds, h->stream, st, lv, t.cmax, t.acc, a);
-      hipLaunchKernelGGL(adjoint_mesh_kernel, mgrid, dim3(SBLOCK), mesh_lds, h->stream, t.acc, t.cmax, nullptr, nullptr, ge, t.nu, a, E, nullptr);
-      hipLaunchKernelGGL(adjoint_pass_kernel<0>, pgrid, dim3(ABLOCK), 0, h->stream, st, t.nu, nullptr, lx, lv, t.cmax, a, E);
-      t.launches += 11;
-    }
-    HIPCHK(h, hipGetLastError());
+  // the law's m-bar of step s + 1 is a cotangent on the field step s left: the walk's mode cotangent of step s (law steps only)
+  auto law_cot = [&](int64_t s) {
+    WalkCot c;
+    if (law && s < T && t.law[(size_t)s] >= 0) { c.modes = t.lcot + (size_t)s * lrow; c.mc = M; }
+    return c;
+  };
+  while (t.wnext >= 0) {
+    rc = walk_reverse(h, law_cot(t.wnext + 1), a, g);
+    if (rc) { t.walk = false; return rc; }
   }
-  if (law && T > 0 && t.law[0] >= 0) {      // lambda_x0 += s W'(x_0) . K^T E-bar_0 at the tape-start positions
-    tape_law_cot(h, 0);
-    hipLaunchKernelGGL(adjoint_mesh_kernel, mgrid, dim3(SBLOCK), mesh_lds, h->stream, nullptr, t.cmax, nullptr, nullptr, nullptr, t.nu, a, E,
-                       (const double*)t.lE);
-    hipLaunchKernelGGL(adjoint_start_kernel, pgrid, dim3(ABLOCK), 0, h->stream, (const double*)t.ck, (const double*)t.nu, lx, a);
-    t.launches += 2;
-  }
+  rc = walk_close(h, law_cot(0), a, g);
+  if (rc) return rc;
   if (g_ext && T > 0) HIPCHK(h, hipMemcpyAsync(g_ext, t.gext, (size_t)T * mesh * sizeof(double), outk, h->stream));
   if (modes_out && T > 0) {
     if (law) HIPCHK(h, hipMemcpyAsync(modes_out, t.lmodes, (size_t)T * lrow * sizeof(double), outk, h->stream));
@@ -2927,26 +3045,18 @@ static int tape_backward(pic_handle* h, const char* who, const double* cot_hist,
   }
   if (g_actions && T > 0) {
     hipLaunchKernelGGL(adjoint_actions_kernel, dim3(E, (unsigned)T), dim3(ABLOCK), 0, h->stream, t.gext, h->basis,
-                       mem_kind == PIC_HOST ? t.gact : g_actions, Ng, h->act_modes, E);
+                       mem_kind == PIC_HOST ? t.gact : g_actions, Ng, M, E);
     ++t.launches;
     if (mem_kind == PIC_HOST)
-      HIPCHK(h, hipMemcpyAsync(g_actions, t.gact, (size_t)T * E * 2 * h->act_modes * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipMemcpyAsync(g_actions, t.gact, (size_t)T * lrow * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   }
   if (g_x0) rc = download(h, g_x0, lx, mem_kind);
   if (!rc && g_v0) rc = download(h, g_v0, lv, mem_kind);
   if (rc) return rc;
   HIPCHK(h, hipGetLastError());
-  if (mem_kind == PIC_HOST) {
-    // host outputs: the call waits anyway, so a replay that left the forward's trajectory (particles written through
-    // pic_device_ptrs while taping) is an error here, not only a count in pic_tape_stats
-    unsigned long long cnt = 0;
-    HIPCHK(h, hipMemcpyAsync(&cnt, t.counters, sizeof(cnt), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (cnt)
-      return fail(h, PIC_ESTATE, w + ": the replay differs from the taped forward in " + std::to_string(cnt) +
-                                     " particle values (were the particles written while the tape was open?): the gradient is not valid");
-  }
-  return PIC_OK;
+  // host outputs: the call waits anyway, so a replay that left the forward's trajectory is an error here, not only a count in
+  // pic_tape_stats
+  return mem_kind == PIC_HOST ? walk_check(h, w) : PIC_OK;
 }
 
 int pic_tape_backward(pic_handle* h, const double* cot_hist, const void* cot_x, const void* cot_v, int mem_kind, double* g_ext,
@@ -2962,6 +3072,128 @@ int pic_tape_backward_feedback(pic_handle* h, const double* cot_hist, const void
     return fail(h, PIC_ESTATE, "pic_tape_backward_feedback: modes_out needs an actuator set before pic_tape_start (pic_set_actuator)");
   return tape_backward(h, "pic_tape_backward_feedback", cot_hist, cot_x, cot_v, cot_modes, mem_kind, g_ext, g_actions, g_x0, g_v0,
                        modes_out);
+}
+
+int pic_tape_walk_begin(pic_handle* h, int obs_modes, int mem_kind) {
+  if (!h) return PIC_EINVAL;
+  if (!h->tape.on) return fail(h, PIC_ESTATE, "pic_tape_walk_begin: no tape is open (pic_tape_start)");
+  if (obs_modes < 1 || obs_modes >= h->cfg.Ng) return fail(h, PIC_EINVAL, "pic_tape_walk_begin: need 1 <= obs_modes < N_mesh");
+  if (mem_kind != PIC_HOST && mem_kind != PIC_DEVICE) return fail(h, PIC_EINVAL, "pic_tape_walk_begin: bad mem_kind");
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  return walk_open(h, obs_modes);
+}
+
+// a walk's host cotangents go through wstage: [2][env][N] particles, then [env][2 M_o] modes
+static int walk_stage(pic_handle* h, double** out) {
+  Tape& t = h->tape;
+  const size_t bytes = ((size_t)2 * h->cfg.num_envs * h->cfg.N + (size_t)h->cfg.num_envs * 2 * t.wmo) * sizeof(double);
+  if (bytes > t.wstage_bytes) {
+    if (t.wstage) {
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+      hipFree(t.wstage);
+      t.wstage = nullptr;
+      t.wstage_bytes = 0;
+    }
+    if (hipMalloc((void**)&t.wstage, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      t.wstage = nullptr;
+      return fail(h, PIC_ENOMEM, "pic_tape_walk: the staging of host cotangents does not fit on the device");
+    }
+    t.wstage_bytes = bytes;
+  }
+  *out = t.wstage;
+  return PIC_OK;
+}
+
+int pic_tape_walk_step(pic_handle* h, const double* cot_energies, const void* cot_x, const void* cot_v, const double* cot_modes,
+                       int mem_kind, double* g_ext, double* g_actions, int64_t* step) {
+  if (!h) return PIC_EINVAL;
+  Tape& t = h->tape;
+  if (!t.on || !t.walk) return fail(h, PIC_ESTATE, "pic_tape_walk_step: no walk in progress (pic_tape_walk_begin)");
+  if (t.wnext < 0) return fail(h, PIC_ESTATE, "pic_tape_walk_step: every step has been walked (pic_tape_walk_end)");
+  if (mem_kind != PIC_HOST && mem_kind != PIC_DEVICE) return fail(h, PIC_EINVAL, "pic_tape_walk_step: bad mem_kind");
+  if (g_actions && !t.gact)
+    return fail(h, PIC_ESTATE, "pic_tape_walk_step: g_actions needs an actuator set before pic_tape_start (pic_set_actuator)");
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  const int E = h->cfg.num_envs;
+  const int64_t s = t.wnext;
+  const size_t mesh = (size_t)E * h->cfg.Ng, arow = (size_t)E * 2 * h->act_modes, N = (size_t)h->cfg.N;
+  const bool host = mem_kind == PIC_HOST;
+  double* cot = t.cot + (size_t)s * 3 * E;
+  if (cot_energies)
+    HIPCHK(h, hipMemcpyAsync(cot, cot_energies, 3 * E * sizeof(double), host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->stream));
+  else
+    HIPCHK(h, hipMemsetAsync(cot, 0, 3 * E * sizeof(double), h->stream));
+  WalkCot c;
+  c.x = static_cast<const double*>(cot_x);
+  c.v = static_cast<const double*>(cot_v);
+  c.modes = cot_modes;
+  c.mc = t.wmo;
+  c.cld = (long long)N;
+  if (host && (cot_x || cot_v || cot_modes)) {
+    double* st = nullptr;
+    int rc = walk_stage(h, &st);
+    if (rc) return rc;
+    if (cot_x) { HIPCHK(h, hipMemcpyAsync(st, cot_x, E * N * sizeof(double), hipMemcpyHostToDevice, h->stream)); c.x = st; }
+    if (cot_v) { HIPCHK(h, hipMemcpyAsync(st + E * N, cot_v, E * N * sizeof(double), hipMemcpyHostToDevice, h->stream)); c.v = st + E * N; }
+    if (cot_modes) {
+      double* sm = st + 2 * E * N;
+      HIPCHK(h, hipMemcpyAsync(sm, cot_modes, (size_t)E * 2 * t.wmo * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      c.modes = sm;
+    }
+  }
+  int rc = walk_reverse(h, c, adjoint_args(h), walk_geom(h));
+  if (rc) { t.walk = false; return rc; }
+  if (g_ext) HIPCHK(h, hipMemcpyAsync(g_ext, t.gext + (size_t)s * mesh, mesh * sizeof(double),
+                                      host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
+  if (g_actions) {      // a-bar_s = B^T e-bar_s of this step alone
+    hipLaunchKernelGGL(adjoint_actions_kernel, dim3(E, 1), dim3(ABLOCK), 0, h->stream, (const double*)(t.gext + (size_t)s * mesh), h->basis,
+                       host ? t.gact + (size_t)s * arow : g_actions, h->cfg.Ng, h->act_modes, E);
+    ++t.launches;
+    HIPCHK(h, hipGetLastError());
+    if (host) HIPCHK(h, hipMemcpyAsync(g_actions, t.gact + (size_t)s * arow, arow * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  }
+  if (host && (g_ext || g_actions)) HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (step) *step = s;
+  return PIC_OK;
+}
+
+int pic_tape_walk_end(pic_handle* h, const void* cot_x0, const void* cot_v0, const double* cot_modes0, int mem_kind, void* g_x0,
+                      void* g_v0) {
+  if (!h) return PIC_EINVAL;
+  Tape& t = h->tape;
+  if (!t.on || !t.walk) return fail(h, PIC_ESTATE, "pic_tape_walk_end: no walk in progress (pic_tape_walk_begin)");
+  if (t.wnext >= 0)
+    return fail(h, PIC_ESTATE, "pic_tape_walk_end: " + std::to_string(t.wnext + 1) + " steps are not walked yet (pic_tape_walk_step)");
+  if (mem_kind != PIC_HOST && mem_kind != PIC_DEVICE) return fail(h, PIC_EINVAL, "pic_tape_walk_end: bad mem_kind");
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  const int E = h->cfg.num_envs;
+  const size_t N = (size_t)h->cfg.N, part = (size_t)E * h->ld;
+  const bool host = mem_kind == PIC_HOST;
+  WalkCot c;
+  c.x = static_cast<const double*>(cot_x0);
+  c.v = static_cast<const double*>(cot_v0);
+  c.modes = cot_modes0;
+  c.mc = t.wmo;
+  c.cld = (long long)N;
+  if (host && (cot_x0 || cot_v0 || cot_modes0)) {
+    double* st = nullptr;
+    int rc = walk_stage(h, &st);
+    if (rc) { t.walk = false; return rc; }
+    if (cot_x0) { HIPCHK(h, hipMemcpyAsync(st, cot_x0, E * N * sizeof(double), hipMemcpyHostToDevice, h->stream)); c.x = st; }
+    if (cot_v0) { HIPCHK(h, hipMemcpyAsync(st + E * N, cot_v0, E * N * sizeof(double), hipMemcpyHostToDevice, h->stream)); c.v = st + E * N; }
+    if (cot_modes0) {
+      double* sm = st + 2 * E * N;
+      HIPCHK(h, hipMemcpyAsync(sm, cot_modes0, (size_t)E * 2 * t.wmo * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      c.modes = sm;
+    }
+  }
+  int rc = walk_close(h, c, adjoint_args(h), walk_geom(h));
+  if (rc) return rc;
+  if (g_x0) rc = download(h, g_x0, t.lam, mem_kind);
+  if (!rc && g_v0) rc = download(h, g_v0, t.lam + part, mem_kind);
+  if (rc) return rc;
+  return host ? walk_check(h, "pic_tape_walk_end") : PIC_OK;
 }
 
 }  // extern "C"

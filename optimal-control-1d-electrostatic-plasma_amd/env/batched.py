@@ -243,6 +243,20 @@ class BatchedPIC:
             self._h.sync()
         return torch.cat([-re, im], dim=1)
 
+    def modes_torch(self, max_mode: int):
+        """The modes of the current field as a float64 CUDA tensor [num_envs, 2*max_mode]: Re E_1..E_M, then Im E_1..E_M
+        (`modes`' rows, pic_get_modes on the device)."""
+        import torch
+        re = torch.empty((self.num_envs, max_mode), dtype=torch.float64, device=f"cuda:{self.device}")
+        im = torch.empty_like(re)
+        shared = getattr(self, "_torch_stream", None) is not None
+        if not shared:
+            torch.cuda.current_stream(self.device).synchronize()
+        self._h.modes_device(max_mode, re.data_ptr(), im.data_ptr())
+        if not shared:
+            self._h.sync()
+        return torch.cat([re, im], dim=1)
+
     def _ordered_views(self):
         """The zero-copy views, safe to read on torch's current stream: on a shared stream (use_torch_stream) the stream
         orders the read behind the steps; otherwise the handle's own stream is drained first."""
@@ -464,6 +478,15 @@ class BatchedPIC:
                                 "(were the particles written while the tape was open?): the gradient is not valid")
         return res
 
+    def walk(self, obs_modes: Optional[int] = None, on_device: bool = False):
+        """The reverse pass of the open tape one step at a time (pic_tape_walk_*): returns a TapeWalk whose
+        step(d_energies, d_x, d_v, d_modes) reverses steps T-1, T-2, ... and end(d_x0, d_v0, d_modes0) closes it.  obs_modes
+        M_o (default: the actuator's max_mode, else 1) sets the layout of the mode cotangents [num_envs, 2*M_o] (Re E_1..E_Mo,
+        then Im, the map of `modes`).  Outputs are float64 CUDA tensors if any cotangent of the call is one or on_device is
+        set, NumPy arrays otherwise.  A later step on the environment, another walk or backward abandons this one (PicError)."""
+        mo = int(obs_modes) if obs_modes is not None else max(1, getattr(self, "max_mode", 0))
+        return TapeWalk(self, mo, on_device)
+
     def _backward_law(self, T, calls, on_device, d_KE, d_PE, d_PE_reward, d_x, d_v, d_modes):
         E, n = self.num_envs, 2 * self.max_mode
 
@@ -512,3 +535,89 @@ class BatchedPIC:
 
     def close(self):
         self._h.close()
+
+
+class TapeWalk:
+    """A reverse walk over an open tape (BatchedPIC.walk)."""
+
+    def __init__(self, env, obs_modes, on_device=False):
+        self.env, self.obs_modes, self.on_device = env, int(obs_modes), bool(on_device)
+        env._h.tape_walk_begin(self.obs_modes)
+        env._walk_serial = getattr(env, "_walk_serial", 0) + 1
+        self._serial = env._walk_serial
+
+    def _live(self, who):
+        if getattr(self.env, "_walk_serial", None) != self._serial:
+            raise _abi.PicError(f"walk.{who}: another walk or backward has replaced this one")
+
+    def _args(self, arrays, shapes):
+        """(on_device, keep-alive list, addresses) of the cotangents, each None = 0."""
+        on_device = self.on_device or any(hasattr(a, "is_cuda") and a.is_cuda for a in arrays if a is not None)
+        keep, addr = [], []
+        for a, shape in zip(arrays, shapes):
+            if a is None:
+                addr.append(0)
+                continue
+            if on_device:
+                import torch
+                a = torch.as_tensor(a, dtype=torch.float64, device=f"cuda:{self.env.device}").reshape(shape).contiguous()
+                addr.append(a.data_ptr())
+            else:
+                a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(shape))
+                addr.append(a.__array_interface__["data"][0])
+            keep.append(a)
+        return on_device, keep, addr
+
+    def _empty(self, on_device, shape):
+        if on_device:
+            import torch
+            return torch.empty(shape, dtype=torch.float64, device=f"cuda:{self.env.device}")
+        return np.zeros(shape)
+
+    @staticmethod
+    def _addr(a):
+        return 0 if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else a.__array_interface__["data"][0])
+
+    def _enter(self, on_device):
+        shared = getattr(self.env, "_torch_stream", None) is not None
+        if on_device and not shared:        # different streams: order them through the host
+            import torch
+            torch.cuda.current_stream(self.env.device).synchronize()
+        return on_device and not shared
+
+    def step(self, d_energies=None, d_x=None, d_v=None, d_modes=None):
+        """Reverse the next step t: d_energies [3, num_envs] (its KE, PE, PE_reward), d_x, d_v [num_envs, N] on the state it
+        left, d_modes [num_envs, 2*M_o] on the modes of the field it left.  Returns (t, g_ext [num_envs, N_mesh],
+        g_actions [num_envs, 2*max_mode] or None without an actuator)."""
+        self._live("step")
+        env, E = self.env, self.env.num_envs
+        on_device, keep, addr = self._args((d_energies, d_x, d_v, d_modes),
+                                           ((3, E), (E, env.N), (E, env.N), (E, 2 * self.obs_modes)))
+        M = getattr(env, "max_mode", 0)
+        g_ext = self._empty(on_device, (E, env.N_mesh))
+        g_act = self._empty(on_device, (E, 2 * M)) if M > 0 else None
+        wait = self._enter(on_device)
+        t = env._h.tape_walk_step(addr[0], addr[1], addr[2], addr[3], _abi.PIC_DEVICE if on_device else _abi.PIC_HOST,
+                                  self._addr(g_ext), self._addr(g_act))
+        if wait:
+            env._h.sync()
+        del keep
+        return t, g_ext, g_act
+
+    def end(self, d_x0=None, d_v0=None, d_modes0=None):
+        """After all steps: cotangents on the tape's starting state and on the modes of the field there; returns (g_x0, g_v0)
+        [num_envs, N].  Raises PicError if a replay of the walk differed from the taped forward."""
+        self._live("end")
+        env, E = self.env, self.env.num_envs
+        on_device, keep, addr = self._args((d_x0, d_v0, d_modes0), ((E, env.N), (E, env.N), (E, 2 * self.obs_modes)))
+        g_x0, g_v0 = self._empty(on_device, (E, env.N)), self._empty(on_device, (E, env.N))
+        self._enter(on_device)
+        env._h.tape_walk_end(addr[0], addr[1], addr[2], _abi.PIC_DEVICE if on_device else _abi.PIC_HOST, self._addr(g_x0),
+                             self._addr(g_v0))
+        del keep
+        if on_device:
+            st = env._h.tape_stats()                 # (waits for the walk)
+            if st["replay_mismatches"]:
+                raise _abi.PicError(f"walk.end: the replay differs from the taped forward in {st['replay_mismatches']} particle "
+                                    "values (were the particles written while the tape was open?): the gradient is not valid")
+        return g_x0, g_v0

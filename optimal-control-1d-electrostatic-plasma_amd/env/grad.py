@@ -7,6 +7,9 @@ the gradient from the device's adjoint (pic_tape_backward).
     KE, PE, PE_reward, modes = rollout_feedback(env, gain, T)   # gain: [num_envs, 2M, 2M] or [2M, 2M], requires_grad
     (PE_reward.sum() + (modes[..., 0] ** 2).sum()).backward()  # fills gain.grad through the closed loop
 
+    KE, PE, PE_reward, actions, obs = rollout_policy(env, policy, T)   # policy: any torch callable, modes -> actions
+    (PE_reward.sum() + lam * (actions ** 2).sum() * L / 4).backward()   # fills the policy's .grad through the closed loop (7e)
+
 Each call opens a fresh tape on `env` (an open one is stopped first) and leaves it open for the backward; stop it with
 `env.stop_tape()` before a reset.  A backward after the environment has moved on (a further step, another rollout, a reset)
 raises PicError.
@@ -105,3 +108,121 @@ def rollout_feedback(env, gain, T, checkpoint_every=0):
     if getattr(env, "max_mode", 0) == 0:
         raise PicError("rollout_feedback: the environment has no actuator (set_actuator)")
     return _RolloutFeedback.apply(gain, env, int(T), int(checkpoint_every))
+
+
+class _PolicyWalk:
+    """What the steps of one rollout_policy share: the environment, the tape's identity, and the reverse walk their backwards
+    advance together (step T-1 first, the start last)."""
+
+    def __init__(self, env, T, observe, obs_modes, serial):
+        self.env, self.T, self.observe, self.obs_modes, self.serial = env, T, observe, obs_modes, serial
+        self.walk, self.next = None, -1
+
+    def reverse_to(self, t):
+        """Make step t the next one to reverse: open a walk if none is running, and reverse the steps after t that no
+        cotangent reached (no output of theirs was used) with zero cotangents."""
+        env = self.env
+        if self.walk is None:
+            if getattr(env, "_tape_serial", None) != self.serial or env.tape_stats()["steps"] != self.T:
+                raise PicError("backward: the environment has moved on since this rollout (a further step, rollout or reset)")
+            self.walk, self.next = env.walk(self.obs_modes, on_device=True), self.T - 1
+        if self.next < t:
+            raise PicError(f"backward: step {t} reached after step {self.next + 1} was reversed (out of order)")
+        while self.next > t:
+            self.walk.step()
+            self.next -= 1
+
+    def cot(self, g_obs):
+        """Cotangents of an observation -> walk arguments."""
+        if self.observe == "modes":
+            return {"d_modes": g_obs[0]}
+        return {"d_x": g_obs[0], "d_v": g_obs[1]}
+
+
+def _observe(env, observe, obs_modes):
+    if observe == "modes":
+        return (env.modes_torch(obs_modes),)
+    v = env._ordered_views()
+    return tuple(v[k].clone(memory_format=torch.contiguous_format) for k in ("x", "v"))
+
+
+class _PolicyStart(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, anchor, pw):
+        ctx.set_materialize_grads(False)
+        ctx.pw = pw
+        return (anchor.new_zeros(0),) + _observe(pw.env, pw.observe, pw.obs_modes)
+
+    @staticmethod
+    def backward(ctx, g_token, *g_obs):
+        pw = ctx.pw
+        pw.reverse_to(-1)
+        walk, pw.walk = pw.walk, None
+        walk.end(**{k + "0": v for k, v in pw.cot(g_obs).items()})
+        return None, None
+
+
+class _PolicyStep(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, token, action, pw, t):
+        ctx.set_materialize_grads(False)
+        ctx.pw, ctx.t = pw, t
+        env = pw.env
+        env.step_actions_torch(action.detach().contiguous())
+        en = env.energy_views_torch()
+        energies = tuple(en[k].clone() for k in ("KE", "PE", "PE_reward"))
+        return (token.new_zeros(0),) + energies + _observe(env, pw.observe, pw.obs_modes)
+
+    @staticmethod
+    def backward(ctx, g_token, g_ke, g_pe, g_per, *g_obs):
+        pw, t = ctx.pw, ctx.t
+        pw.reverse_to(t)
+        d_en = None
+        if any(g is not None for g in (g_ke, g_pe, g_per)):
+            ref = next(g for g in (g_ke, g_pe, g_per) if g is not None)
+            d_en = torch.stack([g if g is not None else torch.zeros_like(ref) for g in (g_ke, g_pe, g_per)])
+        _, _, g_act = pw.walk.step(d_energies=d_en, **pw.cot(g_obs))
+        pw.next -= 1
+        return g_token.new_zeros(0) if g_token is not None else None, g_act, None, None
+
+
+def rollout_policy(env, policy, T, observe="modes", obs_modes=None, checkpoint_every=0):
+    """T steps of `env` (a BatchedPIC with an actuator, on the GPU) in closed loop under a torch policy: at every step the
+    observation o_t goes through `policy(o_t)` to the actions a_t [num_envs, 2*max_mode] (any float dtype: cast to float64), which
+    step_actions_torch applies.  observe="modes": o_t = the modes of the field, float64 [num_envs, 2*M_o] (Re E_1..E_Mo then
+    Im, obs_modes M_o defaulting to max_mode); observe="state": o_t = (x, v), a tuple of float64 copies [num_envs, N] of the
+    particles (torch.cat(o_t, 1) is the reference actor's input).
+    Runs on a fresh tape; returns KE, PE, PE_reward [T, num_envs], actions [T, num_envs, 2*max_mode] and the observations
+    o_0..o_T (a list of T + 1), all differentiable with respect to the policy's parameters (and whatever else it closes over):
+    the backward walks the tape step by step (pic_tape_walk_*) and puts the policy's own vector-Jacobian product
+    between two reverse steps.  With env.use_torch_stream() no step synchronises the host."""
+    if getattr(env, "max_mode", 0) == 0:
+        raise PicError("rollout_policy: the environment has no actuator (set_actuator)")
+    if observe not in ("modes", "state"):
+        raise ValueError('observe must be "modes" or "state"')
+    T = int(T)
+    if T < 1:
+        raise ValueError("need T >= 1")
+    mo = int(obs_modes) if obs_modes is not None else env.max_mode
+    if not 1 <= mo < env.N_mesh:
+        raise ValueError("need 1 <= obs_modes < N_mesh")
+    serial = _start(env, T, int(checkpoint_every))
+    pw = _PolicyWalk(env, T, observe, mo, serial)
+    anchor = torch.zeros(0, dtype=torch.float64, device=f"cuda:{env.device}", requires_grad=True)
+    out = _PolicyStart.apply(anchor, pw)
+    token, o = out[0], (out[1] if observe == "modes" else tuple(out[1:]))
+    obs = [o]
+    ke, pe, per, acts = [], [], [], []
+    n = 2 * env.max_mode
+    for t in range(T):
+        a = policy(o).to(torch.float64)
+        if tuple(a.shape) != (env.num_envs, n):
+            raise ValueError(f"the policy must return actions [{env.num_envs}, {n}], not {tuple(a.shape)}")
+        out = _PolicyStep.apply(token, a, pw, t)
+        token, o = out[0], (out[4] if observe == "modes" else tuple(out[4:]))
+        ke.append(out[1])
+        pe.append(out[2])
+        per.append(out[3])
+        acts.append(a)
+        obs.append(o)
+    return torch.stack(ke), torch.stack(pe), torch.stack(per), torch.stack(acts), obs
