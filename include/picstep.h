@@ -189,6 +189,14 @@ int pic_step_stage(pic_handle* h, int stage, const double* E_ext, int mem_kind);
 int pic_set_integrator(pic_handle* h, int scheme);
 int pic_get_integrator(pic_handle* h, int* scheme, int* evals_per_step);
 
+/* Whether the whole Yoshida-4 steps of the streaming schedule store sweep C's output.  With PIC_READONLY_ON sweep C
+ * stores no particles and sweep D re-derives C's output from C's input and C's field tile, the same arithmetic on the same
+ * operands: 80 bytes per float64 particle-step instead of 96, and the same bits.  PIC_READONLY_AUTO (the default) turns it on for
+ * particle states of 256 MB and more, which stream from HBM.  pic_step_stage, the other integrators and the resident schedule
+ * are not affected.  PIC_EINVAL for an unknown mode, or PIC_READONLY_ON where Ng leaves no LDS for the second field tile. */
+enum { PIC_READONLY_AUTO = 0, PIC_READONLY_OFF = 1, PIC_READONLY_ON = 2 };
+int pic_set_readonly_c(pic_handle* h, int mode);
+
 /* nsteps x PIC.update_state with the energies of every step kept, i.e. the E / PE traces PIC.simulate
  * returns (pic.py:175-223) without its particle snapshots: hist, host [nsteps][3][num_envs] float64 =
  * KE, PE, PE_reward after each step (total energy = KE + PE).  E_ext as in pic_step, constant over the steps.

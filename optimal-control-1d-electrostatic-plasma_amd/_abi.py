@@ -39,6 +39,8 @@ ACCUMULATORS = {None: PIC_ACC_AUTO, "auto": PIC_ACC_AUTO, "fix64": PIC_ACC_FIX64
                 "packed": PIC_ACC_PACKED, "float64": PIC_ACC_F64}
 POSITION_FORMATS = {None: PIC_POS_FLOAT, "float": PIC_POS_FLOAT, "fixed32": PIC_POS_FIXED32}
 
+READONLY_MODES = {"auto": 0, "off": 1, "on": 2}        # pic_set_readonly_c (include/picstep.h PIC_READONLY_*)
+
 KIND_NAMES = ("sweep_A", "sweep_B", "sweep_C", "sweep_D", "field_solve", "sweep_aux", "resident", "sweep_integrator")
 
 
@@ -95,6 +97,7 @@ SIGNATURES = {
     "pic_step": [_vp, _vp, C.c_int, C.c_int],
     "pic_step_stage": [_vp, C.c_int, _vp, C.c_int],
     "pic_set_integrator": [_vp, C.c_int],
+    "pic_set_readonly_c": [_vp, C.c_int],
     "pic_get_integrator": [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "pic_step_history": [_vp, _vp, C.c_int, C.c_int, _vp],
     "pic_step_snapshots": [_vp, _vp, C.c_int, C.c_int, _vp, _vp],
@@ -215,8 +218,10 @@ class Handle:
 
     def __init__(self, N, Ng, num_envs=1, L=50.0, n0=1.0, dt=0.1, gamma=5.0, particle_dtype="float64",
                  accum_dtype=None, interpol="CIC", device_id=0, blocks_per_env=0, env_index_base=0,
-                 position_dtype=None, placement="auto", placement_ms=0, integrator="symplectic_4th_order"):
+                 position_dtype=None, placement="auto", placement_ms=0, integrator="symplectic_4th_order", readonly_c="auto"):
         scheme = integrator_id(integrator)
+        if readonly_c not in READONLY_MODES:
+            raise ValueError(f"readonly_c must be one of {sorted(READONLY_MODES)}, not {readonly_c!r}")
         self.lib = load()
         pd = {"float64": PIC_F64, "float32": PIC_F32}[str(np.dtype(particle_dtype))]
         # LDS mesh accumulator (include/picstep.h PIC_ACC_*).  None: the library's choice -- the packed word for
@@ -243,6 +248,8 @@ class Handle:
             raise PicError(f"pic_create failed ({rc}): {msg.decode() if msg else ''}")
         if scheme != PIC_YOSHIDA4:
             self.set_integrator(scheme)
+        if readonly_c != "auto":
+            self.set_readonly_c(readonly_c)
 
     def _chk(self, rc):
         if rc != 0:
@@ -287,6 +294,10 @@ class Handle:
     def invalidate(self):
         """Call after writing x / v through the device views (or call refresh())."""
         self._chk(self.lib.pic_invalidate(self._h))
+
+    def set_readonly_c(self, mode):
+        """pic_set_readonly_c: "auto", "off" or "on" -- whether whole steps leave sweep C's stores to sweep D (same bits)."""
+        self._chk(self.lib.pic_set_readonly_c(self._h, READONLY_MODES[mode]))
 
     def set_integrator(self, integrator):
         """Time integrator of the later steps: a PIC_* scheme, a reference function name or a function of that name."""

@@ -97,7 +97,13 @@ enum Stage : int {
   ST_SE = 8,       // symplectic Euler: gather at x ; kick(d) ; drift(c) ; wrap ; deposit x' ; KE ; store
   ST_FE = 9,       // forward Euler: gather at x ; drift(c) with the OLD p ; kick(d) ; wrap ; deposit x' ; KE ; store
   ST_VK = 10,      // Verlet's closing half-kick: gather at q ; kick(d) ; wrap ; KE ; store (no deposit: the input row is x''s)
-  ST_VM = 11       // Verlet, merged: as VK, then the next step's half-kick (same field) ; drift(c) ; deposit ; store
+  ST_VM = 11,      // Verlet, merged: as VK, then the next step's half-kick (same field) ; drift(c) ; deposit ; store
+  // A whole step inside one call on a state too large for the Infinity Cache (pic_create: readonly_c): sweep C stores nothing and
+  // sweep D re-derives C's output from C's input, which is still in memory -- 80 bytes per float64 particle-step instead of 96.
+  // The re-derivation is C's own arithmetic on the same operands (push_one: substage), so every bit is the same.
+  ST_C_RO = 12,    // as C without the particle stores; workgroup 0 of each environment stores its field tile (SweepIO::e2)
+  ST_D_RC = 13,    // C's sub-stage again from C's input and ST_C_RO's field tile, then as D
+  ST_D2_RC = 14    // ... then as D2
 };
 
 // Mesh accumulators that cross a kernel boundary: per environment and node the sum of shape weights as a 64-bit
@@ -139,7 +145,7 @@ struct SweepArgs {
   long long sub;      // elements from one sub-row to the next (num_envs * Ng)
   double magic;       // 1.5 * 2^(52 - fg): (w + magic) holds round(w 2^fg) in its low mantissa bits
   double L, dx, rdx, dt;   // rdx = 1/dx (float particles: 1/(float)dx)
-  double c_prev, c_cur, d_cur, c_next;
+  double c_prev, c_cur, d_cur, c_next, d_prev;   // d_prev: the kick of the sub-stage a sweep re-derives (ST_D_RC, ST_D2_RC)
   double scale, n0;   // density scale n0 L / N / dx and mean density, for the in-prologue field solve
   double to_units;    // 2^32 / L: fixed-point position units per length (PosU32)
   double N_over_L;    // PE = PE_reward N / L (util.py:130)
@@ -238,17 +244,17 @@ struct StreamOut {
 // loop-invariant scalars of a sweep in the format's arithmetic type
 template <typename P>
 struct Consts {
-  typename P::W L, dx, rdx, dt, c_prev, c_cur, d_cur, c_next;
+  typename P::W L, dx, rdx, dt, c_prev, c_cur, d_cur, c_next, d_prev;
   float to_units;
   double magic;
   int Ng;
   __device__ explicit Consts(const SweepArgs& a)
       : L((typename P::W)a.L), dx((typename P::W)a.dx), rdx((typename P::W)a.rdx), dt((typename P::W)a.dt),
         c_prev((typename P::W)a.c_prev), c_cur((typename P::W)a.c_cur), d_cur((typename P::W)a.d_cur),
-        c_next((typename P::W)a.c_next), to_units((float)a.to_units), magic(a.magic), Ng(a.Ng) {}
+        c_next((typename P::W)a.c_next), d_prev((typename P::W)a.d_prev), to_units((float)a.to_units), magic(a.magic), Ng(a.Ng) {}
   __device__ Consts(double L_, double dx_, int Ng_)
       : L((typename P::W)L_), dx((typename P::W)dx_), rdx((typename P::W)1 / (typename P::W)dx_), dt(0), c_prev(0),
-        c_cur(0), d_cur(0), c_next(0), to_units((float)(4294967296.0 / L_)), magic(0), Ng(Ng_) {}
+        c_cur(0), d_cur(0), c_next(0), d_prev(0), to_units((float)(4294967296.0 / L_)), magic(0), Ng(Ng_) {}
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -271,6 +277,10 @@ __device__ __noinline__ T wrap_periodic_far(T q, T L) {   // |q| beyond one box 
 
 template <typename T>
 __device__ __forceinline__ T wrap_periodic(T q, T L, unsigned& bad) {
+  // Wave-uniform fast path: where every lane of the wave holds 0 < q < L the result is q (two compares and a scalar branch instead
+  // of the select chain below: 13.5 VALU per wrap in float64).  Zero of either sign, NaN, inf and every position outside the box
+  // take the chain, as does the whole wave of such a lane -- a particle within one sub-stage's drift of a boundary.
+  if (__all(q > T(0) && q < L)) return q;
   // the three near ranges as selects (a particle moves a small fraction of L per sub-stage)
   T up = q + L;                       // q in [-L, 0]
   up = (up >= L) ? T(0) : up;         // tiny negative q: q + L rounds to L, the second mod gives 0

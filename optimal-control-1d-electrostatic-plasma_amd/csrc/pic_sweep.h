@@ -50,13 +50,34 @@ __device__ __forceinline__ void prologue_field(const acc_t* __restrict__ acc_in,
   PIC_STAMP(5);
 }
 
+// The force evaluation of one sub-stage: gather at q from the field tile Es, kick p with d, drift q with c.
+template <typename P, int SHAPE>
+__device__ __forceinline__ void substage(typename P::X& q, typename P::V& p, const typename P::W* __restrict__ Es,
+                                         typename P::W d, typename P::W c, const Consts<P>& k, unsigned& bad) {
+  using T = typename P::W;
+  T w[3];
+  typename P::X xw;
+  int j;
+  unsigned frac;
+  locate<P, SHAPE>(q, k, xw, j, w, frac, bad);
+  const T E = gather_field<T, SHAPE>(Es, j, w);                 // util.py:105 / pic.py:120
+  p = p + (typename P::V)((d * (-E)) * k.dt);                   // integration.py:32, pic.py:127
+  q = drift<P>(q, p, c, k, bad);                                // integration.py:42
+}
+
 // One particle through one sub-stage.  Stages D / REFRESH also deposit the NEXT step's first drift
 // position q1 = x' + (c1 p) dt into a second mesh (acc2), which is exactly what sweep A of the next
 // step would deposit from the stored x', p -- so that sweep (a full read of x and v) is skipped.
+// ST_C_RO is ST_C here (the sweep does not store); ST_D_RC / ST_D2_RC first run sweep C's sub-stage on (q2, v1) from C's field
+// tile Es2, then are ST_D / ST_D2.  That repeated drift and locate count into a scratch counter: C counted them already.
 template <typename P, typename A, int SHAPE, int STAGE>
 __device__ __forceinline__ void push_one(typename P::X& xq, typename P::V& vp, const typename P::W* __restrict__ Es,
-                                         A* __restrict__ acc, A* __restrict__ acc2, const Consts<P>& k, double& ke,
-                                         unsigned& bad) {
+                                         const typename P::W* __restrict__ Es2, A* __restrict__ acc, A* __restrict__ acc2,
+                                         const Consts<P>& k, double& ke, unsigned& bad) {
+  constexpr bool kC = (STAGE == ST_C || STAGE == ST_C_RO);
+  constexpr bool kRC = (STAGE == ST_D_RC || STAGE == ST_D2_RC);
+  constexpr bool kD = (STAGE == ST_D || STAGE == ST_D_RC);
+  constexpr bool kD2 = (STAGE == ST_D2 || STAGE == ST_D2_RC);
   using T = typename P::W;
   T w[3];
   typename P::X xw;
@@ -64,6 +85,10 @@ __device__ __forceinline__ void push_one(typename P::X& xq, typename P::V& vp, c
   unsigned frac;
   typename P::X q = xq;
   typename P::V p = vp;
+  if (kRC) {
+    unsigned again = 0u;
+    substage<P, SHAPE>(q, p, Es2, k.d_prev, k.c_prev, k, again);
+  }
   if (STAGE == ST_B2) {
     // The post-step deposit of the PREVIOUS step (pic.py:145): q is the x' that step's sweep D2 wrapped and stored, so cell and
     // weights are the ones its own deposit would have had (locate = wrap + locate_in_box, and the wrap of a wrapped position
@@ -74,21 +99,18 @@ __device__ __forceinline__ void push_one(typename P::X& xq, typename P::V& vp, c
   }
   if (STAGE == ST_A) {
     q = drift<P>(q, p, k.c_cur, k, bad);                          // integration.py:42, c1
-  } else if (STAGE == ST_B || STAGE == ST_B2 || STAGE == ST_C || STAGE == ST_D || STAGE == ST_D2) {
+  } else if (STAGE == ST_B || STAGE == ST_B2 || kC || kD || kD2) {
     if (STAGE == ST_B || STAGE == ST_B2) q = drift<P>(q, p, k.c_prev, k, bad);      // q1 again (it is never stored)
-    locate<P, SHAPE>(q, k, xw, j, w, frac, bad);
-    const T E = gather_field<T, SHAPE>(Es, j, w);                 // util.py:105 / pic.py:120
-    p = p + (typename P::V)((k.d_cur * (-E)) * k.dt);             // integration.py:32, pic.py:127
-    q = drift<P>(q, p, k.c_cur, k, bad);                          // integration.py:42
+    substage<P, SHAPE>(q, p, Es, k.d_cur, k.c_cur, k, bad);
   }
-  if (STAGE == ST_D2) {                                           // the wrap alone: the deposit of x' is the next sweep B2's
+  if (kD2) {                                           // the wrap alone: the deposit of x' is the next sweep B2's
     if constexpr (P::kFixed) xw = q;
     else xw = wrap_periodic(q, k.L, bad);
   } else {
     locate<P, SHAPE>(q, k, xw, j, w, frac, bad);
     deposit<A, P, SHAPE>(acc, j, w, frac, k.magic);
   }
-  if (STAGE == ST_D || STAGE == ST_D2 || STAGE == ST_REFRESH) {
+  if (kD || kD2 || STAGE == ST_REFRESH) {
     q = xw;                                                       // pic.py:139 (+ util.py:51)
     ke += (double)p * (double)p;
     const typename P::X qn = drift<P>(q, p, k.c_next, k, bad);    // next step's q1 (integration.py:42, c1)
@@ -214,6 +236,7 @@ struct SweepIO {
   // deposit this step's sweep B2 made of the positions it read (rounds 2-3: sweep D deposited them and sweep B carried the solve).
   // post.acc == null: no such workgroup.
   SolveIO post;
+  double* e2;              // [env][Ng + 2] field tile of sweep C_RO, which sweep D_RC / D2_RC re-derives C's output from
 };
 
 constexpr size_t kSweepInlineOffset = 2 * sizeof(void*) + sizeof(SweepIO) + sizeof(SweepArgs);   // sweep_kernel(x, v, io, a, act_inline)
@@ -227,17 +250,19 @@ __global__ __launch_bounds__(BLOCK) void sweep_kernel(typename P::X* __restrict_
   using T = typename P::W;
   using XV = typename P::XV;
   using VV = typename P::VV;
-  constexpr bool kIsB = (STAGE == ST_B || STAGE == ST_B2), kIsD = (STAGE == ST_D || STAGE == ST_D2);
-  constexpr bool kScheme = (STAGE >= ST_SE);                                   // push_scheme's stages
-  constexpr bool kGather = (kIsB || STAGE == ST_C || kIsD || kScheme);
-  constexpr bool kStore = (kGather || STAGE == ST_REFRESH);
-  constexpr bool kStoreV = kGather;
+  constexpr bool kIsB = (STAGE == ST_B || STAGE == ST_B2), kIsC = (STAGE == ST_C || STAGE == ST_C_RO);
+  constexpr bool kRC = (STAGE == ST_D_RC || STAGE == ST_D2_RC);                // re-derives sweep C_RO's output (second field tile)
+  constexpr bool kIsD = (STAGE == ST_D || STAGE == ST_D2 || kRC);
+  constexpr bool kScheme = (STAGE >= ST_SE && STAGE <= ST_VM);                 // push_scheme's stages
+  constexpr bool kGather = (kIsB || kIsC || kIsD || kScheme);
+  constexpr bool kStore = ((kGather && STAGE != ST_C_RO) || STAGE == ST_REFRESH);
+  constexpr bool kStoreV = kGather && STAGE != ST_C_RO;
   constexpr bool kReadV = (STAGE != ST_PROBE);
-  constexpr bool kFirst = (STAGE != ST_D2 && STAGE != ST_VK);                  // deposits into the first LDS mesh (-> acc_out)
+  constexpr bool kFirst = (STAGE != ST_D2 && STAGE != ST_D2_RC && STAGE != ST_VK);   // deposits into the first LDS mesh (-> acc_out)
   constexpr bool kDual = (kIsD || STAGE == ST_REFRESH || STAGE == ST_B2);      // ... into the second one (-> acc_out2)
   constexpr bool kEnergy = (kIsD || STAGE == ST_REFRESH || kScheme);           // sum of p^2 per workgroup
 
-  // LDS: [R meshes: acc][R meshes: acc2 (dual stages)][field tile Es]; the mesh region is the scratch of the
+  // LDS: [R meshes: acc][R meshes: acc2 (dual stages)][field tile Es][sweep C's field tile Es2 (kRC)]; the mesh region is the scratch of the
   // prologue solve first
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int Ng = a.Ng;
@@ -245,12 +270,13 @@ __global__ __launch_bounds__(BLOCK) void sweep_kernel(typename P::X* __restrict_
   A* acc_all = reinterpret_cast<A*>(smem_raw);
   A* acc2_all = acc_all + (size_t)a.R * stride;
   T* Es = reinterpret_cast<T*>(smem_raw + (size_t)2 * a.R * stride * sizeof(A));
+  T* Es2 = Es + stride;
   __shared__ double red[2 * WAVES];
   __shared__ double slot[2];       // mean of the prologue solve's gradient (16 B: keeps the dynamic LDS base aligned)
   static_assert(sizeof(red) + sizeof(slot) == kSweepStaticLds, "pic_create adds the static LDS to the dynamic part it sizes");
   PIC_STAMP(0);
 
-  if (STAGE == ST_C && blockIdx.x == (unsigned)a.nblk) {      // the extra workgroup of its environment (host: only with io.post.acc)
+  if (kIsC && blockIdx.x == (unsigned)a.nblk) {      // the extra workgroup of its environment (host: only with io.post.acc)
     // its arguments are read from the kernel-argument segment here, by this workgroup alone: held in scalar registers from the
     // kernel's entry on they cost every other workgroup of the sweep a wave of occupancy (pic_device.h: kernarg_at)
     SolveIO post = kernarg_at<SolveIO>(2 * sizeof(void*) + offsetof(SweepIO, post));   // x, v, io, a
@@ -304,6 +330,10 @@ __global__ __launch_bounds__(BLOCK) void sweep_kernel(typename P::X* __restrict_
                            (io.ext_out && blk == 0) ? io.ext_out + (size_t)env * Ng : nullptr, Ng, ldexp(1.0, -a.fg), a.scale, a.n0, a.dx,
                            reinterpret_cast<double*>(acc2_all), reinterpret_cast<double*>(smem_raw), slot, Es);
   }
+  if (STAGE == ST_C_RO && blk == 0)      // the field tile of this force evaluation, for the sweep that re-derives it
+    for (int c = tid; c < stride; c += BLOCK) io.e2[(size_t)env * stride + c] = (double)Es[c];
+  if (kRC)                               // (the barrier behind the mesh clearing below covers these LDS writes: kRC is dual)
+    for (int c = tid; c < stride; c += BLOCK) Es2[c] = (T)io.e2[(size_t)env * stride + c];
   if (kIsD && io.next_act && io.ext_out && blk == 0) {   // (inside a rollout: one workgroup per environment)
     const Control ctl = io.ctl;
     for (int j = tid; j < Ng; j += BLOCK)
@@ -336,7 +366,7 @@ __global__ __launch_bounds__(BLOCK) void sweep_kernel(typename P::X* __restrict_
     for (int c = 0; c < VEC; ++c) {
       typename P::V pv = kReadV ? vs[c] : typename P::V(0);
       if constexpr (kScheme) push_scheme<P, A, SHAPE, STAGE>(xs[c], pv, Es, acc, k, ke, bad);
-      else push_one<P, A, SHAPE, STAGE>(xs[c], pv, Es, acc, acc2, k, ke, bad);
+      else push_one<P, A, SHAPE, STAGE>(xs[c], pv, Es, Es2, acc, acc2, k, ke, bad);
       if (kReadV) vs[c] = pv;
     }
     if (kStore) {
@@ -355,7 +385,7 @@ __global__ __launch_bounds__(BLOCK) void sweep_kernel(typename P::X* __restrict_
     typename P::X xq = xe[c];
     typename P::V pv = kReadV ? ve[c] : typename P::V(0);
     if constexpr (kScheme) push_scheme<P, A, SHAPE, STAGE>(xq, pv, Es, acc, k, ke, bad);
-    else push_one<P, A, SHAPE, STAGE>(xq, pv, Es, acc, acc2, k, ke, bad);
+    else push_one<P, A, SHAPE, STAGE>(xq, pv, Es, Es2, acc, acc2, k, ke, bad);
     if (kStore) {
       xe[c] = xq;
       if (kStoreV) ve[c] = pv;

@@ -172,6 +172,9 @@ struct pic_handle {
   int post_slot = -1;                 // ring row whose post-step solve rides with the next sweep C (inside pic_step only)
   bool refresh_pending = false;       // the last sweep was a D2 (inside pic_step only): the next sweep B deposits the positions it reads
   bool light_inner_steps = false;     // inner steps of a call end with sweep D2 (pic_create: particle states of 256 MB and more)
+  bool readonly_c = false;            // whole steps run sweeps C_RO and D_RC / D2_RC (pic_set_readonly_c, or readonly_auto)
+  bool readonly_auto = false;         // pic_create's choice
+  size_t sweep_lds_rc = 0;            // LDS of sweeps D_RC / D2_RC: sweep_lds and sweep C's field tile; 0 = does not fit
   double* hist_row = nullptr;         // where the NEXT post-step solve also records its three energies (step_recording), or null
   double* post_hist_row = nullptr;    // the same for the solve that post_slot stands for
   PlacementStats place{};             // what the search for an (x, v) placement did, all legs together (pic_placement_stats)
@@ -197,6 +200,7 @@ struct pic_handle {
   double* phi = nullptr;
   double* ext = nullptr;          // device copy of a host E_ext / the actuator's field of a step, built once per environment (run_stages)
   double* ext2 = nullptr;         // ... of the step after it (a rollout alternates between the two)
+  double* e2 = nullptr;           // [env][Ng + 2] sweep C_RO's field tile, read by sweep D_RC / D2_RC
   int ext_turn = 0;               // which of the two holds the field of the step being launched
   double* basis = nullptr;        // [2][Ng][M] actuator tables (cos, sin)
   double* act = nullptr;          // [env][2M] actions: device copy of a host action / the feedback law's current action
@@ -319,9 +323,10 @@ void ring_retire(pic_handle* h, int slot) {
 
 template <typename P, typename A, int SHAPE, int STAGE>
 void launch_sweep_t(pic_handle* h, const SweepIO& io, void* x, void* v, const SweepArgs& a) {
-  dim3 grid(h->nblk + ((STAGE == ST_C && io.post.acc) ? 1 : 0), h->cfg.num_envs);
+  dim3 grid(h->nblk + (((STAGE == ST_C || STAGE == ST_C_RO) && io.post.acc) ? 1 : 0), h->cfg.num_envs);
   static const InlineDoubles none{};
-  hipLaunchKernelGGL((sweep_kernel<P, A, SHAPE, STAGE>), grid, dim3(BLOCK), h->sweep_lds, h->stream,
+  const size_t lds = (STAGE == ST_D_RC || STAGE == ST_D2_RC) ? h->sweep_lds_rc : h->sweep_lds;
+  hipLaunchKernelGGL((sweep_kernel<P, A, SHAPE, STAGE>), grid, dim3(BLOCK), lds, h->stream,
                      static_cast<typename P::X*>(x), static_cast<typename P::V*>(v), io, a, a.act_inline ? *h->inline_act : none);
 }
 
@@ -339,6 +344,9 @@ void launch_sweep_s(pic_handle* h, const SweepIO& io, int stage, void* x, void* 
     case ST_FE: launch_sweep_t<P, A, SHAPE, ST_FE>(h, io, x, v, a); break;
     case ST_VK: launch_sweep_t<P, A, SHAPE, ST_VK>(h, io, x, v, a); break;
     case ST_VM: launch_sweep_t<P, A, SHAPE, ST_VM>(h, io, x, v, a); break;
+    case ST_C_RO: launch_sweep_t<P, A, SHAPE, ST_C_RO>(h, io, x, v, a); break;
+    case ST_D_RC: launch_sweep_t<P, A, SHAPE, ST_D_RC>(h, io, x, v, a); break;
+    case ST_D2_RC: launch_sweep_t<P, A, SHAPE, ST_D2_RC>(h, io, x, v, a); break;
     default: launch_sweep_t<P, A, SHAPE, ST_PROBE>(h, io, x, v, a); break;
   }
 }
@@ -428,6 +436,8 @@ void launch_sweep(pic_handle* h, int stage, void* x, void* v, double c_prev, dou
   a.reverse = push ? (h->sweep_parity ^= 1) : 0;
   a.S = h->S; a.sub = (long long)h->cfg.num_envs * h->cfg.Ng;
   a.c_prev = c_prev; a.c_cur = c_cur; a.d_cur = d_cur; a.c_next = h->cs[0];
+  const bool rc = stage == ST_D_RC || stage == ST_D2_RC;
+  a.d_prev = rc ? h->ds[2] : 0.0;      // the sub-stage these sweeps re-derive is sweep C's: kick d3, drift c3 (c_prev)
   SweepIO io{};
   io.acc_in = in_slot >= 0 ? ring_row(h, in_slot) : nullptr;
   io.ctl = ctl;
@@ -444,6 +454,7 @@ void launch_sweep(pic_handle* h, int stage, void* x, void* v, double c_prev, dou
   io.zero1 = z[1] >= 0 ? ring_row(h, z[1]) : nullptr;
   io.ke_part = h->ke_part;
   io.bad = out == h->probe_acc ? h->probe_bad : h->bad;
+  io.e2 = h->e2;
   if (post_slot >= 0) {            // sweep C also carries the previous step's post-step refresh (pic_sweep.h: SweepIO::post)
     io.post.acc = ring_row(h, post_slot);
     io.post.ke_part = h->ke_part; io.post.n = h->n; io.post.out.E = h->E_mesh; io.post.out.phi = h->phi;
@@ -451,8 +462,9 @@ void launch_sweep(pic_handle* h, int stage, void* x, void* v, double c_prev, dou
     io.post.out.hist = h->post_hist_row; io.post.out.num_envs = h->cfg.num_envs;
   }
   // (the particle sweeps of the other integrators -- Verlet's opening sweep is a sweep C -- count in the eighth kind)
-  const bool scheme_sweep = stage >= ST_SE || (stage == ST_C && h->scheme != PIC_YOSHIDA4);
-  prof_begin(h, scheme_sweep ? 7 : stage <= ST_D ? stage : (stage == ST_B2 ? (int)ST_B : (stage == ST_D2 ? (int)ST_D : 5)));
+  const bool scheme_sweep = (stage >= ST_SE && stage <= ST_VM) || (stage == ST_C && h->scheme != PIC_YOSHIDA4);
+  prof_begin(h, scheme_sweep ? 7 : stage <= ST_D ? stage : stage == ST_B2 ? (int)ST_B : stage == ST_C_RO ? (int)ST_C
+                : (stage == ST_D2 || rc) ? (int)ST_D : 5);
   with_format(h, [&](auto p) { launch_sweep_p<decltype(p)>(h, io, stage, x, v, a); });
   prof_end(h);
   for (int k = 0; k < 2; ++k)
@@ -1117,6 +1129,10 @@ int pic_create(const pic_config* cfg, pic_handle** out) {
   // gain nothing or lose (all measured on one box, round 3's tree against this one: 8 x 1e6 float64 131.2 -> 132.6, 64 x 20000
   // float32 TSC 26.2 -> 27.2, config 1 14.5 -> 14.7, one environment of N = 1e5 19.1 -> 19.4): they keep the full sweep D.
   h->light_inner_steps = 2.0 * (double)cfg->num_envs * (double)h->ld * (double)h->esz >= 256.0 * 1048576.0;
+  // Whole steps on such a state also leave sweep C's stores out: sweep D re-derives C's output from C's input (ST_C_RO, ST_D_RC,
+  // ST_D2_RC) -- 80 instead of 96 bytes per float64 particle-step, and D's extra sub-stage fits its issue slots with the wave-uniform
+  // wrap (config 2 959 -> 865 us per step; profiles/r5_readonly.md).  pic_set_readonly_c overrides the choice.
+  h->readonly_auto = h->light_inner_steps;
   h->S = 1;
   while (h->S < 4 && nblk / (2 * h->S) >= 8 && (long long)cfg->num_envs * 2 * h->S <= 32) h->S *= 2;
 
@@ -1130,6 +1146,9 @@ int pic_create(const pic_config* cfg, pic_handle** out) {
   h->solve_lds = 2 * (size_t)cfg->Ng * sizeof(double);
   // a workgroup may use 64 KB of LDS: the dynamic part sized here plus the kernels' static arrays (kSweepStaticLds, kResidentStaticLds)
   constexpr size_t kLdsLimit = 64 * 1024;
+  if (h->sweep_lds + stride * h->esz + kSweepStaticLds <= kLdsLimit) h->sweep_lds_rc = h->sweep_lds + stride * h->esz;
+  else h->readonly_auto = false;
+  h->readonly_c = h->readonly_auto;
   if (h->sweep_lds + kSweepStaticLds > kLdsLimit) {
     const long long max_ng = (long long)((kLdsLimit - kSweepStaticLds) / (2 * h->R * 8 + h->esz)) - 2;
     delete h;
@@ -1212,6 +1231,7 @@ int pic_create(const pic_config* cfg, pic_handle** out) {
     CREATE_CHK(hipMalloc((void**)g, gbytes));
     CREATE_CHK(hipMemsetAsync(*g, 0, gbytes, h->stream));
   }
+  CREATE_CHK(hipMalloc((void**)&h->e2, (size_t)cfg->num_envs * (cfg->Ng + 2) * sizeof(double)));
   // KE | PE | PE_reward live in one allocation so that a getter is a single small D2H copy into
   // pinned memory (a Python RL loop reads them every step)
   const size_t sbytes = (size_t)cfg->num_envs * sizeof(double);
@@ -1240,7 +1260,7 @@ int pic_destroy(pic_handle* h) {
   prof_drain(h);
   for (hipEvent_t e : h->ev) hipEventDestroy(e);
   void* bufs[] = {h->rec.d, h->rec.u, h->rec.phase, h->rec.feq, h->x, h->scratch, h->stage, h->ring, h->ke_part, h->n, h->E_mesh, h->phi, h->ext, h->ext2, h->probe_ext,
-                  h->basis, h->act, h->modes, h->aux_n, h->aux_E, h->aux_pe, h->aux_phi, h->KE, h->bad, h->tw, h->traj, h->res_q1, h->res_carry, h->tape.block,
+                  h->e2, h->basis, h->act, h->modes, h->aux_n, h->aux_E, h->aux_pe, h->aux_phi, h->KE, h->bad, h->tw, h->traj, h->res_q1, h->res_carry, h->tape.block,
                   h->gain, h->fb_modes, h->tape.law_block};
   for (double* g : h->tape.gains) hipFree(g);
   for (void* b : bufs)
@@ -1357,6 +1377,9 @@ static void run_stages(pic_handle* h, int from, int upto, const Control& ctl, bo
   double* mine = h->ext_turn ? h->ext2 : h->ext;
   double* other = h->ext_turn ? h->ext : h->ext2;
   Control first = ctl, later = ctl;
+  // A whole step runs sweep C without its stores where the handle chose it (readonly_c): sweep D re-derives them.  A staged step
+  // keeps them, since its caller may read the particles between the stages.
+  const bool ro = h->readonly_c && from <= 2 && upto == 3;
   if (share_field) {
     later.act = nullptr; later.ext = mine;
     if (field_ready) first = later;
@@ -1385,7 +1408,7 @@ static void run_stages(pic_handle* h, int from, int upto, const Control& ctl, bo
       h->stage_slot = x1;
     } else if (st == 2) {
       const int x2 = ring_take_clean(h);
-      launch_sweep(h, ST_C, h->x, h->v, 0.0, c[2], d[2], h->stage_slot, later, ring_row(h, x2), nullptr, h->post_slot);
+      launch_sweep(h, ro ? ST_C_RO : ST_C, h->x, h->v, 0.0, c[2], d[2], h->stage_slot, later, ring_row(h, x2), nullptr, h->post_slot);
       ring_retire(h, h->post_slot);
       h->post_slot = -1;
       ring_retire(h, h->stage_slot);
@@ -1396,14 +1419,14 @@ static void run_stages(pic_handle* h, int from, int upto, const Control& ctl, bo
         // an inner step of a call: nothing can see its post-step fields before the next step has started, so the deposit they come
         // from is left to that step's sweep B2 (sweep D is the one sweep bound by VALU issue: 336 -> 321 us at config 2, B 320 -> 322)
         const int qn = ring_take_clean(h);
-        launch_sweep(h, ST_D2, h->x, h->v, 0.0, c[3], d[3], h->stage_slot, later, nullptr, ring_row(h, qn), -1,
+        launch_sweep(h, ro ? ST_D2_RC : ST_D2, h->x, h->v, ro ? c[2] : 0.0, c[3], d[3], h->stage_slot, later, nullptr, ring_row(h, qn), -1,
                      hand_on ? other : nullptr, hand_on ? next_act : nullptr);
         h->refresh_pending = true;
         h->post_hist_row = h->hist_row;
         h->q_slot = qn;
       } else {
         const int f = ring_take_clean(h), qn = ring_take_clean(h);
-        launch_sweep(h, ST_D, h->x, h->v, 0.0, c[3], d[3], h->stage_slot, later, ring_row(h, f), ring_row(h, qn), -1,
+        launch_sweep(h, ro ? ST_D_RC : ST_D, h->x, h->v, ro ? c[2] : 0.0, c[3], d[3], h->stage_slot, later, ring_row(h, f), ring_row(h, qn), -1,
                      hand_on ? other : nullptr, hand_on ? next_act : nullptr);
         // (a small state's inner step: the full sweep D, its solve still not a launch -- it rides with the next step's sweep C)
         if (another_step_follows) { h->post_slot = f; h->post_hist_row = h->hist_row; }
@@ -1701,6 +1724,15 @@ int pic_set_integrator(pic_handle* h, int scheme) {
   if (scheme == h->scheme) return PIC_OK;
   drop_cached_deposits(h);           // the cached deposit belongs to a scheme (Yoshida-4: q1 = x + (c1 v) dt; the others: x)
   h->scheme = scheme;
+  return PIC_OK;
+}
+
+int pic_set_readonly_c(pic_handle* h, int mode) {
+  if (!h) return PIC_EINVAL;
+  if (mode < PIC_READONLY_AUTO || mode > PIC_READONLY_ON) return fail(h, PIC_EINVAL, "pic_set_readonly_c: unknown mode");
+  if (mode == PIC_READONLY_ON && !h->sweep_lds_rc)
+    return fail(h, PIC_EINVAL, "pic_set_readonly_c: Ng too large for the second field tile of sweep D_RC");
+  h->readonly_c = mode == PIC_READONLY_AUTO ? h->readonly_auto : mode == PIC_READONLY_ON;
   return PIC_OK;
 }
 
