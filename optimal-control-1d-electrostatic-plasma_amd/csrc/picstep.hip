@@ -45,6 +45,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -79,6 +80,61 @@ struct PlacementState {
 };
 constexpr int RING = 8;                                          // accumulator rows in rotation
 
+// The owner of one HIP resource (device block, pinned host block, event, stream): move-only, releases what it holds at most once
+// (an empty owner releases nothing), and converts to the raw handle, so that launches and argument blocks take it as they did
+// the pointer.
+template <typename P, auto Release>
+class Owner {
+ public:
+  Owner() = default;
+  explicit Owner(P p) : p_(p) {}
+  Owner(Owner&& o) noexcept : p_(o.release()) {}
+  Owner& operator=(Owner&& o) noexcept { reset(o.release()); return *this; }
+  ~Owner() { reset(); }
+  void reset(P p = nullptr) {
+    if (p_ && p_ != p) (void)Release(p_);
+    p_ = p;
+  }
+  P release() { P p = p_; p_ = nullptr; return p; }
+  P get() const { return p_; }
+  operator P() const { return p_; }
+
+ private:
+  P p_ = nullptr;
+};
+template <typename T> using DeviceBuf = Owner<T*, hipFree>;
+template <typename T> using PinnedBuf = Owner<T*, hipHostFree>;
+using EventOwner = Owner<hipEvent_t, hipEventDestroy>;
+using StreamOwner = Owner<hipStream_t, hipStreamDestroy>;
+
+// b lets its block go, then holds `bytes` of new memory (or nothing: the allocation's error is returned)
+template <typename T>
+hipError_t alloc(DeviceBuf<T>& b, size_t bytes) {
+  b.reset();
+  void* p = nullptr;
+  const hipError_t e = hipMalloc(&p, bytes);
+  if (e == hipSuccess) b.reset(static_cast<T*>(p));
+  return e;
+}
+template <typename T>
+hipError_t alloc(PinnedBuf<T>& b, size_t bytes) {
+  b.reset();
+  void* p = nullptr;
+  const hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
+  if (e == hipSuccess) b.reset(static_cast<T*>(p));
+  return e;
+}
+// alloc, then the block zeroed on `stream`
+template <typename T>
+hipError_t alloc_zeroed(DeviceBuf<T>& b, size_t bytes, hipStream_t stream) {
+  const hipError_t e = alloc(b, bytes);
+  return e != hipSuccess ? e : hipMemsetAsync(b, 0, bytes, stream);
+}
+inline EventOwner make_event() {        // empty if hipEventCreate fails
+  hipEvent_t e = nullptr;
+  return EventOwner(hipEventCreate(&e) == hipSuccess ? e : nullptr);
+}
+
 // The rollout recorder of a handle (pic_record_*, pic_record.h).  Records live in two device arrays, one slot per record:
 // doubles [cap][env][d_stride] (KE, PE, PE_reward, field_energy, entropy, kl, re [M], im [M]) and uint32 [cap][env][u_stride]
 // (x_hist, v_hist, inside), the latter zeroed when recording starts; the step indices are known here.
@@ -90,10 +146,10 @@ struct Recorder {
   int64_t k = 0;                      // steps made since pic_record_start
   std::vector<int64_t> steps;         // step index of every record held
   long long d_stride = 0, u_stride = 0;
-  double* d = nullptr;
-  unsigned* u = nullptr;
-  unsigned* phase = nullptr;          // [env][px pv] counts of the record being made (zero between records)
-  double* feq = nullptr;              // [px pv] or null
+  DeviceBuf<double> d;
+  DeviceBuf<unsigned> u;
+  DeviceBuf<unsigned> phase;          // [env][px pv] counts of the record being made (zero between records)
+  DeviceBuf<double> feq;              // [px pv] or null
   int phase_lds = 0;
   int rr = 1;                         // copies of each marginal bin in the particle pass's LDS
   size_t lds = 0;
@@ -104,12 +160,12 @@ struct Recorder {
 
 // The tape of a differentiable rollout (pic_tape_*, pic_adjoint.h).  One device block holds the checkpoints
 // (x, v every `every` steps, the first at pic_tape_start), every step's external field and all the backward's working memory,
-// (a-bar included), so that pic_tape_backward allocates nothing.
+// (a-bar included), so that pic_tape_backward allocates nothing.  ck .. gact are views into `block`, lact .. lE into `law_block`.
 struct Tape {
   bool on = false;
   int64_t max_steps = 0, every = 1, steps = 0, nck = 0;
   size_t bytes = 0;
-  void* block = nullptr;
+  DeviceBuf<void> block;
   double* ck = nullptr;               // [nck][2][env][ld] checkpoints: (x, v) before step c * every
   double* ext = nullptr;              // [max_steps][env][Ng] e_t
   double* seg = nullptr;              // [every + 1][2][env][ld] one segment's replayed states
@@ -127,21 +183,21 @@ struct Tape {
   int64_t budget = 0;                 // budget_bytes of pic_tape_start (0: none)
   // steps of the gain law (pic_step_feedback_gain): one block allocated by the first such call, one gain per call;
   // both count in `bytes`
-  void* law_block = nullptr;
+  DeviceBuf<void> law_block;
   double* lact = nullptr;             // [max_steps][env][2M] a_t of the law's steps (their e_t = B a_t goes to `ext` behind the call)
   double* lmodes = nullptr;           // [max_steps][env][2M] m_t of the law's steps, zero on the others
   double* lcot = nullptr;             // [max_steps][env][2M] cotangents on m_t of a backward
   double* lE = nullptr;               // [env][Ng] E-bar_t = J^T (G^T a-bar_t + m-bar_t) of a law step
   std::vector<int> law;               // [max_steps] per step: the index of its gain in `gains`, or -1 (empty: no law step yet)
-  std::vector<double*> gains;         // per call: [env][2M][2M]
+  std::vector<DeviceBuf<double>> gains;   // per call: [env][2M][2M]
   // the reverse walk (pic_tape_walk_*); pic_tape_backward[_feedback] is a walk of its own.  Any append, start,
   // stop, backward or new walk abandons it.
   bool walk = false;                  // a walk is in progress
   int64_t wnext = -1;                 // the next step it reverses (-1: all walked)
   int wmo = 0;                        // M_o: modes of the walk's mode cotangents
-  double* wstage = nullptr;           // [2][env][N] + [env][2 M_o] host cotangents of a step on the device (allocated on demand)
+  DeviceBuf<double> wstage;           // [2][env][N] + [env][2 M_o] host cotangents of a step on the device (allocated on demand)
   size_t wstage_bytes = 0;
-  double* wE = nullptr;               // [env][Ng] E-bar of a walk's mode cotangents on a tape without a law block (else lE)
+  DeviceBuf<double> wE;               // [env][Ng] E-bar of a walk's mode cotangents on a tape without a law block (else lE)
 };
 
 struct pic_handle {
@@ -167,7 +223,7 @@ struct pic_handle {
   double cs[4]{}, ds[4]{};
   int scheme = PIC_YOSHIDA4;          // time integrator of the steps (pic_set_integrator)
   hipStream_t stream = nullptr;       // the stream every call works on (own_stream, or the caller's)
-  hipStream_t own_stream = nullptr;   // created by pic_create, destroyed by pic_destroy
+  StreamOwner own_stream;             // created by pic_create (declared ahead of the buffers: destroyed after them)
   bool v_separate = false;            // v is an allocation of its own (large states: alloc_particles)
   int post_slot = -1;                 // ring row whose post-step solve rides with the next sweep C (inside pic_step only)
   bool refresh_pending = false;       // the last sweep was a D2 (inside pic_step only): the next sweep B deposits the positions it reads
@@ -181,65 +237,66 @@ struct pic_handle {
   PlacementState place_state{};       // what a later leg of it needs to know (placement_leg, resume_placement)
   Recorder rec{};                     // pic_record_*: reductions recorded after every rec.stride-th step (advance, pic_step_stage)
   Tape tape{};                        // pic_tape_*: checkpoints and external fields of a differentiable rollout (advance)
-  void* x = nullptr;
-  void* v = nullptr;
-  void* scratch = nullptr;        // [env][ld] positions of a probe (eval_field / compute_E)
-  void* stage = nullptr;          // [env][N] float staging: fixed-point positions <-> the caller's floats
+  DeviceBuf<void> x;
+  void* v = nullptr;              // v_block, or a view into x's block (!v_separate)
+  DeviceBuf<void> v_block;        // v's own allocation (v_separate)
+  DeviceBuf<void> scratch;        // [env][ld] positions of a probe (eval_field / compute_E)
+  DeviceBuf<void> stage;          // [env][N] float staging: fixed-point positions <-> the caller's floats
   // accumulator ring: rows [env][Ng] of 64-bit fixed-point weight sums
-  acc_t* ring = nullptr;
+  DeviceBuf<acc_t> ring;
   std::vector<int> clean, dirty;  // rows that are zero / rows whose readers have all been enqueued
   hipError_t ring_error = hipSuccess;   // a clearing memset of ring_take_clean that failed (reported by launch_status)
   int q_slot = -1;                // row holding the deposit of the NEXT step's q1 (sweep A is skipped while >= 0)
   int stage_slot = -1;            // pic_step_stage: row the next stage's field comes from
   int sweep_parity = 0;           // direction of the next push sweep
-  acc_t* probe_acc = nullptr;     // accumulator row of the probes (their own: a probe never touches step state)
-  double* probe_ext = nullptr;    // device copy of a probe's host E_ext
-  double* ke_part = nullptr;      // [env][nblk]
-  double* n = nullptr;
-  double* E_mesh = nullptr;
-  double* phi = nullptr;
-  double* ext = nullptr;          // device copy of a host E_ext / the actuator's field of a step, built once per environment (run_stages)
-  double* ext2 = nullptr;         // ... of the step after it (a rollout alternates between the two)
-  double* e2 = nullptr;           // [env][Ng + 2] sweep C_RO's field tile, read by sweep D_RC / D2_RC
+  acc_t* probe_acc = nullptr;     // view: ring's accumulator row of the probes (their own: a probe never touches step state)
+  DeviceBuf<double> probe_ext;    // device copy of a probe's host E_ext
+  DeviceBuf<double> ke_part;      // [env][nblk]
+  DeviceBuf<double> n;
+  DeviceBuf<double> E_mesh;
+  DeviceBuf<double> phi;
+  DeviceBuf<double> ext;          // device copy of a host E_ext / the actuator's field of a step, built once per environment (run_stages)
+  DeviceBuf<double> ext2;         // ... of the step after it (a rollout alternates between the two)
+  DeviceBuf<double> e2;           // [env][Ng + 2] sweep C_RO's field tile, read by sweep D_RC / D2_RC
   int ext_turn = 0;               // which of the two holds the field of the step being launched
-  double* basis = nullptr;        // [2][Ng][M] actuator tables (cos, sin)
-  double* act = nullptr;          // [env][2M] actions: device copy of a host action / the feedback law's current action
-  double* modes = nullptr;        // [2][env][M] Fourier modes (re, im)
+  DeviceBuf<double> basis;        // [2][Ng][M] actuator tables (cos, sin)
+  DeviceBuf<double> act;          // [env][2M] actions: device copy of a host action / the feedback law's current action
+  DeviceBuf<double> modes;        // [2][env][M] Fourier modes (re, im)
   int act_modes = 0;
   int modes_cap = 0;
-  double* tw = nullptr;           // [2][tw_rows][Ng] twiddles of modes 1..tw_rows (pic_aux.h: twiddle_kernel)
+  DeviceBuf<double> tw;           // [2][tw_rows][Ng] twiddles of modes 1..tw_rows (pic_aux.h: twiddle_kernel)
   int tw_rows = 0;
-  void* traj = nullptr;           // device copy of a host trajectory of actions or fields (pic_step_*_traj), grown on demand
+  DeviceBuf<void> traj;           // device copy of a host trajectory of actions or fields (pic_step_*_traj), grown on demand
   size_t traj_bytes = 0;
-  unsigned long long* res_q1 = nullptr;   // resident schedule: [env][R (Ng + 2)] LDS mesh of the next step's q1 deposit, launch to launch
+  DeviceBuf<unsigned long long> res_q1;   // resident schedule: [env][R (Ng + 2)] LDS mesh of the next step's q1 deposit, launch to launch
   bool res_q1_valid = false;
-  void* res_carry = nullptr;              // ... and the cell and weights of every particle's q1 (pic_resident.h: ResidentEdge), or null
+  DeviceBuf<void> res_carry;              // ... and the cell and weights of every particle's q1 (pic_resident.h: ResidentEdge), or null
   bool res_carry_valid = false;
   const InlineDoubles* inline_act = nullptr;   // streaming schedule, for the duration of a call: the held action rides in the sweeps' argument blocks
   Feedback fb{};                  // feedback outputs wanted from the NEXT post-step solve of the streaming schedule (fb.M = 0: none)
-  double* gain = nullptr;         // [env][2M][2M] device copy of a host gain (pic_step_feedback_gain)
-  double* fb_modes = nullptr;     // [env][2 kMaxFeedbackModes] the gain law's m, step by step
-  double* aux_n = nullptr;        // probe outputs
-  double* aux_E = nullptr;
-  double* aux_pe = nullptr;
-  double* h_probe_pe = nullptr;   // pinned host: the energy of a probe, written by the solve itself (pic_eval_field of a small host state)
+  DeviceBuf<double> gain;         // [env][2M][2M] device copy of a host gain (pic_step_feedback_gain)
+  DeviceBuf<double> fb_modes;     // [env][2 kMaxFeedbackModes] the gain law's m, step by step
+  DeviceBuf<double> aux_n;        // probe outputs
+  DeviceBuf<double> aux_E;
+  DeviceBuf<double> aux_pe;
+  PinnedBuf<double> h_probe_pe;   // pinned host: the energy of a probe, written by the solve itself (pic_eval_field of a small host state)
   bool probe_row_clean = false;   // the probes' accumulator row is zero (the solve of the last probe cleared it behind its read)
-  double* aux_phi = nullptr;
+  DeviceBuf<double> aux_phi;
   int mid_stage = 0;              // pic_step_stage: force evaluations of the current step already done (0 = between steps)
-  double* KE = nullptr;
-  double* PE = nullptr;
+  DeviceBuf<double> KE;
+  double* PE = nullptr;           // views into KE's block
   double* PEr = nullptr;
-  double* h_scal = nullptr;       // pinned host staging for KE | PE | PE_reward
-  void* h_part = nullptr;         // pinned host staging for x | v of states up to 64 MB (from pic_create on up to 4 MB, else on first use)
+  PinnedBuf<double> h_scal;       // pinned host staging for KE | PE | PE_reward
+  PinnedBuf<void> h_part;         // pinned host staging for x | v of states up to 64 MB (from pic_create on up to 4 MB, else on first use)
   bool h_part_refused = false;    // ... could not be had: do not ask again
-  double* h_fields = nullptr;     // pinned host staging for n | E_mesh | phi (meshes up to 256 KB each in total), or null
-  unsigned long long* bad = nullptr;
-  unsigned long long* probe_bad = nullptr;   // bad + 1: where the probes count their non-finite positions (never read: pic_bad_count
+  PinnedBuf<double> h_fields;     // pinned host staging for n | E_mesh | phi (meshes up to 256 KB each in total), or null
+  DeviceBuf<unsigned long long> bad;
+  unsigned long long* probe_bad = nullptr;   // view: bad + 1, where the probes count their non-finite positions (never read: pic_bad_count
                                              // describes the state's particles, and a probe's positions are not among them)
   bool has_state = false;
   // profiling
   bool prof = false;
-  std::vector<hipEvent_t> ev;     // pairs
+  std::vector<EventOwner> ev;     // pairs
   std::vector<int> ev_kind;
   double ms_sum[8]{};
   int64_t launches[8]{};
@@ -382,9 +439,9 @@ void prof_drain(pic_handle* h) {
 }
 void prof_reserve(pic_handle* h, size_t pairs) {
   while (h->ev.size() < 2 * pairs) {
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) break;
-    h->ev.push_back(e);
+    EventOwner e = make_event();
+    if (!e) break;
+    h->ev.push_back(std::move(e));
   }
 }
 void prof_begin(pic_handle* h, int kind) {
@@ -475,7 +532,7 @@ template <typename P, typename A, int SHAPE, int PPT, int NW>
 void launch_resident_t(pic_handle* h, const ResidentIO& io, const SweepArgs& a, const InlineDoubles& act) {
   if (h->scheme != PIC_YOSHIDA4) {      // the other integrators: a kernel of their own (pic_resident.h: resident_scheme_kernel)
     const dim3 grid(h->cfg.num_envs), block(NW * 64);
-    auto* x = static_cast<typename P::X*>(h->x);
+    auto* x = static_cast<typename P::X*>(h->x.get());
     auto* v = static_cast<typename P::V*>(h->v);
     if (h->scheme == PIC_SYMPLECTIC_EULER)
       hipLaunchKernelGGL((resident_scheme_kernel<P, A, SHAPE, PPT, NW, PIC_SYMPLECTIC_EULER>), grid, block, h->res_lds, h->stream, x, v, io, a, act);
@@ -493,12 +550,12 @@ void launch_resident_t(pic_handle* h, const ResidentIO& io, const SweepArgs& a, 
   if constexpr (kCarryFits) {
     if (!h->res_lean) {
       hipLaunchKernelGGL((resident_kernel<P, A, SHAPE, PPT, NW, true>), dim3(h->cfg.num_envs), dim3(NW * 64), h->res_lds,
-                         h->stream, static_cast<typename P::X*>(h->x), static_cast<typename P::V*>(h->v), io, a, act);
+                         h->stream, static_cast<typename P::X*>(h->x.get()), static_cast<typename P::V*>(h->v), io, a, act);
       return;
     }
   }
   hipLaunchKernelGGL((resident_kernel<P, A, SHAPE, PPT, NW, false>), dim3(h->cfg.num_envs), dim3(NW * 64), h->res_lds,
-                     h->stream, static_cast<typename P::X*>(h->x), static_cast<typename P::V*>(h->v), io, a, act);
+                     h->stream, static_cast<typename P::X*>(h->x.get()), static_cast<typename P::V*>(h->v), io, a, act);
 }
 
 template <typename P, typename A, int SHAPE>
@@ -624,9 +681,21 @@ dim3 aux_grid(pic_handle* h, int nenv, long long cap = 1024) {
   return dim3((unsigned)gx, nenv);
 }
 
+// A buffer of the handle (re)allocated with `bytes`: the stream is drained if there is an old block (queued work may still read
+// it), the old block goes, the new one takes its place.  On failure b is empty.
+template <typename T>
+int regrow(pic_handle* h, DeviceBuf<T>& b, size_t bytes, const char* what) {
+  if (b) HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (alloc(b, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(h, PIC_ENOMEM, what);
+  }
+  return PIC_OK;
+}
+
 int ensure_stage(pic_handle* h) {
   if (h->stage) return PIC_OK;
-  HIPCHK(h, hipMalloc(&h->stage, (size_t)h->cfg.num_envs * h->cfg.N * sizeof(float)));
+  HIPCHK(h, alloc(h->stage, (size_t)h->cfg.num_envs * h->cfg.N * sizeof(float)));
   return PIC_OK;
 }
 
@@ -646,7 +715,7 @@ int upload_positions(pic_handle* h, void* dst_padded, const void* src, int mem_k
     int rc = ensure_stage(h);
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(h->stage, src, (size_t)h->cfg.num_envs * h->cfg.N * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    dsrc = static_cast<const float*>(h->stage);
+    dsrc = static_cast<const float*>(h->stage.get());
   }
   hipLaunchKernelGGL((positions_in_kernel<PosU32, float>), aux_grid(h, h->cfg.num_envs), dim3(BLOCK), 0, h->stream, dsrc,
                      static_cast<unsigned*>(dst_padded), h->cfg.N, h->ld, h->cfg.L, bad);
@@ -667,7 +736,7 @@ int download_positions(pic_handle* h, void* dst, const void* src_padded, int mem
   if (mem_kind == PIC_HOST) {
     int rc = ensure_stage(h);
     if (rc) return rc;
-    ddst = static_cast<float*>(h->stage);
+    ddst = static_cast<float*>(h->stage.get());
   }
   hipLaunchKernelGGL((positions_out_kernel<PosU32, float>), aux_grid(h, h->cfg.num_envs), dim3(BLOCK), 0, h->stream,
                      static_cast<const unsigned*>(src_padded), ddst, h->cfg.N, h->ld, h->cfg.L);
@@ -786,15 +855,15 @@ void placement_leg(pic_handle* h, size_t pbytes) {
   auto seconds = [t_begin]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(); };
   ps.legs += 1;
   size_t free_b = 0, total_b = 0;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  bool ok = hipMemGetInfo(&free_b, &total_b) == hipSuccess && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
+  EventOwner e0, e1;
+  bool ok = hipMemGetInfo(&free_b, &total_b) == hipSuccess && (e0 = make_event()) && (e1 = make_event());
   const size_t budget = free_b / 3;
   const long long n2 = (long long)(pbytes / sizeof(double2));
   long long nb = n2 / ((long long)BLOCK * 8);
   if (nb < 256) nb = 256;
   const long long chunk2 = (n2 + nb - 1) / nb;
   const long long nbh = (nb + 1) / 2, chunk2h = (n2 / 2 + nbh - 1) / nbh;
-  double2* xa = static_cast<double2*>(h->x);
+  double2* xa = static_cast<double2*>(h->x.get());
   // filler: the two halves of x streamed against each other (the same kernel at half the size), ~0.1 ms per GB of state
   auto filler = [&](int passes) {
     for (int r = 0; r < passes; ++r)
@@ -949,15 +1018,15 @@ void placement_leg(pic_handle* h, size_t pbytes) {
     outcome = PIC_PLACED_TIMEOUT;                                     // (the feeder's own clock check)
   if (found_at > 0) outcome = PIC_PLACED_FOUND;                       // a fast pair is in hand: no further leg for the rest of the sixteen
   (void)hipStreamSynchronize(h->stream);
-  if (e0) hipEventDestroy(e0);
-  if (e1) hipEventDestroy(e1);
+  e0.reset();                                                         // (the events go here, inside the leg's clock)
+  e1.reset();
   (void)hipGetLastError();
   std::vector<void*>& blocks = feed.blocks;
   if (!best && !blocks.empty()) best = blocks.front();                // nothing could be timed: any block will do
   const double tf = seconds();
   for (void* b : blocks)
     if (b != best) hipFree(b);
-  if (h->v && best != h->v) hipFree(h->v);                            // a later leg found a better block than the one kept
+  h->v_block.reset(best);                                             // (frees the block kept so far if a later leg found a better one)
   st.free_seconds += seconds() - tf;
   h->v = best;
   ps.best_n = best_n; ps.worst_n = worst_n;
@@ -979,17 +1048,19 @@ hipError_t alloc_particles(pic_handle* h, size_t pbytes) {
   h->place = PlacementStats{};
   h->place_state = PlacementState{};
   if (2 * pbytes < kMinBytes || h->cfg.placement == PIC_PLACE_OFF) {
-    const hipError_t e = hipMalloc(&h->x, 2 * pbytes);
-    h->v = static_cast<char*>(h->x) + pbytes;
+    const hipError_t e = alloc(h->x, 2 * pbytes);
+    h->v = static_cast<char*>(h->x.get()) + pbytes;
     return e;
   }
-  hipError_t e = hipMalloc(&h->x, pbytes);
+  hipError_t e = alloc(h->x, pbytes);
   if (e != hipSuccess) return e;
   h->v_separate = true;
   h->place_state.pbytes = pbytes;
   placement_leg(h, pbytes);
-  if (!h->v) return hipMalloc(&h->v, pbytes);                          // no candidate at all (no memory to search in): plain allocation
-  return hipSuccess;
+  if (h->v) return hipSuccess;
+  e = alloc(h->v_block, pbytes);                                       // no candidate at all (no memory to search in): plain allocation
+  h->v = h->v_block;
+  return e;
 }
 
 // A reset replaces the particles: while the search has only ended for lack of time, and nobody outside has been given the arrays'
@@ -1043,7 +1114,8 @@ int pic_create(const pic_config* cfg, pic_handle** out) {
                                          ": libpicstep.so is built for gfx950 (MI355X) only");
   }
 
-  pic_handle* h = new (std::nothrow) pic_handle();
+  std::unique_ptr<pic_handle> owner(new (std::nothrow) pic_handle());     // a return before the end frees all the handle holds
+  pic_handle* h = owner.get();
   if (!h) return fail(nullptr, PIC_ENOMEM, "pic_create: out of host memory");
   h->cfg = *cfg;
   h->fmt = cfg->particle_dtype == PIC_F64 ? FMT_F64 : (cfg->position_dtype == PIC_POS_FIXED32 ? FMT_U32 : FMT_F32);
@@ -1115,7 +1187,7 @@ int pic_create(const pic_config* cfg, pic_handle** out) {
   long long chunk = (cfg->N + nblk - 1) / nblk;
   chunk = (chunk + tile - 1) / tile * tile;
   nblk = (cfg->N + chunk - 1) / chunk;
-  if (nblk > 65535) { delete h; return fail(nullptr, PIC_EINVAL, "pic_create: blocks_per_env too large"); }
+  if (nblk > 65535) return fail(nullptr, PIC_EINVAL, "pic_create: blocks_per_env too large");
   h->chunk = chunk;
   h->nblk = (int)nblk;
   // Sub-rows of an accumulator row (pic_device.h: acc_row_sum): with few environments all workgroups of an environment flush
@@ -1151,7 +1223,6 @@ int pic_create(const pic_config* cfg, pic_handle** out) {
   h->readonly_c = h->readonly_auto;
   if (h->sweep_lds + kSweepStaticLds > kLdsLimit) {
     const long long max_ng = (long long)((kLdsLimit - kSweepStaticLds) / (2 * h->R * 8 + h->esz)) - 2;
-    delete h;
     return fail(nullptr, PIC_EINVAL, "pic_create: Ng too large for the LDS-resident mesh (at most " + std::to_string(max_ng) +
                                      " cells with this particle dtype)");
   }
@@ -1171,7 +1242,6 @@ int pic_create(const pic_config* cfg, pic_handle** out) {
     const bool possible = h->res_nw != 0 && h->res_lds + kResidentStaticLds <= kLdsLimit && h->acc_kind != PIC_ACC_F64;
     if (cfg->blocks_per_env < 0 && !possible) {
       const long long max_ng = (long long)((kLdsLimit - kResidentStaticLds - 2 * (2 * 8 + h->esz)) / (2 * 8 + h->esz + 4 * 8));
-      delete h;
       return fail(nullptr, PIC_EINVAL, "pic_create: the resident schedule needs N <= 8192, Ng <= " + std::to_string(max_ng) +
                                        " (this particle dtype) and an integer accumulator");
     }
@@ -1186,70 +1256,54 @@ int pic_create(const pic_config* cfg, pic_handle** out) {
     h->res_lean = (cfg->num_envs > ncu && h->res_ppt <= 10) || (cfg->interpol == PIC_TSC && h->res_ppt == 16);
   }
 
-#define CREATE_CHK(call)                                                                      \
-  do {                                                                                        \
-    hipError_t e_ = (call);                                                                   \
-    if (e_ != hipSuccess) {                                                                   \
-      std::string m = std::string("pic_create: " #call ": ") + hipGetErrorString(e_);         \
-      pic_destroy(h);                                                                         \
-      return fail(nullptr, e_ == hipErrorOutOfMemory ? PIC_ENOMEM : PIC_EHIP, m);            \
-    }                                                                                         \
-  } while (0)
-
-  CREATE_CHK(hipSetDevice(cfg->device_id));
-  CREATE_CHK(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
-  h->stream = h->own_stream;
+  auto failed = [](hipError_t e, const char* what) {
+    return fail(nullptr, e == hipErrorOutOfMemory ? PIC_ENOMEM : PIC_EHIP, std::string("pic_create: ") + what + ": " + hipGetErrorString(e));
+  };
+  if (hipError_t e = hipSetDevice(cfg->device_id)) return failed(e, "hipSetDevice");
+  if (hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) return failed(e, "hipStreamCreateWithFlags");
+  h->own_stream.reset(h->stream);
   const size_t pbytes = (size_t)cfg->num_envs * h->ld * h->esz;
   const size_t gbytes = (size_t)cfg->num_envs * cfg->Ng * sizeof(double);
-  CREATE_CHK(alloc_particles(h, pbytes));            // x, v: [env][ld] each
-  CREATE_CHK(hipMemsetAsync(h->x, 0, pbytes, h->stream));
-  CREATE_CHK(hipMemsetAsync(h->v, 0, pbytes, h->stream));
+  if (hipError_t e = alloc_particles(h, pbytes)) return failed(e, "allocation of the particles");     // x, v: [env][ld] each
+  if (hipError_t e = hipMemsetAsync(h->x, 0, pbytes, h->stream)) return failed(e, "hipMemsetAsync of x");
+  if (hipError_t e = hipMemsetAsync(h->v, 0, pbytes, h->stream)) return failed(e, "hipMemsetAsync of v");
   // small states (the reference's N = 5000) are read back every step by a Gym-style loop: one copy of x and v
   // together into pinned memory instead of two copies into pageable memory
   if (2 * (size_t)cfg->num_envs * cfg->N * h->esz <= ((size_t)4 << 20))
-    CREATE_CHK(hipHostMalloc(&h->h_part, 2 * (size_t)cfg->num_envs * h->ld * h->esz, hipHostMallocDefault));
-  CREATE_CHK(hipMalloc((void**)&h->ring, (size_t)(RING + 1) * h->S * gbytes));      // acc_t and double are both 8 bytes
-  CREATE_CHK(hipMemsetAsync(h->ring, 0, (size_t)(RING + 1) * h->S * gbytes, h->stream));
+    if (hipError_t e = alloc(h->h_part, 2 * (size_t)cfg->num_envs * h->ld * h->esz)) return failed(e, "pinned particle staging");
+  if (hipError_t e = alloc_zeroed(h->ring, (size_t)(RING + 1) * h->S * gbytes, h->stream))      // acc_t and double are both 8 bytes
+    return failed(e, "accumulator ring");
   h->probe_acc = ring_row(h, RING);
   for (int s = 0; s < RING; ++s) h->clean.push_back(s);
   if (h->resident) {
     const size_t qbytes = (size_t)cfg->num_envs * h->res_R * stride * sizeof(unsigned long long);
-    CREATE_CHK(hipMalloc((void**)&h->res_q1, qbytes));
-    CREATE_CHK(hipMemsetAsync(h->res_q1, 0, qbytes, h->stream));
+    if (hipError_t e = alloc_zeroed(h->res_q1, qbytes, h->stream)) return failed(e, "resident q1 meshes");
     // cells and weights of the q1 positions travel with it where a launch is latency, not traffic: a handful of environments
     // (20 bytes per particle each way: 256 environments would spend 8 us on them), kernels that carry them (pic_resident.h: kHandCarry)
     if (!h->res_lean && h->res_ppt <= 10 && h->esz == 8 && cfg->num_envs <= 32) {
       const size_t cbytes = (size_t)cfg->num_envs * h->res_nw * 64 * h->res_ppt * (sizeof(int) + (cfg->interpol == PIC_TSC ? 4 : 2) * h->esz);
-      CREATE_CHK(hipMalloc(&h->res_carry, cbytes));
-      CREATE_CHK(hipMemsetAsync(h->res_carry, 0, cbytes, h->stream));
+      if (hipError_t e = alloc_zeroed(h->res_carry, cbytes, h->stream)) return failed(e, "resident carried cells");
     }
   }
-  CREATE_CHK(hipMalloc((void**)&h->ke_part, (size_t)cfg->num_envs * h->nblk * sizeof(double)));
-  CREATE_CHK(hipMemsetAsync(h->ke_part, 0, (size_t)cfg->num_envs * h->nblk * sizeof(double), h->stream));
-  double** grids[] = {&h->n, &h->E_mesh, &h->phi, &h->ext, &h->ext2, &h->probe_ext, &h->aux_n, &h->aux_E, &h->aux_phi};
-  for (double** g : grids) {
-    CREATE_CHK(hipMalloc((void**)g, gbytes));
-    CREATE_CHK(hipMemsetAsync(*g, 0, gbytes, h->stream));
-  }
-  CREATE_CHK(hipMalloc((void**)&h->e2, (size_t)cfg->num_envs * (cfg->Ng + 2) * sizeof(double)));
+  if (hipError_t e = alloc_zeroed(h->ke_part, (size_t)cfg->num_envs * h->nblk * sizeof(double), h->stream)) return failed(e, "KE partials");
+  for (DeviceBuf<double>* g : {&h->n, &h->E_mesh, &h->phi, &h->ext, &h->ext2, &h->probe_ext, &h->aux_n, &h->aux_E, &h->aux_phi})
+    if (hipError_t e = alloc_zeroed(*g, gbytes, h->stream)) return failed(e, "meshes");
+  if (hipError_t e = alloc(h->e2, (size_t)cfg->num_envs * (cfg->Ng + 2) * sizeof(double))) return failed(e, "field tiles");
   // KE | PE | PE_reward live in one allocation so that a getter is a single small D2H copy into
   // pinned memory (a Python RL loop reads them every step)
   const size_t sbytes = (size_t)cfg->num_envs * sizeof(double);
-  CREATE_CHK(hipMalloc((void**)&h->KE, 3 * sbytes));
-  CREATE_CHK(hipMemsetAsync(h->KE, 0, 3 * sbytes, h->stream));
+  if (hipError_t e = alloc_zeroed(h->KE, 3 * sbytes, h->stream)) return failed(e, "energies");
   h->PE = h->KE + cfg->num_envs;
   h->PEr = h->KE + 2 * (size_t)cfg->num_envs;
-  CREATE_CHK(hipHostMalloc((void**)&h->h_scal, 3 * sbytes, hipHostMallocDefault));
-  if (gbytes <= ((size_t)256 << 10)) CREATE_CHK(hipHostMalloc((void**)&h->h_fields, 3 * gbytes, hipHostMallocDefault));
-  CREATE_CHK(hipHostMalloc((void**)&h->h_probe_pe, sbytes, hipHostMallocDefault));
-  CREATE_CHK(hipMalloc((void**)&h->aux_pe, sbytes));
-  CREATE_CHK(hipMemsetAsync(h->aux_pe, 0, sbytes, h->stream));
-  CREATE_CHK(hipMalloc((void**)&h->bad, 2 * sizeof(unsigned long long)));
-  CREATE_CHK(hipMemsetAsync(h->bad, 0, 2 * sizeof(unsigned long long), h->stream));
+  if (hipError_t e = alloc(h->h_scal, 3 * sbytes)) return failed(e, "pinned energy staging");
+  if (gbytes <= ((size_t)256 << 10))
+    if (hipError_t e = alloc(h->h_fields, 3 * gbytes)) return failed(e, "pinned mesh staging");
+  if (hipError_t e = alloc(h->h_probe_pe, sbytes)) return failed(e, "pinned probe energy");
+  if (hipError_t e = alloc_zeroed(h->aux_pe, sbytes, h->stream)) return failed(e, "probe energies");
+  if (hipError_t e = alloc_zeroed(h->bad, 2 * sizeof(unsigned long long), h->stream)) return failed(e, "counters");
   h->probe_bad = h->bad + 1;
-  CREATE_CHK(hipStreamSynchronize(h->stream));
-#undef CREATE_CHK
-  *out = h;
+  if (hipError_t e = hipStreamSynchronize(h->stream)) return failed(e, "hipStreamSynchronize");
+  *out = owner.release();
   return PIC_OK;
 }
 
@@ -1258,19 +1312,6 @@ int pic_destroy(pic_handle* h) {
   hipSetDevice(h->cfg.device_id);
   if (h->stream) hipStreamSynchronize(h->stream);
   prof_drain(h);
-  for (hipEvent_t e : h->ev) hipEventDestroy(e);
-  void* bufs[] = {h->rec.d, h->rec.u, h->rec.phase, h->rec.feq, h->x, h->scratch, h->stage, h->ring, h->ke_part, h->n, h->E_mesh, h->phi, h->ext, h->ext2, h->probe_ext,
-                  h->e2, h->basis, h->act, h->modes, h->aux_n, h->aux_E, h->aux_pe, h->aux_phi, h->KE, h->bad, h->tw, h->traj, h->res_q1, h->res_carry, h->tape.block,
-                  h->gain, h->fb_modes, h->tape.law_block};
-  for (double* g : h->tape.gains) hipFree(g);
-  for (void* b : bufs)
-    if (b) hipFree(b);
-  if (h->v_separate && h->v) hipFree(h->v);
-  if (h->h_scal) hipHostFree(h->h_scal);
-  if (h->h_part) hipHostFree(h->h_part);
-  if (h->h_fields) hipHostFree(h->h_fields);
-  if (h->h_probe_pe) hipHostFree(h->h_probe_pe);
-  if (h->own_stream) hipStreamDestroy(h->own_stream);
   delete h;
   return PIC_OK;
 }
@@ -1441,14 +1482,12 @@ static void run_stages(pic_handle* h, int from, int upto, const Control& ctl, bo
 }
 
 // host -> device staging of a call's inputs.  Small per-step inputs have buffers of their own (h->ext, h->act); whole
-// trajectories go through h->traj, grown on demand (growing drains the stream first).
+// trajectories go through h->traj, grown on demand.
 static int ensure_traj(pic_handle* h, size_t bytes) {
   if (bytes <= h->traj_bytes) return PIC_OK;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (h->traj) { hipFree(h->traj); h->traj = nullptr; h->traj_bytes = 0; }
-  if (hipMalloc(&h->traj, bytes) != hipSuccess) return fail(h, PIC_ENOMEM, "trajectory staging buffer");
-  h->traj_bytes = bytes;
-  return PIC_OK;
+  const int rc = regrow(h, h->traj, bytes, "trajectory staging buffer");
+  h->traj_bytes = rc ? 0 : bytes;
+  return rc;
 }
 
 static int stage_ext(pic_handle* h, const double* E_ext, int mem_kind, const double** ext) {
@@ -1465,9 +1504,9 @@ static int stage_ext(pic_handle* h, const double* E_ext, int mem_kind, const dou
 
 static int ensure_twiddle(pic_handle* h, int rows) {
   if (rows <= h->tw_rows) return PIC_OK;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (h->tw) { hipFree(h->tw); h->tw = nullptr; h->tw_rows = 0; }
-  HIPCHK(h, hipMalloc((void**)&h->tw, (size_t)2 * rows * h->cfg.Ng * sizeof(double)));
+  h->tw_rows = 0;
+  const int rc = regrow(h, h->tw, (size_t)2 * rows * h->cfg.Ng * sizeof(double), "twiddle table");
+  if (rc) return rc;
   hipLaunchKernelGGL(twiddle_kernel, dim3((h->cfg.Ng + BLOCK - 1) / BLOCK, rows), dim3(BLOCK), 0, h->stream, h->tw, h->cfg.Ng, rows);
   HIPCHK(h, hipGetLastError());
   h->tw_rows = rows;
@@ -1604,7 +1643,7 @@ static int record_enqueue(pic_handle* h) {
   const dim3 grid(r.gx, E);
   with_format(h, [&](auto p) {
     using P = decltype(p);
-    hipLaunchKernelGGL(record_hist_kernel<P>, grid, dim3(BLOCK), r.lds, h->stream, (const typename P::X*)h->x,
+    hipLaunchKernelGGL(record_hist_kernel<P>, grid, dim3(BLOCK), r.lds, h->stream, (const typename P::X*)h->x.get(),
                        (const typename P::V*)h->v, ha);
   });
   RecordFinishArgs fa{};
@@ -1784,18 +1823,13 @@ static int step_recording(pic_handle* h, StepControl sc, int nsteps, double* his
   const size_t hbytes = (size_t)nsteps * 3 * E * sizeof(double);
   const size_t sbytes = (size_t)nsteps * 2 * E * (size_t)h->cfg.N * h->esz;
   const size_t abytes = (size_t)nsteps * E * 2 * sc.fb.M * sizeof(double);
-  double* dh = nullptr;
-  double* da = nullptr;
-  double* dm = nullptr;
-  void* ds = nullptr;
-  auto release = [&]() { if (dh) hipFree(dh); if (da) hipFree(da); if (dm) hipFree(dm); if (ds) hipFree(ds); };
-  if (hist && hipMalloc((void**)&dh, hbytes) != hipSuccess) return fail(h, PIC_ENOMEM, std::string(who) + ": history buffer");
-  if (act_out && sc.fb.M > 0 && hipMalloc((void**)&da, abytes) != hipSuccess) { release(); return fail(h, PIC_ENOMEM, std::string(who) + ": action record"); }
-  if (modes_out && sc.fb.gain && hipMalloc((void**)&dm, abytes) != hipSuccess) { release(); return fail(h, PIC_ENOMEM, std::string(who) + ": mode record"); }
-  if (snap && hipMalloc(&ds, sbytes) != hipSuccess) {
-    release();
+  DeviceBuf<double> dh, da, dm;      // (freed at the return, behind the wait for the read-backs)
+  DeviceBuf<void> ds;
+  if (hist && alloc(dh, hbytes) != hipSuccess) return fail(h, PIC_ENOMEM, std::string(who) + ": history buffer");
+  if (act_out && sc.fb.M > 0 && alloc(da, abytes) != hipSuccess) return fail(h, PIC_ENOMEM, std::string(who) + ": action record");
+  if (modes_out && sc.fb.gain && alloc(dm, abytes) != hipSuccess) return fail(h, PIC_ENOMEM, std::string(who) + ": mode record");
+  if (snap && alloc(ds, sbytes) != hipSuccess)
     return fail(h, PIC_ENOMEM, std::string(who) + ": the snapshots of all steps do not fit on the device; record fewer steps per call");
-  }
   if (da || !sc.fb.act_hist) sc.fb.act_hist = da;      // (pic_step_feedback_gain under a tape: the tape's rows)
   if (dm) sc.fb.modes_hist = dm;
   int rc = PIC_OK;
@@ -1809,8 +1843,8 @@ static int step_recording(pic_handle* h, StepControl sc, int nsteps, double* his
       if (rc != PIC_OK) break;
       with_format(h, [&](auto p) {
         using P = decltype(p);
-        hipLaunchKernelGGL(record_particles_kernel<P>, grid, dim3(BLOCK), 0, h->stream, (const typename P::X*)h->x,
-                           (const typename P::V*)h->v, (typename P::V*)ds, s, h->cfg.N, h->ld, h->cfg.L);
+        hipLaunchKernelGGL(record_particles_kernel<P>, grid, dim3(BLOCK), 0, h->stream, (const typename P::X*)h->x.get(),
+                           (const typename P::V*)h->v, (typename P::V*)ds.get(), s, h->cfg.N, h->ld, h->cfg.L);
       });
     }
   }
@@ -1825,7 +1859,6 @@ static int step_recording(pic_handle* h, StepControl sc, int nsteps, double* his
   if (rc == PIC_OK && e == hipSuccess && dm) e = hipMemcpyAsync(modes_out, dm, abytes, hipMemcpyDeviceToHost, h->stream);
   if (rc == PIC_OK && e == hipSuccess && ds) e = hipMemcpyAsync(snap, ds, sbytes, hipMemcpyDeviceToHost, h->stream);
   hipError_t e2 = hipStreamSynchronize(h->stream);
-  release();
   if (rc != PIC_OK) return rc;
   if (e != hipSuccess || e2 != hipSuccess)
     return fail(h, PIC_EHIP, std::string(who) + ": " + hipGetErrorString(e != hipSuccess ? e : e2));
@@ -1859,7 +1892,7 @@ static int stage_traj(pic_handle* h, const double* src, int mem_kind, size_t row
   int rc = ensure_traj(h, bytes);
   if (rc) return rc;
   HIPCHK(h, hipMemcpyAsync(h->traj, src, bytes, hipMemcpyHostToDevice, h->stream));
-  *dev = static_cast<const double*>(h->traj);
+  *dev = static_cast<const double*>(h->traj.get());
   return PIC_OK;
 }
 
@@ -1883,8 +1916,7 @@ constexpr size_t kTinyState = (size_t)512 << 10;
 static bool ensure_part_staging(pic_handle* h) {
   const size_t total = 2 * (size_t)h->cfg.num_envs * h->ld * h->esz;      // rows as they lie on the device (padded to ld)
   if (!h->h_part && !h->h_part_refused && total <= ((size_t)64 << 20)) {
-    if (hipHostMalloc(&h->h_part, total, hipHostMallocDefault) != hipSuccess) {
-      h->h_part = nullptr;
+    if (alloc(h->h_part, total) != hipSuccess) {
       h->h_part_refused = true;
       (void)hipGetLastError();
     }
@@ -1904,19 +1936,19 @@ static int enqueue_observe(pic_handle* h, bool scalars, size_t* pitch) {
       HIPCHK(h, hipMemcpyAsync(h->h_part, h->x, 2 * block, hipMemcpyDeviceToHost, h->stream));
     } else {
       HIPCHK(h, hipMemcpyAsync(h->h_part, h->x, block, hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(h, hipMemcpyAsync(static_cast<char*>(h->h_part) + block, h->v, block, hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipMemcpyAsync(static_cast<char*>(h->h_part.get()) + block, h->v, block, hipMemcpyDeviceToHost, h->stream));
     }
     if (scalars) HIPCHK(h, hipMemcpyAsync(h->h_scal, h->KE, 3 * (size_t)E * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     return PIC_OK;
   }
   dim3 grid((unsigned)std::min<long long>((h->cfg.N + BLOCK - 1) / BLOCK, 64), 2 * E);
   if (h->esz == 8)
-    hipLaunchKernelGGL(observe_kernel<double>, grid, dim3(BLOCK), 0, h->stream, static_cast<const double*>(h->x),
-                       static_cast<const double*>(h->v), (long long)h->cfg.N, (long long)h->ld, E, static_cast<double*>(h->h_part),
+    hipLaunchKernelGGL(observe_kernel<double>, grid, dim3(BLOCK), 0, h->stream, static_cast<const double*>(h->x.get()),
+                       static_cast<const double*>(h->v), (long long)h->cfg.N, (long long)h->ld, E, static_cast<double*>(h->h_part.get()),
                        h->KE, scalars ? h->h_scal : nullptr);
   else
-    hipLaunchKernelGGL(observe_kernel<float>, grid, dim3(BLOCK), 0, h->stream, static_cast<const float*>(h->x),
-                       static_cast<const float*>(h->v), (long long)h->cfg.N, (long long)h->ld, E, static_cast<float*>(h->h_part),
+    hipLaunchKernelGGL(observe_kernel<float>, grid, dim3(BLOCK), 0, h->stream, static_cast<const float*>(h->x.get()),
+                       static_cast<const float*>(h->v), (long long)h->cfg.N, (long long)h->ld, E, static_cast<float*>(h->h_part.get()),
                        h->KE, scalars ? h->h_scal : nullptr);
   HIPCHK(h, hipGetLastError());
   return PIC_OK;
@@ -1924,7 +1956,7 @@ static int enqueue_observe(pic_handle* h, bool scalars, size_t* pitch) {
 // staging -> the caller's [num_envs][N] arrays
 static void unpack_part(pic_handle* h, void* x, void* v, size_t pitch) {
   const size_t E = (size_t)h->cfg.num_envs, row = (size_t)h->cfg.N * h->esz;
-  const char* sx = static_cast<const char*>(h->h_part);
+  const char* sx = static_cast<const char*>(h->h_part.get());
   const char* sv = sx + E * pitch;
   if (pitch == row) {
     if (x) std::memcpy(x, sx, E * row);
@@ -2025,8 +2057,7 @@ int pic_get_energies(pic_handle* h, double* KE, double* PE, double* PE_reward) {
 static int ensure_scratch(pic_handle* h) {
   if (h->scratch) return PIC_OK;
   const size_t pbytes = (size_t)h->cfg.num_envs * h->ld * h->esz;
-  HIPCHK(h, hipMalloc(&h->scratch, pbytes));
-  HIPCHK(h, hipMemsetAsync(h->scratch, 0, pbytes, h->stream));
+  HIPCHK(h, alloc_zeroed(h->scratch, pbytes, h->stream));
   return PIC_OK;
 }
 
@@ -2054,11 +2085,11 @@ int pic_get_cic(pic_handle* h, int env, int64_t* indx_l, int64_t* indx_r, double
   if (!h->has_state) return fail(h, PIC_ESTATE, "pic_get_cic: call pic_reset first");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   const long long N = h->cfg.N;
-  long long* dj = nullptr;
-  double* dw = nullptr;
-  HIPCHK(h, hipMalloc((void**)&dj, 3 * N * sizeof(long long)));
-  if (hipMalloc((void**)&dw, 3 * N * sizeof(double)) != hipSuccess) { hipFree(dj); return fail(h, PIC_ENOMEM, "pic_get_cic: hipMalloc"); }
-  const char* xe = (const char*)h->x + (size_t)env * h->ld * h->esz;
+  DeviceBuf<long long> dj;
+  DeviceBuf<double> dw;
+  HIPCHK(h, alloc(dj, 3 * N * sizeof(long long)));
+  if (alloc(dw, 3 * N * sizeof(double)) != hipSuccess) return fail(h, PIC_ENOMEM, "pic_get_cic: hipMalloc");
+  const char* xe = (const char*)h->x.get() + (size_t)env * h->ld * h->esz;
   launch_shape_query(h, xe, 1, PIC_CIC, dj, dw);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess && indx_l) e = hipMemcpyAsync(indx_l, dj, N * sizeof(long long), hipMemcpyDeviceToHost, h->stream);
@@ -2066,8 +2097,6 @@ int pic_get_cic(pic_handle* h, int env, int64_t* indx_l, int64_t* indx_r, double
   if (e == hipSuccess && weight_l) e = hipMemcpyAsync(weight_l, dw, N * sizeof(double), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess && weight_r) e = hipMemcpyAsync(weight_r, dw + N, N * sizeof(double), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  hipFree(dj);
-  hipFree(dw);
   if (e != hipSuccess) return fail(h, PIC_EHIP, std::string("pic_get_cic: ") + hipGetErrorString(e));
   return PIC_OK;
 }
@@ -2110,7 +2139,7 @@ int pic_eval_field(pic_handle* h, const void* x, int mem_kind, const double* E_e
     const size_t pitch = (size_t)h->ld * h->esz;
     HIPCHK(h, hipStreamSynchronize(h->stream));          // (the staging buffer may still be the target of an earlier read-back)
     for (size_t e = 0; e < E; ++e) {
-      char* dst = static_cast<char*>(h->h_part) + e * pitch;
+      char* dst = static_cast<char*>(h->h_part.get()) + e * pitch;
       std::memcpy(dst, static_cast<const char*>(x) + e * row, row);
       std::memset(dst + row, 0, pitch - row);
     }
@@ -2154,12 +2183,12 @@ int pic_compute_E(pic_handle* h, const void* x, int mem_kind, const double* E_ex
   if (phi_mesh) HIPCHK(h, hipMemcpyAsync(phi_mesh, h->aux_phi, gbytes, hipMemcpyDeviceToHost, h->stream));
 
   // gathers at the particles and shape bookkeeping go through one temporary, sized for the larger of the two
-  void* tmp = nullptr;
+  DeviceBuf<void> tmp;
   const size_t part_bytes = (size_t)E_ * N * h->esz;
   const size_t shape_bytes = (size_t)E_ * 3 * N * 8;
   const bool want_shape = idx || w;
   if (E_part || phi_part || want_shape) {
-    if (hipMalloc(&tmp, want_shape ? 2 * shape_bytes : part_bytes) != hipSuccess)
+    if (alloc(tmp, want_shape ? 2 * shape_bytes : part_bytes) != hipSuccess)
       return fail(h, PIC_ENOMEM, "pic_compute_E: hipMalloc of the gather buffer");
   }
   hipError_t e = hipSuccess;
@@ -2173,15 +2202,14 @@ int pic_compute_E(pic_handle* h, const void* x, int mem_kind, const double* E_ex
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);      // tmp is reused
   }
   if (want_shape && e == hipSuccess) {
-    long long* dj = static_cast<long long*>(tmp);
-    double* dw = reinterpret_cast<double*>(static_cast<char*>(tmp) + shape_bytes);
+    long long* dj = static_cast<long long*>(tmp.get());
+    double* dw = reinterpret_cast<double*>(static_cast<char*>(tmp.get()) + shape_bytes);
     launch_shape_query(h, h->scratch, E_, h->cfg.interpol, dj, dw);
     e = hipGetLastError();
     if (e == hipSuccess && idx) e = hipMemcpyAsync(idx, dj, shape_bytes, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess && w) e = hipMemcpyAsync(w, dw, shape_bytes, hipMemcpyDeviceToHost, h->stream);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (tmp) hipFree(tmp);
   if (e != hipSuccess) return fail(h, PIC_EHIP, std::string("pic_compute_E: ") + hipGetErrorString(e));
   return PIC_OK;
 }
@@ -2206,14 +2234,13 @@ int pic_set_actuator(pic_handle* h, int max_mode, const double* basis_cos, const
     return fail(h, PIC_EINVAL, "pic_set_actuator: need 1 <= max_mode <= 64 and both basis tables");
   if (h->tape.on) return fail(h, PIC_ESTATE, "pic_set_actuator: refused while a tape is open (pic_tape_stop first)");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (h->basis) { hipFree(h->basis); h->basis = nullptr; }
-  if (h->act) { hipFree(h->act); h->act = nullptr; }
+  h->act_modes = 0;                      // (until both tables are in place)
   const size_t tb = (size_t)h->cfg.Ng * max_mode * sizeof(double);
-  HIPCHK(h, hipMalloc((void**)&h->basis, 2 * tb));
-  HIPCHK(h, hipMalloc((void**)&h->act, (size_t)h->cfg.num_envs * 2 * max_mode * sizeof(double)));
+  int rc = regrow(h, h->basis, 2 * tb, "pic_set_actuator: the basis tables do not fit on the device");
+  if (!rc) rc = regrow(h, h->act, (size_t)h->cfg.num_envs * 2 * max_mode * sizeof(double), "pic_set_actuator: the actions do not fit on the device");
+  if (rc) return rc;
   HIPCHK(h, hipMemcpyAsync(h->basis, basis_cos, tb, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync((char*)h->basis + tb, basis_sin, tb, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync((char*)h->basis.get() + tb, basis_sin, tb, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->act_modes = max_mode;
   return PIC_OK;
@@ -2338,23 +2365,22 @@ static int tape_law_reserve(pic_handle* h, size_t gbytes) {
   if (t.budget > 0 && t.bytes + lbytes + gbytes > (size_t)t.budget)
     return fail(h, PIC_ENOMEM, std::string(who) + ": the law's record and this call's gain would take the tape past budget_bytes (pic_tape_start)");
   if (!t.law_block) {
-    if (hipMalloc(&t.law_block, lbytes) != hipSuccess) {
+    if (alloc(t.law_block, lbytes) != hipSuccess) {
       (void)hipGetLastError();
-      t.law_block = nullptr;
       return fail(h, PIC_ENOMEM, std::string(who) + ": the tape's record of the law's steps does not fit on the device");
     }
-    char* b = static_cast<char*>(t.law_block);
+    char* b = static_cast<char*>(t.law_block.get());
     t.lact = (double*)b; t.lmodes = (double*)(b + rows); t.lcot = (double*)(b + 2 * rows); t.lE = (double*)(b + 3 * rows);
     HIPCHK(h, hipMemsetAsync(t.lmodes, 0, rows, h->stream));
     t.law.assign((size_t)t.max_steps, -1);
     t.bytes += lbytes;
   }
-  double* g = nullptr;
-  if (hipMalloc((void**)&g, gbytes) != hipSuccess) {
+  DeviceBuf<double> g;
+  if (alloc(g, gbytes) != hipSuccess) {
     (void)hipGetLastError();
     return fail(h, PIC_ENOMEM, std::string(who) + ": the tape's copy of the gain does not fit on the device");
   }
-  t.gains.push_back(g);
+  t.gains.push_back(std::move(g));
   t.bytes += gbytes;
   return PIC_OK;
 }
@@ -2369,7 +2395,7 @@ int pic_step_feedback_gain(pic_handle* h, int max_mode, const double* gain, int 
   if (rc || nsteps == 0) return rc;
   const int E = h->cfg.num_envs, n = 2 * max_mode;
   const size_t gbytes = (size_t)E * n * n * sizeof(double);
-  if (!h->fb_modes) HIPCHK(h, hipMalloc((void**)&h->fb_modes, (size_t)E * 2 * kMaxFeedbackModes * sizeof(double)));
+  if (!h->fb_modes) HIPCHK(h, alloc(h->fb_modes, (size_t)E * 2 * kMaxFeedbackModes * sizeof(double)));
   const hipMemcpyKind in = mem_kind == PIC_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
   Tape& t = h->tape;
   const double* g = gain;
@@ -2379,7 +2405,7 @@ int pic_step_feedback_gain(pic_handle* h, int max_mode, const double* gain, int 
     HIPCHK(h, hipMemcpyAsync(t.gains.back(), gain, gbytes, in, h->stream));
     g = t.gains.back();
   } else if (mem_kind == PIC_HOST) {
-    if (!h->gain) HIPCHK(h, hipMalloc((void**)&h->gain, (size_t)E * 4 * kMaxFeedbackModes * kMaxFeedbackModes * sizeof(double)));
+    if (!h->gain) HIPCHK(h, alloc(h->gain, (size_t)E * 4 * kMaxFeedbackModes * kMaxFeedbackModes * sizeof(double)));
     HIPCHK(h, hipMemcpyAsync(h->gain, gain, gbytes, in, h->stream));
     g = h->gain;
   }
@@ -2405,13 +2431,14 @@ int pic_get_modes(pic_handle* h, int max_mode, double* re, double* im, int mem_k
   if (!h->has_state) return fail(h, PIC_ESTATE, "pic_get_modes: call pic_reset first");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   const size_t nb = (size_t)h->cfg.num_envs * max_mode * sizeof(double);
+  int rc = PIC_OK;
   if (max_mode > h->modes_cap) {          // (re)allocate only when a larger mode count is asked for
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->modes) { hipFree(h->modes); h->modes = nullptr; }
-    HIPCHK(h, hipMalloc((void**)&h->modes, 2 * nb));
+    h->modes_cap = 0;
+    rc = regrow(h, h->modes, 2 * nb, "pic_get_modes: the modes do not fit on the device");
+    if (rc) return rc;
     h->modes_cap = max_mode;
   }
-  int rc = ensure_twiddle(h, max_mode);
+  rc = ensure_twiddle(h, max_mode);
   if (rc) return rc;
   double* dre = h->modes;
   double* dim_ = h->modes + (size_t)h->cfg.num_envs * max_mode;
@@ -2440,7 +2467,7 @@ int pic_reset_sampled(pic_handle* h, int kind, double a, double v0, double sigma
   const dim3 grid = aux_grid(h, h->cfg.num_envs, 2048);
   with_format(h, [&](auto p) {
     using P = decltype(p);
-    hipLaunchKernelGGL(sample_kernel<P>, grid, dim3(BLOCK), 0, h->stream, (typename P::X*)h->x, (typename P::V*)h->v, h->cfg.N,
+    hipLaunchKernelGGL(sample_kernel<P>, grid, dim3(BLOCK), 0, h->stream, (typename P::X*)h->x.get(), (typename P::V*)h->v, h->cfg.N,
                        h->ld, kind, a, v0, sigma, A, n_mode, h->cfg.L, (unsigned long long)seed, h->cfg.env_index_base);
   });
   HIPCHK(h, hipGetLastError());
@@ -2449,25 +2476,20 @@ int pic_reset_sampled(pic_handle* h, int kind, double a, double v0, double sigma
   return refresh_fields(h);      // a reset abandons an open staged step and any cached deposit
 }
 
-// counts[num_envs][nbins][nbins] of the current particles into a fresh device buffer (caller frees it)
-static hipError_t phase_counts(pic_handle* h, int nbins, double vmin, double vmax, unsigned** out) {
+// counts[num_envs][nbins][nbins] of the current particles into a fresh device buffer d
+static hipError_t phase_counts(pic_handle* h, int nbins, double vmin, double vmax, DeviceBuf<unsigned>& d) {
   const size_t nb = (size_t)h->cfg.num_envs * nbins * nbins * sizeof(unsigned);
-  unsigned* d = nullptr;
-  hipError_t e = hipMalloc((void**)&d, nb);
-  if (e != hipSuccess) return e;
-  e = hipMemsetAsync(d, 0, nb, h->stream);
+  hipError_t e = alloc_zeroed(d, nb, h->stream);
   const dim3 grid = aux_grid(h, h->cfg.num_envs, 2048);
   if (e == hipSuccess) {
     with_format(h, [&](auto p) {
       using P = decltype(p);
-      hipLaunchKernelGGL(phase_hist_kernel<P>, grid, dim3(BLOCK), 0, h->stream, (const typename P::X*)h->x,
+      hipLaunchKernelGGL(phase_hist_kernel<P>, grid, dim3(BLOCK), 0, h->stream, (const typename P::X*)h->x.get(),
                          (const typename P::V*)h->v, d, h->cfg.N, h->ld, nbins, h->cfg.L, vmin, vmax);
     });
     e = hipGetLastError();
   }
-  if (e != hipSuccess) { hipFree(d); return e; }
-  *out = d;
-  return hipSuccess;
+  return e;
 }
 
 int pic_phase_histogram(pic_handle* h, int nbins, double vmin, double vmax, uint32_t* counts) {
@@ -2476,11 +2498,10 @@ int pic_phase_histogram(pic_handle* h, int nbins, double vmin, double vmax, uint
   if (!h->has_state) return fail(h, PIC_ESTATE, "pic_phase_histogram: call pic_reset first");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   const size_t nb = (size_t)h->cfg.num_envs * nbins * nbins * sizeof(unsigned);
-  unsigned* d = nullptr;
-  hipError_t e = phase_counts(h, nbins, vmin, vmax, &d);
+  DeviceBuf<unsigned> d;
+  hipError_t e = phase_counts(h, nbins, vmin, vmax, d);
   if (e == hipSuccess) e = hipMemcpyAsync(counts, d, nb, hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (d) hipFree(d);
   if (e != hipSuccess) return fail(h, PIC_EHIP, std::string("pic_phase_histogram: ") + hipGetErrorString(e));
   return PIC_OK;
 }
@@ -2491,10 +2512,10 @@ int pic_phase_kl(pic_handle* h, int nbins, double vmin, double vmax, const doubl
   if (!h->has_state) return fail(h, PIC_ESTATE, "pic_phase_kl: call pic_reset first");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   const int E = h->cfg.num_envs, nb2 = nbins * nbins;
-  unsigned* d = nullptr;
-  double* df = nullptr;
-  hipError_t e = phase_counts(h, nbins, vmin, vmax, &d);
-  if (e == hipSuccess) e = hipMalloc((void**)&df, ((size_t)nb2 + E) * sizeof(double));
+  DeviceBuf<unsigned> d;
+  DeviceBuf<double> df;
+  hipError_t e = phase_counts(h, nbins, vmin, vmax, d);
+  if (e == hipSuccess) e = alloc(df, ((size_t)nb2 + E) * sizeof(double));
   if (e == hipSuccess) e = hipMemcpyAsync(df, feq, (size_t)nb2 * sizeof(double), hipMemcpyHostToDevice, h->stream);
   if (e == hipSuccess) {
     const double dx = h->cfg.L / nbins, dv = (vmax - vmin) / nbins;
@@ -2504,8 +2525,6 @@ int pic_phase_kl(pic_handle* h, int nbins, double vmin, double vmax, const doubl
   }
   if (e == hipSuccess) e = hipMemcpyAsync(kl, df + nb2, (size_t)E * sizeof(double), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (d) hipFree(d);
-  if (df) hipFree(df);
   if (e != hipSuccess) return fail(h, PIC_EHIP, std::string("pic_phase_kl: ") + hipGetErrorString(e));
   return PIC_OK;
 }
@@ -2513,13 +2532,6 @@ int pic_phase_kl(pic_handle* h, int nbins, double vmin, double vmax, const doubl
 // ---------------------------------------------------------------------------------------------
 // Rollout recorder (include/picstep.h: pic_record_*; hooks: advance, pic_step_stage)
 // ---------------------------------------------------------------------------------------------
-static void record_free(pic_handle* h) {
-  Recorder& r = h->rec;
-  for (void* b : {(void*)r.d, (void*)r.u, (void*)r.phase, (void*)r.feq})
-    if (b) hipFree(b);
-  r = Recorder{};
-}
-
 int pic_record_start(pic_handle* h, const pic_record_config* c) {
   if (!h || !c) return fail(h, PIC_EINVAL, "pic_record_start: null argument");
   if (h->rec.on) return fail(h, PIC_ESTATE, "pic_record_start: already recording (pic_record_stop first)");
@@ -2547,42 +2559,37 @@ int pic_record_start(pic_handle* h, const pic_record_config* c) {
   const size_t dbytes = (size_t)r.cap * E * r.d_stride * sizeof(double), ubytes = (size_t)r.cap * E * r.u_stride * sizeof(unsigned);
   if ((size_t)r.cap > ((size_t)1 << 40) / ((size_t)E * (r.d_stride * 8 + r.u_stride * 4)))
     return fail(h, PIC_ENOMEM, "pic_record_start: capacity does not fit on the device");
-  bool ok = hipMalloc((void**)&r.d, dbytes) == hipSuccess && hipMalloc((void**)&r.u, ubytes) == hipSuccess &&
-            (!nb2 || hipMalloc((void**)&r.phase, (size_t)E * nb2 * sizeof(unsigned)) == hipSuccess) &&
-            (!c->feq || hipMalloc((void**)&r.feq, nb2 * sizeof(double)) == hipSuccess);
+  bool ok = alloc(r.d, dbytes) == hipSuccess && alloc(r.u, ubytes) == hipSuccess &&
+            (!nb2 || alloc(r.phase, (size_t)E * nb2 * sizeof(unsigned)) == hipSuccess) &&
+            (!c->feq || alloc(r.feq, nb2 * sizeof(double)) == hipSuccess);
   if (!ok) {
     hipGetLastError();
-    h->rec = r;
-    record_free(h);
     return fail(h, PIC_ENOMEM, "pic_record_start: capacity does not fit on the device");
   }
   hipError_t e = hipMemsetAsync(r.u, 0, ubytes, h->stream);
   if (e == hipSuccess && nb2) e = hipMemsetAsync(r.phase, 0, (size_t)E * nb2 * sizeof(unsigned), h->stream);
   if (e == hipSuccess && c->feq) e = hipMemcpyAsync(r.feq, c->feq, nb2 * sizeof(double), hipMemcpyHostToDevice, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  h->rec = r;
-  if (e != hipSuccess) {
-    record_free(h);
-    return fail(h, PIC_EHIP, std::string("pic_record_start: ") + hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return fail(h, PIC_EHIP, std::string("pic_record_start: ") + hipGetErrorString(e));
   if (r.M > 1) {
     const int rc = ensure_twiddle(h, r.M - 1);
-    if (rc) { record_free(h); return rc; }
+    if (rc) return rc;
   }
   // particle pass geometry: about 1024 workgroups in all, each over a contiguous range of 16-byte tiles
   const long long vec = h->vec;
   const long long cols = ((h->cfg.N + vec - 1) / vec + BLOCK - 1) / BLOCK;     // tiles per lane if one workgroup took it all
   long long gx = std::max(1LL, std::min(cols, (1024LL + E - 1) / E));
-  h->rec.tiles_per_wg = (cols + gx - 1) / gx;
-  h->rec.gx = (int)((cols + h->rec.tiles_per_wg - 1) / h->rec.tiles_per_wg);
+  r.tiles_per_wg = (cols + gx - 1) / gx;
+  r.gx = (int)((cols + r.tiles_per_wg - 1) / r.tiles_per_wg);
   // (pic_record.h: rr copies of each marginal bin within 32 KiB, phase rows of pv + 1 words)
   int rr = 16;
   while (rr > 1 && (size_t)rr * (r.xb + r.vb) * sizeof(unsigned) > ((size_t)32 << 10)) rr /= 2;
-  h->rec.rr = rr;
+  r.rr = rr;
   const size_t marg = ((size_t)rr * (r.xb + r.vb) + 1) * sizeof(unsigned), prow = (size_t)r.px * (r.pv + 1) * sizeof(unsigned);
-  h->rec.phase_lds = marg + prow <= (size_t)kRecordLdsBytes ? 1 : 0;
-  h->rec.lds = marg + (h->rec.phase_lds ? prow : 0);
-  h->rec.on = true;
+  r.phase_lds = marg + prow <= (size_t)kRecordLdsBytes ? 1 : 0;
+  r.lds = marg + (r.phase_lds ? prow : 0);
+  r.on = true;
+  h->rec = std::move(r);
   return PIC_OK;
 }
 
@@ -2640,7 +2647,7 @@ int pic_record_stop(pic_handle* h) {
   if (!h->rec.on) return PIC_OK;
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   const hipError_t e = hipStreamSynchronize(h->stream);
-  record_free(h);
+  h->rec = Recorder{};
   if (e != hipSuccess) return fail(h, PIC_EHIP, std::string("pic_record_stop: ") + hipGetErrorString(e));
   return PIC_OK;
 }
@@ -2649,30 +2656,24 @@ int pic_stream_probe(pic_handle* h, int repeats, double* gbytes_per_s) {
   if (!h || !gbytes_per_s || repeats < 1) return fail(h, PIC_EINVAL, "pic_stream_probe: bad argument");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   const size_t pbytes = (size_t)h->cfg.num_envs * h->ld * h->esz;
-  void *a = nullptr, *b = nullptr;
-  HIPCHK(h, hipMalloc(&a, pbytes));
-  if (hipMalloc(&b, pbytes) != hipSuccess) { hipFree(a); return fail(h, PIC_ENOMEM, "pic_stream_probe: hipMalloc"); }
+  DeviceBuf<double2> a, b;
+  HIPCHK(h, alloc(a, pbytes));
+  if (alloc(b, pbytes) != hipSuccess) return fail(h, PIC_ENOMEM, "pic_stream_probe: hipMalloc");
   hipMemsetAsync(a, 0, pbytes, h->stream);
   hipMemsetAsync(b, 0, pbytes, h->stream);
   const long long n2 = (long long)(pbytes / sizeof(double2));
   long long nb = n2 / ((long long)BLOCK * 31);       // ~31 tiles per lane, like a sweep workgroup
   if (nb < 256) nb = 256;
   const long long chunk2 = (n2 + nb - 1) / nb;
-  hipEvent_t e0, e1;
-  hipEventCreate(&e0);
-  hipEventCreate(&e1);
-  hipLaunchKernelGGL(stream_probe_kernel, dim3((unsigned)nb), dim3(BLOCK), 0, h->stream, (double2*)a, (double2*)b, n2, chunk2, 1.0, 1);
+  EventOwner e0 = make_event(), e1 = make_event();
+  hipLaunchKernelGGL(stream_probe_kernel, dim3((unsigned)nb), dim3(BLOCK), 0, h->stream, a.get(), b.get(), n2, chunk2, 1.0, 1);
   hipEventRecord(e0, h->stream);
   for (int r = 0; r < repeats; ++r)
-    hipLaunchKernelGGL(stream_probe_kernel, dim3((unsigned)nb), dim3(BLOCK), 0, h->stream, (double2*)a, (double2*)b, n2, chunk2, 1.0, r & 1);
+    hipLaunchKernelGGL(stream_probe_kernel, dim3((unsigned)nb), dim3(BLOCK), 0, h->stream, a.get(), b.get(), n2, chunk2, 1.0, r & 1);
   hipEventRecord(e1, h->stream);
   hipError_t e = hipEventSynchronize(e1);
   float ms = 0.f;
   if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
-  hipFree(a);
-  hipFree(b);
   if (e != hipSuccess) return fail(h, PIC_EHIP, std::string("pic_stream_probe: ") + hipGetErrorString(e));
   *gbytes_per_s = 4.0 * (double)pbytes * repeats / (ms * 1e-3) / 1e9;
   return PIC_OK;
@@ -2746,15 +2747,6 @@ static size_t tape_layout(const pic_handle* h, int64_t max_steps, int64_t every,
   return at;
 }
 
-static void tape_free(pic_handle* h) {
-  if (h->tape.block) hipFree(h->tape.block);
-  if (h->tape.wstage) hipFree(h->tape.wstage);
-  if (h->tape.wE) hipFree(h->tape.wE);
-  if (h->tape.law_block) hipFree(h->tape.law_block);
-  for (double* g : h->tape.gains) hipFree(g);
-  h->tape = Tape{};
-}
-
 int pic_tape_start(pic_handle* h, const pic_tape_config* c) {
   if (!h || !c) return fail(h, PIC_EINVAL, "pic_tape_start: null argument");
   if (h->tape.on) return fail(h, PIC_ESTATE, "pic_tape_start: a tape is open (pic_tape_stop first)");
@@ -2792,15 +2784,15 @@ int pic_tape_start(pic_handle* h, const pic_tape_config* c) {
   const size_t bytes = tape_layout(h, c->max_steps, every, offs);
   if (c->budget_bytes > 0 && bytes > (size_t)c->budget_bytes)
     return fail(h, PIC_ENOMEM, "pic_tape_start: the tape needs " + std::to_string(bytes) + " bytes, more than budget_bytes");
-  void* block = nullptr;
-  if (hipMalloc(&block, bytes) != hipSuccess) {
+  DeviceBuf<void> block;
+  if (alloc(block, bytes) != hipSuccess) {
     (void)hipGetLastError();
     return fail(h, PIC_ENOMEM, "pic_tape_start: the tape (" + std::to_string(bytes) + " bytes) does not fit on the device");
   }
   Tape& t = h->tape;
   t = Tape{};
-  t.block = block;
-  char* b = static_cast<char*>(block);
+  t.block = std::move(block);
+  char* b = static_cast<char*>(t.block.get());
   t.ck = (double*)(b + offs[0]); t.ext = (double*)(b + offs[1]); t.seg = (double*)(b + offs[2]); t.F = (double*)(b + offs[3]);
   t.M = (double*)(b + offs[4]); t.lam = (double*)(b + offs[5]); t.cot = (double*)(b + offs[6]); t.gext = (double*)(b + offs[7]);
   t.nu = (double*)(b + offs[8]); t.acc = (acc_t*)(b + offs[9]); t.cmax = (unsigned long long*)(b + offs[10]);
@@ -2810,7 +2802,7 @@ int pic_tape_start(pic_handle* h, const pic_tape_config* c) {
   t.budget = c->budget_bytes;
   HIPCHK(h, hipMemsetAsync(b + offs[9], 0, offs[11] - offs[9], h->stream));    // acc, cmax, counters
   int rc = tape_checkpoint(h, 0);
-  if (rc) { tape_free(h); return rc; }
+  if (rc) { t = Tape{}; return rc; }
   t.on = true;
   return PIC_OK;
 }
@@ -2820,7 +2812,7 @@ int pic_tape_stop(pic_handle* h) {
   if (!h->tape.block) return PIC_OK;
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   const hipError_t e = hipStreamSynchronize(h->stream);
-  tape_free(h);
+  h->tape = Tape{};
   if (e != hipSuccess) return fail(h, PIC_EHIP, std::string("pic_tape_stop: ") + hipGetErrorString(e));
   return PIC_OK;
 }
@@ -2893,9 +2885,8 @@ static int walk_open(pic_handle* h, int mo) {
   if (mo > 0) {
     const int rc = ensure_twiddle(h, mo);
     if (rc) return rc;
-    if (!t.lE && !t.wE && hipMalloc((void**)&t.wE, mesh * sizeof(double)) != hipSuccess) {
+    if (!t.lE && !t.wE && alloc(t.wE, mesh * sizeof(double)) != hipSuccess) {
       (void)hipGetLastError();
-      t.wE = nullptr;
       return fail(h, PIC_ENOMEM, "pic_tape_walk_begin: the walk's mode cotangent does not fit on the device");
     }
   }
@@ -2933,7 +2924,7 @@ static int walk_replay(pic_handle* h, int64_t sgi, const AdjArgs& a, const WalkG
     t.launches += 4;
   }
   const double* end = t.seg + (size_t)len * 2 * part;
-  const double* want_x = sgi + 1 < nseg ? t.ck + (size_t)(sgi + 1) * 2 * part : (const double*)h->x;
+  const double* want_x = sgi + 1 < nseg ? t.ck + (size_t)(sgi + 1) * 2 * part : (const double*)h->x.get();
   const double* want_v = sgi + 1 < nseg ? want_x + part : (const double*)h->v;
   hipLaunchKernelGGL(tape_compare_kernel, g.pgrid, dim3(ABLOCK), 0, h->stream, end, end + part, want_x, want_v, h->cfg.N, h->ld, t.counters);
   ++t.launches;
@@ -3115,25 +3106,31 @@ int pic_tape_walk_begin(pic_handle* h, int obs_modes, int mem_kind) {
   return walk_open(h, obs_modes);
 }
 
-// a walk's host cotangents go through wstage: [2][env][N] particles, then [env][2 M_o] modes
-static int walk_stage(pic_handle* h, double** out) {
+// the cotangents a walk call injects (mem_kind's pointers; rows of N elements); host ones are staged on the device through
+// wstage: [2][env][N] particles, then [env][2 M_o] modes
+static int walk_cot(pic_handle* h, const void* cot_x, const void* cot_v, const double* cot_modes, bool host, WalkCot* c) {
   Tape& t = h->tape;
-  const size_t bytes = ((size_t)2 * h->cfg.num_envs * h->cfg.N + (size_t)h->cfg.num_envs * 2 * t.wmo) * sizeof(double);
+  const size_t E = h->cfg.num_envs, N = h->cfg.N;
+  c->x = static_cast<const double*>(cot_x);
+  c->v = static_cast<const double*>(cot_v);
+  c->modes = cot_modes;
+  c->mc = t.wmo;
+  c->cld = (long long)N;
+  if (!host || !(cot_x || cot_v || cot_modes)) return PIC_OK;
+  const size_t bytes = (2 * E * N + E * 2 * t.wmo) * sizeof(double);
   if (bytes > t.wstage_bytes) {
-    if (t.wstage) {
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      hipFree(t.wstage);
-      t.wstage = nullptr;
-      t.wstage_bytes = 0;
-    }
-    if (hipMalloc((void**)&t.wstage, bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      t.wstage = nullptr;
-      return fail(h, PIC_ENOMEM, "pic_tape_walk: the staging of host cotangents does not fit on the device");
-    }
+    t.wstage_bytes = 0;
+    const int rc = regrow(h, t.wstage, bytes, "pic_tape_walk: the staging of host cotangents does not fit on the device");
+    if (rc) return rc;
     t.wstage_bytes = bytes;
   }
-  *out = t.wstage;
+  double* st = t.wstage;
+  if (cot_x) { HIPCHK(h, hipMemcpyAsync(st, cot_x, E * N * sizeof(double), hipMemcpyHostToDevice, h->stream)); c->x = st; }
+  if (cot_v) { HIPCHK(h, hipMemcpyAsync(st + E * N, cot_v, E * N * sizeof(double), hipMemcpyHostToDevice, h->stream)); c->v = st + E * N; }
+  if (cot_modes) {
+    HIPCHK(h, hipMemcpyAsync(st + 2 * E * N, cot_modes, E * 2 * t.wmo * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    c->modes = st + 2 * E * N;
+  }
   return PIC_OK;
 }
 
@@ -3149,7 +3146,7 @@ int pic_tape_walk_step(pic_handle* h, const double* cot_energies, const void* co
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   const int E = h->cfg.num_envs;
   const int64_t s = t.wnext;
-  const size_t mesh = (size_t)E * h->cfg.Ng, arow = (size_t)E * 2 * h->act_modes, N = (size_t)h->cfg.N;
+  const size_t mesh = (size_t)E * h->cfg.Ng, arow = (size_t)E * 2 * h->act_modes;
   const bool host = mem_kind == PIC_HOST;
   double* cot = t.cot + (size_t)s * 3 * E;
   if (cot_energies)
@@ -3157,24 +3154,9 @@ int pic_tape_walk_step(pic_handle* h, const double* cot_energies, const void* co
   else
     HIPCHK(h, hipMemsetAsync(cot, 0, 3 * E * sizeof(double), h->stream));
   WalkCot c;
-  c.x = static_cast<const double*>(cot_x);
-  c.v = static_cast<const double*>(cot_v);
-  c.modes = cot_modes;
-  c.mc = t.wmo;
-  c.cld = (long long)N;
-  if (host && (cot_x || cot_v || cot_modes)) {
-    double* st = nullptr;
-    int rc = walk_stage(h, &st);
-    if (rc) return rc;
-    if (cot_x) { HIPCHK(h, hipMemcpyAsync(st, cot_x, E * N * sizeof(double), hipMemcpyHostToDevice, h->stream)); c.x = st; }
-    if (cot_v) { HIPCHK(h, hipMemcpyAsync(st + E * N, cot_v, E * N * sizeof(double), hipMemcpyHostToDevice, h->stream)); c.v = st + E * N; }
-    if (cot_modes) {
-      double* sm = st + 2 * E * N;
-      HIPCHK(h, hipMemcpyAsync(sm, cot_modes, (size_t)E * 2 * t.wmo * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      c.modes = sm;
-    }
-  }
-  int rc = walk_reverse(h, c, adjoint_args(h), walk_geom(h));
+  int rc = walk_cot(h, cot_x, cot_v, cot_modes, host, &c);
+  if (rc) return rc;
+  rc = walk_reverse(h, c, adjoint_args(h), walk_geom(h));
   if (rc) { t.walk = false; return rc; }
   if (g_ext) HIPCHK(h, hipMemcpyAsync(g_ext, t.gext + (size_t)s * mesh, mesh * sizeof(double),
                                       host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
@@ -3199,28 +3181,12 @@ int pic_tape_walk_end(pic_handle* h, const void* cot_x0, const void* cot_v0, con
     return fail(h, PIC_ESTATE, "pic_tape_walk_end: " + std::to_string(t.wnext + 1) + " steps are not walked yet (pic_tape_walk_step)");
   if (mem_kind != PIC_HOST && mem_kind != PIC_DEVICE) return fail(h, PIC_EINVAL, "pic_tape_walk_end: bad mem_kind");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  const int E = h->cfg.num_envs;
-  const size_t N = (size_t)h->cfg.N, part = (size_t)E * h->ld;
+  const size_t part = (size_t)h->cfg.num_envs * h->ld;
   const bool host = mem_kind == PIC_HOST;
   WalkCot c;
-  c.x = static_cast<const double*>(cot_x0);
-  c.v = static_cast<const double*>(cot_v0);
-  c.modes = cot_modes0;
-  c.mc = t.wmo;
-  c.cld = (long long)N;
-  if (host && (cot_x0 || cot_v0 || cot_modes0)) {
-    double* st = nullptr;
-    int rc = walk_stage(h, &st);
-    if (rc) { t.walk = false; return rc; }
-    if (cot_x0) { HIPCHK(h, hipMemcpyAsync(st, cot_x0, E * N * sizeof(double), hipMemcpyHostToDevice, h->stream)); c.x = st; }
-    if (cot_v0) { HIPCHK(h, hipMemcpyAsync(st + E * N, cot_v0, E * N * sizeof(double), hipMemcpyHostToDevice, h->stream)); c.v = st + E * N; }
-    if (cot_modes0) {
-      double* sm = st + 2 * E * N;
-      HIPCHK(h, hipMemcpyAsync(sm, cot_modes0, (size_t)E * 2 * t.wmo * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      c.modes = sm;
-    }
-  }
-  int rc = walk_close(h, c, adjoint_args(h), walk_geom(h));
+  int rc = walk_cot(h, cot_x0, cot_v0, cot_modes0, host, &c);
+  if (rc) { t.walk = false; return rc; }
+  rc = walk_close(h, c, adjoint_args(h), walk_geom(h));
   if (rc) return rc;
   if (g_x0) rc = download(h, g_x0, t.lam, mem_kind);
   if (!rc && g_v0) rc = download(h, g_v0, t.lam + part, mem_kind);

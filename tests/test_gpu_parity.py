@@ -1057,24 +1057,36 @@ def test_create_destroy_does_not_leak(oc, po):
     import torch
     N, Ng, L = 200_000, 256, 50.0
     x0, v0 = po.synthetic_bump_on_tail(N, L, seed=1)
+    feq = np.full((8, 8), 1.0 / 64)
 
-    def cycle():
+    def cycle(open_all):
         env = oc.BatchedPIC(4, N, Ng, L=L, dt=0.1)
         env.set_actuator(oc.E_field(L, Ng, 3))
         env.reset(np.stack([x0] * 4), np.stack([v0] * 4))
         env.step_actions(np.zeros((4, 6)), 2)
         env.modes(3)
         env.eval_field(np.stack([x0] * 4))
+        if open_all:     # close() with everything still open that holds memory of its own
+            env.profile(True)
+            env.start_recording(modes=4, phase_bins=8, feq=feq)
+            env.start_tape(4)
+            env.step_feedback_gain(np.diag([-1.0] * 3 + [1.0] * 3), 1)
+            env.step_ext_traj(np.zeros((1, 4, Ng)), snapshots=True)
+            env._h.compute_E(np.stack([x0] * 4))
+            env.kl_divergence(feq)
+            env.stream_probe(1)
+            env.walk().step(d_x=np.ones((4, N)))      # host cotangents: staged on the device
         env.close()
 
-    cycle()
-    torch.cuda.synchronize()
-    free0 = torch.cuda.mem_get_info()[0]
-    for _ in range(25):
-        cycle()
-    torch.cuda.synchronize()
-    free1 = torch.cuda.mem_get_info()[0]
-    assert free0 - free1 < 64 << 20, (free0, free1)      # 25 cycles of ~40 MB each would show up as ~1 GB
+    for open_all in (False, True):
+        cycle(open_all)
+        torch.cuda.synchronize()
+        free0 = torch.cuda.mem_get_info()[0]
+        for _ in range(25):
+            cycle(open_all)
+        torch.cuda.synchronize()
+        free1 = torch.cuda.mem_get_info()[0]
+        assert free0 - free1 < 64 << 20, (open_all, free0, free1)      # 25 cycles of ~40 MB each would show up as ~1 GB
 
 
 def test_placement_search_frees_what_it_does_not_keep(oc):
