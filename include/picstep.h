@@ -430,10 +430,10 @@ typedef struct pic_tape_info {
   int64_t steps;                   /* steps taped so far */
   int64_t checkpoint_every;
   int64_t bytes;                   /* device memory the tape holds */
-  int64_t replay_mismatches;       /* particle values of the last backward's replays that differ from the forward's (0 expected) */
+  int64_t replay_mismatches;       /* particle values of the last backward's or tangent's replays that differ from the forward's (0 expected) */
   int64_t unit_retries;            /* repeated adjoint deposits (0: the unit of the adjoint deposits cannot overflow) */
-  int64_t launches;                /* kernels the last backward enqueued */
-  int64_t replay_bad_positions;    /* non-finite / out-of-range positions the last backward's replay met (0 expected) */
+  int64_t launches;                /* kernels the last backward or tangent enqueued */
+  int64_t replay_bad_positions;    /* non-finite / out-of-range positions the last backward's or tangent's replay met (0 expected) */
 } pic_tape_info;
 
 int pic_tape_start(pic_handle* h, const pic_tape_config* cfg);   /* checkpoints the current state; PIC_ESTATE if a tape is open */
@@ -474,6 +474,24 @@ int pic_tape_walk_step(pic_handle* h, const double* cot_energies, const void* co
                        int mem_kind, double* g_ext, double* g_actions, int64_t* step);
 int pic_tape_walk_end(pic_handle* h, const void* cot_x0, const void* cot_v0, const double* cot_modes0, int mem_kind, void* g_x0,
                       void* g_v0);
+/* Forward mode of the tape: the Jacobian-vector product of the T steps taped so far in K directions at once
+ * (1 <= K <= 8), with the almost-everywhere derivative of the backward.  Inputs (each may be NULL = 0): d_ext [K][T][num_envs][Ng]
+ * tangents of every step's external field e_t, or d_actions [K][T][num_envs][2M] tangents of the actions, mapped through the
+ * actuator basis as e_t is (needs an actuator set before pic_tape_start; at most one of the two); d_x0 / d_v0 [K][num_envs][N]
+ * on the tape's starting state.  Outputs (each may be NULL): d_hist [K][T][3][num_envs] the tangents of KE, PE, PE_reward
+ * (pic_step_history's layout per direction), d_x / d_v [K][num_envs][N] of the final particles, d_E_mesh [K][T][num_envs][Ng] of
+ * every step's post-step E_mesh.  Each direction is computed on its own (K directions in one call equal K calls bit for bit);
+ * results do not depend on blocks_per_env, the checkpoint interval, the schedule or the other environments of the batch.  All in
+ * mem_kind memory, as pic_tape_backward: PIC_DEVICE is asynchronous on the handle's stream; PIC_HOST waits and returns
+ * PIC_ESTATE if a replay differed from the taped forward.  The tape stays open; the handle's particles, fields, energies and
+ * cached deposits are not touched, and a later pic_tape_backward gives the same bits as without this call.  It abandons a walk
+ * in progress; pic_tape_stats then reports this call's replay counts.  The first call with K directions allocates their
+ * working memory ((2 K num_envs ld + 2 K num_envs Ng + 4 K num_envs) * 8 bytes, each part rounded up to 256), which counts in
+ * `bytes` and against budget_bytes (PIC_ENOMEM, the tape still usable) and is freed by pic_tape_stop.  No tape open, or a tape
+ * holding steps of pic_step_feedback_gain (forward mode through the gain law is not built): PIC_ESTATE.  K outside 1..8, both
+ * d_ext and d_actions, or a bad mem_kind: PIC_EINVAL.  T = 0: d_x / d_v are d_x0 / d_v0 and nothing else is written. */
+int pic_tape_tangent(pic_handle* h, int K, const double* d_ext, const double* d_actions, const void* d_x0, const void* d_v0,
+                     int mem_kind, double* d_hist, void* d_x, void* d_v, double* d_E_mesh);
 
 int pic_sync(pic_handle* h);
 /* Number of particle positions found non-finite or out of range by the last sweeps (0 = healthy).  Counts the state's

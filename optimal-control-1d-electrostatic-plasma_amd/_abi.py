@@ -139,6 +139,7 @@ SIGNATURES = {
     "pic_tape_walk_begin": [_vp, C.c_int, C.c_int],
     "pic_tape_walk_step": [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _i64p],
     "pic_tape_walk_end": [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp],
+    "pic_tape_tangent": [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp],
     "pic_set_stream": [_vp, _vp],
     "pic_own_stream": [_vp],
     "pic_schedule": [_vp],
@@ -721,6 +722,29 @@ class Handle:
         """pic_tape_walk_end: addresses (int, 0 = NULL) in and out."""
         p = [None if not q else _ptr(int(q)) for q in (cot_x0, cot_v0, cot_modes0, g_x0, g_v0)]
         self._chk(self.lib.pic_tape_walk_end(self._h, p[0], p[1], p[2], int(mem_kind), p[3], p[4]))
+
+    def tape_tangent(self, K, d_ext=None, d_actions=None, d_x0=None, d_v0=None, fields=False):
+        """pic_tape_tangent with host arrays: K directions in, dict out with hist [K][T][3][num_envs], x / v [K][num_envs][N]
+        and, with fields, E_mesh [K][T][num_envs][Ng]."""
+        T = self.tape_stats()["steps"]
+        E, K = self.num_envs, int(K)
+
+        def host(a, shape):
+            return None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(shape))
+        de = host(d_ext, (K, T, E, self.Ng))
+        da = host(d_actions, (K, T, E, -1))
+        dx, dv = host(d_x0, (K, E, self.N)), host(d_v0, (K, E, self.N))
+        out = {"hist": np.zeros((K, T, 3, E)), "x": np.zeros((K, E, self.N)), "v": np.zeros((K, E, self.N))}
+        if fields:
+            out["E_mesh"] = np.zeros((K, T, E, self.Ng))
+        self._chk(self.lib.pic_tape_tangent(self._h, K, _ptr(de), _ptr(da), _ptr(dx), _ptr(dv), PIC_HOST, _ptr(out["hist"]),
+                                            _ptr(out["x"]), _ptr(out["v"]), _ptr(out.get("E_mesh"))))
+        return out
+
+    def tape_tangent_device(self, K, d_ext, d_actions, d_x0, d_v0, hist, x, v, E_mesh):
+        """pic_tape_tangent on device pointers (int, 0 = NULL); asynchronous on the handle's stream."""
+        p = [None if not q else _ptr(int(q)) for q in (d_ext, d_actions, d_x0, d_v0, hist, x, v, E_mesh)]
+        self._chk(self.lib.pic_tape_tangent(self._h, int(K), p[0], p[1], p[2], p[3], PIC_DEVICE, p[4], p[5], p[6], p[7]))
 
     def stream_probe(self, repeats=10):
         g = C.c_double()

@@ -62,6 +62,7 @@
 #include "pic_aux.h"
 #include "pic_record.h"
 #include "pic_adjoint.h"
+#include "pic_tangent.h"
 
 
 // ---------------------------------------------------------------------------------------------
@@ -177,9 +178,9 @@ struct Tape {
   double* nu = nullptr;               // [env][Ng]
   acc_t* acc = nullptr;               // [env][Ng] zero between uses
   unsigned long long* cmax = nullptr; // [env] zero between uses
-  unsigned long long* counters = nullptr;   // [0] replay mismatches of the last backward, [1] replay positions out of range
+  unsigned long long* counters = nullptr;   // [0] replay mismatches of the last backward or tangent, [1] replay positions out of range
   double* gact = nullptr;             // [max_steps][env][2M] a-bar (M: the actuator's modes at pic_tape_start; none without one)
-  int64_t launches = 0;               // kernels the last backward enqueued
+  int64_t launches = 0;               // kernels the last backward or tangent enqueued
   int64_t budget = 0;                 // budget_bytes of pic_tape_start (0: none)
   // steps of the gain law (pic_step_feedback_gain): one block allocated by the first such call, one gain per call;
   // both count in `bytes`
@@ -198,6 +199,11 @@ struct Tape {
   DeviceBuf<double> wstage;           // [2][env][N] + [env][2 M_o] host cotangents of a step on the device (allocated on demand)
   size_t wstage_bytes = 0;
   DeviceBuf<double> wE;               // [env][Ng] E-bar of a walk's mode cotangents on a tape without a law block (else lE)
+  // forward mode (pic_tape_tangent): the tangent state, meshes and unit words of tan_k directions, allocated by the
+  // first call with that many and grown for more; counts in `bytes`
+  DeviceBuf<void> tan_block;
+  int tan_k = 0;
+  size_t tan_bytes = 0;
 };
 
 struct pic_handle {
@@ -3192,6 +3198,200 @@ int pic_tape_walk_end(pic_handle* h, const void* cot_x0, const void* cot_v0, con
   if (!rc && g_v0) rc = download(h, g_v0, t.lam + part, mem_kind);
   if (rc) return rc;
   return host ? walk_check(h, "pic_tape_walk_end") : PIC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Forward mode of the tape (include/picstep.h: pic_tape_tangent; kernels: pic_tangent.h)
+// ---------------------------------------------------------------------------------------------
+// bytes of the tangent block for kc directions: state [kc][2][env][ld], dF [kc][env][Ng], acc [kc][env][Ng], ke [kc][env],
+// umax [3][kc][env]; *offs: the parts' offsets (everything from offs[2] on is zero between uses)
+static size_t tangent_layout(const pic_handle* h, int kc, size_t (&offs)[5]) {
+  const size_t E = h->cfg.num_envs, mesh = E * h->cfg.Ng;
+  const size_t sizes[5] = {(size_t)kc * 2 * E * h->ld * sizeof(double), kc * mesh * sizeof(double), kc * mesh * sizeof(acc_t),
+                           kc * E * sizeof(acc_t), 3 * kc * E * sizeof(unsigned long long)};
+  size_t at = 0;
+  for (int i = 0; i < 5; ++i) {
+    offs[i] = at;
+    at += (sizes[i] + 255) & ~(size_t)255;
+  }
+  return at;
+}
+
+// the tangent block for K directions, within budget_bytes; on failure the tape keeps what it had
+static int tangent_reserve(pic_handle* h, int K, const std::string& w) {
+  Tape& t = h->tape;
+  if (t.tan_k >= K) return PIC_OK;
+  size_t offs[5];
+  const size_t bytes = tangent_layout(h, K, offs);
+  if (t.budget > 0 && t.bytes - t.tan_bytes + bytes > (size_t)t.budget)
+    return fail(h, PIC_ENOMEM, w + ": the working memory of " + std::to_string(K) + " directions (" + std::to_string(bytes) +
+                                   " bytes) would take the tape past budget_bytes (pic_tape_start)");
+  DeviceBuf<void> b;
+  if (alloc(b, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(h, PIC_ENOMEM, w + ": the working memory of " + std::to_string(K) + " directions does not fit on the device");
+  }
+  if (t.tan_block) HIPCHK(h, hipStreamSynchronize(h->stream));      // queued work may still read the old block
+  t.tan_block = std::move(b);
+  t.bytes = t.bytes - t.tan_bytes + bytes;
+  t.tan_bytes = bytes;
+  t.tan_k = K;
+  return PIC_OK;
+}
+
+extern "C++" {
+// the kernels of a sub-stage for the direction count at hand (1, up to 4, up to 8: the per-direction values live in registers)
+template <int S>
+static void tangent_deposit(pic_handle* h, const AdjStep& st, const TanArgs& ta, const AdjArgs& a, dim3 grid, size_t lds, int kd) {
+  if (kd == 1) hipLaunchKernelGGL((tangent_deposit_kernel<S, 1>), grid, dim3(ABLOCK), lds, h->stream, st, ta, a, kd);
+  else if (kd <= 4) hipLaunchKernelGGL((tangent_deposit_kernel<S, 4>), grid, dim3(ABLOCK), lds, h->stream, st, ta, a, kd);
+  else hipLaunchKernelGGL((tangent_deposit_kernel<S, 8>), grid, dim3(ABLOCK), lds, h->stream, st, ta, a, kd);
+}
+
+template <int S>
+static void tangent_pass(pic_handle* h, const AdjStep& st, const TanArgs& ta, const AdjArgs& a, dim3 grid) {
+  if (ta.K == 1) hipLaunchKernelGGL((tangent_pass_kernel<S, 1>), grid, dim3(ABLOCK), 0, h->stream, st, ta, a);
+  else if (ta.K <= 4) hipLaunchKernelGGL((tangent_pass_kernel<S, 4>), grid, dim3(ABLOCK), 0, h->stream, st, ta, a);
+  else hipLaunchKernelGGL((tangent_pass_kernel<S, 8>), grid, dim3(ABLOCK), 0, h->stream, st, ta, a);
+}
+}  // extern "C++"
+
+int pic_tape_tangent(pic_handle* h, int K, const double* d_ext, const double* d_actions, const void* d_x0, const void* d_v0,
+                     int mem_kind, double* d_hist, void* d_x, void* d_v, double* d_E_mesh) {
+  if (!h) return PIC_EINVAL;
+  Tape& t = h->tape;
+  const std::string w("pic_tape_tangent");
+  if (!t.on) return fail(h, PIC_ESTATE, w + ": no tape is open (pic_tape_start)");
+  if (K < 1 || K > kMaxTangents) return fail(h, PIC_EINVAL, w + ": need 1 <= K <= " + std::to_string(kMaxTangents));
+  if (d_ext && d_actions) return fail(h, PIC_EINVAL, w + ": d_ext and d_actions are both given (at most one)");
+  if (mem_kind != PIC_HOST && mem_kind != PIC_DEVICE) return fail(h, PIC_EINVAL, w + ": bad mem_kind");
+  const int64_t T = t.steps;
+  for (int64_t s = 0; s < T && !t.law.empty(); ++s)
+    if (t.law[(size_t)s] >= 0)
+      return fail(h, PIC_ESTATE, w + ": the tape holds steps of pic_step_feedback_gain, and forward mode through the gain law is "
+                                     "not built (pic_tape_backward_feedback differentiates it in reverse)");
+  if (d_actions && !t.gact)
+    return fail(h, PIC_ESTATE, w + ": d_actions needs an actuator set before pic_tape_start (pic_set_actuator)");
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  const int E = h->cfg.num_envs, Ng = h->cfg.Ng, Mact = h->act_modes;
+  const bool host = mem_kind == PIC_HOST;
+  const size_t N = h->cfg.N, part = (size_t)E * h->ld, mesh = (size_t)E * Ng, row = N * sizeof(double);
+  t.walk = false;                     // (a walk's replayed segment is about to be overwritten)
+  t.launches = 0;
+  HIPCHK(h, hipMemsetAsync(t.counters, 0, 2 * sizeof(unsigned long long), h->stream));
+  if (T == 0) {                       // no step: the tangent of the final particles is the initial one (NULL: 0)
+    const size_t n = (size_t)K * E * row;
+    void* outs[2] = {d_x, d_v};
+    const void* ins[2] = {d_x0, d_v0};
+    for (int k = 0; k < 2; ++k) {
+      if (!outs[k]) continue;
+      if (host && ins[k]) std::memcpy(outs[k], ins[k], n);
+      else if (host) std::memset(outs[k], 0, n);
+      else if (ins[k]) HIPCHK(h, hipMemcpyAsync(outs[k], ins[k], n, hipMemcpyDeviceToDevice, h->stream));
+      else HIPCHK(h, hipMemsetAsync(outs[k], 0, n, h->stream));
+    }
+    if (host) HIPCHK(h, hipStreamSynchronize(h->stream));
+    return PIC_OK;
+  }
+  int rc = tangent_reserve(h, K, w);
+  if (rc) return rc;
+  size_t offs[5];
+  tangent_layout(h, t.tan_k, offs);
+  char* b = static_cast<char*>(t.tan_block.get());
+  TanArgs ta{};
+  ta.st = (double*)b; ta.dstride = (long long)(2 * part); ta.vofs = (long long)part;
+  ta.dF = (double*)(b + offs[1]); ta.acc = (acc_t*)(b + offs[2]); ta.ke = (acc_t*)(b + offs[3]);
+  ta.umax = (unsigned long long*)(b + offs[4]);
+  ta.K = K; ta.num_envs = E;
+  HIPCHK(h, hipMemsetAsync(b + offs[2], 0, t.tan_bytes - offs[2], h->stream));     // acc, ke, umax (a failed call may leave them)
+  // host memory: the control tangents and the mesh-sized outputs go through one device block of this call
+  const size_t in_n = d_ext ? (size_t)K * T * mesh : d_actions ? (size_t)K * T * E * 2 * Mact : 0;
+  const size_t hist_n = d_hist ? (size_t)K * T * 3 * E : 0, em_n = d_E_mesh ? (size_t)K * T * mesh : 0;
+  const double* din = d_ext ? d_ext : d_actions;
+  double* dhist = d_hist;
+  double* dem = d_E_mesh;
+  DeviceBuf<double> stage;
+  if (host && in_n + hist_n + em_n > 0) {
+    if (alloc(stage, (in_n + hist_n + em_n) * sizeof(double)) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(h, PIC_ENOMEM, w + ": the staging of host tangents does not fit on the device");
+    }
+    double* p = stage;
+    if (in_n) {
+      HIPCHK(h, hipMemcpyAsync(p, din, in_n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      din = p;
+      p += in_n;
+    }
+    if (hist_n) { dhist = p; p += hist_n; }
+    if (em_n) dem = p;
+  }
+  // (dx_0, dv_0) of every direction into the state rows (padded to ld)
+  for (int d = 0; d < K; ++d) {
+    const void* ins[2] = {d_x0, d_v0};
+    for (int k = 0; k < 2; ++k) {
+      double* dst = ta.st + (size_t)d * 2 * part + (size_t)k * part;
+      if (ins[k])
+        HIPCHK(h, hipMemcpy2DAsync(dst, (size_t)h->ld * sizeof(double), static_cast<const double*>(ins[k]) + (size_t)d * E * N, row, row,
+                                   E, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->stream));
+      else
+        HIPCHK(h, hipMemsetAsync(dst, 0, part * sizeof(double), h->stream));
+    }
+  }
+  const AdjArgs a = adjoint_args(h);
+  const WalkGeom g = walk_geom(h);
+  hipLaunchKernelGGL(tangent_start_kernel, g.pgrid, dim3(ABLOCK), 0, h->stream, ta, a);
+  ++t.launches;
+  // a deposit workgroup holds kd directions' meshes in 64 KB of LDS; groups of them run side by side (grid z)
+  const int kd = std::min<int>(K, (int)std::max<size_t>(1, 65536 / ((size_t)(Ng + 1) * sizeof(unsigned long long))));
+  const dim3 dgrid(g.pgrid.x, E, (K + kd - 1) / kd), mgrid(E, K);
+  const size_t dlds = (size_t)kd * (Ng + 1) * sizeof(unsigned long long);
+  TanMeshIO io{};
+  io.basis = h->basis; io.Mact = Mact;
+  io.in_dstride = d_ext ? (long long)(T * mesh) : (long long)(T * E * 2 * Mact);
+  io.out_hstride = (long long)(T * 3 * E); io.out_mstride = (long long)(T * mesh);
+  const int64_t nseg = (T + t.every - 1) / t.every;
+  for (int64_t sgi = 0; sgi < nseg; ++sgi) {
+    rc = walk_replay(h, sgi, a, g);
+    if (rc) return rc;
+    const int64_t t0 = sgi * t.every, len = std::min<int64_t>(t.every, T - t0);
+    for (int64_t i = 0; i < len; ++i) {
+      const int64_t s = t0 + i;
+      const double* x = t.seg + (size_t)i * 2 * part;
+      const AdjStep st{x, x + part, t.F + (size_t)i * 3 * mesh, (long long)mesh};
+      TanMeshIO m = io;
+      m.ext = d_ext ? din + (size_t)s * mesh : nullptr;
+      m.act = d_actions ? din + (size_t)s * E * 2 * Mact : nullptr;
+      m.M = t.M + (size_t)i * mesh;
+      m.hist = dhist ? dhist + (size_t)s * 3 * E : nullptr;
+      m.Emesh = dem ? dem + (size_t)s * mesh : nullptr;
+      tangent_deposit<1>(h, st, ta, a, dgrid, dlds, kd);
+      hipLaunchKernelGGL(tangent_mesh_kernel<1>, mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, ta, m, a);
+      tangent_pass<1>(h, st, ta, a, g.pgrid);
+      tangent_deposit<2>(h, st, ta, a, dgrid, dlds, kd);
+      hipLaunchKernelGGL(tangent_mesh_kernel<2>, mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, ta, m, a);
+      tangent_pass<2>(h, st, ta, a, g.pgrid);
+      tangent_deposit<3>(h, st, ta, a, dgrid, dlds, kd);
+      hipLaunchKernelGGL(tangent_mesh_kernel<3>, mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, ta, m, a);
+      tangent_pass<3>(h, st, ta, a, g.pgrid);
+      tangent_deposit<4>(h, st, ta, a, dgrid, dlds, kd);
+      hipLaunchKernelGGL(tangent_mesh_kernel<4>, mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, ta, m, a);
+      t.launches += 11;
+    }
+    HIPCHK(h, hipGetLastError());
+  }
+  if (host && hist_n) HIPCHK(h, hipMemcpyAsync(d_hist, dhist, hist_n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (host && em_n) HIPCHK(h, hipMemcpyAsync(d_E_mesh, dem, em_n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  // (dx', dv') of every direction out of the state rows
+  for (int d = 0; d < K; ++d) {
+    void* outs[2] = {d_x, d_v};
+    for (int k = 0; k < 2; ++k)
+      if (outs[k])
+        HIPCHK(h, hipMemcpy2DAsync(static_cast<double*>(outs[k]) + (size_t)d * E * N, row, ta.st + (size_t)d * 2 * part + (size_t)k * part,
+                                   (size_t)h->ld * sizeof(double), row, E, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
+                                   h->stream));
+  }
+  HIPCHK(h, hipGetLastError());
+  return host ? walk_check(h, w) : PIC_OK;
 }
 
 }  // extern "C"

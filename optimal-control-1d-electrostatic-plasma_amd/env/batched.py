@@ -478,6 +478,58 @@ class BatchedPIC:
                                 "(were the particles written while the tape was open?): the gradient is not valid")
         return res
 
+    def tangent(self, d_ext=None, d_actions=None, d_x0=None, d_v0=None, fields: bool = False):
+        """Jacobian-vector product of the taped steps (pic_tape_tangent): tangents d_ext [T, num_envs, N_mesh] of
+        every step's external field, or d_actions [T, num_envs, 2*max_mode] of its actions (at most one), and d_x0, d_v0
+        [num_envs, N] of the tape's starting particles (each None = 0).  Every input may carry a leading axis of K <= 8
+        directions, computed in one call; without one K = 1 and the outputs have no K axis either.  Returns a dict: "KE", "PE",
+        "PE_reward" [K, T, num_envs], "x", "v" [K, num_envs, N] (final particles) and, with fields, "E_mesh" [K, T, num_envs,
+        N_mesh] (every step's post-step field).  NumPy arrays, or float64 CUDA tensors if any input is one (then stream-ordered like
+        backward).  Raises PicError if the replay of the taped steps does not reproduce the forward bit for bit."""
+        T = self._h.tape_stats()["steps"]
+        E, N, Ng = self.num_envs, self.N, self.N_mesh
+        n = 2 * getattr(self, "max_mode", 0)
+        base = {"d_ext": (T, E, Ng), "d_actions": (T, E, n), "d_x0": (E, N), "d_v0": (E, N)}
+        given = {k: a for k, a in (("d_ext", d_ext), ("d_actions", d_actions), ("d_x0", d_x0), ("d_v0", d_v0)) if a is not None}
+        ks = {int(a.shape[0]) for k, a in given.items() if len(a.shape) == len(base[k]) + 1}
+        if len(ks) > 1:
+            raise ValueError(f"tangent: the inputs disagree on the number of directions: {sorted(ks)}")
+        batched = bool(ks)
+        K = ks.pop() if ks else 1
+        for k, a in given.items():
+            want = ((K,) if batched else ()) + base[k]
+            if tuple(a.shape) != want:
+                raise ValueError(f"tangent: {k} must have shape {want}, not {tuple(a.shape)}")
+        on_device = any(hasattr(a, "is_cuda") and a.is_cuda for a in given.values())
+
+        def split(hist, x, v, em):
+            res = {"KE": hist[:, :, 0], "PE": hist[:, :, 1], "PE_reward": hist[:, :, 2], "x": x, "v": v}
+            if fields:
+                res["E_mesh"] = em
+            return res if batched else {k: a[0] for k, a in res.items()}
+        if not on_device:
+            out = self._h.tape_tangent(K, d_ext, d_actions, d_x0, d_v0, fields)
+            return split(out["hist"], out["x"], out["v"], out.get("E_mesh"))
+        import torch
+        f64 = dict(dtype=torch.float64, device=f"cuda:{self.device}")
+        ins = {k: torch.as_tensor(a, **f64).reshape((K,) + base[k]).contiguous() for k, a in given.items()}
+        hist = torch.empty((K, T, 3, E), **f64)
+        x, v = torch.empty((K, E, N), **f64), torch.empty((K, E, N), **f64)
+        em = torch.empty((K, T, E, Ng), **f64) if fields else None
+        shared = getattr(self, "_torch_stream", None) is not None
+        if not shared:
+            torch.cuda.current_stream(self.device).synchronize()
+
+        def ptr(t):
+            return 0 if t is None or t.numel() == 0 else t.data_ptr()
+        self._h.tape_tangent_device(K, ptr(ins.get("d_ext")), ptr(ins.get("d_actions")), ptr(ins.get("d_x0")),
+                                    ptr(ins.get("d_v0")), ptr(hist), ptr(x), ptr(v), ptr(em))
+        st = self._h.tape_stats()                    # (waits for the tangent)
+        if st["replay_mismatches"]:
+            raise _abi.PicError(f"tangent: the replay differs from the taped forward in {st['replay_mismatches']} particle values "
+                                "(were the particles written while the tape was open?): the tangent is not valid")
+        return split(hist, x, v, em)
+
     def walk(self, obs_modes: Optional[int] = None, on_device: bool = False):
         """The reverse pass of the open tape one step at a time (pic_tape_walk_*): returns a TapeWalk whose
         step(d_energies, d_x, d_v, d_modes) reverses steps T-1, T-2, ... and end(d_x0, d_v0, d_modes0) closes it.  obs_modes

@@ -1,8 +1,10 @@
 """Differentiable rollouts for torch: the energy traces of a rollout as functions of its actions (or raw external fields), with
-the gradient from the device's adjoint (pic_tape_backward).
+the gradient from the device's adjoint (pic_tape_backward) and forward-mode tangents from pic_tape_tangent (7f).
 
     KE, PE, PE_reward = rollout(env, actions)      # actions: float64 CUDA tensor [T, num_envs, 2*max_mode], requires_grad
     (PE_reward.sum() + lam * (actions ** 2).sum() * L / 4).backward()   # fills actions.grad
+    with torch.autograd.forward_ad.dual_level():     # forward mode: the tangent of the traces along a direction du
+        KE, PE, PE_reward = (fwAD.unpack_dual(o).tangent for o in rollout(env, fwAD.make_dual(actions, du)))
 
     KE, PE, PE_reward, modes = rollout_feedback(env, gain, T)   # gain: [num_envs, 2M, 2M] or [2M, 2M], requires_grad
     (PE_reward.sum() + (modes[..., 0] ** 2).sum()).backward()  # fills gain.grad through the closed loop
@@ -39,7 +41,7 @@ class _Rollout(torch.autograd.Function):
             ke, pe, per = env.step_actions_traj(host, history=True)
         else:
             ke, pe, per = env.step_ext_traj(host, history=True)
-        ctx.env, ctx.kind, ctx.serial, ctx.steps = env, kind, serial, T
+        ctx.env, ctx.kind, ctx.serial, ctx.steps, ctx.device = env, kind, serial, T, u.device
         return tuple(torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64, device=u.device) for a in (ke, pe, per))
 
     @staticmethod
@@ -54,6 +56,19 @@ class _Rollout(torch.autograd.Function):
             out = env.backward(d_KE=g_ke.numpy(), d_PE=g_pe.numpy(), d_PE_reward=g_per.numpy())
             g = torch.as_tensor(out["actions"] if ctx.kind == "actions" else out["ext"])
         return g, None, None, None
+
+    @staticmethod
+    def jvp(ctx, u_t, env_t, kind_t, ce_t):
+        """Forward mode (torch.autograd.forward_ad): the tangent of the energy traces along u_t, from pic_tape_tangent on the
+        tape this rollout opened."""
+        env = ctx.env
+        if getattr(env, "_tape_serial", None) != ctx.serial or env.tape_stats()["steps"] != ctx.steps:
+            raise PicError("jvp: the environment has moved on since this rollout (a further step, rollout or reset)")
+        if u_t is None:
+            return tuple(torch.zeros((ctx.steps, env.num_envs), dtype=torch.float64, device=ctx.device) for _ in range(3))
+        u = u_t.contiguous() if u_t.is_cuda else u_t.detach().numpy()
+        out = env.tangent(**{"d_actions" if ctx.kind == "actions" else "d_ext": u})
+        return tuple(torch.as_tensor(out[k], dtype=torch.float64, device=ctx.device) for k in ("KE", "PE", "PE_reward"))
 
 
 def rollout(env, actions, checkpoint_every=0):
