@@ -297,6 +297,34 @@ int pic_phase_histogram(pic_handle* h, int nbins, double vmin, double vmax, uint
  * density, estimate_f of the initial state), kl host [num_envs].  Histogram and reduction stay on the device. */
 int pic_phase_kl(pic_handle* h, int nbins, double vmin, double vmax, const double* feq, double* kl);
 
+/* Smoothed phase-space density and its KL cost, differentiable in the particles (additive to ABI 5).  For every
+ * environment, with dx = L / nx and dv = (vmax - vmin) / nv:
+ *     f[i][j] = n0 / (dx dv N) * sum_k Wx_i(x_k) Wv_j(v_k)        (estimate_f's normalisation, objective.py:12)
+ * Wx is the periodic CIC weight on the bin centres (i + 1/2) dx of the stored, wrapped x; Wv the CIC weight on the centres
+ * vmin + (j + 1/2) dv, the outer half-bins [vmin, vmin + dv/2) and (vmax - dv/2, vmax] giving their whole weight to the edge bin.
+ * A particle outside [0, L] x [vmin, vmax] is dropped, as np.histogram2d drops it: sum f dx dv = n0 inside / N, the histogram's
+ * mass.  A particle's four weights are integers that sum exactly to one particle unit 2^s (s from N: no bin can overflow), so f
+ * is bitwise reproducible and does not depend on blocks_per_env, the schedule or the environment's place in the batch.
+ *     kl = sum_ij rel_entr(f[i][j], feq[i][j] + 1e-12) dx dv        (estimate_KL_divergence, objective.py:16-18)
+ * feq: the target, float64 in feq_mem_kind memory, [nx][nv] for every environment (feq_per_env = 0) or [num_envs][nx][nv] (1):
+ * pic_phase_histogram's f, or this f of an initial state.  Float64 particles and positions only; 1 <= nx, nv <= 1024 and finite
+ * vmin < vmax; anything else is PIC_EINVAL (the reason in pic_last_error).  Both entries return when their outputs have arrived. */
+typedef struct pic_phase_spec {
+  int32_t nx, nv;                  /* bins in x and in v, 1..1024 each                        */
+  double  vmin, vmax;              /* velocity range; x spans [0, L]                          */
+  const double* feq;               /* the KL's target, or NULL (the density alone)            */
+  int32_t feq_per_env;             /* 0: feq [nx][nv]; 1: feq [num_envs][nx][nv]              */
+  int32_t feq_mem_kind;            /* PIC_HOST | PIC_DEVICE                                   */
+} pic_phase_spec;
+/* kl [num_envs] (needs feq) and f [num_envs][nx][nv] of the current particles, in mem_kind memory; either may be NULL, not both. */
+int pic_phase_kl_smooth(pic_handle* h, const pic_phase_spec* spec, int mem_kind, double* kl, double* f);
+/* Vector-Jacobian product of kl: g_x, g_v [num_envs][N] float64 (dense, mem_kind memory; either may be NULL) receive
+ * cot_kl[e] dkl_e/dx and cot_kl[e] dkl_e/dv of the current particles; cot_kl [num_envs] in mem_kind memory.  Needs feq.  The
+ * derivative is the almost-everywhere one of the unquantised weights: dkl/df = (ln(f / (feq + 1e-12)) + 1) dx dv where f > 0
+ * and 0 where f = 0, gathered at a particle's four bins with the CIC slopes -+1/dx in x and -+1/dv in v (0 in v in the clamped
+ * half-bins; 0 for a dropped particle). */
+int pic_phase_kl_smooth_vjp(pic_handle* h, const pic_phase_spec* spec, const double* cot_kl, int mem_kind, void* g_x, void* g_v);
+
 /* Per-kernel timing with HIP events on the handle's stream (bench.py's roofline leg).
  * kinds: 0..3 = sweeps A..D, 4 = field solve, 5 = auxiliary sweeps (refresh, first deposits), 6 = resident launches,
  * 7 = the particle sweeps of the other integrators (pic_set_integrator). ms_sum / launches are arrays of 8. */

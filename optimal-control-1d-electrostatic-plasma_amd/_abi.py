@@ -81,6 +81,12 @@ class PicTapeInfo(C.Structure):
                                                 "launches", "replay_bad_positions")]
 
 
+class PicPhaseSpec(C.Structure):
+    """pic_phase_spec (include/picstep.h): bins, velocity range and KL target of the smoothed phase-space density."""
+    _fields_ = [("nx", C.c_int32), ("nv", C.c_int32), ("vmin", C.c_double), ("vmax", C.c_double), ("feq", C.c_void_p),
+                ("feq_per_env", C.c_int32), ("feq_mem_kind", C.c_int32)]
+
+
 class PicError(RuntimeError):
     pass
 
@@ -125,6 +131,8 @@ SIGNATURES = {
     "pic_get_modes": [_vp, C.c_int, _vp, _vp, C.c_int],
     "pic_phase_histogram": [_vp, C.c_int, C.c_double, C.c_double, _vp],
     "pic_phase_kl": [_vp, C.c_int, C.c_double, C.c_double, _vp, _vp],
+    "pic_phase_kl_smooth": [_vp, C.POINTER(PicPhaseSpec), C.c_int, _vp, _vp],
+    "pic_phase_kl_smooth_vjp": [_vp, C.POINTER(PicPhaseSpec), _vp, C.c_int, _vp, _vp],
     "pic_stream_probe": [_vp, C.c_int, _dp],
     "pic_record_start": [_vp, C.POINTER(PicRecordConfig)],
     "pic_record_now": [_vp],
@@ -595,6 +603,18 @@ class Handle:
         kl = np.empty(self.num_envs)
         self._chk(self.lib.pic_phase_kl(self._h, int(f.shape[0]), float(vmin), float(vmax), _ptr(f), _ptr(kl)))
         return kl
+
+    def phase_kl_smooth(self, nx, nv, vmin, vmax, feq, feq_per_env, feq_kind, mem_kind, kl, f):
+        """pic_phase_kl_smooth on addresses (int, 0 = NULL) in feq_kind / mem_kind memory."""
+        spec = PicPhaseSpec(int(nx), int(nv), float(vmin), float(vmax), int(feq) or None, int(feq_per_env), int(feq_kind))
+        p = [_ptr(int(q)) if q else None for q in (kl, f)]
+        self._chk(self.lib.pic_phase_kl_smooth(self._h, C.byref(spec), int(mem_kind), p[0], p[1]))
+
+    def phase_kl_smooth_vjp(self, nx, nv, vmin, vmax, feq, feq_per_env, feq_kind, cot_kl, mem_kind, g_x, g_v):
+        """pic_phase_kl_smooth_vjp on addresses (int, 0 = NULL)."""
+        spec = PicPhaseSpec(int(nx), int(nv), float(vmin), float(vmax), int(feq) or None, int(feq_per_env), int(feq_kind))
+        p = [_ptr(int(q)) if q else None for q in (cot_kl, g_x, g_v)]
+        self._chk(self.lib.pic_phase_kl_smooth_vjp(self._h, C.byref(spec), p[0], int(mem_kind), p[1], p[2]))
 
     # -- rollout recorder (pic_record_*) ------------------------------------------------------------
     def record_start(self, stride=1, n_modes=0, x_bins=0, v_bins=0, phase_bins=(0, 0), vmin=-25.0, vmax=25.0, phase_dx=0.0,

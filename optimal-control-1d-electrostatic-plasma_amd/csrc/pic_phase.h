@@ -1,0 +1,176 @@
+// pic_phase.h -- the smoothed phase-space density and its KL cost (include/picstep.h: pic_phase_kl_smooth*):
+// an integer CIC deposit of every environment's particles on an nx x nv grid over [0, L] x [vmin, vmax], a per-environment
+// finishing kernel (density, KL against a target, the cotangent grid of the KL) and the gather of that grid back to the particles.
+// Float64 particles only.  Off the step path: the kernels read the state a step left.
+#pragma once
+#include "pic_device.h"
+
+namespace {
+
+constexpr int kPhaseLdsBytes = 64 << 10;      // LDS of a deposit workgroup: its band of grid rows as int64 sums
+constexpr int kPhaseMaxBins = 1024;           // bins per axis
+
+struct PhaseArgs {
+  long long N, ld;
+  long long tiles_per_wg;   // 16-byte tiles (two particles) per workgroup and lane column: a workgroup's range is contiguous
+  int nx, nv;
+  int rows;                 // grid rows (x bins) per band: rows * nv int64 fit in kPhaseLdsBytes
+  int abits, bbits;         // fractional bits of the x and v weights; a particle is 2^(abits + bbits) units
+  double L, vmin, vmax;
+  double rdx, rdv;          // 1 / dx and 1 / dv, rounded once on the host: bins are located by multiplication
+};
+
+// Bins and CIC fractions of one particle: x periodic on the bin centres (i + 1/2) dx, v on vmin + (j + 1/2) dv with the outer
+// half-bins clamped to the edge bin (fv = 0, vslope false).  false: outside [0, L] x [vmin, vmax] (or not finite), dropped as
+// np.histogram2d drops it.  Every index returned lies in its axis's range.
+__device__ __forceinline__ bool phase_locate(double x, double v, const PhaseArgs& a, int& i0, int& i1, int& j0, int& j1,
+                                             double& fx, double& fv, bool& vslope) {
+  if (!(x >= 0.0 && x <= a.L && v >= a.vmin && v <= a.vmax)) return false;
+  const double u = x * a.rdx - 0.5;
+  const double fu = floor(u);
+  fx = u - fu;
+  i0 = (int)fu;                                 // -1 .. nx-1
+  i1 = i0 + 1;
+  if (i0 < 0) i0 += a.nx;
+  if (i1 >= a.nx) i1 -= a.nx;
+  i0 = min(max(i0, 0), a.nx - 1);
+  i1 = min(max(i1, 0), a.nx - 1);
+  const double w = (v - a.vmin) * a.rdv - 0.5;
+  vslope = false;
+  fv = 0.0;
+  if (w < 0.0) {
+    j0 = j1 = 0;
+  } else {
+    const double fw = floor(w);
+    j0 = (int)fw;
+    if (j0 >= a.nv - 1) {
+      j0 = j1 = a.nv - 1;
+    } else {
+      j1 = j0 + 1;
+      fv = w - fw;
+      vslope = true;
+    }
+  }
+  return true;
+}
+
+// Deposit pass: grid (workgroups per environment, bands, environments).  Band b holds grid rows [b rows, (b + 1) rows) in LDS;
+// its workgroups read their particle range once and add the integer weights that fall into it (ds_add_u64), then flush one
+// memory-side atomic per non-zero bin into acc [env][nx][nv].  Integer sums: the result does not depend on the grid.
+__global__ __launch_bounds__(BLOCK) void phase_deposit_kernel(const double* __restrict__ x, const double* __restrict__ v,
+                                                              unsigned long long* __restrict__ acc, PhaseArgs a) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  unsigned long long* h = reinterpret_cast<unsigned long long*>(smem_raw);
+  const int env = blockIdx.z;
+  const int r0 = blockIdx.y * a.rows;
+  const int r1 = min(r0 + a.rows, a.nx);
+  const int words = (r1 - r0) * a.nv;
+  for (int i = threadIdx.x; i < words; i += BLOCK) h[i] = 0ull;
+  __syncthreads();
+  const unsigned long long ua = 1ull << a.abits, ub = 1ull << a.bbits;
+  const double sa = (double)ua, sb = (double)ub;
+  const pic_v2d* xv = reinterpret_cast<const pic_v2d*>(x + (size_t)env * a.ld);
+  const pic_v2d* vv = reinterpret_cast<const pic_v2d*>(v + (size_t)env * a.ld);
+  const long long ntiles = (a.N + 1) / 2;
+  const long long t0 = (long long)blockIdx.x * a.tiles_per_wg * BLOCK;
+  long long t1 = t0 + a.tiles_per_wg * BLOCK;
+  t1 = t1 < ntiles ? t1 : ntiles;
+  for (long long t = t0 + threadIdx.x; t < t1; t += BLOCK) {
+    const pic_v2d xt = stream_load(xv + t);
+    const pic_v2d vt = stream_load(vv + t);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      if (t * 2 + k >= a.N) break;
+      int i0, i1, j0, j1;
+      double fx, fv;
+      bool vs;
+      if (!phase_locate(xt[k], vt[k], a, i0, i1, j0, j1, fx, fv, vs)) continue;
+      const unsigned long long ax = (unsigned long long)rint(fx * sa), av = (unsigned long long)rint(fv * sb);
+      const unsigned long long wx[2] = {ua - ax, ax}, wv[2] = {ub - av, av};
+      const int ii[2] = {i0, i1}, jj[2] = {j0, j1};
+#pragma unroll
+      for (int p = 0; p < 2; ++p) {
+        if (ii[p] < r0 || ii[p] >= r1) continue;
+        const int r = ii[p] - r0;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          const unsigned long long w = wx[p] * wv[q];
+          if (w) atomicAdd(&h[r * a.nv + jj[q]], w);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  unsigned long long* g = acc + ((size_t)env * a.nx + r0) * a.nv;
+  for (int i = threadIdx.x; i < words; i += BLOCK) {
+    const unsigned long long c = h[i];
+    if (c) atomicAdd(&g[i], c);
+  }
+}
+
+struct PhaseFinishArgs {
+  unsigned long long* acc;   // [env][nb2] integer sums (cleared here behind the read)
+  int nb2;
+  double unit, norm, dxdv;   // f = ((double)sum * unit) * norm, unit = 2^-(abits + bbits), norm = n0 / dx / dv / N
+  const double* feq;         // [nb2] or [env][nb2] (feq_stride = nb2), or null
+  long long feq_stride;
+  const double* d_kl;        // [env] cotangents of the KL (read when g is wanted)
+  double* f;                 // [env][nb2] the density, or null
+  double* kl;                // [env], or null (needs feq)
+  double* g;                 // [env][nb2] d_kl dKL/df, or null (needs feq)
+};
+
+// One workgroup per environment; the KL in a fixed order (the threads' strided partial sums, then block_sum's).
+__global__ __launch_bounds__(BLOCK) void phase_finish_kernel(PhaseFinishArgs a) {
+  __shared__ double ws[WAVES];
+  const int env = blockIdx.x;
+  const size_t row = (size_t)env * a.nb2;
+  unsigned long long* c = a.acc + row;
+  const double* feq = a.feq ? a.feq + (size_t)env * a.feq_stride : nullptr;
+  const double d = a.g ? a.d_kl[env] : 0.0;
+  double k = 0.0;
+  for (int i = threadIdx.x; i < a.nb2; i += BLOCK) {
+    const double f = ((double)c[i] * a.unit) * a.norm;
+    c[i] = 0ull;
+    if (a.f) a.f[row + i] = f;
+    if (feq) {
+      double gi = 0.0;
+      if (f > 0.0) {
+        const double r = log(f / (feq[i] + 1e-12));
+        k += f * r;
+        gi = d * ((r + 1.0) * a.dxdv);
+      }
+      if (a.g) a.g[row + i] = gi;
+    }
+  }
+  if (a.kl) {
+    const double K = block_sum<WAVES>(k, ws);
+    if (threadIdx.x == 0) a.kl[env] = K * a.dxdv;
+  }
+}
+
+// The gather: one thread per particle, dKL/dx and dKL/dv of the unquantised CIC weights against g (cx = norm / dx,
+// cv = norm / dv), into dense rows gx, gv [env][N].
+__global__ __launch_bounds__(BLOCK) void phase_vjp_kernel(const double* __restrict__ x, const double* __restrict__ v,
+                                                          const double* __restrict__ g, PhaseArgs a, double cx, double cv,
+                                                          double* __restrict__ gx, double* __restrict__ gv) {
+  const int env = blockIdx.y;
+  const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= a.N) return;
+  const double xs = x[(size_t)env * a.ld + i], vs = v[(size_t)env * a.ld + i];
+  int i0, i1, j0, j1;
+  double fx, fv;
+  bool vsl;
+  double dx = 0.0, dv = 0.0;
+  if (phase_locate(xs, vs, a, i0, i1, j0, j1, fx, fv, vsl)) {
+    const double* gr = g + (size_t)env * a.nx * a.nv;
+    const double g00 = gr[(size_t)i0 * a.nv + j0], g01 = gr[(size_t)i0 * a.nv + j1];
+    const double g10 = gr[(size_t)i1 * a.nv + j0], g11 = gr[(size_t)i1 * a.nv + j1];
+    dx = cx * ((g10 - g00) * (1.0 - fv) + (g11 - g01) * fv);
+    if (vsl) dv = cv * ((g01 - g00) * (1.0 - fx) + (g11 - g10) * fx);
+  }
+  gx[(size_t)env * a.N + i] = dx;
+  gv[(size_t)env * a.N + i] = dv;
+}
+
+}  // namespace

@@ -308,6 +308,68 @@ class BatchedPIC:
         reduction on the device, one value per environment read back (pic_phase_kl)."""
         return self._h.phase_kl(feq, vmin, vmax)
 
+    # -- smoothed phase-space density and KL (pic_phase_kl_smooth*, DESIGN.md 7g) -----------------------
+    def _phase_call(self, feq, arrays):
+        """(on_device, feq as float64 [.., nx, nv] in the memory of the call, its address, per-environment flag, nx, nv, other
+        arrays as float64 in that memory): CUDA tensors in, CUDA tensors out, else NumPy."""
+        given = [a for a in [feq] + list(arrays) if a is not None]
+        on_device = any(hasattr(a, "is_cuda") and a.is_cuda for a in given)
+        if on_device:
+            import torch
+            conv = lambda a: torch.as_tensor(a, dtype=torch.float64, device=f"cuda:{self.device}").contiguous()  # noqa: E731
+        else:
+            conv = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64))  # noqa: E731
+        f = conv(feq)
+        if f.ndim == 3 and f.shape[0] != self.num_envs or f.ndim not in (2, 3):
+            raise ValueError(f"feq must be [nx, nv] or [num_envs, nx, nv], not {list(f.shape)}")
+        out = [None if a is None else conv(a) for a in arrays]
+        if on_device and getattr(self, "_torch_stream", None) is None:
+            import torch
+            torch.cuda.current_stream(self.device).synchronize()
+        return on_device, f, self._addr(f), int(f.ndim == 3), int(f.shape[-2]), int(f.shape[-1]), out
+
+    @staticmethod
+    def _addr(a):
+        return 0 if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data)
+
+    def phase_density_smooth(self, bins, vmin: float = -25.0, vmax: float = 25.0):
+        """The smoothed phase-space density f~ [num_envs, nx, nv] of the current particles: CIC weights on the
+        bin centres of [0, L] x [vmin, vmax] (periodic in x, the outer half-bins of v clamped), estimate_f's normalisation and
+        mass.  bins: int or (nx, nv), 1..1024 each.  Bitwise reproducible; a target feq for kl_smooth built from an initial state."""
+        nx, nv = (int(bins), int(bins)) if np.isscalar(bins) else (int(bins[0]), int(bins[1]))
+        f = np.empty((self.num_envs, nx, nv))
+        self._h.phase_kl_smooth(nx, nv, vmin, vmax, 0, 0, _abi.PIC_HOST, _abi.PIC_HOST, 0, f.ctypes.data)
+        return f
+
+    def kl_smooth(self, feq, vmin: float = -25.0, vmax: float = 25.0):
+        """KL~ of every environment's smoothed density against feq [nx, nv] (shared) or [num_envs, nx, nv] ->
+        [num_envs]: sum rel_entr(f~, feq + 1e-12) dx dv, estimate_KL_divergence's formula.  NumPy, or a float64 CUDA tensor if
+        feq is one."""
+        dev, f, fa, per, nx, nv, _ = self._phase_call(feq, [])
+        kl = self._empty(dev, (self.num_envs,))
+        kind = _abi.PIC_DEVICE if dev else _abi.PIC_HOST
+        self._h.phase_kl_smooth(nx, nv, vmin, vmax, fa, per, kind, kind, self._addr(kl), 0)
+        return kl
+
+    def kl_smooth_grad(self, feq, d_kl=None, vmin: float = -25.0, vmax: float = 25.0):
+        """Gradient of sum_e d_kl[e] KL~_e (d_kl [num_envs], None = ones) with respect to the current particles -> (g_x, g_v)
+        [num_envs, N]: the almost-everywhere derivative of DESIGN.md 7g.  NumPy, or float64 CUDA tensors if feq or d_kl is one."""
+        if d_kl is None:
+            d_kl = np.ones(self.num_envs)
+        dev, f, fa, per, nx, nv, (d,) = self._phase_call(feq, [d_kl])
+        if tuple(d.shape) != (self.num_envs,):
+            raise ValueError(f"d_kl must be [num_envs], not {list(d.shape)}")
+        gx, gv = self._empty(dev, (self.num_envs, self.N)), self._empty(dev, (self.num_envs, self.N))
+        kind = _abi.PIC_DEVICE if dev else _abi.PIC_HOST
+        self._h.phase_kl_smooth_vjp(nx, nv, vmin, vmax, fa, per, kind, self._addr(d), kind, self._addr(gx), self._addr(gv))
+        return gx, gv
+
+    def _empty(self, on_device, shape):
+        if on_device:
+            import torch
+            return torch.empty(shape, dtype=torch.float64, device=f"cuda:{self.device}")
+        return np.empty(shape)
+
     # -- rollout recorder (include/picstep.h: pic_record_*) ----------------------------------------
     def start_recording(self, stride: int = 1, modes: Optional[int] = None, x_bins: int = 0, v_bins: int = 0, phase_bins=None,
                         vmin: float = -25.0, vmax: float = 25.0, feq=None, capacity: int = 4096, phase_dx: float = 0.0,
