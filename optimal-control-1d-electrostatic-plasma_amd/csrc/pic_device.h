@@ -280,7 +280,9 @@ __device__ __forceinline__ T wrap_periodic(T q, T L, unsigned& bad) {
   // Wave-uniform fast path: where every lane of the wave holds 0 < q < L the result is q (two compares and a scalar branch instead
   // of the select chain below: 13.5 VALU per wrap in float64).  Zero of either sign, NaN, inf and every position outside the box
   // take the chain, as does the whole wave of such a lane -- a particle within one sub-stage's drift of a boundary.
-  if (__all(q > T(0) && q < L)) return q;
+  // (the ballot of the lanes OUTSIDE the open box is compared with zero in scalar registers: __all() turns the predicate into a
+  // lane value and compares that again, two VALU more per wrap)
+  if (__builtin_amdgcn_ballot_w64(!(q > T(0) && q < L)) == 0) return q;
   // the three near ranges as selects (a particle moves a small fraction of L per sub-stage)
   T up = q + L;                       // q in [-L, 0]
   up = (up >= L) ? T(0) : up;         // tiny negative q: q + L rounds to L, the second mod gives 0

@@ -257,6 +257,7 @@ __global__ __launch_bounds__(BLOCK) void sweep_kernel(typename P::X* __restrict_
   constexpr bool kGather = (kIsB || kIsC || kIsD || kScheme);
   constexpr bool kStore = ((kGather && STAGE != ST_C_RO) || STAGE == ST_REFRESH);
   constexpr bool kStoreV = kGather && STAGE != ST_C_RO;
+  constexpr bool kAhead = !kStore;                                             // a loop without stores requests its tiles one ahead
   constexpr bool kReadV = (STAGE != ST_PROBE);
   constexpr bool kFirst = (STAGE != ST_D2 && STAGE != ST_D2_RC && STAGE != ST_VK);   // deposits into the first LDS mesh (-> acc_out)
   constexpr bool kDual = (kIsD || STAGE == ST_REFRESH || STAGE == ST_B2);      // ... into the second one (-> acc_out2)
@@ -360,6 +361,17 @@ __global__ __launch_bounds__(BLOCK) void sweep_kernel(typename P::X* __restrict_
   const StreamOut xout(xe + begin), vout(ve + begin);
   while (i + VEC <= end) {
     PIC_STAMP_LOADS(8 + 2 * tile);
+    // A sweep that stores nothing requests its NEXT tile here, into a second pair of registers, before it pushes this one: the
+    // loads run under the tile's arithmetic inside the wave, not only under that of the other waves.  Unconditional, from a
+    // clamped address behind the last tile (as the first tile's: one line for the whole wave).  With no store in the loop the
+    // compiler counts the loads exactly: the next tile's stay in flight under this tile's arithmetic.
+    [[maybe_unused]] XV xv_next;
+    [[maybe_unused]] VV vv_next = {};
+    if constexpr (kAhead) {
+      const long long i_next = (i + step + VEC <= end) ? i + step : 0;
+      xv_next = stream_load(reinterpret_cast<const XV*>(xe + i_next));
+      if (kReadV) vv_next = stream_load(reinterpret_cast<const VV*>(ve + i_next));
+    }
     typename P::X* xs = reinterpret_cast<typename P::X*>(&xv);
     typename P::V* vs = reinterpret_cast<typename P::V*>(&vv);
 #pragma unroll
@@ -376,7 +388,10 @@ __global__ __launch_bounds__(BLOCK) void sweep_kernel(typename P::X* __restrict_
     PIC_STAMP(9 + 2 * tile);
     ++tile;
     i += step;
-    if (i + VEC <= end) {
+    if constexpr (kAhead) {
+      xv = xv_next;
+      vv = vv_next;
+    } else if (i + VEC <= end) {
       xv = stream_load(reinterpret_cast<const XV*>(xe + i));
       if (kReadV) vv = stream_load(reinterpret_cast<const VV*>(ve + i));
     }
