@@ -520,6 +520,32 @@ int pic_tape_walk_end(pic_handle* h, const void* cot_x0, const void* cot_v0, con
  * d_ext and d_actions, or a bad mem_kind: PIC_EINVAL.  T = 0: d_x / d_v are d_x0 / d_v0 and nothing else is written. */
 int pic_tape_tangent(pic_handle* h, int K, const double* d_ext, const double* d_actions, const void* d_x0, const void* d_v0,
                      int mem_kind, double* d_hist, void* d_x, void* d_v, double* d_E_mesh);
+/* The smoothed phase-space KL of pic_phase_kl_smooth after EVERY taped step, forward and adjoint (additive to
+ * ABI 5): with it the running cost sum_t KL~_t of the reference's trainers is differentiable next to the energy traces.
+ * pic_tape_kl_start attaches it to an open tape that holds no step and no KL yet (else PIC_ESTATE).  spec is checked as
+ * pic_phase_kl_smooth checks it and needs feq (else PIC_EINVAL); the tape takes its own device copy of feq, so the caller's may
+ * go away.  It allocates, with nb = nx nv, E = num_envs and every part rounded up to 256 bytes,
+ *     8 ((feq_per_env ? E : 1) nb  +  E nb  +  E nb  +  max_steps E  +  max_steps E)   bytes
+ * (the target, the integer sums, the cotangent grid, the KL trace and its cotangents), which count in pic_tape_info.bytes and
+ * against budget_bytes and are freed by pic_tape_stop.  If they do not fit, or take the tape past budget_bytes: PIC_ENOMEM, and
+ * the tape stays usable without a KL.
+ * From then on every stepping call is cut behind every step (as the recorder cuts with stride 1: particles, fields and energies
+ * are bit for bit those of the same calls without a KL, or without a tape) and two kernels write kl[t][e], bit for bit what
+ * pic_phase_kl_smooth returns when called after step t.  pic_tape_kl copies the trace of the T steps taped so far,
+ * kl [T][num_envs] in mem_kind memory (PIC_HOST waits; PIC_DEVICE is asynchronous on the handle's stream).
+ * pic_tape_kl_cot stores cotangents on it: cot_kl [nsteps][num_envs] in mem_kind memory for steps first_step ..
+ * first_step + nsteps - 1, or NULL to clear those rows.  Rows persist until they are overwritten or cleared, and
+ * pic_tape_kl_start leaves all clear.  Every later pic_tape_backward, pic_tape_backward_feedback and pic_tape_walk_step adds
+ * cot_kl[t] dKL~_t/d(x, v) to the adjoint state when it reverses a step t that holds a row (three more kernels per such step,
+ * counted in `launches`; the derivative is pic_phase_kl_smooth_vjp's); a step without a row costs nothing, so a tape with a KL
+ * and no rows set gives the gradients of a plain tape bit for bit.  The call does not abandon a walk, but rows of steps a walk
+ * in progress has already reversed are refused with PIC_ESTATE; rows outside [0, T) or a bad mem_kind are PIC_EINVAL; no tape
+ * with a KL open is PIC_ESTATE (pic_tape_kl too).  Gradients with KL cotangents are bitwise reproducible and do not depend on
+ * blocks_per_env, the checkpoint interval, the schedule or the other environments of the batch.
+ * Forward mode of the KL is not built: pic_tape_tangent works on such a tape and ignores the KL. */
+int pic_tape_kl_start(pic_handle* h, const pic_phase_spec* spec);
+int pic_tape_kl(pic_handle* h, int mem_kind, double* kl);
+int pic_tape_kl_cot(pic_handle* h, const double* cot_kl, int mem_kind, int64_t first_step, int64_t nsteps);
 
 int pic_sync(pic_handle* h);
 /* Number of particle positions found non-finite or out of range by the last sweeps (0 = healthy).  Counts the state's

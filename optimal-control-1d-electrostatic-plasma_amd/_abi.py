@@ -148,6 +148,9 @@ SIGNATURES = {
     "pic_tape_walk_step": [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _i64p],
     "pic_tape_walk_end": [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp],
     "pic_tape_tangent": [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp],
+    "pic_tape_kl_start": [_vp, C.POINTER(PicPhaseSpec)],
+    "pic_tape_kl": [_vp, C.c_int, _vp],
+    "pic_tape_kl_cot": [_vp, _vp, C.c_int, C.c_int64, C.c_int64],
     "pic_set_stream": [_vp, _vp],
     "pic_own_stream": [_vp],
     "pic_schedule": [_vp],
@@ -765,6 +768,20 @@ class Handle:
         """pic_tape_tangent on device pointers (int, 0 = NULL); asynchronous on the handle's stream."""
         p = [None if not q else _ptr(int(q)) for q in (d_ext, d_actions, d_x0, d_v0, hist, x, v, E_mesh)]
         self._chk(self.lib.pic_tape_tangent(self._h, int(K), p[0], p[1], p[2], p[3], PIC_DEVICE, p[4], p[5], p[6], p[7]))
+
+    def tape_kl_start(self, nx, nv, vmin, vmax, feq, feq_per_env, feq_kind):
+        """pic_tape_kl_start: feq an address in feq_kind memory (the tape copies it)."""
+        spec = PicPhaseSpec(int(nx), int(nv), float(vmin), float(vmax), int(feq) or None, int(feq_per_env), int(feq_kind))
+        self._chk(self.lib.pic_tape_kl_start(self._h, C.byref(spec)))
+
+    def tape_kl(self, mem_kind, kl):
+        """pic_tape_kl into the address kl ([T][num_envs] float64 in mem_kind memory)."""
+        self._chk(self.lib.pic_tape_kl(self._h, int(mem_kind), _ptr(int(kl)) if kl else None))
+
+    def tape_kl_cot(self, cot_kl, mem_kind, first_step, nsteps):
+        """pic_tape_kl_cot: cot_kl an address (int, 0 = NULL: clear the rows) in mem_kind memory."""
+        self._chk(self.lib.pic_tape_kl_cot(self._h, _ptr(int(cot_kl)) if cot_kl else None, int(mem_kind), int(first_step),
+                                           int(nsteps)))
 
     def stream_probe(self, repeats=10):
         g = C.c_double()

@@ -1,6 +1,7 @@
 // pic_phase.h -- the smoothed phase-space density and its KL cost (include/picstep.h: pic_phase_kl_smooth*):
 // an integer CIC deposit of every environment's particles on an nx x nv grid over [0, L] x [vmin, vmax], a per-environment
-// finishing kernel (density, KL against a target, the cotangent grid of the KL) and the gather of that grid back to the particles.
+// finishing kernel (density, KL against a target, the cotangent grid of the KL) and the gather of that grid back to the particles
+// (into dense rows, or added to the adjoint state of a tape: DESIGN.md 7h).
 // Float64 particles only.  Off the step path: the kernels read the state a step left.
 #pragma once
 #include "pic_device.h"
@@ -149,6 +150,23 @@ __global__ __launch_bounds__(BLOCK) void phase_finish_kernel(PhaseFinishArgs a) 
   }
 }
 
+// dKL/dx and dKL/dv of one particle against an environment's cotangent grid gr [nx][nv]: the four bins of phase_locate with the
+// slopes of the unquantised CIC weights (cx = norm / dx, cv = norm / dv); 0 for a dropped particle, 0 in v in a clamped half-bin.
+__device__ __forceinline__ void phase_gather(double xs, double vs, const double* __restrict__ gr, const PhaseArgs& a, double cx,
+                                             double cv, double& dx, double& dv) {
+  int i0, i1, j0, j1;
+  double fx, fv;
+  bool vsl;
+  dx = 0.0;
+  dv = 0.0;
+  if (phase_locate(xs, vs, a, i0, i1, j0, j1, fx, fv, vsl)) {
+    const double g00 = gr[(size_t)i0 * a.nv + j0], g01 = gr[(size_t)i0 * a.nv + j1];
+    const double g10 = gr[(size_t)i1 * a.nv + j0], g11 = gr[(size_t)i1 * a.nv + j1];
+    dx = cx * ((g10 - g00) * (1.0 - fv) + (g11 - g01) * fv);
+    if (vsl) dv = cv * ((g01 - g00) * (1.0 - fx) + (g11 - g10) * fx);
+  }
+}
+
 // The gather: one thread per particle, dKL/dx and dKL/dv of the unquantised CIC weights against g (cx = norm / dx,
 // cv = norm / dv), into dense rows gx, gv [env][N].
 __global__ __launch_bounds__(BLOCK) void phase_vjp_kernel(const double* __restrict__ x, const double* __restrict__ v,
@@ -158,19 +176,46 @@ __global__ __launch_bounds__(BLOCK) void phase_vjp_kernel(const double* __restri
   const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
   if (i >= a.N) return;
   const double xs = x[(size_t)env * a.ld + i], vs = v[(size_t)env * a.ld + i];
-  int i0, i1, j0, j1;
-  double fx, fv;
-  bool vsl;
-  double dx = 0.0, dv = 0.0;
-  if (phase_locate(xs, vs, a, i0, i1, j0, j1, fx, fv, vsl)) {
-    const double* gr = g + (size_t)env * a.nx * a.nv;
-    const double g00 = gr[(size_t)i0 * a.nv + j0], g01 = gr[(size_t)i0 * a.nv + j1];
-    const double g10 = gr[(size_t)i1 * a.nv + j0], g11 = gr[(size_t)i1 * a.nv + j1];
-    dx = cx * ((g10 - g00) * (1.0 - fv) + (g11 - g01) * fv);
-    if (vsl) dv = cv * ((g01 - g00) * (1.0 - fx) + (g11 - g10) * fx);
-  }
+  double dx, dv;
+  phase_gather(xs, vs, g + (size_t)env * a.nx * a.nv, a, cx, cv, dx, dv);
   gx[(size_t)env * a.N + i] = dx;
   gv[(size_t)env * a.N + i] = dv;
+}
+
+// The same gather added to the adjoint state of a taped rollout (pic_tape_kl_cot): lx, lv [env][ld] +=
+// dKL/dx, dKL/dv at the replayed particles x, v [env][ld].  One 16-byte tile (two particles) per lane, as the deposit reads
+// them (rows start on 16 bytes: ld is even); the odd last particle of a row goes alone, so the padding is never written.
+// Grid: (tiles / BLOCK, environments).
+__global__ __launch_bounds__(BLOCK) void phase_vjp_add_kernel(const double* __restrict__ x, const double* __restrict__ v,
+                                                              const double* __restrict__ g, PhaseArgs a, double cx, double cv,
+                                                              double* __restrict__ lx, double* __restrict__ lv) {
+  const int env = blockIdx.y;
+  const long long t = (long long)blockIdx.x * BLOCK + threadIdx.x;
+  const long long i = 2 * t;
+  if (i >= a.N) return;
+  const size_t row = (size_t)env * a.ld;
+  const double* gr = g + (size_t)env * a.nx * a.nv;
+  if (i + 1 < a.N) {
+    const pic_v2d xt = stream_load(reinterpret_cast<const pic_v2d*>(x + row) + t);
+    const pic_v2d vt = stream_load(reinterpret_cast<const pic_v2d*>(v + row) + t);
+    pic_v2d* px = reinterpret_cast<pic_v2d*>(lx + row) + t;
+    pic_v2d* pv = reinterpret_cast<pic_v2d*>(lv + row) + t;
+    pic_v2d ax = *px, av = *pv;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      double dx, dv;
+      phase_gather(xt[k], vt[k], gr, a, cx, cv, dx, dv);
+      ax[k] = ax[k] + dx;
+      av[k] = av[k] + dv;
+    }
+    *px = ax;
+    *pv = av;
+  } else {
+    double dx, dv;
+    phase_gather(x[row + i], v[row + i], gr, a, cx, cv, dx, dv);
+    lx[row + i] = lx[row + i] + dx;
+    lv[row + i] = lv[row + i] + dv;
+  }
 }
 
 }  // namespace

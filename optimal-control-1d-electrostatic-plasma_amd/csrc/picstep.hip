@@ -205,6 +205,17 @@ struct Tape {
   DeviceBuf<void> tan_block;
   int tan_k = 0;
   size_t tan_bytes = 0;
+  // the per-step smoothed KL (pic_tape_kl_*): one block allocated by pic_tape_kl_start, counts in `bytes`;
+  // kl_feq .. kl_cot are views into it
+  DeviceBuf<void> kl_block;
+  bool kl = false;                    // a KL is attached: advance cuts behind every step and writes its row of kl_trace
+  pic_phase_spec kl_spec{};           // the caller's spec with feq = kl_feq (device memory)
+  double* kl_feq = nullptr;           // [nx][nv] or [env][nx][nv] the tape's copy of the target
+  unsigned long long* kl_acc = nullptr;   // [env][nx][nv] integer sums, zero between uses
+  double* kl_g = nullptr;             // [env][nx][nv] cotangent grid of the step being reversed
+  double* kl_trace = nullptr;         // [max_steps][env] KL~ after every step
+  double* kl_cot = nullptr;           // [max_steps][env] cotangents on it (pic_tape_kl_cot)
+  std::vector<char> kl_flag;          // [max_steps] per step: kl_cot holds a row for it
 };
 
 struct pic_handle {
@@ -1695,10 +1706,13 @@ static int tape_checkpoint(pic_handle* h, int64_t c) {
 }
 
 // advance_steps, cut into parts where the recorder or an open tape needs the state between two steps.  A part runs up to the
-// nearest of the next recorded step, the next checkpoint step and the end of the call; such a step therefore ends like the last
+// nearest of the next recorded step, the next checkpoint step (every step of a tape with a KL attached, pic_tape_kl_start) and
+// the end of the call; such a step therefore ends like the last
 // step of a call (full sweep D and a solve launch of its own; resident schedule: the end of a launch) -- stepping call by call
 // gives the same bits.  Behind a part come the record kernels of a recorded step, then the tape's copy of the
 // state after a checkpoint step.  Under a tape each part's external fields go on the tape first.
+static int tape_kl_enqueue(pic_handle* h);      // (defined with the smoothed KL's entries)
+
 static int advance(pic_handle* h, const StepControl& sc, int nsteps, double* hist, void* snap = nullptr) {
   Recorder& r = h->rec;
   Tape& t = h->tape;
@@ -1708,6 +1722,7 @@ static int advance(pic_handle* h, const StepControl& sc, int nsteps, double* his
     int64_t n = nsteps - done;
     if (r.on) n = std::min<int64_t>(n, r.stride - r.k % r.stride);
     if (t.on) n = std::min<int64_t>(n, t.every - t.steps % t.every);
+    if (t.on && t.kl) n = 1;          // the KL of every step: the recorder's cut with stride 1
     const StepControl part = sc.after(done, E);
     int rc = t.on && part.fb.M == 0 ? tape_record_ext(h, part, (int)n) : PIC_OK;
     if (rc) return rc;
@@ -1729,6 +1744,10 @@ static int advance(pic_handle* h, const StepControl& sc, int nsteps, double* his
       made.ctl.basis = sc.ctl.basis; made.ctl.M = sc.ctl.M; made.ctl.act = part.fb.act_hist;
       made.act_step = (long long)E * 2 * sc.ctl.M;
       rc = tape_record_ext(h, made, (int)n);
+      if (rc) return rc;
+    }
+    if (t.kl) {
+      rc = tape_kl_enqueue(h);        // row t.steps of the trace
       if (rc) return rc;
     }
     t.steps += n;
@@ -2577,14 +2596,15 @@ static PhaseArgs phase_args(const pic_handle* h, const pic_phase_spec* s, dim3& 
   return a;
 }
 
-// The deposit of the current particles and the finishing kernel behind it, on the handle's stream.  acc: [env][nx][nv] zero
-// (left zero); feq: device memory or null; d_kl, f, kl, g: device memory or null (PhaseFinishArgs).
-static hipError_t phase_enqueue(pic_handle* h, const pic_phase_spec* s, unsigned long long* acc, const double* feq,
-                                const double* d_kl, double* f, double* kl, double* g, PhaseArgs& a) {
+// The deposit of the particles x, v [env][ld] (the handle's, or a replayed state of the tape) and the finishing kernel behind
+// it, on the handle's stream.  acc: [env][nx][nv] zero (left zero); feq: device memory or null; d_kl, f, kl, g: device memory or
+// null (PhaseFinishArgs).
+static hipError_t phase_enqueue(pic_handle* h, const pic_phase_spec* s, const double* x, const double* v, unsigned long long* acc,
+                                const double* feq, const double* d_kl, double* f, double* kl, double* g, PhaseArgs& a) {
   dim3 grid;
   a = phase_args(h, s, grid);
   hipLaunchKernelGGL(phase_deposit_kernel, grid, dim3(BLOCK), (size_t)a.rows * a.nv * sizeof(unsigned long long), h->stream,
-                     (const double*)h->x.get(), (const double*)h->v, acc, a);
+                     x, v, acc, a);
   const double dx = h->cfg.L / s->nx, dv = (s->vmax - s->vmin) / s->nv;
   PhaseFinishArgs fa{};
   fa.acc = acc; fa.nb2 = s->nx * s->nv;
@@ -2640,7 +2660,7 @@ int pic_phase_kl_smooth(pic_handle* h, const pic_phase_spec* s, int mem_kind, do
   if (e == hipSuccess) e = phase_input(h, s->feq, s->feq_mem_kind, (s->feq_per_env ? E : 1) * nb2 * sizeof(double), dfeq, &feq);
   if (e == hipSuccess) e = phase_output(f, mem_kind, (size_t)E * nb2 * sizeof(double), false, df, &fo);
   if (e == hipSuccess) e = phase_output(kl, mem_kind, (size_t)E * sizeof(double), false, dkl, &klo);
-  if (e == hipSuccess) e = phase_enqueue(h, s, acc, feq, nullptr, fo, klo, nullptr, a);
+  if (e == hipSuccess) e = phase_enqueue(h, s, (const double*)h->x.get(), (const double*)h->v, acc, feq, nullptr, fo, klo, nullptr, a);
   if (e == hipSuccess && f && fo != f) e = hipMemcpyAsync(f, fo, (size_t)E * nb2 * sizeof(double), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess && kl && klo != kl) e = hipMemcpyAsync(kl, klo, (size_t)E * sizeof(double), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
@@ -2667,7 +2687,7 @@ int pic_phase_kl_smooth_vjp(pic_handle* h, const pic_phase_spec* s, const double
   if (e == hipSuccess) e = alloc(dg, (size_t)E * nb2 * sizeof(double));
   if (e == hipSuccess) e = phase_output(g_x, mem_kind, pbytes, true, dgx, &gx);
   if (e == hipSuccess) e = phase_output(g_v, mem_kind, pbytes, true, dgv, &gv);
-  if (e == hipSuccess) e = phase_enqueue(h, s, acc, feq, cot, nullptr, nullptr, dg, a);
+  if (e == hipSuccess) e = phase_enqueue(h, s, (const double*)h->x.get(), (const double*)h->v, acc, feq, cot, nullptr, nullptr, dg, a);
   if (e == hipSuccess) {
     const double dx = h->cfg.L / s->nx, dv = (s->vmax - s->vmin) / s->nv;
     const double norm = h->cfg.n0 / dx / dv / (double)h->cfg.N;
@@ -2680,6 +2700,125 @@ int pic_phase_kl_smooth_vjp(pic_handle* h, const pic_phase_spec* s, const double
   if (e == hipSuccess && g_v && gv != g_v) e = hipMemcpyAsync(g_v, gv, pbytes, hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   if (e != hipSuccess) return fail(h, PIC_EHIP, std::string("pic_phase_kl_smooth_vjp: ") + hipGetErrorString(e));
+  return PIC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The smoothed KL of every taped step (include/picstep.h: pic_tape_kl_*; hooks: advance, walk_reverse)
+// ---------------------------------------------------------------------------------------------
+// bytes of the KL's block on a tape of max_steps steps: feq, acc, g, trace, cot; *offs: the parts' offsets
+static size_t tape_kl_layout(const pic_handle* h, const pic_phase_spec* s, int64_t max_steps, size_t (&offs)[5]) {
+  const size_t E = h->cfg.num_envs, nb2 = (size_t)s->nx * s->nv, rows = (size_t)max_steps * E * sizeof(double);
+  const size_t sizes[5] = {(s->feq_per_env ? E : 1) * nb2 * sizeof(double), E * nb2 * sizeof(unsigned long long),
+                           E * nb2 * sizeof(double), rows, rows};
+  size_t at = 0;
+  for (int i = 0; i < 5; ++i) {
+    offs[i] = at;
+    at += (sizes[i] + 255) & ~(size_t)255;
+  }
+  return at;
+}
+
+int pic_tape_kl_start(pic_handle* h, const pic_phase_spec* s) {
+  const char* who = "pic_tape_kl_start";
+  if (!h) return PIC_EINVAL;
+  Tape& t = h->tape;
+  if (!t.on) return fail(h, PIC_ESTATE, std::string(who) + ": no tape is open (pic_tape_start)");
+  if (t.kl) return fail(h, PIC_ESTATE, std::string(who) + ": the tape has a KL already");
+  if (t.steps != 0) return fail(h, PIC_ESTATE, std::string(who) + ": the tape holds steps already (attach the KL before the first)");
+  int rc = phase_check(h, s, PIC_HOST, who);
+  if (rc) return rc;
+  if (!s->feq) return fail(h, PIC_EINVAL, std::string(who) + ": needs spec->feq");
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  size_t offs[5];
+  const size_t bytes = tape_kl_layout(h, s, t.max_steps, offs);
+  if (t.budget > 0 && t.bytes + bytes > (size_t)t.budget)
+    return fail(h, PIC_ENOMEM, std::string(who) + ": the KL's memory (" + std::to_string(bytes) +
+                                   " bytes) would take the tape past budget_bytes (pic_tape_start)");
+  DeviceBuf<void> block;
+  if (alloc(block, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(h, PIC_ENOMEM, std::string(who) + ": the KL's memory (" + std::to_string(bytes) + " bytes) does not fit on the device");
+  }
+  char* b = static_cast<char*>(block.get());
+  const size_t fbytes = (s->feq_per_env ? (size_t)h->cfg.num_envs : 1) * s->nx * s->nv * sizeof(double);
+  hipError_t e = hipMemcpyAsync(b + offs[0], s->feq, fbytes,
+                                s->feq_mem_kind == PIC_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(b + offs[1], 0, offs[2] - offs[1], h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);          // (the caller's feq may go away behind this call)
+  if (e != hipSuccess) return fail(h, PIC_EHIP, std::string(who) + ": " + hipGetErrorString(e));
+  t.kl_block = std::move(block);
+  t.kl_feq = (double*)(b + offs[0]); t.kl_acc = (unsigned long long*)(b + offs[1]); t.kl_g = (double*)(b + offs[2]);
+  t.kl_trace = (double*)(b + offs[3]); t.kl_cot = (double*)(b + offs[4]);
+  t.kl_spec = *s;
+  t.kl_spec.feq = t.kl_feq;
+  t.kl_spec.feq_mem_kind = PIC_DEVICE;
+  t.kl_flag.assign((size_t)t.max_steps, 0);
+  t.bytes += bytes;
+  t.kl = true;
+  return PIC_OK;
+}
+
+// KL~ of the handle's particles into row t.steps of the trace (advance, behind the step that is about to be counted)
+static int tape_kl_enqueue(pic_handle* h) {
+  Tape& t = h->tape;
+  PhaseArgs a;
+  HIPCHK(h, phase_enqueue(h, &t.kl_spec, (const double*)h->x.get(), (const double*)h->v, t.kl_acc, t.kl_feq, nullptr, nullptr,
+                          t.kl_trace + (size_t)t.steps * h->cfg.num_envs, nullptr, a));
+  return PIC_OK;
+}
+
+// the KL's part of reverse step s (walk_reverse): lambda += k-bar_s dKL~/d(x', v') at the replayed state x', v' the step left
+static int tape_kl_reverse(pic_handle* h, int64_t s, const double* x, const double* v, double* lx, double* lv) {
+  Tape& t = h->tape;
+  const int E = h->cfg.num_envs;
+  const pic_phase_spec& sp = t.kl_spec;
+  PhaseArgs a;
+  HIPCHK(h, phase_enqueue(h, &sp, x, v, t.kl_acc, t.kl_feq, t.kl_cot + (size_t)s * E, nullptr, nullptr, t.kl_g, a));
+  const double dx = h->cfg.L / sp.nx, dv = (sp.vmax - sp.vmin) / sp.nv;
+  const double norm = h->cfg.n0 / dx / dv / (double)h->cfg.N;
+  const long long ntiles = (h->cfg.N + 1) / 2;
+  const dim3 grid((unsigned)((ntiles + BLOCK - 1) / BLOCK), (unsigned)E);
+  hipLaunchKernelGGL(phase_vjp_add_kernel, grid, dim3(BLOCK), 0, h->stream, x, v, (const double*)t.kl_g, a, norm * a.rdx,
+                     norm * a.rdv, lx, lv);
+  t.launches += 3;
+  return PIC_OK;
+}
+
+int pic_tape_kl(pic_handle* h, int mem_kind, double* kl) {
+  const char* who = "pic_tape_kl";
+  if (!h) return PIC_EINVAL;
+  Tape& t = h->tape;
+  if (!t.on || !t.kl) return fail(h, PIC_ESTATE, std::string(who) + ": no tape with a KL is open (pic_tape_kl_start)");
+  if ((mem_kind != PIC_HOST && mem_kind != PIC_DEVICE) || !kl) return fail(h, PIC_EINVAL, std::string(who) + ": bad mem_kind or null kl");
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (t.steps == 0) return PIC_OK;
+  const bool host = mem_kind == PIC_HOST;
+  HIPCHK(h, hipMemcpyAsync(kl, t.kl_trace, (size_t)t.steps * h->cfg.num_envs * sizeof(double),
+                           host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
+  if (host) HIPCHK(h, hipStreamSynchronize(h->stream));
+  return PIC_OK;
+}
+
+int pic_tape_kl_cot(pic_handle* h, const double* cot_kl, int mem_kind, int64_t first_step, int64_t nsteps) {
+  const char* who = "pic_tape_kl_cot";
+  if (!h) return PIC_EINVAL;
+  Tape& t = h->tape;
+  if (!t.on || !t.kl) return fail(h, PIC_ESTATE, std::string(who) + ": no tape with a KL is open (pic_tape_kl_start)");
+  if (mem_kind != PIC_HOST && mem_kind != PIC_DEVICE) return fail(h, PIC_EINVAL, std::string(who) + ": bad mem_kind");
+  if (first_step < 0 || nsteps < 0 || first_step > t.steps || nsteps > t.steps - first_step)
+    return fail(h, PIC_EINVAL, std::string(who) + ": rows outside the " + std::to_string(t.steps) + " steps taped so far");
+  if (nsteps == 0) return PIC_OK;
+  if (t.walk && first_step + nsteps - 1 > t.wnext)
+    return fail(h, PIC_ESTATE, std::string(who) + ": the walk in progress has reversed step " + std::to_string(first_step + nsteps - 1) +
+                                   " already");
+  if (cot_kl) {
+    HIPCHK(h, hipSetDevice(h->cfg.device_id));
+    const size_t E = h->cfg.num_envs;
+    HIPCHK(h, hipMemcpyAsync(t.kl_cot + (size_t)first_step * E, cot_kl, (size_t)nsteps * E * sizeof(double),
+                             mem_kind == PIC_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->stream));
+  }
+  std::fill(t.kl_flag.begin() + first_step, t.kl_flag.begin() + first_step + nsteps, cot_kl ? 1 : 0);
   return PIC_OK;
 }
 
@@ -3111,6 +3250,11 @@ static int walk_reverse(pic_handle* h, const WalkCot& c, const AdjArgs& a, const
   const AdjStep st{x, x + part, t.F + (size_t)i * 3 * mesh, (long long)mesh};
   const double* cot = t.cot + (size_t)s * 3 * E;
   double* ge = t.gext + (size_t)s * mesh;
+  if (t.kl && t.kl_flag[(size_t)s]) {       // lambda_x' += k-bar_s dKL~/dx', lambda_v' += k-bar_s dKL~/dv' 
+    const double* xn = t.seg + (size_t)(i + 1) * 2 * part;
+    const int rc = tape_kl_reverse(h, s, xn, xn + part, lx, lv);
+    if (rc) return rc;
+  }
   // the field step s left is read by the law of step s + 1 and by the caller's observation: E-bar joins its refresh adjoint
   const double* Ebar = tape_mode_cot(h, s + 1, c.modes, c.mc);
   hipLaunchKernelGGL(adjoint_mesh_kernel, g.mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, nullptr, t.cmax, t.M + (size_t)i * mesh, cot, ge, t.nu, a, E,

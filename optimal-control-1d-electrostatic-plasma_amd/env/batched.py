@@ -450,35 +450,90 @@ class BatchedPIC:
         self._h.refresh()
 
     # -- differentiable rollouts (pic_tape_*) ------------------------------------------
-    def start_tape(self, max_steps: int, checkpoint_every: int = 0, budget_bytes: int = 0):
+    def start_tape(self, max_steps: int, checkpoint_every: int = 0, budget_bytes: int = 0, kl=None):
         """Open a tape: the steps that follow (step, step_history, step_actions[_traj], step_ext_traj, step_observe,
         step_feedback_gain, up to max_steps of them) can be differentiated by `backward`.  checkpoint_every = 0: about
         sqrt(max_steps).  Float64 particles, CIC, Yoshida-4 and the fixed-point accumulator only.  Resets, step_feedback (use
         step_feedback_gain with G0 for a differentiable reference law), staged steps and changes of actuator or integrator are
-        refused while it is open."""
+        refused while it is open.
+        kl = dict(feq=..., vmin=-25.0, vmax=25.0) also records the smoothed KL of `kl_smooth` after every step (pic_tape_kl_*,
+        DESIGN.md 7h): `tape_kl()` reads the trace and `backward(d_KL=...)` differentiates it.  feq: NumPy or a CUDA tensor,
+        [nx, nv] or [num_envs, nx, nv]; the tape keeps a copy.  If the KL's memory does not fit (PicError), the tape stays open
+        without one."""
         self._h.tape_start(max_steps, checkpoint_every, budget_bytes)
+        self._tape_kl = False
+        if kl is not None:
+            kl = dict(kl)
+            feq, vmin, vmax = kl.pop("feq"), float(kl.pop("vmin", -25.0)), float(kl.pop("vmax", 25.0))
+            if kl:
+                raise ValueError(f"start_tape: unknown keys in kl: {sorted(kl)}")
+            dev, f, fa, per, nx, nv, _ = self._phase_call(feq, [])
+            self._h.tape_kl_start(nx, nv, vmin, vmax, fa, per, _abi.PIC_DEVICE if dev else _abi.PIC_HOST)
+            self._tape_kl = True
 
     def stop_tape(self):
         self._h.tape_stop()
+        self._tape_kl = False
+
+    def tape_kl(self, on_device: bool = False):
+        """The smoothed KL after every step taped so far, [T, num_envs] (a tape opened with kl=...): each row is bit for bit
+        what kl_smooth returns after that step.  NumPy, or a float64 CUDA tensor with on_device."""
+        if not getattr(self, "_tape_kl", False):
+            raise _abi.PicError("tape_kl: no tape with a KL is open (start_tape(..., kl=...))")
+        T = self._h.tape_stats()["steps"]
+        out = self._empty(on_device, (T, self.num_envs))
+        if T == 0:
+            return out
+        shared = getattr(self, "_torch_stream", None) is not None
+        if on_device and not shared:                 # different streams: order them through the host
+            import torch
+            torch.cuda.current_stream(self.device).synchronize()
+        self._h.tape_kl(_abi.PIC_DEVICE if on_device else _abi.PIC_HOST, self._addr(out))
+        if on_device and not shared:
+            self._h.sync()
+        return out
+
+    def _set_kl_cot(self, d_KL, T, on_device):
+        """The KL cotangents of a backward onto the tape: d_KL [T, num_envs], or None to clear every row.  Returns what must stay
+        alive until the backward has been waited for."""
+        if not getattr(self, "_tape_kl", False):
+            if d_KL is not None:
+                raise ValueError("backward: d_KL needs a tape opened with kl=... (start_tape)")
+            return None
+        if T == 0:
+            return None
+        if d_KL is None:
+            self._h.tape_kl_cot(0, _abi.PIC_HOST, 0, T)
+            return None
+        if on_device:
+            import torch
+            d = torch.as_tensor(d_KL, dtype=torch.float64, device=f"cuda:{self.device}").reshape(T, self.num_envs).contiguous()
+            if getattr(self, "_torch_stream", None) is None:
+                torch.cuda.current_stream(self.device).synchronize()
+            self._h.tape_kl_cot(d.data_ptr(), _abi.PIC_DEVICE, 0, T)
+        else:
+            d = np.ascontiguousarray(np.asarray(d_KL, dtype=np.float64).reshape(T, self.num_envs))
+            self._h.tape_kl_cot(d.ctypes.data, _abi.PIC_HOST, 0, T)
+        return d
 
     def tape_stats(self):
         """steps, checkpoint_every, bytes, replay_mismatches (of the last backward; 0 expected), unit_retries, launches."""
         return self._h.tape_stats()
 
-    def taping(self, max_steps: int, checkpoint_every: int = 0, budget_bytes: int = 0):
+    def taping(self, max_steps: int, checkpoint_every: int = 0, budget_bytes: int = 0, kl=None):
         """Context manager: start_tape(...) on entry, stop_tape() on exit."""
         import contextlib
 
         @contextlib.contextmanager
         def cm():
-            self.start_tape(max_steps, checkpoint_every, budget_bytes)
+            self.start_tape(max_steps, checkpoint_every, budget_bytes, kl=kl)
             try:
                 yield self
             finally:
                 self.stop_tape()
         return cm()
 
-    def backward(self, d_KE=None, d_PE=None, d_PE_reward=None, d_x=None, d_v=None, d_modes=None):
+    def backward(self, d_KE=None, d_PE=None, d_PE_reward=None, d_x=None, d_v=None, d_modes=None, d_KL=None):
         """Vector-Jacobian product of the taped steps: cotangents d_KE, d_PE, d_PE_reward [T, num_envs] of the energy traces
         (step_history's) and d_x, d_v [num_envs, N] of the final particles (each None = 0).  Returns a dict: "ext" [T, num_envs,
         N_mesh] (gradient with respect to every step's external field), "actions" [T, num_envs, 2*max_mode] (= B^T ext; with an
@@ -488,15 +543,20 @@ class BatchedPIC:
         A tape with steps of step_feedback_gain: the gradient includes the path through the law; d_modes
         [T, num_envs, 2*max_mode] are cotangents on their modes (ignored on other steps), and the dict also holds "modes"
         [T, num_envs, 2*max_mode] (the taped m_t, zero on other steps) and "gain": sum over the call's steps of
-        actions_t modes_t^T, [num_envs, 2M, 2M] for one gain-law call, a list of them for several."""
+        actions_t modes_t^T, [num_envs, 2M, 2M] for one gain-law call, a list of them for several.
+        A tape opened with kl=...: d_KL [T, num_envs] are cotangents of the KL trace (`tape_kl`); None = 0.  They
+        are set on the tape (or all cleared) before the reverse pass, so a backward is a function of its arguments alone."""
         T = self._h.tape_stats()["steps"]
         E = self.num_envs
-        given = [a for a in (d_KE, d_PE, d_PE_reward, d_x, d_v, d_modes) if a is not None]
+        given = [a for a in (d_KE, d_PE, d_PE_reward, d_x, d_v, d_modes, d_KL) if a is not None]
         on_device = any(hasattr(a, "is_cuda") and a.is_cuda for a in given)
+        keep_kl = self._set_kl_cot(d_KL, T, on_device)
         M = getattr(self, "max_mode", 0)
         calls = self._h.tape_law_calls()
         if calls:
-            return self._backward_law(T, calls, on_device, d_KE, d_PE, d_PE_reward, d_x, d_v, d_modes)
+            res = self._backward_law(T, calls, on_device, d_KE, d_PE, d_PE_reward, d_x, d_v, d_modes)
+            del keep_kl                              # (both branches of _backward_law wait for the backward)
+            return res
         if d_modes is not None:
             raise ValueError("backward: d_modes needs steps of step_feedback_gain on the tape")
         if not on_device:
@@ -510,6 +570,7 @@ class BatchedPIC:
             res = {"ext": out["g_ext"], "x0": out["g_x0"], "v0": out["g_v0"]}
             if M > 0:
                 res["actions"] = out["g_actions"]
+            del keep_kl
             return res
         import torch
         dev = f"cuda:{self.device}"
@@ -538,6 +599,7 @@ class BatchedPIC:
         if st["replay_mismatches"]:
             raise _abi.PicError(f"backward: the replay differs from the taped forward in {st['replay_mismatches']} particle values "
                                 "(were the particles written while the tape was open?): the gradient is not valid")
+        del keep_kl
         return res
 
     def tangent(self, d_ext=None, d_actions=None, d_x0=None, d_v0=None, fields: bool = False):
@@ -659,6 +721,8 @@ class TapeWalk:
         env._h.tape_walk_begin(self.obs_modes)
         env._walk_serial = getattr(env, "_walk_serial", 0) + 1
         self._serial = env._walk_serial
+        # a tape with a KL: the step each call reverses, for its row of KL cotangents
+        self._kl_next = env._h.tape_stats()["steps"] - 1 if getattr(env, "_tape_kl", False) else None
 
     def _live(self, who):
         if getattr(self.env, "_walk_serial", None) != self._serial:
@@ -699,18 +763,24 @@ class TapeWalk:
             torch.cuda.current_stream(self.env.device).synchronize()
         return on_device and not shared
 
-    def step(self, d_energies=None, d_x=None, d_v=None, d_modes=None):
+    def step(self, d_energies=None, d_x=None, d_v=None, d_modes=None, d_kl=None):
         """Reverse the next step t: d_energies [3, num_envs] (its KE, PE, PE_reward), d_x, d_v [num_envs, N] on the state it
-        left, d_modes [num_envs, 2*M_o] on the modes of the field it left.  Returns (t, g_ext [num_envs, N_mesh],
-        g_actions [num_envs, 2*max_mode] or None without an actuator)."""
+        left, d_modes [num_envs, 2*M_o] on the modes of the field it left, d_kl [num_envs] on its smoothed KL (a tape opened
+        with kl=...; None = 0).  Returns (t, g_ext [num_envs, N_mesh], g_actions [num_envs, 2*max_mode] or None without an
+        actuator)."""
         self._live("step")
         env, E = self.env, self.env.num_envs
-        on_device, keep, addr = self._args((d_energies, d_x, d_v, d_modes),
-                                           ((3, E), (E, env.N), (E, env.N), (E, 2 * self.obs_modes)))
+        if d_kl is not None and self._kl_next is None:
+            raise ValueError("walk.step: d_kl needs a tape opened with kl=... (start_tape)")
+        on_device, keep, addr = self._args((d_energies, d_x, d_v, d_modes, d_kl),
+                                           ((3, E), (E, env.N), (E, env.N), (E, 2 * self.obs_modes), (E,)))
         M = getattr(env, "max_mode", 0)
         g_ext = self._empty(on_device, (E, env.N_mesh))
         g_act = self._empty(on_device, (E, 2 * M)) if M > 0 else None
         wait = self._enter(on_device)
+        if self._kl_next is not None and self._kl_next >= 0:
+            env._h.tape_kl_cot(addr[4], _abi.PIC_DEVICE if on_device and addr[4] else _abi.PIC_HOST, self._kl_next, 1)
+            self._kl_next -= 1
         t = env._h.tape_walk_step(addr[0], addr[1], addr[2], addr[3], _abi.PIC_DEVICE if on_device else _abi.PIC_HOST,
                                   self._addr(g_ext), self._addr(g_act))
         if wait:

@@ -12,6 +12,14 @@ the gradient from the device's adjoint (pic_tape_backward) and for
     KE, PE, PE_reward, actions, obs = rollout_policy(env, policy, T)   # policy: any torch callable, modes -> actions
     (PE_reward.sum() + lam * (actions ** 2).sum() * L / 4).backward()   # fills the policy's .grad through the closed loop (7e)
 
+Every entry takes kl=dict(feq=..., vmin=..., vmax=...) (BatchedPIC.start_tape): the smoothed phase-space KL after every step,
+[T, num_envs], is then appended as one more differentiable output, so that the reference's whole cost is:
+
+    KE, PE, PE_reward, KL = rollout(env, actions, kl=dict(feq=feq, vmin=-6.0, vmax=6.0))
+    (KL.sum() + PE_reward.sum()).backward()
+
+Forward mode of the KL is not built: its tangent is returned as zero.
+
 Each call opens a fresh tape on `env` (an open one is stopped first) and leaves it open for the backward; stop it with
 `env.stop_tape()` before a reset.  A backward after the environment has moved on (a further step, another rollout, a reset)
 raises PicError.
@@ -22,115 +30,124 @@ import torch
 from .._abi import PicError
 
 
-def _start(env, T, checkpoint_every):
+def _start(env, T, checkpoint_every, kl=None):
     env.stop_tape()
-    env.start_tape(T, checkpoint_every)
+    env.start_tape(T, checkpoint_every, kl=kl)
     env._tape_serial = getattr(env, "_tape_serial", 0) + 1
     return env._tape_serial
 
 
 class _Rollout(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, u, env, kind, checkpoint_every):
+    def forward(ctx, u, env, kind, checkpoint_every, kl=None):
         if not (u.dtype == torch.float64 and u.dim() == 3 and u.shape[1] == env.num_envs):
             raise ValueError("the control must be a float64 tensor [T, num_envs, ...]")
         T = int(u.shape[0])
-        serial = _start(env, T, checkpoint_every)
+        serial = _start(env, T, checkpoint_every, kl)
         host = np.ascontiguousarray(u.detach().cpu().numpy())
         if kind == "actions":
             ke, pe, per = env.step_actions_traj(host, history=True)
         else:
             ke, pe, per = env.step_ext_traj(host, history=True)
-        ctx.env, ctx.kind, ctx.serial, ctx.steps, ctx.device = env, kind, serial, T, u.device
-        return tuple(torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64, device=u.device) for a in (ke, pe, per))
+        ctx.env, ctx.kind, ctx.serial, ctx.steps, ctx.device, ctx.kl = env, kind, serial, T, u.device, kl is not None
+        outs = (ke, pe, per) + ((env.tape_kl(),) if kl is not None else ())
+        return tuple(torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64, device=u.device) for a in outs)
 
     @staticmethod
-    def backward(ctx, g_ke, g_pe, g_per):
-        env = ctx.env
-        if getattr(env, "_tape_serial", None) != ctx.serial or env.tape_stats()["steps"] != ctx.steps:
-            raise PicError("backward: the environment has moved on since this rollout (a further step, rollout or reset)")
-        if g_ke.is_cuda:
-            out = env.backward(d_KE=g_ke.contiguous(), d_PE=g_pe.contiguous(), d_PE_reward=g_per.contiguous())
-            g = out["actions"] if ctx.kind == "actions" else out["ext"]
-        else:
-            out = env.backward(d_KE=g_ke.numpy(), d_PE=g_pe.numpy(), d_PE_reward=g_per.numpy())
-            g = torch.as_tensor(out["actions"] if ctx.kind == "actions" else out["ext"])
-        return g, None, None, None
-
-    @staticmethod
-    def jvp(ctx, u_t, env_t, kind_t, ce_t):
-        """Forward mode (torch.autograd.forward_ad): the tangent of the energy traces along u_t, from pic_tape_tangent on the
-        tape this rollout opened."""
-        env = ctx.env
-        if getattr(env, "_tape_serial", None) != ctx.serial or env.tape_stats()["steps"] != ctx.steps:
-            raise PicError("jvp: the environment has moved on since this rollout (a further step, rollout or reset)")
-        if u_t is None:
-            return tuple(torch.zeros((ctx.steps, env.num_envs), dtype=torch.float64, device=ctx.device) for _ in range(3))
-        u = u_t.contiguous() if u_t.is_cuda else u_t.detach().numpy()
-        out = env.tangent(**{"d_actions" if ctx.kind == "actions" else "d_ext": u})
-        return tuple(torch.as_tensor(out[k], dtype=torch.float64, device=ctx.device) for k in ("KE", "PE", "PE_reward"))
-
-
-def rollout(env, actions, checkpoint_every=0):
-    """T = actions.shape[0] steps of `env` (a BatchedPIC with an actuator) under actions [T, num_envs, 2*max_mode] through
-    pic_step_actions_traj on a tape; returns KE, PE, PE_reward [T, num_envs] (float64, on actions' device), differentiable
-    with respect to `actions`."""
-    if getattr(env, "max_mode", 0) == 0:
-        raise PicError("rollout: the environment has no actuator (set_actuator)")
-    return _Rollout.apply(actions, env, "actions", int(checkpoint_every))
-
-
-def rollout_ext(env, E_ext, checkpoint_every=0):
-    """The same under raw external fields E_ext [T, num_envs, N_mesh] (pic_step_ext_traj)."""
-    return _Rollout.apply(E_ext, env, "ext", int(checkpoint_every))
-
-
-class _RolloutFeedback(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, gain, env, T, checkpoint_every):
-        E, n = env.num_envs, 2 * env.max_mode
-        if not (gain.dtype == torch.float64 and tuple(gain.shape) in ((E, n, n), (n, n))):
-            raise ValueError(f"the gain must be a float64 tensor [{E}, {n}, {n}] or [{n}, {n}]")
-        serial = _start(env, T, checkpoint_every)
-        g = gain.detach()
-        if not g.is_cuda:
-            g = g.numpy()
-        out = env.step_feedback_gain(g, T, modes=True, history=True)
-        ctx.env, ctx.serial, ctx.steps, ctx.shared = env, serial, T, gain.dim() == 2
-        return tuple(torch.as_tensor(np.ascontiguousarray(out[k]), dtype=torch.float64, device=gain.device)
-                     for k in ("KE", "PE", "PE_reward", "modes"))
-
-    @staticmethod
-    def backward(ctx, g_ke, g_pe, g_per, g_modes):
+    def backward(ctx, g_ke, g_pe, g_per, g_kl=None):
         env = ctx.env
         if getattr(env, "_tape_serial", None) != ctx.serial or env.tape_stats()["steps"] != ctx.steps:
             raise PicError("backward: the environment has moved on since this rollout (a further step, rollout or reset)")
         if g_ke.is_cuda:
             out = env.backward(d_KE=g_ke.contiguous(), d_PE=g_pe.contiguous(), d_PE_reward=g_per.contiguous(),
-                               d_modes=g_modes.contiguous())
+                               d_KL=g_kl.contiguous() if ctx.kl else None)
+            g = out["actions"] if ctx.kind == "actions" else out["ext"]
+        else:
+            out = env.backward(d_KE=g_ke.numpy(), d_PE=g_pe.numpy(), d_PE_reward=g_per.numpy(),
+                               d_KL=g_kl.numpy() if ctx.kl else None)
+            g = torch.as_tensor(out["actions"] if ctx.kind == "actions" else out["ext"])
+        return g, None, None, None, None
+
+    @staticmethod
+    def jvp(ctx, u_t, env_t, kind_t, ce_t, kl_t=None):
+        """Forward mode (torch.autograd.forward_ad): the tangent of the energy traces along u_t, from pic_tape_tangent on the
+        tape this rollout opened.  The KL output of a rollout with kl=... gets a ZERO tangent: forward mode of
+        the KL is not built, so do not read a directional derivative of the KL from it."""
+        env = ctx.env
+        if getattr(env, "_tape_serial", None) != ctx.serial or env.tape_stats()["steps"] != ctx.steps:
+            raise PicError("jvp: the environment has moved on since this rollout (a further step, rollout or reset)")
+        zero = lambda: torch.zeros((ctx.steps, env.num_envs), dtype=torch.float64, device=ctx.device)  # noqa: E731
+        if u_t is None:
+            return tuple(zero() for _ in range(4 if ctx.kl else 3))
+        u = u_t.contiguous() if u_t.is_cuda else u_t.detach().numpy()
+        out = env.tangent(**{"d_actions" if ctx.kind == "actions" else "d_ext": u})
+        res = tuple(torch.as_tensor(out[k], dtype=torch.float64, device=ctx.device) for k in ("KE", "PE", "PE_reward"))
+        return res + ((zero(),) if ctx.kl else ())
+
+
+def rollout(env, actions, checkpoint_every=0, kl=None):
+    """T = actions.shape[0] steps of `env` (a BatchedPIC with an actuator) under actions [T, num_envs, 2*max_mode] through
+    pic_step_actions_traj on a tape; returns KE, PE, PE_reward [T, num_envs] (float64, on actions' device), differentiable
+    with respect to `actions`.  With kl=dict(feq=..., vmin=..., vmax=...) a fourth output follows: the smoothed KL after
+    every step, [T, num_envs], differentiable too."""
+    if getattr(env, "max_mode", 0) == 0:
+        raise PicError("rollout: the environment has no actuator (set_actuator)")
+    return _Rollout.apply(actions, env, "actions", int(checkpoint_every), kl)
+
+
+def rollout_ext(env, E_ext, checkpoint_every=0, kl=None):
+    """The same under raw external fields E_ext [T, num_envs, N_mesh] (pic_step_ext_traj)."""
+    return _Rollout.apply(E_ext, env, "ext", int(checkpoint_every), kl)
+
+
+class _RolloutFeedback(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gain, env, T, checkpoint_every, kl=None):
+        E, n = env.num_envs, 2 * env.max_mode
+        if not (gain.dtype == torch.float64 and tuple(gain.shape) in ((E, n, n), (n, n))):
+            raise ValueError(f"the gain must be a float64 tensor [{E}, {n}, {n}] or [{n}, {n}]")
+        serial = _start(env, T, checkpoint_every, kl)
+        g = gain.detach()
+        if not g.is_cuda:
+            g = g.numpy()
+        out = env.step_feedback_gain(g, T, modes=True, history=True)
+        ctx.env, ctx.serial, ctx.steps, ctx.shared, ctx.kl = env, serial, T, gain.dim() == 2, kl is not None
+        outs = [out[k] for k in ("KE", "PE", "PE_reward", "modes")] + ([env.tape_kl()] if kl is not None else [])
+        return tuple(torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64, device=gain.device) for a in outs)
+
+    @staticmethod
+    def backward(ctx, g_ke, g_pe, g_per, g_modes, g_kl=None):
+        env = ctx.env
+        if getattr(env, "_tape_serial", None) != ctx.serial or env.tape_stats()["steps"] != ctx.steps:
+            raise PicError("backward: the environment has moved on since this rollout (a further step, rollout or reset)")
+        if g_ke.is_cuda:
+            out = env.backward(d_KE=g_ke.contiguous(), d_PE=g_pe.contiguous(), d_PE_reward=g_per.contiguous(),
+                               d_modes=g_modes.contiguous(), d_KL=g_kl.contiguous() if ctx.kl else None)
             g = out["gain"]
         else:
-            out = env.backward(d_KE=g_ke.numpy(), d_PE=g_pe.numpy(), d_PE_reward=g_per.numpy(), d_modes=g_modes.numpy())
+            out = env.backward(d_KE=g_ke.numpy(), d_PE=g_pe.numpy(), d_PE_reward=g_per.numpy(), d_modes=g_modes.numpy(),
+                               d_KL=g_kl.numpy() if ctx.kl else None)
             g = torch.as_tensor(out["gain"])
-        return (g.sum(0) if ctx.shared else g), None, None, None
+        return (g.sum(0) if ctx.shared else g), None, None, None, None
 
 
-def rollout_feedback(env, gain, T, checkpoint_every=0):
+def rollout_feedback(env, gain, T, checkpoint_every=0, kl=None):
     """T steps of `env` (a BatchedPIC with an actuator) under the closed-loop gain law a_t = G m_t (step_feedback_gain) on a
     tape; returns KE, PE, PE_reward [T, num_envs] and the modes m_t [T, num_envs, 2*max_mode] the law read, differentiable with
     respect to `gain` (float64, [num_envs, 2M, 2M], or [2M, 2M] shared by every environment: its gradient is the sum over
-    them).  Cotangents on `modes` reach the plasma through d_modes, so spectral losses such as sum |E_1|^2 work too."""
+    them).  Cotangents on `modes` reach the plasma through d_modes, so spectral losses such as sum |E_1|^2 work too.  With kl=...
+    the smoothed KL after every step, [T, num_envs], follows as a fifth differentiable output."""
     if getattr(env, "max_mode", 0) == 0:
         raise PicError("rollout_feedback: the environment has no actuator (set_actuator)")
-    return _RolloutFeedback.apply(gain, env, int(T), int(checkpoint_every))
+    return _RolloutFeedback.apply(gain, env, int(T), int(checkpoint_every), kl)
 
 
 class _PolicyWalk:
     """What the steps of one rollout_policy share: the environment, the tape's identity, and the reverse walk their backwards
     advance together (step T-1 first, the start last)."""
 
-    def __init__(self, env, T, observe, obs_modes, serial):
-        self.env, self.T, self.observe, self.obs_modes, self.serial = env, T, observe, obs_modes, serial
+    def __init__(self, env, T, observe, obs_modes, serial, kl=False):
+        self.env, self.T, self.observe, self.obs_modes, self.serial, self.kl = env, T, observe, obs_modes, serial, kl
         self.walk, self.next = None, -1
 
     def reverse_to(self, t):
@@ -186,22 +203,27 @@ class _PolicyStep(torch.autograd.Function):
         env.step_actions_torch(action.detach().contiguous())
         en = env.energy_views_torch()
         energies = tuple(en[k].clone() for k in ("KE", "PE", "PE_reward"))
+        if pw.kl:                                    # the KL of this step: its row of the tape's trace
+            energies += (env.tape_kl(on_device=True)[t].clone(),)
         return (token.new_zeros(0),) + energies + _observe(env, pw.observe, pw.obs_modes)
 
     @staticmethod
     def backward(ctx, g_token, g_ke, g_pe, g_per, *g_obs):
         pw, t = ctx.pw, ctx.t
         pw.reverse_to(t)
+        kw = {}
+        if pw.kl:
+            kw["d_kl"], g_obs = g_obs[0], g_obs[1:]
         d_en = None
         if any(g is not None for g in (g_ke, g_pe, g_per)):
             ref = next(g for g in (g_ke, g_pe, g_per) if g is not None)
             d_en = torch.stack([g if g is not None else torch.zeros_like(ref) for g in (g_ke, g_pe, g_per)])
-        _, _, g_act = pw.walk.step(d_energies=d_en, **pw.cot(g_obs))
+        _, _, g_act = pw.walk.step(d_energies=d_en, **kw, **pw.cot(g_obs))
         pw.next -= 1
         return g_token.new_zeros(0) if g_token is not None else None, g_act, None, None
 
 
-def rollout_policy(env, policy, T, observe="modes", obs_modes=None, checkpoint_every=0):
+def rollout_policy(env, policy, T, observe="modes", obs_modes=None, checkpoint_every=0, kl=None):
     """T steps of `env` (a BatchedPIC with an actuator, on the GPU) in closed loop under a torch policy: at every step the
     observation o_t goes through `policy(o_t)` to the actions a_t [num_envs, 2*max_mode] (any float dtype: cast to float64), which
     step_actions_torch applies.  observe="modes": o_t = the modes of the field, float64 [num_envs, 2*M_o] (Re E_1..E_Mo then
@@ -210,7 +232,8 @@ def rollout_policy(env, policy, T, observe="modes", obs_modes=None, checkpoint_e
     Runs on a fresh tape; returns KE, PE, PE_reward [T, num_envs], actions [T, num_envs, 2*max_mode] and the observations
     o_0..o_T (a list of T + 1), all differentiable with respect to the policy's parameters (and whatever else it closes over):
     the backward walks the tape step by step (pic_tape_walk_*) and puts the policy's own vector-Jacobian product
-    between two reverse steps.  With env.use_torch_stream() no step synchronises the host."""
+    between two reverse steps.  With env.use_torch_stream() no step synchronises the host.  With kl=... the smoothed KL after
+    every step, [T, num_envs], follows as a sixth differentiable output (reading each step's value waits for the step)."""
     if getattr(env, "max_mode", 0) == 0:
         raise PicError("rollout_policy: the environment has no actuator (set_actuator)")
     if observe not in ("modes", "state"):
@@ -221,23 +244,27 @@ def rollout_policy(env, policy, T, observe="modes", obs_modes=None, checkpoint_e
     mo = int(obs_modes) if obs_modes is not None else env.max_mode
     if not 1 <= mo < env.N_mesh:
         raise ValueError("need 1 <= obs_modes < N_mesh")
-    serial = _start(env, T, int(checkpoint_every))
-    pw = _PolicyWalk(env, T, observe, mo, serial)
+    serial = _start(env, T, int(checkpoint_every), kl)
+    pw = _PolicyWalk(env, T, observe, mo, serial, kl is not None)
     anchor = torch.zeros(0, dtype=torch.float64, device=f"cuda:{env.device}", requires_grad=True)
     out = _PolicyStart.apply(anchor, pw)
     token, o = out[0], (out[1] if observe == "modes" else tuple(out[1:]))
     obs = [o]
-    ke, pe, per, acts = [], [], [], []
+    ke, pe, per, acts, kls = [], [], [], [], []
     n = 2 * env.max_mode
+    k0 = 5 if kl is not None else 4                  # where a step's observation starts in its outputs
     for t in range(T):
         a = policy(o).to(torch.float64)
         if tuple(a.shape) != (env.num_envs, n):
             raise ValueError(f"the policy must return actions [{env.num_envs}, {n}], not {tuple(a.shape)}")
         out = _PolicyStep.apply(token, a, pw, t)
-        token, o = out[0], (out[4] if observe == "modes" else tuple(out[4:]))
+        token, o = out[0], (out[k0] if observe == "modes" else tuple(out[k0:]))
         ke.append(out[1])
         pe.append(out[2])
         per.append(out[3])
+        if kl is not None:
+            kls.append(out[4])
         acts.append(a)
         obs.append(o)
-    return torch.stack(ke), torch.stack(pe), torch.stack(per), torch.stack(acts), obs
+    res = (torch.stack(ke), torch.stack(pe), torch.stack(per), torch.stack(acts), obs)
+    return res + ((torch.stack(kls),) if kl is not None else ())
