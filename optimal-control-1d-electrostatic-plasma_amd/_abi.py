@@ -225,6 +225,21 @@ def _ptr(a):
     return C.c_void_p(a.__array_interface__["data"][0])
 
 
+def _ptrs(*addresses):
+    """Addresses (int, 0 or None = NULL) as pointer arguments."""
+    return [_ptr(int(q)) if q else None for q in addresses]
+
+
+def _host(a, shape):
+    """a (or None) as a C-contiguous float64 host array of `shape`."""
+    return None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(shape))
+
+
+def _phase_spec(nx, nv, vmin, vmax, feq, feq_per_env, feq_kind):
+    """pic_phase_spec; feq an address (0 = NULL) in feq_kind memory."""
+    return PicPhaseSpec(int(nx), int(nv), float(vmin), float(vmax), int(feq) or None, int(feq_per_env), int(feq_kind))
+
+
 class Handle:
     """Owns one pic_handle (one device, one stream, `num_envs` environments)."""
 
@@ -609,14 +624,14 @@ class Handle:
 
     def phase_kl_smooth(self, nx, nv, vmin, vmax, feq, feq_per_env, feq_kind, mem_kind, kl, f):
         """pic_phase_kl_smooth on addresses (int, 0 = NULL) in feq_kind / mem_kind memory."""
-        spec = PicPhaseSpec(int(nx), int(nv), float(vmin), float(vmax), int(feq) or None, int(feq_per_env), int(feq_kind))
-        p = [_ptr(int(q)) if q else None for q in (kl, f)]
+        spec = _phase_spec(nx, nv, vmin, vmax, feq, feq_per_env, feq_kind)
+        p = _ptrs(kl, f)
         self._chk(self.lib.pic_phase_kl_smooth(self._h, C.byref(spec), int(mem_kind), p[0], p[1]))
 
     def phase_kl_smooth_vjp(self, nx, nv, vmin, vmax, feq, feq_per_env, feq_kind, cot_kl, mem_kind, g_x, g_v):
         """pic_phase_kl_smooth_vjp on addresses (int, 0 = NULL)."""
-        spec = PicPhaseSpec(int(nx), int(nv), float(vmin), float(vmax), int(feq) or None, int(feq_per_env), int(feq_kind))
-        p = [_ptr(int(q)) if q else None for q in (cot_kl, g_x, g_v)]
+        spec = _phase_spec(nx, nv, vmin, vmax, feq, feq_per_env, feq_kind)
+        p = _ptrs(cot_kl, g_x, g_v)
         self._chk(self.lib.pic_phase_kl_smooth_vjp(self._h, C.byref(spec), p[0], int(mem_kind), p[1], p[2]))
 
     # -- rollout recorder (pic_record_*) ------------------------------------------------------------
@@ -682,10 +697,7 @@ class Handle:
         [num_envs][N] (those asked for)."""
         T = self.tape_stats()["steps"]
         E = self.num_envs
-
-        def host(a, shape):
-            return None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(shape))
-        ch, cx, cv = host(cot_hist, (T, 3, E)), host(cot_x, (E, self.N)), host(cot_v, (E, self.N))
+        ch, cx, cv = _host(cot_hist, (T, 3, E)), _host(cot_x, (E, self.N)), _host(cot_v, (E, self.N))
         out = {}
         if ext:
             out["g_ext"] = np.zeros((T, E, self.Ng))
@@ -700,7 +712,7 @@ class Handle:
 
     def tape_backward_device(self, cot_hist, cot_x, cot_v, g_ext, g_actions, g_x0, g_v0):
         """Device pointers (0 = NULL) in and out; asynchronous on the handle's stream."""
-        p = [None if not q else _ptr(int(q)) for q in (cot_hist, cot_x, cot_v, g_ext, g_actions, g_x0, g_v0)]
+        p = _ptrs(cot_hist, cot_x, cot_v, g_ext, g_actions, g_x0, g_v0)
         self._chk(self.lib.pic_tape_backward(self._h, p[0], p[1], p[2], PIC_DEVICE, p[3], p[4], p[5], p[6]))
 
     def tape_stop(self):
@@ -715,10 +727,7 @@ class Handle:
         """pic_tape_backward_feedback with host arrays: dict with g_ext, g_actions, modes [T][num_envs][2M], g_x0, g_v0."""
         T = self.tape_stats()["steps"]
         E, n = self.num_envs, 2 * self.max_mode
-
-        def host(a, shape):
-            return None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(shape))
-        ch, cx, cv, cm = host(cot_hist, (T, 3, E)), host(cot_x, (E, self.N)), host(cot_v, (E, self.N)), host(cot_modes, (T, E, n))
+        ch, cx, cv, cm = _host(cot_hist, (T, 3, E)), _host(cot_x, (E, self.N)), _host(cot_v, (E, self.N)), _host(cot_modes, (T, E, n))
         out = {"g_ext": np.zeros((T, E, self.Ng)), "g_actions": np.zeros((T, E, n)), "modes": np.zeros((T, E, n)),
                "g_x0": np.zeros((E, self.N)), "g_v0": np.zeros((E, self.N))}
         self._chk(self.lib.pic_tape_backward_feedback(self._h, _ptr(ch), _ptr(cx), _ptr(cv), _ptr(cm), PIC_HOST, _ptr(out["g_ext"]),
@@ -728,7 +737,7 @@ class Handle:
 
     def tape_backward_feedback_device(self, cot_hist, cot_x, cot_v, cot_modes, g_ext, g_actions, g_x0, g_v0, modes):
         """Device pointers (0 = NULL) in and out; asynchronous on the handle's stream."""
-        p = [None if not q else _ptr(int(q)) for q in (cot_hist, cot_x, cot_v, cot_modes, g_ext, g_actions, g_x0, g_v0, modes)]
+        p = _ptrs(cot_hist, cot_x, cot_v, cot_modes, g_ext, g_actions, g_x0, g_v0, modes)
         self._chk(self.lib.pic_tape_backward_feedback(self._h, p[0], p[1], p[2], p[3], PIC_DEVICE, p[4], p[5], p[6], p[7], p[8]))
 
     def tape_walk_begin(self, obs_modes, mem_kind=PIC_HOST):
@@ -736,14 +745,14 @@ class Handle:
 
     def tape_walk_step(self, cot_energies, cot_x, cot_v, cot_modes, mem_kind, g_ext, g_actions):
         """pic_tape_walk_step: addresses (int, 0 = NULL; device or host memory as mem_kind says) in and out; returns the step."""
-        p = [None if not q else _ptr(int(q)) for q in (cot_energies, cot_x, cot_v, cot_modes, g_ext, g_actions)]
+        p = _ptrs(cot_energies, cot_x, cot_v, cot_modes, g_ext, g_actions)
         step = C.c_int64(-1)
         self._chk(self.lib.pic_tape_walk_step(self._h, p[0], p[1], p[2], p[3], int(mem_kind), p[4], p[5], C.byref(step)))
         return step.value
 
     def tape_walk_end(self, cot_x0, cot_v0, cot_modes0, mem_kind, g_x0, g_v0):
         """pic_tape_walk_end: addresses (int, 0 = NULL) in and out."""
-        p = [None if not q else _ptr(int(q)) for q in (cot_x0, cot_v0, cot_modes0, g_x0, g_v0)]
+        p = _ptrs(cot_x0, cot_v0, cot_modes0, g_x0, g_v0)
         self._chk(self.lib.pic_tape_walk_end(self._h, p[0], p[1], p[2], int(mem_kind), p[3], p[4]))
 
     def tape_tangent(self, K, d_ext=None, d_actions=None, d_x0=None, d_v0=None, fields=False):
@@ -751,12 +760,9 @@ class Handle:
         and, with fields, E_mesh [K][T][num_envs][Ng]."""
         T = self.tape_stats()["steps"]
         E, K = self.num_envs, int(K)
-
-        def host(a, shape):
-            return None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(shape))
-        de = host(d_ext, (K, T, E, self.Ng))
-        da = host(d_actions, (K, T, E, -1))
-        dx, dv = host(d_x0, (K, E, self.N)), host(d_v0, (K, E, self.N))
+        de = _host(d_ext, (K, T, E, self.Ng))
+        da = _host(d_actions, (K, T, E, -1))
+        dx, dv = _host(d_x0, (K, E, self.N)), _host(d_v0, (K, E, self.N))
         out = {"hist": np.zeros((K, T, 3, E)), "x": np.zeros((K, E, self.N)), "v": np.zeros((K, E, self.N))}
         if fields:
             out["E_mesh"] = np.zeros((K, T, E, self.Ng))
@@ -766,12 +772,12 @@ class Handle:
 
     def tape_tangent_device(self, K, d_ext, d_actions, d_x0, d_v0, hist, x, v, E_mesh):
         """pic_tape_tangent on device pointers (int, 0 = NULL); asynchronous on the handle's stream."""
-        p = [None if not q else _ptr(int(q)) for q in (d_ext, d_actions, d_x0, d_v0, hist, x, v, E_mesh)]
+        p = _ptrs(d_ext, d_actions, d_x0, d_v0, hist, x, v, E_mesh)
         self._chk(self.lib.pic_tape_tangent(self._h, int(K), p[0], p[1], p[2], p[3], PIC_DEVICE, p[4], p[5], p[6], p[7]))
 
     def tape_kl_start(self, nx, nv, vmin, vmax, feq, feq_per_env, feq_kind):
         """pic_tape_kl_start: feq an address in feq_kind memory (the tape copies it)."""
-        spec = PicPhaseSpec(int(nx), int(nv), float(vmin), float(vmax), int(feq) or None, int(feq_per_env), int(feq_kind))
+        spec = _phase_spec(nx, nv, vmin, vmax, feq, feq_per_env, feq_kind)
         self._chk(self.lib.pic_tape_kl_start(self._h, C.byref(spec)))
 
     def tape_kl(self, mem_kind, kl):

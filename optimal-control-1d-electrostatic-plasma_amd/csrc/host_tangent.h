@@ -1,0 +1,173 @@
+// host_tangent.h -- included by picstep.hip alone, inside its extern "C" block, behind host_tape.h (the replay is the walk's)
+#pragma once
+// ---------------------------------------------------------------------------------------------
+// Forward mode of the tape (include/picstep.h: pic_tape_tangent; kernels: pic_tangent.h)
+// ---------------------------------------------------------------------------------------------
+// the parts of the tangent block for kc directions: state [kc][2][env][ld], dF [kc][env][Ng], acc [kc][env][Ng], ke [kc][env],
+// umax [3][kc][env] (everything from acc on is zero between uses)
+static size_t tangent_parts(Carver c, const pic_handle* h, int kc, TanArgs& ta) {
+  const size_t E = h->cfg.num_envs, mesh = E * h->cfg.Ng;
+  c.take(ta.st, (size_t)kc * 2 * E * h->ld);
+  c.take(ta.dF, kc * mesh);
+  c.take(ta.acc, kc * mesh);
+  c.take(ta.ke, kc * E);
+  c.take(ta.umax, 3 * kc * E);
+  return c.at;
+}
+
+// the tangent block for K directions, within budget_bytes; on failure the tape keeps what it had
+static int tangent_reserve(pic_handle* h, int K, const std::string& w) {
+  Tape& t = h->tape;
+  if (t.tan_k >= K) return PIC_OK;
+  TanArgs scratch{};
+  const size_t bytes = tangent_parts(Carver{}, h, K, scratch);
+  if (t.budget > 0 && t.bytes - t.tan_bytes + bytes > (size_t)t.budget)
+    return fail(h, PIC_ENOMEM, w + ": the working memory of " + std::to_string(K) + " directions (" + std::to_string(bytes) +
+                                   " bytes) would take the tape past budget_bytes (pic_tape_start)");
+  DeviceBuf<void> b;
+  const int rc = regrow(h, b, bytes, (w + ": the working memory of " + std::to_string(K) + " directions does not fit on the device").c_str());
+  if (rc) return rc;
+  if (t.tan_block) HIPCHK(h, hipStreamSynchronize(h->stream));      // queued work may still read the old block
+  t.tan_block = std::move(b);
+  t.bytes = t.bytes - t.tan_bytes + bytes;
+  t.tan_bytes = bytes;
+  t.tan_k = K;
+  return PIC_OK;
+}
+
+extern "C++" {
+// the kernels of a sub-stage for the direction count at hand (1, up to 4, up to 8: the per-direction values live in registers)
+template <int S>
+static void tangent_deposit(pic_handle* h, const AdjStep& st, const TanArgs& ta, const AdjArgs& a, dim3 grid, size_t lds, int kd) {
+  if (kd == 1) hipLaunchKernelGGL((tangent_deposit_kernel<S, 1>), grid, dim3(ABLOCK), lds, h->stream, st, ta, a, kd);
+  else if (kd <= 4) hipLaunchKernelGGL((tangent_deposit_kernel<S, 4>), grid, dim3(ABLOCK), lds, h->stream, st, ta, a, kd);
+  else hipLaunchKernelGGL((tangent_deposit_kernel<S, 8>), grid, dim3(ABLOCK), lds, h->stream, st, ta, a, kd);
+}
+
+template <int S>
+static void tangent_pass(pic_handle* h, const AdjStep& st, const TanArgs& ta, const AdjArgs& a, dim3 grid) {
+  if (ta.K == 1) hipLaunchKernelGGL((tangent_pass_kernel<S, 1>), grid, dim3(ABLOCK), 0, h->stream, st, ta, a);
+  else if (ta.K <= 4) hipLaunchKernelGGL((tangent_pass_kernel<S, 4>), grid, dim3(ABLOCK), 0, h->stream, st, ta, a);
+  else hipLaunchKernelGGL((tangent_pass_kernel<S, 8>), grid, dim3(ABLOCK), 0, h->stream, st, ta, a);
+}
+}  // extern "C++"
+
+int pic_tape_tangent(pic_handle* h, int K, const double* d_ext, const double* d_actions, const void* d_x0, const void* d_v0,
+                     int mem_kind, double* d_hist, void* d_x, void* d_v, double* d_E_mesh) {
+  if (!h) return PIC_EINVAL;
+  Tape& t = h->tape;
+  const std::string w("pic_tape_tangent");
+  if (int rc = check_tape_open(h, w.c_str())) return rc;
+  if (K < 1 || K > kMaxTangents) return fail(h, PIC_EINVAL, w + ": need 1 <= K <= " + std::to_string(kMaxTangents));
+  if (d_ext && d_actions) return fail(h, PIC_EINVAL, w + ": d_ext and d_actions are both given (at most one)");
+  if (int rc = check_mem_kind(h, mem_kind, w.c_str())) return rc;
+  const int64_t T = t.steps;
+  for (int64_t s = 0; s < T && !t.law.empty(); ++s)
+    if (t.law[(size_t)s] >= 0)
+      return fail(h, PIC_ESTATE, w + ": the tape holds steps of pic_step_feedback_gain, and forward mode through the gain law is "
+                                     "not built (pic_tape_backward_feedback differentiates it in reverse)");
+  if (int rc = check_tape_actuator(h, d_actions, "d_actions", w.c_str())) return rc;
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  const int E = h->cfg.num_envs, Ng = h->cfg.Ng, Mact = h->act_modes;
+  const bool host = mem_kind == PIC_HOST;
+  const size_t N = h->cfg.N, part = (size_t)E * h->ld, mesh = (size_t)E * Ng, row = N * sizeof(double);
+  t.walk = false;                     // (a walk's replayed segment is about to be overwritten)
+  t.launches = 0;
+  HIPCHK(h, hipMemsetAsync(t.counters, 0, 2 * sizeof(unsigned long long), h->stream));
+  if (T == 0) {                       // no step: the tangent of the final particles is the initial one (NULL: 0)
+    const size_t n = (size_t)K * E * row;
+    void* outs[2] = {d_x, d_v};
+    const void* ins[2] = {d_x0, d_v0};
+    for (int k = 0; k < 2; ++k) {
+      if (!outs[k]) continue;
+      if (!host) HIPCHK(h, device_fill(h, static_cast<double*>(outs[k]), static_cast<const double*>(ins[k]), n, mem_kind));
+      else if (ins[k]) std::memcpy(outs[k], ins[k], n);
+      else std::memset(outs[k], 0, n);
+    }
+    if (host) HIPCHK(h, hipStreamSynchronize(h->stream));
+    return PIC_OK;
+  }
+  int rc = tangent_reserve(h, K, w);
+  if (rc) return rc;
+  TanArgs ta{};
+  tangent_parts(Carver{static_cast<char*>(t.tan_block.get())}, h, t.tan_k, ta);
+  ta.dstride = (long long)(2 * part); ta.vofs = (long long)part;
+  ta.K = K; ta.num_envs = E;
+  HIPCHK(h, hipMemsetAsync(ta.acc, 0, Carver::upto(ta.acc, ta.umax + 3 * (size_t)t.tan_k * E), h->stream));     // acc, ke, umax (a failed call may leave them)
+  // host memory: the control tangents and the mesh-sized outputs go through one device block of this call
+  const size_t in_n = d_ext ? (size_t)K * T * mesh : d_actions ? (size_t)K * T * E * 2 * Mact : 0;
+  const size_t hist_n = d_hist ? (size_t)K * T * 3 * E : 0, em_n = d_E_mesh ? (size_t)K * T * mesh : 0;
+  const double* din = d_ext ? d_ext : d_actions;
+  double* dhist = d_hist;
+  double* dem = d_E_mesh;
+  DeviceBuf<double> stage;
+  if (host && in_n + hist_n + em_n > 0) {
+    rc = regrow(h, stage, (in_n + hist_n + em_n) * sizeof(double), (w + ": the staging of host tangents does not fit on the device").c_str());
+    if (rc) return rc;
+    double* p = stage;
+    HIPCHK(h, device_input(h, din, PIC_HOST, in_n * sizeof(double), p, &din));
+    dhist = device_output(d_hist, PIC_HOST, p + in_n);
+    dem = device_output(d_E_mesh, PIC_HOST, p + in_n + hist_n);
+  }
+  // (dx_0, dv_0) of every direction into the state rows (padded to ld)
+  for (int d = 0; d < K; ++d) {
+    const void* ins[2] = {d_x0, d_v0};
+    for (int k = 0; k < 2; ++k) {
+      double* dst = ta.st + (size_t)d * 2 * part + (size_t)k * part;
+      if (ins[k]) rc = upload(h, dst, static_cast<const double*>(ins[k]) + (size_t)d * E * N, mem_kind);
+      else HIPCHK(h, hipMemsetAsync(dst, 0, part * sizeof(double), h->stream));
+      if (rc) return rc;
+    }
+  }
+  const AdjArgs a = adjoint_args(h);
+  const WalkGeom g = walk_geom(h);
+  hipLaunchKernelGGL(tangent_start_kernel, g.pgrid, dim3(ABLOCK), 0, h->stream, ta, a);
+  ++t.launches;
+  // a deposit workgroup holds kd directions' meshes in 64 KB of LDS; groups of them run side by side (grid z)
+  const int kd = std::min<int>(K, (int)std::max<size_t>(1, 65536 / ((size_t)(Ng + 1) * sizeof(unsigned long long))));
+  const dim3 dgrid(g.pgrid.x, E, (K + kd - 1) / kd), mgrid(E, K);
+  const size_t dlds = (size_t)kd * (Ng + 1) * sizeof(unsigned long long);
+  TanMeshIO io{};
+  io.basis = h->basis; io.Mact = Mact;
+  io.in_dstride = d_ext ? (long long)(T * mesh) : (long long)(T * E * 2 * Mact);
+  io.out_hstride = (long long)(T * 3 * E); io.out_mstride = (long long)(T * mesh);
+  const int64_t nseg = (T + t.every - 1) / t.every;
+  for (int64_t sgi = 0; sgi < nseg; ++sgi) {
+    rc = walk_replay(h, sgi, a, g);
+    if (rc) return rc;
+    const int64_t t0 = sgi * t.every, len = std::min<int64_t>(t.every, T - t0);
+    for (int64_t i = 0; i < len; ++i) {
+      const int64_t s = t0 + i;
+      const double* x = t.seg + (size_t)i * 2 * part;
+      const AdjStep st{x, x + part, t.F + (size_t)i * 3 * mesh, (long long)mesh};
+      TanMeshIO m = io;
+      m.ext = d_ext ? din + (size_t)s * mesh : nullptr;
+      m.act = d_actions ? din + (size_t)s * E * 2 * Mact : nullptr;
+      m.M = t.M + (size_t)i * mesh;
+      m.hist = dhist ? dhist + (size_t)s * 3 * E : nullptr;
+      m.Emesh = dem ? dem + (size_t)s * mesh : nullptr;
+      tangent_deposit<1>(h, st, ta, a, dgrid, dlds, kd);
+      hipLaunchKernelGGL(tangent_mesh_kernel<1>, mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, ta, m, a);
+      tangent_pass<1>(h, st, ta, a, g.pgrid);
+      tangent_deposit<2>(h, st, ta, a, dgrid, dlds, kd);
+      hipLaunchKernelGGL(tangent_mesh_kernel<2>, mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, ta, m, a);
+      tangent_pass<2>(h, st, ta, a, g.pgrid);
+      tangent_deposit<3>(h, st, ta, a, dgrid, dlds, kd);
+      hipLaunchKernelGGL(tangent_mesh_kernel<3>, mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, ta, m, a);
+      tangent_pass<3>(h, st, ta, a, g.pgrid);
+      tangent_deposit<4>(h, st, ta, a, dgrid, dlds, kd);
+      hipLaunchKernelGGL(tangent_mesh_kernel<4>, mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, ta, m, a);
+      t.launches += 11;
+    }
+    HIPCHK(h, hipGetLastError());
+  }
+  HIPCHK(h, device_result(h, d_hist, dhist, hist_n * sizeof(double)));
+  HIPCHK(h, device_result(h, d_E_mesh, dem, em_n * sizeof(double)));
+  // (dx', dv') of every direction out of the state rows
+  for (int d = 0; d < K && !rc; ++d) {
+    void* outs[2] = {d_x, d_v};
+    for (int k = 0; k < 2 && !rc; ++k)
+      if (outs[k]) rc = download(h, static_cast<double*>(outs[k]) + (size_t)d * E * N, ta.st + (size_t)d * 2 * part + (size_t)k * part, mem_kind);
+  }
+  return rc ? rc : walk_finish(h, w, mem_kind);
+}

@@ -33,7 +33,7 @@
 //
 // Files: pic_device.h (particle formats, per-particle helpers, scans), pic_sweep.h (push sweeps), pic_solve.h
 // (field solve), pic_aux.h (kernels off the step path); this file holds the handle, the launch schedule and
-// the C ABI.
+// the C ABI, but for the host side of the differentiable rollouts: host_diff.h, host_phase.h, host_tape.h, host_tangent.h.
 
 #include <hip/hip_runtime.h>
 
@@ -158,7 +158,6 @@ struct Recorder {
   int gx = 1;                         // particle-pass workgroups per environment
   long long tiles_per_wg = 1;
 };
-
 
 // The tape of a differentiable rollout (pic_tape_*, pic_adjoint.h).  One device block holds the checkpoints
 // (x, v every `every` steps, the first at pic_tape_start), every step's external field and all the backward's working memory,
@@ -792,6 +791,8 @@ void launch_shape_query(pic_handle* h, const void* x, int nenv, int shape, long 
                          h->ld, h->cfg.Ng, h->cfg.L, h->dx, idx, w);
   });
 }
+
+#include "host_diff.h"
 
 }  // namespace
 
@@ -1683,27 +1684,10 @@ static int64_t records_ahead(const pic_handle* h, int64_t nsteps) {
   return r.on ? (r.k + nsteps) / r.stride - r.k / r.stride : 0;
 }
 
-// e_t of n steps of `sc` into the tape (pic_adjoint.h: tape_ext_kernel)
-static int tape_record_ext(pic_handle* h, const StepControl& sc, int n) {
-  Tape& t = h->tape;
-  TapeExtArgs a{};
-  a.ext = sc.ctl.ext; a.act = sc.ctl.act; a.basis = sc.ctl.basis;
-  a.out = t.ext + (size_t)t.steps * h->cfg.num_envs * h->cfg.Ng;
-  a.ext_step = sc.ext_step; a.act_step = sc.act_step;
-  a.Ng = h->cfg.Ng; a.M = sc.ctl.M; a.num_envs = h->cfg.num_envs;
-  a.act_inline = sc.ctl.act && sc.inline_n > 0;
-  hipLaunchKernelGGL(tape_ext_kernel, dim3(h->cfg.num_envs, n), dim3(ABLOCK), 0, h->stream, a, sc.inline_act);
-  HIPCHK(h, hipGetLastError());
-  return PIC_OK;
-}
-
-static int tape_checkpoint(pic_handle* h, int64_t c) {
-  const size_t part = (size_t)h->cfg.num_envs * h->ld;
-  double* dst = h->tape.ck + (size_t)c * 2 * part;
-  HIPCHK(h, hipMemcpyAsync(dst, h->x, part * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(dst + part, h->v, part * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-  return PIC_OK;
-}
+// the host side of the differentiable rollouts (advance calls tape_record_ext, tape_checkpoint and tape_kl_enqueue)
+#include "host_phase.h"
+#include "host_tape.h"
+#include "host_tangent.h"
 
 // advance_steps, cut into parts where the recorder or an open tape needs the state between two steps.  A part runs up to the
 // nearest of the next recorded step, the next checkpoint step (every step of a tape with a KL attached, pic_tape_kl_start) and
@@ -1711,8 +1695,6 @@ static int tape_checkpoint(pic_handle* h, int64_t c) {
 // step of a call (full sweep D and a solve launch of its own; resident schedule: the end of a launch) -- stepping call by call
 // gives the same bits.  Behind a part come the record kernels of a recorded step, then the tape's copy of the
 // state after a checkpoint step.  Under a tape each part's external fields go on the tape first.
-static int tape_kl_enqueue(pic_handle* h);      // (defined with the smoothed KL's entries)
-
 static int advance(pic_handle* h, const StepControl& sc, int nsteps, double* hist, void* snap = nullptr) {
   Recorder& r = h->rec;
   Tape& t = h->tape;
@@ -2382,35 +2364,6 @@ int pic_step_feedback(pic_handle* h, int max_mode, int nsteps, double* actions_o
   return step_recording(h, sc, nsteps, hist, nullptr, actions_out, "pic_step_feedback");
 }
 
-// the gain law's record on an open tape (allocated by its first call) and one more gain of `gbytes`, within budget_bytes
-static int tape_law_reserve(pic_handle* h, size_t gbytes) {
-  Tape& t = h->tape;
-  const char* who = "pic_step_feedback_gain";
-  const size_t rows = ((size_t)t.max_steps * h->cfg.num_envs * 2 * h->act_modes * sizeof(double) + 255) & ~(size_t)255;
-  const size_t lbytes = t.law_block ? 0 : 3 * rows + (size_t)h->cfg.num_envs * h->cfg.Ng * sizeof(double);
-  if (t.budget > 0 && t.bytes + lbytes + gbytes > (size_t)t.budget)
-    return fail(h, PIC_ENOMEM, std::string(who) + ": the law's record and this call's gain would take the tape past budget_bytes (pic_tape_start)");
-  if (!t.law_block) {
-    if (alloc(t.law_block, lbytes) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(h, PIC_ENOMEM, std::string(who) + ": the tape's record of the law's steps does not fit on the device");
-    }
-    char* b = static_cast<char*>(t.law_block.get());
-    t.lact = (double*)b; t.lmodes = (double*)(b + rows); t.lcot = (double*)(b + 2 * rows); t.lE = (double*)(b + 3 * rows);
-    HIPCHK(h, hipMemsetAsync(t.lmodes, 0, rows, h->stream));
-    t.law.assign((size_t)t.max_steps, -1);
-    t.bytes += lbytes;
-  }
-  DeviceBuf<double> g;
-  if (alloc(g, gbytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(h, PIC_ENOMEM, std::string(who) + ": the tape's copy of the gain does not fit on the device");
-  }
-  t.gains.push_back(std::move(g));
-  t.bytes += gbytes;
-  return PIC_OK;
-}
-
 int pic_step_feedback_gain(pic_handle* h, int max_mode, const double* gain, int mem_kind, int nsteps, double* actions_out,
                            double* modes_out, double* hist) {
   const char* who = "pic_step_feedback_gain";
@@ -2552,273 +2505,6 @@ int pic_phase_kl(pic_handle* h, int nbins, double vmin, double vmax, const doubl
   if (e == hipSuccess) e = hipMemcpyAsync(kl, df + nb2, (size_t)E * sizeof(double), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   if (e != hipSuccess) return fail(h, PIC_EHIP, std::string("pic_phase_kl: ") + hipGetErrorString(e));
-  return PIC_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Smoothed phase-space density and KL (include/picstep.h: pic_phase_kl_smooth*; pic_phase.h)
-// ---------------------------------------------------------------------------------------------
-static int phase_check(pic_handle* h, const pic_phase_spec* s, int mem_kind, const char* who) {
-  if (!h) return PIC_EINVAL;
-  const std::string w(who);
-  if (!s || s->nx < 1 || s->nx > kPhaseMaxBins || s->nv < 1 || s->nv > kPhaseMaxBins ||
-      !(std::isfinite(s->vmin) && std::isfinite(s->vmax) && s->vmax > s->vmin))
-    return fail(h, PIC_EINVAL, w + ": need a spec with 1 <= nx, nv <= 1024 and finite vmin < vmax");
-  if ((mem_kind != PIC_HOST && mem_kind != PIC_DEVICE) ||
-      (s->feq && s->feq_mem_kind != PIC_HOST && s->feq_mem_kind != PIC_DEVICE))
-    return fail(h, PIC_EINVAL, w + ": mem_kind must be PIC_HOST or PIC_DEVICE");
-  if (h->fmt != FMT_F64) return fail(h, PIC_EINVAL, w + ": float64 particles and positions only");
-  if (!h->has_state) return fail(h, PIC_ESTATE, w + ": call pic_reset first");
-  return PIC_OK;
-}
-
-static PhaseArgs phase_args(const pic_handle* h, const pic_phase_spec* s, dim3& grid) {
-  PhaseArgs a{};
-  const long long N = h->cfg.N;
-  a.N = N; a.ld = h->ld; a.nx = s->nx; a.nv = s->nv;
-  a.rows = std::min(s->nx, std::max(1, kPhaseLdsBytes / (8 * s->nv)));
-  int bitsN = 1;                                     // N < 2^bitsN: N particles of 2^(62 - bitsN) units stay below 2^62
-  while (bitsN < 62 && (N >> bitsN) != 0) ++bitsN;
-  const int su = 62 - bitsN;
-  a.abits = (su + 1) / 2; a.bbits = su / 2;
-  a.L = h->cfg.L; a.vmin = s->vmin; a.vmax = s->vmax;
-  a.rdx = 1.0 / (h->cfg.L / s->nx);
-  a.rdv = 1.0 / ((s->vmax - s->vmin) / s->nv);
-  // A band's workgroups each flush up to rows * nv words: few workgroups per (environment, band) with long particle ranges
-  // (about 512 workgroups in all, at least 8192 particles each) keep the flush a small share of the pass.
-  const int bands = (s->nx + a.rows - 1) / a.rows;
-  const long long per = (long long)bands * h->cfg.num_envs;
-  const long long wpe = std::max(1LL, std::min((512 + per - 1) / per, (N + 8191) / 8192));
-  const long long ntiles = (N + 1) / 2;
-  a.tiles_per_wg = (ntiles + wpe * BLOCK - 1) / (wpe * BLOCK);
-  grid = dim3((unsigned)((ntiles + a.tiles_per_wg * BLOCK - 1) / (a.tiles_per_wg * BLOCK)), (unsigned)bands,
-              (unsigned)h->cfg.num_envs);
-  return a;
-}
-
-// The deposit of the particles x, v [env][ld] (the handle's, or a replayed state of the tape) and the finishing kernel behind
-// it, on the handle's stream.  acc: [env][nx][nv] zero (left zero); feq: device memory or null; d_kl, f, kl, g: device memory or
-// null (PhaseFinishArgs).
-static hipError_t phase_enqueue(pic_handle* h, const pic_phase_spec* s, const double* x, const double* v, unsigned long long* acc,
-                                const double* feq, const double* d_kl, double* f, double* kl, double* g, PhaseArgs& a) {
-  dim3 grid;
-  a = phase_args(h, s, grid);
-  hipLaunchKernelGGL(phase_deposit_kernel, grid, dim3(BLOCK), (size_t)a.rows * a.nv * sizeof(unsigned long long), h->stream,
-                     x, v, acc, a);
-  const double dx = h->cfg.L / s->nx, dv = (s->vmax - s->vmin) / s->nv;
-  PhaseFinishArgs fa{};
-  fa.acc = acc; fa.nb2 = s->nx * s->nv;
-  fa.unit = ldexp(1.0, -(a.abits + a.bbits));
-  fa.norm = h->cfg.n0 / dx / dv / (double)h->cfg.N;                       // objective.py:12, left to right
-  fa.dxdv = dx * dv;
-  fa.feq = feq; fa.feq_stride = s->feq_per_env ? fa.nb2 : 0;
-  fa.d_kl = d_kl; fa.f = f; fa.kl = kl; fa.g = g;
-  hipLaunchKernelGGL(phase_finish_kernel, dim3(h->cfg.num_envs), dim3(BLOCK), 0, h->stream, fa);
-  return hipGetLastError();
-}
-
-// Device memory holding `bytes` from src: src itself when it is device memory, else a copy in `buf`
-static hipError_t phase_input(pic_handle* h, const double* src, int kind, size_t bytes, DeviceBuf<double>& buf,
-                              const double** out) {
-  if (!src || kind == PIC_DEVICE) {
-    *out = src;
-    return hipSuccess;
-  }
-  hipError_t e = alloc(buf, bytes);
-  if (e == hipSuccess) e = hipMemcpyAsync(buf, src, bytes, hipMemcpyHostToDevice, h->stream);
-  *out = buf;
-  return e;
-}
-
-// Device memory for an output of `bytes`: dst itself when it is device memory, else (or when dst is null and `always`) `buf`
-static hipError_t phase_output(void* dst, int kind, size_t bytes, bool always, DeviceBuf<double>& buf, double** out) {
-  *out = nullptr;
-  if (dst && kind == PIC_DEVICE) {
-    *out = static_cast<double*>(dst);
-    return hipSuccess;
-  }
-  if (!dst && !always) return hipSuccess;
-  const hipError_t e = alloc(buf, bytes);
-  *out = buf;
-  return e;
-}
-
-int pic_phase_kl_smooth(pic_handle* h, const pic_phase_spec* s, int mem_kind, double* kl, double* f) {
-  int rc = phase_check(h, s, mem_kind, "pic_phase_kl_smooth");
-  if (rc) return rc;
-  if (!kl && !f) return fail(h, PIC_EINVAL, "pic_phase_kl_smooth: kl and f are both NULL");
-  if (kl && !s->feq) return fail(h, PIC_EINVAL, "pic_phase_kl_smooth: kl needs spec->feq");
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  const int E = h->cfg.num_envs;
-  const size_t nb2 = (size_t)s->nx * s->nv;
-  DeviceBuf<unsigned long long> acc;
-  DeviceBuf<double> dfeq, df, dkl;
-  const double* feq = nullptr;
-  double *fo = nullptr, *klo = nullptr;
-  PhaseArgs a;
-  hipError_t e = alloc_zeroed(acc, (size_t)E * nb2 * sizeof(unsigned long long), h->stream);
-  if (e == hipSuccess) e = phase_input(h, s->feq, s->feq_mem_kind, (s->feq_per_env ? E : 1) * nb2 * sizeof(double), dfeq, &feq);
-  if (e == hipSuccess) e = phase_output(f, mem_kind, (size_t)E * nb2 * sizeof(double), false, df, &fo);
-  if (e == hipSuccess) e = phase_output(kl, mem_kind, (size_t)E * sizeof(double), false, dkl, &klo);
-  if (e == hipSuccess) e = phase_enqueue(h, s, (const double*)h->x.get(), (const double*)h->v, acc, feq, nullptr, fo, klo, nullptr, a);
-  if (e == hipSuccess && f && fo != f) e = hipMemcpyAsync(f, fo, (size_t)E * nb2 * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess && kl && klo != kl) e = hipMemcpyAsync(kl, klo, (size_t)E * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) return fail(h, PIC_EHIP, std::string("pic_phase_kl_smooth: ") + hipGetErrorString(e));
-  return PIC_OK;
-}
-
-int pic_phase_kl_smooth_vjp(pic_handle* h, const pic_phase_spec* s, const double* cot_kl, int mem_kind, void* g_x, void* g_v) {
-  int rc = phase_check(h, s, mem_kind, "pic_phase_kl_smooth_vjp");
-  if (rc) return rc;
-  if (!s->feq || !cot_kl) return fail(h, PIC_EINVAL, "pic_phase_kl_smooth_vjp: needs spec->feq and cot_kl");
-  if (!g_x && !g_v) return PIC_OK;
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  const int E = h->cfg.num_envs;
-  const size_t nb2 = (size_t)s->nx * s->nv, pbytes = (size_t)E * h->cfg.N * sizeof(double);
-  DeviceBuf<unsigned long long> acc;
-  DeviceBuf<double> dfeq, dcot, dg, dgx, dgv;
-  const double *feq = nullptr, *cot = nullptr;
-  double *gx = nullptr, *gv = nullptr;
-  PhaseArgs a;
-  hipError_t e = alloc_zeroed(acc, (size_t)E * nb2 * sizeof(unsigned long long), h->stream);
-  if (e == hipSuccess) e = phase_input(h, s->feq, s->feq_mem_kind, (s->feq_per_env ? E : 1) * nb2 * sizeof(double), dfeq, &feq);
-  if (e == hipSuccess) e = phase_input(h, cot_kl, mem_kind, (size_t)E * sizeof(double), dcot, &cot);
-  if (e == hipSuccess) e = alloc(dg, (size_t)E * nb2 * sizeof(double));
-  if (e == hipSuccess) e = phase_output(g_x, mem_kind, pbytes, true, dgx, &gx);
-  if (e == hipSuccess) e = phase_output(g_v, mem_kind, pbytes, true, dgv, &gv);
-  if (e == hipSuccess) e = phase_enqueue(h, s, (const double*)h->x.get(), (const double*)h->v, acc, feq, cot, nullptr, nullptr, dg, a);
-  if (e == hipSuccess) {
-    const double dx = h->cfg.L / s->nx, dv = (s->vmax - s->vmin) / s->nv;
-    const double norm = h->cfg.n0 / dx / dv / (double)h->cfg.N;
-    const dim3 grid((unsigned)((h->cfg.N + BLOCK - 1) / BLOCK), (unsigned)E);
-    hipLaunchKernelGGL(phase_vjp_kernel, grid, dim3(BLOCK), 0, h->stream, (const double*)h->x.get(), (const double*)h->v,
-                       (const double*)dg, a, norm * a.rdx, norm * a.rdv, gx, gv);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess && g_x && gx != g_x) e = hipMemcpyAsync(g_x, gx, pbytes, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess && g_v && gv != g_v) e = hipMemcpyAsync(g_v, gv, pbytes, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) return fail(h, PIC_EHIP, std::string("pic_phase_kl_smooth_vjp: ") + hipGetErrorString(e));
-  return PIC_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// The smoothed KL of every taped step (include/picstep.h: pic_tape_kl_*; hooks: advance, walk_reverse)
-// ---------------------------------------------------------------------------------------------
-// bytes of the KL's block on a tape of max_steps steps: feq, acc, g, trace, cot; *offs: the parts' offsets
-static size_t tape_kl_layout(const pic_handle* h, const pic_phase_spec* s, int64_t max_steps, size_t (&offs)[5]) {
-  const size_t E = h->cfg.num_envs, nb2 = (size_t)s->nx * s->nv, rows = (size_t)max_steps * E * sizeof(double);
-  const size_t sizes[5] = {(s->feq_per_env ? E : 1) * nb2 * sizeof(double), E * nb2 * sizeof(unsigned long long),
-                           E * nb2 * sizeof(double), rows, rows};
-  size_t at = 0;
-  for (int i = 0; i < 5; ++i) {
-    offs[i] = at;
-    at += (sizes[i] + 255) & ~(size_t)255;
-  }
-  return at;
-}
-
-int pic_tape_kl_start(pic_handle* h, const pic_phase_spec* s) {
-  const char* who = "pic_tape_kl_start";
-  if (!h) return PIC_EINVAL;
-  Tape& t = h->tape;
-  if (!t.on) return fail(h, PIC_ESTATE, std::string(who) + ": no tape is open (pic_tape_start)");
-  if (t.kl) return fail(h, PIC_ESTATE, std::string(who) + ": the tape has a KL already");
-  if (t.steps != 0) return fail(h, PIC_ESTATE, std::string(who) + ": the tape holds steps already (attach the KL before the first)");
-  int rc = phase_check(h, s, PIC_HOST, who);
-  if (rc) return rc;
-  if (!s->feq) return fail(h, PIC_EINVAL, std::string(who) + ": needs spec->feq");
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  size_t offs[5];
-  const size_t bytes = tape_kl_layout(h, s, t.max_steps, offs);
-  if (t.budget > 0 && t.bytes + bytes > (size_t)t.budget)
-    return fail(h, PIC_ENOMEM, std::string(who) + ": the KL's memory (" + std::to_string(bytes) +
-                                   " bytes) would take the tape past budget_bytes (pic_tape_start)");
-  DeviceBuf<void> block;
-  if (alloc(block, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(h, PIC_ENOMEM, std::string(who) + ": the KL's memory (" + std::to_string(bytes) + " bytes) does not fit on the device");
-  }
-  char* b = static_cast<char*>(block.get());
-  const size_t fbytes = (s->feq_per_env ? (size_t)h->cfg.num_envs : 1) * s->nx * s->nv * sizeof(double);
-  hipError_t e = hipMemcpyAsync(b + offs[0], s->feq, fbytes,
-                                s->feq_mem_kind == PIC_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(b + offs[1], 0, offs[2] - offs[1], h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);          // (the caller's feq may go away behind this call)
-  if (e != hipSuccess) return fail(h, PIC_EHIP, std::string(who) + ": " + hipGetErrorString(e));
-  t.kl_block = std::move(block);
-  t.kl_feq = (double*)(b + offs[0]); t.kl_acc = (unsigned long long*)(b + offs[1]); t.kl_g = (double*)(b + offs[2]);
-  t.kl_trace = (double*)(b + offs[3]); t.kl_cot = (double*)(b + offs[4]);
-  t.kl_spec = *s;
-  t.kl_spec.feq = t.kl_feq;
-  t.kl_spec.feq_mem_kind = PIC_DEVICE;
-  t.kl_flag.assign((size_t)t.max_steps, 0);
-  t.bytes += bytes;
-  t.kl = true;
-  return PIC_OK;
-}
-
-// KL~ of the handle's particles into row t.steps of the trace (advance, behind the step that is about to be counted)
-static int tape_kl_enqueue(pic_handle* h) {
-  Tape& t = h->tape;
-  PhaseArgs a;
-  HIPCHK(h, phase_enqueue(h, &t.kl_spec, (const double*)h->x.get(), (const double*)h->v, t.kl_acc, t.kl_feq, nullptr, nullptr,
-                          t.kl_trace + (size_t)t.steps * h->cfg.num_envs, nullptr, a));
-  return PIC_OK;
-}
-
-// the KL's part of reverse step s (walk_reverse): lambda += k-bar_s dKL~/d(x', v') at the replayed state x', v' the step left
-static int tape_kl_reverse(pic_handle* h, int64_t s, const double* x, const double* v, double* lx, double* lv) {
-  Tape& t = h->tape;
-  const int E = h->cfg.num_envs;
-  const pic_phase_spec& sp = t.kl_spec;
-  PhaseArgs a;
-  HIPCHK(h, phase_enqueue(h, &sp, x, v, t.kl_acc, t.kl_feq, t.kl_cot + (size_t)s * E, nullptr, nullptr, t.kl_g, a));
-  const double dx = h->cfg.L / sp.nx, dv = (sp.vmax - sp.vmin) / sp.nv;
-  const double norm = h->cfg.n0 / dx / dv / (double)h->cfg.N;
-  const long long ntiles = (h->cfg.N + 1) / 2;
-  const dim3 grid((unsigned)((ntiles + BLOCK - 1) / BLOCK), (unsigned)E);
-  hipLaunchKernelGGL(phase_vjp_add_kernel, grid, dim3(BLOCK), 0, h->stream, x, v, (const double*)t.kl_g, a, norm * a.rdx,
-                     norm * a.rdv, lx, lv);
-  t.launches += 3;
-  return PIC_OK;
-}
-
-int pic_tape_kl(pic_handle* h, int mem_kind, double* kl) {
-  const char* who = "pic_tape_kl";
-  if (!h) return PIC_EINVAL;
-  Tape& t = h->tape;
-  if (!t.on || !t.kl) return fail(h, PIC_ESTATE, std::string(who) + ": no tape with a KL is open (pic_tape_kl_start)");
-  if ((mem_kind != PIC_HOST && mem_kind != PIC_DEVICE) || !kl) return fail(h, PIC_EINVAL, std::string(who) + ": bad mem_kind or null kl");
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (t.steps == 0) return PIC_OK;
-  const bool host = mem_kind == PIC_HOST;
-  HIPCHK(h, hipMemcpyAsync(kl, t.kl_trace, (size_t)t.steps * h->cfg.num_envs * sizeof(double),
-                           host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
-  if (host) HIPCHK(h, hipStreamSynchronize(h->stream));
-  return PIC_OK;
-}
-
-int pic_tape_kl_cot(pic_handle* h, const double* cot_kl, int mem_kind, int64_t first_step, int64_t nsteps) {
-  const char* who = "pic_tape_kl_cot";
-  if (!h) return PIC_EINVAL;
-  Tape& t = h->tape;
-  if (!t.on || !t.kl) return fail(h, PIC_ESTATE, std::string(who) + ": no tape with a KL is open (pic_tape_kl_start)");
-  if (mem_kind != PIC_HOST && mem_kind != PIC_DEVICE) return fail(h, PIC_EINVAL, std::string(who) + ": bad mem_kind");
-  if (first_step < 0 || nsteps < 0 || first_step > t.steps || nsteps > t.steps - first_step)
-    return fail(h, PIC_EINVAL, std::string(who) + ": rows outside the " + std::to_string(t.steps) + " steps taped so far");
-  if (nsteps == 0) return PIC_OK;
-  if (t.walk && first_step + nsteps - 1 > t.wnext)
-    return fail(h, PIC_ESTATE, std::string(who) + ": the walk in progress has reversed step " + std::to_string(first_step + nsteps - 1) +
-                                   " already");
-  if (cot_kl) {
-    HIPCHK(h, hipSetDevice(h->cfg.device_id));
-    const size_t E = h->cfg.num_envs;
-    HIPCHK(h, hipMemcpyAsync(t.kl_cot + (size_t)first_step * E, cot_kl, (size_t)nsteps * E * sizeof(double),
-                             mem_kind == PIC_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->stream));
-  }
-  std::fill(t.kl_flag.begin() + first_step, t.kl_flag.begin() + first_step + nsteps, cot_kl ? 1 : 0);
   return PIC_OK;
 }
 
@@ -3006,684 +2692,6 @@ int pic_bad_count(pic_handle* h, int64_t* count) {
   HIPCHK(h, hipStreamSynchronize(h->stream));
   *count = (int64_t)c;
   return PIC_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Differentiable rollouts (include/picstep.h: pic_tape_*; kernels: pic_adjoint.h; hook: advance)
-// ---------------------------------------------------------------------------------------------
-// the forward sweeps' geometry and fixed point (sweep_args), the adjoint deposits' headroom and the Yoshida-4 coefficients
-static AdjArgs adjoint_args(const pic_handle* h) {
-  const SweepArgs s = sweep_args(h);
-  AdjArgs a{};
-  a.N = s.N; a.ld = s.ld; a.Ng = s.Ng; a.fg = s.fg; a.magic = s.magic;
-  int b = 0;
-  while (((int64_t)1 << b) < h->cfg.N) ++b;
-  a.bitsN = b;
-  a.L = s.L; a.dx = s.dx; a.dt = s.dt; a.scale = s.scale; a.N_over_L = s.N_over_L;
-  for (int i = 0; i < 4; ++i) { a.c[i] = h->cs[i]; a.d[i] = h->ds[i]; }
-  return a;
-}
-
-// bytes of a tape of max_steps steps with a checkpoint every `every` steps; *offs: the parts' offsets in its block
-static size_t tape_layout(const pic_handle* h, int64_t max_steps, int64_t every, size_t (&offs)[12]) {
-  const size_t E = h->cfg.num_envs, part = E * h->ld * sizeof(double), mesh = E * h->cfg.Ng * sizeof(double);
-  const int64_t nck = max_steps / every + 1;
-  const size_t sizes[12] = {(size_t)nck * 2 * part, (size_t)max_steps * mesh, (size_t)(every + 1) * 2 * part,
-                            (size_t)every * 3 * mesh, (size_t)every * mesh, 2 * part, (size_t)max_steps * 3 * E * sizeof(double),
-                            (size_t)max_steps * mesh, mesh, E * h->cfg.Ng * sizeof(acc_t), (E + 2) * sizeof(unsigned long long),
-                            (size_t)max_steps * E * 2 * h->act_modes * sizeof(double)};
-  size_t at = 0;
-  for (int i = 0; i < 12; ++i) {
-    offs[i] = at;
-    at += (sizes[i] + 255) & ~(size_t)255;
-  }
-  return at;
-}
-
-int pic_tape_start(pic_handle* h, const pic_tape_config* c) {
-  if (!h || !c) return fail(h, PIC_EINVAL, "pic_tape_start: null argument");
-  if (h->tape.on) return fail(h, PIC_ESTATE, "pic_tape_start: a tape is open (pic_tape_stop first)");
-  if (h->fmt != FMT_F64)
-    return fail(h, PIC_EINVAL, "pic_tape_start: the tape needs float64 particles with float64 positions (float32 and fixed32 are "
-                               "not differentiated)");
-  if (h->acc_kind != PIC_ACC_FIX64)
-    return fail(h, PIC_EINVAL, "pic_tape_start: the tape needs the 64-bit fixed-point accumulator (PIC_ACC_F64 sums depend on the "
-                               "order of the adds, so a replay would not be bitwise)");
-  if (h->cfg.interpol != PIC_CIC)
-    return fail(h, PIC_EINVAL, "pic_tape_start: the tape needs CIC (the reference's TSC weights jump at cell edges: its cost is "
-                               "not differentiable)");
-  if (h->scheme != PIC_YOSHIDA4)
-    return fail(h, PIC_EINVAL, "pic_tape_start: the tape differentiates the Yoshida-4 integrator only");
-  if (c->max_steps < 1 || c->checkpoint_every < 0 || c->budget_bytes < 0)
-    return fail(h, PIC_EINVAL, "pic_tape_start: need max_steps >= 1, checkpoint_every >= 0, budget_bytes >= 0");
-  if (!h->has_state) return fail(h, PIC_ESTATE, "pic_tape_start: call pic_reset first");
-  if (h->mid_stage) return fail(h, PIC_ESTATE, "pic_tape_start: a staged step is in progress");
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  int64_t every = c->checkpoint_every;
-  size_t offs[12];
-  if (every == 0) {
-    // about sqrt(max_steps) (checkpoints and one segment's replay weigh alike); when that exceeds budget_bytes, the interval
-    // that needs the fewest bytes
-    every = std::min<int64_t>(c->max_steps, std::max<int64_t>(1, (int64_t)std::ceil(std::sqrt((double)c->max_steps))));
-    if (c->budget_bytes > 0 && tape_layout(h, c->max_steps, every, offs) > (size_t)c->budget_bytes) {
-      size_t best = tape_layout(h, c->max_steps, every, offs);
-      for (int64_t s = 1; s <= c->max_steps; ++s) {
-        const size_t b = tape_layout(h, c->max_steps, s, offs);
-        if (b < best) { best = b; every = s; }
-      }
-    }
-  }
-  every = std::min<int64_t>(every, c->max_steps);
-  const size_t bytes = tape_layout(h, c->max_steps, every, offs);
-  if (c->budget_bytes > 0 && bytes > (size_t)c->budget_bytes)
-    return fail(h, PIC_ENOMEM, "pic_tape_start: the tape needs " + std::to_string(bytes) + " bytes, more than budget_bytes");
-  DeviceBuf<void> block;
-  if (alloc(block, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(h, PIC_ENOMEM, "pic_tape_start: the tape (" + std::to_string(bytes) + " bytes) does not fit on the device");
-  }
-  Tape& t = h->tape;
-  t = Tape{};
-  t.block = std::move(block);
-  char* b = static_cast<char*>(t.block.get());
-  t.ck = (double*)(b + offs[0]); t.ext = (double*)(b + offs[1]); t.seg = (double*)(b + offs[2]); t.F = (double*)(b + offs[3]);
-  t.M = (double*)(b + offs[4]); t.lam = (double*)(b + offs[5]); t.cot = (double*)(b + offs[6]); t.gext = (double*)(b + offs[7]);
-  t.nu = (double*)(b + offs[8]); t.acc = (acc_t*)(b + offs[9]); t.cmax = (unsigned long long*)(b + offs[10]);
-  t.counters = t.cmax + h->cfg.num_envs;
-  t.gact = h->act_modes ? (double*)(b + offs[11]) : nullptr;
-  t.max_steps = c->max_steps; t.every = every; t.nck = c->max_steps / every + 1; t.bytes = bytes;
-  t.budget = c->budget_bytes;
-  HIPCHK(h, hipMemsetAsync(b + offs[9], 0, offs[11] - offs[9], h->stream));    // acc, cmax, counters
-  int rc = tape_checkpoint(h, 0);
-  if (rc) { t = Tape{}; return rc; }
-  t.on = true;
-  return PIC_OK;
-}
-
-int pic_tape_stop(pic_handle* h) {
-  if (!h) return PIC_EINVAL;
-  if (!h->tape.block) return PIC_OK;
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  const hipError_t e = hipStreamSynchronize(h->stream);
-  h->tape = Tape{};
-  if (e != hipSuccess) return fail(h, PIC_EHIP, std::string("pic_tape_stop: ") + hipGetErrorString(e));
-  return PIC_OK;
-}
-
-int pic_tape_stats(pic_handle* h, pic_tape_info* out) {
-  if (!h || !out) return fail(h, PIC_EINVAL, "pic_tape_stats: null argument");
-  std::memset(out, 0, sizeof(*out));
-  const Tape& t = h->tape;
-  if (!t.on) return PIC_OK;
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  unsigned long long cnt[2] = {0, 0};
-  HIPCHK(h, hipMemcpyAsync(cnt, t.counters, sizeof(cnt), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  out->steps = t.steps;
-  out->checkpoint_every = t.every;
-  out->bytes = (int64_t)t.bytes;
-  out->replay_mismatches = (int64_t)cnt[0];
-  out->unit_retries = 0;              // the adjoint deposits' unit cannot overflow (pic_adjoint.h: adj_unit_exp)
-  out->replay_bad_positions = (int64_t)cnt[1];
-  out->launches = t.launches;
-  return PIC_OK;
-}
-
-// the fields of one replayed sub-stage: deposit in t.acc -> E (+ e_t) into `E_out`, the row cleared behind its read
-static void tape_solve(pic_handle* h, const double* ext, double* E_out) {
-  SolveIO io{};
-  io.acc = h->tape.acc; io.acc_clear = h->tape.acc;
-  io.out.ext = ext; io.out.E = E_out; io.out.num_envs = h->cfg.num_envs;
-  // (not launch_solve: the replay's launches stay out of pic_profile's counters)
-  hipLaunchKernelGGL(field_solve_kernel, dim3(h->cfg.num_envs), dim3(SBLOCK), h->solve_lds, h->stream, io, solve_args(h, 1));
-  ++h->tape.launches;
-}
-
-// E-bar of the field step s started from (pic_adjoint.h: law_adjoint_kernel): the gain law's term if step s is a law step
-// (e-bar_s must be complete), plus cot_m [env][2 mc] on its modes (either may be absent).  Returns where it went (t.lE, or t.wE
-// without a law block), or null: nothing to add.
-static const double* tape_mode_cot(pic_handle* h, int64_t s, const double* cot_m, int mc) {
-  Tape& t = h->tape;
-  const bool lawstep = s >= 0 && s < t.steps && !t.law.empty() && t.law[(size_t)s] >= 0;
-  if (!lawstep && !cot_m) return nullptr;
-  double* Ebar = t.lE ? t.lE : t.wE;
-  const int E = h->cfg.num_envs, Ng = h->cfg.Ng, M = h->act_modes;
-  const int mg = lawstep ? M : 0, R = std::max(mg, cot_m ? mc : 0);
-  hipLaunchKernelGGL(law_adjoint_kernel, dim3(E), dim3(ABLOCK), (size_t)2 * (mg + R) * sizeof(double), h->stream,
-                     lawstep ? (const double*)(t.gext + (size_t)s * E * Ng) : nullptr, (const double*)h->basis,
-                     lawstep ? (const double*)t.gains[(size_t)t.law[(size_t)s]] : nullptr, cot_m, (const double*)h->tw, h->tw_rows,
-                     Ebar, Ng, M, cot_m ? mc : 0);
-  ++t.launches;
-  return Ebar;
-}
-
-// the launch geometry of the reverse pass
-struct WalkGeom {
-  dim3 pgrid, mgrid;
-  size_t acc_lds, mesh_lds;
-};
-
-static WalkGeom walk_geom(const pic_handle* h) {
-  const int E = h->cfg.num_envs, Ng = h->cfg.Ng;
-  long long gx = (h->cfg.N + (long long)ABLOCK * 8 - 1) / ((long long)ABLOCK * 8);       // ~8 particles per lane
-  gx = std::max<long long>(1, std::min<long long>(gx, std::max(1, 2048 / E)));
-  return {dim3((unsigned)gx, E), dim3(E), (size_t)(Ng + 1) * sizeof(unsigned long long), (size_t)Ng * sizeof(double)};
-}
-
-// a walk from step T: lambda, e-bar, the counters and the launch count at zero; twiddles for M_o modes
-static int walk_open(pic_handle* h, int mo) {
-  Tape& t = h->tape;
-  const size_t part = (size_t)h->cfg.num_envs * h->ld, mesh = (size_t)h->cfg.num_envs * h->cfg.Ng;
-  t.walk = false;
-  if (mo > 0) {
-    const int rc = ensure_twiddle(h, mo);
-    if (rc) return rc;
-    if (!t.lE && !t.wE && alloc(t.wE, mesh * sizeof(double)) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(h, PIC_ENOMEM, "pic_tape_walk_begin: the walk's mode cotangent does not fit on the device");
-    }
-  }
-  t.launches = 0;
-  HIPCHK(h, hipMemsetAsync(t.counters, 0, 2 * sizeof(unsigned long long), h->stream));
-  if (t.steps > 0) HIPCHK(h, hipMemsetAsync(t.gext, 0, (size_t)t.steps * mesh * sizeof(double), h->stream));
-  HIPCHK(h, hipMemsetAsync(t.lam, 0, 2 * part * sizeof(double), h->stream));
-  t.walk = true;
-  t.wnext = t.steps - 1;
-  t.wmo = mo;
-  return PIC_OK;
-}
-
-// restore the checkpoint of segment sgi into the replay states (never into the handle's x, v), replay it step by step and
-// compare its end with the state the forward left there
-static int walk_replay(pic_handle* h, int64_t sgi, const AdjArgs& a, const WalkGeom& g) {
-  Tape& t = h->tape;
-  const size_t part = (size_t)h->cfg.num_envs * h->ld, mesh = (size_t)h->cfg.num_envs * h->cfg.Ng;
-  const int64_t nseg = (t.steps + t.every - 1) / t.every;
-  const int64_t t0 = sgi * t.every, len = std::min<int64_t>(t.every, t.steps - t0);
-  HIPCHK(h, hipMemcpyAsync(t.seg, t.ck + (size_t)sgi * 2 * part, 2 * part * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-  for (int64_t i = 0; i < len; ++i) {
-    const double* x = t.seg + (size_t)i * 2 * part;
-    AdjStep st{x, x + part, t.F + (size_t)i * 3 * mesh, (long long)mesh};
-    const double* e_t = t.ext + (size_t)(t0 + i) * mesh;
-    double* xo = t.seg + (size_t)(i + 1) * 2 * part;
-    hipLaunchKernelGGL(adjoint_replay_kernel<1>, g.pgrid, dim3(ABLOCK), g.acc_lds, h->stream, st, t.acc, nullptr, nullptr, a, t.counters + 1);
-    tape_solve(h, e_t, t.F + (size_t)(i * 3 + 0) * mesh);
-    hipLaunchKernelGGL(adjoint_replay_kernel<2>, g.pgrid, dim3(ABLOCK), g.acc_lds, h->stream, st, t.acc, nullptr, nullptr, a, t.counters + 1);
-    tape_solve(h, e_t, t.F + (size_t)(i * 3 + 1) * mesh);
-    hipLaunchKernelGGL(adjoint_replay_kernel<3>, g.pgrid, dim3(ABLOCK), g.acc_lds, h->stream, st, t.acc, nullptr, nullptr, a, t.counters + 1);
-    tape_solve(h, e_t, t.F + (size_t)(i * 3 + 2) * mesh);
-    hipLaunchKernelGGL(adjoint_replay_kernel<4>, g.pgrid, dim3(ABLOCK), g.acc_lds, h->stream, st, t.acc, xo, xo + part, a, t.counters + 1);
-    tape_solve(h, nullptr, t.M + (size_t)i * mesh);
-    t.launches += 4;
-  }
-  const double* end = t.seg + (size_t)len * 2 * part;
-  const double* want_x = sgi + 1 < nseg ? t.ck + (size_t)(sgi + 1) * 2 * part : (const double*)h->x.get();
-  const double* want_v = sgi + 1 < nseg ? want_x + part : (const double*)h->v;
-  hipLaunchKernelGGL(tape_compare_kernel, g.pgrid, dim3(ABLOCK), 0, h->stream, end, end + part, want_x, want_v, h->cfg.N, h->ld, t.counters);
-  ++t.launches;
-  return PIC_OK;
-}
-
-// cotangents a reverse step injects, all on the device: on the modes of the field the step left (mc modes) and on the state it
-// left (rows of cld elements); each may be null
-struct WalkCot {
-  const double* modes = nullptr;
-  int mc = 0;
-  const double* x = nullptr;
-  const double* v = nullptr;
-  long long cld = 0;
-};
-
-// reverse step t.wnext (its energy cotangents in t.cot's row): first the replay of its segment if it is the segment's last step
-static int walk_reverse(pic_handle* h, const WalkCot& c, const AdjArgs& a, const WalkGeom& g) {
-  Tape& t = h->tape;
-  const int E = h->cfg.num_envs;
-  const size_t part = (size_t)E * h->ld, mesh = (size_t)E * h->cfg.Ng;
-  const int64_t s = t.wnext, sgi = s / t.every, t0 = sgi * t.every, i = s - t0;
-  if (s + 1 == std::min<int64_t>(t0 + t.every, t.steps)) {
-    const int rc = walk_replay(h, sgi, a, g);
-    if (rc) return rc;
-  }
-  double* lx = t.lam;
-  double* lv = t.lam + part;
-  const double* x = t.seg + (size_t)i * 2 * part;
-  const AdjStep st{x, x + part, t.F + (size_t)i * 3 * mesh, (long long)mesh};
-  const double* cot = t.cot + (size_t)s * 3 * E;
-  double* ge = t.gext + (size_t)s * mesh;
-  if (t.kl && t.kl_flag[(size_t)s]) {       // lambda_x' += k-bar_s dKL~/dx', lambda_v' += k-bar_s dKL~/dv' 
-    const double* xn = t.seg + (size_t)(i + 1) * 2 * part;
-    const int rc = tape_kl_reverse(h, s, xn, xn + part, lx, lv);
-    if (rc) return rc;
-  }
-  // the field step s left is read by the law of step s + 1 and by the caller's observation: E-bar joins its refresh adjoint
-  const double* Ebar = tape_mode_cot(h, s + 1, c.modes, c.mc);
-  hipLaunchKernelGGL(adjoint_mesh_kernel, g.mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, nullptr, t.cmax, t.M + (size_t)i * mesh, cot, ge, t.nu, a, E,
-                     Ebar);
-  hipLaunchKernelGGL(adjoint_pass_kernel<3>, g.pgrid, dim3(ABLOCK), 0, h->stream, st, t.nu, cot, lx, lv, t.cmax, a, E, c.x, c.v, c.cld);
-  hipLaunchKernelGGL(adjoint_deposit_kernel<3>, g.pgrid, dim3(ABLOCK), g.acc_lds, h->stream, st, lv, t.cmax, t.acc, a);
-  hipLaunchKernelGGL(adjoint_mesh_kernel, g.mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, t.acc, t.cmax, nullptr, nullptr, ge, t.nu, a, E, nullptr);
-  hipLaunchKernelGGL(adjoint_pass_kernel<2>, g.pgrid, dim3(ABLOCK), 0, h->stream, st, t.nu, nullptr, lx, lv, t.cmax, a, E, nullptr, nullptr, 0ll);
-  hipLaunchKernelGGL(adjoint_deposit_kernel<2>, g.pgrid, dim3(ABLOCK), g.acc_lds, h->stream, st, lv, t.cmax, t.acc, a);
-  hipLaunchKernelGGL(adjoint_mesh_kernel, g.mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, t.acc, t.cmax, nullptr, nullptr, ge, t.nu, a, E, nullptr);
-  hipLaunchKernelGGL(adjoint_pass_kernel<1>, g.pgrid, dim3(ABLOCK), 0, h->stream, st, t.nu, nullptr, lx, lv, t.cmax, a, E, nullptr, nullptr, 0ll);
-  hipLaunchKernelGGL(adjoint_deposit_kernel<1>, g.pgrid, dim3(ABLOCK), g.acc_lds, h->stream, st, lv, t.cmax, t.acc, a);
-  hipLaunchKernelGGL(adjoint_mesh_kernel, g.mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, t.acc, t.cmax, nullptr, nullptr, ge, t.nu, a, E, nullptr);
-  hipLaunchKernelGGL(adjoint_pass_kernel<0>, g.pgrid, dim3(ABLOCK), 0, h->stream, st, t.nu, nullptr, lx, lv, t.cmax, a, E, nullptr, nullptr, 0ll);
-  t.launches += 11;
-  --t.wnext;
-  HIPCHK(h, hipGetLastError());
-  return PIC_OK;
-}
-
-// after the last reverse step: the field at the tape start (read by a first law step and by the caller's observation c.modes)
-// and the caller's cotangents on the starting state reach lambda_0 = (g_x0, g_v0)
-static int walk_close(pic_handle* h, const WalkCot& c, const AdjArgs& a, const WalkGeom& g) {
-  Tape& t = h->tape;
-  const int E = h->cfg.num_envs;
-  const size_t part = (size_t)E * h->ld;
-  const double* Ebar = t.steps > 0 ? tape_mode_cot(h, 0, c.modes, c.mc) : nullptr;
-  const bool field = Ebar != nullptr;
-  if (field) {      // lambda_x0 += s W'(x_0) . K^T E-bar_0 at the tape-start positions
-    hipLaunchKernelGGL(adjoint_mesh_kernel, g.mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, nullptr, t.cmax, nullptr, nullptr, nullptr, t.nu, a, E,
-                       Ebar);
-    ++t.launches;
-  }
-  if (field || c.x || c.v) {
-    hipLaunchKernelGGL(adjoint_start_kernel, g.pgrid, dim3(ABLOCK), 0, h->stream, (const double*)t.ck, field ? (const double*)t.nu : nullptr,
-                       t.lam, a, t.lam + part, c.x, c.v, c.cld);
-    ++t.launches;
-  }
-  t.walk = false;
-  HIPCHK(h, hipGetLastError());
-  return PIC_OK;
-}
-
-// waits for the stream; PIC_ESTATE if a replay of the walk left the forward's trajectory (particles written through
-// pic_device_ptrs while taping): the gradient would be wrong
-static int walk_check(pic_handle* h, const std::string& w) {
-  unsigned long long cnt = 0;
-  HIPCHK(h, hipMemcpyAsync(&cnt, h->tape.counters, sizeof(cnt), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (cnt)
-    return fail(h, PIC_ESTATE, w + ": the replay differs from the taped forward in " + std::to_string(cnt) +
-                                   " particle values (were the particles written while the tape was open?): the gradient is not valid");
-  return PIC_OK;
-}
-
-// the whole reverse pass in one call: a walk over every step with the whole trajectory's cotangents
-static int tape_backward(pic_handle* h, const char* who, const double* cot_hist, const void* cot_x, const void* cot_v,
-                         const double* cot_modes, int mem_kind, double* g_ext, double* g_actions, void* g_x0, void* g_v0,
-                         double* modes_out) {
-  Tape& t = h->tape;
-  const std::string w(who);
-  if (!t.on) return fail(h, PIC_ESTATE, w + ": no tape is open (pic_tape_start)");
-  if (mem_kind != PIC_HOST && mem_kind != PIC_DEVICE) return fail(h, PIC_EINVAL, w + ": bad mem_kind");
-  if (g_actions && !t.gact)
-    return fail(h, PIC_ESTATE, w + ": g_actions needs an actuator set before pic_tape_start (pic_set_actuator)");
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  const int E = h->cfg.num_envs, Ng = h->cfg.Ng;
-  const int64_t T = t.steps;
-  const size_t mesh = (size_t)E * Ng;
-  const hipMemcpyKind in = mem_kind == PIC_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-  const hipMemcpyKind outk = mem_kind == PIC_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-  const AdjArgs a = adjoint_args(h);
-  const WalkGeom g = walk_geom(h);
-  int rc = walk_open(h, 0);
-  if (rc) return rc;
-  double* lx = t.lam;
-  double* lv = t.lam + (size_t)E * h->ld;
-  if (cot_hist && T > 0) HIPCHK(h, hipMemcpyAsync(t.cot, cot_hist, (size_t)T * 3 * E * sizeof(double), in, h->stream));
-  else if (T > 0) HIPCHK(h, hipMemsetAsync(t.cot, 0, (size_t)T * 3 * E * sizeof(double), h->stream));
-  if (cot_x) rc = upload(h, lx, cot_x, mem_kind);
-  if (!rc && cot_v) rc = upload(h, lv, cot_v, mem_kind);
-  if (rc) { t.walk = false; return rc; }
-  // steps of the gain law: the action of step s + 1 depends on the field step s left, so the refresh adjoint of
-  // step s also carries E-bar_{s+1} = J^T (G^T a-bar_{s+1} + m-bar_{s+1}); E-bar_0 reaches x_0 through the field at the start
-  const bool law = !t.law.empty();
-  const int M = h->act_modes;
-  const size_t lrow = (size_t)E * 2 * M;
-  if (law && T > 0) {
-    if (cot_modes) HIPCHK(h, hipMemcpyAsync(t.lcot, cot_modes, (size_t)T * lrow * sizeof(double), in, h->stream));
-    else HIPCHK(h, hipMemsetAsync(t.lcot, 0, (size_t)T * lrow * sizeof(double), h->stream));
-  }
-  // the law's m-bar of step s + 1 is a cotangent on the field step s left: the walk's mode cotangent of step s (law steps only)
-  auto law_cot = [&](int64_t s) {
-    WalkCot c;
-    if (law && s < T && t.law[(size_t)s] >= 0) { c.modes = t.lcot + (size_t)s * lrow; c.mc = M; }
-    return c;
-  };
-  while (t.wnext >= 0) {
-    rc = walk_reverse(h, law_cot(t.wnext + 1), a, g);
-    if (rc) { t.walk = false; return rc; }
-  }
-  rc = walk_close(h, law_cot(0), a, g);
-  if (rc) return rc;
-  if (g_ext && T > 0) HIPCHK(h, hipMemcpyAsync(g_ext, t.gext, (size_t)T * mesh * sizeof(double), outk, h->stream));
-  if (modes_out && T > 0) {
-    if (law) HIPCHK(h, hipMemcpyAsync(modes_out, t.lmodes, (size_t)T * lrow * sizeof(double), outk, h->stream));
-    else if (mem_kind == PIC_HOST) std::memset(modes_out, 0, (size_t)T * lrow * sizeof(double));
-    else HIPCHK(h, hipMemsetAsync(modes_out, 0, (size_t)T * lrow * sizeof(double), h->stream));
-  }
-  if (g_actions && T > 0) {
-    hipLaunchKernelGGL(adjoint_actions_kernel, dim3(E, (unsigned)T), dim3(ABLOCK), 0, h->stream, t.gext, h->basis,
-                       mem_kind == PIC_HOST ? t.gact : g_actions, Ng, M, E);
-    ++t.launches;
-    if (mem_kind == PIC_HOST)
-      HIPCHK(h, hipMemcpyAsync(g_actions, t.gact, (size_t)T * lrow * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  }
-  if (g_x0) rc = download(h, g_x0, lx, mem_kind);
-  if (!rc && g_v0) rc = download(h, g_v0, lv, mem_kind);
-  if (rc) return rc;
-  HIPCHK(h, hipGetLastError());
-  // host outputs: the call waits anyway, so a replay that left the forward's trajectory is an error here, not only a count in
-  // pic_tape_stats
-  return mem_kind == PIC_HOST ? walk_check(h, w) : PIC_OK;
-}
-
-int pic_tape_backward(pic_handle* h, const double* cot_hist, const void* cot_x, const void* cot_v, int mem_kind, double* g_ext,
-                      double* g_actions, void* g_x0, void* g_v0) {
-  if (!h) return PIC_EINVAL;
-  return tape_backward(h, "pic_tape_backward", cot_hist, cot_x, cot_v, nullptr, mem_kind, g_ext, g_actions, g_x0, g_v0, nullptr);
-}
-
-int pic_tape_backward_feedback(pic_handle* h, const double* cot_hist, const void* cot_x, const void* cot_v, const double* cot_modes,
-                               int mem_kind, double* g_ext, double* g_actions, void* g_x0, void* g_v0, double* modes_out) {
-  if (!h) return PIC_EINVAL;
-  if (modes_out && !h->tape.gact)
-    return fail(h, PIC_ESTATE, "pic_tape_backward_feedback: modes_out needs an actuator set before pic_tape_start (pic_set_actuator)");
-  return tape_backward(h, "pic_tape_backward_feedback", cot_hist, cot_x, cot_v, cot_modes, mem_kind, g_ext, g_actions, g_x0, g_v0,
-                       modes_out);
-}
-
-int pic_tape_walk_begin(pic_handle* h, int obs_modes, int mem_kind) {
-  if (!h) return PIC_EINVAL;
-  if (!h->tape.on) return fail(h, PIC_ESTATE, "pic_tape_walk_begin: no tape is open (pic_tape_start)");
-  if (obs_modes < 1 || obs_modes >= h->cfg.Ng) return fail(h, PIC_EINVAL, "pic_tape_walk_begin: need 1 <= obs_modes < N_mesh");
-  if (mem_kind != PIC_HOST && mem_kind != PIC_DEVICE) return fail(h, PIC_EINVAL, "pic_tape_walk_begin: bad mem_kind");
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  return walk_open(h, obs_modes);
-}
-
-// the cotangents a walk call injects (mem_kind's pointers; rows of N elements); host ones are staged on the device through
-// wstage: [2][env][N] particles, then [env][2 M_o] modes
-static int walk_cot(pic_handle* h, const void* cot_x, const void* cot_v, const double* cot_modes, bool host, WalkCot* c) {
-  Tape& t = h->tape;
-  const size_t E = h->cfg.num_envs, N = h->cfg.N;
-  c->x = static_cast<const double*>(cot_x);
-  c->v = static_cast<const double*>(cot_v);
-  c->modes = cot_modes;
-  c->mc = t.wmo;
-  c->cld = (long long)N;
-  if (!host || !(cot_x || cot_v || cot_modes)) return PIC_OK;
-  const size_t bytes = (2 * E * N + E * 2 * t.wmo) * sizeof(double);
-  if (bytes > t.wstage_bytes) {
-    t.wstage_bytes = 0;
-    const int rc = regrow(h, t.wstage, bytes, "pic_tape_walk: the staging of host cotangents does not fit on the device");
-    if (rc) return rc;
-    t.wstage_bytes = bytes;
-  }
-  double* st = t.wstage;
-  if (cot_x) { HIPCHK(h, hipMemcpyAsync(st, cot_x, E * N * sizeof(double), hipMemcpyHostToDevice, h->stream)); c->x = st; }
-  if (cot_v) { HIPCHK(h, hipMemcpyAsync(st + E * N, cot_v, E * N * sizeof(double), hipMemcpyHostToDevice, h->stream)); c->v = st + E * N; }
-  if (cot_modes) {
-    HIPCHK(h, hipMemcpyAsync(st + 2 * E * N, cot_modes, E * 2 * t.wmo * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    c->modes = st + 2 * E * N;
-  }
-  return PIC_OK;
-}
-
-int pic_tape_walk_step(pic_handle* h, const double* cot_energies, const void* cot_x, const void* cot_v, const double* cot_modes,
-                       int mem_kind, double* g_ext, double* g_actions, int64_t* step) {
-  if (!h) return PIC_EINVAL;
-  Tape& t = h->tape;
-  if (!t.on || !t.walk) return fail(h, PIC_ESTATE, "pic_tape_walk_step: no walk in progress (pic_tape_walk_begin)");
-  if (t.wnext < 0) return fail(h, PIC_ESTATE, "pic_tape_walk_step: every step has been walked (pic_tape_walk_end)");
-  if (mem_kind != PIC_HOST && mem_kind != PIC_DEVICE) return fail(h, PIC_EINVAL, "pic_tape_walk_step: bad mem_kind");
-  if (g_actions && !t.gact)
-    return fail(h, PIC_ESTATE, "pic_tape_walk_step: g_actions needs an actuator set before pic_tape_start (pic_set_actuator)");
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  const int E = h->cfg.num_envs;
-  const int64_t s = t.wnext;
-  const size_t mesh = (size_t)E * h->cfg.Ng, arow = (size_t)E * 2 * h->act_modes;
-  const bool host = mem_kind == PIC_HOST;
-  double* cot = t.cot + (size_t)s * 3 * E;
-  if (cot_energies)
-    HIPCHK(h, hipMemcpyAsync(cot, cot_energies, 3 * E * sizeof(double), host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->stream));
-  else
-    HIPCHK(h, hipMemsetAsync(cot, 0, 3 * E * sizeof(double), h->stream));
-  WalkCot c;
-  int rc = walk_cot(h, cot_x, cot_v, cot_modes, host, &c);
-  if (rc) return rc;
-  rc = walk_reverse(h, c, adjoint_args(h), walk_geom(h));
-  if (rc) { t.walk = false; return rc; }
-  if (g_ext) HIPCHK(h, hipMemcpyAsync(g_ext, t.gext + (size_t)s * mesh, mesh * sizeof(double),
-                                      host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
-  if (g_actions) {      // a-bar_s = B^T e-bar_s of this step alone
-    hipLaunchKernelGGL(adjoint_actions_kernel, dim3(E, 1), dim3(ABLOCK), 0, h->stream, (const double*)(t.gext + (size_t)s * mesh), h->basis,
-                       host ? t.gact + (size_t)s * arow : g_actions, h->cfg.Ng, h->act_modes, E);
-    ++t.launches;
-    HIPCHK(h, hipGetLastError());
-    if (host) HIPCHK(h, hipMemcpyAsync(g_actions, t.gact + (size_t)s * arow, arow * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  }
-  if (host && (g_ext || g_actions)) HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (step) *step = s;
-  return PIC_OK;
-}
-
-int pic_tape_walk_end(pic_handle* h, const void* cot_x0, const void* cot_v0, const double* cot_modes0, int mem_kind, void* g_x0,
-                      void* g_v0) {
-  if (!h) return PIC_EINVAL;
-  Tape& t = h->tape;
-  if (!t.on || !t.walk) return fail(h, PIC_ESTATE, "pic_tape_walk_end: no walk in progress (pic_tape_walk_begin)");
-  if (t.wnext >= 0)
-    return fail(h, PIC_ESTATE, "pic_tape_walk_end: " + std::to_string(t.wnext + 1) + " steps are not walked yet (pic_tape_walk_step)");
-  if (mem_kind != PIC_HOST && mem_kind != PIC_DEVICE) return fail(h, PIC_EINVAL, "pic_tape_walk_end: bad mem_kind");
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  const size_t part = (size_t)h->cfg.num_envs * h->ld;
-  const bool host = mem_kind == PIC_HOST;
-  WalkCot c;
-  int rc = walk_cot(h, cot_x0, cot_v0, cot_modes0, host, &c);
-  if (rc) { t.walk = false; return rc; }
-  rc = walk_close(h, c, adjoint_args(h), walk_geom(h));
-  if (rc) return rc;
-  if (g_x0) rc = download(h, g_x0, t.lam, mem_kind);
-  if (!rc && g_v0) rc = download(h, g_v0, t.lam + part, mem_kind);
-  if (rc) return rc;
-  return host ? walk_check(h, "pic_tape_walk_end") : PIC_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Forward mode of the tape (include/picstep.h: pic_tape_tangent; kernels: pic_tangent.h)
-// ---------------------------------------------------------------------------------------------
-// bytes of the tangent block for kc directions: state [kc][2][env][ld], dF [kc][env][Ng], acc [kc][env][Ng], ke [kc][env],
-// umax [3][kc][env]; *offs: the parts' offsets (everything from offs[2] on is zero between uses)
-static size_t tangent_layout(const pic_handle* h, int kc, size_t (&offs)[5]) {
-  const size_t E = h->cfg.num_envs, mesh = E * h->cfg.Ng;
-  const size_t sizes[5] = {(size_t)kc * 2 * E * h->ld * sizeof(double), kc * mesh * sizeof(double), kc * mesh * sizeof(acc_t),
-                           kc * E * sizeof(acc_t), 3 * kc * E * sizeof(unsigned long long)};
-  size_t at = 0;
-  for (int i = 0; i < 5; ++i) {
-    offs[i] = at;
-    at += (sizes[i] + 255) & ~(size_t)255;
-  }
-  return at;
-}
-
-// the tangent block for K directions, within budget_bytes; on failure the tape keeps what it had
-static int tangent_reserve(pic_handle* h, int K, const std::string& w) {
-  Tape& t = h->tape;
-  if (t.tan_k >= K) return PIC_OK;
-  size_t offs[5];
-  const size_t bytes = tangent_layout(h, K, offs);
-  if (t.budget > 0 && t.bytes - t.tan_bytes + bytes > (size_t)t.budget)
-    return fail(h, PIC_ENOMEM, w + ": the working memory of " + std::to_string(K) + " directions (" + std::to_string(bytes) +
-                                   " bytes) would take the tape past budget_bytes (pic_tape_start)");
-  DeviceBuf<void> b;
-  if (alloc(b, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(h, PIC_ENOMEM, w + ": the working memory of " + std::to_string(K) + " directions does not fit on the device");
-  }
-  if (t.tan_block) HIPCHK(h, hipStreamSynchronize(h->stream));      // queued work may still read the old block
-  t.tan_block = std::move(b);
-  t.bytes = t.bytes - t.tan_bytes + bytes;
-  t.tan_bytes = bytes;
-  t.tan_k = K;
-  return PIC_OK;
-}
-
-extern "C++" {
-// the kernels of a sub-stage for the direction count at hand (1, up to 4, up to 8: the per-direction values live in registers)
-template <int S>
-static void tangent_deposit(pic_handle* h, const AdjStep& st, const TanArgs& ta, const AdjArgs& a, dim3 grid, size_t lds, int kd) {
-  if (kd == 1) hipLaunchKernelGGL((tangent_deposit_kernel<S, 1>), grid, dim3(ABLOCK), lds, h->stream, st, ta, a, kd);
-  else if (kd <= 4) hipLaunchKernelGGL((tangent_deposit_kernel<S, 4>), grid, dim3(ABLOCK), lds, h->stream, st, ta, a, kd);
-  else hipLaunchKernelGGL((tangent_deposit_kernel<S, 8>), grid, dim3(ABLOCK), lds, h->stream, st, ta, a, kd);
-}
-
-template <int S>
-static void tangent_pass(pic_handle* h, const AdjStep& st, const TanArgs& ta, const AdjArgs& a, dim3 grid) {
-  if (ta.K == 1) hipLaunchKernelGGL((tangent_pass_kernel<S, 1>), grid, dim3(ABLOCK), 0, h->stream, st, ta, a);
-  else if (ta.K <= 4) hipLaunchKernelGGL((tangent_pass_kernel<S, 4>), grid, dim3(ABLOCK), 0, h->stream, st, ta, a);
-  else hipLaunchKernelGGL((tangent_pass_kernel<S, 8>), grid, dim3(ABLOCK), 0, h->stream, st, ta, a);
-}
-}  // extern "C++"
-
-int pic_tape_tangent(pic_handle* h, int K, const double* d_ext, const double* d_actions, const void* d_x0, const void* d_v0,
-                     int mem_kind, double* d_hist, void* d_x, void* d_v, double* d_E_mesh) {
-  if (!h) return PIC_EINVAL;
-  Tape& t = h->tape;
-  const std::string w("pic_tape_tangent");
-  if (!t.on) return fail(h, PIC_ESTATE, w + ": no tape is open (pic_tape_start)");
-  if (K < 1 || K > kMaxTangents) return fail(h, PIC_EINVAL, w + ": need 1 <= K <= " + std::to_string(kMaxTangents));
-  if (d_ext && d_actions) return fail(h, PIC_EINVAL, w + ": d_ext and d_actions are both given (at most one)");
-  if (mem_kind != PIC_HOST && mem_kind != PIC_DEVICE) return fail(h, PIC_EINVAL, w + ": bad mem_kind");
-  const int64_t T = t.steps;
-  for (int64_t s = 0; s < T && !t.law.empty(); ++s)
-    if (t.law[(size_t)s] >= 0)
-      return fail(h, PIC_ESTATE, w + ": the tape holds steps of pic_step_feedback_gain, and forward mode through the gain law is "
-                                     "not built (pic_tape_backward_feedback differentiates it in reverse)");
-  if (d_actions && !t.gact)
-    return fail(h, PIC_ESTATE, w + ": d_actions needs an actuator set before pic_tape_start (pic_set_actuator)");
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  const int E = h->cfg.num_envs, Ng = h->cfg.Ng, Mact = h->act_modes;
-  const bool host = mem_kind == PIC_HOST;
-  const size_t N = h->cfg.N, part = (size_t)E * h->ld, mesh = (size_t)E * Ng, row = N * sizeof(double);
-  t.walk = false;                     // (a walk's replayed segment is about to be overwritten)
-  t.launches = 0;
-  HIPCHK(h, hipMemsetAsync(t.counters, 0, 2 * sizeof(unsigned long long), h->stream));
-  if (T == 0) {                       // no step: the tangent of the final particles is the initial one (NULL: 0)
-    const size_t n = (size_t)K * E * row;
-    void* outs[2] = {d_x, d_v};
-    const void* ins[2] = {d_x0, d_v0};
-    for (int k = 0; k < 2; ++k) {
-      if (!outs[k]) continue;
-      if (host && ins[k]) std::memcpy(outs[k], ins[k], n);
-      else if (host) std::memset(outs[k], 0, n);
-      else if (ins[k]) HIPCHK(h, hipMemcpyAsync(outs[k], ins[k], n, hipMemcpyDeviceToDevice, h->stream));
-      else HIPCHK(h, hipMemsetAsync(outs[k], 0, n, h->stream));
-    }
-    if (host) HIPCHK(h, hipStreamSynchronize(h->stream));
-    return PIC_OK;
-  }
-  int rc = tangent_reserve(h, K, w);
-  if (rc) return rc;
-  size_t offs[5];
-  tangent_layout(h, t.tan_k, offs);
-  char* b = static_cast<char*>(t.tan_block.get());
-  TanArgs ta{};
-  ta.st = (double*)b; ta.dstride = (long long)(2 * part); ta.vofs = (long long)part;
-  ta.dF = (double*)(b + offs[1]); ta.acc = (acc_t*)(b + offs[2]); ta.ke = (acc_t*)(b + offs[3]);
-  ta.umax = (unsigned long long*)(b + offs[4]);
-  ta.K = K; ta.num_envs = E;
-  HIPCHK(h, hipMemsetAsync(b + offs[2], 0, t.tan_bytes - offs[2], h->stream));     // acc, ke, umax (a failed call may leave them)
-  // host memory: the control tangents and the mesh-sized outputs go through one device block of this call
-  const size_t in_n = d_ext ? (size_t)K * T * mesh : d_actions ? (size_t)K * T * E * 2 * Mact : 0;
-  const size_t hist_n = d_hist ? (size_t)K * T * 3 * E : 0, em_n = d_E_mesh ? (size_t)K * T * mesh : 0;
-  const double* din = d_ext ? d_ext : d_actions;
-  double* dhist = d_hist;
-  double* dem = d_E_mesh;
-  DeviceBuf<double> stage;
-  if (host && in_n + hist_n + em_n > 0) {
-    if (alloc(stage, (in_n + hist_n + em_n) * sizeof(double)) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(h, PIC_ENOMEM, w + ": the staging of host tangents does not fit on the device");
-    }
-    double* p = stage;
-    if (in_n) {
-      HIPCHK(h, hipMemcpyAsync(p, din, in_n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      din = p;
-      p += in_n;
-    }
-    if (hist_n) { dhist = p; p += hist_n; }
-    if (em_n) dem = p;
-  }
-  // (dx_0, dv_0) of every direction into the state rows (padded to ld)
-  for (int d = 0; d < K; ++d) {
-    const void* ins[2] = {d_x0, d_v0};
-    for (int k = 0; k < 2; ++k) {
-      double* dst = ta.st + (size_t)d * 2 * part + (size_t)k * part;
-      if (ins[k])
-        HIPCHK(h, hipMemcpy2DAsync(dst, (size_t)h->ld * sizeof(double), static_cast<const double*>(ins[k]) + (size_t)d * E * N, row, row,
-                                   E, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->stream));
-      else
-        HIPCHK(h, hipMemsetAsync(dst, 0, part * sizeof(double), h->stream));
-    }
-  }
-  const AdjArgs a = adjoint_args(h);
-  const WalkGeom g = walk_geom(h);
-  hipLaunchKernelGGL(tangent_start_kernel, g.pgrid, dim3(ABLOCK), 0, h->stream, ta, a);
-  ++t.launches;
-  // a deposit workgroup holds kd directions' meshes in 64 KB of LDS; groups of them run side by side (grid z)
-  const int kd = std::min<int>(K, (int)std::max<size_t>(1, 65536 / ((size_t)(Ng + 1) * sizeof(unsigned long long))));
-  const dim3 dgrid(g.pgrid.x, E, (K + kd - 1) / kd), mgrid(E, K);
-  const size_t dlds = (size_t)kd * (Ng + 1) * sizeof(unsigned long long);
-  TanMeshIO io{};
-  io.basis = h->basis; io.Mact = Mact;
-  io.in_dstride = d_ext ? (long long)(T * mesh) : (long long)(T * E * 2 * Mact);
-  io.out_hstride = (long long)(T * 3 * E); io.out_mstride = (long long)(T * mesh);
-  const int64_t nseg = (T + t.every - 1) / t.every;
-  for (int64_t sgi = 0; sgi < nseg; ++sgi) {
-    rc = walk_replay(h, sgi, a, g);
-    if (rc) return rc;
-    const int64_t t0 = sgi * t.every, len = std::min<int64_t>(t.every, T - t0);
-    for (int64_t i = 0; i < len; ++i) {
-      const int64_t s = t0 + i;
-      const double* x = t.seg + (size_t)i * 2 * part;
-      const AdjStep st{x, x + part, t.F + (size_t)i * 3 * mesh, (long long)mesh};
-      TanMeshIO m = io;
-      m.ext = d_ext ? din + (size_t)s * mesh : nullptr;
-      m.act = d_actions ? din + (size_t)s * E * 2 * Mact : nullptr;
-      m.M = t.M + (size_t)i * mesh;
-      m.hist = dhist ? dhist + (size_t)s * 3 * E : nullptr;
-      m.Emesh = dem ? dem + (size_t)s * mesh : nullptr;
-      tangent_deposit<1>(h, st, ta, a, dgrid, dlds, kd);
-      hipLaunchKernelGGL(tangent_mesh_kernel<1>, mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, ta, m, a);
-      tangent_pass<1>(h, st, ta, a, g.pgrid);
-      tangent_deposit<2>(h, st, ta, a, dgrid, dlds, kd);
-      hipLaunchKernelGGL(tangent_mesh_kernel<2>, mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, ta, m, a);
-      tangent_pass<2>(h, st, ta, a, g.pgrid);
-      tangent_deposit<3>(h, st, ta, a, dgrid, dlds, kd);
-      hipLaunchKernelGGL(tangent_mesh_kernel<3>, mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, ta, m, a);
-      tangent_pass<3>(h, st, ta, a, g.pgrid);
-      tangent_deposit<4>(h, st, ta, a, dgrid, dlds, kd);
-      hipLaunchKernelGGL(tangent_mesh_kernel<4>, mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, ta, m, a);
-      t.launches += 11;
-    }
-    HIPCHK(h, hipGetLastError());
-  }
-  if (host && hist_n) HIPCHK(h, hipMemcpyAsync(d_hist, dhist, hist_n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (host && em_n) HIPCHK(h, hipMemcpyAsync(d_E_mesh, dem, em_n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  // (dx', dv') of every direction out of the state rows
-  for (int d = 0; d < K; ++d) {
-    void* outs[2] = {d_x, d_v};
-    for (int k = 0; k < 2; ++k)
-      if (outs[k])
-        HIPCHK(h, hipMemcpy2DAsync(static_cast<double*>(outs[k]) + (size_t)d * E * N, row, ta.st + (size_t)d * 2 * part + (size_t)k * part,
-                                   (size_t)h->ld * sizeof(double), row, E, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
-                                   h->stream));
-  }
-  HIPCHK(h, hipGetLastError());
-  return host ? walk_check(h, w) : PIC_OK;
 }
 
 }  // extern "C"

@@ -54,7 +54,7 @@ def _planted_positions(c, rng):
 # bounds
 # ---------------------------------------------------------------------------------------------------------------------
 def _fg(N):
-    """Fractional bits of the 64-bit accumulators, as pic_create computes them (csrc/picstep.hip:918-922)."""
+    """Fractional bits of the 64-bit accumulators, as pic_create computes them (csrc/picstep.hip:1096-1099)."""
     lg = 0
     while (1 << lg) < N + 1:
         lg += 1

@@ -318,6 +318,111 @@ def test_default_interval_follows_the_budget():
     env.close()
 
 
+# (bytes, checkpoint_every, launches) of pic_tape_stats after every action of _accounting below, from the code as it was before the
+# tape's device blocks were described by one carver (csrc/host_diff.h): worked out by hand from that code's layout functions
+# (every part rounded up to 256 bytes; ld = 1024; the law's last part unrounded) and its launch counters, not from the carver.
+# Byte accounting is behaviour: these are never re-recorded from the code under test.
+ACCOUNTING = {
+    "start_every0": (254976, 3, 0),
+    "start_every1": (312320, 1, 0),
+    "start_every2": (250880, 2, 0),
+    "start_every5": (328704, 5, 0),
+    "kl_shared": (253952, 2, 0),                  # + 3072: feq 512, acc 1024, g 1024, trace 80 -> 256, cot 256
+    "kl_per_env": (254464, 2, 0),                 # + 3584: feq 1024
+    "gain": (257280, 2, 0),                       # + 3 x 512 + 1024 (the law's record) + 256 (the gain)
+    "backward": (257280, 2, 50),                  # replay 17, steps 14 + 15 (KL 3, the law's E-bar 0 + 1, 11), close 3, a-bar 1
+    "tangent_K1": (286208, 2, 40),                # + 35328; start 1, replay 17, 2 x 11
+    "tangent_K5": (425472, 2, 40),                # + 174592
+}
+
+
+def _accounting_env():
+    """2 environments, N = 1000, 64 nodes, two actuator modes: a row of actions is 64 bytes and a mesh 512, shorter than the 256
+    bytes every part of a block is rounded up to."""
+    import ocplasma_amd as oc
+    from ocplasma_amd.env.batched import BatchedPIC
+    E, N, Ng = 2, 1000, 64
+    env = BatchedPIC(E, N, Ng, L=L, dt=0.1)
+    X, V = np.empty((E, N)), np.empty((E, N))
+    for e in range(E):
+        X[e], V[e] = po.synthetic_bump_on_tail(N, L, seed=31 + 7 * e)
+    env.reset(X, V)
+    env.set_actuator(oc.E_field(L, Ng, 2))
+    return env, X, V
+
+
+def _accounting(env, X, V, budget=None, only=None):
+    """name -> (bytes, checkpoint_every, launches) after every action, max_steps = 5 throughout.  Tapes with checkpoint_every 0
+    (= 3), 1, 2 and 5; then, each on a tape of its own with checkpoint_every = 2: a KL of 8 x 8 bins with a shared target; one
+    with a target per environment; that, one gain-law call of 2 steps and a backward over them with energy and KL cotangents;
+    two plain steps and the tangent for K = 1; those and then K = 5 (pic_tape_tangent refuses a tape that holds gain-law steps,
+    so the tangents have tapes of their own).  budget: name -> budget_bytes of the tape that ends with that action (none by
+    default); only: the tapes to make (all by default)."""
+    budget = budget or {}
+    E, Mk, T = env.num_envs, 2, 5
+    h = env._h
+    got = {}
+
+    def note(name):
+        st = env.tape_stats()
+        got[name] = (st["bytes"], st["checkpoint_every"], st["launches"])
+
+    def tape(name, every=2):
+        if only is not None and name not in only:
+            return False
+        env.stop_tape()
+        env.reset(X, V)
+        env.start_tape(T, every, budget_bytes=budget.get(name, 0))
+        return True
+
+    feq = np.random.default_rng(32).uniform(0.0, 2.0 / (L * 12.0), (E, 8, 8))
+    ones = np.ones((2, E))
+    acts = np.random.default_rng(33).uniform(-0.5, 0.5, (2, E, 2 * Mk))
+    for every in (0, 1, 2, 5):
+        if tape(f"start_every{every}", every):
+            note(f"start_every{every}")
+    if tape("kl_shared"):
+        h.tape_kl_start(8, 8, -6.0, 6.0, feq[0].ctypes.data, 0, 0)
+        note("kl_shared")
+    if tape("kl_per_env"):
+        h.tape_kl_start(8, 8, -6.0, 6.0, feq.ctypes.data, 1, 0)
+        note("kl_per_env")
+    if tape("gain"):
+        h.tape_kl_start(8, 8, -6.0, 6.0, feq.ctypes.data, 1, 0)
+        env.step_feedback_gain(0.1 * np.eye(2 * Mk), 2)
+        note("gain")
+        h.tape_kl_cot(ones.ctypes.data, 0, 0, 2)
+        h.tape_backward_feedback(cot_hist=np.ones((2, 3, E)))
+        note("backward")
+    for name, Ks in (("tangent_K1", (1,)), ("tangent_K5", (1, 5))):
+        if tape(name):
+            env.step_actions_traj(acts)
+            for K in Ks:
+                h.tape_tangent(K, d_actions=np.ones((K, 2, E, 2 * Mk)))
+            note(name)
+    env.stop_tape()
+    return got
+
+
+def test_tape_byte_accounting_is_pinned():
+    """Absolute values of pic_tape_stats' bytes, checkpoint_every and launches (ACCOUNTING), and budget_bytes to the byte: the
+    recorded total is accepted, one byte less is refused with PIC_ENOMEM by the very entry that needs it.  (With
+    checkpoint_every = 0 one byte less than the total of the default interval 3 is not a refusal: the tape then takes the
+    interval that needs the fewest bytes, 2, and it is one byte below that total that is refused.)"""
+    from ocplasma_amd._abi import PicError
+    env, X, V = _accounting_env()
+    assert _accounting(env, X, V) == ACCOUNTING
+    totals = {k: v[0] for k, v in ACCOUNTING.items() if k != "backward"}           # (a backward allocates nothing)
+    assert _accounting(env, X, V, totals) == ACCOUNTING                            # exactly enough, everywhere
+    got = _accounting(env, X, V, {"start_every0": totals["start_every0"] - 1}, only={"start_every0"})
+    assert got == {"start_every0": ACCOUNTING["start_every2"]}
+    entry = {"start": "pic_tape_start", "kl": "pic_tape_kl_start", "gain": "pic_step_feedback_gain", "tangent": "pic_tape_tangent"}
+    for name in totals:
+        floor = totals["start_every2" if name == "start_every0" else name]
+        with pytest.raises(PicError, match=f"error -4: {entry[name.split('_')[0]]}:"):
+            _accounting(env, X, V, {name: floor - 1}, only={name})
+    env.close()
+
 
 def test_torch_rollout_matches_tape_and_passes_gradcheck():
     import torch
