@@ -235,6 +235,11 @@ def _host(a, shape):
     return None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(shape))
 
 
+def _addrs(*arrays):
+    """The addresses of host arrays (None -> 0), for the entry points that take addresses and a mem_kind."""
+    return [0 if a is None else a.__array_interface__["data"][0] for a in arrays]
+
+
 def _phase_spec(nx, nv, vmin, vmax, feq, feq_per_env, feq_kind):
     """pic_phase_spec; feq an address (0 = NULL) in feq_kind memory."""
     return PicPhaseSpec(int(nx), int(nv), float(vmin), float(vmax), int(feq) or None, int(feq_per_env), int(feq_kind))
@@ -267,6 +272,8 @@ class Handle:
         self.fixed_positions = POSITION_FORMATS[pkey] == PIC_POS_FIXED32
         self.N, self.Ng, self.num_envs = int(N), int(Ng), int(num_envs)
         self.dtype = np.dtype(particle_dtype)
+        self.max_mode = 0                              # (no actuator yet: set_actuator)
+        self._taping, self._law_calls = False, []      # (first step, steps) of every gain-law call on the open tape
         self._h = C.c_void_p()
         rc = self.lib.pic_create(C.byref(self.cfg), C.byref(self._h))
         if rc != 0:
@@ -557,7 +564,7 @@ class Handle:
         act = np.empty((k, E, n)) if actions else None
         md = np.empty((k, E, n)) if modes else None
         hist = self._hist_out(k, history)
-        first = self.tape_stats()["steps"] if getattr(self, "_taping", False) else None
+        first = self.tape_stats()["steps"] if self._taping else None
         self._chk(self.lib.pic_step_feedback_gain(self._h, self.max_mode, gp, kind, k, _ptr(act), _ptr(md), _ptr(hist)))
         if first is not None and k > 0:
             self._law_calls.append((first, k))
@@ -685,7 +692,7 @@ class Handle:
     def tape_start(self, max_steps, checkpoint_every=0, budget_bytes=0):
         cfg = PicTapeConfig(int(max_steps), int(checkpoint_every), int(budget_bytes))
         self._chk(self.lib.pic_tape_start(self._h, C.byref(cfg)))
-        self._taping, self._law_calls = True, []       # (first step, steps) of every gain-law call on the tape
+        self._taping, self._law_calls = True, []
 
     def tape_stats(self):
         o = PicTapeInfo()
@@ -697,23 +704,26 @@ class Handle:
         [num_envs][N] (those asked for)."""
         T = self.tape_stats()["steps"]
         E = self.num_envs
-        ch, cx, cv = _host(cot_hist, (T, 3, E)), _host(cot_x, (E, self.N)), _host(cot_v, (E, self.N))
+        ins = [_host(cot_hist, (T, 3, E)), _host(cot_x, (E, self.N)), _host(cot_v, (E, self.N))]
         out = {}
         if ext:
             out["g_ext"] = np.zeros((T, E, self.Ng))
         if actions:
-            out["g_actions"] = np.zeros((T, E, 2 * getattr(self, "max_mode", 0)))
+            out["g_actions"] = np.zeros((T, E, 2 * self.max_mode))
         if particles:
             out["g_x0"] = np.zeros((E, self.N))
             out["g_v0"] = np.zeros((E, self.N))
-        self._chk(self.lib.pic_tape_backward(self._h, _ptr(ch), _ptr(cx), _ptr(cv), PIC_HOST, _ptr(out.get("g_ext")),
-                                             _ptr(out.get("g_actions")), _ptr(out.get("g_x0")), _ptr(out.get("g_v0"))))
+        self._tape_backward(PIC_HOST, *_addrs(*ins, *(out.get(k) for k in ("g_ext", "g_actions", "g_x0", "g_v0"))))
         return out
 
     def tape_backward_device(self, cot_hist, cot_x, cot_v, g_ext, g_actions, g_x0, g_v0):
         """Device pointers (0 = NULL) in and out; asynchronous on the handle's stream."""
+        self._tape_backward(PIC_DEVICE, cot_hist, cot_x, cot_v, g_ext, g_actions, g_x0, g_v0)
+
+    def _tape_backward(self, mem_kind, cot_hist, cot_x, cot_v, g_ext, g_actions, g_x0, g_v0):
+        """pic_tape_backward on addresses (int, 0 = NULL) in mem_kind memory."""
         p = _ptrs(cot_hist, cot_x, cot_v, g_ext, g_actions, g_x0, g_v0)
-        self._chk(self.lib.pic_tape_backward(self._h, p[0], p[1], p[2], PIC_DEVICE, p[3], p[4], p[5], p[6]))
+        self._chk(self.lib.pic_tape_backward(self._h, p[0], p[1], p[2], int(mem_kind), p[3], p[4], p[5], p[6]))
 
     def tape_stop(self):
         self._chk(self.lib.pic_tape_stop(self._h))
@@ -721,24 +731,26 @@ class Handle:
 
     def tape_law_calls(self):
         """(first step, steps) of every pic_step_feedback_gain call on the open tape, in order."""
-        return list(getattr(self, "_law_calls", []))
+        return list(self._law_calls)
 
     def tape_backward_feedback(self, cot_hist=None, cot_x=None, cot_v=None, cot_modes=None):
         """pic_tape_backward_feedback with host arrays: dict with g_ext, g_actions, modes [T][num_envs][2M], g_x0, g_v0."""
         T = self.tape_stats()["steps"]
         E, n = self.num_envs, 2 * self.max_mode
-        ch, cx, cv, cm = _host(cot_hist, (T, 3, E)), _host(cot_x, (E, self.N)), _host(cot_v, (E, self.N)), _host(cot_modes, (T, E, n))
+        ins = [_host(cot_hist, (T, 3, E)), _host(cot_x, (E, self.N)), _host(cot_v, (E, self.N)), _host(cot_modes, (T, E, n))]
         out = {"g_ext": np.zeros((T, E, self.Ng)), "g_actions": np.zeros((T, E, n)), "modes": np.zeros((T, E, n)),
                "g_x0": np.zeros((E, self.N)), "g_v0": np.zeros((E, self.N))}
-        self._chk(self.lib.pic_tape_backward_feedback(self._h, _ptr(ch), _ptr(cx), _ptr(cv), _ptr(cm), PIC_HOST, _ptr(out["g_ext"]),
-                                                      _ptr(out["g_actions"]), _ptr(out["g_x0"]), _ptr(out["g_v0"]),
-                                                      _ptr(out["modes"])))
+        self._tape_backward_feedback(PIC_HOST, *_addrs(*ins, *(out[k] for k in ("g_ext", "g_actions", "g_x0", "g_v0", "modes"))))
         return out
 
     def tape_backward_feedback_device(self, cot_hist, cot_x, cot_v, cot_modes, g_ext, g_actions, g_x0, g_v0, modes):
         """Device pointers (0 = NULL) in and out; asynchronous on the handle's stream."""
+        self._tape_backward_feedback(PIC_DEVICE, cot_hist, cot_x, cot_v, cot_modes, g_ext, g_actions, g_x0, g_v0, modes)
+
+    def _tape_backward_feedback(self, mem_kind, cot_hist, cot_x, cot_v, cot_modes, g_ext, g_actions, g_x0, g_v0, modes):
+        """pic_tape_backward_feedback on addresses (int, 0 = NULL) in mem_kind memory."""
         p = _ptrs(cot_hist, cot_x, cot_v, cot_modes, g_ext, g_actions, g_x0, g_v0, modes)
-        self._chk(self.lib.pic_tape_backward_feedback(self._h, p[0], p[1], p[2], p[3], PIC_DEVICE, p[4], p[5], p[6], p[7], p[8]))
+        self._chk(self.lib.pic_tape_backward_feedback(self._h, p[0], p[1], p[2], p[3], int(mem_kind), p[4], p[5], p[6], p[7], p[8]))
 
     def tape_walk_begin(self, obs_modes, mem_kind=PIC_HOST):
         self._chk(self.lib.pic_tape_walk_begin(self._h, int(obs_modes), int(mem_kind)))
@@ -760,20 +772,22 @@ class Handle:
         and, with fields, E_mesh [K][T][num_envs][Ng]."""
         T = self.tape_stats()["steps"]
         E, K = self.num_envs, int(K)
-        de = _host(d_ext, (K, T, E, self.Ng))
-        da = _host(d_actions, (K, T, E, -1))
-        dx, dv = _host(d_x0, (K, E, self.N)), _host(d_v0, (K, E, self.N))
+        ins = [_host(d_ext, (K, T, E, self.Ng)), _host(d_actions, (K, T, E, -1)), _host(d_x0, (K, E, self.N)),
+               _host(d_v0, (K, E, self.N))]
         out = {"hist": np.zeros((K, T, 3, E)), "x": np.zeros((K, E, self.N)), "v": np.zeros((K, E, self.N))}
         if fields:
             out["E_mesh"] = np.zeros((K, T, E, self.Ng))
-        self._chk(self.lib.pic_tape_tangent(self._h, K, _ptr(de), _ptr(da), _ptr(dx), _ptr(dv), PIC_HOST, _ptr(out["hist"]),
-                                            _ptr(out["x"]), _ptr(out["v"]), _ptr(out.get("E_mesh"))))
+        self._tape_tangent(PIC_HOST, K, *_addrs(*ins, out["hist"], out["x"], out["v"], out.get("E_mesh")))
         return out
 
     def tape_tangent_device(self, K, d_ext, d_actions, d_x0, d_v0, hist, x, v, E_mesh):
         """pic_tape_tangent on device pointers (int, 0 = NULL); asynchronous on the handle's stream."""
+        self._tape_tangent(PIC_DEVICE, K, d_ext, d_actions, d_x0, d_v0, hist, x, v, E_mesh)
+
+    def _tape_tangent(self, mem_kind, K, d_ext, d_actions, d_x0, d_v0, hist, x, v, E_mesh):
+        """pic_tape_tangent on addresses (int, 0 = NULL) in mem_kind memory."""
         p = _ptrs(d_ext, d_actions, d_x0, d_v0, hist, x, v, E_mesh)
-        self._chk(self.lib.pic_tape_tangent(self._h, int(K), p[0], p[1], p[2], p[3], PIC_DEVICE, p[4], p[5], p[6], p[7]))
+        self._chk(self.lib.pic_tape_tangent(self._h, int(K), p[0], p[1], p[2], p[3], int(mem_kind), p[4], p[5], p[6], p[7]))
 
     def tape_kl_start(self, nx, nv, vmin, vmax, feq, feq_per_env, feq_kind):
         """pic_tape_kl_start: feq an address in feq_kind memory (the tape copies it)."""

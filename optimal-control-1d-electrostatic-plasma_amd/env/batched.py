@@ -8,6 +8,7 @@ from typing import Optional
 import numpy as np
 
 from .. import _abi
+from ._arrays import Mem
 from .record import Record, recorder_args, recording_session
 
 
@@ -40,6 +41,10 @@ class BatchedPIC:
                               integrator, readonly_c)
         self.integrator = _abi.INTEGRATOR_NAMES[_abi.integrator_id(integrator)]
         self.fixed_positions = self._h.fixed_positions
+        self.max_mode = 0                    # (no actuator yet: set_actuator)
+        self._torch_stream = None            # (the handle runs on its own stream: use_torch_stream)
+        self._tape_kl = False                # (the open tape records the smoothed KL)
+        self._tape_serial = self._walk_serial = 0       # (the tape env.grad opened last, the walk in progress)
 
     # reset(x0, v0): x0, v0 are [num_envs, N] with any velocity perturbation already applied
     def reset(self, x0, v0):
@@ -145,7 +150,7 @@ class BatchedPIC:
         if not (actions.is_cuda and actions.dtype.is_floating_point and actions.element_size() == 8 and actions.is_contiguous()
                 and actions.dim() == 3 and tuple(actions.shape[1:]) == (self.num_envs, 2 * self.max_mode)):
             raise ValueError("actions must be a contiguous float64 CUDA tensor [nsteps, num_envs, 2*max_mode]")
-        shared = getattr(self, "_torch_stream", None) is not None
+        shared = self._torch_stream is not None
         if not shared:
             import torch
             torch.cuda.current_stream(self.device).synchronize()
@@ -181,7 +186,7 @@ class BatchedPIC:
             if tuple(g.shape) != (E, n, n):
                 raise ValueError(f"gain must be [{E}, {n}, {n}] or [{n}, {n}]")
             g = g.contiguous()
-            shared = getattr(self, "_torch_stream", None) is not None
+            shared = self._torch_stream is not None
             if not shared:
                 torch.cuda.current_stream(self.device).synchronize()
             out = self._h.step_feedback_gain(None, nsteps, actions, modes, history, device_ptr=g.data_ptr())
@@ -221,7 +226,7 @@ class BatchedPIC:
         if not (actions.is_cuda and actions.dtype.is_floating_point and actions.element_size() == 8
                 and actions.is_contiguous() and tuple(actions.shape) == (self.num_envs, 2 * self.max_mode)):
             raise ValueError("actions must be a contiguous float64 CUDA tensor [num_envs, 2*max_mode]")
-        shared = getattr(self, "_torch_stream", None) is not None
+        shared = self._torch_stream is not None
         if not shared:      # different streams: order them through the host
             import torch
             torch.cuda.current_stream(self.device).synchronize()
@@ -235,7 +240,7 @@ class BatchedPIC:
         dev = f"cuda:{self.device}"
         re = torch.empty((self.num_envs, max_mode), dtype=torch.float64, device=dev)
         im = torch.empty_like(re)
-        shared = getattr(self, "_torch_stream", None) is not None
+        shared = self._torch_stream is not None
         if not shared:
             torch.cuda.current_stream(self.device).synchronize()
         self._h.modes_device(max_mode, re.data_ptr(), im.data_ptr())
@@ -249,7 +254,7 @@ class BatchedPIC:
         import torch
         re = torch.empty((self.num_envs, max_mode), dtype=torch.float64, device=f"cuda:{self.device}")
         im = torch.empty_like(re)
-        shared = getattr(self, "_torch_stream", None) is not None
+        shared = self._torch_stream is not None
         if not shared:
             torch.cuda.current_stream(self.device).synchronize()
         self._h.modes_device(max_mode, re.data_ptr(), im.data_ptr())
@@ -262,7 +267,7 @@ class BatchedPIC:
         orders the read behind the steps; otherwise the handle's own stream is drained first."""
         if not hasattr(self, "_views"):
             self._views = self.torch_views()
-        if getattr(self, "_torch_stream", None) is None:
+        if self._torch_stream is None:
             self._h.sync()
         return self._views
 
@@ -309,28 +314,16 @@ class BatchedPIC:
         return self._h.phase_kl(feq, vmin, vmax)
 
     # -- smoothed phase-space density and KL (pic_phase_kl_smooth*) -----------------------
-    def _phase_call(self, feq, arrays):
-        """(on_device, feq as float64 [.., nx, nv] in the memory of the call, its address, per-environment flag, nx, nv, other
-        arrays as float64 in that memory): CUDA tensors in, CUDA tensors out, else NumPy."""
-        given = [a for a in [feq] + list(arrays) if a is not None]
-        on_device = any(hasattr(a, "is_cuda") and a.is_cuda for a in given)
-        if on_device:
-            import torch
-            conv = lambda a: torch.as_tensor(a, dtype=torch.float64, device=f"cuda:{self.device}").contiguous()  # noqa: E731
-        else:
-            conv = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64))  # noqa: E731
-        f = conv(feq)
+    def _phase_call(self, feq, *arrays):
+        """(the Mem of the call, (nx, nv, feq's address, per-environment flag), feq and the other arrays as float64 in that
+        memory): CUDA tensors in, CUDA tensors out, else NumPy.  The call is ordered behind torch on return."""
+        mem = Mem.of(self, feq, *arrays)
+        f = mem.f64(feq)
         if f.ndim == 3 and f.shape[0] != self.num_envs or f.ndim not in (2, 3):
             raise ValueError(f"feq must be [nx, nv] or [num_envs, nx, nv], not {list(f.shape)}")
-        out = [None if a is None else conv(a) for a in arrays]
-        if on_device and getattr(self, "_torch_stream", None) is None:
-            import torch
-            torch.cuda.current_stream(self.device).synchronize()
-        return on_device, f, self._addr(f), int(f.ndim == 3), int(f.shape[-2]), int(f.shape[-1]), out
-
-    @staticmethod
-    def _addr(a):
-        return 0 if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data)
+        held = [f] + [mem.f64(a) for a in arrays]
+        mem.enter()
+        return mem, (int(f.shape[-2]), int(f.shape[-1]), mem.addr(f), int(f.ndim == 3)), held
 
     def phase_density_smooth(self, bins, vmin: float = -25.0, vmax: float = 25.0):
         """The smoothed phase-space density f~ [num_envs, nx, nv] of the current particles: CIC weights on the
@@ -345,10 +338,9 @@ class BatchedPIC:
         """KL~ of every environment's smoothed density against feq [nx, nv] (shared) or [num_envs, nx, nv] ->
         [num_envs]: sum rel_entr(f~, feq + 1e-12) dx dv, estimate_KL_divergence's formula.  NumPy, or a float64 CUDA tensor if
         feq is one."""
-        dev, f, fa, per, nx, nv, _ = self._phase_call(feq, [])
-        kl = self._empty(dev, (self.num_envs,))
-        kind = _abi.PIC_DEVICE if dev else _abi.PIC_HOST
-        self._h.phase_kl_smooth(nx, nv, vmin, vmax, fa, per, kind, kind, self._addr(kl), 0)
+        mem, (nx, nv, fa, per), _held = self._phase_call(feq)
+        kl = mem.empty((self.num_envs,))
+        self._h.phase_kl_smooth(nx, nv, vmin, vmax, fa, per, mem.kind, mem.kind, mem.addr(kl), 0)
         return kl
 
     def kl_smooth_grad(self, feq, d_kl=None, vmin: float = -25.0, vmax: float = 25.0):
@@ -356,19 +348,12 @@ class BatchedPIC:
         [num_envs, N]: the almost-everywhere derivative of DESIGN.md 7g.  NumPy, or float64 CUDA tensors if feq or d_kl is one."""
         if d_kl is None:
             d_kl = np.ones(self.num_envs)
-        dev, f, fa, per, nx, nv, (d,) = self._phase_call(feq, [d_kl])
+        mem, (nx, nv, fa, per), (_f, d) = self._phase_call(feq, d_kl)
         if tuple(d.shape) != (self.num_envs,):
             raise ValueError(f"d_kl must be [num_envs], not {list(d.shape)}")
-        gx, gv = self._empty(dev, (self.num_envs, self.N)), self._empty(dev, (self.num_envs, self.N))
-        kind = _abi.PIC_DEVICE if dev else _abi.PIC_HOST
-        self._h.phase_kl_smooth_vjp(nx, nv, vmin, vmax, fa, per, kind, self._addr(d), kind, self._addr(gx), self._addr(gv))
+        gx, gv = mem.empty((self.num_envs, self.N)), mem.empty((self.num_envs, self.N))
+        self._h.phase_kl_smooth_vjp(nx, nv, vmin, vmax, fa, per, mem.kind, mem.addr(d), mem.kind, mem.addr(gx), mem.addr(gv))
         return gx, gv
-
-    def _empty(self, on_device, shape):
-        if on_device:
-            import torch
-            return torch.empty(shape, dtype=torch.float64, device=f"cuda:{self.device}")
-        return np.empty(shape)
 
     # -- rollout recorder (include/picstep.h: pic_record_*) ----------------------------------------
     def start_recording(self, stride: int = 1, modes: Optional[int] = None, x_bins: int = 0, v_bins: int = 0, phase_bins=None,
@@ -467,8 +452,8 @@ class BatchedPIC:
             feq, vmin, vmax = kl.pop("feq"), float(kl.pop("vmin", -25.0)), float(kl.pop("vmax", 25.0))
             if kl:
                 raise ValueError(f"start_tape: unknown keys in kl: {sorted(kl)}")
-            dev, f, fa, per, nx, nv, _ = self._phase_call(feq, [])
-            self._h.tape_kl_start(nx, nv, vmin, vmax, fa, per, _abi.PIC_DEVICE if dev else _abi.PIC_HOST)
+            mem, (nx, nv, fa, per), _held = self._phase_call(feq)
+            self._h.tape_kl_start(nx, nv, vmin, vmax, fa, per, mem.kind)
             self._tape_kl = True
 
     def stop_tape(self):
@@ -478,25 +463,22 @@ class BatchedPIC:
     def tape_kl(self, on_device: bool = False):
         """The smoothed KL after every step taped so far, [T, num_envs] (a tape opened with kl=...): each row is bit for bit
         what kl_smooth returns after that step.  NumPy, or a float64 CUDA tensor with on_device."""
-        if not getattr(self, "_tape_kl", False):
+        if not self._tape_kl:
             raise _abi.PicError("tape_kl: no tape with a KL is open (start_tape(..., kl=...))")
         T = self._h.tape_stats()["steps"]
-        out = self._empty(on_device, (T, self.num_envs))
+        mem = Mem.of(self, force_device=on_device)
+        out = mem.empty((T, self.num_envs))
         if T == 0:
             return out
-        shared = getattr(self, "_torch_stream", None) is not None
-        if on_device and not shared:                 # different streams: order them through the host
-            import torch
-            torch.cuda.current_stream(self.device).synchronize()
-        self._h.tape_kl(_abi.PIC_DEVICE if on_device else _abi.PIC_HOST, self._addr(out))
-        if on_device and not shared:
-            self._h.sync()
+        mem.enter()
+        self._h.tape_kl(mem.kind, mem.addr(out))
+        mem.leave(self._h)
         return out
 
-    def _set_kl_cot(self, d_KL, T, on_device):
+    def _set_kl_cot(self, d_KL, T, mem):
         """The KL cotangents of a backward onto the tape: d_KL [T, num_envs], or None to clear every row.  Returns what must stay
         alive until the backward has been waited for."""
-        if not getattr(self, "_tape_kl", False):
+        if not self._tape_kl:
             if d_KL is not None:
                 raise ValueError("backward: d_KL needs a tape opened with kl=... (start_tape)")
             return None
@@ -505,16 +487,18 @@ class BatchedPIC:
         if d_KL is None:
             self._h.tape_kl_cot(0, _abi.PIC_HOST, 0, T)
             return None
-        if on_device:
-            import torch
-            d = torch.as_tensor(d_KL, dtype=torch.float64, device=f"cuda:{self.device}").reshape(T, self.num_envs).contiguous()
-            if getattr(self, "_torch_stream", None) is None:
-                torch.cuda.current_stream(self.device).synchronize()
-            self._h.tape_kl_cot(d.data_ptr(), _abi.PIC_DEVICE, 0, T)
-        else:
-            d = np.ascontiguousarray(np.asarray(d_KL, dtype=np.float64).reshape(T, self.num_envs))
-            self._h.tape_kl_cot(d.ctypes.data, _abi.PIC_HOST, 0, T)
+        d = mem.f64(d_KL, (T, self.num_envs))
+        mem.enter()
+        self._h.tape_kl_cot(mem.addr(d), mem.kind, 0, T)
         return d
+
+    def _check_replay(self, who, noun):
+        """After a call in device memory: wait for it, and refuse its result if the replay did not reproduce the forward.  (In
+        host memory the library itself waits and reports it as the call's error.)"""
+        n = self._h.tape_stats()["replay_mismatches"]
+        if n:
+            raise _abi.PicError(f"{who}: the replay differs from the taped forward in {n} particle values (were the particles "
+                                f"written while the tape was open?): the {noun} is not valid")
 
     def tape_stats(self):
         """steps, checkpoint_every, bytes, replay_mismatches (of the last backward; 0 expected), unit_retries, launches."""
@@ -546,60 +530,33 @@ class BatchedPIC:
         actions_t modes_t^T, [num_envs, 2M, 2M] for one gain-law call, a list of them for several.
         A tape opened with kl=...: d_KL [T, num_envs] are cotangents of the KL trace (`tape_kl`); None = 0.  They
         are set on the tape (or all cleared) before the reverse pass, so a backward is a function of its arguments alone."""
-        T = self._h.tape_stats()["steps"]
-        E = self.num_envs
-        given = [a for a in (d_KE, d_PE, d_PE_reward, d_x, d_v, d_modes, d_KL) if a is not None]
-        on_device = any(hasattr(a, "is_cuda") and a.is_cuda for a in given)
-        keep_kl = self._set_kl_cot(d_KL, T, on_device)
-        M = getattr(self, "max_mode", 0)
+        T, E, N, n = self._h.tape_stats()["steps"], self.num_envs, self.N, 2 * self.max_mode
+        mem = Mem.of(self, d_KE, d_PE, d_PE_reward, d_x, d_v, d_modes, d_KL)
+        keep_kl = self._set_kl_cot(d_KL, T, mem)
         calls = self._h.tape_law_calls()
-        if calls:
-            res = self._backward_law(T, calls, on_device, d_KE, d_PE, d_PE_reward, d_x, d_v, d_modes)
-            del keep_kl                              # (both branches of _backward_law wait for the backward)
-            return res
-        if d_modes is not None:
+        if d_modes is not None and not calls:
             raise ValueError("backward: d_modes needs steps of step_feedback_gain on the tape")
-        if not on_device:
-            hist = None
-            if any(a is not None for a in (d_KE, d_PE, d_PE_reward)):
-                hist = np.zeros((T, 3, E))
-                for k, a in enumerate((d_KE, d_PE, d_PE_reward)):
-                    if a is not None:
-                        hist[:, k] = np.asarray(a, dtype=np.float64).reshape(T, E)
-            out = self._h.tape_backward(hist, d_x, d_v, ext=True, actions=M > 0, particles=True)
-            res = {"ext": out["g_ext"], "x0": out["g_x0"], "v0": out["g_v0"]}
-            if M > 0:
-                res["actions"] = out["g_actions"]
-            del keep_kl
-            return res
-        import torch
-        dev = f"cuda:{self.device}"
-        f64 = dict(dtype=torch.float64, device=dev)
-        hist = None
-        if any(a is not None for a in (d_KE, d_PE, d_PE_reward)):
-            hist = torch.zeros((T, 3, E), **f64)
-            for k, a in enumerate((d_KE, d_PE, d_PE_reward)):
-                if a is not None:
-                    hist[:, k] = torch.as_tensor(a, **f64).reshape(T, E)
-        cx = None if d_x is None else torch.as_tensor(d_x, **f64).reshape(E, self.N).contiguous()
-        cv = None if d_v is None else torch.as_tensor(d_v, **f64).reshape(E, self.N).contiguous()
-        res = {"ext": torch.empty((T, E, self.N_mesh), **f64), "x0": torch.empty((E, self.N), **f64),
-               "v0": torch.empty((E, self.N), **f64)}
-        if M > 0:
-            res["actions"] = torch.empty((T, E, 2 * M), **f64)
-        shared = getattr(self, "_torch_stream", None) is not None
-        if not shared:
-            torch.cuda.current_stream(self.device).synchronize()
-
-        def ptr(t):
-            return 0 if t is None or t.numel() == 0 else t.data_ptr()
-        self._h.tape_backward_device(ptr(hist), ptr(cx), ptr(cv), ptr(res["ext"]), ptr(res.get("actions")), ptr(res["x0"]),
-                                     ptr(res["v0"]))
-        st = self._h.tape_stats()                    # (waits for the backward)
-        if st["replay_mismatches"]:
-            raise _abi.PicError(f"backward: the replay differs from the taped forward in {st['replay_mismatches']} particle values "
-                                "(were the particles written while the tape was open?): the gradient is not valid")
-        del keep_kl
+        hist = mem.stack_energies(T, E, d_KE, d_PE, d_PE_reward)
+        cx, cv, cm = mem.f64(d_x, (E, N)), mem.f64(d_v, (E, N)), mem.f64(d_modes, (T, E, n))
+        res = {"ext": mem.out((T, E, self.N_mesh)), "x0": mem.out((E, N)), "v0": mem.out((E, N))}
+        if n > 0:
+            res["actions"] = mem.out((T, E, n))
+        addr = mem.addr
+        mem.enter()
+        if calls:
+            res["modes"] = mem.out((T, E, n))
+            self._h._tape_backward_feedback(mem.kind, addr(hist), addr(cx), addr(cv), addr(cm), addr(res["ext"]),
+                                            addr(res["actions"]), addr(res["x0"]), addr(res["v0"]), addr(res["modes"]))
+        else:
+            self._h._tape_backward(mem.kind, addr(hist), addr(cx), addr(cv), addr(res["ext"]), addr(res.get("actions")),
+                                   addr(res["x0"]), addr(res["v0"]))
+        if mem.on_device:
+            self._check_replay("backward", "gradient")
+        del keep_kl                                  # (the backward has been waited for)
+        if calls:                                    # sum over each gain-law call's steps of actions_t modes_t^T
+            g = [sum(res["actions"][s][:, :, None] * res["modes"][s][:, None, :] for s in range(first, first + k))
+                 for first, k in calls]
+            res["gain"] = g[0] if len(g) == 1 else g
         return res
 
     def tangent(self, d_ext=None, d_actions=None, d_x0=None, d_v0=None, fields: bool = False):
@@ -612,7 +569,7 @@ class BatchedPIC:
         backward).  Raises PicError if the replay of the taped steps does not reproduce the forward bit for bit."""
         T = self._h.tape_stats()["steps"]
         E, N, Ng = self.num_envs, self.N, self.N_mesh
-        n = 2 * getattr(self, "max_mode", 0)
+        n = 2 * self.max_mode
         base = {"d_ext": (T, E, Ng), "d_actions": (T, E, n), "d_x0": (E, N), "d_v0": (E, N)}
         given = {k: a for k, a in (("d_ext", d_ext), ("d_actions", d_actions), ("d_x0", d_x0), ("d_v0", d_v0)) if a is not None}
         ks = {int(a.shape[0]) for k, a in given.items() if len(a.shape) == len(base[k]) + 1}
@@ -624,35 +581,20 @@ class BatchedPIC:
             want = ((K,) if batched else ()) + base[k]
             if tuple(a.shape) != want:
                 raise ValueError(f"tangent: {k} must have shape {want}, not {tuple(a.shape)}")
-        on_device = any(hasattr(a, "is_cuda") and a.is_cuda for a in given.values())
-
-        def split(hist, x, v, em):
-            res = {"KE": hist[:, :, 0], "PE": hist[:, :, 1], "PE_reward": hist[:, :, 2], "x": x, "v": v}
-            if fields:
-                res["E_mesh"] = em
-            return res if batched else {k: a[0] for k, a in res.items()}
-        if not on_device:
-            out = self._h.tape_tangent(K, d_ext, d_actions, d_x0, d_v0, fields)
-            return split(out["hist"], out["x"], out["v"], out.get("E_mesh"))
-        import torch
-        f64 = dict(dtype=torch.float64, device=f"cuda:{self.device}")
-        ins = {k: torch.as_tensor(a, **f64).reshape((K,) + base[k]).contiguous() for k, a in given.items()}
-        hist = torch.empty((K, T, 3, E), **f64)
-        x, v = torch.empty((K, E, N), **f64), torch.empty((K, E, N), **f64)
-        em = torch.empty((K, T, E, Ng), **f64) if fields else None
-        shared = getattr(self, "_torch_stream", None) is not None
-        if not shared:
-            torch.cuda.current_stream(self.device).synchronize()
-
-        def ptr(t):
-            return 0 if t is None or t.numel() == 0 else t.data_ptr()
-        self._h.tape_tangent_device(K, ptr(ins.get("d_ext")), ptr(ins.get("d_actions")), ptr(ins.get("d_x0")),
-                                    ptr(ins.get("d_v0")), ptr(hist), ptr(x), ptr(v), ptr(em))
-        st = self._h.tape_stats()                    # (waits for the tangent)
-        if st["replay_mismatches"]:
-            raise _abi.PicError(f"tangent: the replay differs from the taped forward in {st['replay_mismatches']} particle values "
-                                "(were the particles written while the tape was open?): the tangent is not valid")
-        return split(hist, x, v, em)
+        mem = Mem.of(self, *given.values())
+        ins = {k: mem.f64(a, (K,) + base[k]) for k, a in given.items()}
+        hist, x, v = mem.out((K, T, 3, E)), mem.out((K, E, N)), mem.out((K, E, N))
+        em = mem.out((K, T, E, Ng)) if fields else None
+        addr = mem.addr
+        mem.enter()
+        self._h._tape_tangent(mem.kind, K, addr(ins.get("d_ext")), addr(ins.get("d_actions")), addr(ins.get("d_x0")),
+                              addr(ins.get("d_v0")), addr(hist), addr(x), addr(v), addr(em))
+        if mem.on_device:
+            self._check_replay("tangent", "tangent")
+        res = {"KE": hist[:, :, 0], "PE": hist[:, :, 1], "PE_reward": hist[:, :, 2], "x": x, "v": v}
+        if fields:
+            res["E_mesh"] = em
+        return res if batched else {k: a[0] for k, a in res.items()}
 
     def walk(self, obs_modes: Optional[int] = None, on_device: bool = False):
         """The reverse pass of the open tape one step at a time (pic_tape_walk_*): returns a TapeWalk whose
@@ -660,54 +602,8 @@ class BatchedPIC:
         M_o (default: the actuator's max_mode, else 1) sets the layout of the mode cotangents [num_envs, 2*M_o] (Re E_1..E_Mo,
         then Im, the map of `modes`).  Outputs are float64 CUDA tensors if any cotangent of the call is one or on_device is
         set, NumPy arrays otherwise.  A later step on the environment, another walk or backward abandons this one (PicError)."""
-        mo = int(obs_modes) if obs_modes is not None else max(1, getattr(self, "max_mode", 0))
+        mo = int(obs_modes) if obs_modes is not None else max(1, self.max_mode)
         return TapeWalk(self, mo, on_device)
-
-    def _backward_law(self, T, calls, on_device, d_KE, d_PE, d_PE_reward, d_x, d_v, d_modes):
-        E, n = self.num_envs, 2 * self.max_mode
-
-        def gains(act, md):
-            g = [sum(act[s][:, :, None] * md[s][:, None, :] for s in range(first, first + k)) for first, k in calls]
-            return g[0] if len(g) == 1 else g
-        if not on_device:
-            hist = None
-            if any(a is not None for a in (d_KE, d_PE, d_PE_reward)):
-                hist = np.zeros((T, 3, E))
-                for k, a in enumerate((d_KE, d_PE, d_PE_reward)):
-                    if a is not None:
-                        hist[:, k] = np.asarray(a, dtype=np.float64).reshape(T, E)
-            out = self._h.tape_backward_feedback(hist, d_x, d_v, d_modes)
-            res = {"ext": out["g_ext"], "x0": out["g_x0"], "v0": out["g_v0"], "actions": out["g_actions"], "modes": out["modes"]}
-            res["gain"] = gains(res["actions"], res["modes"])
-            return res
-        import torch
-        dev = f"cuda:{self.device}"
-        f64 = dict(dtype=torch.float64, device=dev)
-        hist = None
-        if any(a is not None for a in (d_KE, d_PE, d_PE_reward)):
-            hist = torch.zeros((T, 3, E), **f64)
-            for k, a in enumerate((d_KE, d_PE, d_PE_reward)):
-                if a is not None:
-                    hist[:, k] = torch.as_tensor(a, **f64).reshape(T, E)
-        cx = None if d_x is None else torch.as_tensor(d_x, **f64).reshape(E, self.N).contiguous()
-        cv = None if d_v is None else torch.as_tensor(d_v, **f64).reshape(E, self.N).contiguous()
-        cm = None if d_modes is None else torch.as_tensor(d_modes, **f64).reshape(T, E, n).contiguous()
-        res = {"ext": torch.empty((T, E, self.N_mesh), **f64), "x0": torch.empty((E, self.N), **f64),
-               "v0": torch.empty((E, self.N), **f64), "actions": torch.empty((T, E, n), **f64), "modes": torch.empty((T, E, n), **f64)}
-        shared = getattr(self, "_torch_stream", None) is not None
-        if not shared:
-            torch.cuda.current_stream(self.device).synchronize()
-
-        def ptr(t):
-            return 0 if t is None or t.numel() == 0 else t.data_ptr()
-        self._h.tape_backward_feedback_device(ptr(hist), ptr(cx), ptr(cv), ptr(cm), ptr(res["ext"]), ptr(res["actions"]),
-                                              ptr(res["x0"]), ptr(res["v0"]), ptr(res["modes"]))
-        st = self._h.tape_stats()                    # (waits for the backward)
-        if st["replay_mismatches"]:
-            raise _abi.PicError(f"backward: the replay differs from the taped forward in {st['replay_mismatches']} particle values "
-                                "(were the particles written while the tape was open?): the gradient is not valid")
-        res["gain"] = gains(res["actions"], res["modes"])
-        return res
 
     def close(self):
         self._h.close()
@@ -719,49 +615,14 @@ class TapeWalk:
     def __init__(self, env, obs_modes, on_device=False):
         self.env, self.obs_modes, self.on_device = env, int(obs_modes), bool(on_device)
         env._h.tape_walk_begin(self.obs_modes)
-        env._walk_serial = getattr(env, "_walk_serial", 0) + 1
+        env._walk_serial += 1
         self._serial = env._walk_serial
         # a tape with a KL: the step each call reverses, for its row of KL cotangents
-        self._kl_next = env._h.tape_stats()["steps"] - 1 if getattr(env, "_tape_kl", False) else None
+        self._kl_next = env._h.tape_stats()["steps"] - 1 if env._tape_kl else None
 
     def _live(self, who):
-        if getattr(self.env, "_walk_serial", None) != self._serial:
+        if self.env._walk_serial != self._serial:
             raise _abi.PicError(f"walk.{who}: another walk or backward has replaced this one")
-
-    def _args(self, arrays, shapes):
-        """(on_device, keep-alive list, addresses) of the cotangents, each None = 0."""
-        on_device = self.on_device or any(hasattr(a, "is_cuda") and a.is_cuda for a in arrays if a is not None)
-        keep, addr = [], []
-        for a, shape in zip(arrays, shapes):
-            if a is None:
-                addr.append(0)
-                continue
-            if on_device:
-                import torch
-                a = torch.as_tensor(a, dtype=torch.float64, device=f"cuda:{self.env.device}").reshape(shape).contiguous()
-                addr.append(a.data_ptr())
-            else:
-                a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(shape))
-                addr.append(a.__array_interface__["data"][0])
-            keep.append(a)
-        return on_device, keep, addr
-
-    def _empty(self, on_device, shape):
-        if on_device:
-            import torch
-            return torch.empty(shape, dtype=torch.float64, device=f"cuda:{self.env.device}")
-        return np.zeros(shape)
-
-    @staticmethod
-    def _addr(a):
-        return 0 if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else a.__array_interface__["data"][0])
-
-    def _enter(self, on_device):
-        shared = getattr(self.env, "_torch_stream", None) is not None
-        if on_device and not shared:        # different streams: order them through the host
-            import torch
-            torch.cuda.current_stream(self.env.device).synchronize()
-        return on_device and not shared
 
     def step(self, d_energies=None, d_x=None, d_v=None, d_modes=None, d_kl=None):
         """Reverse the next step t: d_energies [3, num_envs] (its KE, PE, PE_reward), d_x, d_v [num_envs, N] on the state it
@@ -772,20 +633,18 @@ class TapeWalk:
         env, E = self.env, self.env.num_envs
         if d_kl is not None and self._kl_next is None:
             raise ValueError("walk.step: d_kl needs a tape opened with kl=... (start_tape)")
-        on_device, keep, addr = self._args((d_energies, d_x, d_v, d_modes, d_kl),
-                                           ((3, E), (E, env.N), (E, env.N), (E, 2 * self.obs_modes), (E,)))
-        M = getattr(env, "max_mode", 0)
-        g_ext = self._empty(on_device, (E, env.N_mesh))
-        g_act = self._empty(on_device, (E, 2 * M)) if M > 0 else None
-        wait = self._enter(on_device)
+        mem = Mem.of(env, d_energies, d_x, d_v, d_modes, d_kl, force_device=self.on_device)
+        ce, cx, cv = mem.f64(d_energies, (3, E)), mem.f64(d_x, (E, env.N)), mem.f64(d_v, (E, env.N))
+        cm, ck = mem.f64(d_modes, (E, 2 * self.obs_modes)), mem.f64(d_kl, (E,))
+        g_ext = mem.out((E, env.N_mesh))
+        g_act = mem.out((E, 2 * env.max_mode)) if env.max_mode > 0 else None
+        addr = mem.addr
+        mem.enter()
         if self._kl_next is not None and self._kl_next >= 0:
-            env._h.tape_kl_cot(addr[4], _abi.PIC_DEVICE if on_device and addr[4] else _abi.PIC_HOST, self._kl_next, 1)
+            env._h.tape_kl_cot(addr(ck), _abi.PIC_HOST if ck is None else mem.kind, self._kl_next, 1)
             self._kl_next -= 1
-        t = env._h.tape_walk_step(addr[0], addr[1], addr[2], addr[3], _abi.PIC_DEVICE if on_device else _abi.PIC_HOST,
-                                  self._addr(g_ext), self._addr(g_act))
-        if wait:
-            env._h.sync()
-        del keep
+        t = env._h.tape_walk_step(addr(ce), addr(cx), addr(cv), addr(cm), mem.kind, addr(g_ext), addr(g_act))
+        mem.leave(env._h)                            # (the cotangents above are alive until here)
         return t, g_ext, g_act
 
     def end(self, d_x0=None, d_v0=None, d_modes0=None):
@@ -793,15 +652,12 @@ class TapeWalk:
         [num_envs, N].  Raises PicError if a replay of the walk differed from the taped forward."""
         self._live("end")
         env, E = self.env, self.env.num_envs
-        on_device, keep, addr = self._args((d_x0, d_v0, d_modes0), ((E, env.N), (E, env.N), (E, 2 * self.obs_modes)))
-        g_x0, g_v0 = self._empty(on_device, (E, env.N)), self._empty(on_device, (E, env.N))
-        self._enter(on_device)
-        env._h.tape_walk_end(addr[0], addr[1], addr[2], _abi.PIC_DEVICE if on_device else _abi.PIC_HOST, self._addr(g_x0),
-                             self._addr(g_v0))
-        del keep
-        if on_device:
-            st = env._h.tape_stats()                 # (waits for the walk)
-            if st["replay_mismatches"]:
-                raise _abi.PicError(f"walk.end: the replay differs from the taped forward in {st['replay_mismatches']} particle "
-                                    "values (were the particles written while the tape was open?): the gradient is not valid")
+        mem = Mem.of(env, d_x0, d_v0, d_modes0, force_device=self.on_device)
+        cx, cv, cm = mem.f64(d_x0, (E, env.N)), mem.f64(d_v0, (E, env.N)), mem.f64(d_modes0, (E, 2 * self.obs_modes))
+        g_x0, g_v0 = mem.out((E, env.N)), mem.out((E, env.N))
+        addr = mem.addr
+        mem.enter()
+        env._h.tape_walk_end(addr(cx), addr(cv), addr(cm), mem.kind, addr(g_x0), addr(g_v0))
+        if mem.on_device:
+            env._check_replay("walk.end", "gradient")
         return g_x0, g_v0

@@ -33,8 +33,13 @@ from .._abi import PicError
 def _start(env, T, checkpoint_every, kl=None):
     env.stop_tape()
     env.start_tape(T, checkpoint_every, kl=kl)
-    env._tape_serial = getattr(env, "_tape_serial", 0) + 1
+    env._tape_serial += 1
     return env._tape_serial
+
+
+def _check_live(env, serial, steps, who):
+    if env._tape_serial != serial or env.tape_stats()["steps"] != steps:
+        raise PicError(f"{who}: the environment has moved on since this rollout (a further step, rollout or reset)")
 
 
 class _Rollout(torch.autograd.Function):
@@ -55,17 +60,9 @@ class _Rollout(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_ke, g_pe, g_per, g_kl=None):
-        env = ctx.env
-        if getattr(env, "_tape_serial", None) != ctx.serial or env.tape_stats()["steps"] != ctx.steps:
-            raise PicError("backward: the environment has moved on since this rollout (a further step, rollout or reset)")
-        if g_ke.is_cuda:
-            out = env.backward(d_KE=g_ke.contiguous(), d_PE=g_pe.contiguous(), d_PE_reward=g_per.contiguous(),
-                               d_KL=g_kl.contiguous() if ctx.kl else None)
-            g = out["actions"] if ctx.kind == "actions" else out["ext"]
-        else:
-            out = env.backward(d_KE=g_ke.numpy(), d_PE=g_pe.numpy(), d_PE_reward=g_per.numpy(),
-                               d_KL=g_kl.numpy() if ctx.kl else None)
-            g = torch.as_tensor(out["actions"] if ctx.kind == "actions" else out["ext"])
+        _check_live(ctx.env, ctx.serial, ctx.steps, "backward")
+        out = ctx.env.backward(d_KE=g_ke, d_PE=g_pe, d_PE_reward=g_per, d_KL=g_kl if ctx.kl else None)
+        g = torch.as_tensor(out["actions" if ctx.kind == "actions" else "ext"])       # (NumPy out for CPU cotangents in)
         return g, None, None, None, None
 
     @staticmethod
@@ -74,13 +71,11 @@ class _Rollout(torch.autograd.Function):
         tape this rollout opened.  The KL output of a rollout with kl=... gets a ZERO tangent: forward mode of
         the KL is not built, so do not read a directional derivative of the KL from it."""
         env = ctx.env
-        if getattr(env, "_tape_serial", None) != ctx.serial or env.tape_stats()["steps"] != ctx.steps:
-            raise PicError("jvp: the environment has moved on since this rollout (a further step, rollout or reset)")
+        _check_live(env, ctx.serial, ctx.steps, "jvp")
         zero = lambda: torch.zeros((ctx.steps, env.num_envs), dtype=torch.float64, device=ctx.device)  # noqa: E731
         if u_t is None:
             return tuple(zero() for _ in range(4 if ctx.kl else 3))
-        u = u_t.contiguous() if u_t.is_cuda else u_t.detach().numpy()
-        out = env.tangent(**{"d_actions" if ctx.kind == "actions" else "d_ext": u})
+        out = env.tangent(**{"d_actions" if ctx.kind == "actions" else "d_ext": u_t.detach()})
         res = tuple(torch.as_tensor(out[k], dtype=torch.float64, device=ctx.device) for k in ("KE", "PE", "PE_reward"))
         return res + ((zero(),) if ctx.kl else ())
 
@@ -90,7 +85,7 @@ def rollout(env, actions, checkpoint_every=0, kl=None):
     pic_step_actions_traj on a tape; returns KE, PE, PE_reward [T, num_envs] (float64, on actions' device), differentiable
     with respect to `actions`.  With kl=dict(feq=..., vmin=..., vmax=...) a fourth output follows: the smoothed KL after
     every step, [T, num_envs], differentiable too."""
-    if getattr(env, "max_mode", 0) == 0:
+    if env.max_mode == 0:
         raise PicError("rollout: the environment has no actuator (set_actuator)")
     return _Rollout.apply(actions, env, "actions", int(checkpoint_every), kl)
 
@@ -117,17 +112,9 @@ class _RolloutFeedback(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_ke, g_pe, g_per, g_modes, g_kl=None):
-        env = ctx.env
-        if getattr(env, "_tape_serial", None) != ctx.serial or env.tape_stats()["steps"] != ctx.steps:
-            raise PicError("backward: the environment has moved on since this rollout (a further step, rollout or reset)")
-        if g_ke.is_cuda:
-            out = env.backward(d_KE=g_ke.contiguous(), d_PE=g_pe.contiguous(), d_PE_reward=g_per.contiguous(),
-                               d_modes=g_modes.contiguous(), d_KL=g_kl.contiguous() if ctx.kl else None)
-            g = out["gain"]
-        else:
-            out = env.backward(d_KE=g_ke.numpy(), d_PE=g_pe.numpy(), d_PE_reward=g_per.numpy(), d_modes=g_modes.numpy(),
-                               d_KL=g_kl.numpy() if ctx.kl else None)
-            g = torch.as_tensor(out["gain"])
+        _check_live(ctx.env, ctx.serial, ctx.steps, "backward")
+        out = ctx.env.backward(d_KE=g_ke, d_PE=g_pe, d_PE_reward=g_per, d_modes=g_modes, d_KL=g_kl if ctx.kl else None)
+        g = torch.as_tensor(out["gain"])             # (NumPy out for CPU cotangents in)
         return (g.sum(0) if ctx.shared else g), None, None, None, None
 
 
@@ -137,7 +124,7 @@ def rollout_feedback(env, gain, T, checkpoint_every=0, kl=None):
     respect to `gain` (float64, [num_envs, 2M, 2M], or [2M, 2M] shared by every environment: its gradient is the sum over
     them).  Cotangents on `modes` reach the plasma through d_modes, so spectral losses such as sum |E_1|^2 work too.  With kl=...
     the smoothed KL after every step, [T, num_envs], follows as a fifth differentiable output."""
-    if getattr(env, "max_mode", 0) == 0:
+    if env.max_mode == 0:
         raise PicError("rollout_feedback: the environment has no actuator (set_actuator)")
     return _RolloutFeedback.apply(gain, env, int(T), int(checkpoint_every), kl)
 
@@ -155,8 +142,7 @@ class _PolicyWalk:
         cotangent reached (no output of theirs was used) with zero cotangents."""
         env = self.env
         if self.walk is None:
-            if getattr(env, "_tape_serial", None) != self.serial or env.tape_stats()["steps"] != self.T:
-                raise PicError("backward: the environment has moved on since this rollout (a further step, rollout or reset)")
+            _check_live(env, self.serial, self.T, "backward")
             self.walk, self.next = env.walk(self.obs_modes, on_device=True), self.T - 1
         if self.next < t:
             raise PicError(f"backward: step {t} reached after step {self.next + 1} was reversed (out of order)")
@@ -234,7 +220,7 @@ def rollout_policy(env, policy, T, observe="modes", obs_modes=None, checkpoint_e
     the backward walks the tape step by step (pic_tape_walk_*) and puts the policy's own vector-Jacobian product
     between two reverse steps.  With env.use_torch_stream() no step synchronises the host.  With kl=... the smoothed KL after
     every step, [T, num_envs], follows as a sixth differentiable output (reading each step's value waits for the step)."""
-    if getattr(env, "max_mode", 0) == 0:
+    if env.max_mode == 0:
         raise PicError("rollout_policy: the environment has no actuator (set_actuator)")
     if observe not in ("modes", "state"):
         raise ValueError('observe must be "modes" or "state"')
