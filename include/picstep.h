@@ -324,6 +324,15 @@ int pic_phase_kl_smooth(pic_handle* h, const pic_phase_spec* spec, int mem_kind,
  * and 0 where f = 0, gathered at a particle's four bins with the CIC slopes -+1/dx in x and -+1/dv in v (0 in v in the clamped
  * half-bins; 0 for a dropped particle). */
 int pic_phase_kl_smooth_vjp(pic_handle* h, const pic_phase_spec* spec, const double* cot_kl, int mem_kind, void* g_x, void* g_v);
+/* Jacobian-vector product of kl, the forward mode of the same derivative (additive to ABI 5): for K directions
+ * (1 <= K <= 8) d_kl[k][e] = sum_i dkl_e/dx_i d_x[k][e][i] + dkl_e/dv_i d_v[k][e][i] over the current particles, with exactly the
+ * dkl/dx, dkl/dv that pic_phase_kl_smooth_vjp returns for cot_kl = 1.  d_x, d_v [K][num_envs][N] float64 (dense; either may be
+ * NULL = 0), d_kl [K][num_envs], all in mem_kind memory.  Needs feq; spec is checked as pic_phase_kl_smooth_vjp checks it.
+ * Every environment's particles are cut into chunks of 8192 (a constant); a chunk's products are summed in a fixed order and the
+ * chunks' sums in ascending order, in float64: the result is bitwise reproducible, each direction is computed on its own, and
+ * nothing depends on blocks_per_env, the schedule or the other environments of the batch.  Returns when d_kl has arrived. */
+int pic_phase_kl_smooth_jvp(pic_handle* h, const pic_phase_spec* spec, int K, const void* d_x, const void* d_v, int mem_kind,
+                            double* d_kl);
 
 /* Per-kernel timing with HIP events on the handle's stream (bench.py's roofline leg).
  * kinds: 0..3 = sweeps A..D, 4 = field solve, 5 = auxiliary sweeps (refresh, first deposits), 6 = resident launches,
@@ -542,10 +551,26 @@ int pic_tape_tangent(pic_handle* h, int K, const double* d_ext, const double* d_
  * in progress has already reversed are refused with PIC_ESTATE; rows outside [0, T) or a bad mem_kind are PIC_EINVAL; no tape
  * with a KL open is PIC_ESTATE (pic_tape_kl too).  Gradients with KL cotangents are bitwise reproducible and do not depend on
  * blocks_per_env, the checkpoint interval, the schedule or the other environments of the batch.
- * Forward mode of the KL is not built: pic_tape_tangent works on such a tape and ignores the KL. */
+ * Forward mode: pic_tape_tangent works on such a tape and ignores the KL; pic_tape_tangent_kl returns the KL's tangents too. */
 int pic_tape_kl_start(pic_handle* h, const pic_phase_spec* spec);
 int pic_tape_kl(pic_handle* h, int mem_kind, double* kl);
 int pic_tape_kl_cot(pic_handle* h, const double* cot_kl, int mem_kind, int64_t first_step, int64_t nsteps);
+/* pic_tape_tangent with the tangents of the per-step KL (additive to ABI 5): the arguments of pic_tape_tangent and
+ * d_kl [K][T][num_envs] in mem_kind memory, d_kl[k][t][e] = the derivative of kl[t][e] (pic_tape_kl) along direction k, the
+ * almost-everywhere derivative pic_tape_kl_cot's reverse pass uses: forward and reverse are dual.  d_kl = NULL is pic_tape_tangent
+ * itself (same kernels, same bits; a KL on the tape is ignored).  With d_kl the tape must hold a KL (pic_tape_kl_start), else
+ * PIC_ESTATE; every other refusal is pic_tape_tangent's, a tape with steps of pic_step_feedback_gain included.  Every step then
+ * costs 4 more kernels, counted in `launches`: behind the third sub-stage of step t the deposit and the finishing kernel on the
+ * replayed state the step left (unit cotangents), pic_phase_kl_smooth_jvp's pass over the particles against the tangent state,
+ * and the sum of its chunks.  All other outputs are bit for bit pic_tape_tangent's, and d_kl shares their guarantees: K
+ * directions in one call equal K calls, and nothing depends on blocks_per_env, the checkpoint interval, the schedule or the other
+ * environments of the batch (the sums' order: pic_phase_kl_smooth_jvp).  The KL trace, the rows of pic_tape_kl_cot and a later
+ * pic_tape_backward* are untouched.  The first call with d_kl allocates, with E = num_envs and each part rounded up to 256 bytes,
+ *     8 (E  +  8 E ceil(ceil(N / 2) / 4096))   bytes
+ * (the unit cotangents and the chunks' sums of 8 directions), which count in `bytes` and against budget_bytes (PIC_ENOMEM, the
+ * tape still usable) and are freed by pic_tape_stop.  T = 0: nothing is written to d_kl. */
+int pic_tape_tangent_kl(pic_handle* h, int K, const double* d_ext, const double* d_actions, const void* d_x0, const void* d_v0,
+                        int mem_kind, double* d_hist, void* d_x, void* d_v, double* d_E_mesh, double* d_kl);
 
 int pic_sync(pic_handle* h);
 /* Number of particle positions found non-finite or out of range by the last sweeps (0 = healthy).  Counts the state's

@@ -133,6 +133,7 @@ SIGNATURES = {
     "pic_phase_kl": [_vp, C.c_int, C.c_double, C.c_double, _vp, _vp],
     "pic_phase_kl_smooth": [_vp, C.POINTER(PicPhaseSpec), C.c_int, _vp, _vp],
     "pic_phase_kl_smooth_vjp": [_vp, C.POINTER(PicPhaseSpec), _vp, C.c_int, _vp, _vp],
+    "pic_phase_kl_smooth_jvp": [_vp, C.POINTER(PicPhaseSpec), C.c_int, _vp, _vp, C.c_int, _vp],
     "pic_stream_probe": [_vp, C.c_int, _dp],
     "pic_record_start": [_vp, C.POINTER(PicRecordConfig)],
     "pic_record_now": [_vp],
@@ -148,6 +149,7 @@ SIGNATURES = {
     "pic_tape_walk_step": [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _i64p],
     "pic_tape_walk_end": [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp],
     "pic_tape_tangent": [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp],
+    "pic_tape_tangent_kl": [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp],
     "pic_tape_kl_start": [_vp, C.POINTER(PicPhaseSpec)],
     "pic_tape_kl": [_vp, C.c_int, _vp],
     "pic_tape_kl_cot": [_vp, _vp, C.c_int, C.c_int64, C.c_int64],
@@ -641,6 +643,12 @@ class Handle:
         p = _ptrs(cot_kl, g_x, g_v)
         self._chk(self.lib.pic_phase_kl_smooth_vjp(self._h, C.byref(spec), p[0], int(mem_kind), p[1], p[2]))
 
+    def phase_kl_smooth_jvp(self, nx, nv, vmin, vmax, feq, feq_per_env, feq_kind, K, d_x, d_v, mem_kind, d_kl):
+        """pic_phase_kl_smooth_jvp on addresses (int, 0 = NULL)."""
+        spec = _phase_spec(nx, nv, vmin, vmax, feq, feq_per_env, feq_kind)
+        p = _ptrs(d_x, d_v, d_kl)
+        self._chk(self.lib.pic_phase_kl_smooth_jvp(self._h, C.byref(spec), int(K), p[0], p[1], int(mem_kind), p[2]))
+
     # -- rollout recorder (pic_record_*) ------------------------------------------------------------
     def record_start(self, stride=1, n_modes=0, x_bins=0, v_bins=0, phase_bins=(0, 0), vmin=-25.0, vmax=25.0, phase_dx=0.0,
                      phase_dv=0.0, feq=None, capacity=1024):
@@ -767,9 +775,9 @@ class Handle:
         p = _ptrs(cot_x0, cot_v0, cot_modes0, g_x0, g_v0)
         self._chk(self.lib.pic_tape_walk_end(self._h, p[0], p[1], p[2], int(mem_kind), p[3], p[4]))
 
-    def tape_tangent(self, K, d_ext=None, d_actions=None, d_x0=None, d_v0=None, fields=False):
+    def tape_tangent(self, K, d_ext=None, d_actions=None, d_x0=None, d_v0=None, fields=False, kl=False):
         """pic_tape_tangent with host arrays: K directions in, dict out with hist [K][T][3][num_envs], x / v [K][num_envs][N]
-        and, with fields, E_mesh [K][T][num_envs][Ng]."""
+        and, with fields, E_mesh [K][T][num_envs][Ng]; with kl (pic_tape_tangent_kl), KL [K][T][num_envs]."""
         T = self.tape_stats()["steps"]
         E, K = self.num_envs, int(K)
         ins = [_host(d_ext, (K, T, E, self.Ng)), _host(d_actions, (K, T, E, -1)), _host(d_x0, (K, E, self.N)),
@@ -777,17 +785,25 @@ class Handle:
         out = {"hist": np.zeros((K, T, 3, E)), "x": np.zeros((K, E, self.N)), "v": np.zeros((K, E, self.N))}
         if fields:
             out["E_mesh"] = np.zeros((K, T, E, self.Ng))
-        self._tape_tangent(PIC_HOST, K, *_addrs(*ins, out["hist"], out["x"], out["v"], out.get("E_mesh")))
+        if kl:
+            out["KL"] = np.zeros((K, T, E))
+        self._tape_tangent(PIC_HOST, K, *_addrs(*ins, out["hist"], out["x"], out["v"], out.get("E_mesh")),
+                           kl=out["KL"].ctypes.data if kl else None)
         return out
 
     def tape_tangent_device(self, K, d_ext, d_actions, d_x0, d_v0, hist, x, v, E_mesh):
         """pic_tape_tangent on device pointers (int, 0 = NULL); asynchronous on the handle's stream."""
         self._tape_tangent(PIC_DEVICE, K, d_ext, d_actions, d_x0, d_v0, hist, x, v, E_mesh)
 
-    def _tape_tangent(self, mem_kind, K, d_ext, d_actions, d_x0, d_v0, hist, x, v, E_mesh):
-        """pic_tape_tangent on addresses (int, 0 = NULL) in mem_kind memory."""
+    def _tape_tangent(self, mem_kind, K, d_ext, d_actions, d_x0, d_v0, hist, x, v, E_mesh, kl=None):
+        """pic_tape_tangent on addresses (int, 0 = NULL) in mem_kind memory; kl: None, or the address of d_kl (an address,
+        0 = NULL, makes the call pic_tape_tangent_kl)."""
         p = _ptrs(d_ext, d_actions, d_x0, d_v0, hist, x, v, E_mesh)
-        self._chk(self.lib.pic_tape_tangent(self._h, int(K), p[0], p[1], p[2], p[3], int(mem_kind), p[4], p[5], p[6], p[7]))
+        if kl is None:
+            self._chk(self.lib.pic_tape_tangent(self._h, int(K), p[0], p[1], p[2], p[3], int(mem_kind), p[4], p[5], p[6], p[7]))
+        else:
+            self._chk(self.lib.pic_tape_tangent_kl(self._h, int(K), p[0], p[1], p[2], p[3], int(mem_kind), p[4], p[5], p[6], p[7],
+                                                   _ptrs(kl)[0]))
 
     def tape_kl_start(self, nx, nv, vmin, vmax, feq, feq_per_env, feq_kind):
         """pic_tape_kl_start: feq an address in feq_kind memory (the tape copies it)."""

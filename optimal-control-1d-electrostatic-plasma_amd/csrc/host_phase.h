@@ -133,3 +133,75 @@ int pic_phase_kl_smooth_vjp(pic_handle* h, const pic_phase_spec* s, const double
   if (e != hipSuccess) return fail(h, PIC_EHIP, std::string("pic_phase_kl_smooth_vjp: ") + hipGetErrorString(e));
   return PIC_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Forward mode of the smoothed KL (include/picstep.h: pic_phase_kl_smooth_jvp; pic_phase.h)
+// ---------------------------------------------------------------------------------------------
+// chunks of kJvpChunkTiles tiles per environment: a constant of N alone
+static int phase_jvp_chunks(const pic_handle* h) {
+  return (int)(((h->cfg.N + 1) / 2 + kJvpChunkTiles - 1) / kJvpChunkTiles);
+}
+
+// a row of n ones in device memory (the unit cotangents the finishing kernel scales g with)
+static hipError_t phase_fill_ones(pic_handle* h, double* dst, size_t n) {
+  const std::vector<double> ones(n, 1.0);
+  hipError_t e = hipMemcpyAsync(dst, ones.data(), n * sizeof(double), hipMemcpyHostToDevice, h->stream);
+  return e != hipSuccess ? e : hipStreamSynchronize(h->stream);      // (`ones` goes away behind this call)
+}
+
+// The two kernels behind a deposit and finish that left the unit-cotangent grid g of the particles x, v [env][ld]:
+// out[d * out_dstride + env] = sum_k dKL~/dx_k dx_k + dKL~/dv_k dv_k for the K directions of `j` (dx, dv, dstride, erow set by
+// the caller; part: [K][env][chunks] device memory)
+static hipError_t phase_jvp_enqueue(pic_handle* h, const pic_phase_spec* s, const PhaseArgs& a, const double* x, const double* v,
+                                    const double* g, PhaseJvpArgs j, int K, double* out, long long out_dstride) {
+  const int E = h->cfg.num_envs;
+  j.K = K; j.num_envs = E; j.chunks = phase_jvp_chunks(h);
+  const double norm = phase_norm(h, s);
+  const dim3 grid((unsigned)j.chunks, (unsigned)E);
+  if (K == 1) hipLaunchKernelGGL(phase_jvp_kernel<1>, grid, dim3(BLOCK), 0, h->stream, x, v, g, a, norm * a.rdx, norm * a.rdv, j);
+  else if (K <= 4) hipLaunchKernelGGL(phase_jvp_kernel<4>, grid, dim3(BLOCK), 0, h->stream, x, v, g, a, norm * a.rdx, norm * a.rdv, j);
+  else hipLaunchKernelGGL(phase_jvp_kernel<8>, grid, dim3(BLOCK), 0, h->stream, x, v, g, a, norm * a.rdx, norm * a.rdv, j);
+  hipLaunchKernelGGL(phase_jvp_finish_kernel, dim3(E, K), dim3(1), 0, h->stream, (const double*)j.part, j.chunks, E, out, out_dstride);
+  return hipGetLastError();
+}
+
+int pic_phase_kl_smooth_jvp(pic_handle* h, const pic_phase_spec* s, int K, const void* d_x, const void* d_v, int mem_kind,
+                            double* d_kl) {
+  int rc = phase_check(h, s, mem_kind, "pic_phase_kl_smooth_jvp");
+  if (rc) return rc;
+  if (!s->feq || !d_kl) return fail(h, PIC_EINVAL, "pic_phase_kl_smooth_jvp: needs spec->feq and d_kl");
+  if (K < 1 || K > kMaxTangents) return fail(h, PIC_EINVAL, "pic_phase_kl_smooth_jvp: need 1 <= K <= " + std::to_string(kMaxTangents));
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  const int E = h->cfg.num_envs, chunks = phase_jvp_chunks(h);
+  const size_t nb2 = (size_t)s->nx * s->nv, N = h->cfg.N, pbytes = (size_t)K * E * N * sizeof(double);
+  const size_t feq_bytes = (s->feq_per_env ? E : 1) * nb2 * sizeof(double), obytes = (size_t)K * E * sizeof(double);
+  DeviceBuf<unsigned long long> acc;
+  DeviceBuf<double> dfeq, dones, dg, dpart, ddx, ddv, dout;
+  const double *feq = nullptr, *tx = nullptr, *tv = nullptr;
+  PhaseArgs a;
+  const bool host = mem_kind == PIC_HOST;       // host memory goes through device buffers of this call
+  hipError_t e = alloc_zeroed(acc, (size_t)E * nb2 * sizeof(unsigned long long), h->stream);
+  if (e == hipSuccess && s->feq_mem_kind == PIC_HOST) e = alloc(dfeq, feq_bytes);
+  if (e == hipSuccess) e = device_input(h, s->feq, s->feq_mem_kind, feq_bytes, dfeq, &feq);
+  if (e == hipSuccess) e = alloc(dones, (size_t)E * sizeof(double));
+  if (e == hipSuccess) e = phase_fill_ones(h, dones, (size_t)E);
+  if (e == hipSuccess) e = alloc(dg, (size_t)E * nb2 * sizeof(double));
+  if (e == hipSuccess) e = alloc(dpart, (size_t)K * E * chunks * sizeof(double));
+  if (e == hipSuccess && host && d_x) e = alloc(ddx, pbytes);
+  if (e == hipSuccess && host && d_v) e = alloc(ddv, pbytes);
+  if (e == hipSuccess) e = device_input(h, static_cast<const double*>(d_x), mem_kind, pbytes, ddx, &tx);
+  if (e == hipSuccess) e = device_input(h, static_cast<const double*>(d_v), mem_kind, pbytes, ddv, &tv);
+  if (e == hipSuccess && host) e = alloc(dout, obytes);
+  double* out = device_output(d_kl, mem_kind, dout);
+  const double *x = (const double*)h->x.get(), *v = (const double*)h->v;
+  if (e == hipSuccess) e = phase_enqueue(h, s, x, v, acc, feq, dones, nullptr, nullptr, dg, a);
+  if (e == hipSuccess) {
+    PhaseJvpArgs j{};
+    j.dx = tx; j.dv = tv; j.dstride = (long long)((size_t)E * N); j.erow = (long long)N; j.part = dpart;
+    e = phase_jvp_enqueue(h, s, a, x, v, dg, j, K, out, (long long)E);
+  }
+  if (e == hipSuccess) e = device_result(h, d_kl, out, obytes);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) return fail(h, PIC_EHIP, std::string("pic_phase_kl_smooth_jvp: ") + hipGetErrorString(e));
+  return PIC_OK;
+}

@@ -1,7 +1,8 @@
 // host_tangent.h -- included by picstep.hip alone, inside its extern "C" block, behind host_tape.h (the replay is the walk's)
 #pragma once
 // ---------------------------------------------------------------------------------------------
-// Forward mode of the tape (include/picstep.h: pic_tape_tangent; kernels: pic_tangent.h)
+// Forward mode of the tape (include/picstep.h: pic_tape_tangent[_kl]; kernels: pic_tangent.h), and of its per-step
+// smoothed KL (kernels: pic_phase.h)
 // ---------------------------------------------------------------------------------------------
 // the parts of the tangent block for kc directions: state [kc][2][env][ld], dF [kc][env][Ng], acc [kc][env][Ng], ke [kc][env],
 // umax [3][kc][env] (everything from acc on is zero between uses)
@@ -35,6 +36,52 @@ static int tangent_reserve(pic_handle* h, int K, const std::string& w) {
   return PIC_OK;
 }
 
+// the parts of the block behind the KL's tangent: the unit cotangents [env] and the chunks' sums [kMaxTangents][env][chunks]
+struct TanKlViews {
+  double* ones = nullptr;
+  double* part = nullptr;
+};
+static size_t tangent_kl_parts(Carver c, const pic_handle* h, TanKlViews& v) {
+  const size_t E = h->cfg.num_envs;
+  c.take(v.ones, E);
+  c.take(v.part, (size_t)kMaxTangents * E * phase_jvp_chunks(h));
+  return c.at;
+}
+
+// that block, within budget_bytes (allocated once per tape); on failure the tape keeps what it had
+static int tangent_kl_reserve(pic_handle* h, const std::string& w) {
+  Tape& t = h->tape;
+  if (t.tkl_block) return PIC_OK;
+  TanKlViews v;
+  const size_t bytes = tangent_kl_parts(Carver{}, h, v);
+  if (t.budget > 0 && t.bytes + bytes > (size_t)t.budget)
+    return fail(h, PIC_ENOMEM, w + ": the working memory of the KL's tangent (" + std::to_string(bytes) +
+                                   " bytes) would take the tape past budget_bytes (pic_tape_start)");
+  DeviceBuf<void> b;
+  const int rc = regrow(h, b, bytes, (w + ": the working memory of the KL's tangent does not fit on the device").c_str());
+  if (rc) return rc;
+  tangent_kl_parts(Carver{static_cast<char*>(b.get())}, h, v);
+  HIPCHK(h, phase_fill_ones(h, v.ones, (size_t)h->cfg.num_envs));
+  t.tkl_block = std::move(b);
+  t.tkl_ones = v.ones; t.tkl_part = v.part;
+  t.bytes += bytes;
+  return PIC_OK;
+}
+
+// the KL's part of forward step s (kKlTangentLaunches kernels): the deposit and finish of the replayed state x, v the step left,
+// with unit cotangents, then d_kl[d][s][env] = <dKL~/d(x', v'), (dq_4, dp_3)> on the tangent state after pass 3
+constexpr int kKlTangentLaunches = 4;
+static int tangent_kl_step(pic_handle* h, const TanArgs& ta, const double* x, const double* v, double* out, long long out_dstride) {
+  Tape& t = h->tape;
+  PhaseArgs a;
+  HIPCHK(h, phase_enqueue(h, &t.kl_spec, x, v, t.kl_acc, t.kl_feq, t.tkl_ones, nullptr, nullptr, t.kl_g, a));
+  PhaseJvpArgs j{};
+  j.dx = ta.st; j.dv = ta.st + ta.vofs; j.dstride = ta.dstride; j.erow = h->ld; j.part = t.tkl_part;
+  HIPCHK(h, phase_jvp_enqueue(h, &t.kl_spec, a, x, v, t.kl_g, j, ta.K, out, out_dstride));
+  t.launches += kKlTangentLaunches;
+  return PIC_OK;
+}
+
 extern "C++" {
 // the kernels of a sub-stage for the direction count at hand (1, up to 4, up to 8: the per-direction values live in registers)
 template <int S>
@@ -52,12 +99,13 @@ static void tangent_pass(pic_handle* h, const AdjStep& st, const TanArgs& ta, co
 }
 }  // extern "C++"
 
-int pic_tape_tangent(pic_handle* h, int K, const double* d_ext, const double* d_actions, const void* d_x0, const void* d_v0,
-                     int mem_kind, double* d_hist, void* d_x, void* d_v, double* d_E_mesh) {
-  if (!h) return PIC_EINVAL;
+// pic_tape_tangent (d_kl = null: the KL, if any, is ignored) and pic_tape_tangent_kl
+static int tape_tangent(pic_handle* h, const char* who, int K, const double* d_ext, const double* d_actions, const void* d_x0,
+                        const void* d_v0, int mem_kind, double* d_hist, void* d_x, void* d_v, double* d_E_mesh, double* d_kl) {
   Tape& t = h->tape;
-  const std::string w("pic_tape_tangent");
+  const std::string w(who);
   if (int rc = check_tape_open(h, w.c_str())) return rc;
+  if (d_kl && !t.kl) return fail(h, PIC_ESTATE, w + ": d_kl needs a KL on the tape (pic_tape_kl_start before the first step)");
   if (K < 1 || K > kMaxTangents) return fail(h, PIC_EINVAL, w + ": need 1 <= K <= " + std::to_string(kMaxTangents));
   if (d_ext && d_actions) return fail(h, PIC_EINVAL, w + ": d_ext and d_actions are both given (at most one)");
   if (int rc = check_mem_kind(h, mem_kind, w.c_str())) return rc;
@@ -88,6 +136,7 @@ int pic_tape_tangent(pic_handle* h, int K, const double* d_ext, const double* d_
     return PIC_OK;
   }
   int rc = tangent_reserve(h, K, w);
+  if (!rc && d_kl) rc = tangent_kl_reserve(h, w);
   if (rc) return rc;
   TanArgs ta{};
   tangent_parts(Carver{static_cast<char*>(t.tan_block.get())}, h, t.tan_k, ta);
@@ -97,17 +146,20 @@ int pic_tape_tangent(pic_handle* h, int K, const double* d_ext, const double* d_
   // host memory: the control tangents and the mesh-sized outputs go through one device block of this call
   const size_t in_n = d_ext ? (size_t)K * T * mesh : d_actions ? (size_t)K * T * E * 2 * Mact : 0;
   const size_t hist_n = d_hist ? (size_t)K * T * 3 * E : 0, em_n = d_E_mesh ? (size_t)K * T * mesh : 0;
+  const size_t kl_n = d_kl ? (size_t)K * T * E : 0;
   const double* din = d_ext ? d_ext : d_actions;
   double* dhist = d_hist;
   double* dem = d_E_mesh;
+  double* dkl = d_kl;
   DeviceBuf<double> stage;
-  if (host && in_n + hist_n + em_n > 0) {
-    rc = regrow(h, stage, (in_n + hist_n + em_n) * sizeof(double), (w + ": the staging of host tangents does not fit on the device").c_str());
+  if (host && in_n + hist_n + em_n + kl_n > 0) {
+    rc = regrow(h, stage, (in_n + hist_n + em_n + kl_n) * sizeof(double), (w + ": the staging of host tangents does not fit on the device").c_str());
     if (rc) return rc;
     double* p = stage;
     HIPCHK(h, device_input(h, din, PIC_HOST, in_n * sizeof(double), p, &din));
     dhist = device_output(d_hist, PIC_HOST, p + in_n);
     dem = device_output(d_E_mesh, PIC_HOST, p + in_n + hist_n);
+    dkl = device_output(d_kl, PIC_HOST, p + in_n + hist_n + em_n);
   }
   // (dx_0, dv_0) of every direction into the state rows (padded to ld)
   for (int d = 0; d < K; ++d) {
@@ -155,6 +207,11 @@ int pic_tape_tangent(pic_handle* h, int K, const double* d_ext, const double* d_
       tangent_deposit<3>(h, st, ta, a, dgrid, dlds, kd);
       hipLaunchKernelGGL(tangent_mesh_kernel<3>, mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, ta, m, a);
       tangent_pass<3>(h, st, ta, a, g.pgrid);
+      if (dkl) {                        // the state is (dq_4, dp_3) = (dx', dv'): the tangent of the KL~ of the state step s left
+        const double* xn = t.seg + (size_t)(i + 1) * 2 * part;
+        rc = tangent_kl_step(h, ta, xn, xn + part, dkl + (size_t)s * E, (long long)(T * E));
+        if (rc) return rc;
+      }
       tangent_deposit<4>(h, st, ta, a, dgrid, dlds, kd);
       hipLaunchKernelGGL(tangent_mesh_kernel<4>, mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, ta, m, a);
       t.launches += 11;
@@ -163,6 +220,7 @@ int pic_tape_tangent(pic_handle* h, int K, const double* d_ext, const double* d_
   }
   HIPCHK(h, device_result(h, d_hist, dhist, hist_n * sizeof(double)));
   HIPCHK(h, device_result(h, d_E_mesh, dem, em_n * sizeof(double)));
+  HIPCHK(h, device_result(h, d_kl, dkl, kl_n * sizeof(double)));
   // (dx', dv') of every direction out of the state rows
   for (int d = 0; d < K && !rc; ++d) {
     void* outs[2] = {d_x, d_v};
@@ -170,4 +228,16 @@ int pic_tape_tangent(pic_handle* h, int K, const double* d_ext, const double* d_
       if (outs[k]) rc = download(h, static_cast<double*>(outs[k]) + (size_t)d * E * N, ta.st + (size_t)d * 2 * part + (size_t)k * part, mem_kind);
   }
   return rc ? rc : walk_finish(h, w, mem_kind);
+}
+
+int pic_tape_tangent(pic_handle* h, int K, const double* d_ext, const double* d_actions, const void* d_x0, const void* d_v0,
+                     int mem_kind, double* d_hist, void* d_x, void* d_v, double* d_E_mesh) {
+  if (!h) return PIC_EINVAL;
+  return tape_tangent(h, "pic_tape_tangent", K, d_ext, d_actions, d_x0, d_v0, mem_kind, d_hist, d_x, d_v, d_E_mesh, nullptr);
+}
+
+int pic_tape_tangent_kl(pic_handle* h, int K, const double* d_ext, const double* d_actions, const void* d_x0, const void* d_v0,
+                        int mem_kind, double* d_hist, void* d_x, void* d_v, double* d_E_mesh, double* d_kl) {
+  if (!h) return PIC_EINVAL;
+  return tape_tangent(h, "pic_tape_tangent_kl", K, d_ext, d_actions, d_x0, d_v0, mem_kind, d_hist, d_x, d_v, d_E_mesh, d_kl);
 }

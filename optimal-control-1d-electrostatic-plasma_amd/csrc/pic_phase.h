@@ -1,7 +1,8 @@
 // pic_phase.h -- the smoothed phase-space density and its KL cost (include/picstep.h: pic_phase_kl_smooth*):
 // an integer CIC deposit of every environment's particles on an nx x nv grid over [0, L] x [vmin, vmax], a per-environment
 // finishing kernel (density, KL against a target, the cotangent grid of the KL) and the gather of that grid back to the particles
-// (into dense rows, or added to the adjoint state of a tape: DESIGN.md 7h).
+// (into dense rows, or added to the adjoint state of a tape: DESIGN.md 7h; or dotted with tangents of the particles, the forward
+// mode: DESIGN.md 7j).
 // Float64 particles only.  Off the step path: the kernels read the state a step left.
 #pragma once
 #include "pic_device.h"
@@ -216,6 +217,95 @@ __global__ __launch_bounds__(BLOCK) void phase_vjp_add_kernel(const double* __re
     lx[row + i] = lx[row + i] + dx;
     lv[row + i] = lv[row + i] + dv;
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Forward mode (pic_phase_kl_smooth_jvp, pic_tape_tangent_kl): dKL~ = sum_k dKL~/dx_k dx_k + dKL~/dv_k dv_k per
+// environment and direction, with phase_gather's dKL~/d(x, v) against the grid g the finishing kernel wrote for unit cotangents.
+// ---------------------------------------------------------------------------------------------
+constexpr int kJvpTilesPerLane = 8;                          // tiles a lane sums: a chunk is BLOCK * 8 tiles = 8192 particles,
+constexpr long long kJvpChunkTiles = (long long)BLOCK * kJvpTilesPerLane;   // whatever the grid, the batch or the schedule
+
+// a direction's tile: rows of the dense [K][env][N] layout start on 8 bytes only (N odd)
+typedef double pic_v2d_a8 __attribute__((ext_vector_type(2), aligned(8)));
+
+struct PhaseJvpArgs {
+  const double* dx;       // direction 0, environment 0 of the x tangents, or null (0)
+  const double* dv;       // the same of the v tangents
+  long long dstride;      // elements from one direction to the next
+  long long erow;         // elements from one environment's row to the next (ld of the tangent state, N of dense rows)
+  double* part;           // [K][env][chunks] the chunks' sums
+  int K, num_envs, chunks;
+};
+
+// Chunk c of an environment: tiles [c, c + 1) kJvpChunkTiles of its particles x, v [env][ld].  A lane sums its tiles c0 + lane,
+// c0 + lane + BLOCK, ... in that order (within a tile particle 0, then particle 1; the odd last particle of a row alone, so the
+// padding is never read), block_sum adds the lanes, and part[d][env][c] receives direction d's sum: one value per chunk that
+// depends on the particles and the tangents alone.  phase_gather runs once per particle and serves all KD >= K directions.
+// Grid: (chunks, environments).
+template <int KD>
+__global__ __launch_bounds__(BLOCK) void phase_jvp_kernel(const double* __restrict__ x, const double* __restrict__ v,
+                                                          const double* __restrict__ g, PhaseArgs a, double cx, double cv,
+                                                          PhaseJvpArgs j) {
+  __shared__ double ws[WAVES];
+  const int env = blockIdx.y;
+  const size_t row = (size_t)env * a.ld;
+  const size_t drow = (size_t)env * j.erow;
+  const double* gr = g + (size_t)env * a.nx * a.nv;
+  const long long ntiles = (a.N + 1) / 2;
+  const long long c0 = (long long)blockIdx.x * kJvpChunkTiles;
+  double s[KD];
+#pragma unroll
+  for (int d = 0; d < KD; ++d) s[d] = 0.0;
+#pragma unroll 2
+  for (int q = 0; q < kJvpTilesPerLane; ++q) {
+    const long long t = c0 + (long long)q * BLOCK + threadIdx.x;
+    if (t >= ntiles) break;
+    const long long i = 2 * t;
+    if (i + 1 < a.N) {
+      const pic_v2d xt = stream_load(reinterpret_cast<const pic_v2d*>(x + row) + t);
+      const pic_v2d vt = stream_load(reinterpret_cast<const pic_v2d*>(v + row) + t);
+      double gx[2], gv[2];
+      phase_gather(xt[0], vt[0], gr, a, cx, cv, gx[0], gv[0]);
+      phase_gather(xt[1], vt[1], gr, a, cx, cv, gx[1], gv[1]);
+#pragma unroll
+      for (int d = 0; d < KD; ++d) {
+        if (d >= j.K) break;
+        const size_t o = (size_t)d * j.dstride + drow + i;
+        pic_v2d_a8 dxt = {0.0, 0.0}, dvt = {0.0, 0.0};
+        if (j.dx) dxt = stream_load(reinterpret_cast<const pic_v2d_a8*>(j.dx + o));
+        if (j.dv) dvt = stream_load(reinterpret_cast<const pic_v2d_a8*>(j.dv + o));
+        s[d] = s[d] + (gx[0] * dxt[0] + gv[0] * dvt[0]);
+        s[d] = s[d] + (gx[1] * dxt[1] + gv[1] * dvt[1]);
+      }
+    } else {
+      double gx, gv;
+      phase_gather(x[row + i], v[row + i], gr, a, cx, cv, gx, gv);
+#pragma unroll
+      for (int d = 0; d < KD; ++d) {
+        if (d >= j.K) break;
+        const size_t o = (size_t)d * j.dstride + drow + i;
+        const double dx = j.dx ? j.dx[o] : 0.0, dv = j.dv ? j.dv[o] : 0.0;
+        s[d] = s[d] + (gx * dx + gv * dv);
+      }
+    }
+  }
+#pragma unroll
+  for (int d = 0; d < KD; ++d) {
+    if (d >= j.K) break;
+    const double S = block_sum<WAVES>(s[d], ws);
+    if (threadIdx.x == 0) j.part[((size_t)d * j.num_envs + env) * j.chunks + blockIdx.x] = S;
+  }
+}
+
+// One single-lane workgroup per (environment, direction): the chunks' sums in ascending order into out[d * out_dstride + env].
+__global__ __launch_bounds__(1) void phase_jvp_finish_kernel(const double* __restrict__ part, int chunks, int num_envs,
+                                                             double* __restrict__ out, long long out_dstride) {
+  const int env = blockIdx.x, d = blockIdx.y;
+  const double* p = part + ((size_t)d * num_envs + env) * chunks;
+  double s = 0.0;
+  for (int c = 0; c < chunks; ++c) s += p[c];
+  out[(size_t)d * out_dstride + env] = s;
 }
 
 }  // namespace

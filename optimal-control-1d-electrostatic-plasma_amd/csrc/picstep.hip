@@ -215,6 +215,11 @@ struct Tape {
   double* kl_trace = nullptr;         // [max_steps][env] KL~ after every step
   double* kl_cot = nullptr;           // [max_steps][env] cotangents on it (pic_tape_kl_cot)
   std::vector<char> kl_flag;          // [max_steps] per step: kl_cot holds a row for it
+  // forward mode of that KL (pic_tape_tangent_kl): one block allocated by the first call that asks for d_kl,
+  // counts in `bytes`; tkl_ones and tkl_part are views into it
+  DeviceBuf<void> tkl_block;
+  double* tkl_ones = nullptr;         // [env] unit cotangents: the finishing kernel's g is then dKL~/df
+  double* tkl_part = nullptr;         // [kMaxTangents][env][chunks] the chunks' sums of the step at hand
 };
 
 struct pic_handle {

@@ -355,6 +355,26 @@ class BatchedPIC:
         self._h.phase_kl_smooth_vjp(nx, nv, vmin, vmax, fa, per, mem.kind, mem.addr(d), mem.kind, mem.addr(gx), mem.addr(gv))
         return gx, gv
 
+    def kl_smooth_jvp(self, feq, vmin: float = -25.0, vmax: float = 25.0, d_x=None, d_v=None):
+        """Directional derivatives of KL~ along tangents d_x, d_v [num_envs, N] of the current particles (each None = 0) ->
+        [num_envs]: sum_i dKL~/dx_i d_x_i + dKL~/dv_i d_v_i with kl_smooth_grad's derivative (pic_phase_kl_smooth_jvp,
+        DESIGN.md 7j).  With a leading axis of K <= 8 directions on the inputs the result is [K, num_envs].  Bitwise
+        reproducible.  NumPy, or a float64 CUDA tensor if feq or a tangent is one."""
+        E, N = self.num_envs, self.N
+        given = [a for a in (d_x, d_v) if a is not None]
+        ks = {int(a.shape[0]) for a in given if len(a.shape) == 3}
+        if len(ks) > 1:
+            raise ValueError(f"kl_smooth_jvp: the inputs disagree on the number of directions: {sorted(ks)}")
+        batched = bool(ks)
+        K = ks.pop() if ks else 1
+        for a in given:
+            if tuple(a.shape) != ((K,) if batched else ()) + (E, N):
+                raise ValueError(f"kl_smooth_jvp: a tangent must have shape {((K,) if batched else ()) + (E, N)}, not {tuple(a.shape)}")
+        mem, (nx, nv, fa, per), (_f, tx, tv) = self._phase_call(feq, d_x, d_v)
+        out = mem.empty((K, E))
+        self._h.phase_kl_smooth_jvp(nx, nv, vmin, vmax, fa, per, mem.kind, K, mem.addr(tx), mem.addr(tv), mem.kind, mem.addr(out))
+        return out if batched else out[0]
+
     # -- rollout recorder (include/picstep.h: pic_record_*) ----------------------------------------
     def start_recording(self, stride: int = 1, modes: Optional[int] = None, x_bins: int = 0, v_bins: int = 0, phase_bins=None,
                         vmin: float = -25.0, vmax: float = 25.0, feq=None, capacity: int = 4096, phase_dx: float = 0.0,
@@ -559,14 +579,18 @@ class BatchedPIC:
             res["gain"] = g[0] if len(g) == 1 else g
         return res
 
-    def tangent(self, d_ext=None, d_actions=None, d_x0=None, d_v0=None, fields: bool = False):
+    def tangent(self, d_ext=None, d_actions=None, d_x0=None, d_v0=None, fields: bool = False, kl: bool = False):
         """Jacobian-vector product of the taped steps (pic_tape_tangent): tangents d_ext [T, num_envs, N_mesh] of
         every step's external field, or d_actions [T, num_envs, 2*max_mode] of its actions (at most one), and d_x0, d_v0
         [num_envs, N] of the tape's starting particles (each None = 0).  Every input may carry a leading axis of K <= 8
         directions, computed in one call; without one K = 1 and the outputs have no K axis either.  Returns a dict: "KE", "PE",
         "PE_reward" [K, T, num_envs], "x", "v" [K, num_envs, N] (final particles) and, with fields, "E_mesh" [K, T, num_envs,
-        N_mesh] (every step's post-step field).  NumPy arrays, or float64 CUDA tensors if any input is one (then stream-ordered like
+        N_mesh] (every step's post-step field).  With kl, on a tape opened with kl=..., "KL" [K, T, num_envs] follows: the
+        tangents of the trace `tape_kl` returns (pic_tape_tangent_kl; four more kernels per step); every other key
+        keeps its bits.  NumPy arrays, or float64 CUDA tensors if any input is one (then stream-ordered like
         backward).  Raises PicError if the replay of the taped steps does not reproduce the forward bit for bit."""
+        if kl and not self._tape_kl:
+            raise _abi.PicError("tangent: kl=True needs a KL on the tape (start_tape(..., kl=...))")
         T = self._h.tape_stats()["steps"]
         E, N, Ng = self.num_envs, self.N, self.N_mesh
         n = 2 * self.max_mode
@@ -585,15 +609,18 @@ class BatchedPIC:
         ins = {k: mem.f64(a, (K,) + base[k]) for k, a in given.items()}
         hist, x, v = mem.out((K, T, 3, E)), mem.out((K, E, N)), mem.out((K, E, N))
         em = mem.out((K, T, E, Ng)) if fields else None
+        dkl = mem.out((K, T, E)) if kl else None
         addr = mem.addr
         mem.enter()
         self._h._tape_tangent(mem.kind, K, addr(ins.get("d_ext")), addr(ins.get("d_actions")), addr(ins.get("d_x0")),
-                              addr(ins.get("d_v0")), addr(hist), addr(x), addr(v), addr(em))
+                              addr(ins.get("d_v0")), addr(hist), addr(x), addr(v), addr(em), kl=addr(dkl) if kl else None)
         if mem.on_device:
             self._check_replay("tangent", "tangent")
         res = {"KE": hist[:, :, 0], "PE": hist[:, :, 1], "PE_reward": hist[:, :, 2], "x": x, "v": v}
         if fields:
             res["E_mesh"] = em
+        if kl:
+            res["KL"] = dkl
         return res if batched else {k: a[0] for k, a in res.items()}
 
     def walk(self, obs_modes: Optional[int] = None, on_device: bool = False):

@@ -18,7 +18,8 @@ Every entry takes kl=dict(feq=..., vmin=..., vmax=...) (BatchedPIC.start_tape): 
     KE, PE, PE_reward, KL = rollout(env, actions, kl=dict(feq=feq, vmin=-6.0, vmax=6.0))
     (KL.sum() + PE_reward.sum()).backward()
 
-Forward mode of the KL is not built: its tangent is returned as zero.
+In forward mode the KL output of rollout and rollout_ext carries its tangent like the energy traces (pic_tape_tangent_kl,
+DESIGN.md 7j), so a directional derivative of the whole cost is one dual_level pass.
 
 Each call opens a fresh tape on `env` (an open one is stopped first) and leaves it open for the backward; stop it with
 `env.stop_tape()` before a reset.  A backward after the environment has moved on (a further step, another rollout, a reset)
@@ -68,16 +69,15 @@ class _Rollout(torch.autograd.Function):
     @staticmethod
     def jvp(ctx, u_t, env_t, kind_t, ce_t, kl_t=None):
         """Forward mode (torch.autograd.forward_ad): the tangent of the energy traces along u_t, from pic_tape_tangent on the
-        tape this rollout opened.  The KL output of a rollout with kl=... gets a ZERO tangent: forward mode of
-        the KL is not built, so do not read a directional derivative of the KL from it."""
+        tape this rollout opened, and of the KL trace of a rollout with kl=... from pic_tape_tangent_kl (7j)."""
         env = ctx.env
         _check_live(env, ctx.serial, ctx.steps, "jvp")
         zero = lambda: torch.zeros((ctx.steps, env.num_envs), dtype=torch.float64, device=ctx.device)  # noqa: E731
         if u_t is None:
             return tuple(zero() for _ in range(4 if ctx.kl else 3))
-        out = env.tangent(**{"d_actions" if ctx.kind == "actions" else "d_ext": u_t.detach()})
-        res = tuple(torch.as_tensor(out[k], dtype=torch.float64, device=ctx.device) for k in ("KE", "PE", "PE_reward"))
-        return res + ((zero(),) if ctx.kl else ())
+        out = env.tangent(kl=ctx.kl, **{"d_actions" if ctx.kind == "actions" else "d_ext": u_t.detach()})
+        keys = ("KE", "PE", "PE_reward") + (("KL",) if ctx.kl else ())
+        return tuple(torch.as_tensor(out[k], dtype=torch.float64, device=ctx.device) for k in keys)
 
 
 def rollout(env, actions, checkpoint_every=0, kl=None):
