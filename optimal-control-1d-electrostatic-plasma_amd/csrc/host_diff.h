@@ -20,31 +20,6 @@ struct Carver {
   }
 };
 
-// the kind of a copy to or from the caller's memory: `host_kind` for PIC_HOST, else device to device
-inline hipMemcpyKind copy_kind(int mem_kind, hipMemcpyKind host_kind) {
-  return mem_kind == PIC_HOST ? host_kind : hipMemcpyDeviceToDevice;
-}
-
-// rows of device memory from the caller's src in mem_kind's memory, or zeros for a null src
-inline hipError_t device_fill(pic_handle* h, double* dst, const double* src, size_t bytes, int mem_kind) {
-  return src ? hipMemcpyAsync(dst, src, bytes, copy_kind(mem_kind, hipMemcpyHostToDevice), h->stream) : hipMemsetAsync(dst, 0, bytes, h->stream);
-}
-
-// An input in device memory: src itself when it is device memory (or null), else its copy in `buf`, the caller's device memory
-inline hipError_t device_input(pic_handle* h, const double* src, int kind, size_t bytes, double* buf, const double** out) {
-  *out = src;
-  if (!src || kind == PIC_DEVICE) return hipSuccess;
-  *out = buf;
-  return hipMemcpyAsync(buf, src, bytes, hipMemcpyHostToDevice, h->stream);
-}
-
-// Device memory for an output: dst itself when it is device memory (or null), else `buf`; device_result copies it to dst behind
-// the kernels that wrote it
-inline double* device_output(void* dst, int kind, double* buf) { return dst && kind == PIC_HOST ? buf : static_cast<double*>(dst); }
-inline hipError_t device_result(pic_handle* h, void* dst, const double* dev, size_t bytes) {
-  return dst && dev != dst ? hipMemcpyAsync(dst, dev, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
-}
-
 // argument checks of the pic_tape_* entries
 inline int check_mem_kind(pic_handle* h, int mem_kind, const char* who) {
   return mem_kind == PIC_HOST || mem_kind == PIC_DEVICE ? PIC_OK : fail(h, PIC_EINVAL, std::string(who) + ": bad mem_kind");

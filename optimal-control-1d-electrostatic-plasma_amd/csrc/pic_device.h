@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "picstep.h"
+#include "pic_limits.h"
 
 namespace {
 
@@ -21,7 +22,6 @@ namespace {
 #define PIC_STAMP_LOADS(slot) ((void)0)
 #endif
 
-constexpr int kMaxFeedbackModes = 16;
 constexpr int kInlineDoubles = 32;                 // doubles a call's actuator coefficients may number to travel inside the argument block
 struct InlineDoubles { double v[kInlineDoubles]; };   // modes of the on-device feedback law (pic_step_feedback)
 
@@ -76,9 +76,6 @@ __device__ __forceinline__ void kernarg_warm() {
   asm volatile("" ::"s"(w));                         // the loads are waited for HERE (one wait for all of them), not sunk to a later block
 #endif
 }
-
-constexpr int BLOCK = 512;          // sweep workgroup: 8 waves of 64 (512 beat 256 by 2.7 % and 128 by 11 % at config 2)
-constexpr int WAVES = BLOCK / 64;
 
 enum Stage : int {
   ST_A = 0,        // drift(c) from x,v ; deposit ; nothing stored

@@ -18,8 +18,6 @@
 
 namespace {
 
-constexpr size_t kResidentStaticLds = (4 * 8 + 4 + 2 * kMaxFeedbackModes) * sizeof(double);   // resident_kernel's static __shared__ arrays (NW = 8)
-
 // The kernel's argument block, in groups that are read from the kernel-argument segment WHERE THEY ARE USED (pic_device.h:
 // kernarg_at).  Passed by value and left to the compiler the whole block is loaded into scalar registers at entry and held to
 // its last use -- through every particle phase: the first cut of round 3 paid 400 more v_readlane per step than round 2 and

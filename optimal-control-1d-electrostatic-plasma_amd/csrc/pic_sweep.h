@@ -212,8 +212,6 @@ __device__ __forceinline__ void flush_mesh(const A* __restrict__ acc_all, int R,
   }
 }
 
-constexpr size_t kSweepStaticLds = (2 * WAVES + 2) * sizeof(double);     // sweep_kernel's static __shared__ arrays
-
 // what a sweep reads its field from, where its deposits go, which retired accumulator rows it clears
 struct SweepIO {
   // accumulator rows are [S][env][Ng] (S sub-rows, SweepArgs::S; pic_device.h: acc_row_sum)

@@ -31,9 +31,11 @@
 // a step is bitwise reproducible and does not depend on the launch geometry.  Accumulator rows rotate through a
 // small ring; a row whose readers are done is cleared by a later sweep (no memset launches).
 //
-// Files: pic_device.h (particle formats, per-particle helpers, scans), pic_sweep.h (push sweeps), pic_solve.h
-// (field solve), pic_aux.h (kernels off the step path); this file holds the handle, the launch schedule and
-// the C ABI, but for the host side of the differentiable rollouts: host_diff.h, host_phase.h, host_tape.h, host_tangent.h.
+// Files: pic_limits.h (launch constants), pic_device.h (particle formats, per-particle helpers, scans), pic_sweep.h (push sweeps),
+// pic_solve.h (field solve), pic_aux.h (kernels off the step path); host_plan.h (pic_create's argument checks and the launch plan:
+// no HIP, pinned on a CPU by tests/test_plan_cpu.py), host_place.h (the search for a placement of x and v); this file holds the
+// handle, the launch schedule and the C ABI, but for the host side of the differentiable rollouts: host_diff.h, host_phase.h,
+// host_tape.h, host_tangent.h.
 
 #include <hip/hip_runtime.h>
 
@@ -45,6 +47,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -54,6 +57,8 @@
 #include <vector>
 
 #include "picstep.h"
+
+#include "host_plan.h"
 
 #include "pic_device.h"
 #include "pic_sweep.h"
@@ -69,7 +74,8 @@
 // ---------------------------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------------------------
-enum Format : int { FMT_F64 = 0, FMT_F32 = 1, FMT_U32 = 2 };     // PosF64 / PosF32 / PosU32
+namespace {
+
 typedef pic_placement PlacementStats;
 struct PlacementState {
   size_t pbytes = 0;                  // size of x and of v (0: no search on this handle)
@@ -222,37 +228,16 @@ struct Tape {
   double* tkl_part = nullptr;         // [kMaxTangents][env][chunks] the chunks' sums of the step at hand
 };
 
-struct pic_handle {
+}  // namespace
+
+struct __attribute__((visibility("hidden"))) pic_handle : LaunchPlan {      // the plan: pic_create, once
   pic_config cfg{};
-  int fmt = FMT_F64;
-  int acc_kind = PIC_ACC_FIX64;  // resolved accumulator (never PIC_ACC_AUTO)
-  int vec = 2;
-  size_t esz = 8;          // particle element size (positions and velocities have the same width in every format)
-  long long ld = 0;
-  long long chunk = 0;
-  int nblk = 0;
-  int R = 1;
-  int fg = 42;             // fractional bits of the fixed-point accumulators
-  int S = 1;               // sub-rows per accumulator row (pic_device.h: acc_row_sum)
-  double magic = 0;
-  size_t sweep_lds = 0, solve_lds = 0;
-  // resident schedule (pic_resident.h): one workgroup of res_nw waves holds an environment, res_ppt particles per lane
-  bool resident = false;
-  int res_ppt = 0, res_nw = 0, res_R = 1;
-  bool res_lean = false;          // resident kernel without carried cell / weights (two workgroups per CU)
-  size_t res_lds = 0;
-  double dx = 0, scale = 0;
-  double cs[4]{}, ds[4]{};
   int scheme = PIC_YOSHIDA4;          // time integrator of the steps (pic_set_integrator)
   hipStream_t stream = nullptr;       // the stream every call works on (own_stream, or the caller's)
   StreamOwner own_stream;             // created by pic_create (declared ahead of the buffers: destroyed after them)
-  bool v_separate = false;            // v is an allocation of its own (large states: alloc_particles)
   int post_slot = -1;                 // ring row whose post-step solve rides with the next sweep C (inside pic_step only)
   bool refresh_pending = false;       // the last sweep was a D2 (inside pic_step only): the next sweep B deposits the positions it reads
-  bool light_inner_steps = false;     // inner steps of a call end with sweep D2 (pic_create: particle states of 256 MB and more)
   bool readonly_c = false;            // whole steps run sweeps C_RO and D_RC / D2_RC (pic_set_readonly_c, or readonly_auto)
-  bool readonly_auto = false;         // pic_create's choice
-  size_t sweep_lds_rc = 0;            // LDS of sweeps D_RC / D2_RC: sweep_lds and sweep C's field tile; 0 = does not fit
   double* hist_row = nullptr;         // where the NEXT post-step solve also records its three energies (step_recording), or null
   double* post_hist_row = nullptr;    // the same for the solve that post_slot stands for
   PlacementStats place{};             // what the search for an (x, v) placement did, all legs together (pic_placement_stats)
@@ -355,17 +340,6 @@ void with_format(const pic_handle* h, F&& f) {
 // force evaluations per step of an integrator (pic_get_integrator, pic_step_stage)
 int evals_per_step(int scheme) { return scheme == PIC_YOSHIDA4 ? 3 : (scheme == PIC_VERLET ? 2 : 1); }
 
-void yoshida_coefficients(double (&c)[4], double (&d)[4]) {
-  // integration.py:62-69, same expressions in the same order
-  const double cbrt2 = std::pow(2.0, 1.0 / 3.0);
-  const double w0 = (-1) * cbrt2 / (2 - cbrt2);
-  const double w1 = 1 / (2 - cbrt2);
-  c[0] = c[3] = 0.5 * w1;
-  c[1] = c[2] = 0.5 * (w0 + w1);
-  d[0] = 0.0;
-  d[1] = d[3] = w1;
-  d[2] = w0;
-}
 
 // ---- accumulator ring -------------------------------------------------------------------------
 size_t row_elems(const pic_handle* h) { return (size_t)h->S * h->cfg.num_envs * h->cfg.Ng; }       // one accumulator row: [S][env][Ng]
@@ -721,11 +695,55 @@ int ensure_stage(pic_handle* h) {
   return PIC_OK;
 }
 
+// ---- staging between the caller's memory and the device ------------------------------------------------------------------------
+// the kind of a copy to or from the caller's memory: `host_kind` for PIC_HOST, else device to device
+inline hipMemcpyKind copy_kind(int mem_kind, hipMemcpyKind host_kind) {
+  return mem_kind == PIC_HOST ? host_kind : hipMemcpyDeviceToDevice;
+}
+
+// rows of device memory from the caller's src in mem_kind's memory, or zeros for a null src
+inline hipError_t device_fill(pic_handle* h, double* dst, const double* src, size_t bytes, int mem_kind) {
+  return src ? hipMemcpyAsync(dst, src, bytes, copy_kind(mem_kind, hipMemcpyHostToDevice), h->stream) : hipMemsetAsync(dst, 0, bytes, h->stream);
+}
+
+// An input in device memory: src itself when it is device memory (or null), else its copy in `buf`, the caller's device memory
+inline hipError_t device_input(pic_handle* h, const double* src, int kind, size_t bytes, double* buf, const double** out) {
+  *out = src;
+  if (!src || kind != PIC_HOST) return hipSuccess;
+  *out = buf;
+  return hipMemcpyAsync(buf, src, bytes, hipMemcpyHostToDevice, h->stream);
+}
+
+// Device memory for an output: dst itself when it is device memory (or null), else `buf`; device_result copies it to dst behind
+// the kernels that wrote it
+inline double* device_output(void* dst, int kind, double* buf) { return dst && kind == PIC_HOST ? buf : static_cast<double*>(dst); }
+inline hipError_t device_result(pic_handle* h, void* dst, const double* dev, size_t bytes) {
+  return dst && dev != dst ? hipMemcpyAsync(dst, dev, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
+}
+
+// the read-backs (dst <- src) of `bytes` each that the caller asked for (dst not null), enqueued in their order
+struct Readback { void* dst; const void* src; };
+inline hipError_t read_back(pic_handle* h, size_t bytes, std::initializer_list<Readback> copies) {
+  for (const Readback& c : copies) {
+    if (!c.dst) continue;
+    if (hipError_t e = hipMemcpyAsync(c.dst, c.src, bytes, hipMemcpyDeviceToHost, h->stream)) return e;
+  }
+  return hipSuccess;
+}
+
+// KE | PE | PE_reward out of the pinned staging, behind the wait for the copy or kernel that filled it
+void unpack_scalars(const pic_handle* h, double* KE, double* PE, double* PE_reward) {
+  const size_t E = (size_t)h->cfg.num_envs, b = E * sizeof(double);
+  if (KE) std::memcpy(KE, h->h_scal, b);
+  if (PE) std::memcpy(PE, h->h_scal + E, b);
+  if (PE_reward) std::memcpy(PE_reward, h->h_scal + 2 * E, b);
+}
+
 // copy a dense [env][N] caller array of velocities (or float positions) into a padded [env][ld] device array
 int upload(pic_handle* h, void* dst_padded, const void* src, int mem_kind) {
   const size_t row = (size_t)h->cfg.N * h->esz;
   HIPCHK(h, hipMemcpy2DAsync(dst_padded, (size_t)h->ld * h->esz, src, row, row, h->cfg.num_envs,
-                             mem_kind == PIC_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->stream));
+                             copy_kind(mem_kind, hipMemcpyHostToDevice), h->stream));
   return PIC_OK;
 }
 
@@ -748,7 +766,7 @@ int upload_positions(pic_handle* h, void* dst_padded, const void* src, int mem_k
 int download(pic_handle* h, void* dst, const void* src_padded, int mem_kind) {
   const size_t row = (size_t)h->cfg.N * h->esz;
   HIPCHK(h, hipMemcpy2DAsync(dst, row, src_padded, (size_t)h->ld * h->esz, row, h->cfg.num_envs,
-                             mem_kind == PIC_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
+                             copy_kind(mem_kind, hipMemcpyDeviceToHost), h->stream));
   return PIC_OK;
 }
 
@@ -798,6 +816,7 @@ void launch_shape_query(pic_handle* h, const void* x, int nenv, int shape, long 
 }
 
 #include "host_diff.h"
+#include "host_place.h"
 
 }  // namespace
 
@@ -807,322 +826,12 @@ int pic_abi_version(void) { return PICSTEP_ABI_VERSION; }
 
 const char* pic_last_error(pic_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
-// Where x and v land in HBM decides how fast they stream together.  On an unfragmented MI355X the 288 GiB behave as nine regions
-// of 32 GiB: a kernel that streams two arrays lying in the SAME region runs at 5.25 TB/s, with the arrays in two DIFFERENT
-// regions at 6.05 TB/s, whichever regions and whatever the access pattern (profiles/window_probe.hip: one 120 GiB block, x fixed,
-// v moved through it; profiles/experiments_r2.md 15).  A fresh device hands out neighbouring memory, so x and v of a default
-// allocation share a region almost always; on a device whose memory has been through other processes a block is a mixture of
-// pages from several regions (profiles/touch_probe.hip, experiments_r4.md 1: the class of a 64 MB window follows the window of x
-// it is paired with, not the candidate), which is why the search times WHOLE blocks, never windows of them.
-// For particle states that live in HBM (>= 256 MB) x and v are therefore two allocations: x first, then blocks of the same
-// size one after the other (they are laid down in sequence), and every 3 GiB the pair (x, newest block) is timed with a streaming
-// pass.  The search is a policy on RATIOS, not on this part's numbers: it ends sixteen readings after the best pair seen streams
-// >= 10 % faster than the slowest one seen (the kinds have been told apart and we hold a fast one; the best of all is kept), after
-// 42 GiB walked without an improvement (more than a region, all pairs alike: nothing to gain on this device), or when a third of
-// the free memory is held; everything but x and v is freed before the call returns.
-// pic_config.placement = PIC_PLACE_OFF skips it (x | v in one block).  Smaller states keep x | v in one block too (they sit in
-// the Infinity Cache, and the one-copy read-back of pic_get_particles wants them adjacent).
-//
-// Where the time goes, and why the search comes in LEGS of at most 100 ms (round 4, profiles/experiments_r4.md 1).
-// * Nothing is paid for the first touch of a block (touch_probe: first pass 330 us, later ones 347): a candidate is not cleared
-//   here, a reading is one timed pass behind one untimed pass.
-// * What costs is hipMalloc of memory the device hands out for the first time since it came up: the driver clears it, 1.3 ms per
-//   512 MB block with the GPU otherwise idle and 3-6 ms under a streaming kernel (released memory is wiped in the background and
-//   comes back in 20-70 us; a hipMalloc right behind the exit of a process that held tens of gigabytes can also sit and wait for
-//   that wipe, 0.6-1.5 s seen -- nothing a caller of hipMalloc can bound).  A first create on such a device has x at the very start
-//   of a region, 31 GiB -- 80 to 200 ms of allocations -- from the first block that pairs well with it.  No budget that a
-//   constructor may take covers that.  But what one
-//   leg has cleared and given back stays clean, so the NEXT leg walks through it in microseconds per block and spends its 100 ms
-//   beyond: pic_create runs the first leg, and while it ends for lack of time pic_reset / pic_reset_sampled -- which replace the
-//   particles anyway, so that moving v costs nothing -- run further ones (at most kMaxLegs, and only as long as pic_device_ptrs has
-//   not handed the addresses to anybody).
-// * The blocks are allocated by a thread of the call's own while the calling thread times; over never-used memory (slow mallocs) the
-//   two take turns instead, because the clear and the timed stream slow each other down.
-// * A device that has rested >= 3 ms runs its next 10-20 ms 4-13 % slow (early_steps3.py), and readings taken at different points
-//   of that ramp show a "10 % faster" pair of the SAME kind.  Every reading is therefore a RATIO: the time of (x, candidate) over
-//   the time of (x, the leg's first block) taken in the same breath (again whenever the stream has rested since), behind a filler.
-struct BlockFeed {                                  // candidate blocks, allocated by a thread of their own (placement_leg)
-  std::mutex m;
-  std::condition_variable cv;
-  std::vector<void*> blocks;                        // in allocation order; only ever grown by the feeder
-  size_t taken = 0;                                 // blocks.size() when the timing thread last took one
-  size_t lead = 1;                                  // the feeder stays at most this many blocks ahead of `taken`
-  bool stop = false, done = false;
-  bool timing = false;                              // a reading is being taken
-  bool slow = false;                                // the last hipMalloc was of never-used memory (being cleared): take turns with the readings
-  double malloc_seconds = 0.0;
-};
-
-constexpr int kMaxLegs = 4;
-
-// One leg of the search.  On entry h->x is allocated; h->v is the block kept so far, or null (first leg).
-void placement_leg(pic_handle* h, size_t pbytes) {
-  // Everything the search allocates has to be given back, and the driver wipes released memory before it hands it out again
-  // (asynchronously; whatever allocates next on the device may wait for that): an untouched 32 GiB spacer that carried the search out
-  // of x's own region at once made the next pic_create of a create / destroy loop take 0.4-3 s (experiments_r3.md 18).  Blocks of
-  // the state's own size, given back within the call, do not.
-  constexpr size_t kLead = (size_t)3 << 30;         // distance between two readings
-  constexpr double kGain = 1.10;                    // slowest / best (normalised) at which the search has found what it looks for
-  constexpr size_t kPatience = (size_t)42 << 30;    // walked without an improvement before giving up: more than the 32 GiB a region
-                                                    // spans (15 GiB gave up inside x's own region on some boxes: 1049 instead of 958 us)
-  constexpr int kMore = 16;                         // readings beyond the first that passes kGain
-  // per leg, the release of the blocks included: 100 ms, or what forty steps of the handle being placed take if that is more (a
-  // step moves 12 x pbytes at ~6 TB/s: 1 ms at config 2, 4 ms at config 4's share, 10 ms at config 5's -- whose 2-5 GB blocks cost
-  // 5-60 ms each to allocate on a device that hands them out for the first time)
-  const double kMaxSeconds = h->cfg.placement_ms > 0 ? 1e-3 * h->cfg.placement_ms : std::max(0.100, 40.0 * 12.0 * (double)pbytes / 6.0e12);
-  constexpr double kFreeSeconds = 0.0002;           // what giving one block back costs (hipFree: 25 ms for 110 blocks)
-  constexpr double kSlowPerGiB = 0.0008;            // a hipMalloc slower than this per GiB is clearing never-used memory
-  constexpr int kMaxBlocks = 192;
-  PlacementStats& st = h->place;
-  PlacementState& ps = h->place_state;
-  const auto t_begin = std::chrono::steady_clock::now();
-  auto seconds = [t_begin]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(); };
-  ps.legs += 1;
-  size_t free_b = 0, total_b = 0;
-  EventOwner e0, e1;
-  bool ok = hipMemGetInfo(&free_b, &total_b) == hipSuccess && (e0 = make_event()) && (e1 = make_event());
-  const size_t budget = free_b / 3;
-  const long long n2 = (long long)(pbytes / sizeof(double2));
-  long long nb = n2 / ((long long)BLOCK * 8);
-  if (nb < 256) nb = 256;
-  const long long chunk2 = (n2 + nb - 1) / nb;
-  const long long nbh = (nb + 1) / 2, chunk2h = (n2 / 2 + nbh - 1) / nbh;
-  double2* xa = static_cast<double2*>(h->x.get());
-  // filler: the two halves of x streamed against each other (the same kernel at half the size), ~0.1 ms per GB of state
-  auto filler = [&](int passes) {
-    for (int r = 0; r < passes; ++r)
-      hipLaunchKernelGGL(stream_probe_kernel, dim3((unsigned)nbh), dim3(BLOCK), 0, h->stream, xa, xa + n2 / 2, n2 / 2, chunk2h, 1.0, r & 1);
-  };
-  const double pass_ms_guess = 2.0 * (double)pbytes / 5.0e9;           // one filler pass moves 2 x pbytes at ~5 TB/s
-  const int fill_1ms = std::max(1, (int)std::ceil(1.0 / pass_ms_guess));
-  auto pair_ms = [&](void* vb, float* ms) {                            // one untimed pass over (x, block), one timed
-    double2* b = static_cast<double2*>(vb);
-    hipLaunchKernelGGL(stream_probe_kernel, dim3((unsigned)nb), dim3(BLOCK), 0, h->stream, xa, b, n2, chunk2, 1.0, 0);
-    bool good = hipGetLastError() == hipSuccess && hipEventRecord(e0, h->stream) == hipSuccess;
-    hipLaunchKernelGGL(stream_probe_kernel, dim3((unsigned)nb), dim3(BLOCK), 0, h->stream, xa, b, n2, chunk2, 1.0, 0);
-    return good && hipGetLastError() == hipSuccess && hipEventRecord(e1, h->stream) == hipSuccess &&
-           hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(ms, e0, e1) == hipSuccess;
-  };
-  const double gb_per_ms = 4.0 * (double)pbytes / 1e6;                // one pass, 2 arrays read and written: GB/s = this / ms
-
-  BlockFeed feed;
-  const size_t lead_blocks = std::max<size_t>(1, kLead / pbytes);
-  const int device = h->cfg.device_id;
-  std::thread feeder;
-  if (ok && !ps.x_cleared) {
-    ok = hipMemsetAsync(h->x, 0, pbytes, h->stream) == hipSuccess;    // (x holds particles in a later leg: the passes scale by 1.0)
-    ps.x_cleared = true;
-  }
-  if (ok) {
-    feed.lead = lead_blocks;
-    try {
-    feeder = std::thread([&feed, seconds, pbytes, budget, device, kMaxSeconds]() {
-      const bool dev_ok = hipSetDevice(device) == hipSuccess;
-      for (;;) {
-        {
-          std::unique_lock<std::mutex> lk(feed.m);
-          feed.cv.wait(lk, [&] { return feed.stop || (feed.blocks.size() < feed.taken + feed.lead && !(feed.slow && feed.timing)); });
-          if (feed.stop || !dev_ok || (int)feed.blocks.size() >= kMaxBlocks || (feed.blocks.size() + 2) * pbytes > budget ||
-              seconds() + kFreeSeconds * (double)feed.blocks.size() > kMaxSeconds)
-            break;
-        }
-        void* b = nullptr;
-        const double tm = seconds();
-        const bool got = hipMalloc(&b, pbytes) == hipSuccess;
-        const double dt = seconds() - tm;
-        std::lock_guard<std::mutex> lk(feed.m);
-        feed.malloc_seconds += dt;
-        feed.slow = dt > kSlowPerGiB * ((double)pbytes / (double)(1ull << 30));
-        if (!got) { (void)hipGetLastError(); break; }
-        feed.blocks.push_back(b);
-        feed.cv.notify_all();
-      }
-      std::lock_guard<std::mutex> lk(feed.m);
-      feed.done = true;
-      feed.cv.notify_all();
-    });
-    } catch (...) {                                                   // no thread to be had: no search
-      ok = false;
-    }
-  }
-  // normalised readings: time of (x, block) / time of (x, the leg's first block) taken in the same breath
-  void* ref = nullptr;
-  float ref_ms = 0.f;
-  double last_reading_at = -1.0;                                      // seconds() when the stream last finished a reading
-  auto reading = [&](void* b, double* norm, float* raw_ms) {
-    const double t0 = seconds();
-    {
-      std::lock_guard<std::mutex> lk(feed.m);
-      feed.timing = true;
-    }
-    bool good = true;
-    const bool rested = last_reading_at < 0.0 || t0 - last_reading_at > 0.0005;
-    if (rested) {                                                     // the reference again, behind a filler: same point of the ramp
-      filler(last_reading_at < 0.0 ? 4 * fill_1ms : fill_1ms);
-      good = pair_ms(ref, &ref_ms);
-    }
-    if (good && b != ref) good = pair_ms(b, raw_ms); else *raw_ms = ref_ms;
-    last_reading_at = seconds();
-    {
-      std::lock_guard<std::mutex> lk(feed.m);
-      feed.timing = false;
-      feed.cv.notify_all();
-    }
-    *norm = (double)*raw_ms / (double)ref_ms;
-    st.timing_seconds += seconds() - t0;
-    return good;
-  };
-  void* best = h->v;                                                  // the block kept by earlier legs, or null
-  double best_n = ps.best_n, worst_n = ps.worst_n;                    // normalised; 0 = none yet
-  // raw ms of the kept pair's reading and of the slowest reading of the leg (the rates pic_placement reports).  Blocks are chosen on
-  // normalised readings, whose raw times were taken against different references: the pair with the largest ratio can stream faster
-  // than the one kept, so the slowest rate reported is that of the slowest raw reading, never above the kept pair's.
-  float best_raw = 0.f, slowest_raw = 0.f;
-  int timed = 0, found_at = 0;
-  size_t last = 0, best_at = 0;                                       // blocks.size() at the last / at the best reading
-  int outcome = PIC_PLACED_MEMORY;                                    // (the feeder ran into the block or memory limit, or hipMalloc failed)
-  while (ok) {
-    void* b = nullptr;
-    {
-      std::unique_lock<std::mutex> lk(feed.m);
-      // the next reading is due `lead` blocks further on (or on what the feeder managed before it stopped)
-      feed.cv.wait(lk, [&] { return feed.done || feed.blocks.size() >= last + feed.lead; });
-      if (feed.blocks.size() == last) break;                          // the feeder has stopped and every block it made has been looked at
-      last = feed.taken = feed.blocks.size();
-      b = feed.blocks.back();
-      if (found_at > 0) feed.lead = 1;                                // (past the first find every block is looked at: fewer to give back)
-      if (!ref) ref = feed.blocks.front();
-      feed.cv.notify_all();
-    }
-    if (seconds() + kFreeSeconds * (double)last > kMaxSeconds) {      // (the 100 ms include giving the blocks back)
-      outcome = PIC_PLACED_TIMEOUT;
-      break;
-    }
-    if (last <= ps.frontier) continue;                                // an earlier leg has been here: nothing new to learn
-    double n = 0.0;
-    float raw = 0.f;
-    if (timed == 0) {
-      // first reading of a leg: the reference itself (first leg: it is a candidate like any other, n = 1), or where the block
-      // kept by the earlier legs stands today
-      void* first = h->v ? h->v : ref;
-      ok = reading(first, &n, &raw);
-      if (!ok) break;
-      best = first; best_n = n; best_raw = raw; best_at = last;
-      if (worst_n < n) worst_n = n;
-      slowest_raw = std::max(slowest_raw, raw);
-      ++timed;
-      if (b == first) continue;
-    }
-    ok = reading(b, &n, &raw);
-    if (!ok) break;
-    ++timed;
-    if (best_n == 0.0 || n < best_n) { best = b; best_n = n; best_raw = raw; best_at = last; }
-    if (n > worst_n) worst_n = n;
-    slowest_raw = std::max(slowest_raw, raw);
-    if (worst_n >= kGain * best_n) {                                  // a fast pair, known to be one ...
-      // ... but there are more than two kinds (5.0-5.3 / 5.6-5.75 / 5.85-6.0 TB/s read on used devices, 0.983 / 0.970 / 0.963 ms per
-      // step at config 2), and the first pair 10 % above the slowest is often of the middle one: a reading costs 0.7 ms, so
-      // kMore further blocks are looked at and the best of all is kept
-      if (found_at == 0) found_at = timed;
-      if (timed - found_at >= kMore) { outcome = PIC_PLACED_FOUND; break; }
-      continue;
-    }
-    // (for the 2-5 GB blocks of configs 4 and 5 that is sixteen blocks at least: nine alike have been followed by a fast one)
-    if ((last - best_at) * pbytes >= kPatience && last - best_at >= 16) { outcome = PIC_PLACED_PATIENCE; break; }
-  }
-  if (feeder.joinable()) {
-    {
-      std::lock_guard<std::mutex> lk(feed.m);
-      feed.stop = true;
-      feed.cv.notify_all();
-    }
-    feeder.join();
-  }
-  if (outcome == PIC_PLACED_MEMORY && seconds() + kFreeSeconds * (double)feed.blocks.size() > kMaxSeconds)
-    outcome = PIC_PLACED_TIMEOUT;                                     // (the feeder's own clock check)
-  if (found_at > 0) outcome = PIC_PLACED_FOUND;                       // a fast pair is in hand: no further leg for the rest of the sixteen
-  (void)hipStreamSynchronize(h->stream);
-  e0.reset();                                                         // (the events go here, inside the leg's clock)
-  e1.reset();
-  (void)hipGetLastError();
-  std::vector<void*>& blocks = feed.blocks;
-  if (!best && !blocks.empty()) best = blocks.front();                // nothing could be timed: any block will do
-  const double tf = seconds();
-  for (void* b : blocks)
-    if (b != best) hipFree(b);
-  h->v_block.reset(best);                                             // (frees the block kept so far if a later leg found a better one)
-  st.free_seconds += seconds() - tf;
-  h->v = best;
-  ps.best_n = best_n; ps.worst_n = worst_n;
-  ps.found = found_at > 0;
-  ps.frontier = std::max(ps.frontier, blocks.size());
-  st.blocks += (int)blocks.size();
-  st.pairs_timed += timed;
-  st.malloc_seconds += feed.malloc_seconds;
-  st.outcome = outcome;
-  if (best_raw > 0.f) st.kept_gbytes_per_s = gb_per_ms / best_raw;
-  if (slowest_raw > 0.f && (st.slowest_gbytes_per_s == 0.0 || gb_per_ms / slowest_raw < st.slowest_gbytes_per_s))
-    st.slowest_gbytes_per_s = gb_per_ms / slowest_raw;
-  st.seconds += seconds();
-  st.legs = ps.legs;
-}
-
-hipError_t alloc_particles(pic_handle* h, size_t pbytes) {
-  constexpr size_t kMinBytes = (size_t)256 << 20;
-  h->place = PlacementStats{};
-  h->place_state = PlacementState{};
-  if (2 * pbytes < kMinBytes || h->cfg.placement == PIC_PLACE_OFF) {
-    const hipError_t e = alloc(h->x, 2 * pbytes);
-    h->v = static_cast<char*>(h->x.get()) + pbytes;
-    return e;
-  }
-  hipError_t e = alloc(h->x, pbytes);
-  if (e != hipSuccess) return e;
-  h->v_separate = true;
-  h->place_state.pbytes = pbytes;
-  placement_leg(h, pbytes);
-  if (h->v) return hipSuccess;
-  e = alloc(h->v_block, pbytes);                                       // no candidate at all (no memory to search in): plain allocation
-  h->v = h->v_block;
-  return e;
-}
-
-// A reset replaces the particles: while the search has only ended for lack of time, and nobody outside has been given the arrays'
-// addresses, it may run another leg and move v for nothing.
-void resume_placement(pic_handle* h) {
-  PlacementState& ps = h->place_state;
-  if (!h->v_separate || ps.pbytes == 0 || ps.ptrs_exposed || ps.legs >= kMaxLegs || h->place.outcome != PIC_PLACED_TIMEOUT) return;
-  (void)hipStreamSynchronize(h->stream);
-  placement_leg(h, ps.pbytes);
-}
 
 int pic_create(const pic_config* cfg, pic_handle** out) {
   if (!cfg || !out) return fail(nullptr, PIC_EINVAL, "pic_create: null argument");
   *out = nullptr;
-  if (cfg->N < 1 || cfg->Ng < 4 || cfg->num_envs < 1 || !(cfg->L > 0) || !(cfg->dt > 0) || !(cfg->n0 > 0))
-    return fail(nullptr, PIC_EINVAL, "pic_create: need N>=1, Ng>=4, num_envs>=1, L>0, dt>0, n0>0");
-  if (cfg->N > (1ll << 36)) return fail(nullptr, PIC_EINVAL, "pic_create: N > 2^36");
-  if (cfg->num_envs > 65535) return fail(nullptr, PIC_EINVAL, "pic_create: num_envs > 65535");
-  if (cfg->env_index_base < 0) return fail(nullptr, PIC_EINVAL, "pic_create: env_index_base < 0");
-  if (cfg->particle_dtype != PIC_F64 && cfg->particle_dtype != PIC_F32)
-    return fail(nullptr, PIC_EINVAL, "pic_create: particle_dtype must be PIC_F64 or PIC_F32");
-  if (cfg->position_dtype != PIC_POS_FLOAT && cfg->position_dtype != PIC_POS_FIXED32)
-    return fail(nullptr, PIC_EINVAL, "pic_create: position_dtype must be PIC_POS_FLOAT or PIC_POS_FIXED32");
-  if (cfg->position_dtype == PIC_POS_FIXED32 && cfg->particle_dtype != PIC_F32)
-    return fail(nullptr, PIC_EINVAL, "pic_create: 32-bit fixed-point positions go with float32 particles");
-  if (cfg->accum_dtype < PIC_ACC_AUTO || cfg->accum_dtype > PIC_ACC_F64)
-    return fail(nullptr, PIC_EINVAL, "pic_create: accum_dtype must be PIC_ACC_AUTO, _FIX64, _PACKED or _F64");
-  if (cfg->interpol != PIC_CIC && cfg->interpol != PIC_TSC)
-    return fail(nullptr, PIC_EINVAL, "pic_create: interpol must be PIC_CIC or PIC_TSC");
-  if (cfg->accum_dtype == PIC_ACC_PACKED && cfg->particle_dtype != PIC_F32)
-    return fail(nullptr, PIC_EINVAL, "pic_create: the packed accumulator needs float32 particles");
-  if (cfg->accum_dtype == PIC_ACC_PACKED && cfg->interpol != PIC_CIC)
-    return fail(nullptr, PIC_EINVAL, "pic_create: the packed accumulator is CIC only");
-  if (cfg->placement != PIC_PLACE_AUTO && cfg->placement != PIC_PLACE_OFF)
-    return fail(nullptr, PIC_EINVAL, "pic_create: placement must be PIC_PLACE_AUTO or PIC_PLACE_OFF");
-  if (cfg->placement_ms < 0) return fail(nullptr, PIC_EINVAL, "pic_create: placement_ms < 0");
-  if (cfg->accum_dtype == PIC_ACC_F64 && cfg->particle_dtype != PIC_F64)
-    return fail(nullptr, PIC_EINVAL, "pic_create: the float64 accumulator needs float64 particles");
+  std::string err;
+  if (int rc = check_config(*cfg, &err)) return fail(nullptr, rc, err);
 
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
@@ -1138,147 +847,16 @@ int pic_create(const pic_config* cfg, pic_handle** out) {
                                          ": libpicstep.so is built for gfx950 (MI355X) only");
   }
 
+  int ncu = 256;                             // (what the plan assumes of a device that does not say)
+  if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, cfg->device_id) != hipSuccess) ncu = 256;
+
   std::unique_ptr<pic_handle> owner(new (std::nothrow) pic_handle());     // a return before the end frees all the handle holds
   pic_handle* h = owner.get();
   if (!h) return fail(nullptr, PIC_ENOMEM, "pic_create: out of host memory");
   h->cfg = *cfg;
-  h->fmt = cfg->particle_dtype == PIC_F64 ? FMT_F64 : (cfg->position_dtype == PIC_POS_FIXED32 ? FMT_U32 : FMT_F32);
-  h->acc_kind = cfg->accum_dtype;
-  if (h->acc_kind == PIC_ACC_AUTO)
-    h->acc_kind = (cfg->particle_dtype == PIC_F32 && cfg->interpol == PIC_CIC) ? PIC_ACC_PACKED : PIC_ACC_FIX64;
-  h->esz = cfg->particle_dtype == PIC_F64 ? 8 : 4;
-  h->vec = cfg->particle_dtype == PIC_F64 ? 2 : 4;
-  h->dx = cfg->L / cfg->Ng;                                   // pic.py:36
-  h->scale = cfg->n0 * cfg->L / (double)cfg->N / h->dx;       // interpolate.py:18
-  yoshida_coefficients(h->cs, h->ds);
-  h->ld = (cfg->N + 63) / 64 * 64;
-  // fixed-point accumulators: the weights of all N particles on one node must fit in 63 bits
-  int lg = 0;
-  while ((1ll << lg) < cfg->N + 1) ++lg;
-  h->fg = 62 - lg > 50 ? 50 : 62 - lg;
-  h->magic = std::ldexp(1.5, 52 - h->fg);
-
-  // workgroups per environment: enough in total to fill 256 CUs several times, at least one
-  // BLOCK*VEC tile each
-  const long long tile = (long long)BLOCK * h->vec;
-  long long nblk = cfg->blocks_per_env;      // workgroups per environment of the streaming sweeps (resets and probes always use them)
-  if (nblk <= 0) {
-    const long long target_total = 8192;      // ~128 workgroups per env at 64 envs (profiles/experiments_r1.md)
-    nblk = (target_total + cfg->num_envs - 1) / cfg->num_envs;
-    // Large environments: >= 8 tiles per workgroup (amortises the prologue and the flush).  Small ones in small
-    // ensembles are latency-bound (profiles/experiments_r2.md: N = 1e5 13 -> 98 workgroups 47 -> 28 us/step; N = 1e6
-    // is best at 122 whatever the number of environments): one tile per workgroup, at most 64 workgroups per environment.
-    const bool small = (double)cfg->N * cfg->num_envs <= 4.0e6 && cfg->N <= 131072;
-    long long tiles_min = small ? 1 : 8;
-    // one or two large environments: 4 tiles per workgroup, so that there is a workgroup for every CU (N = 1e6, one
-    // environment: 122 workgroups 64 us/step, 245 56 us, 489 63 us)
-    if (!small && (cfg->N + 8 * tile - 1) / (8 * tile) * cfg->num_envs < 256) tiles_min = 4;
-    long long max_by_work = (cfg->N + tiles_min * tile - 1) / (tiles_min * tile);
-    if (small && max_by_work > 64) max_by_work = 64;
-    if (nblk > max_by_work) nblk = max_by_work;
-    if (nblk < 1) nblk = 1;
-    // ... and at most ~10 tiles (80 KB of x, 80 KB of v) per workgroup: a total of 8192 workgroups is 156 000 particles each at
-    // config 5's share -- 340 us per workgroup, and a last partial round of workgroups that long at the end of every sweep.  Scans
-    // of both large shares (profiles/bpe_big.sh): N = 4e6 x 64 float64 128 -> 384 workgroups per environment 4078 -> 3997 us per
-    // step (512: 4029), N = 1e7 x 128 float32 64 -> 512: 10223 -> 9913 (768: 9928, 1024: 10058); config 2 (122) is not touched.
-    const long long by10 = (cfg->N + 10 * tile - 1) / (10 * tile);
-    if (!small && nblk < by10) nblk = by10;
-    // A handful of large environments run as one to six workgroups per CU: a total that fills the CUs unevenly leaves some
-    // with one workgroup more than others for the whole sweep (3 x 1e6: 3 x 123 = 369 workgroups on 256 CUs 63.3 us/step, 3 x 163
-    // = 489 58.9).  Take the workgroups per environment from the smallest k >= 2 workgroups per CU that keeps >= 8 tiles' worth
-    // ... per workgroup where it can (k ncu / E, at most the 4-tile count); 1, 2, 4, 6, 8, 12 environments keep what they had.
-    if (!small) {
-      int ncu = 256;
-      hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, cfg->device_id);
-      const long long by4 = (cfg->N + 4 * tile - 1) / (4 * tile);
-      if (nblk * cfg->num_envs < 6ll * ncu) {
-        for (long long k = 2; k <= 6; ++k) {
-          long long c = k * ncu / cfg->num_envs;
-          if (c > by4) c = by4;
-          if (c >= nblk || c == by4) { nblk = c; break; }
-        }
-      }
-    }
-  }
-  {                                          // a workgroup's chunk of x or v is addressed with 31-bit byte offsets (StreamOut)
-    const long long cap = (1ll << 27) - tile;
-    if (nblk < (cfg->N + cap - 1) / cap) nblk = (cfg->N + cap - 1) / cap;
-  }
-  if (h->acc_kind == PIC_ACC_PACKED) {       // count field of the packed accumulator: < 2^20 particles per workgroup
-    const long long cap = (1ll << 20) - tile;
-    if (nblk < (cfg->N + cap - 1) / cap) nblk = (cfg->N + cap - 1) / cap;
-  }
-  long long chunk = (cfg->N + nblk - 1) / nblk;
-  chunk = (chunk + tile - 1) / tile * tile;
-  nblk = (cfg->N + chunk - 1) / chunk;
-  if (nblk > 65535) return fail(nullptr, PIC_EINVAL, "pic_create: blocks_per_env too large");
-  h->chunk = chunk;
-  h->nblk = (int)nblk;
-  // Sub-rows of an accumulator row (pic_device.h: acc_row_sum): with few environments all workgroups of an environment flush
-  // at about the same time, and their atomics on one 8 Ng-byte row are serialised at the memory side.  At most 4 sub-rows (1 / 2 /
-  // 3 / 4 environments of 1e6: 31.2 / 45.0 / 64.5 / 74.0 us per step with 4, 31.6 / 45.3 / 65.5 / 75.1 with 8, 33.3 / 47.8 /
-  // 65.2 / 75.4 with 16: every reader sums them), at least 8 workgroups per sub-row; with 16 environments or more the rows
-  // themselves spread the traffic (and the flushes hide under the streaming of the other workgroups).
-  // Inner steps of a multi-step call leave the deposit of their final positions to the next step's sweep B2 (run_stages) where the
-  // sweeps are bound by HBM -- a particle state that does not fit the 256 MB Infinity Cache: there sweep B has the issue slots that
-  // sweep D lacks (config 2 969 -> 948 us per step).  States that live in the cache, or are bound by the latency of each launch,
-  // gain nothing or lose (all measured on one box, round 3's tree against this one: 8 x 1e6 float64 131.2 -> 132.6, 64 x 20000
-  // float32 TSC 26.2 -> 27.2, config 1 14.5 -> 14.7, one environment of N = 1e5 19.1 -> 19.4): they keep the full sweep D.
-  h->light_inner_steps = 2.0 * (double)cfg->num_envs * (double)h->ld * (double)h->esz >= 256.0 * 1048576.0;
-  // Whole steps on such a state also leave sweep C's stores out: sweep D re-derives C's output from C's input (ST_C_RO, ST_D_RC,
-  // ST_D2_RC) -- 80 instead of 96 bytes per float64 particle-step, and D's extra sub-stage fits its issue slots with the wave-uniform
-  // wrap (config 2 959 -> 865 us per step; profiles/r5_readonly.md).  pic_set_readonly_c overrides the choice.
-  h->readonly_auto = h->light_inner_steps;
-  h->S = 1;
-  while (h->S < 4 && nblk / (2 * h->S) >= 8 && (long long)cfg->num_envs * 2 * h->S <= 32) h->S *= 2;
-
-  const size_t stride = (size_t)cfg->Ng + 2;
-  // LDS: 2 R meshes (sweep D deposits two) + the field tile.  R = 1: one mesh for the eight waves of a workgroup.  Copies per
-  // wave pair (R = 4, rounds 1-2) bought nothing at config 2 and cost 2-4 % where a step is short (more to sum and clear per
-  // workgroup); even with every particle in ONE cell a sweep is only 16 % slower, with 1 copy as with 4
-  // (profiles/experiments_r2.md 17, profiles/clustered.py)
-  h->R = 1;
-  h->sweep_lds = 2 * h->R * stride * 8 + stride * h->esz;
-  h->solve_lds = 2 * (size_t)cfg->Ng * sizeof(double);
-  // a workgroup may use 64 KB of LDS: the dynamic part sized here plus the kernels' static arrays (kSweepStaticLds, kResidentStaticLds)
-  constexpr size_t kLdsLimit = 64 * 1024;
-  if (h->sweep_lds + stride * h->esz + kSweepStaticLds <= kLdsLimit) h->sweep_lds_rc = h->sweep_lds + stride * h->esz;
-  else h->readonly_auto = false;
+  if (int rc = plan_launch(*cfg, ncu, h, &err)) return fail(nullptr, rc, err);      // (host_plan.h: geometry, LDS, schedule)
   h->readonly_c = h->readonly_auto;
-  if (h->sweep_lds + kSweepStaticLds > kLdsLimit) {
-    const long long max_ng = (long long)((kLdsLimit - kSweepStaticLds) / (2 * h->R * 8 + h->esz)) - 2;
-    return fail(nullptr, PIC_EINVAL, "pic_create: Ng too large for the LDS-resident mesh (at most " + std::to_string(max_ng) +
-                                     " cells with this particle dtype)");
-  }
-  // Resident schedule (pic_resident.h): environments whose particles fit one workgroup's registers are stepped by
-  // one launch per pic_step call.  blocks_per_env: 0 = use it where it applies, > 0 = streaming sweeps with that many
-  // workgroups, -1 = resident or fail.
-  {
-    // 512-thread workgroups holding 4, 8, 10 or 16 particles per lane (1024 threads leave 128 registers per lane:
-    // the 10- and 16-particle bodies spill there, so larger environments stay with the sweeps)
-    static const int shapes[4][3] = {{8, 4, 2048}, {8, 8, 4096}, {8, 10, 5120}, {8, 16, 8192}};
-    for (const auto& sh : shapes)
-      if (cfg->N <= sh[2]) { h->res_nw = sh[0]; h->res_ppt = sh[1]; break; }
-    h->res_R = 1;   // one mesh per workgroup: replicas cost more in node sums and clearing than they save in LDS atomic contention (experiments_r2.md 17)
-    auto need = [&](int R) { return (size_t)2 * R * stride * 8 + 4 * (size_t)cfg->Ng * 8 + stride * h->esz; };
-    while (h->res_R > 1 && need(h->res_R) > 48 * 1024) h->res_R >>= 1;
-    h->res_lds = need(h->res_R);
-    const bool possible = h->res_nw != 0 && h->res_lds + kResidentStaticLds <= kLdsLimit && h->acc_kind != PIC_ACC_F64;
-    if (cfg->blocks_per_env < 0 && !possible) {
-      const long long max_ng = (long long)((kLdsLimit - kResidentStaticLds - 2 * (2 * 8 + h->esz)) / (2 * 8 + h->esz + 4 * 8));
-      return fail(nullptr, PIC_EINVAL, "pic_create: the resident schedule needs N <= 8192, Ng <= " + std::to_string(max_ng) +
-                                       " (this particle dtype) and an integer accumulator");
-    }
-    // Measured (profiles/experiments_r2.md): one workgroup steps 5000 float64 particles in ~17 us whatever the number of
-    // environments, the sweeps need 22 us for one environment of 8000 and 35-110 us for 64-1024 of 5000.  A lone
-    // large-ish environment is therefore left to the sweeps (they spread it over many CUs).
-    const bool worth = cfg->N <= 5120 || cfg->num_envs >= 32;
-    h->resident = possible && (cfg->blocks_per_env < 0 || (cfg->blocks_per_env == 0 && worth));
-    int ncu = 256;
-    hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, cfg->device_id);
-    // (carrying three TSC weights for 16 particles per lane would need more than 256 registers)
-    h->res_lean = (cfg->num_envs > ncu && h->res_ppt <= 10) || (cfg->interpol == PIC_TSC && h->res_ppt == 16);
-  }
+  const size_t stride = (size_t)cfg->Ng + 2;
 
   auto failed = [](hipError_t e, const char* what) {
     return fail(nullptr, e == hipErrorOutOfMemory ? PIC_ENOMEM : PIC_EHIP, std::string("pic_create: ") + what + ": " + hipGetErrorString(e));
@@ -1293,7 +871,7 @@ int pic_create(const pic_config* cfg, pic_handle** out) {
   if (hipError_t e = hipMemsetAsync(h->v, 0, pbytes, h->stream)) return failed(e, "hipMemsetAsync of v");
   // small states (the reference's N = 5000) are read back every step by a Gym-style loop: one copy of x and v
   // together into pinned memory instead of two copies into pageable memory
-  if (2 * (size_t)cfg->num_envs * cfg->N * h->esz <= ((size_t)4 << 20))
+  if (h->h_part_at_create)
     if (hipError_t e = alloc(h->h_part, 2 * (size_t)cfg->num_envs * h->ld * h->esz)) return failed(e, "pinned particle staging");
   if (hipError_t e = alloc_zeroed(h->ring, (size_t)(RING + 1) * h->S * gbytes, h->stream))      // acc_t and double are both 8 bytes
     return failed(e, "accumulator ring");
@@ -1304,10 +882,8 @@ int pic_create(const pic_config* cfg, pic_handle** out) {
     if (hipError_t e = alloc_zeroed(h->res_q1, qbytes, h->stream)) return failed(e, "resident q1 meshes");
     // cells and weights of the q1 positions travel with it where a launch is latency, not traffic: a handful of environments
     // (20 bytes per particle each way: 256 environments would spend 8 us on them), kernels that carry them (pic_resident.h: kHandCarry)
-    if (!h->res_lean && h->res_ppt <= 10 && h->esz == 8 && cfg->num_envs <= 32) {
-      const size_t cbytes = (size_t)cfg->num_envs * h->res_nw * 64 * h->res_ppt * (sizeof(int) + (cfg->interpol == PIC_TSC ? 4 : 2) * h->esz);
-      if (hipError_t e = alloc_zeroed(h->res_carry, cbytes, h->stream)) return failed(e, "resident carried cells");
-    }
+    if (h->res_carry_bytes)
+      if (hipError_t e = alloc_zeroed(h->res_carry, h->res_carry_bytes, h->stream)) return failed(e, "resident carried cells");
   }
   if (hipError_t e = alloc_zeroed(h->ke_part, (size_t)cfg->num_envs * h->nblk * sizeof(double), h->stream)) return failed(e, "KE partials");
   for (DeviceBuf<double>* g : {&h->n, &h->E_mesh, &h->phi, &h->ext, &h->ext2, &h->probe_ext, &h->aux_n, &h->aux_E, &h->aux_phi})
@@ -1320,7 +896,7 @@ int pic_create(const pic_config* cfg, pic_handle** out) {
   h->PE = h->KE + cfg->num_envs;
   h->PEr = h->KE + 2 * (size_t)cfg->num_envs;
   if (hipError_t e = alloc(h->h_scal, 3 * sbytes)) return failed(e, "pinned energy staging");
-  if (gbytes <= ((size_t)256 << 10))
+  if (h->LaunchPlan::h_fields)                 // (the plan's flag: the buffer of the same name hides it)
     if (hipError_t e = alloc(h->h_fields, 3 * gbytes)) return failed(e, "pinned mesh staging");
   if (hipError_t e = alloc(h->h_probe_pe, sbytes)) return failed(e, "pinned probe energy");
   if (hipError_t e = alloc_zeroed(h->aux_pe, sbytes, h->stream)) return failed(e, "probe energies");
@@ -1515,14 +1091,7 @@ static int ensure_traj(pic_handle* h, size_t bytes) {
 }
 
 static int stage_ext(pic_handle* h, const double* E_ext, int mem_kind, const double** ext) {
-  *ext = nullptr;
-  if (!E_ext) return PIC_OK;
-  *ext = E_ext;
-  if (mem_kind == PIC_HOST) {
-    HIPCHK(h, hipMemcpyAsync(h->ext, E_ext, (size_t)h->cfg.num_envs * h->cfg.Ng * sizeof(double), hipMemcpyHostToDevice,
-                             h->stream));
-    *ext = h->ext;
-  }
+  HIPCHK(h, device_input(h, E_ext, mem_kind, (size_t)h->cfg.num_envs * h->cfg.Ng * sizeof(double), h->ext, ext));
   return PIC_OK;
 }
 
@@ -1899,13 +1468,10 @@ int pic_step_snapshots(pic_handle* h, const double* E_ext, int mem_kind, int nst
 
 // a per-step input trajectory [nsteps][row] (host or device) -> device pointer
 static int stage_traj(pic_handle* h, const double* src, int mem_kind, size_t row_elems_, int nsteps, const double** dev) {
-  *dev = src;
-  if (mem_kind != PIC_HOST) return PIC_OK;
   const size_t bytes = (size_t)nsteps * row_elems_ * sizeof(double);
-  int rc = ensure_traj(h, bytes);
-  if (rc) return rc;
-  HIPCHK(h, hipMemcpyAsync(h->traj, src, bytes, hipMemcpyHostToDevice, h->stream));
-  *dev = static_cast<const double*>(h->traj.get());
+  if (mem_kind == PIC_HOST)
+    if (int rc = ensure_traj(h, bytes)) return rc;
+  HIPCHK(h, device_input(h, src, mem_kind, bytes, static_cast<double*>(h->traj.get()), dev));
   return PIC_OK;
 }
 
@@ -1966,6 +1532,17 @@ static int enqueue_observe(pic_handle* h, bool scalars, size_t* pitch) {
   HIPCHK(h, hipGetLastError());
   return PIC_OK;
 }
+// x and v (either may be null) on their way to the caller, enqueued; the caller waits.  staged: through the pinned staging, rows
+// *pitch bytes apart (unpack_part behind the wait; the two callers differ in when they stage), else straight into x and v in
+// mem_kind's memory.  scalars: the energies travel along, into h_scal.
+static int enqueue_particles_out(pic_handle* h, void* x, void* v, int mem_kind, bool staged, bool scalars, size_t* pitch) {
+  if (staged) return enqueue_observe(h, scalars, pitch);
+  if (scalars) HIPCHK(h, hipMemcpyAsync(h->h_scal, h->KE, 3 * (size_t)h->cfg.num_envs * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  int rc = PIC_OK;
+  if (x) rc = download_positions(h, x, h->x, mem_kind);
+  if (!rc && v) rc = download(h, v, h->v, mem_kind);
+  return rc;
+}
 // staging -> the caller's [num_envs][N] arrays
 static void unpack_part(pic_handle* h, void* x, void* v, size_t pitch) {
   const size_t E = (size_t)h->cfg.num_envs, row = (size_t)h->cfg.N * h->esz;
@@ -2000,20 +1577,13 @@ static int stage_actions(pic_handle* h, const double* actions, StepControl& sc) 
 int pic_get_particles(pic_handle* h, void* x, void* v, int mem_kind) {
   if (!h) return PIC_EINVAL;
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (x && v && mem_kind == PIC_HOST && h->fmt != FMT_U32 && ensure_part_staging(h)) {
-    // states up to 64 MB go through pinned staging (enqueue_observe)
-    size_t pitch = 0;
-    const int rc = enqueue_observe(h, false, &pitch);
-    if (rc) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    unpack_part(h, x, v, pitch);
-    return PIC_OK;
-  }
-  int rc = PIC_OK;
-  if (x) rc = download_positions(h, x, h->x, mem_kind);
-  if (!rc && v) rc = download(h, v, h->v, mem_kind);
+  // states up to 64 MB go through pinned staging (enqueue_observe)
+  const bool staged = x && v && mem_kind == PIC_HOST && h->fmt != FMT_U32 && ensure_part_staging(h);
+  size_t pitch = 0;
+  const int rc = enqueue_particles_out(h, x, v, mem_kind, staged, false, &pitch);
   if (rc) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (staged) unpack_part(h, x, v, pitch);
   return PIC_OK;
 }
 
@@ -2048,9 +1618,7 @@ int pic_get_fields(pic_handle* h, double* n, double* E_mesh, double* phi) {
     if (phi) std::memcpy(phi, h->h_fields + 2 * count, gbytes);
     return PIC_OK;
   }
-  if (n) HIPCHK(h, hipMemcpyAsync(n, h->n, gbytes, hipMemcpyDeviceToHost, h->stream));
-  if (E_mesh) HIPCHK(h, hipMemcpyAsync(E_mesh, h->E_mesh, gbytes, hipMemcpyDeviceToHost, h->stream));
-  if (phi) HIPCHK(h, hipMemcpyAsync(phi, h->phi, gbytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, read_back(h, gbytes, {{n, h->n}, {E_mesh, h->E_mesh}, {phi, h->phi}}));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return PIC_OK;
 }
@@ -2058,12 +1626,9 @@ int pic_get_fields(pic_handle* h, double* n, double* E_mesh, double* phi) {
 int pic_get_energies(pic_handle* h, double* KE, double* PE, double* PE_reward) {
   if (!h) return PIC_EINVAL;
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  const size_t E = (size_t)h->cfg.num_envs, b = E * sizeof(double);
-  HIPCHK(h, hipMemcpyAsync(h->h_scal, h->KE, 3 * b, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->h_scal, h->KE, 3 * (size_t)h->cfg.num_envs * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (KE) std::memcpy(KE, h->h_scal, b);
-  if (PE) std::memcpy(PE, h->h_scal + E, b);
-  if (PE_reward) std::memcpy(PE_reward, h->h_scal + 2 * E, b);
+  unpack_scalars(h, KE, PE, PE_reward);
   return PIC_OK;
 }
 
@@ -2120,10 +1685,7 @@ int pic_get_cic(pic_handle* h, int env, int64_t* indx_l, int64_t* indx_r, double
 static int probe_solve(pic_handle* h, const double* E_ext, bool want_phi, void* xs = nullptr, double* pe_out = nullptr) {
   const size_t gbytes = (size_t)h->cfg.num_envs * h->cfg.Ng * sizeof(double);
   const double* ext = nullptr;
-  if (E_ext) {
-    HIPCHK(h, hipMemcpyAsync(h->probe_ext, E_ext, gbytes, hipMemcpyHostToDevice, h->stream));
-    ext = h->probe_ext;
-  }
+  HIPCHK(h, device_input(h, E_ext, PIC_HOST, gbytes, h->probe_ext, &ext));
   if (!xs) xs = h->scratch;
   // (the solve zeroes the row behind its read: one command less per probe; a probe that failed half way leaves it unknown)
   if (!h->probe_row_clean) HIPCHK(h, hipMemsetAsync(h->probe_acc, 0, row_elems(h) * sizeof(acc_t), h->stream));
@@ -2158,8 +1720,7 @@ int pic_eval_field(pic_handle* h, const void* x, int mem_kind, const double* E_e
     }
     int rc = probe_solve(h, E_ext, false, h->h_part, h->h_probe_pe);
     if (rc) return rc;
-    if (n) HIPCHK(h, hipMemcpyAsync(n, h->aux_n, gbytes, hipMemcpyDeviceToHost, h->stream));
-    if (E_mesh) HIPCHK(h, hipMemcpyAsync(E_mesh, h->aux_E, gbytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, read_back(h, gbytes, {{n, h->aux_n}, {E_mesh, h->aux_E}}));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (half_sum_E2_dx) std::memcpy(half_sum_E2_dx, h->h_probe_pe, E * sizeof(double));
     return PIC_OK;
@@ -2170,8 +1731,7 @@ int pic_eval_field(pic_handle* h, const void* x, int mem_kind, const double* E_e
   if (rc) return rc;
   rc = probe_solve(h, E_ext, false);
   if (rc) return rc;
-  if (n) HIPCHK(h, hipMemcpyAsync(n, h->aux_n, gbytes, hipMemcpyDeviceToHost, h->stream));
-  if (E_mesh) HIPCHK(h, hipMemcpyAsync(E_mesh, h->aux_E, gbytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, read_back(h, gbytes, {{n, h->aux_n}, {E_mesh, h->aux_E}}));
   if (half_sum_E2_dx)
     HIPCHK(h, hipMemcpyAsync(half_sum_E2_dx, h->aux_pe, (size_t)h->cfg.num_envs * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2191,9 +1751,7 @@ int pic_compute_E(pic_handle* h, const void* x, int mem_kind, const double* E_ex
   const size_t gbytes = (size_t)E_ * h->cfg.Ng * sizeof(double);
   rc = probe_solve(h, E_ext, true);
   if (rc) return rc;
-  if (n) HIPCHK(h, hipMemcpyAsync(n, h->aux_n, gbytes, hipMemcpyDeviceToHost, h->stream));
-  if (E_mesh) HIPCHK(h, hipMemcpyAsync(E_mesh, h->aux_E, gbytes, hipMemcpyDeviceToHost, h->stream));
-  if (phi_mesh) HIPCHK(h, hipMemcpyAsync(phi_mesh, h->aux_phi, gbytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, read_back(h, gbytes, {{n, h->aux_n}, {E_mesh, h->aux_E}, {phi_mesh, h->aux_phi}}));
 
   // gathers at the particles and shape bookkeeping go through one temporary, sized for the larger of the two
   DeviceBuf<void> tmp;
@@ -2236,8 +1794,7 @@ int pic_solve_poisson(pic_handle* h, const double* rhs, double* phi, double* E_m
   o.rhs = h->aux_n; o.out.E = h->aux_E; o.out.phi = h->aux_phi;
   launch_solve(h, o);
   HIPCHK(h, hipGetLastError());
-  if (phi) HIPCHK(h, hipMemcpyAsync(phi, h->aux_phi, gbytes, hipMemcpyDeviceToHost, h->stream));
-  if (E_mesh) HIPCHK(h, hipMemcpyAsync(E_mesh, h->aux_E, gbytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, read_back(h, gbytes, {{phi, h->aux_phi}, {E_mesh, h->aux_E}}));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return PIC_OK;
 }
@@ -2313,8 +1870,7 @@ int pic_step_observe(pic_handle* h, const double* E_ext, const double* actions, 
   // (h_part).  A one-step call of the resident schedule needs nothing else: its kernel records the particles after the step
   // (the snapshot of PIC.simulate, positions in length units whatever their format) and the step's energies (the energy
   // history) -- both straight into the pinned buffers, whose layouts are those records' for one step.
-  const size_t E = (size_t)h->cfg.num_envs, b = E * sizeof(double);
-  const size_t row = (size_t)h->cfg.N * h->esz, half = row * E;
+  const size_t row = (size_t)h->cfg.N * h->esz, half = row * (size_t)h->cfg.num_envs;
   const bool want_part = x || v;
   bool part_pinned = false;
   size_t pitch = row;
@@ -2326,23 +1882,14 @@ int pic_step_observe(pic_handle* h, const double* E_ext, const double* actions, 
   } else {
     rc = advance(h, sc, nsteps, nullptr);
     if (rc) return rc;
-    if (want_part && h->h_part && h->fmt != FMT_U32) {
-      rc = enqueue_observe(h, true, &pitch);
-      if (rc) return rc;
-      part_pinned = true;
-    } else {
-      HIPCHK(h, hipMemcpyAsync(h->h_scal, h->KE, 3 * b, hipMemcpyDeviceToHost, h->stream));
-      if (x) rc = download_positions(h, x, h->x, PIC_HOST);
-      if (!rc && v) rc = download(h, v, h->v, PIC_HOST);
-      if (rc) return rc;
-    }
+    part_pinned = want_part && h->h_part && h->fmt != FMT_U32;
+    rc = enqueue_particles_out(h, x, v, PIC_HOST, part_pinned, true, &pitch);
+    if (rc) return rc;
   }
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (part_pinned) unpack_part(h, x, v, pitch);
-  if (KE) std::memcpy(KE, h->h_scal, b);
-  if (PE) std::memcpy(PE, h->h_scal + E, b);
-  if (PE_reward) std::memcpy(PE_reward, h->h_scal + 2 * E, b);
+  unpack_scalars(h, KE, PE, PE_reward);
   return PIC_OK;
 }
 
@@ -2380,18 +1927,16 @@ int pic_step_feedback_gain(pic_handle* h, int max_mode, const double* gain, int 
   const int E = h->cfg.num_envs, n = 2 * max_mode;
   const size_t gbytes = (size_t)E * n * n * sizeof(double);
   if (!h->fb_modes) HIPCHK(h, alloc(h->fb_modes, (size_t)E * 2 * kMaxFeedbackModes * sizeof(double)));
-  const hipMemcpyKind in = mem_kind == PIC_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
   Tape& t = h->tape;
   const double* g = gain;
   if (t.on) {                        // the gain goes on the tape once per call
     rc = tape_law_reserve(h, gbytes);
     if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(t.gains.back(), gain, gbytes, in, h->stream));
+    HIPCHK(h, hipMemcpyAsync(t.gains.back(), gain, gbytes, copy_kind(mem_kind, hipMemcpyHostToDevice), h->stream));
     g = t.gains.back();
-  } else if (mem_kind == PIC_HOST) {
-    if (!h->gain) HIPCHK(h, alloc(h->gain, (size_t)E * 4 * kMaxFeedbackModes * kMaxFeedbackModes * sizeof(double)));
-    HIPCHK(h, hipMemcpyAsync(h->gain, gain, gbytes, in, h->stream));
-    g = h->gain;
+  } else {
+    if (mem_kind == PIC_HOST && !h->gain) HIPCHK(h, alloc(h->gain, (size_t)E * 4 * kMaxFeedbackModes * kMaxFeedbackModes * sizeof(double)));
+    HIPCHK(h, device_input(h, gain, mem_kind, gbytes, h->gain, &g));
   }
   sc.fb.gain = g;
   sc.fb.modes = h->fb_modes;
@@ -2429,7 +1974,7 @@ int pic_get_modes(pic_handle* h, int max_mode, double* re, double* im, int mem_k
   hipLaunchKernelGGL(modes_kernel, dim3(max_mode, h->cfg.num_envs), dim3(BLOCK), 0, h->stream, h->E_mesh, h->tw, h->tw_rows,
                      dre, dim_, h->cfg.Ng, max_mode);
   HIPCHK(h, hipGetLastError());
-  const hipMemcpyKind k = mem_kind == PIC_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  const hipMemcpyKind k = copy_kind(mem_kind, hipMemcpyDeviceToHost);
   if (re) HIPCHK(h, hipMemcpyAsync(re, dre, nb, k, h->stream));
   if (im) HIPCHK(h, hipMemcpyAsync(im, dim_, nb, k, h->stream));
   if (mem_kind == PIC_HOST) HIPCHK(h, hipStreamSynchronize(h->stream));   // device outputs stay stream-ordered

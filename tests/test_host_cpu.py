@@ -3,6 +3,7 @@ library's exports, and that the product path refuses to run without a GPU (no fa
 import ctypes
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -97,6 +98,14 @@ def test_header_symbols_are_exported(lib_path):
     for name in declared:
         assert hasattr(lib, name), name
     assert lib.pic_abi_version() == _abi.ABI_VERSION
+    # ... and nothing else of the library's own: every helper has internal linkage.  What the toolchain adds stays: the HIP
+    # compilation-unit id (__hip_cuid_<hash>) and the weak out-of-line copies of libstdc++ templates the host code instantiates
+    # (std::vector<int>::push_back and ::_M_fill_assign, std::vector<char>::_M_fill_assign, std::to_string(int / long / unsigned long),
+    # std::string(const char*, const allocator&), four operator+ on std::string), all mangled _ZNSt... or _ZSt...
+    nm = subprocess.run(["nm", "-D", "--defined-only", lib_path], capture_output=True, text=True, check=True).stdout
+    exported = {line.split()[-1] for line in nm.splitlines() if line.strip()}
+    toolchain = {s for s in exported if s.startswith(("__hip_cuid_", "_ZNSt", "_ZSt"))}
+    assert exported - toolchain == declared, (exported - toolchain) ^ declared
 
 
 def test_no_kernel_spills_registers(lib_path):
