@@ -572,6 +572,41 @@ int pic_tape_kl_cot(pic_handle* h, const double* cot_kl, int mem_kind, int64_t f
 int pic_tape_tangent_kl(pic_handle* h, int K, const double* d_ext, const double* d_actions, const void* d_x0, const void* d_v0,
                         int mem_kind, double* d_hist, void* d_x, void* d_v, double* d_E_mesh, double* d_kl);
 
+/* ---- Fluid moments on the mesh (additive to ABI 5) --------------------------------------------------------------
+ * The density, momentum density and twice the kinetic-energy density of the stored (wrapped) particles on the handle's N_mesh
+ * nodes, with s = n0 L / (N dx) and W the handle's own shape function (CIC or TSC; the cell is the forward's; the weights are
+ * the forward's for float64 particles, and for float32 / fixed32 particles the shape function evaluated in double at the held
+ * position's offset in that cell, because the forward's float32 weights carry up to ulp(L) / dx of cancellation error):
+ *     m0_j = s sum_i W_j(x_i)        m1_j = s sum_i W_j(x_i) v_i        m2_j = s sum_i W_j(x_i) v_i^2
+ * (mean velocity u = m1 / m0, temperature T = m2 / m0 - u^2).  pic_moments fills m [num_envs][3][N_mesh] float64 in mem_kind
+ * memory for every particle format (PIC_HOST waits; PIC_DEVICE is asynchronous on the handle's stream); PIC_ESTATE before
+ * pic_reset and during a staged step.  All three are 64-bit integer sums: m0 in the forward's fixed-point units, so that on a
+ * float64 handle with the fixed-point accumulator it equals pic_get_fields' n of a fresh state bit for bit; m1 and m2 in units
+ * taken from the environment's max |v| < 2^e, 2^(e + b - 61) and 2^(2e + b - 61) with 2^b >= N.  The result therefore does
+ * not depend on blocks_per_env, the schedule, accum_dtype or the environment's place in the batch.  An environment at rest has
+ * m1 = m2 = +0; one with a non-finite velocity has NaN in m1 and m2 (m0 and the other environments are unaffected); with
+ * max |v| >= 2^511, m2 is +inf.  Particles, fields, energies and pic_bad_count are untouched.  N_mesh above 2728 is PIC_EINVAL
+ * (three meshes of 64-bit sums in 64 KB of LDS).  The first call allocates 8 (6 num_envs N_mesh + num_envs) bytes.
+ * pic_moments_vjp: with cot_m [num_envs][3][N_mesh], g_x and g_v [num_envs][N] float64 (either may be NULL) receive the gradient
+ * of sum cot_m . m with respect to the current particles, the almost-everywhere derivative of the CIC weights (as the tape's,
+ * with the unquantised weights): with j, jr the nodes and w_l, w_r the weights of particle i,
+ *     g_x_i = s (slope(c0) + v_i slope(c1) + v_i^2 slope(c2)),       slope(c) = (c[jr] - c[j]) / dx
+ *     g_v_i = s ((w_l c1[j] + w_r c1[jr]) + 2 v_i (w_l c2[j] + w_r c2[jr])).
+ * PIC_EINVAL for float32 / fixed32 particles and for TSC.
+ * pic_tape_moments_cot stores cotangents on the moments of the states of an open tape: cot_m [nsteps][num_envs][3][N_mesh] in
+ * mem_kind memory for rows first_step .. first_step + nsteps - 1, or NULL to clear those rows; row s belongs to the state step s
+ * left, row -1 to the state at the start of the tape.  Rows persist until they are overwritten or cleared.  Every later
+ * pic_tape_backward, pic_tape_backward_feedback and pic_tape_walk_step adds the gradient above, at the replayed state, to the
+ * adjoint state when it reverses a step whose row is set (one more kernel, counted in `launches`), and pic_tape_walk_end (or the
+ * end of a backward) adds row -1 at the first checkpoint; a tape with no row set launches nothing new and its gradients keep
+ * their bits.  The first call that sets a row allocates 8 (max_steps + 1) num_envs 3 N_mesh bytes (rounded up to 256), which
+ * count in pic_tape_info.bytes and against budget_bytes (PIC_ENOMEM, the tape still usable) and are freed by pic_tape_stop.
+ * No open tape: PIC_ESTATE; rows outside [-1, T) or a bad mem_kind: PIC_EINVAL; rows of steps a walk in progress has already
+ * reversed: PIC_ESTATE (the call does not abandon the walk). */
+int pic_moments(pic_handle* h, int mem_kind, double* m);
+int pic_moments_vjp(pic_handle* h, const double* cot_m, int mem_kind, void* g_x, void* g_v);
+int pic_tape_moments_cot(pic_handle* h, const double* cot_m, int mem_kind, int64_t first_step, int64_t nsteps);
+
 int pic_sync(pic_handle* h);
 /* Number of particle positions found non-finite or out of range by the last sweeps (0 = healthy).  Counts the state's
  * particles only: the positions of pic_eval_field / pic_compute_E probes never add to it. */

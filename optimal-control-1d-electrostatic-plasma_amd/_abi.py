@@ -153,6 +153,9 @@ SIGNATURES = {
     "pic_tape_kl_start": [_vp, C.POINTER(PicPhaseSpec)],
     "pic_tape_kl": [_vp, C.c_int, _vp],
     "pic_tape_kl_cot": [_vp, _vp, C.c_int, C.c_int64, C.c_int64],
+    "pic_moments": [_vp, C.c_int, _vp],
+    "pic_moments_vjp": [_vp, _vp, C.c_int, _vp, _vp],
+    "pic_tape_moments_cot": [_vp, _vp, C.c_int, C.c_int64, C.c_int64],
     "pic_set_stream": [_vp, _vp],
     "pic_own_stream": [_vp],
     "pic_schedule": [_vp],
@@ -818,6 +821,21 @@ class Handle:
         """pic_tape_kl_cot: cot_kl an address (int, 0 = NULL: clear the rows) in mem_kind memory."""
         self._chk(self.lib.pic_tape_kl_cot(self._h, _ptr(int(cot_kl)) if cot_kl else None, int(mem_kind), int(first_step),
                                            int(nsteps)))
+
+    # -- fluid moments on the mesh (pic_moments*, DESIGN.md 7k) ---------------------------------------
+    def moments(self, mem_kind, m):
+        """pic_moments into the address m ([num_envs][3][Ng] float64 in mem_kind memory)."""
+        self._chk(self.lib.pic_moments(self._h, int(mem_kind), _ptr(int(m)) if m else None))
+
+    def moments_vjp(self, cot_m, mem_kind, g_x, g_v):
+        """pic_moments_vjp on addresses (int, 0 = NULL) in mem_kind memory."""
+        p = _ptrs(cot_m, g_x, g_v)
+        self._chk(self.lib.pic_moments_vjp(self._h, p[0], int(mem_kind), p[1], p[2]))
+
+    def tape_moments_cot(self, cot_m, mem_kind, first_step, nsteps):
+        """pic_tape_moments_cot: cot_m an address (int, 0 = NULL: clear the rows) in mem_kind memory; first_step -1 = the start."""
+        self._chk(self.lib.pic_tape_moments_cot(self._h, _ptr(int(cot_m)) if cot_m else None, int(mem_kind), int(first_step),
+                                                int(nsteps)))
 
     def stream_probe(self, repeats=10):
         g = C.c_double()

@@ -1,0 +1,199 @@
+// host_moments.h -- included by picstep.hip alone, inside its extern "C" block and ahead of host_tape.h, whose walk calls
+// tape_moments_reverse
+#pragma once
+// ---------------------------------------------------------------------------------------------
+// Fluid moments on the mesh (include/picstep.h: pic_moments*, pic_tape_moments_cot; pic_moments.h)
+// ---------------------------------------------------------------------------------------------
+// the kernels' arguments and the deposit's grid: about 512 workgroups in all and at least 8192 particles each, so that the
+// flush (up to 3 Ng memory-side atomics per workgroup) stays a small share of the pass
+static MomArgs moments_args(const pic_handle* h, dim3& grid) {
+  MomArgs a{};
+  const long long N = h->cfg.N, E = h->cfg.num_envs;
+  a.N = N; a.ld = h->ld; a.Ng = h->cfg.Ng; a.fg = h->fg; a.num_envs = (int)E; a.magic = h->magic;
+  int b = 0;
+  while (((int64_t)1 << b) < N) ++b;
+  a.bitsN = b;
+  a.L = h->cfg.L; a.dx = h->dx; a.scale = h->scale;
+  const long long wpe = std::max(1LL, std::min((512 + E - 1) / E, (N + 8191) / 8192));
+  const long long ntiles = (N + h->vec - 1) / h->vec;
+  a.tiles_per_wg = (ntiles + wpe * BLOCK - 1) / (wpe * BLOCK);
+  grid = dim3((unsigned)((ntiles + a.tiles_per_wg * BLOCK - 1) / (a.tiles_per_wg * BLOCK)), (unsigned)E);
+  return a;
+}
+
+static size_t moments_lds(const pic_handle* h) { return (size_t)3 * (h->cfg.Ng + 2) * sizeof(unsigned long long); }
+
+// the parts of the handle's block: the integer sums [3][env][Ng], the max words [env] (both zero between calls) and the
+// device copy of a result that goes to host memory
+static size_t moments_parts(Carver c, pic_handle* h) {
+  const size_t E = h->cfg.num_envs, mesh3 = 3 * E * h->cfg.Ng;
+  c.take(h->mom_acc, mesh3);
+  c.take(h->mom_max, E);
+  c.take(h->mom_out, mesh3);
+  return c.at;
+}
+
+static int moments_ensure(pic_handle* h, const char* who) {
+  if (h->mom_block) return PIC_OK;
+  if (moments_lds(h) > (size_t)(64 << 10))
+    return fail(h, PIC_EINVAL, std::string(who) + ": N_mesh too large for three LDS meshes of 64-bit sums (at most 2728 cells)");
+  const size_t bytes = moments_parts(Carver{}, h);
+  const int rc = regrow(h, h->mom_block, bytes, (std::string(who) + ": the moments' accumulators do not fit on the device").c_str());
+  if (rc) return rc;
+  moments_parts(Carver{static_cast<char*>(h->mom_block.get())}, h);
+  HIPCHK(h, hipMemsetAsync(h->mom_acc, 0, Carver::upto(h->mom_acc, h->mom_max + h->cfg.num_envs), h->stream));
+  return PIC_OK;
+}
+
+// the three kernels of the moments of the handle's particles into m [env][3][Ng] (device memory), on the handle's stream
+static hipError_t moments_enqueue(pic_handle* h, double* m) {
+  dim3 grid;
+  const MomArgs a = moments_args(h, grid);
+  const size_t lds = moments_lds(h);
+  const bool tsc = h->cfg.interpol == PIC_TSC;
+  with_format(h, [&](auto p) {
+    using P = decltype(p);
+    const typename P::X* x = static_cast<const typename P::X*>(h->x.get());
+    const typename P::V* v = static_cast<const typename P::V*>(h->v);
+    hipLaunchKernelGGL((moments_max_kernel<P>), grid, dim3(BLOCK), 0, h->stream, v, h->mom_max, a);
+    if (tsc)
+      hipLaunchKernelGGL((moments_deposit_kernel<P, PIC_TSC>), grid, dim3(BLOCK), lds, h->stream, x, v,
+                         (const unsigned long long*)h->mom_max, h->mom_acc, a);
+    else
+      hipLaunchKernelGGL((moments_deposit_kernel<P, PIC_CIC>), grid, dim3(BLOCK), lds, h->stream, x, v,
+                         (const unsigned long long*)h->mom_max, h->mom_acc, a);
+  });
+  hipLaunchKernelGGL(moments_finish_kernel, dim3(h->cfg.num_envs), dim3(BLOCK), 0, h->stream, h->mom_acc, h->mom_max, m, a);
+  return hipGetLastError();
+}
+
+int pic_moments(pic_handle* h, int mem_kind, double* m) {
+  const char* who = "pic_moments";
+  if (!h) return PIC_EINVAL;
+  if (int rc = check_mem_kind(h, mem_kind, who)) return rc;
+  if (!m) return fail(h, PIC_EINVAL, std::string(who) + ": m is NULL");
+  if (!h->has_state) return fail(h, PIC_ESTATE, std::string(who) + ": call pic_reset first");
+  if (h->mid_stage) return fail(h, PIC_ESTATE, std::string(who) + ": a staged step is in progress");
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (int rc = moments_ensure(h, who)) return rc;
+  double* out = device_output(m, mem_kind, h->mom_out);
+  hipError_t e = moments_enqueue(h, out);
+  if (e == hipSuccess) e = device_result(h, m, out, (size_t)h->cfg.num_envs * 3 * h->cfg.Ng * sizeof(double));
+  if (e == hipSuccess && mem_kind == PIC_HOST) e = hipStreamSynchronize(h->stream);      // device outputs stay stream-ordered
+  if (e != hipSuccess) return fail(h, PIC_EHIP, std::string(who) + ": " + hipGetErrorString(e));
+  return PIC_OK;
+}
+
+// the gather of a cotangent g [env][3][Ng] (device memory) at the particles x, v [env][ld] into rows of `orow` elements
+// (overwritten, or added to)
+static void moments_vjp_launch(pic_handle* h, bool add, const double* x, const double* v, const double* g, double* ox, double* ov,
+                               long long orow) {
+  dim3 unused;
+  const MomArgs a = moments_args(h, unused);
+  const dim3 grid((unsigned)((h->cfg.N + BLOCK - 1) / BLOCK), (unsigned)h->cfg.num_envs);
+  if (add) hipLaunchKernelGGL(moments_vjp_kernel<true>, grid, dim3(BLOCK), 0, h->stream, x, v, g, a, ox, ov, orow);
+  else hipLaunchKernelGGL(moments_vjp_kernel<false>, grid, dim3(BLOCK), 0, h->stream, x, v, g, a, ox, ov, orow);
+}
+
+int pic_moments_vjp(pic_handle* h, const double* cot_m, int mem_kind, void* g_x, void* g_v) {
+  const char* who = "pic_moments_vjp";
+  if (!h) return PIC_EINVAL;
+  if (int rc = check_mem_kind(h, mem_kind, who)) return rc;
+  if (h->fmt != FMT_F64)
+    return fail(h, PIC_EINVAL, std::string(who) + ": the gradient needs float64 particles with float64 positions (float32 and fixed32 "
+                                                  "are not differentiated)");
+  if (h->cfg.interpol != PIC_CIC)
+    return fail(h, PIC_EINVAL, std::string(who) + ": the gradient needs CIC (the reference's TSC weights jump at cell edges: the "
+                                                  "moments are not differentiable)");
+  if (!cot_m) return fail(h, PIC_EINVAL, std::string(who) + ": cot_m is NULL");
+  if (!h->has_state) return fail(h, PIC_ESTATE, std::string(who) + ": call pic_reset first");
+  if (h->mid_stage) return fail(h, PIC_ESTATE, std::string(who) + ": a staged step is in progress");
+  if (!g_x && !g_v) return PIC_OK;
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  const size_t E = h->cfg.num_envs, N = h->cfg.N, cbytes = E * 3 * h->cfg.Ng * sizeof(double), pbytes = E * N * sizeof(double);
+  DeviceBuf<double> dcot, dgx, dgv;
+  const double* cot = nullptr;
+  const bool host = mem_kind == PIC_HOST;       // host memory goes through device buffers of this call, and so does a null output
+  hipError_t e = hipSuccess;
+  if (host) e = alloc(dcot, cbytes);
+  if (e == hipSuccess) e = device_input(h, cot_m, mem_kind, cbytes, dcot, &cot);
+  if (e == hipSuccess && (host || !g_x)) e = alloc(dgx, pbytes);
+  if (e == hipSuccess && (host || !g_v)) e = alloc(dgv, pbytes);
+  double* gx = g_x && !host ? static_cast<double*>(g_x) : dgx.get();
+  double* gv = g_v && !host ? static_cast<double*>(g_v) : dgv.get();
+  if (e == hipSuccess) {
+    moments_vjp_launch(h, false, (const double*)h->x.get(), (const double*)h->v, cot, gx, gv, (long long)N);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = device_result(h, g_x, gx, pbytes);
+  if (e == hipSuccess) e = device_result(h, g_v, gv, pbytes);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);           // (this call's buffers go away behind it)
+  if (e != hipSuccess) return fail(h, PIC_EHIP, std::string(who) + ": " + hipGetErrorString(e));
+  return PIC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Cotangents on the moments of the states of a tape (hooks: walk_reverse, walk_close)
+// ---------------------------------------------------------------------------------------------
+// the rows [max_steps + 1][env][3][Ng]: row s + 1 is a cotangent on the moments of the state step s left, row 0 on those of
+// the state at the start of the tape
+static size_t tape_moments_parts(Carver c, const pic_handle* h, Tape& t, int64_t max_steps) {
+  c.take(t.mom_cot, (size_t)(max_steps + 1) * h->cfg.num_envs * 3 * h->cfg.Ng);
+  return c.at;
+}
+
+// row s (-1: the start) of the open tape holds a cotangent
+static bool tape_moments_row(const pic_handle* h, int64_t s) {
+  const Tape& t = h->tape;
+  return t.mom_cot && t.mom_flag[(size_t)(s + 1)];
+}
+
+// lambda += the gather of row s at the state x, v [env][ld] it belongs to (walk_reverse: the replayed state step s left;
+// walk_close: the first checkpoint)
+static void tape_moments_reverse(pic_handle* h, int64_t s, const double* x, const double* v, double* lx, double* lv) {
+  Tape& t = h->tape;
+  const double* g = t.mom_cot + (size_t)(s + 1) * h->cfg.num_envs * 3 * h->cfg.Ng;
+  moments_vjp_launch(h, true, x, v, g, lx, lv, (long long)h->ld);
+  ++t.launches;
+}
+
+int pic_tape_moments_cot(pic_handle* h, const double* cot_m, int mem_kind, int64_t first_step, int64_t nsteps) {
+  const char* who = "pic_tape_moments_cot";
+  if (!h) return PIC_EINVAL;
+  Tape& t = h->tape;
+  if (int rc = check_tape_open(h, who)) return rc;
+  if (int rc = check_mem_kind(h, mem_kind, who)) return rc;
+  if (first_step < -1 || nsteps < 0 || first_step > t.steps || nsteps > t.steps - first_step)
+    return fail(h, PIC_EINVAL, std::string(who) + ": rows outside the start (-1) and the " + std::to_string(t.steps) + " steps taped so far");
+  if (nsteps == 0) return PIC_OK;
+  if (t.walk && first_step + nsteps - 1 > t.wnext)
+    return fail(h, PIC_ESTATE, std::string(who) + ": the walk in progress has reversed step " + std::to_string(first_step + nsteps - 1) +
+                                   " already");
+  if (!t.mom_cot) {
+    if (!cot_m) return PIC_OK;                  // (no row was ever set: all are clear)
+    Tape v;                                     // the block's view: the tape's own once the block is there
+    const size_t bytes = tape_moments_parts(Carver{}, h, v, t.max_steps);
+    if (t.budget > 0 && t.bytes + bytes > (size_t)t.budget)
+      return fail(h, PIC_ENOMEM, std::string(who) + ": the moments' cotangents (" + std::to_string(bytes) +
+                                     " bytes) would take the tape past budget_bytes (pic_tape_start)");
+    HIPCHK(h, hipSetDevice(h->cfg.device_id));
+    DeviceBuf<void> block;
+    const int rc = regrow(h, block, bytes, (std::string(who) + ": the moments' cotangents (" + std::to_string(bytes) +
+                                            " bytes) do not fit on the device").c_str());
+    if (rc) return rc;
+    tape_moments_parts(Carver{static_cast<char*>(block.get())}, h, v, t.max_steps);
+    t.mom_block = std::move(block);
+    t.mom_cot = v.mom_cot;
+    t.mom_flag.assign((size_t)t.max_steps + 1, 0);
+    t.bytes += bytes;
+  }
+  if (cot_m) {
+    HIPCHK(h, hipSetDevice(h->cfg.device_id));
+    const size_t row = (size_t)h->cfg.num_envs * 3 * h->cfg.Ng;
+    HIPCHK(h, hipMemcpyAsync(t.mom_cot + (size_t)(first_step + 1) * row, cot_m, (size_t)nsteps * row * sizeof(double),
+                             copy_kind(mem_kind, hipMemcpyHostToDevice), h->stream));
+    if (mem_kind == PIC_HOST) HIPCHK(h, hipStreamSynchronize(h->stream));      // (the caller's rows may go away behind this call)
+  }
+  std::fill(t.mom_flag.begin() + (first_step + 1), t.mom_flag.begin() + (first_step + 1 + nsteps), cot_m ? 1 : 0);
+  return PIC_OK;
+}

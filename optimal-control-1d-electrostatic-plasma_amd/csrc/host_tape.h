@@ -1,5 +1,5 @@
 // host_tape.h -- included by picstep.hip alone, inside its extern "C" block and ahead of advance, which calls tape_record_ext,
-// tape_checkpoint and tape_kl_enqueue
+// tape_checkpoint and tape_kl_enqueue; behind host_moments.h (tape_moments_row, tape_moments_reverse)
 #pragma once
 // ---------------------------------------------------------------------------------------------
 // Differentiable rollouts (include/picstep.h: pic_tape_*; kernels: pic_adjoint.h; hook: advance)
@@ -403,6 +403,10 @@ static int walk_reverse(pic_handle* h, const WalkCot& c, const AdjArgs& a, const
     const int rc = tape_kl_reverse(h, s, xn, xn + part, lx, lv);
     if (rc) return rc;
   }
+  if (tape_moments_row(h, s)) {             // lambda' += the gather of m-bar_s at the replayed state step s left
+    const double* xn = t.seg + (size_t)(i + 1) * 2 * part;
+    tape_moments_reverse(h, s, xn, xn + part, lx, lv);
+  }
   // the field step s left is read by the law of step s + 1 and by the caller's observation: E-bar joins its refresh adjoint
   const double* Ebar = tape_mode_cot(h, s + 1, c.modes, c.mc);
   hipLaunchKernelGGL(adjoint_mesh_kernel, g.mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, nullptr, t.cmax, t.M + (size_t)i * mesh, cot, ge, t.nu, a, E,
@@ -441,6 +445,7 @@ static int walk_close(pic_handle* h, const WalkCot& c, const AdjArgs& a, const W
                        t.lam, a, t.lam + part, c.x, c.v, c.cld);
     ++t.launches;
   }
+  if (tape_moments_row(h, -1)) tape_moments_reverse(h, -1, t.ck, t.ck + part, t.lam, t.lam + part);   // m-bar at the tape start
   t.walk = false;
   HIPCHK(h, hipGetLastError());
   return PIC_OK;

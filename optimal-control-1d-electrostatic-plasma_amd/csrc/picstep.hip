@@ -69,6 +69,7 @@
 #include "pic_adjoint.h"
 #include "pic_tangent.h"
 #include "pic_phase.h"
+#include "pic_moments.h"
 
 
 // ---------------------------------------------------------------------------------------------
@@ -226,6 +227,11 @@ struct Tape {
   DeviceBuf<void> tkl_block;
   double* tkl_ones = nullptr;         // [env] unit cotangents: the finishing kernel's g is then dKL~/df
   double* tkl_part = nullptr;         // [kMaxTangents][env][chunks] the chunks' sums of the step at hand
+  // cotangents on the fluid moments of the tape's states (pic_tape_moments_cot): one block allocated by the first
+  // call that sets a row, counts in `bytes`
+  DeviceBuf<void> mom_block;
+  double* mom_cot = nullptr;          // [max_steps + 1][env][3][Ng]: row s + 1 for the state step s left, row 0 for the tape start
+  std::vector<char> mom_flag;         // [max_steps + 1] per row: mom_cot holds a cotangent there
 };
 
 }  // namespace
@@ -297,6 +303,10 @@ struct __attribute__((visibility("hidden"))) pic_handle : LaunchPlan {      // t
   PinnedBuf<void> h_part;         // pinned host staging for x | v of states up to 64 MB (from pic_create on up to 4 MB, else on first use)
   bool h_part_refused = false;    // ... could not be had: do not ask again
   PinnedBuf<double> h_fields;     // pinned host staging for n | E_mesh | phi (meshes up to 256 KB each in total), or null
+  DeviceBuf<void> mom_block;      // pic_moments, allocated by its first call; mom_acc .. mom_out are views into it
+  unsigned long long* mom_acc = nullptr;   // [3][env][Ng] integer sums of the three moments, zero between calls
+  unsigned long long* mom_max = nullptr;   // [env] bit pattern of max |v|, zero between calls
+  double* mom_out = nullptr;               // [env][3][Ng] the device copy of a result that goes to host memory
   DeviceBuf<unsigned long long> bad;
   unsigned long long* probe_bad = nullptr;   // view: bad + 1, where the probes count their non-finite positions (never read: pic_bad_count
                                              // describes the state's particles, and a probe's positions are not among them)
@@ -1260,6 +1270,7 @@ static int64_t records_ahead(const pic_handle* h, int64_t nsteps) {
 
 // the host side of the differentiable rollouts (advance calls tape_record_ext, tape_checkpoint and tape_kl_enqueue)
 #include "host_phase.h"
+#include "host_moments.h"
 #include "host_tape.h"
 #include "host_tangent.h"
 

@@ -44,6 +44,7 @@ class BatchedPIC:
         self.max_mode = 0                    # (no actuator yet: set_actuator)
         self._torch_stream = None            # (the handle runs on its own stream: use_torch_stream)
         self._tape_kl = False                # (the open tape records the smoothed KL)
+        self._tape_moments = False           # (the open tape has held cotangents on the moments)
         self._tape_serial = self._walk_serial = 0       # (the tape env.grad opened last, the walk in progress)
 
     # reset(x0, v0): x0, v0 are [num_envs, N] with any velocity perturbation already applied
@@ -375,6 +376,62 @@ class BatchedPIC:
         self._h.phase_kl_smooth_jvp(nx, nv, vmin, vmax, fa, per, mem.kind, K, mem.addr(tx), mem.addr(tv), mem.kind, mem.addr(out))
         return out if batched else out[0]
 
+    # -- fluid moments on the mesh (pic_moments*) ----------------------------------------
+    def moments(self, on_device: bool = False):
+        """The fluid moments of the current particles, [num_envs, 3, N_mesh] float64: m0 = s sum W (the density), m1 = s sum W v
+        (momentum density), m2 = s sum W v^2 (twice the kinetic-energy density), s = n0 L / (N dx), W the environment's own shape
+        function.  Every particle format; bitwise reproducible, whatever blocks_per_env, the schedule, accum_dtype or the
+        batch.  NumPy, or a float64 CUDA tensor with on_device."""
+        mem = Mem.of(self, force_device=on_device)
+        out = mem.empty((self.num_envs, 3, self.N_mesh))
+        mem.enter()
+        self._h.moments(mem.kind, mem.addr(out))
+        mem.leave(self._h)
+        return out
+
+    def moments_torch(self):
+        """`moments` as a float64 CUDA tensor on torch's current stream: no host synchronisation on a stream shared with torch
+        (use_torch_stream), like modes_torch."""
+        return self.moments(on_device=True)
+
+    def fluid(self):
+        """(n, u, T), each [num_envs, N_mesh]: the density m0, the mean velocity u = m1 / m0 and the temperature
+        T = m2 / m0 - u^2 of `moments`; u = T = 0 on a node without particles."""
+        m = self.moments()
+        n = m[:, 0]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            u = np.where(n != 0, m[:, 1] / n, 0.0)
+            T = np.where(n != 0, m[:, 2] / n - u * u, 0.0)
+        return n, u, T
+
+    def moments_vjp(self, g):
+        """Gradient of sum g . moments (g [num_envs, 3, N_mesh]) with respect to the current particles -> (g_x, g_v)
+        [num_envs, N]: the almost-everywhere derivative of the CIC weights (float64 particles and CIC only).  NumPy, or float64
+        CUDA tensors if g is one."""
+        mem = Mem.of(self, g)
+        c = mem.f64(g)
+        if tuple(c.shape) != (self.num_envs, 3, self.N_mesh):
+            raise ValueError(f"g must be [num_envs, 3, N_mesh], not {list(c.shape)}")
+        gx, gv = mem.empty((self.num_envs, self.N)), mem.empty((self.num_envs, self.N))
+        mem.enter()
+        self._h.moments_vjp(mem.addr(c), mem.kind, mem.addr(gx), mem.addr(gv))
+        return gx, gv
+
+    def _set_moments_cot(self, d_moments, T, mem):
+        """The moments' cotangents of a backward onto the tape: d_moments [T, num_envs, 3, N_mesh] (row t on the state step t
+        left), or None to clear every row, the start's included.  Returns what must stay alive until the backward is done."""
+        if d_moments is None:
+            if self._tape_moments:
+                self._h.tape_moments_cot(0, _abi.PIC_HOST, -1, T + 1)
+            return None
+        d = mem.f64(d_moments, (T, self.num_envs, 3, self.N_mesh))
+        mem.enter()
+        self._tape_moments = True
+        self._h.tape_moments_cot(0, _abi.PIC_HOST, -1, 1)
+        if T > 0:
+            self._h.tape_moments_cot(mem.addr(d), mem.kind, 0, T)
+        return d
+
     # -- rollout recorder (include/picstep.h: pic_record_*) ----------------------------------------
     def start_recording(self, stride: int = 1, modes: Optional[int] = None, x_bins: int = 0, v_bins: int = 0, phase_bins=None,
                         vmin: float = -25.0, vmax: float = 25.0, feq=None, capacity: int = 4096, phase_dx: float = 0.0,
@@ -466,7 +523,7 @@ class BatchedPIC:
         [nx, nv] or [num_envs, nx, nv]; the tape keeps a copy.  If the KL's memory does not fit (PicError), the tape stays open
         without one."""
         self._h.tape_start(max_steps, checkpoint_every, budget_bytes)
-        self._tape_kl = False
+        self._tape_kl = self._tape_moments = False
         if kl is not None:
             kl = dict(kl)
             feq, vmin, vmax = kl.pop("feq"), float(kl.pop("vmin", -25.0)), float(kl.pop("vmax", 25.0))
@@ -478,7 +535,7 @@ class BatchedPIC:
 
     def stop_tape(self):
         self._h.tape_stop()
-        self._tape_kl = False
+        self._tape_kl = self._tape_moments = False
 
     def tape_kl(self, on_device: bool = False):
         """The smoothed KL after every step taped so far, [T, num_envs] (a tape opened with kl=...): each row is bit for bit
@@ -537,7 +594,7 @@ class BatchedPIC:
                 self.stop_tape()
         return cm()
 
-    def backward(self, d_KE=None, d_PE=None, d_PE_reward=None, d_x=None, d_v=None, d_modes=None, d_KL=None):
+    def backward(self, d_KE=None, d_PE=None, d_PE_reward=None, d_x=None, d_v=None, d_modes=None, d_KL=None, d_moments=None):
         """Vector-Jacobian product of the taped steps: cotangents d_KE, d_PE, d_PE_reward [T, num_envs] of the energy traces
         (step_history's) and d_x, d_v [num_envs, N] of the final particles (each None = 0).  Returns a dict: "ext" [T, num_envs,
         N_mesh] (gradient with respect to every step's external field), "actions" [T, num_envs, 2*max_mode] (= B^T ext; with an
@@ -549,10 +606,12 @@ class BatchedPIC:
         [T, num_envs, 2*max_mode] (the taped m_t, zero on other steps) and "gain": sum over the call's steps of
         actions_t modes_t^T, [num_envs, 2M, 2M] for one gain-law call, a list of them for several.
         A tape opened with kl=...: d_KL [T, num_envs] are cotangents of the KL trace (`tape_kl`); None = 0.  They
-        are set on the tape (or all cleared) before the reverse pass, so a backward is a function of its arguments alone."""
+        are set on the tape (or all cleared) before the reverse pass, so a backward is a function of its arguments alone.
+        d_moments [T, num_envs, 3, N_mesh]: row t is a cotangent on `moments` of the state step t left; None = 0.
+        Set or cleared the same way (pic_tape_moments_cot)."""
         T, E, N, n = self._h.tape_stats()["steps"], self.num_envs, self.N, 2 * self.max_mode
-        mem = Mem.of(self, d_KE, d_PE, d_PE_reward, d_x, d_v, d_modes, d_KL)
-        keep_kl = self._set_kl_cot(d_KL, T, mem)
+        mem = Mem.of(self, d_KE, d_PE, d_PE_reward, d_x, d_v, d_modes, d_KL, d_moments)
+        keep_kl = self._set_kl_cot(d_KL, T, mem), self._set_moments_cot(d_moments, T, mem)
         calls = self._h.tape_law_calls()
         if d_modes is not None and not calls:
             raise ValueError("backward: d_modes needs steps of step_feedback_gain on the tape")
@@ -646,23 +705,32 @@ class TapeWalk:
         self._serial = env._walk_serial
         # a tape with a KL: the step each call reverses, for its row of KL cotangents
         self._kl_next = env._h.tape_stats()["steps"] - 1 if env._tape_kl else None
+        self._steps, self._done = None, 0                      # the tape's steps (read when first needed), the steps reversed so far
+        if env._tape_moments:                                  # rows an earlier backward or walk left: this walk sets its own
+            env._h.tape_moments_cot(0, _abi.PIC_HOST, -1, self._tape_steps() + 1)
+
+    def _tape_steps(self):
+        if self._steps is None:
+            self._steps = self.env._h.tape_stats()["steps"]
+        return self._steps
 
     def _live(self, who):
         if self.env._walk_serial != self._serial:
             raise _abi.PicError(f"walk.{who}: another walk or backward has replaced this one")
 
-    def step(self, d_energies=None, d_x=None, d_v=None, d_modes=None, d_kl=None):
+    def step(self, d_energies=None, d_x=None, d_v=None, d_modes=None, d_kl=None, d_moments=None):
         """Reverse the next step t: d_energies [3, num_envs] (its KE, PE, PE_reward), d_x, d_v [num_envs, N] on the state it
         left, d_modes [num_envs, 2*M_o] on the modes of the field it left, d_kl [num_envs] on its smoothed KL (a tape opened
-        with kl=...; None = 0).  Returns (t, g_ext [num_envs, N_mesh], g_actions [num_envs, 2*max_mode] or None without an
-        actuator)."""
+        with kl=...; None = 0), d_moments [num_envs, 3, N_mesh] on the moments of the state it left (None = 0).  Returns
+        (t, g_ext [num_envs, N_mesh], g_actions [num_envs, 2*max_mode] or None without an actuator)."""
         self._live("step")
         env, E = self.env, self.env.num_envs
         if d_kl is not None and self._kl_next is None:
             raise ValueError("walk.step: d_kl needs a tape opened with kl=... (start_tape)")
-        mem = Mem.of(env, d_energies, d_x, d_v, d_modes, d_kl, force_device=self.on_device)
+        mem = Mem.of(env, d_energies, d_x, d_v, d_modes, d_kl, d_moments, force_device=self.on_device)
         ce, cx, cv = mem.f64(d_energies, (3, E)), mem.f64(d_x, (E, env.N)), mem.f64(d_v, (E, env.N))
         cm, ck = mem.f64(d_modes, (E, 2 * self.obs_modes)), mem.f64(d_kl, (E,))
+        cf = mem.f64(d_moments, (E, 3, env.N_mesh))
         g_ext = mem.out((E, env.N_mesh))
         g_act = mem.out((E, 2 * env.max_mode)) if env.max_mode > 0 else None
         addr = mem.addr
@@ -670,20 +738,29 @@ class TapeWalk:
         if self._kl_next is not None and self._kl_next >= 0:
             env._h.tape_kl_cot(addr(ck), _abi.PIC_HOST if ck is None else mem.kind, self._kl_next, 1)
             self._kl_next -= 1
+        if cf is not None:
+            env._tape_moments = True
+            env._h.tape_moments_cot(addr(cf), mem.kind, self._tape_steps() - 1 - self._done, 1)
+        self._done += 1
         t = env._h.tape_walk_step(addr(ce), addr(cx), addr(cv), addr(cm), mem.kind, addr(g_ext), addr(g_act))
         mem.leave(env._h)                            # (the cotangents above are alive until here)
         return t, g_ext, g_act
 
-    def end(self, d_x0=None, d_v0=None, d_modes0=None):
-        """After all steps: cotangents on the tape's starting state and on the modes of the field there; returns (g_x0, g_v0)
-        [num_envs, N].  Raises PicError if a replay of the walk differed from the taped forward."""
+    def end(self, d_x0=None, d_v0=None, d_modes0=None, d_moments0=None):
+        """After all steps: cotangents on the tape's starting state, on the modes of the field there and on its moments
+        (d_moments0 [num_envs, 3, N_mesh]); returns (g_x0, g_v0) [num_envs, N].  Raises PicError if a replay of the walk differed
+        from the taped forward."""
         self._live("end")
         env, E = self.env, self.env.num_envs
-        mem = Mem.of(env, d_x0, d_v0, d_modes0, force_device=self.on_device)
+        mem = Mem.of(env, d_x0, d_v0, d_modes0, d_moments0, force_device=self.on_device)
         cx, cv, cm = mem.f64(d_x0, (E, env.N)), mem.f64(d_v0, (E, env.N)), mem.f64(d_modes0, (E, 2 * self.obs_modes))
+        cf = mem.f64(d_moments0, (E, 3, env.N_mesh))
         g_x0, g_v0 = mem.out((E, env.N)), mem.out((E, env.N))
         addr = mem.addr
         mem.enter()
+        if cf is not None:
+            env._tape_moments = True
+            env._h.tape_moments_cot(addr(cf), mem.kind, -1, 1)
         env._h.tape_walk_end(addr(cx), addr(cv), addr(cm), mem.kind, addr(g_x0), addr(g_v0))
         if mem.on_device:
             env._check_replay("walk.end", "gradient")

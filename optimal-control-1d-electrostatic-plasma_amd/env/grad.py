@@ -12,6 +12,9 @@ the gradient from the device's adjoint (pic_tape_backward) and for
     KE, PE, PE_reward, actions, obs = rollout_policy(env, policy, T)   # policy: any torch callable, modes -> actions
     (PE_reward.sum() + lam * (actions ** 2).sum() * L / 4).backward()   # fills the policy's .grad through the closed loop (7e)
 
+rollout_policy(..., observe="moments") hands the policy the fluid moments on the mesh, [num_envs, 3, N_mesh], instead of the modes
+(DESIGN.md 7k); the backward sets the policy's cotangent on them through pic_tape_moments_cot.
+
 Every entry takes kl=dict(feq=..., vmin=..., vmax=...) (BatchedPIC.start_tape): the smoothed phase-space KL after every step,
 [T, num_envs], is then appended as one more differentiable output, so that the reference's whole cost is:
 
@@ -154,12 +157,16 @@ class _PolicyWalk:
         """Cotangents of an observation -> walk arguments."""
         if self.observe == "modes":
             return {"d_modes": g_obs[0]}
+        if self.observe == "moments":
+            return {"d_moments": g_obs[0]}
         return {"d_x": g_obs[0], "d_v": g_obs[1]}
 
 
 def _observe(env, observe, obs_modes):
     if observe == "modes":
         return (env.modes_torch(obs_modes),)
+    if observe == "moments":
+        return (env.moments_torch(),)
     v = env._ordered_views()
     return tuple(v[k].clone(memory_format=torch.contiguous_format) for k in ("x", "v"))
 
@@ -214,7 +221,9 @@ def rollout_policy(env, policy, T, observe="modes", obs_modes=None, checkpoint_e
     observation o_t goes through `policy(o_t)` to the actions a_t [num_envs, 2*max_mode] (any float dtype: cast to float64), which
     step_actions_torch applies.  observe="modes": o_t = the modes of the field, float64 [num_envs, 2*M_o] (Re E_1..E_Mo then
     Im, obs_modes M_o defaulting to max_mode); observe="state": o_t = (x, v), a tuple of float64 copies [num_envs, N] of the
-    particles (torch.cat(o_t, 1) is the reference actor's input).
+    particles (torch.cat(o_t, 1) is the reference actor's input); observe="moments": o_t = the fluid moments on the mesh, float64
+    [num_envs, 3, N_mesh] (BatchedPIC.moments: density, momentum density, twice the kinetic-energy density; the policy derives
+    u = m1 / m0 and T = m2 / m0 - u^2 itself, where autograd sees it).
     Runs on a fresh tape; returns KE, PE, PE_reward [T, num_envs], actions [T, num_envs, 2*max_mode] and the observations
     o_0..o_T (a list of T + 1), all differentiable with respect to the policy's parameters (and whatever else it closes over):
     the backward walks the tape step by step (pic_tape_walk_*) and puts the policy's own vector-Jacobian product
@@ -222,8 +231,8 @@ def rollout_policy(env, policy, T, observe="modes", obs_modes=None, checkpoint_e
     every step, [T, num_envs], follows as a sixth differentiable output (reading each step's value waits for the step)."""
     if env.max_mode == 0:
         raise PicError("rollout_policy: the environment has no actuator (set_actuator)")
-    if observe not in ("modes", "state"):
-        raise ValueError('observe must be "modes" or "state"')
+    if observe not in ("modes", "state", "moments"):
+        raise ValueError('observe must be "modes", "state" or "moments"')
     T = int(T)
     if T < 1:
         raise ValueError("need T >= 1")
@@ -234,7 +243,7 @@ def rollout_policy(env, policy, T, observe="modes", obs_modes=None, checkpoint_e
     pw = _PolicyWalk(env, T, observe, mo, serial, kl is not None)
     anchor = torch.zeros(0, dtype=torch.float64, device=f"cuda:{env.device}", requires_grad=True)
     out = _PolicyStart.apply(anchor, pw)
-    token, o = out[0], (out[1] if observe == "modes" else tuple(out[1:]))
+    token, o = out[0], (tuple(out[1:]) if observe == "state" else out[1])
     obs = [o]
     ke, pe, per, acts, kls = [], [], [], [], []
     n = 2 * env.max_mode
@@ -244,7 +253,7 @@ def rollout_policy(env, policy, T, observe="modes", obs_modes=None, checkpoint_e
         if tuple(a.shape) != (env.num_envs, n):
             raise ValueError(f"the policy must return actions [{env.num_envs}, {n}], not {tuple(a.shape)}")
         out = _PolicyStep.apply(token, a, pw, t)
-        token, o = out[0], (out[k0] if observe == "modes" else tuple(out[k0:]))
+        token, o = out[0], (tuple(out[k0:]) if observe == "state" else out[k0])
         ke.append(out[1])
         pe.append(out[2])
         per.append(out[3])

@@ -145,6 +145,13 @@ class PIC:
     def phi_mesh(self):
         return None if self._fields_hidden else self._fields()["phi_mesh"]
 
+    def fluid_moments(self):
+        """The fluid moments of the current particles on the mesh (pic_moments): three [N_mesh] arrays, the
+        density sum W, the momentum density sum W v and twice the kinetic-energy density sum W v^2 (each times n0 L / (N dx))."""
+        m = np.empty((1, 3, self.N_mesh))
+        self._ensure_handle().moments(_abi.PIC_HOST, m.ctypes.data)
+        return m[0, 0], m[0, 1], m[0, 2]
+
     @property
     def E(self):
         if self._fields_hidden:
