@@ -607,6 +607,43 @@ int pic_moments(pic_handle* h, int mem_kind, double* m);
 int pic_moments_vjp(pic_handle* h, const double* cot_m, int mem_kind, void* g_x, void* g_v);
 int pic_tape_moments_cot(pic_handle* h, const double* cot_m, int mem_kind, int64_t first_step, int64_t nsteps);
 
+/* ---- Forward mode of the fluid moments (additive to ABI 5) -------------------------------------------------------
+ * pic_moments_jvp: the directional derivative of pic_moments along K (1..8) tangents of the current particles, d_x and d_v
+ * [K][num_envs][N] float64 in mem_kind memory (either may be NULL: 0), into d_m [K][num_envs][3][N_mesh].  float64 particles and
+ * CIC only (PIC_EINVAL otherwise, and for N_mesh above 2728); PIC_ESTATE before pic_reset and during a staged step.  The
+ * derivative is pic_moments_vjp's, transposed term by term: with iota = d_x_i / dx, particle i adds to its nodes j and jr
+ *     dm0:  -iota                          +iota
+ *     dm1:  w_l d_v_i - iota v_i           w_r d_v_i + iota v_i
+ *     dm2:  2 w_l v_i d_v_i - iota v_i^2   2 w_r v_i d_v_i + iota v_i^2
+ * times s, so that sum c . pic_moments_jvp(u) = pic_moments_vjp(c) . u, sum_j dm0_j = 0 (exactly: both halves are one rounded
+ * integer) and sum_j dm2_j N dx / (2 n0 L) = sum_i v_i d_v_i.  Every term is a 64-bit integer in the unit 2^(e + b - 61), 2^b >= N,
+ * where 2^e exceeds the largest bound |iota|, |d_v| + |iota v|, 2 |v d_v| + |iota| v^2 on one term of that moment, direction and
+ * environment: the result is bitwise reproducible, K directions in one call equal K calls, and nothing depends on blocks_per_env,
+ * the schedule or the environment's place in the batch.  A moment whose terms are all zero is +0; a non-finite tangent or velocity
+ * gives NaN in the moments it reaches, of that direction and environment only.  The call allocates its working memory
+ * (8 (3 K num_envs N_mesh + 3 K num_envs) bytes, plus device copies of host arrays) and waits for the stream before it lets go
+ * of it; the kernels run on the handle's stream.  Particles, fields, energies, pic_moments' own accumulators and the tape are
+ * untouched.
+ * pic_tape_moments_start turns on a trace of the moments on an open tape that holds no step yet (PIC_ESTATE otherwise, and for a
+ * second start): behind every taped step the three kernels of pic_moments write row t of [max_steps][num_envs][3][N_mesh], so row
+ * t is bit for bit what pic_moments returns after step t.  Like a tape with a KL, such a tape runs its steps one launch at a time;
+ * the steps keep their bits.  The trace takes 8 max_steps num_envs 3 N_mesh bytes (rounded up to 256), which count in
+ * pic_tape_info.bytes and against budget_bytes (PIC_ENOMEM, the tape still usable without a trace) and are freed by
+ * pic_tape_stop.  pic_tape_moments copies the rows of the steps taped so far to m in mem_kind memory (PIC_HOST waits).
+ * pic_tape_tangent_moments is pic_tape_tangent_kl with d_moments [K][T][num_envs][3][N_mesh]: d_moments[k][t] = pic_moments_jvp
+ * of the state step t left along direction k's tangent of that state.  d_moments = NULL is pic_tape_tangent_kl itself.  It needs
+ * no trace on the tape.  Every step costs 3 more kernels, counted in `launches` (11 + 3 per step; + 4 with d_kl), behind the third
+ * sub-stage next to the KL's.  All other outputs keep their bits, and d_moments shares their guarantees (K, checkpoint interval,
+ * schedule, batch).  The first call with d_moments allocates, each part rounded up to 256 bytes,
+ *     8 (24 num_envs N_mesh  +  24 num_envs)   bytes
+ * (the integer sums and max words of 8 directions), which count in `bytes` and against budget_bytes and are freed by
+ * pic_tape_stop.  Tapes with steps of pic_step_feedback_gain stay refused. */
+int pic_moments_jvp(pic_handle* h, int K, const void* d_x, const void* d_v, int mem_kind, double* d_m);
+int pic_tape_moments_start(pic_handle* h);
+int pic_tape_moments(pic_handle* h, int mem_kind, double* m);
+int pic_tape_tangent_moments(pic_handle* h, int K, const double* d_ext, const double* d_actions, const void* d_x0, const void* d_v0,
+                             int mem_kind, double* d_hist, void* d_x, void* d_v, double* d_E_mesh, double* d_kl, double* d_moments);
+
 int pic_sync(pic_handle* h);
 /* Number of particle positions found non-finite or out of range by the last sweeps (0 = healthy).  Counts the state's
  * particles only: the positions of pic_eval_field / pic_compute_E probes never add to it. */

@@ -156,6 +156,10 @@ SIGNATURES = {
     "pic_moments": [_vp, C.c_int, _vp],
     "pic_moments_vjp": [_vp, _vp, C.c_int, _vp, _vp],
     "pic_tape_moments_cot": [_vp, _vp, C.c_int, C.c_int64, C.c_int64],
+    "pic_moments_jvp": [_vp, C.c_int, _vp, _vp, C.c_int, _vp],
+    "pic_tape_moments_start": [_vp],
+    "pic_tape_moments": [_vp, C.c_int, _vp],
+    "pic_tape_tangent_moments": [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp],
     "pic_set_stream": [_vp, _vp],
     "pic_own_stream": [_vp],
     "pic_schedule": [_vp],
@@ -798,9 +802,12 @@ class Handle:
         """pic_tape_tangent on device pointers (int, 0 = NULL); asynchronous on the handle's stream."""
         self._tape_tangent(PIC_DEVICE, K, d_ext, d_actions, d_x0, d_v0, hist, x, v, E_mesh)
 
-    def _tape_tangent(self, mem_kind, K, d_ext, d_actions, d_x0, d_v0, hist, x, v, E_mesh, kl=None):
+    def _tape_tangent(self, mem_kind, K, d_ext, d_actions, d_x0, d_v0, hist, x, v, E_mesh, kl=None, moments=None):
         """pic_tape_tangent on addresses (int, 0 = NULL) in mem_kind memory; kl: None, or the address of d_kl (an address,
-        0 = NULL, makes the call pic_tape_tangent_kl)."""
+        0 = NULL, makes the call pic_tape_tangent_kl); moments: None, or the address of d_moments (an address makes the call
+        pic_tape_tangent_moments)."""
+        if moments is not None:
+            return self.tape_tangent_moments(mem_kind, K, d_ext, d_actions, d_x0, d_v0, hist, x, v, E_mesh, kl or 0, moments)
         p = _ptrs(d_ext, d_actions, d_x0, d_v0, hist, x, v, E_mesh)
         if kl is None:
             self._chk(self.lib.pic_tape_tangent(self._h, int(K), p[0], p[1], p[2], p[3], int(mem_kind), p[4], p[5], p[6], p[7]))
@@ -836,6 +843,25 @@ class Handle:
         """pic_tape_moments_cot: cot_m an address (int, 0 = NULL: clear the rows) in mem_kind memory; first_step -1 = the start."""
         self._chk(self.lib.pic_tape_moments_cot(self._h, _ptr(int(cot_m)) if cot_m else None, int(mem_kind), int(first_step),
                                                 int(nsteps)))
+
+    # -- forward mode of the moments and their trace on a tape (DESIGN.md 7l) ---------------------------
+    def moments_jvp(self, K, d_x, d_v, mem_kind, d_m):
+        """pic_moments_jvp on addresses (int, 0 = NULL) in mem_kind memory."""
+        p = _ptrs(d_x, d_v, d_m)
+        self._chk(self.lib.pic_moments_jvp(self._h, int(K), p[0], p[1], int(mem_kind), p[2]))
+
+    def tape_moments_start(self):
+        """pic_tape_moments_start: the moments of every taped step, on an open tape before its first step."""
+        self._chk(self.lib.pic_tape_moments_start(self._h))
+
+    def tape_moments(self, mem_kind, m):
+        """pic_tape_moments into the address m ([T][num_envs][3][Ng] float64 in mem_kind memory)."""
+        self._chk(self.lib.pic_tape_moments(self._h, int(mem_kind), _ptr(int(m)) if m else None))
+
+    def tape_tangent_moments(self, mem_kind, K, d_ext, d_actions, d_x0, d_v0, hist, x, v, E_mesh, kl, moments):
+        """pic_tape_tangent_moments on addresses (int, 0 = NULL) in mem_kind memory."""
+        p = _ptrs(d_ext, d_actions, d_x0, d_v0, hist, x, v, E_mesh, kl, moments)
+        self._chk(self.lib.pic_tape_tangent_moments(self._h, int(K), p[0], p[1], p[2], p[3], int(mem_kind), *p[4:]))
 
     def stream_probe(self, repeats=10):
         g = C.c_double()

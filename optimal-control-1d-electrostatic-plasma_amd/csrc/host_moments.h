@@ -197,3 +197,145 @@ int pic_tape_moments_cot(pic_handle* h, const double* cot_m, int mem_kind, int64
   std::fill(t.mom_flag.begin() + (first_step + 1), t.mom_flag.begin() + (first_step + 1 + nsteps), cot_m ? 1 : 0);
   return PIC_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Forward mode of the moments (include/picstep.h: pic_moments_jvp, pic_tape_tangent_moments; pic_moments.h)
+// ---------------------------------------------------------------------------------------------
+// directions a deposit workgroup holds: three LDS meshes of Ng + 1 64-bit words each, within 64 KB (0: the mesh does not fit)
+static int moments_jvp_kd(const pic_handle* h, int K) {
+  return std::min<int>(K, (int)((size_t)(64 << 10) / ((size_t)3 * (h->cfg.Ng + 1) * sizeof(unsigned long long))));
+}
+
+// what pic_moments_jvp and the tape's tangent refuse alike
+static int moments_jvp_check(pic_handle* h, const std::string& who) {
+  if (h->fmt != FMT_F64)
+    return fail(h, PIC_EINVAL, who + ": the tangent needs float64 particles with float64 positions (float32 and fixed32 are not "
+                                     "differentiated)");
+  if (h->cfg.interpol != PIC_CIC)
+    return fail(h, PIC_EINVAL, who + ": the tangent needs CIC (the reference's TSC weights jump at cell edges: the moments are "
+                                     "not differentiable)");
+  if (moments_lds(h) > (size_t)(64 << 10))
+    return fail(h, PIC_EINVAL, who + ": N_mesh too large for three LDS meshes of 64-bit sums (at most 2728 cells)");
+  return PIC_OK;
+}
+
+// the parts of the forward mode's working memory for kc directions: the integer sums [3][kc][env][Ng] and the max words
+// [3][kc][env] (zero between uses)
+static size_t moments_jvp_parts(Carver c, const pic_handle* h, int kc, MomJvpArgs& j) {
+  const size_t E = h->cfg.num_envs;
+  c.take(j.acc, (size_t)3 * kc * E * h->cfg.Ng);
+  c.take(j.umax, (size_t)3 * kc * E);
+  return c.at;
+}
+
+// the three kernels: the moments' tangents at the particles x, v [env][ld] along the K directions of `j` (dx, dv, dstride, erow,
+// acc, umax set by the caller) into out[d * out_dstride + (env 3 + m) Ng + node] (device memory), on the handle's stream
+constexpr int kMomentsJvpLaunches = 3;
+static hipError_t moments_jvp_enqueue(pic_handle* h, const double* x, const double* v, MomJvpArgs j, int K, double* out,
+                                      long long out_dstride) {
+  dim3 grid;
+  const MomArgs a = moments_args(h, grid);
+  j.K = K; j.kd = moments_jvp_kd(h, K);
+  const dim3 dgrid(grid.x, grid.y, (unsigned)((K + j.kd - 1) / j.kd));
+  const size_t lds = (size_t)j.kd * 3 * (h->cfg.Ng + 1) * sizeof(unsigned long long);
+  if (K == 1) hipLaunchKernelGGL(moments_jvp_max_kernel<1>, grid, dim3(BLOCK), 0, h->stream, v, a, j);
+  else if (K <= 4) hipLaunchKernelGGL(moments_jvp_max_kernel<4>, grid, dim3(BLOCK), 0, h->stream, v, a, j);
+  else hipLaunchKernelGGL(moments_jvp_max_kernel<8>, grid, dim3(BLOCK), 0, h->stream, v, a, j);
+  if (j.kd == 1) hipLaunchKernelGGL(moments_jvp_deposit_kernel<1>, dgrid, dim3(BLOCK), lds, h->stream, x, v, a, j);
+  else if (j.kd <= 4) hipLaunchKernelGGL(moments_jvp_deposit_kernel<4>, dgrid, dim3(BLOCK), lds, h->stream, x, v, a, j);
+  else hipLaunchKernelGGL(moments_jvp_deposit_kernel<8>, dgrid, dim3(BLOCK), lds, h->stream, x, v, a, j);
+  hipLaunchKernelGGL(moments_jvp_finish_kernel, dim3(h->cfg.num_envs, K), dim3(BLOCK), 0, h->stream, a, j, out, out_dstride);
+  return hipGetLastError();
+}
+
+int pic_moments_jvp(pic_handle* h, int K, const void* d_x, const void* d_v, int mem_kind, double* d_m) {
+  const char* who = "pic_moments_jvp";
+  if (!h) return PIC_EINVAL;
+  if (int rc = check_mem_kind(h, mem_kind, who)) return rc;
+  if (int rc = moments_jvp_check(h, who)) return rc;
+  if (K < 1 || K > kMaxTangents) return fail(h, PIC_EINVAL, std::string(who) + ": need 1 <= K <= " + std::to_string(kMaxTangents));
+  if (!d_m) return fail(h, PIC_EINVAL, std::string(who) + ": d_m is NULL");
+  if (!h->has_state) return fail(h, PIC_ESTATE, std::string(who) + ": call pic_reset first");
+  if (h->mid_stage) return fail(h, PIC_ESTATE, std::string(who) + ": a staged step is in progress");
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  const size_t E = h->cfg.num_envs, N = h->cfg.N, Ng = h->cfg.Ng;
+  const size_t pbytes = (size_t)K * E * N * sizeof(double), obytes = (size_t)K * E * 3 * Ng * sizeof(double);
+  MomJvpArgs j{};
+  DeviceBuf<void> work;
+  DeviceBuf<double> ddx, ddv, dout;
+  const double *tx = nullptr, *tv = nullptr;
+  const bool host = mem_kind == PIC_HOST;       // host memory goes through device buffers of this call
+  const size_t wbytes = moments_jvp_parts(Carver{}, h, K, j);
+  hipError_t e = alloc_zeroed(work, wbytes, h->stream);
+  if (e == hipSuccess) moments_jvp_parts(Carver{static_cast<char*>(work.get())}, h, K, j);
+  if (e == hipSuccess && host && d_x) e = alloc(ddx, pbytes);
+  if (e == hipSuccess && host && d_v) e = alloc(ddv, pbytes);
+  if (e == hipSuccess) e = device_input(h, static_cast<const double*>(d_x), mem_kind, pbytes, ddx, &tx);
+  if (e == hipSuccess) e = device_input(h, static_cast<const double*>(d_v), mem_kind, pbytes, ddv, &tv);
+  if (e == hipSuccess && host) e = alloc(dout, obytes);
+  double* out = device_output(d_m, mem_kind, dout);
+  if (e == hipSuccess) {
+    j.dx = tx; j.dv = tv; j.dstride = (long long)(E * N); j.erow = (long long)N;
+    e = moments_jvp_enqueue(h, (const double*)h->x.get(), (const double*)h->v, j, K, out, (long long)(E * 3 * Ng));
+  }
+  if (e == hipSuccess) e = device_result(h, d_m, out, obytes);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);           // (this call's buffers go away behind it)
+  if (e != hipSuccess) return fail(h, PIC_EHIP, std::string(who) + ": " + hipGetErrorString(e));
+  return PIC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The moments of every taped step (include/picstep.h: pic_tape_moments_start, pic_tape_moments; hook: advance)
+// ---------------------------------------------------------------------------------------------
+// the trace [max_steps][env][3][Ng]: row t holds the moments of the state step t left
+static size_t tape_moments_trace_parts(Carver c, const pic_handle* h, Tape& t, int64_t max_steps) {
+  c.take(t.mom_trace, (size_t)max_steps * h->cfg.num_envs * 3 * h->cfg.Ng);
+  return c.at;
+}
+
+int pic_tape_moments_start(pic_handle* h) {
+  const char* who = "pic_tape_moments_start";
+  if (!h) return PIC_EINVAL;
+  Tape& t = h->tape;
+  if (int rc = check_tape_open(h, who)) return rc;
+  if (t.mom_trace) return fail(h, PIC_ESTATE, std::string(who) + ": the tape has a moments trace already");
+  if (t.steps != 0) return fail(h, PIC_ESTATE, std::string(who) + ": the tape holds steps already (start the trace before the first)");
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  Tape v;                               // the block's view: the tape's own once the block is there
+  const size_t bytes = tape_moments_trace_parts(Carver{}, h, v, t.max_steps);
+  if (t.budget > 0 && t.bytes + bytes > (size_t)t.budget)
+    return fail(h, PIC_ENOMEM, std::string(who) + ": the moments' trace (" + std::to_string(bytes) +
+                                   " bytes) would take the tape past budget_bytes (pic_tape_start)");
+  if (int rc = moments_ensure(h, who)) return rc;
+  DeviceBuf<void> block;
+  const int rc = regrow(h, block, bytes, (std::string(who) + ": the moments' trace (" + std::to_string(bytes) +
+                                          " bytes) does not fit on the device").c_str());
+  if (rc) return rc;
+  tape_moments_trace_parts(Carver{static_cast<char*>(block.get())}, h, v, t.max_steps);
+  t.mtr_block = std::move(block);
+  t.mom_trace = v.mom_trace;
+  t.bytes += bytes;
+  return PIC_OK;
+}
+
+// the moments of the handle's particles into row t.steps of the trace (advance, behind the step that is about to be counted)
+static int tape_moments_enqueue(pic_handle* h) {
+  Tape& t = h->tape;
+  HIPCHK(h, moments_enqueue(h, t.mom_trace + (size_t)t.steps * h->cfg.num_envs * 3 * h->cfg.Ng));
+  return PIC_OK;
+}
+
+int pic_tape_moments(pic_handle* h, int mem_kind, double* m) {
+  const char* who = "pic_tape_moments";
+  if (!h) return PIC_EINVAL;
+  Tape& t = h->tape;
+  if (!t.on || !t.mom_trace)
+    return fail(h, PIC_ESTATE, std::string(who) + ": no tape with a moments trace is open (pic_tape_moments_start)");
+  if ((mem_kind != PIC_HOST && mem_kind != PIC_DEVICE) || !m) return fail(h, PIC_EINVAL, std::string(who) + ": bad mem_kind or null m");
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (t.steps == 0) return PIC_OK;
+  HIPCHK(h, hipMemcpyAsync(m, t.mom_trace, (size_t)t.steps * h->cfg.num_envs * 3 * h->cfg.Ng * sizeof(double),
+                           copy_kind(mem_kind, hipMemcpyDeviceToHost), h->stream));
+  if (mem_kind == PIC_HOST) HIPCHK(h, hipStreamSynchronize(h->stream));
+  return PIC_OK;
+}

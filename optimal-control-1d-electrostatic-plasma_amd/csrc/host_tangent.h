@@ -1,8 +1,8 @@
 // host_tangent.h -- included by picstep.hip alone, inside its extern "C" block, behind host_tape.h (the replay is the walk's)
 #pragma once
 // ---------------------------------------------------------------------------------------------
-// Forward mode of the tape (include/picstep.h: pic_tape_tangent[_kl]; kernels: pic_tangent.h), and of its per-step
-// smoothed KL (kernels: pic_phase.h)
+// Forward mode of the tape (include/picstep.h: pic_tape_tangent[_kl]; kernels: pic_tangent.h), of its per-step
+// smoothed KL (kernels: pic_phase.h) and of its per-step moments (kernels: pic_moments.h)
 // ---------------------------------------------------------------------------------------------
 // the parts of the tangent block for kc directions: state [kc][2][env][ld], dF [kc][env][Ng], acc [kc][env][Ng], ke [kc][env],
 // umax [3][kc][env] (everything from acc on is zero between uses)
@@ -82,6 +82,37 @@ static int tangent_kl_step(pic_handle* h, const TanArgs& ta, const double* x, co
   return PIC_OK;
 }
 
+// the working memory behind the moments' tangents (kMaxTangents directions), within budget_bytes (allocated once per tape); on
+// failure the tape keeps what it had
+static int tangent_moments_reserve(pic_handle* h, const std::string& w) {
+  Tape& t = h->tape;
+  if (t.tmom_block) return PIC_OK;
+  MomJvpArgs v{};
+  const size_t bytes = moments_jvp_parts(Carver{}, h, kMaxTangents, v);
+  if (t.budget > 0 && t.bytes + bytes > (size_t)t.budget)
+    return fail(h, PIC_ENOMEM, w + ": the working memory of the moments' tangent (" + std::to_string(bytes) +
+                                   " bytes) would take the tape past budget_bytes (pic_tape_start)");
+  DeviceBuf<void> b;
+  const int rc = regrow(h, b, bytes, (w + ": the working memory of the moments' tangent does not fit on the device").c_str());
+  if (rc) return rc;
+  moments_jvp_parts(Carver{static_cast<char*>(b.get())}, h, kMaxTangents, v);
+  t.tmom_block = std::move(b);
+  t.tmom_acc = v.acc; t.tmom_max = v.umax;
+  t.bytes += bytes;
+  return PIC_OK;
+}
+
+// the moments' part of forward step s (kMomentsJvpLaunches kernels): d_moments[d][s] = the tangent of the moments of the replayed
+// state x, v the step left, along the tangent state after pass 3, (dq_4, dp_3) = (dx', dv')
+static int tangent_moments_step(pic_handle* h, const TanArgs& ta, const double* x, const double* v, double* out, long long out_dstride) {
+  Tape& t = h->tape;
+  MomJvpArgs j{};
+  j.dx = ta.st; j.dv = ta.st + ta.vofs; j.dstride = ta.dstride; j.erow = h->ld; j.acc = t.tmom_acc; j.umax = t.tmom_max;
+  HIPCHK(h, moments_jvp_enqueue(h, x, v, j, ta.K, out, out_dstride));
+  t.launches += kMomentsJvpLaunches;
+  return PIC_OK;
+}
+
 extern "C++" {
 // the kernels of a sub-stage for the direction count at hand (1, up to 4, up to 8: the per-direction values live in registers)
 template <int S>
@@ -99,9 +130,11 @@ static void tangent_pass(pic_handle* h, const AdjStep& st, const TanArgs& ta, co
 }
 }  // extern "C++"
 
-// pic_tape_tangent (d_kl = null: the KL, if any, is ignored) and pic_tape_tangent_kl
+// pic_tape_tangent (d_kl = null: the KL, if any, is ignored), pic_tape_tangent_kl and pic_tape_tangent_moments (d_moments = null:
+// no kernel, byte or launch of the moments')
 static int tape_tangent(pic_handle* h, const char* who, int K, const double* d_ext, const double* d_actions, const void* d_x0,
-                        const void* d_v0, int mem_kind, double* d_hist, void* d_x, void* d_v, double* d_E_mesh, double* d_kl) {
+                        const void* d_v0, int mem_kind, double* d_hist, void* d_x, void* d_v, double* d_E_mesh, double* d_kl,
+                        double* d_moments = nullptr) {
   Tape& t = h->tape;
   const std::string w(who);
   if (int rc = check_tape_open(h, w.c_str())) return rc;
@@ -115,6 +148,8 @@ static int tape_tangent(pic_handle* h, const char* who, int K, const double* d_e
       return fail(h, PIC_ESTATE, w + ": the tape holds steps of pic_step_feedback_gain, and forward mode through the gain law is "
                                      "not built (pic_tape_backward_feedback differentiates it in reverse)");
   if (int rc = check_tape_actuator(h, d_actions, "d_actions", w.c_str())) return rc;
+  if (d_moments)
+    if (int rc = moments_jvp_check(h, w)) return rc;
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   const int E = h->cfg.num_envs, Ng = h->cfg.Ng, Mact = h->act_modes;
   const bool host = mem_kind == PIC_HOST;
@@ -137,7 +172,10 @@ static int tape_tangent(pic_handle* h, const char* who, int K, const double* d_e
   }
   int rc = tangent_reserve(h, K, w);
   if (!rc && d_kl) rc = tangent_kl_reserve(h, w);
+  if (!rc && d_moments) rc = tangent_moments_reserve(h, w);
   if (rc) return rc;
+  if (d_moments)                       // (a failed call may leave sums or max words)
+    HIPCHK(h, hipMemsetAsync(t.tmom_acc, 0, Carver::upto(t.tmom_acc, t.tmom_max + 3 * (size_t)kMaxTangents * E), h->stream));
   TanArgs ta{};
   tangent_parts(Carver{static_cast<char*>(t.tan_block.get())}, h, t.tan_k, ta);
   ta.dstride = (long long)(2 * part); ta.vofs = (long long)part;
@@ -146,20 +184,22 @@ static int tape_tangent(pic_handle* h, const char* who, int K, const double* d_e
   // host memory: the control tangents and the mesh-sized outputs go through one device block of this call
   const size_t in_n = d_ext ? (size_t)K * T * mesh : d_actions ? (size_t)K * T * E * 2 * Mact : 0;
   const size_t hist_n = d_hist ? (size_t)K * T * 3 * E : 0, em_n = d_E_mesh ? (size_t)K * T * mesh : 0;
-  const size_t kl_n = d_kl ? (size_t)K * T * E : 0;
+  const size_t kl_n = d_kl ? (size_t)K * T * E : 0, mom_n = d_moments ? (size_t)K * T * 3 * mesh : 0;
   const double* din = d_ext ? d_ext : d_actions;
   double* dhist = d_hist;
   double* dem = d_E_mesh;
   double* dkl = d_kl;
+  double* dmom = d_moments;
   DeviceBuf<double> stage;
-  if (host && in_n + hist_n + em_n + kl_n > 0) {
-    rc = regrow(h, stage, (in_n + hist_n + em_n + kl_n) * sizeof(double), (w + ": the staging of host tangents does not fit on the device").c_str());
+  if (host && in_n + hist_n + em_n + kl_n + mom_n > 0) {
+    rc = regrow(h, stage, (in_n + hist_n + em_n + kl_n + mom_n) * sizeof(double), (w + ": the staging of host tangents does not fit on the device").c_str());
     if (rc) return rc;
     double* p = stage;
     HIPCHK(h, device_input(h, din, PIC_HOST, in_n * sizeof(double), p, &din));
     dhist = device_output(d_hist, PIC_HOST, p + in_n);
     dem = device_output(d_E_mesh, PIC_HOST, p + in_n + hist_n);
     dkl = device_output(d_kl, PIC_HOST, p + in_n + hist_n + em_n);
+    dmom = device_output(d_moments, PIC_HOST, p + in_n + hist_n + em_n + kl_n);
   }
   // (dx_0, dv_0) of every direction into the state rows (padded to ld)
   for (int d = 0; d < K; ++d) {
@@ -212,6 +252,11 @@ static int tape_tangent(pic_handle* h, const char* who, int K, const double* d_e
         rc = tangent_kl_step(h, ta, xn, xn + part, dkl + (size_t)s * E, (long long)(T * E));
         if (rc) return rc;
       }
+      if (dmom) {                       // the same tangent state against the same replayed state: the moments' tangents (7l)
+        const double* xn = t.seg + (size_t)(i + 1) * 2 * part;
+        rc = tangent_moments_step(h, ta, xn, xn + part, dmom + (size_t)s * 3 * mesh, (long long)(T * 3 * mesh));
+        if (rc) return rc;
+      }
       tangent_deposit<4>(h, st, ta, a, dgrid, dlds, kd);
       hipLaunchKernelGGL(tangent_mesh_kernel<4>, mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, ta, m, a);
       t.launches += 11;
@@ -221,6 +266,7 @@ static int tape_tangent(pic_handle* h, const char* who, int K, const double* d_e
   HIPCHK(h, device_result(h, d_hist, dhist, hist_n * sizeof(double)));
   HIPCHK(h, device_result(h, d_E_mesh, dem, em_n * sizeof(double)));
   HIPCHK(h, device_result(h, d_kl, dkl, kl_n * sizeof(double)));
+  HIPCHK(h, device_result(h, d_moments, dmom, mom_n * sizeof(double)));
   // (dx', dv') of every direction out of the state rows
   for (int d = 0; d < K && !rc; ++d) {
     void* outs[2] = {d_x, d_v};
@@ -240,4 +286,11 @@ int pic_tape_tangent_kl(pic_handle* h, int K, const double* d_ext, const double*
                         int mem_kind, double* d_hist, void* d_x, void* d_v, double* d_E_mesh, double* d_kl) {
   if (!h) return PIC_EINVAL;
   return tape_tangent(h, "pic_tape_tangent_kl", K, d_ext, d_actions, d_x0, d_v0, mem_kind, d_hist, d_x, d_v, d_E_mesh, d_kl);
+}
+
+int pic_tape_tangent_moments(pic_handle* h, int K, const double* d_ext, const double* d_actions, const void* d_x0, const void* d_v0,
+                             int mem_kind, double* d_hist, void* d_x, void* d_v, double* d_E_mesh, double* d_kl, double* d_moments) {
+  if (!h) return PIC_EINVAL;
+  return tape_tangent(h, d_moments ? "pic_tape_tangent_moments" : "pic_tape_tangent_kl", K, d_ext, d_actions, d_x0, d_v0, mem_kind,
+                      d_hist, d_x, d_v, d_E_mesh, d_kl, d_moments);
 }

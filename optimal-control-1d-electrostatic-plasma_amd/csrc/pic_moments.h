@@ -8,6 +8,7 @@
 // Off the step path: the kernels read the state a step left.
 #pragma once
 #include "pic_adjoint.h"
+#include "pic_phase.h"      // pic_v2d_a8: a tangent tile of dense rows that start on 8 bytes only (N odd)
 
 namespace {
 
@@ -245,6 +246,244 @@ __global__ __launch_bounds__(BLOCK) void moments_vjp_kernel(const double* __rest
     ov[o] = dv;
   }
   (void)bad;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Forward mode (pic_moments_jvp, pic_tape_tangent_moments): the directional derivative of the three moments along
+// tangents (dx_i, dv_i) of the particles, float64 + CIC, with the almost-everywhere derivative of the gather above (weight slopes
+// -/+ 1/dx).  With iota = dx_i / dx a particle adds to its left node j and its right node jr
+//   dm0:  -iota                         +iota
+//   dm1:  w_l dv - iota v               w_r dv + iota v
+//   dm2:  2 w_l v dv - iota v^2         2 w_r v dv + iota v^2
+// (times s): term by term the transpose of moments_vjp_kernel.  Every term is rounded to a 64-bit integer in a unit taken from the
+// max of a bound on one term per (moment, direction, environment), so the sums do not depend on their order.
+// ---------------------------------------------------------------------------------------------
+struct MomJvpArgs {
+  const double* dx;            // direction 0, environment 0 of the x tangents, or null (0)
+  const double* dv;            // the same of the v tangents
+  long long dstride;           // elements from one direction to the next
+  long long erow;              // elements from one environment's row to the next (ld of the tangent state, N of dense rows)
+  unsigned long long* acc;     // [3][K][env][Ng] integer sums, zero between uses
+  unsigned long long* umax;    // [3][K][env] bit patterns of the terms' bounds, zero between uses
+  int K;                       // directions
+  int kd;                      // directions a deposit workgroup holds in LDS (grid z: groups of kd)
+};
+
+// tile t (particles 2t, 2t + 1) of a tangent row, or zeros for a null row; the odd last particle of a row is read alone, so nothing
+// beyond N is ever read
+__device__ __forceinline__ pic_v2d mom_tan_tile(const double* __restrict__ row, long long t, bool pair) {
+  pic_v2d r = {0.0, 0.0};
+  if (row) {
+    if (pair) {
+      const pic_v2d_a8 q = stream_load(reinterpret_cast<const pic_v2d_a8*>(row + 2 * t));
+      r[0] = q[0]; r[1] = q[1];
+    } else {
+      r[0] = row[2 * t];
+    }
+  }
+  return r;
+}
+
+// running max of bounds as bit patterns (ordered like the non-negative values); a non-finite bound saturates it for good
+__device__ __forceinline__ void mom_max_bits(unsigned long long& m, double bound) {
+  unsigned long long b = (unsigned long long)__double_as_longlong(bound);
+  if (!(bound <= 1.7976931348623157e308)) b = kMomInfBits;
+  m = b > m ? b : m;
+}
+
+__device__ __forceinline__ unsigned long long* mom_jvp_word(const MomJvpArgs& j, int m, int d, int num_envs, int env) {
+  return j.umax + ((size_t)m * j.K + d) * num_envs + env;
+}
+
+// Max pass: grid (workgroups per environment, environments), the deposit's ranges.  One read of v and of every direction's dx, dv;
+// per (moment, direction, environment) the max of a bound on one deposited term,
+//   b0 = |iota|   b1 = |dv| + |iota v|   b2 = 2 |v dv| + |iota| v^2
+// through block_max_to (order-free; a non-finite value saturates the word).
+template <int KD>
+__global__ __launch_bounds__(BLOCK) void moments_jvp_max_kernel(const double* __restrict__ v, MomArgs a, MomJvpArgs j) {
+  const int env = blockIdx.y;
+  const pic_v2d* vv = reinterpret_cast<const pic_v2d*>(v + (size_t)env * a.ld);
+  const long long ntiles = (a.N + 1) / 2;
+  const long long t0 = (long long)blockIdx.x * a.tiles_per_wg * BLOCK;
+  long long t1 = t0 + a.tiles_per_wg * BLOCK;
+  t1 = t1 < ntiles ? t1 : ntiles;
+  const size_t drow = (size_t)env * j.erow;
+  unsigned long long m0[KD], m1[KD], m2[KD];
+#pragma unroll
+  for (int d = 0; d < KD; ++d) m0[d] = m1[d] = m2[d] = 0ull;
+  for (long long t = t0 + threadIdx.x; t < t1; t += BLOCK) {
+    const bool pair = 2 * t + 1 < a.N;
+    const pic_v2d vt = stream_load(vv + t);
+#pragma unroll
+    for (int d = 0; d < KD; ++d) {
+      if (d >= j.K) break;
+      const size_t o = (size_t)d * j.dstride + drow;
+      const pic_v2d xd = mom_tan_tile(j.dx ? j.dx + o : nullptr, t, pair);
+      const pic_v2d vd = mom_tan_tile(j.dv ? j.dv + o : nullptr, t, pair);
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        if (k == 1 && !pair) break;
+        const double vs = vt[k], io = fabs(xd[k] / a.dx);
+        mom_max_bits(m0[d], io);
+        mom_max_bits(m1[d], fabs(vd[k]) + fabs(io * vs));
+        mom_max_bits(m2[d], 2.0 * fabs(vs * vd[k]) + io * (vs * vs));
+      }
+    }
+  }
+#pragma unroll
+  for (int d = 0; d < KD; ++d) {
+    if (d >= j.K) break;
+    block_max_to(__longlong_as_double((long long)m0[d]), mom_jvp_word(j, 0, d, a.num_envs, env));
+    block_max_to(__longlong_as_double((long long)m1[d]), mom_jvp_word(j, 1, d, a.num_envs, env));
+    block_max_to(__longlong_as_double((long long)m2[d]), mom_jvp_word(j, 2, d, a.num_envs, env));
+  }
+}
+
+// Deposit pass: grid (workgroups per environment, environments, groups of kd <= KD directions).  LDS [kd][3][Ng + 1] 64-bit
+// words (the right node of the last cell is slot Ng), cleared under the latency of the first tile's loads.  x, v and the group's
+// dx, dv are read once in 16-byte tiles, the next tile requested before the current one is deposited; cell, weights, v and v^2
+// are computed once per particle and serve every direction.  dm0 adds -r and +r of one rounded r: its integer sum is zero.  A
+// (moment, direction) whose max word is zero or saturated is skipped (the finishing kernel writes +0 / NaN there).  The flush is
+// one memory-side atomic per non-zero node.
+template <int KD>
+__global__ __launch_bounds__(BLOCK) void moments_jvp_deposit_kernel(const double* __restrict__ x, const double* __restrict__ v,
+                                                                    MomArgs a, MomJvpArgs j) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  unsigned long long* lds = reinterpret_cast<unsigned long long*>(smem_raw);
+  const int env = blockIdx.y, Ng = a.Ng, stride = Ng + 1, d0 = blockIdx.z * j.kd;
+  const int nd = min(j.kd, j.K - d0);
+  const pic_v2d* xv = reinterpret_cast<const pic_v2d*>(x + (size_t)env * a.ld);
+  const pic_v2d* vv = reinterpret_cast<const pic_v2d*>(v + (size_t)env * a.ld);
+  const long long ntiles = (a.N + 1) / 2;
+  const long long t0 = (long long)blockIdx.x * a.tiles_per_wg * BLOCK;
+  long long t1 = t0 + a.tiles_per_wg * BLOCK;
+  t1 = t1 < ntiles ? t1 : ntiles;
+  const size_t drow = (size_t)d0 * j.dstride + (size_t)env * j.erow;
+  const double* tx = j.dx ? j.dx + drow : nullptr;
+  const double* tv = j.dv ? j.dv + drow : nullptr;
+  long long t = t0 + threadIdx.x;
+  bool have = t < t1;
+  pic_v2d xn = {0.0, 0.0}, vn = {0.0, 0.0}, dxn[KD], dvn[KD];
+#pragma unroll
+  for (int d = 0; d < KD; ++d) dxn[d] = dvn[d] = pic_v2d{0.0, 0.0};
+  if (have) {
+    const bool pair = 2 * t + 1 < a.N;
+    xn = stream_load(xv + t);
+    vn = stream_load(vv + t);
+#pragma unroll
+    for (int d = 0; d < KD; ++d) {
+      if (d >= nd) break;
+      dxn[d] = mom_tan_tile(tx ? tx + (size_t)d * j.dstride : nullptr, t, pair);
+      dvn[d] = mom_tan_tile(tv ? tv + (size_t)d * j.dstride : nullptr, t, pair);
+    }
+  }
+  for (int c = threadIdx.x; c < nd * 3 * stride; c += BLOCK) lds[c] = 0ull;
+  int ue[3][KD];
+  bool on[3][KD];
+#pragma unroll
+  for (int m = 0; m < 3; ++m) {
+#pragma unroll
+    for (int d = 0; d < KD; ++d) {
+      const unsigned long long mb = d < nd ? *mom_jvp_word(j, m, d0 + d, a.num_envs, env) : 0ull;
+      on[m][d] = mb != 0ull && mb < kMomInfBits;
+      ue[m][d] = adj_unit_exp(mb, a.bitsN);
+    }
+  }
+  __syncthreads();
+  const Consts<PosF64> kc(a.L, a.dx, Ng);
+  unsigned bad = 0u;
+  while (have) {
+    const pic_v2d xt = xn, vt = vn;
+    pic_v2d dxt[KD], dvt[KD];
+#pragma unroll
+    for (int d = 0; d < KD; ++d) { dxt[d] = dxn[d]; dvt[d] = dvn[d]; }
+    const long long tc = t;
+    t += BLOCK;
+    have = t < t1;
+    if (have) {
+      const bool pair = 2 * t + 1 < a.N;
+      xn = stream_load(xv + t);
+      vn = stream_load(vv + t);
+#pragma unroll
+      for (int d = 0; d < KD; ++d) {
+        if (d >= nd) break;
+        dxn[d] = mom_tan_tile(tx ? tx + (size_t)d * j.dstride : nullptr, t, pair);
+        dvn[d] = mom_tan_tile(tv ? tv + (size_t)d * j.dstride : nullptr, t, pair);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      if (2 * tc + k >= a.N) break;
+      double w[3], xw;
+      int jl, jr;
+      adj_locate(xt[k], kc, xw, jl, jr, w, bad);
+      const double vs = vt[k], v2 = vs * vs;
+#pragma unroll
+      for (int d = 0; d < KD; ++d) {
+        if (d >= nd) break;
+        unsigned long long* l0 = lds + (size_t)d * 3 * stride + jl;
+        const double io = dxt[d][k] / a.dx, dvs = dvt[d][k];
+        if (on[0][d]) {
+          const long long r = __double2ll_rn(ldexp(io, -ue[0][d]));
+          atomicAdd(l0, (unsigned long long)(-r));
+          atomicAdd(l0 + 1, (unsigned long long)r);
+        }
+        if (on[1][d]) {
+          const double iv = io * vs;
+          atomicAdd(l0 + stride, (unsigned long long)__double2ll_rn(ldexp(w[0] * dvs - iv, -ue[1][d])));
+          atomicAdd(l0 + stride + 1, (unsigned long long)__double2ll_rn(ldexp(w[1] * dvs + iv, -ue[1][d])));
+        }
+        if (on[2][d]) {
+          const double iv2 = io * v2, vdv = 2.0 * (vs * dvs);
+          atomicAdd(l0 + 2 * stride, (unsigned long long)__double2ll_rn(ldexp(w[0] * vdv - iv2, -ue[2][d])));
+          atomicAdd(l0 + 2 * stride + 1, (unsigned long long)__double2ll_rn(ldexp(w[1] * vdv + iv2, -ue[2][d])));
+        }
+      }
+    }
+  }
+  (void)bad;                                               // (the state's bad positions are the sweeps' to count)
+  __syncthreads();
+#pragma unroll
+  for (int m = 0; m < 3; ++m) {
+#pragma unroll
+    for (int d = 0; d < KD; ++d) {
+      if (d >= nd) break;
+      if (!on[m][d]) continue;
+      const unsigned long long* lm = lds + ((size_t)d * 3 + m) * stride;
+      unsigned long long* out = j.acc + (((size_t)m * j.K + d0 + d) * a.num_envs + env) * Ng;
+      for (int c = threadIdx.x; c < Ng; c += BLOCK) {
+        unsigned long long s = lm[c];
+        if (c == 0) s += lm[Ng];
+        if (s) atomicAdd(out + c, s);
+      }
+    }
+  }
+}
+
+// One workgroup per (environment, direction): integers x unit x s into out[d * out_dstride + (env 3 + m) Ng + node]; +0 in a
+// moment whose max word is zero, NaN in one whose max word is saturated (that moment of that direction of that environment only);
+// the accumulators and the three max words are cleared behind the read.
+__global__ __launch_bounds__(BLOCK) void moments_jvp_finish_kernel(MomArgs a, MomJvpArgs j, double* __restrict__ out,
+                                                                   long long out_dstride) {
+  const int env = blockIdx.x, d = blockIdx.y, Ng = a.Ng;
+  const double nan = __longlong_as_double(0x7FF8000000000000ll);
+  double* o = out + (size_t)d * out_dstride + (size_t)env * 3 * Ng;
+#pragma unroll
+  for (int m = 0; m < 3; ++m) {
+    const unsigned long long mb = *mom_jvp_word(j, m, d, a.num_envs, env);
+    const bool finite = mb < kMomInfBits, dep = mb != 0ull && finite;
+    const int ue = adj_unit_exp(mb, a.bitsN);
+    unsigned long long* am = j.acc + (((size_t)m * j.K + d) * a.num_envs + env) * Ng;
+    for (int c = threadIdx.x; c < Ng; c += BLOCK) {
+      double r = 0.0;
+      if (dep) r = ldexp((double)(long long)am[c], ue) * a.scale;
+      if (!finite) r = nan;
+      o[(size_t)m * Ng + c] = r;
+      am[c] = 0ull;
+    }
+  }
+  __syncthreads();                                         // (every lane has read the max words)
+  if (threadIdx.x < 3) *mom_jvp_word(j, threadIdx.x, d, a.num_envs, env) = 0ull;
 }
 
 }  // namespace

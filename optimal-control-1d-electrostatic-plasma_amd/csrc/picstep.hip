@@ -232,6 +232,14 @@ struct Tape {
   DeviceBuf<void> mom_block;
   double* mom_cot = nullptr;          // [max_steps + 1][env][3][Ng]: row s + 1 for the state step s left, row 0 for the tape start
   std::vector<char> mom_flag;         // [max_steps + 1] per row: mom_cot holds a cotangent there
+  // the moments of every taped step (pic_tape_moments_start): one block allocated by that call, counts in `bytes`
+  DeviceBuf<void> mtr_block;
+  double* mom_trace = nullptr;        // [max_steps][env][3][Ng]; set: advance cuts behind every step and writes its row
+  // forward mode of the moments (pic_tape_tangent_moments): one block for kMaxTangents directions allocated by the
+  // first call that asks for d_moments, counts in `bytes`; tmom_acc and tmom_max are views into it
+  DeviceBuf<void> tmom_block;
+  unsigned long long* tmom_acc = nullptr;   // [3][K][env][Ng] integer sums of the step at hand, zero between uses
+  unsigned long long* tmom_max = nullptr;   // [3][K][env] bit patterns of the terms' bounds, zero between uses
 };
 
 }  // namespace
@@ -1289,7 +1297,7 @@ static int advance(pic_handle* h, const StepControl& sc, int nsteps, double* his
     int64_t n = nsteps - done;
     if (r.on) n = std::min<int64_t>(n, r.stride - r.k % r.stride);
     if (t.on) n = std::min<int64_t>(n, t.every - t.steps % t.every);
-    if (t.on && t.kl) n = 1;          // the KL of every step: the recorder's cut with stride 1
+    if (t.on && (t.kl || t.mom_trace)) n = 1;   // the KL or the moments (7l) of every step: the recorder's cut with stride 1
     const StepControl part = sc.after(done, E);
     int rc = t.on && part.fb.M == 0 ? tape_record_ext(h, part, (int)n) : PIC_OK;
     if (rc) return rc;
@@ -1315,6 +1323,10 @@ static int advance(pic_handle* h, const StepControl& sc, int nsteps, double* his
     }
     if (t.kl) {
       rc = tape_kl_enqueue(h);        // row t.steps of the trace
+      if (rc) return rc;
+    }
+    if (t.mom_trace) {
+      rc = tape_moments_enqueue(h);   // row t.steps of the moments' trace
       if (rc) return rc;
     }
     t.steps += n;

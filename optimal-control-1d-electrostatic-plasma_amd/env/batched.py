@@ -45,6 +45,7 @@ class BatchedPIC:
         self._torch_stream = None            # (the handle runs on its own stream: use_torch_stream)
         self._tape_kl = False                # (the open tape records the smoothed KL)
         self._tape_moments = False           # (the open tape has held cotangents on the moments)
+        self._tape_mom_trace = False         # (the open tape records the moments of every step)
         self._tape_serial = self._walk_serial = 0       # (the tape env.grad opened last, the walk in progress)
 
     # reset(x0, v0): x0, v0 are [num_envs, N] with any velocity perturbation already applied
@@ -417,6 +418,29 @@ class BatchedPIC:
         self._h.moments_vjp(mem.addr(c), mem.kind, mem.addr(gx), mem.addr(gv))
         return gx, gv
 
+    def moments_jvp(self, d_x=None, d_v=None):
+        """Directional derivatives of `moments` along tangents d_x, d_v [num_envs, N] of the current particles (each None = 0) ->
+        [num_envs, 3, N_mesh], with moments_vjp's derivative: sum g . moments_jvp(d_x, d_v) = g_x . d_x + g_v . d_v for (g_x, g_v)
+        = moments_vjp(g) (pic_moments_jvp).  With a leading axis of K <= 8 directions on the inputs the result is
+        [K, num_envs, 3, N_mesh].  Float64 particles and CIC only.  Bitwise reproducible.  NumPy, or a float64 CUDA tensor if a
+        tangent is one."""
+        E, N = self.num_envs, self.N
+        given = [a for a in (d_x, d_v) if a is not None]
+        ks = {int(a.shape[0]) for a in given if len(a.shape) == 3}
+        if len(ks) > 1:
+            raise ValueError(f"moments_jvp: the inputs disagree on the number of directions: {sorted(ks)}")
+        batched = bool(ks)
+        K = ks.pop() if ks else 1
+        for a in given:
+            if tuple(a.shape) != ((K,) if batched else ()) + (E, N):
+                raise ValueError(f"moments_jvp: a tangent must have shape {((K,) if batched else ()) + (E, N)}, not {tuple(a.shape)}")
+        mem = Mem.of(self, d_x, d_v)
+        tx, tv = mem.f64(d_x), mem.f64(d_v)
+        out = mem.empty((K, E, 3, self.N_mesh))
+        mem.enter()
+        self._h.moments_jvp(K, mem.addr(tx), mem.addr(tv), mem.kind, mem.addr(out))
+        return out if batched else out[0]
+
     def _set_moments_cot(self, d_moments, T, mem):
         """The moments' cotangents of a backward onto the tape: d_moments [T, num_envs, 3, N_mesh] (row t on the state step t
         left), or None to clear every row, the start's included.  Returns what must stay alive until the backward is done."""
@@ -512,7 +536,7 @@ class BatchedPIC:
         self._h.refresh()
 
     # -- differentiable rollouts (pic_tape_*) ------------------------------------------
-    def start_tape(self, max_steps: int, checkpoint_every: int = 0, budget_bytes: int = 0, kl=None):
+    def start_tape(self, max_steps: int, checkpoint_every: int = 0, budget_bytes: int = 0, kl=None, moments: bool = False):
         """Open a tape: the steps that follow (step, step_history, step_actions[_traj], step_ext_traj, step_observe,
         step_feedback_gain, up to max_steps of them) can be differentiated by `backward`.  checkpoint_every = 0: about
         sqrt(max_steps).  Float64 particles, CIC, Yoshida-4 and the fixed-point accumulator only.  Resets, step_feedback (use
@@ -521,9 +545,12 @@ class BatchedPIC:
         kl = dict(feq=..., vmin=-25.0, vmax=25.0) also records the smoothed KL of `kl_smooth` after every step (pic_tape_kl_*,
         DESIGN.md 7h): `tape_kl()` reads the trace and `backward(d_KL=...)` differentiates it.  feq: NumPy or a CUDA tensor,
         [nx, nv] or [num_envs, nx, nv]; the tape keeps a copy.  If the KL's memory does not fit (PicError), the tape stays open
-        without one."""
+        without one.
+        moments=True also records `moments` after every step (pic_tape_moments_start): `tape_moments()` reads the
+        trace, `backward(d_moments=...)` and `tangent(moments=True)` differentiate it.  If the trace does not fit (PicError), the
+        tape stays open without one."""
         self._h.tape_start(max_steps, checkpoint_every, budget_bytes)
-        self._tape_kl = self._tape_moments = False
+        self._tape_kl = self._tape_moments = self._tape_mom_trace = False
         if kl is not None:
             kl = dict(kl)
             feq, vmin, vmax = kl.pop("feq"), float(kl.pop("vmin", -25.0)), float(kl.pop("vmax", 25.0))
@@ -532,10 +559,28 @@ class BatchedPIC:
             mem, (nx, nv, fa, per), _held = self._phase_call(feq)
             self._h.tape_kl_start(nx, nv, vmin, vmax, fa, per, mem.kind)
             self._tape_kl = True
+        if moments:
+            self._h.tape_moments_start()
+            self._tape_mom_trace = True
 
     def stop_tape(self):
         self._h.tape_stop()
-        self._tape_kl = self._tape_moments = False
+        self._tape_kl = self._tape_moments = self._tape_mom_trace = False
+
+    def tape_moments(self, on_device: bool = False):
+        """The moments after every step taped so far, [T, num_envs, 3, N_mesh] (a tape opened with moments=True): each row is
+        bit for bit what `moments` returns after that step.  NumPy, or a float64 CUDA tensor with on_device."""
+        if not self._tape_mom_trace:
+            raise _abi.PicError("tape_moments: no tape with a moments trace is open (start_tape(..., moments=True))")
+        T = self._h.tape_stats()["steps"]
+        mem = Mem.of(self, force_device=on_device)
+        out = mem.empty((T, self.num_envs, 3, self.N_mesh))
+        if T == 0:
+            return out
+        mem.enter()
+        self._h.tape_moments(mem.kind, mem.addr(out))
+        mem.leave(self._h)
+        return out
 
     def tape_kl(self, on_device: bool = False):
         """The smoothed KL after every step taped so far, [T, num_envs] (a tape opened with kl=...): each row is bit for bit
@@ -581,13 +626,13 @@ class BatchedPIC:
         """steps, checkpoint_every, bytes, replay_mismatches (of the last backward; 0 expected), unit_retries, launches."""
         return self._h.tape_stats()
 
-    def taping(self, max_steps: int, checkpoint_every: int = 0, budget_bytes: int = 0, kl=None):
+    def taping(self, max_steps: int, checkpoint_every: int = 0, budget_bytes: int = 0, kl=None, moments: bool = False):
         """Context manager: start_tape(...) on entry, stop_tape() on exit."""
         import contextlib
 
         @contextlib.contextmanager
         def cm():
-            self.start_tape(max_steps, checkpoint_every, budget_bytes, kl=kl)
+            self.start_tape(max_steps, checkpoint_every, budget_bytes, kl=kl, moments=moments)
             try:
                 yield self
             finally:
@@ -638,7 +683,8 @@ class BatchedPIC:
             res["gain"] = g[0] if len(g) == 1 else g
         return res
 
-    def tangent(self, d_ext=None, d_actions=None, d_x0=None, d_v0=None, fields: bool = False, kl: bool = False):
+    def tangent(self, d_ext=None, d_actions=None, d_x0=None, d_v0=None, fields: bool = False, kl: bool = False,
+                moments: bool = False):
         """Jacobian-vector product of the taped steps (pic_tape_tangent): tangents d_ext [T, num_envs, N_mesh] of
         every step's external field, or d_actions [T, num_envs, 2*max_mode] of its actions (at most one), and d_x0, d_v0
         [num_envs, N] of the tape's starting particles (each None = 0).  Every input may carry a leading axis of K <= 8
@@ -646,8 +692,11 @@ class BatchedPIC:
         "PE_reward" [K, T, num_envs], "x", "v" [K, num_envs, N] (final particles) and, with fields, "E_mesh" [K, T, num_envs,
         N_mesh] (every step's post-step field).  With kl, on a tape opened with kl=..., "KL" [K, T, num_envs] follows: the
         tangents of the trace `tape_kl` returns (pic_tape_tangent_kl; four more kernels per step); every other key
-        keeps its bits.  NumPy arrays, or float64 CUDA tensors if any input is one (then stream-ordered like
-        backward).  Raises PicError if the replay of the taped steps does not reproduce the forward bit for bit."""
+        keeps its bits.  With moments, "moments" [K, T, num_envs, 3, N_mesh] follows: the tangents of `moments` of the state
+        every step left (pic_tape_tangent_moments; three more kernels per step; no trace on the tape needed), dual
+        to backward(d_moments=...); every other key keeps its bits.  NumPy arrays, or float64 CUDA tensors if any input is one
+        (then stream-ordered like backward).  Raises PicError if the replay of the taped steps does not reproduce the forward
+        bit for bit."""
         if kl and not self._tape_kl:
             raise _abi.PicError("tangent: kl=True needs a KL on the tape (start_tape(..., kl=...))")
         T = self._h.tape_stats()["steps"]
@@ -669,10 +718,12 @@ class BatchedPIC:
         hist, x, v = mem.out((K, T, 3, E)), mem.out((K, E, N)), mem.out((K, E, N))
         em = mem.out((K, T, E, Ng)) if fields else None
         dkl = mem.out((K, T, E)) if kl else None
+        dmom = mem.out((K, T, E, 3, Ng)) if moments else None
         addr = mem.addr
         mem.enter()
         self._h._tape_tangent(mem.kind, K, addr(ins.get("d_ext")), addr(ins.get("d_actions")), addr(ins.get("d_x0")),
-                              addr(ins.get("d_v0")), addr(hist), addr(x), addr(v), addr(em), kl=addr(dkl) if kl else None)
+                              addr(ins.get("d_v0")), addr(hist), addr(x), addr(v), addr(em), kl=addr(dkl) if kl else None,
+                              moments=addr(dmom) if moments else None)
         if mem.on_device:
             self._check_replay("tangent", "tangent")
         res = {"KE": hist[:, :, 0], "PE": hist[:, :, 1], "PE_reward": hist[:, :, 2], "x": x, "v": v}
@@ -680,6 +731,8 @@ class BatchedPIC:
             res["E_mesh"] = em
         if kl:
             res["KL"] = dkl
+        if moments:
+            res["moments"] = dmom
         return res if batched else {k: a[0] for k, a in res.items()}
 
     def walk(self, obs_modes: Optional[int] = None, on_device: bool = False):

@@ -24,6 +24,13 @@ Every entry takes kl=dict(feq=..., vmin=..., vmax=...) (BatchedPIC.start_tape): 
 In forward mode the KL output of rollout and rollout_ext carries its tangent like the energy traces (pic_tape_tangent_kl,
 DESIGN.md 7j), so a directional derivative of the whole cost is one dual_level pass.
 
+rollout and rollout_ext take moments=True: the fluid moments of the state every step left, [T, num_envs, 3, N_mesh], follow the
+other outputs (KE, PE, PE_reward, then KL if asked, then the moments), differentiable in reverse (pic_tape_moments_cot) and in
+forward mode (pic_tape_tangent_moments):
+
+    KE, PE, PE_reward, mom = rollout(env, actions, moments=True)
+    ((mom[:, :, 0] - target) ** 2).sum().backward()                 # a density-profile tracking cost
+
 Each call opens a fresh tape on `env` (an open one is stopped first) and leaves it open for the backward; stop it with
 `env.stop_tape()` before a reset.  A backward after the environment has moved on (a further step, another rollout, a reset)
 raises PicError.
@@ -34,9 +41,9 @@ import torch
 from .._abi import PicError
 
 
-def _start(env, T, checkpoint_every, kl=None):
+def _start(env, T, checkpoint_every, kl=None, moments=False):
     env.stop_tape()
-    env.start_tape(T, checkpoint_every, kl=kl)
+    env.start_tape(T, checkpoint_every, kl=kl, moments=moments)
     env._tape_serial += 1
     return env._tape_serial
 
@@ -48,54 +55,60 @@ def _check_live(env, serial, steps, who):
 
 class _Rollout(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, u, env, kind, checkpoint_every, kl=None):
+    def forward(ctx, u, env, kind, checkpoint_every, kl=None, moments=False):
         if not (u.dtype == torch.float64 and u.dim() == 3 and u.shape[1] == env.num_envs):
             raise ValueError("the control must be a float64 tensor [T, num_envs, ...]")
         T = int(u.shape[0])
-        serial = _start(env, T, checkpoint_every, kl)
+        serial = _start(env, T, checkpoint_every, kl, moments)
         host = np.ascontiguousarray(u.detach().cpu().numpy())
         if kind == "actions":
             ke, pe, per = env.step_actions_traj(host, history=True)
         else:
             ke, pe, per = env.step_ext_traj(host, history=True)
         ctx.env, ctx.kind, ctx.serial, ctx.steps, ctx.device, ctx.kl = env, kind, serial, T, u.device, kl is not None
-        outs = (ke, pe, per) + ((env.tape_kl(),) if kl is not None else ())
+        ctx.moments = bool(moments)
+        outs = (ke, pe, per) + ((env.tape_kl(),) if kl is not None else ()) + ((env.tape_moments(),) if moments else ())
         return tuple(torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64, device=u.device) for a in outs)
 
     @staticmethod
-    def backward(ctx, g_ke, g_pe, g_per, g_kl=None):
+    def backward(ctx, g_ke, g_pe, g_per, *g_extra):
         _check_live(ctx.env, ctx.serial, ctx.steps, "backward")
-        out = ctx.env.backward(d_KE=g_ke, d_PE=g_pe, d_PE_reward=g_per, d_KL=g_kl if ctx.kl else None)
+        g_extra = list(g_extra)
+        g_kl = g_extra.pop(0) if ctx.kl else None
+        g_mom = g_extra.pop(0) if ctx.moments else None
+        out = ctx.env.backward(d_KE=g_ke, d_PE=g_pe, d_PE_reward=g_per, d_KL=g_kl, d_moments=g_mom)
         g = torch.as_tensor(out["actions" if ctx.kind == "actions" else "ext"])       # (NumPy out for CPU cotangents in)
-        return g, None, None, None, None
+        return g, None, None, None, None, None
 
     @staticmethod
-    def jvp(ctx, u_t, env_t, kind_t, ce_t, kl_t=None):
+    def jvp(ctx, u_t, env_t, kind_t, ce_t, kl_t=None, mom_t=None):
         """Forward mode (torch.autograd.forward_ad): the tangent of the energy traces along u_t, from pic_tape_tangent on the
-        tape this rollout opened, and of the KL trace of a rollout with kl=... from pic_tape_tangent_kl (7j)."""
+        tape this rollout opened, of the KL trace of a rollout with kl=... from pic_tape_tangent_kl (7j) and of
+        the moments' trace of one with moments=True from pic_tape_tangent_moments (7l)."""
         env = ctx.env
         _check_live(env, ctx.serial, ctx.steps, "jvp")
-        zero = lambda: torch.zeros((ctx.steps, env.num_envs), dtype=torch.float64, device=ctx.device)  # noqa: E731
+        zero = lambda *s: torch.zeros((ctx.steps, env.num_envs) + s, dtype=torch.float64, device=ctx.device)  # noqa: E731
         if u_t is None:
-            return tuple(zero() for _ in range(4 if ctx.kl else 3))
-        out = env.tangent(kl=ctx.kl, **{"d_actions" if ctx.kind == "actions" else "d_ext": u_t.detach()})
-        keys = ("KE", "PE", "PE_reward") + (("KL",) if ctx.kl else ())
+            return tuple(zero() for _ in range(4 if ctx.kl else 3)) + ((zero(3, env.N_mesh),) if ctx.moments else ())
+        out = env.tangent(kl=ctx.kl, moments=ctx.moments, **{"d_actions" if ctx.kind == "actions" else "d_ext": u_t.detach()})
+        keys = ("KE", "PE", "PE_reward") + (("KL",) if ctx.kl else ()) + (("moments",) if ctx.moments else ())
         return tuple(torch.as_tensor(out[k], dtype=torch.float64, device=ctx.device) for k in keys)
 
 
-def rollout(env, actions, checkpoint_every=0, kl=None):
+def rollout(env, actions, checkpoint_every=0, kl=None, moments=False):
     """T = actions.shape[0] steps of `env` (a BatchedPIC with an actuator) under actions [T, num_envs, 2*max_mode] through
     pic_step_actions_traj on a tape; returns KE, PE, PE_reward [T, num_envs] (float64, on actions' device), differentiable
     with respect to `actions`.  With kl=dict(feq=..., vmin=..., vmax=...) a fourth output follows: the smoothed KL after
-    every step, [T, num_envs], differentiable too."""
+    every step, [T, num_envs], differentiable too.  With moments=True one more output follows the others: the fluid moments of
+    the state every step left, [T, num_envs, 3, N_mesh] (BatchedPIC.tape_moments), differentiable in both modes."""
     if env.max_mode == 0:
         raise PicError("rollout: the environment has no actuator (set_actuator)")
-    return _Rollout.apply(actions, env, "actions", int(checkpoint_every), kl)
+    return _Rollout.apply(actions, env, "actions", int(checkpoint_every), kl, bool(moments))
 
 
-def rollout_ext(env, E_ext, checkpoint_every=0, kl=None):
+def rollout_ext(env, E_ext, checkpoint_every=0, kl=None, moments=False):
     """The same under raw external fields E_ext [T, num_envs, N_mesh] (pic_step_ext_traj)."""
-    return _Rollout.apply(E_ext, env, "ext", int(checkpoint_every), kl)
+    return _Rollout.apply(E_ext, env, "ext", int(checkpoint_every), kl, bool(moments))
 
 
 class _RolloutFeedback(torch.autograd.Function):
