@@ -582,8 +582,12 @@ int pic_tape_tangent_kl(pic_handle* h, int K, const double* d_ext, const double*
  * memory for every particle format (PIC_HOST waits; PIC_DEVICE is asynchronous on the handle's stream); PIC_ESTATE before
  * pic_reset and during a staged step.  All three are 64-bit integer sums: m0 in the forward's fixed-point units, so that on a
  * float64 handle with the fixed-point accumulator it equals pic_get_fields' n of a fresh state bit for bit; m1 and m2 in units
- * taken from the environment's max |v| < 2^e, 2^(e + b - 61) and 2^(2e + b - 61) with 2^b >= N.  The result therefore does
- * not depend on blocks_per_env, the schedule, accum_dtype or the environment's place in the batch.  An environment at rest has
+ * taken from the environment's max |v| < 2^e, 2^(e + b - 61) and 2^(2e + b - 61) with 2^b >= N.  Every term is rounded to nearest
+ * in its unit, so m1 and m2 of a node are off by up to half a unit per particle that touches it, whatever that node's own
+ * velocities: one fast particle coarsens m1 and m2 of its whole environment (and of no other), which resolve N 2^-61 of
+ * N max |v| and N max |v|^2, not of the node's own value.  Scaling every velocity of an environment by 2^k scales m1 by 2^k and m2
+ * by 2^(2k) bit for bit while every result stays a normal double.  The result does not depend on blocks_per_env, the schedule,
+ * accum_dtype or the environment's place in the batch.  An environment at rest has
  * m1 = m2 = +0; one with a non-finite velocity has NaN in m1 and m2 (m0 and the other environments are unaffected); with
  * max |v| >= 2^511, m2 is +inf.  Particles, fields, energies and pic_bad_count are untouched.  N_mesh above 2728 is PIC_EINVAL
  * (three meshes of 64-bit sums in 64 KB of LDS).  The first call allocates 8 (6 num_envs N_mesh + num_envs) bytes.
@@ -615,8 +619,10 @@ int pic_tape_moments_cot(pic_handle* h, const double* cot_m, int mem_kind, int64
  *     dm0:  -iota                          +iota
  *     dm1:  w_l d_v_i - iota v_i           w_r d_v_i + iota v_i
  *     dm2:  2 w_l v_i d_v_i - iota v_i^2   2 w_r v_i d_v_i + iota v_i^2
- * times s, so that sum c . pic_moments_jvp(u) = pic_moments_vjp(c) . u, sum_j dm0_j = 0 (exactly: both halves are one rounded
- * integer) and sum_j dm2_j N dx / (2 n0 L) = sum_i v_i d_v_i.  Every term is a 64-bit integer in the unit 2^(e + b - 61), 2^b >= N,
+ * times s, so that sum c . pic_moments_jvp(u) = pic_moments_vjp(c) . u, sum_j dm0_j = 0 (exactly in the integer sums: both halves
+ * are one rounded integer; each float64 dm0_j then carries the rounding of its conversion and of the product by s, so
+ * |sum_j dm0_j| <= 2^-52 sum_j |dm0_j|) and sum_j dm2_j N dx / (2 n0 L) = sum_i v_i d_v_i.  Every term is a 64-bit integer in the
+ * unit 2^(e + b - 61), 2^b >= N,
  * where 2^e exceeds the largest bound |iota|, |d_v| + |iota v|, 2 |v d_v| + |iota| v^2 on one term of that moment, direction and
  * environment: the result is bitwise reproducible, K directions in one call equal K calls, and nothing depends on blocks_per_env,
  * the schedule or the environment's place in the batch.  A moment whose terms are all zero is +0; a non-finite tangent or velocity
