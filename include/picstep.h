@@ -650,6 +650,26 @@ int pic_tape_moments(pic_handle* h, int mem_kind, double* m);
 int pic_tape_tangent_moments(pic_handle* h, int K, const double* d_ext, const double* d_actions, const void* d_x0, const void* d_v0,
                              int mem_kind, double* d_hist, void* d_x, void* d_v, double* d_E_mesh, double* d_kl, double* d_moments);
 
+/* Copies of whole environments on the device: afterwards environment e of dst is environment map[e] of src --
+ * particles (the whole padded row, byte for byte), n, E_mesh, phi, the energies and the cached first deposit of the next step
+ * (the resident schedule's hand-over mesh and carried cells included), so that a copy continues bit for bit like its source.
+ * map: dst->num_envs entries in mem_kind memory.
+ *   src == dst (fork): map[e] == e keeps environment e; every other entry must name a kept environment (map[map[e]] == map[e]),
+ *     so no source is overwritten while it is read.  map = NULL is refused.
+ *   src != dst (broadcast / restore): every environment of dst is overwritten; 0 <= map[e] < src->num_envs; map = NULL is the
+ *     identity and needs equal num_envs.  The handles must agree in N, Ng, L, n0, dt, particle and position dtype, interpol,
+ *     accumulator, integrator and device (PIC_EINVAL names the field); num_envs, blocks_per_env and the schedule may differ.
+ *     Where they lay a cache out differently, dst's cache is dropped as pic_invalidate drops it (the same bits afterwards).
+ * PIC_ESTATE if src has no state, if either handle is inside a staged step, if dst has a tape open, or if a device map meets
+ * a dst without state (an entry the kernels refuse keeps its environment, so there must be one to keep).  A recorder on dst stays
+ * on and counts no step; pic_bad_count of either handle is unchanged; dst has state afterwards.
+ * Asynchronous on dst's stream; between two handles dst's stream first waits for the work queued on src's, and src's stream then
+ * waits for the copy.  A host map is checked on the host (PIC_EINVAL, nothing copied).  A device map is checked by the kernels
+ * without a host synchronisation: an entry out of range or against the keep rule leaves its environment as it was and adds 1 to
+ * a counter of dst, which pic_copy_envs_rejected reads (it waits for the stream; cumulative since pic_create). */
+int pic_copy_envs(pic_handle* dst, pic_handle* src, const int32_t* map, int mem_kind);
+int pic_copy_envs_rejected(pic_handle* dst, int64_t* count);
+
 int pic_sync(pic_handle* h);
 /* Number of particle positions found non-finite or out of range by the last sweeps (0 = healthy).  Counts the state's
  * particles only: the positions of pic_eval_field / pic_compute_E probes never add to it. */

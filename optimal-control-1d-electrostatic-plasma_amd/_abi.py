@@ -165,6 +165,8 @@ SIGNATURES = {
     "pic_schedule": [_vp],
     "pic_placement_info": [_vp, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)],
     "pic_placement_stats": [_vp, _vp],
+    "pic_copy_envs": [_vp, _vp, _vp, C.c_int],
+    "pic_copy_envs_rejected": [_vp, _i64p],
     "pic_sync": [_vp],
     "pic_bad_count": [_vp, _i64p],
     "pic_last_error": [_vp],
@@ -337,6 +339,32 @@ class Handle:
     def invalidate(self):
         """Call after writing x / v through the device views (or call refresh())."""
         self._chk(self.lib.pic_invalidate(self._h))
+
+    def copy_envs(self, src, map=None):
+        """pic_copy_envs: environment e of this handle becomes environment map[e] of `src` (a Handle; this one: a fork).  map: a
+        sequence or NumPy array of num_envs indices (checked on the host), an int32 CUDA tensor of that length (passed by
+        pointer and checked by the kernels: copy_envs_rejected), or None (two handles of equal num_envs: the identity).
+        Asynchronous on this handle's stream."""
+        if map is None:
+            ptr, kind = None, PIC_HOST
+        elif hasattr(map, "data_ptr"):
+            if not (map.is_cuda and map.element_size() == 4 and not map.dtype.is_floating_point and map.is_contiguous()
+                    and tuple(map.shape) == (self.num_envs,)):
+                raise ValueError("map must be a contiguous int32 CUDA tensor [num_envs]")
+            ptr, kind = _ptr(int(map.data_ptr())), PIC_DEVICE
+        else:
+            m = np.asarray(map)
+            if m.shape != (self.num_envs,) or m.dtype.kind not in "iu":
+                raise ValueError(f"map must hold num_envs = {self.num_envs} integer indices")
+            m = np.ascontiguousarray(np.clip(m, -1, 2 ** 31 - 1), dtype=np.int32)      # (out of int32's range: refused as -1 / too large)
+            ptr, kind = _ptr(m), PIC_HOST
+        self._chk(self.lib.pic_copy_envs(self._h, src._h, ptr, kind))
+
+    def copy_envs_rejected(self):
+        """Entries of device maps that copy_envs' kernels refused since the handle was created (waits for the stream)."""
+        c = C.c_int64()
+        self._chk(self.lib.pic_copy_envs_rejected(self._h, C.byref(c)))
+        return c.value
 
     def set_readonly_c(self, mode):
         """pic_set_readonly_c: "auto", "off" or "on" -- whether whole steps leave sweep C's stores to sweep D (same bits)."""

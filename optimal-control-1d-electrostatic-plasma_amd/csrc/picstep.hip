@@ -35,7 +35,7 @@
 // pic_solve.h (field solve), pic_aux.h (kernels off the step path); host_plan.h (pic_create's argument checks and the launch plan:
 // no HIP, pinned on a CPU by tests/test_plan_cpu.py), host_place.h (the search for a placement of x and v); this file holds the
 // handle, the launch schedule and the C ABI, but for the host side of the differentiable rollouts: host_diff.h, host_phase.h,
-// host_tape.h, host_tangent.h.
+// host_tape.h, host_tangent.h.  pic_copy.h, host_copy.h and host_copy_map.h: copies of whole environments (pic_copy_envs).
 
 #include <hip/hip_runtime.h>
 
@@ -59,6 +59,7 @@
 #include "picstep.h"
 
 #include "host_plan.h"
+#include "host_copy_map.h"
 
 #include "pic_device.h"
 #include "pic_sweep.h"
@@ -70,6 +71,7 @@
 #include "pic_tangent.h"
 #include "pic_phase.h"
 #include "pic_moments.h"
+#include "pic_copy.h"
 
 
 // ---------------------------------------------------------------------------------------------
@@ -319,6 +321,10 @@ struct __attribute__((visibility("hidden"))) pic_handle : LaunchPlan {      // t
   unsigned long long* probe_bad = nullptr;   // view: bad + 1, where the probes count their non-finite positions (never read: pic_bad_count
                                              // describes the state's particles, and a probe's positions are not among them)
   bool has_state = false;
+  // pic_copy_envs, all allocated by its first call
+  DeviceBuf<int> copy_map;                    // [env] device copy of a host map
+  DeviceBuf<unsigned long long> copy_rejected;   // entries of device maps refused by the kernels since pic_create
+  EventOwner copy_ev[2];                      // a copy between two streams: behind the source's work, behind the copy's read
   // profiling
   bool prof = false;
   std::vector<EventOwner> ev;     // pairs
@@ -1281,6 +1287,7 @@ static int64_t records_ahead(const pic_handle* h, int64_t nsteps) {
 #include "host_moments.h"
 #include "host_tape.h"
 #include "host_tangent.h"
+#include "host_copy.h"
 
 // advance_steps, cut into parts where the recorder or an open tape needs the state between two steps.  A part runs up to the
 // nearest of the next recorded step, the next checkpoint step (every step of a tape with a KL attached, pic_tape_kl_start) and

@@ -40,6 +40,10 @@ class BatchedPIC:
                               interpol, device, blocks_per_env, env_index_base, position_dtype, placement, placement_ms,
                               integrator, readonly_c)
         self.integrator = _abi.INTEGRATOR_NAMES[_abi.integrator_id(integrator)]
+        # what another BatchedPIC of the same physics is made with (env.plan.MPPI builds its samples from it)
+        self._like = dict(N=self.N, N_mesh=self.N_mesh, n0=n0, L=L, dt=self.dt, gamma=gamma, interpol=interpol, device=device,
+                          dtype=self.dtype, accum_dtype=accum_dtype, position_dtype=position_dtype, integrator=self.integrator)
+        self._actuator = None
         self.fixed_positions = self._h.fixed_positions
         self.max_mode = 0                    # (no actuator yet: set_actuator)
         self._torch_stream = None            # (the handle runs on its own stream: use_torch_stream)
@@ -124,6 +128,7 @@ class BatchedPIC:
         """Upload an `E_field`'s basis tables (its linspace mesh included) for `step_actions`."""
         self._h.set_actuator(actuator.basis_cos, actuator.basis_sin)
         self.max_mode = actuator.max_mode
+        self._actuator = actuator
 
     def step_actions(self, actions, nsteps: int = 1):
         """actions [num_envs, 2*max_mode] (cos coefficients, then sin): E_ext is built on the device
@@ -526,6 +531,43 @@ class BatchedPIC:
         for k in ("KE", "PE", "PE_reward"):
             out[k] = torch.as_tensor(_DeviceView(p[k], (self.num_envs,), "<f8"), device=dev)
         return out
+
+    # -- copies of whole environments (pic_copy_envs) --------------------------------------
+    def _copy(self, src, index):
+        """copy_envs with the CUDA-tensor rules of step_actions_torch: a tensor map is read in stream order on a shared stream
+        (use_torch_stream), otherwise the two streams are ordered through the host."""
+        if not hasattr(index, "data_ptr"):
+            return self._h.copy_envs(src, index)
+        shared = self._torch_stream is not None
+        if not shared:
+            import torch
+            torch.cuda.current_stream(self.device).synchronize()
+        self._h.copy_envs(src, index)
+        if not shared:
+            self._h.sync()               # (the map may be a temporary: it must outlive the kernels that read it)
+
+    def fork(self, index):
+        """Environment e becomes a copy of environment index[e], on the device: particles, fields, energies and the cached
+        deposit of the next step, so that a copy continues bit for bit like its source.  index[e] == e keeps e; every other
+        entry must name a kept environment.  index: a sequence, a NumPy array (checked here: PicError, nothing copied) or an
+        int32 CUDA tensor [num_envs] (checked on the device: a wrong entry keeps its environment and counts in
+        `copy_rejected`).  Asynchronous."""
+        self._copy(self._h, index)
+
+    def copy_from(self, other, index=None):
+        """Every environment of this handle becomes a copy of an environment of `other` (a BatchedPIC or a PIC with the same
+        N, N_mesh, L, n0, dt, dtypes, interpol, accumulator, integrator and device; num_envs, blocks_per_env and the schedule
+        may differ).  index: an int (broadcast that environment to all), an array or int32 CUDA tensor [num_envs] of source
+        environments, or None (equal num_envs: environment by environment).  Asynchronous on this handle's stream, ordered
+        behind the work queued on `other` and ahead of its later steps."""
+        src = other._ensure_handle() if hasattr(other, "_ensure_handle") else other._h
+        if index is not None and not hasattr(index, "data_ptr") and np.ndim(index) == 0:
+            index = np.full(self.num_envs, int(index), dtype=np.int64)
+        self._copy(src, index)
+
+    def copy_rejected(self) -> int:
+        """Entries of CUDA-tensor maps that `fork` / `copy_from` refused since this object was created (waits for the stream)."""
+        return self._h.copy_envs_rejected()
 
     def invalidate(self):
         """After a write to x / v through `torch_views()`: drop the cached first deposit of the next step."""

@@ -385,6 +385,14 @@ class PIC:
         info = {"KE": self._cache["energies"][0], "PE": self._cache["energies"][1], "PE_reward": self._cache["energies"][2]}
         return obs, max(1.0 - pe_pre, 0.0), False, info
 
+    def copy_from(self, other):
+        """This environment becomes a copy of `other` (a PIC, or a BatchedPIC of one environment) on the device
+        (pic_copy_envs): the same bits from here on."""
+        src = other._ensure_handle() if hasattr(other, "_ensure_handle") else other._h
+        self._ensure_handle().copy_envs(src, None)
+        self._invalidate()
+        self._fields_hidden = False
+
     # -- rollout recorder (BatchedPIC.start_recording on this object's handle) ------------------------
     def start_recording(self, stride: int = 1, modes: Optional[int] = None, x_bins: int = 0, v_bins: int = 0, phase_bins=None,
                         vmin: float = -25.0, vmax: float = 25.0, feq=None, capacity: int = 4096, phase_dx: float = 0.0,
