@@ -650,6 +650,46 @@ int pic_tape_moments(pic_handle* h, int mem_kind, double* m);
 int pic_tape_tangent_moments(pic_handle* h, int K, const double* d_ext, const double* d_actions, const void* d_x0, const void* d_v0,
                              int mem_kind, double* d_hist, void* d_x, void* d_v, double* d_E_mesh, double* d_kl, double* d_moments);
 
+/* Forward mode through closed loops (additive to ABI 5): the T steps on the tape one at a time, forward in time, in
+ * K <= 8 directions, so that the action tangent of a step can come from the field tangent the step before left -- through the
+ * gain law on the device, or through any policy's Jacobian-vector product on the caller's side between two steps.  Dual to
+ * pic_tape_walk_* and pic_tape_backward_feedback; pic_tape_tangent* keep refusing tapes with steps of pic_step_feedback_gain.
+ * pic_tape_tangent_walk_begin: 1 <= K <= 8; obs_modes M_o = 0 (no observation) or 1 <= M_o < N_mesh; d_x0 / d_v0
+ * [K][num_envs][N] tangents of the tape's starting particles (NULL = 0); d_gain [K][num_envs][2M][2M] (NULL = 0) the tangent of
+ * the gain of every gain-law step on the tape (PIC_EINVAL on a tape without one; tapes whose gains need different tangents inject
+ * dG m_t through d_actions instead).  It computes the tangent of the field the tape started from, dE_0 = K drho(x_0; dx_0), by
+ * a tangent deposit at the stored x_0, and from it d_modes0 [K][num_envs][2 M_o] (per environment Re E_1..E_Mo, then Im: the map
+ * of pic_get_modes and of pic_tape_walk_*'s mode cotangents) and the law's dm_0.
+ * pic_tape_tangent_walk_step advances the next step s (0, 1, ...; its index in *step).  d_ext [K][num_envs][N_mesh] or d_actions
+ * [K][num_envs][2M] (at most one) is this step's injection.  On a gain-law step the device forms
+ * da_s = (G_s dm_s + dG m_s) + d_actions with the taped m_s and G_s (G dm by the forward law's rule: the non-zero G[i][k] in
+ * ascending k; dG m as a plain ascending sum); d_ext there is PIC_EINVAL.  Outputs, each optional, of the state step s left:
+ * d_energies [K][3][num_envs], d_modes [K][num_envs][2 M_o] (the observation o_{s+1}), d_actions_out [K][num_envs][2M] (the
+ * total applied), d_x / d_v [K][num_envs][N], d_E_mesh [K][num_envs][N_mesh].  The first step of a checkpoint segment replays
+ * and compares the segment, as pic_tape_tangent does.  pic_tape_tangent_walk_end, valid once all T steps are walked, returns the
+ * final d_x / d_v; in PIC_HOST memory it returns PIC_ESTATE if a replay differed from the taped forward.
+ * pic_tape_tangent_feedback is the whole tape in one call through the same per-step function: d_actions [K][T][num_envs][2M]
+ * injections, d_modes [K][T][num_envs][2M] the tangents of the law's own modes m_t (zero on other steps), d_actions_out
+ * [K][T][num_envs][2M], the others in pic_tape_tangent's layouts.  On a tape without law steps and with equal inputs, d_hist,
+ * d_E_mesh, d_x and d_v are pic_tape_tangent's bit for bit; with zero injections the walk and the one-call entry give the same
+ * bits.  All outputs are bitwise reproducible and independent of K's grouping, checkpoint_every, blocks_per_env, the schedule
+ * of the forward and the batch.  Every step costs pic_tape_tangent's 11 kernels plus one small one (the modes; none without a law
+ * step or an observation) and one more where a caller's d_actions arrives; all counted in `launches`.
+ * Any step appended to the tape, pic_tape_start / stop / backward*, pic_tape_tangent*, pic_tape_walk_begin and a new begin abandon
+ * a tangent walk; a tangent walk abandons a reverse walk (both replay into the segment buffer).  walk_step / walk_end without a
+ * live walk, or walk_step past T, return PIC_ESTATE.  The working rows, each part rounded up to 256 bytes,
+ *     8 K (num_envs N_mesh + 3 num_envs + 2 M_o num_envs + 2 (2M num_envs) + 4 M^2 num_envs + num_envs max(N_mesh, 2M))   bytes
+ * next to pic_tape_tangent's block, count in `bytes` and against budget_bytes.  The tangents of the per-step KL and of the
+ * moments are not available step by step. */
+int pic_tape_tangent_walk_begin(pic_handle* h, int K, int obs_modes, const void* d_x0, const void* d_v0, const double* d_gain,
+                                int mem_kind, double* d_modes0);
+int pic_tape_tangent_walk_step(pic_handle* h, const double* d_ext, const double* d_actions, int mem_kind, double* d_energies,
+                               double* d_modes, double* d_actions_out, void* d_x, void* d_v, double* d_E_mesh, int64_t* step);
+int pic_tape_tangent_walk_end(pic_handle* h, int mem_kind, void* d_x, void* d_v);
+int pic_tape_tangent_feedback(pic_handle* h, int K, const double* d_gain, const void* d_x0, const void* d_v0,
+                              const double* d_actions, int mem_kind, double* d_hist, double* d_modes, double* d_actions_out,
+                              void* d_x, void* d_v, double* d_E_mesh);
+
 /* Copies of whole environments on the device: afterwards environment e of dst is environment map[e] of src --
  * particles (the whole padded row, byte for byte), n, E_mesh, phi, the energies and the cached first deposit of the next step
  * (the resident schedule's hand-over mesh and carried cells included), so that a copy continues bit for bit like its source.

@@ -160,6 +160,10 @@ SIGNATURES = {
     "pic_tape_moments_start": [_vp],
     "pic_tape_moments": [_vp, C.c_int, _vp],
     "pic_tape_tangent_moments": [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pic_tape_tangent_walk_begin": [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp],
+    "pic_tape_tangent_walk_step": [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _i64p],
+    "pic_tape_tangent_walk_end": [_vp, C.c_int, _vp, _vp],
+    "pic_tape_tangent_feedback": [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp],
     "pic_set_stream": [_vp, _vp],
     "pic_own_stream": [_vp],
     "pic_schedule": [_vp],
@@ -890,6 +894,29 @@ class Handle:
         """pic_tape_tangent_moments on addresses (int, 0 = NULL) in mem_kind memory."""
         p = _ptrs(d_ext, d_actions, d_x0, d_v0, hist, x, v, E_mesh, kl, moments)
         self._chk(self.lib.pic_tape_tangent_moments(self._h, int(K), p[0], p[1], p[2], p[3], int(mem_kind), *p[4:]))
+
+    # -- forward mode through closed loops (pic_tape_tangent_walk_*, DESIGN.md 7n) ------------------------
+    def tape_tangent_walk_begin(self, K, obs_modes, d_x0, d_v0, d_gain, mem_kind, d_modes0):
+        """pic_tape_tangent_walk_begin on addresses (int, 0 = NULL) in mem_kind memory."""
+        p = _ptrs(d_x0, d_v0, d_gain, d_modes0)
+        self._chk(self.lib.pic_tape_tangent_walk_begin(self._h, int(K), int(obs_modes), p[0], p[1], p[2], int(mem_kind), p[3]))
+
+    def tape_tangent_walk_step(self, d_ext, d_actions, mem_kind, d_energies, d_modes, d_actions_out, d_x, d_v, d_E_mesh):
+        """pic_tape_tangent_walk_step on addresses (int, 0 = NULL) in mem_kind memory; returns the step."""
+        p = _ptrs(d_ext, d_actions, d_energies, d_modes, d_actions_out, d_x, d_v, d_E_mesh)
+        step = C.c_int64(-1)
+        self._chk(self.lib.pic_tape_tangent_walk_step(self._h, p[0], p[1], int(mem_kind), *p[2:], C.byref(step)))
+        return step.value
+
+    def tape_tangent_walk_end(self, mem_kind, d_x, d_v):
+        """pic_tape_tangent_walk_end on addresses (int, 0 = NULL) in mem_kind memory."""
+        p = _ptrs(d_x, d_v)
+        self._chk(self.lib.pic_tape_tangent_walk_end(self._h, int(mem_kind), p[0], p[1]))
+
+    def tape_tangent_feedback(self, K, d_gain, d_x0, d_v0, d_actions, mem_kind, d_hist, d_modes, d_actions_out, d_x, d_v, d_E_mesh):
+        """pic_tape_tangent_feedback on addresses (int, 0 = NULL) in mem_kind memory."""
+        p = _ptrs(d_gain, d_x0, d_v0, d_actions, d_hist, d_modes, d_actions_out, d_x, d_v, d_E_mesh)
+        self._chk(self.lib.pic_tape_tangent_feedback(self._h, int(K), p[0], p[1], p[2], p[3], int(mem_kind), *p[4:]))
 
     def stream_probe(self, repeats=10):
         g = C.c_double()

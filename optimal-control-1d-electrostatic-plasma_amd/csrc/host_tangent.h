@@ -130,6 +130,53 @@ static void tangent_pass(pic_handle* h, const AdjStep& st, const TanArgs& ta, co
 }
 }  // extern "C++"
 
+// the launch geometry of a forward-mode step: a deposit workgroup holds kd directions' meshes in 64 KB of LDS; groups of them run
+// side by side (grid z); one mesh workgroup per (environment, direction)
+struct TanGeom {
+  int kd;
+  dim3 dgrid, mgrid;
+  size_t dlds;
+};
+
+static TanGeom tangent_geom(const pic_handle* h, const WalkGeom& g, int K) {
+  const int E = h->cfg.num_envs, Ng = h->cfg.Ng;
+  const int kd = std::min<int>(K, (int)std::max<size_t>(1, 65536 / ((size_t)(Ng + 1) * sizeof(unsigned long long))));
+  return {kd, dim3(g.pgrid.x, E, (K + kd - 1) / kd), dim3(E, K), (size_t)kd * (Ng + 1) * sizeof(unsigned long long)};
+}
+
+// Forward-mode step i of the replayed segment (pic_tape_tangent, the tangent walk and pic_tape_tangent_feedback all advance
+// through here): deposit -> mesh -> pass for the sub-stages 1..3, then the deposit and mesh of the state the step left.  m: the
+// step's injection and outputs (its M is set here).  dkl / dmom: direction 0's row of this step, or null.
+static int tangent_step(pic_handle* h, const TanArgs& ta, const AdjArgs& a, const WalkGeom& g, const TanGeom& tg, int64_t i, TanMeshIO m,
+                        double* dkl, long long kl_dstride, double* dmom, long long mom_dstride) {
+  Tape& t = h->tape;
+  const size_t part = (size_t)h->cfg.num_envs * h->ld, mesh = (size_t)h->cfg.num_envs * h->cfg.Ng;
+  const double* x = t.seg + (size_t)i * 2 * part;
+  const AdjStep st{x, x + part, t.F + (size_t)i * 3 * mesh, (long long)mesh};
+  m.M = t.M + (size_t)i * mesh;
+  tangent_deposit<1>(h, st, ta, a, tg.dgrid, tg.dlds, tg.kd);
+  hipLaunchKernelGGL(tangent_mesh_kernel<1>, tg.mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, ta, m, a);
+  tangent_pass<1>(h, st, ta, a, g.pgrid);
+  tangent_deposit<2>(h, st, ta, a, tg.dgrid, tg.dlds, tg.kd);
+  hipLaunchKernelGGL(tangent_mesh_kernel<2>, tg.mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, ta, m, a);
+  tangent_pass<2>(h, st, ta, a, g.pgrid);
+  tangent_deposit<3>(h, st, ta, a, tg.dgrid, tg.dlds, tg.kd);
+  hipLaunchKernelGGL(tangent_mesh_kernel<3>, tg.mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, ta, m, a);
+  tangent_pass<3>(h, st, ta, a, g.pgrid);
+  if (dkl) {                        // the state is (dq_4, dp_3) = (dx', dv'): the tangent of the KL~ of the state the step left
+    const double* xn = t.seg + (size_t)(i + 1) * 2 * part;
+    if (int rc = tangent_kl_step(h, ta, xn, xn + part, dkl, kl_dstride)) return rc;
+  }
+  if (dmom) {                       // the same tangent state against the same replayed state: the moments' tangents (7l)
+    const double* xn = t.seg + (size_t)(i + 1) * 2 * part;
+    if (int rc = tangent_moments_step(h, ta, xn, xn + part, dmom, mom_dstride)) return rc;
+  }
+  tangent_deposit<4>(h, st, ta, a, tg.dgrid, tg.dlds, tg.kd);
+  hipLaunchKernelGGL(tangent_mesh_kernel<4>, tg.mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, ta, m, a);
+  t.launches += 11;
+  return PIC_OK;
+}
+
 // pic_tape_tangent (d_kl = null: the KL, if any, is ignored), pic_tape_tangent_kl and pic_tape_tangent_moments (d_moments = null:
 // no kernel, byte or launch of the moments')
 static int tape_tangent(pic_handle* h, const char* who, int K, const double* d_ext, const double* d_actions, const void* d_x0,
@@ -154,7 +201,7 @@ static int tape_tangent(pic_handle* h, const char* who, int K, const double* d_e
   const int E = h->cfg.num_envs, Ng = h->cfg.Ng, Mact = h->act_modes;
   const bool host = mem_kind == PIC_HOST;
   const size_t N = h->cfg.N, part = (size_t)E * h->ld, mesh = (size_t)E * Ng, row = N * sizeof(double);
-  t.walk = false;                     // (a walk's replayed segment is about to be overwritten)
+  t.walk = t.twalk = false;           // (a walk's replayed segment is about to be overwritten)
   t.launches = 0;
   HIPCHK(h, hipMemsetAsync(t.counters, 0, 2 * sizeof(unsigned long long), h->stream));
   if (T == 0) {                       // no step: the tangent of the final particles is the initial one (NULL: 0)
@@ -215,10 +262,7 @@ static int tape_tangent(pic_handle* h, const char* who, int K, const double* d_e
   const WalkGeom g = walk_geom(h);
   hipLaunchKernelGGL(tangent_start_kernel, g.pgrid, dim3(ABLOCK), 0, h->stream, ta, a);
   ++t.launches;
-  // a deposit workgroup holds kd directions' meshes in 64 KB of LDS; groups of them run side by side (grid z)
-  const int kd = std::min<int>(K, (int)std::max<size_t>(1, 65536 / ((size_t)(Ng + 1) * sizeof(unsigned long long))));
-  const dim3 dgrid(g.pgrid.x, E, (K + kd - 1) / kd), mgrid(E, K);
-  const size_t dlds = (size_t)kd * (Ng + 1) * sizeof(unsigned long long);
+  const TanGeom tg = tangent_geom(h, g, K);
   TanMeshIO io{};
   io.basis = h->basis; io.Mact = Mact;
   io.in_dstride = d_ext ? (long long)(T * mesh) : (long long)(T * E * 2 * Mact);
@@ -230,36 +274,14 @@ static int tape_tangent(pic_handle* h, const char* who, int K, const double* d_e
     const int64_t t0 = sgi * t.every, len = std::min<int64_t>(t.every, T - t0);
     for (int64_t i = 0; i < len; ++i) {
       const int64_t s = t0 + i;
-      const double* x = t.seg + (size_t)i * 2 * part;
-      const AdjStep st{x, x + part, t.F + (size_t)i * 3 * mesh, (long long)mesh};
       TanMeshIO m = io;
       m.ext = d_ext ? din + (size_t)s * mesh : nullptr;
       m.act = d_actions ? din + (size_t)s * E * 2 * Mact : nullptr;
-      m.M = t.M + (size_t)i * mesh;
       m.hist = dhist ? dhist + (size_t)s * 3 * E : nullptr;
       m.Emesh = dem ? dem + (size_t)s * mesh : nullptr;
-      tangent_deposit<1>(h, st, ta, a, dgrid, dlds, kd);
-      hipLaunchKernelGGL(tangent_mesh_kernel<1>, mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, ta, m, a);
-      tangent_pass<1>(h, st, ta, a, g.pgrid);
-      tangent_deposit<2>(h, st, ta, a, dgrid, dlds, kd);
-      hipLaunchKernelGGL(tangent_mesh_kernel<2>, mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, ta, m, a);
-      tangent_pass<2>(h, st, ta, a, g.pgrid);
-      tangent_deposit<3>(h, st, ta, a, dgrid, dlds, kd);
-      hipLaunchKernelGGL(tangent_mesh_kernel<3>, mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, ta, m, a);
-      tangent_pass<3>(h, st, ta, a, g.pgrid);
-      if (dkl) {                        // the state is (dq_4, dp_3) = (dx', dv'): the tangent of the KL~ of the state step s left
-        const double* xn = t.seg + (size_t)(i + 1) * 2 * part;
-        rc = tangent_kl_step(h, ta, xn, xn + part, dkl + (size_t)s * E, (long long)(T * E));
-        if (rc) return rc;
-      }
-      if (dmom) {                       // the same tangent state against the same replayed state: the moments' tangents (7l)
-        const double* xn = t.seg + (size_t)(i + 1) * 2 * part;
-        rc = tangent_moments_step(h, ta, xn, xn + part, dmom + (size_t)s * 3 * mesh, (long long)(T * 3 * mesh));
-        if (rc) return rc;
-      }
-      tangent_deposit<4>(h, st, ta, a, dgrid, dlds, kd);
-      hipLaunchKernelGGL(tangent_mesh_kernel<4>, mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, ta, m, a);
-      t.launches += 11;
+      rc = tangent_step(h, ta, a, g, tg, i, m, dkl ? dkl + (size_t)s * E : nullptr, (long long)(T * E),
+                        dmom ? dmom + (size_t)s * 3 * mesh : nullptr, (long long)(T * 3 * mesh));
+      if (rc) return rc;
     }
     HIPCHK(h, hipGetLastError());
   }

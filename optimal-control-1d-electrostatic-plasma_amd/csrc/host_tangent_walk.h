@@ -1,0 +1,346 @@
+// host_tangent_walk.h -- included by picstep.hip alone, inside its extern "C" block, behind host_tangent.h (tangent_step is the walk's)
+#pragma once
+// ---------------------------------------------------------------------------------------------
+// Forward mode through closed loops (include/picstep.h: pic_tape_tangent_walk_*, pic_tape_tangent_feedback; kernels: pic_tangent.h;
+// DESIGN.md 7n): the tape's steps one at a time, forward in time, with the action tangent of a step fed from the field tangent
+// the step before left -- by the gain law on the device, or by the caller between two steps
+// ---------------------------------------------------------------------------------------------
+// the working rows of a walk of kc directions observing mo modes (M: the actuator's modes): the field tangent the last step left
+// dM [kc][env][Ng], its energies' tangents [kc][3][env], the observation's tangent [kc][env][2 mo], the law's dm [kc][env][2M],
+// the action tangent of the step at hand da [kc][env][2M], dG [kc][env][2M][2M], and a step's injection from host memory
+struct TanWalkViews {
+  double* dM = nullptr;
+  double* hist = nullptr;
+  double* obs = nullptr;
+  double* dm = nullptr;
+  double* da = nullptr;
+  double* dG = nullptr;
+  double* in = nullptr;
+};
+
+static size_t tanwalk_parts(Carver c, const pic_handle* h, int kc, int mo, TanWalkViews& v) {
+  const size_t E = h->cfg.num_envs, mesh = E * h->cfg.Ng, arow = E * 2 * h->act_modes, k = (size_t)kc;
+  c.take(v.dM, k * mesh);
+  c.take(v.hist, k * 3 * E);
+  c.take(v.obs, k * E * 2 * mo);
+  c.take(v.dm, k * arow);
+  c.take(v.da, k * arow);
+  c.take(v.dG, k * arow * 2 * h->act_modes);
+  c.take(v.in, k * std::max(mesh, arow));
+  return c.at;
+}
+
+// that block for K directions and mo modes, within budget_bytes; on failure the tape keeps what it had
+static int tanwalk_reserve(pic_handle* h, int K, int mo, const std::string& w) {
+  Tape& t = h->tape;
+  if (t.tw_cap_k >= K && t.tw_cap_mo >= mo && t.tw_block) return PIC_OK;
+  const int kc = std::max(K, t.tw_cap_k), mc = std::max(mo, t.tw_cap_mo);
+  TanWalkViews scratch;
+  const size_t bytes = tanwalk_parts(Carver{}, h, kc, mc, scratch);
+  if (t.budget > 0 && t.bytes - t.tw_bytes + bytes > (size_t)t.budget)
+    return fail(h, PIC_ENOMEM, w + ": the walk's working rows (" + std::to_string(bytes) + " bytes) would take the tape past budget_bytes (pic_tape_start)");
+  DeviceBuf<void> b;
+  const int rc = regrow(h, b, bytes, (w + ": the walk's working rows do not fit on the device").c_str());
+  if (rc) return rc;
+  if (t.tw_block) HIPCHK(h, hipStreamSynchronize(h->stream));      // queued work may still read the old block
+  t.tw_block = std::move(b);
+  t.bytes = t.bytes - t.tw_bytes + bytes;
+  t.tw_bytes = bytes;
+  t.tw_cap_k = kc; t.tw_cap_mo = mc;
+  return PIC_OK;
+}
+
+static TanWalkViews tanwalk_views(const pic_handle* h) {
+  TanWalkViews v;
+  tanwalk_parts(Carver{static_cast<char*>(h->tape.tw_block.get())}, h, h->tape.tw_cap_k, h->tape.tw_cap_mo, v);
+  return v;
+}
+
+// the tangent block's views for K live directions (as pic_tape_tangent sets them)
+static TanArgs tanwalk_state(const pic_handle* h, int K) {
+  const Tape& t = h->tape;
+  const size_t part = (size_t)h->cfg.num_envs * h->ld;
+  TanArgs ta{};
+  tangent_parts(Carver{static_cast<char*>(t.tan_block.get())}, h, t.tan_k, ta);
+  ta.dstride = (long long)(2 * part); ta.vofs = (long long)part;
+  ta.K = K; ta.num_envs = h->cfg.num_envs;
+  return ta;
+}
+
+// the modes the gain law of this tape reads (0: no law step was taped)
+static int tanwalk_law_modes(const pic_handle* h) { return h->tape.lact ? h->act_modes : 0; }
+
+static bool tanwalk_is_law(const pic_handle* h, int64_t s) {
+  const Tape& t = h->tape;
+  return s >= 0 && s < t.steps && !t.law.empty() && t.law[(size_t)s] >= 0;
+}
+
+// K rows of n doubles from the walk's contiguous rows to the caller's array in mem_kind's memory, its rows `pitch` doubles apart
+static hipError_t tanwalk_rows_out(pic_handle* h, double* dst, size_t pitch, const double* src, size_t n, int K, int mem_kind) {
+  if (!dst || !n) return hipSuccess;
+  const hipMemcpyKind kind = copy_kind(mem_kind, hipMemcpyDeviceToHost);
+  if (pitch == n) return hipMemcpyAsync(dst, src, (size_t)K * n * sizeof(double), kind, h->stream);
+  return hipMemcpy2DAsync(dst, pitch * sizeof(double), src, n * sizeof(double), n * sizeof(double), (size_t)K, kind, h->stream);
+}
+
+static hipError_t tanwalk_rows_zero(pic_handle* h, double* dst, size_t pitch, size_t n, int K, int mem_kind) {
+  if (!dst || !n) return hipSuccess;
+  if (mem_kind == PIC_HOST) {
+    for (int d = 0; d < K; ++d) std::memset(dst + (size_t)d * pitch, 0, n * sizeof(double));
+    return hipSuccess;
+  }
+  return hipMemset2DAsync(dst, pitch * sizeof(double), 0, n * sizeof(double), (size_t)K, h->stream);
+}
+
+// dm = J dM of the field tangent in v.dM (the field step s_next reads): the observation's tangent, the law's dm, and the da row of
+// step s_next if it is a law step (pic_tangent.h: tangent_law_kernel).  Nothing to do without a law block and an observation.
+static void tanwalk_law(pic_handle* h, const TanWalkViews& v, int64_t s_next) {
+  Tape& t = h->tape;
+  const int Ml = tanwalk_law_modes(h), mo = t.tw_mo, E = h->cfg.num_envs;
+  if (Ml == 0 && mo == 0) return;
+  const bool lawstep = tanwalk_is_law(h, s_next);
+  TanLawArgs l{};
+  l.dM = v.dM; l.tw = (const double*)h->tw; l.rows = h->tw_rows;
+  l.obs = mo ? v.obs : nullptr;
+  l.dm = v.dm;
+  l.gain = lawstep ? (const double*)t.gains[(size_t)t.law[(size_t)s_next]] : nullptr;
+  l.dgain = lawstep && t.tw_dgain ? v.dG : nullptr;
+  l.modes = lawstep ? t.lmodes + (size_t)s_next * E * 2 * Ml : nullptr;
+  l.da = v.da;
+  l.Ng = h->cfg.Ng; l.M = Ml; l.Mo = mo; l.num_envs = E;
+  hipLaunchKernelGGL(tangent_law_kernel, dim3(E, t.tw_k), dim3(ABLOCK), 0, h->stream, l);
+  ++t.launches;
+}
+
+extern "C++" {
+static void tangent_start_deposit(pic_handle* h, const double* x, const TanArgs& ta, const AdjArgs& a, const TanGeom& tg) {
+  if (tg.kd == 1) hipLaunchKernelGGL((tangent_start_deposit_kernel<1>), tg.dgrid, dim3(ABLOCK), tg.dlds, h->stream, x, ta, a, tg.kd);
+  else if (tg.kd <= 4) hipLaunchKernelGGL((tangent_start_deposit_kernel<4>), tg.dgrid, dim3(ABLOCK), tg.dlds, h->stream, x, ta, a, tg.kd);
+  else hipLaunchKernelGGL((tangent_start_deposit_kernel<8>), tg.dgrid, dim3(ABLOCK), tg.dlds, h->stream, x, ta, a, tg.kd);
+}
+}  // extern "C++"
+
+// pic_tape_tangent_walk_begin, and the start of pic_tape_tangent_feedback (mo = 0)
+static int tanwalk_open(pic_handle* h, const char* who, int K, int mo, const void* d_x0, const void* d_v0, const double* d_gain,
+                        int mem_kind, double* d_modes0) {
+  Tape& t = h->tape;
+  const std::string w(who);
+  if (int rc = check_tape_open(h, who)) return rc;
+  if (K < 1 || K > kMaxTangents) return fail(h, PIC_EINVAL, w + ": need 1 <= K <= " + std::to_string(kMaxTangents));
+  if (mo < 0 || mo >= h->cfg.Ng) return fail(h, PIC_EINVAL, w + ": need obs_modes = 0 or 1 <= obs_modes < N_mesh");
+  if (int rc = check_mem_kind(h, mem_kind, who)) return rc;
+  if (d_modes0 && mo == 0) return fail(h, PIC_EINVAL, w + ": d_modes0 needs obs_modes >= 1");
+  const int64_t T = t.steps;
+  bool law = false;
+  for (int64_t s = 0; s < T && !law; ++s) law = tanwalk_is_law(h, s);
+  if (d_gain && !law) return fail(h, PIC_EINVAL, w + ": d_gain needs a step of pic_step_feedback_gain on the tape");
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  t.walk = t.twalk = false;           // (a walk's replayed segment is about to be overwritten)
+  const int E = h->cfg.num_envs, Ng = h->cfg.Ng, Ml = tanwalk_law_modes(h);
+  const size_t N = h->cfg.N, part = (size_t)E * h->ld, mesh = (size_t)E * Ng, arow = (size_t)E * 2 * h->act_modes;
+  int rc = std::max(Ml, mo) > 0 ? ensure_twiddle(h, std::max(Ml, mo)) : PIC_OK;
+  if (!rc) rc = tangent_reserve(h, K, w);
+  if (!rc) rc = tanwalk_reserve(h, K, mo, w);
+  if (rc) return rc;
+  t.launches = 0;
+  HIPCHK(h, hipMemsetAsync(t.counters, 0, 2 * sizeof(unsigned long long), h->stream));
+  const TanArgs ta = tanwalk_state(h, K);
+  const TanWalkViews v = tanwalk_views(h);
+  HIPCHK(h, hipMemsetAsync(ta.acc, 0, Carver::upto(ta.acc, ta.umax + 3 * (size_t)t.tan_k * E), h->stream));     // acc, ke, umax
+  for (int d = 0; d < K; ++d) {       // (dx_0, dv_0) of every direction into the state rows (padded to ld)
+    const void* ins[2] = {d_x0, d_v0};
+    for (int k = 0; k < 2; ++k) {
+      double* dst = ta.st + (size_t)d * 2 * part + (size_t)k * part;
+      if (ins[k]) rc = upload(h, dst, static_cast<const double*>(ins[k]) + (size_t)d * E * N, mem_kind);
+      else HIPCHK(h, hipMemsetAsync(dst, 0, part * sizeof(double), h->stream));
+      if (rc) return rc;
+    }
+  }
+  if (d_gain) HIPCHK(h, device_fill(h, v.dG, d_gain, (size_t)K * arow * 2 * h->act_modes * sizeof(double), mem_kind));
+  t.tw_k = K; t.tw_mo = mo; t.tw_dgain = d_gain != nullptr;
+  const AdjArgs a = adjoint_args(h);
+  const WalkGeom g = walk_geom(h);
+  if (Ml > 0 || mo > 0) {
+    // the tangent of the field the tape started from, dE_0 = K drho(x_0; dx_0), read by the observation o_0 and by a first law step
+    const TanGeom tg = tangent_geom(h, g, K);
+    if (d_x0) {
+      hipLaunchKernelGGL(tangent_x_max_kernel, g.pgrid, dim3(ABLOCK), 0, h->stream, ta, a);
+      tangent_start_deposit(h, t.ck, ta, a, tg);
+      t.launches += 2;
+    }
+    HIPCHK(h, hipMemsetAsync(ta.dF, 0, mesh * sizeof(double), h->stream));      // stands in for a post-step field: no energies here
+    TanMeshIO m{};
+    m.basis = h->basis; m.Mact = h->act_modes;
+    m.M = ta.dF; m.Emesh = v.dM; m.out_mstride = (long long)mesh;
+    hipLaunchKernelGGL(tangent_mesh_kernel<4>, tg.mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, ta, m, a);
+    ++t.launches;
+    tanwalk_law(h, v, 0);
+  }
+  hipLaunchKernelGGL(tangent_start_kernel, g.pgrid, dim3(ABLOCK), 0, h->stream, ta, a);
+  ++t.launches;
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, tanwalk_rows_out(h, d_modes0, (size_t)E * 2 * mo, v.obs, (size_t)E * 2 * mo, K, mem_kind));
+  if (d_modes0 && mem_kind == PIC_HOST) HIPCHK(h, hipStreamSynchronize(h->stream));
+  t.twalk = true;
+  t.tnext = 0;
+  return PIC_OK;
+}
+
+// what a step of the walk takes and returns, in mem_kind's memory: every array's direction d lies d * its pitch doubles behind
+// direction 0's row (the walk: one step's arrays; pic_tape_tangent_feedback: rows of the whole trajectory's)
+struct TanWalkIO {
+  const double* ext = nullptr;        // [env][Ng]
+  const double* act = nullptr;        // [env][2M]
+  size_t in_pitch = 0;
+  double* hist = nullptr;             // [3][env]
+  size_t hist_pitch = 0;
+  double* obs = nullptr;              // [env][2 Mo] of the field the step left; contiguous directions
+  double* lawm = nullptr;             // [env][2M] the law's dm of the field the step read (zero on other steps)
+  double* aout = nullptr;             // [env][2M] the action tangent applied
+  size_t act_pitch = 0;               // of lawm and aout
+  double* em = nullptr;               // [env][Ng]
+  size_t em_pitch = 0;
+};
+
+// step t.tnext of a live walk: first the replay of its segment if it is the segment's first step
+static int tanwalk_advance(pic_handle* h, const TanWalkIO& io, int mem_kind) {
+  Tape& t = h->tape;
+  const int E = h->cfg.num_envs, K = t.tw_k, Mact = h->act_modes;
+  const size_t mesh = (size_t)E * h->cfg.Ng, arow = (size_t)E * 2 * Mact;
+  const int64_t s = t.tnext, sgi = s / t.every, i = s - sgi * t.every;
+  const AdjArgs a = adjoint_args(h);
+  const WalkGeom g = walk_geom(h);
+  const TanGeom tg = tangent_geom(h, g, K);
+  const TanArgs ta = tanwalk_state(h, K);
+  const TanWalkViews v = tanwalk_views(h);
+  const bool lawstep = tanwalk_is_law(h, s), host = mem_kind == PIC_HOST;
+  if (i == 0)
+    if (int rc = walk_replay(h, sgi, a, g)) return rc;
+  if (io.lawm) HIPCHK(h, lawstep ? tanwalk_rows_out(h, io.lawm, io.act_pitch, v.dm, arow, K, mem_kind)
+                                 : tanwalk_rows_zero(h, io.lawm, io.act_pitch, arow, K, mem_kind));
+  TanMeshIO m{};
+  m.basis = h->basis; m.Mact = Mact;
+  m.hist = io.hist ? v.hist : nullptr; m.out_hstride = (long long)(3 * E);
+  m.Emesh = v.dM; m.out_mstride = (long long)mesh;
+  // the injection: device memory is read where it lies, host memory through the walk's row
+  const double* in = io.ext ? io.ext : io.act;
+  size_t in_pitch = io.in_pitch;
+  if (in && host) {
+    const size_t n = io.ext ? mesh : arow;
+    HIPCHK(h, hipMemcpy2DAsync(v.in, n * sizeof(double), in, in_pitch * sizeof(double), n * sizeof(double), (size_t)K, hipMemcpyHostToDevice,
+                               h->stream));
+    in = v.in;
+    in_pitch = n;
+  }
+  if (io.ext) {
+    m.ext = in; m.in_dstride = (long long)in_pitch;
+  } else if (io.act || lawstep) {
+    if (io.act) {                     // da_s = (G dm + dG m) + the caller's, or the caller's alone
+      hipLaunchKernelGGL(tangent_action_kernel, dim3((unsigned)((arow + ABLOCK - 1) / ABLOCK), K), dim3(ABLOCK), 0, h->stream, v.da, in,
+                         (long long)in_pitch, (int)arow, lawstep ? 1 : 0);
+      ++t.launches;
+    }
+    m.act = v.da; m.in_dstride = (long long)arow;
+  }
+  if (io.aout) HIPCHK(h, m.act ? tanwalk_rows_out(h, io.aout, io.act_pitch, v.da, arow, K, mem_kind)
+                               : tanwalk_rows_zero(h, io.aout, io.act_pitch, arow, K, mem_kind));
+  if (int rc = tangent_step(h, ta, a, g, tg, i, m, nullptr, 0, nullptr, 0)) return rc;
+  tanwalk_law(h, v, s + 1);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, tanwalk_rows_out(h, io.hist, io.hist_pitch, v.hist, (size_t)3 * E, K, mem_kind));
+  HIPCHK(h, tanwalk_rows_out(h, io.obs, (size_t)E * 2 * t.tw_mo, v.obs, (size_t)E * 2 * t.tw_mo, K, mem_kind));
+  HIPCHK(h, tanwalk_rows_out(h, io.em, io.em_pitch, v.dM, mesh, K, mem_kind));
+  ++t.tnext;
+  return PIC_OK;
+}
+
+// (dx, dv) of every direction out of the state rows (each may be null)
+static int tanwalk_state_out(pic_handle* h, int mem_kind, void* d_x, void* d_v) {
+  const Tape& t = h->tape;
+  const size_t part = (size_t)h->cfg.num_envs * h->ld, EN = (size_t)h->cfg.num_envs * h->cfg.N;
+  const TanArgs ta = tanwalk_state(h, t.tw_k);
+  void* outs[2] = {d_x, d_v};
+  for (int d = 0; d < t.tw_k; ++d)
+    for (int k = 0; k < 2; ++k)
+      if (outs[k])
+        if (int rc = download(h, static_cast<double*>(outs[k]) + (size_t)d * EN, ta.st + (size_t)d * 2 * part + (size_t)k * part, mem_kind)) return rc;
+  return PIC_OK;
+}
+
+int pic_tape_tangent_walk_begin(pic_handle* h, int K, int obs_modes, const void* d_x0, const void* d_v0, const double* d_gain,
+                                int mem_kind, double* d_modes0) {
+  if (!h) return PIC_EINVAL;
+  return tanwalk_open(h, "pic_tape_tangent_walk_begin", K, obs_modes, d_x0, d_v0, d_gain, mem_kind, d_modes0);
+}
+
+int pic_tape_tangent_walk_step(pic_handle* h, const double* d_ext, const double* d_actions, int mem_kind, double* d_energies,
+                               double* d_modes, double* d_actions_out, void* d_x, void* d_v, double* d_E_mesh, int64_t* step) {
+  const char* who = "pic_tape_tangent_walk_step";
+  if (!h) return PIC_EINVAL;
+  Tape& t = h->tape;
+  if (!t.on || !t.twalk) return fail(h, PIC_ESTATE, std::string(who) + ": no tangent walk in progress (pic_tape_tangent_walk_begin)");
+  if (t.tnext >= t.steps) return fail(h, PIC_ESTATE, std::string(who) + ": every step has been walked (pic_tape_tangent_walk_end)");
+  if (int rc = check_mem_kind(h, mem_kind, who)) return rc;
+  if (d_ext && d_actions) return fail(h, PIC_EINVAL, std::string(who) + ": d_ext and d_actions are both given (at most one)");
+  if (d_ext && tanwalk_is_law(h, t.tnext))
+    return fail(h, PIC_EINVAL, std::string(who) + ": d_ext on a step of pic_step_feedback_gain (inject through d_actions)");
+  if (d_modes && t.tw_mo == 0) return fail(h, PIC_EINVAL, std::string(who) + ": d_modes needs a walk begun with obs_modes >= 1");
+  if (int rc = check_tape_actuator(h, d_actions, "d_actions", who)) return rc;
+  if (int rc = check_tape_actuator(h, d_actions_out, "d_actions_out", who)) return rc;
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  const size_t E = h->cfg.num_envs, mesh = E * h->cfg.Ng, arow = E * 2 * h->act_modes;
+  TanWalkIO io;
+  io.ext = d_ext; io.act = d_actions; io.in_pitch = d_ext ? mesh : arow;
+  io.hist = d_energies; io.hist_pitch = 3 * E;
+  io.obs = d_modes;
+  io.aout = d_actions_out; io.act_pitch = arow;
+  io.em = d_E_mesh; io.em_pitch = mesh;
+  const int64_t s = t.tnext;
+  int rc = tanwalk_advance(h, io, mem_kind);
+  if (!rc) rc = tanwalk_state_out(h, mem_kind, d_x, d_v);
+  if (rc) { t.twalk = false; return rc; }
+  if (mem_kind == PIC_HOST && (d_energies || d_modes || d_actions_out || d_x || d_v || d_E_mesh)) HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (step) *step = s;
+  return PIC_OK;
+}
+
+int pic_tape_tangent_walk_end(pic_handle* h, int mem_kind, void* d_x, void* d_v) {
+  const char* who = "pic_tape_tangent_walk_end";
+  if (!h) return PIC_EINVAL;
+  Tape& t = h->tape;
+  if (!t.on || !t.twalk) return fail(h, PIC_ESTATE, std::string(who) + ": no tangent walk in progress (pic_tape_tangent_walk_begin)");
+  if (t.tnext < t.steps)
+    return fail(h, PIC_ESTATE, std::string(who) + ": " + std::to_string(t.steps - t.tnext) + " steps are not walked yet (pic_tape_tangent_walk_step)");
+  if (int rc = check_mem_kind(h, mem_kind, who)) return rc;
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  t.twalk = false;
+  const int rc = tanwalk_state_out(h, mem_kind, d_x, d_v);
+  return rc ? rc : walk_finish(h, who, mem_kind);
+}
+
+int pic_tape_tangent_feedback(pic_handle* h, int K, const double* d_gain, const void* d_x0, const void* d_v0, const double* d_actions,
+                              int mem_kind, double* d_hist, double* d_modes, double* d_actions_out, void* d_x, void* d_v,
+                              double* d_E_mesh) {
+  const char* who = "pic_tape_tangent_feedback";
+  if (!h) return PIC_EINVAL;
+  Tape& t = h->tape;
+  if (int rc = check_tape_open(h, who)) return rc;
+  for (const void* p : {(const void*)d_actions, (const void*)d_modes, (const void*)d_actions_out})
+    if (int rc = check_tape_actuator(h, p, "d_actions, d_modes or d_actions_out", who)) return rc;
+  int rc = tanwalk_open(h, who, K, 0, d_x0, d_v0, d_gain, mem_kind, nullptr);
+  if (rc) return rc;
+  const size_t E = h->cfg.num_envs, mesh = E * h->cfg.Ng, arow = E * 2 * h->act_modes, T = (size_t)t.steps;
+  for (size_t s = 0; s < T; ++s) {
+    TanWalkIO io;
+    io.act = d_actions ? d_actions + s * arow : nullptr; io.in_pitch = T * arow;
+    io.hist = d_hist ? d_hist + s * 3 * E : nullptr; io.hist_pitch = T * 3 * E;
+    io.lawm = d_modes ? d_modes + s * arow : nullptr;
+    io.aout = d_actions_out ? d_actions_out + s * arow : nullptr; io.act_pitch = T * arow;
+    io.em = d_E_mesh ? d_E_mesh + s * mesh : nullptr; io.em_pitch = T * mesh;
+    rc = tanwalk_advance(h, io, mem_kind);
+    if (rc) { t.twalk = false; return rc; }
+  }
+  t.twalk = false;
+  rc = tanwalk_state_out(h, mem_kind, d_x, d_v);
+  return rc ? rc : walk_finish(h, who, mem_kind);
+}

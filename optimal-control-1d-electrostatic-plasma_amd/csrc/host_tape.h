@@ -322,7 +322,7 @@ static WalkGeom walk_geom(const pic_handle* h) {
 static int walk_open(pic_handle* h, int mo) {
   Tape& t = h->tape;
   const size_t part = (size_t)h->cfg.num_envs * h->ld, mesh = (size_t)h->cfg.num_envs * h->cfg.Ng;
-  t.walk = false;
+  t.walk = t.twalk = false;          // (a forward walk replays into the same segment buffer)
   if (mo > 0) {
     const int rc = ensure_twiddle(h, mo);
     if (rc) return rc;

@@ -9,6 +9,13 @@
 //   tangent_pass_kernel    sub-stage S of every direction: dE_S through the gather, the kick and the drift; the maxima behind
 //                          the next deposit's unit
 //
+// The closed loop in forward mode (pic_tape_tangent_walk_*, pic_tape_tangent_feedback):
+//   tangent_x_max_kernel          max |dx_0| per direction and environment: the unit of the deposit at the tape's start
+//   tangent_start_deposit_kernel  drho(x_0; dx_0) at the stored starting positions (the forward twin of adjoint_start_kernel)
+//   tangent_law_kernel            dm = J dM of the field tangent a step left (the observation's and the law's modes), and the next
+//                                 law step's da = G dm + dG m
+//   tangent_action_kernel         the caller's injection into a step's da row
+//
 // Every particle's base quantities (q_S, p_S, cell, weights, slope of F_S) come from replay_particle once per pass and serve all
 // directions.  The tangent state is (dq, dp) [K][2][env][ld]: (dx, dv) at the start of a step, (dq_{S+1}, dp_S) after pass S.
 #pragma once
@@ -253,6 +260,122 @@ __global__ __launch_bounds__(ABLOCK) void tangent_pass_kernel(AdjStep s, TanArgs
     }
   }
   (void)bad;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The closed loop in forward mode
+// ---------------------------------------------------------------------------------------------
+// slot 0 <- max |dx| of the tangent state (grid (gx, env); directions one after the other): the unit of tangent_start_deposit_kernel
+__global__ __launch_bounds__(ABLOCK) void tangent_x_max_kernel(TanArgs t, AdjArgs a) {
+  const int env = blockIdx.y;
+  const size_t prow = (size_t)env * a.ld;
+  for (int d = 0; d < t.K; ++d) {
+    const double* sq = t.st + (size_t)d * t.dstride + prow;
+    double m = 0.0;
+    for (long long i = (long long)blockIdx.x * ABLOCK + threadIdx.x; i < a.N; i += (long long)gridDim.x * ABLOCK) max_abs(m, sq[i]);
+    block_max_to(m, tan_max(t, 0, d, env));
+  }
+}
+
+// tangent_deposit_kernel at stored positions x [env][ld] (the tape's first checkpoint) with dq = dx_0: the deposit behind the
+// tangent of the field the tape started from, dE_0 = K drho(x_0; dx_0).  Same grid, LDS and integer sums (unit of slot 0).
+template <int KB>
+__global__ __launch_bounds__(ABLOCK) void tangent_start_deposit_kernel(const double* __restrict__ x, TanArgs t, AdjArgs a, int kd) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  unsigned long long* lds = reinterpret_cast<unsigned long long*>(smem_raw);
+  const int env = blockIdx.y, Ng = a.Ng, d0 = blockIdx.z * kd;
+  const int nd = min(kd, t.K - d0);
+  for (int c = threadIdx.x; c < nd * (Ng + 1); c += ABLOCK) lds[c] = 0ull;
+  int ue[KB];
+  bool on[KB];
+#pragma unroll
+  for (int d = 0; d < KB; ++d) {
+    const unsigned long long mb = d < nd ? *tan_max(t, 0, d0 + d, env) : 0ull;
+    on[d] = mb != 0ull;
+    ue[d] = adj_unit_exp(mb, a.bitsN);
+  }
+  __syncthreads();
+  const Consts<PosF64> k(a.L, a.dx, Ng);
+  const size_t prow = (size_t)env * a.ld, row = (size_t)env * Ng;
+  unsigned bad = 0u;
+  for (long long i = (long long)blockIdx.x * ABLOCK + threadIdx.x; i < a.N; i += (long long)gridDim.x * ABLOCK) {
+    double w[3], xw;
+    int j, jr;
+    adj_locate(x[prow + i], k, xw, j, jr, w, bad);
+#pragma unroll
+    for (int d = 0; d < KB; ++d) {
+      if (d >= nd) break;
+      if (!on[d]) continue;
+      const long long r = __double2ll_rn(ldexp(t.st[(size_t)(d0 + d) * t.dstride + prow + i], -ue[d]));
+      atomicAdd(lds + d * (Ng + 1) + j, (unsigned long long)(-r));
+      atomicAdd(lds + d * (Ng + 1) + j + 1, (unsigned long long)r);
+    }
+  }
+  __syncthreads();
+  for (int d = 0; d < nd; ++d) adj_flush(lds + d * (Ng + 1), Ng, t.acc + (size_t)(d0 + d) * t.num_envs * Ng + row);
+  (void)bad;
+}
+
+// what tangent_law_kernel reads and writes
+struct TanLawArgs {
+  const double* dM;       // [K][env][Ng] the field tangent the step left
+  const double* tw;       // [2][rows][Ng] cos | sin twiddles, row m-1 = mode m
+  double* obs;            // [K][env][2 Mo] the observation's tangent, or null
+  double* dm;             // [K][env][2M] the law's dm, or null (M = 0)
+  const double* gain;     // [env][2M][2M] G of the step that reads this field, or null: not a law step
+  const double* dgain;    // [K][env][2M][2M] dG, or null
+  const double* modes;    // [env][2M] m of that step (with dgain)
+  double* da;             // [K][env][2M] that step's da = G dm + dG m (with gain)
+  int rows, Ng, M, Mo, num_envs, pad_;
+};
+
+// One workgroup per (environment, direction).  dm = J dM for R = max(M, Mo) modes, mesh_mode's map: one wave per coefficient,
+// lane l sums the nodes l + 64 k in ascending k, then a fixed-order wave sum.  The first Mo modes go to obs, the first M to dm;
+// if the next step is a law step, da_i = sum_k G[i][k] dm_k (gain_row: the forward law's rule) + sum_k dG[i][k] m_k (ascending k).
+__global__ __launch_bounds__(ABLOCK) void tangent_law_kernel(TanLawArgs l) {
+  __shared__ double sm[2 * kMaxFeedbackModes];
+  const int env = blockIdx.x, d = blockIdx.y, Ng = l.Ng, M = l.M, Mo = l.Mo, R = M > Mo ? M : Mo;
+  const int lane = threadIdx.x & 63;
+  const size_t de = (size_t)d * l.num_envs + env;
+  const double* dM = l.dM + de * Ng;
+  for (int r = threadIdx.x >> 6; r < 2 * R; r += AWAVES) {
+    const int m = r < R ? r : r - R, im = r < R ? 0 : 1;
+    const double* tw = l.tw + ((size_t)(im ? l.rows : 0) + m) * Ng;
+    double s = 0.0;
+    if (im) for (int j = lane; j < Ng; j += 64) s -= dM[j] * tw[j];
+    else for (int j = lane; j < Ng; j += 64) s += dM[j] * tw[j];
+    s = wave_sum(s) / Ng * 2.0;
+    if (lane == 0) {
+      if (m < Mo) l.obs[de * 2 * Mo + (size_t)im * Mo + m] = s;
+      if (m < M) {
+        l.dm[de * 2 * M + (size_t)im * M + m] = s;
+        sm[im * M + m] = s;
+      }
+    }
+  }
+  if (!l.gain) return;
+  __syncthreads();
+  const int n = 2 * M, i = threadIdx.x;
+  if (i >= n) return;
+  double a = gain_row(l.gain + ((size_t)env * n + i) * n, sm, n);
+  if (l.dgain) {
+    const double* dG = l.dgain + (de * n + i) * n;
+    const double* mv = l.modes + (size_t)env * n;
+    double b = 0.0;
+    for (int k = 0; k < n; ++k) b += dG[k] * mv[k];
+    a = a + b;
+  }
+  l.da[de * n + i] = a;
+}
+
+// row d of da [K][n] takes the caller's injection inj + d stride: added to the law's da (add), or alone
+__global__ __launch_bounds__(ABLOCK) void tangent_action_kernel(double* __restrict__ da, const double* __restrict__ inj,
+                                                                long long stride, int n, int add) {
+  const int d = blockIdx.y;
+  const int i = blockIdx.x * ABLOCK + threadIdx.x;
+  if (i >= n) return;
+  const double v = inj[(size_t)d * stride + i];
+  da[(size_t)d * n + i] = add ? da[(size_t)d * n + i] + v : v;
 }
 
 }  // namespace

@@ -35,7 +35,7 @@
 // pic_solve.h (field solve), pic_aux.h (kernels off the step path); host_plan.h (pic_create's argument checks and the launch plan:
 // no HIP, pinned on a CPU by tests/test_plan_cpu.py), host_place.h (the search for a placement of x and v); this file holds the
 // handle, the launch schedule and the C ABI, but for the host side of the differentiable rollouts: host_diff.h, host_phase.h,
-// host_tape.h, host_tangent.h.  pic_copy.h, host_copy.h and host_copy_map.h: copies of whole environments (pic_copy_envs).
+// host_tape.h, host_tangent.h, host_tangent_walk.h.  pic_copy.h, host_copy.h and host_copy_map.h: copies of whole environments (pic_copy_envs).
 
 #include <hip/hip_runtime.h>
 
@@ -201,7 +201,7 @@ struct Tape {
   std::vector<int> law;               // [max_steps] per step: the index of its gain in `gains`, or -1 (empty: no law step yet)
   std::vector<DeviceBuf<double>> gains;   // per call: [env][2M][2M]
   // the reverse walk (pic_tape_walk_*); pic_tape_backward[_feedback] is a walk of its own.  Any append, start,
-  // stop, backward or new walk abandons it.
+  // stop, backward, tangent, tangent walk or new walk abandons it.
   bool walk = false;                  // a walk is in progress
   int64_t wnext = -1;                 // the next step it reverses (-1: all walked)
   int wmo = 0;                        // M_o: modes of the walk's mode cotangents
@@ -213,6 +213,17 @@ struct Tape {
   DeviceBuf<void> tan_block;
   int tan_k = 0;
   size_t tan_bytes = 0;
+  // the forward walk through closed loops (pic_tape_tangent_walk_*, pic_tape_tangent_feedback): its working rows
+  // (host_tangent_walk.h: tanwalk_parts) for tw_cap_k directions and tw_cap_mo observed modes, allocated by the first walk and
+  // grown for more; counts in `bytes`.  It replays into the segment buffer as the reverse walk does, so either abandons the
+  // other; any append, start, stop, backward or tangent abandons it too.
+  bool twalk = false;                 // a forward walk is in progress
+  int64_t tnext = 0;                  // the next step it advances
+  int tw_k = 0, tw_mo = 0;            // its directions and observed modes
+  bool tw_dgain = false;              // it carries a gain tangent
+  DeviceBuf<void> tw_block;
+  size_t tw_bytes = 0;
+  int tw_cap_k = 0, tw_cap_mo = 0;
   // the per-step smoothed KL (pic_tape_kl_*): one block allocated by pic_tape_kl_start, counts in `bytes`;
   // kl_feq .. kl_cot are views into it
   DeviceBuf<void> kl_block;
@@ -1287,6 +1298,7 @@ static int64_t records_ahead(const pic_handle* h, int64_t nsteps) {
 #include "host_moments.h"
 #include "host_tape.h"
 #include "host_tangent.h"
+#include "host_tangent_walk.h"
 #include "host_copy.h"
 
 // advance_steps, cut into parts where the recorder or an open tape needs the state between two steps.  A part runs up to the
@@ -1299,7 +1311,7 @@ static int advance(pic_handle* h, const StepControl& sc, int nsteps, double* his
   Recorder& r = h->rec;
   Tape& t = h->tape;
   const int E = h->cfg.num_envs;
-  t.walk = false;                     // appending abandons a walk
+  t.walk = t.twalk = false;           // appending abandons a walk
   for (int done = 0; done < nsteps;) {
     int64_t n = nsteps - done;
     if (r.on) n = std::min<int64_t>(n, r.stride - r.k % r.stride);

@@ -786,8 +786,147 @@ class BatchedPIC:
         mo = int(obs_modes) if obs_modes is not None else max(1, self.max_mode)
         return TapeWalk(self, mo, on_device)
 
+    # -- forward mode through closed loops (pic_tape_tangent_walk_*) ------------------------
+    def _directions(self, who, K, base, given):
+        """The number of directions of a forward-mode call and whether its arrays carry a leading K axis: from K if given (then
+        they do), else from the inputs (`given`: name -> array; `base`: name -> shape without K)."""
+        ks = {int(a.shape[0]) for k, a in given.items() if len(a.shape) == len(base[k]) + 1}
+        if K is not None:
+            ks.add(int(K))
+        if len(ks) > 1:
+            raise ValueError(f"{who}: the inputs disagree on the number of directions: {sorted(ks)}")
+        batched = bool(ks)
+        K = ks.pop() if ks else 1
+        for k, a in given.items():
+            want = ((K,) if batched else ()) + base[k]
+            if tuple(a.shape) != want:
+                raise ValueError(f"{who}: {k} must have shape {want}, not {tuple(a.shape)}")
+        return K, batched
+
+    def tangent_walk(self, K=None, obs_modes: Optional[int] = None, d_x0=None, d_v0=None, d_gain=None, on_device: bool = False):
+        """The forward-mode pass of the open tape one step at a time, forward in time (pic_tape_tangent_walk_*):
+        returns a TangentWalk whose step(d_actions, d_ext) advances steps 0, 1, ... and whose end() returns the final particles'
+        tangents.  d_x0, d_v0 [num_envs, N]: tangents of the tape's starting particles; d_gain [num_envs, 2M, 2M]: the tangent
+        of the gain of the tape's step_feedback_gain steps (each None = 0).  K <= 8 directions at once: every array then carries
+        a leading K axis (K given, or read off the inputs); without one K = 1 and no array has it.  obs_modes M_o (default: the
+        actuator's max_mode, else 1; 0 = none) sets the observation's layout [num_envs, 2*M_o] (Re E_1..E_Mo, then Im, the map of
+        `modes`); `.d_modes0` holds its tangent at the tape's start.  On a gain-law step the device forms
+        d_a = G d_m + d_G m + d_actions itself; between two steps the caller can put any policy's JVP.  The tangents of the
+        per-step KL and of the moments are not available step by step.  Outputs are float64 CUDA tensors if any input is one or
+        on_device is set, NumPy arrays otherwise.  A later step on the environment, a reverse walk, backward or tangent abandons
+        this walk (PicError), and it abandons a reverse walk."""
+        mo = int(obs_modes) if obs_modes is not None else max(1, self.max_mode)
+        return TangentWalk(self, K, mo, d_x0, d_v0, d_gain, on_device)
+
+    def tangent_feedback(self, d_gain=None, d_x0=None, d_v0=None, d_actions=None, fields: bool = False):
+        """Jacobian-vector product of the taped steps through the gain law (pic_tape_tangent_feedback), dual to
+        `backward` on a tape with steps of step_feedback_gain: tangents d_gain [num_envs, 2M, 2M] of their gain, d_x0, d_v0
+        [num_envs, N] of the starting particles, d_actions [T, num_envs, 2M] added to every step's action (each None = 0; a
+        leading axis of K <= 8 directions as in `tangent`).  Returns a dict: "KE", "PE", "PE_reward" [K, T, num_envs], "modes"
+        [K, T, num_envs, 2M] (the tangents of the law's m_t, zero on other steps), "actions" [K, T, num_envs, 2M] (the action
+        tangents applied), "x", "v" [K, num_envs, N] and, with fields, "E_mesh" [K, T, num_envs, N_mesh].  On a tape without law
+        steps it is `tangent` bit for bit."""
+        T = self._h.tape_stats()["steps"]
+        E, N, Ng, n = self.num_envs, self.N, self.N_mesh, 2 * self.max_mode
+        base = {"d_gain": (E, n, n), "d_x0": (E, N), "d_v0": (E, N), "d_actions": (T, E, n)}
+        given = {k: a for k, a in (("d_gain", d_gain), ("d_x0", d_x0), ("d_v0", d_v0), ("d_actions", d_actions)) if a is not None}
+        K, batched = self._directions("tangent_feedback", None, base, given)
+        mem = Mem.of(self, *given.values())
+        ins = {k: mem.f64(a, (K,) + base[k]) for k, a in given.items()}
+        hist, x, v = mem.out((K, T, 3, E)), mem.out((K, E, N)), mem.out((K, E, N))
+        dm = mem.out((K, T, E, n)) if n else None
+        da = mem.out((K, T, E, n)) if n else None
+        em = mem.out((K, T, E, Ng)) if fields else None
+        addr = mem.addr
+        mem.enter()
+        self._walk_serial += 1
+        self._h.tape_tangent_feedback(K, addr(ins.get("d_gain")), addr(ins.get("d_x0")), addr(ins.get("d_v0")),
+                                      addr(ins.get("d_actions")), mem.kind, addr(hist), addr(dm), addr(da), addr(x), addr(v), addr(em))
+        if mem.on_device:
+            self._check_replay("tangent_feedback", "tangent")
+        res = {"KE": hist[:, :, 0], "PE": hist[:, :, 1], "PE_reward": hist[:, :, 2], "x": x, "v": v}
+        if n:
+            res["modes"], res["actions"] = dm, da
+        if fields:
+            res["E_mesh"] = em
+        return res if batched else {k: a[0] for k, a in res.items()}
+
     def close(self):
         self._h.close()
+
+
+class TangentWalk:
+    """A forward-mode walk over an open tape (BatchedPIC.tangent_walk)."""
+
+    def __init__(self, env, K, obs_modes, d_x0=None, d_v0=None, d_gain=None, on_device=False):
+        E, N, n = env.num_envs, env.N, 2 * env.max_mode
+        base = {"d_x0": (E, N), "d_v0": (E, N), "d_gain": (E, n, n)}
+        given = {k: a for k, a in (("d_x0", d_x0), ("d_v0", d_v0), ("d_gain", d_gain)) if a is not None}
+        self.K, self.batched = env._directions("tangent_walk", K, base, given)
+        self.env, self.obs_modes, self.on_device = env, int(obs_modes), bool(on_device)
+        mem = Mem.of(env, *given.values(), force_device=self.on_device)
+        ins = {k: mem.f64(a, (self.K,) + base[k]) for k, a in given.items()}
+        m0 = mem.out((self.K, E, 2 * self.obs_modes)) if self.obs_modes > 0 else None
+        mem.enter()
+        env._h.tape_tangent_walk_begin(self.K, self.obs_modes, mem.addr(ins.get("d_x0")), mem.addr(ins.get("d_v0")),
+                                       mem.addr(ins.get("d_gain")), mem.kind, mem.addr(m0))
+        mem.leave(env._h)                            # (the inputs above are alive until here)
+        env._walk_serial += 1                        # (a reverse walk in progress is abandoned)
+        self._serial = env._walk_serial
+        self.d_modes0 = m0 if self.batched or m0 is None else m0[0]
+
+    def _live(self, who):
+        if self.env._walk_serial != self._serial:
+            raise _abi.PicError(f"tangent_walk.{who}: another walk, backward or tangent has replaced this one")
+
+    def step(self, d_actions=None, d_ext=None, state: bool = False, fields: bool = False):
+        """Advance the next step t under this step's injection d_actions [num_envs, 2*max_mode] or d_ext [num_envs, N_mesh] (at
+        most one; on a gain-law step d_actions is added to the law's own action tangent and d_ext is refused).  Returns a dict:
+        "t", "KE", "PE", "PE_reward" [num_envs], "modes" [num_envs, 2*M_o] (the tangent of the observation of the field the step
+        left; with M_o > 0), "actions" [num_envs, 2*max_mode] (the action tangent applied; with an actuator) and, with state,
+        "x", "v" [num_envs, N], with fields, "E_mesh" [num_envs, N_mesh]; each with the walk's leading K axis, if it has one."""
+        self._live("step")
+        env, K, E = self.env, self.K, self.env.num_envs
+        n = 2 * env.max_mode
+        base = {"d_actions": (E, n), "d_ext": (E, env.N_mesh)}
+        given = {k: a for k, a in (("d_actions", d_actions), ("d_ext", d_ext)) if a is not None}
+        for k, a in given.items():
+            want = ((K,) if self.batched else ()) + base[k]
+            if tuple(a.shape) != want:
+                raise ValueError(f"tangent_walk.step: {k} must have shape {want}, not {tuple(a.shape)}")
+        mem = Mem.of(env, *given.values(), force_device=self.on_device)
+        ins = {k: mem.f64(a, (K,) + base[k]) for k, a in given.items()}
+        en = mem.out((K, 3, E))
+        mo = mem.out((K, E, 2 * self.obs_modes)) if self.obs_modes > 0 else None
+        ao = mem.out((K, E, n)) if n else None
+        x, v = (mem.out((K, E, env.N)), mem.out((K, E, env.N))) if state else (None, None)
+        em = mem.out((K, E, env.N_mesh)) if fields else None
+        addr = mem.addr
+        mem.enter()
+        t = env._h.tape_tangent_walk_step(addr(ins.get("d_ext")), addr(ins.get("d_actions")), mem.kind, addr(en), addr(mo), addr(ao),
+                                          addr(x), addr(v), addr(em))
+        mem.leave(env._h)                            # (the injections above are alive until here)
+        res = {"KE": en[:, 0], "PE": en[:, 1], "PE_reward": en[:, 2]}
+        for k, a in (("modes", mo), ("actions", ao), ("x", x), ("v", v), ("E_mesh", em)):
+            if a is not None:
+                res[k] = a
+        if not self.batched:
+            res = {k: a[0] for k, a in res.items()}
+        res["t"] = t
+        return res
+
+    def end(self):
+        """After all steps: the tangents of the final particles, (d_x, d_v) [num_envs, N] (with the walk's K axis, if any).
+        Raises PicError if a replay of the walk differed from the taped forward."""
+        self._live("end")
+        env = self.env
+        mem = Mem.of(env, force_device=self.on_device)
+        x, v = mem.out((self.K, env.num_envs, env.N)), mem.out((self.K, env.num_envs, env.N))
+        mem.enter()
+        env._h.tape_tangent_walk_end(mem.kind, mem.addr(x), mem.addr(v))
+        if mem.on_device:
+            env._check_replay("tangent_walk.end", "tangent")
+        return (x, v) if self.batched else (x[0], v[0])
 
 
 class TapeWalk:

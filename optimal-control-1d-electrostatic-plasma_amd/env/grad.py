@@ -123,6 +123,7 @@ class _RolloutFeedback(torch.autograd.Function):
             g = g.numpy()
         out = env.step_feedback_gain(g, T, modes=True, history=True)
         ctx.env, ctx.serial, ctx.steps, ctx.shared, ctx.kl = env, serial, T, gain.dim() == 2, kl is not None
+        ctx.device = gain.device
         outs = [out[k] for k in ("KE", "PE", "PE_reward", "modes")] + ([env.tape_kl()] if kl is not None else [])
         return tuple(torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64, device=gain.device) for a in outs)
 
@@ -132,6 +133,27 @@ class _RolloutFeedback(torch.autograd.Function):
         out = ctx.env.backward(d_KE=g_ke, d_PE=g_pe, d_PE_reward=g_per, d_modes=g_modes, d_KL=g_kl if ctx.kl else None)
         g = torch.as_tensor(out["gain"])             # (NumPy out for CPU cotangents in)
         return (g.sum(0) if ctx.shared else g), None, None, None, None
+
+    @staticmethod
+    def jvp(ctx, gain_t, env_t, T_t, ce_t, kl_t=None):
+        """Forward mode (torch.autograd.forward_ad): the tangents of the traces and of the law's modes along gain_t, from
+        pic_tape_tangent_feedback on the tape this rollout opened.  The KL's tangent through the closed loop is
+        not built."""
+        env = ctx.env
+        _check_live(env, ctx.serial, ctx.steps, "jvp")
+        if ctx.kl:
+            raise NotImplementedError("rollout_feedback: forward mode of the KL through the gain law is not built (DESIGN.md 7n)")
+        E, n = env.num_envs, 2 * env.max_mode
+        if gain_t is None:
+            z = lambda *s: torch.zeros((ctx.steps, E) + s, dtype=torch.float64, device=ctx.device)  # noqa: E731
+            return z(), z(), z(), z(n)
+        g = gain_t.detach().to(torch.float64)
+        if ctx.shared:
+            g = g.expand(E, n, n)
+        g = g.contiguous()
+        out = env.tangent_feedback(d_gain=g if g.is_cuda else g.numpy())
+        return tuple(torch.as_tensor(np.ascontiguousarray(out[k]) if isinstance(out[k], np.ndarray) else out[k],
+                                     dtype=torch.float64, device=ctx.device) for k in ("KE", "PE", "PE_reward", "modes"))
 
 
 def rollout_feedback(env, gain, T, checkpoint_every=0, kl=None):
@@ -276,3 +298,83 @@ def rollout_policy(env, policy, T, observe="modes", obs_modes=None, checkpoint_e
         obs.append(o)
     res = (torch.stack(ke), torch.stack(pe), torch.stack(per), torch.stack(acts), obs)
     return res + ((torch.stack(kls),) if kl is not None else ())
+
+
+def _policy_jvp(fn, params, o, d_params, d_o):
+    """The Jacobian-vector product of fn(params, o) along (d_params, d_o): torch.func.jvp where this torch has it, else
+    torch.autograd.forward_ad."""
+    if hasattr(torch, "func") and hasattr(torch.func, "jvp"):
+        return torch.func.jvp(fn, (params, o), (d_params, d_o))[1]
+    import torch.autograd.forward_ad as fwAD
+    with fwAD.dual_level():
+        dual = lambda a, t: fwAD.make_dual(a, t)  # noqa: E731
+        p = {k: dual(a, d_params[k]) for k, a in params.items()}
+        od = tuple(dual(a, t) for a, t in zip(o, d_o)) if isinstance(o, tuple) else dual(o, d_o)
+        t = fwAD.unpack_dual(fn(p, od)).tangent
+        return torch.zeros_like(fn(params, o)) if t is None else t
+
+
+def rollout_policy_jvp(env, fn, params, d_params, T, observe="modes", obs_modes=None, d_x0=None, d_v0=None, checkpoint_every=0):
+    """Forward mode through a closed loop under a torch policy written fn(params, o) -> actions [num_envs, 2*max_mode]
+    (DESIGN.md 7n): the directional derivatives of the traces along K <= 8 directions at once.  params: a dict of tensors on the
+    environment's device; d_params: a list of K dicts of tangents (missing names = 0); d_x0, d_v0 [K, num_envs, N]: tangents of
+    the starting particles (None = 0).  observe="modes" (o_t = the modes [num_envs, 2*M_o]) or "state" (o_t = (x, v)) as in
+    rollout_policy; "moments" is not built in forward mode.  Runs the loop on a fresh tape without grad, then walks it forward
+    (pic_tape_tangent_walk_*): per step and direction d_a_t = the JVP of fn at (params, o_t) along (d_params[k], d_o_t[k]) goes
+    in as the step's d_actions, and the step's tangent of the observation is d_o_{t+1}.  Returns a dict: the primal "KE", "PE",
+    "PE_reward" [T, num_envs], "actions" [T, num_envs, 2M], "obs" (o_0..o_T) and the tangents "dKE", "dPE", "dPE_reward"
+    [K, T, num_envs], "d_actions" [K, T, num_envs, 2M], "d_x", "d_v" [K, num_envs, N] (final particles)."""
+    if env.max_mode == 0:
+        raise PicError("rollout_policy_jvp: the environment has no actuator (set_actuator)")
+    if observe == "moments":
+        raise ValueError('rollout_policy_jvp: observe="moments" is not built in forward mode (DESIGN.md 7n)')
+    if observe not in ("modes", "state"):
+        raise ValueError('observe must be "modes" or "state"')
+    T, K = int(T), len(d_params)
+    if T < 1:
+        raise ValueError("need T >= 1")
+    if not 1 <= K <= 8:
+        raise ValueError("need 1 <= len(d_params) <= 8")
+    mo = int(obs_modes) if obs_modes is not None else env.max_mode
+    if not 1 <= mo < env.N_mesh:
+        raise ValueError("need 1 <= obs_modes < N_mesh")
+    unknown = sorted({k for d in d_params for k in d} - set(params))
+    if unknown:
+        raise ValueError(f"d_params names unknown parameters: {unknown}")
+    E, N, n = env.num_envs, env.N, 2 * env.max_mode
+    dev = f"cuda:{env.device}"
+    _start(env, T, int(checkpoint_every))
+    ke, pe, per, acts = [], [], [], []
+    with torch.no_grad():
+        o = _observe(env, observe, mo)
+        o = o if observe == "state" else o[0]
+        obs = [o]
+        for _ in range(T):
+            a = fn(params, o).to(torch.float64)
+            if tuple(a.shape) != (E, n):
+                raise ValueError(f"the policy must return actions [{E}, {n}], not {tuple(a.shape)}")
+            env.step_actions_torch(a.contiguous())
+            en = env.energy_views_torch()
+            ke.append(en["KE"].clone()), pe.append(en["PE"].clone()), per.append(en["PE_reward"].clone())
+            acts.append(a)
+            o = _observe(env, observe, mo)
+            o = o if observe == "state" else o[0]
+            obs.append(o)
+    full = [{k: (torch.as_tensor(d[k], dtype=p.dtype, device=p.device) if k in d else torch.zeros_like(p)) for k, p in params.items()}
+            for d in d_params]
+    t64 = lambda a: None if a is None else torch.as_tensor(a, dtype=torch.float64, device=dev).reshape(K, E, N)  # noqa: E731
+    dx0, dv0 = t64(d_x0), t64(d_v0)
+    walk = env.tangent_walk(K=K, obs_modes=mo if observe == "modes" else 0, d_x0=dx0, d_v0=dv0, on_device=True)
+    zeros = torch.zeros((K, E, N), dtype=torch.float64, device=dev)
+    d_o = walk.d_modes0 if observe == "modes" else (dx0 if dx0 is not None else zeros, dv0 if dv0 is not None else zeros)
+    dke, dpe, dper, dacts = [], [], [], []
+    for t in range(T):
+        rows = [d_o[k] if observe == "modes" else (d_o[0][k], d_o[1][k]) for k in range(K)]
+        da = torch.stack([_policy_jvp(fn, params, obs[t], full[k], rows[k]).to(torch.float64) for k in range(K)])
+        r = walk.step(d_actions=da, state=observe == "state")
+        dke.append(r["KE"]), dpe.append(r["PE"]), dper.append(r["PE_reward"]), dacts.append(r["actions"])
+        d_o = r["modes"] if observe == "modes" else (r["x"], r["v"])
+    d_x, d_v = walk.end()
+    return {"KE": torch.stack(ke), "PE": torch.stack(pe), "PE_reward": torch.stack(per), "actions": torch.stack(acts), "obs": obs,
+            "dKE": torch.stack(dke, 1), "dPE": torch.stack(dpe, 1), "dPE_reward": torch.stack(dper, 1),
+            "d_actions": torch.stack(dacts, 1), "d_x": d_x, "d_v": d_v}
