@@ -710,6 +710,55 @@ int pic_tape_tangent_feedback(pic_handle* h, int K, const double* d_gain, const 
 int pic_copy_envs(pic_handle* dst, pic_handle* src, const int32_t* map, int mem_kind);
 int pic_copy_envs_rejected(pic_handle* dst, int64_t* count);
 
+/* ---- Closed loops under an MLP policy on the device (additive to ABI 5) -----------------------------------------
+ * a = pi(o): the observation o = (Re E_1..Re E_Mo, Im E_1..Im E_Mo) is what pic_get_modes(Mo) returns for the same field, bit for
+ * bit (the layout of the gain law's m); pi is an MLP of 1..4 linear layers, evaluated by one workgroup per environment.
+ *   h_0 = o, or o * obs_scale element by element.
+ *   layer l: y_i = b_i; then, for k ascending, y_i = y_i + W[i][k] * h_l[k] -- the product rounded, then the sum, no fused
+ *     multiply-add.  Behind every layer but the last h_{l+1} = tanh(y) (the device's float64 tanh, PIC_ACT_TANH) or
+ *     y > 0 ? y : +0.0 (PIC_ACT_RELU).
+ *   z = the last layer's y.  With noise: u = z + std_i * eps_i (the product rounded first; std NULL = 1); without: u = z.
+ *   squash 0: a = u.  squash 1: a = action_scale * tanh(u).
+ * The library draws nothing: eps is the caller's, so a rollout is reproducible bit for bit. */
+#define PIC_ACT_TANH 0
+#define PIC_ACT_RELU 1
+typedef struct pic_policy {
+  int obs_modes;           /* Mo, 1 <= Mo <= 64 and Mo < Ng */
+  int n_layers;            /* 1..4 linear layers */
+  int width[5];            /* width[0] = 2 Mo, width[n_layers] = 2 max_mode of pic_set_actuator, every width 1..256 */
+  int activation;          /* PIC_ACT_TANH or PIC_ACT_RELU behind every layer but the last */
+  int squash;              /* 0: a = u;  1: a = action_scale * tanh(u) */
+  int per_env;             /* 0: one parameter vector for all environments;  1: params is [num_envs][P] */
+  double action_scale;
+  const double* params;    /* per layer l: W_l [width[l+1]][width[l]] row-major, then b_l [width[l+1]];  P doubles in all */
+  const double* obs_scale; /* NULL, or [2 Mo] */
+} pic_policy;
+
+/* pic_policy_eval: the policy once, for every environment, on obs [num_envs][2 Mo] or (obs NULL) on the modes of the current
+ * E_mesh; the state is not touched (allowed while a tape is open).  noise: [num_envs][2M] or NULL; std: [2M] or NULL.
+ * obs_out [num_envs][2 Mo] (the observation before obs_scale), pre_out (u) and actions_out (a) [num_envs][2M]: any may be NULL.
+ *
+ * pic_step_policy: nsteps closed-loop steps without returning to the host between them.  Step s is pic_policy_eval on the field
+ * the previous step left (the current E_mesh for the first step), then one step exactly as pic_step_actions(a_s on the device, 1)
+ * makes it: the call gives the bits of that host loop, and is accepted wherever pic_step_actions is (every particle format, CIC
+ * or TSC, every integrator, both schedules, recorder on or off).  One policy launch plus one step's launches per step; the
+ * actions of all steps lie in one device buffer of the handle, a row per step.  noise: [nsteps][num_envs][2M] or NULL;
+ * obs_out [nsteps][num_envs][2 Mo], pre_out, actions_out [nsteps][num_envs][2M]; hist: NULL, or host [nsteps][3][num_envs] as
+ * pic_step_actions_traj.
+ *
+ * mem_kind covers params, obs_scale, obs, noise, std and the three per-step outputs (all float64); inputs are read in stream
+ * order.  With PIC_HOST outputs (or hist) the call waits once, at the end; with PIC_DEVICE and no hist it is asynchronous on the
+ * handle's stream.
+ * PIC_ESTATE: no actuator (pic_set_actuator); before pic_reset (pic_policy_eval: only with obs NULL); pic_step_policy while a tape
+ * is open (the gradient through the policy would be missing: the differentiable route is a torch policy on the tape) or inside a
+ * staged step.  PIC_EINVAL, with the reason in pic_last_error, before anything is enqueued and with the state untouched: a NULL
+ * policy or params, n_layers outside 1..4, Mo outside 1..64 or >= Ng, a width outside 1..256, width[0] != 2 Mo,
+ * width[n_layers] != 2M, an unknown activation, squash or per_env other than 0 / 1, a bad mem_kind, nsteps < 0. */
+int pic_policy_eval(pic_handle* h, const pic_policy* p, const double* obs, const double* noise, const double* std, int mem_kind,
+                    double* obs_out, double* pre_out, double* actions_out);
+int pic_step_policy(pic_handle* h, const pic_policy* p, const double* noise, const double* std, int mem_kind, int nsteps,
+                    double* obs_out, double* pre_out, double* actions_out, double* hist);
+
 int pic_sync(pic_handle* h);
 /* Number of particle positions found non-finite or out of range by the last sweeps (0 = healthy).  Counts the state's
  * particles only: the positions of pic_eval_field / pic_compute_E probes never add to it. */

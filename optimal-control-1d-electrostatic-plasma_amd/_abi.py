@@ -87,6 +87,17 @@ class PicPhaseSpec(C.Structure):
                 ("feq_per_env", C.c_int32), ("feq_mem_kind", C.c_int32)]
 
 
+PIC_ACT_TANH, PIC_ACT_RELU = 0, 1
+ACTIVATIONS = {"tanh": PIC_ACT_TANH, "relu": PIC_ACT_RELU}
+
+
+class PicPolicy(C.Structure):
+    """pic_policy (include/picstep.h): an MLP policy on the modes of the mesh field; params / obs_scale are addresses."""
+    _fields_ = [("obs_modes", C.c_int32), ("n_layers", C.c_int32), ("width", C.c_int32 * 5), ("activation", C.c_int32),
+                ("squash", C.c_int32), ("per_env", C.c_int32), ("action_scale", C.c_double), ("params", C.c_void_p),
+                ("obs_scale", C.c_void_p)]
+
+
 class PicError(RuntimeError):
     pass
 
@@ -171,6 +182,8 @@ SIGNATURES = {
     "pic_placement_stats": [_vp, _vp],
     "pic_copy_envs": [_vp, _vp, _vp, C.c_int],
     "pic_copy_envs_rejected": [_vp, _i64p],
+    "pic_policy_eval": [_vp, C.POINTER(PicPolicy), _vp, _vp, _vp, C.c_int, _vp, _vp, _vp],
+    "pic_step_policy": [_vp, C.POINTER(PicPolicy), _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp],
     "pic_sync": [_vp],
     "pic_bad_count": [_vp, _i64p],
     "pic_last_error": [_vp],
@@ -617,6 +630,17 @@ class Handle:
         if hist is not None:
             out.update(KE=hist[:, 0], PE=hist[:, 1], PE_reward=hist[:, 2])
         return out or None
+
+    def policy_eval(self, spec, obs, noise, std, kind, obs_out, pre_out, actions_out):
+        """pic_policy_eval on addresses (0 or None = NULL) in `kind` memory; spec: a PicPolicy whose params / obs_scale are
+        addresses in the same memory."""
+        self._chk(self.lib.pic_policy_eval(self._h, C.byref(spec), *_ptrs(obs, noise, std), int(kind),
+                                           *_ptrs(obs_out, pre_out, actions_out)))
+
+    def step_policy(self, spec, noise, std, kind, nsteps, obs_out, pre_out, actions_out, hist=None):
+        """pic_step_policy on addresses (0 or None = NULL) in `kind` memory; hist: a host array [nsteps][3][num_envs] or None."""
+        self._chk(self.lib.pic_step_policy(self._h, C.byref(spec), *_ptrs(noise, std), int(kind), int(nsteps),
+                                           *_ptrs(obs_out, pre_out, actions_out), _ptr(hist)))
 
     def step_observe(self, E_ext=None, actions=None, nsteps=1, particles=True, out=None):
         """One Gym-style iteration in one call with one synchronisation (pic_step_observe): nsteps steps under E_ext

@@ -1,2 +1,3 @@
 from .actuator import E_field
 from .reward import Reward
+from .policy import MLPPolicy

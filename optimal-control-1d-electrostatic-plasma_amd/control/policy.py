@@ -1,0 +1,199 @@
+"""An MLP policy a = pi(o) on the Fourier modes of the mesh field, in the layout the device evaluates (pic_policy).
+
+The parameters are one flat float64 vector: per layer W [out][in] row-major, then b [out].  `BatchedPIC.policy_eval` and
+`BatchedPIC.step_policy` take an `MLPPolicy`; `from_torch` / `to_torch` move between it and an `nn.Sequential` for the update
+step of a trainer.  torch is imported only by the methods that need it.
+"""
+import ctypes as C
+from collections import namedtuple
+
+import numpy as np
+
+from .._abi import ACTIVATIONS, PicPolicy
+
+MAX_LAYERS, MAX_WIDTH, MAX_OBS_MODES = 4, 256, 64
+
+# what BatchedPIC.step_policy returns: obs [T, E, 2 M_o], pre (u) and actions (a) [T, E, 2M]; KE, PE, PE_reward [T, E] or None
+PolicyRollout = namedtuple("PolicyRollout", "obs pre actions KE PE PE_reward")
+
+
+def param_count(widths):
+    """P: the length of one parameter vector of an MLP with these layer widths."""
+    return sum(widths[l + 1] * widths[l] + widths[l + 1] for l in range(len(widths) - 1))
+
+
+def _is_tensor(a):
+    return hasattr(a, "data_ptr")
+
+
+def _host(a):
+    """a (NumPy, a tensor or None) as a NumPy array."""
+    return None if a is None else (a.detach().cpu().numpy() if _is_tensor(a) else np.asarray(a))
+
+
+class MLPPolicy:
+    """widths [2 M_o, ..., 2M] of 1..4 linear layers; activation "tanh" or "relu" behind every layer but the last; params a flat
+    float64 vector of `param_count(widths)` (NumPy or a CUDA tensor), or [num_envs, P] with per_env; squash: a = action_scale *
+    tanh(u) instead of a = u; obs_scale None or [2 M_o], multiplied into the observation before the first layer."""
+
+    def __init__(self, widths, activation, params, obs_modes, squash=False, action_scale=1.0, obs_scale=None, per_env=False):
+        self.widths = [int(w) for w in widths]
+        self.obs_modes = int(obs_modes)
+        if activation not in ACTIVATIONS:
+            raise ValueError(f"activation must be one of {sorted(ACTIVATIONS)}, not {activation!r}")
+        self.activation = activation
+        n = len(self.widths) - 1
+        if not 1 <= n <= MAX_LAYERS:
+            raise ValueError(f"an MLPPolicy has 1..{MAX_LAYERS} linear layers, not {n}")
+        if not 1 <= self.obs_modes <= MAX_OBS_MODES:
+            raise ValueError(f"obs_modes must be 1..{MAX_OBS_MODES}, not {self.obs_modes}")
+        if any(not 1 <= w <= MAX_WIDTH for w in self.widths):
+            raise ValueError(f"every width must be 1..{MAX_WIDTH}: {self.widths}")
+        if self.widths[0] != 2 * self.obs_modes:
+            raise ValueError(f"the widths do not chain: the first is {self.widths[0]}, the observation has 2 obs_modes = "
+                             f"{2 * self.obs_modes} entries")
+        self.squash, self.action_scale, self.per_env = bool(squash), float(action_scale), bool(per_env)
+        P = param_count(self.widths)
+        if not _is_tensor(params):
+            params = np.ascontiguousarray(np.asarray(params, dtype=np.float64))
+        shape = tuple(params.shape)
+        if (len(shape) != 2 or shape[1] != P) if self.per_env else shape != (P,):
+            raise ValueError(f"params must be {'[num_envs, P]' if self.per_env else '[P]'} with P = {P} for widths {self.widths}, "
+                             f"not {list(shape)}")
+        self.params = params
+        if obs_scale is not None:
+            if not _is_tensor(obs_scale):
+                obs_scale = np.ascontiguousarray(np.asarray(obs_scale, dtype=np.float64))
+            if tuple(obs_scale.shape) != (self.widths[0],):
+                raise ValueError(f"obs_scale must be [{self.widths[0]}], not {list(obs_scale.shape)}")
+        self.obs_scale = obs_scale
+
+    @property
+    def n_params(self):
+        return param_count(self.widths)
+
+    # -- the flat vector <-> per-layer (W, b) ----------------------------------------------------------------------------------
+    @staticmethod
+    def pack(layers):
+        """[(W [out, in], b [out]), ...] -> the flat float64 vector; the layers must chain (in of a layer = out of the one before)."""
+        parts, prev = [], None
+        for l, (W, b) in enumerate(layers):
+            W, b = np.asarray(W, dtype=np.float64), np.asarray(b, dtype=np.float64)
+            if W.ndim != 2 or b.shape != (W.shape[0],):
+                raise ValueError(f"layer {l}: W must be [out, in] and b [out], not {W.shape} and {b.shape}")
+            if prev is not None and W.shape[1] != prev:
+                raise ValueError(f"the widths do not chain: layer {l} takes {W.shape[1]} inputs, layer {l - 1} gives {prev}")
+            prev = W.shape[0]
+            parts += [W.ravel(), b]
+        return np.concatenate(parts)
+
+    @staticmethod
+    def widths_of(layers):
+        return [int(np.shape(layers[0][0])[1])] + [int(np.shape(W)[0]) for W, _ in layers]
+
+    def unpack(self, params=None):
+        """The flat vector (this policy's, or one of its shape) -> [(W, b), ...] as views; a [num_envs, P] array gives
+        W [num_envs, out, in] and b [num_envs, out]."""
+        p = self.params if params is None else params
+        if _is_tensor(p):
+            p = p.detach().cpu().numpy()
+        p = np.asarray(p, dtype=np.float64)
+        lead, out, at = p.shape[:-1], [], 0
+        for l in range(len(self.widths) - 1):
+            nin, nout = self.widths[l], self.widths[l + 1]
+            W = p[..., at:at + nout * nin].reshape(*lead, nout, nin)
+            at += nout * nin
+            out.append((W, p[..., at:at + nout]))
+            at += nout
+        return out
+
+    @classmethod
+    def from_layers(cls, layers, activation, obs_modes, **kwargs):
+        return cls(cls.widths_of(layers), activation, cls.pack(layers), obs_modes, **kwargs)
+
+    # -- torch -----------------------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_torch(cls, module, obs_modes, action_scale=1.0, obs_scale=None):
+        """An nn.Sequential of Linear layers with one kind of activation (Tanh or ReLU) between them and an optional final Tanh
+        (squash) -> the packed policy; the weights are copied as float64."""
+        import torch.nn as nn
+        mods = list(module)
+        squash = False
+        if len(mods) > 1 and isinstance(mods[-1], nn.Tanh) and isinstance(mods[-2], nn.Linear):
+            squash, mods = True, mods[:-1]
+        layers, acts = [], set()
+        for i, m in enumerate(mods):
+            if i % 2 == 0:
+                if not isinstance(m, nn.Linear) or m.bias is None:
+                    raise ValueError(f"module {i} must be an nn.Linear with a bias, not {type(m).__name__}")
+                layers.append((m.weight.detach().cpu().double().numpy(), m.bias.detach().cpu().double().numpy()))
+            elif isinstance(m, nn.Tanh):
+                acts.add("tanh")
+            elif isinstance(m, nn.ReLU):
+                acts.add("relu")
+            else:
+                raise ValueError(f"module {i} must be nn.Tanh or nn.ReLU, not {type(m).__name__}")
+        if len(mods) % 2 == 0 or len(acts) > 1:
+            raise ValueError("the module must be Linear (activation Linear)* [Tanh] with one kind of activation")
+        return cls.from_layers(layers, acts.pop() if acts else "tanh", obs_modes, squash=squash, action_scale=action_scale,
+                               obs_scale=obs_scale)
+
+    def to_torch(self):
+        """A float64 nn.Sequential with this policy's weights (a final Tanh with squash): u or tanh(u) of an observation that
+        obs_scale has already been multiplied into; `torch_actions` applies both scales.  Not for a per-environment policy."""
+        import torch
+        import torch.nn as nn
+        if self.per_env:
+            raise ValueError("to_torch: a per-environment policy has no single module (unpack() gives its weights)")
+        mods = []
+        layers = self.unpack()
+        for l, (W, b) in enumerate(layers):
+            lin = nn.Linear(W.shape[1], W.shape[0], dtype=torch.float64)
+            with torch.no_grad():
+                lin.weight.copy_(torch.from_numpy(np.ascontiguousarray(W)))
+                lin.bias.copy_(torch.from_numpy(np.ascontiguousarray(b)))
+            mods.append(lin)
+            if l + 1 < len(layers):
+                mods.append(nn.Tanh() if self.activation == "tanh" else nn.ReLU())
+        if self.squash:
+            mods.append(nn.Tanh())
+        return nn.Sequential(*mods)
+
+    def torch_actions(self, module, obs):
+        """The actions of `module` (to_torch's, or one of its shape) on observations obs [..., 2 M_o] with this policy's
+        obs_scale and action_scale: the differentiable twin of the device's evaluation without noise."""
+        import torch
+        if self.obs_scale is not None:
+            obs = obs * torch.as_tensor(self.obs_scale, dtype=obs.dtype, device=obs.device)
+        out = module(obs)
+        return self.action_scale * out if self.squash else out
+
+    def with_params(self, params):
+        """The same policy on another parameter vector (e.g. repacked after an update)."""
+        return MLPPolicy(self.widths, self.activation, params, self.obs_modes, self.squash, self.action_scale, self.obs_scale,
+                         self.per_env)
+
+    @classmethod
+    def stack(cls, policies):
+        """E policies of one shape -> one per-environment policy, environment e under policies[e]."""
+        first = policies[0]
+        key = lambda p: (p.widths, p.activation, p.obs_modes, p.squash, p.action_scale, p.per_env)
+        if first.per_env or any(key(p) != key(first) for p in policies):
+            raise ValueError("stack: the policies must share widths, activation, obs_modes, squash and action_scale")
+        scales = [_host(p.obs_scale) for p in policies]
+        if any((s is None) != (scales[0] is None) or (s is not None and not np.array_equal(s, scales[0])) for s in scales):
+            raise ValueError("stack: the policies must share obs_scale")
+        flat = np.stack([_host(p.params) for p in policies])
+        return cls(first.widths, first.activation, flat, first.obs_modes, first.squash, first.action_scale, first.obs_scale, True)
+
+    # -- the C struct ----------------------------------------------------------------------------------------------------------
+    def spec(self, mem, num_envs):
+        """(PicPolicy, keep): the struct of a call in `mem`'s memory (env._arrays.Mem) and the arrays its addresses point into,
+        to be held until the call has read them."""
+        if self.per_env and self.params.shape[0] != num_envs:
+            raise ValueError(f"a per-environment policy needs params [{num_envs}, P], not {list(self.params.shape)}")
+        params, scale = mem.f64(self.params), mem.f64(self.obs_scale)
+        width = (self.widths + [0] * 5)[:5]
+        s = PicPolicy(self.obs_modes, len(self.widths) - 1, (C.c_int32 * 5)(*width), ACTIVATIONS[self.activation],
+                      int(self.squash), int(self.per_env), self.action_scale, mem.addr(params) or None, mem.addr(scale) or None)
+        return s, (params, scale)

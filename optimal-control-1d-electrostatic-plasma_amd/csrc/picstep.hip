@@ -36,6 +36,7 @@
 // no HIP, pinned on a CPU by tests/test_plan_cpu.py), host_place.h (the search for a placement of x and v); this file holds the
 // handle, the launch schedule and the C ABI, but for the host side of the differentiable rollouts: host_diff.h, host_phase.h,
 // host_tape.h, host_tangent.h, host_tangent_walk.h.  pic_copy.h, host_copy.h and host_copy_map.h: copies of whole environments (pic_copy_envs).
+// pic_policy.h and host_policy.h: the MLP policy of pic_policy_eval and pic_step_policy.
 
 #include <hip/hip_runtime.h>
 
@@ -72,6 +73,7 @@
 #include "pic_phase.h"
 #include "pic_moments.h"
 #include "pic_copy.h"
+#include "pic_policy.h"
 
 
 // ---------------------------------------------------------------------------------------------
@@ -310,6 +312,8 @@ struct __attribute__((visibility("hidden"))) pic_handle : LaunchPlan {      // t
   Feedback fb{};                  // feedback outputs wanted from the NEXT post-step solve of the streaming schedule (fb.M = 0: none)
   DeviceBuf<double> gain;         // [env][2M][2M] device copy of a host gain (pic_step_feedback_gain)
   DeviceBuf<double> fb_modes;     // [env][2 kMaxFeedbackModes] the gain law's m, step by step
+  DeviceBuf<void> pol;            // the block of a policy call (host_policy.h: policy_parts), grown on demand
+  size_t pol_bytes = 0;
   DeviceBuf<double> aux_n;        // probe outputs
   DeviceBuf<double> aux_E;
   DeviceBuf<double> aux_pe;
@@ -1996,6 +2000,9 @@ int pic_step_feedback_gain(pic_handle* h, int max_mode, const double* gain, int 
   if (actions_out || modes_out) HIPCHK(h, hipStreamSynchronize(h->stream));
   return PIC_OK;
 }
+
+// closed loops under an MLP policy (pic_policy_eval, pic_step_policy)
+#include "host_policy.h"
 
 int pic_get_modes(pic_handle* h, int max_mode, double* re, double* im, int mem_kind) {
   if (!h || max_mode < 1 || max_mode >= h->cfg.Ng) return fail(h, PIC_EINVAL, "pic_get_modes: bad max_mode");

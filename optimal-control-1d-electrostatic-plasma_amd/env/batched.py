@@ -205,6 +205,48 @@ class BatchedPIC:
             g = np.broadcast_to(g, (E, n, n))
         return self._h.step_feedback_gain(np.ascontiguousarray(g), nsteps, actions, modes, history)
 
+    # -- closed loops under an MLP policy on the device (pic_policy_eval, pic_step_policy) ------------------
+    def _policy_call(self, policy, T, obs, noise, std, on_device):
+        """The memory, the struct and the arrays of one policy call: inputs as float64 arrays of that memory, fresh outputs."""
+        E, nO, nA = self.num_envs, 2 * policy.obs_modes, 2 * self.max_mode
+        mem = Mem.of(self, policy.params, obs, noise, std, force_device=on_device)
+        spec, keep = policy.spec(mem, E)
+        lead = () if T is None else (T,)
+        obs = mem.f64(obs, (E, nO))
+        noise = mem.f64(noise, lead + (E, nA))
+        std = mem.f64(std, (nA,))
+        outs = mem.empty(lead + (E, nO)), mem.empty(lead + (E, nA)), mem.empty(lead + (E, nA))
+        return mem, spec, keep, obs, noise, std, outs
+
+    def policy_eval(self, policy, obs=None, noise=None, std=None, on_device: bool = False):
+        """`policy` (control.policy.MLPPolicy) once for every environment -> (obs [num_envs, 2 M_o], pre, actions [num_envs, 2M]):
+        on obs if given, else on the modes of the current E_mesh (`modes(M_o)`, bit for bit: Re E_1..E_Mo, then Im).  pre is
+        u = z + std * eps with noise = eps [num_envs, 2M] (std [2M], None = 1), or u = z; actions a = u, or action_scale tanh(u)
+        with squash.  NumPy, or float64 CUDA tensors if an input is one or with on_device.  The state is not touched."""
+        mem, spec, keep, obs, noise, std, (o, u, a) = self._policy_call(policy, None, obs, noise, std, on_device)
+        mem.enter()
+        self._h.policy_eval(spec, mem.addr(obs), mem.addr(noise), mem.addr(std), mem.kind, mem.addr(o), mem.addr(u), mem.addr(a))
+        mem.leave(self._h)
+        return o, u, a
+
+    def step_policy(self, policy, nsteps: int, noise=None, std=None, history: bool = True, on_device: bool = False):
+        """nsteps closed-loop steps under `policy` in ONE call, without returning to the host between steps (pic_step_policy):
+        step s evaluates the policy on the field step s-1 left (the current E_mesh for the first), then steps under its actions
+        -- bit for bit the host loop `policy_eval` -> `step_actions`.  noise: eps [nsteps, num_envs, 2M] (one torch.randn for the
+        whole rollout; the library draws nothing) or None; std [2M] or None.  -> PolicyRollout(obs [nsteps, num_envs, 2 M_o],
+        pre, actions [nsteps, num_envs, 2M], KE, PE, PE_reward [nsteps, num_envs] NumPy -- None without history).  NumPy, or
+        float64 CUDA tensors if an input is one or with on_device (then asynchronous without history).  Refused while a tape is
+        open: env.grad.rollout_policy is the differentiable route."""
+        from ..control.policy import PolicyRollout
+        T = int(nsteps)
+        mem, spec, keep, _, noise, std, (o, u, a) = self._policy_call(policy, T, None, noise, std, on_device)
+        hist = np.empty((T, 3, self.num_envs)) if history else None
+        mem.enter()
+        self._h.step_policy(spec, mem.addr(noise), mem.addr(std), mem.kind, T, mem.addr(o), mem.addr(u), mem.addr(a), hist)
+        mem.leave(self._h)
+        ke, pe, per = (None, None, None) if hist is None else (hist[:, 0], hist[:, 1], hist[:, 2])
+        return PolicyRollout(o, u, a, ke, pe, per)
+
     def modes(self, max_mode: int):
         """Complex [num_envs, max_mode]: rows 1..max_mode of compute_E_k_spectrum for the current E_mesh."""
         return self._h.modes(max_mode)
