@@ -750,14 +750,66 @@ typedef struct pic_policy {
  * order.  With PIC_HOST outputs (or hist) the call waits once, at the end; with PIC_DEVICE and no hist it is asynchronous on the
  * handle's stream.
  * PIC_ESTATE: no actuator (pic_set_actuator); before pic_reset (pic_policy_eval: only with obs NULL); pic_step_policy while a tape
- * is open (the gradient through the policy would be missing: the differentiable route is a torch policy on the tape) or inside a
- * staged step.  PIC_EINVAL, with the reason in pic_last_error, before anything is enqueued and with the state untouched: a NULL
+ * is open (the gradient through the policy would be missing: pic_tape_step_policy below is the taped entry; a torch policy on the
+ * tape is the route for other networks) or inside a staged step.  PIC_EINVAL, with the reason in pic_last_error, before anything is enqueued and with the state untouched: a NULL
  * policy or params, n_layers outside 1..4, Mo outside 1..64 or >= Ng, a width outside 1..256, width[0] != 2 Mo,
  * width[n_layers] != 2M, an unknown activation, squash or per_env other than 0 / 1, a bad mem_kind, nsteps < 0. */
 int pic_policy_eval(pic_handle* h, const pic_policy* p, const double* obs, const double* noise, const double* std, int mem_kind,
                     double* obs_out, double* pre_out, double* actions_out);
 int pic_step_policy(pic_handle* h, const pic_policy* p, const double* noise, const double* std, int mem_kind, int nsteps,
                     double* obs_out, double* pre_out, double* actions_out, double* hist);
+
+/* ---- Policy gradients on the device (additive to ABI 5) -----------------------------------------------------------
+ * The vector-Jacobian product of the evaluation above, for one environment and one evaluation: from the recorded observation o,
+ * the recorded u (pre) and a cotangent a-bar on the action.
+ *   1. h_0 .. h_{L-1} are recomputed from o exactly as the forward computes them (the same bits).
+ *   2. squash 0: u-bar_i = a-bar_i.  squash 1: t = tanh(u_i), s = action_scale * (1.0 - t*t), u-bar_i = a-bar_i * s.  Noise and
+ *      std are additive, so z-bar = u-bar; g_pre = u-bar, and the caller forms d/d std as sum g_pre * eps.
+ *   3. delta = z-bar.  For l = L-1 .. 0:  g_b_l[i] = delta[i];  g_W_l[i][k] = delta[i] * h_l[k];
+ *      h-bar_l[k] = sum_i W_l[i][k] * delta[i], i ascending, the product rounded before the sum (no fused multiply-add), the
+ *      first product starting the sum;  if l > 0: delta[k] = h-bar_l[k] * d[k], with d = 1.0 - h*h (tanh; h the activation) or
+ *      h > 0 ? 1.0 : 0.0 (relu; h > 0 exactly where the pre-activation is).
+ *   4. o-bar[k] = h-bar_0[k], times obs_scale[k] if given.
+ * Parameter gradients are summed per environment over the policy steps in the order a reverse pass meets them (t descending),
+ * each sum as g = g + term with the first term starting it; with per_env the result is [num_envs][P], with shared parameters the
+ * per-environment sums are then added in ascending environment order.  No floating-point atomics: the result does not depend on
+ * blocks_per_env, the checkpoint interval, the schedule or the launch geometry.
+ *
+ * pic_policy_vjp: the VJP once for every environment, on obs [num_envs][2 Mo], pre [num_envs][2M] (NULL allowed only with
+ * squash == 0) and cot_actions [num_envs][2M]; g_params [P] or [num_envs][P] (per_env), g_obs [num_envs][2 Mo], g_pre
+ * [num_envs][2M], each may be NULL.  The state is not touched (allowed while a tape is open, needs no pic_reset).  Checked like
+ * pic_policy_eval: PIC_EINVAL with the reason, nothing enqueued.  With PIC_HOST the call waits; with PIC_DEVICE it is asynchronous.
+ *
+ * pic_tape_step_policy: pic_step_policy appended to an open tape (PIC_ESTATE without one).  Particles, fields, energies and the
+ * three outputs have the bits of the untaped call.  The tape keeps one copy of the call's parameters and obs_scale, every step's
+ * o_t, u_t and a_t, and which call each step belongs to; e_t = B a_t goes on the tape as an actions step's, so the replay compares
+ * bit for bit.  max_steps and budget_bytes are checked before any step runs (PIC_ENOMEM; the record counts in
+ * pic_tape_info.bytes).  All policy calls of one tape must agree in widths, activation, squash, per_env and Mo (PIC_EINVAL);
+ * they may be mixed with pic_step_actions* and pic_step_feedback_gain calls.  pic_step_policy itself stays refused under a tape.
+ *
+ * pic_tape_backward_policy: pic_tape_backward on a tape with policy steps.  cot_actions [T][num_envs][2M] and cot_obs
+ * [T][num_envs][2 Mo] (each may be NULL) are direct cotangents on the policy steps' actions and observations (rows of other steps
+ * are ignored).  At a policy step t, once e-bar_t is complete: a-bar_t = B^T e-bar_t + cot_actions_t; the VJP above; m-bar_t = o-bar_t + cot_obs_t; E-bar_t = J^T m-bar_t joins the refresh adjoint of
+ * step t-1, or reaches x_0 through the tape's starting field for t = 0.  g_params: the sum over all policy steps of the tape;
+ * g_pre, g_actions [T][num_envs][2M] and g_obs [T][num_envs][2 Mo] hold u-bar_t, a-bar_t and o-bar_t, zero on the other steps.
+ * Every output may be NULL.  PIC_ESTATE on a tape without policy steps.
+ * B^T e-bar_t is summed twice, as pic_tape_backward_feedback sums it for a step of the gain law: in ascending mesh order (the
+ * sum every g_actions reports) for the a-bar_t that g_actions, g_pre, g_obs and g_params follow from by the VJP above, bit for
+ * bit; and one wave per coefficient (the law's own adjoint) for the a-bar_t whose o-bar_t goes on into E-bar_t, so that a one-layer
+ * linear policy W = G, b = 0 gives the law's g_actions, g_x0 and g_v0 bit for bit.  The two sums differ in rounding only.
+ * The reverse pass is a walk, so pic_tape_backward[_feedback] and pic_tape_walk_step apply the same term at a policy step (a walk's
+ * cot_modes on the field such a step read is its cot_obs and needs obs_modes == Mo, else PIC_EINVAL); pic_tape_policy_grad reads
+ * the accumulated g_params after a backward or a pic_tape_walk_end (PIC_ESTATE before one, or once steps were appended).
+ * pic_tape_kl_cot and pic_tape_moments_cot work unchanged on such a tape.  pic_tape_tangent* and pic_tape_tangent_walk_begin
+ * return PIC_EINVAL on it: policy steps are not built in forward mode, and are never treated as open loop. */
+int pic_policy_vjp(pic_handle* h, const pic_policy* p, const double* obs, const double* pre, const double* cot_actions, int mem_kind,
+                   double* g_params, double* g_obs, double* g_pre);
+int pic_tape_step_policy(pic_handle* h, const pic_policy* p, const double* noise, const double* std, int mem_kind, int nsteps,
+                         double* obs_out, double* pre_out, double* actions_out, double* hist);
+int pic_tape_backward_policy(pic_handle* h, const double* cot_hist, const void* cot_x, const void* cot_v, const double* cot_actions,
+                             const double* cot_obs, int mem_kind, double* g_params, double* g_pre, double* g_obs, double* g_actions,
+                             void* g_x0, void* g_v0);
+int pic_tape_policy_grad(pic_handle* h, int mem_kind, double* g_params);
 
 int pic_sync(pic_handle* h);
 /* Number of particle positions found non-finite or out of range by the last sweeps (0 = healthy).  Counts the state's

@@ -184,6 +184,10 @@ SIGNATURES = {
     "pic_copy_envs_rejected": [_vp, _i64p],
     "pic_policy_eval": [_vp, C.POINTER(PicPolicy), _vp, _vp, _vp, C.c_int, _vp, _vp, _vp],
     "pic_step_policy": [_vp, C.POINTER(PicPolicy), _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp],
+    "pic_policy_vjp": [_vp, C.POINTER(PicPolicy), _vp, _vp, _vp, C.c_int, _vp, _vp, _vp],
+    "pic_tape_step_policy": [_vp, C.POINTER(PicPolicy), _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp],
+    "pic_tape_backward_policy": [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pic_tape_policy_grad": [_vp, C.c_int, _vp],
     "pic_sync": [_vp],
     "pic_bad_count": [_vp, _i64p],
     "pic_last_error": [_vp],
@@ -641,6 +645,26 @@ class Handle:
         """pic_step_policy on addresses (0 or None = NULL) in `kind` memory; hist: a host array [nsteps][3][num_envs] or None."""
         self._chk(self.lib.pic_step_policy(self._h, C.byref(spec), *_ptrs(noise, std), int(kind), int(nsteps),
                                            *_ptrs(obs_out, pre_out, actions_out), _ptr(hist)))
+
+    # -- policy gradients on the device (DESIGN.md 7p) -------------------------------------------------------------------------
+    def policy_vjp(self, spec, obs, pre, cot_actions, kind, g_params, g_obs, g_pre):
+        """pic_policy_vjp on addresses (0 or None = NULL) in `kind` memory; spec as for policy_eval."""
+        self._chk(self.lib.pic_policy_vjp(self._h, C.byref(spec), *_ptrs(obs, pre, cot_actions), int(kind),
+                                          *_ptrs(g_params, g_obs, g_pre)))
+
+    def tape_step_policy(self, spec, noise, std, kind, nsteps, obs_out, pre_out, actions_out, hist=None):
+        """pic_tape_step_policy: step_policy's arguments, on an open tape."""
+        self._chk(self.lib.pic_tape_step_policy(self._h, C.byref(spec), *_ptrs(noise, std), int(kind), int(nsteps),
+                                                *_ptrs(obs_out, pre_out, actions_out), _ptr(hist)))
+
+    def tape_backward_policy(self, kind, cot_hist, cot_x, cot_v, cot_actions, cot_obs, g_params, g_pre, g_obs, g_actions, g_x0, g_v0):
+        """pic_tape_backward_policy on addresses (0 or None = NULL) in `kind` memory."""
+        p = _ptrs(cot_hist, cot_x, cot_v, cot_actions, cot_obs, g_params, g_pre, g_obs, g_actions, g_x0, g_v0)
+        self._chk(self.lib.pic_tape_backward_policy(self._h, *p[:5], int(kind), *p[5:]))
+
+    def tape_policy_grad(self, kind, g_params):
+        """pic_tape_policy_grad into the address g_params in `kind` memory."""
+        self._chk(self.lib.pic_tape_policy_grad(self._h, int(kind), _ptr(g_params)))
 
     def step_observe(self, E_ext=None, actions=None, nsteps=1, particles=True, out=None):
         """One Gym-style iteration in one call with one synchronisation (pic_step_observe): nsteps steps under E_ext

@@ -107,6 +107,15 @@ class MLPPolicy:
             at += nout
         return out
 
+    def unpack_grad(self, g):
+        """A flat gradient with respect to the packed parameters ([P], or [num_envs, P]; NumPy or a tensor, e.g. what
+        BatchedPIC.backward_policy or env.grad.rollout_mlp gives) -> [(gW [out, in], gb [out]), ...] with the layers' shapes, in
+        the order of `to_torch()`'s Linear modules: the twin's optimiser takes them as .grad of weight and bias.  `pack` of the
+        result is g again."""
+        if tuple(np.shape(g))[-1:] != (self.n_params,):
+            raise ValueError(f"a gradient of this policy ends in P = {self.n_params} entries, not {list(np.shape(g))}")
+        return self.unpack(g)
+
     @classmethod
     def from_layers(cls, layers, activation, obs_modes, **kwargs):
         return cls(cls.widths_of(layers), activation, cls.pack(layers), obs_modes, **kwargs)

@@ -1,4 +1,4 @@
-// host_policy.h -- the host side of pic_policy_eval and pic_step_policy (kernel: pic_policy.h).
+// host_policy.h -- the host side of pic_policy_eval, pic_step_policy, pic_policy_vjp and pic_tape_step_policy (7p); kernels: pic_policy.h.
 // Included by picstep.hip inside its extern "C" block, behind the stepping entries (step_prologue, actuator_control, advance).
 
 // P, the doubles of one parameter vector
@@ -161,6 +161,212 @@ int pic_policy_eval(pic_handle* h, const pic_policy* p, const double* obs, const
   if (rc) return rc;
   policy_launch(h, a);
   return policy_finish(h, k, a, who);
+}
+
+// ---- the policy's vector-Jacobian product (pic_policy_vjp; kernel: pic_policy.h) ---------------------------------
+// the parts of the handle's policy block a pic_policy_vjp call works on: the per-environment sums, their reduction, and -- for a
+// call in host memory -- the device copies of its inputs and outputs
+struct PolicyVjpCall {
+  double *gE = nullptr, *g = nullptr, *params = nullptr, *scale = nullptr, *obs = nullptr, *pre = nullptr, *cot = nullptr,
+         *g_obs = nullptr, *g_pre = nullptr;
+};
+
+static size_t policy_vjp_parts(Carver& c, PolicyVjpCall& k, const pic_handle* h, const pic_policy* p, bool host, bool has_pre,
+                               bool want_obs, bool want_pre) {
+  const size_t E = (size_t)h->cfg.num_envs, P = policy_param_count(p);
+  const size_t nO = 2 * (size_t)p->obs_modes, nA = 2 * (size_t)h->act_modes;
+  c.take(k.gE, E * P);
+  c.take(k.g, p->per_env ? 0 : P);
+  if (!host) return c.at;
+  c.take(k.params, (p->per_env ? E : 1) * P);
+  c.take(k.scale, p->obs_scale ? nO : 0);
+  c.take(k.obs, E * nO);
+  c.take(k.pre, has_pre ? E * nA : 0);
+  c.take(k.cot, E * nA);
+  c.take(k.g_obs, want_obs ? E * nO : 0);
+  c.take(k.g_pre, want_pre ? E * nA : 0);
+  return c.at;
+}
+
+int pic_policy_vjp(pic_handle* h, const pic_policy* p, const double* obs, const double* pre, const double* cot_actions, int mem_kind,
+                   double* g_params, double* g_obs, double* g_pre) {
+  const char* who = "pic_policy_vjp";
+  if (!h) return PIC_EINVAL;
+  if (const char* bad = policy_bad_args(h, p, mem_kind)) return fail(h, PIC_EINVAL, std::string(who) + ": " + bad);
+  int rc = policy_actuator(h, p, who);
+  if (rc) return rc;
+  if (!obs || !cot_actions) return fail(h, PIC_EINVAL, std::string(who) + ": null obs or cot_actions");
+  if (!pre && p->squash) return fail(h, PIC_EINVAL, std::string(who) + ": pre may be NULL only with squash == 0");
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  const bool host = mem_kind == PIC_HOST;
+  Carver size;
+  PolicyVjpCall k;
+  const size_t bytes = policy_vjp_parts(size, k, h, p, host, pre != nullptr, g_obs != nullptr, g_pre != nullptr);
+  if (bytes > h->pol_bytes) {
+    h->pol_bytes = 0;
+    rc = regrow(h, h->pol, bytes, "pic_policy_vjp: the policy's device block does not fit on the device");
+    if (rc) return rc;
+    h->pol_bytes = bytes;
+  }
+  Carver c;
+  c.base = static_cast<char*>(h->pol.get());
+  policy_vjp_parts(c, k, h, p, host, pre != nullptr, g_obs != nullptr, g_pre != nullptr);
+  const size_t E = (size_t)h->cfg.num_envs, D = sizeof(double), P = policy_param_count(p);
+  const size_t nO = 2 * (size_t)p->obs_modes, nA = 2 * (size_t)h->act_modes;
+  PolicyVjpArgs a{};
+  HIPCHK(h, device_input(h, p->params, mem_kind, (p->per_env ? E : 1) * P * D, k.params, &a.params));
+  HIPCHK(h, device_input(h, p->obs_scale, mem_kind, nO * D, k.scale, &a.obs_scale));
+  HIPCHK(h, device_input(h, obs, mem_kind, E * nO * D, k.obs, &a.obs));
+  HIPCHK(h, device_input(h, pre, mem_kind, E * nA * D, k.pre, &a.pre));
+  HIPCHK(h, device_input(h, cot_actions, mem_kind, E * nA * D, k.cot, &a.cot_a));
+  a.g_params = k.gE;
+  a.g_obs = device_output(g_obs, mem_kind, k.g_obs);
+  a.g_pre = device_output(g_pre, mem_kind, k.g_pre);
+  a.env_params = p->per_env ? (long long)P : 0;
+  a.P = (long long)P;
+  a.action_scale = p->action_scale;
+  a.first = 1;
+  a.Mo = p->obs_modes; a.n_layers = p->n_layers;
+  a.w0 = p->width[0]; a.w1 = p->width[1]; a.w2 = p->width[2]; a.w3 = p->width[3]; a.w4 = p->width[4];
+  a.activation = p->activation; a.squash = p->squash;
+  hipLaunchKernelGGL(policy_vjp_kernel, dim3(h->cfg.num_envs), dim3(BLOCK), 0, h->stream, a);
+  const double* gsrc = k.gE;
+  if (!p->per_env && g_params) {
+    hipLaunchKernelGGL(policy_grad_reduce_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->stream, (const double*)k.gE, k.g,
+                       (long long)P, h->cfg.num_envs);
+    gsrc = k.g;
+  }
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess && g_params)
+    e = hipMemcpyAsync(g_params, gsrc, (p->per_env ? E : 1) * P * D, copy_kind(mem_kind, hipMemcpyDeviceToHost), h->stream);
+  if (host) {
+    if (e == hipSuccess) e = device_result(h, g_obs, a.g_obs, E * nO * D);
+    if (e == hipSuccess) e = device_result(h, g_pre, a.g_pre, E * nA * D);
+  }
+  const hipError_t e2 = host ? hipStreamSynchronize(h->stream) : hipSuccess;
+  if (e != hipSuccess || e2 != hipSuccess)
+    return fail(h, PIC_EHIP, std::string(who) + ": " + hipGetErrorString(e != hipSuccess ? e : e2));
+  return PIC_OK;
+}
+
+// ---- policy steps on an open tape (pic_tape_step_policy) --------------------------------------------------------
+static size_t tape_policy_parts(Carver c, const pic_handle* h, Tape& t, const pic_policy* p, int64_t max_steps) {
+  const size_t E = (size_t)h->cfg.num_envs, T = (size_t)max_steps, P = policy_param_count(p);
+  const size_t orows = T * E * 2 * (size_t)p->obs_modes, arows = T * E * 2 * (size_t)h->act_modes;
+  c.take(t.pobs, orows);
+  c.take(t.ppre, arows);
+  c.take(t.pact, arows);
+  c.take(t.pgobs, orows);             // (pgobs, pgpre, pgact: cleared as one range by walk_open)
+  c.take(t.pgpre, arows);
+  c.take(t.pgact, arows);
+  c.take(t.pcobs, orows);
+  c.take(t.pcact, arows);
+  c.take(t.pmbar, E * 2 * (size_t)p->obs_modes);
+  c.take(t.pgE, E * P);
+  c.take(t.pg, p->per_env ? 0 : P);
+  return c.at;
+}
+
+static bool policy_same_shape(const pic_policy& a, const pic_policy& b) {
+  if (a.obs_modes != b.obs_modes || a.n_layers != b.n_layers || a.activation != b.activation || a.squash != b.squash ||
+      a.per_env != b.per_env)
+    return false;
+  for (int l = 0; l <= a.n_layers; ++l)
+    if (a.width[l] != b.width[l]) return false;
+  return true;
+}
+
+// The policy record of an open tape (allocated by the first policy call) and room for one more call's parameters, within
+// budget_bytes; nothing is enqueued or changed when it fails.
+static int tape_policy_reserve(pic_handle* h, const pic_policy* p, const char* who) {
+  Tape& t = h->tape;
+  if (t.pol_block && !policy_same_shape(t.pshape, *p))
+    return fail(h, PIC_EINVAL, std::string(who) + ": every policy call of one tape must have the same shape (widths, activation, "
+                                                  "squash, per_env, obs_modes)");
+  Tape v;                               // the block's views: the tape's own once the block is there
+  const size_t P = policy_param_count(p), nO = 2 * (size_t)p->obs_modes;
+  const size_t bbytes = t.pol_block ? 0 : tape_policy_parts(Carver{}, h, v, p, t.max_steps);
+  const size_t cbytes = Carver::rounded((p->per_env ? (size_t)h->cfg.num_envs : 1) * P * sizeof(double)) + nO * sizeof(double);
+  if (t.budget > 0 && t.bytes + bbytes + cbytes > (size_t)t.budget)
+    return fail(h, PIC_ENOMEM, std::string(who) + ": the policy's record (" + std::to_string(bbytes + cbytes) +
+                                   " bytes) would take the tape past budget_bytes (pic_tape_start)");
+  if (!t.pol_block) {
+    DeviceBuf<void> block;
+    const int rc = regrow(h, block, bbytes, (std::string(who) + ": the tape's record of the policy's steps does not fit on the device").c_str());
+    if (rc) return rc;
+    tape_policy_parts(Carver{static_cast<char*>(block.get())}, h, v, p, t.max_steps);
+    t.pol_block = std::move(block);
+    t.pobs = v.pobs; t.ppre = v.ppre; t.pact = v.pact; t.pgobs = v.pgobs; t.pgpre = v.pgpre; t.pgact = v.pgact;
+    t.pcobs = v.pcobs; t.pcact = v.pcact; t.pmbar = v.pmbar; t.pgE = v.pgE; t.pg = v.pg;
+    t.pshape = *p;
+    t.pshape.params = t.pshape.obs_scale = nullptr;
+    t.pP = P;
+    t.pol.assign((size_t)t.max_steps, -1);
+    t.bytes += bbytes;
+  }
+  Tape::PolicyCopy pc;
+  const int rc = regrow(h, pc.params, cbytes, (std::string(who) + ": the tape's copy of the parameters does not fit on the device").c_str());
+  if (rc) return rc;
+  pc.scale = p->obs_scale ? pc.params.get() + (cbytes / sizeof(double) - nO) : nullptr;
+  pc.action_scale = p->action_scale;
+  pc.bytes = cbytes;
+  t.pcalls.push_back(std::move(pc));
+  t.bytes += cbytes;
+  return PIC_OK;
+}
+
+int pic_tape_step_policy(pic_handle* h, const pic_policy* p, const double* noise, const double* std, int mem_kind, int nsteps,
+                         double* obs_out, double* pre_out, double* actions_out, double* hist) {
+  const char* who = "pic_tape_step_policy";
+  if (h && !h->tape.on) return fail(h, PIC_ESTATE, "pic_tape_step_policy: no tape is open (pic_tape_start)");
+  int rc = step_prologue(h, nsteps, who, h ? policy_bad_args(h, p, mem_kind) : nullptr);
+  if (rc) return rc;
+  rc = policy_actuator(h, p, who);
+  if (rc || nsteps == 0) return rc;
+  StepControl sc;
+  rc = actuator_control(h, sc, who);
+  if (rc) return rc;
+  Tape& t = h->tape;
+  rc = tape_policy_reserve(h, p, who);
+  if (rc) return rc;
+  // the three records are the tape's rows: the call's own outputs are copied from there behind the steps
+  PolicyCall k{p, nullptr, noise, std, mem_kind, nsteps, true, nullptr, nullptr, nullptr, hist};
+  PolicyArgs a0;
+  rc = policy_begin(h, k, a0);
+  if (rc) {                           // (the copy goes again, and its bytes with it)
+    t.bytes -= t.pcalls.back().bytes;
+    t.pcalls.pop_back();
+    return rc;
+  }
+  const size_t E = (size_t)h->cfg.num_envs, D = sizeof(double), P = t.pP;
+  const size_t nO = 2 * (size_t)p->obs_modes, nA = 2 * (size_t)h->act_modes, T = (size_t)nsteps;
+  const int64_t s0 = t.steps;
+  const Tape::PolicyCopy& pc = t.pcalls.back();
+  double* tp = pc.params.get();
+  HIPCHK(h, hipMemcpyAsync(tp, a0.params, (p->per_env ? E : 1) * P * D, hipMemcpyDeviceToDevice, h->stream));
+  if (pc.scale) HIPCHK(h, hipMemcpyAsync(const_cast<double*>(pc.scale), a0.obs_scale, nO * D, hipMemcpyDeviceToDevice, h->stream));
+  a0.params = tp;
+  a0.obs_scale = pc.scale;
+  a0.obs_out = t.pobs + (size_t)s0 * E * nO;
+  a0.pre_out = t.ppre + (size_t)s0 * E * nA;
+  a0.act = t.pact + (size_t)s0 * E * nA;
+  a0.act_out = nullptr;
+  for (int s = 0; s < nsteps && rc == PIC_OK; ++s) {      // (as pic_step_policy; advance puts e_t = B a_t on the tape)
+    const PolicyArgs a = policy_at(a0, (size_t)s, E, nA);
+    policy_launch(h, a);
+    sc.ctl.act = a.act;
+    rc = advance(h, sc, 1, hist_at(h, k.d_hist, (size_t)s));
+  }
+  for (int64_t s = s0; s < t.steps; ++s) t.pol[(size_t)s] = (int)t.pcalls.size() - 1;
+  const hipMemcpyKind outk = copy_kind(mem_kind, hipMemcpyDeviceToHost);
+  hipError_t e = hipSuccess;
+  if (e == hipSuccess && obs_out) e = hipMemcpyAsync(obs_out, a0.obs_out, T * E * nO * D, outk, h->stream);
+  if (e == hipSuccess && pre_out) e = hipMemcpyAsync(pre_out, a0.pre_out, T * E * nA * D, outk, h->stream);
+  if (e == hipSuccess && actions_out) e = hipMemcpyAsync(actions_out, a0.act, T * E * nA * D, outk, h->stream);
+  if (e != hipSuccess) return fail(h, PIC_EHIP, std::string(who) + ": " + hipGetErrorString(e));
+  const int rf = policy_finish(h, k, a0, who);      // (the energies' record; after a failed step too)
+  if (!rf && mem_kind == PIC_HOST && !hist && (obs_out || pre_out || actions_out)) HIPCHK(h, hipStreamSynchronize(h->stream));
+  return rc ? rc : rf;
 }
 
 int pic_step_policy(pic_handle* h, const pic_policy* p, const double* noise, const double* std, int mem_kind, int nsteps,

@@ -185,6 +185,7 @@ static int tape_tangent(pic_handle* h, const char* who, int K, const double* d_e
   Tape& t = h->tape;
   const std::string w(who);
   if (int rc = check_tape_open(h, w.c_str())) return rc;
+  if (int rc = check_no_policy_steps(h, w.c_str())) return rc;
   if (d_kl && !t.kl) return fail(h, PIC_ESTATE, w + ": d_kl needs a KL on the tape (pic_tape_kl_start before the first step)");
   if (K < 1 || K > kMaxTangents) return fail(h, PIC_EINVAL, w + ": need 1 <= K <= " + std::to_string(kMaxTangents));
   if (d_ext && d_actions) return fail(h, PIC_EINVAL, w + ": d_ext and d_actions are both given (at most one)");

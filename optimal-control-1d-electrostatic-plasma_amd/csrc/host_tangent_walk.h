@@ -126,6 +126,7 @@ static int tanwalk_open(pic_handle* h, const char* who, int K, int mo, const voi
   Tape& t = h->tape;
   const std::string w(who);
   if (int rc = check_tape_open(h, who)) return rc;
+  if (int rc = check_no_policy_steps(h, who)) return rc;
   if (K < 1 || K > kMaxTangents) return fail(h, PIC_EINVAL, w + ": need 1 <= K <= " + std::to_string(kMaxTangents));
   if (mo < 0 || mo >= h->cfg.Ng) return fail(h, PIC_EINVAL, w + ": need obs_modes = 0 or 1 <= obs_modes < N_mesh");
   if (int rc = check_mem_kind(h, mem_kind, who)) return rc;
@@ -325,6 +326,7 @@ int pic_tape_tangent_feedback(pic_handle* h, int K, const double* d_gain, const 
   if (!h) return PIC_EINVAL;
   Tape& t = h->tape;
   if (int rc = check_tape_open(h, who)) return rc;
+  if (int rc = check_no_policy_steps(h, who)) return rc;
   for (const void* p : {(const void*)d_actions, (const void*)d_modes, (const void*)d_actions_out})
     if (int rc = check_tape_actuator(h, p, "d_actions, d_modes or d_actions_out", who)) return rc;
   int rc = tanwalk_open(h, who, K, 0, d_x0, d_v0, d_gain, mem_kind, nullptr);

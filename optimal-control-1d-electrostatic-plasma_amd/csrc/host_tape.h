@@ -323,8 +323,10 @@ static int walk_open(pic_handle* h, int mo) {
   Tape& t = h->tape;
   const size_t part = (size_t)h->cfg.num_envs * h->ld, mesh = (size_t)h->cfg.num_envs * h->cfg.Ng;
   t.walk = t.twalk = false;          // (a forward walk replays into the same segment buffer)
-  if (mo > 0) {
-    const int rc = ensure_twiddle(h, mo);
+  t.pvalid = false;
+  const int mp = t.pol_block ? t.pshape.obs_modes : 0;      // a policy step's m-bar goes the way of a walk's mode cotangent
+  if (mo > 0 || mp > 0) {
+    const int rc = ensure_twiddle(h, std::max(mo, mp));
     if (rc) return rc;
     if (!t.lE && !t.wE && alloc(t.wE, mesh * sizeof(double)) != hipSuccess) {
       (void)hipGetLastError();
@@ -335,6 +337,9 @@ static int walk_open(pic_handle* h, int mo) {
   HIPCHK(h, hipMemsetAsync(t.counters, 0, 2 * sizeof(unsigned long long), h->stream));
   if (t.steps > 0) HIPCHK(h, hipMemsetAsync(t.gext, 0, (size_t)t.steps * mesh * sizeof(double), h->stream));
   HIPCHK(h, hipMemsetAsync(t.lam, 0, 2 * part * sizeof(double), h->stream));
+  if (t.pol_block) HIPCHK(h, hipMemsetAsync(t.pgobs, 0, Carver::upto(t.pgobs, t.pcobs), h->stream));    // o-bar, u-bar, a-bar
+  t.pfirst = true;
+  t.pcot_obs = t.pcot_act = false;
   t.walk = true;
   t.wnext = t.steps - 1;
   t.wmo = mo;
@@ -382,12 +387,66 @@ struct WalkCot {
   long long cld = 0;
 };
 
+// The policy's part of a reverse pass: step s ran under an MLP policy and e-bar_s is complete.  a-bar_s = B^T
+// e-bar_s (summed inside policy_vjp_kernel, in both of the gain law's orders: pic_policy.h) plus a backward's direct cotangent;
+// the kernel gives u-bar_s, o-bar_s and adds the step's parameter terms to the per-environment sums; m-bar_s = o-bar_s plus a direct
+// cotangent on the observation (a backward's row, or the walk's mode cotangent c.modes on the same field) replaces c.modes, so
+// tape_mode_cot sends it through J^T as it sends a walk's.
+static bool tape_policy_step(const pic_handle* h, int64_t s) {
+  const Tape& t = h->tape;
+  return s >= 0 && s < t.steps && !t.pol.empty() && t.pol[(size_t)s] >= 0;
+}
+
+static int tape_policy_reverse(pic_handle* h, int64_t s, WalkCot& c) {
+  Tape& t = h->tape;
+  const int E = h->cfg.num_envs, Ng = h->cfg.Ng, M = h->act_modes, Mo = t.pshape.obs_modes;
+  if (c.modes && c.mc != Mo)
+    return fail(h, PIC_EINVAL, "pic_tape_walk: a mode cotangent on the field a policy step reads needs obs_modes = the policy's " +
+                                   std::to_string(Mo) + " (pic_tape_walk_begin)");
+  const size_t arow = (size_t)E * 2 * M, orow = (size_t)E * 2 * Mo;
+  const Tape::PolicyCopy& pc = t.pcalls[(size_t)t.pol[(size_t)s]];
+  const pic_policy& p = t.pshape;
+  PolicyVjpArgs a{};
+  a.obs = t.pobs + (size_t)s * orow;
+  a.obs_scale = pc.scale;
+  a.params = pc.params.get();
+  a.pre = t.ppre + (size_t)s * arow;
+  a.gext = t.gext + (size_t)s * E * Ng;
+  a.basis = h->basis;
+  a.Ng = Ng;
+  a.cot_a2 = t.pcot_act ? t.pcact + (size_t)s * arow : nullptr;
+  a.cot_obs = c.modes ? c.modes : (t.pcot_obs ? t.pcobs + (size_t)s * orow : nullptr);
+  a.g_params = t.pgE;
+  a.g_obs = t.pgobs + (size_t)s * orow;
+  a.g_pre = t.pgpre + (size_t)s * arow;
+  a.g_act = t.pgact + (size_t)s * arow;
+  a.mbar = t.pmbar;
+  a.env_params = p.per_env ? (long long)t.pP : 0;
+  a.P = (long long)t.pP;
+  a.action_scale = pc.action_scale;
+  a.first = t.pfirst ? 1 : 0;
+  a.Mo = Mo; a.n_layers = p.n_layers;
+  a.w0 = p.width[0]; a.w1 = p.width[1]; a.w2 = p.width[2]; a.w3 = p.width[3]; a.w4 = p.width[4];
+  a.activation = p.activation; a.squash = p.squash;
+  hipLaunchKernelGGL(policy_vjp_kernel, dim3(E), dim3(BLOCK), 0, h->stream, a);
+  t.pfirst = false;
+  ++t.launches;
+  c.modes = t.pmbar;
+  c.mc = Mo;
+  return PIC_OK;
+}
+
 // reverse step t.wnext (its energy cotangents in t.cot's row): first the replay of its segment if it is the segment's last step
-static int walk_reverse(pic_handle* h, const WalkCot& c, const AdjArgs& a, const WalkGeom& g) {
+static int walk_reverse(pic_handle* h, const WalkCot& given, const AdjArgs& a, const WalkGeom& g) {
   Tape& t = h->tape;
   const int E = h->cfg.num_envs;
   const size_t part = (size_t)E * h->ld, mesh = (size_t)E * h->cfg.Ng;
   const int64_t s = t.wnext, sgi = s / t.every, t0 = sgi * t.every, i = s - t0;
+  WalkCot c = given;
+  if (tape_policy_step(h, s + 1)) {         // the policy of step s + 1 read the field step s left (nothing is enqueued if it fails)
+    const int rc = tape_policy_reverse(h, s + 1, c);
+    if (rc) return rc;
+  }
   if (s + 1 == std::min<int64_t>(t0 + t.every, t.steps)) {
     const int rc = walk_replay(h, sgi, a, g);
     if (rc) return rc;
@@ -429,10 +488,15 @@ static int walk_reverse(pic_handle* h, const WalkCot& c, const AdjArgs& a, const
 
 // after the last reverse step: the field at the tape start (read by a first law step and by the caller's observation c.modes)
 // and the caller's cotangents on the starting state reach lambda_0 = (g_x0, g_v0)
-static int walk_close(pic_handle* h, const WalkCot& c, const AdjArgs& a, const WalkGeom& g) {
+static int walk_close(pic_handle* h, const WalkCot& given, const AdjArgs& a, const WalkGeom& g) {
   Tape& t = h->tape;
   const int E = h->cfg.num_envs;
   const size_t part = (size_t)E * h->ld;
+  WalkCot c = given;
+  if (tape_policy_step(h, 0)) {             // a first step under a policy read the field the tape started from
+    const int rc = tape_policy_reverse(h, 0, c);
+    if (rc) { t.walk = false; return rc; }
+  }
   const double* Ebar = t.steps > 0 ? tape_mode_cot(h, 0, c.modes, c.mc) : nullptr;
   const bool field = Ebar != nullptr;
   if (field) {      // lambda_x0 += s W'(x_0) . K^T E-bar_0 at the tape-start positions
@@ -447,6 +511,7 @@ static int walk_close(pic_handle* h, const WalkCot& c, const AdjArgs& a, const W
   }
   if (tape_moments_row(h, -1)) tape_moments_reverse(h, -1, t.ck, t.ck + part, t.lam, t.lam + part);   // m-bar at the tape start
   t.walk = false;
+  t.pvalid = t.pol_block && !t.pfirst;
   HIPCHK(h, hipGetLastError());
   return PIC_OK;
 }
@@ -484,10 +549,52 @@ static int tape_actions_out(pic_handle* h, int64_t s0, int64_t n, int mem_kind, 
   return PIC_OK;
 }
 
+// what pic_tape_backward_policy adds to a backward: direct cotangents on the policy steps' actions and observations (each may be
+// null) and the per-step outputs (each may be null), all in the call's mem_kind
+struct PolicyBackward {
+  const double *cot_actions, *cot_obs;
+  double *g_params, *g_pre, *g_obs, *g_actions;
+};
+
+// the accumulated parameter gradient to the caller's g_params: [env][P] with per_env, else the environments' sums added in
+// ascending order
+static int tape_policy_grad_out(pic_handle* h, int mem_kind, double* g_params) {
+  Tape& t = h->tape;
+  const size_t P = t.pP, E = (size_t)h->cfg.num_envs;
+  const hipMemcpyKind outk = copy_kind(mem_kind, hipMemcpyDeviceToHost);
+  if (t.pshape.per_env) {
+    HIPCHK(h, hipMemcpyAsync(g_params, t.pgE, E * P * sizeof(double), outk, h->stream));
+    return PIC_OK;
+  }
+  hipLaunchKernelGGL(policy_grad_reduce_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->stream, (const double*)t.pgE, t.pg,
+                     (long long)P, (int)E);
+  ++t.launches;
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(g_params, t.pg, P * sizeof(double), outk, h->stream));
+  return PIC_OK;
+}
+
+// the outputs of pic_tape_backward_policy behind the walk
+static int tape_policy_out(pic_handle* h, int mem_kind, const PolicyBackward& pb) {
+  Tape& t = h->tape;
+  const size_t E = (size_t)h->cfg.num_envs, T = (size_t)t.steps, D = sizeof(double);
+  const size_t arow = E * 2 * h->act_modes, orow = E * 2 * t.pshape.obs_modes;
+  const hipMemcpyKind outk = copy_kind(mem_kind, hipMemcpyDeviceToHost);
+  if (pb.g_params) {
+    const int rc = tape_policy_grad_out(h, mem_kind, pb.g_params);
+    if (rc) return rc;
+  }
+  if (T == 0) return PIC_OK;
+  if (pb.g_pre) HIPCHK(h, hipMemcpyAsync(pb.g_pre, t.pgpre, T * arow * D, outk, h->stream));
+  if (pb.g_obs) HIPCHK(h, hipMemcpyAsync(pb.g_obs, t.pgobs, T * orow * D, outk, h->stream));
+  if (pb.g_actions) HIPCHK(h, hipMemcpyAsync(pb.g_actions, t.pgact, T * arow * D, outk, h->stream));
+  return PIC_OK;
+}
+
 // the whole reverse pass in one call: a walk over every step with the whole trajectory's cotangents
 static int tape_backward(pic_handle* h, const char* who, const double* cot_hist, const void* cot_x, const void* cot_v,
                          const double* cot_modes, int mem_kind, double* g_ext, double* g_actions, void* g_x0, void* g_v0,
-                         double* modes_out) {
+                         double* modes_out, const PolicyBackward* pb = nullptr) {
   Tape& t = h->tape;
   const std::string w(who);
   if (int rc = check_tape_open(h, who)) return rc;
@@ -506,6 +613,17 @@ static int tape_backward(pic_handle* h, const char* who, const double* cot_hist,
   if (cot_x) rc = upload(h, t.lam, cot_x, mem_kind);
   if (!rc && cot_v) rc = upload(h, t.lam + (size_t)E * h->ld, cot_v, mem_kind);
   if (rc) { t.walk = false; return rc; }
+  if (pb && T > 0) {                  // the direct cotangents of the policy steps, read row by row by the walk
+    const size_t arow = (size_t)E * 2 * h->act_modes, orow = (size_t)E * 2 * t.pshape.obs_modes;
+    if (pb->cot_actions) {
+      HIPCHK(h, device_fill(h, t.pcact, pb->cot_actions, (size_t)T * arow * sizeof(double), mem_kind));
+      t.pcot_act = true;
+    }
+    if (pb->cot_obs) {
+      HIPCHK(h, device_fill(h, t.pcobs, pb->cot_obs, (size_t)T * orow * sizeof(double), mem_kind));
+      t.pcot_obs = true;
+    }
+  }
   // steps of the gain law: the action of step s + 1 depends on the field step s left, so the refresh adjoint of
   // step s also carries E-bar_{s+1} = J^T (G^T a-bar_{s+1} + m-bar_{s+1}); E-bar_0 reaches x_0 through the field at the start
   const bool law = !t.law.empty();
@@ -531,8 +649,37 @@ static int tape_backward(pic_handle* h, const char* who, const double* cot_hist,
     else HIPCHK(h, hipMemsetAsync(modes_out, 0, (size_t)T * lrow * sizeof(double), h->stream));
   }
   if (g_actions && T > 0) rc = tape_actions_out(h, 0, T, mem_kind, g_actions);
+  if (!rc && pb) rc = tape_policy_out(h, mem_kind, *pb);
   if (rc) return rc;
   return walk_finish(h, w, mem_kind, g_x0, g_v0);
+}
+
+int pic_tape_backward_policy(pic_handle* h, const double* cot_hist, const void* cot_x, const void* cot_v, const double* cot_actions,
+                             const double* cot_obs, int mem_kind, double* g_params, double* g_pre, double* g_obs, double* g_actions,
+                             void* g_x0, void* g_v0) {
+  const char* who = "pic_tape_backward_policy";
+  if (!h) return PIC_EINVAL;
+  if (int rc = check_tape_open(h, who)) return rc;
+  if (!h->tape.pol_block) return fail(h, PIC_ESTATE, std::string(who) + ": the tape holds no steps of pic_tape_step_policy");
+  const PolicyBackward pb{cot_actions, cot_obs, g_params, g_pre, g_obs, g_actions};
+  return tape_backward(h, who, cot_hist, cot_x, cot_v, nullptr, mem_kind, nullptr, nullptr, g_x0, g_v0, nullptr, &pb);
+}
+
+int pic_tape_policy_grad(pic_handle* h, int mem_kind, double* g_params) {
+  const char* who = "pic_tape_policy_grad";
+  if (!h) return PIC_EINVAL;
+  if (int rc = check_tape_open(h, who)) return rc;
+  if (int rc = check_mem_kind(h, mem_kind, who)) return rc;
+  if (!g_params) return fail(h, PIC_EINVAL, std::string(who) + ": null g_params");
+  Tape& t = h->tape;
+  if (!t.pol_block) return fail(h, PIC_ESTATE, std::string(who) + ": the tape holds no steps of pic_tape_step_policy");
+  if (!t.pvalid)
+    return fail(h, PIC_ESTATE, std::string(who) + ": no finished reverse pass over the steps taped so far (pic_tape_walk_end or a backward first)");
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  const int rc = tape_policy_grad_out(h, mem_kind, g_params);
+  if (rc) return rc;
+  if (mem_kind == PIC_HOST) HIPCHK(h, hipStreamSynchronize(h->stream));
+  return PIC_OK;
 }
 
 int pic_tape_backward(pic_handle* h, const double* cot_hist, const void* cot_x, const void* cot_v, int mem_kind, double* g_ext,

@@ -1,4 +1,4 @@
-// pic_policy.h -- the MLP policy a = pi(o) on the modes of the mesh field (pic_policy_eval, pic_step_policy).
+// pic_policy.h -- the MLP policy a = pi(o) on the modes of the mesh field (pic_policy_eval, pic_step_policy) and its VJP (7p).
 // Included by picstep.hip only, behind pic_device.h.
 #pragma once
 
@@ -102,6 +102,191 @@ __global__ __launch_bounds__(BLOCK) void policy_kernel(PolicyArgs a) {
       if (a.act_out) a.act_out[at] = act;
     }
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The policy's vector-Jacobian product (pic_policy_vjp, pic_tape_backward_policy; include/picstep.h)
+// ---------------------------------------------------------------------------------------------
+// One evaluation of the VJP for every environment.  Pointers are those of environment 0 (and of the step the launch is for).
+struct PolicyVjpArgs {
+  const double* obs;         // [env][2 Mo] the recorded observation (before obs_scale)
+  const double* obs_scale;   // [2 Mo] or null
+  const double* params;      // as PolicyArgs
+  const double* pre;         // [env][nA] the recorded u, or null (squash == 0)
+  const double* cot_a;       // [env][nA] a cotangent on the action, or null: 0 (gext null)
+  const double* gext;        // [env][Ng] e-bar of the step, or null: the cotangent on the action is then B^T e-bar, not cot_a
+  const double* basis;       // [2][Ng][M] the actuator's tables (gext)
+  const double* cot_a2;      // [env][nA] a second one, added to the first (the caller's direct cotangent), or null
+  const double* cot_obs;     // [env][2 Mo] a direct cotangent on the observation: m-bar = o-bar + cot_obs, or null
+  double* g_params;          // [env][P] per-environment sums: g = g + term (first: g = term)
+  double* g_obs;             // [env][2 Mo] o-bar, or null
+  double* g_pre;             // [env][nA] u-bar, or null
+  double* g_act;             // [env][nA] the reported a-bar (+ cot_a2), or null
+  double* mbar;              // [env][2 Mo] the o-bar that goes on into the plasma, + cot_obs; or null
+  long long env_params;      // doubles from one environment's parameters to the next (0: shared)
+  long long P;               // doubles of one parameter vector
+  double action_scale;
+  int first;                 // this launch starts the sums of g_params
+  int Ng;                    // (gext)
+  int Mo, n_layers;
+  int w0, w1, w2, w3, w4;
+  int activation, squash;
+};
+
+// One backward sweep through the layers from the delta in ds[0] (a barrier behind its write), ending in a barrier.  REP: the sweep
+// of the reported a-bar: it adds the parameter terms and writes g_obs.  PROP: the sweep whose o-bar goes on: it writes mbar.
+template <bool REP, bool PROP>
+__device__ __forceinline__ void policy_vjp_sweep(const PolicyVjpArgs& a, const double* __restrict__ p0,
+                                                 const double (*hs)[kPolicyMaxWidth], double (*ds)[kPolicyMaxWidth], int env, int t) {
+  const int width[kPolicyMaxLayers + 1] = {a.w0, a.w1, a.w2, a.w3, a.w4};
+  const int L = a.n_layers, n0 = a.w0;
+  long long off[kPolicyMaxLayers];    // where each layer's W starts in the parameter vector
+  {
+    long long at = 0;
+#pragma unroll
+    for (int l = 0; l < kPolicyMaxLayers; ++l) {
+      off[l] = at;
+      at += (long long)width[l + 1] * width[l] + width[l + 1];
+    }
+  }
+  double* __restrict__ g = a.g_params + (size_t)env * a.P;
+  int cur = 0;
+#pragma unroll
+  for (int l = kPolicyMaxLayers - 1; l >= 0; --l) {
+    if (l >= L) continue;               // (uniform)
+    const int nin = width[l], nout = width[l + 1];
+    const double* __restrict__ W = p0 + off[l];
+    const double* __restrict__ delta = ds[cur];
+    const double* __restrict__ hin = hs[l];
+    if (REP) {
+      double* __restrict__ gW = g + off[l];
+      double* __restrict__ gb = gW + (size_t)nout * nin;
+      if (t < nout) gb[t] = a.first ? delta[t] : gb[t] + delta[t];
+      for (int at = t; at < nout * nin; at += BLOCK) {      // (at most 65536: an int)
+        const int i = at / nin, k = at - i * nin;
+        const double term = delta[i] * hin[k];
+        gW[at] = a.first ? term : gW[at] + term;
+      }
+    }
+    if (t < nin) {
+      double s = W[t] * delta[0];
+      for (int i = 1; i < nout; ++i) s = s + W[(size_t)i * nin + t] * delta[i];
+      if (l > 0) {
+        const double hv = hin[t];
+        const double dact = a.activation == PIC_ACT_TANH ? 1.0 - hv * hv : (hv > 0.0 ? 1.0 : 0.0);
+        ds[cur ^ 1][t] = s * dact;
+      } else {
+        const double ob = a.obs_scale ? s * a.obs_scale[t] : s;
+        const size_t at = (size_t)env * n0 + t;
+        if (REP && a.g_obs) a.g_obs[at] = ob;
+        if (PROP && a.mbar) a.mbar[at] = a.cot_obs ? ob + a.cot_obs[at] : ob;
+      }
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+}
+
+// One workgroup per environment.  The forward is recomputed with policy_row / policy_activation (the forward's bits): thread i
+// owns row i.  Backwards thread k owns column k of W^T delta, so consecutive lanes read consecutive W[i][k]; the parameter terms
+// delta_i h_k are one read-modify-write of the environment's own [P] block, element idx by thread idx % BLOCK: no two lanes, and
+// no two workgroups, touch one sum.  The activations of every layer and two delta vectors live in LDS.
+__global__ __launch_bounds__(BLOCK) void policy_vjp_kernel(PolicyVjpArgs a) {
+  __shared__ double hs[kPolicyMaxLayers][kPolicyMaxWidth];      // h_0 .. h_{L-1}
+  __shared__ double ds[2][kPolicyMaxWidth];
+  const int env = blockIdx.x, t = threadIdx.x;
+  const int width[kPolicyMaxLayers + 1] = {a.w0, a.w1, a.w2, a.w3, a.w4};
+  const int n0 = a.w0, L = a.n_layers;
+  if (t < n0) {
+    const double o = a.obs[(size_t)env * n0 + t];
+    hs[0][t] = a.obs_scale ? o * a.obs_scale[t] : o;
+  }
+  __syncthreads();
+  const double* __restrict__ p0 = a.params + (size_t)env * a.env_params;
+  {
+    const double* __restrict__ p = p0;
+#pragma unroll
+    for (int l = 0; l < kPolicyMaxLayers - 1; ++l) {
+      if (l + 1 >= L) break;            // (uniform)
+      const int nin = width[l], nout = width[l + 1];
+      const double* __restrict__ W = p;
+      const double* __restrict__ b = p + (size_t)nout * nin;
+      p = b + nout;
+      if (t < nout) hs[l + 1][t] = policy_activation(policy_row(W, b, hs[l], t, nin), a.activation);
+      __syncthreads();
+    }
+  }
+  const int nA = L == 1 ? a.w1 : (L == 2 ? a.w2 : (L == 3 ? a.w3 : a.w4));
+  // Inside a reverse pass (gext) a-bar = B^T e-bar is formed twice, as the gain law's backward forms it:
+  // ab_rep with adjoint_actions_kernel's sum (the mesh ascending, from 0.0) is the a-bar that is reported and that the parameter
+  // gradient, u-bar and o-bar follow from; ab_prop with law_adjoint_kernel's sum (lanes strided by 64, then wave_sum) is the
+  // one whose o-bar goes on into the plasma, so that a linear policy continues the law's reverse pass bit for bit.  The two
+  // differ in rounding only.  One wave per coefficient makes both from the same rounded products: each lane adds its own to
+  // the strided sum, and every lane adds all 64 of a chunk in lane order (readlane with a uniform index) to the ascending one.
+  // Outside a reverse pass (pic_policy_vjp) there is one a-bar and one sweep.
+  double ab_rep = 0.0, ab_prop = 0.0, sq = 1.0;
+  if (a.gext) {
+    const double* __restrict__ g = a.gext + (size_t)env * a.Ng;
+    const int lane = t & 63, Mh = nA / 2;
+    for (int m = t >> 6; m < nA; m += WAVES) {          // (uniform within a wave)
+      const double* __restrict__ b = a.basis + (m < Mh ? 0 : (size_t)a.Ng * Mh);
+      const int mm = m < Mh ? m : m - Mh;
+      double strided = 0.0, ascending = 0.0;
+      for (int base = 0; base < a.Ng; base += 64) {
+        const int j = base + lane;
+        double p = 0.0;
+        if (j < a.Ng) {
+          p = b[(size_t)j * Mh + mm] * g[j];
+          strided += p;
+        }
+        const int cnt = a.Ng - base < 64 ? a.Ng - base : 64;
+        for (int l = 0; l < cnt; ++l)
+          ascending += __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(p), l),
+                                        __builtin_amdgcn_readlane(__double2loint(p), l));
+      }
+      strided = wave_sum(strided);
+      if (lane == 0) { ds[0][m] = ascending; ds[1][m] = strided; }      // (both free until the first sweep's delta goes there)
+    }
+    __syncthreads();
+    if (t < nA) { ab_rep = ds[0][t]; ab_prop = ds[1][t]; }
+    __syncthreads();
+  } else if (t < nA && a.cot_a) {
+    ab_rep = ab_prop = a.cot_a[(size_t)env * nA + t];
+  }
+  if (t < nA) {
+    const size_t at = (size_t)env * nA + t;
+    if (a.cot_a2) {
+      ab_rep = ab_rep + a.cot_a2[at];
+      ab_prop = ab_prop + a.cot_a2[at];
+    }
+    if (a.squash) {
+      const double th = tanh(a.pre[at]);
+      sq = a.action_scale * (1.0 - th * th);
+    }
+    if (a.g_act) a.g_act[at] = ab_rep;
+    if (a.g_pre) a.g_pre[at] = a.squash ? ab_rep * sq : ab_rep;
+    ds[0][t] = a.squash ? ab_rep * sq : ab_rep;
+  }
+  __syncthreads();
+  if (!a.gext) {                        // (uniform)
+    policy_vjp_sweep<true, true>(a, p0, hs, ds, env, t);
+    return;
+  }
+  policy_vjp_sweep<true, false>(a, p0, hs, ds, env, t);
+  if (t < nA) ds[0][t] = a.squash ? ab_prop * sq : ab_prop;
+  __syncthreads();
+  policy_vjp_sweep<false, true>(a, p0, hs, ds, env, t);
+}
+
+// g [P] = the per-environment sums gE [env][P] added in ascending environment order, the first starting the sum: one thread per
+// parameter
+__global__ __launch_bounds__(256) void policy_grad_reduce_kernel(const double* __restrict__ gE, double* __restrict__ g,
+                                                                 long long P, int num_envs) {
+  const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= P) return;
+  double s = gE[p];
+  for (int e = 1; e < num_envs; ++e) s = s + gE[(size_t)e * P + p];
+  g[p] = s;
 }
 
 }  // namespace

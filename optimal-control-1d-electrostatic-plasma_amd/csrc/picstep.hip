@@ -255,6 +255,28 @@ struct Tape {
   DeviceBuf<void> tmom_block;
   unsigned long long* tmom_acc = nullptr;   // [3][K][env][Ng] integer sums of the step at hand, zero between uses
   unsigned long long* tmom_max = nullptr;   // [3][K][env] bit patterns of the terms' bounds, zero between uses
+  // steps under an MLP policy (pic_tape_step_policy): one block allocated by the first such call (pobs .. pg are
+  // views into it) and one copy of the parameters and obs_scale per call; all count in `bytes`
+  DeviceBuf<void> pol_block;
+  pic_policy pshape{};                // the shape every policy call of this tape has (params, obs_scale: unused)
+  size_t pP = 0;                      // doubles of one parameter vector
+  double* pobs = nullptr;             // [max_steps][env][2 Mo] o_t of the policy's steps
+  double* ppre = nullptr;             // [max_steps][env][2M] u_t
+  double* pact = nullptr;             // [max_steps][env][2M] a_t (their e_t = B a_t goes to `ext` as an actions step's)
+  double* pgobs = nullptr;            // [max_steps][env][2 Mo] o-bar_t of the last reverse pass, zero on the other steps
+  double* pgpre = nullptr;            // [max_steps][env][2M] u-bar_t
+  double* pgact = nullptr;            // [max_steps][env][2M] a-bar_t = B^T e-bar_t + the direct cotangent
+  double* pcobs = nullptr;            // [max_steps][env][2 Mo] direct cotangents on o_t of a backward
+  double* pcact = nullptr;            // [max_steps][env][2M] direct cotangents on a_t of a backward
+  double* pmbar = nullptr;            // [env][2 Mo] m-bar of the step being reversed
+  double* pgE = nullptr;              // [env][P] the parameter gradient's per-environment sums
+  double* pg = nullptr;               // [P] their sum in ascending environment order (shared parameters)
+  struct PolicyCopy { DeviceBuf<double> params; const double* scale; double action_scale; size_t bytes; };
+  std::vector<PolicyCopy> pcalls;     // per call: params [P] or [env][P], then obs_scale [2 Mo] behind them (scale: null without)
+  std::vector<int> pol;               // [max_steps] per step: the index of its call in `pcalls`, or -1 (empty: no policy step yet)
+  bool pfirst = true;                 // the reverse pass in progress has met no policy step yet: the next one starts pgE's sums
+  bool pcot_obs = false, pcot_act = false;   // pcobs / pcact hold a backward's cotangents
+  bool pvalid = false;                // pgE holds the sums of a finished reverse pass over the steps taped so far
 };
 
 }  // namespace
@@ -1315,7 +1337,7 @@ static int advance(pic_handle* h, const StepControl& sc, int nsteps, double* his
   Recorder& r = h->rec;
   Tape& t = h->tape;
   const int E = h->cfg.num_envs;
-  t.walk = t.twalk = false;           // appending abandons a walk
+  t.walk = t.twalk = t.pvalid = false;   // appending abandons a walk (and dates the policy gradient of the last one)
   for (int done = 0; done < nsteps;) {
     int64_t n = nsteps - done;
     if (r.on) n = std::min<int64_t>(n, r.stride - r.k % r.stride);

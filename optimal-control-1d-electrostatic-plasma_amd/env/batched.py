@@ -50,6 +50,7 @@ class BatchedPIC:
         self._tape_kl = False                # (the open tape records the smoothed KL)
         self._tape_moments = False           # (the open tape has held cotangents on the moments)
         self._tape_mom_trace = False         # (the open tape records the moments of every step)
+        self._tape_policy = None             # (obs width, P, per_env) of the open tape's policy steps
         self._tape_serial = self._walk_serial = 0       # (the tape env.grad opened last, the walk in progress)
 
     # reset(x0, v0): x0, v0 are [num_envs, N] with any velocity perturbation already applied
@@ -236,7 +237,7 @@ class BatchedPIC:
         whole rollout; the library draws nothing) or None; std [2M] or None.  -> PolicyRollout(obs [nsteps, num_envs, 2 M_o],
         pre, actions [nsteps, num_envs, 2M], KE, PE, PE_reward [nsteps, num_envs] NumPy -- None without history).  NumPy, or
         float64 CUDA tensors if an input is one or with on_device (then asynchronous without history).  Refused while a tape is
-        open: env.grad.rollout_policy is the differentiable route."""
+        open: tape_step_policy / env.grad.rollout_mlp are the differentiable route (env.grad.rollout_policy for other networks)."""
         from ..control.policy import PolicyRollout
         T = int(nsteps)
         mem, spec, keep, _, noise, std, (o, u, a) = self._policy_call(policy, T, None, noise, std, on_device)
@@ -246,6 +247,82 @@ class BatchedPIC:
         mem.leave(self._h)
         ke, pe, per = (None, None, None) if hist is None else (hist[:, 0], hist[:, 1], hist[:, 2])
         return PolicyRollout(o, u, a, ke, pe, per)
+
+    # -- policy gradients on the device (pic_policy_vjp, pic_tape_step_policy, pic_tape_backward_policy) -----------
+    def policy_vjp(self, policy, obs, cot_actions, pre=None, on_device: bool = False):
+        """The vector-Jacobian product of `policy_eval` for every environment (pic_policy_vjp): from observations obs
+        [num_envs, 2 M_o], the recorded pre (u) [num_envs, 2M] (needed with squash only) and a cotangent cot_actions
+        [num_envs, 2M] on the actions -> (g_params [P], or [num_envs, P] with per_env; g_obs [num_envs, 2 M_o]; g_pre
+        [num_envs, 2M]).  The gradient with respect to std is sum(g_pre * eps).  NumPy, or float64 CUDA tensors if an input is
+        one or with on_device.  The state is not touched."""
+        E, nO, nA = self.num_envs, 2 * policy.obs_modes, 2 * self.max_mode
+        mem = Mem.of(self, policy.params, obs, pre, cot_actions, force_device=on_device)
+        spec, keep = policy.spec(mem, E)
+        obs, pre, cot = mem.f64(obs, (E, nO)), mem.f64(pre, (E, nA)), mem.f64(cot_actions, (E, nA))
+        gp = mem.empty((E, policy.n_params) if policy.per_env else (policy.n_params,))
+        go, gu = mem.empty((E, nO)), mem.empty((E, nA))
+        mem.enter()
+        self._h.policy_vjp(spec, mem.addr(obs), mem.addr(pre), mem.addr(cot), mem.kind, mem.addr(gp), mem.addr(go), mem.addr(gu))
+        mem.leave(self._h)
+        del keep
+        return gp, go, gu
+
+    def tape_step_policy(self, policy, nsteps: int, noise=None, std=None, history: bool = True, on_device: bool = False):
+        """`step_policy` appended to the open tape (pic_tape_step_policy): the same arguments, the same PolicyRollout and the
+        same bits, and the steps can be differentiated through the policy by `backward_policy`.  The tape keeps a copy of the
+        parameters and every step's observation, pre and action.  All policy calls of one tape must have one shape; they may be
+        mixed with step_actions* and step_feedback_gain calls."""
+        from ..control.policy import PolicyRollout
+        T = int(nsteps)
+        mem, spec, keep, _, noise, std, (o, u, a) = self._policy_call(policy, T, None, noise, std, on_device)
+        hist = np.empty((T, 3, self.num_envs)) if history else None
+        mem.enter()
+        self._h.tape_step_policy(spec, mem.addr(noise), mem.addr(std), mem.kind, T, mem.addr(o), mem.addr(u), mem.addr(a), hist)
+        mem.leave(self._h)
+        self._tape_policy = (2 * policy.obs_modes, policy.n_params, policy.per_env)
+        ke, pe, per = (None, None, None) if hist is None else (hist[:, 0], hist[:, 1], hist[:, 2])
+        return PolicyRollout(o, u, a, ke, pe, per)
+
+    def backward_policy(self, d_KE=None, d_PE=None, d_PE_reward=None, d_x=None, d_v=None, d_actions=None, d_obs=None,
+                        d_KL=None, d_moments=None):
+        """`backward` on a tape with steps of `tape_step_policy` (pic_tape_backward_policy): the cotangents of `backward`, plus
+        d_actions [T, num_envs, 2M] and d_obs [T, num_envs, 2 M_o], direct cotangents on the policy steps' actions and
+        observations (each None = 0).  Returns a dict: "params" ([P], or [num_envs, P] with per_env: the gradient with respect to
+        the packed parameters, summed over the tape's policy steps), "pre", "actions" [T, num_envs, 2M] and "obs"
+        [T, num_envs, 2 M_o] (u-bar_t, a-bar_t = B^T e-bar_t + d_actions_t and o-bar_t; zero on steps without a policy), "x0",
+        "v0" [num_envs, N].  NumPy arrays, or float64 CUDA tensors if any cotangent is one."""
+        if getattr(self, "_tape_policy", None) is None:
+            raise _abi.PicError("backward_policy: the tape holds no steps of tape_step_policy")
+        nO, P, per_env = self._tape_policy
+        T, E, N, n = self._h.tape_stats()["steps"], self.num_envs, self.N, 2 * self.max_mode
+        mem = Mem.of(self, d_KE, d_PE, d_PE_reward, d_x, d_v, d_actions, d_obs, d_KL, d_moments)
+        keep = self._set_kl_cot(d_KL, T, mem), self._set_moments_cot(d_moments, T, mem)
+        hist = mem.stack_energies(T, E, d_KE, d_PE, d_PE_reward)
+        cx, cv = mem.f64(d_x, (E, N)), mem.f64(d_v, (E, N))
+        ca, co = mem.f64(d_actions, (T, E, n)), mem.f64(d_obs, (T, E, nO))
+        res = {"params": mem.out((E, P) if per_env else (P,)), "pre": mem.out((T, E, n)), "obs": mem.out((T, E, nO)),
+               "actions": mem.out((T, E, n)), "x0": mem.out((E, N)), "v0": mem.out((E, N))}
+        addr = mem.addr
+        mem.enter()
+        self._h.tape_backward_policy(mem.kind, addr(hist), addr(cx), addr(cv), addr(ca), addr(co), addr(res["params"]),
+                                     addr(res["pre"]), addr(res["obs"]), addr(res["actions"]), addr(res["x0"]), addr(res["v0"]))
+        if mem.on_device:
+            self._check_replay("backward_policy", "gradient")
+        del keep                                     # (the backward has been waited for)
+        return res
+
+    def tape_policy_grad(self, on_device: bool = False):
+        """The parameter gradient a finished reverse pass over the tape's policy steps accumulated (pic_tape_policy_grad): after
+        `backward`, `backward_policy` or a `TapeWalk` that reached the tape's start."""
+        if getattr(self, "_tape_policy", None) is None:
+            raise _abi.PicError("tape_policy_grad: the tape holds no steps of tape_step_policy")
+        _, P, per_env = self._tape_policy
+        mem = Mem.of(self, force_device=on_device)
+        out = mem.empty((self.num_envs, P) if per_env else (P,))
+        mem.enter()
+        self._h.tape_policy_grad(mem.kind, mem.addr(out))
+        mem.leave(self._h)
+        return out
 
     def modes(self, max_mode: int):
         """Complex [num_envs, max_mode]: rows 1..max_mode of compute_E_k_spectrum for the current E_mesh."""
@@ -635,6 +712,7 @@ class BatchedPIC:
         tape stays open without one."""
         self._h.tape_start(max_steps, checkpoint_every, budget_bytes)
         self._tape_kl = self._tape_moments = self._tape_mom_trace = False
+        self._tape_policy = None
         if kl is not None:
             kl = dict(kl)
             feq, vmin, vmax = kl.pop("feq"), float(kl.pop("vmin", -25.0)), float(kl.pop("vmax", 25.0))
@@ -650,6 +728,7 @@ class BatchedPIC:
     def stop_tape(self):
         self._h.tape_stop()
         self._tape_kl = self._tape_moments = self._tape_mom_trace = False
+        self._tape_policy = None
 
     def tape_moments(self, on_device: bool = False):
         """The moments after every step taped so far, [T, num_envs, 3, N_mesh] (a tape opened with moments=True): each row is

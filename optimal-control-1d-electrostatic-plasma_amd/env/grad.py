@@ -12,6 +12,9 @@ the gradient from the device's adjoint (pic_tape_backward) and for
     KE, PE, PE_reward, actions, obs = rollout_policy(env, policy, T)   # policy: any torch callable, modes -> actions
     (PE_reward.sum() + lam * (actions ** 2).sum() * L / 4).backward()   # fills the policy's .grad through the closed loop (7e)
 
+    KE, PE, PE_reward, actions, pre, obs = rollout_mlp(env, policy, params, T)   # policy: an MLPPolicy, params: its packed vector
+    (PE_reward.sum() + lam * (actions ** 2).sum() * L / 4).backward()   # fills params.grad: one device call each way (7p)
+
 rollout_policy(..., observe="moments") hands the policy the fluid moments on the mesh, [num_envs, 3, N_mesh], instead of the modes
 (DESIGN.md 7k); the backward sets the policy's cotangent on them through pic_tape_moments_cot.
 
@@ -298,6 +301,63 @@ def rollout_policy(env, policy, T, observe="modes", obs_modes=None, checkpoint_e
         obs.append(o)
     res = (torch.stack(ke), torch.stack(pe), torch.stack(per), torch.stack(acts), obs)
     return res + ((torch.stack(kls),) if kl is not None else ())
+
+
+class _RolloutMLP(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, params, std, env, policy, T, noise, checkpoint_every, kl=None):
+        ctx.set_materialize_grads(False)
+        serial = _start(env, T, checkpoint_every, kl)
+        r = env.tape_step_policy(policy.with_params(params.detach().contiguous()), T, noise=noise,
+                                 std=None if std is None else std.detach(), history=True, on_device=True)
+        ctx.env, ctx.serial, ctx.steps, ctx.kl, ctx.squash = env, serial, T, kl is not None, policy.squash
+        ctx.noise, ctx.has_std = noise, std is not None
+        dev = params.device
+        energies = tuple(torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64, device=dev) for a in (r.KE, r.PE, r.PE_reward))
+        return energies + (r.actions, r.pre, r.obs) + ((env.tape_kl(on_device=True),) if kl is not None else ())
+
+    @staticmethod
+    def backward(ctx, g_ke, g_pe, g_per, g_act, g_pre, g_obs, g_kl=None):
+        env = ctx.env
+        _check_live(env, ctx.serial, ctx.steps, "backward")
+        if g_pre is not None:
+            if ctx.squash:
+                raise NotImplementedError("rollout_mlp: a cotangent on `pre` of a squashed policy is not built (use `actions`)")
+            g_act = g_pre if g_act is None else g_act + g_pre      # (a = u without squash)
+        dev = f"cuda:{env.device}"
+        on = lambda g: None if g is None else g.to(dev)  # noqa: E731
+        out = env.backward_policy(d_KE=on(g_ke), d_PE=on(g_pe), d_PE_reward=on(g_per), d_actions=on(g_act), d_obs=on(g_obs),
+                                  d_KL=on(g_kl) if ctx.kl else None)
+        g_params = torch.as_tensor(out["params"], dtype=torch.float64, device=dev)
+        g_std = None
+        if ctx.has_std and ctx.noise is not None:
+            eps = torch.as_tensor(ctx.noise, dtype=torch.float64, device=dev).reshape(ctx.steps, env.num_envs, -1)
+            g_std = (torch.as_tensor(out["pre"], dtype=torch.float64, device=dev) * eps).sum((0, 1))
+        return g_params, g_std, None, None, None, None, None, None
+
+
+def rollout_mlp(env, policy, params, T, noise=None, std=None, checkpoint_every=0, kl=None):
+    """T steps of `env` (a BatchedPIC with an actuator, on the GPU) in closed loop under the MLP `policy`
+    (control.policy.MLPPolicy: its shape, scales and squash) with the packed parameters `params`, a float64 CUDA tensor [P] or
+    [num_envs, P] (one vector per environment): ONE autograd function for the whole rollout.  The forward is
+    start_tape plus one tape_step_policy, the backward one backward_policy: no step returns to Python in either direction.
+    noise: eps [T, num_envs, 2M] or None; std: a float64 tensor [2M] or None.  Returns KE, PE, PE_reward [T, num_envs], actions
+    and pre [T, num_envs, 2M], obs [T, num_envs, 2 M_o] (obs[t] is what step t's policy read), and with kl=... the smoothed KL
+    after every step; all differentiable with respect to `params` and `std`.  `MLPPolicy.unpack_grad` gives params.grad the
+    layers' shapes."""
+    if env.max_mode == 0:
+        raise PicError("rollout_mlp: the environment has no actuator (set_actuator)")
+    T = int(T)
+    if T < 1:
+        raise ValueError("need T >= 1")
+    if not (torch.is_tensor(params) and params.is_cuda and params.dtype == torch.float64 and params.dim() in (1, 2)):
+        raise ValueError("params must be a float64 CUDA tensor [P] or [num_envs, P]")
+    if std is not None and not torch.is_tensor(std):
+        raise ValueError("std must be a tensor or None")
+    from ..control.policy import MLPPolicy
+    shape = MLPPolicy(policy.widths, policy.activation, params.detach(), policy.obs_modes, policy.squash, policy.action_scale,
+                      policy.obs_scale, per_env=params.dim() == 2)
+    return _RolloutMLP.apply(params, std, env, shape, T, noise, int(checkpoint_every), kl)
 
 
 def _policy_jvp(fn, params, o, d_params, d_o):
