@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <string>
 
 #include "picstep.h"
@@ -110,6 +111,11 @@ static inline int plan_launch(const pic_config& c, int ncu, LaunchPlan* p, std::
   while ((1ll << lg) < cfg->N + 1) ++lg;
   p->fg = 62 - lg > 50 ? 50 : 62 - lg;
   p->magic = std::ldexp(1.5, 52 - p->fg);
+  {  // to_fixed (pic_device.h) subtracts the high words alone: the low word of magic's bit pattern is zero for every fg
+    std::uint64_t bits;
+    std::memcpy(&bits, &p->magic, sizeof(bits));
+    if ((bits & 0xffffffffull) != 0) return plan_fail(err, "pic_create: the fixed-point magic has a non-zero low word");
+  }
 
   // workgroups per environment: enough in total to fill 256 CUs several times, at least one
   // BLOCK*VEC tile each

@@ -279,19 +279,23 @@ __device__ __forceinline__ T wrap_periodic(T q, T L, unsigned& bad) {
   // take the chain, as does the whole wave of such a lane -- a particle within one sub-stage's drift of a boundary.
   // (the ballot of the lanes OUTSIDE the open box is compared with zero in scalar registers: __all() turns the predicate into a
   // lane value and compares that again, two VALU more per wrap)
-  if (__builtin_amdgcn_ballot_w64(!(q > T(0) && q < L)) == 0) return q;
-  // the three near ranges as selects (a particle moves a small fraction of L per sub-stage)
-  T up = q + L;                       // q in [-L, 0]
-  up = (up >= L) ? T(0) : up;         // tiny negative q: q + L rounds to L, the second mod gives 0
-  T r = (q <= T(0)) ? up : q;         // q = -0.0 (or +0.0): L -> +0.0, as np.mod gives (not -0.0)
-  r = (q >= L) ? q - L : r;           // q in [L, 2L): exact (Sterbenz)
-  // For q in [-L, 2L) r now lies in [0, L).  One range test therefore catches both a position further away
-  // (fmod path) and a NaN / inf one (counted, parked on node 0, never used as an index).
-  if (__builtin_expect(!(r >= T(0) && r < L), 0)) {
-    r = wrap_periodic_far(q, L);
-    if (!(r >= T(0) && r < L)) {
-      bad += 1u;
-      r = T(0);
+  // (the result IS q's register on that path, overwritten on the other: returning from two places left a 64-bit copy per wrap
+  // where they merge)
+  T r = q;
+  if (__builtin_amdgcn_ballot_w64(!(q > T(0) && q < L)) != 0) {
+    // the three near ranges as selects (a particle moves a small fraction of L per sub-stage)
+    T up = q + L;                       // q in [-L, 0]
+    up = (up >= L) ? T(0) : up;         // tiny negative q: q + L rounds to L, the second mod gives 0
+    r = (q <= T(0)) ? up : q;           // q = -0.0 (or +0.0): L -> +0.0, as np.mod gives (not -0.0)
+    r = (q >= L) ? q - L : r;           // q in [L, 2L): exact (Sterbenz)
+    // For q in [-L, 2L) r now lies in [0, L).  One range test therefore catches both a position further away
+    // (fmod path) and a NaN / inf one (counted, parked on node 0, never used as an index).
+    if (__builtin_expect(!(r >= T(0) && r < L), 0)) {
+      r = wrap_periodic_far(q, L);
+      if (!(r >= T(0) && r < L)) {
+        bad += 1u;
+        r = T(0);
+      }
     }
   }
   return r;
@@ -312,7 +316,9 @@ __device__ __forceinline__ T div_dx(T a, T dx, T rdx) {
 
 // The part of `locate` behind the wrap: cell and weights of a position already in [0, L).  Sweep B2 uses it on the positions
 // sweep D2 stored (wrapped there): the same xw, hence the same cell and weights as the deposit D would have made.
-template <typename P, int SHAPE>
+// FOLD = false: the caller's mesh and field tile have slots Ng and Ng + 1 that stand for nodes 0 and 1 (the sweeps, CIC), so an
+// index the wrap already bounds needs no fold.
+template <typename P, int SHAPE, bool FOLD = true>
 __device__ __forceinline__ void locate_in_box(typename P::X xw, const Consts<P>& k, int& j, typename P::W (&w)[3], unsigned& frac) {
   using T = typename P::W;
   static_assert(!P::kFixed, "fixed-point positions need no wrap: locate() is the whole of it");
@@ -321,7 +327,7 @@ __device__ __forceinline__ void locate_in_box(typename P::X xw, const Consts<P>&
   j = (int)jf;
   // j == Ng happens when xw/dx rounds up to Ng (undefined in the reference: bincount grows a bin and
   // solve.py:32 raises); it is folded to node 0 with the weights of the unfolded index.
-  if ((unsigned)j >= (unsigned)k.Ng) j = 0;
+  if (FOLD && (unsigned)j >= (unsigned)k.Ng) j = 0;
   if (SHAPE == PIC_CIC) {
     w[0] = div_dx((jf + T(1)) * k.dx - xw, k.dx, k.rdx);
     w[1] = div_dx(xw - jf * k.dx, k.dx, k.rdx);
@@ -341,7 +347,7 @@ __device__ __forceinline__ void locate_in_box(typename P::X xw, const Consts<P>&
 //   TSC (interpolate.py:24-34): d = (xw - jm dx)/dx; wl = .5(1.5-d)^2; wm = .75-(d-1)^2; wr = .5(d-.5)^2
 // xw: the wrapped position (what sweep D stores).  frac: PosU32 only, the position inside the cell in
 // units of 2^-32 cell (the right CIC weight, exactly).
-template <typename P, int SHAPE>
+template <typename P, int SHAPE, bool FOLD = true>
 __device__ __forceinline__ void locate(typename P::X q, const Consts<P>& k, typename P::X& xw, int& j,
                                        typename P::W (&w)[3], unsigned& frac, unsigned& bad) {
   using T = typename P::W;
@@ -362,7 +368,7 @@ __device__ __forceinline__ void locate(typename P::X q, const Consts<P>& k, type
     }
   } else {
     xw = wrap_periodic(q, k.L, bad);
-    locate_in_box<P, SHAPE>(xw, k, j, w, frac);
+    locate_in_box<P, SHAPE, FOLD>(xw, k, j, w, frac);
   }
 }
 
@@ -427,9 +433,17 @@ struct fix_t { unsigned long long v; };
 constexpr int FX_FRAC = 24;
 constexpr int FX_LOW = 44;
 
+typedef int pic_v2i __attribute__((ext_vector_type(2)));
+
 __device__ __forceinline__ acc_t to_fixed(double w, double magic) {
-  // w + magic has ulp 2^-fg, so its mantissa differs from magic's by round-to-nearest-even(w 2^fg)
-  return __double_as_longlong(w + magic) - __double_as_longlong(magic);
+  // w + magic has ulp 2^-fg, so its mantissa differs from magic's by round-to-nearest-even(w 2^fg).  magic = 1.5 2^(52 - fg) has
+  // a zero low word in its bit pattern for every fg (its mantissa is 0x8000000000000; host_plan.h asserts it), so the 64-bit
+  // difference of the two patterns is (high word - magic's high word, low word): no borrow can leave the low word, for a negative
+  // difference either.  One 32-bit subtract of a value that sits in a scalar register already instead of a carry chain; the words
+  // are kept as a two-lane vector so that the optimiser does not put the 64-bit subtraction back together.
+  pic_v2i s = __builtin_bit_cast(pic_v2i, w + magic);
+  s.y -= __builtin_bit_cast(pic_v2i, magic).y;
+  return __builtin_bit_cast(acc_t, s);
 }
 
 template <typename A, typename P, int SHAPE>

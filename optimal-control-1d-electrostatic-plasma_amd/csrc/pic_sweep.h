@@ -50,8 +50,18 @@ __device__ __forceinline__ void prologue_field(const acc_t* __restrict__ acc_in,
   PIC_STAMP(5);
 }
 
+// Does a `locate` of the sweeps fold the index Ng to node 0?  Behind wrap_periodic a position lies in [0, L) (or is parked at 0), so
+// j = floor(xw / dx) lies in [0, Ng], and j == Ng happens where the quotient rounds up (L = 50: Ng = 150 and 300 at
+// xw = nextafter(L, 0)).  A sweep's LDS meshes and field tiles have Ng + 2 slots; with CIC the prologue fills Es[Ng] = E[0] and
+// Es[Ng + 1] = E[1], so a gather at j = Ng reads what the folded one reads, and a deposit at j = Ng lands in slots Ng and Ng + 1,
+// which mesh_node_sum<.., WIDE> adds to nodes 0 and 1: the same integer sums, without a compare and a select per locate.  TSC
+// uses both ghost slots for its own offset and the packed accumulator has one word per cell: they fold.  So does everything that
+// does not come from a wrap (sweep B2's locate_in_box on stored positions) and every kernel outside this file.
+template <typename A, int SHAPE>
+constexpr bool kFoldIndex = !(SHAPE == PIC_CIC && !std::is_same<A, fix_t>::value);
+
 // The force evaluation of one sub-stage: gather at q from the field tile Es, kick p with d, drift q with c.
-template <typename P, int SHAPE>
+template <typename P, int SHAPE, bool FOLD>
 __device__ __forceinline__ void substage(typename P::X& q, typename P::V& p, const typename P::W* __restrict__ Es,
                                          typename P::W d, typename P::W c, const Consts<P>& k, unsigned& bad) {
   using T = typename P::W;
@@ -59,7 +69,7 @@ __device__ __forceinline__ void substage(typename P::X& q, typename P::V& p, con
   typename P::X xw;
   int j;
   unsigned frac;
-  locate<P, SHAPE>(q, k, xw, j, w, frac, bad);
+  locate<P, SHAPE, FOLD>(q, k, xw, j, w, frac, bad);            // (behind a wrap: 0 <= j <= Ng, kFoldIndex)
   const T E = gather_field<T, SHAPE>(Es, j, w);                 // util.py:105 / pic.py:120
   p = p + (typename P::V)((d * (-E)) * k.dt);                   // integration.py:32, pic.py:127
   q = drift<P>(q, p, c, k, bad);                                // integration.py:42
@@ -78,6 +88,7 @@ __device__ __forceinline__ void push_one(typename P::X& xq, typename P::V& vp, c
   constexpr bool kRC = (STAGE == ST_D_RC || STAGE == ST_D2_RC);
   constexpr bool kD = (STAGE == ST_D || STAGE == ST_D_RC);
   constexpr bool kD2 = (STAGE == ST_D2 || STAGE == ST_D2_RC);
+  constexpr bool kFold = kFoldIndex<A, SHAPE>;           // every locate<.., kFold> below comes behind a wrap: 0 <= j <= Ng
   using T = typename P::W;
   T w[3];
   typename P::X xw;
@@ -87,27 +98,27 @@ __device__ __forceinline__ void push_one(typename P::X& xq, typename P::V& vp, c
   typename P::V p = vp;
   if (kRC) {
     unsigned again = 0u;
-    substage<P, SHAPE>(q, p, Es2, k.d_prev, k.c_prev, k, again);
+    substage<P, SHAPE, kFold>(q, p, Es2, k.d_prev, k.c_prev, k, again);
   }
   if (STAGE == ST_B2) {
     // The post-step deposit of the PREVIOUS step (pic.py:145): q is the x' that step's sweep D2 wrapped and stored, so cell and
     // weights are the ones its own deposit would have had (locate = wrap + locate_in_box, and the wrap of a wrapped position
     // is the position).  A value outside [0, L) cannot come from D2; should memory hold one, its index folds to node 0 below.
     if constexpr (P::kFixed) locate<P, SHAPE>(q, k, xw, j, w, frac, bad);
-    else locate_in_box<P, SHAPE>(q, k, j, w, frac);
+    else locate_in_box<P, SHAPE>(q, k, j, w, frac);               // (straight from memory, no wrap in front: folds)
     deposit<A, P, SHAPE>(acc2, j, w, frac, k.magic);
   }
   if (STAGE == ST_A) {
     q = drift<P>(q, p, k.c_cur, k, bad);                          // integration.py:42, c1
   } else if (STAGE == ST_B || STAGE == ST_B2 || kC || kD || kD2) {
     if (STAGE == ST_B || STAGE == ST_B2) q = drift<P>(q, p, k.c_prev, k, bad);      // q1 again (it is never stored)
-    substage<P, SHAPE>(q, p, Es, k.d_cur, k.c_cur, k, bad);
+    substage<P, SHAPE, kFold>(q, p, Es, k.d_cur, k.c_cur, k, bad);
   }
   if (kD2) {                                           // the wrap alone: the deposit of x' is the next sweep B2's
     if constexpr (P::kFixed) xw = q;
     else xw = wrap_periodic(q, k.L, bad);
   } else {
-    locate<P, SHAPE>(q, k, xw, j, w, frac, bad);
+    locate<P, SHAPE, kFold>(q, k, xw, j, w, frac, bad);
     deposit<A, P, SHAPE>(acc, j, w, frac, k.magic);
   }
   if (kD || kD2 || STAGE == ST_REFRESH) {
@@ -115,7 +126,7 @@ __device__ __forceinline__ void push_one(typename P::X& xq, typename P::V& vp, c
     ke += (double)p * (double)p;
     const typename P::X qn = drift<P>(q, p, k.c_next, k, bad);    // next step's q1 (integration.py:42, c1)
     typename P::X xn;
-    locate<P, SHAPE>(qn, k, xn, j, w, frac, bad);
+    locate<P, SHAPE, kFold>(qn, k, xn, j, w, frac, bad);
     deposit<A, P, SHAPE>(acc2, j, w, frac, k.magic);
   }
   xq = q;
@@ -137,7 +148,8 @@ __device__ __forceinline__ void push_scheme(typename P::X& xq, typename P::V& vp
   unsigned frac;
   typename P::X q = xq;
   V p = vp;
-  locate<P, SHAPE>(q, k, xw, j, w, frac, bad);
+  constexpr bool kFold = kFoldIndex<A, SHAPE>;                  // (both locates come behind a wrap: 0 <= j <= Ng)
+  locate<P, SHAPE, kFold>(q, k, xw, j, w, frac, bad);
   const T E = gather_field<T, SHAPE>(Es, j, w);                 // util.py:105 / pic.py:120
   if (STAGE == ST_FE) {
     // integration.py:10, eta + dt grad(eta): the drift takes the velocity the step starts with.  (grad_func has wrapped eta's
@@ -154,7 +166,7 @@ __device__ __forceinline__ void push_scheme(typename P::X& xq, typename P::V& vp
     if (STAGE != ST_VK) q = drift<P>(q, p, k.c_cur, k, bad);     // integration.py:42
   }
   if (STAGE != ST_VK) {
-    locate<P, SHAPE>(q, k, xw, j, w, frac, bad);
+    locate<P, SHAPE, kFold>(q, k, xw, j, w, frac, bad);
     deposit<A, P, SHAPE>(acc, j, w, frac, k.magic);
     if (STAGE != ST_VM) {                                        // (VM stores the drifted q, as sweep C does: the next sweep wraps it)
       q = xw;
@@ -166,8 +178,9 @@ __device__ __forceinline__ void push_scheme(typename P::X& xq, typename P::V& vp
 }
 
 // Total of one mesh node over the R LDS replicas of a workgroup, periodic ghost slots folded in, as an integer
-// in units of 2^-fg (the unit of the global accumulators).
-template <typename A, int SHAPE>
+// in units of 2^-fg (the unit of the global accumulators).  WIDE (CIC): slot Ng + 1 holds deposits too, those of node 1 made at
+// the unfolded index Ng (kFoldIndex: the sweeps; the resident kernel folds the index and leaves the slot alone).
+template <typename A, int SHAPE, bool WIDE = false>
 __device__ __forceinline__ acc_t mesh_node_sum(const A* __restrict__ acc_all, int R, int stride, int Ng, int fg, int c) {
   constexpr int OFF = (SHAPE == PIC_TSC) ? 1 : 0;
   if constexpr (std::is_same<A, fix_t>::value) {
@@ -188,6 +201,7 @@ __device__ __forceinline__ acc_t mesh_node_sum(const A* __restrict__ acc_all, in
       A t = ar[c + OFF];
       if (SHAPE == PIC_CIC) {
         if (c == 0) t += ar[Ng];
+        if (WIDE && c == 1) t += ar[Ng + 1];
       } else {
         if (c == 0) t += ar[Ng + 1];
         if (c == Ng - 1) t += ar[0];
@@ -207,7 +221,7 @@ __device__ __forceinline__ void flush_mesh(const A* __restrict__ acc_all, int R,
                                            acc_t* __restrict__ row) {
   unsigned long long* out = reinterpret_cast<unsigned long long*>(row);
   for (int c = threadIdx.x; c < Ng; c += BLOCK) {
-    const acc_t q = mesh_node_sum<A, SHAPE>(acc_all, R, stride, Ng, fg, c);
+    const acc_t q = mesh_node_sum<A, SHAPE, !kFoldIndex<A, SHAPE>>(acc_all, R, stride, Ng, fg, c);
     if (q) atomicAdd(out + c, (unsigned long long)q);
   }
 }
@@ -357,6 +371,75 @@ __global__ __launch_bounds__(BLOCK) void sweep_kernel(typename P::X* __restrict_
   unsigned bad = 0u;
   [[maybe_unused]] int tile = 0;
   const StreamOut xout(xe + begin), vout(ve + begin);
+  if constexpr (kAhead) {
+    // The whole tiles of a chunk, nfull of them, are the same for every lane of the workgroup: the tiles whose SUCCESSOR is a whole
+    // tile too run here, on a trip count and a tile base that are wave-uniform -- no per-lane index, end test or clamped address,
+    // and the next tile's loads leave unconditionally from a pointer that advances by a constant.  Two tiles per trip, on two
+    // pairs of registers that take turns, so that no tile is copied from "next" to "current".  The last whole tile, the partial
+    // one and the lane tail stay with the per-lane loop below, which alone may meet a tile that some lanes do not have (and
+    // alone prefetches from a clamped address: nothing is read here that is not pushed).
+    const int nfull = (int)((end - begin) / step);
+    if (nfull >= 2) {
+      // (addresses as a wave-uniform base, advanced in scalar registers, plus the lane's constant 32-bit offset: the form a
+      // load takes without any address arithmetic on the VALU.  The empty asm pins the base to scalar registers at each load;
+      // left to itself the optimiser re-associates base and offset into per-lane 64-bit pointers again)
+      // (global address space, spelled out: behind the asm the compiler cannot infer it and would emit flat loads)
+      using GlobalBytes = const __attribute__((address_space(1))) char*;
+      GlobalBytes xp = (GlobalBytes) reinterpret_cast<const char*>(xe + begin);
+      GlobalBytes vp = (GlobalBytes) reinterpret_cast<const char*>(ve + begin);
+      unsigned lane_off = (unsigned)tid * (unsigned)sizeof(XV);
+      asm("" : "+v"(lane_off));
+      constexpr size_t kTileBytes = (size_t)BLOCK * sizeof(XV);
+      static_assert(sizeof(XV) == sizeof(VV), "one lane offset serves both streams");
+      auto tile_x = [&](GlobalBytes base) __attribute__((always_inline)) {
+        asm("" : "+s"(base));
+        return *reinterpret_cast<const __attribute__((address_space(1))) XV*>(base + lane_off);
+      };
+      auto tile_v = [&](GlobalBytes base) __attribute__((always_inline)) {
+        asm("" : "+s"(base));
+        return *reinterpret_cast<const __attribute__((address_space(1))) VV*>(base + lane_off);
+      };
+      auto push_tile = [&](XV& xt, VV& vt) __attribute__((always_inline)) {
+        typename P::X* xs = reinterpret_cast<typename P::X*>(&xt);
+        typename P::V* vs = reinterpret_cast<typename P::V*>(&vt);
+#pragma unroll
+        for (int c = 0; c < VEC; ++c) {
+          typename P::V pv = kReadV ? vs[c] : typename P::V(0);
+          push_one<P, A, SHAPE, STAGE>(xs[c], pv, Es, Es2, acc, acc2, k, ke, bad);
+        }
+      };
+      XV xw;
+      VV vw = {};
+      int left = nfull - 1;                                  // tiles with a whole successor
+      for (; left >= 2; left -= 2) {
+        PIC_STAMP_LOADS(8 + 2 * tile);
+        xw = tile_x(xp + kTileBytes);
+        if (kReadV) vw = tile_v(vp + kTileBytes);
+        push_tile(xv, vv);
+        PIC_STAMP(9 + 2 * tile);
+        ++tile;
+        xp += 2 * kTileBytes;
+        vp += 2 * kTileBytes;
+        PIC_STAMP_LOADS(8 + 2 * tile);
+        xv = tile_x(xp);
+        if (kReadV) vv = tile_v(vp);
+        push_tile(xw, vw);
+        PIC_STAMP(9 + 2 * tile);
+        ++tile;
+      }
+      if (left) {                                            // an odd one: once per workgroup, with the copy
+        PIC_STAMP_LOADS(8 + 2 * tile);
+        xw = tile_x(xp + kTileBytes);
+        if (kReadV) vw = tile_v(vp + kTileBytes);
+        push_tile(xv, vv);
+        PIC_STAMP(9 + 2 * tile);
+        ++tile;
+        xv = xw;
+        vv = vw;
+      }
+      i += (long long)(nfull - 1) * step;
+    }
+  }
   while (i + VEC <= end) {
     PIC_STAMP_LOADS(8 + 2 * tile);
     // A sweep that stores nothing requests its NEXT tile here, into a second pair of registers, before it pushes this one: the
