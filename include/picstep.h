@@ -801,7 +801,8 @@ int pic_step_policy(pic_handle* h, const pic_policy* p, const double* noise, con
  * cot_modes on the field such a step read is its cot_obs and needs obs_modes == Mo, else PIC_EINVAL); pic_tape_policy_grad reads
  * the accumulated g_params after a backward or a pic_tape_walk_end (PIC_ESTATE before one, or once steps were appended).
  * pic_tape_kl_cot and pic_tape_moments_cot work unchanged on such a tape.  pic_tape_tangent* and pic_tape_tangent_walk_begin
- * return PIC_EINVAL on it: policy steps are not built in forward mode, and are never treated as open loop. */
+ * return PIC_EINVAL on it: they take no parameter direction, and policy steps are never treated as open loop
+ * (pic_tape_tangent_policy below is the forward-mode entry for such a tape). */
 int pic_policy_vjp(pic_handle* h, const pic_policy* p, const double* obs, const double* pre, const double* cot_actions, int mem_kind,
                    double* g_params, double* g_obs, double* g_pre);
 int pic_tape_step_policy(pic_handle* h, const pic_policy* p, const double* noise, const double* std, int mem_kind, int nsteps,
@@ -810,6 +811,52 @@ int pic_tape_backward_policy(pic_handle* h, const double* cot_hist, const void* 
                              const double* cot_obs, int mem_kind, double* g_params, double* g_pre, double* g_obs, double* g_actions,
                              void* g_x0, void* g_v0);
 int pic_tape_policy_grad(pic_handle* h, int mem_kind, double* g_params);
+
+/* ---- Forward mode through the policy's steps (additive to ABI 5) --------------------------------------------------
+ * The Jacobian-vector product of the evaluation above, for one environment, one evaluation and one direction: from the recorded
+ * observation o, the recorded u (pre), a parameter tangent dtheta (per layer dW [out][in], then db [out]: the order of params),
+ * an observation tangent do and an additive injection du_inj in front of the squash (the caller's d_std * eps: the library has
+ * no random numbers and never sees eps).
+ *   1. h_0 .. h_{L-1} are recomputed from o exactly as the forward computes them (the same bits).
+ *   2. dh_0 = do, or do * obs_scale element by element.
+ *   3. layer l, row i:  dy_i = db_i;  then, for k ascending, dy_i = dy_i + dW[i][k] * h_l[k];  then, for k ascending,
+ *      dy_i = dy_i + W[i][k] * dh_l[k] -- every product rounded before its sum, no fused multiply-add.  With dtheta NULL
+ *      dy_i starts at +0.0 and the first loop is left out (the same bits as a dtheta of zeros).
+ *      Behind every layer but the last: dh_{l+1}[i] = dy_i * d_i, with d = 1.0 - h*h (tanh; h = h_{l+1}[i]) or h > 0 ? 1.0 : 0.0
+ *      (relu): pic_policy_vjp's factors.
+ *   4. dz = the last layer's dy;  du = dz + du_inj (du = dz without an injection).
+ *   5. squash 0: da = du.  squash 1: t = tanh(u), da = (action_scale * (1.0 - t*t)) * du: pic_policy_vjp's operands.
+ *      On a tape a step's d_actions is then added: da = da + d_actions.
+ * Nothing is summed across lanes, workgroups or launches: K directions in one call give the bits of K calls with one each, and
+ * the result does not depend on blocks_per_env, the checkpoint interval, the schedule or the batch.
+ *
+ * pic_policy_jvp: the JVP once for every environment and 1 <= K <= 8 directions, on obs [num_envs][2 Mo], pre [num_envs][2M]
+ * (NULL allowed only with squash == 0), d_params [K][P] or [K][num_envs][P] (per_env), d_obs [K][num_envs][2 Mo], d_pre
+ * [K][num_envs][2M] (each NULL = 0); d_pre_out (du) and d_actions_out (da) [K][num_envs][2M], each may be NULL.  The state is not
+ * touched (allowed while a tape is open, needs no pic_reset).  Checked like pic_policy_vjp: PIC_EINVAL with the reason, nothing
+ * enqueued (K outside 1..8 too).  With PIC_HOST the call waits; with PIC_DEVICE it is asynchronous.
+ *
+ * pic_tape_tangent_policy: pic_tape_tangent_feedback on a tape that holds steps of pic_tape_step_policy.  d_params as above is
+ * the tangent of the parameters of every policy call on the tape; d_pre and d_actions [K][T][num_envs][2M] are per-step
+ * injections (du_inj and the addend of item 5; rows of d_pre on other steps are ignored); d_x0 / d_v0 [K][num_envs][N]; each
+ * NULL = 0.  The walk observes the policy's M_o modes: do_s = J dE_s of the field step s reads (dE_0 = K drho(x_0; dx_0)), the
+ * kernel above at the taped o_s, u_s and the parameter copy of the step's call gives da_s, and de_s = B da_s drives the tangent
+ * of the step as on any other.  On a mixed tape a pic_step_actions* step takes its d_actions row as its whole da_s and a gain-law
+ * step da_s = G_s dm_s + d_actions_s with its taped gain (dG = 0).  Outputs, each optional: d_hist [K][T][3][num_envs], d_obs
+ * [K][T][num_envs][2 Mo] (do_s), d_pre_out [K][T][num_envs][2M] (du_s, zero on other steps), d_actions_out
+ * [K][T][num_envs][2M] (the da_s applied), d_x / d_v [K][num_envs][N] (final), d_E_mesh [K][T][num_envs][N_mesh].
+ * Every step costs pic_tape_tangent's kernels plus the modes' one, and one more on a policy step.  The working rows, each part
+ * rounded up to 256 bytes,  8 K (P or num_envs P) + 2 * 8 K (2M num_envs)  bytes, next to pic_tape_tangent_feedback's (with
+ * M_o observed modes), count in pic_tape_info.bytes and against budget_bytes: PIC_ENOMEM before anything runs.  PIC_ESTATE without
+ * a tape; PIC_EINVAL for K outside 1..8, a bad mem_kind or a tape without policy steps.  The call abandons a live reverse or
+ * tangent walk; a replay that differs from the taped forward is reported as pic_tape_tangent reports it.  pic_tape_tangent*,
+ * pic_tape_tangent_walk_begin and pic_tape_tangent_feedback keep refusing such a tape: they take no parameter direction.  A
+ * tangent of the gain, d_ext, and the per-step KL's and moments' tangents are not part of this entry. */
+int pic_policy_jvp(pic_handle* h, const pic_policy* p, const double* obs, const double* pre, int K, const double* d_params,
+                   const double* d_obs, const double* d_pre, int mem_kind, double* d_pre_out, double* d_actions_out);
+int pic_tape_tangent_policy(pic_handle* h, int K, const double* d_params, const double* d_pre, const double* d_actions,
+                            const void* d_x0, const void* d_v0, int mem_kind, double* d_hist, double* d_obs, double* d_pre_out,
+                            double* d_actions_out, void* d_x, void* d_v, double* d_E_mesh);
 
 int pic_sync(pic_handle* h);
 /* Number of particle positions found non-finite or out of range by the last sweeps (0 = healthy).  Counts the state's

@@ -188,6 +188,8 @@ SIGNATURES = {
     "pic_tape_step_policy": [_vp, C.POINTER(PicPolicy), _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp],
     "pic_tape_backward_policy": [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp],
     "pic_tape_policy_grad": [_vp, C.c_int, _vp],
+    "pic_policy_jvp": [_vp, C.POINTER(PicPolicy), _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp],
+    "pic_tape_tangent_policy": [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pic_sync": [_vp],
     "pic_bad_count": [_vp, _i64p],
     "pic_last_error": [_vp],
@@ -665,6 +667,18 @@ class Handle:
     def tape_policy_grad(self, kind, g_params):
         """pic_tape_policy_grad into the address g_params in `kind` memory."""
         self._chk(self.lib.pic_tape_policy_grad(self._h, int(kind), _ptr(g_params)))
+
+    # -- forward mode through the policy's steps (DESIGN.md 7q) -----------------------------------------------------------------
+    def policy_jvp(self, spec, obs, pre, K, d_params, d_obs, d_pre, kind, d_pre_out, d_actions_out):
+        """pic_policy_jvp on addresses (0 or None = NULL) in `kind` memory; spec as for policy_eval."""
+        self._chk(self.lib.pic_policy_jvp(self._h, C.byref(spec), *_ptrs(obs, pre), int(K), *_ptrs(d_params, d_obs, d_pre), int(kind),
+                                          *_ptrs(d_pre_out, d_actions_out)))
+
+    def tape_tangent_policy(self, K, d_params, d_pre, d_actions, d_x0, d_v0, kind, d_hist, d_obs, d_pre_out, d_actions_out, d_x, d_v,
+                            d_E_mesh):
+        """pic_tape_tangent_policy on addresses (0 or None = NULL) in `kind` memory."""
+        p = _ptrs(d_params, d_pre, d_actions, d_x0, d_v0, d_hist, d_obs, d_pre_out, d_actions_out, d_x, d_v, d_E_mesh)
+        self._chk(self.lib.pic_tape_tangent_policy(self._h, int(K), *p[:5], int(kind), *p[5:]))
 
     def step_observe(self, E_ext=None, actions=None, nsteps=1, particles=True, out=None):
         """One Gym-style iteration in one call with one synchronisation (pic_step_observe): nsteps steps under E_ext

@@ -116,6 +116,22 @@ class MLPPolicy:
             raise ValueError(f"a gradient of this policy ends in P = {self.n_params} entries, not {list(np.shape(g))}")
         return self.unpack(g)
 
+    def pack_tangent(self, layers):
+        """A direction in the parameters given as layers [(dW [out, in], db [out]), ...] (None for a part = zeros; e.g. the
+        tangents of `to_torch()`'s Linear modules) -> the flat float64 vector [P] that BatchedPIC.policy_jvp / tangent_policy
+        take as d_params; `unpack` of the result gives the layers again.  Stack K of them for K directions."""
+        if len(layers) != len(self.widths) - 1:
+            raise ValueError(f"a direction of this policy has {len(self.widths) - 1} layers, not {len(layers)}")
+        full = []
+        for l, (dW, db) in enumerate(layers):
+            nin, nout = self.widths[l], self.widths[l + 1]
+            dW = np.zeros((nout, nin)) if dW is None else np.asarray(_host(dW), dtype=np.float64)
+            db = np.zeros(nout) if db is None else np.asarray(_host(db), dtype=np.float64)
+            if dW.shape != (nout, nin) or db.shape != (nout,):
+                raise ValueError(f"layer {l}: dW must be [{nout}, {nin}] and db [{nout}], not {dW.shape} and {db.shape}")
+            full.append((dW, db))
+        return self.pack(full)
+
     @classmethod
     def from_layers(cls, layers, activation, obs_modes, **kwargs):
         return cls(cls.widths_of(layers), activation, cls.pack(layers), obs_modes, **kwargs)

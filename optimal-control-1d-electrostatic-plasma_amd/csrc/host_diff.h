@@ -27,7 +27,8 @@ inline int check_mem_kind(pic_handle* h, int mem_kind, const char* who) {
 inline int check_tape_open(pic_handle* h, const char* who) {
   return h->tape.on ? PIC_OK : fail(h, PIC_ESTATE, std::string(who) + ": no tape is open (pic_tape_start)");
 }
-// forward mode stops at steps under an MLP policy (pic_tape_step_policy): their actions depend on the state through the network
+// the forward-mode entries that take no parameter direction stop at steps under an MLP policy (pic_tape_step_policy): their
+// actions depend on the state through the network; pic_tape_tangent_policy (host_tangent_walk.h) is the entry for such a tape
 inline int check_no_policy_steps(pic_handle* h, const char* who) {
   return h->tape.pcalls.empty() ? PIC_OK
                              : fail(h, PIC_EINVAL, std::string(who) + ": the tape holds steps of pic_tape_step_policy (policy steps are "

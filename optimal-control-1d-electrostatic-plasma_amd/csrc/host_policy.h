@@ -1,4 +1,4 @@
-// host_policy.h -- the host side of pic_policy_eval, pic_step_policy, pic_policy_vjp and pic_tape_step_policy (7p); kernels: pic_policy.h.
+// host_policy.h -- the host side of pic_policy_eval, pic_step_policy, pic_policy_vjp and pic_tape_step_policy (7p) and pic_policy_jvp (7q); kernels: pic_policy.h.
 // Included by picstep.hip inside its extern "C" block, behind the stepping entries (step_prologue, actuator_control, advance).
 
 // P, the doubles of one parameter vector
@@ -242,6 +242,85 @@ int pic_policy_vjp(pic_handle* h, const pic_policy* p, const double* obs, const 
   if (host) {
     if (e == hipSuccess) e = device_result(h, g_obs, a.g_obs, E * nO * D);
     if (e == hipSuccess) e = device_result(h, g_pre, a.g_pre, E * nA * D);
+  }
+  const hipError_t e2 = host ? hipStreamSynchronize(h->stream) : hipSuccess;
+  if (e != hipSuccess || e2 != hipSuccess)
+    return fail(h, PIC_EHIP, std::string(who) + ": " + hipGetErrorString(e != hipSuccess ? e : e2));
+  return PIC_OK;
+}
+
+// ---- the policy's Jacobian-vector product (pic_policy_jvp; kernel: pic_policy.h) ---------------------------------
+// the parts of the handle's policy block a pic_policy_jvp call in host memory works on: the device copies of its inputs and outputs
+struct PolicyJvpCall {
+  double *params = nullptr, *scale = nullptr, *obs = nullptr, *pre = nullptr, *d_params = nullptr, *d_obs = nullptr, *d_pre = nullptr,
+         *du = nullptr, *da = nullptr;
+};
+
+static size_t policy_jvp_parts(Carver& c, PolicyJvpCall& k, const pic_handle* h, const pic_policy* p, int K, bool has_pre,
+                               bool has_dparams, bool has_dobs, bool has_dpre, bool want_du, bool want_da) {
+  const size_t E = (size_t)h->cfg.num_envs, P = policy_param_count(p), PE = (p->per_env ? E : 1) * P, kk = (size_t)K;
+  const size_t nO = 2 * (size_t)p->obs_modes, nA = 2 * (size_t)h->act_modes;
+  c.take(k.params, PE);
+  c.take(k.scale, p->obs_scale ? nO : 0);
+  c.take(k.obs, E * nO);
+  c.take(k.pre, has_pre ? E * nA : 0);
+  c.take(k.d_params, has_dparams ? kk * PE : 0);
+  c.take(k.d_obs, has_dobs ? kk * E * nO : 0);
+  c.take(k.d_pre, has_dpre ? kk * E * nA : 0);
+  c.take(k.du, want_du ? kk * E * nA : 0);
+  c.take(k.da, want_da ? kk * E * nA : 0);
+  return c.at;
+}
+
+int pic_policy_jvp(pic_handle* h, const pic_policy* p, const double* obs, const double* pre, int K, const double* d_params,
+                   const double* d_obs, const double* d_pre, int mem_kind, double* d_pre_out, double* d_actions_out) {
+  const char* who = "pic_policy_jvp";
+  if (!h) return PIC_EINVAL;
+  if (const char* bad = policy_bad_args(h, p, mem_kind)) return fail(h, PIC_EINVAL, std::string(who) + ": " + bad);
+  int rc = policy_actuator(h, p, who);
+  if (rc) return rc;
+  if (K < 1 || K > kMaxTangents) return fail(h, PIC_EINVAL, std::string(who) + ": need 1 <= K <= " + std::to_string(kMaxTangents));
+  if (!obs) return fail(h, PIC_EINVAL, std::string(who) + ": null obs");
+  if (!pre && p->squash) return fail(h, PIC_EINVAL, std::string(who) + ": pre may be NULL only with squash == 0");
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  const bool host = mem_kind == PIC_HOST;
+  const size_t E = (size_t)h->cfg.num_envs, D = sizeof(double), P = policy_param_count(p), PE = (p->per_env ? E : 1) * P;
+  const size_t nO = 2 * (size_t)p->obs_modes, nA = 2 * (size_t)h->act_modes, kk = (size_t)K;
+  PolicyJvpCall k;
+  if (host) {
+    Carver size;
+    const size_t bytes = policy_jvp_parts(size, k, h, p, K, pre != nullptr, d_params != nullptr, d_obs != nullptr, d_pre != nullptr,
+                                          d_pre_out != nullptr, d_actions_out != nullptr);
+    if (bytes > h->pol_bytes) {
+      h->pol_bytes = 0;
+      rc = regrow(h, h->pol, bytes, "pic_policy_jvp: the policy's device block does not fit on the device");
+      if (rc) return rc;
+      h->pol_bytes = bytes;
+    }
+    Carver c;
+    c.base = static_cast<char*>(h->pol.get());
+    policy_jvp_parts(c, k, h, p, K, pre != nullptr, d_params != nullptr, d_obs != nullptr, d_pre != nullptr, d_pre_out != nullptr,
+                     d_actions_out != nullptr);
+  }
+  PolicyJvpArgs a{};
+  HIPCHK(h, device_input(h, p->params, mem_kind, PE * D, k.params, &a.params));
+  HIPCHK(h, device_input(h, p->obs_scale, mem_kind, nO * D, k.scale, &a.obs_scale));
+  HIPCHK(h, device_input(h, obs, mem_kind, E * nO * D, k.obs, &a.obs));
+  HIPCHK(h, device_input(h, pre, mem_kind, E * nA * D, k.pre, &a.pre));
+  HIPCHK(h, device_input(h, d_params, mem_kind, kk * PE * D, k.d_params, &a.d_params));
+  HIPCHK(h, device_input(h, d_obs, mem_kind, kk * E * nO * D, k.d_obs, &a.d_obs));
+  HIPCHK(h, device_input(h, d_pre, mem_kind, kk * E * nA * D, k.d_pre, &a.d_pre));
+  a.du = device_output(d_pre_out, mem_kind, k.du);
+  a.da = device_output(d_actions_out, mem_kind, k.da);
+  a.dparams_stride = (long long)PE;
+  a.dobs_stride = (long long)(E * nO);
+  a.dpre_stride = a.du_stride = a.da_stride = (long long)(E * nA);
+  policy_jvp_shape(a, *p, P, p->action_scale);
+  hipLaunchKernelGGL(policy_jvp_kernel, dim3(h->cfg.num_envs, K), dim3(BLOCK), 0, h->stream, a);
+  hipError_t e = hipGetLastError();
+  if (host) {
+    if (e == hipSuccess) e = device_result(h, d_pre_out, a.du, kk * E * nA * D);
+    if (e == hipSuccess) e = device_result(h, d_actions_out, a.da, kk * E * nA * D);
   }
   const hipError_t e2 = host ? hipStreamSynchronize(h->stream) : hipSuccess;
   if (e != hipSuccess || e2 != hipSuccess)

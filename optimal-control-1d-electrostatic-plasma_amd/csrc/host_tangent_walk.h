@@ -3,7 +3,8 @@
 // ---------------------------------------------------------------------------------------------
 // Forward mode through closed loops (include/picstep.h: pic_tape_tangent_walk_*, pic_tape_tangent_feedback; kernels: pic_tangent.h;
 // DESIGN.md 7n): the tape's steps one at a time, forward in time, with the action tangent of a step fed from the field tangent
-// the step before left -- by the gain law on the device, or by the caller between two steps
+// the step before left -- by the gain law on the device, by the caller between two steps, or (pic_tape_tangent_policy, DESIGN.md
+// 7q) by the MLP policy's JVP kernel on the device
 // ---------------------------------------------------------------------------------------------
 // the working rows of a walk of kc directions observing mo modes (M: the actuator's modes): the field tangent the last step left
 // dM [kc][env][Ng], its energies' tangents [kc][3][env], the observation's tangent [kc][env][2 mo], the law's dm [kc][env][2M],
@@ -54,6 +55,57 @@ static TanWalkViews tanwalk_views(const pic_handle* h) {
   TanWalkViews v;
   tanwalk_parts(Carver{static_cast<char*>(h->tape.tw_block.get())}, h, h->tape.tw_cap_k, h->tape.tw_cap_mo, v);
   return v;
+}
+
+// the working rows of a walk through the policy's steps (pic_tape_tangent_policy) for kc directions: the parameters'
+// tangent dtheta [kc][P] or [kc][env][P], the du of the step at hand [kc][env][2M], and a step's d_pre from host memory
+struct TanPolViews {
+  double* dtheta = nullptr;
+  double* du = nullptr;
+  double* pin = nullptr;
+};
+
+static size_t tanpol_parts(Carver c, const pic_handle* h, int kc, TanPolViews& v) {
+  const Tape& t = h->tape;
+  const size_t E = h->cfg.num_envs, arow = E * 2 * h->act_modes, k = (size_t)kc;
+  c.take(v.dtheta, k * (t.pshape.per_env ? E : 1) * t.pP);
+  c.take(v.du, k * arow);
+  c.take(v.pin, k * arow);
+  return c.at;
+}
+
+// that block for K directions, within budget_bytes; on failure the tape keeps what it had
+static int tanpol_reserve(pic_handle* h, int K, const std::string& w) {
+  Tape& t = h->tape;
+  if (t.tp_cap_k >= K && t.tp_block) return PIC_OK;
+  TanPolViews scratch;
+  const size_t bytes = tanpol_parts(Carver{}, h, K, scratch);
+  if (t.budget > 0 && t.bytes - t.tp_bytes + bytes > (size_t)t.budget)
+    return fail(h, PIC_ENOMEM, w + ": the policy tangent's working rows (" + std::to_string(bytes) + " bytes) would take the tape past budget_bytes (pic_tape_start)");
+  DeviceBuf<void> b;
+  const int rc = regrow(h, b, bytes, (w + ": the policy tangent's working rows do not fit on the device").c_str());
+  if (rc) return rc;
+  if (t.tp_block) HIPCHK(h, hipStreamSynchronize(h->stream));      // queued work may still read the old block
+  t.tp_block = std::move(b);
+  t.bytes = t.bytes - t.tp_bytes + bytes;
+  t.tp_bytes = bytes;
+  t.tp_cap_k = K;
+  return PIC_OK;
+}
+
+static TanPolViews tanpol_views(const pic_handle* h) {
+  TanPolViews v;
+  tanpol_parts(Carver{static_cast<char*>(h->tape.tp_block.get())}, h, h->tape.tp_cap_k, v);
+  return v;
+}
+
+// the shape of a policy into the JVP kernel's argument block (P: the doubles of one parameter vector)
+static void policy_jvp_shape(PolicyJvpArgs& a, const pic_policy& p, size_t P, double action_scale) {
+  a.env_params = p.per_env ? (long long)P : 0;
+  a.action_scale = action_scale;
+  a.n_layers = p.n_layers;
+  a.w0 = p.width[0]; a.w1 = p.width[1]; a.w2 = p.width[2]; a.w3 = p.width[3]; a.w4 = p.width[4];
+  a.activation = p.activation; a.squash = p.squash;
 }
 
 // the tangent block's views for K live directions (as pic_tape_tangent sets them)
@@ -120,13 +172,15 @@ static void tangent_start_deposit(pic_handle* h, const double* x, const TanArgs&
 }
 }  // extern "C++"
 
-// pic_tape_tangent_walk_begin, and the start of pic_tape_tangent_feedback (mo = 0)
+// pic_tape_tangent_walk_begin, the start of pic_tape_tangent_feedback (mo = 0) and, with `policy`, of pic_tape_tangent_policy
+// (mo = the policy's M_o; d_params [K][P] or [K][env][P], null = 0): only that one goes through the steps of pic_tape_step_policy
 static int tanwalk_open(pic_handle* h, const char* who, int K, int mo, const void* d_x0, const void* d_v0, const double* d_gain,
-                        int mem_kind, double* d_modes0) {
+                        int mem_kind, double* d_modes0, bool policy = false, const double* d_params = nullptr) {
   Tape& t = h->tape;
   const std::string w(who);
   if (int rc = check_tape_open(h, who)) return rc;
-  if (int rc = check_no_policy_steps(h, who)) return rc;
+  if (!policy)
+    if (int rc = check_no_policy_steps(h, who)) return rc;
   if (K < 1 || K > kMaxTangents) return fail(h, PIC_EINVAL, w + ": need 1 <= K <= " + std::to_string(kMaxTangents));
   if (mo < 0 || mo >= h->cfg.Ng) return fail(h, PIC_EINVAL, w + ": need obs_modes = 0 or 1 <= obs_modes < N_mesh");
   if (int rc = check_mem_kind(h, mem_kind, who)) return rc;
@@ -142,6 +196,7 @@ static int tanwalk_open(pic_handle* h, const char* who, int K, int mo, const voi
   int rc = std::max(Ml, mo) > 0 ? ensure_twiddle(h, std::max(Ml, mo)) : PIC_OK;
   if (!rc) rc = tangent_reserve(h, K, w);
   if (!rc) rc = tanwalk_reserve(h, K, mo, w);
+  if (!rc && policy) rc = tanpol_reserve(h, K, w);
   if (rc) return rc;
   t.launches = 0;
   HIPCHK(h, hipMemsetAsync(t.counters, 0, 2 * sizeof(unsigned long long), h->stream));
@@ -159,6 +214,9 @@ static int tanwalk_open(pic_handle* h, const char* who, int K, int mo, const voi
   }
   if (d_gain) HIPCHK(h, device_fill(h, v.dG, d_gain, (size_t)K * arow * 2 * h->act_modes * sizeof(double), mem_kind));
   t.tw_k = K; t.tw_mo = mo; t.tw_dgain = d_gain != nullptr;
+  t.tw_pol = policy; t.tp_dparams = policy && d_params;
+  if (t.tp_dparams)
+    HIPCHK(h, device_fill(h, tanpol_views(h).dtheta, d_params, (size_t)K * (t.pshape.per_env ? E : 1) * t.pP * sizeof(double), mem_kind));
   const AdjArgs a = adjoint_args(h);
   const WalkGeom g = walk_geom(h);
   if (Ml > 0 || mo > 0) {
@@ -192,13 +250,17 @@ static int tanwalk_open(pic_handle* h, const char* who, int K, int mo, const voi
 struct TanWalkIO {
   const double* ext = nullptr;        // [env][Ng]
   const double* act = nullptr;        // [env][2M]
+  const double* pre = nullptr;        // [env][2M] added to du on a policy step (pic_tape_tangent_policy); act's pitch
   size_t in_pitch = 0;
   double* hist = nullptr;             // [3][env]
   size_t hist_pitch = 0;
   double* obs = nullptr;              // [env][2 Mo] of the field the step left; contiguous directions
   double* lawm = nullptr;             // [env][2M] the law's dm of the field the step read (zero on other steps)
   double* aout = nullptr;             // [env][2M] the action tangent applied
-  size_t act_pitch = 0;               // of lawm and aout
+  double* uout = nullptr;             // [env][2M] du of a policy step (zero on other steps)
+  size_t act_pitch = 0;               // of lawm, aout and uout
+  double* obs_in = nullptr;           // [env][2 Mo] the observation's tangent of the field the step read
+  size_t obs_pitch = 0;
   double* em = nullptr;               // [env][Ng]
   size_t em_pitch = 0;
 };
@@ -214,7 +276,7 @@ static int tanwalk_advance(pic_handle* h, const TanWalkIO& io, int mem_kind) {
   const TanGeom tg = tangent_geom(h, g, K);
   const TanArgs ta = tanwalk_state(h, K);
   const TanWalkViews v = tanwalk_views(h);
-  const bool lawstep = tanwalk_is_law(h, s), host = mem_kind == PIC_HOST;
+  const bool lawstep = tanwalk_is_law(h, s), polstep = t.tw_pol && tape_policy_step(h, s), host = mem_kind == PIC_HOST;
   if (i == 0)
     if (int rc = walk_replay(h, sgi, a, g)) return rc;
   if (io.lawm) HIPCHK(h, lawstep ? tanwalk_rows_out(h, io.lawm, io.act_pitch, v.dm, arow, K, mem_kind)
@@ -233,7 +295,40 @@ static int tanwalk_advance(pic_handle* h, const TanWalkIO& io, int mem_kind) {
     in = v.in;
     in_pitch = n;
   }
-  if (io.ext) {
+  HIPCHK(h, tanwalk_rows_out(h, io.obs_in, io.obs_pitch, v.obs, (size_t)E * 2 * t.tw_mo, K, mem_kind));
+  if (polstep) {                        // da_s = the policy's JVP at (o_s, u_s) along (dtheta, do_s, d_pre_s), + the caller's
+    const TanPolViews pv = tanpol_views(h);
+    const Tape::PolicyCopy& pc = t.pcalls[(size_t)t.pol[(size_t)s]];
+    const size_t orow = (size_t)E * 2 * t.pshape.obs_modes;
+    const double* pre = io.pre;
+    size_t pre_pitch = io.in_pitch;
+    if (pre && host) {
+      HIPCHK(h, hipMemcpy2DAsync(pv.pin, arow * sizeof(double), pre, pre_pitch * sizeof(double), arow * sizeof(double), (size_t)K,
+                                 hipMemcpyHostToDevice, h->stream));
+      pre = pv.pin;
+      pre_pitch = arow;
+    }
+    PolicyJvpArgs pa{};
+    pa.obs = t.pobs + (size_t)s * orow;
+    pa.obs_scale = pc.scale;
+    pa.params = pc.params.get();
+    pa.pre = t.ppre + (size_t)s * arow;
+    pa.d_params = t.tp_dparams ? pv.dtheta : nullptr;
+    pa.d_obs = v.obs;
+    pa.d_pre = pre;
+    pa.d_act = in;
+    pa.du = pv.du;
+    pa.da = v.da;
+    pa.dparams_stride = (long long)((t.pshape.per_env ? (size_t)E : 1) * t.pP);
+    pa.dobs_stride = (long long)orow;
+    pa.dpre_stride = (long long)pre_pitch;
+    pa.dact_stride = (long long)in_pitch;
+    pa.du_stride = pa.da_stride = (long long)arow;
+    policy_jvp_shape(pa, t.pshape, t.pP, pc.action_scale);
+    hipLaunchKernelGGL(policy_jvp_kernel, dim3(E, K), dim3(BLOCK), 0, h->stream, pa);
+    ++t.launches;
+    m.act = v.da; m.in_dstride = (long long)arow;
+  } else if (io.ext) {
     m.ext = in; m.in_dstride = (long long)in_pitch;
   } else if (io.act || lawstep) {
     if (io.act) {                     // da_s = (G dm + dG m) + the caller's, or the caller's alone
@@ -245,6 +340,8 @@ static int tanwalk_advance(pic_handle* h, const TanWalkIO& io, int mem_kind) {
   }
   if (io.aout) HIPCHK(h, m.act ? tanwalk_rows_out(h, io.aout, io.act_pitch, v.da, arow, K, mem_kind)
                                : tanwalk_rows_zero(h, io.aout, io.act_pitch, arow, K, mem_kind));
+  if (io.uout) HIPCHK(h, polstep ? tanwalk_rows_out(h, io.uout, io.act_pitch, tanpol_views(h).du, arow, K, mem_kind)
+                                 : tanwalk_rows_zero(h, io.uout, io.act_pitch, arow, K, mem_kind));
   if (int rc = tangent_step(h, ta, a, g, tg, i, m, nullptr, 0, nullptr, 0)) return rc;
   tanwalk_law(h, v, s + 1);
   HIPCHK(h, hipGetLastError());
@@ -337,6 +434,35 @@ int pic_tape_tangent_feedback(pic_handle* h, int K, const double* d_gain, const 
     io.act = d_actions ? d_actions + s * arow : nullptr; io.in_pitch = T * arow;
     io.hist = d_hist ? d_hist + s * 3 * E : nullptr; io.hist_pitch = T * 3 * E;
     io.lawm = d_modes ? d_modes + s * arow : nullptr;
+    io.aout = d_actions_out ? d_actions_out + s * arow : nullptr; io.act_pitch = T * arow;
+    io.em = d_E_mesh ? d_E_mesh + s * mesh : nullptr; io.em_pitch = T * mesh;
+    rc = tanwalk_advance(h, io, mem_kind);
+    if (rc) { t.twalk = false; return rc; }
+  }
+  t.twalk = false;
+  rc = tanwalk_state_out(h, mem_kind, d_x, d_v);
+  return rc ? rc : walk_finish(h, who, mem_kind);
+}
+
+int pic_tape_tangent_policy(pic_handle* h, int K, const double* d_params, const double* d_pre, const double* d_actions, const void* d_x0,
+                            const void* d_v0, int mem_kind, double* d_hist, double* d_obs, double* d_pre_out, double* d_actions_out,
+                            void* d_x, void* d_v, double* d_E_mesh) {
+  const char* who = "pic_tape_tangent_policy";
+  if (!h) return PIC_EINVAL;
+  Tape& t = h->tape;
+  if (int rc = check_tape_open(h, who)) return rc;
+  if (!t.pol_block) return fail(h, PIC_EINVAL, std::string(who) + ": the tape holds no steps of pic_tape_step_policy");
+  const int mo = t.pshape.obs_modes;
+  int rc = tanwalk_open(h, who, K, mo, d_x0, d_v0, nullptr, mem_kind, nullptr, true, d_params);
+  if (rc) return rc;
+  const size_t E = h->cfg.num_envs, mesh = E * h->cfg.Ng, arow = E * 2 * h->act_modes, orow = E * 2 * mo, T = (size_t)t.steps;
+  for (size_t s = 0; s < T; ++s) {
+    TanWalkIO io;
+    io.act = d_actions ? d_actions + s * arow : nullptr; io.in_pitch = T * arow;
+    io.pre = d_pre ? d_pre + s * arow : nullptr;
+    io.hist = d_hist ? d_hist + s * 3 * E : nullptr; io.hist_pitch = T * 3 * E;
+    io.obs_in = d_obs ? d_obs + s * orow : nullptr; io.obs_pitch = T * orow;
+    io.uout = d_pre_out ? d_pre_out + s * arow : nullptr;
     io.aout = d_actions_out ? d_actions_out + s * arow : nullptr; io.act_pitch = T * arow;
     io.em = d_E_mesh ? d_E_mesh + s * mesh : nullptr; io.em_pitch = T * mesh;
     rc = tanwalk_advance(h, io, mem_kind);

@@ -1,4 +1,4 @@
-// pic_policy.h -- the MLP policy a = pi(o) on the modes of the mesh field (pic_policy_eval, pic_step_policy) and its VJP (7p).
+// pic_policy.h -- the MLP policy a = pi(o) on the modes of the mesh field (pic_policy_eval, pic_step_policy), its VJP (7p) and its JVP (7q).
 // Included by picstep.hip only, behind pic_device.h.
 #pragma once
 
@@ -287,6 +287,95 @@ __global__ __launch_bounds__(256) void policy_grad_reduce_kernel(const double* _
   double s = gE[p];
   for (int e = 1; e < num_envs; ++e) s = s + gE[(size_t)e * P + p];
   g[p] = s;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The policy's Jacobian-vector product (pic_policy_jvp, pic_tape_tangent_policy; include/picstep.h)
+// ---------------------------------------------------------------------------------------------
+// One evaluation of the JVP for every (environment, direction).  Pointers are those of environment 0 and direction 0 (and of the
+// step the launch is for); every per-direction array carries its own distance, in doubles, from one direction's row to the next.
+struct PolicyJvpArgs {
+  const double* obs;         // [env][2 Mo] the recorded observation (before obs_scale)
+  const double* obs_scale;   // [2 Mo] or null
+  const double* params;      // as PolicyArgs
+  const double* pre;         // [env][nA] the recorded u, or null (squash == 0)
+  const double* d_params;    // [K][P] or [K][env][P] the parameters' tangent, or null: 0
+  const double* d_obs;       // [K][env][2 Mo] the observation's tangent (before obs_scale), or null: 0
+  const double* d_pre;       // [K][env][nA] added to du (the caller's d_std * eps), or null
+  const double* d_act;       // [K][env][nA] added to da behind the squash (a step's d_actions), or null
+  double* du;                // [K][env][nA] du, or null
+  double* da;                // [K][env][nA] da, or null
+  long long dparams_stride, dobs_stride, dpre_stride, dact_stride, du_stride, da_stride;
+  long long env_params;      // doubles from one environment's parameters (and their tangent) to the next (0: shared)
+  double action_scale;
+  int n_layers;
+  int w0, w1, w2, w3, w4;
+  int activation, squash;
+};
+
+// One workgroup per (environment, direction): blockIdx.y is the direction.  Carrying the directions of an environment in one
+// workgroup would recompute the forward once instead of K times, but the forward is the smaller half of a layer's work here, and
+// at 256 environments K workgroups per environment are what fills the device.  Thread i owns row i of a layer,
+// for the forward (policy_row: the forward's bits) and for the tangent; h_l, h_{l+1} and their tangents live in LDS.
+//   dy_i = db_i;  k ascending: dy_i = dy_i + dW[i][k] * h[k];  k ascending: dy_i = dy_i + W[i][k] * dh[k].
+__global__ __launch_bounds__(BLOCK) void policy_jvp_kernel(PolicyJvpArgs a) {
+  __shared__ double hbuf[2][kPolicyMaxWidth];
+  __shared__ double dbuf[2][kPolicyMaxWidth];
+  const int env = blockIdx.x, d = blockIdx.y, t = threadIdx.x;
+  const int width[kPolicyMaxLayers + 1] = {a.w0, a.w1, a.w2, a.w3, a.w4};
+  const int n0 = a.w0, L = a.n_layers;
+  if (t < n0) {
+    const double o = a.obs[(size_t)env * n0 + t];
+    const double dob = a.d_obs ? a.d_obs[(size_t)d * a.dobs_stride + (size_t)env * n0 + t] : 0.0;
+    hbuf[0][t] = a.obs_scale ? o * a.obs_scale[t] : o;
+    dbuf[0][t] = a.obs_scale ? dob * a.obs_scale[t] : dob;
+  }
+  __syncthreads();
+  const double* __restrict__ p = a.params + (size_t)env * a.env_params;
+  const double* __restrict__ dp = a.d_params ? a.d_params + (size_t)d * a.dparams_stride + (size_t)env * a.env_params : nullptr;
+  int cur = 0;
+#pragma unroll
+  for (int l = 0; l < kPolicyMaxLayers; ++l) {
+    if (l >= L) break;                  // (uniform)
+    const int nin = width[l], nout = width[l + 1];
+    const size_t nW = (size_t)nout * nin;
+    const bool last = l + 1 == L;
+    if (t < nout) {
+      const double* __restrict__ hin = hbuf[cur];
+      const double* __restrict__ dh = dbuf[cur];
+      const double* __restrict__ w = p + (size_t)t * nin;
+      double dy = 0.0;
+      if (dp) {
+        const double* __restrict__ dw = dp + (size_t)t * nin;
+        dy = dp[nW + t];
+        for (int k = 0; k < nin; ++k) dy = dy + dw[k] * hin[k];
+      }
+      for (int k = 0; k < nin; ++k) dy = dy + w[k] * dh[k];
+      if (!last) {
+        const double hv = policy_activation(policy_row(p, p + nW, hin, t, nin), a.activation);
+        const double dact = a.activation == PIC_ACT_TANH ? 1.0 - hv * hv : (hv > 0.0 ? 1.0 : 0.0);
+        hbuf[cur ^ 1][t] = hv;
+        dbuf[cur ^ 1][t] = dy * dact;
+      } else {
+        const size_t at = (size_t)env * nout + t;
+        double du = dy;
+        if (a.d_pre) du = dy + a.d_pre[(size_t)d * a.dpre_stride + at];
+        double da = du;
+        if (a.squash) {
+          const double th = tanh(a.pre[at]);
+          da = (a.action_scale * (1.0 - th * th)) * du;
+        }
+        if (a.d_act) da = da + a.d_act[(size_t)d * a.dact_stride + at];
+        if (a.du) a.du[(size_t)d * a.du_stride + at] = du;
+        if (a.da) a.da[(size_t)d * a.da_stride + at] = da;
+      }
+    }
+    if (last) break;
+    __syncthreads();
+    p += nW + nout;
+    if (dp) dp += nW + nout;
+    cur ^= 1;
+  }
 }
 
 }  // namespace

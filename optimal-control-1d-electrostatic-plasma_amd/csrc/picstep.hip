@@ -277,6 +277,13 @@ struct Tape {
   bool pfirst = true;                 // the reverse pass in progress has met no policy step yet: the next one starts pgE's sums
   bool pcot_obs = false, pcot_act = false;   // pcobs / pcact hold a backward's cotangents
   bool pvalid = false;                // pgE holds the sums of a finished reverse pass over the steps taped so far
+  // forward mode through the policy's steps (pic_tape_tangent_policy): the working rows of tp_cap_k directions
+  // (host_tangent_walk.h: tanpol_parts) next to the walk's, allocated by the first call and grown for more; counts in `bytes`
+  DeviceBuf<void> tp_block;
+  size_t tp_bytes = 0;
+  int tp_cap_k = 0;
+  bool tw_pol = false;                // the forward walk in progress goes through the policy's steps
+  bool tp_dparams = false;            // it carries a parameter tangent
 };
 
 }  // namespace

@@ -324,6 +324,77 @@ class BatchedPIC:
         mem.leave(self._h)
         return out
 
+    # -- forward mode through the policy's steps (pic_policy_jvp, pic_tape_tangent_policy) ---------------------------
+    def policy_jvp(self, policy, obs, pre=None, d_params=None, d_obs=None, d_pre=None, on_device: bool = False):
+        """The Jacobian-vector product of `policy_eval` for every environment (pic_policy_jvp), dual to `policy_vjp`: from
+        observations obs [num_envs, 2 M_o], the recorded pre (u) [num_envs, 2M] (needed with squash only) and the tangents
+        d_params [P] (or [num_envs, P] with per_env; `MLPPolicy.pack_tangent` packs layers), d_obs [num_envs, 2 M_o] and d_pre
+        [num_envs, 2M], an injection in front of the squash (d_std * eps); each None = 0 -> (d_pre, d_actions) [num_envs, 2M].
+        K <= 8 directions at once: every tangent then carries a leading K axis, and so do the results.  NumPy, or float64 CUDA
+        tensors if an input is one or with on_device.  The state is not touched."""
+        E, nO, nA, P = self.num_envs, 2 * policy.obs_modes, 2 * self.max_mode, policy.n_params
+        base = {"d_params": (E, P) if policy.per_env else (P,), "d_obs": (E, nO), "d_pre": (E, nA)}
+        given = {k: a for k, a in (("d_params", d_params), ("d_obs", d_obs), ("d_pre", d_pre)) if a is not None}
+        K, batched = self._directions("policy_jvp", None, base, given)
+        mem = Mem.of(self, policy.params, obs, pre, *given.values(), force_device=on_device)
+        spec, keep = policy.spec(mem, E)
+        obs, pre = mem.f64(obs, (E, nO)), mem.f64(pre, (E, nA))
+        ins = {k: mem.f64(a, (K,) + base[k]) for k, a in given.items()}
+        du, da = mem.empty((K, E, nA)), mem.empty((K, E, nA))
+        addr = mem.addr
+        mem.enter()
+        self._h.policy_jvp(spec, addr(obs), addr(pre), K, addr(ins.get("d_params")), addr(ins.get("d_obs")), addr(ins.get("d_pre")),
+                           mem.kind, addr(du), addr(da))
+        mem.leave(self._h)
+        del keep
+        return (du, da) if batched else (du[0], da[0])
+
+    def tangent_policy(self, d_params=None, d_std=None, noise=None, d_pre=None, d_actions=None, d_x0=None, d_v0=None,
+                       fields: bool = False, on_device: bool = False):
+        """Jacobian-vector product of the taped steps through the MLP policy (pic_tape_tangent_policy), dual to
+        `backward_policy`: tangents d_params [P] (or [num_envs, P] with per_env) of the parameters of every tape_step_policy call,
+        d_std [2M] of std (with noise = eps [T, num_envs, 2M], the rollout's own: d_std * eps is added to d_pre here, the dual of
+        g_std = sum g_pre * eps), d_pre and d_actions [T, num_envs, 2M] injections in front of the squash and on the action,
+        d_x0, d_v0 [num_envs, N] of the starting particles; each None = 0, and a leading axis of K <= 8 directions as in
+        `tangent`.  Returns a dict: "dKE", "dPE", "dPE_reward" [K, T, num_envs], "d_obs" [K, T, num_envs, 2 M_o] (of what step
+        t's policy read), "d_pre", "d_actions" [K, T, num_envs, 2M] (d_pre zero on steps without a policy), "d_x", "d_v"
+        [K, num_envs, N] (final particles) and, with fields, "d_E_mesh" [K, T, num_envs, N_mesh].  On a mixed tape a
+        step_actions* step takes d_actions as its whole tangent and a gain-law step uses its taped gain.  NumPy arrays, or float64
+        CUDA tensors if any input is one or with on_device."""
+        if getattr(self, "_tape_policy", None) is None:
+            raise _abi.PicError("tangent_policy: the tape holds no steps of tape_step_policy")
+        nO, P, per_env = self._tape_policy
+        T = self._h.tape_stats()["steps"]
+        E, N, Ng, n = self.num_envs, self.N, self.N_mesh, 2 * self.max_mode
+        if d_std is not None and noise is None:
+            raise ValueError("tangent_policy: d_std needs noise, the eps of the rollout")
+        base = {"d_params": (E, P) if per_env else (P,), "d_std": (n,), "d_pre": (T, E, n), "d_actions": (T, E, n),
+                "d_x0": (E, N), "d_v0": (E, N)}
+        given = {k: a for k, a in (("d_params", d_params), ("d_std", d_std), ("d_pre", d_pre), ("d_actions", d_actions),
+                                   ("d_x0", d_x0), ("d_v0", d_v0)) if a is not None}
+        K, batched = self._directions("tangent_policy", None, base, given)
+        mem = Mem.of(self, noise, *given.values(), force_device=on_device)
+        ins = {k: mem.f64(a, (K,) + base[k]) for k, a in given.items()}
+        if "d_std" in ins:
+            inj = ins.pop("d_std").reshape(K, 1, 1, n) * mem.f64(noise, (1, T, E, n))
+            ins["d_pre"] = mem.f64(inj + ins["d_pre"] if "d_pre" in ins else inj, (K, T, E, n))
+        hist, x, v = mem.out((K, T, 3, E)), mem.out((K, E, N)), mem.out((K, E, N))
+        do, du, da = mem.out((K, T, E, nO)), mem.out((K, T, E, n)), mem.out((K, T, E, n))
+        em = mem.out((K, T, E, Ng)) if fields else None
+        addr = mem.addr
+        mem.enter()
+        self._walk_serial += 1
+        self._h.tape_tangent_policy(K, addr(ins.get("d_params")), addr(ins.get("d_pre")), addr(ins.get("d_actions")),
+                                    addr(ins.get("d_x0")), addr(ins.get("d_v0")), mem.kind, addr(hist), addr(do), addr(du), addr(da),
+                                    addr(x), addr(v), addr(em))
+        if mem.on_device:
+            self._check_replay("tangent_policy", "tangent")
+        res = {"dKE": hist[:, :, 0], "dPE": hist[:, :, 1], "dPE_reward": hist[:, :, 2], "d_obs": do, "d_pre": du, "d_actions": da,
+               "d_x": x, "d_v": v}
+        if fields:
+            res["d_E_mesh"] = em
+        return res if batched else {k: a[0] for k, a in res.items()}
+
     def modes(self, max_mode: int):
         """Complex [num_envs, max_mode]: rows 1..max_mode of compute_E_k_spectrum for the current E_mesh."""
         return self._h.modes(max_mode)

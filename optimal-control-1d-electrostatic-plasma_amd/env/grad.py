@@ -14,6 +14,8 @@ the gradient from the device's adjoint (pic_tape_backward) and for
 
     KE, PE, PE_reward, actions, pre, obs = rollout_mlp(env, policy, params, T)   # policy: an MLPPolicy, params: its packed vector
     (PE_reward.sum() + lam * (actions ** 2).sum() * L / 4).backward()   # fills params.grad: one device call each way (7p)
+    with fwAD.dual_level():                          # forward mode in params and std: one pic_tape_tangent_policy (7q)
+        outs = rollout_mlp(env, policy, fwAD.make_dual(params, d_params), T)
 
 rollout_policy(..., observe="moments") hands the policy the fluid moments on the mesh, [num_envs, 3, N_mesh], instead of the modes
 (DESIGN.md 7k); the backward sets the policy's cotangent on them through pic_tape_moments_cot.
@@ -335,6 +337,21 @@ class _RolloutMLP(torch.autograd.Function):
             g_std = (torch.as_tensor(out["pre"], dtype=torch.float64, device=dev) * eps).sum((0, 1))
         return g_params, g_std, None, None, None, None, None, None
 
+    @staticmethod
+    def jvp(ctx, params_t, std_t, env_t, policy_t, T_t, noise_t, ce_t, kl_t=None):
+        """Forward mode (torch.autograd.forward_ad): the tangents of the traces, the actions, pre and obs along (params_t, std_t),
+        from one pic_tape_tangent_policy with K = 1 on the tape this rollout opened.  The KL's tangent through the
+        closed loop is not built."""
+        env = ctx.env
+        _check_live(env, ctx.serial, ctx.steps, "jvp")
+        if ctx.kl:
+            raise NotImplementedError("rollout_mlp: forward mode of the KL through the policy is not built (DESIGN.md 7q)")
+        dev = f"cuda:{env.device}"
+        on = lambda a: None if a is None else a.detach().to(dev, torch.float64).contiguous()  # noqa: E731
+        d_std = on(std_t) if ctx.has_std and ctx.noise is not None else None
+        out = env.tangent_policy(d_params=on(params_t), d_std=d_std, noise=ctx.noise if d_std is not None else None, on_device=True)
+        return tuple(out[k].contiguous() for k in ("dKE", "dPE", "dPE_reward", "d_actions", "d_pre", "d_obs"))
+
 
 def rollout_mlp(env, policy, params, T, noise=None, std=None, checkpoint_every=0, kl=None):
     """T steps of `env` (a BatchedPIC with an actuator, on the GPU) in closed loop under the MLP `policy`
@@ -344,7 +361,8 @@ def rollout_mlp(env, policy, params, T, noise=None, std=None, checkpoint_every=0
     noise: eps [T, num_envs, 2M] or None; std: a float64 tensor [2M] or None.  Returns KE, PE, PE_reward [T, num_envs], actions
     and pre [T, num_envs, 2M], obs [T, num_envs, 2 M_o] (obs[t] is what step t's policy read), and with kl=... the smoothed KL
     after every step; all differentiable with respect to `params` and `std`.  `MLPPolicy.unpack_grad` gives params.grad the
-    layers' shapes."""
+    layers' shapes.  Under torch.autograd.forward_ad the outputs carry their tangents along (params, std) from one
+    BatchedPIC.tangent_policy; with kl=... forward mode raises NotImplementedError."""
     if env.max_mode == 0:
         raise PicError("rollout_mlp: the environment has no actuator (set_actuator)")
     T = int(T)
