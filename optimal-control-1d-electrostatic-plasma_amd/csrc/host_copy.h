@@ -31,7 +31,7 @@ int pic_copy_envs(pic_handle* dst, pic_handle* src, const int32_t* map, int mem_
   if (!src->has_state) return fail(h, PIC_ESTATE, "pic_copy_envs: the source holds no state (call pic_reset on it first)");
   if (src->mid_stage || dst->mid_stage)
     return fail(h, PIC_ESTATE, "pic_copy_envs: a staged step is in progress (finish its pic_step_stage calls)");
-  if (dst->tape.on || dst->tape.walk)
+  if (dst->tape.on || dst->tape.walk.on)
     return fail(h, PIC_ESTATE, "pic_copy_envs: refused while a tape is open on the destination (pic_tape_stop first)");
   const int E = dst->cfg.num_envs, Es = src->cfg.num_envs, Ng = h->cfg.Ng;
   const bool host_map = mem_kind == PIC_HOST || !map;

@@ -1,24 +1,104 @@
-// host_diff.h -- shared by host_phase.h, host_tape.h and host_tangent.h; included by picstep.hip alone, behind its helpers
+// host_diff.h -- shared by host_phase.h, host_moments.h, host_tape.h, host_tangent.h, host_tangent_walk.h and host_policy.h; included
+// by picstep.hip alone, behind its helpers.  The layouts of the carved blocks are host_blocks.h's; here: the two functions that
+// allocate one.
 #pragma once
 
-// A device block cut into parts, every part rounded up to 256 bytes.  A block is described once, by a function that take()s its
-// parts in order into the views of a holder and returns `at`, the block's bytes (tape_parts, tape_kl_parts, tangent_parts): with
-// base = null and a scratch holder it only sizes the block, with the block's address it assigns the views.  A part without
-// elements gets no view (null).
-struct Carver {
-  char* base = nullptr;
-  size_t at = 0;
-  static size_t rounded(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-  template <typename T>
-  void take(T*& view, size_t count) {
-    if (base) view = count ? reinterpret_cast<T*>(base + at) : nullptr;
-    at += rounded(count * sizeof(T));
+static_assert(std::is_same<acc_t, long long>::value, "host_blocks.h: TapeViews::acc is an accumulator row");
+
+// what the layouts read of a handle
+inline BlockDims block_dims(const pic_handle* h) {
+  BlockDims d;
+  d.num_envs = (size_t)h->cfg.num_envs; d.ld = (size_t)h->ld; d.Ng = (size_t)h->cfg.Ng; d.act_modes = (size_t)h->act_modes;
+  return d;
+}
+
+// P, the doubles of one parameter vector
+inline size_t policy_param_count(const pic_policy* p) {
+  size_t P = 0;
+  for (int l = 0; l < p->n_layers; ++l) P += (size_t)p->width[l + 1] * p->width[l] + p->width[l + 1];
+  return P;
+}
+
+// ... and of a policy's shape
+inline BlockDims policy_dims(const pic_handle* h, const pic_policy& p) {
+  BlockDims d = block_dims(h);
+  d.P = policy_param_count(&p); d.obs_modes = (size_t)p.obs_modes; d.per_env = p.per_env != 0;
+  return d;
+}
+
+// The one reserve path of the tape's blocks.  `b` becomes a block laid out by `layout` (size_t(Carver, Views&): host_blocks.h),
+// its views go to `views`, and -- with `copy` -- a per-call copy of copy_bytes is allocated with it (keep: b stays as it is, only
+// the copy is new).  In this order: size the block; the tape's bytes with it (less what it replaces) against budget_bytes;
+// allocate aside; wait for the stream if an old block goes (queued work may still read it); carve; views; bytes.  On any failure
+// the tape is as it was, pic_tape_info.bytes included.
+template <typename Views, typename Layout>
+int tape_reserve(pic_handle* h, TapeBlock& b, const char* who, const char* noun, Views& views, Layout layout,
+                 DeviceBuf<double>* copy = nullptr, size_t copy_bytes = 0, bool keep = false) {
+  Tape& t = h->tape;
+  Views v{};
+  const size_t bytes = keep ? b.bytes : layout(Carver{}, v);
+  const size_t total = t.bytes - b.bytes + bytes + copy_bytes;
+  const std::string what = std::string(who) + ": " + noun + " (" + std::to_string((keep ? 0 : bytes) + copy_bytes) + " bytes)";
+  if (t.budget > 0 && total > (size_t)t.budget)
+    return fail(h, PIC_ENOMEM, what + " would take the tape past budget_bytes (pic_tape_start)");
+  DeviceBuf<void> mem;
+  DeviceBuf<double> cmem;
+  int rc = keep ? PIC_OK : regrow(h, mem, bytes, (what + " does not fit on the device").c_str());
+  if (!rc && copy) rc = regrow(h, cmem, copy_bytes, (what + " does not fit on the device").c_str());
+  if (rc) return rc;
+  if (!keep) {
+    if (b) HIPCHK(h, hipStreamSynchronize(h->stream));
+    layout(Carver{static_cast<char*>(mem.get())}, v);
+    b.mem = std::move(mem);
+    b.bytes = bytes;
+    views = v;
   }
-  // bytes of consecutive parts: from the start of the first to `end`, the end of the last one's elements, rounded
-  static size_t upto(const void* first, const void* end) {
-    return rounded((size_t)(static_cast<const char*>(end) - static_cast<const char*>(first)));
+  if (copy) *copy = std::move(cmem);
+  t.bytes = total;
+  return PIC_OK;
+}
+
+// a block of the tape goes again, and its bytes with it: for an entry that fails behind its tape_reserve
+template <typename Attached>
+void tape_release(Tape& t, Attached& a) {
+  t.bytes -= a.block.bytes;
+  a = Attached{};
+}
+
+// tape_reserve's sequence for a block of the handle that a call works on, outside any budget: `b` holds at least *cap bytes and
+// grows to what `layout` needs (cap = null: the block is allocated as it is sized); the views are carved in any case.
+template <typename Views, typename Layout>
+int call_reserve(pic_handle* h, DeviceBuf<void>& b, size_t* cap, const char* who, const char* noun, Views& views, Layout layout) {
+  Views v = views;
+  const size_t bytes = layout(Carver{}, v);
+  if (!cap || bytes > *cap) {
+    if (cap) *cap = 0;
+    const std::string what = std::string(who) + ": " + noun + " (" + std::to_string(bytes) + " bytes) does not fit on the device";
+    if (int rc = regrow(h, b, bytes, what.c_str())) return rc;
+    if (cap) *cap = bytes;
   }
-};
+  layout(Carver{static_cast<char*>(b.get())}, views);
+  return PIC_OK;
+}
+
+// The tail of an entry that enqueued work: the first of `e` and the wait it asks for (wait: the call read something back to host
+// memory) is the entry's PIC_EHIP
+inline int hip_tail(pic_handle* h, hipError_t e, bool wait, const char* who) {
+  const hipError_t e2 = wait ? hipStreamSynchronize(h->stream) : hipSuccess;
+  if (e == hipSuccess) e = e2;
+  return e == hipSuccess ? PIC_OK : fail(h, PIC_EHIP, std::string(who) + ": " + hipGetErrorString(e));
+}
+
+// the shape of a policy into the argument block of one of its three kernels (PolicyArgs, PolicyVjpArgs, PolicyJvpArgs; P: the
+// doubles of one parameter vector)
+template <typename Args>
+void policy_shape(Args& a, const pic_policy& p, size_t P, double action_scale) {
+  a.env_params = p.per_env ? (long long)P : 0;
+  a.action_scale = action_scale;
+  a.n_layers = p.n_layers;
+  a.w0 = p.width[0]; a.w1 = p.width[1]; a.w2 = p.width[2]; a.w3 = p.width[3]; a.w4 = p.width[4];
+  a.activation = p.activation; a.squash = p.squash;
+}
 
 // argument checks of the pic_tape_* entries
 inline int check_mem_kind(pic_handle* h, int mem_kind, const char* who) {
@@ -30,7 +110,7 @@ inline int check_tape_open(pic_handle* h, const char* who) {
 // the forward-mode entries that take no parameter direction stop at steps under an MLP policy (pic_tape_step_policy): their
 // actions depend on the state through the network; pic_tape_tangent_policy (host_tangent_walk.h) is the entry for such a tape
 inline int check_no_policy_steps(pic_handle* h, const char* who) {
-  return h->tape.pcalls.empty() ? PIC_OK
+  return h->tape.policy.calls.empty() ? PIC_OK
                              : fail(h, PIC_EINVAL, std::string(who) + ": the tape holds steps of pic_tape_step_policy (policy steps are "
                                                                       "not built in forward mode)");
 }

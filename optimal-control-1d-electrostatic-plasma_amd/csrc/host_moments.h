@@ -23,25 +23,15 @@ static MomArgs moments_args(const pic_handle* h, dim3& grid) {
 
 static size_t moments_lds(const pic_handle* h) { return (size_t)3 * (h->cfg.Ng + 2) * sizeof(unsigned long long); }
 
-// the parts of the handle's block: the integer sums [3][env][Ng], the max words [env] (both zero between calls) and the
-// device copy of a result that goes to host memory
-static size_t moments_parts(Carver c, pic_handle* h) {
-  const size_t E = h->cfg.num_envs, mesh3 = 3 * E * h->cfg.Ng;
-  c.take(h->mom_acc, mesh3);
-  c.take(h->mom_max, E);
-  c.take(h->mom_out, mesh3);
-  return c.at;
-}
-
+// the handle's block (host_blocks.h: moments_parts), allocated by the first call that needs it
 static int moments_ensure(pic_handle* h, const char* who) {
   if (h->mom_block) return PIC_OK;
   if (moments_lds(h) > (size_t)(64 << 10))
     return fail(h, PIC_EINVAL, std::string(who) + ": N_mesh too large for three LDS meshes of 64-bit sums (at most 2728 cells)");
-  const size_t bytes = moments_parts(Carver{}, h);
-  const int rc = regrow(h, h->mom_block, bytes, (std::string(who) + ": the moments' accumulators do not fit on the device").c_str());
+  const int rc = call_reserve(h, h->mom_block, nullptr, who, "the moments' accumulators", h->mom,
+                              [&](Carver c, MomViews& v) { return moments_parts(c, block_dims(h), v); });
   if (rc) return rc;
-  moments_parts(Carver{static_cast<char*>(h->mom_block.get())}, h);
-  HIPCHK(h, hipMemsetAsync(h->mom_acc, 0, Carver::upto(h->mom_acc, h->mom_max + h->cfg.num_envs), h->stream));
+  HIPCHK(h, hipMemsetAsync(h->mom.acc, 0, Carver::upto(h->mom.acc, h->mom.max + h->cfg.num_envs), h->stream));
   return PIC_OK;
 }
 
@@ -55,15 +45,15 @@ static hipError_t moments_enqueue(pic_handle* h, double* m) {
     using P = decltype(p);
     const typename P::X* x = static_cast<const typename P::X*>(h->x.get());
     const typename P::V* v = static_cast<const typename P::V*>(h->v);
-    hipLaunchKernelGGL((moments_max_kernel<P>), grid, dim3(BLOCK), 0, h->stream, v, h->mom_max, a);
+    hipLaunchKernelGGL((moments_max_kernel<P>), grid, dim3(BLOCK), 0, h->stream, v, h->mom.max, a);
     if (tsc)
       hipLaunchKernelGGL((moments_deposit_kernel<P, PIC_TSC>), grid, dim3(BLOCK), lds, h->stream, x, v,
-                         (const unsigned long long*)h->mom_max, h->mom_acc, a);
+                         (const unsigned long long*)h->mom.max, h->mom.acc, a);
     else
       hipLaunchKernelGGL((moments_deposit_kernel<P, PIC_CIC>), grid, dim3(BLOCK), lds, h->stream, x, v,
-                         (const unsigned long long*)h->mom_max, h->mom_acc, a);
+                         (const unsigned long long*)h->mom.max, h->mom.acc, a);
   });
-  hipLaunchKernelGGL(moments_finish_kernel, dim3(h->cfg.num_envs), dim3(BLOCK), 0, h->stream, h->mom_acc, h->mom_max, m, a);
+  hipLaunchKernelGGL(moments_finish_kernel, dim3(h->cfg.num_envs), dim3(BLOCK), 0, h->stream, h->mom.acc, h->mom.max, m, a);
   return hipGetLastError();
 }
 
@@ -76,12 +66,10 @@ int pic_moments(pic_handle* h, int mem_kind, double* m) {
   if (h->mid_stage) return fail(h, PIC_ESTATE, std::string(who) + ": a staged step is in progress");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   if (int rc = moments_ensure(h, who)) return rc;
-  double* out = device_output(m, mem_kind, h->mom_out);
+  double* out = device_output(m, mem_kind, h->mom.out);
   hipError_t e = moments_enqueue(h, out);
   if (e == hipSuccess) e = device_result(h, m, out, (size_t)h->cfg.num_envs * 3 * h->cfg.Ng * sizeof(double));
-  if (e == hipSuccess && mem_kind == PIC_HOST) e = hipStreamSynchronize(h->stream);      // device outputs stay stream-ordered
-  if (e != hipSuccess) return fail(h, PIC_EHIP, std::string(who) + ": " + hipGetErrorString(e));
-  return PIC_OK;
+  return hip_tail(h, e, mem_kind == PIC_HOST, who);      // device outputs stay stream-ordered
 }
 
 // the gather of a cotangent g [env][3][Ng] (device memory) at the particles x, v [env][ld] into rows of `orow` elements
@@ -127,32 +115,23 @@ int pic_moments_vjp(pic_handle* h, const double* cot_m, int mem_kind, void* g_x,
   }
   if (e == hipSuccess) e = device_result(h, g_x, gx, pbytes);
   if (e == hipSuccess) e = device_result(h, g_v, gv, pbytes);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);           // (this call's buffers go away behind it)
-  if (e != hipSuccess) return fail(h, PIC_EHIP, std::string(who) + ": " + hipGetErrorString(e));
-  return PIC_OK;
+  return hip_tail(h, e, true, who);           // (this call's buffers go away behind it)
 }
 
 // ---------------------------------------------------------------------------------------------
 // Cotangents on the moments of the states of a tape (hooks: walk_reverse, walk_close)
 // ---------------------------------------------------------------------------------------------
-// the rows [max_steps + 1][env][3][Ng]: row s + 1 is a cotangent on the moments of the state step s left, row 0 on those of
-// the state at the start of the tape
-static size_t tape_moments_parts(Carver c, const pic_handle* h, Tape& t, int64_t max_steps) {
-  c.take(t.mom_cot, (size_t)(max_steps + 1) * h->cfg.num_envs * 3 * h->cfg.Ng);
-  return c.at;
-}
-
 // row s (-1: the start) of the open tape holds a cotangent
 static bool tape_moments_row(const pic_handle* h, int64_t s) {
   const Tape& t = h->tape;
-  return t.mom_cot && t.mom_flag[(size_t)(s + 1)];
+  return t.mom_cot.cot && t.mom_cot.flag[(size_t)(s + 1)];
 }
 
 // lambda += the gather of row s at the state x, v [env][ld] it belongs to (walk_reverse: the replayed state step s left;
 // walk_close: the first checkpoint)
 static void tape_moments_reverse(pic_handle* h, int64_t s, const double* x, const double* v, double* lx, double* lv) {
   Tape& t = h->tape;
-  const double* g = t.mom_cot + (size_t)(s + 1) * h->cfg.num_envs * 3 * h->cfg.Ng;
+  const double* g = t.mom_cot.cot + (size_t)(s + 1) * h->cfg.num_envs * 3 * h->cfg.Ng;
   moments_vjp_launch(h, true, x, v, g, lx, lv, (long long)h->ld);
   ++t.launches;
 }
@@ -166,35 +145,26 @@ int pic_tape_moments_cot(pic_handle* h, const double* cot_m, int mem_kind, int64
   if (first_step < -1 || nsteps < 0 || first_step > t.steps || nsteps > t.steps - first_step)
     return fail(h, PIC_EINVAL, std::string(who) + ": rows outside the start (-1) and the " + std::to_string(t.steps) + " steps taped so far");
   if (nsteps == 0) return PIC_OK;
-  if (t.walk && first_step + nsteps - 1 > t.wnext)
+  if (t.walk.on && first_step + nsteps - 1 > t.walk.next)
     return fail(h, PIC_ESTATE, std::string(who) + ": the walk in progress has reversed step " + std::to_string(first_step + nsteps - 1) +
                                    " already");
-  if (!t.mom_cot) {
+  if (!t.mom_cot.cot) {
     if (!cot_m) return PIC_OK;                  // (no row was ever set: all are clear)
-    Tape v;                                     // the block's view: the tape's own once the block is there
-    const size_t bytes = tape_moments_parts(Carver{}, h, v, t.max_steps);
-    if (t.budget > 0 && t.bytes + bytes > (size_t)t.budget)
-      return fail(h, PIC_ENOMEM, std::string(who) + ": the moments' cotangents (" + std::to_string(bytes) +
-                                     " bytes) would take the tape past budget_bytes (pic_tape_start)");
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
-    DeviceBuf<void> block;
-    const int rc = regrow(h, block, bytes, (std::string(who) + ": the moments' cotangents (" + std::to_string(bytes) +
-                                            " bytes) do not fit on the device").c_str());
+    const int rc = tape_reserve<MomCotViews>(h, t.mom_cot.block, who, "the moments' cotangents", t.mom_cot, [&](Carver c, MomCotViews& v) {
+      return tape_moments_parts(c, block_dims(h), t.max_steps, v);
+    });
     if (rc) return rc;
-    tape_moments_parts(Carver{static_cast<char*>(block.get())}, h, v, t.max_steps);
-    t.mom_block = std::move(block);
-    t.mom_cot = v.mom_cot;
-    t.mom_flag.assign((size_t)t.max_steps + 1, 0);
-    t.bytes += bytes;
+    t.mom_cot.flag.assign((size_t)t.max_steps + 1, 0);
   }
   if (cot_m) {
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
     const size_t row = (size_t)h->cfg.num_envs * 3 * h->cfg.Ng;
-    HIPCHK(h, hipMemcpyAsync(t.mom_cot + (size_t)(first_step + 1) * row, cot_m, (size_t)nsteps * row * sizeof(double),
+    HIPCHK(h, hipMemcpyAsync(t.mom_cot.cot + (size_t)(first_step + 1) * row, cot_m, (size_t)nsteps * row * sizeof(double),
                              copy_kind(mem_kind, hipMemcpyHostToDevice), h->stream));
     if (mem_kind == PIC_HOST) HIPCHK(h, hipStreamSynchronize(h->stream));      // (the caller's rows may go away behind this call)
   }
-  std::fill(t.mom_flag.begin() + (first_step + 1), t.mom_flag.begin() + (first_step + 1 + nsteps), cot_m ? 1 : 0);
+  std::fill(t.mom_cot.flag.begin() + (first_step + 1), t.mom_cot.flag.begin() + (first_step + 1 + nsteps), cot_m ? 1 : 0);
   return PIC_OK;
 }
 
@@ -217,15 +187,6 @@ static int moments_jvp_check(pic_handle* h, const std::string& who) {
   if (moments_lds(h) > (size_t)(64 << 10))
     return fail(h, PIC_EINVAL, who + ": N_mesh too large for three LDS meshes of 64-bit sums (at most 2728 cells)");
   return PIC_OK;
-}
-
-// the parts of the forward mode's working memory for kc directions: the integer sums [3][kc][env][Ng] and the max words
-// [3][kc][env] (zero between uses)
-static size_t moments_jvp_parts(Carver c, const pic_handle* h, int kc, MomJvpArgs& j) {
-  const size_t E = h->cfg.num_envs;
-  c.take(j.acc, (size_t)3 * kc * E * h->cfg.Ng);
-  c.take(j.umax, (size_t)3 * kc * E);
-  return c.at;
 }
 
 // the three kernels: the moments' tangents at the particles x, v [env][ld] along the K directions of `j` (dx, dv, dstride, erow,
@@ -265,9 +226,11 @@ int pic_moments_jvp(pic_handle* h, int K, const void* d_x, const void* d_v, int 
   DeviceBuf<double> ddx, ddv, dout;
   const double *tx = nullptr, *tv = nullptr;
   const bool host = mem_kind == PIC_HOST;       // host memory goes through device buffers of this call
-  const size_t wbytes = moments_jvp_parts(Carver{}, h, K, j);
-  hipError_t e = alloc_zeroed(work, wbytes, h->stream);
-  if (e == hipSuccess) moments_jvp_parts(Carver{static_cast<char*>(work.get())}, h, K, j);
+  // (a work block that does not fit has always been this entry's PIC_EHIP)
+  hipError_t e = call_reserve(h, work, nullptr, who, "the working memory", j, [&](Carver c, MomJvpArgs& v) {
+                   return moments_jvp_parts(c, block_dims(h), K, v);
+                 }) ? hipErrorOutOfMemory : hipSuccess;
+  if (e == hipSuccess) e = hipMemsetAsync(j.acc, 0, Carver::upto(j.acc, j.umax + (size_t)3 * K * E), h->stream);
   if (e == hipSuccess && host && d_x) e = alloc(ddx, pbytes);
   if (e == hipSuccess && host && d_v) e = alloc(ddv, pbytes);
   if (e == hipSuccess) e = device_input(h, static_cast<const double*>(d_x), mem_kind, pbytes, ddx, &tx);
@@ -279,49 +242,31 @@ int pic_moments_jvp(pic_handle* h, int K, const void* d_x, const void* d_v, int 
     e = moments_jvp_enqueue(h, (const double*)h->x.get(), (const double*)h->v, j, K, out, (long long)(E * 3 * Ng));
   }
   if (e == hipSuccess) e = device_result(h, d_m, out, obytes);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);           // (this call's buffers go away behind it)
-  if (e != hipSuccess) return fail(h, PIC_EHIP, std::string(who) + ": " + hipGetErrorString(e));
-  return PIC_OK;
+  return hip_tail(h, e, true, who);           // (this call's buffers go away behind it)
 }
 
 // ---------------------------------------------------------------------------------------------
 // The moments of every taped step (include/picstep.h: pic_tape_moments_start, pic_tape_moments; hook: advance)
 // ---------------------------------------------------------------------------------------------
-// the trace [max_steps][env][3][Ng]: row t holds the moments of the state step t left
-static size_t tape_moments_trace_parts(Carver c, const pic_handle* h, Tape& t, int64_t max_steps) {
-  c.take(t.mom_trace, (size_t)max_steps * h->cfg.num_envs * 3 * h->cfg.Ng);
-  return c.at;
-}
-
 int pic_tape_moments_start(pic_handle* h) {
   const char* who = "pic_tape_moments_start";
   if (!h) return PIC_EINVAL;
   Tape& t = h->tape;
   if (int rc = check_tape_open(h, who)) return rc;
-  if (t.mom_trace) return fail(h, PIC_ESTATE, std::string(who) + ": the tape has a moments trace already");
+  if (t.mom_trace.trace) return fail(h, PIC_ESTATE, std::string(who) + ": the tape has a moments trace already");
   if (t.steps != 0) return fail(h, PIC_ESTATE, std::string(who) + ": the tape holds steps already (start the trace before the first)");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  Tape v;                               // the block's view: the tape's own once the block is there
-  const size_t bytes = tape_moments_trace_parts(Carver{}, h, v, t.max_steps);
-  if (t.budget > 0 && t.bytes + bytes > (size_t)t.budget)
-    return fail(h, PIC_ENOMEM, std::string(who) + ": the moments' trace (" + std::to_string(bytes) +
-                                   " bytes) would take the tape past budget_bytes (pic_tape_start)");
-  if (int rc = moments_ensure(h, who)) return rc;
-  DeviceBuf<void> block;
-  const int rc = regrow(h, block, bytes, (std::string(who) + ": the moments' trace (" + std::to_string(bytes) +
-                                          " bytes) does not fit on the device").c_str());
-  if (rc) return rc;
-  tape_moments_trace_parts(Carver{static_cast<char*>(block.get())}, h, v, t.max_steps);
-  t.mtr_block = std::move(block);
-  t.mom_trace = v.mom_trace;
-  t.bytes += bytes;
-  return PIC_OK;
+  int rc = tape_reserve<MomTraceViews>(h, t.mom_trace.block, who, "the moments' trace", t.mom_trace, [&](Carver c, MomTraceViews& v) {
+    return tape_moments_trace_parts(c, block_dims(h), t.max_steps, v);
+  });
+  if (!rc && (rc = moments_ensure(h, who)) != PIC_OK) tape_release(t, t.mom_trace);      // (budget_bytes first, then what allocates)
+  return rc;
 }
 
 // the moments of the handle's particles into row t.steps of the trace (advance, behind the step that is about to be counted)
 static int tape_moments_enqueue(pic_handle* h) {
   Tape& t = h->tape;
-  HIPCHK(h, moments_enqueue(h, t.mom_trace + (size_t)t.steps * h->cfg.num_envs * 3 * h->cfg.Ng));
+  HIPCHK(h, moments_enqueue(h, t.mom_trace.trace + (size_t)t.steps * h->cfg.num_envs * 3 * h->cfg.Ng));
   return PIC_OK;
 }
 
@@ -329,12 +274,12 @@ int pic_tape_moments(pic_handle* h, int mem_kind, double* m) {
   const char* who = "pic_tape_moments";
   if (!h) return PIC_EINVAL;
   Tape& t = h->tape;
-  if (!t.on || !t.mom_trace)
+  if (!t.on || !t.mom_trace.trace)
     return fail(h, PIC_ESTATE, std::string(who) + ": no tape with a moments trace is open (pic_tape_moments_start)");
   if ((mem_kind != PIC_HOST && mem_kind != PIC_DEVICE) || !m) return fail(h, PIC_EINVAL, std::string(who) + ": bad mem_kind or null m");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   if (t.steps == 0) return PIC_OK;
-  HIPCHK(h, hipMemcpyAsync(m, t.mom_trace, (size_t)t.steps * h->cfg.num_envs * 3 * h->cfg.Ng * sizeof(double),
+  HIPCHK(h, hipMemcpyAsync(m, t.mom_trace.trace, (size_t)t.steps * h->cfg.num_envs * 3 * h->cfg.Ng * sizeof(double),
                            copy_kind(mem_kind, hipMemcpyDeviceToHost), h->stream));
   if (mem_kind == PIC_HOST) HIPCHK(h, hipStreamSynchronize(h->stream));
   return PIC_OK;

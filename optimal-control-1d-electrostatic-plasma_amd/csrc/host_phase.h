@@ -90,9 +90,7 @@ int pic_phase_kl_smooth(pic_handle* h, const pic_phase_spec* s, int mem_kind, do
   if (e == hipSuccess) e = phase_enqueue(h, s, (const double*)h->x.get(), (const double*)h->v, acc, feq, nullptr, fo, klo, nullptr, a);
   if (e == hipSuccess) e = device_result(h, f, fo, (size_t)E * nb2 * sizeof(double));
   if (e == hipSuccess) e = device_result(h, kl, klo, (size_t)E * sizeof(double));
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) return fail(h, PIC_EHIP, std::string("pic_phase_kl_smooth: ") + hipGetErrorString(e));
-  return PIC_OK;
+  return hip_tail(h, e, true, "pic_phase_kl_smooth");
 }
 
 int pic_phase_kl_smooth_vjp(pic_handle* h, const pic_phase_spec* s, const double* cot_kl, int mem_kind, void* g_x, void* g_v) {
@@ -129,9 +127,7 @@ int pic_phase_kl_smooth_vjp(pic_handle* h, const pic_phase_spec* s, const double
   }
   if (e == hipSuccess) e = device_result(h, g_x, gx, pbytes);
   if (e == hipSuccess) e = device_result(h, g_v, gv, pbytes);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) return fail(h, PIC_EHIP, std::string("pic_phase_kl_smooth_vjp: ") + hipGetErrorString(e));
-  return PIC_OK;
+  return hip_tail(h, e, true, "pic_phase_kl_smooth_vjp");
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -201,7 +197,5 @@ int pic_phase_kl_smooth_jvp(pic_handle* h, const pic_phase_spec* s, int K, const
     e = phase_jvp_enqueue(h, s, a, x, v, dg, j, K, out, (long long)E);
   }
   if (e == hipSuccess) e = device_result(h, d_kl, out, obytes);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) return fail(h, PIC_EHIP, std::string("pic_phase_kl_smooth_jvp: ") + hipGetErrorString(e));
-  return PIC_OK;
+  return hip_tail(h, e, true, "pic_phase_kl_smooth_jvp");
 }

@@ -1,12 +1,6 @@
 // host_policy.h -- the host side of pic_policy_eval, pic_step_policy, pic_policy_vjp and pic_tape_step_policy (7p) and pic_policy_jvp (7q); kernels: pic_policy.h.
-// Included by picstep.hip inside its extern "C" block, behind the stepping entries (step_prologue, actuator_control, advance).
-
-// P, the doubles of one parameter vector
-static size_t policy_param_count(const pic_policy* p) {
-  size_t P = 0;
-  for (int l = 0; l < p->n_layers; ++l) P += (size_t)p->width[l + 1] * p->width[l] + p->width[l + 1];
-  return P;
-}
+// Included by picstep.hip inside its extern "C" block, behind the stepping entries (step_prologue, actuator_control, advance); the
+// layouts of its blocks are host_blocks.h's, call_reserve and tape_reserve (host_diff.h) allocate them.
 
 // what is wrong with a policy whatever the actuator, or null
 static const char* policy_bad_args(const pic_handle* h, const pic_policy* p, int mem_kind) {
@@ -34,55 +28,29 @@ static int policy_actuator(pic_handle* h, const pic_policy* p, const char* who) 
   return PIC_OK;
 }
 
-// One call's arguments, and the views into the handle's policy block it works on (h->pol): the per-step rows of the actions the
-// steps read, the energies' record, and -- for a call in host memory -- the device copies of its inputs and outputs.
-struct PolicyCall {
+// One call's arguments; its base: the views into the handle's policy block it works on (host_blocks.h: policy_parts)
+struct PolicyCall : PolicyCallViews {
   const pic_policy* p;
   const double *obs, *noise, *std;
   int mem_kind, nsteps;
   bool stepping;
   double *obs_out, *pre_out, *actions_out, *hist;
-  // views
-  double *d_act = nullptr, *d_hist = nullptr, *d_params = nullptr, *d_scale = nullptr, *d_std = nullptr, *d_noise = nullptr,
-         *d_obs = nullptr, *d_obs_out = nullptr, *d_pre_out = nullptr;
 };
 
-static size_t policy_parts(Carver& c, PolicyCall& k, const pic_handle* h) {
-  const size_t E = (size_t)h->cfg.num_envs, T = (size_t)k.nsteps;
-  const size_t nO = 2 * (size_t)k.p->obs_modes, nA = 2 * (size_t)h->act_modes;
-  const bool host = k.mem_kind == PIC_HOST;
-  c.take(k.d_act, k.stepping ? T * E * nA : (host && k.actions_out ? E * nA : 0));
-  c.take(k.d_hist, k.hist ? T * 3 * E : 0);
-  if (!host) return c.at;
-  c.take(k.d_params, (k.p->per_env ? E : 1) * policy_param_count(k.p));
-  c.take(k.d_scale, k.p->obs_scale ? nO : 0);
-  c.take(k.d_std, k.std ? nA : 0);
-  c.take(k.d_noise, k.noise ? T * E * nA : 0);
-  c.take(k.d_obs, k.obs ? E * nO : 0);
-  c.take(k.d_obs_out, k.obs_out ? T * E * nO : 0);
-  c.take(k.d_pre_out, k.pre_out ? T * E * nA : 0);
-  return c.at;
-}
-
 // The block of a call, its inputs on the device and the argument block of its first step (the per-step pointers at row 0)
-static int policy_begin(pic_handle* h, PolicyCall& k, PolicyArgs& a) {
-  Carver size;
-  PolicyCall scratch = k;
-  const size_t bytes = policy_parts(size, scratch, h);
-  if (bytes > h->pol_bytes) {
-    h->pol_bytes = 0;
-    const int rc = regrow(h, h->pol, bytes, "the policy's device block does not fit on the device");
-    if (rc) return rc;
-    h->pol_bytes = bytes;
-  }
-  Carver c;
-  c.base = static_cast<char*>(h->pol.get());
-  policy_parts(c, k, h);
+static int policy_begin(pic_handle* h, PolicyCall& k, PolicyArgs& a, const char* who) {
   const pic_policy* p = k.p;
-  const size_t E = (size_t)h->cfg.num_envs, T = (size_t)k.nsteps, D = sizeof(double);
-  const size_t nO = 2 * (size_t)p->obs_modes, nA = 2 * (size_t)h->act_modes, P = policy_param_count(p);
+  const BlockDims d = policy_dims(h, *p);
+  PolicyCallShape s;
+  s.nsteps = (size_t)k.nsteps; s.host = k.mem_kind == PIC_HOST; s.stepping = k.stepping;
+  s.scale = p->obs_scale; s.std = k.std; s.noise = k.noise; s.obs = k.obs;
+  s.obs_out = k.obs_out; s.pre_out = k.pre_out; s.actions_out = k.actions_out; s.hist = k.hist;
+  if (int rc = call_reserve<PolicyCallViews>(h, h->pol, &h->pol_bytes, who, "the policy's device block", k,
+                                             [&](Carver c, PolicyCallViews& v) { return policy_parts(c, d, s, v); }))
+    return rc;
+  const size_t E = d.num_envs, T = s.nsteps, D = sizeof(double), nO = 2 * d.obs_modes, nA = 2 * d.act_modes;
   a = PolicyArgs{};
-  HIPCHK(h, device_input(h, p->params, k.mem_kind, (p->per_env ? E : 1) * P * D, k.d_params, &a.params));
+  HIPCHK(h, device_input(h, p->params, k.mem_kind, d.params() * D, k.d_params, &a.params));
   HIPCHK(h, device_input(h, p->obs_scale, k.mem_kind, nO * D, k.d_scale, &a.obs_scale));
   HIPCHK(h, device_input(h, k.std, k.mem_kind, nA * D, k.d_std, &a.std));
   HIPCHK(h, device_input(h, k.noise, k.mem_kind, T * E * nA * D, k.d_noise, &a.noise));
@@ -100,11 +68,8 @@ static int policy_begin(pic_handle* h, PolicyCall& k, PolicyArgs& a) {
   } else {
     a.act = device_output(k.actions_out, k.mem_kind, k.d_act);
   }
-  a.env_params = p->per_env ? (long long)P : 0;
-  a.action_scale = p->action_scale;
-  a.Mo = p->obs_modes; a.n_layers = p->n_layers;
-  a.w0 = p->width[0]; a.w1 = p->width[1]; a.w2 = p->width[2]; a.w3 = p->width[3]; a.w4 = p->width[4];
-  a.activation = p->activation; a.squash = p->squash;
+  a.Mo = p->obs_modes;
+  policy_shape(a, *p, d.P, p->action_scale);
   return PIC_OK;
 }
 
@@ -140,10 +105,7 @@ static int policy_finish(pic_handle* h, const PolicyCall& k, const PolicyArgs& a
     if (e == hipSuccess) e = hipMemcpyAsync(k.hist, k.d_hist, T * 3 * E * D, hipMemcpyDeviceToHost, h->stream);
     wait = true;
   }
-  const hipError_t e2 = wait ? hipStreamSynchronize(h->stream) : hipSuccess;
-  if (e != hipSuccess || e2 != hipSuccess)
-    return fail(h, PIC_EHIP, std::string(who) + ": " + hipGetErrorString(e != hipSuccess ? e : e2));
-  return PIC_OK;
+  return hip_tail(h, e, wait, who);
 }
 
 int pic_policy_eval(pic_handle* h, const pic_policy* p, const double* obs, const double* noise, const double* std, int mem_kind,
@@ -155,39 +117,15 @@ int pic_policy_eval(pic_handle* h, const pic_policy* p, const double* obs, const
   if (rc) return rc;
   if (!obs && !h->has_state) return fail(h, PIC_ESTATE, std::string(who) + ": call pic_reset first (obs = NULL reads the current E_mesh)");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  PolicyCall k{p, obs, noise, std, mem_kind, 1, false, obs_out, pre_out, actions_out, nullptr};
+  PolicyCall k{{}, p, obs, noise, std, mem_kind, 1, false, obs_out, pre_out, actions_out, nullptr};
   PolicyArgs a;
-  rc = policy_begin(h, k, a);
+  rc = policy_begin(h, k, a, who);
   if (rc) return rc;
   policy_launch(h, a);
   return policy_finish(h, k, a, who);
 }
 
 // ---- the policy's vector-Jacobian product (pic_policy_vjp; kernel: pic_policy.h) ---------------------------------
-// the parts of the handle's policy block a pic_policy_vjp call works on: the per-environment sums, their reduction, and -- for a
-// call in host memory -- the device copies of its inputs and outputs
-struct PolicyVjpCall {
-  double *gE = nullptr, *g = nullptr, *params = nullptr, *scale = nullptr, *obs = nullptr, *pre = nullptr, *cot = nullptr,
-         *g_obs = nullptr, *g_pre = nullptr;
-};
-
-static size_t policy_vjp_parts(Carver& c, PolicyVjpCall& k, const pic_handle* h, const pic_policy* p, bool host, bool has_pre,
-                               bool want_obs, bool want_pre) {
-  const size_t E = (size_t)h->cfg.num_envs, P = policy_param_count(p);
-  const size_t nO = 2 * (size_t)p->obs_modes, nA = 2 * (size_t)h->act_modes;
-  c.take(k.gE, E * P);
-  c.take(k.g, p->per_env ? 0 : P);
-  if (!host) return c.at;
-  c.take(k.params, (p->per_env ? E : 1) * P);
-  c.take(k.scale, p->obs_scale ? nO : 0);
-  c.take(k.obs, E * nO);
-  c.take(k.pre, has_pre ? E * nA : 0);
-  c.take(k.cot, E * nA);
-  c.take(k.g_obs, want_obs ? E * nO : 0);
-  c.take(k.g_pre, want_pre ? E * nA : 0);
-  return c.at;
-}
-
 int pic_policy_vjp(pic_handle* h, const pic_policy* p, const double* obs, const double* pre, const double* cot_actions, int mem_kind,
                    double* g_params, double* g_obs, double* g_pre) {
   const char* who = "pic_policy_vjp";
@@ -199,20 +137,14 @@ int pic_policy_vjp(pic_handle* h, const pic_policy* p, const double* obs, const 
   if (!pre && p->squash) return fail(h, PIC_EINVAL, std::string(who) + ": pre may be NULL only with squash == 0");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   const bool host = mem_kind == PIC_HOST;
-  Carver size;
-  PolicyVjpCall k;
-  const size_t bytes = policy_vjp_parts(size, k, h, p, host, pre != nullptr, g_obs != nullptr, g_pre != nullptr);
-  if (bytes > h->pol_bytes) {
-    h->pol_bytes = 0;
-    rc = regrow(h, h->pol, bytes, "pic_policy_vjp: the policy's device block does not fit on the device");
-    if (rc) return rc;
-    h->pol_bytes = bytes;
-  }
-  Carver c;
-  c.base = static_cast<char*>(h->pol.get());
-  policy_vjp_parts(c, k, h, p, host, pre != nullptr, g_obs != nullptr, g_pre != nullptr);
-  const size_t E = (size_t)h->cfg.num_envs, D = sizeof(double), P = policy_param_count(p);
-  const size_t nO = 2 * (size_t)p->obs_modes, nA = 2 * (size_t)h->act_modes;
+  const BlockDims d = policy_dims(h, *p);
+  PolicyCallShape s;
+  s.host = host; s.scale = p->obs_scale; s.pre = pre; s.obs_out = g_obs; s.pre_out = g_pre;
+  PolicyVjpViews k;
+  rc = call_reserve(h, h->pol, &h->pol_bytes, who, "the policy's device block", k,
+                    [&](Carver c, PolicyVjpViews& v) { return policy_vjp_parts(c, d, s, v); });
+  if (rc) return rc;
+  const size_t E = d.num_envs, D = sizeof(double), P = d.P, nO = 2 * d.obs_modes, nA = 2 * d.act_modes;
   PolicyVjpArgs a{};
   HIPCHK(h, device_input(h, p->params, mem_kind, (p->per_env ? E : 1) * P * D, k.params, &a.params));
   HIPCHK(h, device_input(h, p->obs_scale, mem_kind, nO * D, k.scale, &a.obs_scale));
@@ -222,13 +154,10 @@ int pic_policy_vjp(pic_handle* h, const pic_policy* p, const double* obs, const 
   a.g_params = k.gE;
   a.g_obs = device_output(g_obs, mem_kind, k.g_obs);
   a.g_pre = device_output(g_pre, mem_kind, k.g_pre);
-  a.env_params = p->per_env ? (long long)P : 0;
   a.P = (long long)P;
-  a.action_scale = p->action_scale;
   a.first = 1;
-  a.Mo = p->obs_modes; a.n_layers = p->n_layers;
-  a.w0 = p->width[0]; a.w1 = p->width[1]; a.w2 = p->width[2]; a.w3 = p->width[3]; a.w4 = p->width[4];
-  a.activation = p->activation; a.squash = p->squash;
+  a.Mo = p->obs_modes;
+  policy_shape(a, *p, P, p->action_scale);
   hipLaunchKernelGGL(policy_vjp_kernel, dim3(h->cfg.num_envs), dim3(BLOCK), 0, h->stream, a);
   const double* gsrc = k.gE;
   if (!p->per_env && g_params) {
@@ -243,35 +172,10 @@ int pic_policy_vjp(pic_handle* h, const pic_policy* p, const double* obs, const 
     if (e == hipSuccess) e = device_result(h, g_obs, a.g_obs, E * nO * D);
     if (e == hipSuccess) e = device_result(h, g_pre, a.g_pre, E * nA * D);
   }
-  const hipError_t e2 = host ? hipStreamSynchronize(h->stream) : hipSuccess;
-  if (e != hipSuccess || e2 != hipSuccess)
-    return fail(h, PIC_EHIP, std::string(who) + ": " + hipGetErrorString(e != hipSuccess ? e : e2));
-  return PIC_OK;
+  return hip_tail(h, e, host, who);
 }
 
 // ---- the policy's Jacobian-vector product (pic_policy_jvp; kernel: pic_policy.h) ---------------------------------
-// the parts of the handle's policy block a pic_policy_jvp call in host memory works on: the device copies of its inputs and outputs
-struct PolicyJvpCall {
-  double *params = nullptr, *scale = nullptr, *obs = nullptr, *pre = nullptr, *d_params = nullptr, *d_obs = nullptr, *d_pre = nullptr,
-         *du = nullptr, *da = nullptr;
-};
-
-static size_t policy_jvp_parts(Carver& c, PolicyJvpCall& k, const pic_handle* h, const pic_policy* p, int K, bool has_pre,
-                               bool has_dparams, bool has_dobs, bool has_dpre, bool want_du, bool want_da) {
-  const size_t E = (size_t)h->cfg.num_envs, P = policy_param_count(p), PE = (p->per_env ? E : 1) * P, kk = (size_t)K;
-  const size_t nO = 2 * (size_t)p->obs_modes, nA = 2 * (size_t)h->act_modes;
-  c.take(k.params, PE);
-  c.take(k.scale, p->obs_scale ? nO : 0);
-  c.take(k.obs, E * nO);
-  c.take(k.pre, has_pre ? E * nA : 0);
-  c.take(k.d_params, has_dparams ? kk * PE : 0);
-  c.take(k.d_obs, has_dobs ? kk * E * nO : 0);
-  c.take(k.d_pre, has_dpre ? kk * E * nA : 0);
-  c.take(k.du, want_du ? kk * E * nA : 0);
-  c.take(k.da, want_da ? kk * E * nA : 0);
-  return c.at;
-}
-
 int pic_policy_jvp(pic_handle* h, const pic_policy* p, const double* obs, const double* pre, int K, const double* d_params,
                    const double* d_obs, const double* d_pre, int mem_kind, double* d_pre_out, double* d_actions_out) {
   const char* who = "pic_policy_jvp";
@@ -286,21 +190,14 @@ int pic_policy_jvp(pic_handle* h, const pic_policy* p, const double* obs, const 
   const bool host = mem_kind == PIC_HOST;
   const size_t E = (size_t)h->cfg.num_envs, D = sizeof(double), P = policy_param_count(p), PE = (p->per_env ? E : 1) * P;
   const size_t nO = 2 * (size_t)p->obs_modes, nA = 2 * (size_t)h->act_modes, kk = (size_t)K;
-  PolicyJvpCall k;
+  PolicyJvpViews k;
   if (host) {
-    Carver size;
-    const size_t bytes = policy_jvp_parts(size, k, h, p, K, pre != nullptr, d_params != nullptr, d_obs != nullptr, d_pre != nullptr,
-                                          d_pre_out != nullptr, d_actions_out != nullptr);
-    if (bytes > h->pol_bytes) {
-      h->pol_bytes = 0;
-      rc = regrow(h, h->pol, bytes, "pic_policy_jvp: the policy's device block does not fit on the device");
-      if (rc) return rc;
-      h->pol_bytes = bytes;
-    }
-    Carver c;
-    c.base = static_cast<char*>(h->pol.get());
-    policy_jvp_parts(c, k, h, p, K, pre != nullptr, d_params != nullptr, d_obs != nullptr, d_pre != nullptr, d_pre_out != nullptr,
-                     d_actions_out != nullptr);
+    PolicyCallShape s;
+    s.host = true; s.scale = p->obs_scale; s.pre = pre; s.d_params = d_params; s.d_obs = d_obs; s.d_pre = d_pre;
+    s.pre_out = d_pre_out; s.actions_out = d_actions_out;
+    rc = call_reserve(h, h->pol, &h->pol_bytes, who, "the policy's device block", k,
+                      [&](Carver c, PolicyJvpViews& v) { return policy_jvp_parts(c, policy_dims(h, *p), s, K, v); });
+    if (rc) return rc;
   }
   PolicyJvpArgs a{};
   HIPCHK(h, device_input(h, p->params, mem_kind, PE * D, k.params, &a.params));
@@ -315,37 +212,17 @@ int pic_policy_jvp(pic_handle* h, const pic_policy* p, const double* obs, const 
   a.dparams_stride = (long long)PE;
   a.dobs_stride = (long long)(E * nO);
   a.dpre_stride = a.du_stride = a.da_stride = (long long)(E * nA);
-  policy_jvp_shape(a, *p, P, p->action_scale);
+  policy_shape(a, *p, P, p->action_scale);
   hipLaunchKernelGGL(policy_jvp_kernel, dim3(h->cfg.num_envs, K), dim3(BLOCK), 0, h->stream, a);
   hipError_t e = hipGetLastError();
   if (host) {
     if (e == hipSuccess) e = device_result(h, d_pre_out, a.du, kk * E * nA * D);
     if (e == hipSuccess) e = device_result(h, d_actions_out, a.da, kk * E * nA * D);
   }
-  const hipError_t e2 = host ? hipStreamSynchronize(h->stream) : hipSuccess;
-  if (e != hipSuccess || e2 != hipSuccess)
-    return fail(h, PIC_EHIP, std::string(who) + ": " + hipGetErrorString(e != hipSuccess ? e : e2));
-  return PIC_OK;
+  return hip_tail(h, e, host, who);
 }
 
 // ---- policy steps on an open tape (pic_tape_step_policy) --------------------------------------------------------
-static size_t tape_policy_parts(Carver c, const pic_handle* h, Tape& t, const pic_policy* p, int64_t max_steps) {
-  const size_t E = (size_t)h->cfg.num_envs, T = (size_t)max_steps, P = policy_param_count(p);
-  const size_t orows = T * E * 2 * (size_t)p->obs_modes, arows = T * E * 2 * (size_t)h->act_modes;
-  c.take(t.pobs, orows);
-  c.take(t.ppre, arows);
-  c.take(t.pact, arows);
-  c.take(t.pgobs, orows);             // (pgobs, pgpre, pgact: cleared as one range by walk_open)
-  c.take(t.pgpre, arows);
-  c.take(t.pgact, arows);
-  c.take(t.pcobs, orows);
-  c.take(t.pcact, arows);
-  c.take(t.pmbar, E * 2 * (size_t)p->obs_modes);
-  c.take(t.pgE, E * P);
-  c.take(t.pg, p->per_env ? 0 : P);
-  return c.at;
-}
-
 static bool policy_same_shape(const pic_policy& a, const pic_policy& b) {
   if (a.obs_modes != b.obs_modes || a.n_layers != b.n_layers || a.activation != b.activation || a.squash != b.squash ||
       a.per_env != b.per_env)
@@ -359,38 +236,29 @@ static bool policy_same_shape(const pic_policy& a, const pic_policy& b) {
 // budget_bytes; nothing is enqueued or changed when it fails.
 static int tape_policy_reserve(pic_handle* h, const pic_policy* p, const char* who) {
   Tape& t = h->tape;
-  if (t.pol_block && !policy_same_shape(t.pshape, *p))
+  if (t.policy.block && !policy_same_shape(t.policy.shape, *p))
     return fail(h, PIC_EINVAL, std::string(who) + ": every policy call of one tape must have the same shape (widths, activation, "
                                                   "squash, per_env, obs_modes)");
-  Tape v;                               // the block's views: the tape's own once the block is there
-  const size_t P = policy_param_count(p), nO = 2 * (size_t)p->obs_modes;
-  const size_t bbytes = t.pol_block ? 0 : tape_policy_parts(Carver{}, h, v, p, t.max_steps);
-  const size_t cbytes = Carver::rounded((p->per_env ? (size_t)h->cfg.num_envs : 1) * P * sizeof(double)) + nO * sizeof(double);
-  if (t.budget > 0 && t.bytes + bbytes + cbytes > (size_t)t.budget)
-    return fail(h, PIC_ENOMEM, std::string(who) + ": the policy's record (" + std::to_string(bbytes + cbytes) +
-                                   " bytes) would take the tape past budget_bytes (pic_tape_start)");
-  if (!t.pol_block) {
-    DeviceBuf<void> block;
-    const int rc = regrow(h, block, bbytes, (std::string(who) + ": the tape's record of the policy's steps does not fit on the device").c_str());
-    if (rc) return rc;
-    tape_policy_parts(Carver{static_cast<char*>(block.get())}, h, v, p, t.max_steps);
-    t.pol_block = std::move(block);
-    t.pobs = v.pobs; t.ppre = v.ppre; t.pact = v.pact; t.pgobs = v.pgobs; t.pgpre = v.pgpre; t.pgact = v.pgact;
-    t.pcobs = v.pcobs; t.pcact = v.pcact; t.pmbar = v.pmbar; t.pgE = v.pgE; t.pg = v.pg;
-    t.pshape = *p;
-    t.pshape.params = t.pshape.obs_scale = nullptr;
-    t.pP = P;
-    t.pol.assign((size_t)t.max_steps, -1);
-    t.bytes += bbytes;
-  }
-  Tape::PolicyCopy pc;
-  const int rc = regrow(h, pc.params, cbytes, (std::string(who) + ": the tape's copy of the parameters does not fit on the device").c_str());
+  const BlockDims d = policy_dims(h, *p);
+  const bool first = !t.policy.block;
+  PolicyCopyViews cv;
+  const size_t cbytes = policy_copy_parts(Carver{}, d, p->obs_scale, cv);
+  Tape::Policy::Copy pc;
+  const int rc = tape_reserve<TapePolicyViews>(h, t.policy.block, who, "the policy's record and this call's parameters", t.policy,
+                                               [&](Carver c, TapePolicyViews& v) { return tape_policy_parts(c, d, t.max_steps, v); },
+                                               &pc.params, cbytes, !first);
   if (rc) return rc;
-  pc.scale = p->obs_scale ? pc.params.get() + (cbytes / sizeof(double) - nO) : nullptr;
+  if (first) {
+    t.policy.shape = *p;
+    t.policy.shape.params = t.policy.shape.obs_scale = nullptr;
+    t.policy.P = d.P;
+    t.policy.step.assign((size_t)t.max_steps, -1);
+  }
+  policy_copy_parts(Carver{reinterpret_cast<char*>(pc.params.get())}, d, p->obs_scale, cv);
+  pc.scale = cv.scale;
   pc.action_scale = p->action_scale;
   pc.bytes = cbytes;
-  t.pcalls.push_back(std::move(pc));
-  t.bytes += cbytes;
+  t.policy.calls.push_back(std::move(pc));
   return PIC_OK;
 }
 
@@ -409,26 +277,26 @@ int pic_tape_step_policy(pic_handle* h, const pic_policy* p, const double* noise
   rc = tape_policy_reserve(h, p, who);
   if (rc) return rc;
   // the three records are the tape's rows: the call's own outputs are copied from there behind the steps
-  PolicyCall k{p, nullptr, noise, std, mem_kind, nsteps, true, nullptr, nullptr, nullptr, hist};
+  PolicyCall k{{}, p, nullptr, noise, std, mem_kind, nsteps, true, nullptr, nullptr, nullptr, hist};
   PolicyArgs a0;
-  rc = policy_begin(h, k, a0);
+  rc = policy_begin(h, k, a0, who);
   if (rc) {                           // (the copy goes again, and its bytes with it)
-    t.bytes -= t.pcalls.back().bytes;
-    t.pcalls.pop_back();
+    t.bytes -= t.policy.calls.back().bytes;
+    t.policy.calls.pop_back();
     return rc;
   }
-  const size_t E = (size_t)h->cfg.num_envs, D = sizeof(double), P = t.pP;
+  const size_t E = (size_t)h->cfg.num_envs, D = sizeof(double), P = t.policy.P;
   const size_t nO = 2 * (size_t)p->obs_modes, nA = 2 * (size_t)h->act_modes, T = (size_t)nsteps;
   const int64_t s0 = t.steps;
-  const Tape::PolicyCopy& pc = t.pcalls.back();
+  const Tape::Policy::Copy& pc = t.policy.calls.back();
   double* tp = pc.params.get();
   HIPCHK(h, hipMemcpyAsync(tp, a0.params, (p->per_env ? E : 1) * P * D, hipMemcpyDeviceToDevice, h->stream));
   if (pc.scale) HIPCHK(h, hipMemcpyAsync(const_cast<double*>(pc.scale), a0.obs_scale, nO * D, hipMemcpyDeviceToDevice, h->stream));
   a0.params = tp;
   a0.obs_scale = pc.scale;
-  a0.obs_out = t.pobs + (size_t)s0 * E * nO;
-  a0.pre_out = t.ppre + (size_t)s0 * E * nA;
-  a0.act = t.pact + (size_t)s0 * E * nA;
+  a0.obs_out = t.policy.obs + (size_t)s0 * E * nO;
+  a0.pre_out = t.policy.pre + (size_t)s0 * E * nA;
+  a0.act = t.policy.act + (size_t)s0 * E * nA;
   a0.act_out = nullptr;
   for (int s = 0; s < nsteps && rc == PIC_OK; ++s) {      // (as pic_step_policy; advance puts e_t = B a_t on the tape)
     const PolicyArgs a = policy_at(a0, (size_t)s, E, nA);
@@ -436,7 +304,7 @@ int pic_tape_step_policy(pic_handle* h, const pic_policy* p, const double* noise
     sc.ctl.act = a.act;
     rc = advance(h, sc, 1, hist_at(h, k.d_hist, (size_t)s));
   }
-  for (int64_t s = s0; s < t.steps; ++s) t.pol[(size_t)s] = (int)t.pcalls.size() - 1;
+  for (int64_t s = s0; s < t.steps; ++s) t.policy.step[(size_t)s] = (int)t.policy.calls.size() - 1;
   const hipMemcpyKind outk = copy_kind(mem_kind, hipMemcpyDeviceToHost);
   hipError_t e = hipSuccess;
   if (e == hipSuccess && obs_out) e = hipMemcpyAsync(obs_out, a0.obs_out, T * E * nO * D, outk, h->stream);
@@ -460,9 +328,9 @@ int pic_step_policy(pic_handle* h, const pic_policy* p, const double* noise, con
   StepControl sc;
   rc = actuator_control(h, sc, who);
   if (rc) return rc;
-  PolicyCall k{p, nullptr, noise, std, mem_kind, nsteps, true, obs_out, pre_out, actions_out, hist};
+  PolicyCall k{{}, p, nullptr, noise, std, mem_kind, nsteps, true, obs_out, pre_out, actions_out, hist};
   PolicyArgs a0;
-  rc = policy_begin(h, k, a0);
+  rc = policy_begin(h, k, a0, who);
   if (rc) return rc;
   // Step s: the policy on the field step s-1 left, into row s of the actions; then the step pic_step_actions(row s, 1) makes.
   // No row is written twice within a call, so the policy launch of step s+1 cannot overtake a force evaluation of step s.

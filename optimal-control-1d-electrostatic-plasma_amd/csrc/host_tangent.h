@@ -4,68 +4,61 @@
 // Forward mode of the tape (include/picstep.h: pic_tape_tangent[_kl]; kernels: pic_tangent.h), of its per-step
 // smoothed KL (kernels: pic_phase.h) and of its per-step moments (kernels: pic_moments.h)
 // ---------------------------------------------------------------------------------------------
-// the parts of the tangent block for kc directions: state [kc][2][env][ld], dF [kc][env][Ng], acc [kc][env][Ng], ke [kc][env],
-// umax [3][kc][env] (everything from acc on is zero between uses)
-static size_t tangent_parts(Carver c, const pic_handle* h, int kc, TanArgs& ta) {
-  const size_t E = h->cfg.num_envs, mesh = E * h->cfg.Ng;
-  c.take(ta.st, (size_t)kc * 2 * E * h->ld);
-  c.take(ta.dF, kc * mesh);
-  c.take(ta.acc, kc * mesh);
-  c.take(ta.ke, kc * E);
-  c.take(ta.umax, 3 * kc * E);
-  return c.at;
+// the tangent block for K directions, within budget_bytes (grown for more; on failure the tape keeps what it had)
+static int tangent_reserve(pic_handle* h, int K, const char* who) {
+  Tape& t = h->tape;
+  if (t.tan.k >= K) return PIC_OK;
+  const int rc = tape_reserve(h, t.tan.block, who, "the tangent's working memory", t.tan.views,
+                              [&](Carver c, TanArgs& v) { return tangent_parts(c, block_dims(h), K, v); });
+  if (!rc) t.tan.k = K;
+  return rc;
 }
 
-// the tangent block for K directions, within budget_bytes; on failure the tape keeps what it had
-static int tangent_reserve(pic_handle* h, int K, const std::string& w) {
-  Tape& t = h->tape;
-  if (t.tan_k >= K) return PIC_OK;
-  TanArgs scratch{};
-  const size_t bytes = tangent_parts(Carver{}, h, K, scratch);
-  if (t.budget > 0 && t.bytes - t.tan_bytes + bytes > (size_t)t.budget)
-    return fail(h, PIC_ENOMEM, w + ": the working memory of " + std::to_string(K) + " directions (" + std::to_string(bytes) +
-                                   " bytes) would take the tape past budget_bytes (pic_tape_start)");
-  DeviceBuf<void> b;
-  const int rc = regrow(h, b, bytes, (w + ": the working memory of " + std::to_string(K) + " directions does not fit on the device").c_str());
-  if (rc) return rc;
-  if (t.tan_block) HIPCHK(h, hipStreamSynchronize(h->stream));      // queued work may still read the old block
-  t.tan_block = std::move(b);
-  t.bytes = t.bytes - t.tan_bytes + bytes;
-  t.tan_bytes = bytes;
-  t.tan_k = K;
+// the tangent block's views for K live directions, into the kernels' argument block
+static TanArgs tangent_args(const pic_handle* h, int K) {
+  const size_t part = (size_t)h->cfg.num_envs * h->ld;
+  TanArgs ta = h->tape.tan.views;
+  ta.dstride = (long long)(2 * part); ta.vofs = (long long)part;
+  ta.K = K; ta.num_envs = h->cfg.num_envs;
+  return ta;
+}
+
+// (dx_0, dv_0) of ta.K directions from the caller's [K][env][N] (each may be null: 0) into the state rows (padded to ld)
+static int tangent_state_in(pic_handle* h, const TanArgs& ta, const void* d_x0, const void* d_v0, int mem_kind) {
+  const size_t part = (size_t)h->cfg.num_envs * h->ld, EN = (size_t)h->cfg.num_envs * h->cfg.N;
+  const void* ins[2] = {d_x0, d_v0};
+  for (int d = 0; d < ta.K; ++d)
+    for (int k = 0; k < 2; ++k) {
+      double* dst = ta.st + (size_t)d * 2 * part + (size_t)k * part;
+      if (!ins[k]) HIPCHK(h, hipMemsetAsync(dst, 0, part * sizeof(double), h->stream));
+      else if (int rc = upload(h, dst, static_cast<const double*>(ins[k]) + (size_t)d * EN, mem_kind)) return rc;
+    }
   return PIC_OK;
 }
 
-// the parts of the block behind the KL's tangent: the unit cotangents [env] and the chunks' sums [kMaxTangents][env][chunks]
-struct TanKlViews {
-  double* ones = nullptr;
-  double* part = nullptr;
-};
-static size_t tangent_kl_parts(Carver c, const pic_handle* h, TanKlViews& v) {
-  const size_t E = h->cfg.num_envs;
-  c.take(v.ones, E);
-  c.take(v.part, (size_t)kMaxTangents * E * phase_jvp_chunks(h));
-  return c.at;
+// (dx, dv) of every direction out of the state rows to the caller's [K][env][N] (each may be null)
+static int tangent_state_out(pic_handle* h, const TanArgs& ta, int mem_kind, void* d_x, void* d_v) {
+  const size_t part = (size_t)h->cfg.num_envs * h->ld, EN = (size_t)h->cfg.num_envs * h->cfg.N;
+  void* outs[2] = {d_x, d_v};
+  for (int d = 0; d < ta.K; ++d)
+    for (int k = 0; k < 2; ++k)
+      if (outs[k])
+        if (int rc = download(h, static_cast<double*>(outs[k]) + (size_t)d * EN, ta.st + (size_t)d * 2 * part + (size_t)k * part, mem_kind)) return rc;
+  return PIC_OK;
 }
 
-// that block, within budget_bytes (allocated once per tape); on failure the tape keeps what it had
-static int tangent_kl_reserve(pic_handle* h, const std::string& w) {
+// the block behind the KL's tangent (kMaxTangents directions), within budget_bytes (allocated once per tape)
+static int tangent_kl_reserve(pic_handle* h, const char* who) {
   Tape& t = h->tape;
-  if (t.tkl_block) return PIC_OK;
-  TanKlViews v;
-  const size_t bytes = tangent_kl_parts(Carver{}, h, v);
-  if (t.budget > 0 && t.bytes + bytes > (size_t)t.budget)
-    return fail(h, PIC_ENOMEM, w + ": the working memory of the KL's tangent (" + std::to_string(bytes) +
-                                   " bytes) would take the tape past budget_bytes (pic_tape_start)");
-  DeviceBuf<void> b;
-  const int rc = regrow(h, b, bytes, (w + ": the working memory of the KL's tangent does not fit on the device").c_str());
+  if (t.tkl.block) return PIC_OK;
+  BlockDims d = block_dims(h);
+  d.chunks = (size_t)phase_jvp_chunks(h);
+  const int rc = tape_reserve<TanKlViews>(h, t.tkl.block, who, "the working memory of the KL's tangent", t.tkl,
+                                          [&](Carver c, TanKlViews& v) { return tangent_kl_parts(c, d, kMaxTangents, v); });
   if (rc) return rc;
-  tangent_kl_parts(Carver{static_cast<char*>(b.get())}, h, v);
-  HIPCHK(h, phase_fill_ones(h, v.ones, (size_t)h->cfg.num_envs));
-  t.tkl_block = std::move(b);
-  t.tkl_ones = v.ones; t.tkl_part = v.part;
-  t.bytes += bytes;
-  return PIC_OK;
+  const hipError_t e = phase_fill_ones(h, t.tkl.ones, (size_t)h->cfg.num_envs);
+  if (e != hipSuccess) tape_release(t, t.tkl);
+  return hip_tail(h, e, false, who);
 }
 
 // the KL's part of forward step s (kKlTangentLaunches kernels): the deposit and finish of the replayed state x, v the step left,
@@ -74,40 +67,28 @@ constexpr int kKlTangentLaunches = 4;
 static int tangent_kl_step(pic_handle* h, const TanArgs& ta, const double* x, const double* v, double* out, long long out_dstride) {
   Tape& t = h->tape;
   PhaseArgs a;
-  HIPCHK(h, phase_enqueue(h, &t.kl_spec, x, v, t.kl_acc, t.kl_feq, t.tkl_ones, nullptr, nullptr, t.kl_g, a));
+  HIPCHK(h, phase_enqueue(h, &t.kl.spec, x, v, t.kl.acc, t.kl.feq, t.tkl.ones, nullptr, nullptr, t.kl.g, a));
   PhaseJvpArgs j{};
-  j.dx = ta.st; j.dv = ta.st + ta.vofs; j.dstride = ta.dstride; j.erow = h->ld; j.part = t.tkl_part;
-  HIPCHK(h, phase_jvp_enqueue(h, &t.kl_spec, a, x, v, t.kl_g, j, ta.K, out, out_dstride));
+  j.dx = ta.st; j.dv = ta.st + ta.vofs; j.dstride = ta.dstride; j.erow = h->ld; j.part = t.tkl.part;
+  HIPCHK(h, phase_jvp_enqueue(h, &t.kl.spec, a, x, v, t.kl.g, j, ta.K, out, out_dstride));
   t.launches += kKlTangentLaunches;
   return PIC_OK;
 }
 
-// the working memory behind the moments' tangents (kMaxTangents directions), within budget_bytes (allocated once per tape); on
-// failure the tape keeps what it had
-static int tangent_moments_reserve(pic_handle* h, const std::string& w) {
+// the working memory behind the moments' tangents (kMaxTangents directions), within budget_bytes (allocated once per tape)
+static int tangent_moments_reserve(pic_handle* h, const char* who) {
   Tape& t = h->tape;
-  if (t.tmom_block) return PIC_OK;
-  MomJvpArgs v{};
-  const size_t bytes = moments_jvp_parts(Carver{}, h, kMaxTangents, v);
-  if (t.budget > 0 && t.bytes + bytes > (size_t)t.budget)
-    return fail(h, PIC_ENOMEM, w + ": the working memory of the moments' tangent (" + std::to_string(bytes) +
-                                   " bytes) would take the tape past budget_bytes (pic_tape_start)");
-  DeviceBuf<void> b;
-  const int rc = regrow(h, b, bytes, (w + ": the working memory of the moments' tangent does not fit on the device").c_str());
-  if (rc) return rc;
-  moments_jvp_parts(Carver{static_cast<char*>(b.get())}, h, kMaxTangents, v);
-  t.tmom_block = std::move(b);
-  t.tmom_acc = v.acc; t.tmom_max = v.umax;
-  t.bytes += bytes;
-  return PIC_OK;
+  if (t.tmom.block) return PIC_OK;
+  return tape_reserve(h, t.tmom.block, who, "the working memory of the moments' tangent", t.tmom.views,
+                      [&](Carver c, MomJvpArgs& v) { return moments_jvp_parts(c, block_dims(h), kMaxTangents, v); });
 }
 
 // the moments' part of forward step s (kMomentsJvpLaunches kernels): d_moments[d][s] = the tangent of the moments of the replayed
 // state x, v the step left, along the tangent state after pass 3, (dq_4, dp_3) = (dx', dv')
 static int tangent_moments_step(pic_handle* h, const TanArgs& ta, const double* x, const double* v, double* out, long long out_dstride) {
   Tape& t = h->tape;
-  MomJvpArgs j{};
-  j.dx = ta.st; j.dv = ta.st + ta.vofs; j.dstride = ta.dstride; j.erow = h->ld; j.acc = t.tmom_acc; j.umax = t.tmom_max;
+  MomJvpArgs j = t.tmom.views;
+  j.dx = ta.st; j.dv = ta.st + ta.vofs; j.dstride = ta.dstride; j.erow = h->ld;
   HIPCHK(h, moments_jvp_enqueue(h, x, v, j, ta.K, out, out_dstride));
   t.launches += kMomentsJvpLaunches;
   return PIC_OK;
@@ -186,13 +167,13 @@ static int tape_tangent(pic_handle* h, const char* who, int K, const double* d_e
   const std::string w(who);
   if (int rc = check_tape_open(h, w.c_str())) return rc;
   if (int rc = check_no_policy_steps(h, w.c_str())) return rc;
-  if (d_kl && !t.kl) return fail(h, PIC_ESTATE, w + ": d_kl needs a KL on the tape (pic_tape_kl_start before the first step)");
+  if (d_kl && !t.kl.on) return fail(h, PIC_ESTATE, w + ": d_kl needs a KL on the tape (pic_tape_kl_start before the first step)");
   if (K < 1 || K > kMaxTangents) return fail(h, PIC_EINVAL, w + ": need 1 <= K <= " + std::to_string(kMaxTangents));
   if (d_ext && d_actions) return fail(h, PIC_EINVAL, w + ": d_ext and d_actions are both given (at most one)");
   if (int rc = check_mem_kind(h, mem_kind, w.c_str())) return rc;
   const int64_t T = t.steps;
-  for (int64_t s = 0; s < T && !t.law.empty(); ++s)
-    if (t.law[(size_t)s] >= 0)
+  for (int64_t s = 0; s < T; ++s)
+    if (tape_law_step(h, s))
       return fail(h, PIC_ESTATE, w + ": the tape holds steps of pic_step_feedback_gain, and forward mode through the gain law is "
                                      "not built (pic_tape_backward_feedback differentiates it in reverse)");
   if (int rc = check_tape_actuator(h, d_actions, "d_actions", w.c_str())) return rc;
@@ -201,8 +182,8 @@ static int tape_tangent(pic_handle* h, const char* who, int K, const double* d_e
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   const int E = h->cfg.num_envs, Ng = h->cfg.Ng, Mact = h->act_modes;
   const bool host = mem_kind == PIC_HOST;
-  const size_t N = h->cfg.N, part = (size_t)E * h->ld, mesh = (size_t)E * Ng, row = N * sizeof(double);
-  t.walk = t.twalk = false;           // (a walk's replayed segment is about to be overwritten)
+  const size_t N = h->cfg.N, mesh = (size_t)E * Ng, row = N * sizeof(double);
+  t.walk.on = t.twalk.on = false;           // (a walk's replayed segment is about to be overwritten)
   t.launches = 0;
   HIPCHK(h, hipMemsetAsync(t.counters, 0, 2 * sizeof(unsigned long long), h->stream));
   if (T == 0) {                       // no step: the tangent of the final particles is the initial one (NULL: 0)
@@ -218,17 +199,14 @@ static int tape_tangent(pic_handle* h, const char* who, int K, const double* d_e
     if (host) HIPCHK(h, hipStreamSynchronize(h->stream));
     return PIC_OK;
   }
-  int rc = tangent_reserve(h, K, w);
-  if (!rc && d_kl) rc = tangent_kl_reserve(h, w);
-  if (!rc && d_moments) rc = tangent_moments_reserve(h, w);
+  int rc = tangent_reserve(h, K, who);
+  if (!rc && d_kl) rc = tangent_kl_reserve(h, who);
+  if (!rc && d_moments) rc = tangent_moments_reserve(h, who);
   if (rc) return rc;
   if (d_moments)                       // (a failed call may leave sums or max words)
-    HIPCHK(h, hipMemsetAsync(t.tmom_acc, 0, Carver::upto(t.tmom_acc, t.tmom_max + 3 * (size_t)kMaxTangents * E), h->stream));
-  TanArgs ta{};
-  tangent_parts(Carver{static_cast<char*>(t.tan_block.get())}, h, t.tan_k, ta);
-  ta.dstride = (long long)(2 * part); ta.vofs = (long long)part;
-  ta.K = K; ta.num_envs = E;
-  HIPCHK(h, hipMemsetAsync(ta.acc, 0, Carver::upto(ta.acc, ta.umax + 3 * (size_t)t.tan_k * E), h->stream));     // acc, ke, umax (a failed call may leave them)
+    HIPCHK(h, hipMemsetAsync(t.tmom.views.acc, 0, Carver::upto(t.tmom.views.acc, t.tmom.views.umax + 3 * (size_t)kMaxTangents * E), h->stream));
+  const TanArgs ta = tangent_args(h, K);
+  HIPCHK(h, hipMemsetAsync(ta.acc, 0, Carver::upto(ta.acc, ta.umax + 3 * (size_t)t.tan.k * E), h->stream));     // acc, ke, umax (a failed call may leave them)
   // host memory: the control tangents and the mesh-sized outputs go through one device block of this call
   const size_t in_n = d_ext ? (size_t)K * T * mesh : d_actions ? (size_t)K * T * E * 2 * Mact : 0;
   const size_t hist_n = d_hist ? (size_t)K * T * 3 * E : 0, em_n = d_E_mesh ? (size_t)K * T * mesh : 0;
@@ -249,16 +227,8 @@ static int tape_tangent(pic_handle* h, const char* who, int K, const double* d_e
     dkl = device_output(d_kl, PIC_HOST, p + in_n + hist_n + em_n);
     dmom = device_output(d_moments, PIC_HOST, p + in_n + hist_n + em_n + kl_n);
   }
-  // (dx_0, dv_0) of every direction into the state rows (padded to ld)
-  for (int d = 0; d < K; ++d) {
-    const void* ins[2] = {d_x0, d_v0};
-    for (int k = 0; k < 2; ++k) {
-      double* dst = ta.st + (size_t)d * 2 * part + (size_t)k * part;
-      if (ins[k]) rc = upload(h, dst, static_cast<const double*>(ins[k]) + (size_t)d * E * N, mem_kind);
-      else HIPCHK(h, hipMemsetAsync(dst, 0, part * sizeof(double), h->stream));
-      if (rc) return rc;
-    }
-  }
+  rc = tangent_state_in(h, ta, d_x0, d_v0, mem_kind);
+  if (rc) return rc;
   const AdjArgs a = adjoint_args(h);
   const WalkGeom g = walk_geom(h);
   hipLaunchKernelGGL(tangent_start_kernel, g.pgrid, dim3(ABLOCK), 0, h->stream, ta, a);
@@ -290,12 +260,7 @@ static int tape_tangent(pic_handle* h, const char* who, int K, const double* d_e
   HIPCHK(h, device_result(h, d_E_mesh, dem, em_n * sizeof(double)));
   HIPCHK(h, device_result(h, d_kl, dkl, kl_n * sizeof(double)));
   HIPCHK(h, device_result(h, d_moments, dmom, mom_n * sizeof(double)));
-  // (dx', dv') of every direction out of the state rows
-  for (int d = 0; d < K && !rc; ++d) {
-    void* outs[2] = {d_x, d_v};
-    for (int k = 0; k < 2 && !rc; ++k)
-      if (outs[k]) rc = download(h, static_cast<double*>(outs[k]) + (size_t)d * E * N, ta.st + (size_t)d * 2 * part + (size_t)k * part, mem_kind);
-  }
+  rc = tangent_state_out(h, ta, mem_kind, d_x, d_v);
   return rc ? rc : walk_finish(h, w, mem_kind);
 }
 

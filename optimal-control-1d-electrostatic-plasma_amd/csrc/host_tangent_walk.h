@@ -6,126 +6,31 @@
 // the step before left -- by the gain law on the device, by the caller between two steps, or (pic_tape_tangent_policy, DESIGN.md
 // 7q) by the MLP policy's JVP kernel on the device
 // ---------------------------------------------------------------------------------------------
-// the working rows of a walk of kc directions observing mo modes (M: the actuator's modes): the field tangent the last step left
-// dM [kc][env][Ng], its energies' tangents [kc][3][env], the observation's tangent [kc][env][2 mo], the law's dm [kc][env][2M],
-// the action tangent of the step at hand da [kc][env][2M], dG [kc][env][2M][2M], and a step's injection from host memory
-struct TanWalkViews {
-  double* dM = nullptr;
-  double* hist = nullptr;
-  double* obs = nullptr;
-  double* dm = nullptr;
-  double* da = nullptr;
-  double* dG = nullptr;
-  double* in = nullptr;
-};
-
-static size_t tanwalk_parts(Carver c, const pic_handle* h, int kc, int mo, TanWalkViews& v) {
-  const size_t E = h->cfg.num_envs, mesh = E * h->cfg.Ng, arow = E * 2 * h->act_modes, k = (size_t)kc;
-  c.take(v.dM, k * mesh);
-  c.take(v.hist, k * 3 * E);
-  c.take(v.obs, k * E * 2 * mo);
-  c.take(v.dm, k * arow);
-  c.take(v.da, k * arow);
-  c.take(v.dG, k * arow * 2 * h->act_modes);
-  c.take(v.in, k * std::max(mesh, arow));
-  return c.at;
+// the walk's working rows (host_blocks.h: tanwalk_parts) for K directions and mo modes, within budget_bytes (grown for more; on
+// failure the tape keeps what it had)
+static int tanwalk_reserve(pic_handle* h, int K, int mo, const char* who) {
+  Tape::TanWalk& w = h->tape.twalk;
+  if (w.cap_k >= K && w.cap_mo >= mo && w.block) return PIC_OK;
+  const int kc = std::max(K, w.cap_k), mc = std::max(mo, w.cap_mo);
+  const int rc = tape_reserve<TanWalkViews>(h, w.block, who, "the walk's working rows", w,
+                                            [&](Carver c, TanWalkViews& v) { return tanwalk_parts(c, block_dims(h), kc, mc, v); });
+  if (!rc) { w.cap_k = kc; w.cap_mo = mc; }
+  return rc;
 }
 
-// that block for K directions and mo modes, within budget_bytes; on failure the tape keeps what it had
-static int tanwalk_reserve(pic_handle* h, int K, int mo, const std::string& w) {
+// the working rows of a walk through the policy's steps (host_blocks.h: tanpol_parts) for K directions, likewise
+static int tanpol_reserve(pic_handle* h, int K, const char* who) {
   Tape& t = h->tape;
-  if (t.tw_cap_k >= K && t.tw_cap_mo >= mo && t.tw_block) return PIC_OK;
-  const int kc = std::max(K, t.tw_cap_k), mc = std::max(mo, t.tw_cap_mo);
-  TanWalkViews scratch;
-  const size_t bytes = tanwalk_parts(Carver{}, h, kc, mc, scratch);
-  if (t.budget > 0 && t.bytes - t.tw_bytes + bytes > (size_t)t.budget)
-    return fail(h, PIC_ENOMEM, w + ": the walk's working rows (" + std::to_string(bytes) + " bytes) would take the tape past budget_bytes (pic_tape_start)");
-  DeviceBuf<void> b;
-  const int rc = regrow(h, b, bytes, (w + ": the walk's working rows do not fit on the device").c_str());
-  if (rc) return rc;
-  if (t.tw_block) HIPCHK(h, hipStreamSynchronize(h->stream));      // queued work may still read the old block
-  t.tw_block = std::move(b);
-  t.bytes = t.bytes - t.tw_bytes + bytes;
-  t.tw_bytes = bytes;
-  t.tw_cap_k = kc; t.tw_cap_mo = mc;
-  return PIC_OK;
-}
-
-static TanWalkViews tanwalk_views(const pic_handle* h) {
-  TanWalkViews v;
-  tanwalk_parts(Carver{static_cast<char*>(h->tape.tw_block.get())}, h, h->tape.tw_cap_k, h->tape.tw_cap_mo, v);
-  return v;
-}
-
-// the working rows of a walk through the policy's steps (pic_tape_tangent_policy) for kc directions: the parameters'
-// tangent dtheta [kc][P] or [kc][env][P], the du of the step at hand [kc][env][2M], and a step's d_pre from host memory
-struct TanPolViews {
-  double* dtheta = nullptr;
-  double* du = nullptr;
-  double* pin = nullptr;
-};
-
-static size_t tanpol_parts(Carver c, const pic_handle* h, int kc, TanPolViews& v) {
-  const Tape& t = h->tape;
-  const size_t E = h->cfg.num_envs, arow = E * 2 * h->act_modes, k = (size_t)kc;
-  c.take(v.dtheta, k * (t.pshape.per_env ? E : 1) * t.pP);
-  c.take(v.du, k * arow);
-  c.take(v.pin, k * arow);
-  return c.at;
-}
-
-// that block for K directions, within budget_bytes; on failure the tape keeps what it had
-static int tanpol_reserve(pic_handle* h, int K, const std::string& w) {
-  Tape& t = h->tape;
-  if (t.tp_cap_k >= K && t.tp_block) return PIC_OK;
-  TanPolViews scratch;
-  const size_t bytes = tanpol_parts(Carver{}, h, K, scratch);
-  if (t.budget > 0 && t.bytes - t.tp_bytes + bytes > (size_t)t.budget)
-    return fail(h, PIC_ENOMEM, w + ": the policy tangent's working rows (" + std::to_string(bytes) + " bytes) would take the tape past budget_bytes (pic_tape_start)");
-  DeviceBuf<void> b;
-  const int rc = regrow(h, b, bytes, (w + ": the policy tangent's working rows do not fit on the device").c_str());
-  if (rc) return rc;
-  if (t.tp_block) HIPCHK(h, hipStreamSynchronize(h->stream));      // queued work may still read the old block
-  t.tp_block = std::move(b);
-  t.bytes = t.bytes - t.tp_bytes + bytes;
-  t.tp_bytes = bytes;
-  t.tp_cap_k = K;
-  return PIC_OK;
-}
-
-static TanPolViews tanpol_views(const pic_handle* h) {
-  TanPolViews v;
-  tanpol_parts(Carver{static_cast<char*>(h->tape.tp_block.get())}, h, h->tape.tp_cap_k, v);
-  return v;
-}
-
-// the shape of a policy into the JVP kernel's argument block (P: the doubles of one parameter vector)
-static void policy_jvp_shape(PolicyJvpArgs& a, const pic_policy& p, size_t P, double action_scale) {
-  a.env_params = p.per_env ? (long long)P : 0;
-  a.action_scale = action_scale;
-  a.n_layers = p.n_layers;
-  a.w0 = p.width[0]; a.w1 = p.width[1]; a.w2 = p.width[2]; a.w3 = p.width[3]; a.w4 = p.width[4];
-  a.activation = p.activation; a.squash = p.squash;
-}
-
-// the tangent block's views for K live directions (as pic_tape_tangent sets them)
-static TanArgs tanwalk_state(const pic_handle* h, int K) {
-  const Tape& t = h->tape;
-  const size_t part = (size_t)h->cfg.num_envs * h->ld;
-  TanArgs ta{};
-  tangent_parts(Carver{static_cast<char*>(t.tan_block.get())}, h, t.tan_k, ta);
-  ta.dstride = (long long)(2 * part); ta.vofs = (long long)part;
-  ta.K = K; ta.num_envs = h->cfg.num_envs;
-  return ta;
+  if (t.tpol.cap_k >= K && t.tpol.block) return PIC_OK;
+  const int rc = tape_reserve<TanPolViews>(h, t.tpol.block, who, "the policy tangent's working rows", t.tpol, [&](Carver c, TanPolViews& v) {
+    return tanpol_parts(c, policy_dims(h, t.policy.shape), K, v);
+  });
+  if (!rc) t.tpol.cap_k = K;
+  return rc;
 }
 
 // the modes the gain law of this tape reads (0: no law step was taped)
-static int tanwalk_law_modes(const pic_handle* h) { return h->tape.lact ? h->act_modes : 0; }
-
-static bool tanwalk_is_law(const pic_handle* h, int64_t s) {
-  const Tape& t = h->tape;
-  return s >= 0 && s < t.steps && !t.law.empty() && t.law[(size_t)s] >= 0;
-}
+static int tanwalk_law_modes(const pic_handle* h) { return h->tape.law.act ? h->act_modes : 0; }
 
 // K rows of n doubles from the walk's contiguous rows to the caller's array in mem_kind's memory, its rows `pitch` doubles apart
 static hipError_t tanwalk_rows_out(pic_handle* h, double* dst, size_t pitch, const double* src, size_t n, int K, int mem_kind) {
@@ -148,19 +53,19 @@ static hipError_t tanwalk_rows_zero(pic_handle* h, double* dst, size_t pitch, si
 // step s_next if it is a law step (pic_tangent.h: tangent_law_kernel).  Nothing to do without a law block and an observation.
 static void tanwalk_law(pic_handle* h, const TanWalkViews& v, int64_t s_next) {
   Tape& t = h->tape;
-  const int Ml = tanwalk_law_modes(h), mo = t.tw_mo, E = h->cfg.num_envs;
+  const int Ml = tanwalk_law_modes(h), mo = t.twalk.mo, E = h->cfg.num_envs;
   if (Ml == 0 && mo == 0) return;
-  const bool lawstep = tanwalk_is_law(h, s_next);
+  const bool lawstep = tape_law_step(h, s_next);
   TanLawArgs l{};
   l.dM = v.dM; l.tw = (const double*)h->tw; l.rows = h->tw_rows;
   l.obs = mo ? v.obs : nullptr;
   l.dm = v.dm;
-  l.gain = lawstep ? (const double*)t.gains[(size_t)t.law[(size_t)s_next]] : nullptr;
-  l.dgain = lawstep && t.tw_dgain ? v.dG : nullptr;
-  l.modes = lawstep ? t.lmodes + (size_t)s_next * E * 2 * Ml : nullptr;
+  l.gain = lawstep ? (const double*)t.law.gains[(size_t)t.law.step[(size_t)s_next]] : nullptr;
+  l.dgain = lawstep && t.twalk.dgain ? v.dG : nullptr;
+  l.modes = lawstep ? t.law.modes + (size_t)s_next * E * 2 * Ml : nullptr;
   l.da = v.da;
   l.Ng = h->cfg.Ng; l.M = Ml; l.Mo = mo; l.num_envs = E;
-  hipLaunchKernelGGL(tangent_law_kernel, dim3(E, t.tw_k), dim3(ABLOCK), 0, h->stream, l);
+  hipLaunchKernelGGL(tangent_law_kernel, dim3(E, t.twalk.k), dim3(ABLOCK), 0, h->stream, l);
   ++t.launches;
 }
 
@@ -187,36 +92,29 @@ static int tanwalk_open(pic_handle* h, const char* who, int K, int mo, const voi
   if (d_modes0 && mo == 0) return fail(h, PIC_EINVAL, w + ": d_modes0 needs obs_modes >= 1");
   const int64_t T = t.steps;
   bool law = false;
-  for (int64_t s = 0; s < T && !law; ++s) law = tanwalk_is_law(h, s);
+  for (int64_t s = 0; s < T && !law; ++s) law = tape_law_step(h, s);
   if (d_gain && !law) return fail(h, PIC_EINVAL, w + ": d_gain needs a step of pic_step_feedback_gain on the tape");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  t.walk = t.twalk = false;           // (a walk's replayed segment is about to be overwritten)
+  t.walk.on = t.twalk.on = false;           // (a walk's replayed segment is about to be overwritten)
   const int E = h->cfg.num_envs, Ng = h->cfg.Ng, Ml = tanwalk_law_modes(h);
-  const size_t N = h->cfg.N, part = (size_t)E * h->ld, mesh = (size_t)E * Ng, arow = (size_t)E * 2 * h->act_modes;
+  const size_t mesh = (size_t)E * Ng, arow = (size_t)E * 2 * h->act_modes;
   int rc = std::max(Ml, mo) > 0 ? ensure_twiddle(h, std::max(Ml, mo)) : PIC_OK;
-  if (!rc) rc = tangent_reserve(h, K, w);
-  if (!rc) rc = tanwalk_reserve(h, K, mo, w);
-  if (!rc && policy) rc = tanpol_reserve(h, K, w);
+  if (!rc) rc = tangent_reserve(h, K, who);
+  if (!rc) rc = tanwalk_reserve(h, K, mo, who);
+  if (!rc && policy) rc = tanpol_reserve(h, K, who);
   if (rc) return rc;
   t.launches = 0;
   HIPCHK(h, hipMemsetAsync(t.counters, 0, 2 * sizeof(unsigned long long), h->stream));
-  const TanArgs ta = tanwalk_state(h, K);
-  const TanWalkViews v = tanwalk_views(h);
-  HIPCHK(h, hipMemsetAsync(ta.acc, 0, Carver::upto(ta.acc, ta.umax + 3 * (size_t)t.tan_k * E), h->stream));     // acc, ke, umax
-  for (int d = 0; d < K; ++d) {       // (dx_0, dv_0) of every direction into the state rows (padded to ld)
-    const void* ins[2] = {d_x0, d_v0};
-    for (int k = 0; k < 2; ++k) {
-      double* dst = ta.st + (size_t)d * 2 * part + (size_t)k * part;
-      if (ins[k]) rc = upload(h, dst, static_cast<const double*>(ins[k]) + (size_t)d * E * N, mem_kind);
-      else HIPCHK(h, hipMemsetAsync(dst, 0, part * sizeof(double), h->stream));
-      if (rc) return rc;
-    }
-  }
+  const TanArgs ta = tangent_args(h, K);
+  const TanWalkViews& v = t.twalk;
+  HIPCHK(h, hipMemsetAsync(ta.acc, 0, Carver::upto(ta.acc, ta.umax + 3 * (size_t)t.tan.k * E), h->stream));     // acc, ke, umax
+  rc = tangent_state_in(h, ta, d_x0, d_v0, mem_kind);
+  if (rc) return rc;
   if (d_gain) HIPCHK(h, device_fill(h, v.dG, d_gain, (size_t)K * arow * 2 * h->act_modes * sizeof(double), mem_kind));
-  t.tw_k = K; t.tw_mo = mo; t.tw_dgain = d_gain != nullptr;
-  t.tw_pol = policy; t.tp_dparams = policy && d_params;
-  if (t.tp_dparams)
-    HIPCHK(h, device_fill(h, tanpol_views(h).dtheta, d_params, (size_t)K * (t.pshape.per_env ? E : 1) * t.pP * sizeof(double), mem_kind));
+  t.twalk.k = K; t.twalk.mo = mo; t.twalk.dgain = d_gain != nullptr;
+  t.twalk.policy = policy; t.tpol.dparams = policy && d_params;
+  if (t.tpol.dparams)
+    HIPCHK(h, device_fill(h, t.tpol.dtheta, d_params, (size_t)K * (t.policy.shape.per_env ? E : 1) * t.policy.P * sizeof(double), mem_kind));
   const AdjArgs a = adjoint_args(h);
   const WalkGeom g = walk_geom(h);
   if (Ml > 0 || mo > 0) {
@@ -240,8 +138,8 @@ static int tanwalk_open(pic_handle* h, const char* who, int K, int mo, const voi
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, tanwalk_rows_out(h, d_modes0, (size_t)E * 2 * mo, v.obs, (size_t)E * 2 * mo, K, mem_kind));
   if (d_modes0 && mem_kind == PIC_HOST) HIPCHK(h, hipStreamSynchronize(h->stream));
-  t.twalk = true;
-  t.tnext = 0;
+  t.twalk.on = true;
+  t.twalk.next = 0;
   return PIC_OK;
 }
 
@@ -265,18 +163,18 @@ struct TanWalkIO {
   size_t em_pitch = 0;
 };
 
-// step t.tnext of a live walk: first the replay of its segment if it is the segment's first step
+// step t.twalk.next of a live walk: first the replay of its segment if it is the segment's first step
 static int tanwalk_advance(pic_handle* h, const TanWalkIO& io, int mem_kind) {
   Tape& t = h->tape;
-  const int E = h->cfg.num_envs, K = t.tw_k, Mact = h->act_modes;
+  const int E = h->cfg.num_envs, K = t.twalk.k, Mact = h->act_modes;
   const size_t mesh = (size_t)E * h->cfg.Ng, arow = (size_t)E * 2 * Mact;
-  const int64_t s = t.tnext, sgi = s / t.every, i = s - sgi * t.every;
+  const int64_t s = t.twalk.next, sgi = s / t.every, i = s - sgi * t.every;
   const AdjArgs a = adjoint_args(h);
   const WalkGeom g = walk_geom(h);
   const TanGeom tg = tangent_geom(h, g, K);
-  const TanArgs ta = tanwalk_state(h, K);
-  const TanWalkViews v = tanwalk_views(h);
-  const bool lawstep = tanwalk_is_law(h, s), polstep = t.tw_pol && tape_policy_step(h, s), host = mem_kind == PIC_HOST;
+  const TanArgs ta = tangent_args(h, K);
+  const TanWalkViews& v = t.twalk;
+  const bool lawstep = tape_law_step(h, s), polstep = t.twalk.policy && tape_policy_step(h, s), host = mem_kind == PIC_HOST;
   if (i == 0)
     if (int rc = walk_replay(h, sgi, a, g)) return rc;
   if (io.lawm) HIPCHK(h, lawstep ? tanwalk_rows_out(h, io.lawm, io.act_pitch, v.dm, arow, K, mem_kind)
@@ -295,11 +193,11 @@ static int tanwalk_advance(pic_handle* h, const TanWalkIO& io, int mem_kind) {
     in = v.in;
     in_pitch = n;
   }
-  HIPCHK(h, tanwalk_rows_out(h, io.obs_in, io.obs_pitch, v.obs, (size_t)E * 2 * t.tw_mo, K, mem_kind));
+  HIPCHK(h, tanwalk_rows_out(h, io.obs_in, io.obs_pitch, v.obs, (size_t)E * 2 * t.twalk.mo, K, mem_kind));
   if (polstep) {                        // da_s = the policy's JVP at (o_s, u_s) along (dtheta, do_s, d_pre_s), + the caller's
-    const TanPolViews pv = tanpol_views(h);
-    const Tape::PolicyCopy& pc = t.pcalls[(size_t)t.pol[(size_t)s]];
-    const size_t orow = (size_t)E * 2 * t.pshape.obs_modes;
+    const TanPolViews& pv = t.tpol;
+    const Tape::Policy::Copy& pc = t.policy.calls[(size_t)t.policy.step[(size_t)s]];
+    const size_t orow = (size_t)E * 2 * t.policy.shape.obs_modes;
     const double* pre = io.pre;
     size_t pre_pitch = io.in_pitch;
     if (pre && host) {
@@ -309,22 +207,22 @@ static int tanwalk_advance(pic_handle* h, const TanWalkIO& io, int mem_kind) {
       pre_pitch = arow;
     }
     PolicyJvpArgs pa{};
-    pa.obs = t.pobs + (size_t)s * orow;
+    pa.obs = t.policy.obs + (size_t)s * orow;
     pa.obs_scale = pc.scale;
     pa.params = pc.params.get();
-    pa.pre = t.ppre + (size_t)s * arow;
-    pa.d_params = t.tp_dparams ? pv.dtheta : nullptr;
+    pa.pre = t.policy.pre + (size_t)s * arow;
+    pa.d_params = t.tpol.dparams ? pv.dtheta : nullptr;
     pa.d_obs = v.obs;
     pa.d_pre = pre;
     pa.d_act = in;
     pa.du = pv.du;
     pa.da = v.da;
-    pa.dparams_stride = (long long)((t.pshape.per_env ? (size_t)E : 1) * t.pP);
+    pa.dparams_stride = (long long)((t.policy.shape.per_env ? (size_t)E : 1) * t.policy.P);
     pa.dobs_stride = (long long)orow;
     pa.dpre_stride = (long long)pre_pitch;
     pa.dact_stride = (long long)in_pitch;
     pa.du_stride = pa.da_stride = (long long)arow;
-    policy_jvp_shape(pa, t.pshape, t.pP, pc.action_scale);
+    policy_shape(pa, t.policy.shape, t.policy.P, pc.action_scale);
     hipLaunchKernelGGL(policy_jvp_kernel, dim3(E, K), dim3(BLOCK), 0, h->stream, pa);
     ++t.launches;
     m.act = v.da; m.in_dstride = (long long)arow;
@@ -340,28 +238,15 @@ static int tanwalk_advance(pic_handle* h, const TanWalkIO& io, int mem_kind) {
   }
   if (io.aout) HIPCHK(h, m.act ? tanwalk_rows_out(h, io.aout, io.act_pitch, v.da, arow, K, mem_kind)
                                : tanwalk_rows_zero(h, io.aout, io.act_pitch, arow, K, mem_kind));
-  if (io.uout) HIPCHK(h, polstep ? tanwalk_rows_out(h, io.uout, io.act_pitch, tanpol_views(h).du, arow, K, mem_kind)
+  if (io.uout) HIPCHK(h, polstep ? tanwalk_rows_out(h, io.uout, io.act_pitch, t.tpol.du, arow, K, mem_kind)
                                  : tanwalk_rows_zero(h, io.uout, io.act_pitch, arow, K, mem_kind));
   if (int rc = tangent_step(h, ta, a, g, tg, i, m, nullptr, 0, nullptr, 0)) return rc;
   tanwalk_law(h, v, s + 1);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, tanwalk_rows_out(h, io.hist, io.hist_pitch, v.hist, (size_t)3 * E, K, mem_kind));
-  HIPCHK(h, tanwalk_rows_out(h, io.obs, (size_t)E * 2 * t.tw_mo, v.obs, (size_t)E * 2 * t.tw_mo, K, mem_kind));
+  HIPCHK(h, tanwalk_rows_out(h, io.obs, (size_t)E * 2 * t.twalk.mo, v.obs, (size_t)E * 2 * t.twalk.mo, K, mem_kind));
   HIPCHK(h, tanwalk_rows_out(h, io.em, io.em_pitch, v.dM, mesh, K, mem_kind));
-  ++t.tnext;
-  return PIC_OK;
-}
-
-// (dx, dv) of every direction out of the state rows (each may be null)
-static int tanwalk_state_out(pic_handle* h, int mem_kind, void* d_x, void* d_v) {
-  const Tape& t = h->tape;
-  const size_t part = (size_t)h->cfg.num_envs * h->ld, EN = (size_t)h->cfg.num_envs * h->cfg.N;
-  const TanArgs ta = tanwalk_state(h, t.tw_k);
-  void* outs[2] = {d_x, d_v};
-  for (int d = 0; d < t.tw_k; ++d)
-    for (int k = 0; k < 2; ++k)
-      if (outs[k])
-        if (int rc = download(h, static_cast<double*>(outs[k]) + (size_t)d * EN, ta.st + (size_t)d * 2 * part + (size_t)k * part, mem_kind)) return rc;
+  ++t.twalk.next;
   return PIC_OK;
 }
 
@@ -376,13 +261,13 @@ int pic_tape_tangent_walk_step(pic_handle* h, const double* d_ext, const double*
   const char* who = "pic_tape_tangent_walk_step";
   if (!h) return PIC_EINVAL;
   Tape& t = h->tape;
-  if (!t.on || !t.twalk) return fail(h, PIC_ESTATE, std::string(who) + ": no tangent walk in progress (pic_tape_tangent_walk_begin)");
-  if (t.tnext >= t.steps) return fail(h, PIC_ESTATE, std::string(who) + ": every step has been walked (pic_tape_tangent_walk_end)");
+  if (!t.on || !t.twalk.on) return fail(h, PIC_ESTATE, std::string(who) + ": no tangent walk in progress (pic_tape_tangent_walk_begin)");
+  if (t.twalk.next >= t.steps) return fail(h, PIC_ESTATE, std::string(who) + ": every step has been walked (pic_tape_tangent_walk_end)");
   if (int rc = check_mem_kind(h, mem_kind, who)) return rc;
   if (d_ext && d_actions) return fail(h, PIC_EINVAL, std::string(who) + ": d_ext and d_actions are both given (at most one)");
-  if (d_ext && tanwalk_is_law(h, t.tnext))
+  if (d_ext && tape_law_step(h, t.twalk.next))
     return fail(h, PIC_EINVAL, std::string(who) + ": d_ext on a step of pic_step_feedback_gain (inject through d_actions)");
-  if (d_modes && t.tw_mo == 0) return fail(h, PIC_EINVAL, std::string(who) + ": d_modes needs a walk begun with obs_modes >= 1");
+  if (d_modes && t.twalk.mo == 0) return fail(h, PIC_EINVAL, std::string(who) + ": d_modes needs a walk begun with obs_modes >= 1");
   if (int rc = check_tape_actuator(h, d_actions, "d_actions", who)) return rc;
   if (int rc = check_tape_actuator(h, d_actions_out, "d_actions_out", who)) return rc;
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
@@ -393,10 +278,10 @@ int pic_tape_tangent_walk_step(pic_handle* h, const double* d_ext, const double*
   io.obs = d_modes;
   io.aout = d_actions_out; io.act_pitch = arow;
   io.em = d_E_mesh; io.em_pitch = mesh;
-  const int64_t s = t.tnext;
+  const int64_t s = t.twalk.next;
   int rc = tanwalk_advance(h, io, mem_kind);
-  if (!rc) rc = tanwalk_state_out(h, mem_kind, d_x, d_v);
-  if (rc) { t.twalk = false; return rc; }
+  if (!rc) rc = tangent_state_out(h, tangent_args(h, t.twalk.k), mem_kind, d_x, d_v);
+  if (rc) { t.twalk.on = false; return rc; }
   if (mem_kind == PIC_HOST && (d_energies || d_modes || d_actions_out || d_x || d_v || d_E_mesh)) HIPCHK(h, hipStreamSynchronize(h->stream));
   if (step) *step = s;
   return PIC_OK;
@@ -406,13 +291,13 @@ int pic_tape_tangent_walk_end(pic_handle* h, int mem_kind, void* d_x, void* d_v)
   const char* who = "pic_tape_tangent_walk_end";
   if (!h) return PIC_EINVAL;
   Tape& t = h->tape;
-  if (!t.on || !t.twalk) return fail(h, PIC_ESTATE, std::string(who) + ": no tangent walk in progress (pic_tape_tangent_walk_begin)");
-  if (t.tnext < t.steps)
-    return fail(h, PIC_ESTATE, std::string(who) + ": " + std::to_string(t.steps - t.tnext) + " steps are not walked yet (pic_tape_tangent_walk_step)");
+  if (!t.on || !t.twalk.on) return fail(h, PIC_ESTATE, std::string(who) + ": no tangent walk in progress (pic_tape_tangent_walk_begin)");
+  if (t.twalk.next < t.steps)
+    return fail(h, PIC_ESTATE, std::string(who) + ": " + std::to_string(t.steps - t.twalk.next) + " steps are not walked yet (pic_tape_tangent_walk_step)");
   if (int rc = check_mem_kind(h, mem_kind, who)) return rc;
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  t.twalk = false;
-  const int rc = tanwalk_state_out(h, mem_kind, d_x, d_v);
+  t.twalk.on = false;
+  const int rc = tangent_state_out(h, tangent_args(h, t.twalk.k), mem_kind, d_x, d_v);
   return rc ? rc : walk_finish(h, who, mem_kind);
 }
 
@@ -437,10 +322,10 @@ int pic_tape_tangent_feedback(pic_handle* h, int K, const double* d_gain, const 
     io.aout = d_actions_out ? d_actions_out + s * arow : nullptr; io.act_pitch = T * arow;
     io.em = d_E_mesh ? d_E_mesh + s * mesh : nullptr; io.em_pitch = T * mesh;
     rc = tanwalk_advance(h, io, mem_kind);
-    if (rc) { t.twalk = false; return rc; }
+    if (rc) { t.twalk.on = false; return rc; }
   }
-  t.twalk = false;
-  rc = tanwalk_state_out(h, mem_kind, d_x, d_v);
+  t.twalk.on = false;
+  rc = tangent_state_out(h, tangent_args(h, t.twalk.k), mem_kind, d_x, d_v);
   return rc ? rc : walk_finish(h, who, mem_kind);
 }
 
@@ -451,8 +336,8 @@ int pic_tape_tangent_policy(pic_handle* h, int K, const double* d_params, const 
   if (!h) return PIC_EINVAL;
   Tape& t = h->tape;
   if (int rc = check_tape_open(h, who)) return rc;
-  if (!t.pol_block) return fail(h, PIC_EINVAL, std::string(who) + ": the tape holds no steps of pic_tape_step_policy");
-  const int mo = t.pshape.obs_modes;
+  if (!t.policy.block) return fail(h, PIC_EINVAL, std::string(who) + ": the tape holds no steps of pic_tape_step_policy");
+  const int mo = t.policy.shape.obs_modes;
   int rc = tanwalk_open(h, who, K, mo, d_x0, d_v0, nullptr, mem_kind, nullptr, true, d_params);
   if (rc) return rc;
   const size_t E = h->cfg.num_envs, mesh = E * h->cfg.Ng, arow = E * 2 * h->act_modes, orow = E * 2 * mo, T = (size_t)t.steps;
@@ -466,9 +351,9 @@ int pic_tape_tangent_policy(pic_handle* h, int K, const double* d_params, const 
     io.aout = d_actions_out ? d_actions_out + s * arow : nullptr; io.act_pitch = T * arow;
     io.em = d_E_mesh ? d_E_mesh + s * mesh : nullptr; io.em_pitch = T * mesh;
     rc = tanwalk_advance(h, io, mem_kind);
-    if (rc) { t.twalk = false; return rc; }
+    if (rc) { t.twalk.on = false; return rc; }
   }
-  t.twalk = false;
-  rc = tanwalk_state_out(h, mem_kind, d_x, d_v);
+  t.twalk.on = false;
+  rc = tangent_state_out(h, tangent_args(h, t.twalk.k), mem_kind, d_x, d_v);
   return rc ? rc : walk_finish(h, who, mem_kind);
 }

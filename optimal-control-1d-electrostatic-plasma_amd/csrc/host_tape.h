@@ -17,24 +17,6 @@ static AdjArgs adjoint_args(const pic_handle* h) {
   return a;
 }
 
-// the parts of the block of a tape of max_steps steps with a checkpoint every `every` steps
-static size_t tape_parts(Carver c, const pic_handle* h, Tape& t, int64_t max_steps, int64_t every) {
-  const size_t E = h->cfg.num_envs, part = E * h->ld, mesh = E * h->cfg.Ng, T = (size_t)max_steps, ev = (size_t)every;
-  c.take(t.ck, (size_t)(max_steps / every + 1) * 2 * part);
-  c.take(t.ext, T * mesh);
-  c.take(t.seg, (ev + 1) * 2 * part);
-  c.take(t.F, ev * 3 * mesh);
-  c.take(t.M, ev * mesh);
-  c.take(t.lam, 2 * part);
-  c.take(t.cot, T * 3 * E);
-  c.take(t.gext, T * mesh);
-  c.take(t.nu, mesh);
-  c.take(t.acc, mesh);
-  c.take(t.cmax, E + 2);                         // [env], and the two counters behind it
-  c.take(t.gact, T * E * 2 * h->act_modes);
-  return c.at;
-}
-
 // e_t of n steps of `sc` into the tape (pic_adjoint.h: tape_ext_kernel)
 static int tape_record_ext(pic_handle* h, const StepControl& sc, int n) {
   Tape& t = h->tape;
@@ -77,8 +59,8 @@ int pic_tape_start(pic_handle* h, const pic_tape_config* c) {
   if (h->mid_stage) return fail(h, PIC_ESTATE, "pic_tape_start: a staged step is in progress");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   int64_t every = c->checkpoint_every;
-  Tape scratch;                         // takes the views of the sizing passes
-  const auto tape_bytes = [&](int64_t ev) { return tape_parts(Carver{}, h, scratch, c->max_steps, ev); };
+  const BlockDims d = block_dims(h);
+  const auto tape_bytes = [&](int64_t ev) { TapeViews sized; return tape_parts(Carver{}, d, c->max_steps, ev, sized); };
   if (every == 0) {
     // about sqrt(max_steps) (checkpoints and one segment's replay weigh alike); when that exceeds budget_bytes, the interval
     // that needs the fewest bytes
@@ -92,20 +74,16 @@ int pic_tape_start(pic_handle* h, const pic_tape_config* c) {
     }
   }
   every = std::min<int64_t>(every, c->max_steps);
-  const size_t bytes = tape_bytes(every);
-  if (c->budget_bytes > 0 && bytes > (size_t)c->budget_bytes)
-    return fail(h, PIC_ENOMEM, "pic_tape_start: the tape needs " + std::to_string(bytes) + " bytes, more than budget_bytes");
-  DeviceBuf<void> block;
-  int rc = regrow(h, block, bytes, ("pic_tape_start: the tape (" + std::to_string(bytes) + " bytes) does not fit on the device").c_str());
-  if (rc) return rc;
   Tape& t = h->tape;
   t = Tape{};
-  t.block = std::move(block);
-  tape_parts(Carver{static_cast<char*>(t.block.get())}, h, t, c->max_steps, every);
-  t.counters = t.cmax + h->cfg.num_envs;
-  t.max_steps = c->max_steps; t.every = every; t.nck = c->max_steps / every + 1; t.bytes = bytes;
   t.budget = c->budget_bytes;
-  HIPCHK(h, hipMemsetAsync(t.acc, 0, Carver::upto(t.acc, t.counters + 2), h->stream));    // acc, cmax, counters
+  int rc = tape_reserve<TapeViews>(h, t.block, "pic_tape_start", "the tape", t,
+                                   [&](Carver cv, TapeViews& v) { return tape_parts(cv, d, c->max_steps, every, v); });
+  if (rc) { t = Tape{}; return rc; }
+  t.counters = t.cmax + h->cfg.num_envs;
+  t.max_steps = c->max_steps; t.every = every; t.nck = c->max_steps / every + 1;
+  hipError_t e = hipMemsetAsync(t.acc, 0, Carver::upto(t.acc, t.counters + 2), h->stream);    // acc, cmax, counters
+  if (e != hipSuccess) { t = Tape{}; return hip_tail(h, e, false, "pic_tape_start"); }
   rc = tape_checkpoint(h, 0);
   if (rc) { t = Tape{}; return rc; }
   t.on = true;
@@ -118,8 +96,7 @@ int pic_tape_stop(pic_handle* h) {
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   const hipError_t e = hipStreamSynchronize(h->stream);
   h->tape = Tape{};
-  if (e != hipSuccess) return fail(h, PIC_EHIP, std::string("pic_tape_stop: ") + hipGetErrorString(e));
-  return PIC_OK;
+  return hip_tail(h, e, false, "pic_tape_stop");
 }
 
 int pic_tape_stats(pic_handle* h, pic_tape_info* out) {
@@ -141,78 +118,59 @@ int pic_tape_stats(pic_handle* h, pic_tape_info* out) {
   return PIC_OK;
 }
 
+// step s of the open tape ran under the gain law
+static bool tape_law_step(const pic_handle* h, int64_t s) {
+  const Tape& t = h->tape;
+  return s >= 0 && s < t.steps && !t.law.step.empty() && t.law.step[(size_t)s] >= 0;
+}
+
 // the gain law's record on an open tape (allocated by its first call) and one more gain of `gbytes`, within budget_bytes
 static int tape_law_reserve(pic_handle* h, size_t gbytes) {
   Tape& t = h->tape;
-  const char* who = "pic_step_feedback_gain";
-  const size_t rows = ((size_t)t.max_steps * h->cfg.num_envs * 2 * h->act_modes * sizeof(double) + 255) & ~(size_t)255;
-  const size_t lbytes = t.law_block ? 0 : 3 * rows + (size_t)h->cfg.num_envs * h->cfg.Ng * sizeof(double);
-  if (t.budget > 0 && t.bytes + lbytes + gbytes > (size_t)t.budget)
-    return fail(h, PIC_ENOMEM, std::string(who) + ": the law's record and this call's gain would take the tape past budget_bytes (pic_tape_start)");
-  if (!t.law_block) {
-    const int rc = regrow(h, t.law_block, lbytes, (std::string(who) + ": the tape's record of the law's steps does not fit on the device").c_str());
-    if (rc) return rc;
-    char* b = static_cast<char*>(t.law_block.get());
-    t.lact = (double*)b; t.lmodes = (double*)(b + rows); t.lcot = (double*)(b + 2 * rows); t.lE = (double*)(b + 3 * rows);
-    HIPCHK(h, hipMemsetAsync(t.lmodes, 0, rows, h->stream));
-    t.law.assign((size_t)t.max_steps, -1);
-    t.bytes += lbytes;
-  }
+  const bool first = !t.law.block;
   DeviceBuf<double> g;
-  const int rc = regrow(h, g, gbytes, (std::string(who) + ": the tape's copy of the gain does not fit on the device").c_str());
+  const int rc = tape_reserve<LawViews>(h, t.law.block, "pic_step_feedback_gain", "the law's record and this call's gain", t.law,
+                                        [&](Carver c, LawViews& v) { return law_parts(c, block_dims(h), t.max_steps, v); }, &g, gbytes,
+                                        !first);
   if (rc) return rc;
-  t.gains.push_back(std::move(g));
-  t.bytes += gbytes;
+  t.law.gains.push_back(std::move(g));
+  if (first) {
+    t.law.step.assign((size_t)t.max_steps, -1);
+    HIPCHK(h, hipMemsetAsync(t.law.modes, 0, Carver::upto(t.law.modes, t.law.cot), h->stream));
+  }
   return PIC_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
 // The smoothed KL of every taped step (include/picstep.h: pic_tape_kl_*; hooks: advance, walk_reverse)
 // ---------------------------------------------------------------------------------------------
-// the parts of the KL's block on a tape of max_steps steps for a spec of the caller's
-static size_t tape_kl_parts(Carver c, const pic_handle* h, Tape& t, const pic_phase_spec* s, int64_t max_steps) {
-  const size_t E = h->cfg.num_envs, nb2 = (size_t)s->nx * s->nv, rows = (size_t)max_steps * E;
-  c.take(t.kl_feq, (s->feq_per_env ? E : 1) * nb2);
-  c.take(t.kl_acc, E * nb2);
-  c.take(t.kl_g, E * nb2);
-  c.take(t.kl_trace, rows);
-  c.take(t.kl_cot, rows);
-  return c.at;
-}
-
 int pic_tape_kl_start(pic_handle* h, const pic_phase_spec* s) {
   const char* who = "pic_tape_kl_start";
   if (!h) return PIC_EINVAL;
   Tape& t = h->tape;
   if (int rc = check_tape_open(h, who)) return rc;
-  if (t.kl) return fail(h, PIC_ESTATE, std::string(who) + ": the tape has a KL already");
+  if (t.kl.on) return fail(h, PIC_ESTATE, std::string(who) + ": the tape has a KL already");
   if (t.steps != 0) return fail(h, PIC_ESTATE, std::string(who) + ": the tape holds steps already (attach the KL before the first)");
   int rc = phase_check(h, s, PIC_HOST, who);
   if (rc) return rc;
   if (!s->feq) return fail(h, PIC_EINVAL, std::string(who) + ": needs spec->feq");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  Tape v;                               // the block's views: the tape's own once the block is filled
-  const size_t bytes = tape_kl_parts(Carver{}, h, v, s, t.max_steps);
-  if (t.budget > 0 && t.bytes + bytes > (size_t)t.budget)
-    return fail(h, PIC_ENOMEM, std::string(who) + ": the KL's memory (" + std::to_string(bytes) +
-                                   " bytes) would take the tape past budget_bytes (pic_tape_start)");
-  DeviceBuf<void> block;
-  rc = regrow(h, block, bytes, (std::string(who) + ": the KL's memory (" + std::to_string(bytes) + " bytes) does not fit on the device").c_str());
+  rc = tape_reserve<KlViews>(h, t.kl.block, who, "the KL's memory", t.kl, [&](Carver c, KlViews& v) {
+    return tape_kl_parts(c, block_dims(h), s->nx, s->nv, s->feq_per_env != 0, t.max_steps, v);
+  });
   if (rc) return rc;
-  tape_kl_parts(Carver{static_cast<char*>(block.get())}, h, v, s, t.max_steps);
   const size_t fbytes = (s->feq_per_env ? (size_t)h->cfg.num_envs : 1) * s->nx * s->nv * sizeof(double);
-  hipError_t e = hipMemcpyAsync(v.kl_feq, s->feq, fbytes, copy_kind(s->feq_mem_kind, hipMemcpyHostToDevice), h->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(v.kl_acc, 0, Carver::upto(v.kl_acc, v.kl_g), h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);          // (the caller's feq may go away behind this call)
-  if (e != hipSuccess) return fail(h, PIC_EHIP, std::string(who) + ": " + hipGetErrorString(e));
-  t.kl_block = std::move(block);
-  t.kl_feq = v.kl_feq; t.kl_acc = v.kl_acc; t.kl_g = v.kl_g; t.kl_trace = v.kl_trace; t.kl_cot = v.kl_cot;
-  t.kl_spec = *s;
-  t.kl_spec.feq = t.kl_feq;
-  t.kl_spec.feq_mem_kind = PIC_DEVICE;
-  t.kl_flag.assign((size_t)t.max_steps, 0);
-  t.bytes += bytes;
-  t.kl = true;
+  hipError_t e = hipMemcpyAsync(t.kl.feq, s->feq, fbytes, copy_kind(s->feq_mem_kind, hipMemcpyHostToDevice), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(t.kl.acc, 0, Carver::upto(t.kl.acc, t.kl.g), h->stream);
+  if (int rt = hip_tail(h, e, true, who)) {                          // (the caller's feq may go away behind this call)
+    tape_release(t, t.kl);
+    return rt;
+  }
+  t.kl.spec = *s;
+  t.kl.spec.feq = t.kl.feq;
+  t.kl.spec.feq_mem_kind = PIC_DEVICE;
+  t.kl.flag.assign((size_t)t.max_steps, 0);
+  t.kl.on = true;
   return PIC_OK;
 }
 
@@ -220,8 +178,8 @@ int pic_tape_kl_start(pic_handle* h, const pic_phase_spec* s) {
 static int tape_kl_enqueue(pic_handle* h) {
   Tape& t = h->tape;
   PhaseArgs a;
-  HIPCHK(h, phase_enqueue(h, &t.kl_spec, (const double*)h->x.get(), (const double*)h->v, t.kl_acc, t.kl_feq, nullptr, nullptr,
-                          t.kl_trace + (size_t)t.steps * h->cfg.num_envs, nullptr, a));
+  HIPCHK(h, phase_enqueue(h, &t.kl.spec, (const double*)h->x.get(), (const double*)h->v, t.kl.acc, t.kl.feq, nullptr, nullptr,
+                          t.kl.trace + (size_t)t.steps * h->cfg.num_envs, nullptr, a));
   return PIC_OK;
 }
 
@@ -229,13 +187,13 @@ static int tape_kl_enqueue(pic_handle* h) {
 static int tape_kl_reverse(pic_handle* h, int64_t s, const double* x, const double* v, double* lx, double* lv) {
   Tape& t = h->tape;
   const int E = h->cfg.num_envs;
-  const pic_phase_spec& sp = t.kl_spec;
+  const pic_phase_spec& sp = t.kl.spec;
   PhaseArgs a;
-  HIPCHK(h, phase_enqueue(h, &sp, x, v, t.kl_acc, t.kl_feq, t.kl_cot + (size_t)s * E, nullptr, nullptr, t.kl_g, a));
+  HIPCHK(h, phase_enqueue(h, &sp, x, v, t.kl.acc, t.kl.feq, t.kl.cot + (size_t)s * E, nullptr, nullptr, t.kl.g, a));
   const double norm = phase_norm(h, &sp);
   const long long ntiles = (h->cfg.N + 1) / 2;
   const dim3 grid((unsigned)((ntiles + BLOCK - 1) / BLOCK), (unsigned)E);
-  hipLaunchKernelGGL(phase_vjp_add_kernel, grid, dim3(BLOCK), 0, h->stream, x, v, (const double*)t.kl_g, a, norm * a.rdx,
+  hipLaunchKernelGGL(phase_vjp_add_kernel, grid, dim3(BLOCK), 0, h->stream, x, v, (const double*)t.kl.g, a, norm * a.rdx,
                      norm * a.rdv, lx, lv);
   t.launches += 3;
   return PIC_OK;
@@ -245,11 +203,11 @@ int pic_tape_kl(pic_handle* h, int mem_kind, double* kl) {
   const char* who = "pic_tape_kl";
   if (!h) return PIC_EINVAL;
   Tape& t = h->tape;
-  if (!t.on || !t.kl) return fail(h, PIC_ESTATE, std::string(who) + ": no tape with a KL is open (pic_tape_kl_start)");
+  if (!t.on || !t.kl.on) return fail(h, PIC_ESTATE, std::string(who) + ": no tape with a KL is open (pic_tape_kl_start)");
   if ((mem_kind != PIC_HOST && mem_kind != PIC_DEVICE) || !kl) return fail(h, PIC_EINVAL, std::string(who) + ": bad mem_kind or null kl");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   if (t.steps == 0) return PIC_OK;
-  HIPCHK(h, hipMemcpyAsync(kl, t.kl_trace, (size_t)t.steps * h->cfg.num_envs * sizeof(double), copy_kind(mem_kind, hipMemcpyDeviceToHost),
+  HIPCHK(h, hipMemcpyAsync(kl, t.kl.trace, (size_t)t.steps * h->cfg.num_envs * sizeof(double), copy_kind(mem_kind, hipMemcpyDeviceToHost),
                            h->stream));
   if (mem_kind == PIC_HOST) HIPCHK(h, hipStreamSynchronize(h->stream));
   return PIC_OK;
@@ -259,21 +217,21 @@ int pic_tape_kl_cot(pic_handle* h, const double* cot_kl, int mem_kind, int64_t f
   const char* who = "pic_tape_kl_cot";
   if (!h) return PIC_EINVAL;
   Tape& t = h->tape;
-  if (!t.on || !t.kl) return fail(h, PIC_ESTATE, std::string(who) + ": no tape with a KL is open (pic_tape_kl_start)");
+  if (!t.on || !t.kl.on) return fail(h, PIC_ESTATE, std::string(who) + ": no tape with a KL is open (pic_tape_kl_start)");
   if (int rc = check_mem_kind(h, mem_kind, who)) return rc;
   if (first_step < 0 || nsteps < 0 || first_step > t.steps || nsteps > t.steps - first_step)
     return fail(h, PIC_EINVAL, std::string(who) + ": rows outside the " + std::to_string(t.steps) + " steps taped so far");
   if (nsteps == 0) return PIC_OK;
-  if (t.walk && first_step + nsteps - 1 > t.wnext)
+  if (t.walk.on && first_step + nsteps - 1 > t.walk.next)
     return fail(h, PIC_ESTATE, std::string(who) + ": the walk in progress has reversed step " + std::to_string(first_step + nsteps - 1) +
                                    " already");
   if (cot_kl) {
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
     const size_t E = h->cfg.num_envs;
-    HIPCHK(h, hipMemcpyAsync(t.kl_cot + (size_t)first_step * E, cot_kl, (size_t)nsteps * E * sizeof(double),
+    HIPCHK(h, hipMemcpyAsync(t.kl.cot + (size_t)first_step * E, cot_kl, (size_t)nsteps * E * sizeof(double),
                              copy_kind(mem_kind, hipMemcpyHostToDevice), h->stream));
   }
-  std::fill(t.kl_flag.begin() + first_step, t.kl_flag.begin() + first_step + nsteps, cot_kl ? 1 : 0);
+  std::fill(t.kl.flag.begin() + first_step, t.kl.flag.begin() + first_step + nsteps, cot_kl ? 1 : 0);
   return PIC_OK;
 }
 
@@ -288,18 +246,18 @@ static void tape_solve(pic_handle* h, const double* ext, double* E_out) {
 }
 
 // E-bar of the field step s started from (pic_adjoint.h: law_adjoint_kernel): the gain law's term if step s is a law step
-// (e-bar_s must be complete), plus cot_m [env][2 mc] on its modes (either may be absent).  Returns where it went (t.lE, or t.wE
+// (e-bar_s must be complete), plus cot_m [env][2 mc] on its modes (either may be absent).  Returns where it went (t.law.E, or t.walk.E
 // without a law block), or null: nothing to add.
 static const double* tape_mode_cot(pic_handle* h, int64_t s, const double* cot_m, int mc) {
   Tape& t = h->tape;
-  const bool lawstep = s >= 0 && s < t.steps && !t.law.empty() && t.law[(size_t)s] >= 0;
+  const bool lawstep = tape_law_step(h, s);
   if (!lawstep && !cot_m) return nullptr;
-  double* Ebar = t.lE ? t.lE : t.wE;
+  double* Ebar = t.law.E ? t.law.E : t.walk.E;
   const int E = h->cfg.num_envs, Ng = h->cfg.Ng, M = h->act_modes;
   const int mg = lawstep ? M : 0, R = std::max(mg, cot_m ? mc : 0);
   hipLaunchKernelGGL(law_adjoint_kernel, dim3(E), dim3(ABLOCK), (size_t)2 * (mg + R) * sizeof(double), h->stream,
                      lawstep ? (const double*)(t.gext + (size_t)s * E * Ng) : nullptr, (const double*)h->basis,
-                     lawstep ? (const double*)t.gains[(size_t)t.law[(size_t)s]] : nullptr, cot_m, (const double*)h->tw, h->tw_rows,
+                     lawstep ? (const double*)t.law.gains[(size_t)t.law.step[(size_t)s]] : nullptr, cot_m, (const double*)h->tw, h->tw_rows,
                      Ebar, Ng, M, cot_m ? mc : 0);
   ++t.launches;
   return Ebar;
@@ -322,13 +280,13 @@ static WalkGeom walk_geom(const pic_handle* h) {
 static int walk_open(pic_handle* h, int mo) {
   Tape& t = h->tape;
   const size_t part = (size_t)h->cfg.num_envs * h->ld, mesh = (size_t)h->cfg.num_envs * h->cfg.Ng;
-  t.walk = t.twalk = false;          // (a forward walk replays into the same segment buffer)
-  t.pvalid = false;
-  const int mp = t.pol_block ? t.pshape.obs_modes : 0;      // a policy step's m-bar goes the way of a walk's mode cotangent
+  t.walk.on = t.twalk.on = false;          // (a forward walk replays into the same segment buffer)
+  t.policy.valid = false;
+  const int mp = t.policy.block ? t.policy.shape.obs_modes : 0;      // a policy step's m-bar goes the way of a walk's mode cotangent
   if (mo > 0 || mp > 0) {
     const int rc = ensure_twiddle(h, std::max(mo, mp));
     if (rc) return rc;
-    if (!t.lE && !t.wE && alloc(t.wE, mesh * sizeof(double)) != hipSuccess) {
+    if (!t.law.E && !t.walk.E && alloc(t.walk.E, mesh * sizeof(double)) != hipSuccess) {
       (void)hipGetLastError();
       return fail(h, PIC_ENOMEM, "pic_tape_walk_begin: the walk's mode cotangent does not fit on the device");
     }
@@ -337,12 +295,12 @@ static int walk_open(pic_handle* h, int mo) {
   HIPCHK(h, hipMemsetAsync(t.counters, 0, 2 * sizeof(unsigned long long), h->stream));
   if (t.steps > 0) HIPCHK(h, hipMemsetAsync(t.gext, 0, (size_t)t.steps * mesh * sizeof(double), h->stream));
   HIPCHK(h, hipMemsetAsync(t.lam, 0, 2 * part * sizeof(double), h->stream));
-  if (t.pol_block) HIPCHK(h, hipMemsetAsync(t.pgobs, 0, Carver::upto(t.pgobs, t.pcobs), h->stream));    // o-bar, u-bar, a-bar
-  t.pfirst = true;
-  t.pcot_obs = t.pcot_act = false;
-  t.walk = true;
-  t.wnext = t.steps - 1;
-  t.wmo = mo;
+  if (t.policy.block) HIPCHK(h, hipMemsetAsync(t.policy.gobs, 0, Carver::upto(t.policy.gobs, t.policy.cobs), h->stream));    // o-bar, u-bar, a-bar
+  t.policy.first = true;
+  t.policy.cot_obs = t.policy.cot_act = false;
+  t.walk.on = true;
+  t.walk.next = t.steps - 1;
+  t.walk.mo = mo;
   return PIC_OK;
 }
 
@@ -394,54 +352,50 @@ struct WalkCot {
 // tape_mode_cot sends it through J^T as it sends a walk's.
 static bool tape_policy_step(const pic_handle* h, int64_t s) {
   const Tape& t = h->tape;
-  return s >= 0 && s < t.steps && !t.pol.empty() && t.pol[(size_t)s] >= 0;
+  return s >= 0 && s < t.steps && !t.policy.step.empty() && t.policy.step[(size_t)s] >= 0;
 }
 
 static int tape_policy_reverse(pic_handle* h, int64_t s, WalkCot& c) {
   Tape& t = h->tape;
-  const int E = h->cfg.num_envs, Ng = h->cfg.Ng, M = h->act_modes, Mo = t.pshape.obs_modes;
+  const int E = h->cfg.num_envs, Ng = h->cfg.Ng, M = h->act_modes, Mo = t.policy.shape.obs_modes;
   if (c.modes && c.mc != Mo)
     return fail(h, PIC_EINVAL, "pic_tape_walk: a mode cotangent on the field a policy step reads needs obs_modes = the policy's " +
                                    std::to_string(Mo) + " (pic_tape_walk_begin)");
   const size_t arow = (size_t)E * 2 * M, orow = (size_t)E * 2 * Mo;
-  const Tape::PolicyCopy& pc = t.pcalls[(size_t)t.pol[(size_t)s]];
-  const pic_policy& p = t.pshape;
+  const Tape::Policy::Copy& pc = t.policy.calls[(size_t)t.policy.step[(size_t)s]];
   PolicyVjpArgs a{};
-  a.obs = t.pobs + (size_t)s * orow;
+  a.obs = t.policy.obs + (size_t)s * orow;
   a.obs_scale = pc.scale;
   a.params = pc.params.get();
-  a.pre = t.ppre + (size_t)s * arow;
+  a.pre = t.policy.pre + (size_t)s * arow;
   a.gext = t.gext + (size_t)s * E * Ng;
   a.basis = h->basis;
   a.Ng = Ng;
-  a.cot_a2 = t.pcot_act ? t.pcact + (size_t)s * arow : nullptr;
-  a.cot_obs = c.modes ? c.modes : (t.pcot_obs ? t.pcobs + (size_t)s * orow : nullptr);
-  a.g_params = t.pgE;
-  a.g_obs = t.pgobs + (size_t)s * orow;
-  a.g_pre = t.pgpre + (size_t)s * arow;
-  a.g_act = t.pgact + (size_t)s * arow;
-  a.mbar = t.pmbar;
-  a.env_params = p.per_env ? (long long)t.pP : 0;
-  a.P = (long long)t.pP;
-  a.action_scale = pc.action_scale;
-  a.first = t.pfirst ? 1 : 0;
-  a.Mo = Mo; a.n_layers = p.n_layers;
-  a.w0 = p.width[0]; a.w1 = p.width[1]; a.w2 = p.width[2]; a.w3 = p.width[3]; a.w4 = p.width[4];
-  a.activation = p.activation; a.squash = p.squash;
+  a.cot_a2 = t.policy.cot_act ? t.policy.cact + (size_t)s * arow : nullptr;
+  a.cot_obs = c.modes ? c.modes : (t.policy.cot_obs ? t.policy.cobs + (size_t)s * orow : nullptr);
+  a.g_params = t.policy.gE;
+  a.g_obs = t.policy.gobs + (size_t)s * orow;
+  a.g_pre = t.policy.gpre + (size_t)s * arow;
+  a.g_act = t.policy.gact + (size_t)s * arow;
+  a.mbar = t.policy.mbar;
+  a.P = (long long)t.policy.P;
+  a.first = t.policy.first ? 1 : 0;
+  a.Mo = Mo;
+  policy_shape(a, t.policy.shape, t.policy.P, pc.action_scale);
   hipLaunchKernelGGL(policy_vjp_kernel, dim3(E), dim3(BLOCK), 0, h->stream, a);
-  t.pfirst = false;
+  t.policy.first = false;
   ++t.launches;
-  c.modes = t.pmbar;
+  c.modes = t.policy.mbar;
   c.mc = Mo;
   return PIC_OK;
 }
 
-// reverse step t.wnext (its energy cotangents in t.cot's row): first the replay of its segment if it is the segment's last step
+// reverse step t.walk.next (its energy cotangents in t.cot's row): first the replay of its segment if it is the segment's last step
 static int walk_reverse(pic_handle* h, const WalkCot& given, const AdjArgs& a, const WalkGeom& g) {
   Tape& t = h->tape;
   const int E = h->cfg.num_envs;
   const size_t part = (size_t)E * h->ld, mesh = (size_t)E * h->cfg.Ng;
-  const int64_t s = t.wnext, sgi = s / t.every, t0 = sgi * t.every, i = s - t0;
+  const int64_t s = t.walk.next, sgi = s / t.every, t0 = sgi * t.every, i = s - t0;
   WalkCot c = given;
   if (tape_policy_step(h, s + 1)) {         // the policy of step s + 1 read the field step s left (nothing is enqueued if it fails)
     const int rc = tape_policy_reverse(h, s + 1, c);
@@ -457,7 +411,7 @@ static int walk_reverse(pic_handle* h, const WalkCot& given, const AdjArgs& a, c
   const AdjStep st{x, x + part, t.F + (size_t)i * 3 * mesh, (long long)mesh};
   const double* cot = t.cot + (size_t)s * 3 * E;
   double* ge = t.gext + (size_t)s * mesh;
-  if (t.kl && t.kl_flag[(size_t)s]) {       // lambda_x' += k-bar_s dKL~/dx', lambda_v' += k-bar_s dKL~/dv' 
+  if (t.kl.on && t.kl.flag[(size_t)s]) {       // lambda_x' += k-bar_s dKL~/dx', lambda_v' += k-bar_s dKL~/dv' 
     const double* xn = t.seg + (size_t)(i + 1) * 2 * part;
     const int rc = tape_kl_reverse(h, s, xn, xn + part, lx, lv);
     if (rc) return rc;
@@ -481,7 +435,7 @@ static int walk_reverse(pic_handle* h, const WalkCot& given, const AdjArgs& a, c
   hipLaunchKernelGGL(adjoint_mesh_kernel, g.mgrid, dim3(SBLOCK), g.mesh_lds, h->stream, t.acc, t.cmax, nullptr, nullptr, ge, t.nu, a, E, nullptr);
   hipLaunchKernelGGL(adjoint_pass_kernel<0>, g.pgrid, dim3(ABLOCK), 0, h->stream, st, t.nu, nullptr, lx, lv, t.cmax, a, E, nullptr, nullptr, 0ll);
   t.launches += 11;
-  --t.wnext;
+  --t.walk.next;
   HIPCHK(h, hipGetLastError());
   return PIC_OK;
 }
@@ -495,7 +449,7 @@ static int walk_close(pic_handle* h, const WalkCot& given, const AdjArgs& a, con
   WalkCot c = given;
   if (tape_policy_step(h, 0)) {             // a first step under a policy read the field the tape started from
     const int rc = tape_policy_reverse(h, 0, c);
-    if (rc) { t.walk = false; return rc; }
+    if (rc) { t.walk.on = false; return rc; }
   }
   const double* Ebar = t.steps > 0 ? tape_mode_cot(h, 0, c.modes, c.mc) : nullptr;
   const bool field = Ebar != nullptr;
@@ -510,8 +464,8 @@ static int walk_close(pic_handle* h, const WalkCot& given, const AdjArgs& a, con
     ++t.launches;
   }
   if (tape_moments_row(h, -1)) tape_moments_reverse(h, -1, t.ck, t.ck + part, t.lam, t.lam + part);   // m-bar at the tape start
-  t.walk = false;
-  t.pvalid = t.pol_block && !t.pfirst;
+  t.walk.on = false;
+  t.policy.valid = t.policy.block && !t.policy.first;
   HIPCHK(h, hipGetLastError());
   return PIC_OK;
 }
@@ -560,17 +514,17 @@ struct PolicyBackward {
 // ascending order
 static int tape_policy_grad_out(pic_handle* h, int mem_kind, double* g_params) {
   Tape& t = h->tape;
-  const size_t P = t.pP, E = (size_t)h->cfg.num_envs;
+  const size_t P = t.policy.P, E = (size_t)h->cfg.num_envs;
   const hipMemcpyKind outk = copy_kind(mem_kind, hipMemcpyDeviceToHost);
-  if (t.pshape.per_env) {
-    HIPCHK(h, hipMemcpyAsync(g_params, t.pgE, E * P * sizeof(double), outk, h->stream));
+  if (t.policy.shape.per_env) {
+    HIPCHK(h, hipMemcpyAsync(g_params, t.policy.gE, E * P * sizeof(double), outk, h->stream));
     return PIC_OK;
   }
-  hipLaunchKernelGGL(policy_grad_reduce_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->stream, (const double*)t.pgE, t.pg,
+  hipLaunchKernelGGL(policy_grad_reduce_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->stream, (const double*)t.policy.gE, t.policy.g,
                      (long long)P, (int)E);
   ++t.launches;
   HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipMemcpyAsync(g_params, t.pg, P * sizeof(double), outk, h->stream));
+  HIPCHK(h, hipMemcpyAsync(g_params, t.policy.g, P * sizeof(double), outk, h->stream));
   return PIC_OK;
 }
 
@@ -578,16 +532,16 @@ static int tape_policy_grad_out(pic_handle* h, int mem_kind, double* g_params) {
 static int tape_policy_out(pic_handle* h, int mem_kind, const PolicyBackward& pb) {
   Tape& t = h->tape;
   const size_t E = (size_t)h->cfg.num_envs, T = (size_t)t.steps, D = sizeof(double);
-  const size_t arow = E * 2 * h->act_modes, orow = E * 2 * t.pshape.obs_modes;
+  const size_t arow = E * 2 * h->act_modes, orow = E * 2 * t.policy.shape.obs_modes;
   const hipMemcpyKind outk = copy_kind(mem_kind, hipMemcpyDeviceToHost);
   if (pb.g_params) {
     const int rc = tape_policy_grad_out(h, mem_kind, pb.g_params);
     if (rc) return rc;
   }
   if (T == 0) return PIC_OK;
-  if (pb.g_pre) HIPCHK(h, hipMemcpyAsync(pb.g_pre, t.pgpre, T * arow * D, outk, h->stream));
-  if (pb.g_obs) HIPCHK(h, hipMemcpyAsync(pb.g_obs, t.pgobs, T * orow * D, outk, h->stream));
-  if (pb.g_actions) HIPCHK(h, hipMemcpyAsync(pb.g_actions, t.pgact, T * arow * D, outk, h->stream));
+  if (pb.g_pre) HIPCHK(h, hipMemcpyAsync(pb.g_pre, t.policy.gpre, T * arow * D, outk, h->stream));
+  if (pb.g_obs) HIPCHK(h, hipMemcpyAsync(pb.g_obs, t.policy.gobs, T * orow * D, outk, h->stream));
+  if (pb.g_actions) HIPCHK(h, hipMemcpyAsync(pb.g_actions, t.policy.gact, T * arow * D, outk, h->stream));
   return PIC_OK;
 }
 
@@ -612,39 +566,39 @@ static int tape_backward(pic_handle* h, const char* who, const double* cot_hist,
   if (T > 0) HIPCHK(h, device_fill(h, t.cot, cot_hist, (size_t)T * 3 * E * sizeof(double), mem_kind));
   if (cot_x) rc = upload(h, t.lam, cot_x, mem_kind);
   if (!rc && cot_v) rc = upload(h, t.lam + (size_t)E * h->ld, cot_v, mem_kind);
-  if (rc) { t.walk = false; return rc; }
+  if (rc) { t.walk.on = false; return rc; }
   if (pb && T > 0) {                  // the direct cotangents of the policy steps, read row by row by the walk
-    const size_t arow = (size_t)E * 2 * h->act_modes, orow = (size_t)E * 2 * t.pshape.obs_modes;
+    const size_t arow = (size_t)E * 2 * h->act_modes, orow = (size_t)E * 2 * t.policy.shape.obs_modes;
     if (pb->cot_actions) {
-      HIPCHK(h, device_fill(h, t.pcact, pb->cot_actions, (size_t)T * arow * sizeof(double), mem_kind));
-      t.pcot_act = true;
+      HIPCHK(h, device_fill(h, t.policy.cact, pb->cot_actions, (size_t)T * arow * sizeof(double), mem_kind));
+      t.policy.cot_act = true;
     }
     if (pb->cot_obs) {
-      HIPCHK(h, device_fill(h, t.pcobs, pb->cot_obs, (size_t)T * orow * sizeof(double), mem_kind));
-      t.pcot_obs = true;
+      HIPCHK(h, device_fill(h, t.policy.cobs, pb->cot_obs, (size_t)T * orow * sizeof(double), mem_kind));
+      t.policy.cot_obs = true;
     }
   }
   // steps of the gain law: the action of step s + 1 depends on the field step s left, so the refresh adjoint of
   // step s also carries E-bar_{s+1} = J^T (G^T a-bar_{s+1} + m-bar_{s+1}); E-bar_0 reaches x_0 through the field at the start
-  const bool law = !t.law.empty();
+  const bool law = !t.law.step.empty();
   const int M = h->act_modes;
   const size_t lrow = (size_t)E * 2 * M;
-  if (law && T > 0) HIPCHK(h, device_fill(h, t.lcot, cot_modes, (size_t)T * lrow * sizeof(double), mem_kind));
+  if (law && T > 0) HIPCHK(h, device_fill(h, t.law.cot, cot_modes, (size_t)T * lrow * sizeof(double), mem_kind));
   // the law's m-bar of step s + 1 is a cotangent on the field step s left: the walk's mode cotangent of step s (law steps only)
   auto law_cot = [&](int64_t s) {
     WalkCot c;
-    if (law && s < T && t.law[(size_t)s] >= 0) { c.modes = t.lcot + (size_t)s * lrow; c.mc = M; }
+    if (tape_law_step(h, s)) { c.modes = t.law.cot + (size_t)s * lrow; c.mc = M; }
     return c;
   };
-  while (t.wnext >= 0) {
-    rc = walk_reverse(h, law_cot(t.wnext + 1), a, g);
-    if (rc) { t.walk = false; return rc; }
+  while (t.walk.next >= 0) {
+    rc = walk_reverse(h, law_cot(t.walk.next + 1), a, g);
+    if (rc) { t.walk.on = false; return rc; }
   }
   rc = walk_close(h, law_cot(0), a, g);
   if (rc) return rc;
   if (g_ext && T > 0) HIPCHK(h, hipMemcpyAsync(g_ext, t.gext, (size_t)T * mesh * sizeof(double), outk, h->stream));
   if (modes_out && T > 0) {
-    if (law) HIPCHK(h, hipMemcpyAsync(modes_out, t.lmodes, (size_t)T * lrow * sizeof(double), outk, h->stream));
+    if (law) HIPCHK(h, hipMemcpyAsync(modes_out, t.law.modes, (size_t)T * lrow * sizeof(double), outk, h->stream));
     else if (mem_kind == PIC_HOST) std::memset(modes_out, 0, (size_t)T * lrow * sizeof(double));
     else HIPCHK(h, hipMemsetAsync(modes_out, 0, (size_t)T * lrow * sizeof(double), h->stream));
   }
@@ -660,7 +614,7 @@ int pic_tape_backward_policy(pic_handle* h, const double* cot_hist, const void* 
   const char* who = "pic_tape_backward_policy";
   if (!h) return PIC_EINVAL;
   if (int rc = check_tape_open(h, who)) return rc;
-  if (!h->tape.pol_block) return fail(h, PIC_ESTATE, std::string(who) + ": the tape holds no steps of pic_tape_step_policy");
+  if (!h->tape.policy.block) return fail(h, PIC_ESTATE, std::string(who) + ": the tape holds no steps of pic_tape_step_policy");
   const PolicyBackward pb{cot_actions, cot_obs, g_params, g_pre, g_obs, g_actions};
   return tape_backward(h, who, cot_hist, cot_x, cot_v, nullptr, mem_kind, nullptr, nullptr, g_x0, g_v0, nullptr, &pb);
 }
@@ -672,8 +626,8 @@ int pic_tape_policy_grad(pic_handle* h, int mem_kind, double* g_params) {
   if (int rc = check_mem_kind(h, mem_kind, who)) return rc;
   if (!g_params) return fail(h, PIC_EINVAL, std::string(who) + ": null g_params");
   Tape& t = h->tape;
-  if (!t.pol_block) return fail(h, PIC_ESTATE, std::string(who) + ": the tape holds no steps of pic_tape_step_policy");
-  if (!t.pvalid)
+  if (!t.policy.block) return fail(h, PIC_ESTATE, std::string(who) + ": the tape holds no steps of pic_tape_step_policy");
+  if (!t.policy.valid)
     return fail(h, PIC_ESTATE, std::string(who) + ": no finished reverse pass over the steps taped so far (pic_tape_walk_end or a backward first)");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   const int rc = tape_policy_grad_out(h, mem_kind, g_params);
@@ -713,20 +667,20 @@ static int walk_cot(pic_handle* h, const void* cot_x, const void* cot_v, const d
   c->x = static_cast<const double*>(cot_x);
   c->v = static_cast<const double*>(cot_v);
   c->modes = cot_modes;
-  c->mc = t.wmo;
+  c->mc = t.walk.mo;
   c->cld = (long long)N;
   if (!host || !(cot_x || cot_v || cot_modes)) return PIC_OK;
-  const size_t bytes = (2 * E * N + E * 2 * t.wmo) * sizeof(double);
-  if (bytes > t.wstage_bytes) {
-    t.wstage_bytes = 0;
-    const int rc = regrow(h, t.wstage, bytes, "pic_tape_walk: the staging of host cotangents does not fit on the device");
+  const size_t bytes = (2 * E * N + E * 2 * t.walk.mo) * sizeof(double);
+  if (bytes > t.walk.stage_bytes) {
+    t.walk.stage_bytes = 0;
+    const int rc = regrow(h, t.walk.stage, bytes, "pic_tape_walk: the staging of host cotangents does not fit on the device");
     if (rc) return rc;
-    t.wstage_bytes = bytes;
+    t.walk.stage_bytes = bytes;
   }
-  double* st = t.wstage;
+  double* st = t.walk.stage;
   HIPCHK(h, device_input(h, c->x, PIC_HOST, E * N * sizeof(double), st, &c->x));
   HIPCHK(h, device_input(h, c->v, PIC_HOST, E * N * sizeof(double), st + E * N, &c->v));
-  HIPCHK(h, device_input(h, c->modes, PIC_HOST, E * 2 * t.wmo * sizeof(double), st + 2 * E * N, &c->modes));
+  HIPCHK(h, device_input(h, c->modes, PIC_HOST, E * 2 * t.walk.mo * sizeof(double), st + 2 * E * N, &c->modes));
   return PIC_OK;
 }
 
@@ -734,13 +688,13 @@ int pic_tape_walk_step(pic_handle* h, const double* cot_energies, const void* co
                        int mem_kind, double* g_ext, double* g_actions, int64_t* step) {
   if (!h) return PIC_EINVAL;
   Tape& t = h->tape;
-  if (!t.on || !t.walk) return fail(h, PIC_ESTATE, "pic_tape_walk_step: no walk in progress (pic_tape_walk_begin)");
-  if (t.wnext < 0) return fail(h, PIC_ESTATE, "pic_tape_walk_step: every step has been walked (pic_tape_walk_end)");
+  if (!t.on || !t.walk.on) return fail(h, PIC_ESTATE, "pic_tape_walk_step: no walk in progress (pic_tape_walk_begin)");
+  if (t.walk.next < 0) return fail(h, PIC_ESTATE, "pic_tape_walk_step: every step has been walked (pic_tape_walk_end)");
   if (int rc = check_mem_kind(h, mem_kind, "pic_tape_walk_step")) return rc;
   if (int rc = check_tape_actuator(h, g_actions, "g_actions", "pic_tape_walk_step")) return rc;
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   const int E = h->cfg.num_envs;
-  const int64_t s = t.wnext;
+  const int64_t s = t.walk.next;
   const size_t mesh = (size_t)E * h->cfg.Ng;
   const bool host = mem_kind == PIC_HOST;
   double* cot = t.cot + (size_t)s * 3 * E;
@@ -749,7 +703,7 @@ int pic_tape_walk_step(pic_handle* h, const double* cot_energies, const void* co
   int rc = walk_cot(h, cot_x, cot_v, cot_modes, host, &c);
   if (rc) return rc;
   rc = walk_reverse(h, c, adjoint_args(h), walk_geom(h));
-  if (rc) { t.walk = false; return rc; }
+  if (rc) { t.walk.on = false; return rc; }
   if (g_ext) HIPCHK(h, hipMemcpyAsync(g_ext, t.gext + (size_t)s * mesh, mesh * sizeof(double), copy_kind(mem_kind, hipMemcpyDeviceToHost), h->stream));
   if (g_actions) rc = tape_actions_out(h, s, 1, mem_kind, g_actions);      // a-bar_s = B^T e-bar_s of this step alone
   if (rc) return rc;
@@ -762,14 +716,14 @@ int pic_tape_walk_end(pic_handle* h, const void* cot_x0, const void* cot_v0, con
                       void* g_v0) {
   if (!h) return PIC_EINVAL;
   Tape& t = h->tape;
-  if (!t.on || !t.walk) return fail(h, PIC_ESTATE, "pic_tape_walk_end: no walk in progress (pic_tape_walk_begin)");
-  if (t.wnext >= 0)
-    return fail(h, PIC_ESTATE, "pic_tape_walk_end: " + std::to_string(t.wnext + 1) + " steps are not walked yet (pic_tape_walk_step)");
+  if (!t.on || !t.walk.on) return fail(h, PIC_ESTATE, "pic_tape_walk_end: no walk in progress (pic_tape_walk_begin)");
+  if (t.walk.next >= 0)
+    return fail(h, PIC_ESTATE, "pic_tape_walk_end: " + std::to_string(t.walk.next + 1) + " steps are not walked yet (pic_tape_walk_step)");
   if (int rc = check_mem_kind(h, mem_kind, "pic_tape_walk_end")) return rc;
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   WalkCot c;
   int rc = walk_cot(h, cot_x0, cot_v0, cot_modes0, mem_kind == PIC_HOST, &c);
-  if (rc) { t.walk = false; return rc; }
+  if (rc) { t.walk.on = false; return rc; }
   rc = walk_close(h, c, adjoint_args(h), walk_geom(h));
   return rc ? rc : walk_finish(h, "pic_tape_walk_end", mem_kind, g_x0, g_v0);
 }

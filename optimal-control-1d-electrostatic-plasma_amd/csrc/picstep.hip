@@ -33,7 +33,8 @@
 //
 // Files: pic_limits.h (launch constants), pic_device.h (particle formats, per-particle helpers, scans), pic_sweep.h (push sweeps),
 // pic_solve.h (field solve), pic_aux.h (kernels off the step path); host_plan.h (pic_create's argument checks and the launch plan:
-// no HIP, pinned on a CPU by tests/test_plan_cpu.py), host_place.h (the search for a placement of x and v); this file holds the
+// no HIP, pinned on a CPU by tests/test_plan_cpu.py), host_blocks.h (the layout of every carved device block: no HIP either, pinned by
+// tests/test_blocks_cpu.py), host_place.h (the search for a placement of x and v); this file holds the
 // handle, the launch schedule and the C ABI, but for the host side of the differentiable rollouts: host_diff.h, host_phase.h,
 // host_tape.h, host_tangent.h, host_tangent_walk.h.  pic_copy.h, host_copy.h and host_copy_map.h: copies of whole environments (pic_copy_envs).
 // pic_policy.h and host_policy.h: the MLP policy of pic_policy_eval and pic_step_policy.
@@ -61,6 +62,7 @@
 
 #include "host_plan.h"
 #include "host_copy_map.h"
+#include "host_blocks.h"
 
 #include "pic_device.h"
 #include "pic_sweep.h"
@@ -170,120 +172,109 @@ struct Recorder {
   long long tiles_per_wg = 1;
 };
 
+// One carved device block of the tape and the bytes it counts in Tape::bytes; host_diff.h: tape_reserve is the one place that
+// allocates, carves and counts one
+struct TapeBlock {
+  DeviceBuf<void> mem;
+  size_t bytes = 0;
+  explicit operator bool() const { return mem.get() != nullptr; }
+};
+
 // The tape of a differentiable rollout (pic_tape_*, pic_adjoint.h).  One device block holds the checkpoints
 // (x, v every `every` steps, the first at pic_tape_start), every step's external field and all the backward's working memory,
-// (a-bar included), so that pic_tape_backward allocates nothing.  ck .. gact are views into `block`, lact .. lE into `law_block`.
-struct Tape {
+// (a-bar included), so that pic_tape_backward allocates nothing: TapeViews (host_blocks.h) are the views into it.  Everything
+// attached to a tape later is a member struct: its block, the views into it (its base, laid out in host_blocks.h) and its state.
+// Every block counts in `bytes`.
+struct Tape : TapeViews {
   bool on = false;
   int64_t max_steps = 0, every = 1, steps = 0, nck = 0;
   size_t bytes = 0;
-  DeviceBuf<void> block;
-  double* ck = nullptr;               // [nck][2][env][ld] checkpoints: (x, v) before step c * every
-  double* ext = nullptr;              // [max_steps][env][Ng] e_t
-  double* seg = nullptr;              // [every + 1][2][env][ld] one segment's replayed states
-  double* F = nullptr;                // [every][3][env][Ng] its sub-stage fields
-  double* M = nullptr;                // [every][env][Ng] its post-step fields
-  double* lam = nullptr;              // [2][env][ld] lambda_q, lambda_p
-  double* cot = nullptr;              // [max_steps][3][env] energy cotangents
-  double* gext = nullptr;             // [max_steps][env][Ng] e-bar
-  double* nu = nullptr;               // [env][Ng]
-  acc_t* acc = nullptr;               // [env][Ng] zero between uses
-  unsigned long long* cmax = nullptr; // [env] zero between uses
-  unsigned long long* counters = nullptr;   // [0] replay mismatches of the last backward or tangent, [1] replay positions out of range
-  double* gact = nullptr;             // [max_steps][env][2M] a-bar (M: the actuator's modes at pic_tape_start; none without one)
+  TapeBlock block;
+  unsigned long long* counters = nullptr;   // cmax + env: [0] replay mismatches of the last backward or tangent, [1] replay positions out of range
   int64_t launches = 0;               // kernels the last backward or tangent enqueued
   int64_t budget = 0;                 // budget_bytes of pic_tape_start (0: none)
-  // steps of the gain law (pic_step_feedback_gain): one block allocated by the first such call, one gain per call;
-  // both count in `bytes`
-  DeviceBuf<void> law_block;
-  double* lact = nullptr;             // [max_steps][env][2M] a_t of the law's steps (their e_t = B a_t goes to `ext` behind the call)
-  double* lmodes = nullptr;           // [max_steps][env][2M] m_t of the law's steps, zero on the others
-  double* lcot = nullptr;             // [max_steps][env][2M] cotangents on m_t of a backward
-  double* lE = nullptr;               // [env][Ng] E-bar_t = J^T (G^T a-bar_t + m-bar_t) of a law step
-  std::vector<int> law;               // [max_steps] per step: the index of its gain in `gains`, or -1 (empty: no law step yet)
-  std::vector<DeviceBuf<double>> gains;   // per call: [env][2M][2M]
+  // steps of the gain law (pic_step_feedback_gain): the block comes with the first such call, one gain per call
+  struct Law : LawViews {
+    TapeBlock block;
+    std::vector<int> step;            // [max_steps] per step: the index of its gain in `gains`, or -1 (empty: no law step yet)
+    std::vector<DeviceBuf<double>> gains;   // per call: [env][2M][2M]
+  } law;
   // the reverse walk (pic_tape_walk_*); pic_tape_backward[_feedback] is a walk of its own.  Any append, start,
   // stop, backward, tangent, tangent walk or new walk abandons it.
-  bool walk = false;                  // a walk is in progress
-  int64_t wnext = -1;                 // the next step it reverses (-1: all walked)
-  int wmo = 0;                        // M_o: modes of the walk's mode cotangents
-  DeviceBuf<double> wstage;           // [2][env][N] + [env][2 M_o] host cotangents of a step on the device (allocated on demand)
-  size_t wstage_bytes = 0;
-  DeviceBuf<double> wE;               // [env][Ng] E-bar of a walk's mode cotangents on a tape without a law block (else lE)
-  // forward mode (pic_tape_tangent): the tangent state, meshes and unit words of tan_k directions, allocated by the
-  // first call with that many and grown for more; counts in `bytes`
-  DeviceBuf<void> tan_block;
-  int tan_k = 0;
-  size_t tan_bytes = 0;
+  struct Walk {
+    bool on = false;                  // a walk is in progress
+    int64_t next = -1;                // the next step it reverses (-1: all walked)
+    int mo = 0;                       // M_o: modes of the walk's mode cotangents
+    DeviceBuf<double> stage;          // [2][env][N] + [env][2 M_o] host cotangents of a step on the device (allocated on demand)
+    size_t stage_bytes = 0;
+    DeviceBuf<double> E;              // [env][Ng] E-bar of a walk's mode cotangents on a tape without a law block (else law.E)
+  } walk;
+  // forward mode (pic_tape_tangent): the tangent state, meshes and unit words of k directions, allocated by the
+  // first call with that many and grown for more
+  struct Tan {
+    TapeBlock block;
+    int k = 0;
+    TanArgs views{};                  // st, dF, acc, ke, umax (host_tangent.h: tangent_args fills in the rest)
+  } tan;
   // the forward walk through closed loops (pic_tape_tangent_walk_*, pic_tape_tangent_feedback): its working rows
-  // (host_tangent_walk.h: tanwalk_parts) for tw_cap_k directions and tw_cap_mo observed modes, allocated by the first walk and
-  // grown for more; counts in `bytes`.  It replays into the segment buffer as the reverse walk does, so either abandons the
-  // other; any append, start, stop, backward or tangent abandons it too.
-  bool twalk = false;                 // a forward walk is in progress
-  int64_t tnext = 0;                  // the next step it advances
-  int tw_k = 0, tw_mo = 0;            // its directions and observed modes
-  bool tw_dgain = false;              // it carries a gain tangent
-  DeviceBuf<void> tw_block;
-  size_t tw_bytes = 0;
-  int tw_cap_k = 0, tw_cap_mo = 0;
-  // the per-step smoothed KL (pic_tape_kl_*): one block allocated by pic_tape_kl_start, counts in `bytes`;
-  // kl_feq .. kl_cot are views into it
-  DeviceBuf<void> kl_block;
-  bool kl = false;                    // a KL is attached: advance cuts behind every step and writes its row of kl_trace
-  pic_phase_spec kl_spec{};           // the caller's spec with feq = kl_feq (device memory)
-  double* kl_feq = nullptr;           // [nx][nv] or [env][nx][nv] the tape's copy of the target
-  unsigned long long* kl_acc = nullptr;   // [env][nx][nv] integer sums, zero between uses
-  double* kl_g = nullptr;             // [env][nx][nv] cotangent grid of the step being reversed
-  double* kl_trace = nullptr;         // [max_steps][env] KL~ after every step
-  double* kl_cot = nullptr;           // [max_steps][env] cotangents on it (pic_tape_kl_cot)
-  std::vector<char> kl_flag;          // [max_steps] per step: kl_cot holds a row for it
-  // forward mode of that KL (pic_tape_tangent_kl): one block allocated by the first call that asks for d_kl,
-  // counts in `bytes`; tkl_ones and tkl_part are views into it
-  DeviceBuf<void> tkl_block;
-  double* tkl_ones = nullptr;         // [env] unit cotangents: the finishing kernel's g is then dKL~/df
-  double* tkl_part = nullptr;         // [kMaxTangents][env][chunks] the chunks' sums of the step at hand
-  // cotangents on the fluid moments of the tape's states (pic_tape_moments_cot): one block allocated by the first
-  // call that sets a row, counts in `bytes`
-  DeviceBuf<void> mom_block;
-  double* mom_cot = nullptr;          // [max_steps + 1][env][3][Ng]: row s + 1 for the state step s left, row 0 for the tape start
-  std::vector<char> mom_flag;         // [max_steps + 1] per row: mom_cot holds a cotangent there
-  // the moments of every taped step (pic_tape_moments_start): one block allocated by that call, counts in `bytes`
-  DeviceBuf<void> mtr_block;
-  double* mom_trace = nullptr;        // [max_steps][env][3][Ng]; set: advance cuts behind every step and writes its row
-  // forward mode of the moments (pic_tape_tangent_moments): one block for kMaxTangents directions allocated by the
-  // first call that asks for d_moments, counts in `bytes`; tmom_acc and tmom_max are views into it
-  DeviceBuf<void> tmom_block;
-  unsigned long long* tmom_acc = nullptr;   // [3][K][env][Ng] integer sums of the step at hand, zero between uses
-  unsigned long long* tmom_max = nullptr;   // [3][K][env] bit patterns of the terms' bounds, zero between uses
-  // steps under an MLP policy (pic_tape_step_policy): one block allocated by the first such call (pobs .. pg are
-  // views into it) and one copy of the parameters and obs_scale per call; all count in `bytes`
-  DeviceBuf<void> pol_block;
-  pic_policy pshape{};                // the shape every policy call of this tape has (params, obs_scale: unused)
-  size_t pP = 0;                      // doubles of one parameter vector
-  double* pobs = nullptr;             // [max_steps][env][2 Mo] o_t of the policy's steps
-  double* ppre = nullptr;             // [max_steps][env][2M] u_t
-  double* pact = nullptr;             // [max_steps][env][2M] a_t (their e_t = B a_t goes to `ext` as an actions step's)
-  double* pgobs = nullptr;            // [max_steps][env][2 Mo] o-bar_t of the last reverse pass, zero on the other steps
-  double* pgpre = nullptr;            // [max_steps][env][2M] u-bar_t
-  double* pgact = nullptr;            // [max_steps][env][2M] a-bar_t = B^T e-bar_t + the direct cotangent
-  double* pcobs = nullptr;            // [max_steps][env][2 Mo] direct cotangents on o_t of a backward
-  double* pcact = nullptr;            // [max_steps][env][2M] direct cotangents on a_t of a backward
-  double* pmbar = nullptr;            // [env][2 Mo] m-bar of the step being reversed
-  double* pgE = nullptr;              // [env][P] the parameter gradient's per-environment sums
-  double* pg = nullptr;               // [P] their sum in ascending environment order (shared parameters)
-  struct PolicyCopy { DeviceBuf<double> params; const double* scale; double action_scale; size_t bytes; };
-  std::vector<PolicyCopy> pcalls;     // per call: params [P] or [env][P], then obs_scale [2 Mo] behind them (scale: null without)
-  std::vector<int> pol;               // [max_steps] per step: the index of its call in `pcalls`, or -1 (empty: no policy step yet)
-  bool pfirst = true;                 // the reverse pass in progress has met no policy step yet: the next one starts pgE's sums
-  bool pcot_obs = false, pcot_act = false;   // pcobs / pcact hold a backward's cotangents
-  bool pvalid = false;                // pgE holds the sums of a finished reverse pass over the steps taped so far
-  // forward mode through the policy's steps (pic_tape_tangent_policy): the working rows of tp_cap_k directions
-  // (host_tangent_walk.h: tanpol_parts) next to the walk's, allocated by the first call and grown for more; counts in `bytes`
-  DeviceBuf<void> tp_block;
-  size_t tp_bytes = 0;
-  int tp_cap_k = 0;
-  bool tw_pol = false;                // the forward walk in progress goes through the policy's steps
-  bool tp_dparams = false;            // it carries a parameter tangent
+  // for cap_k directions and cap_mo observed modes, allocated by the first walk and grown for more.  It replays into the segment
+  // buffer as the reverse walk does, so either abandons the other; any append, start, stop, backward or tangent abandons it too.
+  struct TanWalk : TanWalkViews {
+    TapeBlock block;
+    int cap_k = 0, cap_mo = 0;
+    bool on = false;                  // a forward walk is in progress
+    int64_t next = 0;                 // the next step it advances
+    int k = 0, mo = 0;                // its directions and observed modes
+    bool dgain = false;               // it carries a gain tangent
+    bool policy = false;              // it goes through the policy's steps
+  } twalk;
+  // the per-step smoothed KL (pic_tape_kl_*): the block comes with pic_tape_kl_start
+  struct Kl : KlViews {
+    TapeBlock block;
+    bool on = false;                  // a KL is attached: advance cuts behind every step and writes its row of the trace
+    pic_phase_spec spec{};            // the caller's spec with feq = the tape's copy (device memory)
+    std::vector<char> flag;           // [max_steps] per step: cot holds a row for it
+  } kl;
+  // forward mode of that KL (pic_tape_tangent_kl): the block comes with the first call that asks for d_kl
+  struct TanKl : TanKlViews {
+    TapeBlock block;
+  } tkl;
+  // cotangents on the fluid moments of the tape's states (pic_tape_moments_cot): the block comes with the first
+  // call that sets a row
+  struct MomCot : MomCotViews {
+    TapeBlock block;
+    std::vector<char> flag;           // [max_steps + 1] per row: cot holds a cotangent there
+  } mom_cot;
+  // the moments of every taped step (pic_tape_moments_start); trace set: advance cuts behind every step and writes its row
+  struct MomTrace : MomTraceViews {
+    TapeBlock block;
+  } mom_trace;
+  // forward mode of the moments (pic_tape_tangent_moments): one block for kMaxTangents directions, with the first
+  // call that asks for d_moments
+  struct TanMom {
+    TapeBlock block;
+    MomJvpArgs views{};               // acc, umax (the rest is a step's)
+  } tmom;
+  // steps under an MLP policy (pic_tape_step_policy): the block comes with the first such call, and every call
+  // keeps a copy of its parameters and obs_scale
+  struct Policy : TapePolicyViews {
+    TapeBlock block;
+    pic_policy shape{};               // the shape every policy call of this tape has (params, obs_scale: unused)
+    size_t P = 0;                     // doubles of one parameter vector
+    struct Copy { DeviceBuf<double> params; const double* scale; double action_scale; size_t bytes; };
+    std::vector<Copy> calls;          // per call: params [P] or [env][P], then obs_scale [2 Mo] behind them (scale: null without)
+    std::vector<int> step;            // [max_steps] per step: the index of its call in `calls`, or -1 (empty: no policy step yet)
+    bool first = true;                // the reverse pass in progress has met no policy step yet: the next one starts gE's sums
+    bool cot_obs = false, cot_act = false;   // cobs / cact hold a backward's cotangents
+    bool valid = false;               // gE holds the sums of a finished reverse pass over the steps taped so far
+  } policy;
+  // forward mode through the policy's steps (pic_tape_tangent_policy): the working rows of cap_k directions next
+  // to the walk's, allocated by the first call and grown for more
+  struct TanPolicy : TanPolViews {
+    TapeBlock block;
+    int cap_k = 0;
+    bool dparams = false;             // the walk in progress carries a parameter tangent
+  } tpol;
 };
 
 }  // namespace
@@ -357,10 +348,8 @@ struct __attribute__((visibility("hidden"))) pic_handle : LaunchPlan {      // t
   PinnedBuf<void> h_part;         // pinned host staging for x | v of states up to 64 MB (from pic_create on up to 4 MB, else on first use)
   bool h_part_refused = false;    // ... could not be had: do not ask again
   PinnedBuf<double> h_fields;     // pinned host staging for n | E_mesh | phi (meshes up to 256 KB each in total), or null
-  DeviceBuf<void> mom_block;      // pic_moments, allocated by its first call; mom_acc .. mom_out are views into it
-  unsigned long long* mom_acc = nullptr;   // [3][env][Ng] integer sums of the three moments, zero between calls
-  unsigned long long* mom_max = nullptr;   // [env] bit pattern of max |v|, zero between calls
-  double* mom_out = nullptr;               // [env][3][Ng] the device copy of a result that goes to host memory
+  DeviceBuf<void> mom_block;      // pic_moments, allocated by its first call
+  MomViews mom;                   // views into it (host_blocks.h: moments_parts)
   DeviceBuf<unsigned long long> bad;
   unsigned long long* probe_bad = nullptr;   // view: bad + 1, where the probes count their non-finite positions (never read: pic_bad_count
                                              // describes the state's particles, and a probe's positions are not among them)
@@ -1344,12 +1333,12 @@ static int advance(pic_handle* h, const StepControl& sc, int nsteps, double* his
   Recorder& r = h->rec;
   Tape& t = h->tape;
   const int E = h->cfg.num_envs;
-  t.walk = t.twalk = t.pvalid = false;   // appending abandons a walk (and dates the policy gradient of the last one)
+  t.walk.on = t.twalk.on = t.policy.valid = false;   // appending abandons a walk (and dates the policy gradient of the last one)
   for (int done = 0; done < nsteps;) {
     int64_t n = nsteps - done;
     if (r.on) n = std::min<int64_t>(n, r.stride - r.k % r.stride);
     if (t.on) n = std::min<int64_t>(n, t.every - t.steps % t.every);
-    if (t.on && (t.kl || t.mom_trace)) n = 1;   // the KL or the moments (7l) of every step: the recorder's cut with stride 1
+    if (t.on && (t.kl.on || t.mom_trace.trace)) n = 1;   // the KL or the moments (7l) of every step: the recorder's cut with stride 1
     const StepControl part = sc.after(done, E);
     int rc = t.on && part.fb.M == 0 ? tape_record_ext(h, part, (int)n) : PIC_OK;
     if (rc) return rc;
@@ -1373,11 +1362,11 @@ static int advance(pic_handle* h, const StepControl& sc, int nsteps, double* his
       rc = tape_record_ext(h, made, (int)n);
       if (rc) return rc;
     }
-    if (t.kl) {
+    if (t.kl.on) {
       rc = tape_kl_enqueue(h);        // row t.steps of the trace
       if (rc) return rc;
     }
-    if (t.mom_trace) {
+    if (t.mom_trace.trace) {
       rc = tape_moments_enqueue(h);   // row t.steps of the moments' trace
       if (rc) return rc;
     }
@@ -1506,20 +1495,16 @@ static int step_recording(pic_handle* h, StepControl sc, int nsteps, double* his
     }
   }
   hipError_t e = hipGetLastError();
-  if (!dh && !da && !dm && !ds) {
-    if (rc != PIC_OK) return rc;
-    if (e != hipSuccess) return fail(h, PIC_EHIP, std::string(who) + ": " + hipGetErrorString(e));
-    return PIC_OK;
-  }
+  const bool wait = dh || da || dm || ds;
   if (rc == PIC_OK && e == hipSuccess && dh) e = hipMemcpyAsync(hist, dh, hbytes, hipMemcpyDeviceToHost, h->stream);
   if (rc == PIC_OK && e == hipSuccess && da) e = hipMemcpyAsync(act_out, da, abytes, hipMemcpyDeviceToHost, h->stream);
   if (rc == PIC_OK && e == hipSuccess && dm) e = hipMemcpyAsync(modes_out, dm, abytes, hipMemcpyDeviceToHost, h->stream);
   if (rc == PIC_OK && e == hipSuccess && ds) e = hipMemcpyAsync(snap, ds, sbytes, hipMemcpyDeviceToHost, h->stream);
-  hipError_t e2 = hipStreamSynchronize(h->stream);
-  if (rc != PIC_OK) return rc;
-  if (e != hipSuccess || e2 != hipSuccess)
-    return fail(h, PIC_EHIP, std::string(who) + ": " + hipGetErrorString(e != hipSuccess ? e : e2));
-  return PIC_OK;
+  if (rc != PIC_OK) {                 // (a failed step's error stands; what was enqueued is waited for)
+    if (wait) (void)hipStreamSynchronize(h->stream);
+    return rc;
+  }
+  return hip_tail(h, e, wait, who);
 }
 
 // pic_step_history and pic_step_snapshots: a held field (or none), the energies and / or the particles of every step read back
@@ -1749,9 +1734,7 @@ int pic_get_cic(pic_handle* h, int env, int64_t* indx_l, int64_t* indx_r, double
   if (e == hipSuccess && indx_r) e = hipMemcpyAsync(indx_r, dj + N, N * sizeof(long long), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess && weight_l) e = hipMemcpyAsync(weight_l, dw, N * sizeof(double), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess && weight_r) e = hipMemcpyAsync(weight_r, dw + N, N * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) return fail(h, PIC_EHIP, std::string("pic_get_cic: ") + hipGetErrorString(e));
-  return PIC_OK;
+  return hip_tail(h, e, true, "pic_get_cic");
 }
 
 // deposit of the positions in h->scratch into the probe accumulator, then one solve with `ext` added
@@ -1855,9 +1838,7 @@ int pic_compute_E(pic_handle* h, const void* x, int mem_kind, const double* E_ex
     if (e == hipSuccess && idx) e = hipMemcpyAsync(idx, dj, shape_bytes, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess && w) e = hipMemcpyAsync(w, dw, shape_bytes, hipMemcpyDeviceToHost, h->stream);
   }
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) return fail(h, PIC_EHIP, std::string("pic_compute_E: ") + hipGetErrorString(e));
-  return PIC_OK;
+  return hip_tail(h, e, true, "pic_compute_E");
 }
 
 int pic_solve_poisson(pic_handle* h, const double* rhs, double* phi, double* E_mesh) {
@@ -2007,8 +1988,8 @@ int pic_step_feedback_gain(pic_handle* h, int max_mode, const double* gain, int 
   if (t.on) {                        // the gain goes on the tape once per call
     rc = tape_law_reserve(h, gbytes);
     if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(t.gains.back(), gain, gbytes, copy_kind(mem_kind, hipMemcpyHostToDevice), h->stream));
-    g = t.gains.back();
+    HIPCHK(h, hipMemcpyAsync(t.law.gains.back(), gain, gbytes, copy_kind(mem_kind, hipMemcpyHostToDevice), h->stream));
+    g = t.law.gains.back();
   } else {
     if (mem_kind == PIC_HOST && !h->gain) HIPCHK(h, alloc(h->gain, (size_t)E * 4 * kMaxFeedbackModes * kMaxFeedbackModes * sizeof(double)));
     HIPCHK(h, device_input(h, gain, mem_kind, gbytes, h->gain, &g));
@@ -2019,10 +2000,10 @@ int pic_step_feedback_gain(pic_handle* h, int max_mode, const double* gain, int 
   // taped: the steps write their actions and modes on the tape, the caller's records are copied from there
   const int64_t s0 = t.steps;
   const size_t row = (size_t)E * n;
-  sc.fb.act_hist = t.lact + (size_t)s0 * row;
-  sc.fb.modes_hist = t.lmodes + (size_t)s0 * row;
+  sc.fb.act_hist = t.law.act + (size_t)s0 * row;
+  sc.fb.modes_hist = t.law.modes + (size_t)s0 * row;
   rc = step_recording(h, sc, nsteps, hist, nullptr, nullptr, who);
-  for (int64_t s = s0; s < t.steps; ++s) t.law[(size_t)s] = (int)t.gains.size() - 1;
+  for (int64_t s = s0; s < t.steps; ++s) t.law.step[(size_t)s] = (int)t.law.gains.size() - 1;
   if (rc) return rc;
   if (actions_out) HIPCHK(h, hipMemcpyAsync(actions_out, sc.fb.act_hist, (size_t)nsteps * row * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (modes_out) HIPCHK(h, hipMemcpyAsync(modes_out, sc.fb.modes_hist, (size_t)nsteps * row * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -2108,9 +2089,7 @@ int pic_phase_histogram(pic_handle* h, int nbins, double vmin, double vmax, uint
   DeviceBuf<unsigned> d;
   hipError_t e = phase_counts(h, nbins, vmin, vmax, d);
   if (e == hipSuccess) e = hipMemcpyAsync(counts, d, nb, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) return fail(h, PIC_EHIP, std::string("pic_phase_histogram: ") + hipGetErrorString(e));
-  return PIC_OK;
+  return hip_tail(h, e, true, "pic_phase_histogram");
 }
 
 int pic_phase_kl(pic_handle* h, int nbins, double vmin, double vmax, const double* feq, double* kl) {
@@ -2131,9 +2110,7 @@ int pic_phase_kl(pic_handle* h, int nbins, double vmin, double vmax, const doubl
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpyAsync(kl, df + nb2, (size_t)E * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) return fail(h, PIC_EHIP, std::string("pic_phase_kl: ") + hipGetErrorString(e));
-  return PIC_OK;
+  return hip_tail(h, e, true, "pic_phase_kl");
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2255,8 +2232,7 @@ int pic_record_stop(pic_handle* h) {
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   const hipError_t e = hipStreamSynchronize(h->stream);
   h->rec = Recorder{};
-  if (e != hipSuccess) return fail(h, PIC_EHIP, std::string("pic_record_stop: ") + hipGetErrorString(e));
-  return PIC_OK;
+  return hip_tail(h, e, false, "pic_record_stop");
 }
 
 int pic_stream_probe(pic_handle* h, int repeats, double* gbytes_per_s) {

@@ -424,6 +424,159 @@ def test_tape_byte_accounting_is_pinned():
     env.close()
 
 
+# The blocks ACCOUNTING does not reach, at its shape (E = 2, N = 1000, Ng = 64, two actuator modes, max_steps = 5,
+# checkpoint_every = 2): name -> (bytes, checkpoint_every, launches) of pic_tape_stats behind the last action of the tape of that
+# name (_more_accounting).  Recorded from a run of the code as it was before the blocks got one reserve path (csrc/host_diff.h:
+# tape_reserve) and checked against the sums of that code's layout functions, which tests/test_blocks_cpu.py pins on the CPU (every
+# part rounded up to 256 bytes; a row of actions is 64 bytes, of observations 96, a mesh of both environments 1024, ld = 1024).  Never re-recorded from
+# the code under test.
+START2, TANGENT1, TANGENT5 = 250880, 35328, 174592        # ACCOUNTING: start_every2, and what tangent_K1 / tangent_K5 add to it
+MORE_ACCOUNTING = {
+    # the record: o, u, a, o-bar, u-bar, a-bar and the two direct cotangents 8 x 512 (480 and 320 bytes rounded), m-bar 96 -> 256,
+    # the per-environment sums 2 x 59 x 8 = 944 -> 1024, their sum 472 -> 512; a call's copy: the parameters 472 -> 512 and the 48
+    # bytes of obs_scale behind them, unrounded; two calls
+    "policy_shared": (START2 + 5888 + 2 * 560, 2, 0),
+    "policy_per_env": (START2 + 5376 + 1072, 2, 0),       # no sum over the environments; the copy: 944 -> 1024, + 48
+    # the walk's rows for K = 1 and two observed modes: dM 1024, energies 48 -> 256, observation, dm, da 64 -> 256 each, dG 256,
+    # injection 1024; begin: 1 launch of the start's field, the law kernel, the start kernel
+    "twalk_K1": (START2 + TANGENT1 + 3328, 2, 3),
+    "twalk_K5": (START2 + TANGENT5 + 13312, 2, 3),        # dM 5120, 240 -> 256, 3 x (320 -> 512), dG 1280, injection 5120
+    # the tangent's block for K = 1, the walk's rows with three observed modes (96 -> 256: as above) and the policy tangent's:
+    # dtheta 472 -> 512, du 256, d_pre 256; launches: begin 3, replay 17, 2 x (policy JVP 1, step 11, law 1)
+    "tpol": (START2 + 5888 + 560 + TANGENT1 + 3328 + 1024, 2, 46),
+    "mom_cot": (START2 + 18432, 2, 0),                    # 6 rows of 2 x 3 x 64 doubles
+    "mom_trace": (START2 + 15360, 2, 0),                  # 5 rows
+    "tkl": (START2 + 3072 + TANGENT1 + 256 + 256, 2, 48), # kl_shared's block; unit cotangents 16 -> 256, 8 x 2 x 1 chunk sums 128 -> 256
+    "tmom": (START2 + TANGENT1 + 24576 + 512, 2, 46),     # sums 3 x 8 x 2 x 64 words, max words 3 x 8 x 2 x 8 = 384 -> 512
+}
+# what the refusal of the last action leaves in `bytes` on top of what was there: tangent_policy reserves the tangent's block and
+# the walk's rows before the policy tangent's, each on its own
+MORE_PARTIAL = {"tpol": TANGENT1 + 3328}
+MORE_ENTRY = {"policy_shared": "pic_tape_step_policy", "policy_per_env": "pic_tape_step_policy",
+              "twalk_K1": "pic_tape_tangent_walk_begin", "twalk_K5": "pic_tape_tangent_walk_begin", "tpol": "pic_tape_tangent_policy",
+              "mom_cot": "pic_tape_moments_cot", "mom_trace": "pic_tape_moments_start", "tkl": "pic_tape_tangent_kl",
+              "tmom": "pic_tape_tangent_moments"}
+# E = 1, Ng = 100 (pic_create takes any Ng >= 4): the tape, the law's record 3 x (160 -> 256) + the 800 bytes of its last part,
+# unrounded, and a gain of 128 bytes (unrounded as well: an allocation of its own)
+LAW_TAIL = (132352 + 3 * 256 + 800 + 128, 2, 0)
+
+
+def _more_accounting(env, X, V, name, budget=0):
+    """The tape `name` of MORE_ACCOUNTING with budget_bytes = budget: every action but the last, then -> (the last action as a
+    callable, pic_tape_stats in front of it)."""
+    from ocplasma_amd.control.policy import MLPPolicy
+    E, Mk, T, Mo = env.num_envs, 2, 5, 3
+    h = env._h
+    env.stop_tape()
+    env.reset(X, V)
+    env.start_tape(T, 2, budget_bytes=budget)
+    rng = np.random.default_rng(34)
+    acts = rng.uniform(-0.5, 0.5, (2, E, 2 * Mk))
+    widths = (2 * Mo, 5, 2 * Mk)
+    P = sum(widths[l + 1] * widths[l] + widths[l + 1] for l in range(2))           # 59
+
+    def policy(per_env):
+        theta = rng.uniform(-0.3, 0.3, (E, P) if per_env else (P,))
+        return MLPPolicy(widths, "tanh", theta, Mo, squash=True, obs_scale=np.ones(2 * Mo), per_env=per_env)
+
+    if name == "policy_shared":
+        pol = policy(False)
+        env.tape_step_policy(pol, 1)
+        last = lambda: env.tape_step_policy(pol, 1)
+    elif name == "policy_per_env":
+        last = lambda pol=policy(True): env.tape_step_policy(pol, 2)
+    elif name in ("twalk_K1", "twalk_K5"):
+        env.step_actions_traj(acts)
+        h.tape_tangent(1, d_actions=np.ones((1, 2, E, 2 * Mk)))
+        last = lambda: env.tangent_walk(K=1)
+        if name == "twalk_K5":
+            last()
+            h.tape_tangent(5, d_actions=np.ones((5, 2, E, 2 * Mk)))
+            last = lambda: env.tangent_walk(K=5)
+    elif name == "tpol":
+        pol = policy(False)
+        env.tape_step_policy(pol, 2)
+        last = lambda: env.tangent_policy(d_params=np.ones(P))
+    elif name == "mom_cot":
+        env.step_actions_traj(acts)
+        cot = np.ones((2, E, 3, 64))
+        last = lambda: h.tape_moments_cot(cot.ctypes.data, 0, 0, 2)
+    elif name == "mom_trace":
+        last = h.tape_moments_start
+    elif name == "tkl":
+        feq = np.random.default_rng(32).uniform(0.0, 2.0 / (L * 12.0), (8, 8))
+        h.tape_kl_start(8, 8, -6.0, 6.0, feq.ctypes.data, 0, 0)
+        env._tape_kl = True
+        env.step_actions_traj(acts)
+        env.tangent(d_actions=np.ones((2, E, 2 * Mk)))
+        last = lambda: env.tangent(d_actions=np.ones((2, E, 2 * Mk)), kl=True)
+    elif name == "tmom":
+        env.step_actions_traj(acts)
+        env.tangent(d_actions=np.ones((2, E, 2 * Mk)))
+        last = lambda: env.tangent(d_actions=np.ones((2, E, 2 * Mk)), moments=True)
+    else:
+        raise KeyError(name)
+    return last, env.tape_stats()
+
+
+def _stats3(env):
+    st = env.tape_stats()
+    return st["bytes"], st["checkpoint_every"], st["launches"]
+
+
+def test_tape_byte_accounting_of_the_attached_blocks_is_pinned():
+    """MORE_ACCOUNTING: the policy's record and its per-call copies, the tangent walk's rows and their growth, the policy
+    tangent's rows, the moments' cotangents and trace, and the blocks behind the KL's and the moments' tangents.  For each: the
+    recorded total without a budget, the same total accepted as budget_bytes to the byte, and one byte less refused with
+    PIC_ENOMEM by the entry that needs the block, with steps and bytes as they were -- twice, where the entry reserves other
+    blocks first (MORE_PARTIAL)."""
+    from ocplasma_amd._abi import PicError
+    env, X, V = _accounting_env()
+    for name, want in MORE_ACCOUNTING.items():
+        for budget in (0, want[0]):
+            last, _ = _more_accounting(env, X, V, name, budget)
+            last()
+            got = _stats3(env)
+            print(name, budget, got)
+            assert got == want, (name, budget, got)
+        last, before = _more_accounting(env, X, V, name, want[0] - 1)
+        held = before["bytes"] + MORE_PARTIAL.get(name, 0)
+        for _ in range(2):
+            with pytest.raises(PicError, match=f"error -4: {MORE_ENTRY[name]}:"):
+                last()
+            st = env.tape_stats()
+            assert (st["steps"], st["bytes"]) == (before["steps"], held), (name, st, before)
+    env.stop_tape()
+    env.close()
+
+
+def test_tape_byte_accounting_keeps_the_laws_unrounded_tail():
+    """LAW_TAIL: at E = 1, Ng = 100 the last part of the law's record, E-bar [env][Ng], takes its 800 bytes, not 1024."""
+    import ocplasma_amd as oc
+    from ocplasma_amd._abi import PicError
+    from ocplasma_amd.env.batched import BatchedPIC
+    env = BatchedPIC(1, 1000, 100, L=L, dt=0.1)
+    X, V = (a[None] for a in po.synthetic_bump_on_tail(1000, L, seed=31))
+    env.reset(X, V)
+    env.set_actuator(oc.E_field(L, 100, 2))
+    for budget in (0, LAW_TAIL[0]):
+        env.start_tape(5, 2, budget_bytes=budget)
+        env.step_feedback_gain(0.1 * np.eye(4), 2)
+        got = _stats3(env)
+        print("law_tail", budget, got)
+        assert got == LAW_TAIL, (budget, got)
+        env.stop_tape()
+        env.reset(X, V)
+    env.start_tape(5, 2, budget_bytes=LAW_TAIL[0] - 1)
+    before = env.tape_stats()
+    with pytest.raises(PicError, match="error -4: pic_step_feedback_gain:"):
+        env.step_feedback_gain(0.1 * np.eye(4), 2)
+    st = env.tape_stats()
+    assert (st["steps"], st["bytes"]) == (before["steps"], before["bytes"]), (st, before)
+    env.stop_tape()
+    env.close()
+
+
 def test_torch_rollout_matches_tape_and_passes_gradcheck():
     import torch
     from ocplasma_amd._abi import PicError
