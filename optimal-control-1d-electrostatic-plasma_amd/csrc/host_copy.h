@@ -29,7 +29,7 @@ int pic_copy_envs(pic_handle* dst, pic_handle* src, const int32_t* map, int mem_
                                  "particle and position dtype, interpol, accum_dtype, integrator and device)");
   }
   if (!src->has_state) return fail(h, PIC_ESTATE, "pic_copy_envs: the source holds no state (call pic_reset on it first)");
-  if (src->mid_stage || dst->mid_stage)
+  if (src->sched.mid_stage || dst->sched.mid_stage)
     return fail(h, PIC_ESTATE, "pic_copy_envs: a staged step is in progress (finish its pic_step_stage calls)");
   if (dst->tape.on || dst->tape.walk.on)
     return fail(h, PIC_ESTATE, "pic_copy_envs: refused while a tape is open on the destination (pic_tape_stop first)");
@@ -67,14 +67,14 @@ int pic_copy_envs(pic_handle* dst, pic_handle* src, const int32_t* map, int mem_
   // unless the host has checked the map (an entry a device map gets wrong keeps its environment, and that environment's part of
   // a cache it never had would be zeros).  Everything else is dropped as pic_invalidate drops it: integer sums, the same bits.
   const bool fills_all = same || host_map;
-  bool ring = src->q_slot >= 0 && dst->S == src->S && dst->resident == src->resident && (dst->q_slot >= 0 || fills_all);
+  bool ring = src->sched.q_slot >= 0 && dst->S == src->S && dst->resident == src->resident && (dst->sched.q_slot >= 0 || fills_all);
   bool q1 = src->resident && dst->resident && src->res_q1_valid && dst->res_R == src->res_R && dst->res_lean == src->res_lean &&
             (dst->res_q1_valid || fills_all);
   bool carry = q1 && src->res_carry_valid && dst->res_carry && src->res_carry &&
                dst->res_carry_bytes / E == src->res_carry_bytes / Es && (dst->res_carry_valid || fills_all);
   if (!same) {
-    if (ring && dst->q_slot < 0) dst->q_slot = ring_take_clean(dst);
-    if (!ring) { ring_retire(dst, dst->q_slot); dst->q_slot = -1; }
+    if (ring && dst->sched.q_slot < 0) dst->sched.q_slot = ring_take_clean(dst);
+    if (!ring) { dst->sched.ring.retire(dst->sched.q_slot); dst->sched.q_slot = -1; }
     dst->res_q1_valid = q1;
     dst->res_carry_valid = carry;
   }
@@ -92,7 +92,7 @@ int pic_copy_envs(pic_handle* dst, pic_handle* src, const int32_t* map, int mem_
   seg(src->KE, dst->KE, 1, 1, 1);
   seg(src->PE, dst->PE, 1, 1, 1);
   seg(src->PEr, dst->PEr, 1, 1, 1);
-  if (ring) seg(ring_row(src, src->q_slot), ring_row(dst, dst->q_slot), Ng, Ng, Ng, dst->S, (long long)Es * Ng, (long long)E * Ng);
+  if (ring) seg(ring_row(src, src->sched.q_slot), ring_row(dst, dst->sched.q_slot), Ng, Ng, Ng, dst->S, (long long)Es * Ng, (long long)E * Ng);
   if (q1) {
     const int w = dst->res_R * (Ng + 2);
     seg(src->res_q1, dst->res_q1, w, w, w);

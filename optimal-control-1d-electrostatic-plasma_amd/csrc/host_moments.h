@@ -63,7 +63,7 @@ int pic_moments(pic_handle* h, int mem_kind, double* m) {
   if (int rc = check_mem_kind(h, mem_kind, who)) return rc;
   if (!m) return fail(h, PIC_EINVAL, std::string(who) + ": m is NULL");
   if (!h->has_state) return fail(h, PIC_ESTATE, std::string(who) + ": call pic_reset first");
-  if (h->mid_stage) return fail(h, PIC_ESTATE, std::string(who) + ": a staged step is in progress");
+  if (h->sched.mid_stage) return fail(h, PIC_ESTATE, std::string(who) + ": a staged step is in progress");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   if (int rc = moments_ensure(h, who)) return rc;
   double* out = device_output(m, mem_kind, h->mom.out);
@@ -95,7 +95,7 @@ int pic_moments_vjp(pic_handle* h, const double* cot_m, int mem_kind, void* g_x,
                                                   "moments are not differentiable)");
   if (!cot_m) return fail(h, PIC_EINVAL, std::string(who) + ": cot_m is NULL");
   if (!h->has_state) return fail(h, PIC_ESTATE, std::string(who) + ": call pic_reset first");
-  if (h->mid_stage) return fail(h, PIC_ESTATE, std::string(who) + ": a staged step is in progress");
+  if (h->sched.mid_stage) return fail(h, PIC_ESTATE, std::string(who) + ": a staged step is in progress");
   if (!g_x && !g_v) return PIC_OK;
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   const size_t E = h->cfg.num_envs, N = h->cfg.N, cbytes = E * 3 * h->cfg.Ng * sizeof(double), pbytes = E * N * sizeof(double);
@@ -217,7 +217,7 @@ int pic_moments_jvp(pic_handle* h, int K, const void* d_x, const void* d_v, int 
   if (K < 1 || K > kMaxTangents) return fail(h, PIC_EINVAL, std::string(who) + ": need 1 <= K <= " + std::to_string(kMaxTangents));
   if (!d_m) return fail(h, PIC_EINVAL, std::string(who) + ": d_m is NULL");
   if (!h->has_state) return fail(h, PIC_ESTATE, std::string(who) + ": call pic_reset first");
-  if (h->mid_stage) return fail(h, PIC_ESTATE, std::string(who) + ": a staged step is in progress");
+  if (h->sched.mid_stage) return fail(h, PIC_ESTATE, std::string(who) + ": a staged step is in progress");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   const size_t E = h->cfg.num_envs, N = h->cfg.N, Ng = h->cfg.Ng;
   const size_t pbytes = (size_t)K * E * N * sizeof(double), obytes = (size_t)K * E * 3 * Ng * sizeof(double);

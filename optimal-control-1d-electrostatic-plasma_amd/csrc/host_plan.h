@@ -176,7 +176,7 @@ static inline int plan_launch(const pic_config& c, int ncu, LaunchPlan* p, std::
   // 3 / 4 environments of 1e6: 31.2 / 45.0 / 64.5 / 74.0 us per step with 4, 31.6 / 45.3 / 65.5 / 75.1 with 8, 33.3 / 47.8 /
   // 65.2 / 75.4 with 16: every reader sums them), at least 8 workgroups per sub-row; with 16 environments or more the rows
   // themselves spread the traffic (and the flushes hide under the streaming of the other workgroups).
-  // Inner steps of a multi-step call leave the deposit of their final positions to the next step's sweep B2 (run_stages) where the
+  // Inner steps of a multi-step call leave the deposit of their final positions to the next step's sweep B2 (host_schedule.h) where the
   // sweeps are bound by HBM -- a particle state that does not fit the 256 MB Infinity Cache: there sweep B has the issue slots that
   // sweep D lacks (config 2 969 -> 948 us per step).  States that live in the cache, or are bound by the latency of each launch,
   // gain nothing or lose (all measured on one box, round 3's tree against this one: 8 x 1e6 float64 131.2 -> 132.6, 64 x 20000

@@ -56,7 +56,7 @@ int pic_tape_start(pic_handle* h, const pic_tape_config* c) {
   if (c->max_steps < 1 || c->checkpoint_every < 0 || c->budget_bytes < 0)
     return fail(h, PIC_EINVAL, "pic_tape_start: need max_steps >= 1, checkpoint_every >= 0, budget_bytes >= 0");
   if (!h->has_state) return fail(h, PIC_ESTATE, "pic_tape_start: call pic_reset first");
-  if (h->mid_stage) return fail(h, PIC_ESTATE, "pic_tape_start: a staged step is in progress");
+  if (h->sched.mid_stage) return fail(h, PIC_ESTATE, "pic_tape_start: a staged step is in progress");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   int64_t every = c->checkpoint_every;
   const BlockDims d = block_dims(h);

@@ -77,32 +77,6 @@ __device__ __forceinline__ void kernarg_warm() {
 #endif
 }
 
-enum Stage : int {
-  ST_A = 0,        // drift(c) from x,v ; deposit ; nothing stored
-  ST_B = 1,        // recompute q1 = x + (c_prev v) dt ; gather ; kick ; drift ; deposit ; store
-  ST_C = 2,        // gather ; kick ; drift ; deposit ; store
-  ST_D = 3,        // as C, then wrap, KE ; store wrapped x ; deposit the next step's q1 as well
-  ST_REFRESH = 4,  // wrap x ; deposit ; KE ; store wrapped x ; deposit the next step's q1   (pic.py:93-112 on reset)
-  ST_PROBE = 5,    // deposit positions of a scratch array, nothing stored             (util.py:73-116 callers)
-  // Inside a multi-step call (round 4): the post-step deposit of the final positions x' -- density, E_mesh, phi, PE of the state after
-  // a step, which nothing of the next step's dynamics reads -- moves from sweep D, the one sweep bound by VALU issue, into the next
-  // step's sweep B, which is bound by memory and reads x' anyway.  Same positions, same cells and weights, same integer sums.
-  ST_B2 = 6,       // as B, and deposits its INPUT positions (the previous step's x') into the second mesh
-  ST_D2 = 7,       // as D without the deposit of x' (wrap, KE, store, the next step's q1 deposit)
-  // The one-evaluation schemes and Stormer-Verlet (pic_set_integrator).  Their steps start from the deposit of the
-  // stored, wrapped x itself (no first drift), which the step before made as its post-step deposit: one row serves both.
-  ST_SE = 8,       // symplectic Euler: gather at x ; kick(d) ; drift(c) ; wrap ; deposit x' ; KE ; store
-  ST_FE = 9,       // forward Euler: gather at x ; drift(c) with the OLD p ; kick(d) ; wrap ; deposit x' ; KE ; store
-  ST_VK = 10,      // Verlet's closing half-kick: gather at q ; kick(d) ; wrap ; KE ; store (no deposit: the input row is x''s)
-  ST_VM = 11,      // Verlet, merged: as VK, then the next step's half-kick (same field) ; drift(c) ; deposit ; store
-  // A whole step inside one call on a state too large for the Infinity Cache (pic_create: readonly_c): sweep C stores nothing and
-  // sweep D re-derives C's output from C's input, which is still in memory -- 80 bytes per float64 particle-step instead of 96.
-  // The re-derivation is C's own arithmetic on the same operands (push_one: substage), so every bit is the same.
-  ST_C_RO = 12,    // as C without the particle stores; workgroup 0 of each environment stores its field tile (SweepIO::e2)
-  ST_D_RC = 13,    // C's sub-stage again from C's input and ST_C_RO's field tile, then as D
-  ST_D2_RC = 14    // ... then as D2
-};
-
 // Mesh accumulators that cross a kernel boundary: per environment and node the sum of shape weights as a 64-bit
 // integer in units of 2^-fg.  Integer sums do not depend on the order of the adds, so the result of a sweep is
 // the same whatever the launch geometry and however the adds of different workgroups interleave.

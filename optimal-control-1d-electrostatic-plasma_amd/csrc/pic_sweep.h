@@ -234,7 +234,7 @@ struct SweepIO {
   // The actuator's field is built ONCE per environment and step where the schedule allows it, not in every workgroup of every
   // sweep: ext_out [env][Ng] (or null) receives, from workgroup 0 of every environment, the field this sweep built from ctl.act
   // (sweep B of a call's first step: it cannot wait for anyone) or -- with ctl.ext and next_act -- the field of the NEXT step's
-  // coefficients (sweep D inside a rollout).  The sweeps that follow read it as a mesh field (host: run_stages).
+  // coefficients (sweep D inside a rollout).  The sweeps that follow read it as a mesh field (host_schedule.h: CTL_SHARED).
   double* ext_out;
   const double* next_act;  // [env][2M] coefficients of the next step (environment 0), or null
   acc_t* acc_out;          // receives this sweep's deposit (zero on entry; null in sweep D2, which makes none)

@@ -63,6 +63,7 @@
 #include "host_plan.h"
 #include "host_copy_map.h"
 #include "host_blocks.h"
+#include "host_schedule.h"
 
 #include "pic_device.h"
 #include "pic_sweep.h"
@@ -93,7 +94,6 @@ struct PlacementState {
   bool ptrs_exposed = false;          // pic_device_ptrs has handed out the addresses of x and v: v stays where it is
   bool x_cleared = false;
 };
-constexpr int RING = 8;                                          // accumulator rows in rotation
 
 // The owner of one HIP resource (device block, pinned host block, event, stream): move-only, releases what it holds at most once
 // (an empty owner releases nothing), and converts to the raw handle, so that launches and argument blocks take it as they did
@@ -284,11 +284,7 @@ struct __attribute__((visibility("hidden"))) pic_handle : LaunchPlan {      // t
   int scheme = PIC_YOSHIDA4;          // time integrator of the steps (pic_set_integrator)
   hipStream_t stream = nullptr;       // the stream every call works on (own_stream, or the caller's)
   StreamOwner own_stream;             // created by pic_create (declared ahead of the buffers: destroyed after them)
-  int post_slot = -1;                 // ring row whose post-step solve rides with the next sweep C (inside pic_step only)
-  bool refresh_pending = false;       // the last sweep was a D2 (inside pic_step only): the next sweep B deposits the positions it reads
   bool readonly_c = false;            // whole steps run sweeps C_RO and D_RC / D2_RC (pic_set_readonly_c, or readonly_auto)
-  double* hist_row = nullptr;         // where the NEXT post-step solve also records its three energies (step_recording), or null
-  double* post_hist_row = nullptr;    // the same for the solve that post_slot stands for
   PlacementStats place{};             // what the search for an (x, v) placement did, all legs together (pic_placement_stats)
   PlacementState place_state{};       // what a later leg of it needs to know (placement_leg, resume_placement)
   Recorder rec{};                     // pic_record_*: reductions recorded after every rec.stride-th step (advance, pic_step_stage)
@@ -300,21 +296,18 @@ struct __attribute__((visibility("hidden"))) pic_handle : LaunchPlan {      // t
   DeviceBuf<void> stage;          // [env][N] float staging: fixed-point positions <-> the caller's floats
   // accumulator ring: rows [env][Ng] of 64-bit fixed-point weight sums
   DeviceBuf<acc_t> ring;
-  std::vector<int> clean, dirty;  // rows that are zero / rows whose readers have all been enqueued
+  Schedule sched;                 // which rows are clean, retired or hold a cached deposit, and the rest of what the streaming
+                                  // schedule remembers between two calls (host_schedule.h)
   hipError_t ring_error = hipSuccess;   // a clearing memset of ring_take_clean that failed (reported by launch_status)
-  int q_slot = -1;                // row holding the deposit of the NEXT step's q1 (sweep A is skipped while >= 0)
-  int stage_slot = -1;            // pic_step_stage: row the next stage's field comes from
-  int sweep_parity = 0;           // direction of the next push sweep
   acc_t* probe_acc = nullptr;     // view: ring's accumulator row of the probes (their own: a probe never touches step state)
   DeviceBuf<double> probe_ext;    // device copy of a probe's host E_ext
   DeviceBuf<double> ke_part;      // [env][nblk]
   DeviceBuf<double> n;
   DeviceBuf<double> E_mesh;
   DeviceBuf<double> phi;
-  DeviceBuf<double> ext;          // device copy of a host E_ext / the actuator's field of a step, built once per environment (run_stages)
+  DeviceBuf<double> ext;          // device copy of a host E_ext / the actuator's field of a step, built once per environment (EXT_THIS)
   DeviceBuf<double> ext2;         // ... of the step after it (a rollout alternates between the two)
   DeviceBuf<double> e2;           // [env][Ng + 2] sweep C_RO's field tile, read by sweep D_RC / D2_RC
-  int ext_turn = 0;               // which of the two holds the field of the step being launched
   DeviceBuf<double> basis;        // [2][Ng][M] actuator tables (cos, sin)
   DeviceBuf<double> act;          // [env][2M] actions: device copy of a host action / the feedback law's current action
   DeviceBuf<double> modes;        // [2][env][M] Fourier modes (re, im)
@@ -328,8 +321,6 @@ struct __attribute__((visibility("hidden"))) pic_handle : LaunchPlan {      // t
   bool res_q1_valid = false;
   DeviceBuf<void> res_carry;              // ... and the cell and weights of every particle's q1 (pic_resident.h: ResidentEdge), or null
   bool res_carry_valid = false;
-  const InlineDoubles* inline_act = nullptr;   // streaming schedule, for the duration of a call: the held action rides in the sweeps' argument blocks
-  Feedback fb{};                  // feedback outputs wanted from the NEXT post-step solve of the streaming schedule (fb.M = 0: none)
   DeviceBuf<double> gain;         // [env][2M][2M] device copy of a host gain (pic_step_feedback_gain)
   DeviceBuf<double> fb_modes;     // [env][2 kMaxFeedbackModes] the gain law's m, step by step
   DeviceBuf<void> pol;            // the block of a policy call (host_policy.h: policy_parts), grown on demand
@@ -340,7 +331,6 @@ struct __attribute__((visibility("hidden"))) pic_handle : LaunchPlan {      // t
   PinnedBuf<double> h_probe_pe;   // pinned host: the energy of a probe, written by the solve itself (pic_eval_field of a small host state)
   bool probe_row_clean = false;   // the probes' accumulator row is zero (the solve of the last probe cleared it behind its read)
   DeviceBuf<double> aux_phi;
-  int mid_stage = 0;              // pic_step_stage: force evaluations of the current step already done (0 = between steps)
   DeviceBuf<double> KE;
   double* PE = nullptr;           // views into KE's block
   double* PEr = nullptr;
@@ -394,27 +384,24 @@ void with_format(const pic_handle* h, F&& f) {
   else f(PosU32{});
 }
 
-// force evaluations per step of an integrator (pic_get_integrator, pic_step_stage)
-int evals_per_step(int scheme) { return scheme == PIC_YOSHIDA4 ? 3 : (scheme == PIC_VERLET ? 2 : 1); }
-
 
 // ---- accumulator ring -------------------------------------------------------------------------
 size_t row_elems(const pic_handle* h) { return (size_t)h->S * h->cfg.num_envs * h->cfg.Ng; }       // one accumulator row: [S][env][Ng]
 acc_t* ring_row(pic_handle* h, int slot) { return h->ring + (size_t)slot * row_elems(h); }
 
-// a zeroed row for the deposit of the sweep about to be launched
+// Ring::take's guard was needed: `slot` came from the retired rows and is cleared here, ahead of the launch that fills it.  The
+// step schedule does not get here (tests/test_schedule_cpu.py: no order of calls to depth 4, and no long random one, needs it).
+// (a failure must not pass silently as a dirty row: it is kept for the caller's next check, launch_status below)
+void ring_clear_late(pic_handle* h, int slot) {
+  const hipError_t e = hipMemsetAsync(ring_row(h, slot), 0, row_elems(h) * sizeof(acc_t), h->stream);
+  if (e != hipSuccess && h->ring_error == hipSuccess) h->ring_error = e;
+}
+
+// a zeroed row for a deposit made outside the step schedule (pic_copy_envs)
 int ring_take_clean(pic_handle* h) {
-  if (h->clean.empty()) {          // not reached by the step schedule (every sweep clears two retired rows)
-    const int s = h->dirty.front();
-    h->dirty.erase(h->dirty.begin());
-    // (a failure here must not pass silently as a dirty row: it is kept for the caller's next check, pic_* entry points end
-    // with HIPCHK(h, ring_status(h)) through hipGetLastError's siblings below)
-    const hipError_t e = hipMemsetAsync(ring_row(h, s), 0, row_elems(h) * sizeof(acc_t), h->stream);
-    if (e != hipSuccess && h->ring_error == hipSuccess) h->ring_error = e;
-    return s;
-  }
-  const int s = h->clean.back();
-  h->clean.pop_back();
+  bool unclean = false;
+  const int s = h->sched.ring.take(&unclean);
+  if (unclean) ring_clear_late(h, s);
   return s;
 }
 
@@ -426,55 +413,49 @@ hipError_t launch_status(pic_handle* h) {
   return e;
 }
 
-// the last kernel reading `slot` has been enqueued: any later sweep may clear it
-void ring_retire(pic_handle* h, int slot) {
-  if (slot >= 0) h->dirty.push_back(slot);
-}
-
 template <typename P, typename A, int SHAPE, int STAGE>
-void launch_sweep_t(pic_handle* h, const SweepIO& io, void* x, void* v, const SweepArgs& a) {
+void launch_sweep_t(pic_handle* h, const SweepIO& io, void* x, void* v, const SweepArgs& a, const InlineDoubles& act) {
   dim3 grid(h->nblk + (((STAGE == ST_C || STAGE == ST_C_RO) && io.post.acc) ? 1 : 0), h->cfg.num_envs);
-  static const InlineDoubles none{};
   const size_t lds = (STAGE == ST_D_RC || STAGE == ST_D2_RC) ? h->sweep_lds_rc : h->sweep_lds;
   hipLaunchKernelGGL((sweep_kernel<P, A, SHAPE, STAGE>), grid, dim3(BLOCK), lds, h->stream,
-                     static_cast<typename P::X*>(x), static_cast<typename P::V*>(v), io, a, a.act_inline ? *h->inline_act : none);
+                     static_cast<typename P::X*>(x), static_cast<typename P::V*>(v), io, a, act);
 }
 
 template <typename P, typename A, int SHAPE>
-void launch_sweep_s(pic_handle* h, const SweepIO& io, int stage, void* x, void* v, const SweepArgs& a) {
+void launch_sweep_s(pic_handle* h, const SweepIO& io, int stage, void* x, void* v, const SweepArgs& a, const InlineDoubles& act) {
   switch (stage) {
-    case ST_A: launch_sweep_t<P, A, SHAPE, ST_A>(h, io, x, v, a); break;
-    case ST_B: launch_sweep_t<P, A, SHAPE, ST_B>(h, io, x, v, a); break;
-    case ST_C: launch_sweep_t<P, A, SHAPE, ST_C>(h, io, x, v, a); break;
-    case ST_D: launch_sweep_t<P, A, SHAPE, ST_D>(h, io, x, v, a); break;
-    case ST_REFRESH: launch_sweep_t<P, A, SHAPE, ST_REFRESH>(h, io, x, v, a); break;
-    case ST_B2: launch_sweep_t<P, A, SHAPE, ST_B2>(h, io, x, v, a); break;
-    case ST_D2: launch_sweep_t<P, A, SHAPE, ST_D2>(h, io, x, v, a); break;
-    case ST_SE: launch_sweep_t<P, A, SHAPE, ST_SE>(h, io, x, v, a); break;
-    case ST_FE: launch_sweep_t<P, A, SHAPE, ST_FE>(h, io, x, v, a); break;
-    case ST_VK: launch_sweep_t<P, A, SHAPE, ST_VK>(h, io, x, v, a); break;
-    case ST_VM: launch_sweep_t<P, A, SHAPE, ST_VM>(h, io, x, v, a); break;
-    case ST_C_RO: launch_sweep_t<P, A, SHAPE, ST_C_RO>(h, io, x, v, a); break;
-    case ST_D_RC: launch_sweep_t<P, A, SHAPE, ST_D_RC>(h, io, x, v, a); break;
-    case ST_D2_RC: launch_sweep_t<P, A, SHAPE, ST_D2_RC>(h, io, x, v, a); break;
-    default: launch_sweep_t<P, A, SHAPE, ST_PROBE>(h, io, x, v, a); break;
+    case ST_A: launch_sweep_t<P, A, SHAPE, ST_A>(h, io, x, v, a, act); break;
+    case ST_B: launch_sweep_t<P, A, SHAPE, ST_B>(h, io, x, v, a, act); break;
+    case ST_C: launch_sweep_t<P, A, SHAPE, ST_C>(h, io, x, v, a, act); break;
+    case ST_D: launch_sweep_t<P, A, SHAPE, ST_D>(h, io, x, v, a, act); break;
+    case ST_REFRESH: launch_sweep_t<P, A, SHAPE, ST_REFRESH>(h, io, x, v, a, act); break;
+    case ST_B2: launch_sweep_t<P, A, SHAPE, ST_B2>(h, io, x, v, a, act); break;
+    case ST_D2: launch_sweep_t<P, A, SHAPE, ST_D2>(h, io, x, v, a, act); break;
+    case ST_SE: launch_sweep_t<P, A, SHAPE, ST_SE>(h, io, x, v, a, act); break;
+    case ST_FE: launch_sweep_t<P, A, SHAPE, ST_FE>(h, io, x, v, a, act); break;
+    case ST_VK: launch_sweep_t<P, A, SHAPE, ST_VK>(h, io, x, v, a, act); break;
+    case ST_VM: launch_sweep_t<P, A, SHAPE, ST_VM>(h, io, x, v, a, act); break;
+    case ST_C_RO: launch_sweep_t<P, A, SHAPE, ST_C_RO>(h, io, x, v, a, act); break;
+    case ST_D_RC: launch_sweep_t<P, A, SHAPE, ST_D_RC>(h, io, x, v, a, act); break;
+    case ST_D2_RC: launch_sweep_t<P, A, SHAPE, ST_D2_RC>(h, io, x, v, a, act); break;
+    default: launch_sweep_t<P, A, SHAPE, ST_PROBE>(h, io, x, v, a, act); break;
   }
 }
 
 template <typename P>
-void launch_sweep_p(pic_handle* h, const SweepIO& io, int stage, void* x, void* v, const SweepArgs& a) {
+void launch_sweep_p(pic_handle* h, const SweepIO& io, int stage, void* x, void* v, const SweepArgs& a, const InlineDoubles& act) {
   const bool tsc = h->cfg.interpol == PIC_TSC;
   if constexpr (std::is_same<P, PosF64>::value) {
     if (h->acc_kind == PIC_ACC_F64) {
-      if (tsc) launch_sweep_s<P, double, PIC_TSC>(h, io, stage, x, v, a);
-      else launch_sweep_s<P, double, PIC_CIC>(h, io, stage, x, v, a);
+      if (tsc) launch_sweep_s<P, double, PIC_TSC>(h, io, stage, x, v, a, act);
+      else launch_sweep_s<P, double, PIC_CIC>(h, io, stage, x, v, a, act);
       return;
     }
   } else {
-    if (h->acc_kind == PIC_ACC_PACKED) { launch_sweep_s<P, fix_t, PIC_CIC>(h, io, stage, x, v, a); return; }
+    if (h->acc_kind == PIC_ACC_PACKED) { launch_sweep_s<P, fix_t, PIC_CIC>(h, io, stage, x, v, a, act); return; }
   }
-  if (tsc) launch_sweep_s<P, acc_t, PIC_TSC>(h, io, stage, x, v, a);
-  else launch_sweep_s<P, acc_t, PIC_CIC>(h, io, stage, x, v, a);
+  if (tsc) launch_sweep_s<P, acc_t, PIC_TSC>(h, io, stage, x, v, a, act);
+  else launch_sweep_s<P, acc_t, PIC_CIC>(h, io, stage, x, v, a, act);
 }
 
 // Per-launch HIP-event brackets on the handle's stream.  Events come from a pool that is only grown
@@ -531,54 +512,6 @@ SolveArgs solve_args(const pic_handle* h, int S) {
   a.scale = h->scale; a.N_over_L = (double)h->cfg.N / h->cfg.L;
   a.S = S; a.sub = (long long)h->cfg.num_envs * h->cfg.Ng;
   return a;
-}
-
-// One sweep over all environments.  in_slot: ring row the gather field is solved from (gather stages);
-// out / out2: rows (or the probe accumulator) receiving the deposits.  The sweep also clears up to two
-// retired ring rows for later use.
-void launch_sweep(pic_handle* h, int stage, void* x, void* v, double c_prev, double c_cur, double d_cur,
-                  int in_slot, const Control& ctl, acc_t* out, acc_t* out2, int post_slot = -1, double* ext_out = nullptr,
-                  const double* next_act = nullptr) {
-  SweepArgs a = sweep_args(h);
-  a.chunk = h->chunk; a.nblk = h->nblk; a.R = h->R;
-  a.act_inline = (ctl.act && h->inline_act) ? 1 : 0;
-  const bool push = stage <= ST_D || stage == ST_B2 || stage == ST_D2 || stage >= ST_SE;
-  a.reverse = push ? (h->sweep_parity ^= 1) : 0;
-  a.S = h->S; a.sub = (long long)h->cfg.num_envs * h->cfg.Ng;
-  a.c_prev = c_prev; a.c_cur = c_cur; a.d_cur = d_cur; a.c_next = h->cs[0];
-  const bool rc = stage == ST_D_RC || stage == ST_D2_RC;
-  a.d_prev = rc ? h->ds[2] : 0.0;      // the sub-stage these sweeps re-derive is sweep C's: kick d3, drift c3 (c_prev)
-  SweepIO io{};
-  io.acc_in = in_slot >= 0 ? ring_row(h, in_slot) : nullptr;
-  io.ctl = ctl;
-  io.ext_out = (ctl.act || next_act) ? ext_out : nullptr;
-  io.next_act = next_act;
-  io.acc_out = out;
-  io.acc_out2 = out2;
-  int z[2] = {-1, -1};
-  for (int k = 0; k < 2 && !h->dirty.empty(); ++k) {
-    z[k] = h->dirty.front();
-    h->dirty.erase(h->dirty.begin());
-  }
-  io.zero0 = z[0] >= 0 ? ring_row(h, z[0]) : nullptr;
-  io.zero1 = z[1] >= 0 ? ring_row(h, z[1]) : nullptr;
-  io.ke_part = h->ke_part;
-  io.bad = out == h->probe_acc ? h->probe_bad : h->bad;
-  io.e2 = h->e2;
-  if (post_slot >= 0) {            // sweep C also carries the previous step's post-step refresh (pic_sweep.h: SweepIO::post)
-    io.post.acc = ring_row(h, post_slot);
-    io.post.ke_part = h->ke_part; io.post.n = h->n; io.post.out.E = h->E_mesh; io.post.out.phi = h->phi;
-    io.post.out.KE = h->KE; io.post.out.PE = h->PE; io.post.out.PEr = h->PEr;
-    io.post.out.hist = h->post_hist_row; io.post.out.num_envs = h->cfg.num_envs;
-  }
-  // (the particle sweeps of the other integrators -- Verlet's opening sweep is a sweep C -- count in the eighth kind)
-  const bool scheme_sweep = (stage >= ST_SE && stage <= ST_VM) || (stage == ST_C && h->scheme != PIC_YOSHIDA4);
-  prof_begin(h, scheme_sweep ? 7 : stage <= ST_D ? stage : stage == ST_B2 ? (int)ST_B : stage == ST_C_RO ? (int)ST_C
-                : (stage == ST_D2 || rc) ? (int)ST_D : 5);
-  with_format(h, [&](auto p) { launch_sweep_p<decltype(p)>(h, io, stage, x, v, a); });
-  prof_end(h);
-  for (int k = 0; k < 2; ++k)
-    if (z[k] >= 0) h->clean.push_back(z[k]);      // zero for every LATER launch of this stream
 }
 
 template <typename P, typename A, int SHAPE, int PPT, int NW>
@@ -691,39 +624,86 @@ void launch_solve(pic_handle* h, const SolveIO& io) {
   prof_end(h);
 }
 
-// the post-step refresh (pic.py:145-146, no external field: pic.py:114-117) from the deposit in ring row `slot`; retire = false
-// (the other integrators): the row stays, as the deposit the next step's force is solved from
-void launch_final_solve(pic_handle* h, int slot, bool retire = true) {
-  SolveIO o{};
-  o.acc = ring_row(h, slot);
-  o.ke_part = h->ke_part; o.n = h->n; o.out.E = h->E_mesh; o.out.phi = h->phi;
-  o.out.KE = h->KE; o.out.PE = h->PE; o.out.PEr = h->PEr;
-  o.out.hist = h->hist_row; o.out.num_envs = h->cfg.num_envs;
-  o.out.fb = h->fb;
-  launch_solve(h, o);
-  if (retire) ring_retire(h, slot);
+// What the launches of one call need besides the schedule's descriptors.  It lives on the caller's stack for that call.
+struct CallCtx {
+  const StepControl* sc = nullptr;   // the call's control: its fields or actions, the feedback law, the inline action (null: none)
+  double* hist = nullptr;            // device [nsteps][3][env] record of the energies, or null
+  void* probe_x = nullptr;           // a field probe: the positions it deposits instead of the state's
+};
+
+// The one place that turns a Launch of the step schedule (host_schedule.h) into kernel arguments and a launch.
+void run_launch(pic_handle* h, const CallCtx& cx, const Launch& d) {
+  const int E = h->cfg.num_envs;
+  if (d.stage == ST_SOLVE) {
+    SolveIO o{};
+    o.acc = ring_row(h, d.in);
+    o.ke_part = h->ke_part; o.n = h->n; o.out.E = h->E_mesh; o.out.phi = h->phi;
+    o.out.KE = h->KE; o.out.PE = h->PE; o.out.PEr = h->PEr;
+    o.out.hist = hist_at(h, cx.hist, d.step); o.out.num_envs = E;
+    if (d.feedback) {                // the action of step + 1 is the feedback law's on the field this solve leaves
+      o.out.fb = cx.sc->after(d.step + 1, E).fb;
+      o.out.fb.act_out = h->act;
+    }
+    launch_solve(h, o);
+    return;
+  }
+  for (int k = 0; k < 2; ++k)
+    if (d.unclean >> k & 1) ring_clear_late(h, d.fill[k]);
+  auto row = [&](int slot) { return slot >= 0 ? ring_row(h, slot) : nullptr; };
+  double* const field[2] = {h->ext.get(), h->ext2.get()};
+  Control ctl{};
+  if (d.ctl != CTL_NONE && cx.sc) {
+    ctl = cx.sc->after(d.step, E).ctl;
+    if (cx.sc->fb.M > 0) { ctl.act = h->act; ctl.ext = nullptr; }
+    if (d.ctl == CTL_SHARED) { ctl.act = nullptr; ctl.ext = field[d.turn]; }
+  }
+  SweepArgs a = sweep_args(h);
+  a.chunk = h->chunk; a.nblk = h->nblk; a.R = h->R;
+  a.act_inline = (ctl.act && cx.sc->inline_n > 0) ? 1 : 0;      // the held action rides in the sweep's argument block
+  a.reverse = d.reverse;
+  a.S = h->S; a.sub = (long long)E * h->cfg.Ng;
+  a.c_prev = d.c_prev; a.c_cur = d.c_cur; a.d_cur = d.d_cur; a.c_next = h->cs[0];
+  const bool rc = d.stage == ST_D_RC || d.stage == ST_D2_RC;
+  a.d_prev = rc ? h->ds[2] : 0.0;      // the sub-stage these sweeps re-derive is sweep C's: kick d3, drift c3 (c_prev)
+  SweepIO io{};
+  io.acc_in = row(d.in);
+  io.ctl = ctl;
+  if (d.ext_out != EXT_NONE) io.ext_out = field[d.ext_out == EXT_THIS ? d.turn : d.turn ^ 1];
+  if (d.hand_on) io.next_act = cx.sc->after(d.step + 1, E).ctl.act;
+  io.acc_out = row(d.fill[0]);
+  io.acc_out2 = row(d.fill[1]);
+  io.zero0 = row(d.clear[0]);
+  io.zero1 = row(d.clear[1]);
+  io.ke_part = h->ke_part;
+  io.bad = d.fill[0] == RING ? h->probe_bad : h->bad;
+  io.e2 = h->e2;
+  if (d.post >= 0) {               // sweep C also carries the previous step's post-step refresh (pic_sweep.h: SweepIO::post)
+    io.post.acc = ring_row(h, d.post);
+    io.post.ke_part = h->ke_part; io.post.n = h->n; io.post.out.E = h->E_mesh; io.post.out.phi = h->phi;
+    io.post.out.KE = h->KE; io.post.out.PE = h->PE; io.post.out.PEr = h->PEr;
+    io.post.out.hist = hist_at(h, cx.hist, d.post_step); io.post.out.num_envs = E;
+  }
+  void* x = cx.probe_x ? cx.probe_x : h->x.get();
+  void* v = cx.probe_x ? cx.probe_x : h->v;
+  static const InlineDoubles none{};
+  const InlineDoubles& act = a.act_inline ? cx.sc->inline_act : none;
+  // (the particle sweeps of the other integrators -- Verlet's opening sweep is a sweep C -- count in the eighth kind)
+  const int stage = d.stage;
+  const bool scheme_sweep = (stage >= ST_SE && stage <= ST_VM) || (stage == ST_C && h->scheme != PIC_YOSHIDA4);
+  prof_begin(h, scheme_sweep ? 7 : stage <= ST_D ? stage : stage == ST_B2 ? (int)ST_B : stage == ST_C_RO ? (int)ST_C
+                : (stage == ST_D2 || rc) ? (int)ST_D : 5);
+  with_format(h, [&](auto p) { launch_sweep_p<decltype(p)>(h, io, stage, x, v, a, act); });
+  prof_end(h);
 }
 
 void drop_cached_deposits(pic_handle* h) {
-  ring_retire(h, h->q_slot);
-  ring_retire(h, h->stage_slot);
-  h->q_slot = h->stage_slot = -1;
-  h->mid_stage = 0;
+  plan_drop(h->sched);
   h->res_q1_valid = false;
 }
 
 int refresh_fields(pic_handle* h) {
-  drop_cached_deposits(h);
-  const int f = ring_take_clean(h), qn = ring_take_clean(h);
-  launch_sweep(h, ST_REFRESH, h->x, h->v, 0, 0, 0, -1, Control{}, ring_row(h, f), ring_row(h, qn));
-  if (h->scheme == PIC_YOSHIDA4) {
-    launch_final_solve(h, f);
-    h->q_slot = qn;   // ST_REFRESH also deposited the next step's q1
-  } else {
-    launch_final_solve(h, f, false);
-    ring_retire(h, qn);
-    h->q_slot = f;    // the other integrators start from the deposit of x itself
-  }
+  h->res_q1_valid = false;
+  plan_refresh(h->sched, h->scheme, [&](const Launch& d) { run_launch(h, CallCtx{}, d); });
   HIPCHK(h, launch_status(h));
   return PIC_OK;
 }
@@ -933,7 +913,6 @@ int pic_create(const pic_config* cfg, pic_handle** out) {
   if (hipError_t e = alloc_zeroed(h->ring, (size_t)(RING + 1) * h->S * gbytes, h->stream))      // acc_t and double are both 8 bytes
     return failed(e, "accumulator ring");
   h->probe_acc = ring_row(h, RING);
-  for (int s = 0; s < RING; ++s) h->clean.push_back(s);
   if (h->resident) {
     const size_t qbytes = (size_t)cfg->num_envs * h->res_R * stride * sizeof(unsigned long long);
     if (hipError_t e = alloc_zeroed(h->res_q1, qbytes, h->stream)) return failed(e, "resident q1 meshes");
@@ -1056,88 +1035,6 @@ int pic_reset(pic_handle* h, const void* x0, const void* v0, int mem_kind) {
   return refresh_fields(h);
 }
 
-// the sweeps of one environment step; `upto`: 1 = through sweep B, 2 = through C, 3 = whole step.  from: first
-// stage to run (1, 2, 3).  Each force evaluation takes `ctl` (may differ per stage in the staged entry point).
-// another_step_follows (the steps of one call but the last): this step ends with sweep D2, which leaves the deposit of its final
-// positions to the next step's sweep B2, and its post-step solve is not launched: that step's sweep C carries it in one extra
-// workgroup per environment (its results -- n, E_mesh, phi, the energies -- are read by nothing inside the call; the last step
-// ends with the full sweep D and a solve launch of its own as ever).  Every refresh is made, from the same integer sums.
-static void run_stages(pic_handle* h, int from, int upto, const Control& ctl, bool another_step_follows = false,
-                       bool field_ready = false, const double* next_act = nullptr) {
-  const double* c = h->cs;
-  const double* d = h->ds;
-  // A whole step under actuator coefficients builds the actuator's field once per environment, not in every workgroup of every
-  // sweep (pic_sweep.h: SweepIO::ext_out).  h->ext / h->ext2 -- idle in such a call: they stage host fields -- take turns:
-  // `mine` holds this step's field, written by sweep B of a call's first step (which builds it in every workgroup: it cannot
-  // wait for anyone) or by the previous step's sweep D (field_ready); sweep D writes the next step's from next_act into the
-  // other one.  Same doubles, same sums: config 3 as specified pays 0.5 % for its control instead of 2.6 %.
-  const bool share_field = from == 1 && upto == 3 && ctl.act != nullptr;
-  double* mine = h->ext_turn ? h->ext2 : h->ext;
-  double* other = h->ext_turn ? h->ext : h->ext2;
-  Control first = ctl, later = ctl;
-  // A whole step runs sweep C without its stores where the handle chose it (readonly_c): sweep D re-derives them.  A staged step
-  // keeps them, since its caller may read the particles between the stages.
-  const bool ro = h->readonly_c && from <= 2 && upto == 3;
-  if (share_field) {
-    later.act = nullptr; later.ext = mine;
-    if (field_ready) first = later;
-  }
-  for (int st = from; st <= upto; ++st) {
-    if (st == 1) {
-      if (h->q_slot < 0) {          // particles were loaded without a refresh: deposit q1 = x + (c1 v) dt now
-        h->q_slot = ring_take_clean(h);
-        launch_sweep(h, ST_A, h->x, h->v, 0.0, c[0], 0.0, -1, Control{}, ring_row(h, h->q_slot), nullptr);
-      }
-      const int x1 = ring_take_clean(h);
-      if (h->refresh_pending) {
-        // the step before ended with sweep D2: this sweep B deposits the positions it reads (that step's x') into row r, and sweep C
-        // carries the post-step solve of that step from it
-        const int r = ring_take_clean(h);
-        launch_sweep(h, ST_B2, h->x, h->v, c[0], c[1], d[1], h->q_slot, first, ring_row(h, x1), ring_row(h, r), -1,
-                     share_field && !field_ready ? mine : nullptr);
-        h->refresh_pending = false;
-        h->post_slot = r;
-      } else {
-        launch_sweep(h, ST_B, h->x, h->v, c[0], c[1], d[1], h->q_slot, first, ring_row(h, x1), nullptr, -1,
-                     share_field && !field_ready ? mine : nullptr);
-      }
-      ring_retire(h, h->q_slot);
-      h->q_slot = -1;
-      h->stage_slot = x1;
-    } else if (st == 2) {
-      const int x2 = ring_take_clean(h);
-      launch_sweep(h, ro ? ST_C_RO : ST_C, h->x, h->v, 0.0, c[2], d[2], h->stage_slot, later, ring_row(h, x2), nullptr, h->post_slot);
-      ring_retire(h, h->post_slot);
-      h->post_slot = -1;
-      ring_retire(h, h->stage_slot);
-      h->stage_slot = x2;
-    } else {
-      const bool hand_on = share_field && next_act != nullptr;
-      if (another_step_follows && h->light_inner_steps) {
-        // an inner step of a call: nothing can see its post-step fields before the next step has started, so the deposit they come
-        // from is left to that step's sweep B2 (sweep D is the one sweep bound by VALU issue: 336 -> 321 us at config 2, B 320 -> 322)
-        const int qn = ring_take_clean(h);
-        launch_sweep(h, ro ? ST_D2_RC : ST_D2, h->x, h->v, ro ? c[2] : 0.0, c[3], d[3], h->stage_slot, later, nullptr, ring_row(h, qn), -1,
-                     hand_on ? other : nullptr, hand_on ? next_act : nullptr);
-        h->refresh_pending = true;
-        h->post_hist_row = h->hist_row;
-        h->q_slot = qn;
-      } else {
-        const int f = ring_take_clean(h), qn = ring_take_clean(h);
-        launch_sweep(h, ro ? ST_D_RC : ST_D, h->x, h->v, ro ? c[2] : 0.0, c[3], d[3], h->stage_slot, later, ring_row(h, f), ring_row(h, qn), -1,
-                     hand_on ? other : nullptr, hand_on ? next_act : nullptr);
-        // (a small state's inner step: the full sweep D, its solve still not a launch -- it rides with the next step's sweep C)
-        if (another_step_follows) { h->post_slot = f; h->post_hist_row = h->hist_row; }
-        else launch_final_solve(h, f);
-        h->q_slot = qn;
-      }
-      if (hand_on) h->ext_turn ^= 1;
-      ring_retire(h, h->stage_slot);
-      h->stage_slot = -1;
-    }
-  }
-}
-
 // host -> device staging of a call's inputs.  Small per-step inputs have buffers of their own (h->ext, h->act); whole
 // trajectories go through h->traj, grown on demand.
 static int ensure_traj(pic_handle* h, size_t bytes) {
@@ -1163,49 +1060,14 @@ static int ensure_twiddle(pic_handle* h, int rows) {
   return PIC_OK;
 }
 
-// ---- the other integrators on the streaming schedule (pic_set_integrator) ----------------------------------------
-// Between steps h->q_slot holds the deposit of the stored, wrapped x: the post-step deposit of the step before, which is also the
-// field of the next step's (first) force evaluation -- one row, no first drift to deposit.  Where it is missing (particles loaded
-// without a refresh, or a Yoshida-4 q1 dropped by a change of scheme) a probe sweep deposits x.
-static void scheme_first_deposit(pic_handle* h) {
-  if (h->q_slot >= 0) return;
-  h->q_slot = ring_take_clean(h);
-  launch_sweep(h, ST_PROBE, h->x, h->v, 0.0, 0.0, 0.0, -1, Control{}, ring_row(h, h->q_slot), nullptr);
-}
-
-// One step's sweeps under `ctl`, or its stage `only` (1..S) for pic_step_stage.  merge (Verlet, a further step follows with the
-// same external field): the closing half-kick of this step and the opening half-kick and drift of the next one are ONE sweep
-// (ST_VM), two additions in the order separate sweeps make them; *open tells the next step that its opening sweep is done.
-static void run_scheme_step(pic_handle* h, const Control& ctl, int only, bool merge, bool* open) {
-  if (h->scheme != PIC_VERLET) {
-    scheme_first_deposit(h);
-    const int f = ring_take_clean(h);
-    launch_sweep(h, h->scheme == PIC_SYMPLECTIC_EULER ? ST_SE : ST_FE, h->x, h->v, 0.0, 1.0, 1.0, h->q_slot, ctl, ring_row(h, f),
-                 nullptr);                                   // integration.py:50-51 (c = d = 1) / :8-10
-    ring_retire(h, h->q_slot);
-    launch_final_solve(h, f, false);
-    h->q_slot = f;
-    return;
-  }
-  if (only != 2 && !(open && *open)) {                       // step(c = 1, d = 0.5): kick, drift, deposit of q' (a sweep C)
-    scheme_first_deposit(h);
-    const int r = ring_take_clean(h);
-    launch_sweep(h, ST_C, h->x, h->v, 0.0, 1.0, 0.5, h->q_slot, ctl, ring_row(h, r), nullptr);
-    ring_retire(h, h->q_slot);
-    h->q_slot = r;
-  }
-  if (only == 1) return;
-  if (merge) {                                               // step(c = 0, d = 0.5), then the next step's step(c = 1, d = 0.5)
-    const int r = ring_take_clean(h);
-    launch_sweep(h, ST_VM, h->x, h->v, 0.0, 1.0, 0.5, h->q_slot, ctl, ring_row(h, r), nullptr);
-    launch_final_solve(h, h->q_slot);                        // this step's refresh: KE from the merged sweep, n and E from x''s deposit
-    h->q_slot = r;
-    *open = true;
-  } else {                                                   // step(c = 0, d = 0.5): the closing half-kick alone
-    launch_sweep(h, ST_VK, h->x, h->v, 0.0, 0.0, 0.5, h->q_slot, ctl, nullptr, nullptr);
-    launch_final_solve(h, h->q_slot, false);
-    if (open) *open = false;
-  }
+// the shape of a call under `sc`, for the step schedule (host_schedule.h)
+static CallShape call_shape(const pic_handle* h, const StepControl& sc) {
+  CallShape p;
+  p.scheme = h->scheme; p.cs = h->cs; p.ds = h->ds;
+  p.light_inner_steps = h->light_inner_steps; p.readonly_c = h->readonly_c;
+  p.feedback = sc.fb.M > 0; p.action = sc.ctl.act != nullptr;
+  p.per_step_field = sc.ext_step != 0; p.per_step_action = sc.act_step != 0;
+  return p;
 }
 
 // nsteps x PIC.update_state under `sc`, all launches enqueued, no host synchronisation.  hist: device [nsteps][3][env] record of
@@ -1215,9 +1077,7 @@ static int advance_steps(pic_handle* h, const StepControl& sc, int nsteps, doubl
   const int E = h->cfg.num_envs;
   if (h->resident) {
     launch_resident(h, sc, nsteps, hist, snap);
-    ring_retire(h, h->q_slot);       // the ring's q1 deposit belongs to the particles before these steps
-    ring_retire(h, h->stage_slot);
-    h->q_slot = h->stage_slot = -1;
+    h->sched.drop_rows();            // the ring's q1 deposit belongs to the particles before these steps
     // the q1 mesh and the carried cells the kernel leaves behind are valid only if the launch went out: after a failed one the
     // next call must deposit q1 itself instead of taking over an unwritten block (the other integrators' kernel leaves none)
     const hipError_t e = launch_status(h);
@@ -1226,46 +1086,16 @@ static int advance_steps(pic_handle* h, const StepControl& sc, int nsteps, doubl
     HIPCHK(h, e);
     return PIC_OK;
   }
-  h->inline_act = sc.inline_n > 0 ? &sc.inline_act : nullptr;      // (launch_sweep: the held action inside the sweeps' arguments)
-  // (Yoshida-4: the actuator's field of step s is built by sweep B of step 0, after that by the previous step's sweep D -- or,
-  // under a held action, still the one step 0 left; the feedback law's action exists only after the post-step solve: every step
-  // builds)
-  const bool rollout = sc.fb.M == 0 && sc.ctl.act != nullptr;
-  // Verlet merges where the two half-kicks of a merged sweep see one external field: held for the call.  A new field every step,
-  // or the feedback law's (whose action needs the post-step solve first), runs two sweeps per step.
-  const bool held = sc.fb.M == 0 && sc.ext_step == 0 && sc.act_step == 0;
-  bool open = false;
-  for (int s = 0; s < nsteps; ++s) {
-    const bool last = s + 1 == nsteps;
-    Control ctl = sc.after(s, E).ctl;
-    h->hist_row = hist_at(h, hist, s);
-    if (sc.fb.M > 0) {
-      // The action of step s is the feedback law's on the field step s-1 left: the post-step solve is on the critical path
-      // (a launch of its own that also computes the next action); before the first step a small kernel does it.
-      if (s == 0) {
-        Feedback fb = sc.fb;
-        fb.act_out = h->act;
-        hipLaunchKernelGGL(feedback_kernel, dim3(E), dim3(BLOCK), 0, h->stream, h->E_mesh, fb, h->cfg.Ng);
-      }
-      ctl.act = h->act;
-      ctl.ext = nullptr;
-      h->fb = Feedback{};
-      if (!last) {
-        h->fb = sc.after(s + 1, E).fb;
-        h->fb.act_out = h->act;
-      }
-    }
-    if (h->scheme == PIC_YOSHIDA4) {
-      // the post-step solve rides with the next step's sweep C, but for the last step's and the feedback law's
-      const double* next_act = (rollout && sc.act_step != 0 && !last) ? sc.after(s + 1, E).ctl.act : nullptr;
-      run_stages(h, 1, 3, ctl, !last && sc.fb.M == 0, rollout && s > 0, next_act);
-    } else {
-      run_scheme_step(h, ctl, 0, held && !last, &open);
-    }
+  if (sc.fb.M > 0) {
+    // The action of step s is the feedback law's on the field step s-1 left: the post-step solve is on the critical path
+    // (a launch of its own that also computes the next action); before the first step a small kernel does it.
+    Feedback fb = sc.fb;
+    fb.act_out = h->act;
+    hipLaunchKernelGGL(feedback_kernel, dim3(E), dim3(BLOCK), 0, h->stream, h->E_mesh, fb, h->cfg.Ng);
   }
-  h->hist_row = h->post_hist_row = nullptr;
-  h->fb = Feedback{};
-  h->inline_act = nullptr;
+  CallCtx cx;
+  cx.sc = &sc; cx.hist = hist;
+  plan_call(h->sched, call_shape(h, sc), nsteps, [&](const Launch& d) { run_launch(h, cx, d); });
   HIPCHK(h, launch_status(h));
   return PIC_OK;
 }
@@ -1384,7 +1214,7 @@ int pic_step_stage(pic_handle* h, int stage, const double* E_ext, int mem_kind) 
   if (h->tape.on) return fail(h, PIC_ESTATE, "pic_step_stage: refused while a tape is open (pic_tape_stop first)");
   if (!h->has_state) return fail(h, PIC_ESTATE, "pic_step_stage: call pic_reset first");
   const int S = evals_per_step(h->scheme);
-  if (stage < 1 || stage > S || stage != h->mid_stage + 1)
+  if (stage < 1 || stage > S || stage != h->sched.mid_stage + 1)
     return fail(h, PIC_ESTATE, "pic_step_stage: stages run in the order 1.." + std::to_string(S) + " of the handle's integrator");
   if (stage == 1 && h->rec.on && (int64_t)h->rec.steps.size() + records_ahead(h, 1) > h->rec.cap)
     return fail(h, PIC_ENOMEM, "pic_step_stage: the step would take the recorder past its capacity");
@@ -1393,9 +1223,11 @@ int pic_step_stage(pic_handle* h, int stage, const double* E_ext, int mem_kind) 
   int rc = stage_ext(h, E_ext, mem_kind, &ctl.ext);
   if (rc) return rc;
   h->res_q1_valid = false;           // (a resident handle steps by sweeps here: its carried q1 mesh goes stale)
-  if (h->scheme == PIC_YOSHIDA4) run_stages(h, stage, stage, ctl);
-  else run_scheme_step(h, ctl, S == 1 ? 0 : stage, false, nullptr);
-  h->mid_stage = stage == S ? 0 : stage;
+  StepControl sc;
+  sc.ctl = ctl;
+  CallCtx cx;
+  cx.sc = &sc;
+  plan_stage(h->sched, call_shape(h, sc), stage, [&](const Launch& d) { run_launch(h, cx, d); });
   HIPCHK(h, hipGetLastError());
   if (stage == S && h->rec.on && ++h->rec.k % h->rec.stride == 0) return record_enqueue(h);
   return PIC_OK;
@@ -1405,7 +1237,7 @@ int pic_set_integrator(pic_handle* h, int scheme) {
   if (!h) return PIC_EINVAL;
   if (h->tape.on) return fail(h, PIC_ESTATE, "pic_set_integrator: refused while a tape is open (pic_tape_stop first)");
   if (scheme < PIC_YOSHIDA4 || scheme > PIC_FORWARD_EULER) return fail(h, PIC_EINVAL, "pic_set_integrator: unknown scheme");
-  if (h->mid_stage) return fail(h, PIC_ESTATE, "pic_set_integrator: a staged step is in progress (finish its pic_step_stage calls)");
+  if (h->sched.mid_stage) return fail(h, PIC_ESTATE, "pic_set_integrator: a staged step is in progress (finish its pic_step_stage calls)");
   if (scheme == h->scheme) return PIC_OK;
   drop_cached_deposits(h);           // the cached deposit belongs to a scheme (Yoshida-4: q1 = x + (c1 v) dt; the others: x)
   h->scheme = scheme;
@@ -1431,7 +1263,7 @@ int pic_get_integrator(pic_handle* h, int* scheme, int* evals) {
 static int check_steppable(pic_handle* h, int nsteps, const char* who) {
   if (!h->has_state) return fail(h, PIC_ESTATE, std::string(who) + ": call pic_reset first");
   if (nsteps < 0) return fail(h, PIC_EINVAL, std::string(who) + ": nsteps < 0");
-  if (h->mid_stage) return fail(h, PIC_ESTATE, std::string(who) + ": a staged step is in progress (finish its pic_step_stage calls)");
+  if (h->sched.mid_stage) return fail(h, PIC_ESTATE, std::string(who) + ": a staged step is in progress (finish its pic_step_stage calls)");
   if (h->rec.on && (int64_t)h->rec.steps.size() + records_ahead(h, nsteps) > h->rec.cap)
     return fail(h, PIC_ENOMEM, std::string(who) + ": the steps would take the recorder past its capacity (read and restart it, or "
                                                    "record with a larger capacity)");
@@ -1748,7 +1580,9 @@ static int probe_solve(pic_handle* h, const double* E_ext, bool want_phi, void* 
   // (the solve zeroes the row behind its read: one command less per probe; a probe that failed half way leaves it unknown)
   if (!h->probe_row_clean) HIPCHK(h, hipMemsetAsync(h->probe_acc, 0, row_elems(h) * sizeof(acc_t), h->stream));
   h->probe_row_clean = false;
-  launch_sweep(h, ST_PROBE, xs, xs, 0, 0, 0, -1, Control{}, h->probe_acc, nullptr);
+  CallCtx cx;
+  cx.probe_x = xs;
+  plan_probe(h->sched, [&](const Launch& d) { run_launch(h, cx, d); });
   SolveIO o{};
   o.acc = h->probe_acc; o.acc_clear = h->probe_acc; o.out.ext = ext; o.n = h->aux_n; o.out.E = h->aux_E;
   o.out.PEr = pe_out ? pe_out : h->aux_pe;
@@ -2119,7 +1953,7 @@ int pic_phase_kl(pic_handle* h, int nbins, double vmin, double vmax, const doubl
 int pic_record_start(pic_handle* h, const pic_record_config* c) {
   if (!h || !c) return fail(h, PIC_EINVAL, "pic_record_start: null argument");
   if (h->rec.on) return fail(h, PIC_ESTATE, "pic_record_start: already recording (pic_record_stop first)");
-  if (h->mid_stage) return fail(h, PIC_ESTATE, "pic_record_start: a staged step is in progress (finish its pic_step_stage calls)");
+  if (h->sched.mid_stage) return fail(h, PIC_ESTATE, "pic_record_start: a staged step is in progress (finish its pic_step_stage calls)");
   const int Ng = h->cfg.Ng;
   const bool phase = c->phase_x_bins > 0 || c->phase_v_bins > 0;
   if (c->stride < 1 || c->n_modes < 0 || c->n_modes > Ng / 2 + 1 || c->x_bins < 0 || c->x_bins > 4096 || c->v_bins < 0 ||
@@ -2181,7 +2015,7 @@ int pic_record_now(pic_handle* h) {
   if (!h) return PIC_EINVAL;
   if (!h->rec.on) return fail(h, PIC_ESTATE, "pic_record_now: not recording (pic_record_start first)");
   if (!h->has_state) return fail(h, PIC_ESTATE, "pic_record_now: call pic_reset first");
-  if (h->mid_stage) return fail(h, PIC_ESTATE, "pic_record_now: a staged step is in progress (finish its pic_step_stage calls)");
+  if (h->sched.mid_stage) return fail(h, PIC_ESTATE, "pic_record_now: a staged step is in progress (finish its pic_step_stage calls)");
   if ((int64_t)h->rec.steps.size() >= h->rec.cap) return fail(h, PIC_ENOMEM, "pic_record_now: the recorder is full");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   return record_enqueue(h);

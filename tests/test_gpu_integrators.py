@@ -365,6 +365,30 @@ def test_sweeps_per_call(oc, scheme, K):
     assert prof["sweep_integrator"][1] == (K + 1 if scheme == "verlet" and K > 1 else (2 * K if scheme == "verlet" else K))
 
 
+def test_launches_match_schedule(oc):
+    """One launch per descriptor of the step schedule: the launches per profile kind of reset, step(1), step(3), step_history(2),
+    read-only C with step(3), then Verlet with step(3) are the counts tests/schedule_driver.cpp prints for the script
+    "0 0 0 i r s1 s3 s2 o1 s3 k2 s3" (tests/test_schedule_cpu.py::test_gpu_script_launch_counts holds the driver to them)."""
+    E, N, Ng, L = 2, 3000, 64, 50.0
+    env = oc.BatchedPIC(E, N, Ng, L=L, dt=0.1, blocks_per_env=2)
+    assert env._h.schedule() == "streaming"
+    rng = np.random.default_rng(11)
+    env.profile(True)
+    env.reset(rng.uniform(0.0, L, (E, N)), rng.normal(0.0, 1.0, (E, N)))
+    env.step(None, 1)
+    env.step(None, 3)
+    env.step_history(None, 2)
+    env._h.set_readonly_c("on")
+    env.step(None, 3)
+    env._h.set_integrator("verlet")
+    env.step(None, 3)
+    env.sync()
+    prof = {k: n for k, (_, n) in env.profile_read().items()}
+    env.close()
+    # (profile_read leaves out the kinds that never ran: no sweep A, no resident launch)
+    assert prof == {"sweep_B": 9, "sweep_C": 9, "sweep_D": 9, "field_solve": 8, "sweep_aux": 2, "sweep_integrator": 4}, prof
+
+
 # -- 7. switching schemes -------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("scheme", SCHEMES)
 @pytest.mark.parametrize("bpe", [-1, 2])
