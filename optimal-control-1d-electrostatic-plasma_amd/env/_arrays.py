@@ -1,9 +1,32 @@
 """Where the arrays of one call of the differentiation layer live: host memory as NumPy arrays, or device memory
 as float64 CUDA tensors.  `Mem` is decided once per call and is the only place that knows which; torch is imported only when a
-call works on the device."""
+call works on the device.  `directions` reads the number of directions of a forward-mode call off its inputs."""
 import numpy as np
 
 from .._abi import PIC_DEVICE, PIC_HOST
+
+
+def directions(who, base, given, K=None, walk=None):
+    """(K, batched) of a forward-mode call: the number of directions and whether its arrays carry a leading K axis.  `given`:
+    name -> array (None = absent); `base`: name -> shape without K.  From K if given (then they do), else from the inputs;
+    `walk`: the fixed (K, batched) of a walk in progress, which the inputs of a step must match.  ValueError(who: ...) if the
+    inputs disagree or one has another shape.  K is not capped here: the library refuses K > 8."""
+    shapes = {k: tuple(a.shape) for k, a in given.items() if a is not None}
+    if walk is not None:
+        K, batched = walk
+    else:
+        ks = {s[0] for k, s in shapes.items() if len(s) == len(base[k]) + 1}
+        if K is not None:
+            ks.add(int(K))
+        if len(ks) > 1:
+            raise ValueError(f"{who}: the inputs disagree on the number of directions: {sorted(ks)}")
+        batched = bool(ks)
+        K = ks.pop() if ks else 1
+    for k, s in shapes.items():
+        want = ((K,) if batched else ()) + base[k]
+        if s != want:
+            raise ValueError(f"{who}: {k} must have shape {want}, not {s}")
+    return K, batched
 
 
 class Mem:
