@@ -1,0 +1,63 @@
+"""examples/policy_gradient.py's DeepSets policy with the per-particle layer and the mean computed by the library
+(control.pool.PoolEncoder -> pic_pool / pic_pool_vjp): no [num_envs, N, hidden] tensor exists in the forward or in
+the backward.  phi is one layer, tanh(W (cos q, sin q, v) + b), in float64; rho is the example's.  Trained with Adam on the same
+cost on the same ensemble; prints J (mean over the ensemble) for each iteration.
+
+    python examples/pooled_policy.py [num_envs] [N] [steps] [iterations]
+"""
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import ocplasma_amd  # noqa: F401,E402
+from ocplasma_amd import BatchedPIC, E_field  # noqa: E402
+from ocplasma_amd.control.pool import PoolEncoder  # noqa: E402
+from policy_gradient import iteration  # noqa: E402
+
+
+class PooledDeepSets(torch.nn.Module):
+    """(x, v) [E, N] each -> actions [E, 2M]: PoolEncoder (phi and the mean, on the device's own kernels), then rho; the last
+    layer starts at zero (a = 0: the uncontrolled plasma)."""
+
+    def __init__(self, env, max_mode, hidden=32):
+        super().__init__()
+        self.enc = PoolEncoder(env, hidden)
+        self.rho = torch.nn.Sequential(torch.nn.Linear(hidden, hidden), torch.nn.Tanh(), torch.nn.Linear(hidden, 2 * max_mode)).double()
+        torch.nn.init.zeros_(self.rho[-1].weight)
+        torch.nn.init.zeros_(self.rho[-1].bias)
+
+    def forward(self, xv):
+        return self.rho(self.enc(xv))
+
+
+def make(env, max_mode, hidden=32):
+    torch.manual_seed(0)
+    return PooledDeepSets(env, max_mode, hidden).to("cuda")
+
+
+def run(num_envs=64, N=5000, steps=50, iters=10, N_mesh=250, L=50.0, max_mode=5, lam=0.1, lr=0.02, seed=3):
+    env = BatchedPIC(num_envs, N, N_mesh, L=L, dt=0.1)
+    env.set_actuator(E_field(L, N_mesh, max_mode))
+    env.use_torch_stream()
+    policy = make(env, max_mode)
+    opt = torch.optim.Adam(policy.parameters(), lr=lr)
+    history = []
+    for it in range(iters):
+        t0 = time.perf_counter()
+        opt.zero_grad()
+        J = iteration(env, policy, "state", steps, max_mode, lam, L, seed)
+        opt.step()
+        history.append(float(J.mean()))
+        print(f"pooled  iter {it:2d}  J = {history[-1]:.6e}  ({time.perf_counter() - t0:.3f} s)", flush=True)
+    env.stop_tape()
+    env.close()
+    return history
+
+
+if __name__ == "__main__":
+    h = run(*[int(a) for a in sys.argv[1:]])
+    print(f"pooled: J {h[0]:.6e} -> {h[-1]:.6e}")

@@ -858,6 +858,46 @@ int pic_tape_tangent_policy(pic_handle* h, int K, const double* d_params, const 
                             const void* d_x0, const void* d_v0, int mem_kind, double* d_hist, double* d_obs, double* d_pre_out,
                             double* d_actions_out, void* d_x, void* d_v, double* d_E_mesh);
 
+/* ---- Pooled particle features (additive to ABI 5) ------------------------------------------------------------
+ * A DeepSets encoder's per-particle layer and mean, without an [N][H] array.  Per environment, with H = hidden units (1..256),
+ * parameters W [H][3] row-major followed by b [H] (P = 4H float64; one vector, or [num_envs][P] with per_env, in
+ * params_mem_kind memory) and a scalar v_scale, all in float64 with every product rounded before its sum (no FMA):
+ *     q_i = ((2 pi) x_i) / L   (2 pi the float64 constant)      c_i, s_i = the device's cos, sin of q_i      u_i = v_i v_scale
+ *     z_ik = b_k, then + W_k0 c_i, then + W_k1 s_i, then + W_k2 u_i
+ *     h_ik = tanh(z_ik) (PIC_ACT_TANH) or z_ik > 0 ? z_ik : +0.0 (PIC_ACT_RELU)
+ *     out_k = (sum_i h_ik) / N
+ * The sum over particles is a 64-bit integer sum of the terms rounded to nearest in the unit 2^(e_k + b - 61), 2^b >= N and
+ * 2^(e_k) >= B_k: B_k = 1 for tanh (e_k = 0); for relu B_k = ((|W_k0| + |W_k1|) + |W_k2| u_max) + |b_k|, times 1 + 2^-50,
+ * e_k = ilogb(B_k) + 1, with u_max = max_i |u_i| of the environment, taken first as an order-independent max of bit patterns.
+ * So no sum can overflow, out resolves N 2^-61 of 2^(e_k), and it depends neither on the order of the particles nor on the
+ * launch geometry nor on the environment's place in the batch; two calls give the same bits.  B_k = 0 gives +0.  A non-finite
+ * u_i or q_i gives NaN in every output of that environment and of no other; a non-finite W_k., b_k or B_k gives NaN in out_k.
+ * pic_pool: x and v dense float64 [num_envs][N] in mem_kind memory (positions need not be wrapped), or both NULL: the handle's
+ * stored particles (float64 handles only: PIC_EINVAL for float32 / fixed32; PIC_ESTATE before pic_reset and during a staged
+ * step).  out [num_envs][H].  PIC_DEVICE is asynchronous on the handle's stream, PIC_HOST waits.
+ * pic_pool_vjp: for a cotangent cot [num_envs][H], with a_ik = 1 - h_ik^2 (tanh) or z_ik > 0 (relu) and r_ik = (cot_k a_ik) / N,
+ *     g_x_i = (2 pi / L) sum_k r_ik (W_k1 c_i - W_k0 s_i)          g_v_i = v_scale sum_k r_ik W_k2
+ * (float64 sums from +0 over ascending k, one thread per particle; dense [num_envs][N] rows, overwritten) and
+ *     g_W_k0 = sum_i r_ik c_i     g_W_k1 = sum_i r_ik s_i     g_W_k2 = sum_i r_ik u_i     g_b_k = sum_i r_ik
+ * as integer sums in the unit of the bound (|cot_k| / N) max(1, u_max), known before the pass.  g_params is [P] -- the
+ * per-environment vectors added in ascending environment order -- or [num_envs][P] with per_env; g_x, g_v, g_params may each be
+ * NULL.  The activations are recomputed.  Scaling an environment's cotangent by a power of two scales its gradients bit for bit
+ * while they stay normal doubles; a zero cotangent gives +0 (v_scale > 0).  The NaN rule is the forward's; a non-finite cot_k
+ * gives NaN in g_W_k., g_b_k.
+ * Both calls check everything before anything is enqueued (PIC_EINVAL with the reason: hidden outside 1..256, an unknown
+ * activation, per_env not 0 or 1, a bad mem kind, NULL params, out or cot, exactly one of x / v NULL, a non-finite v_scale), are
+ * allowed under an open tape and during a walk, and touch no particles, fields, energies, pic_bad_count, deposits or tape
+ * state.  Their working memory is one block of the handle that grows to what a call needs: 8 num_envs (1 + 4H) bytes of sums and
+ * max words, 8 num_envs P more for shared parameters' gradient, and the device copies of what is given in host memory. */
+typedef struct pic_pool_spec {
+  int32_t hidden, activation, per_env, params_mem_kind;
+  double v_scale;
+  const double* params;
+} pic_pool_spec;
+int pic_pool(pic_handle* h, const pic_pool_spec* s, const void* x, const void* v, int mem_kind, double* out);
+int pic_pool_vjp(pic_handle* h, const pic_pool_spec* s, const void* x, const void* v, const double* cot, int mem_kind, void* g_x,
+                 void* g_v, double* g_params);
+
 int pic_sync(pic_handle* h);
 /* Number of particle positions found non-finite or out of range by the last sweeps (0 = healthy).  Counts the state's
  * particles only: the positions of pic_eval_field / pic_compute_E probes never add to it. */

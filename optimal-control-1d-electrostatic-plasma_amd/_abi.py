@@ -98,6 +98,12 @@ class PicPolicy(C.Structure):
                 ("obs_scale", C.c_void_p)]
 
 
+class PicPoolSpec(C.Structure):
+    """pic_pool_spec (include/picstep.h): the pooled features' layer; params is an address in params_mem_kind memory."""
+    _fields_ = [("hidden", C.c_int32), ("activation", C.c_int32), ("per_env", C.c_int32), ("params_mem_kind", C.c_int32),
+                ("v_scale", C.c_double), ("params", C.c_void_p)]
+
+
 class PicError(RuntimeError):
     pass
 
@@ -190,6 +196,8 @@ SIGNATURES = {
     "pic_tape_policy_grad": [_vp, C.c_int, _vp],
     "pic_policy_jvp": [_vp, C.POINTER(PicPolicy), _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp],
     "pic_tape_tangent_policy": [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pic_pool": [_vp, C.POINTER(PicPoolSpec), _vp, _vp, C.c_int, _vp],
+    "pic_pool_vjp": [_vp, C.POINTER(PicPoolSpec), _vp, _vp, _vp, C.c_int, _vp, _vp, _vp],
     "pic_sync": [_vp],
     "pic_bad_count": [_vp, _i64p],
     "pic_last_error": [_vp],
@@ -937,6 +945,17 @@ class Handle:
         """pic_tape_moments_cot: cot_m an address (int, 0 = NULL: clear the rows) in mem_kind memory; first_step -1 = the start."""
         self._chk(self.lib.pic_tape_moments_cot(self._h, _ptr(int(cot_m)) if cot_m else None, int(mem_kind), int(first_step),
                                                 int(nsteps)))
+
+    # -- pooled particle features (pic_pool*, DESIGN.md 7r) -----------------------------------------------
+    def pool(self, spec, x, v, mem_kind, out):
+        """pic_pool on addresses (int, 0 = NULL) in mem_kind memory; spec: a PicPoolSpec."""
+        p = _ptrs(x, v, out)
+        self._chk(self.lib.pic_pool(self._h, C.byref(spec), p[0], p[1], int(mem_kind), p[2]))
+
+    def pool_vjp(self, spec, x, v, cot, mem_kind, g_x, g_v, g_params):
+        """pic_pool_vjp on addresses (int, 0 = NULL) in mem_kind memory; spec: a PicPoolSpec."""
+        p = _ptrs(x, v, cot, g_x, g_v, g_params)
+        self._chk(self.lib.pic_pool_vjp(self._h, C.byref(spec), p[0], p[1], p[2], int(mem_kind), p[3], p[4], p[5]))
 
     # -- forward mode of the moments and their trace on a tape (DESIGN.md 7l) ---------------------------
     def moments_jvp(self, K, d_x, d_v, mem_kind, d_m):

@@ -1,0 +1,127 @@
+// host_pool.h -- included by picstep.hip alone, inside its extern "C" block behind host_diff.h
+#pragma once
+// ---------------------------------------------------------------------------------------------
+// Pooled particle features (include/picstep.h: pic_pool, pic_pool_vjp; pic_pool.h)
+// ---------------------------------------------------------------------------------------------
+// what is wrong with a spec (null: nothing)
+static const char* pool_spec_error(const pic_pool_spec* s) {
+  if (!s) return "spec is NULL";
+  if (s->hidden < 1 || s->hidden > kPoolMaxHidden) return "hidden must be 1..256";
+  if (s->activation != PIC_ACT_TANH && s->activation != PIC_ACT_RELU) return "activation must be PIC_ACT_TANH or PIC_ACT_RELU";
+  if (s->per_env != 0 && s->per_env != 1) return "per_env must be 0 or 1";
+  if (s->params_mem_kind != PIC_HOST && s->params_mem_kind != PIC_DEVICE) return "bad params_mem_kind";
+  if (!s->params) return "params is NULL";
+  if (!std::isfinite(s->v_scale)) return "v_scale is not finite";
+  return nullptr;
+}
+
+// One call's checks, block and kernel arguments.  `result`: out (pic_pool) or cot (pic_pool_vjp), which must not be NULL.
+// Everything is refused before anything is enqueued; on PIC_OK the block is carved for `shape`, its sums are zero, the
+// parameters and the particles are on the device and `a`, `grid` are the passes'.
+static int pool_begin(pic_handle* h, const pic_pool_spec* s, const void* x, const void* v, const void* result, const char* result_name,
+                      int mem_kind, PoolCallShape shape, const char* who, PoolViews& w, PoolArgs& a, dim3& grid) {
+  if (!h) return PIC_EINVAL;
+  if (int rc = check_mem_kind(h, mem_kind, who)) return rc;
+  if (const char* bad = pool_spec_error(s)) return fail(h, PIC_EINVAL, std::string(who) + ": " + bad);
+  if (!result) return fail(h, PIC_EINVAL, std::string(who) + ": " + result_name + " is NULL");
+  if (!x != !v) return fail(h, PIC_EINVAL, std::string(who) + ": x and v must both be given or both be NULL");
+  if (!x) {
+    if (h->fmt != FMT_F64)
+      return fail(h, PIC_EINVAL, std::string(who) + ": the stored particles need float64 particles with float64 positions (float32 and "
+                                                    "fixed32 are not differentiated); pass x and v");
+    if (!h->has_state) return fail(h, PIC_ESTATE, std::string(who) + ": call pic_reset first");
+    if (h->sched.mid_stage) return fail(h, PIC_ESTATE, std::string(who) + ": a staged step is in progress");
+  }
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  const size_t E = h->cfg.num_envs, N = h->cfg.N, H = (size_t)s->hidden, P = 4 * H;
+  shape.H = H; shape.N = N; shape.per_env = s->per_env != 0;
+  shape.host = mem_kind == PIC_HOST; shape.params_host = s->params_mem_kind == PIC_HOST; shape.xv = x != nullptr;
+  const size_t cap_before = h->pool_cap;      // (the block grows only: another capacity is another allocation)
+  if (int rc = call_reserve(h, h->pool_block, &h->pool_cap, who, "the working memory", w,
+                            [&](Carver c, PoolViews& k) { return pool_parts(c, block_dims(h), shape, k); }))
+    return rc;
+  const size_t accn = E * (shape.vjp ? P : H), zero = (size_t)((char*)(w.acc + accn) - (char*)w.max);
+  if (h->pool_cap != cap_before || zero > h->pool_zero) {
+    h->pool_zero = 0;
+    HIPCHK(h, hipMemsetAsync(w.max, 0, Carver::upto(w.max, w.acc + accn), h->stream));
+  }
+  h->pool_zero = zero;       // (what lies behind may hold this call's copies)
+  a = PoolArgs{};
+  const double* params = nullptr;
+  HIPCHK(h, device_input(h, s->params, s->params_mem_kind, (shape.per_env ? E : 1) * P * sizeof(double), w.params, &params));
+  a.params = params;
+  a.env_params = shape.per_env ? (long long)P : 0;
+  if (x) {
+    HIPCHK(h, device_input(h, static_cast<const double*>(x), mem_kind, E * N * sizeof(double), w.x, &a.x));
+    HIPCHK(h, device_input(h, static_cast<const double*>(v), mem_kind, E * N * sizeof(double), w.v, &a.v));
+    a.ld = (long long)N;
+  } else {
+    a.x = static_cast<const double*>(h->x.get());
+    a.v = static_cast<const double*>(h->v);
+    a.ld = h->ld;
+  }
+  a.umax = w.max; a.acc = w.acc;
+  a.N = (long long)N; a.L = h->cfg.L; a.v_scale = s->v_scale; a.H = (int)H; a.activation = s->activation;
+  while (((int64_t)1 << a.bitsN) < (int64_t)N) ++a.bitsN;
+  // about 4096 workgroups of 4 waves in all: the passes are bound by tanh and sincos, and a workgroup holds 8 KB of LDS at most
+  const long long chunk = (long long)POOL_BLOCK * kPoolTiles, ntiles = ((long long)N + 1) / 2, nchunks = (ntiles + chunk - 1) / chunk;
+  const long long wpe = std::max(1LL, std::min((4096 + (long long)E - 1) / (long long)E, nchunks));
+  a.chunks_per_wg = (nchunks + wpe - 1) / wpe;
+  grid = dim3((unsigned)((nchunks + a.chunks_per_wg - 1) / a.chunks_per_wg), (unsigned)E);
+  return PIC_OK;
+}
+
+// the tail of a pool call: a failed call leaves the sums unknown
+static int pool_end(pic_handle* h, hipError_t e, bool wait, const char* who) {
+  const int rc = hip_tail(h, e, wait, who);
+  if (rc) h->pool_zero = 0;
+  return rc;
+}
+
+int pic_pool(pic_handle* h, const pic_pool_spec* s, const void* x, const void* v, int mem_kind, double* out) {
+  const char* who = "pic_pool";
+  PoolViews w;
+  PoolArgs a;
+  dim3 grid;
+  if (int rc = pool_begin(h, s, x, v, out, "out", mem_kind, PoolCallShape{}, who, w, a, grid)) return rc;
+  double* dev = device_output(out, mem_kind, w.out);
+  hipLaunchKernelGGL(pool_max_kernel, grid, dim3(POOL_BLOCK), 0, h->stream, a);
+  hipLaunchKernelGGL(pool_kernel, grid, dim3(POOL_BLOCK), 0, h->stream, a);
+  hipLaunchKernelGGL(pool_finish_kernel, dim3(h->cfg.num_envs), dim3(POOL_BLOCK), 0, h->stream, a, dev);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = device_result(h, out, dev, (size_t)h->cfg.num_envs * a.H * sizeof(double));
+  return pool_end(h, e, mem_kind == PIC_HOST, who);        // device outputs stay stream-ordered
+}
+
+int pic_pool_vjp(pic_handle* h, const pic_pool_spec* s, const void* x, const void* v, const double* cot, int mem_kind, void* g_x,
+                 void* g_v, double* g_params) {
+  const char* who = "pic_pool_vjp";
+  PoolCallShape shape;
+  shape.vjp = true; shape.g_x = g_x != nullptr; shape.g_v = g_v != nullptr; shape.g_params = g_params != nullptr;
+  PoolViews w;
+  PoolArgs a;
+  dim3 grid;
+  if (int rc = pool_begin(h, s, x, v, cot, "cot", mem_kind, shape, who, w, a, grid)) return rc;
+  if (!g_x && !g_v && !g_params) return PIC_OK;
+  const size_t E = h->cfg.num_envs, N = h->cfg.N, P = 4 * (size_t)a.H;
+  const bool host = mem_kind == PIC_HOST;
+  PoolVjpArgs g{};
+  HIPCHK(h, device_input(h, cot, mem_kind, E * a.H * sizeof(double), w.cot, &g.cot));
+  g.g_x = device_output(g_x, mem_kind, w.g_x);
+  g.g_v = device_output(g_v, mem_kind, w.g_v);
+  g.want_params = g_params != nullptr;
+  // the per-environment sums go to the block (shared parameters, or host memory) or straight to the caller
+  double* gE = w.gE ? w.gE : g_params;
+  double* gp = s->per_env ? gE : device_output(g_params, mem_kind, w.g);
+  hipLaunchKernelGGL(pool_max_kernel, grid, dim3(POOL_BLOCK), 0, h->stream, a);
+  hipLaunchKernelGGL(pool_vjp_kernel, grid, dim3(POOL_BLOCK), 0, h->stream, a, g);
+  hipLaunchKernelGGL(pool_vjp_finish_kernel, dim3(E), dim3(POOL_BLOCK), 0, h->stream, a, g, gE);
+  if (g_params && !s->per_env)
+    hipLaunchKernelGGL(policy_grad_reduce_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->stream, (const double*)gE, gp,
+                       (long long)P, (int)E);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = device_result(h, g_x, g.g_x, E * N * sizeof(double));
+  if (e == hipSuccess) e = device_result(h, g_v, g.g_v, E * N * sizeof(double));
+  if (e == hipSuccess) e = device_result(h, g_params, gp, (s->per_env ? E : 1) * P * sizeof(double));
+  return pool_end(h, e, host, who);
+}

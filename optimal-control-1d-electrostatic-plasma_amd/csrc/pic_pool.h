@@ -1,0 +1,348 @@
+// pic_pool.h -- pooled particle features (include/picstep.h: pic_pool, pic_pool_vjp): per environment
+//   out_k = (1/N) sum_i act(b_k + W_k0 cos q_i + W_k1 sin q_i + W_k2 u_i),   q_i = 2 pi x_i / L,  u_i = v_i v_scale
+// and its vector-Jacobian product, without an [N][H] array: a lane holds kPoolPerLane particles (cos, sin, u) in registers and
+// walks the H rows of W, which are the same for every lane of the workgroup (scalar loads).  The sums over particles are 64-bit
+// integer sums of terms rounded to nearest in a power-of-two unit that is known before the pass (pic_moments' pattern), so
+// nothing depends on the order of the particles, the grid or the batch.  Off the step path: the kernels read x, v and write
+// their own work block only.  Built with -ffp-contract=off: every product is rounded before its sum.
+#pragma once
+#include <climits>
+
+#include "pic_moments.h"    // kMomInfBits, mom_max_bits; pic_v2d_a8 (rows that start on 8 bytes only: N odd)
+
+namespace {
+
+constexpr int kPoolMaxHidden = 256;
+constexpr int POOL_BLOCK = 256;          // 4 waves: a workgroup's chunk is 1024 particles, so 5000 particles still make 5 workgroups
+constexpr int kPoolTiles = 2;            // 16-byte tiles (2 particles each) a lane holds through one walk over k
+constexpr int kPoolPerLane = 2 * kPoolTiles;
+constexpr int kPoolSkip = INT_MIN;       // a unit word: nothing is deposited, the result is +0
+constexpr int kPoolNan = INT_MIN + 1;    // ... the result is NaN
+constexpr double kTwoPi = 6.283185307179586;
+
+struct PoolArgs {
+  const double* x;             // [env][ld] positions (not necessarily wrapped)
+  const double* v;             // [env][ld]
+  const double* params;        // W [H][3] row-major, then b [H]
+  unsigned long long* umax;    // [env] bit pattern of max |u|, zero between calls
+  unsigned long long* acc;     // [env][H] (forward) or [env][4][H] (VJP) integer sums, zero between calls
+  long long env_params;        // doubles from one environment's parameters to the next (0: shared)
+  long long N, ld;
+  long long chunks_per_wg;     // chunks of POOL_BLOCK * kPoolTiles tiles per workgroup: a workgroup's range is contiguous
+  double L, v_scale;
+  int H, activation;
+  int bitsN;                   // 2^bitsN >= N
+};
+
+__device__ __forceinline__ bool pool_finite(double a) { return fabs(a) <= 1.7976931348623157e308; }
+
+// exponent of the unit of sums of N terms bounded by `bound`: 2^e >= bound, unit 2^(e + bitsN - 61) (two bits of headroom in an
+// int64: no overflow, whatever the data); kPoolSkip for a zero bound, kPoolNan for a non-finite one
+__device__ __forceinline__ int pool_unit(double bound, int bitsN) {
+  if (!pool_finite(bound)) return kPoolNan;
+  if (!(bound > 0.0)) return kPoolSkip;
+  return ilogb(bound) + 1 + bitsN - 61;
+}
+
+// the unit word of out_k: tanh is bounded by 1 = 2^0; relu by B_k = |W_k0| + |W_k1| + |W_k2| u_max + |b_k|, rounded up
+__device__ __forceinline__ int pool_fwd_unit(const double* __restrict__ p, int H, int k, int activation, double umx, int bitsN) {
+  const double w0 = p[3 * k], w1 = p[3 * k + 1], w2 = p[3 * k + 2], bk = p[3 * H + k];
+  if (!(pool_finite(w0) && pool_finite(w1) && pool_finite(w2) && pool_finite(bk))) return kPoolNan;
+  if (activation == PIC_ACT_TANH) return bitsN - 61;
+  const double B = ((fabs(w0) + fabs(w1)) + fabs(w2) * umx) + fabs(bk);
+  return pool_unit(B * 0x1.0000000000004p+0, bitsN);     // (1 + 2^-50: above the rounding of B and of z)
+}
+
+// the unit word of g_W_k*, g_b_k: every term is bounded by (|g_k| / N) max(1, u_max)
+__device__ __forceinline__ int pool_vjp_unit(const double* __restrict__ p, int H, int k, double gk, double umx, double Nd, int bitsN) {
+  const double w0 = p[3 * k], w1 = p[3 * k + 1], w2 = p[3 * k + 2], bk = p[3 * H + k];
+  if (!(pool_finite(w0) && pool_finite(w1) && pool_finite(w2) && pool_finite(bk))) return kPoolNan;
+  return pool_unit((fabs(gk) / Nd) * (umx > 1.0 ? umx : 1.0), bitsN);
+}
+
+// wave_incl_scan's DPP steps on 64-bit integers (a masked-off or absent source adds 0); all 64 lanes must be active
+template <int CTRL, int ROW_MASK = 0xF>
+__device__ __forceinline__ long long dpp_add_i64(long long v) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, true);
+  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(v >> 32), CTRL, ROW_MASK, 0xF, true);
+  return v + (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+// sum over the 64 lanes, the same value in every lane
+__device__ __forceinline__ long long wave_sum_i64(long long v) {
+  v = dpp_add_i64<0x111>(v);
+  v = dpp_add_i64<0x112>(v);
+  v = dpp_add_i64<0x114>(v);
+  v = dpp_add_i64<0x118>(v);
+  v = dpp_add_i64<0x142, 0xA>(v);
+  v = dpp_add_i64<0x143, 0xC>(v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)v, 63);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(v >> 32), 63);
+  return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+// tile t (particles 2t, 2t + 1) of a row; the odd last particle is read alone, so nothing beyond N is ever read
+__device__ __forceinline__ pic_v2d pool_tile(const double* __restrict__ row, long long t, long long N) {
+  pic_v2d r = {0.0, 0.0};
+  if (2 * t + 1 < N) {
+    const pic_v2d_a8 q = stream_load(reinterpret_cast<const pic_v2d_a8*>(row + 2 * t));
+    r[0] = q[0]; r[1] = q[1];
+  } else if (2 * t < N) {
+    r[0] = row[2 * t];
+  }
+  return r;
+}
+
+// the tiles [t0, t1) of workgroup blockIdx.x
+__device__ __forceinline__ void pool_range(const PoolArgs& a, long long& t0, long long& t1) {
+  const long long ntiles = (a.N + 1) / 2, per = a.chunks_per_wg * POOL_BLOCK * kPoolTiles;
+  t0 = (long long)blockIdx.x * per;
+  t1 = t0 + per < ntiles ? t0 + per : ntiles;
+}
+
+// a lane's particles of the chunk that starts at tile tc: cos q, sin q, u and whether the slot holds a particle
+struct PoolLane {
+  double c[kPoolPerLane], s[kPoolPerLane], u[kPoolPerLane];
+  bool on[kPoolPerLane];
+};
+
+__device__ __forceinline__ void pool_load(const PoolArgs& a, const double* __restrict__ xe, const double* __restrict__ ve,
+                                          long long tc, long long t1, PoolLane& p) {
+#pragma unroll
+  for (int j = 0; j < kPoolTiles; ++j) {
+    const long long t = tc + (long long)j * POOL_BLOCK + threadIdx.x;
+    const bool have = t < t1;
+    const pic_v2d xt = have ? pool_tile(xe, t, a.N) : pic_v2d{0.0, 0.0};
+    const pic_v2d vt = have ? pool_tile(ve, t, a.N) : pic_v2d{0.0, 0.0};
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      const int s = 2 * j + m;
+      const double q = (kTwoPi * xt[m]) / a.L;
+      p.on[s] = have && 2 * t + m < a.N;
+      sincos(q, &p.s[s], &p.c[s]);
+      p.u[s] = vt[m] * a.v_scale;
+    }
+  }
+}
+
+// z_k = b_k, + W_k0 c, + W_k1 s, + W_k2 u: each product rounded, then the sum
+__device__ __forceinline__ double pool_pre(double w0, double w1, double w2, double bk, double c, double s, double u) {
+  double z = bk;
+  z = z + w0 * c;
+  z = z + w1 * s;
+  z = z + w2 * u;
+  return z;
+}
+
+// Per-environment max |u| as the bit pattern of a non-negative double into umax[env] (zero before).  A non-finite u or q
+// saturates it at kMomInfBits: the finishing kernels then write NaN for that environment.  Grid: the passes'.
+__global__ __launch_bounds__(POOL_BLOCK) void pool_max_kernel(PoolArgs a) {
+  const int env = blockIdx.y;
+  const double* __restrict__ xe = a.x + (size_t)env * a.ld;
+  const double* __restrict__ ve = a.v + (size_t)env * a.ld;
+  long long t0, t1;
+  pool_range(a, t0, t1);
+  unsigned long long mb = 0ull;
+  for (long long t = t0 + threadIdx.x; t < t1; t += POOL_BLOCK) {
+    const pic_v2d xt = pool_tile(xe, t, a.N), vt = pool_tile(ve, t, a.N);     // (a slot beyond N holds 0)
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      mom_max_bits(mb, fabs(vt[m] * a.v_scale));
+      if (!pool_finite((kTwoPi * xt[m]) / a.L)) mb = kMomInfBits;
+    }
+  }
+  block_max_to(__longlong_as_double((long long)mb), a.umax + env);
+}
+
+// Forward pass: grid (workgroups per environment, environments).  LDS: the H unit words and H 64-bit sums.  Per chunk a lane
+// computes cos, sin and u of its particles once, then for every k its kPoolPerLane terms, rounded to integers; the wave's sum
+// (DPP) is one ds_add_u64 per wave and k.  The flush is one memory-side atomic per non-zero k into acc [env][H].
+__global__ __launch_bounds__(POOL_BLOCK) void pool_kernel(PoolArgs a) {
+  __shared__ unsigned long long sums[kPoolMaxHidden];
+  __shared__ int unit[kPoolMaxHidden];
+  const int env = blockIdx.y, H = a.H, lane = threadIdx.x & 63;
+  const unsigned long long mb = a.umax[env];
+  if (mb >= kMomInfBits) return;                           // (uniform: the finishing kernel writes NaN)
+  const double* __restrict__ p = a.params + (size_t)env * a.env_params;
+  const double* __restrict__ xe = a.x + (size_t)env * a.ld;
+  const double* __restrict__ ve = a.v + (size_t)env * a.ld;
+  const double umx = __longlong_as_double((long long)mb);
+  for (int k = threadIdx.x; k < H; k += POOL_BLOCK) {
+    sums[k] = 0ull;
+    unit[k] = pool_fwd_unit(p, H, k, a.activation, umx, a.bitsN);
+  }
+  __syncthreads();
+  long long t0, t1;
+  pool_range(a, t0, t1);
+  const bool is_tanh = a.activation == PIC_ACT_TANH;
+  for (long long tc = t0; tc < t1; tc += (long long)POOL_BLOCK * kPoolTiles) {
+    PoolLane q;
+    pool_load(a, xe, ve, tc, t1, q);
+    for (int k = 0; k < H; ++k) {
+      const int ue = unit[k];
+      if (ue == kPoolSkip || ue == kPoolNan) continue;     // (uniform)
+      const double w0 = p[3 * k], w1 = p[3 * k + 1], w2 = p[3 * k + 2], bk = p[3 * H + k];
+      long long part = 0;
+#pragma unroll
+      for (int j = 0; j < kPoolPerLane; ++j) {
+        const double z = pool_pre(w0, w1, w2, bk, q.c[j], q.s[j], q.u[j]);
+        const double h = is_tanh ? tanh(z) : (z > 0.0 ? z : 0.0);
+        if (q.on[j]) part += __double2ll_rn(ldexp(h, -ue));
+      }
+      part = wave_sum_i64(part);
+      if (lane == 0 && part) atomicAdd(sums + k, (unsigned long long)part);
+    }
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < H; k += POOL_BLOCK) {
+    const unsigned long long s = sums[k];
+    if (s) atomicAdd(a.acc + (size_t)env * H + k, s);
+  }
+}
+
+// One workgroup per environment: the integer sums to out [env][H] = sum / N; +0 where nothing was deposited, NaN in the outputs
+// of a non-finite row of parameters and in every output of an environment with a non-finite particle; the accumulators and the
+// environment's max word are cleared behind the read.
+__global__ __launch_bounds__(POOL_BLOCK) void pool_finish_kernel(PoolArgs a, double* __restrict__ out) {
+  const int env = blockIdx.x, H = a.H;
+  const unsigned long long mb = a.umax[env];
+  const bool finite = mb < kMomInfBits;
+  const double* __restrict__ p = a.params + (size_t)env * a.env_params;
+  const double umx = __longlong_as_double((long long)mb);
+  const double nan = __longlong_as_double(0x7FF8000000000000ll);
+  for (int k = threadIdx.x; k < H; k += POOL_BLOCK) {
+    unsigned long long* s = a.acc + (size_t)env * H + k;
+    const int ue = finite ? pool_fwd_unit(p, H, k, a.activation, umx, a.bitsN) : kPoolNan;
+    double r = 0.0;
+    if (ue == kPoolNan) r = nan;
+    else if (ue != kPoolSkip) r = ldexp((double)(long long)*s, ue) / (double)a.N;
+    out[(size_t)env * H + k] = r;
+    *s = 0ull;
+  }
+  __syncthreads();                                         // (every lane has read the max word)
+  if (threadIdx.x == 0) a.umax[env] = 0ull;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The vector-Jacobian product for a cotangent g [env][H] (pic_pool_vjp)
+// ---------------------------------------------------------------------------------------------
+struct PoolVjpArgs {
+  const double* cot;           // [env][H]
+  double* g_x;                 // [env][N] dense rows, overwritten; or null
+  double* g_v;                 // the same
+  int want_params;             // deposit the 4H parameter sums into acc [env][4][H]
+};
+
+// The forward's pass with the activations recomputed: one thread owns a particle, so g_x_i and g_v_i are float64 sums over
+// ascending k; the parameter terms r c, r s, r u, r are rounded to integers in the unit of k and summed like the forward's.
+__global__ __launch_bounds__(POOL_BLOCK) void pool_vjp_kernel(PoolArgs a, PoolVjpArgs g) {
+  __shared__ unsigned long long sums[4 * kPoolMaxHidden];
+  __shared__ int unit[kPoolMaxHidden];
+  const int env = blockIdx.y, H = a.H, lane = threadIdx.x & 63;
+  const unsigned long long mb = a.umax[env];
+  const bool finite = mb < kMomInfBits;
+  const double* __restrict__ p = a.params + (size_t)env * a.env_params;
+  const double* __restrict__ xe = a.x + (size_t)env * a.ld;
+  const double* __restrict__ ve = a.v + (size_t)env * a.ld;
+  const double* __restrict__ ge = g.cot + (size_t)env * H;
+  const double umx = __longlong_as_double((long long)mb), Nd = (double)a.N;
+  const double nan = __longlong_as_double(0x7FF8000000000000ll);
+  const bool dep = g.want_params && finite;
+  for (int k = threadIdx.x; k < H; k += POOL_BLOCK) {
+    sums[k] = sums[H + k] = sums[2 * H + k] = sums[3 * H + k] = 0ull;
+    unit[k] = dep ? pool_vjp_unit(p, H, k, ge[k], umx, Nd, a.bitsN) : kPoolSkip;
+  }
+  __syncthreads();
+  long long t0, t1;
+  pool_range(a, t0, t1);
+  const bool is_tanh = a.activation == PIC_ACT_TANH;
+  const double cx = kTwoPi / a.L;
+  for (long long tc = t0; tc < t1; tc += (long long)POOL_BLOCK * kPoolTiles) {
+    PoolLane q;
+    pool_load(a, xe, ve, tc, t1, q);
+    double sx[kPoolPerLane], sv[kPoolPerLane];
+#pragma unroll
+    for (int j = 0; j < kPoolPerLane; ++j) sx[j] = sv[j] = 0.0;
+    for (int k = 0; k < H; ++k) {
+      const int ue = unit[k];
+      const bool on = ue != kPoolSkip && ue != kPoolNan;   // (uniform)
+      const double w0 = p[3 * k], w1 = p[3 * k + 1], w2 = p[3 * k + 2], bk = p[3 * H + k], gk = ge[k];
+      long long pc = 0, ps = 0, pu = 0, pr = 0;
+#pragma unroll
+      for (int j = 0; j < kPoolPerLane; ++j) {
+        const double z = pool_pre(w0, w1, w2, bk, q.c[j], q.s[j], q.u[j]);
+        double act;
+        if (is_tanh) {
+          const double h = tanh(z);
+          act = 1.0 - h * h;
+        } else {
+          act = z > 0.0 ? 1.0 : 0.0;
+        }
+        const double r = (gk * act) / Nd;
+        sx[j] = sx[j] + r * (w1 * q.c[j] - w0 * q.s[j]);
+        sv[j] = sv[j] + r * w2;
+        if (on && q.on[j]) {
+          pc += __double2ll_rn(ldexp(r * q.c[j], -ue));
+          ps += __double2ll_rn(ldexp(r * q.s[j], -ue));
+          pu += __double2ll_rn(ldexp(r * q.u[j], -ue));
+          pr += __double2ll_rn(ldexp(r, -ue));
+        }
+      }
+      if (on) {
+        pc = wave_sum_i64(pc);
+        ps = wave_sum_i64(ps);
+        pu = wave_sum_i64(pu);
+        pr = wave_sum_i64(pr);
+        if (lane == 0) {
+          if (pc) atomicAdd(sums + k, (unsigned long long)pc);
+          if (ps) atomicAdd(sums + H + k, (unsigned long long)ps);
+          if (pu) atomicAdd(sums + 2 * H + k, (unsigned long long)pu);
+          if (pr) atomicAdd(sums + 3 * H + k, (unsigned long long)pr);
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kPoolPerLane; ++j) {
+      if (!q.on[j]) continue;
+      const long long i = 2 * (tc + (long long)(j >> 1) * POOL_BLOCK + threadIdx.x) + (j & 1);
+      const size_t o = (size_t)env * a.N + i;
+      if (g.g_x) g.g_x[o] = finite ? cx * sx[j] : nan;
+      if (g.g_v) g.g_v[o] = finite ? a.v_scale * sv[j] : nan;
+    }
+  }
+  __syncthreads();
+  if (!dep) return;
+  for (int c = threadIdx.x; c < 4 * H; c += POOL_BLOCK) {
+    const unsigned long long s = sums[c];
+    if (s) atomicAdd(a.acc + (size_t)env * 4 * H + c, s);
+  }
+}
+
+// One workgroup per environment: the 4H integer sums to gE [env][4H] in the parameters' order (g_W [H][3], then g_b [H]); +0
+// for a zero cotangent, NaN for a non-finite cotangent or row of parameters and for an environment with a non-finite particle;
+// the accumulators and the max word are cleared behind the read.
+__global__ __launch_bounds__(POOL_BLOCK) void pool_vjp_finish_kernel(PoolArgs a, PoolVjpArgs g, double* __restrict__ gE) {
+  const int env = blockIdx.x, H = a.H;
+  const unsigned long long mb = a.umax[env];
+  const bool finite = mb < kMomInfBits;
+  const double* __restrict__ p = a.params + (size_t)env * a.env_params;
+  const double* __restrict__ ge = g.cot + (size_t)env * H;
+  const double umx = __longlong_as_double((long long)mb);
+  const double nan = __longlong_as_double(0x7FF8000000000000ll);
+  if (g.want_params) {
+    for (int c = threadIdx.x; c < 4 * H; c += POOL_BLOCK) {
+      const int m = c / H, k = c - m * H;
+      unsigned long long* s = a.acc + (size_t)env * 4 * H + c;
+      const int ue = finite ? pool_vjp_unit(p, H, k, ge[k], umx, (double)a.N, a.bitsN) : kPoolNan;
+      double r = 0.0;
+      if (ue == kPoolNan) r = nan;
+      else if (ue != kPoolSkip) r = ldexp((double)(long long)*s, ue);
+      gE[(size_t)env * 4 * H + (m < 3 ? 3 * k + m : 3 * H + k)] = r;
+      *s = 0ull;
+    }
+  }
+  __syncthreads();                                         // (every lane has read the max word)
+  if (threadIdx.x == 0) a.umax[env] = 0ull;
+}
+
+}  // namespace

@@ -38,6 +38,7 @@
 // handle, the launch schedule and the C ABI, but for the host side of the differentiable rollouts: host_diff.h, host_phase.h,
 // host_tape.h, host_tangent.h, host_tangent_walk.h.  pic_copy.h, host_copy.h and host_copy_map.h: copies of whole environments (pic_copy_envs).
 // pic_policy.h and host_policy.h: the MLP policy of pic_policy_eval and pic_step_policy.
+// pic_pool.h and host_pool.h: the pooled particle features of pic_pool and pic_pool_vjp.
 
 #include <hip/hip_runtime.h>
 
@@ -77,6 +78,7 @@
 #include "pic_moments.h"
 #include "pic_copy.h"
 #include "pic_policy.h"
+#include "pic_pool.h"
 
 
 // ---------------------------------------------------------------------------------------------
@@ -340,6 +342,9 @@ struct __attribute__((visibility("hidden"))) pic_handle : LaunchPlan {      // t
   PinnedBuf<double> h_fields;     // pinned host staging for n | E_mesh | phi (meshes up to 256 KB each in total), or null
   DeviceBuf<void> mom_block;      // pic_moments, allocated by its first call
   MomViews mom;                   // views into it (host_blocks.h: moments_parts)
+  DeviceBuf<void> pool_block;     // pic_pool, pic_pool_vjp: grows to what a call needs (host_blocks.h: pool_parts)
+  size_t pool_cap = 0;            // its bytes
+  size_t pool_zero = 0;           // ... of which the leading ones (max words, integer sums) are zero between calls
   DeviceBuf<unsigned long long> bad;
   unsigned long long* probe_bad = nullptr;   // view: bad + 1, where the probes count their non-finite positions (never read: pic_bad_count
                                              // describes the state's particles, and a probe's positions are not among them)
@@ -1148,6 +1153,7 @@ static int64_t records_ahead(const pic_handle* h, int64_t nsteps) {
 // the host side of the differentiable rollouts (advance calls tape_record_ext, tape_checkpoint and tape_kl_enqueue)
 #include "host_phase.h"
 #include "host_moments.h"
+#include "host_pool.h"
 #include "host_tape.h"
 #include "host_tangent.h"
 #include "host_tangent_walk.h"

@@ -1,0 +1,411 @@
+"""Pooled particle features on the device (pic_pool, pic_pool_vjp, control/pool.py): parity with the longdouble twin
+of tests/hp_pool.py, order-freeness and reproducibility bit for bit, exact powers of two and the NaN rule, device finite
+differences, the state rules and refusals, and the closed loop through rollout_policy(observe="state")."""
+import numpy as np
+import pytest
+import torch
+
+import hp_policy as hpp
+import hp_pool as hp
+from conftest import record_measure, rel_err
+from oracle import pic_oracle as po
+
+pytestmark = pytest.mark.gpu
+
+L = 50.0
+ACTS = ("tanh", "relu")
+
+
+def _env(E, N, Ng=64, **kw):
+    from ocplasma_amd.env.batched import BatchedPIC
+    return BatchedPIC(E, N, Ng, L=L, dt=0.1, **kw)
+
+
+def _data(E, N, seed):
+    """Wrapped positions with the box's edges among them (-0.0, the last double below L), velocities of a bump-on-tail's size."""
+    rng = np.random.default_rng(seed)
+    X, V = rng.uniform(0.0, L, (E, N)), rng.normal(0.0, 2.0, (E, N))
+    X[:, 0] = -0.0
+    if N >= 3:
+        X[:, 1] = np.nextafter(L, 0.0)
+    return X, V
+
+
+def _layer(H, seed, lead=()):
+    rng = np.random.default_rng(seed)
+    return rng.normal(0.0, 0.5, lead + (H, 3)), rng.normal(0.0, 0.1, lead + (H,))
+
+
+def _np(a):
+    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+
+
+def _bits(a):
+    return np.ascontiguousarray(_np(a)).view(np.int64)
+
+
+def _same(a, b):
+    return np.array_equal(_bits(a), _bits(b))
+
+
+def _same_results(out, g, out2, g2):
+    return _same(out, out2) and all(_same(g[k], g2[k]) for k in ("g_x", "g_v", "g_W", "g_b"))
+
+
+def _cuda(*arrays):
+    return [torch.as_tensor(a, device="cuda") for a in arrays]
+
+
+# ---- 1. parity ------------------------------------------------------------------------------------------------------------------------
+def _env_errors(out_e, g, e, ref, X, V, W, b, cot, act):
+    """(forward, g_x / g_v) errors of environment e against its reference, relative to the scales of hp_pool."""
+    q, u = hp.features(X[e], V[e], L, 1.0)
+    sx, sv, _ = hp.vjp_scales(W, cot[e], u, X.shape[1], L, 1.0)
+    ef = float(np.max(np.abs(out_e.astype(hp.LD) - ref[0]) / hp.forward_scale(W, b, u, act)))
+    eg = max(float(np.max(np.abs(g["g_x"][e].astype(hp.LD) - ref[1]))) / sx, float(np.max(np.abs(g["g_v"][e].astype(hp.LD) - ref[2]))) / sv)
+    return ef, eg
+
+
+def _param_error(gW, gb, refs, scales):
+    """The parameter gradient against the sum of the environments' references, relative to the sum of their scales."""
+    wW, wb, sp = sum(r[3] for r in refs), sum(r[4] for r in refs), sum(scales)
+    return max(float(np.max(np.abs(gW.astype(hp.LD) - wW) / sp[:, None])), float(np.max(np.abs(gb.astype(hp.LD) - wb) / sp)))
+
+
+@pytest.mark.parametrize("H", [1, 5, 64, 256])
+@pytest.mark.parametrize("N", [1, 63, 4097, 8193])
+def test_parity_with_the_longdouble_twin(N, H):
+    """Forward and VJP against the twin for tanh and relu, shared and per-environment parameters, in a batch of three and alone.
+    The twin is evaluated once per (environment, parameter set, activation); x, v given or the stored particles, host or device
+    memory are the same kernels on the same data and must agree with the checked result bit for bit."""
+    X, V = _data(3, N, seed=N + H)
+    env3 = _env(3, N)
+    env3.reset(X, V)
+    Xs, Vs = env3.particles()                      # what the NULL form reads (the reset's stored particles)
+    env1 = _env(1, N)
+    env1.reset(Xs[:1], Vs[:1])
+    sets = [_layer(H, seed=1), _layer(H, seed=2)]
+    cot = np.random.default_rng(H).normal(0.0, 1.0, (3, H))
+    worst = {"forward": 0.0, "vjp": 0.0}
+    for act in ACTS:
+        refs = {}
+
+        def ref(e, s):
+            if (e, s) not in refs:
+                q, u = hp.features(Xs[e], Vs[e], L, 1.0)
+                refs[e, s] = (hp.both_ld(Xs[e], Vs[e], *sets[s], cot[e], L, act), hp.vjp_scales(sets[s][0], cot[e], u, N, L, 1.0)[2])
+            return refs[e, s]
+
+        for env, E in ((env3, 3), (env1, 1)):
+            for per_env in (False, True):
+                which = [1, 0, 0][:E] if per_env else [0] * E          # the parameter set of every environment
+                W = np.stack([sets[s][0] for s in which]) if per_env else sets[0][0]
+                b = np.stack([sets[s][1] for s in which]) if per_env else sets[0][1]
+                x, v, c = Xs[:E], Vs[:E], cot[:E]
+                out = env.pool(W, b, act, x=x, v=v)
+                g = env.pool_vjp(W, b, c, act, x=x, v=v)
+                for e in range(E):
+                    ef, eg = _env_errors(out[e], g, e, ref(e, which[e])[0], Xs, Vs, *sets[which[e]], cot, act)
+                    worst["forward"], worst["vjp"] = max(worst["forward"], ef), max(worst["vjp"], eg)
+                    if per_env:
+                        ep = _param_error(g["g_W"][e], g["g_b"][e], [ref(e, which[e])[0]], [ref(e, which[e])[1]])
+                        worst["vjp"] = max(worst["vjp"], ep)
+                if not per_env:
+                    rs = [ref(e, 0) for e in range(E)]
+                    worst["vjp"] = max(worst["vjp"], _param_error(g["g_W"], g["g_b"], [r[0] for r in rs], [r[1] for r in rs]))
+                # the other forms of the same call
+                assert _same_results(out, g, env.pool(W, b, act), env.pool_vjp(W, b, c, act)), (act, E, per_env, "stored, host")
+                tW, tb, tc, tx, tv = _cuda(W, b, c, x, v)
+                assert _same_results(out, g, env.pool(tW, tb, act, x=tx, v=tv), env.pool_vjp(tW, tb, tc, act, x=tx, v=tv)), (act, E, per_env, "device")
+                assert _same_results(out, g, env.pool(tW, tb, act), env.pool_vjp(tW, tb, tc, act)), (act, E, per_env, "stored, device")
+    record_measure(f"pool_parity_forward_N{N}_H{H}", worst["forward"])
+    record_measure(f"pool_parity_vjp_N{N}_H{H}", worst["vjp"])
+    assert worst["forward"] < hp.bound("forward", N) and worst["vjp"] < hp.bound("vjp", N), worst
+    env3.close()
+    env1.close()
+
+
+@pytest.mark.parametrize("act", ACTS)
+def test_parity_off_the_box(act):
+    """Positions need not be wrapped: -0.0, the last double below L and 3.3 L among positions over several box lengths."""
+    E, N, H = 2, 63, 5
+    env = _env(E, N)
+    x, v, W, b, cot = hp.case(N, H, seed=4)
+    X, V = np.stack([x, x[::-1]]), np.stack([v, 0.5 * v])
+    X[:, 0], X[:, 1], X[:, 2] = -0.0, np.nextafter(L, 0.0), 3.3 * L
+    c = np.stack([cot, -cot])
+    out, g = env.pool(W, b, act, x=X, v=V), env.pool_vjp(W, b, c, act, x=X, v=V)
+    for e in range(E):
+        ef, eg = hp.errors(out[e], (g["g_x"][e], g["g_v"][e], None, None), X[e], V[e], W, b, c[e], L, act)
+        assert ef < hp.bound("forward", N) and eg < hp.bound("vjp", N), (e, ef, eg)
+    env.close()
+
+
+# ---- 2. order-freeness, bit for bit -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("act", ACTS)
+def test_results_do_not_depend_on_order_batch_geometry_or_run(act):
+    E, N, H = 2, 4097, 5
+    X, V = _data(E, N, seed=21)
+    W, b = _layer(H, seed=3)
+    cot = np.random.default_rng(5).normal(0.0, 1.0, (E, H))
+    env = _env(E, N)
+    env.reset(X, V)
+    Xs, Vs = env.particles()
+    out, g = env.pool(W, b, act), env.pool_vjp(W, b, cot, act)
+    assert _same_results(out, g, env.pool(W, b, act), env.pool_vjp(W, b, cot, act))                  # two calls
+    perm = np.random.default_rng(6).permutation(N)
+    Xp, Vp = Xs.copy(), Vs.copy()
+    Xp[1], Vp[1] = Xs[1][perm], Vs[1][perm]
+    outp, gp = env.pool(W, b, act, x=Xp, v=Vp), env.pool_vjp(W, b, cot, act, x=Xp, v=Vp)
+    assert _same(out, outp) and _same(g["g_W"], gp["g_W"]) and _same(g["g_b"], gp["g_b"])
+    assert _same(g["g_x"][1][perm], gp["g_x"][1]) and _same(g["g_v"][1][perm], gp["g_v"][1]) and _same(g["g_x"][0], gp["g_x"][0])
+    env.close()
+    for bpe in (1, 7):                                                                              # another launch geometry of the handle
+        other = _env(E, N, blocks_per_env=bpe)
+        other.reset(X, V)
+        assert _same_results(out, g, other.pool(W, b, act), other.pool_vjp(W, b, cot, act)), bpe
+        other.close()
+    # environment 1 alone, and at row 299 of a batch of 300 (per-environment parameters: its own gradient)
+    We, be = np.broadcast_to(W, (300, H, 3)).copy(), np.broadcast_to(b, (300, H)).copy()
+    big = _env(300, N)
+    Xb, Vb, cb = np.tile(Xs[0], (300, 1)), np.tile(Vs[0], (300, 1)), np.tile(cot[0], (300, 1))
+    Xb[299], Vb[299], cb[299] = Xs[1], Vs[1], cot[1]
+    ob, gb = big.pool(We, be, act, x=Xb, v=Vb), big.pool_vjp(We, be, cb, act, x=Xb, v=Vb)
+    big.close()
+    one = _env(1, N)
+    o1, g1 = one.pool(W[None], b[None], act, x=Xs[1:], v=Vs[1:]), one.pool_vjp(W[None], b[None], cot[1:], act, x=Xs[1:], v=Vs[1:])
+    one.close()
+    assert _same(o1[0], ob[299]) and _same(o1[0], out[1])
+    assert all(_same(g1[k][0], gb[k][299]) for k in ("g_x", "g_v", "g_W", "g_b"))
+    assert _same(g1["g_x"][0], g["g_x"][1]) and _same(g1["g_v"][0], g["g_v"][1])
+
+
+# ---- 3. powers of two and non-finite input ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("act", ACTS)
+def test_cotangents_scale_by_exact_powers_of_two(act):
+    E, N, H = 3, 1000, 5
+    X, V = _data(E, N, seed=31)
+    W, b = _layer(H, seed=7, lead=(E,))
+    cot = np.random.default_rng(8).normal(0.0, 1.0, (E, H))
+    env = _env(E, N)
+    g = env.pool_vjp(W, b, cot, act, x=X, v=V)
+    scale = np.array([2.0 ** 300, 2.0 ** -300, 0.0])
+    gs = env.pool_vjp(W, b, cot * scale[:, None], act, x=X, v=V)
+    for k in ("g_x", "g_v", "g_W", "g_b"):
+        a, c = g[k], gs[k]
+        assert np.all(a[:2] != 0) or act == "relu"                      # (nothing to scale would show nothing)
+        for e in range(E):
+            assert _same(a[e] * scale[e] + 0.0, c[e]), (k, e)           # (+ 0.0: a zero cotangent gives +0, whatever the sign)
+        assert not np.signbit(c[2]).any(), k
+    env.close()
+
+
+def test_huge_and_non_finite_velocities():
+    E, N, H = 3, 1000, 5
+    X, V = _data(E, N, seed=41)
+    W, b = _layer(H, seed=9)
+    cot = np.random.default_rng(10).normal(0.0, 1.0, (E, H))
+    env = _env(E, N)
+    Vh = V.copy()
+    Vh[1, 17] = 1e300
+    for act in ACTS:
+        out, g = env.pool(W, b, act, x=X, v=Vh), env.pool_vjp(W, b, cot, act, x=X, v=Vh)
+        assert all(np.isfinite(a).all() for a in (out, g["g_x"], g["g_v"], g["g_W"], g["g_b"])), act
+        clean, gc = env.pool(W, b, act, x=X, v=V), env.pool_vjp(W, b, cot, act, x=X, v=V)
+        Vi = V.copy()
+        Vi[1, 17] = np.inf
+        Wp, bp = np.broadcast_to(W, (E, H, 3)).copy(), np.broadcast_to(b, (E, H)).copy()       # per environment: a gradient each
+        gcp = env.pool_vjp(Wp, bp, cot, act, x=X, v=V)
+        out, g = env.pool(W, b, act, x=X, v=Vi), env.pool_vjp(Wp, bp, cot, act, x=X, v=Vi)
+        assert np.isnan(out[1]).all() and all(np.isnan(g[k][1]).all() for k in ("g_x", "g_v", "g_W", "g_b")), act
+        for e in (0, 2):
+            assert _same(out[e], clean[e]) and all(_same(g[k][e], gcp[k][e]) for k in ("g_x", "g_v", "g_W", "g_b")), (act, e)
+        assert _same(gc["g_x"], gcp["g_x"])
+        # ... and the next call finds the work block clean
+        assert _same(env.pool(W, b, act, x=X, v=V), clean)
+    env.close()
+
+
+# ---- 4. device finite differences ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("act", ACTS)
+def test_vjp_matches_device_central_differences(act):
+    """<g, d> of pool_vjp against central differences of pool along random directions in (x, v, W, b) at eps = 1e-6; the bound is
+    100 x the same quantity of the restatement alone (its hand VJP against its own central differences), computed here."""
+    N, H, eps = 501, 5, 1e-6
+    x, v, W, b, cot = hp.case(N, H, seed=11)
+    env = _env(1, N)
+    fwd = lambda x_, v_, W_, b_: env.pool(W_, b_, act, x=x_[None], v=v_[None])[0]
+
+    def grad(x_, v_, W_, b_):
+        g = env.pool_vjp(W_, b_, cot[None], act, x=x_[None], v=v_[None])
+        return g["g_x"][0], g["g_v"][0], g["g_W"], g["g_b"]
+    seeds = range(3)
+    dev = max(hp.fd_error(fwd, grad, x, v, W, b, cot, eps, s) for s in seeds)
+    own = max(hp.fd_error(lambda *a: hp.forward(*a, L, act), lambda *a: hp.vjp(*a, cot, L, act), x, v, W, b, cot, eps, s) for s in seeds)
+    record_measure(f"pool_fd_device_{act}", dev)
+    record_measure(f"pool_fd_restatement_{act}", own)
+    assert dev < 100 * own, (dev, own)
+    env.close()
+
+
+# ---- 5. state rules ----------------------------------------------------------------------------------------------------------------------
+def _state(env):
+    return (*env.particles(), *env.fields(), *env.energies(), np.array([env.bad_count()]))
+
+
+def test_calls_touch_no_state_and_run_under_a_tape_and_a_walk():
+    import ocplasma_amd as oc
+    E, N, Ng, H, T = 2, 2000, 64, 5, 4
+    env = _env(E, N, Ng)
+    X = np.empty((E, N))
+    V = np.empty((E, N))
+    for e in range(E):
+        X[e], V[e] = po.synthetic_bump_on_tail(N, L, seed=3 + e)
+    env.reset(X, V)
+    env.set_actuator(oc.E_field(L, Ng, 2))
+    W, b = _layer(H, seed=12)
+    cot = np.random.default_rng(13).normal(0.0, 1.0, (E, H))
+    env.step(nsteps=2)
+    before = _state(env)
+    out, g = env.pool(W, b), env.pool_vjp(W, b, cot)
+    assert all(_same(a, c) for a, c in zip(before, _state(env)))
+    # under an open tape, and between the steps of a walk: allowed, the same bits, the tape as it was
+    env.start_tape(T)
+    env.step_actions_traj(np.zeros((T, E, 4)))
+    x_end, v_end = env.particles()
+    stats = env.tape_stats()
+    ot, gt = env.pool(W, b), env.pool_vjp(W, b, cot)
+    assert env.tape_stats() == stats
+    assert _same(ot, env.pool(W, b, x=x_end, v=v_end))
+    w = env.walk(2)
+    w.step(d_energies=np.ones((3, E)))
+    assert _same_results(ot, gt, env.pool(W, b), env.pool_vjp(W, b, cot))
+    for _ in range(T - 1):
+        w.step()
+    w.end()
+    env.stop_tape()
+    env.close()
+    assert np.isfinite(out).all() and np.isfinite(g["g_W"]).all()
+
+
+def test_refusals_name_their_reason():
+    from ocplasma_amd import _abi
+    E, N, H = 2, 100, 4
+    env = _env(E, N)
+    X, V = _data(E, N, seed=51)
+    p = np.zeros(4 * H)
+    out, cot, gx = np.zeros((E, H)), np.ones((E, H)), np.zeros((E, N))
+    A = lambda a: a.ctypes.data
+
+    def spec(hidden=H, activation=0, per_env=0, params_kind=_abi.PIC_HOST, v_scale=1.0, params=A(p)):
+        return _abi.PicPoolSpec(hidden, activation, per_env, params_kind, v_scale, params)
+
+    def both(why, s, x=A(X), v=A(V), kind=_abi.PIC_HOST):
+        with pytest.raises(_abi.PicError, match=why):
+            env._h.pool(s, x, v, kind, A(out))
+        with pytest.raises(_abi.PicError, match=why):
+            env._h.pool_vjp(s, x, v, A(cot), kind, A(gx), 0, 0)
+    both(r"error -1: pic_pool\w*: hidden must be 1\.\.256", spec(hidden=0))
+    both(r"error -1: pic_pool\w*: hidden must be 1\.\.256", spec(hidden=257))
+    both(r"error -1: pic_pool\w*: activation must be", spec(activation=2))
+    both(r"error -1: pic_pool\w*: per_env must be 0 or 1", spec(per_env=2))
+    both(r"error -1: pic_pool\w*: bad params_mem_kind", spec(params_kind=7))
+    both(r"error -1: pic_pool\w*: params is NULL", spec(params=None))
+    both(r"error -1: pic_pool\w*: v_scale is not finite", spec(v_scale=float("nan")))
+    both(r"error -1: pic_pool\w*: bad mem_kind", spec(), kind=5)
+    both(r"error -1: pic_pool\w*: x and v must both be given or both be NULL", spec(), v=0)
+    both(r"error -1: pic_pool\w*: x and v must both be given or both be NULL", spec(), x=0)
+    with pytest.raises(_abi.PicError, match="error -1: pic_pool: out is NULL"):
+        env._h.pool(spec(), A(X), A(V), _abi.PIC_HOST, 0)
+    with pytest.raises(_abi.PicError, match="error -1: pic_pool_vjp: cot is NULL"):
+        env._h.pool_vjp(spec(), A(X), A(V), 0, _abi.PIC_HOST, A(gx), 0, 0)
+    # the stored particles: PIC_ESTATE before pic_reset and during a staged step, PIC_EINVAL on a float32 / fixed32 handle
+    both(r"error -3: pic_pool\w*: call pic_reset first", spec(), x=0, v=0)
+    env.reset(X, V)
+    env._h.pool(spec(), 0, 0, _abi.PIC_HOST, A(out))
+    env._h.step_stage(1, np.zeros((E, 64)))
+    both(r"error -3: pic_pool\w*: a staged step is in progress", spec(), x=0, v=0)
+    env._h.pool(spec(), A(X), A(V), _abi.PIC_HOST, A(out))          # (given particles need no state)
+    env.close()
+    for kw in (dict(dtype="float32"), dict(dtype="float32", position_dtype="fixed32")):
+        env = _env(E, N, **kw)
+        env.reset(X, V)
+        both(r"error -1: pic_pool\w*: the stored particles need float64 particles with float64 positions", spec(), x=0, v=0)
+        env._h.pool(spec(), A(X), A(V), _abi.PIC_HOST, A(out))
+        env.close()
+
+
+def test_forward_mode_is_torchs_own_error():
+    from ocplasma_amd.control.pool import pooled_features
+    import torch.autograd.forward_ad as fwAD
+    E, N, H = 1, 63, 5
+    env = _env(E, N)
+    X, V = _data(E, N, seed=61)
+    x, v, W, b = _cuda(X, V, *_layer(H, seed=14))
+    with fwAD.dual_level():
+        with pytest.raises(NotImplementedError, match="forward mode AD"):
+            pooled_features(env, x, v, fwAD.make_dual(W, torch.ones_like(W)), b)
+    env.close()
+
+
+# ---- 6. the closed loop ------------------------------------------------------------------------------------------------------------------
+def test_closed_loop_gradients_match_the_autograd_oracle():
+    """rollout_policy(observe="state") under rho(PoolEncoder(x, v)) against hp_policy.rollout with deepsets_state on the same
+    parameters: traces and the gradients of W, b and rho's parameters, with test_gpu_policy_grad's bound for its state policy."""
+    import ocplasma_amd as oc
+    from ocplasma_amd.control.pool import PoolEncoder
+    from ocplasma_amd.env import grad
+    from test_gpu_policy_grad import GRAD_BOUND, M, _make, _weights
+    import hp_feedback as hf
+    import hp_tangent_walk as hw
+    from hp_grad_cases import NODE_DISTANCE
+    E, N, Ng, T, H = 2, 3000, 64, 3, 8
+    p = hpp.deepsets_params(2 * M, H, seed=3)
+    w_hist, _ = _weights(T, E, M, seed=4)
+    S = hpp.ha.Setup(N, Ng, L, 1.0, 0.1)
+    B = hf.basis(L, Ng, M)
+    for seed in (7, 8, 9, 10):          # (a draw with a sub-stage position on a node gets another seed, never another threshold)
+        env, X, V = _make(E, N, Ng, seed=seed)
+        # the oracle: shared parameters, so the gradient is the sum over the environments
+        pc = {k: t.clone().requires_grad_(True) for k, t in p.items()}
+        Jc, hists, dist = 0.0, [], np.inf
+        for e in range(E):
+            hist, acts, obs = hpp.rollout(torch.as_tensor(X[e]), torch.as_tensor(V[e]), lambda o: hpp.deepsets_state(pc, o, L), S, T, M, "state")
+            Jc = Jc + hpp.loss_terms(hist, acts, obs, w_hist[:, e], 0.05)
+            hists.append(hist)
+            dist = min(dist, hw.node_distance(X[e], V[e], [B @ a for a in acts.detach().numpy()], S))
+        if dist > NODE_DISTANCE:
+            break
+        env.close()
+    assert dist > NODE_DISTANCE, dist
+    gc = torch.autograd.grad(Jc, [pc[k] for k in ("W1", "b1", "W2", "b2")])
+    env.use_torch_stream()
+    enc = PoolEncoder(env, H)
+    with torch.no_grad():
+        enc.W.copy_(p["W1"])
+        enc.b.copy_(p["b1"])
+    W2, b2 = (p[k].to("cuda").clone().requires_grad_(True) for k in ("W2", "b2"))
+    wh = torch.as_tensor(w_hist, device="cuda")
+
+    def loss(policy):
+        ke, pe, per, acts, obs = grad.rollout_policy(env, policy, T, observe="state")
+        return (torch.stack([ke, pe, per], -1) * wh).sum() + 0.05 * (acts ** 2).sum(), torch.stack([ke, pe, per], -1)
+
+    J, hist_dev = loss(lambda o: enc(o) @ W2.T + b2)
+    J.backward()
+    got = [t.grad.cpu().numpy().ravel() for t in (enc.W, enc.b, W2, b2)]
+    env.stop_tape()
+    # the torch-layers route on the device, from the same start
+    env.reset(X, V)
+    pt = {k: t.to("cuda").clone().requires_grad_(True) for k, t in p.items()}
+    Jt, _ = loss(lambda o: hpp.deepsets_state(pt, o, L))
+    Jt.backward()
+    torch_route = [pt[k].grad.cpu().numpy().ravel() for k in ("W1", "b1", "W2", "b2")]
+    record_measure("pool_closed_loop_vs_torch_layers_rel_err", rel_err(np.concatenate(got), np.concatenate(torch_route)))
+    env.stop_tape()
+    env.close()
+    err = rel_err(np.concatenate(got), np.concatenate([g.numpy().ravel() for g in gc]))
+    err_hist = rel_err(hist_dev.detach().cpu().numpy(), torch.stack(hists, 1).detach().numpy())
+    record_measure("pool_closed_loop_grad_rel_err", err)
+    record_measure("pool_closed_loop_trace_rel_err", err_hist)
+    assert err < GRAD_BOUND and err_hist < GRAD_BOUND, (err, err_hist)
