@@ -258,6 +258,21 @@ inline size_t pool_parts(Carver c, const BlockDims& d, const PoolCallShape& s, P
   return c.at;
 }
 
+// The passes' launch: a workgroup walks chunks_per_wg consecutive chunks of kPoolChunkTiles tiles (2 particles each), and
+// `workgroups` of them cover an environment.  About 4096 workgroups of 4 waves in all: the passes are bound by tanh and sincos,
+// and a workgroup holds 8 KB of LDS at most.
+constexpr long long kPoolChunkTiles = 512;      // (pic_pool.h: POOL_BLOCK * kPoolTiles; host_pool.h asserts it)
+struct PoolPlan { long long chunks_per_wg = 0, workgroups = 0; };
+
+inline PoolPlan pool_plan(size_t num_envs, size_t N) {
+  const long long E = (long long)num_envs, ntiles = ((long long)N + 1) / 2, nchunks = (ntiles + kPoolChunkTiles - 1) / kPoolChunkTiles;
+  const long long wpe = std::max(1LL, std::min((4096 + E - 1) / E, nchunks));
+  PoolPlan p;
+  p.chunks_per_wg = (nchunks + wpe - 1) / wpe;
+  p.workgroups = (nchunks + p.chunks_per_wg - 1) / p.chunks_per_wg;
+  return p;
+}
+
 // ---- forward mode through closed loops (host_tangent_walk.h) ------------------------------------------------------
 // the working rows of a walk of kc directions observing mo modes: the field tangent the last step left dM [kc][env][Ng], its
 // energies' tangents [kc][3][env], the observation's tangent [kc][env][2 mo], the law's dm [kc][env][2M], the action tangent of

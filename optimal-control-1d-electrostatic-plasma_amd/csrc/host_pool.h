@@ -63,11 +63,10 @@ static int pool_begin(pic_handle* h, const pic_pool_spec* s, const void* x, cons
   a.umax = w.max; a.acc = w.acc;
   a.N = (long long)N; a.L = h->cfg.L; a.v_scale = s->v_scale; a.H = (int)H; a.activation = s->activation;
   while (((int64_t)1 << a.bitsN) < (int64_t)N) ++a.bitsN;
-  // about 4096 workgroups of 4 waves in all: the passes are bound by tanh and sincos, and a workgroup holds 8 KB of LDS at most
-  const long long chunk = (long long)POOL_BLOCK * kPoolTiles, ntiles = ((long long)N + 1) / 2, nchunks = (ntiles + chunk - 1) / chunk;
-  const long long wpe = std::max(1LL, std::min((4096 + (long long)E - 1) / (long long)E, nchunks));
-  a.chunks_per_wg = (nchunks + wpe - 1) / wpe;
-  grid = dim3((unsigned)((nchunks + a.chunks_per_wg - 1) / a.chunks_per_wg), (unsigned)E);
+  static_assert(kPoolChunkTiles == (long long)POOL_BLOCK * kPoolTiles, "pool_plan's chunk is the kernels'");
+  const PoolPlan plan = pool_plan(E, N);
+  a.chunks_per_wg = plan.chunks_per_wg;
+  grid = dim3((unsigned)plan.workgroups, (unsigned)E);
   return PIC_OK;
 }
 

@@ -225,3 +225,130 @@ def fd_error(fwd, grad, x, v, W, b, cot, eps, seed):
     lin = sum(float(np.sum(np.asarray(gi) * di)) for gi, di in zip(g, d))
     f = lambda sgn: float(np.dot(cot, fwd(*(a + sgn * eps * di for a, di in zip((x, v, W, b), d)))))
     return abs(lin - (f(1.0) - f(-1.0)) / (2.0 * eps)) / abs(lin)
+
+
+# ---- the passes' launch plan (csrc/host_blocks.h: pool_plan), mirrored; tests/test_pool_cpu.py pins it against the C++ ---------
+CHUNK_TILES = 512               # tiles of 2 particles in a workgroup's chunk
+
+
+def plan(E, N):
+    """{"nchunks", "wpe", "chunks_per_wg", "workgroups"} of a pool call on E environments of N particles."""
+    nchunks = -(-((N + 1) // 2) // CHUNK_TILES)
+    wpe = max(1, min(-(-4096 // E), nchunks))
+    cpw = -(-nchunks // wpe)
+    return {"nchunks": nchunks, "wpe": wpe, "chunks_per_wg": cpw, "workgroups": -(-nchunks // cpw)}
+
+
+# ---- data and cases of the edge tests (tests/test_gpu_pool_edges.py and their CPU companions) ------------------------------------
+def box_data(E, N, seed, L=50.0):
+    """Wrapped positions with the box's edges among them (-0.0, the last double below L), velocities of a bump-on-tail's size."""
+    rng = np.random.default_rng(seed)
+    X, V = rng.uniform(0.0, L, (E, N)), rng.normal(0.0, 2.0, (E, N))
+    X[:, 0] = -0.0
+    if N >= 3:
+        X[:, 1] = np.nextafter(L, 0.0)
+    return X, V
+
+
+def layer(H, seed, lead=()):
+    rng = np.random.default_rng(seed)
+    return rng.normal(0.0, 0.5, lead + (H, 3)), rng.normal(0.0, 0.1, lead + (H,))
+
+
+# v_scale and L: the exact powers of two (and -2), and the parity matrix
+V_SCALES_EXACT = (2.0 ** -20, 2.0 ** 7, -2.0)
+V_SCALES = (0.37, -3.0, 1e3)
+BOX_LENGTHS = (TWO_PI, 0.1, 1000.0)
+SCALE_NS, SCALE_H = (2, 1025), 5
+# every (L, v_scale, N, H) a device test compares with the twin under bound(): the restatement alone must be inside it there
+BOUND_SETS = sorted({(Lb, s, N, SCALE_H) for Lb in BOX_LENGTHS for s in V_SCALES for N in SCALE_NS}
+                    | {(50.0, s, 1025, SCALE_H) for s in V_SCALES_EXACT + (1.0,)}
+                    | {(Lb, s, N, SCALE_H) for Lb in (50.0,) + BOX_LENGTHS for s in (1.0, 2.0 ** -20) for N in SCALE_NS})
+
+
+def scale_case(Lb, s, N, H):
+    """One environment of the v_scale / L tests: (X [2, N], V, W, b, cot [2, H])."""
+    X, V = box_data(2, N, seed=N + H, L=Lb)
+    W, b = layer(H, seed=3)
+    return X, V, W, b, np.random.default_rng(H).normal(0.0, 1.0, (2, H))
+
+
+def batch_errors(out, g, X, V, W, b, cot, L, activation, v_scale=1.0, skip=()):
+    """(forward error, VJP error): the worst of errors() over the environments of a batch.  out [E, H] or None; g: pool_vjp's
+    dict or None (entries may be None); W [E, H, 3] and b [E, H] for per-environment parameters -- shared ones have one summed
+    gradient, which is not looked at here.  The hidden units in `skip` are left out of the forward's comparison."""
+    ef = eg = 0.0
+    keep = [k for k in range(np.shape(b)[-1]) if k not in skip]
+    for e in range(len(X)):
+        per_env = np.ndim(W) == 3
+        We, be = (W[e], b[e]) if per_env else (W, b)
+        gv = None
+        if g is not None:
+            pick = lambda k: None if g[k] is None else np.asarray(g[k])[e]
+            gv = (pick("g_x"), pick("g_v"), pick("g_W") if per_env else None, pick("g_b") if per_env else None)
+        if out is not None and skip:
+            q, u = features(X[e], V[e], L, v_scale)
+            ref = forward_ld(X[e], V[e], We, be, L, activation, v_scale)
+            d = np.abs(np.asarray(out)[e].astype(LD) - ref) / forward_scale(We, be, u, activation)
+            ef = max(ef, float(np.max(d[keep])))
+            a, c = errors(None, gv, X[e], V[e], We, be, cot[e], L, activation, v_scale) if gv else (0.0, 0.0)
+        else:
+            a, c = errors(None if out is None else np.asarray(out)[e], gv, X[e], V[e], We, be,
+                          None if cot is None else cot[e], L, activation, v_scale)
+        ef, eg = max(ef, a), max(eg, c)
+    return ef, eg
+
+
+def restated(X, V, W, b, cot, L, activation, v_scale=1.0, vjp_too=True):
+    """The float64 restatement over a batch, shaped like the device's results: out [E, H] and pool_vjp's dict (per-environment
+    gradients when W is [E, H, 3], else the environments' sum in ascending order)."""
+    per_env = np.ndim(W) == 3
+    pe = lambda e: (W[e], b[e]) if per_env else (W, b)
+    out = np.stack([forward(X[e], V[e], *pe(e), L, activation, v_scale) for e in range(len(X))])
+    if not vjp_too:
+        return out, None
+    gs = [vjp(X[e], V[e], *pe(e), cot[e], L, activation, v_scale) for e in range(len(X))]
+    g = {"g_x": np.stack([a[0] for a in gs]), "g_v": np.stack([a[1] for a in gs])}
+    if per_env:
+        g["g_W"], g["g_b"] = np.stack([a[2] for a in gs]), np.stack([a[3] for a in gs])
+    else:
+        g["g_W"], g["g_b"] = gs[0][2], gs[0][3]
+        for a in gs[1:]:
+            g["g_W"], g["g_b"] = g["g_W"] + a[2], g["g_b"] + a[3]
+    return out, g
+
+
+# activation edges: N = 1000, H = 6, E = 2
+EDGE_N, EDGE_H, EDGE_E = 1000, 6, 2
+
+
+def edge_layer():
+    """W [6, 3], b [6]: row 0 = (0, 0, 1), -1 (relu's kink at u = 1), row 1 with W_12 = 40 (tanh saturates for |u| > 1), row 2
+    all zero (B_2 = 0), rows 3..5 a policy's size."""
+    W, b = layer(EDGE_H, seed=17)
+    W[0], b[0] = (0.0, 0.0, 1.0), -1.0
+    W[1, 2] = 40.0
+    W[2], b[2] = 0.0, 0.0
+    return W, b
+
+
+def edge_cot():
+    return np.random.default_rng(18).normal(0.0, 1.0, (EDGE_E, EDGE_H))
+
+
+def kink_velocities(scale):
+    """(V [2, 1000], v_scale) with u = V v_scale = 1.0 exactly at the even particles; the odd ones have u < 1 in environment 0
+    and u = 3 in environment 1.  scale = 1: v = 1, v_scale = 1; scale = 2: v = 2, v_scale = 0.5 (the same u, bit for bit)."""
+    V = np.ones((EDGE_E, EDGE_N))
+    V[0, 1::2] = np.random.default_rng(19).uniform(-3.0, 0.99, EDGE_N // 2)
+    V[1, 1::2] = 3.0
+    return V * scale, 1.0 / scale
+
+
+def saturating_velocities():
+    """V [2, 1000]: |v| in [1.5, 4] with random signs in environment 0 (every particle saturates row 1), a bump-on-tail's size in
+    environment 1."""
+    rng = np.random.default_rng(20)
+    V = rng.normal(0.0, 2.0, (EDGE_E, EDGE_N))
+    V[0] = rng.uniform(1.5, 4.0, EDGE_N) * rng.choice([-1.0, 1.0], EDGE_N)
+    return V

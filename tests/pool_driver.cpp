@@ -1,8 +1,9 @@
-// pool_driver.cpp -- the layout of the pooled features' work block (csrc/host_blocks.h: pool_parts) as a stand-alone program,
-// for tests/test_pool_cpu.py.
+// pool_driver.cpp -- the layout of the pooled features' work block and the launch plan of their passes (csrc/host_blocks.h:
+// pool_parts, pool_plan) as a stand-alone program, for tests/test_pool_cpu.py.
 // stdin: one call per line,  num_envs N H flags  (bit i of flags = field i of: per_env vjp host params_host xv g_x g_v g_params).
 // stdout: one line each: "ok pool=<bytes>" followed by "view=<offset>" for each view in order ("null" for a part without
 // elements).  The sizing pass (no base) must give the same bytes and set no view: the driver checks both.
+// A line  plan num_envs N  gives "ok chunks_per_wg=<n> workgroups=<n>".
 #include <cstdio>
 
 #include "host_blocks.h"
@@ -20,6 +21,11 @@ int main() {
   while (std::fgets(line, sizeof line, stdin)) {
     long long E, N, H;
     int flags;
+    if (std::sscanf(line, "plan %lld %lld", &E, &N) == 2) {
+      const PoolPlan p = pool_plan((size_t)E, (size_t)N);
+      std::printf("ok chunks_per_wg=%lld workgroups=%lld\n", p.chunks_per_wg, p.workgroups);
+      continue;
+    }
     if (std::sscanf(line, "%lld %lld %lld %d", &E, &N, &H, &flags) != 4) {
       std::fprintf(stderr, "pool_driver: malformed line: %s", line);
       return 2;

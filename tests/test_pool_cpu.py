@@ -1,6 +1,7 @@
 """The pooled particle features (pic_pool, pic_pool_vjp) without a GPU: the CPU restatement (tests/hp_pool.py)
-against torch and against finite differences, its floor against the longdouble twin, the work block's layout through a
-stand-alone driver (also under the address and undefined-behaviour sanitizers), and the Python argument checks."""
+against torch and against finite differences, its floor against the longdouble twin, the work block's layout and the passes'
+launch plan through a stand-alone driver (also under the address and undefined-behaviour sanitizers), the Python argument checks,
+and the preconditions of the device's edge tests (tests/test_gpu_pool_edges.py) on the restatement."""
 import os
 import shutil
 import subprocess
@@ -225,3 +226,109 @@ def test_header_abi_and_exports_agree():
     assert _abi.SIGNATURES["pic_pool"] == [vp, ctypes.POINTER(_abi.PicPoolSpec), vp, vp, ci, vp]
     assert _abi.SIGNATURES["pic_pool_vjp"] == [vp, ctypes.POINTER(_abi.PicPoolSpec), vp, vp, vp, ci, vp, vp, vp]
     assert "#define PICSTEP_ABI_VERSION 5" in flat and _abi.ABI_VERSION == 5
+
+
+# ---- 6. the passes' launch plan ---------------------------------------------------------------------------------------------------
+PLAN_TABLE = [
+    # E, N, nchunks, wpe, chunks_per_wg, workgroups
+    (3, 8193, 9, 9, 1, 9),              # the largest shapes of tests/test_gpu_pool.py: one chunk per workgroup, all of them
+    (300, 4097, 5, 5, 1, 5),
+    (2, 3000, 3, 3, 1, 3),
+    (64, 1000000, 977, 64, 16, 62),     # the workload of profiles/pool_cost.md
+    (4096, 1025, 2, 1, 2, 1),           # tests/test_gpu_pool_edges.py: the smallest shapes with a second chunk
+    (4096, 2561, 3, 1, 3, 1),
+    (1366, 3075, 4, 3, 2, 2),
+    (300, 20001, 20, 14, 2, 10),
+    (1, 1, 1, 1, 1, 1),
+    (1, 1025, 2, 2, 1, 2),
+    (5000, 1024, 1, 1, 1, 1),
+]
+
+
+def test_pool_plan_table_and_mirror(drivers):
+    import itertools
+    for E, N, nchunks, wpe, cpw, wgs in PLAN_TABLE:
+        assert hp.plan(E, N) == {"nchunks": nchunks, "wpe": wpe, "chunks_per_wg": cpw, "workgroups": wgs}, (E, N)
+    shapes = [(E, N) for E, N, *_ in PLAN_TABLE]
+    shapes += list(itertools.product((1, 2, 3, 64, 300, 1365, 1366, 2048, 4095, 4096, 4097, 100000),
+                                     (1, 2, 1023, 1024, 1025, 2048, 2049, 2561, 3075, 8193, 20001, 1000000, 2 ** 31 + 1)))
+    lines = [f"plan {E} {N}" for E, N in shapes]
+    for run in drivers:
+        for (E, N), got in zip(shapes, run(lines)):
+            p = hp.plan(E, N)
+            assert got == f"ok chunks_per_wg={p['chunks_per_wg']} workgroups={p['workgroups']}", (E, N)
+            # the workgroups cover every chunk, and none of them is empty
+            assert p["workgroups"] * p["chunks_per_wg"] >= p["nchunks"] > (p["workgroups"] - 1) * p["chunks_per_wg"], (E, N)
+
+
+# ---- 7. the edge tests' preconditions and their exact claims, on the restatement ----------------------------------------------------
+def test_restatement_alone_is_inside_the_bound_at_every_scale_set():
+    """tests/test_gpu_pool_edges.py compares the device with the twin under hp.bound at other v_scale and L than the floor was
+    taken at: the restatement alone must be inside the bound there, or the bound would not be the device's to miss."""
+    worst = {"forward": 0.0, "vjp": 0.0}
+    for Lb, s, N, H in hp.BOUND_SETS:
+        X, V, W, b, cot = hp.scale_case(Lb, s, N, H)
+        Wp, bp = np.broadcast_to(W, (2, H, 3)), np.broadcast_to(b, (2, H))
+        for act in ("tanh", "relu"):
+            out, g = hp.restated(X, V, Wp, bp, cot, Lb, act, s)
+            ef, eg = hp.batch_errors(out, g, X, V, Wp, bp, cot, Lb, act, s)
+            assert ef < hp.bound("forward", N) and eg < hp.bound("vjp", N), (Lb, s, N, act, ef, eg)
+            worst["forward"], worst["vjp"] = max(worst["forward"], ef), max(worst["vjp"], eg)
+    record_measure("pool_edges_restatement_forward", worst["forward"])
+    record_measure("pool_edges_restatement_vjp", worst["vjp"])
+
+
+def _eq(a, b):
+    return np.array_equal(np.ascontiguousarray(a).view(np.int64), np.ascontiguousarray(b).view(np.int64))
+
+
+@pytest.mark.parametrize("act", ["tanh", "relu"])
+def test_restatement_v_scale_is_exact_for_powers_of_two_and_zero(act):
+    X, V, W, b, cot = hp.scale_case(L, 1.0, 1025, 5)
+    for s in hp.V_SCALES_EXACT:
+        o1, g1 = hp.restated(X, V, W, b, cot, L, act, s)
+        o2, g2 = hp.restated(X, s * V, W, b, cot, L, act, 1.0)
+        assert _eq(o1, o2) and all(_eq(g1[k], g2[k]) for k in ("g_x", "g_W", "g_b")) and _eq(g1["g_v"], s * g2["g_v"]), s
+    o0, g0 = hp.restated(X, V, W, b, cot, L, act, 0.0)
+    oz, gz = hp.restated(X, np.zeros_like(V), W, b, cot, L, act, 1.0)
+    assert _eq(o0, oz) and _eq(g0["g_x"], gz["g_x"]) and _eq(g0["g_W"][:, :2], gz["g_W"][:, :2]) and _eq(g0["g_b"], gz["g_b"])
+    assert np.all(g0["g_v"] == 0) and np.all(g0["g_W"][:, 2] == 0)
+
+
+def test_restatement_activation_edges():
+    """The exact claims of the device's activation-edge tests hold for the contract as restated, and the restatement stays
+    inside the bound at those inputs."""
+    E, N, H = hp.EDGE_E, hp.EDGE_N, hp.EDGE_H
+    X, _ = hp.box_data(E, N, seed=23)
+    W, b = hp.edge_layer()
+    Wp, bp, cot = np.broadcast_to(W, (E, H, 3)).copy(), np.broadcast_to(b, (E, H)).copy(), hp.edge_cot()
+    fb, vb = hp.bound("forward", N), hp.bound("vjp", N)
+    # relu's kink
+    outs = []
+    for scale in (1.0, 2.0):
+        V, s = hp.kink_velocities(scale)
+        out, g = hp.restated(X, V, Wp, bp, cot, L, "relu", s)
+        ef, eg = hp.batch_errors(out, g, X, V, Wp, bp, cot, L, "relu", s)
+        assert ef < fb and eg < vb, (scale, ef, eg)
+        assert _eq(out[0, 0], 0.0) and _eq(g["g_b"][0, 0], 0.0)
+        outs.append(out)
+    assert _eq(*outs)
+    # tanh's saturation
+    V = hp.saturating_velocities()
+    out, g = hp.restated(X, V, Wp, bp, cot, L, "tanh")
+    ef, eg = hp.batch_errors(out, g, X, V, Wp, bp, cot, L, "tanh")
+    assert ef < fb and eg < vb, (ef, eg)
+    assert _eq(out[0, 1], float(np.sum(np.sign(V[0]))) / N) and _eq(g["g_W"][0, 1], np.zeros(3)) and _eq(g["g_b"][0, 1], 0.0)
+    Vh, Wh = V.copy(), Wp.copy()
+    Vh[1, 5], Wh[:, 1, 2] = 1e200, 1e200
+    with np.errstate(over="ignore"):                  # (z = inf is the case)
+        out, _ = hp.restated(X, Vh, Wh, bp, None, L, "tanh", vjp_too=False)
+    assert np.isfinite(out).all() and hp.batch_errors(out, None, X, Vh, Wh, bp, None, L, "tanh")[0] < fb
+    # B_k = 0: +0, and the other rows as without it
+    V = hp.box_data(E, N, seed=23)[1]
+    out, g = hp.restated(X, V, Wp, bp, cot, L, "relu")
+    rest = [0, 1, 3, 4, 5]
+    o5, g5 = hp.restated(X, V, Wp[:, rest], bp[:, rest], cot[:, rest], L, "relu")
+    assert _eq(out[:, 2], np.zeros(E)) and _eq(g["g_W"][:, 2], np.zeros((E, 3))) and _eq(g["g_b"][:, 2], np.zeros(E))
+    assert _eq(out[:, rest], o5) and _eq(g["g_W"][:, rest], g5["g_W"]) and _eq(g["g_b"][:, rest], g5["g_b"])
+    assert _eq(g["g_x"], g5["g_x"]) and _eq(g["g_v"], g5["g_v"])
