@@ -3,7 +3,7 @@
 the backward.  phi is one layer, tanh(W (cos q, sin q, v) + b), in float64; rho is the example's.  Trained with Adam on the same
 cost on the same ensemble; prints J (mean over the ensemble) for each iteration.
 
-    python examples/pooled_policy.py [num_envs] [N] [steps] [iterations]
+    python examples/pooled_policy.py [num_envs] [N] [steps] [iterations] [--layernorm]
 """
 import os
 import sys
@@ -23,9 +23,10 @@ class PooledDeepSets(torch.nn.Module):
     """(x, v) [E, N] each -> actions [E, 2M]: PoolEncoder (phi and the mean, on the device's own kernels), then rho; the last
     layer starts at zero (a = 0: the uncontrolled plasma)."""
 
-    def __init__(self, env, max_mode, hidden=32):
+    def __init__(self, env, max_mode, hidden=32, layernorm=False):
         super().__init__()
-        self.enc = PoolEncoder(env, hidden)
+        # --layernorm: phi = Linear -> LayerNorm -> ReLU, the reference encoder's per-particle layer (pic_pool_ln, DESIGN.md 7s)
+        self.enc = PoolEncoder(env, hidden, "relu", layernorm=True) if layernorm else PoolEncoder(env, hidden)
         self.rho = torch.nn.Sequential(torch.nn.Linear(hidden, hidden), torch.nn.Tanh(), torch.nn.Linear(hidden, 2 * max_mode)).double()
         torch.nn.init.zeros_(self.rho[-1].weight)
         torch.nn.init.zeros_(self.rho[-1].bias)
@@ -34,16 +35,16 @@ class PooledDeepSets(torch.nn.Module):
         return self.rho(self.enc(xv))
 
 
-def make(env, max_mode, hidden=32):
+def make(env, max_mode, hidden=32, layernorm=False):
     torch.manual_seed(0)
-    return PooledDeepSets(env, max_mode, hidden).to("cuda")
+    return PooledDeepSets(env, max_mode, hidden, layernorm).to("cuda")
 
 
-def run(num_envs=64, N=5000, steps=50, iters=10, N_mesh=250, L=50.0, max_mode=5, lam=0.1, lr=0.02, seed=3):
+def run(num_envs=64, N=5000, steps=50, iters=10, N_mesh=250, L=50.0, max_mode=5, lam=0.1, lr=0.02, seed=3, layernorm=False):
     env = BatchedPIC(num_envs, N, N_mesh, L=L, dt=0.1)
     env.set_actuator(E_field(L, N_mesh, max_mode))
     env.use_torch_stream()
-    policy = make(env, max_mode)
+    policy = make(env, max_mode, layernorm=layernorm)
     opt = torch.optim.Adam(policy.parameters(), lr=lr)
     history = []
     for it in range(iters):
@@ -59,5 +60,5 @@ def run(num_envs=64, N=5000, steps=50, iters=10, N_mesh=250, L=50.0, max_mode=5,
 
 
 if __name__ == "__main__":
-    h = run(*[int(a) for a in sys.argv[1:]])
+    h = run(*[int(a) for a in sys.argv[1:] if a != "--layernorm"], layernorm="--layernorm" in sys.argv[1:])
     print(f"pooled: J {h[0]:.6e} -> {h[-1]:.6e}")

@@ -898,6 +898,53 @@ int pic_pool(pic_handle* h, const pic_pool_spec* s, const void* x, const void* v
 int pic_pool_vjp(pic_handle* h, const pic_pool_spec* s, const void* x, const void* v, const double* cot, int mem_kind, void* g_x,
                  void* g_v, double* g_params);
 
+/* ---- Pooled particle features with a LayerNorm (additive to ABI 5) ---------------------------------------------
+ * The per-particle layer Linear(3, H) -> LayerNorm(H) -> activation and the mean over the particles, without an [N][H] array.
+ * Parameters W [H][3] row-major, b [H], gamma [H], beta [H] (P = 6H float64; one vector, or [num_envs][P] with per_env, in
+ * params_mem_kind memory), scalars v_scale, eps and period (0: the handle's L).  All arithmetic is float64 with every product
+ * rounded before its sum (no FMA).  Per particle i, H = hidden units (1..256):
+ *     q_i = ((2 pi) x_i) / period      c_i, s_i = the device's cos, sin of q_i      u_i = v_i v_scale      z_ik as pic_pool's
+ *     mu_i = (sum_k z_ik) / H   (from +0 over ascending k)        d_ik = z_ik - mu_i
+ *     var_i = (sum_k d_ik d_ik) / H   (two-pass, biased)          r_i = 1 / sqrt(var_i + eps)        y_ik = d_ik r_i
+ *     n_ik = gamma_k y_ik + beta_k   (the product rounded first)
+ *     h_ik = tanh(n_ik) (PIC_ACT_TANH) or n_ik > 0 ? n_ik : +0.0 (PIC_ACT_RELU)            out_k = (sum_i h_ik) / N
+ * The sum over particles is pic_pool's 64-bit integer sum in the unit 2^(e_k + b - 61), 2^b >= N: e_k = 0 for tanh; for relu
+ * B_k = (|gamma_k| sqrt(H) + |beta_k|) (1 + 2^-50), e_k = ilogb(B_k) + 1.  |y_ik| <= sqrt(H - 1) < sqrt(H) whatever the data, so
+ * the relu unit depends on the parameters alone; B_k = 0 gives +0.  Order-free and reproducible as pic_pool.
+ * pic_pool_ln_vjp: for a cotangent cot [num_envs][H], with a_ik = 1 - h_ik^2 (tanh) or n_ik > 0 (relu),
+ *     dn_ik = (cot_k a_ik) / N       g_gamma_k = sum_i dn_ik y_ik       g_beta_k = sum_i dn_ik       dy_ik = dn_ik gamma_k
+ *     m1_i = (sum_k dy_ik) / H       m2_i = (sum_k dy_ik y_ik) / H      dz_ik = ((dy_ik - m1_i) - y_ik m2_i) r_i
+ *     g_W_k0 = sum_i dz_ik c_i    g_W_k1 = sum_i dz_ik s_i    g_W_k2 = sum_i dz_ik u_i    g_b_k = sum_i dz_ik
+ *     g_x_i = (2 pi / period) sum_k dz_ik (W_k1 c_i - W_k0 s_i)         g_v_i = v_scale sum_k dz_ik W_k2
+ * g_x, g_v: float64 sums from +0 over ascending k, one thread per particle; dense [num_envs][N] rows, overwritten.  The six
+ * parameter sums are integer sums in the units of bounds known before the pass, each times the margin 1 + 2^-40:
+ *     g_beta_k: |cot_k| / N         g_gamma_k: (|cot_k| / N) sqrt(H)
+ *     g_W_k., g_b_k: ((D_k + (1 + sqrt(H)) D_max) r_max) max(1, u_max),   D_k = (|cot_k| |gamma_k|) / N,  D_max = max_k D_k,
+ * r_max = max_i r_i (at most 1 / sqrt(eps)) and u_max = max_i |u_i| of the environment, both taken first as order-independent
+ * maxima of bit patterns.  A zero bound gives +0, a non-finite bound NaN.  g_params is laid out as params: [P], the
+ * per-environment vectors added in ascending environment order, or [num_envs][P] with per_env; g_x, g_v, g_params may each be
+ * NULL.  Scaling an environment's cotangent by a power of two scales its gradients bit for bit while they stay normal doubles.
+ * Non-finite and overflowing input.  An environment is NaN as a whole -- every output of that environment and of no other --
+ *   - for a non-finite u_i or q_i;
+ *   - for a non-finite W_k. or b_k (the mean over k spreads it to every unit);
+ *   - where z or var could overflow: max_k (((|W_k0| + |W_k1|) + |W_k2| u_max) + |b_k|) > 2^500;
+ *   - in pic_pool_ln_vjp also for a non-finite gamma_k, beta_k or cot_k (they reach every dz through m1, m2).
+ * In pic_pool_ln a non-finite gamma_k or beta_k gives NaN in out_k alone.  The next call finds the work block clean.
+ * H = 1: d = 0, y = 0, out = act(beta), and every dz is exactly +0: g_x, g_v, g_W, g_b are exactly 0.
+ * Memory kinds, the stored particles (x = v = NULL; float64 handles only), state rules and refusals are pic_pool's and
+ * pic_pool_vjp's, with the same messages; in addition PIC_EINVAL, before anything is enqueued, unless eps is finite and > 0 and
+ * period finite and >= 0.  The working memory is pic_pool's block, laid out per call: 8 num_envs (1 + H) bytes of sums and max
+ * words for pic_pool_ln, 8 num_envs (2 + 6H) for the VJP, 8 num_envs P more for shared parameters' gradient, and the device
+ * copies of what is given in host memory. */
+typedef struct pic_pool_ln_spec {
+  int32_t hidden, activation, per_env, params_mem_kind;
+  double v_scale, eps, period;
+  const double* params;
+} pic_pool_ln_spec;
+int pic_pool_ln(pic_handle* h, const pic_pool_ln_spec* s, const void* x, const void* v, int mem_kind, double* out);
+int pic_pool_ln_vjp(pic_handle* h, const pic_pool_ln_spec* s, const void* x, const void* v, const double* cot, int mem_kind,
+                    void* g_x, void* g_v, double* g_params);
+
 int pic_sync(pic_handle* h);
 /* Number of particle positions found non-finite or out of range by the last sweeps (0 = healthy).  Counts the state's
  * particles only: the positions of pic_eval_field / pic_compute_E probes never add to it. */

@@ -104,6 +104,13 @@ class PicPoolSpec(C.Structure):
                 ("v_scale", C.c_double), ("params", C.c_void_p)]
 
 
+class PicPoolLnSpec(C.Structure):
+    """pic_pool_ln_spec (include/picstep.h): the layer with a LayerNorm; params (W, b, gamma, beta) is an address in
+    params_mem_kind memory; period 0 = the handle's L."""
+    _fields_ = [("hidden", C.c_int32), ("activation", C.c_int32), ("per_env", C.c_int32), ("params_mem_kind", C.c_int32),
+                ("v_scale", C.c_double), ("eps", C.c_double), ("period", C.c_double), ("params", C.c_void_p)]
+
+
 class PicError(RuntimeError):
     pass
 
@@ -198,6 +205,8 @@ SIGNATURES = {
     "pic_tape_tangent_policy": [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pic_pool": [_vp, C.POINTER(PicPoolSpec), _vp, _vp, C.c_int, _vp],
     "pic_pool_vjp": [_vp, C.POINTER(PicPoolSpec), _vp, _vp, _vp, C.c_int, _vp, _vp, _vp],
+    "pic_pool_ln": [_vp, C.POINTER(PicPoolLnSpec), _vp, _vp, C.c_int, _vp],
+    "pic_pool_ln_vjp": [_vp, C.POINTER(PicPoolLnSpec), _vp, _vp, _vp, C.c_int, _vp, _vp, _vp],
     "pic_sync": [_vp],
     "pic_bad_count": [_vp, _i64p],
     "pic_last_error": [_vp],
@@ -956,6 +965,16 @@ class Handle:
         """pic_pool_vjp on addresses (int, 0 = NULL) in mem_kind memory; spec: a PicPoolSpec."""
         p = _ptrs(x, v, cot, g_x, g_v, g_params)
         self._chk(self.lib.pic_pool_vjp(self._h, C.byref(spec), p[0], p[1], p[2], int(mem_kind), p[3], p[4], p[5]))
+
+    def pool_ln(self, spec, x, v, mem_kind, out):
+        """pic_pool_ln on addresses (int, 0 = NULL) in mem_kind memory; spec: a PicPoolLnSpec."""
+        p = _ptrs(x, v, out)
+        self._chk(self.lib.pic_pool_ln(self._h, C.byref(spec), p[0], p[1], int(mem_kind), p[2]))
+
+    def pool_ln_vjp(self, spec, x, v, cot, mem_kind, g_x, g_v, g_params):
+        """pic_pool_ln_vjp on addresses (int, 0 = NULL) in mem_kind memory; spec: a PicPoolLnSpec."""
+        p = _ptrs(x, v, cot, g_x, g_v, g_params)
+        self._chk(self.lib.pic_pool_ln_vjp(self._h, C.byref(spec), p[0], p[1], p[2], int(mem_kind), p[3], p[4], p[5]))
 
     # -- forward mode of the moments and their trace on a tape (DESIGN.md 7l) ---------------------------
     def moments_jvp(self, K, d_x, d_v, mem_kind, d_m):

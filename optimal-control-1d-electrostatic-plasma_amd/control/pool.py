@@ -2,6 +2,10 @@
 encoder on the particles themselves, phi(cos q, sin q, v) averaged over the particles, computed by the library without an
 [num_envs, N, H] tensor in either pass.  `pooled_features` is differentiable with respect to x, v, W and b (reverse mode only),
 so a policy built on it plugs into env.grad.rollout_policy(env, policy, T, observe="state") as any torch policy does.
+
+With gamma and beta the layer is Linear -> LayerNorm -> activation (pic_pool_ln, pic_pool_ln_vjp), differentiable
+in gamma and beta too.  `PoolEncoder.from_reference` and `ReferenceEncoder` load the state dict of a DeepSets particle encoder
+whose phi and rho are both Linear -> LayerNorm -> ReLU.
 """
 import torch
 
@@ -25,28 +29,97 @@ class _Pooled(torch.autograd.Function):
         return (None, g["g_x"], g["g_v"], g["g_W"] if need[3] else None, g["g_b"] if need[4] else None, None, None)
 
 
-def pooled_features(env, x, v, W, b, activation="tanh", v_scale=1.0):
+class _PooledLn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, env, x, v, W, b, gamma, beta, activation, v_scale, eps, period):
+        for name, t in (("x", x), ("v", v), ("W", W), ("b", b), ("gamma", gamma), ("beta", beta)):
+            if not (t.is_cuda and t.dtype == torch.float64):
+                raise ValueError(f"pooled_features: {name} must be a float64 CUDA tensor, not {t.dtype} on {t.device}")
+        ctx.env, ctx.kw = env, dict(activation=activation, v_scale=float(v_scale), eps=float(eps), period=period)
+        ctx.save_for_backward(x, v, W, b, gamma, beta)
+        return env.pool(W.detach(), b.detach(), x=x.detach(), v=v.detach(), on_device=True, gamma=gamma.detach(),
+                        beta=beta.detach(), **ctx.kw)
+
+    @staticmethod
+    def backward(ctx, cot):
+        x, v, W, b, gamma, beta = ctx.saved_tensors
+        need = ctx.needs_input_grad                     # (env, x, v, W, b, gamma, beta, ...)
+        g = ctx.env.pool_vjp(W, b, cot, x=x, v=v, on_device=True, g_x=need[1], g_v=need[2], g_params=any(need[3:7]), gamma=gamma,
+                             beta=beta, **ctx.kw)
+        grads = [g[k] if n else None for k, n in zip(("g_x", "g_v", "g_W", "g_b", "g_gamma", "g_beta"), need[1:7])]
+        return (None, *grads, None, None, None, None)
+
+
+def pooled_features(env, x, v, W, b, activation="tanh", v_scale=1.0, gamma=None, beta=None, eps=1e-5, period=None):
     """[num_envs, H]: out_k = mean_i act(b_k + W_k0 cos q_i + W_k1 sin q_i + W_k2 v_i v_scale), q = 2 pi x / L, of float64 CUDA
     tensors x, v [num_envs, N], W [H, 3] (or [num_envs, H, 3]) and b [H] (or [num_envs, H]) on `env` (a BatchedPIC), which
     supplies L, the stream and the working memory.  The backward is one pic_pool_vjp, which computes the gradients that are
-    needed and no others.  Forward mode is not built: torch raises its own error for a function without a jvp."""
-    return _Pooled.apply(env, x, v, W, b, activation, v_scale)
+    needed and no others.  Forward mode is not built: torch raises its own error for a function without a jvp.
+    With gamma and beta (shaped like b) a LayerNorm over the H units of each particle (eps) stands between the linear layer and
+    the activation, and q = 2 pi x / period (None: the environment's L); differentiable in gamma and beta too."""
+    if gamma is None and beta is None:
+        return _Pooled.apply(env, x, v, W, b, activation, v_scale)
+    if gamma is None or beta is None:
+        raise ValueError("pooled_features: gamma and beta must both be given or both be None")
+    return _PooledLn.apply(env, x, v, W, b, gamma, beta, activation, v_scale, eps, period)
 
 
 class PoolEncoder(torch.nn.Module):
     """phi and the mean of a DeepSets encoder as one module: holds W [H, 3] and b [H] (float64) and maps the (x, v) tuple that
-    rollout_policy(observe="state") hands a policy to the pooled features [num_envs, H]."""
+    rollout_policy(observe="state") hands a policy to the pooled features [num_envs, H].  With layernorm it also holds gamma
+    (ones) and beta (zeros) [H] of a LayerNorm(H, eps) between the linear layer and the activation; `period` (None: the
+    environment's L) is the period of the positions' features."""
 
-    def __init__(self, env, hidden, activation="tanh", v_scale=1.0, scale=0.5, generator=None):
+    def __init__(self, env, hidden, activation="tanh", v_scale=1.0, scale=0.5, generator=None, layernorm=False, eps=1e-5, period=None):
         super().__init__()
         if not 1 <= int(hidden) <= 256:
             raise ValueError(f"PoolEncoder: hidden must be 1..256, not {hidden}")
         dev = f"cuda:{env.device}"
         self.env, self.activation, self.v_scale = env, activation, float(v_scale)
+        self.eps, self.period = float(eps), period
         r = lambda *s: torch.randn(*s, generator=generator, dtype=torch.float64)
         self.W = torch.nn.Parameter((r(int(hidden), 3) * scale).to(dev))
         self.b = torch.nn.Parameter((r(int(hidden)) * 0.1).to(dev))
+        self.gamma = self.beta = None
+        if layernorm:
+            self.gamma = torch.nn.Parameter(torch.ones(int(hidden), dtype=torch.float64, device=dev))
+            self.beta = torch.nn.Parameter(torch.zeros(int(hidden), dtype=torch.float64, device=dev))
+
+    @classmethod
+    def from_reference(cls, env, state_dict, L_ref=50.0, x_norm=1.0, v_norm=1.0):
+        """The phi of a DeepSets particle encoder (Linear(3, H) -> LayerNorm(H) -> ReLU, period L_ref) from its state dict
+        (`phi.0.weight`, `phi.0.bias`, `phi.1.weight`, `phi.1.bias`: arrays or tensors, converted to float64), for positions
+        and velocities that the network is fed as x / x_norm and v / v_norm: period = L_ref x_norm, v_scale = 1 / v_norm."""
+        get = lambda k: torch.as_tensor(state_dict[k]).detach().to(torch.float64)
+        W = get("phi.0.weight")
+        enc = cls(env, W.shape[0], "relu", 1.0 / float(v_norm), layernorm=True, eps=1e-5, period=float(L_ref) * float(x_norm))
+        with torch.no_grad():
+            for p, k in ((enc.W, "phi.0.weight"), (enc.b, "phi.0.bias"), (enc.gamma, "phi.1.weight"), (enc.beta, "phi.1.bias")):
+                p.copy_(get(k))
+        return enc
 
     def forward(self, xv):
         x, v = xv
-        return pooled_features(self.env, x, v, self.W, self.b, self.activation, self.v_scale)
+        return pooled_features(self.env, x, v, self.W, self.b, self.activation, self.v_scale, self.gamma, self.beta, self.eps, self.period)
+
+
+class ReferenceEncoder(torch.nn.Module):
+    """A whole DeepSets particle encoder from its state dict: `PoolEncoder.from_reference` for phi and the mean, then rho =
+    Linear(H, H_out) -> LayerNorm(H_out) -> ReLU as float64 torch layers (`rho.0.*`, `rho.1.*`).  Maps the (x, v) of
+    rollout_policy(observe="state") to what the encoder returns for cat(x / x_norm, v / v_norm)."""
+
+    def __init__(self, env, state_dict, L_ref=50.0, x_norm=1.0, v_norm=1.0):
+        super().__init__()
+        self.phi = PoolEncoder.from_reference(env, state_dict, L_ref, x_norm, v_norm)
+        get = lambda k: torch.as_tensor(state_dict[k]).detach().to(torch.float64)
+        Wr = get("rho.0.weight")
+        lin, norm = torch.nn.Linear(Wr.shape[1], Wr.shape[0], dtype=torch.float64), torch.nn.LayerNorm(Wr.shape[0], eps=1e-5, dtype=torch.float64)
+        with torch.no_grad():
+            lin.weight.copy_(Wr)
+            lin.bias.copy_(get("rho.0.bias"))
+            norm.weight.copy_(get("rho.1.weight"))
+            norm.bias.copy_(get("rho.1.bias"))
+        self.rho = torch.nn.Sequential(lin, norm, torch.nn.ReLU()).to(self.phi.W.device)
+
+    def forward(self, xv):
+        return self.rho(self.phi(xv))

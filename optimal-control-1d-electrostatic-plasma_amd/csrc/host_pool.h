@@ -16,6 +16,7 @@ static const char* pool_spec_error(const pic_pool_spec* s) {
 }
 
 // One call's checks, block and kernel arguments.  `result`: out (pic_pool) or cot (pic_pool_vjp), which must not be NULL.
+// shape.ln: a call of pic_pool_ln* (below), whose parameters are 6H per vector and whose block is pool_ln_parts'.
 // Everything is refused before anything is enqueued; on PIC_OK the block is carved for `shape`, its sums are zero, the
 // parameters and the particles are on the device and `a`, `grid` are the passes'.
 static int pool_begin(pic_handle* h, const pic_pool_spec* s, const void* x, const void* v, const void* result, const char* result_name,
@@ -33,12 +34,14 @@ static int pool_begin(pic_handle* h, const pic_pool_spec* s, const void* x, cons
     if (h->sched.mid_stage) return fail(h, PIC_ESTATE, std::string(who) + ": a staged step is in progress");
   }
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  const size_t E = h->cfg.num_envs, N = h->cfg.N, H = (size_t)s->hidden, P = 4 * H;
+  const size_t E = h->cfg.num_envs, N = h->cfg.N, H = (size_t)s->hidden, P = (shape.ln ? 6 : 4) * H;
   shape.H = H; shape.N = N; shape.per_env = s->per_env != 0;
   shape.host = mem_kind == PIC_HOST; shape.params_host = s->params_mem_kind == PIC_HOST; shape.xv = x != nullptr;
   const size_t cap_before = h->pool_cap;      // (the block grows only: another capacity is another allocation)
   if (int rc = call_reserve(h, h->pool_block, &h->pool_cap, who, "the working memory", w,
-                            [&](Carver c, PoolViews& k) { return pool_parts(c, block_dims(h), shape, k); }))
+                            [&](Carver c, PoolViews& k) {
+                              return shape.ln ? pool_ln_parts(c, block_dims(h), shape, k) : pool_parts(c, block_dims(h), shape, k);
+                            }))
     return rc;
   const size_t accn = E * (shape.vjp ? P : H), zero = (size_t)((char*)(w.acc + accn) - (char*)w.max);
   if (h->pool_cap != cap_before || zero > h->pool_zero) {
@@ -123,4 +126,74 @@ int pic_pool_vjp(pic_handle* h, const pic_pool_spec* s, const void* x, const voi
   if (e == hipSuccess) e = device_result(h, g_v, g.g_v, E * N * sizeof(double));
   if (e == hipSuccess) e = device_result(h, g_params, gp, (s->per_env ? E : 1) * P * sizeof(double));
   return pool_end(h, e, host, who);
+}
+
+// ---------------------------------------------------------------------------------------------
+// ... with a LayerNorm inside the per-particle layer (pic_pool_ln, pic_pool_ln_vjp; pic_pool_ln.h)
+// ---------------------------------------------------------------------------------------------
+// pool_begin for a pic_pool_ln_spec: its own checks, then pic_pool's with the shared members; `n` are the LayerNorm's arguments
+static int pool_ln_begin(pic_handle* h, const pic_pool_ln_spec* s, const void* x, const void* v, const void* result,
+                         const char* result_name, int mem_kind, PoolCallShape shape, const char* who, PoolViews& w, PoolArgs& a,
+                         PoolLnArgs& n, dim3& grid) {
+  if (!h) return PIC_EINVAL;
+  if (!s) return fail(h, PIC_EINVAL, std::string(who) + ": spec is NULL");
+  const pic_pool_spec base{s->hidden, s->activation, s->per_env, s->params_mem_kind, s->v_scale, s->params};
+  if (const char* bad = pool_spec_error(&base)) return fail(h, PIC_EINVAL, std::string(who) + ": " + bad);
+  if (!(std::isfinite(s->eps) && s->eps > 0.0)) return fail(h, PIC_EINVAL, std::string(who) + ": eps must be finite and > 0");
+  if (!(std::isfinite(s->period) && s->period >= 0.0)) return fail(h, PIC_EINVAL, std::string(who) + ": period must be finite and >= 0");
+  shape.ln = true;
+  if (int rc = pool_begin(h, &base, x, v, result, result_name, mem_kind, shape, who, w, a, grid)) return rc;
+  if (s->period > 0.0) a.L = s->period;
+  n = PoolLnArgs{};
+  n.eps = s->eps; n.Hd = (double)a.H; n.sqrtH = std::sqrt(n.Hd);
+  return PIC_OK;
+}
+
+int pic_pool_ln(pic_handle* h, const pic_pool_ln_spec* s, const void* x, const void* v, int mem_kind, double* out) {
+  const char* who = "pic_pool_ln";
+  PoolViews w;
+  PoolArgs a;
+  PoolLnArgs n;
+  dim3 grid;
+  if (int rc = pool_ln_begin(h, s, x, v, out, "out", mem_kind, PoolCallShape{}, who, w, a, n, grid)) return rc;
+  double* dev = device_output(out, mem_kind, w.out);
+  hipLaunchKernelGGL(pool_max_kernel, grid, dim3(POOL_BLOCK), 0, h->stream, a);       // (u_max and the non-finite mark alone)
+  hipLaunchKernelGGL(pool_ln_kernel, grid, dim3(POOL_BLOCK), 0, h->stream, a, n);
+  hipLaunchKernelGGL(pool_ln_finish_kernel, dim3(h->cfg.num_envs), dim3(POOL_BLOCK), 0, h->stream, a, n, dev);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = device_result(h, out, dev, (size_t)h->cfg.num_envs * a.H * sizeof(double));
+  return pool_end(h, e, mem_kind == PIC_HOST, who);
+}
+
+int pic_pool_ln_vjp(pic_handle* h, const pic_pool_ln_spec* s, const void* x, const void* v, const double* cot, int mem_kind,
+                    void* g_x, void* g_v, double* g_params) {
+  const char* who = "pic_pool_ln_vjp";
+  PoolCallShape shape;
+  shape.vjp = true; shape.g_x = g_x != nullptr; shape.g_v = g_v != nullptr; shape.g_params = g_params != nullptr;
+  PoolViews w;
+  PoolArgs a;
+  PoolLnArgs n;
+  dim3 grid;
+  if (int rc = pool_ln_begin(h, s, x, v, cot, "cot", mem_kind, shape, who, w, a, n, grid)) return rc;
+  if (!g_x && !g_v && !g_params) return PIC_OK;
+  const size_t E = h->cfg.num_envs, N = h->cfg.N, P = 6 * (size_t)a.H;
+  PoolVjpArgs g{};
+  HIPCHK(h, device_input(h, cot, mem_kind, E * a.H * sizeof(double), w.cot, &n.cot));
+  n.rmax = w.max + E;
+  g.g_x = device_output(g_x, mem_kind, w.g_x);
+  g.g_v = device_output(g_v, mem_kind, w.g_v);
+  g.want_params = g_params != nullptr;
+  double* gE = w.gE ? w.gE : g_params;
+  double* gp = s->per_env ? gE : device_output(g_params, mem_kind, w.g);
+  hipLaunchKernelGGL(pool_ln_max_kernel, grid, dim3(POOL_BLOCK), 0, h->stream, a, n);
+  hipLaunchKernelGGL(pool_ln_vjp_kernel, grid, dim3(POOL_BLOCK), 0, h->stream, a, n, g);
+  hipLaunchKernelGGL(pool_ln_vjp_finish_kernel, dim3(E), dim3(POOL_BLOCK), 0, h->stream, a, n, g, gE);
+  if (g_params && !s->per_env)
+    hipLaunchKernelGGL(policy_grad_reduce_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->stream, (const double*)gE, gp,
+                       (long long)P, (int)E);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = device_result(h, g_x, g.g_x, E * N * sizeof(double));
+  if (e == hipSuccess) e = device_result(h, g_v, g.g_v, E * N * sizeof(double));
+  if (e == hipSuccess) e = device_result(h, g_params, gp, (s->per_env ? E : 1) * P * sizeof(double));
+  return pool_end(h, e, mem_kind == PIC_HOST, who);
 }

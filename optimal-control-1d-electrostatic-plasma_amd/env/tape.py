@@ -544,9 +544,10 @@ class TapePIC:
         self._h.moments_jvp(K, mem.addr(tx), mem.addr(tv), mem.kind, mem.addr(out))
         return out if batched else out[0]
 
-    # -- pooled particle features (pic_pool*) ---------------------------------------------
-    def _pool_call(self, who, W, b, activation, v_scale, x, v, on_device, cot=None):
-        """The memory, the spec and the arrays of one pool call; every shape is checked here, before the device is touched."""
+    # -- pooled particle features (pic_pool*; pic_pool_ln*, 7s) -----------------------------
+    def _pool_call(self, who, W, b, activation, v_scale, x, v, on_device, cot=None, gamma=None, beta=None, eps=1e-5, period=None):
+        """The memory, the spec and the arrays of one pool call; every shape is checked here, before the device is touched.
+        With gamma and beta the spec is pic_pool_ln's and the parameters are (W, b, gamma, beta)."""
         E, N = self.num_envs, self.N
         if activation not in _abi.ACTIVATIONS:
             raise ValueError(f"{who}: activation must be one of {sorted(_abi.ACTIVATIONS)}, not {activation!r}")
@@ -558,6 +559,17 @@ class TapePIC:
             raise ValueError(f"{who}: H must be 1..256, not {H}")
         if bs != ws[:-1]:
             raise ValueError(f"{who}: b must have shape {list(ws[:-1])}, not {list(bs)}")
+        ln = gamma is not None or beta is not None
+        if ln:
+            if gamma is None or beta is None:
+                raise ValueError(f"{who}: gamma and beta must both be given or both be None")
+            for name, a in (("gamma", gamma), ("beta", beta)):
+                if tuple(np.shape(a)) != bs:
+                    raise ValueError(f"{who}: {name} must have shape {list(bs)}, not {list(np.shape(a))}")
+            if not (np.isfinite(eps) and eps > 0):
+                raise ValueError(f"{who}: eps must be finite and > 0, not {eps!r}")
+            if period is not None and not (np.isfinite(period) and period >= 0):
+                raise ValueError(f"{who}: period must be finite and >= 0 (0 or None: the environment's L), not {period!r}")
         if (x is None) != (v is None):
             raise ValueError(f"{who}: x and v must both be given or both be None")
         for name, a in (("x", x), ("v", v)):
@@ -567,50 +579,69 @@ class TapePIC:
             raise ValueError(f"{who}: cot must be [num_envs, H] = {[E, H]}, not {list(np.shape(cot))}")
         if not np.isfinite(v_scale):
             raise ValueError(f"{who}: v_scale must be finite, not {v_scale!r}")
-        mem = Mem.of(self, W, b, x, v, cot, force_device=on_device)
+        mem = Mem.of(self, W, b, x, v, cot, gamma, beta, force_device=on_device)
         lead = (E,) if per_env else ()
+        parts = [mem.f64(W).reshape(lead + (3 * H,)), mem.f64(b)] + ([mem.f64(gamma), mem.f64(beta)] if ln else [])
         if mem.on_device:
             import torch
-            params = torch.cat([mem.f64(W).reshape(lead + (3 * H,)), mem.f64(b)], dim=-1).contiguous()
+            params = torch.cat(parts, dim=-1).contiguous()
         else:
-            params = np.ascontiguousarray(np.concatenate([mem.f64(W).reshape(lead + (3 * H,)), mem.f64(b)], axis=-1))
-        spec = _abi.PicPoolSpec(H, _abi.ACTIVATIONS[activation], int(per_env), mem.kind, float(v_scale), mem.addr(params))
+            params = np.ascontiguousarray(np.concatenate(parts, axis=-1))
+        if ln:
+            spec = _abi.PicPoolLnSpec(H, _abi.ACTIVATIONS[activation], int(per_env), mem.kind, float(v_scale), float(eps),
+                                      float(period or 0.0), mem.addr(params))
+        else:
+            spec = _abi.PicPoolSpec(H, _abi.ACTIVATIONS[activation], int(per_env), mem.kind, float(v_scale), mem.addr(params))
         return mem, spec, params, H, per_env, mem.f64(x), mem.f64(v)
 
-    def pool(self, W, b, activation: str = "tanh", v_scale: float = 1.0, x=None, v=None, on_device: bool = False):
+    def pool(self, W, b, activation: str = "tanh", v_scale: float = 1.0, x=None, v=None, on_device: bool = False,
+             gamma=None, beta=None, eps: float = 1e-5, period=None):
         """The pooled particle features [num_envs, H] (pic_pool): out_k = mean_i act(b_k + W_k0 cos q_i + W_k1 sin q_i +
         W_k2 v_i v_scale), q = 2 pi x / L -- a DeepSets encoder's per-particle layer and mean without an [N, H] array.  W [H, 3]
         and b [H], or [num_envs, H, 3] and [num_envs, H] for per-environment parameters; x, v [num_envs, N] (positions need not
         be wrapped), or None: the stored particles of a float64 environment.  Bitwise reproducible and independent of the order
-        of the particles.  NumPy, or float64 CUDA tensors if an input is one or with on_device.  The state is not touched."""
-        mem, spec, keep, H, _, x, v = self._pool_call("pool", W, b, activation, v_scale, x, v, on_device)
+        of the particles.  NumPy, or float64 CUDA tensors if an input is one or with on_device.  The state is not touched.
+        With gamma and beta (shaped like b) the layer is Linear -> LayerNorm(H; eps) -> act (pic_pool_ln): the
+        pre-activations of each particle are normalised over the H units, scaled by gamma and shifted by beta; period (None or
+        0: the environment's L) replaces L in q."""
+        mem, spec, keep, H, _, x, v = self._pool_call("pool", W, b, activation, v_scale, x, v, on_device, None, gamma, beta, eps, period)
         out = mem.empty((self.num_envs, H))
         mem.enter()
-        self._h.pool(spec, mem.addr(x), mem.addr(v), mem.kind, mem.addr(out))
+        call = self._h.pool_ln if gamma is not None else self._h.pool
+        call(spec, mem.addr(x), mem.addr(v), mem.kind, mem.addr(out))
         mem.leave(self._h)
         del keep
         return out
 
     def pool_vjp(self, W, b, cot, activation: str = "tanh", v_scale: float = 1.0, x=None, v=None, on_device: bool = False,
-                 g_x: bool = True, g_v: bool = True, g_params: bool = True):
+                 g_x: bool = True, g_v: bool = True, g_params: bool = True, gamma=None, beta=None, eps: float = 1e-5, period=None):
         """The vector-Jacobian product of `pool` for a cotangent cot [num_envs, H] (pic_pool_vjp) -> a dict: "g_x", "g_v"
         [num_envs, N], "g_W" and "g_b" shaped like W and b (shared parameters: summed over the environments in ascending
-        order).  An output that is switched off (g_x, g_v, g_params = False) is None and is not computed."""
+        order).  An output that is switched off (g_x, g_v, g_params = False) is None and is not computed.  With gamma and beta
+        (pic_pool_ln_vjp) the dict also holds "g_gamma" and "g_beta", shaped like b."""
         if cot is None:
             raise ValueError("pool_vjp: cot must be [num_envs, H], not None")
-        mem, spec, keep, H, per_env, x, v = self._pool_call("pool_vjp", W, b, activation, v_scale, x, v, on_device, cot)
+        mem, spec, keep, H, per_env, x, v = self._pool_call("pool_vjp", W, b, activation, v_scale, x, v, on_device, cot, gamma, beta,
+                                                            eps, period)
         E, N = self.num_envs, self.N
+        ln = gamma is not None
+        P = (6 if ln else 4) * H
         c = mem.f64(cot)
         gx = mem.empty((E, N)) if g_x else None
         gv = mem.empty((E, N)) if g_v else None
-        gp = mem.empty((E, 4 * H) if per_env else (4 * H,)) if g_params else None
+        gp = mem.empty((E, P) if per_env else (P,)) if g_params else None
         mem.enter()
-        self._h.pool_vjp(spec, mem.addr(x), mem.addr(v), mem.addr(c), mem.kind, mem.addr(gx), mem.addr(gv), mem.addr(gp))
+        call = self._h.pool_ln_vjp if ln else self._h.pool_vjp
+        call(spec, mem.addr(x), mem.addr(v), mem.addr(c), mem.kind, mem.addr(gx), mem.addr(gv), mem.addr(gp))
         mem.leave(self._h)
         del keep
         lead = (E,) if per_env else ()
-        return {"g_x": gx, "g_v": gv, "g_W": None if gp is None else gp[..., :3 * H].reshape(lead + (H, 3)),
-                "g_b": None if gp is None else gp[..., 3 * H:]}
+        g = {"g_x": gx, "g_v": gv, "g_W": None if gp is None else gp[..., :3 * H].reshape(lead + (H, 3)),
+             "g_b": None if gp is None else gp[..., 3 * H:4 * H]}
+        if ln:
+            g["g_gamma"] = None if gp is None else gp[..., 4 * H:5 * H]
+            g["g_beta"] = None if gp is None else gp[..., 5 * H:]
+        return g
 
     def _set_moments_cot(self, d_moments, T, mem):
         """The moments' cotangents of a backward onto the tape: d_moments [T, num_envs, 3, N_mesh] (row t on the state step t
