@@ -221,8 +221,8 @@ size_t moments_jvp_parts(Carver c, const BlockDims& d, int kc, Holder& j) {
   return c.at;
 }
 
-// ---- pooled particle features (host_pool.h) ------------------------------------------------------------------------
-// what a pic_pool / pic_pool_vjp call gives and wants, as far as its block depends on it
+// ---- pooled particle features (host_pool.h) --------------------------------------------------------------------
+// what a pic_pool / pic_pool_vjp / pic_pool_ln / pic_pool_ln_vjp call gives and wants, as far as its block depends on it
 struct PoolCallShape {
   size_t H = 0, N = 0;                // hidden units; particles per environment
   bool per_env = false;               // a parameter vector per environment
@@ -230,11 +230,12 @@ struct PoolCallShape {
   bool host = false, params_host = false;               // the call's arrays, its parameters: in host memory
   bool xv = false;                    // x and v are given (else the handle's particles)
   bool g_x = false, g_v = false, g_params = false;      // outputs wanted (vjp)
-  bool ln = false;                    // pic_pool_ln / pic_pool_ln_vjp: the block is pool_ln_parts'
+  bool ln = false;                    // pic_pool_ln / pic_pool_ln_vjp: P = 6H (W, b, gamma, beta), two max words in the VJP
 };
 
-// the handle's block: the max words [env] and the integer sums [env][H] or [env][4H] (both zero between calls), the VJP's
-// per-environment parameter sums and -- for what lives in host memory -- the device copies of the call's inputs and outputs
+// the handle's block: the max words [env] (the LayerNorm's VJP: r_max [env] behind them) and the integer sums [env][H] or
+// [env][P] (both zero between calls), the VJP's per-environment parameter sums and -- for what lives in host memory -- the
+// device copies of the call's inputs and outputs
 struct PoolViews {
   unsigned long long *max = nullptr, *acc = nullptr;
   double *gE = nullptr, *params = nullptr, *x = nullptr, *v = nullptr, *cot = nullptr, *out = nullptr, *g_x = nullptr,
@@ -242,29 +243,10 @@ struct PoolViews {
 };
 
 inline size_t pool_parts(Carver c, const BlockDims& d, const PoolCallShape& s, PoolViews& k) {
-  const size_t E = d.num_envs, P = 4 * s.H, rows = E * s.N;
-  c.take(k.max, E);
+  const size_t E = d.num_envs, P = (s.ln ? 6 : 4) * s.H, rows = E * s.N;
+  c.take(k.max, s.ln && s.vjp ? 2 * E : E);
   c.take(k.acc, E * (s.vjp ? P : s.H));
   // (shared parameters: the rows the reduction reads; per-environment ones in device memory are written where the caller wants them)
-  c.take(k.gE, s.vjp && s.g_params && (!s.per_env || s.host) ? E * P : 0);
-  c.take(k.params, s.params_host ? (s.per_env ? E : 1) * P : 0);
-  if (!s.host) return c.at;
-  c.take(k.x, s.xv ? rows : 0);
-  c.take(k.v, s.xv ? rows : 0);
-  c.take(k.cot, s.vjp ? E * s.H : 0);
-  c.take(k.out, s.vjp ? 0 : E * s.H);
-  c.take(k.g_x, s.g_x ? rows : 0);
-  c.take(k.g_v, s.g_v ? rows : 0);
-  c.take(k.g, s.g_params && !s.per_env ? P : 0);
-  return c.at;
-}
-
-// the same block for pic_pool_ln / pic_pool_ln_vjp: P = 6H (W, b, gamma, beta), the VJP has a second max word per
-// environment (r_max, behind the [env] words of u_max) and 6H sums; the other parts are pool_parts' with that P
-inline size_t pool_ln_parts(Carver c, const BlockDims& d, const PoolCallShape& s, PoolViews& k) {
-  const size_t E = d.num_envs, P = 6 * s.H, rows = E * s.N;
-  c.take(k.max, s.vjp ? 2 * E : E);
-  c.take(k.acc, E * (s.vjp ? P : s.H));
   c.take(k.gE, s.vjp && s.g_params && (!s.per_env || s.host) ? E * P : 0);
   c.take(k.params, s.params_host ? (s.per_env ? E : 1) * P : 0);
   if (!s.host) return c.at;

@@ -1,7 +1,9 @@
 // host_pool.h -- included by picstep.hip alone, inside its extern "C" block behind host_diff.h
 #pragma once
 // ---------------------------------------------------------------------------------------------
-// Pooled particle features (include/picstep.h: pic_pool, pic_pool_vjp; pic_pool.h)
+// Pooled particle features (include/picstep.h: pic_pool, pic_pool_vjp; pic_pool.h) and the same with a LayerNorm
+// inside the per-particle layer (pic_pool_ln, pic_pool_ln_vjp; pic_pool_ln.h): one begin, one forward and one VJP
+// for both layers; call.shape.ln picks the kernels
 // ---------------------------------------------------------------------------------------------
 // what is wrong with a spec (null: nothing)
 static const char* pool_spec_error(const pic_pool_spec* s) {
@@ -15,12 +17,21 @@ static const char* pool_spec_error(const pic_pool_spec* s) {
   return nullptr;
 }
 
-// One call's checks, block and kernel arguments.  `result`: out (pic_pool) or cot (pic_pool_vjp), which must not be NULL.
-// shape.ln: a call of pic_pool_ln* (below), whose parameters are 6H per vector and whose block is pool_ln_parts'.
-// Everything is refused before anything is enqueued; on PIC_OK the block is carved for `shape`, its sums are zero, the
-// parameters and the particles are on the device and `a`, `grid` are the passes'.
+// one call: what pool_begin makes of the arguments
+struct PoolCall {
+  PoolCallShape shape;
+  PoolViews w;
+  PoolArgs a;
+  PoolLnArgs n;              // (shape.ln)
+  dim3 grid;
+};
+
+// One call's checks, block and kernel arguments.  `result`: out (forward) or cot (VJP), which must not be NULL.  c.shape: vjp,
+// g_* and ln as the caller set them (ln: the parameters are 6H per vector); the rest is filled in here.
+// Everything is refused before anything is enqueued; on PIC_OK the block is carved for c.shape, its sums are zero, the
+// parameters and the particles are on the device and c.a, c.grid are the passes'.
 static int pool_begin(pic_handle* h, const pic_pool_spec* s, const void* x, const void* v, const void* result, const char* result_name,
-                      int mem_kind, PoolCallShape shape, const char* who, PoolViews& w, PoolArgs& a, dim3& grid) {
+                      int mem_kind, const char* who, PoolCall& c) {
   if (!h) return PIC_EINVAL;
   if (int rc = check_mem_kind(h, mem_kind, who)) return rc;
   if (const char* bad = pool_spec_error(s)) return fail(h, PIC_EINVAL, std::string(who) + ": " + bad);
@@ -34,14 +45,13 @@ static int pool_begin(pic_handle* h, const pic_pool_spec* s, const void* x, cons
     if (h->sched.mid_stage) return fail(h, PIC_ESTATE, std::string(who) + ": a staged step is in progress");
   }
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  PoolCallShape& shape = c.shape; PoolViews& w = c.w; PoolArgs& a = c.a;
   const size_t E = h->cfg.num_envs, N = h->cfg.N, H = (size_t)s->hidden, P = (shape.ln ? 6 : 4) * H;
   shape.H = H; shape.N = N; shape.per_env = s->per_env != 0;
   shape.host = mem_kind == PIC_HOST; shape.params_host = s->params_mem_kind == PIC_HOST; shape.xv = x != nullptr;
   const size_t cap_before = h->pool_cap;      // (the block grows only: another capacity is another allocation)
   if (int rc = call_reserve(h, h->pool_block, &h->pool_cap, who, "the working memory", w,
-                            [&](Carver c, PoolViews& k) {
-                              return shape.ln ? pool_ln_parts(c, block_dims(h), shape, k) : pool_parts(c, block_dims(h), shape, k);
-                            }))
+                            [&](Carver cv, PoolViews& k) { return pool_parts(cv, block_dims(h), shape, k); }))
     return rc;
   const size_t accn = E * (shape.vjp ? P : H), zero = (size_t)((char*)(w.acc + accn) - (char*)w.max);
   if (h->pool_cap != cap_before || zero > h->pool_zero) {
@@ -69,7 +79,25 @@ static int pool_begin(pic_handle* h, const pic_pool_spec* s, const void* x, cons
   static_assert(kPoolChunkTiles == (long long)POOL_BLOCK * kPoolTiles, "pool_plan's chunk is the kernels'");
   const PoolPlan plan = pool_plan(E, N);
   a.chunks_per_wg = plan.chunks_per_wg;
-  grid = dim3((unsigned)plan.workgroups, (unsigned)E);
+  c.grid = dim3((unsigned)plan.workgroups, (unsigned)E);
+  return PIC_OK;
+}
+
+// pool_begin for a pic_pool_ln_spec: its own checks, then pic_pool's with the shared members; c.n are the LayerNorm's arguments
+static int pool_ln_begin(pic_handle* h, const pic_pool_ln_spec* s, const void* x, const void* v, const void* result,
+                         const char* result_name, int mem_kind, const char* who, PoolCall& c) {
+  if (!h) return PIC_EINVAL;
+  if (!s) return fail(h, PIC_EINVAL, std::string(who) + ": spec is NULL");
+  const pic_pool_spec base{s->hidden, s->activation, s->per_env, s->params_mem_kind, s->v_scale, s->params};
+  if (const char* bad = pool_spec_error(&base)) return fail(h, PIC_EINVAL, std::string(who) + ": " + bad);
+  if (!(std::isfinite(s->eps) && s->eps > 0.0)) return fail(h, PIC_EINVAL, std::string(who) + ": eps must be finite and > 0");
+  if (!(std::isfinite(s->period) && s->period >= 0.0)) return fail(h, PIC_EINVAL, std::string(who) + ": period must be finite and >= 0");
+  c.shape.ln = true;
+  if (int rc = pool_begin(h, &base, x, v, result, result_name, mem_kind, who, c)) return rc;
+  if (s->period > 0.0) c.a.L = s->period;
+  c.n = PoolLnArgs{};
+  c.n.rmax = c.shape.vjp ? c.w.max + h->cfg.num_envs : nullptr;
+  c.n.eps = s->eps; c.n.Hd = (double)c.a.H; c.n.sqrtH = std::sqrt(c.n.Hd);
   return PIC_OK;
 }
 
@@ -80,33 +108,39 @@ static int pool_end(pic_handle* h, hipError_t e, bool wait, const char* who) {
   return rc;
 }
 
-int pic_pool(pic_handle* h, const pic_pool_spec* s, const void* x, const void* v, int mem_kind, double* out) {
-  const char* who = "pic_pool";
-  PoolViews w;
-  PoolArgs a;
-  dim3 grid;
-  if (int rc = pool_begin(h, s, x, v, out, "out", mem_kind, PoolCallShape{}, who, w, a, grid)) return rc;
-  double* dev = device_output(out, mem_kind, w.out);
-  hipLaunchKernelGGL(pool_max_kernel, grid, dim3(POOL_BLOCK), 0, h->stream, a);
-  hipLaunchKernelGGL(pool_kernel, grid, dim3(POOL_BLOCK), 0, h->stream, a);
-  hipLaunchKernelGGL(pool_finish_kernel, dim3(h->cfg.num_envs), dim3(POOL_BLOCK), 0, h->stream, a, dev);
+// the forward of a call that has begun: the max pass (u_max and the non-finite mark alone, for both layers), the pass, the finish
+static int pool_forward(pic_handle* h, const PoolCall& c, int mem_kind, double* out, const char* who) {
+  const PoolArgs& a = c.a;
+  const dim3 block(POOL_BLOCK), envs(h->cfg.num_envs);
+  double* dev = device_output(out, mem_kind, c.w.out);
+  hipLaunchKernelGGL(pool_max_kernel, c.grid, block, 0, h->stream, a);
+  if (c.shape.ln) {
+    hipLaunchKernelGGL(pool_ln_kernel, c.grid, block, 0, h->stream, a, c.n);
+    hipLaunchKernelGGL(pool_ln_finish_kernel, envs, block, 0, h->stream, a, c.n, dev);
+  } else {
+    hipLaunchKernelGGL(pool_kernel, c.grid, block, 0, h->stream, a);
+    hipLaunchKernelGGL(pool_finish_kernel, envs, block, 0, h->stream, a, dev);
+  }
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = device_result(h, out, dev, (size_t)h->cfg.num_envs * a.H * sizeof(double));
   return pool_end(h, e, mem_kind == PIC_HOST, who);        // device outputs stay stream-ordered
 }
 
-int pic_pool_vjp(pic_handle* h, const pic_pool_spec* s, const void* x, const void* v, const double* cot, int mem_kind, void* g_x,
-                 void* g_v, double* g_params) {
-  const char* who = "pic_pool_vjp";
+// the shape of a VJP call that wants these outputs
+static PoolCallShape pool_vjp_shape(const void* g_x, const void* g_v, const double* g_params) {
   PoolCallShape shape;
   shape.vjp = true; shape.g_x = g_x != nullptr; shape.g_v = g_v != nullptr; shape.g_params = g_params != nullptr;
-  PoolViews w;
-  PoolArgs a;
-  dim3 grid;
-  if (int rc = pool_begin(h, s, x, v, cot, "cot", mem_kind, shape, who, w, a, grid)) return rc;
+  return shape;
+}
+
+// the VJP of a call that has begun: the max pass (the LayerNorm's with r_max), the pass, the finish, the shared parameters' sum
+static int pool_backward(pic_handle* h, const PoolCall& c, const double* cot, int mem_kind, void* g_x, void* g_v, double* g_params,
+                         const char* who) {
   if (!g_x && !g_v && !g_params) return PIC_OK;
-  const size_t E = h->cfg.num_envs, N = h->cfg.N, P = 4 * (size_t)a.H;
-  const bool host = mem_kind == PIC_HOST;
+  const PoolArgs& a = c.a;
+  const PoolViews& w = c.w;
+  const size_t E = h->cfg.num_envs, N = h->cfg.N, P = (c.shape.ln ? 6 : 4) * (size_t)a.H;
+  const dim3 block(POOL_BLOCK), envs((unsigned)E);
   PoolVjpArgs g{};
   HIPCHK(h, device_input(h, cot, mem_kind, E * a.H * sizeof(double), w.cot, &g.cot));
   g.g_x = device_output(g_x, mem_kind, w.g_x);
@@ -114,86 +148,50 @@ int pic_pool_vjp(pic_handle* h, const pic_pool_spec* s, const void* x, const voi
   g.want_params = g_params != nullptr;
   // the per-environment sums go to the block (shared parameters, or host memory) or straight to the caller
   double* gE = w.gE ? w.gE : g_params;
-  double* gp = s->per_env ? gE : device_output(g_params, mem_kind, w.g);
-  hipLaunchKernelGGL(pool_max_kernel, grid, dim3(POOL_BLOCK), 0, h->stream, a);
-  hipLaunchKernelGGL(pool_vjp_kernel, grid, dim3(POOL_BLOCK), 0, h->stream, a, g);
-  hipLaunchKernelGGL(pool_vjp_finish_kernel, dim3(E), dim3(POOL_BLOCK), 0, h->stream, a, g, gE);
-  if (g_params && !s->per_env)
+  double* gp = c.shape.per_env ? gE : device_output(g_params, mem_kind, w.g);
+  if (c.shape.ln) {
+    hipLaunchKernelGGL(pool_ln_max_kernel, c.grid, block, 0, h->stream, a, c.n);
+    hipLaunchKernelGGL(pool_ln_vjp_kernel, c.grid, block, 0, h->stream, a, c.n, g);
+    hipLaunchKernelGGL(pool_ln_vjp_finish_kernel, envs, block, 0, h->stream, a, c.n, g, gE);
+  } else {
+    hipLaunchKernelGGL(pool_max_kernel, c.grid, block, 0, h->stream, a);
+    hipLaunchKernelGGL(pool_vjp_kernel, c.grid, block, 0, h->stream, a, g);
+    hipLaunchKernelGGL(pool_vjp_finish_kernel, envs, block, 0, h->stream, a, g, gE);
+  }
+  if (g_params && !c.shape.per_env)
     hipLaunchKernelGGL(policy_grad_reduce_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->stream, (const double*)gE, gp,
                        (long long)P, (int)E);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = device_result(h, g_x, g.g_x, E * N * sizeof(double));
   if (e == hipSuccess) e = device_result(h, g_v, g.g_v, E * N * sizeof(double));
-  if (e == hipSuccess) e = device_result(h, g_params, gp, (s->per_env ? E : 1) * P * sizeof(double));
-  return pool_end(h, e, host, who);
+  if (e == hipSuccess) e = device_result(h, g_params, gp, (c.shape.per_env ? E : 1) * P * sizeof(double));
+  return pool_end(h, e, mem_kind == PIC_HOST, who);
 }
 
-// ---------------------------------------------------------------------------------------------
-// ... with a LayerNorm inside the per-particle layer (pic_pool_ln, pic_pool_ln_vjp; pic_pool_ln.h)
-// ---------------------------------------------------------------------------------------------
-// pool_begin for a pic_pool_ln_spec: its own checks, then pic_pool's with the shared members; `n` are the LayerNorm's arguments
-static int pool_ln_begin(pic_handle* h, const pic_pool_ln_spec* s, const void* x, const void* v, const void* result,
-                         const char* result_name, int mem_kind, PoolCallShape shape, const char* who, PoolViews& w, PoolArgs& a,
-                         PoolLnArgs& n, dim3& grid) {
-  if (!h) return PIC_EINVAL;
-  if (!s) return fail(h, PIC_EINVAL, std::string(who) + ": spec is NULL");
-  const pic_pool_spec base{s->hidden, s->activation, s->per_env, s->params_mem_kind, s->v_scale, s->params};
-  if (const char* bad = pool_spec_error(&base)) return fail(h, PIC_EINVAL, std::string(who) + ": " + bad);
-  if (!(std::isfinite(s->eps) && s->eps > 0.0)) return fail(h, PIC_EINVAL, std::string(who) + ": eps must be finite and > 0");
-  if (!(std::isfinite(s->period) && s->period >= 0.0)) return fail(h, PIC_EINVAL, std::string(who) + ": period must be finite and >= 0");
-  shape.ln = true;
-  if (int rc = pool_begin(h, &base, x, v, result, result_name, mem_kind, shape, who, w, a, grid)) return rc;
-  if (s->period > 0.0) a.L = s->period;
-  n = PoolLnArgs{};
-  n.eps = s->eps; n.Hd = (double)a.H; n.sqrtH = std::sqrt(n.Hd);
-  return PIC_OK;
+int pic_pool(pic_handle* h, const pic_pool_spec* s, const void* x, const void* v, int mem_kind, double* out) {
+  PoolCall c;
+  if (int rc = pool_begin(h, s, x, v, out, "out", mem_kind, "pic_pool", c)) return rc;
+  return pool_forward(h, c, mem_kind, out, "pic_pool");
+}
+
+int pic_pool_vjp(pic_handle* h, const pic_pool_spec* s, const void* x, const void* v, const double* cot, int mem_kind, void* g_x,
+                 void* g_v, double* g_params) {
+  PoolCall c;
+  c.shape = pool_vjp_shape(g_x, g_v, g_params);
+  if (int rc = pool_begin(h, s, x, v, cot, "cot", mem_kind, "pic_pool_vjp", c)) return rc;
+  return pool_backward(h, c, cot, mem_kind, g_x, g_v, g_params, "pic_pool_vjp");
 }
 
 int pic_pool_ln(pic_handle* h, const pic_pool_ln_spec* s, const void* x, const void* v, int mem_kind, double* out) {
-  const char* who = "pic_pool_ln";
-  PoolViews w;
-  PoolArgs a;
-  PoolLnArgs n;
-  dim3 grid;
-  if (int rc = pool_ln_begin(h, s, x, v, out, "out", mem_kind, PoolCallShape{}, who, w, a, n, grid)) return rc;
-  double* dev = device_output(out, mem_kind, w.out);
-  hipLaunchKernelGGL(pool_max_kernel, grid, dim3(POOL_BLOCK), 0, h->stream, a);       // (u_max and the non-finite mark alone)
-  hipLaunchKernelGGL(pool_ln_kernel, grid, dim3(POOL_BLOCK), 0, h->stream, a, n);
-  hipLaunchKernelGGL(pool_ln_finish_kernel, dim3(h->cfg.num_envs), dim3(POOL_BLOCK), 0, h->stream, a, n, dev);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = device_result(h, out, dev, (size_t)h->cfg.num_envs * a.H * sizeof(double));
-  return pool_end(h, e, mem_kind == PIC_HOST, who);
+  PoolCall c;
+  if (int rc = pool_ln_begin(h, s, x, v, out, "out", mem_kind, "pic_pool_ln", c)) return rc;
+  return pool_forward(h, c, mem_kind, out, "pic_pool_ln");
 }
 
 int pic_pool_ln_vjp(pic_handle* h, const pic_pool_ln_spec* s, const void* x, const void* v, const double* cot, int mem_kind,
                     void* g_x, void* g_v, double* g_params) {
-  const char* who = "pic_pool_ln_vjp";
-  PoolCallShape shape;
-  shape.vjp = true; shape.g_x = g_x != nullptr; shape.g_v = g_v != nullptr; shape.g_params = g_params != nullptr;
-  PoolViews w;
-  PoolArgs a;
-  PoolLnArgs n;
-  dim3 grid;
-  if (int rc = pool_ln_begin(h, s, x, v, cot, "cot", mem_kind, shape, who, w, a, n, grid)) return rc;
-  if (!g_x && !g_v && !g_params) return PIC_OK;
-  const size_t E = h->cfg.num_envs, N = h->cfg.N, P = 6 * (size_t)a.H;
-  PoolVjpArgs g{};
-  HIPCHK(h, device_input(h, cot, mem_kind, E * a.H * sizeof(double), w.cot, &n.cot));
-  n.rmax = w.max + E;
-  g.g_x = device_output(g_x, mem_kind, w.g_x);
-  g.g_v = device_output(g_v, mem_kind, w.g_v);
-  g.want_params = g_params != nullptr;
-  double* gE = w.gE ? w.gE : g_params;
-  double* gp = s->per_env ? gE : device_output(g_params, mem_kind, w.g);
-  hipLaunchKernelGGL(pool_ln_max_kernel, grid, dim3(POOL_BLOCK), 0, h->stream, a, n);
-  hipLaunchKernelGGL(pool_ln_vjp_kernel, grid, dim3(POOL_BLOCK), 0, h->stream, a, n, g);
-  hipLaunchKernelGGL(pool_ln_vjp_finish_kernel, dim3(E), dim3(POOL_BLOCK), 0, h->stream, a, n, g, gE);
-  if (g_params && !s->per_env)
-    hipLaunchKernelGGL(policy_grad_reduce_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->stream, (const double*)gE, gp,
-                       (long long)P, (int)E);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = device_result(h, g_x, g.g_x, E * N * sizeof(double));
-  if (e == hipSuccess) e = device_result(h, g_v, g.g_v, E * N * sizeof(double));
-  if (e == hipSuccess) e = device_result(h, g_params, gp, (s->per_env ? E : 1) * P * sizeof(double));
-  return pool_end(h, e, mem_kind == PIC_HOST, who);
+  PoolCall c;
+  c.shape = pool_vjp_shape(g_x, g_v, g_params);
+  if (int rc = pool_ln_begin(h, s, x, v, cot, "cot", mem_kind, "pic_pool_ln_vjp", c)) return rc;
+  return pool_backward(h, c, cot, mem_kind, g_x, g_v, g_params, "pic_pool_ln_vjp");
 }

@@ -5,6 +5,8 @@
 // integer sums of terms rounded to nearest in a power-of-two unit that is known before the pass (pic_moments' pattern), so
 // nothing depends on the order of the particles, the grid or the batch.  Off the step path: the kernels read x, v and write
 // their own work block only.  Built with -ffp-contract=off: every product is rounded before its sum.
+// The passes are written once, as bodies over a layer type (below: "the skeleton"): PoolPlain here, PoolLn in pic_pool_ln.h.
+// A kernel is a body with its layer.
 #pragma once
 #include <climits>
 
@@ -23,9 +25,9 @@ constexpr double kTwoPi = 6.283185307179586;
 struct PoolArgs {
   const double* x;             // [env][ld] positions (not necessarily wrapped)
   const double* v;             // [env][ld]
-  const double* params;        // W [H][3] row-major, then b [H]
+  const double* params;        // W [H][3] row-major, then b [H] (pic_pool_ln: then gamma [H], beta [H])
   unsigned long long* umax;    // [env] bit pattern of max |u|, zero between calls
-  unsigned long long* acc;     // [env][H] (forward) or [env][4][H] (VJP) integer sums, zero between calls
+  unsigned long long* acc;     // [env][H] (forward) or [env][kSums][H] (VJP) integer sums, zero between calls
   long long env_params;        // doubles from one environment's parameters to the next (0: shared)
   long long N, ld;
   long long chunks_per_wg;     // chunks of POOL_BLOCK * kPoolTiles tiles per workgroup: a workgroup's range is contiguous
@@ -34,7 +36,16 @@ struct PoolArgs {
   int bitsN;                   // 2^bitsN >= N
 };
 
+struct PoolVjpArgs {
+  const double* cot;           // [env][H]
+  double* g_x;                 // [env][N] dense rows, overwritten; or null
+  double* g_v;                 // the same
+  int want_params;             // deposit the parameter sums into acc [env][kSums][H]
+};
+
 __device__ __forceinline__ bool pool_finite(double a) { return fabs(a) <= 1.7976931348623157e308; }
+__device__ __forceinline__ double pool_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
+__device__ __forceinline__ bool pool_on(int ue) { return ue != kPoolSkip && ue != kPoolNan; }      // a unit word that deposits
 
 // exponent of the unit of sums of N terms bounded by `bound`: 2^e >= bound, unit 2^(e + bitsN - 61) (two bits of headroom in an
 // int64: no overflow, whatever the data); kPoolSkip for a zero bound, kPoolNan for a non-finite one
@@ -42,22 +53,6 @@ __device__ __forceinline__ int pool_unit(double bound, int bitsN) {
   if (!pool_finite(bound)) return kPoolNan;
   if (!(bound > 0.0)) return kPoolSkip;
   return ilogb(bound) + 1 + bitsN - 61;
-}
-
-// the unit word of out_k: tanh is bounded by 1 = 2^0; relu by B_k = |W_k0| + |W_k1| + |W_k2| u_max + |b_k|, rounded up
-__device__ __forceinline__ int pool_fwd_unit(const double* __restrict__ p, int H, int k, int activation, double umx, int bitsN) {
-  const double w0 = p[3 * k], w1 = p[3 * k + 1], w2 = p[3 * k + 2], bk = p[3 * H + k];
-  if (!(pool_finite(w0) && pool_finite(w1) && pool_finite(w2) && pool_finite(bk))) return kPoolNan;
-  if (activation == PIC_ACT_TANH) return bitsN - 61;
-  const double B = ((fabs(w0) + fabs(w1)) + fabs(w2) * umx) + fabs(bk);
-  return pool_unit(B * 0x1.0000000000004p+0, bitsN);     // (1 + 2^-50: above the rounding of B and of z)
-}
-
-// the unit word of g_W_k*, g_b_k: every term is bounded by (|g_k| / N) max(1, u_max)
-__device__ __forceinline__ int pool_vjp_unit(const double* __restrict__ p, int H, int k, double gk, double umx, double Nd, int bitsN) {
-  const double w0 = p[3 * k], w1 = p[3 * k + 1], w2 = p[3 * k + 2], bk = p[3 * H + k];
-  if (!(pool_finite(w0) && pool_finite(w1) && pool_finite(w2) && pool_finite(bk))) return kPoolNan;
-  return pool_unit((fabs(gk) / Nd) * (umx > 1.0 ? umx : 1.0), bitsN);
 }
 
 // wave_incl_scan's DPP steps on 64-bit integers (a masked-off or absent source adds 0); all 64 lanes must be active
@@ -134,6 +129,78 @@ __device__ __forceinline__ double pool_pre(double w0, double w1, double w2, doub
   return z;
 }
 
+// the activation of the argument z
+__device__ __forceinline__ double pool_act(double z, bool is_tanh) { return is_tanh ? tanh(z) : (z > 0.0 ? z : 0.0); }
+
+// (cot_k act'(z)) / N of one term
+__device__ __forceinline__ double pool_dn(double z, double cot, double Nd, bool is_tanh) {
+  double act;
+  if (is_tanh) {
+    const double h = tanh(z);
+    act = 1.0 - h * h;
+  } else {
+    act = z > 0.0 ? 1.0 : 0.0;
+  }
+  return (cot * act) / Nd;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The plain layer (pic_pool, pic_pool_vjp).  What a layer type supplies to the skeleton below:
+//   kSums, kUnits          the VJP's parameter sums and unit words per hidden unit
+//   Row, row(k)            the parameters of unit k (the same for every lane: scalar loads)
+//   Stats, prepare()       what a lane's particles need before a walk over k
+//   arg()                  the activation's argument of particle j under unit k (and y_ik where there is one)
+//   env_bad()              whether the environment is NaN as a whole apart from its particles; the same in every thread
+//   fwd_unit()             the unit word of out_k
+//   vjp_env(), vjp_units(), vjp_unit()   the VJP's per-environment values, the unit words of unit k into LDS, that of sum m
+//   first_walk(), back()   what the VJP does before its walk, and d cost / d z_ik from (cot_k act') / N
+//   clear()                the layer's own max words of an environment, behind the finish
+// ---------------------------------------------------------------------------------------------
+struct PoolPlain {
+  static constexpr int kSums = 4, kUnits = 1;      // r c, r s, r u, r in one unit
+  struct Row { double w0, w1, w2, b; };
+  struct Stats {};
+  const double* __restrict__ p;
+  int H, activation, bitsN;
+
+  __device__ __forceinline__ PoolPlain(const PoolArgs& a, int env)
+      : p(a.params + (size_t)env * a.env_params), H(a.H), activation(a.activation), bitsN(a.bitsN) {}
+  __device__ __forceinline__ Row row(int k) const { return Row{p[3 * k], p[3 * k + 1], p[3 * k + 2], p[3 * H + k]}; }
+  __device__ __forceinline__ static bool row_finite(const Row& w) {
+    return pool_finite(w.w0) && pool_finite(w.w1) && pool_finite(w.w2) && pool_finite(w.b);
+  }
+  __device__ __forceinline__ bool env_bad(const double*, double) const { return false; }
+  __device__ __forceinline__ void prepare(const PoolLane&, Stats&) const {}
+  __device__ __forceinline__ double arg(const Row& w, const PoolLane& q, const Stats&, int j, double& y) const {
+    y = 0.0;
+    return pool_pre(w.w0, w.w1, w.w2, w.b, q.c[j], q.s[j], q.u[j]);
+  }
+  // tanh is bounded by 1 = 2^0; relu by B_k = |W_k0| + |W_k1| + |W_k2| u_max + |b_k|, rounded up
+  __device__ __forceinline__ int fwd_unit(int k, double umx) const {
+    const Row w = row(k);
+    if (!row_finite(w)) return kPoolNan;
+    if (activation == PIC_ACT_TANH) return bitsN - 61;
+    const double B = ((fabs(w.w0) + fabs(w.w1)) + fabs(w.w2) * umx) + fabs(w.b);
+    return pool_unit(B * 0x1.0000000000004p+0, bitsN);     // (1 + 2^-50: above the rounding of B and of z)
+  }
+  __device__ __forceinline__ void vjp_env(const double*, double, int) {}
+  // the unit word of g_W_k*, g_b_k (every m): every term is bounded by (|g_k| / N) max(1, u_max)
+  __device__ __forceinline__ int vjp_unit(int, int k, double gk, double umx, double Nd) const {
+    if (!row_finite(row(k))) return kPoolNan;
+    return pool_unit((fabs(gk) / Nd) * (umx > 1.0 ? umx : 1.0), bitsN);
+  }
+  __device__ __forceinline__ void vjp_units(int* unit, int k, double gk, double umx, double Nd, bool dep) const {
+    unit[k] = dep ? vjp_unit(0, k, gk, umx, Nd) : kPoolSkip;
+  }
+  __device__ __forceinline__ void first_walk(const PoolLane&, Stats&, const double*, double, bool, const int*,
+                                             unsigned long long*) const {}
+  __device__ __forceinline__ double back(const Row&, double dn, double, const Stats&, int) const { return dn; }
+  __device__ __forceinline__ void clear(int) const {}
+};
+
+// ---------------------------------------------------------------------------------------------
+// The skeleton: the four passes of either layer
+// ---------------------------------------------------------------------------------------------
 // Per-environment max |u| as the bit pattern of a non-negative double into umax[env] (zero before).  A non-finite u or q
 // saturates it at kMomInfBits: the finishing kernels then write NaN for that environment.  Grid: the passes'.
 __global__ __launch_bounds__(POOL_BLOCK) void pool_max_kernel(PoolArgs a) {
@@ -155,21 +222,23 @@ __global__ __launch_bounds__(POOL_BLOCK) void pool_max_kernel(PoolArgs a) {
 }
 
 // Forward pass: grid (workgroups per environment, environments).  LDS: the H unit words and H 64-bit sums.  Per chunk a lane
-// computes cos, sin and u of its particles once, then for every k its kPoolPerLane terms, rounded to integers; the wave's sum
-// (DPP) is one ds_add_u64 per wave and k.  The flush is one memory-side atomic per non-zero k into acc [env][H].
-__global__ __launch_bounds__(POOL_BLOCK) void pool_kernel(PoolArgs a) {
+// computes cos, sin and u of its particles once (and what the layer prepares from them), then for every k its kPoolPerLane
+// terms, rounded to integers; the wave's sum (DPP) is one ds_add_u64 per wave and k.  The flush is one memory-side atomic per
+// non-zero k into acc [env][H].
+template <typename Layer>
+__device__ __forceinline__ void pool_fwd_body(const PoolArgs& a, const Layer& layer) {
   __shared__ unsigned long long sums[kPoolMaxHidden];
   __shared__ int unit[kPoolMaxHidden];
   const int env = blockIdx.y, H = a.H, lane = threadIdx.x & 63;
   const unsigned long long mb = a.umax[env];
   if (mb >= kMomInfBits) return;                           // (uniform: the finishing kernel writes NaN)
-  const double* __restrict__ p = a.params + (size_t)env * a.env_params;
   const double* __restrict__ xe = a.x + (size_t)env * a.ld;
   const double* __restrict__ ve = a.v + (size_t)env * a.ld;
   const double umx = __longlong_as_double((long long)mb);
+  if (layer.env_bad(nullptr, umx)) return;                 // (uniform, the same)
   for (int k = threadIdx.x; k < H; k += POOL_BLOCK) {
     sums[k] = 0ull;
-    unit[k] = pool_fwd_unit(p, H, k, a.activation, umx, a.bitsN);
+    unit[k] = layer.fwd_unit(k, umx);
   }
   __syncthreads();
   long long t0, t1;
@@ -178,15 +247,17 @@ __global__ __launch_bounds__(POOL_BLOCK) void pool_kernel(PoolArgs a) {
   for (long long tc = t0; tc < t1; tc += (long long)POOL_BLOCK * kPoolTiles) {
     PoolLane q;
     pool_load(a, xe, ve, tc, t1, q);
+    typename Layer::Stats st;
+    layer.prepare(q, st);
     for (int k = 0; k < H; ++k) {
       const int ue = unit[k];
-      if (ue == kPoolSkip || ue == kPoolNan) continue;     // (uniform)
-      const double w0 = p[3 * k], w1 = p[3 * k + 1], w2 = p[3 * k + 2], bk = p[3 * H + k];
+      if (!pool_on(ue)) continue;                          // (uniform)
+      const typename Layer::Row w = layer.row(k);
       long long part = 0;
 #pragma unroll
       for (int j = 0; j < kPoolPerLane; ++j) {
-        const double z = pool_pre(w0, w1, w2, bk, q.c[j], q.s[j], q.u[j]);
-        const double h = is_tanh ? tanh(z) : (z > 0.0 ? z : 0.0);
+        double y;
+        const double h = pool_act(layer.arg(w, q, st, j, y), is_tanh);
         if (q.on[j]) part += __double2ll_rn(ldexp(h, -ue));
       }
       part = wave_sum_i64(part);
@@ -201,20 +272,20 @@ __global__ __launch_bounds__(POOL_BLOCK) void pool_kernel(PoolArgs a) {
 }
 
 // One workgroup per environment: the integer sums to out [env][H] = sum / N; +0 where nothing was deposited, NaN in the outputs
-// of a non-finite row of parameters and in every output of an environment with a non-finite particle; the accumulators and the
-// environment's max word are cleared behind the read.
-__global__ __launch_bounds__(POOL_BLOCK) void pool_finish_kernel(PoolArgs a, double* __restrict__ out) {
+// of a unit whose word is kPoolNan and in every output of an environment that is NaN as a whole (a non-finite particle, or the
+// layer's rule); the accumulators and the environment's max word are cleared behind the read.
+template <typename Layer>
+__device__ __forceinline__ void pool_finish_body(const PoolArgs& a, const Layer& layer, double* __restrict__ out) {
   const int env = blockIdx.x, H = a.H;
   const unsigned long long mb = a.umax[env];
   const bool finite = mb < kMomInfBits;
-  const double* __restrict__ p = a.params + (size_t)env * a.env_params;
-  const double umx = __longlong_as_double((long long)mb);
-  const double nan = __longlong_as_double(0x7FF8000000000000ll);
+  const double umx = finite ? __longlong_as_double((long long)mb) : 0.0;
+  const bool bad = layer.env_bad(nullptr, umx) || !finite;
   for (int k = threadIdx.x; k < H; k += POOL_BLOCK) {
     unsigned long long* s = a.acc + (size_t)env * H + k;
-    const int ue = finite ? pool_fwd_unit(p, H, k, a.activation, umx, a.bitsN) : kPoolNan;
+    const int ue = bad ? kPoolNan : layer.fwd_unit(k, umx);
     double r = 0.0;
-    if (ue == kPoolNan) r = nan;
+    if (ue == kPoolNan) r = pool_nan();
     else if (ue != kPoolSkip) r = ldexp((double)(long long)*s, ue) / (double)a.N;
     out[(size_t)env * H + k] = r;
     *s = 0ull;
@@ -223,64 +294,65 @@ __global__ __launch_bounds__(POOL_BLOCK) void pool_finish_kernel(PoolArgs a, dou
   if (threadIdx.x == 0) a.umax[env] = 0ull;
 }
 
-// ---------------------------------------------------------------------------------------------
-// The vector-Jacobian product for a cotangent g [env][H] (pic_pool_vjp)
-// ---------------------------------------------------------------------------------------------
-struct PoolVjpArgs {
-  const double* cot;           // [env][H]
-  double* g_x;                 // [env][N] dense rows, overwritten; or null
-  double* g_v;                 // the same
-  int want_params;             // deposit the 4H parameter sums into acc [env][4][H]
-};
-
-// The forward's pass with the activations recomputed: one thread owns a particle, so g_x_i and g_v_i are float64 sums over
-// ascending k; the parameter terms r c, r s, r u, r are rounded to integers in the unit of k and summed like the forward's.
-__global__ __launch_bounds__(POOL_BLOCK) void pool_vjp_kernel(PoolArgs a, PoolVjpArgs g) {
-  __shared__ unsigned long long sums[4 * kPoolMaxHidden];
-  __shared__ int unit[kPoolMaxHidden];
+// The vector-Jacobian product for a cotangent g.cot [env][H]: the forward's pass with the activations recomputed.  One thread
+// owns a particle, so g_x_i and g_v_i are float64 sums over ascending k; the parameter terms dz c, dz s, dz u, dz
+// (dz_ik = d cost / d z_ik: the layer's `back`) are rounded to integers in the unit of k and summed like the forward's.  What
+// the layer deposits besides is its `first_walk`'s.  An environment that is NaN as a whole gets NaN rows and deposits nothing:
+// the finishing kernel writes the parameters' NaN.  LDS: kSums H sums and kUnits H unit words.
+template <typename Layer>
+__device__ __forceinline__ void pool_vjp_body(const PoolArgs& a, const PoolVjpArgs& g, Layer& layer) {
+  __shared__ unsigned long long sums[Layer::kSums * kPoolMaxHidden];
+  __shared__ int unit[Layer::kUnits * kPoolMaxHidden];
   const int env = blockIdx.y, H = a.H, lane = threadIdx.x & 63;
   const unsigned long long mb = a.umax[env];
   const bool finite = mb < kMomInfBits;
-  const double* __restrict__ p = a.params + (size_t)env * a.env_params;
   const double* __restrict__ xe = a.x + (size_t)env * a.ld;
   const double* __restrict__ ve = a.v + (size_t)env * a.ld;
   const double* __restrict__ ge = g.cot + (size_t)env * H;
-  const double umx = __longlong_as_double((long long)mb), Nd = (double)a.N;
-  const double nan = __longlong_as_double(0x7FF8000000000000ll);
-  const bool dep = g.want_params && finite;
-  for (int k = threadIdx.x; k < H; k += POOL_BLOCK) {
-    sums[k] = sums[H + k] = sums[2 * H + k] = sums[3 * H + k] = 0ull;
-    unit[k] = dep ? pool_vjp_unit(p, H, k, ge[k], umx, Nd, a.bitsN) : kPoolSkip;
-  }
-  __syncthreads();
+  const double umx = finite ? __longlong_as_double((long long)mb) : 0.0, Nd = (double)a.N;
+  const bool bad = layer.env_bad(ge, umx) || !finite;
+  layer.vjp_env(ge, Nd, env);
   long long t0, t1;
   pool_range(a, t0, t1);
+  if (bad) {                                               // (uniform)
+    const long long i1 = 2 * t1 < a.N ? 2 * t1 : a.N;
+    for (long long i = 2 * t0 + threadIdx.x; i < i1; i += POOL_BLOCK) {
+      if (g.g_x) g.g_x[(size_t)env * a.N + i] = pool_nan();
+      if (g.g_v) g.g_v[(size_t)env * a.N + i] = pool_nan();
+    }
+    return;
+  }
+  const bool dep = g.want_params != 0;
+  for (int k = threadIdx.x; k < H; k += POOL_BLOCK) {
+#pragma unroll
+    for (int m = 0; m < Layer::kSums; ++m) sums[m * H + k] = 0ull;
+    layer.vjp_units(unit, k, ge[k], umx, Nd, dep);
+  }
+  __syncthreads();
   const bool is_tanh = a.activation == PIC_ACT_TANH;
   const double cx = kTwoPi / a.L;
   for (long long tc = t0; tc < t1; tc += (long long)POOL_BLOCK * kPoolTiles) {
     PoolLane q;
     pool_load(a, xe, ve, tc, t1, q);
+    typename Layer::Stats st;
+    layer.prepare(q, st);
+    layer.first_walk(q, st, ge, Nd, is_tanh, unit, sums);
     double sx[kPoolPerLane], sv[kPoolPerLane];
 #pragma unroll
     for (int j = 0; j < kPoolPerLane; ++j) sx[j] = sv[j] = 0.0;
     for (int k = 0; k < H; ++k) {
       const int ue = unit[k];
-      const bool on = ue != kPoolSkip && ue != kPoolNan;   // (uniform)
-      const double w0 = p[3 * k], w1 = p[3 * k + 1], w2 = p[3 * k + 2], bk = p[3 * H + k], gk = ge[k];
+      const bool on = pool_on(ue);                         // (uniform)
+      const typename Layer::Row w = layer.row(k);
+      const double gk = ge[k];
       long long pc = 0, ps = 0, pu = 0, pr = 0;
 #pragma unroll
       for (int j = 0; j < kPoolPerLane; ++j) {
-        const double z = pool_pre(w0, w1, w2, bk, q.c[j], q.s[j], q.u[j]);
-        double act;
-        if (is_tanh) {
-          const double h = tanh(z);
-          act = 1.0 - h * h;
-        } else {
-          act = z > 0.0 ? 1.0 : 0.0;
-        }
-        const double r = (gk * act) / Nd;
-        sx[j] = sx[j] + r * (w1 * q.c[j] - w0 * q.s[j]);
-        sv[j] = sv[j] + r * w2;
+        double y;
+        const double z = layer.arg(w, q, st, j, y);
+        const double r = layer.back(w, pool_dn(z, gk, Nd, is_tanh), y, st, j);
+        sx[j] = sx[j] + r * (w.w1 * q.c[j] - w.w0 * q.s[j]);
+        sv[j] = sv[j] + r * w.w2;
         if (on && q.on[j]) {
           pc += __double2ll_rn(ldexp(r * q.c[j], -ue));
           ps += __double2ll_rn(ldexp(r * q.s[j], -ue));
@@ -306,43 +378,63 @@ __global__ __launch_bounds__(POOL_BLOCK) void pool_vjp_kernel(PoolArgs a, PoolVj
       if (!q.on[j]) continue;
       const long long i = 2 * (tc + (long long)(j >> 1) * POOL_BLOCK + threadIdx.x) + (j & 1);
       const size_t o = (size_t)env * a.N + i;
-      if (g.g_x) g.g_x[o] = finite ? cx * sx[j] : nan;
-      if (g.g_v) g.g_v[o] = finite ? a.v_scale * sv[j] : nan;
+      if (g.g_x) g.g_x[o] = cx * sx[j];
+      if (g.g_v) g.g_v[o] = a.v_scale * sv[j];
     }
   }
   __syncthreads();
   if (!dep) return;
-  for (int c = threadIdx.x; c < 4 * H; c += POOL_BLOCK) {
+  for (int c = threadIdx.x; c < Layer::kSums * H; c += POOL_BLOCK) {
     const unsigned long long s = sums[c];
-    if (s) atomicAdd(a.acc + (size_t)env * 4 * H + c, s);
+    if (s) atomicAdd(a.acc + (size_t)env * Layer::kSums * H + c, s);
   }
 }
 
-// One workgroup per environment: the 4H integer sums to gE [env][4H] in the parameters' order (g_W [H][3], then g_b [H]); +0
-// for a zero cotangent, NaN for a non-finite cotangent or row of parameters and for an environment with a non-finite particle;
-// the accumulators and the max word are cleared behind the read.
-__global__ __launch_bounds__(POOL_BLOCK) void pool_vjp_finish_kernel(PoolArgs a, PoolVjpArgs g, double* __restrict__ gE) {
-  const int env = blockIdx.x, H = a.H;
+// One workgroup per environment: the kSums H integer sums to gE [env][kSums H] in the parameters' order (g_W [H][3], then [H]
+// each); +0 where the bound is zero, NaN for a non-finite bound and for an environment that is NaN as a whole; the accumulators
+// and the max words are cleared behind the read.
+template <typename Layer>
+__device__ __forceinline__ void pool_vjp_finish_body(const PoolArgs& a, const PoolVjpArgs& g, Layer& layer, double* __restrict__ gE) {
+  const int env = blockIdx.x, H = a.H, P = Layer::kSums * H;
   const unsigned long long mb = a.umax[env];
   const bool finite = mb < kMomInfBits;
-  const double* __restrict__ p = a.params + (size_t)env * a.env_params;
   const double* __restrict__ ge = g.cot + (size_t)env * H;
-  const double umx = __longlong_as_double((long long)mb);
-  const double nan = __longlong_as_double(0x7FF8000000000000ll);
+  const double umx = finite ? __longlong_as_double((long long)mb) : 0.0, Nd = (double)a.N;
+  const bool bad = layer.env_bad(ge, umx) || !finite;
+  layer.vjp_env(ge, Nd, env);
   if (g.want_params) {
-    for (int c = threadIdx.x; c < 4 * H; c += POOL_BLOCK) {
+    for (int c = threadIdx.x; c < P; c += POOL_BLOCK) {
       const int m = c / H, k = c - m * H;
-      unsigned long long* s = a.acc + (size_t)env * 4 * H + c;
-      const int ue = finite ? pool_vjp_unit(p, H, k, ge[k], umx, (double)a.N, a.bitsN) : kPoolNan;
+      unsigned long long* s = a.acc + (size_t)env * P + c;
+      const int ue = bad ? kPoolNan : layer.vjp_unit(m, k, ge[k], umx, Nd);
       double r = 0.0;
-      if (ue == kPoolNan) r = nan;
+      if (ue == kPoolNan) r = pool_nan();
       else if (ue != kPoolSkip) r = ldexp((double)(long long)*s, ue);
-      gE[(size_t)env * 4 * H + (m < 3 ? 3 * k + m : 3 * H + k)] = r;
+      gE[(size_t)env * P + (m < 3 ? 3 * k + m : m * H + k)] = r;
       *s = 0ull;
     }
   }
-  __syncthreads();                                         // (every lane has read the max word)
-  if (threadIdx.x == 0) a.umax[env] = 0ull;
+  __syncthreads();                                         // (every lane has read the max words)
+  if (threadIdx.x == 0) {
+    a.umax[env] = 0ull;
+    layer.clear(env);
+  }
+}
+
+__global__ __launch_bounds__(POOL_BLOCK) void pool_kernel(PoolArgs a) { pool_fwd_body(a, PoolPlain(a, blockIdx.y)); }
+
+__global__ __launch_bounds__(POOL_BLOCK) void pool_finish_kernel(PoolArgs a, double* __restrict__ out) {
+  pool_finish_body(a, PoolPlain(a, blockIdx.x), out);
+}
+
+__global__ __launch_bounds__(POOL_BLOCK) void pool_vjp_kernel(PoolArgs a, PoolVjpArgs g) {
+  PoolPlain layer(a, blockIdx.y);
+  pool_vjp_body(a, g, layer);
+}
+
+__global__ __launch_bounds__(POOL_BLOCK) void pool_vjp_finish_kernel(PoolArgs a, PoolVjpArgs g, double* __restrict__ gE) {
+  PoolPlain layer(a, blockIdx.x);
+  pool_vjp_finish_body(a, g, layer, gE);
 }
 
 }  // namespace

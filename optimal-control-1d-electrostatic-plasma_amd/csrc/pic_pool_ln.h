@@ -1,11 +1,10 @@
 // pic_pool_ln.h -- pooled particle features with a LayerNorm inside the per-particle layer (include/picstep.h: pic_pool_ln,
 // pic_pool_ln_vjp): per environment
 //   out_k = (1/N) sum_i act(gamma_k y_ik + beta_k),   y_ik = (z_ik - mu_i) r_i,   r_i = 1 / sqrt(var_i + eps)
-// with pic_pool's z_ik and mu_i, var_i the mean and the biased variance of z_i. over the H units.  The passes are pic_pool.h's: a
-// lane holds kPoolPerLane particles (cos, sin, u) in registers and walks the H rows of the parameters, which are wave-uniform
-// loads; z is three multiply-adds and is recomputed in every walk, so nothing of size [H] is kept per particle.  New are the
-// walks before the terms: sum z, then sum d^2 (forward, and the VJP's max pass: r_max), and in the VJP one more for m1 and m2.
-// The sums over particles are pic_pool's 64-bit integer sums in units known before the pass.  -ffp-contract=off.
+// with pic_pool's z_ik and mu_i, var_i the mean and the biased variance of z_i. over the H units.  The passes are pic_pool.h's
+// skeleton with the layer type PoolLn: this file holds only what is the LayerNorm's.  z is three multiply-adds and is recomputed
+// in every walk, so nothing of size [H] is kept per particle.  New are the walks before the terms: sum z, then sum d^2 (forward,
+// and the VJP's max pass: r_max), and in the VJP one more for m1 and m2.  -ffp-contract=off.
 #pragma once
 #include "pic_pool.h"
 
@@ -17,7 +16,6 @@ constexpr double kLnOverflow = 0x1p+500;               // a bound of |z| above t
 
 struct PoolLnArgs {
   unsigned long long* rmax;    // [env] bit pattern of max r (VJP; zero between calls), or null
-  const double* cot;           // [env][H] (VJP), or null
   double eps, Hd, sqrtH;       // Hd = (double)H, sqrtH = sqrt(Hd)
 };
 
@@ -85,78 +83,110 @@ __device__ __forceinline__ int ln_fwd_unit(const LnRow& w, int activation, doubl
   return pool_unit((fabs(w.g) * sqrtH + fabs(w.be)) * kLnFwdUp, bitsN);
 }
 
-// Forward pass: pool_kernel's grid and LDS.  Per chunk a lane computes cos, sin, u of its particles once, then mu and r (two
-// walks over k), then for every k its kPoolPerLane terms, rounded to integers.
-__global__ __launch_bounds__(POOL_BLOCK) void pool_ln_kernel(PoolArgs a, PoolLnArgs n) {
-  __shared__ unsigned long long sums[kPoolMaxHidden];
-  __shared__ int unit[kPoolMaxHidden];
-  const int env = blockIdx.y, H = a.H, lane = threadIdx.x & 63;
-  const unsigned long long mb = a.umax[env];
-  if (mb >= kMomInfBits) return;                           // (uniform: the finishing kernel writes NaN)
-  const double* __restrict__ p = a.params + (size_t)env * a.env_params;
-  const double* __restrict__ xe = a.x + (size_t)env * a.ld;
-  const double* __restrict__ ve = a.v + (size_t)env * a.ld;
-  if (ln_env_bad(p, nullptr, H, __longlong_as_double((long long)mb))) return;
-  for (int k = threadIdx.x; k < H; k += POOL_BLOCK) {
-    sums[k] = 0ull;
-    unit[k] = ln_fwd_unit(ln_row(p, H, k), a.activation, n.sqrtH, a.bitsN);
-  }
+// the units of the six parameter sums of unit k, given D_max = max_k |cot_k| |gamma_k| / N
+struct LnVjpUnits { int w, g, b; };
+
+__device__ __forceinline__ LnVjpUnits ln_vjp_units(double gamma, double cot, double dmax, double rmx, double umx, double Nd,
+                                                   double sqrtH, int bitsN) {
+  const double ck = fabs(cot) / Nd, dk = (fabs(cot) * fabs(gamma)) / Nd;
+  const double bw = (((dk + (1.0 + sqrtH) * dmax) * rmx) * (umx > 1.0 ? umx : 1.0)) * kLnVjpUp;
+  return LnVjpUnits{pool_unit(bw, bitsN), pool_unit((ck * sqrtH) * kLnVjpUp, bitsN), pool_unit(ck * kLnVjpUp, bitsN)};
+}
+
+// D_max of the environment through an LDS word: the same value in every thread of the workgroup (two barriers)
+__device__ __forceinline__ double ln_dmax(const double* __restrict__ p, const double* __restrict__ cot, int H, double Nd) {
+  __shared__ unsigned long long word;
+  if (threadIdx.x == 0) word = 0ull;
   __syncthreads();
-  long long t0, t1;
-  pool_range(a, t0, t1);
-  const bool is_tanh = a.activation == PIC_ACT_TANH;
-  for (long long tc = t0; tc < t1; tc += (long long)POOL_BLOCK * kPoolTiles) {
-    PoolLane q;
-    pool_load(a, xe, ve, tc, t1, q);
-    double mu[kPoolPerLane], r[kPoolPerLane];
-    ln_stats(p, H, n, q, mu, r);
+  unsigned long long m = 0ull;
+  for (int k = threadIdx.x; k < H; k += POOL_BLOCK) mom_max_bits(m, (fabs(cot[k]) * fabs(p[4 * H + k])) / Nd);
+  if (m) atomicMax(&word, m);
+  __syncthreads();
+  return __longlong_as_double((long long)word);
+}
+
+// The LayerNorm's layer type for pic_pool.h's skeleton (what a layer supplies: there).  The VJP has six sums per unit (g_W_k*
+// and g_b_k in one unit word, g_gamma_k and g_beta_k in one each) and walks k once more before the skeleton's walk.
+struct PoolLn {
+  static constexpr int kSums = 6, kUnits = 3;
+  using Row = LnRow;
+  struct Stats { double mu[kPoolPerLane], r[kPoolPerLane], m1[kPoolPerLane], m2[kPoolPerLane]; };      // (m1, m2: the VJP's)
+  const double* __restrict__ p;
+  PoolLnArgs n;
+  int H, activation, bitsN;
+  double rmx = 0.0, dmax = 0.0;      // the environment's largest r_i and D_max (vjp_env)
+
+  __device__ __forceinline__ PoolLn(const PoolArgs& a, const PoolLnArgs& n_, int env)
+      : p(a.params + (size_t)env * a.env_params), n(n_), H(a.H), activation(a.activation), bitsN(a.bitsN) {}
+  __device__ __forceinline__ Row row(int k) const { return ln_row(p, H, k); }
+  __device__ __forceinline__ bool env_bad(const double* cot, double umx) const { return ln_env_bad(p, cot, H, umx); }
+  __device__ __forceinline__ void prepare(const PoolLane& q, Stats& st) const { ln_stats(p, H, n, q, st.mu, st.r); }
+  __device__ __forceinline__ double arg(const Row& w, const PoolLane& q, const Stats& st, int j, double& y) const {
+    return ln_norm(w, q.c[j], q.s[j], q.u[j], st.mu[j], st.r[j], y);
+  }
+  __device__ __forceinline__ int fwd_unit(int k, double) const { return ln_fwd_unit(row(k), activation, n.sqrtH, bitsN); }
+  __device__ __forceinline__ void vjp_env(const double* ge, double Nd, int env) {
+    rmx = __longlong_as_double((long long)n.rmax[env]);
+    dmax = ln_dmax(p, ge, H, Nd);
+  }
+  __device__ __forceinline__ LnVjpUnits units(int k, double gk, double umx, double Nd) const {
+    return ln_vjp_units(p[4 * H + k], gk, dmax, rmx, umx, Nd, n.sqrtH, bitsN);
+  }
+  __device__ __forceinline__ int vjp_unit(int m, int k, double gk, double umx, double Nd) const {
+    const LnVjpUnits us = units(k, gk, umx, Nd);
+    return m < 4 ? us.w : (m == 4 ? us.g : us.b);
+  }
+  __device__ __forceinline__ void vjp_units(int* unit, int k, double gk, double umx, double Nd, bool dep) const {
+    const LnVjpUnits ue = units(k, gk, umx, Nd);
+    unit[k] = dep ? ue.w : kPoolSkip;
+    unit[H + k] = dep ? ue.g : kPoolSkip;
+    unit[2 * H + k] = dep ? ue.b : kPoolSkip;
+  }
+  // the walk over k behind mu and r: m1_i and m2_i, and the deposits of g_gamma, g_beta
+  __device__ __forceinline__ void first_walk(const PoolLane& q, Stats& st, const double* __restrict__ ge, double Nd, bool is_tanh,
+                                             const int* unit, unsigned long long* sums) const {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int j = 0; j < kPoolPerLane; ++j) st.m1[j] = st.m2[j] = 0.0;
     for (int k = 0; k < H; ++k) {
-      const int ue = unit[k];
-      if (ue == kPoolSkip || ue == kPoolNan) continue;     // (uniform)
+      const int ug = unit[H + k], ub = unit[2 * H + k];
+      const bool ong = pool_on(ug), onb = pool_on(ub);     // (uniform)
       const LnRow w = ln_row(p, H, k);
-      long long part = 0;
+      const double ck = ge[k];
+      long long pg = 0, pb = 0;
 #pragma unroll
       for (int j = 0; j < kPoolPerLane; ++j) {
         double y;
-        const double nn = ln_norm(w, q.c[j], q.s[j], q.u[j], mu[j], r[j], y);
-        const double h = is_tanh ? tanh(nn) : (nn > 0.0 ? nn : 0.0);
-        if (q.on[j]) part += __double2ll_rn(ldexp(h, -ue));
+        const double nn = ln_norm(w, q.c[j], q.s[j], q.u[j], st.mu[j], st.r[j], y);
+        const double dn = pool_dn(nn, ck, Nd, is_tanh), dy = dn * w.g;
+        st.m1[j] = st.m1[j] + dy;
+        st.m2[j] = st.m2[j] + dy * y;
+        if (ong && q.on[j]) pg += __double2ll_rn(ldexp(dn * y, -ug));
+        if (onb && q.on[j]) pb += __double2ll_rn(ldexp(dn, -ub));
       }
-      part = wave_sum_i64(part);
-      if (lane == 0 && part) atomicAdd(sums + k, (unsigned long long)part);
+      if (ong) {
+        pg = wave_sum_i64(pg);
+        if (lane == 0 && pg) atomicAdd(sums + 4 * H + k, (unsigned long long)pg);
+      }
+      if (onb) {
+        pb = wave_sum_i64(pb);
+        if (lane == 0 && pb) atomicAdd(sums + 5 * H + k, (unsigned long long)pb);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kPoolPerLane; ++j) {
+      st.m1[j] = st.m1[j] / n.Hd;
+      st.m2[j] = st.m2[j] / n.Hd;
     }
   }
-  __syncthreads();
-  for (int k = threadIdx.x; k < H; k += POOL_BLOCK) {
-    const unsigned long long s = sums[k];
-    if (s) atomicAdd(a.acc + (size_t)env * H + k, s);
+  // dz_ik from dn_ik = (cot_k a_ik) / N
+  __device__ __forceinline__ double back(const Row& w, double dn, double y, const Stats& st, int j) const {
+    const double dy = dn * w.g;
+    return ((dy - st.m1[j]) - y * st.m2[j]) * st.r[j];
   }
-}
+  __device__ __forceinline__ void clear(int env) const { n.rmax[env] = 0ull; }
+};
 
-// One workgroup per environment: pool_finish_kernel with the LayerNorm's units and NaN rule.
-__global__ __launch_bounds__(POOL_BLOCK) void pool_ln_finish_kernel(PoolArgs a, PoolLnArgs n, double* __restrict__ out) {
-  const int env = blockIdx.x, H = a.H;
-  const unsigned long long mb = a.umax[env];
-  const bool finite = mb < kMomInfBits;
-  const double* __restrict__ p = a.params + (size_t)env * a.env_params;
-  const bool bad = ln_env_bad(p, nullptr, H, finite ? __longlong_as_double((long long)mb) : 0.0) || !finite;
-  const double nan = __longlong_as_double(0x7FF8000000000000ll);
-  for (int k = threadIdx.x; k < H; k += POOL_BLOCK) {
-    unsigned long long* s = a.acc + (size_t)env * H + k;
-    const int ue = bad ? kPoolNan : ln_fwd_unit(ln_row(p, H, k), a.activation, n.sqrtH, a.bitsN);
-    double r = 0.0;
-    if (ue == kPoolNan) r = nan;
-    else if (ue != kPoolSkip) r = ldexp((double)(long long)*s, ue) / (double)a.N;
-    out[(size_t)env * H + k] = r;
-    *s = 0ull;
-  }
-  __syncthreads();                                         // (every lane has read the max word)
-  if (threadIdx.x == 0) a.umax[env] = 0ull;
-}
-
-// ---------------------------------------------------------------------------------------------
-// The vector-Jacobian product for a cotangent cot [env][H] (pic_pool_ln_vjp)
-// ---------------------------------------------------------------------------------------------
 // The VJP's max pass: pool_max_kernel's word (max |u|, saturated by a non-finite u or q) and next to it the environment's largest
 // r_i in rmax[env].  It walks k twice per particle.  Grid: the passes'.
 __global__ __launch_bounds__(POOL_BLOCK) void pool_ln_max_kernel(PoolArgs a, PoolLnArgs n) {
@@ -184,201 +214,20 @@ __global__ __launch_bounds__(POOL_BLOCK) void pool_ln_max_kernel(PoolArgs a, Poo
   block_max_to(__longlong_as_double((long long)rb), n.rmax + env);
 }
 
-// the units of the six parameter sums of unit k, given D_max = max_k |cot_k| |gamma_k| / N
-struct LnVjpUnits { int w, g, b; };
+__global__ __launch_bounds__(POOL_BLOCK) void pool_ln_kernel(PoolArgs a, PoolLnArgs n) { pool_fwd_body(a, PoolLn(a, n, blockIdx.y)); }
 
-__device__ __forceinline__ LnVjpUnits ln_vjp_units(double gamma, double cot, double dmax, double rmx, double umx, double Nd,
-                                                   double sqrtH, int bitsN) {
-  const double ck = fabs(cot) / Nd, dk = (fabs(cot) * fabs(gamma)) / Nd;
-  const double bw = (((dk + (1.0 + sqrtH) * dmax) * rmx) * (umx > 1.0 ? umx : 1.0)) * kLnVjpUp;
-  return LnVjpUnits{pool_unit(bw, bitsN), pool_unit((ck * sqrtH) * kLnVjpUp, bitsN), pool_unit(ck * kLnVjpUp, bitsN)};
+__global__ __launch_bounds__(POOL_BLOCK) void pool_ln_finish_kernel(PoolArgs a, PoolLnArgs n, double* __restrict__ out) {
+  pool_finish_body(a, PoolLn(a, n, blockIdx.x), out);
 }
 
-// D_max of the environment through an LDS word: the same value in every thread of the workgroup (two barriers)
-__device__ __forceinline__ double ln_dmax(const double* __restrict__ p, const double* __restrict__ cot, int H, double Nd,
-                                          unsigned long long* word) {
-  if (threadIdx.x == 0) *word = 0ull;
-  __syncthreads();
-  unsigned long long m = 0ull;
-  for (int k = threadIdx.x; k < H; k += POOL_BLOCK) mom_max_bits(m, (fabs(cot[k]) * fabs(p[4 * H + k])) / Nd);
-  if (m) atomicMax(word, m);
-  __syncthreads();
-  return __longlong_as_double((long long)*word);
-}
-
-// a_ik and dn_ik = (cot_k a_ik) / N of one term
-__device__ __forceinline__ double ln_dn(double nn, double cot, double Nd, bool is_tanh) {
-  double act;
-  if (is_tanh) {
-    const double h = tanh(nn);
-    act = 1.0 - h * h;
-  } else {
-    act = nn > 0.0 ? 1.0 : 0.0;
-  }
-  return (cot * act) / Nd;
-}
-
-// The forward's pass with the activations recomputed, twice: the first walk over k behind mu and r gives m1_i, m2_i and deposits
-// g_gamma, g_beta; the second forms dz_ik, sums g_x_i and g_v_i in float64 over ascending k (one thread owns a particle) and
-// deposits g_W, g_b.  LDS: 6H sums and 3H unit words.
 __global__ __launch_bounds__(POOL_BLOCK) void pool_ln_vjp_kernel(PoolArgs a, PoolLnArgs n, PoolVjpArgs g) {
-  __shared__ unsigned long long sums[6 * kPoolMaxHidden];
-  __shared__ int unit[3 * kPoolMaxHidden];
-  __shared__ unsigned long long dword;
-  const int env = blockIdx.y, H = a.H, lane = threadIdx.x & 63;
-  const unsigned long long mb = a.umax[env];
-  const bool finite = mb < kMomInfBits;
-  const double* __restrict__ p = a.params + (size_t)env * a.env_params;
-  const double* __restrict__ xe = a.x + (size_t)env * a.ld;
-  const double* __restrict__ ve = a.v + (size_t)env * a.ld;
-  const double* __restrict__ ge = n.cot + (size_t)env * H;
-  const double umx = finite ? __longlong_as_double((long long)mb) : 0.0, Nd = (double)a.N;
-  const double rmx = __longlong_as_double((long long)n.rmax[env]);
-  const double nan = __longlong_as_double(0x7FF8000000000000ll);
-  const bool bad = ln_env_bad(p, ge, H, umx) || !finite;
-  const double dmax = ln_dmax(p, ge, H, Nd, &dword);
-  long long t0, t1;
-  pool_range(a, t0, t1);
-  if (bad) {                                               // (uniform) NaN rows; the finishing kernel writes the parameters' NaN
-    const long long i1 = 2 * t1 < a.N ? 2 * t1 : a.N;
-    for (long long i = 2 * t0 + threadIdx.x; i < i1; i += POOL_BLOCK) {
-      if (g.g_x) g.g_x[(size_t)env * a.N + i] = nan;
-      if (g.g_v) g.g_v[(size_t)env * a.N + i] = nan;
-    }
-    return;
-  }
-  const bool dep = g.want_params != 0;
-  for (int k = threadIdx.x; k < H; k += POOL_BLOCK) {
-#pragma unroll
-    for (int m = 0; m < 6; ++m) sums[m * H + k] = 0ull;
-    const LnVjpUnits ue = ln_vjp_units(p[4 * H + k], ge[k], dmax, rmx, umx, Nd, n.sqrtH, a.bitsN);
-    unit[k] = dep ? ue.w : kPoolSkip;
-    unit[H + k] = dep ? ue.g : kPoolSkip;
-    unit[2 * H + k] = dep ? ue.b : kPoolSkip;
-  }
-  __syncthreads();
-  const bool is_tanh = a.activation == PIC_ACT_TANH;
-  const double cx = kTwoPi / a.L;
-  for (long long tc = t0; tc < t1; tc += (long long)POOL_BLOCK * kPoolTiles) {
-    PoolLane q;
-    pool_load(a, xe, ve, tc, t1, q);
-    double mu[kPoolPerLane], r[kPoolPerLane], m1[kPoolPerLane], m2[kPoolPerLane];
-    ln_stats(p, H, n, q, mu, r);
-#pragma unroll
-    for (int j = 0; j < kPoolPerLane; ++j) m1[j] = m2[j] = 0.0;
-    for (int k = 0; k < H; ++k) {
-      const int ug = unit[H + k], ub = unit[2 * H + k];
-      const bool ong = ug != kPoolSkip && ug != kPoolNan, onb = ub != kPoolSkip && ub != kPoolNan;      // (uniform)
-      const LnRow w = ln_row(p, H, k);
-      const double ck = ge[k];
-      long long pg = 0, pb = 0;
-#pragma unroll
-      for (int j = 0; j < kPoolPerLane; ++j) {
-        double y;
-        const double nn = ln_norm(w, q.c[j], q.s[j], q.u[j], mu[j], r[j], y);
-        const double dn = ln_dn(nn, ck, Nd, is_tanh), dy = dn * w.g;
-        m1[j] = m1[j] + dy;
-        m2[j] = m2[j] + dy * y;
-        if (ong && q.on[j]) pg += __double2ll_rn(ldexp(dn * y, -ug));
-        if (onb && q.on[j]) pb += __double2ll_rn(ldexp(dn, -ub));
-      }
-      if (ong) {
-        pg = wave_sum_i64(pg);
-        if (lane == 0 && pg) atomicAdd(sums + 4 * H + k, (unsigned long long)pg);
-      }
-      if (onb) {
-        pb = wave_sum_i64(pb);
-        if (lane == 0 && pb) atomicAdd(sums + 5 * H + k, (unsigned long long)pb);
-      }
-    }
-    double sx[kPoolPerLane], sv[kPoolPerLane];
-#pragma unroll
-    for (int j = 0; j < kPoolPerLane; ++j) {
-      m1[j] = m1[j] / n.Hd;
-      m2[j] = m2[j] / n.Hd;
-      sx[j] = sv[j] = 0.0;
-    }
-    for (int k = 0; k < H; ++k) {
-      const int ue = unit[k];
-      const bool on = ue != kPoolSkip && ue != kPoolNan;   // (uniform)
-      const LnRow w = ln_row(p, H, k);
-      const double ck = ge[k];
-      long long pc = 0, ps = 0, pu = 0, pr = 0;
-#pragma unroll
-      for (int j = 0; j < kPoolPerLane; ++j) {
-        double y;
-        const double nn = ln_norm(w, q.c[j], q.s[j], q.u[j], mu[j], r[j], y);
-        const double dy = ln_dn(nn, ck, Nd, is_tanh) * w.g;
-        const double dz = ((dy - m1[j]) - y * m2[j]) * r[j];
-        sx[j] = sx[j] + dz * (w.w1 * q.c[j] - w.w0 * q.s[j]);
-        sv[j] = sv[j] + dz * w.w2;
-        if (on && q.on[j]) {
-          pc += __double2ll_rn(ldexp(dz * q.c[j], -ue));
-          ps += __double2ll_rn(ldexp(dz * q.s[j], -ue));
-          pu += __double2ll_rn(ldexp(dz * q.u[j], -ue));
-          pr += __double2ll_rn(ldexp(dz, -ue));
-        }
-      }
-      if (on) {
-        pc = wave_sum_i64(pc);
-        ps = wave_sum_i64(ps);
-        pu = wave_sum_i64(pu);
-        pr = wave_sum_i64(pr);
-        if (lane == 0) {
-          if (pc) atomicAdd(sums + k, (unsigned long long)pc);
-          if (ps) atomicAdd(sums + H + k, (unsigned long long)ps);
-          if (pu) atomicAdd(sums + 2 * H + k, (unsigned long long)pu);
-          if (pr) atomicAdd(sums + 3 * H + k, (unsigned long long)pr);
-        }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < kPoolPerLane; ++j) {
-      if (!q.on[j]) continue;
-      const long long i = 2 * (tc + (long long)(j >> 1) * POOL_BLOCK + threadIdx.x) + (j & 1);
-      const size_t o = (size_t)env * a.N + i;
-      if (g.g_x) g.g_x[o] = cx * sx[j];
-      if (g.g_v) g.g_v[o] = a.v_scale * sv[j];
-    }
-  }
-  __syncthreads();
-  if (!dep) return;
-  for (int c = threadIdx.x; c < 6 * H; c += POOL_BLOCK) {
-    const unsigned long long s = sums[c];
-    if (s) atomicAdd(a.acc + (size_t)env * 6 * H + c, s);
-  }
+  PoolLn layer(a, n, blockIdx.y);
+  pool_vjp_body(a, g, layer);
 }
 
-// One workgroup per environment: the 6H integer sums to gE [env][6H] in the parameters' order (g_W [H][3], g_b, g_gamma, g_beta
-// [H] each); +0 where the bound is zero, NaN for a non-finite bound and for an environment that is NaN as a whole; the
-// accumulators and the two max words are cleared behind the read.
 __global__ __launch_bounds__(POOL_BLOCK) void pool_ln_vjp_finish_kernel(PoolArgs a, PoolLnArgs n, PoolVjpArgs g, double* __restrict__ gE) {
-  __shared__ unsigned long long dword;
-  const int env = blockIdx.x, H = a.H;
-  const unsigned long long mb = a.umax[env];
-  const bool finite = mb < kMomInfBits;
-  const double* __restrict__ p = a.params + (size_t)env * a.env_params;
-  const double* __restrict__ ge = n.cot + (size_t)env * H;
-  const double umx = finite ? __longlong_as_double((long long)mb) : 0.0, Nd = (double)a.N;
-  const double rmx = __longlong_as_double((long long)n.rmax[env]);
-  const double nan = __longlong_as_double(0x7FF8000000000000ll);
-  const bool bad = ln_env_bad(p, ge, H, umx) || !finite;
-  const double dmax = ln_dmax(p, ge, H, Nd, &dword);
-  if (g.want_params) {
-    for (int c = threadIdx.x; c < 6 * H; c += POOL_BLOCK) {
-      const int m = c / H, k = c - m * H;
-      unsigned long long* s = a.acc + (size_t)env * 6 * H + c;
-      const LnVjpUnits us = ln_vjp_units(p[4 * H + k], ge[k], dmax, rmx, umx, Nd, n.sqrtH, a.bitsN);
-      const int ue = bad ? kPoolNan : (m < 4 ? us.w : (m == 4 ? us.g : us.b));
-      double r = 0.0;
-      if (ue == kPoolNan) r = nan;
-      else if (ue != kPoolSkip) r = ldexp((double)(long long)*s, ue);
-      gE[(size_t)env * 6 * H + (m < 3 ? 3 * k + m : m * H + k)] = r;
-      *s = 0ull;
-    }
-  }
-  __syncthreads();                                         // (every lane has read the max words)
-  if (threadIdx.x == 0) a.umax[env] = n.rmax[env] = 0ull;
+  PoolLn layer(a, n, blockIdx.x);
+  pool_vjp_finish_body(a, g, layer, gE);
 }
 
 }  // namespace

@@ -38,8 +38,8 @@
 // handle, the launch schedule and the C ABI, but for the host side of the differentiable rollouts: host_diff.h, host_phase.h,
 // host_tape.h, host_tangent.h, host_tangent_walk.h.  pic_copy.h, host_copy.h and host_copy_map.h: copies of whole environments (pic_copy_envs).
 // pic_policy.h and host_policy.h: the MLP policy of pic_policy_eval and pic_step_policy.
-// pic_pool.h and host_pool.h: the pooled particle features of pic_pool and pic_pool_vjp; pic_pool_ln.h: those of pic_pool_ln and
-// pic_pool_ln_vjp (a LayerNorm inside the per-particle layer).
+// pic_pool.h and host_pool.h: the pooled particle features of pic_pool and pic_pool_vjp, as passes over a layer type;
+// pic_pool_ln.h: the layer type of pic_pool_ln and pic_pool_ln_vjp (a LayerNorm inside the per-particle layer).
 
 #include <hip/hip_runtime.h>
 

@@ -49,11 +49,12 @@ def _same(a, b):
 
 
 def _same_results(out, g, out2, g2):
-    return _same(out, out2) and all(_same(g[k], g2[k]) for k in ("g_x", "g_v", "g_W", "g_b"))
+    """Every gradient of the call: g_x, g_v, g_W, g_b, and with a LayerNorm (tests/test_gpu_pool_ln.py) g_gamma and g_beta."""
+    return _same(out, out2) and g.keys() == g2.keys() >= {"g_x", "g_v", "g_W", "g_b"} and all(_same(g[k], g2[k]) for k in g)
 
 
 def _cuda(*arrays):
-    return [torch.as_tensor(a, device="cuda") for a in arrays]
+    return [None if a is None else torch.as_tensor(a, device="cuda") for a in arrays]
 
 
 # ---- 1. parity ------------------------------------------------------------------------------------------------------------------------

@@ -11,6 +11,7 @@ import torch
 import hp_pool as hp
 import hp_pool_ln as hpl
 from conftest import record_measure, rel_err
+from test_gpu_pool import _bits, _cuda, _np, _same, _same_results  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -22,26 +23,6 @@ KEYS = ("g_x", "g_v", "g_W", "g_b", "g_gamma", "g_beta")
 def _env(E, N, Ng=64, L_=L, **kw):
     from ocplasma_amd.env.batched import BatchedPIC
     return BatchedPIC(E, N, Ng, L=L_, dt=0.1, **kw)
-
-
-def _np(a):
-    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
-
-
-def _bits(a):
-    return np.ascontiguousarray(_np(a)).view(np.int64)
-
-
-def _same(a, b):
-    return np.array_equal(_bits(a), _bits(b))
-
-
-def _same_results(out, g, out2, g2):
-    return _same(out, out2) and all(_same(g[k], g2[k]) for k in KEYS)
-
-
-def _cuda(*arrays):
-    return [None if a is None else torch.as_tensor(a, device="cuda") for a in arrays]
 
 
 def _fwd(env, p, act, x=None, v=None, **kw):

@@ -5,22 +5,22 @@ twin, the proof that every term of an integer sum is within its stated bound (on
 of every relu pre-activation from the kink, the work block's layout through a stand-alone driver (also under the address and
 undefined-behaviour sanitizers), the compiler's resource report of the new kernels and the Python argument checks."""
 import ctypes
+import functools
 import itertools
 import json
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import hp_pool as hp
+import hp_pool_layout
 import hp_pool_ln as hpl
 from conftest import record_measure
+from hp_pool_layout import _flags, drivers  # noqa: F401  (drivers: a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "optimal-control-1d-electrostatic-plasma_amd", "csrc")
 L = hpl.L
 G19, PHI = hpl.G19, hpl.PHI
 
@@ -224,65 +224,8 @@ def test_restatement_is_order_free_and_scales_by_powers_of_two():
 
 
 # ---- 7. the work block's layout ---------------------------------------------------------------------------------------------------
-FLAGS = "per_env vjp host params_host xv g_x g_v g_params".split()
-
-
-def _flags(**kw):
-    assert set(kw) <= set(FLAGS)
-    return sum(1 << i for i, f in enumerate(FLAGS) if kw.get(f))
-
-
-def _build(tmp, name, extra):
-    out = str(tmp / name)
-    args = ["-std=c++17", "-O1", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC] + extra + [os.path.join(ROOT, "tests", "pool_ln_driver.cpp"), "-o", out]
-    cxx = shutil.which("c++")
-    if cxx:
-        cmd = [cxx] + args
-    else:
-        hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-        if not os.path.exists(hipcc):
-            pytest.skip("no host C++ compiler (c++ or hipcc) to build tests/pool_ln_driver.cpp with")
-        cmd = [hipcc, "-x", "c++"] + args
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-
-    def run(lines):
-        p = subprocess.run([out], input="".join(l + "\n" for l in lines), capture_output=True, text=True)
-        assert p.returncode == 0 and not p.stderr, p.stderr
-        res = p.stdout.splitlines()
-        assert len(res) == len(lines)
-        return res
-    return run
-
-
-@pytest.fixture(scope="module")
-def drivers(tmp_path_factory):
-    tmp = tmp_path_factory.mktemp("pool_ln")
-    return _build(tmp, "pool_ln_driver", []), _build(tmp, "pool_ln_driver_san", ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
-
-
-def _model(E, N, H, f):
-    """The layout restated: the parts in order, each rounded up to 256 bytes; a part without elements has no view."""
-    on = {k: bool(f >> i & 1) for i, k in enumerate(FLAGS)}
-    P, rows = 6 * H, E * N
-    parts = [("max", 2 * E if on["vjp"] else E), ("acc", E * (P if on["vjp"] else H)),
-             ("gE", E * P if on["vjp"] and on["g_params"] and (not on["per_env"] or on["host"]) else 0),
-             ("params", (E if on["per_env"] else 1) * P if on["params_host"] else 0)]
-    if on["host"]:
-        parts += [("x", rows if on["xv"] else 0), ("v", rows if on["xv"] else 0), ("cot", E * H if on["vjp"] else 0),
-                  ("out", 0 if on["vjp"] else E * H), ("g_x", rows if on["g_x"] else 0), ("g_v", rows if on["g_v"] else 0),
-                  ("g", P if on["g_params"] and not on["per_env"] else 0)]
-    else:
-        parts += [(k, 0) for k in ("x", "v", "cot", "out", "g_x", "g_v", "g")]
-    at, views, spans = 0, [], []
-    for name, count in parts:
-        views.append(f"{name}={at if count else 'null'}")
-        if count:
-            spans.append((at, at + 8 * count))
-        at = (at + 8 * count + 255) // 256 * 256
-    assert all(a[1] <= b[0] for a, b in zip(spans, spans[1:])) and (not spans or spans[-1][1] <= at)      # overlap-free, inside
-    return f"ok pool={at} " + " ".join(views)
-
+LN = True                       # (hp_pool_layout: the drivers fixture)
+_model = functools.partial(hp_pool_layout._model, ln=LN)
 
 TABLE = [
     # a device forward of the stored particles: the max words and H sums per environment, nothing else
