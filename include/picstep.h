@@ -945,6 +945,43 @@ int pic_pool_ln(pic_handle* h, const pic_pool_ln_spec* s, const void* x, const v
 int pic_pool_ln_vjp(pic_handle* h, const pic_pool_ln_spec* s, const void* x, const void* v, const double* cot, int mem_kind,
                     void* g_x, void* g_v, double* g_params);
 
+/* ---- Forward mode of the pooled particle features (additive to ABI 5) -------------------------------------------
+ * pic_pool_jvp, pic_pool_ln_jvp: the directional derivatives of pic_pool / pic_pool_ln along K directions (1 <= K <= 8) in one
+ * call.  d_x, d_v [K][num_envs][N] float64 in mem_kind memory, each may be NULL (0); d_params [K][P], or [K][num_envs][P] with
+ * per_env, laid out as the parameters (P = 4H or 6H), in s->params_mem_kind memory, may be NULL (0); d_out [K][num_envs][H].
+ * All three tangents NULL is allowed and gives +0 everywhere.  Float64, every product rounded before its sum (no FMA), the
+ * additions in the order written.  With c, s, u, z, h, a_ik of the VJP and, per direction,
+ *     tq_i = ((2 pi) d_x_i) / L   (period for L in the LayerNorm form)          tu_i = d_v_i v_scale
+ *     dz_ik = db_k, + dW_k0 c_i, + dW_k1 s_i, + dW_k2 u_i, + (W_k1 c_i - W_k0 s_i) tq_i, + W_k2 tu_i
+ * pic_pool_jvp:     d_out_k = (sum_i a_ik dz_ik) / N
+ * pic_pool_ln_jvp:  dmu_i = (sum_k dz_ik) / H   (from +0 over ascending k)       e_ik = dz_ik - dmu_i
+ *                   p_i = (sum_k y_ik e_ik) / H   (the same)                      dy_ik = (e_ik - y_ik p_i) r_i
+ *                   dn_ik = (dgamma_k y_ik + gamma_k dy_ik) + dbeta_k             d_out_k = (sum_i a_ik dn_ik) / N
+ * The sum over particles is pic_pool's 64-bit integer sum in the unit 2^(e + b - 61), 2^b >= N, 2^e above a bound on one term
+ * that is known before the pass, per (direction, environment, k), each times the margin 1 + 2^-40:
+ *     pic_pool_jvp:     Z_k = |db_k|, + |dW_k0|, + |dW_k1|, + |dW_k2| u_max, + (|W_k0| + |W_k1|) tq_max, + |W_k2| tu_max
+ *     pic_pool_ln_jvp:  (|dgamma_k| sqrt(H) + |gamma_k| ((Z_k + (1 + sqrt(H)) Z_max) r_max)) + |dbeta_k|,   Z_max = max_k Z_k
+ * (|y| <= sqrt(H), mean_k y^2 <= 1 and mean_k e^2 <= Z_max^2), with tq_max = max_i |tq_i| and tu_max = max_i |tu_i| of the
+ * (direction, environment), taken in the max pass next to u_max (and r_max) as order-independent maxima of bit patterns.  So the
+ * result depends neither on the order of the particles nor on the launch geometry nor on the environment's place in the batch,
+ * and K directions in one call equal, bit for bit, K calls of one direction.  A zero bound deposits nothing and gives +0;
+ * tangents scaled per direction by a power of two scale the result's bits by exactly that factor while everything stays a
+ * normal double.
+ * Non-finite input.  A non-finite u_i or q_i makes every direction of that environment NaN; a non-finite tq_i or tu_i that
+ * (direction, environment) and no other.  pic_pool_jvp: a non-finite W_k., b_k, dW_k. or db_k gives NaN in d_out_k (of that
+ * direction only where it is a tangent).  pic_pool_ln_jvp: whatever makes pic_pool_ln NaN as a whole does so here, and so does a
+ * non-finite dW_k. or db_k for its direction (the mean over k spreads it); a non-finite gamma_k, beta_k, dgamma_k or dbeta_k
+ * gives NaN in d_out_k alone.  H = 1 with the LayerNorm: every dy is +0 and the term is exactly a dbeta.  The next call of any
+ * pool entry finds the work block clean.
+ * x, v, the stored particles (both NULL; float64 handles only), the memory kinds, the state rules, PIC_EINVAL / PIC_ESTATE and
+ * their messages are pic_pool's / pic_pool_ln's (d_out for out); in addition PIC_EINVAL, before anything is enqueued, for K
+ * outside 1..8.  The working memory is pic_pool's block: 8 num_envs (1 + 2K + K H) bytes of max words and sums (one more word
+ * per environment with the LayerNorm), and the device copies of what is given in host memory. */
+int pic_pool_jvp(pic_handle* h, const pic_pool_spec* s, const void* x, const void* v, int K, const void* d_x, const void* d_v,
+                 const double* d_params, int mem_kind, double* d_out);
+int pic_pool_ln_jvp(pic_handle* h, const pic_pool_ln_spec* s, const void* x, const void* v, int K, const void* d_x, const void* d_v,
+                    const double* d_params, int mem_kind, double* d_out);
+
 int pic_sync(pic_handle* h);
 /* Number of particle positions found non-finite or out of range by the last sweeps (0 = healthy).  Counts the state's
  * particles only: the positions of pic_eval_field / pic_compute_E probes never add to it. */

@@ -207,6 +207,8 @@ SIGNATURES = {
     "pic_pool_vjp": [_vp, C.POINTER(PicPoolSpec), _vp, _vp, _vp, C.c_int, _vp, _vp, _vp],
     "pic_pool_ln": [_vp, C.POINTER(PicPoolLnSpec), _vp, _vp, C.c_int, _vp],
     "pic_pool_ln_vjp": [_vp, C.POINTER(PicPoolLnSpec), _vp, _vp, _vp, C.c_int, _vp, _vp, _vp],
+    "pic_pool_jvp": [_vp, C.POINTER(PicPoolSpec), _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp],
+    "pic_pool_ln_jvp": [_vp, C.POINTER(PicPoolLnSpec), _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp],
     "pic_sync": [_vp],
     "pic_bad_count": [_vp, _i64p],
     "pic_last_error": [_vp],
@@ -975,6 +977,17 @@ class Handle:
         """pic_pool_ln_vjp on addresses (int, 0 = NULL) in mem_kind memory; spec: a PicPoolLnSpec."""
         p = _ptrs(x, v, cot, g_x, g_v, g_params)
         self._chk(self.lib.pic_pool_ln_vjp(self._h, C.byref(spec), p[0], p[1], p[2], int(mem_kind), p[3], p[4], p[5]))
+
+    def pool_jvp(self, spec, x, v, K, d_x, d_v, d_params, mem_kind, d_out):
+        """pic_pool_jvp on addresses (int, 0 = NULL) in mem_kind memory (d_params: in the spec's params_mem_kind memory); spec: a
+        PicPoolSpec."""
+        p = _ptrs(x, v, d_x, d_v, d_params, d_out)
+        self._chk(self.lib.pic_pool_jvp(self._h, C.byref(spec), p[0], p[1], int(K), p[2], p[3], p[4], int(mem_kind), p[5]))
+
+    def pool_ln_jvp(self, spec, x, v, K, d_x, d_v, d_params, mem_kind, d_out):
+        """pic_pool_ln_jvp on addresses (int, 0 = NULL) in mem_kind memory; spec: a PicPoolLnSpec."""
+        p = _ptrs(x, v, d_x, d_v, d_params, d_out)
+        self._chk(self.lib.pic_pool_ln_jvp(self._h, C.byref(spec), p[0], p[1], int(K), p[2], p[3], p[4], int(mem_kind), p[5]))
 
     # -- forward mode of the moments and their trace on a tape (DESIGN.md 7l) ---------------------------
     def moments_jvp(self, K, d_x, d_v, mem_kind, d_m):

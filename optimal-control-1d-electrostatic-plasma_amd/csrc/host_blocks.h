@@ -221,8 +221,8 @@ size_t moments_jvp_parts(Carver c, const BlockDims& d, int kc, Holder& j) {
   return c.at;
 }
 
-// ---- pooled particle features (host_pool.h) --------------------------------------------------------------------
-// what a pic_pool / pic_pool_vjp / pic_pool_ln / pic_pool_ln_vjp call gives and wants, as far as its block depends on it
+// ---- pooled particle features (host_pool.h) ----------------------------------------------------------------
+// what a pic_pool / pic_pool_vjp / pic_pool_jvp call (or its _ln form) gives and wants, as far as its block depends on it
 struct PoolCallShape {
   size_t H = 0, N = 0;                // hidden units; particles per environment
   bool per_env = false;               // a parameter vector per environment
@@ -231,32 +231,42 @@ struct PoolCallShape {
   bool xv = false;                    // x and v are given (else the handle's particles)
   bool g_x = false, g_v = false, g_params = false;      // outputs wanted (vjp)
   bool ln = false;                    // pic_pool_ln / pic_pool_ln_vjp: P = 6H (W, b, gamma, beta), two max words in the VJP
+  bool jvp = false;                   // pic_pool_jvp / pic_pool_ln_jvp (vjp is false then)
+  int K = 0;                          // ... its directions
+  bool d_x = false, d_v = false, d_params = false;      // ... the tangents given
 };
 
-// the handle's block: the max words [env] (the LayerNorm's VJP: r_max [env] behind them) and the integer sums [env][H] or
-// [env][P] (both zero between calls), the VJP's per-environment parameter sums and -- for what lives in host memory -- the
-// device copies of the call's inputs and outputs
+// the handle's block: the max words [env] (the LayerNorm's VJP and JVP: r_max [env] behind them; the JVP: the tangents' maxima
+// [2][K][env] behind those) and the integer sums [env][H], [env][P] or [K][env][H] (all zero between calls), the VJP's
+// per-environment parameter sums and -- for what lives in host memory -- the device copies of the call's inputs and outputs
 struct PoolViews {
   unsigned long long *max = nullptr, *acc = nullptr;
   double *gE = nullptr, *params = nullptr, *x = nullptr, *v = nullptr, *cot = nullptr, *out = nullptr, *g_x = nullptr,
          *g_v = nullptr, *g = nullptr;
+  unsigned long long* tmax = nullptr;                   // the JVP's [2][K][env] inside `max`
+  double *d_params = nullptr, *d_x = nullptr, *d_v = nullptr;      // the JVP's tangents given in host memory (out: d_out)
 };
 
 inline size_t pool_parts(Carver c, const BlockDims& d, const PoolCallShape& s, PoolViews& k) {
-  const size_t E = d.num_envs, P = (s.ln ? 6 : 4) * s.H, rows = E * s.N;
-  c.take(k.max, s.ln && s.vjp ? 2 * E : E);
-  c.take(k.acc, E * (s.vjp ? P : s.H));
+  const size_t E = d.num_envs, P = (s.ln ? 6 : 4) * s.H, rows = E * s.N, K = s.jvp ? (size_t)s.K : 1;
+  const size_t own = s.ln && (s.vjp || s.jvp) ? 2 * E : E;      // (u_max, and r_max where a bound needs it)
+  c.take(k.max, own + (s.jvp ? 2 * K * E : 0));
+  if (s.jvp && k.max) k.tmax = k.max + own;
+  c.take(k.acc, E * (s.vjp ? P : K * s.H));
   // (shared parameters: the rows the reduction reads; per-environment ones in device memory are written where the caller wants them)
   c.take(k.gE, s.vjp && s.g_params && (!s.per_env || s.host) ? E * P : 0);
   c.take(k.params, s.params_host ? (s.per_env ? E : 1) * P : 0);
+  c.take(k.d_params, s.jvp && s.d_params && s.params_host ? K * (s.per_env ? E : 1) * P : 0);
   if (!s.host) return c.at;
   c.take(k.x, s.xv ? rows : 0);
   c.take(k.v, s.xv ? rows : 0);
   c.take(k.cot, s.vjp ? E * s.H : 0);
-  c.take(k.out, s.vjp ? 0 : E * s.H);
+  c.take(k.out, s.vjp ? 0 : K * E * s.H);
   c.take(k.g_x, s.g_x ? rows : 0);
   c.take(k.g_v, s.g_v ? rows : 0);
   c.take(k.g, s.g_params && !s.per_env ? P : 0);
+  c.take(k.d_x, s.jvp && s.d_x ? K * rows : 0);
+  c.take(k.d_v, s.jvp && s.d_v ? K * rows : 0);
   return c.at;
 }
 

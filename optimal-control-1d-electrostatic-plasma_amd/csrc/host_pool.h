@@ -2,8 +2,8 @@
 #pragma once
 // ---------------------------------------------------------------------------------------------
 // Pooled particle features (include/picstep.h: pic_pool, pic_pool_vjp; pic_pool.h) and the same with a LayerNorm
-// inside the per-particle layer (pic_pool_ln, pic_pool_ln_vjp; pic_pool_ln.h): one begin, one forward and one VJP
-// for both layers; call.shape.ln picks the kernels
+// inside the per-particle layer (pic_pool_ln, pic_pool_ln_vjp; pic_pool_ln.h): one begin, one forward, one VJP
+// and one JVP (pic_pool_jvp, pic_pool_ln_jvp) for both layers; call.shape.ln picks the kernels
 // ---------------------------------------------------------------------------------------------
 // what is wrong with a spec (null: nothing)
 static const char* pool_spec_error(const pic_pool_spec* s) {
@@ -26,8 +26,8 @@ struct PoolCall {
   dim3 grid;
 };
 
-// One call's checks, block and kernel arguments.  `result`: out (forward) or cot (VJP), which must not be NULL.  c.shape: vjp,
-// g_* and ln as the caller set them (ln: the parameters are 6H per vector); the rest is filled in here.
+// One call's checks, block and kernel arguments.  `result`: out (forward), cot (VJP) or d_out (JVP), which must not be NULL.
+// c.shape: vjp, g_*, jvp, K, d_* and ln as the caller set them (ln: the parameters are 6H per vector); the rest is filled in here.
 // Everything is refused before anything is enqueued; on PIC_OK the block is carved for c.shape, its sums are zero, the
 // parameters and the particles are on the device and c.a, c.grid are the passes'.
 static int pool_begin(pic_handle* h, const pic_pool_spec* s, const void* x, const void* v, const void* result, const char* result_name,
@@ -36,6 +36,8 @@ static int pool_begin(pic_handle* h, const pic_pool_spec* s, const void* x, cons
   if (int rc = check_mem_kind(h, mem_kind, who)) return rc;
   if (const char* bad = pool_spec_error(s)) return fail(h, PIC_EINVAL, std::string(who) + ": " + bad);
   if (!result) return fail(h, PIC_EINVAL, std::string(who) + ": " + result_name + " is NULL");
+  if (c.shape.jvp && (c.shape.K < 1 || c.shape.K > kMaxTangents))
+    return fail(h, PIC_EINVAL, std::string(who) + ": need 1 <= K <= " + std::to_string(kMaxTangents));
   if (!x != !v) return fail(h, PIC_EINVAL, std::string(who) + ": x and v must both be given or both be NULL");
   if (!x) {
     if (h->fmt != FMT_F64)
@@ -53,7 +55,7 @@ static int pool_begin(pic_handle* h, const pic_pool_spec* s, const void* x, cons
   if (int rc = call_reserve(h, h->pool_block, &h->pool_cap, who, "the working memory", w,
                             [&](Carver cv, PoolViews& k) { return pool_parts(cv, block_dims(h), shape, k); }))
     return rc;
-  const size_t accn = E * (shape.vjp ? P : H), zero = (size_t)((char*)(w.acc + accn) - (char*)w.max);
+  const size_t accn = E * (shape.vjp ? P : (shape.jvp ? (size_t)shape.K : 1) * H), zero = (size_t)((char*)(w.acc + accn) - (char*)w.max);
   if (h->pool_cap != cap_before || zero > h->pool_zero) {
     h->pool_zero = 0;
     HIPCHK(h, hipMemsetAsync(w.max, 0, Carver::upto(w.max, w.acc + accn), h->stream));
@@ -96,7 +98,7 @@ static int pool_ln_begin(pic_handle* h, const pic_pool_ln_spec* s, const void* x
   if (int rc = pool_begin(h, &base, x, v, result, result_name, mem_kind, who, c)) return rc;
   if (s->period > 0.0) c.a.L = s->period;
   c.n = PoolLnArgs{};
-  c.n.rmax = c.shape.vjp ? c.w.max + h->cfg.num_envs : nullptr;
+  c.n.rmax = c.shape.vjp || c.shape.jvp ? c.w.max + h->cfg.num_envs : nullptr;
   c.n.eps = s->eps; c.n.Hd = (double)c.a.H; c.n.sqrtH = std::sqrt(c.n.Hd);
   return PIC_OK;
 }
@@ -168,6 +170,45 @@ static int pool_backward(pic_handle* h, const PoolCall& c, const double* cot, in
   return pool_end(h, e, mem_kind == PIC_HOST, who);
 }
 
+// the shape of a JVP call of K directions with these tangents
+static PoolCallShape pool_jvp_shape(int K, const void* d_x, const void* d_v, const double* d_params) {
+  PoolCallShape shape;
+  shape.jvp = true; shape.K = K; shape.d_x = d_x != nullptr; shape.d_v = d_v != nullptr; shape.d_params = d_params != nullptr;
+  return shape;
+}
+
+// the JVP of a call that has begun, for both layers: the max pass (u_max, the LayerNorm's r_max, every direction's tq_max and
+// tu_max), the pass over groups of directions, the finish
+static int pool_tangent(pic_handle* h, const PoolCall& c, int params_mem_kind, const void* d_x, const void* d_v, const double* d_params,
+                        int mem_kind, double* d_out, const char* who) {
+  const PoolArgs& a = c.a;
+  const PoolViews& w = c.w;
+  const size_t E = h->cfg.num_envs, N = h->cfg.N, K = (size_t)c.shape.K, P = (c.shape.ln ? 6 : 4) * (size_t)a.H;
+  const dim3 block(POOL_BLOCK), envs((unsigned)E);
+  PoolJvpArgs t{};
+  HIPCHK(h, device_input(h, static_cast<const double*>(d_x), mem_kind, K * E * N * sizeof(double), w.d_x, &t.d_x));
+  HIPCHK(h, device_input(h, static_cast<const double*>(d_v), mem_kind, K * E * N * sizeof(double), w.d_v, &t.d_v));
+  t.dir_params = (long long)((c.shape.per_env ? E : 1) * P);
+  HIPCHK(h, device_input(h, d_params, params_mem_kind, K * (size_t)t.dir_params * sizeof(double), w.d_params, &t.d_params));
+  t.tmax = w.tmax; t.K = (int)K; t.num_envs = (int)E;
+  double* dev = device_output(d_out, mem_kind, w.out);
+  static_assert(kPoolMaxDirs == kMaxTangents, "the max pass unrolls over every direction a call may have");
+  if (c.shape.ln) {
+    const dim3 grid(c.grid.x, c.grid.y, (unsigned)((K + kPoolLnJvpDirs - 1) / kPoolLnJvpDirs));
+    hipLaunchKernelGGL(pool_ln_jvp_max_kernel, c.grid, block, 0, h->stream, a, c.n, t);
+    hipLaunchKernelGGL(pool_ln_jvp_kernel, grid, block, 0, h->stream, a, c.n, t);
+    hipLaunchKernelGGL(pool_ln_jvp_finish_kernel, envs, block, 0, h->stream, a, c.n, t, dev);
+  } else {
+    const dim3 grid(c.grid.x, c.grid.y, (unsigned)((K + kPoolJvpDirs - 1) / kPoolJvpDirs));
+    hipLaunchKernelGGL(pool_jvp_max_kernel, c.grid, block, 0, h->stream, a, t);
+    hipLaunchKernelGGL(pool_jvp_kernel, grid, block, 0, h->stream, a, t);
+    hipLaunchKernelGGL(pool_jvp_finish_kernel, envs, block, 0, h->stream, a, t, dev);
+  }
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = device_result(h, d_out, dev, K * E * a.H * sizeof(double));
+  return pool_end(h, e, mem_kind == PIC_HOST, who);
+}
+
 int pic_pool(pic_handle* h, const pic_pool_spec* s, const void* x, const void* v, int mem_kind, double* out) {
   PoolCall c;
   if (int rc = pool_begin(h, s, x, v, out, "out", mem_kind, "pic_pool", c)) return rc;
@@ -194,4 +235,20 @@ int pic_pool_ln_vjp(pic_handle* h, const pic_pool_ln_spec* s, const void* x, con
   c.shape = pool_vjp_shape(g_x, g_v, g_params);
   if (int rc = pool_ln_begin(h, s, x, v, cot, "cot", mem_kind, "pic_pool_ln_vjp", c)) return rc;
   return pool_backward(h, c, cot, mem_kind, g_x, g_v, g_params, "pic_pool_ln_vjp");
+}
+
+int pic_pool_jvp(pic_handle* h, const pic_pool_spec* s, const void* x, const void* v, int K, const void* d_x, const void* d_v,
+                 const double* d_params, int mem_kind, double* d_out) {
+  PoolCall c;
+  c.shape = pool_jvp_shape(K, d_x, d_v, d_params);
+  if (int rc = pool_begin(h, s, x, v, d_out, "d_out", mem_kind, "pic_pool_jvp", c)) return rc;
+  return pool_tangent(h, c, s->params_mem_kind, d_x, d_v, d_params, mem_kind, d_out, "pic_pool_jvp");
+}
+
+int pic_pool_ln_jvp(pic_handle* h, const pic_pool_ln_spec* s, const void* x, const void* v, int K, const void* d_x, const void* d_v,
+                    const double* d_params, int mem_kind, double* d_out) {
+  PoolCall c;
+  c.shape = pool_jvp_shape(K, d_x, d_v, d_params);
+  if (int rc = pool_ln_begin(h, s, x, v, d_out, "d_out", mem_kind, "pic_pool_ln_jvp", c)) return rc;
+  return pool_tangent(h, c, s->params_mem_kind, d_x, d_v, d_params, mem_kind, d_out, "pic_pool_ln_jvp");
 }

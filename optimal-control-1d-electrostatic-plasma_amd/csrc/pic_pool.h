@@ -1,10 +1,11 @@
-// pic_pool.h -- pooled particle features (include/picstep.h: pic_pool, pic_pool_vjp): per environment
+// pic_pool.h -- pooled particle features (include/picstep.h: pic_pool, pic_pool_vjp; pic_pool_jvp: 7t): per
+// environment
 //   out_k = (1/N) sum_i act(b_k + W_k0 cos q_i + W_k1 sin q_i + W_k2 u_i),   q_i = 2 pi x_i / L,  u_i = v_i v_scale
-// and its vector-Jacobian product, without an [N][H] array: a lane holds kPoolPerLane particles (cos, sin, u) in registers and
-// walks the H rows of W, which are the same for every lane of the workgroup (scalar loads).  The sums over particles are 64-bit
-// integer sums of terms rounded to nearest in a power-of-two unit that is known before the pass (pic_moments' pattern), so
-// nothing depends on the order of the particles, the grid or the batch.  Off the step path: the kernels read x, v and write
-// their own work block only.  Built with -ffp-contract=off: every product is rounded before its sum.
+// its vector-Jacobian product and its directional derivatives, without an [N][H] array: a lane holds kPoolPerLane particles
+// (cos, sin, u) in registers and walks the H rows of W, which are the same for every lane of the workgroup (scalar loads).  The
+// sums over particles are 64-bit integer sums of terms rounded to nearest in a power-of-two unit that is known before the pass
+// (pic_moments' pattern), so nothing depends on the order of the particles, the grid or the batch.  Off the step path: the
+// kernels read x, v and write their own work block only.  Built with -ffp-contract=off: every product is rounded before its sum.
 // The passes are written once, as bodies over a layer type (below: "the skeleton"): PoolPlain here, PoolLn in pic_pool_ln.h.
 // A kernel is a body with its layer.
 #pragma once
@@ -144,6 +145,75 @@ __device__ __forceinline__ double pool_dn(double z, double cot, double Nd, bool 
   return (cot * act) / Nd;
 }
 
+// ---- forward mode (pic_pool_jvp, pic_pool_ln_jvp) ---------------------------------------------------------------
+constexpr int kPoolMaxDirs = 8;                      // directions of one call
+constexpr double kPoolJvpUp = 0x1.0000000001p+0;     // 1 + 2^-40: above the rounding of the JVP's bounds and terms
+
+struct PoolJvpArgs {
+  const double* d_x;           // [K][env][N] dense rows, or null: 0
+  const double* d_v;           // the same
+  const double* d_params;      // [K][P] or [K][env][P] in the parameters' layout, or null: 0
+  unsigned long long* tmax;    // [2][K][env] bit patterns of max |tq|, max |tu|; zero between calls
+  long long dir_params;        // doubles from one direction's tangent parameters to the next
+  int K, num_envs;
+};
+
+// what the bounds of one (direction, environment) rest on: u_max, tq_max, tu_max
+struct PoolJvpMax { double umx, tqm, tum; };
+// ... and what a layer adds per (direction, environment): Z_max and r_max (the LayerNorm's)
+struct PoolJvpEnv { PoolJvpMax m; double zmax, rmx; };
+
+// a lane's tangents of a group of KD directions: tq = ((2 pi) d_x) / L and tu = d_v v_scale of its particles
+template <int KD>
+struct PoolTan { double tq[KD][kPoolPerLane], tu[KD][kPoolPerLane]; };
+
+// the direction's max words of an environment; false where one is saturated (a non-finite tq or tu: that direction is NaN)
+__device__ __forceinline__ bool pool_jvp_max(const PoolJvpArgs& t, int dir, int env, double umx, PoolJvpMax& m) {
+  const unsigned long long qb = t.tmax[((size_t)0 * t.K + dir) * t.num_envs + env];
+  const unsigned long long ub = t.tmax[((size_t)1 * t.K + dir) * t.num_envs + env];
+  m = PoolJvpMax{umx, __longlong_as_double((long long)qb), __longlong_as_double((long long)ub)};
+  return qb < kMomInfBits && ub < kMomInfBits;
+}
+
+// the direction's tangent parameters of an environment (null: 0)
+__device__ __forceinline__ const double* pool_jvp_params(const PoolArgs& a, const PoolJvpArgs& t, int dir, int env) {
+  return t.d_params ? t.d_params + (size_t)dir * t.dir_params + (size_t)env * a.env_params : nullptr;
+}
+
+// Z_k, the bound of |dz_ik|: |db_k|, + |dW_k0|, + |dW_k1|, + |dW_k2| u_max, + (|W_k0| + |W_k1|) tq_max, + |W_k2| tu_max
+template <typename TRow>
+__device__ __forceinline__ double pool_jvp_z(double w0, double w1, double w2, const TRow& d, const PoolJvpMax& m) {
+  double Z = fabs(d.b);
+  Z = Z + fabs(d.w0);
+  Z = Z + fabs(d.w1);
+  Z = Z + fabs(d.w2) * m.umx;
+  Z = Z + (fabs(w0) + fabs(w1)) * m.tqm;
+  Z = Z + fabs(w2) * m.tum;
+  return Z;
+}
+
+// dz_ik = db_k, + dW_k0 c, + dW_k1 s, + dW_k2 u, + (W_k1 c - W_k0 s) tq, + W_k2 tu: each product rounded, then the sum
+template <typename TRow>
+__device__ __forceinline__ double pool_dz(double w0, double w1, double w2, const TRow& d, double c, double s, double u, double tq,
+                                          double tu) {
+  double dz = d.b;
+  dz = dz + d.w0 * c;
+  dz = dz + d.w1 * s;
+  dz = dz + d.w2 * u;
+  dz = dz + (w1 * c - w0 * s) * tq;
+  dz = dz + w2 * tu;
+  return dz;
+}
+
+// a_ik: the activation's derivative at the argument z
+__device__ __forceinline__ double pool_dact(double z, bool is_tanh) {
+  if (is_tanh) {
+    const double h = tanh(z);
+    return 1.0 - h * h;
+  }
+  return z > 0.0 ? 1.0 : 0.0;
+}
+
 // ---------------------------------------------------------------------------------------------
 // The plain layer (pic_pool, pic_pool_vjp).  What a layer type supplies to the skeleton below:
 //   kSums, kUnits          the VJP's parameter sums and unit words per hidden unit
@@ -155,9 +225,13 @@ __device__ __forceinline__ double pool_dn(double z, double cot, double Nd, bool 
 //   vjp_env(), vjp_units(), vjp_unit()   the VJP's per-environment values, the unit words of unit k into LDS, that of sum m
 //   first_walk(), back()   what the VJP does before its walk, and d cost / d z_ik from (cot_k act') / N
 //   clear()                the layer's own max words of an environment, behind the finish
+//   kRmax, trow(), jvp_env(), jvp_unit()   forward mode: whether the max pass takes r_max, the tangent row of unit k, the
+//                          (direction, environment)'s values, the unit word of d_out_k
+//   Tan, jvp_walks(), jvp_dn()   ... what a lane's particles need per direction before the walk, and dn_ik from dz_ik
 // ---------------------------------------------------------------------------------------------
 struct PoolPlain {
   static constexpr int kSums = 4, kUnits = 1;      // r c, r s, r u, r in one unit
+  static constexpr bool kRmax = false;
   struct Row { double w0, w1, w2, b; };
   struct Stats {};
   const double* __restrict__ p;
@@ -196,6 +270,26 @@ struct PoolPlain {
                                              unsigned long long*) const {}
   __device__ __forceinline__ double back(const Row&, double dn, double, const Stats&, int) const { return dn; }
   __device__ __forceinline__ void clear(int) const {}
+
+  // forward mode (pic_pool_jvp): the tangent row of unit k (tp: the direction's tangent parameters, null = 0), nothing per
+  // environment or per particle, the unit word of d_out_k from the bound Z_k, and dn = dz
+  template <int KD> struct Tan {};
+  __device__ __forceinline__ static Row trow(const double* __restrict__ tp, int H, int k) {
+    return tp ? Row{tp[3 * k], tp[3 * k + 1], tp[3 * k + 2], tp[3 * H + k]} : Row{0.0, 0.0, 0.0, 0.0};
+  }
+  __device__ __forceinline__ PoolJvpEnv jvp_env(const double*, const PoolJvpMax& m, int) const { return PoolJvpEnv{m, 0.0, 0.0}; }
+  __device__ __forceinline__ int jvp_unit(int k, const double* __restrict__ tp, const PoolJvpEnv& e) const {
+    const Row w = row(k);
+    if (!row_finite(w)) return kPoolNan;
+    return pool_unit(pool_jvp_z(w.w0, w.w1, w.w2, trow(tp, H, k), e.m) * kPoolJvpUp, bitsN);
+  }
+  template <int KD>
+  __device__ __forceinline__ void jvp_walks(const PoolLane&, const Stats&, const PoolTan<KD>&, const double* const (&)[KD],
+                                            const bool (&)[KD], Tan<KD>&) const {}
+  template <int KD>
+  __device__ __forceinline__ double jvp_dn(const Row&, const Row&, double dz, double, const Stats&, const Tan<KD>&, int, int) const {
+    return dz;
+  }
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -421,6 +515,211 @@ __device__ __forceinline__ void pool_vjp_finish_body(const PoolArgs& a, const Po
   }
 }
 
+// The forward mode's max pass: pool_max_kernel's word (the LayerNorm's: and r_max, as pool_ln_max_kernel) and, per direction,
+// the largest |tq_i| and |tu_i| of the environment as bit patterns into t.tmax (a non-finite one saturates its word: that
+// direction of that environment is NaN).  x, v and every direction's d_x, d_v are read once.  Grid: the passes'.
+template <typename Layer>
+__device__ __forceinline__ void pool_jvp_max_body(const PoolArgs& a, const PoolJvpArgs& t, const Layer& layer,
+                                                  unsigned long long* __restrict__ rmax) {
+  const int env = blockIdx.y;
+  const double* __restrict__ xe = a.x + (size_t)env * a.ld;
+  const double* __restrict__ ve = a.v + (size_t)env * a.ld;
+  long long t0, t1;
+  pool_range(a, t0, t1);
+  unsigned long long mb = 0ull, rb = 0ull, qb[kPoolMaxDirs], ub[kPoolMaxDirs];
+#pragma unroll
+  for (int d = 0; d < kPoolMaxDirs; ++d) qb[d] = ub[d] = 0ull;
+  for (long long tc = t0; tc < t1; tc += (long long)POOL_BLOCK * kPoolTiles) {
+    if constexpr (Layer::kRmax) {
+      PoolLane q;
+      pool_load(a, xe, ve, tc, t1, q);
+      typename Layer::Stats st;
+      layer.prepare(q, st);
+#pragma unroll
+      for (int j = 0; j < kPoolPerLane; ++j) {
+        if (!q.on[j]) continue;
+        mom_max_bits(mb, fabs(q.u[j]));
+        if (!pool_finite(q.c[j])) mb = kMomInfBits;        // (cos of a non-finite q is NaN)
+        mom_max_bits(rb, st.r[j]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kPoolTiles; ++j) {
+      const long long tt = tc + (long long)j * POOL_BLOCK + threadIdx.x;
+      if (tt >= t1) continue;
+      if constexpr (!Layer::kRmax) {
+        const pic_v2d xt = pool_tile(xe, tt, a.N), vt = pool_tile(ve, tt, a.N);     // (a slot beyond N holds 0)
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+          mom_max_bits(mb, fabs(vt[m] * a.v_scale));
+          if (!pool_finite((kTwoPi * xt[m]) / a.L)) mb = kMomInfBits;
+        }
+      }
+#pragma unroll
+      for (int d = 0; d < kPoolMaxDirs; ++d) {
+        if (d >= t.K) continue;                            // (uniform)
+        const size_t row = ((size_t)d * t.num_envs + env) * a.N;
+        const pic_v2d dx = t.d_x ? pool_tile(t.d_x + row, tt, a.N) : pic_v2d{0.0, 0.0};
+        const pic_v2d dv = t.d_v ? pool_tile(t.d_v + row, tt, a.N) : pic_v2d{0.0, 0.0};
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+          mom_max_bits(qb[d], fabs((kTwoPi * dx[m]) / a.L));
+          mom_max_bits(ub[d], fabs(dv[m] * a.v_scale));
+        }
+      }
+    }
+  }
+  block_max_to(__longlong_as_double((long long)mb), a.umax + env);
+  if constexpr (Layer::kRmax) block_max_to(__longlong_as_double((long long)rb), rmax + env);
+#pragma unroll
+  for (int d = 0; d < kPoolMaxDirs; ++d) {
+    if (d >= t.K) continue;
+    block_max_to(__longlong_as_double((long long)qb[d]), t.tmax + ((size_t)0 * t.K + d) * t.num_envs + env);
+    block_max_to(__longlong_as_double((long long)ub[d]), t.tmax + ((size_t)1 * t.K + d) * t.num_envs + env);
+  }
+}
+
+// The forward mode's pass: grid (workgroups per environment, environments, groups of KD directions).  The forward's pass with
+// the activation's derivative in place of the activation: cos, sin, u, the layer's statistics and a_ik are computed once per
+// particle (and k) and serve every direction of the group, whose tangents tq, tu a lane keeps in registers.  Per k and
+// direction the term a_ik dn_ik (dn from dz: the layer's) is rounded to an integer in the unit of that (direction, k) and
+// summed like the forward's.  LDS: KD H unit words and sums.  A direction that is NaN as a whole deposits nothing.
+template <typename Layer, int KD>
+__device__ __forceinline__ void pool_jvp_body(const PoolArgs& a, const PoolJvpArgs& t, const Layer& layer) {
+  __shared__ unsigned long long sums[KD * kPoolMaxHidden];
+  __shared__ int unit[KD * kPoolMaxHidden];
+  const int env = blockIdx.y, H = a.H, lane = threadIdx.x & 63, d0 = blockIdx.z * KD;
+  const unsigned long long mb = a.umax[env];
+  if (mb >= kMomInfBits) return;                           // (uniform: the finishing kernel writes NaN)
+  const double* __restrict__ xe = a.x + (size_t)env * a.ld;
+  const double* __restrict__ ve = a.v + (size_t)env * a.ld;
+  const double umx = __longlong_as_double((long long)mb);
+  if (layer.env_bad(nullptr, umx)) return;                 // (uniform, the same)
+  const double* tp[KD];
+  bool live[KD];
+  bool any = false;
+#pragma unroll
+  for (int d = 0; d < KD; ++d) {                           // (everything here is uniform)
+    const int dir = d0 + d;
+    PoolJvpMax m{umx, 0.0, 0.0};
+    live[d] = dir < t.K && pool_jvp_max(t, dir, env, umx, m);
+    tp[d] = live[d] ? pool_jvp_params(a, t, dir, env) : nullptr;
+    const PoolJvpEnv e = layer.jvp_env(tp[d], m, env);     // (every thread: it may hold barriers)
+    for (int k = threadIdx.x; k < H; k += POOL_BLOCK) {
+      sums[d * H + k] = 0ull;
+      unit[d * H + k] = live[d] ? layer.jvp_unit(k, tp[d], e) : kPoolSkip;
+    }
+    any = any || live[d];
+  }
+  if (!any) return;
+  __syncthreads();
+  long long t0, t1;
+  pool_range(a, t0, t1);
+  const bool is_tanh = a.activation == PIC_ACT_TANH;
+  for (long long tc = t0; tc < t1; tc += (long long)POOL_BLOCK * kPoolTiles) {
+    PoolLane q;
+    pool_load(a, xe, ve, tc, t1, q);
+    typename Layer::Stats st;
+    layer.prepare(q, st);
+    PoolTan<KD> tn;
+#pragma unroll
+    for (int d = 0; d < KD; ++d) {
+      const size_t row = ((size_t)(d0 + d) * t.num_envs + env) * a.N;
+#pragma unroll
+      for (int j = 0; j < kPoolTiles; ++j) {
+        const long long tt = tc + (long long)j * POOL_BLOCK + threadIdx.x;
+        const bool have = live[d] && tt < t1;
+        const pic_v2d dx = have && t.d_x ? pool_tile(t.d_x + row, tt, a.N) : pic_v2d{0.0, 0.0};
+        const pic_v2d dv = have && t.d_v ? pool_tile(t.d_v + row, tt, a.N) : pic_v2d{0.0, 0.0};
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+          tn.tq[d][2 * j + m] = (kTwoPi * dx[m]) / a.L;
+          tn.tu[d][2 * j + m] = dv[m] * a.v_scale;
+        }
+      }
+    }
+    typename Layer::template Tan<KD> lt;
+    layer.template jvp_walks<KD>(q, st, tn, tp, live, lt);
+    for (int k = 0; k < H; ++k) {
+      int ue[KD];
+      bool on = false;
+#pragma unroll
+      for (int d = 0; d < KD; ++d) {
+        ue[d] = unit[d * H + k];
+        on = on || pool_on(ue[d]);
+      }
+      if (!on) continue;                                   // (uniform)
+      const typename Layer::Row w = layer.row(k);
+      typename Layer::Row tw[KD];
+      long long part[KD];
+#pragma unroll
+      for (int d = 0; d < KD; ++d) {
+        tw[d] = Layer::trow(tp[d], H, k);
+        part[d] = 0;
+      }
+#pragma unroll
+      for (int j = 0; j < kPoolPerLane; ++j) {
+        double y;
+        const double act = pool_dact(layer.arg(w, q, st, j, y), is_tanh);
+#pragma unroll
+        for (int d = 0; d < KD; ++d) {
+          if (!pool_on(ue[d])) continue;                   // (uniform)
+          const double dz = pool_dz(w.w0, w.w1, w.w2, tw[d], q.c[j], q.s[j], q.u[j], tn.tq[d][j], tn.tu[d][j]);
+          const double term = act * layer.template jvp_dn<KD>(w, tw[d], dz, y, st, lt, d, j);
+          if (q.on[j]) part[d] += __double2ll_rn(ldexp(term, -ue[d]));
+        }
+      }
+#pragma unroll
+      for (int d = 0; d < KD; ++d) {
+        if (!pool_on(ue[d])) continue;
+        const long long s = wave_sum_i64(part[d]);
+        if (lane == 0 && s) atomicAdd(sums + d * H + k, (unsigned long long)s);
+      }
+    }
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < KD * H; c += POOL_BLOCK) {
+    const int d = c / H, k = c - d * H;
+    const unsigned long long s = sums[c];
+    if (s) atomicAdd(a.acc + ((size_t)(d0 + d) * t.num_envs + env) * H + k, s);      // (a direction beyond K deposited nothing)
+  }
+}
+
+// One workgroup per environment, direction after direction: the integer sums to d_out [K][env][H] = sum / N; +0 where the
+// bound is zero, NaN for a unit word kPoolNan, for a direction whose tq or tu is not finite and for an environment that is NaN
+// as a whole; the accumulators and every max word of the environment are cleared behind the read.
+template <typename Layer>
+__device__ __forceinline__ void pool_jvp_finish_body(const PoolArgs& a, const PoolJvpArgs& t, const Layer& layer,
+                                                     double* __restrict__ d_out) {
+  const int env = blockIdx.x, H = a.H;
+  const unsigned long long mb = a.umax[env];
+  const bool finite = mb < kMomInfBits;
+  const double umx = finite ? __longlong_as_double((long long)mb) : 0.0;
+  const bool bad = layer.env_bad(nullptr, umx) || !finite;
+  for (int dir = 0; dir < t.K; ++dir) {
+    PoolJvpMax m;
+    const bool live = pool_jvp_max(t, dir, env, umx, m) && !bad;
+    if (!live) m = PoolJvpMax{umx, 0.0, 0.0};
+    const double* __restrict__ tp = pool_jvp_params(a, t, dir, env);
+    const PoolJvpEnv e = layer.jvp_env(tp, m, env);
+    for (int k = threadIdx.x; k < H; k += POOL_BLOCK) {
+      const size_t o = ((size_t)dir * t.num_envs + env) * H + k;
+      const int ue = live ? layer.jvp_unit(k, tp, e) : kPoolNan;
+      double r = 0.0;
+      if (ue == kPoolNan) r = pool_nan();
+      else if (ue != kPoolSkip) r = ldexp((double)(long long)a.acc[o], ue) / (double)a.N;
+      d_out[o] = r;
+      a.acc[o] = 0ull;
+    }
+  }
+  __syncthreads();                                         // (every lane has read the max words)
+  if (threadIdx.x == 0) {
+    a.umax[env] = 0ull;
+    layer.clear(env);
+  }
+  for (int c = threadIdx.x; c < 2 * t.K; c += POOL_BLOCK) t.tmax[(size_t)c * t.num_envs + env] = 0ull;
+}
+
 __global__ __launch_bounds__(POOL_BLOCK) void pool_kernel(PoolArgs a) { pool_fwd_body(a, PoolPlain(a, blockIdx.y)); }
 
 __global__ __launch_bounds__(POOL_BLOCK) void pool_finish_kernel(PoolArgs a, double* __restrict__ out) {
@@ -435,6 +734,20 @@ __global__ __launch_bounds__(POOL_BLOCK) void pool_vjp_kernel(PoolArgs a, PoolVj
 __global__ __launch_bounds__(POOL_BLOCK) void pool_vjp_finish_kernel(PoolArgs a, PoolVjpArgs g, double* __restrict__ gE) {
   PoolPlain layer(a, blockIdx.x);
   pool_vjp_finish_body(a, g, layer, gE);
+}
+
+constexpr int kPoolJvpDirs = 4;          // directions of a group of pool_jvp_kernel (the largest without scratch)
+
+__global__ __launch_bounds__(POOL_BLOCK) void pool_jvp_max_kernel(PoolArgs a, PoolJvpArgs t) {
+  pool_jvp_max_body(a, t, PoolPlain(a, blockIdx.y), nullptr);
+}
+
+__global__ __launch_bounds__(POOL_BLOCK) void pool_jvp_kernel(PoolArgs a, PoolJvpArgs t) {
+  pool_jvp_body<PoolPlain, kPoolJvpDirs>(a, t, PoolPlain(a, blockIdx.y));
+}
+
+__global__ __launch_bounds__(POOL_BLOCK) void pool_jvp_finish_kernel(PoolArgs a, PoolJvpArgs t, double* __restrict__ d_out) {
+  pool_jvp_finish_body(a, t, PoolPlain(a, blockIdx.x), d_out);
 }
 
 }  // namespace

@@ -1,10 +1,10 @@
 // pic_pool_ln.h -- pooled particle features with a LayerNorm inside the per-particle layer (include/picstep.h: pic_pool_ln,
-// pic_pool_ln_vjp): per environment
+// pic_pool_ln_vjp; pic_pool_ln_jvp: 7t): per environment
 //   out_k = (1/N) sum_i act(gamma_k y_ik + beta_k),   y_ik = (z_ik - mu_i) r_i,   r_i = 1 / sqrt(var_i + eps)
 // with pic_pool's z_ik and mu_i, var_i the mean and the biased variance of z_i. over the H units.  The passes are pic_pool.h's
 // skeleton with the layer type PoolLn: this file holds only what is the LayerNorm's.  z is three multiply-adds and is recomputed
 // in every walk, so nothing of size [H] is kept per particle.  New are the walks before the terms: sum z, then sum d^2 (forward,
-// and the VJP's max pass: r_max), and in the VJP one more for m1 and m2.  -ffp-contract=off.
+// and the VJP's max pass: r_max), in the VJP one more for m1 and m2, in the JVP two more for dmu and p.  -ffp-contract=off.
 #pragma once
 #include "pic_pool.h"
 
@@ -15,7 +15,7 @@ constexpr double kLnVjpUp = 0x1.0000000001p+0;         // 1 + 2^-40: above the r
 constexpr double kLnOverflow = 0x1p+500;               // a bound of |z| above this: the environment is NaN
 
 struct PoolLnArgs {
-  unsigned long long* rmax;    // [env] bit pattern of max r (VJP; zero between calls), or null
+  unsigned long long* rmax;    // [env] bit pattern of max r (VJP, JVP; zero between calls), or null
   double eps, Hd, sqrtH;       // Hd = (double)H, sqrtH = sqrt(Hd)
 };
 
@@ -105,6 +105,24 @@ __device__ __forceinline__ double ln_dmax(const double* __restrict__ p, const do
   return __longlong_as_double((long long)word);
 }
 
+// Z_max = max_k Z_k of a (direction, environment) through an LDS word (tp: the direction's tangent parameters, null = 0); a Z_k
+// that is not finite saturates it.  The same value in every thread of the workgroup (three barriers).
+__device__ __forceinline__ double ln_jvp_zmax(const double* __restrict__ p, const double* __restrict__ tp, int H, const PoolJvpMax& mx) {
+  __shared__ unsigned long long word;
+  if (threadIdx.x == 0) word = 0ull;
+  __syncthreads();
+  unsigned long long m = 0ull;
+  for (int k = threadIdx.x; k < H; k += POOL_BLOCK) {
+    const LnRow d = tp ? ln_row(tp, H, k) : LnRow{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    mom_max_bits(m, pool_jvp_z(p[3 * k], p[3 * k + 1], p[3 * k + 2], d, mx));
+  }
+  if (m) atomicMax(&word, m);
+  __syncthreads();
+  const double zmax = __longlong_as_double((long long)word);
+  __syncthreads();                                         // (the next direction's call clears the word)
+  return zmax;
+}
+
 // The LayerNorm's layer type for pic_pool.h's skeleton (what a layer supplies: there).  The VJP has six sums per unit (g_W_k*
 // and g_b_k in one unit word, g_gamma_k and g_beta_k in one each) and walks k once more before the skeleton's walk.
 struct PoolLn {
@@ -185,6 +203,81 @@ struct PoolLn {
     return ((dy - st.m1[j]) - y * st.m2[j]) * st.r[j];
   }
   __device__ __forceinline__ void clear(int env) const { n.rmax[env] = 0ull; }
+
+  // forward mode (pic_pool_ln_jvp): the tangent row of unit k, Z_max and r_max of a (direction, environment), the unit word of
+  // d_out_k, the two walks over k for dmu_i and p_i of every direction of a group, and dn from dz
+  static constexpr bool kRmax = true;
+  template <int KD> struct Tan { double dmu[KD][kPoolPerLane], p[KD][kPoolPerLane]; };
+  __device__ __forceinline__ static Row trow(const double* __restrict__ tp, int H, int k) {
+    return tp ? ln_row(tp, H, k) : LnRow{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  }
+  __device__ __forceinline__ PoolJvpEnv jvp_env(const double* __restrict__ tp, const PoolJvpMax& m, int env) const {
+    return PoolJvpEnv{m, ln_jvp_zmax(p, tp, H, m), __longlong_as_double((long long)n.rmax[env])};
+  }
+  // |dgamma_k| sqrt(H) + |gamma_k| (Z_k + (1 + sqrt(H)) Z_max) r_max + |dbeta_k|, rounded up
+  __device__ __forceinline__ int jvp_unit(int k, const double* __restrict__ tp, const PoolJvpEnv& e) const {
+    const Row w = row(k), d = trow(tp, H, k);
+    if (!(pool_finite(w.g) && pool_finite(w.be) && pool_finite(d.g) && pool_finite(d.be))) return kPoolNan;
+    const double Zk = pool_jvp_z(w.w0, w.w1, w.w2, d, e.m);
+    const double bz = (Zk + (1.0 + n.sqrtH) * e.zmax) * e.rmx;
+    return pool_unit(((fabs(d.g) * n.sqrtH + fabs(w.g) * bz) + fabs(d.be)) * kPoolJvpUp, bitsN);
+  }
+  template <int KD>
+  __device__ __forceinline__ void jvp_walks(const PoolLane& q, const Stats& st, const PoolTan<KD>& tn, const double* const (&tp)[KD],
+                                            const bool (&live)[KD], Tan<KD>& lt) const {
+    double acc[KD][kPoolPerLane];
+#pragma unroll
+    for (int d = 0; d < KD; ++d)
+#pragma unroll
+      for (int j = 0; j < kPoolPerLane; ++j) acc[d][j] = 0.0;
+    for (int k = 0; k < H; ++k) {
+      const Row w = row(k);
+#pragma unroll
+      for (int d = 0; d < KD; ++d) {
+        if (!live[d]) continue;                            // (uniform)
+        const Row tw = trow(tp[d], H, k);
+#pragma unroll
+        for (int j = 0; j < kPoolPerLane; ++j)
+          acc[d][j] = acc[d][j] + pool_dz(w.w0, w.w1, w.w2, tw, q.c[j], q.s[j], q.u[j], tn.tq[d][j], tn.tu[d][j]);
+      }
+    }
+#pragma unroll
+    for (int d = 0; d < KD; ++d)
+#pragma unroll
+      for (int j = 0; j < kPoolPerLane; ++j) {
+        lt.dmu[d][j] = acc[d][j] / n.Hd;
+        acc[d][j] = 0.0;
+      }
+    for (int k = 0; k < H; ++k) {
+      const Row w = row(k);
+      double y[kPoolPerLane];
+#pragma unroll
+      for (int j = 0; j < kPoolPerLane; ++j) y[j] = (pool_pre(w.w0, w.w1, w.w2, w.b, q.c[j], q.s[j], q.u[j]) - st.mu[j]) * st.r[j];
+#pragma unroll
+      for (int d = 0; d < KD; ++d) {
+        if (!live[d]) continue;
+        const Row tw = trow(tp[d], H, k);
+#pragma unroll
+        for (int j = 0; j < kPoolPerLane; ++j) {
+          const double e = pool_dz(w.w0, w.w1, w.w2, tw, q.c[j], q.s[j], q.u[j], tn.tq[d][j], tn.tu[d][j]) - lt.dmu[d][j];
+          acc[d][j] = acc[d][j] + y[j] * e;
+        }
+      }
+    }
+#pragma unroll
+    for (int d = 0; d < KD; ++d)
+#pragma unroll
+      for (int j = 0; j < kPoolPerLane; ++j) lt.p[d][j] = acc[d][j] / n.Hd;
+  }
+  // dn_ik = (dgamma_k y_ik + gamma_k dy_ik) + dbeta_k,   dy_ik = (e_ik - y_ik p_i) r_i,   e_ik = dz_ik - dmu_i
+  template <int KD>
+  __device__ __forceinline__ double jvp_dn(const Row& w, const Row& tw, double dz, double y, const Stats& st, const Tan<KD>& lt, int d,
+                                           int j) const {
+    const double e = dz - lt.dmu[d][j];
+    const double dy = (e - y * lt.p[d][j]) * st.r[j];
+    const double gy = tw.g * y, gd = w.g * dy;
+    return (gy + gd) + tw.be;
+  }
 };
 
 // The VJP's max pass: pool_max_kernel's word (max |u|, saturated by a non-finite u or q) and next to it the environment's largest
@@ -228,6 +321,22 @@ __global__ __launch_bounds__(POOL_BLOCK) void pool_ln_vjp_kernel(PoolArgs a, Poo
 __global__ __launch_bounds__(POOL_BLOCK) void pool_ln_vjp_finish_kernel(PoolArgs a, PoolLnArgs n, PoolVjpArgs g, double* __restrict__ gE) {
   PoolLn layer(a, n, blockIdx.x);
   pool_vjp_finish_body(a, g, layer, gE);
+}
+
+// directions of a group of pool_ln_jvp_kernel: with 4 hipcc reports no scratch either, but 30 AGPRs of spills and
+// one wave per SIMD, and the call measured 1.4 x slower
+constexpr int kPoolLnJvpDirs = 2;
+
+__global__ __launch_bounds__(POOL_BLOCK) void pool_ln_jvp_max_kernel(PoolArgs a, PoolLnArgs n, PoolJvpArgs t) {
+  pool_jvp_max_body(a, t, PoolLn(a, n, blockIdx.y), n.rmax);
+}
+
+__global__ __launch_bounds__(POOL_BLOCK) void pool_ln_jvp_kernel(PoolArgs a, PoolLnArgs n, PoolJvpArgs t) {
+  pool_jvp_body<PoolLn, kPoolLnJvpDirs>(a, t, PoolLn(a, n, blockIdx.y));
+}
+
+__global__ __launch_bounds__(POOL_BLOCK) void pool_ln_jvp_finish_kernel(PoolArgs a, PoolLnArgs n, PoolJvpArgs t, double* __restrict__ d_out) {
+  pool_jvp_finish_body(a, t, PoolLn(a, n, blockIdx.x), d_out);
 }
 
 }  // namespace

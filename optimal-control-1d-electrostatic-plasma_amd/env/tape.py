@@ -545,9 +545,11 @@ class TapePIC:
         return out if batched else out[0]
 
     # -- pooled particle features (pic_pool*; pic_pool_ln*, 7s) -----------------------------
-    def _pool_call(self, who, W, b, activation, v_scale, x, v, on_device, cot=None, gamma=None, beta=None, eps=1e-5, period=None):
+    def _pool_call(self, who, W, b, activation, v_scale, x, v, on_device, cot=None, gamma=None, beta=None, eps=1e-5, period=None,
+                   then=None):
         """The memory, the spec and the arrays of one pool call; every shape is checked here, before the device is touched.
-        With gamma and beta the spec is pic_pool_ln's and the parameters are (W, b, gamma, beta)."""
+        With gamma and beta the spec is pic_pool_ln's and the parameters are (W, b, gamma, beta).  `then`: the caller's own
+        checks, run behind these and before the device is touched."""
         E, N = self.num_envs, self.N
         if activation not in _abi.ACTIVATIONS:
             raise ValueError(f"{who}: activation must be one of {sorted(_abi.ACTIVATIONS)}, not {activation!r}")
@@ -579,6 +581,8 @@ class TapePIC:
             raise ValueError(f"{who}: cot must be [num_envs, H] = {[E, H]}, not {list(np.shape(cot))}")
         if not np.isfinite(v_scale):
             raise ValueError(f"{who}: v_scale must be finite, not {v_scale!r}")
+        if then is not None:
+            then()
         mem = Mem.of(self, W, b, x, v, cot, gamma, beta, force_device=on_device)
         lead = (E,) if per_env else ()
         parts = [mem.f64(W).reshape(lead + (3 * H,)), mem.f64(b)] + ([mem.f64(gamma), mem.f64(beta)] if ln else [])
@@ -642,6 +646,50 @@ class TapePIC:
             g["g_gamma"] = None if gp is None else gp[..., 4 * H:5 * H]
             g["g_beta"] = None if gp is None else gp[..., 5 * H:]
         return g
+
+    def pool_jvp(self, W, b, d_x=None, d_v=None, d_W=None, d_b=None, activation: str = "tanh", v_scale: float = 1.0, x=None, v=None,
+                 on_device: bool = False, gamma=None, beta=None, d_gamma=None, d_beta=None, eps: float = 1e-5, period=None):
+        """Directional derivatives of `pool` along tangents d_x, d_v [num_envs, N] of the particles and d_W, d_b (with gamma and
+        beta: d_gamma, d_beta too) shaped like the parameters, each None = 0 (pic_pool_jvp, pic_pool_ln_jvp) ->
+        [num_envs, H], dual to pool_vjp: sum cot . pool_jvp = g_x . d_x + g_v . d_v + g_W . d_W + ...  With a leading axis of
+        K <= 8 directions on the tangents the result is [K, num_envs, H], bit for bit what K calls of one direction give.
+        Bitwise reproducible and independent of the order of the particles.  NumPy, or a float64 CUDA tensor if an input is one
+        or with on_device."""
+        who = "pool_jvp"
+        ln = gamma is not None or beta is not None
+        if not ln and (d_gamma is not None or d_beta is not None):
+            raise ValueError(f"{who}: d_gamma and d_beta need gamma and beta")
+        given = {"d_x": d_x, "d_v": d_v, "d_W": d_W, "d_b": d_b, "d_gamma": d_gamma, "d_beta": d_beta}
+        given = {k: a if a is None or hasattr(a, "shape") else np.asarray(a) for k, a in given.items()}
+        dirs = []
+
+        def check():
+            ws, bs = tuple(np.shape(W)), tuple(np.shape(b))
+            rows = (self.num_envs, self.N)
+            dirs.append(directions(who, {"d_x": rows, "d_v": rows, "d_W": ws, "d_b": bs, "d_gamma": bs, "d_beta": bs}, given))
+
+        # (a tangent that is a CUDA tensor moves the whole call to the device, as any other input does)
+        on_device = on_device or any(getattr(a, "is_cuda", False) for a in given.values())
+        mem, spec, keep, H, per_env, x, v = self._pool_call(who, W, b, activation, v_scale, x, v, on_device, None, gamma, beta, eps,
+                                                            period, then=check)
+        K, batched = dirs[0]
+        E, N = self.num_envs, self.N
+        tx, tv = mem.f64(d_x, (K, E, N)), mem.f64(d_v, (K, E, N))
+        names = ("d_W", "d_b") + (("d_gamma", "d_beta") if ln else ())
+        tparams = None
+        if any(given[k] is not None for k in names):
+            lead = (K, E) if per_env else (K,)
+            tparams = mem.zeros(lead + ((6 if ln else 4) * H,))
+            for k, lo, n in zip(names, (0, 3 * H, 4 * H, 5 * H), (3 * H, H, H, H)):
+                if given[k] is not None:
+                    tparams[..., lo:lo + n] = mem.f64(given[k], lead + (n,))
+        out = mem.empty((K, E, H))
+        mem.enter()
+        call = self._h.pool_ln_jvp if ln else self._h.pool_jvp
+        call(spec, mem.addr(x), mem.addr(v), K, mem.addr(tx), mem.addr(tv), mem.addr(tparams), mem.kind, mem.addr(out))
+        mem.leave(self._h)
+        del keep
+        return out if batched else out[0]
 
     def _set_moments_cot(self, d_moments, T, mem):
         """The moments' cotangents of a backward onto the tape: d_moments [T, num_envs, 3, N_mesh] (row t on the state step t
