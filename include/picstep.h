@@ -982,6 +982,65 @@ int pic_pool_jvp(pic_handle* h, const pic_pool_spec* s, const void* x, const voi
 int pic_pool_ln_jvp(pic_handle* h, const pic_pool_ln_spec* s, const void* x, const void* v, int K, const void* d_x, const void* d_v,
                     const double* d_params, int mem_kind, double* d_out);
 
+/* ---- The DeepSets particle actor in closed loop on the device (additive to ABI 5) --------------------------------
+ * a = pi(x, v): the pooled particle features of pic_pool or pic_pool_ln (exactly one of `pool` / `pool_ln` is given: the
+ * per-particle layer and the mean), then a head of 1..6 linear layers, with a LayerNorm and an activation behind every layer
+ * but the last, evaluated by one workgroup per environment.  Float64 throughout, every product rounded before its sum (no fused
+ * multiply-add).
+ *   h_0 = f, the pooled features [num_envs][H]: the bits pic_pool / pic_pool_ln return for the same spec and particles.
+ *   layer l: y_i = b_i; then, for k ascending, y_i = y_i + W[i][k] * h_l[k]   (pic_policy's rule).
+ *   With layernorm, behind every layer but the last, over the layer's n outputs (pic_pool_ln's formulas):
+ *     mu = (sum_i y_i) / n  (from +0 over ascending i)      d_i = y_i - mu      var = (sum_i d_i d_i) / n  (the same)
+ *     r = 1 / sqrt(var + ln_eps)                            n_i = gamma_i (d_i r) + beta_i   (the product rounded first)
+ *   Then h_{l+1} = tanh(.) (PIC_ACT_TANH) or . > 0 ? . : +0.0 (PIC_ACT_RELU) of n_i (of y_i without layernorm).
+ *   z = the last layer's y.  With noise: u = z + std_i * eps_i (the product rounded first; std NULL = 1); without: u = z.
+ *   squash 0: a = u.  squash 1: a = action_shift + action_scale * tanh(u)   (the product rounded first).
+ * Both LayerNorm sums run over ascending i and are never split, so the result does not depend on the launch.  The library
+ * draws nothing: eps is the caller's.  Non-finite input: the features follow pic_pool's / pic_pool_ln's rule (NaN in every
+ * feature of an environment with a non-finite particle, and of no other); the head is plain IEEE arithmetic on them, so NaN
+ * passes through linear layers, LayerNorms and tanh, while the comparison of PIC_ACT_RELU sends a NaN to +0 as pic_policy's does.
+ * params: per layer W [out][in] row-major, b [out] and -- with layernorm, not behind the last layer -- gamma [out], beta [out];
+ * P doubles in all, one vector or [num_envs][P] with per_env.  mem_kind covers params, features, x, v, noise, std and the three
+ * outputs; the pool spec's params stay in its own params_mem_kind memory.
+ *
+ * pic_actor_eval: the actor once, for every environment, on one of three sources: `features` [num_envs][H] (the head alone
+ * runs; the pool spec is checked but its params are not read); x and v [num_envs][N] as pic_pool takes them; or all three NULL:
+ * the stored particles under pic_pool's rules (float64 handles only, after pic_reset, not inside a staged step).  noise
+ * [num_envs][2M] or NULL; std [2M] or NULL.  features_out [num_envs][H], pre_out (u) and actions_out (a) [num_envs][2M]: any
+ * may be NULL.  It touches no particles, fields, energies or tape state and is allowed under an open tape.
+ *
+ * pic_step_actor: nsteps closed-loop steps without returning to the host between them.  Step s is pic_actor_eval on the stored
+ * particles step s-1 left, then the one step pic_step_actions(a_s on the device, 1) makes: the call gives the bits of the host
+ * loop pic_pool[_ln](x = v = NULL) -> pic_actor_eval(features) -> pic_step_actions, on both schedules, CIC or TSC, every
+ * integrator, recorder on or off.  Per step: the pool's max pass and pass, the actor's kernel (which finishes the pool's sums,
+ * writes the feature row once and runs the head on it) and one step's launches; the pool call is begun once per call.  noise
+ * [nsteps][num_envs][2M] or NULL; features_out [nsteps][num_envs][H]; pre_out, actions_out [nsteps][num_envs][2M]; hist: NULL,
+ * or host [nsteps][3][num_envs] as pic_step_actions_traj.  Waiting: as pic_step_policy (PIC_HOST outputs or hist: one wait at
+ * the end; PIC_DEVICE without hist: asynchronous on the handle's stream).
+ *
+ * Everything is refused before anything is enqueued, with the state untouched and the reason in pic_last_error.  PIC_EINVAL:
+ * a NULL actor; both or neither of pool / pool_ln; whatever pic_pool / pic_pool_ln refuse in their spec, with their messages;
+ * n_layers outside 1..6; a width outside 1..256; width[0] != hidden; width[n_layers] != 2M; layernorm, squash or per_env other
+ * than 0 / 1; an unknown activation; with layernorm an ln_eps that is not finite and > 0; a non-finite action_scale or
+ * action_shift; NULL params; a bad mem_kind; nsteps < 0; features together with x or v; exactly one of x / v; a handle that is
+ * not float64 with float64 positions where the stored particles are read (pic_pool's message).  PIC_ESTATE: no actuator
+ * (pic_set_actuator); before pic_reset or inside a staged step where the stored particles are read; pic_step_actor while a tape
+ * is open (there is no taped entry: a torch policy on the tape is the route). */
+typedef struct pic_actor {
+  const pic_pool_spec*    pool;      /* exactly one of pool / pool_ln is non-NULL: the per-particle layer and the mean (7r / 7s) */
+  const pic_pool_ln_spec* pool_ln;
+  int32_t n_layers;                  /* 1..6 linear layers behind the mean */
+  int32_t width[7];                  /* width[0] = the pool's hidden; width[n_layers] = 2 max_mode of pic_set_actuator; each 1..256 */
+  int32_t layernorm;                 /* 0 / 1: a LayerNorm(width[l+1], ln_eps) behind every linear layer but the last */
+  int32_t activation, squash, per_env;
+  double  ln_eps, action_scale, action_shift;
+  const double* params;              /* per layer: W [out][in] row-major, b [out], and (layernorm, not the last layer) gamma [out], beta [out] */
+} pic_actor;
+int pic_actor_eval(pic_handle* h, const pic_actor* a, const double* features, const void* x, const void* v, const double* noise,
+                   const double* std, int mem_kind, double* features_out, double* pre_out, double* actions_out);
+int pic_step_actor(pic_handle* h, const pic_actor* a, const double* noise, const double* std, int mem_kind, int nsteps,
+                   double* features_out, double* pre_out, double* actions_out, double* hist);
+
 int pic_sync(pic_handle* h);
 /* Number of particle positions found non-finite or out of range by the last sweeps (0 = healthy).  Counts the state's
  * particles only: the positions of pic_eval_field / pic_compute_E probes never add to it. */

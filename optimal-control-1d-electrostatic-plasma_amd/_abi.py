@@ -111,6 +111,15 @@ class PicPoolLnSpec(C.Structure):
                 ("v_scale", C.c_double), ("eps", C.c_double), ("period", C.c_double), ("params", C.c_void_p)]
 
 
+class PicActor(C.Structure):
+    """pic_actor (include/picstep.h): the pooled particle features (exactly one of pool / pool_ln points to its
+    spec) and a head of 1..6 linear layers; params is an address in the call's memory."""
+    _fields_ = [("pool", C.POINTER(PicPoolSpec)), ("pool_ln", C.POINTER(PicPoolLnSpec)), ("n_layers", C.c_int32),
+                ("width", C.c_int32 * 7), ("layernorm", C.c_int32), ("activation", C.c_int32), ("squash", C.c_int32),
+                ("per_env", C.c_int32), ("ln_eps", C.c_double), ("action_scale", C.c_double), ("action_shift", C.c_double),
+                ("params", C.c_void_p)]
+
+
 class PicError(RuntimeError):
     pass
 
@@ -209,6 +218,8 @@ SIGNATURES = {
     "pic_pool_ln_vjp": [_vp, C.POINTER(PicPoolLnSpec), _vp, _vp, _vp, C.c_int, _vp, _vp, _vp],
     "pic_pool_jvp": [_vp, C.POINTER(PicPoolSpec), _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp],
     "pic_pool_ln_jvp": [_vp, C.POINTER(PicPoolLnSpec), _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp],
+    "pic_actor_eval": [_vp, C.POINTER(PicActor), _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp],
+    "pic_step_actor": [_vp, C.POINTER(PicActor), _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp],
     "pic_sync": [_vp],
     "pic_bad_count": [_vp, _i64p],
     "pic_last_error": [_vp],
@@ -666,6 +677,18 @@ class Handle:
         """pic_step_policy on addresses (0 or None = NULL) in `kind` memory; hist: a host array [nsteps][3][num_envs] or None."""
         self._chk(self.lib.pic_step_policy(self._h, C.byref(spec), *_ptrs(noise, std), int(kind), int(nsteps),
                                            *_ptrs(obs_out, pre_out, actions_out), _ptr(hist)))
+
+    # -- the DeepSets particle actor in closed loop (DESIGN.md 7u) ---------------------------------------------------------------
+    def actor_eval(self, spec, features, x, v, noise, std, kind, features_out, pre_out, actions_out):
+        """pic_actor_eval on addresses (0 or None = NULL) in `kind` memory; spec: a PicActor whose params is an address in the
+        same memory and whose pool / pool_ln points to a live spec."""
+        self._chk(self.lib.pic_actor_eval(self._h, C.byref(spec), *_ptrs(features, x, v, noise, std), int(kind),
+                                          *_ptrs(features_out, pre_out, actions_out)))
+
+    def step_actor(self, spec, noise, std, kind, nsteps, features_out, pre_out, actions_out, hist=None):
+        """pic_step_actor on addresses (0 or None = NULL) in `kind` memory; hist: a host array [nsteps][3][num_envs] or None."""
+        self._chk(self.lib.pic_step_actor(self._h, C.byref(spec), *_ptrs(noise, std), int(kind), int(nsteps),
+                                          *_ptrs(features_out, pre_out, actions_out), _ptr(hist)))
 
     # -- policy gradients on the device (DESIGN.md 7p) -------------------------------------------------------------------------
     def policy_vjp(self, spec, obs, pre, cot_actions, kind, g_params, g_obs, g_pre):

@@ -1,3 +1,4 @@
 from .actuator import E_field
 from .reward import Reward
 from .policy import MLPPolicy
+from .actor import ParticleActor

@@ -347,6 +347,38 @@ inline size_t policy_parts(Carver c, const BlockDims& d, const PolicyCallShape& 
   return c.at;
 }
 
+// ---- the particle actor's calls on the same block (host_actor.h); d: the head's dims (P, per_env) ------------------
+struct ActorCallShape {
+  size_t nsteps = 1, H = 0;           // steps of the call (pic_actor_eval: 1); the pool's hidden units
+  bool host = false, stepping = false;
+  bool particles = false;             // the feature rows come from the pool's sums (else: features are given)
+  bool std = false, noise = false;                                            // inputs given
+  bool features_out = false, pre_out = false, actions_out = false, hist = false;      // outputs wanted
+};
+
+// pic_actor_eval, pic_step_actor: the per-step rows of the actions the steps read, the feature rows the kernel writes where they
+// do not go straight to the caller's device memory (a row feeds the head, so there always is one where the sums are finished),
+// the energies' record, and -- for a call in host memory -- the device copies of its inputs and outputs
+struct ActorCallViews {
+  double *d_act = nullptr, *d_feat = nullptr, *d_hist = nullptr, *d_params = nullptr, *d_std = nullptr, *d_noise = nullptr,
+         *d_features = nullptr, *d_pre_out = nullptr;
+};
+
+inline size_t actor_parts(Carver c, const BlockDims& d, const ActorCallShape& s, ActorCallViews& k) {
+  const size_t T = s.nsteps, frow = d.num_envs * s.H, arow = d.arow();
+  const bool to_caller = !s.host && s.features_out;       // the kernel writes the caller's rows itself
+  c.take(k.d_act, s.stepping ? T * arow : (s.host && s.actions_out ? arow : 0));
+  c.take(k.d_feat, (s.particles ? !to_caller : s.host && s.features_out) ? T * frow : 0);
+  c.take(k.d_hist, s.hist ? T * 3 * d.num_envs : 0);
+  if (!s.host) return c.at;
+  c.take(k.d_params, d.params());
+  c.take(k.d_std, s.std ? 2 * d.act_modes : 0);
+  c.take(k.d_noise, s.noise ? T * arow : 0);
+  c.take(k.d_features, s.particles ? 0 : frow);
+  c.take(k.d_pre_out, s.pre_out ? T * arow : 0);
+  return c.at;
+}
+
 // pic_policy_vjp: the per-environment sums, their reduction, and -- in host memory -- the copies of its inputs and outputs
 struct PolicyVjpViews {
   double *gE = nullptr, *g = nullptr, *params = nullptr, *scale = nullptr, *obs = nullptr, *pre = nullptr, *cot = nullptr,

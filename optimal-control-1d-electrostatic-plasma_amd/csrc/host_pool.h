@@ -17,6 +17,31 @@ static const char* pool_spec_error(const pic_pool_spec* s) {
   return nullptr;
 }
 
+// the members a pic_pool_ln_spec shares with a pic_pool_spec
+static pic_pool_spec pool_ln_base(const pic_pool_ln_spec* s) {
+  return pic_pool_spec{s->hidden, s->activation, s->per_env, s->params_mem_kind, s->v_scale, s->params};
+}
+
+// what is wrong with a pic_pool_ln_spec (null: nothing): pic_pool's checks on the shared members, then its own
+static const char* pool_ln_spec_error(const pic_pool_ln_spec* s) {
+  if (!s) return "spec is NULL";
+  const pic_pool_spec base = pool_ln_base(s);
+  if (const char* bad = pool_spec_error(&base)) return bad;
+  if (!(std::isfinite(s->eps) && s->eps > 0.0)) return "eps must be finite and > 0";
+  if (!(std::isfinite(s->period) && s->period >= 0.0)) return "period must be finite and >= 0";
+  return nullptr;
+}
+
+// whether a call may read the handle's stored particles (x = v = NULL); nothing is enqueued or changed
+static int pool_stored_check(pic_handle* h, const char* who) {
+  if (h->fmt != FMT_F64)
+    return fail(h, PIC_EINVAL, std::string(who) + ": the stored particles need float64 particles with float64 positions (float32 and "
+                                                  "fixed32 are not differentiated); pass x and v");
+  if (!h->has_state) return fail(h, PIC_ESTATE, std::string(who) + ": call pic_reset first");
+  if (h->sched.mid_stage) return fail(h, PIC_ESTATE, std::string(who) + ": a staged step is in progress");
+  return PIC_OK;
+}
+
 // one call: what pool_begin makes of the arguments
 struct PoolCall {
   PoolCallShape shape;
@@ -39,13 +64,8 @@ static int pool_begin(pic_handle* h, const pic_pool_spec* s, const void* x, cons
   if (c.shape.jvp && (c.shape.K < 1 || c.shape.K > kMaxTangents))
     return fail(h, PIC_EINVAL, std::string(who) + ": need 1 <= K <= " + std::to_string(kMaxTangents));
   if (!x != !v) return fail(h, PIC_EINVAL, std::string(who) + ": x and v must both be given or both be NULL");
-  if (!x) {
-    if (h->fmt != FMT_F64)
-      return fail(h, PIC_EINVAL, std::string(who) + ": the stored particles need float64 particles with float64 positions (float32 and "
-                                                    "fixed32 are not differentiated); pass x and v");
-    if (!h->has_state) return fail(h, PIC_ESTATE, std::string(who) + ": call pic_reset first");
-    if (h->sched.mid_stage) return fail(h, PIC_ESTATE, std::string(who) + ": a staged step is in progress");
-  }
+  if (!x)
+    if (int rc = pool_stored_check(h, who)) return rc;
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   PoolCallShape& shape = c.shape; PoolViews& w = c.w; PoolArgs& a = c.a;
   const size_t E = h->cfg.num_envs, N = h->cfg.N, H = (size_t)s->hidden, P = (shape.ln ? 6 : 4) * H;
@@ -89,11 +109,8 @@ static int pool_begin(pic_handle* h, const pic_pool_spec* s, const void* x, cons
 static int pool_ln_begin(pic_handle* h, const pic_pool_ln_spec* s, const void* x, const void* v, const void* result,
                          const char* result_name, int mem_kind, const char* who, PoolCall& c) {
   if (!h) return PIC_EINVAL;
-  if (!s) return fail(h, PIC_EINVAL, std::string(who) + ": spec is NULL");
-  const pic_pool_spec base{s->hidden, s->activation, s->per_env, s->params_mem_kind, s->v_scale, s->params};
-  if (const char* bad = pool_spec_error(&base)) return fail(h, PIC_EINVAL, std::string(who) + ": " + bad);
-  if (!(std::isfinite(s->eps) && s->eps > 0.0)) return fail(h, PIC_EINVAL, std::string(who) + ": eps must be finite and > 0");
-  if (!(std::isfinite(s->period) && s->period >= 0.0)) return fail(h, PIC_EINVAL, std::string(who) + ": period must be finite and >= 0");
+  if (const char* bad = pool_ln_spec_error(s)) return fail(h, PIC_EINVAL, std::string(who) + ": " + bad);
+  const pic_pool_spec base = pool_ln_base(s);
   c.shape.ln = true;
   if (int rc = pool_begin(h, &base, x, v, result, result_name, mem_kind, who, c)) return rc;
   if (s->period > 0.0) c.a.L = s->period;

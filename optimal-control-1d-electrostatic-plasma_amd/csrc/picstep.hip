@@ -40,6 +40,7 @@
 // pic_policy.h and host_policy.h: the MLP policy of pic_policy_eval and pic_step_policy.
 // pic_pool.h and host_pool.h: the pooled particle features of pic_pool and pic_pool_vjp, as passes over a layer type;
 // pic_pool_ln.h: the layer type of pic_pool_ln and pic_pool_ln_vjp (a LayerNorm inside the per-particle layer).
+// pic_actor.h and host_actor.h: the DeepSets particle actor of pic_actor_eval and pic_step_actor (the pooled features and a head).
 
 #include <hip/hip_runtime.h>
 
@@ -81,6 +82,7 @@
 #include "pic_policy.h"
 #include "pic_pool.h"
 #include "pic_pool_ln.h"
+#include "pic_actor.h"
 
 
 // ---------------------------------------------------------------------------------------------
@@ -1855,6 +1857,8 @@ int pic_step_feedback_gain(pic_handle* h, int max_mode, const double* gain, int 
 
 // closed loops under an MLP policy (pic_policy_eval, pic_step_policy)
 #include "host_policy.h"
+// ... and under the DeepSets particle actor (pic_actor_eval, pic_step_actor)
+#include "host_actor.h"
 
 int pic_get_modes(pic_handle* h, int max_mode, double* re, double* im, int mem_kind) {
   if (!h || max_mode < 1 || max_mode >= h->cfg.Ng) return fail(h, PIC_EINVAL, "pic_get_modes: bad max_mode");

@@ -305,6 +305,67 @@ class TapePIC:
         ke, pe, per = (None, None, None) if hist is None else (hist[:, 0], hist[:, 1], hist[:, 2])
         return PolicyRollout(o, u, a, ke, pe, per)
 
+    # -- closed loops under the DeepSets particle actor (pic_actor_eval, pic_step_actor) -------------------------
+    def _actor_call(self, who, actor, T, features, x, v, noise, std, on_device):
+        """The memory, the struct and the arrays of one actor call; every shape is checked here, before the device is touched."""
+        E, N, H, nA = self.num_envs, self.N, actor.hidden, 2 * self.max_mode
+        lead = () if T is None else (T,)
+        if T is not None and T < 0:
+            raise ValueError(f"{who}: nsteps must be >= 0, not {T}")
+        if self.max_mode and actor.widths[-1] != nA:          # (without an actuator the library refuses: PIC_ESTATE)
+            raise ValueError(f"{who}: the actor's last width must be 2 max_mode of the actuator = {nA}, not {actor.widths[-1]}")
+        if actor.per_env and actor.W.shape[0] != E:
+            raise ValueError(f"{who}: a per-environment actor needs parameters for {E} environments, not {actor.W.shape[0]}")
+        if features is not None and (x is not None or v is not None):
+            raise ValueError(f"{who}: features must not be given together with x or v")
+        if (x is None) != (v is None):
+            raise ValueError(f"{who}: x and v must both be given or both be None")
+        for name, a, want in (("features", features, (E, H)), ("x", x, (E, N)), ("v", v, (E, N)), ("noise", noise, lead + (E, nA)),
+                              ("std", std, (nA,))):
+            if a is not None and tuple(np.shape(a)) != want:
+                raise ValueError(f"{who}: {name} must have shape {list(want)}, not {list(np.shape(a))}")
+        mem = Mem.of(self, actor.params, features, x, v, noise, std, force_device=on_device)
+        spec, keep = actor.spec(mem, E)
+        ins = [mem.f64(a) for a in (features, x, v, noise, std)]
+        outs = mem.empty(lead + (E, H)), mem.empty(lead + (E, nA)), mem.empty(lead + (E, nA))
+        return mem, spec, keep, ins, outs
+
+    def actor_eval(self, actor, features=None, x=None, v=None, noise=None, std=None, on_device: bool = False):
+        """`actor` (control.actor.ParticleActor) once for every environment -> (features [num_envs, H], pre, actions
+        [num_envs, 2M]): on features [num_envs, H] if given (the head alone), else on the particles x, v [num_envs, N], else on
+        the stored particles of a float64 environment -- the features are then `pool(...)`'s for the actor's pool part, bit for
+        bit.  pre is u = z + std * eps with noise = eps [num_envs, 2M] (std [2M], None = 1), or u = z; actions a = u, or
+        action_shift + action_scale tanh(u) with squash.  NumPy, or float64 CUDA tensors if an input is one or with on_device.
+        The state is not touched."""
+        mem, spec, keep, (f, x, v, noise, std), (fo, u, a) = self._actor_call("actor_eval", actor, None, features, x, v, noise, std,
+                                                                               on_device)
+        mem.enter()
+        self._h.actor_eval(spec, mem.addr(f), mem.addr(x), mem.addr(v), mem.addr(noise), mem.addr(std), mem.kind, mem.addr(fo),
+                           mem.addr(u), mem.addr(a))
+        mem.leave(self._h)
+        del keep
+        return fo, u, a
+
+    def step_actor(self, actor, nsteps: int, noise=None, std=None, history: bool = True, on_device: bool = False):
+        """nsteps closed-loop steps under `actor` in ONE call, without returning to the host between steps (pic_step_actor): step
+        s evaluates the actor on the particles step s-1 left (the stored ones for the first), then steps under its actions --
+        bit for bit the host loop `pool` -> `actor_eval(features=...)` -> `step_actions`.  noise: eps [nsteps, num_envs, 2M] (the
+        library draws nothing) or None; std [2M] or None.  -> ActorRollout(features [nsteps, num_envs, H], pre, actions
+        [nsteps, num_envs, 2M], KE, PE, PE_reward [nsteps, num_envs] NumPy -- None without history).  NumPy, or float64 CUDA
+        tensors if an input is one or with on_device (then asynchronous without history).  Float64 environments only.  Refused
+        while a tape is open: `actor.to_torch(env)` under env.grad.rollout_policy(observe="state") is the differentiable route."""
+        from ..control.actor import ActorRollout
+        T = int(nsteps)
+        mem, spec, keep, (_, _, _, noise, std), (fo, u, a) = self._actor_call("step_actor", actor, T, None, None, None, noise, std,
+                                                                               on_device)
+        hist = np.empty((T, 3, self.num_envs)) if history else None
+        mem.enter()
+        self._h.step_actor(spec, mem.addr(noise), mem.addr(std), mem.kind, T, mem.addr(fo), mem.addr(u), mem.addr(a), hist)
+        mem.leave(self._h)
+        del keep
+        ke, pe, per = (None, None, None) if hist is None else (hist[:, 0], hist[:, 1], hist[:, 2])
+        return ActorRollout(fo, u, a, ke, pe, per)
+
     # -- policy gradients on the device (pic_policy_vjp, pic_tape_step_policy, pic_tape_backward_policy; DESIGN.md 7p) -----------
     def policy_vjp(self, policy, obs, cot_actions, pre=None, on_device: bool = False):
         """The vector-Jacobian product of `policy_eval` for every environment (pic_policy_vjp): from observations obs
