@@ -15,7 +15,9 @@ from collections import namedtuple
 
 import numpy as np
 
+from . import _head
 from .._abi import ACTIVATIONS, PicActor, PicPoolLnSpec, PicPoolSpec
+from ._head import _is_tensor
 
 MAX_LAYERS, MAX_WIDTH = 6, 256
 
@@ -25,19 +27,12 @@ ActorRollout = namedtuple("ActorRollout", "features pre actions KE PE PE_reward"
 
 def head_param_count(widths, layernorm):
     """P: the length of one parameter vector of a head with these layer widths."""
-    n = len(widths) - 1
-    return sum(widths[l + 1] * widths[l] + widths[l + 1] + (2 * widths[l + 1] if layernorm and l + 1 < n else 0) for l in range(n))
-
-
-def _is_tensor(a):
-    return hasattr(a, "data_ptr")
+    return _head.param_count(widths, layernorm)
 
 
 def _host(a):
     """a (NumPy, a tensor or None) as a float64 NumPy array."""
-    if a is None:
-        return None
-    return np.asarray(a.detach().cpu().numpy() if _is_tensor(a) else a, dtype=np.float64)
+    return _head._host(a, np.float64)
 
 
 class ParticleActor:
@@ -111,46 +106,14 @@ class ParticleActor:
     def pack(layers):
         """[(W [out, in], b [out], gamma [out] or None, beta [out] or None), ...] -> the flat float64 vector; a tuple (W, b)
         stands for (W, b, None, None).  The layers must chain; with a LayerNorm every layer but the last has gamma and beta."""
-        parts, prev = [], None
-        norms = [len(t) == 4 and t[2] is not None for t in layers]
-        if norms[-1] or len(set(norms[:-1])) > 1:
-            raise ValueError("pack: gamma and beta belong behind every layer but the last, or behind none")
-        for l, t in enumerate(layers):
-            W, b = np.asarray(t[0], dtype=np.float64), np.asarray(t[1], dtype=np.float64)
-            if W.ndim != 2 or b.shape != (W.shape[0],):
-                raise ValueError(f"layer {l}: W must be [out, in] and b [out], not {W.shape} and {b.shape}")
-            if prev is not None and W.shape[1] != prev:
-                raise ValueError(f"the widths do not chain: layer {l} takes {W.shape[1]} inputs, layer {l - 1} gives {prev}")
-            prev = W.shape[0]
-            parts += [W.ravel(), b]
-            if norms[l]:
-                g, be = np.asarray(t[2], dtype=np.float64), np.asarray(t[3], dtype=np.float64)
-                if g.shape != b.shape or be.shape != b.shape:
-                    raise ValueError(f"layer {l}: gamma and beta must be [{prev}], not {g.shape} and {be.shape}")
-                parts += [g, be]
-        return np.concatenate(parts)
+        return _head.pack(layers)
 
-    @staticmethod
-    def widths_of(layers):
-        return [int(np.shape(layers[0][0])[1])] + [int(np.shape(t[0])[0]) for t in layers]
+    widths_of = staticmethod(_head.widths_of)
 
     def unpack(self, params=None):
         """The flat vector (this actor's, or one of its shape) -> [(W, b, gamma, beta), ...] as views (gamma, beta None where
         there is no LayerNorm); a [num_envs, P] array gives W [num_envs, out, in] and [num_envs, out] vectors."""
-        p = _host(self.params if params is None else params)
-        lead, out, at, n = p.shape[:-1], [], 0, len(self.widths) - 1
-        for l in range(n):
-            nin, nout = self.widths[l], self.widths[l + 1]
-            W = p[..., at:at + nout * nin].reshape(*lead, nout, nin)
-            at += nout * nin
-            b = p[..., at:at + nout]
-            at += nout
-            g = be = None
-            if self.layernorm and l + 1 < n:
-                g, be = p[..., at:at + nout], p[..., at + nout:at + 2 * nout]
-                at += 2 * nout
-            out.append((W, b, g, be))
-        return out
+        return _head.unpack(self.params if params is None else params, self.widths, self.layernorm)
 
     def _kw(self):
         return dict(activation=self.activation, head_activation=self.head_activation, v_scale=self.v_scale, eps=self.eps, period=self.period, layernorm=self.layernorm,
@@ -214,23 +177,7 @@ class ParticleActor:
                     for p, a in ((self.pool.W, actor.W), (self.pool.b, actor.b), (self.pool.gamma, actor.gamma), (self.pool.beta, actor.beta)):
                         if p is not None:
                             p.copy_(torch.from_numpy(np.ascontiguousarray(a)))
-                mods, layers = [], actor.unpack()
-                for l, (W, b, g, be) in enumerate(layers):
-                    lin = nn.Linear(W.shape[1], W.shape[0], dtype=torch.float64)
-                    with torch.no_grad():
-                        lin.weight.copy_(torch.from_numpy(np.ascontiguousarray(W)))
-                        lin.bias.copy_(torch.from_numpy(np.ascontiguousarray(b)))
-                    mods.append(lin)
-                    if l + 1 == len(layers):
-                        break
-                    if g is not None:
-                        norm = nn.LayerNorm(W.shape[0], eps=actor.ln_eps, dtype=torch.float64)
-                        with torch.no_grad():
-                            norm.weight.copy_(torch.from_numpy(np.ascontiguousarray(g)))
-                            norm.bias.copy_(torch.from_numpy(np.ascontiguousarray(be)))
-                        mods.append(norm)
-                    mods.append(nn.Tanh() if actor.head_activation == "tanh" else nn.ReLU())
-                self.head = nn.Sequential(*mods).to(dev)
+                self.head = nn.Sequential(*_head.torch_layers(actor.unpack(), actor.head_activation, actor.ln_eps)).to(dev)
                 self.squash, self.action_scale, self.action_shift = actor.squash, actor.action_scale, actor.action_shift
 
             def forward(self, xv):

@@ -9,7 +9,9 @@ from collections import namedtuple
 
 import numpy as np
 
+from . import _head
 from .._abi import ACTIVATIONS, PicPolicy
+from ._head import _host, _is_tensor
 
 MAX_LAYERS, MAX_WIDTH, MAX_OBS_MODES = 4, 256, 64
 
@@ -19,16 +21,7 @@ PolicyRollout = namedtuple("PolicyRollout", "obs pre actions KE PE PE_reward")
 
 def param_count(widths):
     """P: the length of one parameter vector of an MLP with these layer widths."""
-    return sum(widths[l + 1] * widths[l] + widths[l + 1] for l in range(len(widths) - 1))
-
-
-def _is_tensor(a):
-    return hasattr(a, "data_ptr")
-
-
-def _host(a):
-    """a (NumPy, a tensor or None) as a NumPy array."""
-    return None if a is None else (a.detach().cpu().numpy() if _is_tensor(a) else np.asarray(a))
+    return _head.param_count(widths)
 
 
 class MLPPolicy:
@@ -76,36 +69,16 @@ class MLPPolicy:
     @staticmethod
     def pack(layers):
         """[(W [out, in], b [out]), ...] -> the flat float64 vector; the layers must chain (in of a layer = out of the one before)."""
-        parts, prev = [], None
-        for l, (W, b) in enumerate(layers):
-            W, b = np.asarray(W, dtype=np.float64), np.asarray(b, dtype=np.float64)
-            if W.ndim != 2 or b.shape != (W.shape[0],):
-                raise ValueError(f"layer {l}: W must be [out, in] and b [out], not {W.shape} and {b.shape}")
-            if prev is not None and W.shape[1] != prev:
-                raise ValueError(f"the widths do not chain: layer {l} takes {W.shape[1]} inputs, layer {l - 1} gives {prev}")
-            prev = W.shape[0]
-            parts += [W.ravel(), b]
-        return np.concatenate(parts)
+        return _head.pack([(W, b) for W, b in layers])
 
     @staticmethod
     def widths_of(layers):
-        return [int(np.shape(layers[0][0])[1])] + [int(np.shape(W)[0]) for W, _ in layers]
+        return _head.widths_of([(W, b) for W, b in layers])
 
     def unpack(self, params=None):
         """The flat vector (this policy's, or one of its shape) -> [(W, b), ...] as views; a [num_envs, P] array gives
         W [num_envs, out, in] and b [num_envs, out]."""
-        p = self.params if params is None else params
-        if _is_tensor(p):
-            p = p.detach().cpu().numpy()
-        p = np.asarray(p, dtype=np.float64)
-        lead, out, at = p.shape[:-1], [], 0
-        for l in range(len(self.widths) - 1):
-            nin, nout = self.widths[l], self.widths[l + 1]
-            W = p[..., at:at + nout * nin].reshape(*lead, nout, nin)
-            at += nout * nin
-            out.append((W, p[..., at:at + nout]))
-            at += nout
-        return out
+        return [(W, b) for W, b, _, _ in _head.unpack(self.params if params is None else params, self.widths)]
 
     def unpack_grad(self, g):
         """A flat gradient with respect to the packed parameters ([P], or [num_envs, P]; NumPy or a tensor, e.g. what
@@ -166,23 +139,11 @@ class MLPPolicy:
     def to_torch(self):
         """A float64 nn.Sequential with this policy's weights (a final Tanh with squash): u or tanh(u) of an observation that
         obs_scale has already been multiplied into; `torch_actions` applies both scales.  Not for a per-environment policy."""
-        import torch
         import torch.nn as nn
         if self.per_env:
             raise ValueError("to_torch: a per-environment policy has no single module (unpack() gives its weights)")
-        mods = []
-        layers = self.unpack()
-        for l, (W, b) in enumerate(layers):
-            lin = nn.Linear(W.shape[1], W.shape[0], dtype=torch.float64)
-            with torch.no_grad():
-                lin.weight.copy_(torch.from_numpy(np.ascontiguousarray(W)))
-                lin.bias.copy_(torch.from_numpy(np.ascontiguousarray(b)))
-            mods.append(lin)
-            if l + 1 < len(layers):
-                mods.append(nn.Tanh() if self.activation == "tanh" else nn.ReLU())
-        if self.squash:
-            mods.append(nn.Tanh())
-        return nn.Sequential(*mods)
+        mods = _head.torch_layers(_head.unpack(self.params, self.widths), self.activation)
+        return nn.Sequential(*mods, *([nn.Tanh()] if self.squash else []))
 
     def torch_actions(self, module, obs):
         """The actions of `module` (to_torch's, or one of its shape) on observations obs [..., 2 M_o] with this policy's

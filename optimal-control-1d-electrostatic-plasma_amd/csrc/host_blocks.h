@@ -32,7 +32,7 @@ struct Carver {
   }
 };
 
-// What the layouts read of a handle (host_diff.h: block_dims), of a policy (policy_dims) and of the phase JVP
+// What the layouts read of a handle (host_diff.h: block_dims), of a policy (host_policy.h: policy_dims) and of the phase JVP
 struct BlockDims {
   size_t num_envs = 0, ld = 0, Ng = 0, act_modes = 0;
   size_t P = 0, obs_modes = 0;        // the policy's: doubles of one parameter vector, observed modes

@@ -1,6 +1,6 @@
-// host_diff.h -- shared by host_phase.h, host_moments.h, host_tape.h, host_tangent.h, host_tangent_walk.h and host_policy.h; included
-// by picstep.hip alone, behind its helpers.  The layouts of the carved blocks are host_blocks.h's; here: the two functions that
-// allocate one.
+// host_diff.h -- shared by host_phase.h, host_moments.h, host_pool.h, host_tape.h, host_tangent.h, host_tangent_walk.h, host_head.h,
+// host_policy.h and host_actor.h; included by picstep.hip alone, behind its helpers.  The layouts of the carved blocks are
+// host_blocks.h's; here: the two functions that allocate one.
 #pragma once
 
 static_assert(std::is_same<acc_t, long long>::value, "host_blocks.h: TapeViews::acc is an accumulator row");
@@ -9,20 +9,6 @@ static_assert(std::is_same<acc_t, long long>::value, "host_blocks.h: TapeViews::
 inline BlockDims block_dims(const pic_handle* h) {
   BlockDims d;
   d.num_envs = (size_t)h->cfg.num_envs; d.ld = (size_t)h->ld; d.Ng = (size_t)h->cfg.Ng; d.act_modes = (size_t)h->act_modes;
-  return d;
-}
-
-// P, the doubles of one parameter vector
-inline size_t policy_param_count(const pic_policy* p) {
-  size_t P = 0;
-  for (int l = 0; l < p->n_layers; ++l) P += (size_t)p->width[l + 1] * p->width[l] + p->width[l + 1];
-  return P;
-}
-
-// ... and of a policy's shape
-inline BlockDims policy_dims(const pic_handle* h, const pic_policy& p) {
-  BlockDims d = block_dims(h);
-  d.P = policy_param_count(&p); d.obs_modes = (size_t)p.obs_modes; d.per_env = p.per_env != 0;
   return d;
 }
 

@@ -1,41 +1,34 @@
 // host_policy.h -- the host side of pic_policy_eval, pic_step_policy, pic_policy_vjp and pic_tape_step_policy (7p) and pic_policy_jvp (7q); kernels: pic_policy.h.
-// Included by picstep.hip inside its extern "C" block, behind the stepping entries (step_prologue, actuator_control, advance); the
-// layouts of its blocks are host_blocks.h's, call_reserve and tape_reserve (host_diff.h) allocate them.
+// Included by picstep.hip inside its extern "C" block, behind the stepping entries (step_prologue, actuator_control) and
+// host_head.h, which holds what a call shares with the particle actor's (host_actor.h); the layouts of its blocks are
+// host_blocks.h's, call_reserve and tape_reserve (host_diff.h) allocate them.
 
-// what is wrong with a policy whatever the actuator, or null
+// the policy's dims (host_blocks.h: BlockDims)
+static BlockDims policy_dims(const pic_handle* h, const pic_policy& p) {
+  BlockDims d = block_dims(h);
+  d.P = head_param_count(p.width, p.n_layers, false); d.obs_modes = (size_t)p.obs_modes; d.per_env = p.per_env != 0;
+  return d;
+}
+
+// what is wrong with a policy whatever the actuator, or null: head_bad_shape and, at their places, the checks of its observation
 static const char* policy_bad_args(const pic_handle* h, const pic_policy* p, int mem_kind) {
   if (!p) return "null policy";
-  if (mem_kind != PIC_HOST && mem_kind != PIC_DEVICE) return "bad mem_kind";
-  if (p->n_layers < 1 || p->n_layers > kPolicyMaxLayers) return "n_layers must be 1..4";
-  if (p->obs_modes < 1 || p->obs_modes > kPolicyMaxObsModes) return "obs_modes must be 1..64";
-  if (p->obs_modes >= h->cfg.Ng) return "obs_modes must be below N_mesh";
-  for (int l = 0; l <= p->n_layers; ++l)
-    if (p->width[l] < 1 || p->width[l] > kPolicyMaxWidth) return "every width must be 1..256";
-  if (p->width[0] != 2 * p->obs_modes) return "width[0] must be 2 obs_modes";
-  if (p->activation != PIC_ACT_TANH && p->activation != PIC_ACT_RELU) return "activation must be PIC_ACT_TANH or PIC_ACT_RELU";
-  if (p->squash != 0 && p->squash != 1) return "squash must be 0 or 1";
-  if (p->per_env != 0 && p->per_env != 1) return "per_env must be 0 or 1";
-  if (!p->params) return "null params";
-  return nullptr;
+  return head_bad_shape(*p, mem_kind, kPolicyMaxLayers, [&](int slot) -> const char* {
+    if (slot == kOwnBehindLayers) {
+      if (p->obs_modes < 1 || p->obs_modes > kPolicyMaxObsModes) return "obs_modes must be 1..64";
+      if (p->obs_modes >= h->cfg.Ng) return "obs_modes must be below N_mesh";
+    }
+    if (slot == kOwnBehindWidths && p->width[0] != 2 * p->obs_modes) return "width[0] must be 2 obs_modes";
+    return nullptr;
+  });
 }
 
-// the actuator a policy acts through: PIC_ESTATE without one, PIC_EINVAL if the last width is not its 2M
-static int policy_actuator(pic_handle* h, const pic_policy* p, const char* who) {
-  if (!h->act_modes) return fail(h, PIC_ESTATE, std::string(who) + ": call pic_set_actuator first");
-  if (p->width[p->n_layers] != 2 * h->act_modes)
-    return fail(h, PIC_EINVAL, std::string(who) + ": the last width must be 2 max_mode of the actuator (pic_set_actuator) = " +
-                                   std::to_string(2 * h->act_modes));
-  return PIC_OK;
-}
-
-// One call's arguments; its base: the views into the handle's policy block it works on (host_blocks.h: policy_parts)
-struct PolicyCall : PolicyCallViews {
+// One call's arguments on the views into the handle's policy block it works on (host_blocks.h: policy_parts)
+struct PolicyCall : PolicyCallViews, HeadCall {
   const pic_policy* p;
-  const double *obs, *noise, *std;
-  int mem_kind, nsteps;
-  bool stepping;
-  double *obs_out, *pre_out, *actions_out, *hist;
+  const double* obs;
 };
+static HeadRow<PolicyArgs> policy_row(const pic_policy* p) { return {&PolicyArgs::obs_out, 2 * (size_t)p->obs_modes}; }
 
 // The block of a call, its inputs on the device and the argument block of its first step (the per-step pointers at row 0)
 static int policy_begin(pic_handle* h, PolicyCall& k, PolicyArgs& a, const char* who) {
@@ -44,94 +37,49 @@ static int policy_begin(pic_handle* h, PolicyCall& k, PolicyArgs& a, const char*
   PolicyCallShape s;
   s.nsteps = (size_t)k.nsteps; s.host = k.mem_kind == PIC_HOST; s.stepping = k.stepping;
   s.scale = p->obs_scale; s.std = k.std; s.noise = k.noise; s.obs = k.obs;
-  s.obs_out = k.obs_out; s.pre_out = k.pre_out; s.actions_out = k.actions_out; s.hist = k.hist;
+  s.obs_out = k.row_out; s.pre_out = k.pre_out; s.actions_out = k.actions_out; s.hist = k.hist;
   if (int rc = call_reserve<PolicyCallViews>(h, h->pol, &h->pol_bytes, who, "the policy's device block", k,
                                              [&](Carver c, PolicyCallViews& v) { return policy_parts(c, d, s, v); }))
     return rc;
-  const size_t E = d.num_envs, T = s.nsteps, D = sizeof(double), nO = 2 * d.obs_modes, nA = 2 * d.act_modes;
   a = PolicyArgs{};
-  HIPCHK(h, device_input(h, p->params, k.mem_kind, d.params() * D, k.d_params, &a.params));
-  HIPCHK(h, device_input(h, p->obs_scale, k.mem_kind, nO * D, k.d_scale, &a.obs_scale));
-  HIPCHK(h, device_input(h, k.std, k.mem_kind, nA * D, k.d_std, &a.std));
-  HIPCHK(h, device_input(h, k.noise, k.mem_kind, T * E * nA * D, k.d_noise, &a.noise));
-  HIPCHK(h, device_input(h, k.obs, k.mem_kind, E * nO * D, k.d_obs, &a.obs));
+  if (int rc = head_stage(h, k, p->params, d, a)) return rc;
+  HIPCHK(h, device_input(h, p->obs_scale, k.mem_kind, 2 * d.obs_modes * sizeof(double), k.d_scale, &a.obs_scale));
+  HIPCHK(h, device_input(h, k.obs, k.mem_kind, d.orow() * sizeof(double), k.d_obs, &a.obs));
   if (!k.obs) {
     const int rc = ensure_twiddle(h, p->obs_modes);
     if (rc) return rc;
   }
   a.E_mesh = h->E_mesh; a.tw = h->tw; a.rows = h->tw_rows; a.Ng = h->cfg.Ng;
-  a.obs_out = device_output(k.obs_out, k.mem_kind, k.d_obs_out);
-  a.pre_out = device_output(k.pre_out, k.mem_kind, k.d_pre_out);
-  if (k.stepping) {
-    a.act = k.d_act;
-    a.act_out = k.mem_kind == PIC_DEVICE ? k.actions_out : nullptr;      // (host: the rows themselves are read back)
-  } else {
-    a.act = device_output(k.actions_out, k.mem_kind, k.d_act);
-  }
+  a.obs_out = device_output(k.row_out, k.mem_kind, k.d_obs_out);
   a.Mo = p->obs_modes;
   policy_shape(a, *p, d.P, p->action_scale);
   return PIC_OK;
-}
-
-// the argument block of step s: every per-step row moved on by s steps
-static PolicyArgs policy_at(const PolicyArgs& a0, size_t s, size_t E, size_t nA) {
-  PolicyArgs a = a0;
-  const size_t ro = s * E * 2 * (size_t)a.Mo, ra = s * E * nA;
-  if (a.noise) a.noise += ra;
-  if (a.obs_out) a.obs_out += ro;
-  if (a.pre_out) a.pre_out += ra;
-  if (a.act) a.act += ra;
-  if (a.act_out) a.act_out += ra;
-  return a;
 }
 
 static void policy_launch(pic_handle* h, const PolicyArgs& a) {
   hipLaunchKernelGGL(policy_kernel, dim3(h->cfg.num_envs), dim3(BLOCK), 0, h->stream, a);
 }
 
-// the read-backs of a call in host memory and of the energies' record; one wait, if anything is read back
-static int policy_finish(pic_handle* h, const PolicyCall& k, const PolicyArgs& a0, const char* who) {
-  const size_t E = (size_t)h->cfg.num_envs, T = (size_t)k.nsteps, D = sizeof(double);
-  const size_t nO = 2 * (size_t)k.p->obs_modes, nA = 2 * (size_t)h->act_modes;
-  hipError_t e = hipGetLastError();
-  bool wait = false;
-  if (k.mem_kind == PIC_HOST) {
-    if (e == hipSuccess) e = device_result(h, k.obs_out, a0.obs_out, T * E * nO * D);
-    if (e == hipSuccess) e = device_result(h, k.pre_out, a0.pre_out, T * E * nA * D);
-    if (e == hipSuccess) e = device_result(h, k.actions_out, a0.act, T * E * nA * D);
-    wait = k.obs_out || k.pre_out || k.actions_out;
-  }
-  if (k.hist) {
-    if (e == hipSuccess) e = hipMemcpyAsync(k.hist, k.d_hist, T * 3 * E * D, hipMemcpyDeviceToHost, h->stream);
-    wait = true;
-  }
-  return hip_tail(h, e, wait, who);
-}
-
 int pic_policy_eval(pic_handle* h, const pic_policy* p, const double* obs, const double* noise, const double* std, int mem_kind,
                     double* obs_out, double* pre_out, double* actions_out) {
   const char* who = "pic_policy_eval";
-  if (!h) return PIC_EINVAL;
-  if (const char* bad = policy_bad_args(h, p, mem_kind)) return fail(h, PIC_EINVAL, std::string(who) + ": " + bad);
-  int rc = policy_actuator(h, p, who);
+  int rc = head_entry(h, p, h ? policy_bad_args(h, p, mem_kind) : nullptr, who);
   if (rc) return rc;
   if (!obs && !h->has_state) return fail(h, PIC_ESTATE, std::string(who) + ": call pic_reset first (obs = NULL reads the current E_mesh)");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  PolicyCall k{{}, p, obs, noise, std, mem_kind, 1, false, obs_out, pre_out, actions_out, nullptr};
+  PolicyCall k{{}, {noise, std, mem_kind, 1, false, obs_out, pre_out, actions_out, nullptr}, p, obs};
   PolicyArgs a;
   rc = policy_begin(h, k, a, who);
   if (rc) return rc;
   policy_launch(h, a);
-  return policy_finish(h, k, a, who);
+  return head_finish(h, k, a, policy_row(p), who);
 }
 
 // ---- the policy's vector-Jacobian product (pic_policy_vjp; kernel: pic_policy.h) ---------------------------------
 int pic_policy_vjp(pic_handle* h, const pic_policy* p, const double* obs, const double* pre, const double* cot_actions, int mem_kind,
                    double* g_params, double* g_obs, double* g_pre) {
   const char* who = "pic_policy_vjp";
-  if (!h) return PIC_EINVAL;
-  if (const char* bad = policy_bad_args(h, p, mem_kind)) return fail(h, PIC_EINVAL, std::string(who) + ": " + bad);
-  int rc = policy_actuator(h, p, who);
+  int rc = head_entry(h, p, h ? policy_bad_args(h, p, mem_kind) : nullptr, who);
   if (rc) return rc;
   if (!obs || !cot_actions) return fail(h, PIC_EINVAL, std::string(who) + ": null obs or cot_actions");
   if (!pre && p->squash) return fail(h, PIC_EINVAL, std::string(who) + ": pre may be NULL only with squash == 0");
@@ -179,16 +127,14 @@ int pic_policy_vjp(pic_handle* h, const pic_policy* p, const double* obs, const 
 int pic_policy_jvp(pic_handle* h, const pic_policy* p, const double* obs, const double* pre, int K, const double* d_params,
                    const double* d_obs, const double* d_pre, int mem_kind, double* d_pre_out, double* d_actions_out) {
   const char* who = "pic_policy_jvp";
-  if (!h) return PIC_EINVAL;
-  if (const char* bad = policy_bad_args(h, p, mem_kind)) return fail(h, PIC_EINVAL, std::string(who) + ": " + bad);
-  int rc = policy_actuator(h, p, who);
+  int rc = head_entry(h, p, h ? policy_bad_args(h, p, mem_kind) : nullptr, who);
   if (rc) return rc;
   if (K < 1 || K > kMaxTangents) return fail(h, PIC_EINVAL, std::string(who) + ": need 1 <= K <= " + std::to_string(kMaxTangents));
   if (!obs) return fail(h, PIC_EINVAL, std::string(who) + ": null obs");
   if (!pre && p->squash) return fail(h, PIC_EINVAL, std::string(who) + ": pre may be NULL only with squash == 0");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   const bool host = mem_kind == PIC_HOST;
-  const size_t E = (size_t)h->cfg.num_envs, D = sizeof(double), P = policy_param_count(p), PE = (p->per_env ? E : 1) * P;
+  const size_t E = (size_t)h->cfg.num_envs, D = sizeof(double), P = policy_dims(h, *p).P, PE = (p->per_env ? E : 1) * P;
   const size_t nO = 2 * (size_t)p->obs_modes, nA = 2 * (size_t)h->act_modes, kk = (size_t)K;
   PolicyJvpViews k;
   if (host) {
@@ -268,7 +214,7 @@ int pic_tape_step_policy(pic_handle* h, const pic_policy* p, const double* noise
   if (h && !h->tape.on) return fail(h, PIC_ESTATE, "pic_tape_step_policy: no tape is open (pic_tape_start)");
   int rc = step_prologue(h, nsteps, who, h ? policy_bad_args(h, p, mem_kind) : nullptr);
   if (rc) return rc;
-  rc = policy_actuator(h, p, who);
+  rc = head_actuator(h, p->width[p->n_layers], who);
   if (rc || nsteps == 0) return rc;
   StepControl sc;
   rc = actuator_control(h, sc, who);
@@ -277,7 +223,7 @@ int pic_tape_step_policy(pic_handle* h, const pic_policy* p, const double* noise
   rc = tape_policy_reserve(h, p, who);
   if (rc) return rc;
   // the three records are the tape's rows: the call's own outputs are copied from there behind the steps
-  PolicyCall k{{}, p, nullptr, noise, std, mem_kind, nsteps, true, nullptr, nullptr, nullptr, hist};
+  PolicyCall k{{}, {noise, std, mem_kind, nsteps, true, nullptr, nullptr, nullptr, hist}, p, nullptr};
   PolicyArgs a0;
   rc = policy_begin(h, k, a0, who);
   if (rc) {                           // (the copy goes again, and its bytes with it)
@@ -298,12 +244,8 @@ int pic_tape_step_policy(pic_handle* h, const pic_policy* p, const double* noise
   a0.pre_out = t.policy.pre + (size_t)s0 * E * nA;
   a0.act = t.policy.act + (size_t)s0 * E * nA;
   a0.act_out = nullptr;
-  for (int s = 0; s < nsteps && rc == PIC_OK; ++s) {      // (as pic_step_policy; advance puts e_t = B a_t on the tape)
-    const PolicyArgs a = policy_at(a0, (size_t)s, E, nA);
-    policy_launch(h, a);
-    sc.ctl.act = a.act;
-    rc = advance(h, sc, 1, hist_at(h, k.d_hist, (size_t)s));
-  }
+  // (as pic_step_policy; advance puts e_t = B a_t on the tape)
+  rc = head_steps(h, sc, a0, policy_row(p), nsteps, k.d_hist, [&](const PolicyArgs& a) { policy_launch(h, a); });
   for (int64_t s = s0; s < t.steps; ++s) t.policy.step[(size_t)s] = (int)t.policy.calls.size() - 1;
   const hipMemcpyKind outk = copy_kind(mem_kind, hipMemcpyDeviceToHost);
   hipError_t e = hipSuccess;
@@ -311,7 +253,7 @@ int pic_tape_step_policy(pic_handle* h, const pic_policy* p, const double* noise
   if (e == hipSuccess && pre_out) e = hipMemcpyAsync(pre_out, a0.pre_out, T * E * nA * D, outk, h->stream);
   if (e == hipSuccess && actions_out) e = hipMemcpyAsync(actions_out, a0.act, T * E * nA * D, outk, h->stream);
   if (e != hipSuccess) return fail(h, PIC_EHIP, std::string(who) + ": " + hipGetErrorString(e));
-  const int rf = policy_finish(h, k, a0, who);      // (the energies' record; after a failed step too)
+  const int rf = head_finish(h, k, a0, policy_row(p), who);      // (the energies' record alone: k names no output)
   if (!rf && mem_kind == PIC_HOST && !hist && (obs_out || pre_out || actions_out)) HIPCHK(h, hipStreamSynchronize(h->stream));
   return rc ? rc : rf;
 }
@@ -323,24 +265,16 @@ int pic_step_policy(pic_handle* h, const pic_policy* p, const double* noise, con
     return fail(h, PIC_ESTATE, "pic_step_policy: refused while a tape is open (its actions depend on the state: the gradient through the policy would be missing)");
   int rc = step_prologue(h, nsteps, who, h ? policy_bad_args(h, p, mem_kind) : nullptr);
   if (rc) return rc;
-  rc = policy_actuator(h, p, who);
+  rc = head_actuator(h, p->width[p->n_layers], who);
   if (rc || nsteps == 0) return rc;
   StepControl sc;
   rc = actuator_control(h, sc, who);
   if (rc) return rc;
-  PolicyCall k{{}, p, nullptr, noise, std, mem_kind, nsteps, true, obs_out, pre_out, actions_out, hist};
+  PolicyCall k{{}, {noise, std, mem_kind, nsteps, true, obs_out, pre_out, actions_out, hist}, p, nullptr};
   PolicyArgs a0;
   rc = policy_begin(h, k, a0, who);
   if (rc) return rc;
-  // Step s: the policy on the field step s-1 left, into row s of the actions; then the step pic_step_actions(row s, 1) makes.
-  // No row is written twice within a call, so the policy launch of step s+1 cannot overtake a force evaluation of step s.
-  const int E = h->cfg.num_envs;
-  for (int s = 0; s < nsteps && rc == PIC_OK; ++s) {
-    const PolicyArgs a = policy_at(a0, (size_t)s, (size_t)E, 2 * (size_t)h->act_modes);
-    policy_launch(h, a);
-    sc.ctl.act = a.act;
-    rc = advance(h, sc, 1, hist_at(h, k.d_hist, (size_t)s));
-  }
-  const int rf = policy_finish(h, k, a0, who);      // (after a failed step too: what was enqueued is waited for)
+  rc = head_steps(h, sc, a0, policy_row(p), nsteps, k.d_hist, [&](const PolicyArgs& a) { policy_launch(h, a); });
+  const int rf = head_finish(h, k, a0, policy_row(p), who);
   return rc ? rc : rf;
 }

@@ -22,9 +22,10 @@ static int tanwalk_reserve(pic_handle* h, int K, int mo, const char* who) {
 static int tanpol_reserve(pic_handle* h, int K, const char* who) {
   Tape& t = h->tape;
   if (t.tpol.cap_k >= K && t.tpol.block) return PIC_OK;
-  const int rc = tape_reserve<TanPolViews>(h, t.tpol.block, who, "the policy tangent's working rows", t.tpol, [&](Carver c, TanPolViews& v) {
-    return tanpol_parts(c, policy_dims(h, t.policy.shape), K, v);
-  });
+  BlockDims d = block_dims(h);        // (with what the tape keeps of its policy: the layout reads no more of it)
+  d.P = t.policy.P; d.per_env = t.policy.shape.per_env != 0;
+  const int rc = tape_reserve<TanPolViews>(h, t.tpol.block, who, "the policy tangent's working rows", t.tpol,
+                                           [&](Carver c, TanPolViews& v) { return tanpol_parts(c, d, K, v); });
   if (!rc) t.tpol.cap_k = K;
   return rc;
 }

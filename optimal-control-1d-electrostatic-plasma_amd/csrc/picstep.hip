@@ -41,6 +41,7 @@
 // pic_pool.h and host_pool.h: the pooled particle features of pic_pool and pic_pool_vjp, as passes over a layer type;
 // pic_pool_ln.h: the layer type of pic_pool_ln and pic_pool_ln_vjp (a LayerNorm inside the per-particle layer).
 // pic_actor.h and host_actor.h: the DeepSets particle actor of pic_actor_eval and pic_step_actor (the pooled features and a head).
+// host_head.h: what the calls of the two controllers share (its parameter count and shape check: no HIP, tests/test_head_cpu.py).
 
 #include <hip/hip_runtime.h>
 
@@ -1855,7 +1856,8 @@ int pic_step_feedback_gain(pic_handle* h, int max_mode, const double* gain, int 
   return PIC_OK;
 }
 
-// closed loops under an MLP policy (pic_policy_eval, pic_step_policy)
+// what a controller call has in common, then closed loops under an MLP policy (pic_policy_eval, pic_step_policy)
+#include "host_head.h"
 #include "host_policy.h"
 // ... and under the DeepSets particle actor (pic_actor_eval, pic_step_actor)
 #include "host_actor.h"

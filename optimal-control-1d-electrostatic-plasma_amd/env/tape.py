@@ -260,28 +260,38 @@ class TapePIC:
         return self._tape_pass("tangent_feedback", "tangent", mem, base, given, outs, call, K, batched, bump=True)
 
     # -- closed loops under an MLP policy on the device (pic_policy_eval, pic_step_policy) ------------------
-    def _policy_call(self, policy, T, obs, noise, std, on_device):
-        """The memory, the struct and the arrays of one policy call: inputs as float64 arrays of that memory, fresh outputs."""
-        E, nO, nA = self.num_envs, 2 * policy.obs_modes, 2 * self.max_mode
+    def _head_call(self, mem, T, row, noise, std, history, call):
+        """What a call of either controller shares, the MLP policy's and the particle actor's: noise and std as float64 arrays
+        of `mem`, fresh outputs -- the controller's own rows [num_envs, row], pre and actions [num_envs, 2M], behind a leading T
+        axis for a rollout of T steps (T None: one evaluation) -- and with `history` the energies' record.  `call` is the Handle
+        method with the arguments in front of noise bound: it gets the tail every such entry has, (noise, std, mem_kind, own,
+        pre, actions) for an evaluation and (noise, std, mem_kind, T, own, pre, actions, hist) for a rollout, between mem.enter()
+        and mem.leave().  -> (own, pre, actions, KE, PE, PE_reward), the last three [T, num_envs] NumPy, or None without history."""
+        E, nA = self.num_envs, 2 * self.max_mode
+        lead = () if T is None else (T,)
+        noise, std = mem.f64(noise, lead + (E, nA)), mem.f64(std, (nA,))
+        outs = mem.empty(lead + (E, row)), mem.empty(lead + (E, nA)), mem.empty(lead + (E, nA))
+        hist = np.empty((T, 3, E)) if history else None
+        mem.enter()
+        call(mem.addr(noise), mem.addr(std), mem.kind, *lead, *(mem.addr(a) for a in outs), *(() if T is None else (hist,)))
+        mem.leave(self._h)
+        return outs + ((None, None, None) if hist is None else (hist[:, 0], hist[:, 1], hist[:, 2]))
+
+    def _policy_call(self, call, policy, T, obs, noise, std, history, on_device):
+        """`_head_call` for the policy: `call` is Handle.policy_eval (T None; it takes the observation) or one of the rollouts."""
+        E, nO = self.num_envs, 2 * policy.obs_modes
         mem = Mem.of(self, policy.params, obs, noise, std, force_device=on_device)
         spec, keep = policy.spec(mem, E)
-        lead = () if T is None else (T,)
         obs = mem.f64(obs, (E, nO))
-        noise = mem.f64(noise, lead + (E, nA))
-        std = mem.f64(std, (nA,))
-        outs = mem.empty(lead + (E, nO)), mem.empty(lead + (E, nA)), mem.empty(lead + (E, nA))
-        return mem, spec, keep, obs, noise, std, outs
+        front = (spec, mem.addr(obs)) if T is None else (spec,)
+        return self._head_call(mem, T, nO, noise, std, history, lambda *tail: call(*front, *tail))
 
     def policy_eval(self, policy, obs=None, noise=None, std=None, on_device: bool = False):
         """`policy` (control.policy.MLPPolicy) once for every environment -> (obs [num_envs, 2 M_o], pre, actions [num_envs, 2M]):
         on obs if given, else on the modes of the current E_mesh (`modes(M_o)`, bit for bit: Re E_1..E_Mo, then Im).  pre is
         u = z + std * eps with noise = eps [num_envs, 2M] (std [2M], None = 1), or u = z; actions a = u, or action_scale tanh(u)
         with squash.  NumPy, or float64 CUDA tensors if an input is one or with on_device.  The state is not touched."""
-        mem, spec, keep, obs, noise, std, (o, u, a) = self._policy_call(policy, None, obs, noise, std, on_device)
-        mem.enter()
-        self._h.policy_eval(spec, mem.addr(obs), mem.addr(noise), mem.addr(std), mem.kind, mem.addr(o), mem.addr(u), mem.addr(a))
-        mem.leave(self._h)
-        return o, u, a
+        return self._policy_call(self._h.policy_eval, policy, None, obs, noise, std, False, on_device)[:3]
 
     def step_policy(self, policy, nsteps: int, noise=None, std=None, history: bool = True, on_device: bool = False):
         """nsteps closed-loop steps under `policy` in ONE call, without returning to the host between steps (pic_step_policy):
@@ -296,18 +306,12 @@ class TapePIC:
     def _rollout_policy(self, step, policy, nsteps, noise, std, history, on_device):
         """step_policy and tape_step_policy: `step` is the Handle method of the one or the other."""
         from ..control.policy import PolicyRollout
-        T = int(nsteps)
-        mem, spec, keep, _, noise, std, (o, u, a) = self._policy_call(policy, T, None, noise, std, on_device)
-        hist = np.empty((T, 3, self.num_envs)) if history else None
-        mem.enter()
-        step(spec, mem.addr(noise), mem.addr(std), mem.kind, T, mem.addr(o), mem.addr(u), mem.addr(a), hist)
-        mem.leave(self._h)
-        ke, pe, per = (None, None, None) if hist is None else (hist[:, 0], hist[:, 1], hist[:, 2])
-        return PolicyRollout(o, u, a, ke, pe, per)
+        return PolicyRollout(*self._policy_call(step, policy, int(nsteps), None, noise, std, history, on_device))
 
     # -- closed loops under the DeepSets particle actor (pic_actor_eval, pic_step_actor; DESIGN.md 7u) -------------------------
-    def _actor_call(self, who, actor, T, features, x, v, noise, std, on_device):
-        """The memory, the struct and the arrays of one actor call; every shape is checked here, before the device is touched."""
+    def _actor_call(self, who, actor, T, features, x, v, noise, std, history, on_device):
+        """`_head_call` for the actor: `who` names the Handle method, actor_eval (T None; it takes features, x and v) or
+        step_actor.  Every shape is checked here, before the handle or the device is touched."""
         E, N, H, nA = self.num_envs, self.N, actor.hidden, 2 * self.max_mode
         lead = () if T is None else (T,)
         if T is not None and T < 0:
@@ -326,9 +330,9 @@ class TapePIC:
                 raise ValueError(f"{who}: {name} must have shape {list(want)}, not {list(np.shape(a))}")
         mem = Mem.of(self, actor.params, features, x, v, noise, std, force_device=on_device)
         spec, keep = actor.spec(mem, E)
-        ins = [mem.f64(a) for a in (features, x, v, noise, std)]
-        outs = mem.empty(lead + (E, H)), mem.empty(lead + (E, nA)), mem.empty(lead + (E, nA))
-        return mem, spec, keep, ins, outs
+        ins = [mem.f64(a) for a in (features, x, v)]
+        front = (spec, *(mem.addr(a) for a in ins)) if T is None else (spec,)
+        return self._head_call(mem, T, H, noise, std, history, lambda *tail: getattr(self._h, who)(*front, *tail))
 
     def actor_eval(self, actor, features=None, x=None, v=None, noise=None, std=None, on_device: bool = False):
         """`actor` (control.actor.ParticleActor) once for every environment -> (features [num_envs, H], pre, actions
@@ -337,14 +341,7 @@ class TapePIC:
         bit.  pre is u = z + std * eps with noise = eps [num_envs, 2M] (std [2M], None = 1), or u = z; actions a = u, or
         action_shift + action_scale tanh(u) with squash.  NumPy, or float64 CUDA tensors if an input is one or with on_device.
         The state is not touched."""
-        mem, spec, keep, (f, x, v, noise, std), (fo, u, a) = self._actor_call("actor_eval", actor, None, features, x, v, noise, std,
-                                                                               on_device)
-        mem.enter()
-        self._h.actor_eval(spec, mem.addr(f), mem.addr(x), mem.addr(v), mem.addr(noise), mem.addr(std), mem.kind, mem.addr(fo),
-                           mem.addr(u), mem.addr(a))
-        mem.leave(self._h)
-        del keep
-        return fo, u, a
+        return self._actor_call("actor_eval", actor, None, features, x, v, noise, std, False, on_device)[:3]
 
     def step_actor(self, actor, nsteps: int, noise=None, std=None, history: bool = True, on_device: bool = False):
         """nsteps closed-loop steps under `actor` in ONE call, without returning to the host between steps (pic_step_actor): step
@@ -355,16 +352,7 @@ class TapePIC:
         tensors if an input is one or with on_device (then asynchronous without history).  Float64 environments only.  Refused
         while a tape is open: `actor.to_torch(env)` under env.grad.rollout_policy(observe="state") is the differentiable route."""
         from ..control.actor import ActorRollout
-        T = int(nsteps)
-        mem, spec, keep, (_, _, _, noise, std), (fo, u, a) = self._actor_call("step_actor", actor, T, None, None, None, noise, std,
-                                                                               on_device)
-        hist = np.empty((T, 3, self.num_envs)) if history else None
-        mem.enter()
-        self._h.step_actor(spec, mem.addr(noise), mem.addr(std), mem.kind, T, mem.addr(fo), mem.addr(u), mem.addr(a), hist)
-        mem.leave(self._h)
-        del keep
-        ke, pe, per = (None, None, None) if hist is None else (hist[:, 0], hist[:, 1], hist[:, 2])
-        return ActorRollout(fo, u, a, ke, pe, per)
+        return ActorRollout(*self._actor_call("step_actor", actor, int(nsteps), None, None, None, noise, std, history, on_device))
 
     # -- policy gradients on the device (pic_policy_vjp, pic_tape_step_policy, pic_tape_backward_policy; DESIGN.md 7p) -----------
     def policy_vjp(self, policy, obs, cot_actions, pre=None, on_device: bool = False):

@@ -467,6 +467,30 @@ def test_contract(pool_ln):
     refused(EINVAL, "action_scale", action_shift=float("nan"))
     refused(EINVAL, "null params", params=None)
     refused(EINVAL, "mem_kind", kind=2)
+    # the checks an actor shares with the MLP policy (csrc/host_head.h), in their own words ...
+    last = f"the last width must be 2 max_mode of the actuator (pic_set_actuator) = {2 * M}"
+    for reason, fields in (("bad mem_kind", dict(kind=2)), ("n_layers must be 1..6", dict(n_layers=7)),
+                           ("every width must be 1..256", dict(width1=257)),
+                           ("activation must be PIC_ACT_TANH or PIC_ACT_RELU", dict(activation=2)),
+                           ("squash must be 0 or 1", dict(squash=2)), ("per_env must be 0 or 1", dict(per_env=2)),
+                           ("null params", dict(params=None)), (last, dict(width3=2 * M + 2))):
+        for nsteps in (1, 0):
+            refused(EINVAL, ": " + reason, nsteps=nsteps, **fields)
+    # ... and of two faults at once the one that is checked first, with steps and without
+    for nsteps in (1, 0):
+        refused(EINVAL, "bad mem_kind", nsteps=nsteps, kind=2, width1=257)
+        refused(EINVAL, "bad mem_kind", nsteps=nsteps, kind=2, inner=dict(hidden=257))
+        refused(EINVAL, "hidden must be 1..256", nsteps=nsteps, inner=dict(hidden=257), n_layers=7)
+        refused(EINVAL, "n_layers must be 1..6", nsteps=nsteps, n_layers=7, width1=257)
+        refused(EINVAL, "every width must be 1..256", nsteps=nsteps, width1=257, width0=H + 1)
+        refused(EINVAL, "width[0] must be the pool's hidden", nsteps=nsteps, width0=H + 1, layernorm=2)
+        refused(EINVAL, "layernorm must be 0 or 1", nsteps=nsteps, layernorm=2, activation=2)
+        refused(EINVAL, "per_env must be 0 or 1", nsteps=nsteps, per_env=2, ln_eps=0.0)
+        refused(EINVAL, "ln_eps must be finite and > 0", nsteps=nsteps, ln_eps=0.0, params=None)
+        refused(EINVAL, "null params", nsteps=nsteps, params=None, width3=2 * M + 2)
+    lib, hh = env._h.lib, env._h._h
+    assert lib.pic_actor_eval(hh, None, None, None, None, None, None, 0, None, None, None) == EINVAL and "pic_actor_eval: null actor" in _err(env)
+    assert lib.pic_step_actor(hh, None, None, None, 0, 1, None, None, None, None) == EINVAL and "pic_step_actor: null actor" in _err(env)
     assert _rc_step(env, spec, -1) == EINVAL and "nsteps" in _err(env)
     assert _rc_eval(env, spec, features=feats, x=X, v=X) == EINVAL and "features must not be given together" in _err(env)
     assert _rc_eval(env, spec, features=feats, v=X) == EINVAL and "features must not be given together" in _err(env)
@@ -489,8 +513,11 @@ def test_contract(pool_ln):
     fresh.close()
     bare = _make(E, N, Ng, M, actuator=False)
     x0 = _state(bare)
-    for rc in (_rc_step(bare, spec), _rc_eval(bare, spec), _rc_eval(bare, spec, features=feats)):
-        assert rc == ESTATE and "pic_set_actuator" in _err(bare)
+    wrong, keep_wrong = _spec(env, actor)
+    wrong.width[3] = 2 * M + 2                   # (a missing actuator is reported before a last width that would not fit one)
+    for rc in (_rc_step(bare, spec), _rc_eval(bare, spec), _rc_eval(bare, spec, features=feats), _rc_step(bare, wrong),
+               _rc_step(bare, wrong, 0), _rc_eval(bare, wrong), _rc_eval(bare, wrong, features=feats)):
+        assert rc == ESTATE and ": call pic_set_actuator first" in _err(bare)
     assert _same(_state(bare), x0)
     bare.close()
     f32 = _make(E, N, Ng, M, dtype="float32")

@@ -325,6 +325,27 @@ def test_contract():
     refused(EINVAL, "activation", activation=2)
     refused(EINVAL, "squash", squash=2)
     refused(EINVAL, "params", params=None)
+    # the checks a policy shares with the particle actor (csrc/host_head.h), in their own words ...
+    last = f"the last width must be 2 max_mode of the actuator (pic_set_actuator) = {2 * M}"
+    for reason, fields in (("bad mem_kind", dict(kind=2)), ("n_layers must be 1..4", dict(n_layers=5)),
+                           ("every width must be 1..256", dict(width1=257)),
+                           ("activation must be PIC_ACT_TANH or PIC_ACT_RELU", dict(activation=2)),
+                           ("squash must be 0 or 1", dict(squash=2)), ("per_env must be 0 or 1", dict(per_env=2)),
+                           ("null params", dict(params=None)), (last, dict(width2=2 * M + 2))):
+        for nsteps in (1, 0):
+            refused(EINVAL, ": " + reason, nsteps=nsteps, **fields)
+    # ... and of two faults at once the one that is checked first, with steps and without
+    for nsteps in (1, 0):
+        refused(EINVAL, "bad mem_kind", nsteps=nsteps, kind=2, width1=257)
+        refused(EINVAL, "n_layers must be 1..4", nsteps=nsteps, n_layers=5, width1=257)
+        refused(EINVAL, "obs_modes must be 1..64", nsteps=nsteps, obs_modes=65, width1=257)
+        refused(EINVAL, "every width must be 1..256", nsteps=nsteps, width1=257, width0=2 * Mo + 2)
+        refused(EINVAL, "width[0] must be 2 obs_modes", nsteps=nsteps, width0=2 * Mo + 2, activation=2)
+        refused(EINVAL, "per_env must be 0 or 1", nsteps=nsteps, per_env=2, params=None)
+        refused(EINVAL, "null params", nsteps=nsteps, params=None, width2=2 * M + 2)
+    lib, hh = env._h.lib, env._h._h
+    assert lib.pic_policy_eval(hh, None, None, None, None, 0, None, None, None) == EINVAL and "pic_policy_eval: null policy" in _err(env)
+    assert lib.pic_step_policy(hh, None, None, None, 0, 1, None, None, None, None) == EINVAL and "pic_step_policy: null policy" in _err(env)
     assert _rc_step(env, spec, -1) == EINVAL and "nsteps" in _err(env)
     # PIC_ESTATE: a tape open (pic_step_policy alone: an evaluation changes nothing), before reset, without an actuator
     env.start_tape(4)
@@ -343,8 +364,10 @@ def test_contract():
     fresh.close()
     bare = _make(2, 1000, Ng, actuator=False)
     x0 = _state(bare)
-    for rc in (_rc_step(bare, spec), _rc_eval(bare, spec)):
-        assert rc == ESTATE and "pic_set_actuator" in _err(bare)
+    wrong, keep_wrong = _spec(env, pol)
+    wrong.width[2] = 2 * M + 2                   # (a missing actuator is reported before a last width that would not fit one)
+    for rc in (_rc_step(bare, spec), _rc_eval(bare, spec), _rc_step(bare, wrong), _rc_step(bare, wrong, 0), _rc_eval(bare, wrong)):
+        assert rc == ESTATE and ": call pic_set_actuator first" in _err(bare)
     assert _same(_state(bare), x0)
     bare.close()
     # ... and after all the refusals the handle steps as one that saw none
