@@ -197,6 +197,15 @@ int pic_get_integrator(pic_handle* h, int* scheme, int* evals_per_step);
 enum { PIC_READONLY_AUTO = 0, PIC_READONLY_OFF = 1, PIC_READONLY_ON = 2 };
 int pic_set_readonly_c(pic_handle* h, int mode);
 
+/* Whether every second inner step of a call of whole Yoshida-4 steps stores its particles once.  With
+ * PIC_ALTERNATE_ON such a step's sweeps B and D store nothing, its sweep C re-derives B and stores, and the next step's sweep B
+ * re-derives D: three storing sweeps per pair of steps instead of four, 72 bytes per float64 particle-step instead of 80, and the
+ * same bits.  In force only where the read-only sweep C is (pic_set_readonly_c), in a call of two or more steps without a feedback
+ * law; a call's first and last step store as ever.  PIC_ALTERNATE_AUTO (the default) follows PIC_READONLY_AUTO.  PIC_EINVAL for an
+ * unknown mode, or PIC_ALTERNATE_ON where Ng leaves no LDS for the second field tile. */
+enum { PIC_ALTERNATE_AUTO = 0, PIC_ALTERNATE_OFF = 1, PIC_ALTERNATE_ON = 2 };
+int pic_set_alternate_stores(pic_handle* h, int mode);
+
 /* nsteps x PIC.update_state with the energies of every step kept, i.e. the E / PE traces PIC.simulate
  * returns (pic.py:175-223) without its particle snapshots: hist, host [nsteps][3][num_envs] float64 =
  * KE, PE, PE_reward after each step (total energy = KE + PE).  E_ext as in pic_step, constant over the steps.

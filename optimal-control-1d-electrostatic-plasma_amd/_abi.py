@@ -40,6 +40,7 @@ ACCUMULATORS = {None: PIC_ACC_AUTO, "auto": PIC_ACC_AUTO, "fix64": PIC_ACC_FIX64
 POSITION_FORMATS = {None: PIC_POS_FLOAT, "float": PIC_POS_FLOAT, "fixed32": PIC_POS_FIXED32}
 
 READONLY_MODES = {"auto": 0, "off": 1, "on": 2}        # pic_set_readonly_c (include/picstep.h PIC_READONLY_*)
+ALTERNATE_MODES = {"auto": 0, "off": 1, "on": 2}       # pic_set_alternate_stores (PIC_ALTERNATE_*)
 
 KIND_NAMES = ("sweep_A", "sweep_B", "sweep_C", "sweep_D", "field_solve", "sweep_aux", "resident", "sweep_integrator")
 
@@ -137,6 +138,7 @@ SIGNATURES = {
     "pic_step_stage": [_vp, C.c_int, _vp, C.c_int],
     "pic_set_integrator": [_vp, C.c_int],
     "pic_set_readonly_c": [_vp, C.c_int],
+    "pic_set_alternate_stores": [_vp, C.c_int],
     "pic_get_integrator": [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "pic_step_history": [_vp, _vp, C.c_int, C.c_int, _vp],
     "pic_step_snapshots": [_vp, _vp, C.c_int, C.c_int, _vp, _vp],
@@ -314,8 +316,11 @@ class Handle:
 
     def __init__(self, N, Ng, num_envs=1, L=50.0, n0=1.0, dt=0.1, gamma=5.0, particle_dtype="float64",
                  accum_dtype=None, interpol="CIC", device_id=0, blocks_per_env=0, env_index_base=0,
-                 position_dtype=None, placement="auto", placement_ms=0, integrator="symplectic_4th_order", readonly_c="auto"):
+                 position_dtype=None, placement="auto", placement_ms=0, integrator="symplectic_4th_order", readonly_c="auto",
+                 alternate_stores="auto"):
         scheme = integrator_id(integrator)
+        if alternate_stores not in ALTERNATE_MODES:
+            raise ValueError(f"alternate_stores must be one of {sorted(ALTERNATE_MODES)}, not {alternate_stores!r}")
         if readonly_c not in READONLY_MODES:
             raise ValueError(f"readonly_c must be one of {sorted(READONLY_MODES)}, not {readonly_c!r}")
         self.lib = load()
@@ -348,6 +353,8 @@ class Handle:
             self.set_integrator(scheme)
         if readonly_c != "auto":
             self.set_readonly_c(readonly_c)
+        if alternate_stores != "auto":
+            self.set_alternate_stores(alternate_stores)
 
     def _chk(self, rc):
         if rc != 0:
@@ -418,6 +425,10 @@ class Handle:
         c = C.c_int64()
         self._chk(self.lib.pic_copy_envs_rejected(self._h, C.byref(c)))
         return c.value
+
+    def set_alternate_stores(self, mode):
+        """pic_set_alternate_stores: "auto", "off" or "on" -- whether every second inner step of a call stores once (same bits)."""
+        self._chk(self.lib.pic_set_alternate_stores(self._h, ALTERNATE_MODES[mode]))
 
     def set_readonly_c(self, mode):
         """pic_set_readonly_c: "auto", "off" or "on" -- whether whole steps leave sweep C's stores to sweep D (same bits)."""

@@ -39,7 +39,8 @@ struct LaunchPlan {
   double cs[4]{}, ds[4]{};
   bool light_inner_steps = false;     // inner steps of a call end with sweep D2 (particle states of 256 MB and more)
   bool readonly_auto = false;         // whole steps run sweeps C_RO and D_RC / D2_RC unless pic_set_readonly_c says otherwise
-  size_t sweep_lds_rc = 0;            // LDS of sweeps D_RC / D2_RC: sweep_lds and sweep C's field tile; 0 = does not fit
+  bool alternate_auto = false;        // ... and every second inner step of a call stores once unless pic_set_alternate_stores says otherwise
+  size_t sweep_lds_rc = 0;            // LDS of the sweeps that re-derive another (D_RC, D2_RC, C_RB, B2_RD): sweep_lds and that sweep's field tile; 0 = does not fit
   bool v_separate = false;            // v is an allocation of its own (states of 256 MB and more: host_place.h, alloc_particles)
   bool h_part_at_create = false;      // pinned staging for x | v from pic_create on (states up to 4 MB)
   bool h_fields = false;              // pinned staging for n | E_mesh | phi (meshes up to 256 KB each in total)
@@ -199,6 +200,9 @@ static inline int plan_launch(const pic_config& c, int ncu, LaunchPlan* p, std::
   p->solve_lds = 2 * (size_t)cfg->Ng * sizeof(double);
   if (p->sweep_lds + stride * p->esz + kSweepStaticLds <= kLdsLimit) p->sweep_lds_rc = p->sweep_lds + stride * p->esz;
   else p->readonly_auto = false;
+  // ... and store particles in every other sweep of a call's inner steps, not in two of three (host_schedule.h: X and Y steps;
+  // 72 instead of 80 bytes per float64 particle-step; profiles/r8_alternate_stores.md)
+  p->alternate_auto = p->readonly_auto;
   if (p->sweep_lds + kSweepStaticLds > kLdsLimit) {
     const long long max_ng = (long long)((kLdsLimit - kSweepStaticLds) / (2 * p->R * 8 + p->esz)) - 2;
     return plan_fail(err, "pic_create: Ng too large for the LDS-resident mesh (at most " + std::to_string(max_ng) +

@@ -98,6 +98,7 @@ struct CallShape {
   const double* ds = nullptr;
   bool light_inner_steps = false;        // LaunchPlan: inner steps end with sweep D2
   bool readonly_c = false;               // whole steps run sweeps C_RO and D_RC / D2_RC
+  bool alternate_stores = false;         // ... and every second inner step of a call stores its particles once (alternates below)
   bool feedback = false;                 // the on-device feedback law drives the field
   bool action = false;                   // the control is an actuator's action (not a field, or nothing)
   bool per_step_field = false;           // a new field / a new action with every step (else held for the call)
@@ -150,7 +151,21 @@ struct StepShape {
   bool field_ready = false;    // the previous step's sweep D has built this step's field
   bool hand_on = false;        // this step's sweep D builds the next one's
   bool feedback = false;       // this step's solve computes the next action
+  bool alternate = false;      // the call alternates its stores (alternates below): its inner steps end with a D2 flavour
+  bool lean = false;           // ... and this is a Y step: sweeps B2_RO, C_RB, D2_RO
+  bool after_lean = false;     // ... or the step behind one: its sweep B is B2_RD
 };
+
+// Does a call of nsteps whole steps store its particles in every other sweep?  Only where the read-only sweep C is in force, in a
+// call of two or more Yoshida-4 steps; not under the feedback law, which needs each step's field before the next sweep B.
+inline bool alternates(const CallShape& p, int nsteps) {
+  return p.alternate_stores && p.readonly_c && p.scheme == PIC_YOSHIDA4 && !p.feedback && nsteps >= 2;
+}
+// Inside such a call the steps are of two kinds.  X is the step of every other call: B or B2 (stores), C_RO, D2_RC or D_RC (stores).
+// Y stores once: B2_RO, C_RB (re-derives B, stores), D2_RO; the X step behind it opens with B2_RD, which re-derives D.  A call
+// begins with an X step (it reads stored state) and ends with one (state and fields are in memory when it returns), and no two Y
+// steps follow each other: step i of K is Y exactly when i >= 1 and K - 1 - i is odd.  Storing sweeps: 2 K - floor((K - 1) / 2).
+inline bool lean_step(int i, int nsteps) { return i >= 1 && ((nsteps - 1 - i) & 1) != 0; }
 
 // The sweeps of one Yoshida-4 step, stages from..upto (1 = sweep B, 2 = C, 3 = D; 1..3: a whole step inside a call).
 // another (the steps of one call but the last): on a large state (light_inner_steps) the step ends with sweep D2, which leaves
@@ -183,8 +198,8 @@ void yoshida_stages(Schedule& S, const CallShape& p, int from, int upto, const S
         S.q_slot = take(S, a, 0);
         emit_sweep(S, a, emit);
       }
-      l.stage = L.refresh_pending ? ST_B2 : ST_B;
-      l.c_prev = c[0]; l.c_cur = c[1]; l.d_cur = d[1];
+      l.stage = !L.refresh_pending ? ST_B : st.lean ? ST_B2_RO : st.after_lean ? ST_B2_RD : ST_B2;
+      l.c_prev = l.stage == ST_B2_RD ? c[3] : c[0]; l.c_cur = c[1]; l.d_cur = d[1];     // (B2_RD: the drift of sweep D, which it re-derives)
       l.in = S.q_slot;
       l.ctl = share && st.field_ready ? CTL_SHARED : CTL_OWN;
       l.ext_out = share && !st.field_ready ? EXT_THIS : EXT_NONE;
@@ -198,8 +213,8 @@ void yoshida_stages(Schedule& S, const CallShape& p, int from, int upto, const S
       S.q_slot = -1;
       S.stage_slot = x1;
     } else if (stage == 2) {
-      l.stage = ro ? ST_C_RO : ST_C;
-      l.c_cur = c[2]; l.d_cur = d[2];
+      l.stage = st.lean ? ST_C_RB : ro ? ST_C_RO : ST_C;
+      l.c_prev = st.lean ? c[1] : 0.0; l.c_cur = c[2]; l.d_cur = d[2];                  // (C_RB: the drift of sweep B, which it re-derives)
       l.in = S.stage_slot;
       l.ctl = later;
       l.post = L.post;
@@ -211,15 +226,15 @@ void yoshida_stages(Schedule& S, const CallShape& p, int from, int upto, const S
       S.ring.retire(S.stage_slot);
       S.stage_slot = x2;
     } else {
-      l.c_prev = ro ? c[2] : 0.0; l.c_cur = c[3]; l.d_cur = d[3];
+      l.c_prev = ro && !st.lean ? c[2] : 0.0; l.c_cur = c[3]; l.d_cur = d[3];
       l.in = S.stage_slot;
       l.ctl = later;
       l.hand_on = share && st.hand_on;
       l.ext_out = l.hand_on ? EXT_NEXT : EXT_NONE;
-      if (st.another && p.light_inner_steps) {
+      if (st.another && (p.light_inner_steps || st.alternate)) {
         // an inner step of a call: nothing can see its post-step fields before the next step has started, so the deposit they come
         // from is left to that step's sweep B2 (sweep D is the one sweep bound by VALU issue: 336 -> 321 us at config 2, B 320 -> 322)
-        l.stage = ro ? ST_D2_RC : ST_D2;
+        l.stage = st.lean ? ST_D2_RO : ro ? ST_D2_RC : ST_D2;
         const int qn = take(S, l, 1);
         emit_sweep(S, l, emit);
         L.refresh_pending = true;
@@ -356,6 +371,7 @@ CallLocals plan_call(Schedule& S, const CallShape& p, int nsteps, F&& emit) {
   CallLocals L;
   const bool rollout = !p.feedback && p.action;
   const bool held = !p.feedback && !p.per_step_field && !p.per_step_action;
+  const bool alt = alternates(p, nsteps);
   for (int s = 0; s < nsteps; ++s) {
     const bool last = s + 1 == nsteps;
     StepShape st;
@@ -365,6 +381,9 @@ CallLocals plan_call(Schedule& S, const CallShape& p, int nsteps, F&& emit) {
       st.another = !last && !p.feedback;
       st.field_ready = rollout && s > 0;
       st.hand_on = rollout && p.per_step_action && !last;
+      st.alternate = alt;
+      st.lean = alt && lean_step(s, nsteps);
+      st.after_lean = alt && s > 0 && lean_step(s - 1, nsteps);
       yoshida_stages(S, p, 1, 3, st, L, emit);
     } else {
       scheme_step(S, p.scheme, 0, held && !last, st, L, emit);

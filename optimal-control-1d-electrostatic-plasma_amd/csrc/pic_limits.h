@@ -35,5 +35,12 @@ enum Stage : int {
   // The re-derivation is C's own arithmetic on the same operands (push_one: substage), so every bit is the same.
   ST_C_RO = 12,    // as C without the particle stores; workgroup 0 of each environment stores its field tile (SweepIO::e2)
   ST_D_RC = 13,    // C's sub-stage again from C's input and ST_C_RO's field tile, then as D
-  ST_D2_RC = 14    // ... then as D2
+  ST_D2_RC = 14,   // ... then as D2
+  // Inside such a call every second step (host_schedule.h: a Y step) stores its particles once, in sweep C, and the step behind it
+  // opens with a sweep B that re-derives sweep D: three storing sweeps per pair of steps instead of four, 72 bytes per float64
+  // particle-step instead of 80.  Each storing sweep re-derives one sub-stage, on the same operands: every bit is the same.
+  ST_B2_RO = 15,   // as B2 without the particle stores; workgroup 0 of each environment stores its field tile (SweepIO::e2)
+  ST_C_RB = 16,    // B's drift and sub-stage again from B2_RO's input and field tile, then as C (stores)
+  ST_D2_RO = 17,   // as D2 without the particle stores; workgroup 0 of each environment stores its field tile
+  ST_B2_RD = 18    // D's sub-stage and wrap again from D2_RO's input and field tile, then as B2 (stores)
 };

@@ -80,14 +80,16 @@ __device__ __forceinline__ void substage(typename P::X& q, typename P::V& p, con
 // step would deposit from the stored x', p -- so that sweep (a full read of x and v) is skipped.
 // ST_C_RO is ST_C here (the sweep does not store); ST_D_RC / ST_D2_RC first run sweep C's sub-stage on (q2, v1) from C's field
 // tile Es2, then are ST_D / ST_D2.  That repeated drift and locate count into a scratch counter: C counted them already.
+// ST_B2_RO and ST_D2_RO are ST_B2 and ST_D2 here; ST_C_RB and ST_B2_RD first repeat what those did not store, from their tile in Es2.
 template <typename P, typename A, int SHAPE, int STAGE>
 __device__ __forceinline__ void push_one(typename P::X& xq, typename P::V& vp, const typename P::W* __restrict__ Es,
                                          const typename P::W* __restrict__ Es2, A* __restrict__ acc, A* __restrict__ acc2,
                                          const Consts<P>& k, double& ke, unsigned& bad) {
-  constexpr bool kC = (STAGE == ST_C || STAGE == ST_C_RO);
+  constexpr bool kB2 = (STAGE == ST_B2 || STAGE == ST_B2_RO || STAGE == ST_B2_RD);
+  constexpr bool kC = (STAGE == ST_C || STAGE == ST_C_RO || STAGE == ST_C_RB);
   constexpr bool kRC = (STAGE == ST_D_RC || STAGE == ST_D2_RC);
   constexpr bool kD = (STAGE == ST_D || STAGE == ST_D_RC);
-  constexpr bool kD2 = (STAGE == ST_D2 || STAGE == ST_D2_RC);
+  constexpr bool kD2 = (STAGE == ST_D2 || STAGE == ST_D2_RC || STAGE == ST_D2_RO);
   constexpr bool kFold = kFoldIndex<A, SHAPE>;           // every locate<.., kFold> below comes behind a wrap: 0 <= j <= Ng
   using T = typename P::W;
   T w[3];
@@ -100,7 +102,17 @@ __device__ __forceinline__ void push_one(typename P::X& xq, typename P::V& vp, c
     unsigned again = 0u;
     substage<P, SHAPE, kFold>(q, p, Es2, k.d_prev, k.c_prev, k, again);
   }
-  if (STAGE == ST_B2) {
+  if (STAGE == ST_B2_RD) {                               // sweep D2_RO's sub-stage and wrap on (q3, v2): the x', v' it did not store
+    unsigned again = 0u;
+    substage<P, SHAPE, kFold>(q, p, Es2, k.d_prev, k.c_prev, k, again);
+    if constexpr (!P::kFixed) q = wrap_periodic(q, k.L, again);
+  }
+  if (STAGE == ST_C_RB) {                                // sweep B2_RO's drift and sub-stage on the stored x', v': (q2, v1)
+    unsigned again = 0u;
+    q = drift<P>(q, p, k.c_next, k, again);              // q1 (c_next is c1 in every sweep)
+    substage<P, SHAPE, kFold>(q, p, Es2, k.d_prev, k.c_prev, k, again);
+  }
+  if (kB2) {
     // The post-step deposit of the PREVIOUS step (pic.py:145): q is the x' that step's sweep D2 wrapped and stored, so cell and
     // weights are the ones its own deposit would have had (locate = wrap + locate_in_box, and the wrap of a wrapped position
     // is the position).  A value outside [0, L) cannot come from D2; should memory hold one, its index folds to node 0 below.
@@ -110,8 +122,9 @@ __device__ __forceinline__ void push_one(typename P::X& xq, typename P::V& vp, c
   }
   if (STAGE == ST_A) {
     q = drift<P>(q, p, k.c_cur, k, bad);                          // integration.py:42, c1
-  } else if (STAGE == ST_B || STAGE == ST_B2 || kC || kD || kD2) {
-    if (STAGE == ST_B || STAGE == ST_B2) q = drift<P>(q, p, k.c_prev, k, bad);      // q1 again (it is never stored)
+  } else if (STAGE == ST_B || kB2 || kC || kD || kD2) {
+    // q1 again (it is never stored); ST_B2_RD's c_prev is the re-derived drift's, its c1 is c_next's -- the same double
+    if (STAGE == ST_B || kB2) q = drift<P>(q, p, STAGE == ST_B2_RD ? k.c_next : k.c_prev, k, bad);
     substage<P, SHAPE, kFold>(q, p, Es, k.d_cur, k.c_cur, k, bad);
   }
   if (kD2) {                                           // the wrap alone: the deposit of x' is the next sweep B2's
@@ -248,7 +261,8 @@ struct SweepIO {
   // deposit this step's sweep B2 made of the positions it read (rounds 2-3: sweep D deposited them and sweep B carried the solve).
   // post.acc == null: no such workgroup.
   SolveIO post;
-  double* e2;              // [env][Ng + 2] field tile of sweep C_RO, which sweep D_RC / D2_RC re-derives C's output from
+  double* e2;              // [env][Ng + 2] field tile of a sweep that stores no particles (C_RO, B2_RO, D2_RO); the next launch re-derives
+                           // that sweep's output from it (D_RC / D2_RC, C_RB, B2_RD)
 };
 
 constexpr size_t kSweepInlineOffset = 2 * sizeof(void*) + sizeof(SweepIO) + sizeof(SweepArgs);   // sweep_kernel(x, v, io, a, act_inline)
@@ -262,20 +276,26 @@ __global__ __launch_bounds__(BLOCK) void sweep_kernel(typename P::X* __restrict_
   using T = typename P::W;
   using XV = typename P::XV;
   using VV = typename P::VV;
-  constexpr bool kIsB = (STAGE == ST_B || STAGE == ST_B2), kIsC = (STAGE == ST_C || STAGE == ST_C_RO);
+  constexpr bool kIsB2 = (STAGE == ST_B2 || STAGE == ST_B2_RO || STAGE == ST_B2_RD);
+  constexpr bool kIsB = (STAGE == ST_B || kIsB2), kIsC = (STAGE == ST_C || STAGE == ST_C_RO || STAGE == ST_C_RB);
   constexpr bool kRC = (STAGE == ST_D_RC || STAGE == ST_D2_RC);                // re-derives sweep C_RO's output (second field tile)
-  constexpr bool kIsD = (STAGE == ST_D || STAGE == ST_D2 || kRC);
+  constexpr bool kIsD = (STAGE == ST_D || STAGE == ST_D2 || STAGE == ST_D2_RO || kRC);
+  constexpr bool kTileOut = (STAGE == ST_C_RO || STAGE == ST_B2_RO || STAGE == ST_D2_RO);   // stores no particles, but its field tile
+  constexpr bool kTileIn = (kRC || STAGE == ST_C_RB || STAGE == ST_B2_RD);     // re-derives the sweep before it from that tile
   constexpr bool kScheme = (STAGE >= ST_SE && STAGE <= ST_VM);                 // push_scheme's stages
   constexpr bool kGather = (kIsB || kIsC || kIsD || kScheme);
-  constexpr bool kStore = ((kGather && STAGE != ST_C_RO) || STAGE == ST_REFRESH);
-  constexpr bool kStoreV = kGather && STAGE != ST_C_RO;
+  constexpr bool kStore = ((kGather && !kTileOut) || STAGE == ST_REFRESH);
+  constexpr bool kStoreV = kGather && !kTileOut;
   constexpr bool kAhead = !kStore;                                             // a loop without stores requests its tiles one ahead
+  // ... and its whole tiles in the wave-uniform loop below, but for B2_RO on fixed-point positions: four particles per lane through
+  // two deposits on two pairs of tile registers take 66-76 VGPRs there, 54-60 in the per-lane loop alone
+  constexpr bool kUniform = kAhead && !(P::kFixed && STAGE == ST_B2_RO);
   constexpr bool kReadV = (STAGE != ST_PROBE);
-  constexpr bool kFirst = (STAGE != ST_D2 && STAGE != ST_D2_RC && STAGE != ST_VK);   // deposits into the first LDS mesh (-> acc_out)
-  constexpr bool kDual = (kIsD || STAGE == ST_REFRESH || STAGE == ST_B2);      // ... into the second one (-> acc_out2)
+  constexpr bool kFirst = (STAGE != ST_D2 && STAGE != ST_D2_RC && STAGE != ST_D2_RO && STAGE != ST_VK);   // deposits into the first LDS mesh (-> acc_out)
+  constexpr bool kDual = (kIsD || STAGE == ST_REFRESH || kIsB2);               // ... into the second one (-> acc_out2)
   constexpr bool kEnergy = (kIsD || STAGE == ST_REFRESH || kScheme);           // sum of p^2 per workgroup
 
-  // LDS: [R meshes: acc][R meshes: acc2 (dual stages)][field tile Es][sweep C's field tile Es2 (kRC)]; the mesh region is the scratch of the
+  // LDS: [R meshes: acc][R meshes: acc2 (dual stages)][field tile Es][the re-derived sweep's field tile Es2 (kTileIn)]; the mesh region is the scratch of the
   // prologue solve first
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int Ng = a.Ng;
@@ -343,9 +363,11 @@ __global__ __launch_bounds__(BLOCK) void sweep_kernel(typename P::X* __restrict_
                            (io.ext_out && blk == 0) ? io.ext_out + (size_t)env * Ng : nullptr, Ng, ldexp(1.0, -a.fg), a.scale, a.n0, a.dx,
                            reinterpret_cast<double*>(acc2_all), reinterpret_cast<double*>(smem_raw), slot, Es);
   }
-  if (STAGE == ST_C_RO && blk == 0)      // the field tile of this force evaluation, for the sweep that re-derives it
+  // (a sweep that does both -- none does -- would have to read the tile of the sweep before it ahead of storing its own)
+  static_assert(!(kTileOut && kTileIn), "one tile buffer: the sweep that reads a tile is the launch right behind its writer");
+  if (kTileOut && blk == 0)              // the field tile of this force evaluation, for the sweep that re-derives it
     for (int c = tid; c < stride; c += BLOCK) io.e2[(size_t)env * stride + c] = (double)Es[c];
-  if (kRC)                               // (the barrier behind the mesh clearing below covers these LDS writes: kRC is dual)
+  if (kTileIn)                           // (the barrier behind the mesh clearing below covers these LDS writes)
     for (int c = tid; c < stride; c += BLOCK) Es2[c] = (T)io.e2[(size_t)env * stride + c];
   if (kIsD && io.next_act && io.ext_out && blk == 0) {   // (inside a rollout: one workgroup per environment)
     const Control ctl = io.ctl;
@@ -359,7 +381,7 @@ __global__ __launch_bounds__(BLOCK) void sweep_kernel(typename P::X* __restrict_
     if (io.zero0) for (int c = tid; c < Ng; c += BLOCK) io.zero0[z + c] = 0;
     if (io.zero1) for (int c = tid; c < Ng; c += BLOCK) io.zero1[z + c] = 0;
   }
-  if (clear_first || kDual) __syncthreads();
+  if (clear_first || kDual || kTileIn) __syncthreads();
   PIC_STAMP(6);
 
   const int rep = (tid >> 6) & (a.R - 1);
@@ -371,7 +393,7 @@ __global__ __launch_bounds__(BLOCK) void sweep_kernel(typename P::X* __restrict_
   unsigned bad = 0u;
   [[maybe_unused]] int tile = 0;
   const StreamOut xout(xe + begin), vout(ve + begin);
-  if constexpr (kAhead) {
+  if constexpr (kUniform) {
     // The whole tiles of a chunk, nfull of them, are the same for every lane of the workgroup: the tiles whose SUCCESSOR is a whole
     // tile too run here, on a trip count and a tile base that are wave-uniform -- no per-lane index, end test or clamped address,
     // and the next tile's loads leave unconditionally from a pointer that advances by a constant.  Two tiles per trip, on two

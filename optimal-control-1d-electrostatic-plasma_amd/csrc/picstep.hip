@@ -292,6 +292,7 @@ struct __attribute__((visibility("hidden"))) pic_handle : LaunchPlan {      // t
   hipStream_t stream = nullptr;       // the stream every call works on (own_stream, or the caller's)
   StreamOwner own_stream;             // created by pic_create (declared ahead of the buffers: destroyed after them)
   bool readonly_c = false;            // whole steps run sweeps C_RO and D_RC / D2_RC (pic_set_readonly_c, or readonly_auto)
+  bool alternate_stores = false;      // ... and every second inner step of a call stores once (pic_set_alternate_stores, or alternate_auto)
   PlacementStats place{};             // what the search for an (x, v) placement did, all legs together (pic_placement_stats)
   PlacementState place_state{};       // what a later leg of it needs to know (placement_leg, resume_placement)
   Recorder rec{};                     // pic_record_*: reductions recorded after every rec.stride-th step (advance, pic_step_stage)
@@ -425,8 +426,9 @@ hipError_t launch_status(pic_handle* h) {
 
 template <typename P, typename A, int SHAPE, int STAGE>
 void launch_sweep_t(pic_handle* h, const SweepIO& io, void* x, void* v, const SweepArgs& a, const InlineDoubles& act) {
-  dim3 grid(h->nblk + (((STAGE == ST_C || STAGE == ST_C_RO) && io.post.acc) ? 1 : 0), h->cfg.num_envs);
-  const size_t lds = (STAGE == ST_D_RC || STAGE == ST_D2_RC) ? h->sweep_lds_rc : h->sweep_lds;
+  dim3 grid(h->nblk + (((STAGE == ST_C || STAGE == ST_C_RO || STAGE == ST_C_RB) && io.post.acc) ? 1 : 0), h->cfg.num_envs);
+  constexpr bool two_tiles = STAGE == ST_D_RC || STAGE == ST_D2_RC || STAGE == ST_C_RB || STAGE == ST_B2_RD;
+  const size_t lds = two_tiles ? h->sweep_lds_rc : h->sweep_lds;
   hipLaunchKernelGGL((sweep_kernel<P, A, SHAPE, STAGE>), grid, dim3(BLOCK), lds, h->stream,
                      static_cast<typename P::X*>(x), static_cast<typename P::V*>(v), io, a, act);
 }
@@ -448,6 +450,10 @@ void launch_sweep_s(pic_handle* h, const SweepIO& io, int stage, void* x, void* 
     case ST_C_RO: launch_sweep_t<P, A, SHAPE, ST_C_RO>(h, io, x, v, a, act); break;
     case ST_D_RC: launch_sweep_t<P, A, SHAPE, ST_D_RC>(h, io, x, v, a, act); break;
     case ST_D2_RC: launch_sweep_t<P, A, SHAPE, ST_D2_RC>(h, io, x, v, a, act); break;
+    case ST_B2_RO: launch_sweep_t<P, A, SHAPE, ST_B2_RO>(h, io, x, v, a, act); break;
+    case ST_C_RB: launch_sweep_t<P, A, SHAPE, ST_C_RB>(h, io, x, v, a, act); break;
+    case ST_D2_RO: launch_sweep_t<P, A, SHAPE, ST_D2_RO>(h, io, x, v, a, act); break;
+    case ST_B2_RD: launch_sweep_t<P, A, SHAPE, ST_B2_RD>(h, io, x, v, a, act); break;
     default: launch_sweep_t<P, A, SHAPE, ST_PROBE>(h, io, x, v, a, act); break;
   }
 }
@@ -674,7 +680,8 @@ void run_launch(pic_handle* h, const CallCtx& cx, const Launch& d) {
   a.S = h->S; a.sub = (long long)E * h->cfg.Ng;
   a.c_prev = d.c_prev; a.c_cur = d.c_cur; a.d_cur = d.d_cur; a.c_next = h->cs[0];
   const bool rc = d.stage == ST_D_RC || d.stage == ST_D2_RC;
-  a.d_prev = rc ? h->ds[2] : 0.0;      // the sub-stage these sweeps re-derive is sweep C's: kick d3, drift c3 (c_prev)
+  // the kick of the sub-stage a sweep re-derives (its drift is c_prev): sweep C's in D_RC / D2_RC, sweep B's in C_RB, sweep D's in B2_RD
+  a.d_prev = rc ? h->ds[2] : d.stage == ST_C_RB ? h->ds[1] : d.stage == ST_B2_RD ? h->ds[3] : 0.0;
   SweepIO io{};
   io.acc_in = row(d.in);
   io.ctl = ctl;
@@ -700,8 +707,9 @@ void run_launch(pic_handle* h, const CallCtx& cx, const Launch& d) {
   // (the particle sweeps of the other integrators -- Verlet's opening sweep is a sweep C -- count in the eighth kind)
   const int stage = d.stage;
   const bool scheme_sweep = (stage >= ST_SE && stage <= ST_VM) || (stage == ST_C && h->scheme != PIC_YOSHIDA4);
-  prof_begin(h, scheme_sweep ? 7 : stage <= ST_D ? stage : stage == ST_B2 ? (int)ST_B : stage == ST_C_RO ? (int)ST_C
-                : (stage == ST_D2 || rc) ? (int)ST_D : 5);
+  const bool b2 = stage == ST_B2 || stage == ST_B2_RO || stage == ST_B2_RD;
+  prof_begin(h, scheme_sweep ? 7 : stage <= ST_D ? stage : b2 ? (int)ST_B : (stage == ST_C_RO || stage == ST_C_RB) ? (int)ST_C
+                : (stage == ST_D2 || stage == ST_D2_RO || rc) ? (int)ST_D : 5);
   with_format(h, [&](auto p) { launch_sweep_p<decltype(p)>(h, io, stage, x, v, a, act); });
   prof_end(h);
 }
@@ -903,6 +911,7 @@ int pic_create(const pic_config* cfg, pic_handle** out) {
   h->cfg = *cfg;
   if (int rc = plan_launch(*cfg, ncu, h, &err)) return fail(nullptr, rc, err);      // (host_plan.h: geometry, LDS, schedule)
   h->readonly_c = h->readonly_auto;
+  h->alternate_stores = h->alternate_auto;
   const size_t stride = (size_t)cfg->Ng + 2;
 
   auto failed = [](hipError_t e, const char* what) {
@@ -1075,6 +1084,7 @@ static CallShape call_shape(const pic_handle* h, const StepControl& sc) {
   CallShape p;
   p.scheme = h->scheme; p.cs = h->cs; p.ds = h->ds;
   p.light_inner_steps = h->light_inner_steps; p.readonly_c = h->readonly_c;
+  p.alternate_stores = h->alternate_stores;
   p.feedback = sc.fb.M > 0; p.action = sc.ctl.act != nullptr;
   p.per_step_field = sc.ext_step != 0; p.per_step_action = sc.act_step != 0;
   return p;
@@ -1261,6 +1271,15 @@ int pic_set_readonly_c(pic_handle* h, int mode) {
   if (mode == PIC_READONLY_ON && !h->sweep_lds_rc)
     return fail(h, PIC_EINVAL, "pic_set_readonly_c: Ng too large for the second field tile of sweep D_RC");
   h->readonly_c = mode == PIC_READONLY_AUTO ? h->readonly_auto : mode == PIC_READONLY_ON;
+  return PIC_OK;
+}
+
+int pic_set_alternate_stores(pic_handle* h, int mode) {
+  if (!h) return PIC_EINVAL;
+  if (mode < PIC_ALTERNATE_AUTO || mode > PIC_ALTERNATE_ON) return fail(h, PIC_EINVAL, "pic_set_alternate_stores: unknown mode");
+  if (mode == PIC_ALTERNATE_ON && !h->sweep_lds_rc)
+    return fail(h, PIC_EINVAL, "pic_set_alternate_stores: Ng too large for the second field tile of sweeps C_RB and B2_RD");
+  h->alternate_stores = mode == PIC_ALTERNATE_AUTO ? h->alternate_auto : mode == PIC_ALTERNATE_ON;
   return PIC_OK;
 }
 

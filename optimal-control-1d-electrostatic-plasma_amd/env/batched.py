@@ -24,7 +24,8 @@ class BatchedPIC(TapePIC):
     def __init__(self, num_envs: int, N: int, N_mesh: int, n0: float = 1.0, L: float = 50.0, dt: float = 0.1,
                  gamma: float = 5.0, interpol: str = "CIC", device: int = 0, dtype="float64", accum_dtype=None,
                  blocks_per_env: int = 0, verbose: bool = False, env_index_base: int = 0, position_dtype=None,
-                 placement: str = "auto", placement_ms: int = 0, integrator="symplectic_4th_order", readonly_c: str = "auto"):
+                 placement: str = "auto", placement_ms: int = 0, integrator="symplectic_4th_order", readonly_c: str = "auto",
+                 alternate_stores: str = "auto"):
         self.num_envs, self.N, self.N_mesh = int(num_envs), int(N), int(N_mesh)
         self.n0, self.L, self.gamma, self.interpol = n0, L, gamma, interpol
         self.dx = L / N_mesh
@@ -38,7 +39,7 @@ class BatchedPIC(TapePIC):
         self.dtype = np.dtype(dtype)
         self._h = _abi.Handle(self.N, self.N_mesh, self.num_envs, L, n0, self.dt, gamma, self.dtype, accum_dtype,
                               interpol, device, blocks_per_env, env_index_base, position_dtype, placement, placement_ms,
-                              integrator, readonly_c)
+                              integrator, readonly_c, alternate_stores)
         self.integrator = _abi.INTEGRATOR_NAMES[_abi.integrator_id(integrator)]
         # what another BatchedPIC of the same physics is made with (env.plan.MPPI builds its samples from it)
         self._like = dict(N=self.N, N_mesh=self.N_mesh, n0=n0, L=L, dt=self.dt, gamma=gamma, interpol=interpol, device=device,
