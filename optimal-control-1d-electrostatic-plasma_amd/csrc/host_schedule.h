@@ -74,7 +74,7 @@ enum ExtRole : int { EXT_NONE = 0, EXT_THIS = 1, EXT_NEXT = 2 };     // the buff
 // One launch: a sweep over all environments, or a field solve of its own.  Slots and roles, never device pointers.
 struct Launch {
   int stage = ST_SOLVE;                      // a Stage, or ST_SOLVE
-  double c_prev = 0, c_cur = 0, d_cur = 0;   // a sweep's stage coefficients
+  double c_prev = 0, d_prev = 0, c_cur = 0, d_cur = 0;   // a sweep's stage coefficients (d_prev: the kick of the sub-stage it re-derives, or 0)
   int in = -1;                               // ring row the gather field is solved from; a solve: the row it solves
   int fill[2] = {-1, -1};                    // rows receiving the first / second deposit (RING: the probes' row)
   int unclean = 0;                           // bit k: fill[k] came from Ring::take's guard and must be cleared before the launch
@@ -126,8 +126,7 @@ inline int take(Schedule& S, Launch& l, int k) {
 // the sweep also clears up to two retired ring rows for later use
 template <typename F>
 void emit_sweep(Schedule& S, Launch& l, F& emit) {
-  const bool push = l.stage != ST_REFRESH && l.stage != ST_PROBE;
-  l.reverse = push ? (S.sweep_parity ^= 1) : 0;
+  l.reverse = pushes(stage_traits(l.stage)) ? (S.sweep_parity ^= 1) : 0;
   l.turn = S.ext_turn;
   for (int k = 0; k < 2; ++k) l.clear[k] = S.ring.pop_retired();
   emit(static_cast<const Launch&>(l));
@@ -200,6 +199,7 @@ void yoshida_stages(Schedule& S, const CallShape& p, int from, int upto, const S
       }
       l.stage = !L.refresh_pending ? ST_B : st.lean ? ST_B2_RO : st.after_lean ? ST_B2_RD : ST_B2;
       l.c_prev = l.stage == ST_B2_RD ? c[3] : c[0]; l.c_cur = c[1]; l.d_cur = d[1];     // (B2_RD: the drift of sweep D, which it re-derives)
+      l.d_prev = kick_again(stage_traits(l.stage), d);
       l.in = S.q_slot;
       l.ctl = share && st.field_ready ? CTL_SHARED : CTL_OWN;
       l.ext_out = share && !st.field_ready ? EXT_THIS : EXT_NONE;
@@ -215,6 +215,7 @@ void yoshida_stages(Schedule& S, const CallShape& p, int from, int upto, const S
     } else if (stage == 2) {
       l.stage = st.lean ? ST_C_RB : ro ? ST_C_RO : ST_C;
       l.c_prev = st.lean ? c[1] : 0.0; l.c_cur = c[2]; l.d_cur = d[2];                  // (C_RB: the drift of sweep B, which it re-derives)
+      l.d_prev = kick_again(stage_traits(l.stage), d);
       l.in = S.stage_slot;
       l.ctl = later;
       l.post = L.post;
@@ -234,14 +235,14 @@ void yoshida_stages(Schedule& S, const CallShape& p, int from, int upto, const S
       if (st.another && (p.light_inner_steps || st.alternate)) {
         // an inner step of a call: nothing can see its post-step fields before the next step has started, so the deposit they come
         // from is left to that step's sweep B2 (sweep D is the one sweep bound by VALU issue: 336 -> 321 us at config 2, B 320 -> 322)
-        l.stage = st.lean ? ST_D2_RO : ro ? ST_D2_RC : ST_D2;
+        l.stage = st.lean ? ST_D2_RO : ro ? ST_D2_RC : ST_D2; l.d_prev = kick_again(stage_traits(l.stage), d);
         const int qn = take(S, l, 1);
         emit_sweep(S, l, emit);
         L.refresh_pending = true;
         L.post_step = st.step;
         S.q_slot = qn;
       } else {
-        l.stage = ro ? ST_D_RC : ST_D;
+        l.stage = ro ? ST_D_RC : ST_D; l.d_prev = kick_again(stage_traits(l.stage), d);
         const int f = take(S, l, 0), qn = take(S, l, 1);
         emit_sweep(S, l, emit);
         // (a small state's inner step: the full sweep D, its solve still not a launch -- it rides with the next step's sweep C)

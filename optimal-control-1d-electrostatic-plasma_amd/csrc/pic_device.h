@@ -116,8 +116,7 @@ struct SweepArgs {
   long long sub;      // elements from one sub-row to the next (num_envs * Ng)
   double magic;       // 1.5 * 2^(52 - fg): (w + magic) holds round(w 2^fg) in its low mantissa bits
   double L, dx, rdx, dt;   // rdx = 1/dx (float particles: 1/(float)dx)
-  double c_prev, c_cur, d_cur, c_next, d_prev;   // c_prev, d_prev: drift and kick of the sub-stage a sweep re-derives (ST_D_RC, ST_D2_RC,
-                                                 // ST_C_RB, ST_B2_RD; ST_B, ST_B2, ST_B2_RO: c_prev is c1); c_next is c1 in every sweep
+  double c_prev, c_cur, d_cur, c_next, d_prev;   // c_prev, d_prev: drift and kick of the sub-stage a sweep re-derives (a sweep B that re-derives none: c_prev is c1); c_next is c1 in every sweep
   double scale, n0;   // density scale n0 L / N / dx and mean density, for the in-prologue field solve
   double to_units;    // 2^32 / L: fixed-point position units per length (PosU32)
   double N_over_L;    // PE = PE_reward N / L (util.py:130)

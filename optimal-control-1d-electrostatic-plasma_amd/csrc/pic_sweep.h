@@ -78,18 +78,13 @@ __device__ __forceinline__ void substage(typename P::X& q, typename P::V& p, con
 // One particle through one sub-stage.  Stages D / REFRESH also deposit the NEXT step's first drift
 // position q1 = x' + (c1 p) dt into a second mesh (acc2), which is exactly what sweep A of the next
 // step would deposit from the stored x', p -- so that sweep (a full read of x and v) is skipped.
-// ST_C_RO is ST_C here (the sweep does not store); ST_D_RC / ST_D2_RC first run sweep C's sub-stage on (q2, v1) from C's field
-// tile Es2, then are ST_D / ST_D2.  That repeated drift and locate count into a scratch counter: C counted them already.
-// ST_B2_RO and ST_D2_RO are ST_B2 and ST_D2 here; ST_C_RB and ST_B2_RD first repeat what those did not store, from their tile in Es2.
+// A stage that does not store is the storing one here; the stage behind it first repeats what it did not store, from its field
+// tile Es2 (stage_traits: rederives).  That repeated drift and locate count into a scratch counter: they were counted already.
 template <typename P, typename A, int SHAPE, int STAGE>
 __device__ __forceinline__ void push_one(typename P::X& xq, typename P::V& vp, const typename P::W* __restrict__ Es,
                                          const typename P::W* __restrict__ Es2, A* __restrict__ acc, A* __restrict__ acc2,
                                          const Consts<P>& k, double& ke, unsigned& bad) {
-  constexpr bool kB2 = (STAGE == ST_B2 || STAGE == ST_B2_RO || STAGE == ST_B2_RD);
-  constexpr bool kC = (STAGE == ST_C || STAGE == ST_C_RO || STAGE == ST_C_RB);
-  constexpr bool kRC = (STAGE == ST_D_RC || STAGE == ST_D2_RC);
-  constexpr bool kD = (STAGE == ST_D || STAGE == ST_D_RC);
-  constexpr bool kD2 = (STAGE == ST_D2 || STAGE == ST_D2_RC || STAGE == ST_D2_RO);
+  constexpr StageTraits kT = stage_traits(STAGE);
   constexpr bool kFold = kFoldIndex<A, SHAPE>;           // every locate<.., kFold> below comes behind a wrap: 0 <= j <= Ng
   using T = typename P::W;
   T w[3];
@@ -98,21 +93,13 @@ __device__ __forceinline__ void push_one(typename P::X& xq, typename P::V& vp, c
   unsigned frac;
   typename P::X q = xq;
   typename P::V p = vp;
-  if (kRC) {
+  if (reads_tile(kT)) {                                  // the sub-stage of the sweep before, which did not store, from its tile Es2
     unsigned again = 0u;
-    substage<P, SHAPE, kFold>(q, p, Es2, k.d_prev, k.c_prev, k, again);
+    if (kT.rederives == AR_B) q = drift<P>(q, p, k.c_next, k, again);       // sweep B2_RO's drift on the stored x', v' first: q1 (c_next is c1 in every sweep)
+    substage<P, SHAPE, kFold>(q, p, Es2, k.d_prev, k.c_prev, k, again);     // (q2, v1) behind sweeps B2_RO and C_RO, (q3, v2) behind D2_RO
+    if constexpr (kT.rederives == AR_D && !P::kFixed) q = wrap_periodic(q, k.L, again);   // ... and sweep D2_RO's wrap: the x', v' it did not store
   }
-  if (STAGE == ST_B2_RD) {                               // sweep D2_RO's sub-stage and wrap on (q3, v2): the x', v' it did not store
-    unsigned again = 0u;
-    substage<P, SHAPE, kFold>(q, p, Es2, k.d_prev, k.c_prev, k, again);
-    if constexpr (!P::kFixed) q = wrap_periodic(q, k.L, again);
-  }
-  if (STAGE == ST_C_RB) {                                // sweep B2_RO's drift and sub-stage on the stored x', v': (q2, v1)
-    unsigned again = 0u;
-    q = drift<P>(q, p, k.c_next, k, again);              // q1 (c_next is c1 in every sweep)
-    substage<P, SHAPE, kFold>(q, p, Es2, k.d_prev, k.c_prev, k, again);
-  }
-  if (kB2) {
+  if (kT.second == M2_INPUT) {
     // The post-step deposit of the PREVIOUS step (pic.py:145): q is the x' that step's sweep D2 wrapped and stored, so cell and
     // weights are the ones its own deposit would have had (locate = wrap + locate_in_box, and the wrap of a wrapped position
     // is the position).  A value outside [0, L) cannot come from D2; should memory hold one, its index folds to node 0 below.
@@ -120,21 +107,21 @@ __device__ __forceinline__ void push_one(typename P::X& xq, typename P::V& vp, c
     else locate_in_box<P, SHAPE>(q, k, j, w, frac);               // (straight from memory, no wrap in front: folds)
     deposit<A, P, SHAPE>(acc2, j, w, frac, k.magic);
   }
-  if (STAGE == ST_A) {
+  if (kT.arith == AR_A) {
     q = drift<P>(q, p, k.c_cur, k, bad);                          // integration.py:42, c1
-  } else if (STAGE == ST_B || kB2 || kC || kD || kD2) {
+  } else if (gathers(kT)) {
     // q1 again (it is never stored); ST_B2_RD's c_prev is the re-derived drift's, its c1 is c_next's -- the same double
-    if (STAGE == ST_B || kB2) q = drift<P>(q, p, STAGE == ST_B2_RD ? k.c_next : k.c_prev, k, bad);
+    if (kT.arith == AR_B) q = drift<P>(q, p, kT.rederives == AR_D ? k.c_next : k.c_prev, k, bad);
     substage<P, SHAPE, kFold>(q, p, Es, k.d_cur, k.c_cur, k, bad);
   }
-  if (kD2) {                                           // the wrap alone: the deposit of x' is the next sweep B2's
+  if (wrap_only(kT)) {                                 // the wrap alone: the deposit of x' is the next sweep B2's
     if constexpr (P::kFixed) xw = q;
     else xw = wrap_periodic(q, k.L, bad);
   } else {
     locate<P, SHAPE, kFold>(q, k, xw, j, w, frac, bad);
     deposit<A, P, SHAPE>(acc, j, w, frac, k.magic);
   }
-  if (kD || kD2 || STAGE == ST_REFRESH) {
+  if (kT.second == M2_NEXT_Q1) {
     q = xw;                                                       // pic.py:139 (+ util.py:51)
     ke += (double)p * (double)p;
     const typename P::X qn = drift<P>(q, p, k.c_next, k, bad);    // next step's q1 (integration.py:42, c1)
@@ -171,7 +158,7 @@ __device__ __forceinline__ void push_scheme(typename P::X& xq, typename P::V& vp
     p = p + (V)((k.d_cur * (-E)) * k.dt);                        // v + (1 (-E)) dt = v + dt (-E)
   } else {
     p = p + (V)((k.d_cur * (-E)) * k.dt);                        // integration.py:32
-    if (STAGE == ST_VK || STAGE == ST_VM) {
+    if (STAGE != ST_SE) {                                        // (VK, VM)
       q = xw;                                                    // pic.py:139 (+ util.py:51): the step ends here
       ke += (double)p * (double)p;
     }
@@ -276,24 +263,19 @@ __global__ __launch_bounds__(BLOCK) void sweep_kernel(typename P::X* __restrict_
   using T = typename P::W;
   using XV = typename P::XV;
   using VV = typename P::VV;
-  constexpr bool kIsB2 = (STAGE == ST_B2 || STAGE == ST_B2_RO || STAGE == ST_B2_RD);
-  constexpr bool kIsB = (STAGE == ST_B || kIsB2), kIsC = (STAGE == ST_C || STAGE == ST_C_RO || STAGE == ST_C_RB);
-  constexpr bool kRC = (STAGE == ST_D_RC || STAGE == ST_D2_RC);                // re-derives sweep C_RO's output (second field tile)
-  constexpr bool kIsD = (STAGE == ST_D || STAGE == ST_D2 || STAGE == ST_D2_RO || kRC);
-  constexpr bool kTileOut = (STAGE == ST_C_RO || STAGE == ST_B2_RO || STAGE == ST_D2_RO);   // stores no particles, but its field tile
-  constexpr bool kTileIn = (kRC || STAGE == ST_C_RB || STAGE == ST_B2_RD);     // re-derives the sweep before it from that tile
-  constexpr bool kScheme = (STAGE >= ST_SE && STAGE <= ST_VM);                 // push_scheme's stages
-  constexpr bool kGather = (kIsB || kIsC || kIsD || kScheme);
-  constexpr bool kStore = ((kGather && !kTileOut) || STAGE == ST_REFRESH);
-  constexpr bool kStoreV = kGather && !kTileOut;
+  constexpr StageTraits kT = stage_traits(STAGE);
+  constexpr bool kTileOut = leaves_tile(kT);                                   // stores no particles, but its field tile
+  constexpr bool kTileIn = reads_tile(kT);                                     // re-derives the sweep before it from that tile
+  constexpr bool kScheme = kT.arith == AR_SCHEME;                              // push_scheme's stages
+  constexpr bool kGather = gathers(kT);
+  constexpr bool kStore = kT.stores;
+  constexpr bool kStoreV = kStore && kGather;                                  // (REFRESH stores its wrapped x alone)
   constexpr bool kAhead = !kStore;                                             // a loop without stores requests its tiles one ahead
   // ... and its whole tiles in the wave-uniform loop below, but for B2_RO on fixed-point positions: four particles per lane through
   // two deposits on two pairs of tile registers take 66-76 VGPRs there, 54-60 in the per-lane loop alone
   constexpr bool kUniform = kAhead && !(P::kFixed && STAGE == ST_B2_RO);
-  constexpr bool kReadV = (STAGE != ST_PROBE);
-  constexpr bool kFirst = (STAGE != ST_D2 && STAGE != ST_D2_RC && STAGE != ST_D2_RO && STAGE != ST_VK);   // deposits into the first LDS mesh (-> acc_out)
-  constexpr bool kDual = (kIsD || STAGE == ST_REFRESH || kIsB2);               // ... into the second one (-> acc_out2)
-  constexpr bool kEnergy = (kIsD || STAGE == ST_REFRESH || kScheme);           // sum of p^2 per workgroup
+  constexpr bool kReadV = reads_v(kT);
+  constexpr bool kDual = kT.second != M2_NONE;                                 // deposits into the second LDS mesh as well (-> acc_out2)
 
   // LDS: [R meshes: acc][R meshes: acc2 (dual stages)][field tile Es][the re-derived sweep's field tile Es2 (kTileIn)]; the mesh region is the scratch of the
   // prologue solve first
@@ -309,7 +291,7 @@ __global__ __launch_bounds__(BLOCK) void sweep_kernel(typename P::X* __restrict_
   static_assert(sizeof(red) + sizeof(slot) == kSweepStaticLds, "pic_create adds the static LDS to the dynamic part it sizes");
   PIC_STAMP(0);
 
-  if (kIsC && blockIdx.x == (unsigned)a.nblk) {      // the extra workgroup of its environment (host: only with io.post.acc)
+  if (carries_solve(kT) && blockIdx.x == (unsigned)a.nblk) {      // the extra workgroup of its environment (host: only with io.post.acc)
     // its arguments are read from the kernel-argument segment here, by this workgroup alone: held in scalar registers from the
     // kernel's entry on they cost every other workgroup of the sweep a wave of occupancy (pic_device.h: kernarg_at)
     SolveIO post = kernarg_at<SolveIO>(2 * sizeof(void*) + offsetof(SweepIO, post));   // x, v, io, a
@@ -363,13 +345,12 @@ __global__ __launch_bounds__(BLOCK) void sweep_kernel(typename P::X* __restrict_
                            (io.ext_out && blk == 0) ? io.ext_out + (size_t)env * Ng : nullptr, Ng, ldexp(1.0, -a.fg), a.scale, a.n0, a.dx,
                            reinterpret_cast<double*>(acc2_all), reinterpret_cast<double*>(smem_raw), slot, Es);
   }
-  // (a sweep that does both -- none does -- would have to read the tile of the sweep before it ahead of storing its own)
-  static_assert(!(kTileOut && kTileIn), "one tile buffer: the sweep that reads a tile is the launch right behind its writer");
-  if (kTileOut && blk == 0)              // the field tile of this force evaluation, for the sweep that re-derives it
+  // (never both, stage_traits_hold: there is one tile buffer, and the sweep that reads a tile is the launch right behind its writer)
+  if (kTileOut && blk == 0)             // the field tile of this force evaluation, for the sweep that re-derives it
     for (int c = tid; c < stride; c += BLOCK) io.e2[(size_t)env * stride + c] = (double)Es[c];
   if (kTileIn)                           // (the barrier behind the mesh clearing below covers these LDS writes)
     for (int c = tid; c < stride; c += BLOCK) Es2[c] = (T)io.e2[(size_t)env * stride + c];
-  if (kIsD && io.next_act && io.ext_out && blk == 0) {   // (inside a rollout: one workgroup per environment)
+  if (kT.arith == AR_D && io.next_act && io.ext_out && blk == 0) {   // (inside a rollout: one workgroup per environment)
     const Control ctl = io.ctl;
     for (int j = tid; j < Ng; j += BLOCK)
       io.ext_out[(size_t)env * Ng + j] = actuator_field(ctl.basis, ctl.basis + (size_t)Ng * ctl.M, io.next_act + (size_t)env * 2 * ctl.M, j, ctl.M);
@@ -513,11 +494,11 @@ __global__ __launch_bounds__(BLOCK) void sweep_kernel(typename P::X* __restrict_
   PIC_STAMP(24);
 
   const size_t sub_row = (size_t)(blk % a.S) * a.sub + (size_t)env * Ng;
-  if (kFirst) flush_mesh<A, SHAPE>(acc_all, a.R, stride, Ng, a.fg, io.acc_out + sub_row);
+  if (kT.first) flush_mesh<A, SHAPE>(acc_all, a.R, stride, Ng, a.fg, io.acc_out + sub_row);
   if (kDual) flush_mesh<A, SHAPE>(acc2_all, a.R, stride, Ng, a.fg, io.acc_out2 + sub_row);
   PIC_STAMP(25);
 
-  if (kEnergy) {
+  if (ends_step(kT)) {                                   // sum of p^2 per workgroup
     double w = wave_sum(ke);
     if ((tid & 63) == 0) red[tid >> 6] = w;
     __syncthreads();

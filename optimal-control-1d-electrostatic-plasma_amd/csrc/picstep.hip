@@ -60,6 +60,7 @@
 #include <string>
 #include <thread>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "picstep.h"
@@ -426,52 +427,34 @@ hipError_t launch_status(pic_handle* h) {
 
 template <typename P, typename A, int SHAPE, int STAGE>
 void launch_sweep_t(pic_handle* h, const SweepIO& io, void* x, void* v, const SweepArgs& a, const InlineDoubles& act) {
-  dim3 grid(h->nblk + (((STAGE == ST_C || STAGE == ST_C_RO || STAGE == ST_C_RB) && io.post.acc) ? 1 : 0), h->cfg.num_envs);
-  constexpr bool two_tiles = STAGE == ST_D_RC || STAGE == ST_D2_RC || STAGE == ST_C_RB || STAGE == ST_B2_RD;
-  const size_t lds = two_tiles ? h->sweep_lds_rc : h->sweep_lds;
+  constexpr StageTraits t = stage_traits(STAGE);
+  dim3 grid(h->nblk + ((carries_solve(t) && io.post.acc) ? 1 : 0), h->cfg.num_envs);
+  const size_t lds = reads_tile(t) ? h->sweep_lds_rc : h->sweep_lds;
   hipLaunchKernelGGL((sweep_kernel<P, A, SHAPE, STAGE>), grid, dim3(BLOCK), lds, h->stream,
                      static_cast<typename P::X*>(x), static_cast<typename P::V*>(v), io, a, act);
 }
 
-template <typename P, typename A, int SHAPE>
-void launch_sweep_s(pic_handle* h, const SweepIO& io, int stage, void* x, void* v, const SweepArgs& a, const InlineDoubles& act) {
-  switch (stage) {
-    case ST_A: launch_sweep_t<P, A, SHAPE, ST_A>(h, io, x, v, a, act); break;
-    case ST_B: launch_sweep_t<P, A, SHAPE, ST_B>(h, io, x, v, a, act); break;
-    case ST_C: launch_sweep_t<P, A, SHAPE, ST_C>(h, io, x, v, a, act); break;
-    case ST_D: launch_sweep_t<P, A, SHAPE, ST_D>(h, io, x, v, a, act); break;
-    case ST_REFRESH: launch_sweep_t<P, A, SHAPE, ST_REFRESH>(h, io, x, v, a, act); break;
-    case ST_B2: launch_sweep_t<P, A, SHAPE, ST_B2>(h, io, x, v, a, act); break;
-    case ST_D2: launch_sweep_t<P, A, SHAPE, ST_D2>(h, io, x, v, a, act); break;
-    case ST_SE: launch_sweep_t<P, A, SHAPE, ST_SE>(h, io, x, v, a, act); break;
-    case ST_FE: launch_sweep_t<P, A, SHAPE, ST_FE>(h, io, x, v, a, act); break;
-    case ST_VK: launch_sweep_t<P, A, SHAPE, ST_VK>(h, io, x, v, a, act); break;
-    case ST_VM: launch_sweep_t<P, A, SHAPE, ST_VM>(h, io, x, v, a, act); break;
-    case ST_C_RO: launch_sweep_t<P, A, SHAPE, ST_C_RO>(h, io, x, v, a, act); break;
-    case ST_D_RC: launch_sweep_t<P, A, SHAPE, ST_D_RC>(h, io, x, v, a, act); break;
-    case ST_D2_RC: launch_sweep_t<P, A, SHAPE, ST_D2_RC>(h, io, x, v, a, act); break;
-    case ST_B2_RO: launch_sweep_t<P, A, SHAPE, ST_B2_RO>(h, io, x, v, a, act); break;
-    case ST_C_RB: launch_sweep_t<P, A, SHAPE, ST_C_RB>(h, io, x, v, a, act); break;
-    case ST_D2_RO: launch_sweep_t<P, A, SHAPE, ST_D2_RO>(h, io, x, v, a, act); break;
-    case ST_B2_RD: launch_sweep_t<P, A, SHAPE, ST_B2_RD>(h, io, x, v, a, act); break;
-    default: launch_sweep_t<P, A, SHAPE, ST_PROBE>(h, io, x, v, a, act); break;
-  }
+// the instantiation for `stage` among those for S... = every Stage, 0 .. kStages - 1 (the step schedule hands on no other)
+template <typename P, typename A, int SHAPE, int... S>
+void launch_sweep_s(pic_handle* h, const SweepIO& io, int stage, void* x, void* v, const SweepArgs& a, const InlineDoubles& act, std::integer_sequence<int, S...>) {
+  ((stage == S ? launch_sweep_t<P, A, SHAPE, S>(h, io, x, v, a, act) : void()), ...);
 }
 
 template <typename P>
 void launch_sweep_p(pic_handle* h, const SweepIO& io, int stage, void* x, void* v, const SweepArgs& a, const InlineDoubles& act) {
   const bool tsc = h->cfg.interpol == PIC_TSC;
+  const std::make_integer_sequence<int, kStages> all{};
   if constexpr (std::is_same<P, PosF64>::value) {
     if (h->acc_kind == PIC_ACC_F64) {
-      if (tsc) launch_sweep_s<P, double, PIC_TSC>(h, io, stage, x, v, a, act);
-      else launch_sweep_s<P, double, PIC_CIC>(h, io, stage, x, v, a, act);
+      if (tsc) launch_sweep_s<P, double, PIC_TSC>(h, io, stage, x, v, a, act, all);
+      else launch_sweep_s<P, double, PIC_CIC>(h, io, stage, x, v, a, act, all);
       return;
     }
   } else {
-    if (h->acc_kind == PIC_ACC_PACKED) { launch_sweep_s<P, fix_t, PIC_CIC>(h, io, stage, x, v, a, act); return; }
+    if (h->acc_kind == PIC_ACC_PACKED) { launch_sweep_s<P, fix_t, PIC_CIC>(h, io, stage, x, v, a, act, all); return; }
   }
-  if (tsc) launch_sweep_s<P, acc_t, PIC_TSC>(h, io, stage, x, v, a, act);
-  else launch_sweep_s<P, acc_t, PIC_CIC>(h, io, stage, x, v, a, act);
+  if (tsc) launch_sweep_s<P, acc_t, PIC_TSC>(h, io, stage, x, v, a, act, all);
+  else launch_sweep_s<P, acc_t, PIC_CIC>(h, io, stage, x, v, a, act, all);
 }
 
 // Per-launch HIP-event brackets on the handle's stream.  Events come from a pool that is only grown
@@ -678,10 +661,7 @@ void run_launch(pic_handle* h, const CallCtx& cx, const Launch& d) {
   a.act_inline = (ctl.act && cx.sc->inline_n > 0) ? 1 : 0;      // the held action rides in the sweep's argument block
   a.reverse = d.reverse;
   a.S = h->S; a.sub = (long long)E * h->cfg.Ng;
-  a.c_prev = d.c_prev; a.c_cur = d.c_cur; a.d_cur = d.d_cur; a.c_next = h->cs[0];
-  const bool rc = d.stage == ST_D_RC || d.stage == ST_D2_RC;
-  // the kick of the sub-stage a sweep re-derives (its drift is c_prev): sweep C's in D_RC / D2_RC, sweep B's in C_RB, sweep D's in B2_RD
-  a.d_prev = rc ? h->ds[2] : d.stage == ST_C_RB ? h->ds[1] : d.stage == ST_B2_RD ? h->ds[3] : 0.0;
+  a.c_prev = d.c_prev; a.d_prev = d.d_prev; a.c_cur = d.c_cur; a.d_cur = d.d_cur; a.c_next = h->cs[0];
   SweepIO io{};
   io.acc_in = row(d.in);
   io.ctl = ctl;
@@ -705,12 +685,8 @@ void run_launch(pic_handle* h, const CallCtx& cx, const Launch& d) {
   static const InlineDoubles none{};
   const InlineDoubles& act = a.act_inline ? cx.sc->inline_act : none;
   // (the particle sweeps of the other integrators -- Verlet's opening sweep is a sweep C -- count in the eighth kind)
-  const int stage = d.stage;
-  const bool scheme_sweep = (stage >= ST_SE && stage <= ST_VM) || (stage == ST_C && h->scheme != PIC_YOSHIDA4);
-  const bool b2 = stage == ST_B2 || stage == ST_B2_RO || stage == ST_B2_RD;
-  prof_begin(h, scheme_sweep ? 7 : stage <= ST_D ? stage : b2 ? (int)ST_B : (stage == ST_C_RO || stage == ST_C_RB) ? (int)ST_C
-                : (stage == ST_D2 || stage == ST_D2_RO || rc) ? (int)ST_D : 5);
-  with_format(h, [&](auto p) { launch_sweep_p<decltype(p)>(h, io, stage, x, v, a, act); });
+  prof_begin(h, (d.stage == ST_C && h->scheme != PIC_YOSHIDA4) ? 7 : profile_kind(stage_traits(d.stage)));
+  with_format(h, [&](auto p) { launch_sweep_p<decltype(p)>(h, io, d.stage, x, v, a, act); });
   prof_end(h);
 }
 
