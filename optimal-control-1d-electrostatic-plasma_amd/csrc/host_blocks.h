@@ -6,6 +6,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "pic_limits.h"
+
 namespace {      // internal linkage throughout: the library exports its C ABI alone
 
 // A device block cut into parts, every part rounded up to 256 bytes.  A block is described once, by a layout function below that
@@ -282,6 +284,34 @@ inline PoolPlan pool_plan(size_t num_envs, size_t N) {
   PoolPlan p;
   p.chunks_per_wg = (nchunks + wpe - 1) / wpe;
   p.workgroups = (nchunks + p.chunks_per_wg - 1) / p.chunks_per_wg;
+  return p;
+}
+
+// The recorder's particle pass (pic_record.h: record_hist_kernel), planned at pic_record_start; tests/record_plan_driver.cpp and
+// tests/test_record_edges_cpu.py pin it.  Geometry: about 1024 workgroups in all, gx per environment, each over a contiguous
+// range of tiles_per_wg tile columns (a column: one 16-byte tile of `vec` particles per lane).  LDS: rr copies of each marginal
+// bin within 32 KiB, then the word of `inside`, then the phase histogram in rows of pv + 1 words where all of it fits
+// kRecordLdsBytes (phase_lds); global atomics otherwise.  Counts are integers: no result depends on any of it.
+constexpr int kRecordLdsBytes = 64 << 10;       // LDS of the particle pass: sub-histograms up to this size live in LDS
+struct RecordPlan {
+  int gx = 1;
+  long long tiles_per_wg = 1;
+  int rr = 1, phase_lds = 0;
+  size_t lds = 0;
+};
+
+inline RecordPlan record_plan(long long N, long long vec, int E, int xb, int vb, int px, int pv) {
+  RecordPlan p;
+  const long long cols = ((N + vec - 1) / vec + BLOCK - 1) / BLOCK;     // tiles per lane if one workgroup took it all
+  const long long gx = std::max(1LL, std::min(cols, (1024LL + E - 1) / E));
+  p.tiles_per_wg = (cols + gx - 1) / gx;
+  p.gx = (int)((cols + p.tiles_per_wg - 1) / p.tiles_per_wg);
+  int rr = 16;
+  while (rr > 1 && (size_t)rr * (xb + vb) * sizeof(unsigned) > ((size_t)32 << 10)) rr /= 2;
+  p.rr = rr;
+  const size_t marg = ((size_t)rr * (xb + vb) + 1) * sizeof(unsigned), prow = (size_t)px * (pv + 1) * sizeof(unsigned);
+  p.phase_lds = marg + prow <= (size_t)kRecordLdsBytes ? 1 : 0;
+  p.lds = marg + (p.phase_lds ? prow : 0);
   return p;
 }
 

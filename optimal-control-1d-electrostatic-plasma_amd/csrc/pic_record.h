@@ -6,9 +6,7 @@
 
 namespace {
 
-constexpr int kRecordLdsBytes = 64 << 10;       // LDS of the particle pass: sub-histograms up to this size live in LDS
-
-// the particle pass: x_hist | v_hist | inside of record slot `rec` (zeroed at pic_record_start) and the phase counts
+// the particle pass (host_blocks.h: record_plan sizes its grid and lays out its LDS): x_hist | v_hist | inside of record slot `rec` (zeroed at pic_record_start) and the phase counts
 // ([env][px][pv] scratch, zeroed by the finishing kernel of the previous record)
 struct RecordHistArgs {
   unsigned* rec;          // [env][u_stride]: x_hist [xb], v_hist [vb], inside [1]

@@ -173,11 +173,7 @@ struct Recorder {
   DeviceBuf<unsigned> u;
   DeviceBuf<unsigned> phase;          // [env][px pv] counts of the record being made (zero between records)
   DeviceBuf<double> feq;              // [px pv] or null
-  int phase_lds = 0;
-  int rr = 1;                         // copies of each marginal bin in the particle pass's LDS
-  size_t lds = 0;
-  int gx = 1;                         // particle-pass workgroups per environment
-  long long tiles_per_wg = 1;
+  RecordPlan plan;                    // the particle pass's grid and LDS layout (host_blocks.h: record_plan)
 };
 
 // One carved device block of the tape and the bytes it counts in Tape::bytes; host_diff.h: tape_reserve is the one place that
@@ -1107,19 +1103,19 @@ static int record_enqueue(pic_handle* h) {
   ha.u_stride = r.u_stride;
   ha.phase = r.phase;
   ha.xb = r.xb; ha.vb = r.vb; ha.px = r.px; ha.pv = r.pv;
-  ha.phase_lds = r.phase_lds;
-  ha.rr = r.rr;
-  ha.N = h->cfg.N; ha.ld = h->ld; ha.tiles_per_wg = r.tiles_per_wg;
+  ha.phase_lds = r.plan.phase_lds;
+  ha.rr = r.plan.rr;
+  ha.N = h->cfg.N; ha.ld = h->ld; ha.tiles_per_wg = r.plan.tiles_per_wg;
   ha.L = h->cfg.L; ha.vmin = r.vmin; ha.vmax = r.vmax;
   // np.linspace steps: (stop - start) / div
   ha.sx = r.xb ? (h->cfg.L - 0.0) / r.xb : 0.0;
   ha.sv = r.vb ? (r.vmax - r.vmin) / r.vb : 0.0;
   ha.spx = r.px ? (h->cfg.L - 0.0) / r.px : 0.0;
   ha.spv = r.pv ? (r.vmax - r.vmin) / r.pv : 0.0;
-  const dim3 grid(r.gx, E);
+  const dim3 grid(r.plan.gx, E);
   with_format(h, [&](auto p) {
     using P = decltype(p);
-    hipLaunchKernelGGL(record_hist_kernel<P>, grid, dim3(BLOCK), r.lds, h->stream, (const typename P::X*)h->x.get(),
+    hipLaunchKernelGGL(record_hist_kernel<P>, grid, dim3(BLOCK), r.plan.lds, h->stream, (const typename P::X*)h->x.get(),
                        (const typename P::V*)h->v, ha);
   });
   RecordFinishArgs fa{};
@@ -2002,19 +1998,7 @@ int pic_record_start(pic_handle* h, const pic_record_config* c) {
     const int rc = ensure_twiddle(h, r.M - 1);
     if (rc) return rc;
   }
-  // particle pass geometry: about 1024 workgroups in all, each over a contiguous range of 16-byte tiles
-  const long long vec = h->vec;
-  const long long cols = ((h->cfg.N + vec - 1) / vec + BLOCK - 1) / BLOCK;     // tiles per lane if one workgroup took it all
-  long long gx = std::max(1LL, std::min(cols, (1024LL + E - 1) / E));
-  r.tiles_per_wg = (cols + gx - 1) / gx;
-  r.gx = (int)((cols + r.tiles_per_wg - 1) / r.tiles_per_wg);
-  // (pic_record.h: rr copies of each marginal bin within 32 KiB, phase rows of pv + 1 words)
-  int rr = 16;
-  while (rr > 1 && (size_t)rr * (r.xb + r.vb) * sizeof(unsigned) > ((size_t)32 << 10)) rr /= 2;
-  r.rr = rr;
-  const size_t marg = ((size_t)rr * (r.xb + r.vb) + 1) * sizeof(unsigned), prow = (size_t)r.px * (r.pv + 1) * sizeof(unsigned);
-  r.phase_lds = marg + prow <= (size_t)kRecordLdsBytes ? 1 : 0;
-  r.lds = marg + (r.phase_lds ? prow : 0);
+  r.plan = record_plan(h->cfg.N, h->vec, E, r.xb, r.vb, r.px, r.pv);
   r.on = true;
   h->rec = std::move(r);
   return PIC_OK;
